@@ -32,9 +32,6 @@ import os
 import sys
 import time
 
-# HIP maps streams onto 4 hardware queues by default; the tracer keeps (samples in flight) x 2 streams busy
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
-
 import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -473,6 +470,14 @@ def viewpoint_free_section(grt, device, steps, warmup):
     return burst_section(grt, device, steps, warmup, dict(static_slot_learning_viewpoint=0), "the same scene, camera, samples and frame loop (one declared burst); the flattened tree's children seated by sample rays from free-space points and surfaces only (static_slot_learning_viewpoint = 0: no ray from the benchmark's camera)")
 
 
+def dump_outputs(directory, pt):
+    """What the timed path hands its caller: the framebuffer as rt_read_framebuffer returns it, without the row padding
+    (1920 x 1080 x float4 = 33 MB). Its inputs are fixed: the scene, the camera and the sample indices of the steps (the
+    random numbers of a path are a function of its pixel, bounce and sample index)."""
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "framebuffer.npy"), np.ascontiguousarray(pt.read_framebuffer()[:, :WIDTH, :], dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -492,19 +497,22 @@ def main():
     ap.add_argument("--exchange", choices=["native", "torch"], default="native", help="N > 1: who runs the per-frame all-gather. native (default): the library's own frame exchange, ncclAllGather on the context's stream through rt_comm_init_rank / rt_all_gather_framebuffer (torch.distributed only carries the 128-byte communicator id and the timing reductions); torch: dist.all_gather_into_tensor on torch's stream around rt_pack_pixels / rt_unpack_pixels. Falls back to torch when the library cannot set up its communicator")
     ap.add_argument("--batch", type=int, default=SPP, help="samples per pixel per submission (rt_render_samples), 1..%d" % SPP)
     ap.add_argument("--samples-in-flight", type=int, default=0, help="samples per pixel rendered concurrently (rt_set_samples_in_flight)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what they computed -- the framebuffer a caller reads back (rt_read_framebuffer: "
+                                                                        "the accumulated radiance of the last step's frame, float32 HEIGHT x WIDTH x 4) -- to DIR/framebuffer.npy (rank 0)")
     args = ap.parse_args()
     global MERGE_STATIC, EXPAND_TEXTURES
     EXPAND_TEXTURES = args.expand_textures
     MERGE_STATIC = args.merge_static
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # `python bench.py --gpus N` without a launcher: become the launcher (one rank per GPU, rendezvous on 127.0.0.1)
+        # `python bench.py --gpus N` without a launcher: start one (one rank per GPU, rendezvous on 127.0.0.1) as a child process
         import socket
+        import subprocess
         with socket.socket() as sock:
             sock.bind(("127.0.0.1", 0)); port = sock.getsockname()[1]
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        raise SystemExit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
+                                          "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]))
 
     import torch
     import torch.distributed as dist
@@ -738,6 +746,8 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:   # before anything below renders into the framebuffer again
+        dump_outputs(args.dump_outputs, pt)
     if not events_in_timed_region and not os.environ.get("BENCH_NO_LAUNCH_TIMING"):
         grt.set_profiling(ctx, 2)
         run(plan)

@@ -14,6 +14,7 @@ import ctypes
 import fcntl
 import os
 import tarfile
+import tempfile
 from ctypes import POINTER, byref, c_char_p, c_double, c_float, c_int, c_int32, c_size_t, c_uint8, c_uint32, c_void_p
 
 import numpy as np
@@ -68,10 +69,6 @@ def device_lib():
     if _device is None:
         if not os.path.exists(DEVICE_LIB_PATH):
             raise DeviceLibraryMissing("%s is missing -- run `python __graft_entry__.py` (build()) first" % DEVICE_LIB_PATH)
-        # HIP reads this at the first HIP call of the process; the per-submission scheduler runs up to 18 streams.
-        # The library itself leaves the environment alone; a process that initialised HIP earlier (torch imported and used
-        # first) keeps HIP's default of 4 queues and the context says so when it matters.
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
         lib = ctypes.CDLL(DEVICE_LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         if hasattr(lib, "rt_abi_version") and lib.rt_abi_version() != 8:
             raise DeviceLibraryMissing("%s has ABI version %d, this front end was written for 8 -- rebuild (python __graft_entry__.py)" % (DEVICE_LIB_PATH, lib.rt_abi_version()))
@@ -232,11 +229,16 @@ def _view(ptr, nbytes, dtype):
 
 # ---- scenes ---------------------------------------------------------------------------------------
 
+SCENES = {"cornellbox": ("cornellbox.tar.xz", "cornellbox/scene.xml"), "sponza": ("sponza_geometry.tar.xz", "Sponza/scene.xml")}
+
+
 def scene_path(name):
     """Path of a bundled scene's xml; archives under assets/scenes are unpacked on first use.
 
     'cornellbox' and 'sponza' are the geometry of the reference's Data/cornellbox and
     Data/Sponza (Crytek Sponza), packed because /root/reference does not exist on the GPU box.
+    They are unpacked into assets/_cache (build() does it for Sponza). A tree built by one user and run by another
+    can leave that cache readable but not writable: what it holds is used as it is, what it lacks goes to user_cache_dir().
     """
     cache = os.path.join(ASSET_DIR, "_cache")
     if name == "sponza_reference_maps":   # Sponza with the reference's own texture files (install_reference_sponza_textures)
@@ -244,23 +246,47 @@ def scene_path(name):
             raise FileNotFoundError("the reference's Sponza textures are not installed (build() copies them where /root/reference is mounted)")
         scene_path("sponza")
         return os.path.join(cache, "Sponza", "scene_reference_maps.xml")
-    table = {"cornellbox": ("cornellbox.tar.xz", "cornellbox/scene.xml"), "sponza": ("sponza_geometry.tar.xz", "Sponza/scene.xml")}
-    if name not in table:
+    if name not in SCENES:
         raise KeyError("unknown bundled scene %r" % name)
-    archive, xml = table[name]
-    target = os.path.join(cache, xml)
-    os.makedirs(cache, exist_ok=True)
-    with open(os.path.join(cache, ".lock"), "w") as lock:   # the ranks of a multi-GPU job start together
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            if not os.path.exists(target):
-                with tarfile.open(os.path.join(ASSET_DIR, "scenes", archive)) as tar:
-                    tar.extractall(cache)
-            if name == "sponza":
-                _unpack_sponza_textures(cache)
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-    return target
+    if not _unpack_scene(cache, name):
+        cache = user_cache_dir()
+        if not _unpack_scene(cache, name):
+            raise PermissionError("cannot unpack the bundled scene %r: neither %s nor %s can be written" % (name, os.path.join(ASSET_DIR, "_cache"), cache))
+    return os.path.join(cache, SCENES[name][1])
+
+
+def user_cache_dir():
+    """Where this user unpacks the bundled scenes that assets/_cache lacks and cannot take."""
+    return os.path.join(tempfile.gettempdir(), "gpu_raytracer_amd-%d" % os.getuid(), "_cache")
+
+
+def _unpack_scene(cache, name):
+    """Unpacks bundled scene `name` under `cache` unless it is complete there already. False: it is not, and `cache`
+    cannot be written."""
+    archive, xml = SCENES[name]
+    done = os.path.join(cache, "." + archive + ".complete")   # written after the last file of the scene
+    if os.path.exists(done) and (name != "sponza" or _sponza_textures_unpacked(cache)):
+        return True
+    try:
+        os.makedirs(cache, exist_ok=True)
+    except PermissionError:
+        return False
+    lock = os.open(cache, os.O_RDONLY)   # the lock is the directory itself: taking it needs no write permission
+    try:
+        fcntl.flock(lock, fcntl.LOCK_EX)   # the ranks of a multi-GPU job start together
+        if not os.path.exists(os.path.join(cache, xml)):
+            with tarfile.open(os.path.join(ASSET_DIR, "scenes", archive)) as tar:
+                tar.extractall(cache)
+        if name == "sponza":
+            _unpack_sponza_textures(cache)
+        if not os.path.exists(done):
+            open(done, "w").close()
+    except PermissionError:
+        # a cache another user unpacked before the markers existed: complete if it has the scene, else not ours to fill
+        return os.path.exists(os.path.join(cache, xml)) and (name != "sponza" or _sponza_textures_unpacked(cache))
+    finally:
+        os.close(lock)   # (closing releases the lock)
+    return True
 
 
 REFERENCE_SPONZA_TEXTURES = "/root/reference/Data/Sponza/textures"
@@ -299,6 +325,10 @@ def install_reference_sponza_textures():
 
 def reference_sponza_textures_installed():
     return os.path.exists(os.path.join(ASSET_DIR, "_cache", "Sponza", "textures_reference", ".complete"))
+
+
+def _sponza_textures_unpacked(cache):
+    return os.path.exists(os.path.join(cache, "Sponza", "textures", ".complete")) or not os.path.exists(os.path.join(ASSET_DIR, "scenes", "sponza_textures_256.tar.xz"))
 
 
 def _unpack_sponza_textures(cache):

@@ -24,9 +24,9 @@ static thread_local std::string g_global_error;
 // the HIP runtime initialises, i.e. at the first HIP call of the PROCESS. The per-submission scheduler keeps up to 2 x
 // (submissions in flight) streams busy and loses their overlap silently when they share queues
 // (profiles/r01_small_range_concurrency.txt). A library has no business editing its host's environment (and cannot know
-// whether HIP is already up -- PyTorch imported first, say): the applications that ship with it set the variable before
-// their first HIP call (bench.py, the Python front end, the command-line renderer), INTEGRATION.md tells embedders to, and
-// a context says so once when it is asked for more concurrent streams than the process has queues for.
+// whether HIP is already up -- PyTorch imported first, say), and neither do the applications that ship with it: the queue
+// slots of a GPU are shared by every process on it. The merged wavefront (the default scheduler) needs two streams; a
+// context says so once when it is asked for more concurrent streams than the process has queues for.
 static void warn_if_streams_share_queues(int streams_needed) {
 	static bool warned = false;
 	if (warned) return;
@@ -35,7 +35,7 @@ static void warn_if_streams_share_queues(int streams_needed) {
 	if (queues >= streams_needed) return;
 	warned = true;
 	fprintf(stderr, "[grt] %d streams in flight but GPU_MAX_HW_QUEUES=%s: HIP will multiplex them onto %d hardware queues and serialise their kernels; "
-	                "export GPU_MAX_HW_QUEUES=24 before the process makes its first HIP call\n", streams_needed, value ? value : "(unset, 4)", queues);
+	                "the merged scheduler (the default) needs two streams\n", streams_needed, value ? value : "(unset, 4)", queues);
 }
 
 // Everything one sample per pixel owns while it is in flight. Up to RT_MAX_SAMPLE_SLOTS samples

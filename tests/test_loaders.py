@@ -860,6 +860,7 @@ def test_texture_decoders_equal_the_references_stb_image(grt, oracle, tmp_path):
 
 
 JPEG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "jpeg")
+JPEG_PHOTO_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "jpeg_photos")
 
 
 def _decode_without_gamma(grt, path):
@@ -889,12 +890,9 @@ def test_jpeg_decoder_live_against_stb_image(grt, oracle):
     if oracle.ref_lib() is None or not hasattr(oracle.ref_lib(), "ref_stbi_load_rgba"):
         pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
     files = sorted(glob.glob(os.path.join(JPEG_DIR, "*.jpg")))
-    # photographs that happen to be on the build machine, among them the reference's own JPEG textures
-    for extra in ("/root/reference/Data/instancing/textures/concrete.jpg", "/root/reference/Data/instancing/textures/wall.jpg",
-                  "/usr/local/lib/python3.10/dist-packages/sklearn/datasets/images/flower.jpg",
-                  "/usr/local/lib/python3.10/dist-packages/matplotlib/mpl-data/sample_data/grace_hopper.jpg"):
-        if os.path.exists(extra):
-            files.append(extra)
+    # and two photographs (baseline 4:2:0 and 4:4:4; the sample images of matplotlib and scikit-learn)
+    files += sorted(glob.glob(os.path.join(JPEG_PHOTO_DIR, "*.jpg")))
+    assert len(files) >= 22
     grt.config_reset(); grt.config_set(enable_mipmapping=0)
     for f in files:
         ref = oracle.ref_stbi_load(f)

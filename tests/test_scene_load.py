@@ -121,6 +121,12 @@ def posix_copy_of(grt, name, tmp_path):
     src = os.path.dirname(grt.scene_path(name))
     dst = tmp_path / name
     shutil.copytree(src, dst)
+    # the archives' members are read-only and copytree keeps their modes: the copy must be writable for the edit below
+    # and for the reference's caches (root would not notice)
+    for directory, _, files in os.walk(dst):
+        os.chmod(directory, 0o755)
+        for f in files:
+            os.chmod(os.path.join(directory, f), 0o644)
     xml = (dst / "scene.xml").read_text().replace("\\\\", "/").replace("\\", "/")
     (dst / "scene.xml").write_text(xml)
     return dst / "scene.xml"
@@ -138,6 +144,41 @@ def test_sponza_loads_like_the_reference(grt, oracle, tmp_path, block_compressio
                                key="sponza_bc%d" % block_compression, enable_block_compression=block_compression)
     if result:
         assert result[1].count("\nmesh ") >= 383 and result[1].count("\ntexture ") == 24
+
+
+def test_bundled_scenes_load_from_a_tree_another_user_unpacked(grt, tmp_path, monkeypatch):
+    """build() unpacks Sponza into assets/_cache, and the tree may then be run by a user who can read that cache but not
+    write it: scene_path hands out what the cache holds as it is and unpacks what it lacks into user_cache_dir()."""
+    import tempfile
+    assets = tmp_path / "assets"
+    (assets / "scenes").mkdir(parents=True)
+    for archive in ("cornellbox.tar.xz", "sponza_geometry.tar.xz", "sponza_textures_256.tar.xz"):
+        shutil.copy(os.path.join(grt.ASSET_DIR, "scenes", archive), str(assets / "scenes"))
+    (tmp_path / "tmp").mkdir()
+    monkeypatch.setattr(grt, "ASSET_DIR", str(assets))
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path / "tmp"))
+    sponza = grt.scene_path("sponza")
+    assert sponza == str(assets / "_cache" / "Sponza" / "scene.xml")
+    files_before = sorted(os.path.relpath(os.path.join(d, f), str(assets)) for d, _, fs in os.walk(str(assets)) for f in fs)
+    for directory, _, files in os.walk(str(assets)):   # the tree changes hands
+        os.chmod(directory, 0o555)
+        for f in files:
+            os.chmod(os.path.join(directory, f), 0o444)
+    try:
+        assert grt.scene_path("sponza") == sponza
+        cornell = grt.scene_path("cornellbox")
+        if os.access(str(assets / "_cache"), os.W_OK):   # (root: permissions are not enforced)
+            assert cornell == str(assets / "_cache" / "cornellbox" / "scene.xml")
+        else:
+            assert cornell == os.path.join(grt.user_cache_dir(), "cornellbox", "scene.xml")
+            assert files_before == sorted(os.path.relpath(os.path.join(d, f), str(assets)) for d, _, fs in os.walk(str(assets)) for f in fs)
+        grt.config_reset()
+        scene = grt.Scene(cornell)
+        assert scene.mesh_count > 0
+        scene.close()
+    finally:
+        for directory, _, files in os.walk(str(tmp_path)):
+            os.chmod(directory, 0o755)
 
 
 def write_feature_scene(tmp_path):
