@@ -43,7 +43,6 @@
 #endif
 // (Per-XCD chunks of the ray range -- L2 affinity via HW_REG_XCC_ID -- were tried and measured slower
 // than one shared cursor: 1.84 vs 2.01 Grays/s at 8M incoherent rays; see profiles/r01_trace_variants.txt.)
-#define RT_NUM_XCD 1
 #ifndef RT_TRI_BATCH
 #define RT_TRI_BATCH 2           // triangles whose loads are issued together
 #endif
@@ -539,7 +538,7 @@ template<int MODE, typename Source> RT_DEV void source_finish(const Source & src
 // SKIP: "skip behind the hit" (above; rt_set_skip_behind_hit) -- only for scenes that are ONE tree (p.entry_tlas_stack_size == 0): a stack entry
 // is then always a group of inner children of that tree.
 template<int MODE, bool COUNT, bool NARROW, bool UNIFIED = false, bool FLAT = false, bool SKIP = false, typename Source>
-RT_DEV void bvh8_trace_engine(const RtParams & p, Source & src, int ray_count, int * xcd_counters, unsigned long long * stats = nullptr, int ray_count_2 = 0, int * cursor_2 = nullptr, int * regions = nullptr) {
+RT_DEV void bvh8_trace_engine(const RtParams & p, Source & src, int ray_count, int * cursor, unsigned long long * stats = nullptr, int ray_count_2 = 0, int * cursor_2 = nullptr, int * regions = nullptr) {
 	constexpr bool SHADOW = MODE == RT_TRACE_SHADOW;   // the kind of every ray, unless MODE == RT_TRACE_MIXED: then lane_shadow
 	bool lane_shadow = SHADOW;
 	#define RT_IS_SHADOW (MODE == RT_TRACE_MIXED ? lane_shadow : SHADOW)
@@ -598,7 +597,7 @@ RT_DEV void bvh8_trace_engine(const RtParams & p, Source & src, int ray_count, i
 				int region = fetch_state[3];   // 0: this wave still takes blocks from the shared cursor; r + 1: it works on region r
 				if (region == 0) {
 					int base = main_limit;
-					if (main_limit > 0) { if (elected) base = atomicAdd(xcd_counters, ray_block); base = __builtin_amdgcn_readfirstlane(base); }
+					if (main_limit > 0) { if (elected) base = atomicAdd(cursor, ray_block); base = __builtin_amdgcn_readfirstlane(base); }
 					if (base < main_limit) { next = base; end = min(base + ray_block, main_limit); }
 					else region = int(wave_in_grid) + 1;
 				}
@@ -647,7 +646,7 @@ RT_DEV void bvh8_trace_engine(const RtParams & p, Source & src, int ray_count, i
 			if (fetch_state[2]) return -1;
 			const bool second_queue = MODE == RT_TRACE_MIXED && fetch_state[3] != 0;
 			const int queue_count = second_queue ? ray_count_2 : ray_count;
-			int * const queue_cursor = second_queue ? cursor_2 : xcd_counters;
+			int * const queue_cursor = second_queue ? cursor_2 : cursor;
 			unsigned long long want = __ballot(1);
 			unsigned long long askers = NARROW ? (want & 0x0101010101010101ull) : want; // one per ray wanted
 			int n_want = __popcll(askers);
@@ -946,7 +945,7 @@ RT_DEV void bvh8_trace_engine(const RtParams & p, Source & src, int ray_count, i
 // `coherent`: primary rays keep one ray per lane at any count (neighbouring lanes walk the same nodes).
 // (closest-hit rays of a one-tree scene take the skipping walk when the context asks for it -- rt_skip_walk, rt_types.h; uniform over the launch)
 template<bool SHADOW, bool COUNT, typename Source>
-RT_DEV void bvh8_trace_persistent(const RtParams & p, Source & src, int ray_count, int * cursor, unsigned long long * stats = nullptr, bool coherent = false) {
+RT_DEV void bvh8_trace_persistent(const RtParams & p, const Source & src, int ray_count, int * cursor, unsigned long long * stats = nullptr, bool coherent = false) {
 	const bool narrow = !COUNT && !coherent && ray_count <= RT_NARROW_MAX_RAYS;
 	if (!SHADOW && rt_skip_walk(p)) {
 		if (narrow) bvh8_trace_engine<RT_TRACE_CLOSEST, false, true, false, false, true>(p, src, ray_count, cursor);
@@ -956,7 +955,6 @@ RT_DEV void bvh8_trace_persistent(const RtParams & p, Source & src, int ray_coun
 	if (narrow) bvh8_trace_engine<SHADOW ? RT_TRACE_SHADOW : RT_TRACE_CLOSEST, false, true>(p, src, ray_count, cursor);
 	else bvh8_trace_engine<SHADOW ? RT_TRACE_SHADOW : RT_TRACE_CLOSEST, COUNT, false>(p, src, ray_count, cursor, stats);
 }
-#define RT_TRACE_ENGINE bvh8_trace_persistent
 
 RT_DEV uint4 pack_hit(const HitRecord & h) { // Buffers.h:25-32
 	unsigned uv = unsigned(int(h.u * 65535.0f)) | (unsigned(int(h.v * 65535.0f)) << 16);
@@ -1038,15 +1036,93 @@ struct ShadowExplicitSource {
 
 
 // =================================================================================================
-// Binary BVH (BVH2.h:46-244): the reference's `bvh_type = BVH` configuration (BASELINE config #1).
-// Same persistent-wave machinery (block-claimed rays, LDS stack with HBM spill, one node step or one
-// triangle batch per round); a node is 32 B (AABB + left_or_first + count/axis), children are visited
-// near-first by the sign of the ray direction on the split axis. Not the fast path -- it exists so that
-// every BVH type the host can build can also be traced on the device, bit-exactly like the oracle.
+// Binary and 4-wide BVH (BVH2.h:46-244, BVH4.h:4-295): the reference's `bvh_type = BVH` (BASELINE config #1)
+// and `bvh_type = BVH4` configurations. Not the fast path -- they exist so that every BVH type the host can
+// build can also be traced on the device, bit-exactly like the oracle. One persistent walker serves both
+// widths with the machinery of the CWBVH engine (block-claimed rays, LDS stack with HBM spill, one node step
+// or one triangle batch per round, TLAS -> BLAS instancing); the width is a node step (Bvh2Step, Bvh4Step)
+// that either pushes the children of the popped stack entry or returns the leaf (first, count) it reached.
+// A step is constructed once per walker, so that its node array is loaded once and not in every round; the ray
+// is passed by value: through a reference, Bvh2Step's split-axis select indexed it in scratch memory.
 // =================================================================================================
-template<bool SHADOW, typename Source>
-RT_DEV void bvh2_trace_persistent(const RtParams & p, Source & src, int ray_count, int * cursor) {
-	const float4 * __restrict__ nodes     = p.bvh2_nodes;
+
+// AABB::intersects (BVH2.h:8-16) with t = (plane - origin) * inv_dir; t_near is the entry distance.
+RT_DEV bool aabb_intersect(f3 lo, f3 hi, const Ray3 & ray, f3 inv_dir, float limit, float & t_near) {
+	float t0x = (lo.x - ray.origin.x) * inv_dir.x, t1x = (hi.x - ray.origin.x) * inv_dir.x;
+	float t0y = (lo.y - ray.origin.y) * inv_dir.y, t1y = (hi.y - ray.origin.y) * inv_dir.y;
+	float t0z = (lo.z - ray.origin.z) * inv_dir.z, t1z = (hi.z - ray.origin.z) * inv_dir.z;
+	t_near      = fmaxf(fminf(t0x, t1x), fmaxf(fminf(t0y, t1y), fmaxf(fminf(t0z, t1z), 0.0f)));
+	float t_far = fminf(fmaxf(t0x, t1x), fminf(fmaxf(t0y, t1y), fminf(fmaxf(t0z, t1z), limit)));
+	return t_near < t_far;
+}
+
+struct LeafRange { int first, count; };   // count 0: no leaf reached
+
+// Binary BVH: a stack entry is a node index, a node 32 B (AABB + left_or_first + count/axis); children are
+// visited near-first by the sign of the ray direction on the split axis.
+struct Bvh2Step {
+	const float4 * __restrict__ nodes;
+	RT_DEV explicit Bvh2Step(const RtParams & p) : nodes(p.bvh2_nodes) {}
+	RT_DEV LeafRange step(const RtParams & p, TraversalStack & stack, uint2 entry, Ray3 ray, f3 inv_dir, float limit) const {
+		const float4 * node = (entry.x < unsigned(p.tlas_node_count) ? p.tlas_nodes : nodes) + size_t(entry.x) * 2;
+		float4 a = node[0], b = node[1];
+		int      left_or_first = __float_as_int(b.z);
+		unsigned count_axis    = __float_as_uint(b.w);
+		unsigned count = count_axis & 0x3fffffffu, axis = count_axis >> 30;
+		float t_near;
+		if (!aabb_intersect(mk3(a.x, a.y, a.z), mk3(a.w, b.x, b.y), ray, inv_dir, limit, t_near)) return { 0, 0 };
+		if (count > 0) return { left_or_first, int(count) };
+		float d = axis == 0 ? ray.direction.x : (axis == 1 ? ray.direction.y : ray.direction.z);
+		bool left_first = d > 0.0f;
+		stack.push(make_uint2(unsigned(left_first ? left_or_first + 1 : left_or_first), 0));
+		stack.push(make_uint2(unsigned(left_first ? left_or_first : left_or_first + 1), 0));
+		return { 0, 0 };
+	}
+};
+
+// 4-wide BVH: 128-B nodes, the boxes of up to four children in SoA form plus (index, count) per child. The
+// reference's stack holds (node, child id) and re-reads the child's (index, count) when it pops; here the stack
+// entry IS (index, count) -- the same values, one dependent load less per step. Children are pushed far-to-near
+// (near distances tagged with the child id in two mantissa bits and sorted, as in bvh4_node_intersect), so the
+// nearest is popped first.
+RT_DEV float float4_at(float4 v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); }
+struct Bvh4Step {
+	const float4 * __restrict__ nodes;
+	RT_DEV explicit Bvh4Step(const RtParams & p) : nodes(p.bvh4_nodes) {}
+	RT_DEV LeafRange step(const RtParams & p, TraversalStack & stack, uint2 entry, Ray3 ray, f3 inv_dir, float limit) const {
+		int index = int(entry.x), count = int(entry.y);
+		if (count > 0) return { index, count };
+		const float4 * node = (index < p.tlas_node_count ? p.tlas_nodes : nodes) + size_t(index) * 8;
+		float4 min_x = node[0], min_y = node[1], min_z = node[2], max_x = node[3], max_y = node[4], max_z = node[5], ic01 = node[6], ic23 = node[7];
+		float t_near[4]; unsigned hit_mask = 0;
+		#pragma unroll
+		for (int i = 0; i < 4; i++) {
+			float tn;
+			if (aabb_intersect(mk3(float4_at(min_x, i), float4_at(min_y, i), float4_at(min_z, i)),
+			                   mk3(float4_at(max_x, i), float4_at(max_y, i), float4_at(max_z, i)), ray, inv_dir, limit, tn)) hit_mask |= 1u << i;
+			t_near[i] = __uint_as_float((__float_as_uint(tn) & 0xfffffffcu) | unsigned(i));
+		}
+		#pragma unroll
+		for (int i = 1; i < 4; i++) {
+			#pragma unroll
+			for (int j = i - 1; j >= 0; j--) if (t_near[j] < t_near[j + 1]) { float t = t_near[j]; t_near[j] = t_near[j + 1]; t_near[j + 1] = t; }
+		}
+		#pragma unroll
+		for (int i = 0; i < 4; i++) {
+			unsigned id = __float_as_uint(t_near[i]) & 3u;
+			if ((hit_mask >> id) & 1u) {
+				float cx = id == 0 ? ic01.x : (id == 1 ? ic01.z : (id == 2 ? ic23.x : ic23.z));
+				float cy = id == 0 ? ic01.y : (id == 1 ? ic01.w : (id == 2 ? ic23.y : ic23.w));
+				stack.push(make_uint2(__float_as_uint(cx), __float_as_uint(cy)));
+			}
+		}
+		return { 0, 0 };
+	}
+};
+
+template<typename NodeStep, bool SHADOW, typename Source>
+RT_DEV void bvh_trace_persistent(const RtParams & p, const Source & src, int ray_count, int * cursor) {
+	const NodeStep node_step(p);
 	const float4 * __restrict__ triangles = p.triangle_positions;
 
 	unsigned lane = threadIdx.x & (RT_WAVE_SIZE - 1);
@@ -1064,7 +1140,7 @@ RT_DEV void bvh2_trace_persistent(const RtParams & p, Source & src, int ray_coun
 	typedef volatile __attribute__((address_space(3))) int LdsFetchWord;
 	LdsFetchWord * fetch_state = (LdsFetchWord *)&shared_fetch[wave][0];
 	if (lane == 0) { fetch_state[0] = 0; fetch_state[1] = 0; fetch_state[2] = 0; }
-	auto fetch_ray = [&]() -> int { // see bvh8_trace_persistent
+	auto fetch_ray = [&]() -> int { // the block claim of bvh8_trace_engine's fetch_ray, one queue and one ray per lane
 		while (true) {
 			if (fetch_state[2]) return -1;
 			unsigned long long want = __ballot(1);
@@ -1107,7 +1183,7 @@ RT_DEV void bvh2_trace_persistent(const RtParams & p, Source & src, int ray_coun
 			inv_dir = reciprocal(ray.direction);
 			hit.t = RT_INFINITY; hit.u = 0.0f; hit.v = 0.0f; hit.mesh_id = 0; hit.triangle_id = RT_INVALID;
 			tlas_stack_size = RT_INVALID;
-			stack.push(make_uint2(0, 0)); // root of the TLAS
+			stack.push(make_uint2(0, 0)); // the TLAS root (BVH4: child 0 of the entry node, node 1 -- an inner node)
 		}
 
 		int iterations_lost = 0;
@@ -1131,164 +1207,12 @@ RT_DEV void bvh2_trace_persistent(const RtParams & p, Source & src, int ray_coun
 						inv_dir = reciprocal(ray.direction);
 					}
 				}
-				unsigned node_index = stack.pop().x;
-				const float4 * node = (node_index < unsigned(p.tlas_node_count) ? p.tlas_nodes : nodes) + size_t(node_index) * 2;
-				float4 a = node[0], b = node[1];
-				int      left_or_first = __float_as_int(b.z);
-				unsigned count_axis    = __float_as_uint(b.w);
-				unsigned count = count_axis & 0x3fffffffu, axis = count_axis >> 30;
-
-				// AABB::intersects (BVH2.h:8-16) with t = (plane - origin) * inv_dir
-				float t0x = (a.x - ray.origin.x) * inv_dir.x, t1x = (a.w - ray.origin.x) * inv_dir.x;
-				float t0y = (a.y - ray.origin.y) * inv_dir.y, t1y = (b.x - ray.origin.y) * inv_dir.y;
-				float t0z = (a.z - ray.origin.z) * inv_dir.z, t1z = (b.y - ray.origin.z) * inv_dir.z;
-				float t_near = fmaxf(fminf(t0x, t1x), fmaxf(fminf(t0y, t1y), fmaxf(fminf(t0z, t1z), 0.0f)));
-				float t_far  = fminf(fmaxf(t0x, t1x), fminf(fmaxf(t0y, t1y), fminf(fmaxf(t0z, t1z), SHADOW ? max_distance : hit.t)));
-
-				if (t_near < t_far) {
-					if (count > 0) {
-						if (tlas_stack_size == RT_INVALID) { // TLAS leaf: enter the instance
-							tlas_stack_size = stack.size;
-							mesh_id = left_or_first;
-							unsigned root = unsigned(p.mesh_bvh_root_indices[mesh_id]);
-							mesh_has_identity_transform = (root >> 31) != 0;
-							if (!mesh_has_identity_transform) {
-								const float4 * m = p.mesh_transforms_inv + size_t(mesh_id) * 3;
-								ray.origin    = transform_position (m, ray.origin);
-								ray.direction = transform_direction(m, ray.direction);
-								inv_dir = reciprocal(ray.direction);
-							}
-							stack.push(make_uint2(root & 0x7fffffffu, 0));
-						} else {
-							tri_next = left_or_first; tri_end = left_or_first + int(count);
-						}
-					} else {
-						float d = axis == 0 ? ray.direction.x : (axis == 1 ? ray.direction.y : ray.direction.z);
-						bool left_first = d > 0.0f;
-						unsigned first  = unsigned(left_first ? left_or_first     : left_or_first + 1);
-						unsigned second = unsigned(left_first ? left_or_first + 1 : left_or_first);
-						stack.push(make_uint2(second, 0));
-						stack.push(make_uint2(first, 0));
-					}
-				}
-			}
-
-			if (SHADOW && occluded) {
-				src.finish(ray_index, hit, true);
-				stack.size = 0; tri_next = tri_end = 0;
-				break;
-			}
-			if (stack.size == 0 && tri_next >= tri_end) {
-				src.finish(ray_index, hit, false);
-				break;
-			}
-			iterations_lost += RT_WAVE_SIZE - __popcll(__ballot(1)) - RT_N_D;
-		} while (iterations_lost < RT_N_W);
-	}
-}
-
-
-// =================================================================================================
-// 4-wide BVH (BVH4.h:4-295, `bvh_type = BVH4`). 128-B nodes: the boxes of up to four children in SoA
-// form plus (index, count) per child. The reference's stack holds (node, child id) and re-reads the
-// child's (index, count) when it pops; here the stack entry IS (index, count) -- the same values, one
-// dependent load less per step. Children are pushed far-to-near (near distances tagged with the child
-// id in two mantissa bits and sorted, as in bvh4_node_intersect), so the nearest is popped first.
-// =================================================================================================
-template<bool SHADOW, typename Source>
-RT_DEV void bvh4_trace_persistent(const RtParams & p, Source & src, int ray_count, int * cursor) {
-	const float4 * __restrict__ nodes     = p.bvh4_nodes;
-	const float4 * __restrict__ triangles = p.triangle_positions;
-
-	unsigned lane = threadIdx.x & (RT_WAVE_SIZE - 1);
-	unsigned wave = threadIdx.x / RT_WAVE_SIZE;
-
-	TraversalStack stack;
-	stack.lds   = (LdsUint2 *)&shared_stack[wave * (RT_LDS_STACK * RT_WAVE_SIZE) + lane];
-	stack.spill_stride = int(gridDim.x * blockDim.x);
-	stack.spill = (GlobalUint2 *)(p.stack_spill + (blockIdx.x * blockDim.x + threadIdx.x));
-	stack.size  = 0;
-
-	const int waves_in_grid = int(gridDim.x) * (RT_TRACE_BLOCK / RT_WAVE_SIZE);
-	const int ray_block = max(RT_WAVE_SIZE, min(RT_FETCH_BLOCK_MAX, (ray_count / (2 * waves_in_grid)) & ~(RT_WAVE_SIZE - 1)));
-	if ((blockIdx.x * (RT_TRACE_BLOCK / RT_WAVE_SIZE) + wave) * unsigned(ray_block) >= unsigned(ray_count)) return;
-	typedef volatile __attribute__((address_space(3))) int LdsFetchWord;
-	LdsFetchWord * fetch_state = (LdsFetchWord *)&shared_fetch[wave][0];
-	if (lane == 0) { fetch_state[0] = 0; fetch_state[1] = 0; fetch_state[2] = 0; }
-	auto fetch_ray = [&]() -> int { // see bvh8_trace_persistent
-		while (true) {
-			if (fetch_state[2]) return -1;
-			unsigned long long want = __ballot(1);
-			int n_want = __popcll(want);
-			unsigned rank = __builtin_amdgcn_mbcnt_hi(unsigned(want >> 32), __builtin_amdgcn_mbcnt_lo(unsigned(want), 0u));
-			int next = fetch_state[0], end = fetch_state[1];
-			if (next >= end) {
-				int base = 0;
-				if (rank == 0) base = atomicAdd(cursor, ray_block);
-				base = __builtin_amdgcn_readfirstlane(base);
-				next = min(base, ray_count);
-				end  = min(base + ray_block, ray_count);
-			}
-			int give = min(n_want, end - next);
-			if (rank == 0) {
-				fetch_state[0] = next + give;
-				fetch_state[1] = end;
-				if (next >= end) fetch_state[2] = 1;
-			}
-			if (int(rank) < give) return next + int(rank);
-		}
-	};
-
-	int  ray_index = 0;
-	Ray3 ray;
-	f3   inv_dir;
-	float max_distance = 0.0f;
-	HitRecord hit;
-	int  tlas_stack_size = RT_INVALID;
-	int  mesh_id = 0;
-	bool mesh_has_identity_transform = true;
-	int  tri_next = 0, tri_end = 0;
-
-	while (true) {
-		bool inactive = stack.size == 0 && tri_next >= tri_end;
-		if (inactive) {
-			ray_index = fetch_ray();
-			if (ray_index < 0) return;
-			src.load(ray_index, ray, max_distance);
-			inv_dir = reciprocal(ray.direction);
-			hit.t = RT_INFINITY; hit.u = 0.0f; hit.v = 0.0f; hit.mesh_id = 0; hit.triangle_id = RT_INVALID;
-			tlas_stack_size = RT_INVALID;
-			stack.push(make_uint2(0, 0)); // child 0 of the entry node (node 1): the TLAS root, an inner node
-		}
-
-		int iterations_lost = 0;
-		do {
-			bool occluded = false;
-			if (tri_next < tri_end) {
-				#pragma unroll
-				for (int k = 0; k < RT_TRI_BATCH; k++) {
-					if (tri_next < tri_end && !occluded) {
-						const float4 * tri = triangles + size_t(tri_next) * 3;
-						if (triangle_test_loaded<SHADOW>(tri[0], tri[1], make_float4(tri[2].x, 0.0f, 0.0f, 0.0f), mesh_id, tri_next, ray, max_distance, hit)) occluded = true;
-						tri_next++;
-					}
-				}
-			} else {
-				if (stack.size == tlas_stack_size) {
-					tlas_stack_size = RT_INVALID;
-					if (!mesh_has_identity_transform) {
-						float unused;
-						src.load(ray_index, ray, unused);
-						inv_dir = reciprocal(ray.direction);
-					}
-				}
 				uint2 entry = stack.pop();
-				int index = int(entry.x), count = int(entry.y);
-
-				if (count > 0) {
-					if (tlas_stack_size == RT_INVALID) { // TLAS leaf: enter the instance through its entry node
+				LeafRange leaf = node_step.step(p, stack, entry, ray, inv_dir, SHADOW ? max_distance : hit.t);
+				if (leaf.count > 0) {
+					if (tlas_stack_size == RT_INVALID) { // TLAS leaf: enter the instance
 						tlas_stack_size = stack.size;
-						mesh_id = index;
+						mesh_id = leaf.first;
 						unsigned root = unsigned(p.mesh_bvh_root_indices[mesh_id]);
 						mesh_has_identity_transform = (root >> 31) != 0;
 						if (!mesh_has_identity_transform) {
@@ -1297,38 +1221,9 @@ RT_DEV void bvh4_trace_persistent(const RtParams & p, Source & src, int ray_coun
 							ray.direction = transform_direction(m, ray.direction);
 							inv_dir = reciprocal(ray.direction);
 						}
-						stack.push(make_uint2(root & 0x7fffffffu, 0)); // = child 0 of node root + 1
+						stack.push(make_uint2(root & 0x7fffffffu, 0)); // (BVH4: child 0 of node root + 1)
 					} else {
-						tri_next = index; tri_end = index + count;
-					}
-				} else {
-					const float4 * node = (index < p.tlas_node_count ? p.tlas_nodes : nodes) + size_t(index) * 8;
-					float4 min_x = node[0], min_y = node[1], min_z = node[2], max_x = node[3], max_y = node[4], max_z = node[5], ic01 = node[6], ic23 = node[7];
-					float limit = SHADOW ? max_distance : hit.t;
-					float t_near[4]; unsigned hit_mask = 0;
-					#define RT_BVH4_CHILD(i, c) { \
-						float t0x = (min_x.c - ray.origin.x) * inv_dir.x, t1x = (max_x.c - ray.origin.x) * inv_dir.x; \
-						float t0y = (min_y.c - ray.origin.y) * inv_dir.y, t1y = (max_y.c - ray.origin.y) * inv_dir.y; \
-						float t0z = (min_z.c - ray.origin.z) * inv_dir.z, t1z = (max_z.c - ray.origin.z) * inv_dir.z; \
-						float tn = fmaxf(fminf(t0x, t1x), fmaxf(fminf(t0y, t1y), fmaxf(fminf(t0z, t1z), 0.0f))); \
-						float tf = fminf(fmaxf(t0x, t1x), fminf(fmaxf(t0y, t1y), fminf(fmaxf(t0z, t1z), limit))); \
-						if (tn < tf) hit_mask |= 1u << i; \
-						t_near[i] = __uint_as_float((__float_as_uint(tn) & 0xfffffffcu) | unsigned(i)); }
-					RT_BVH4_CHILD(0, x) RT_BVH4_CHILD(1, y) RT_BVH4_CHILD(2, z) RT_BVH4_CHILD(3, w)
-					#undef RT_BVH4_CHILD
-					#pragma unroll
-					for (int i = 1; i < 4; i++) {
-						#pragma unroll
-						for (int j = i - 1; j >= 0; j--) if (t_near[j] < t_near[j + 1]) { float t = t_near[j]; t_near[j] = t_near[j + 1]; t_near[j + 1] = t; }
-					}
-					#pragma unroll
-					for (int i = 0; i < 4; i++) {
-						unsigned id = __float_as_uint(t_near[i]) & 3u;
-						if ((hit_mask >> id) & 1u) {
-							float cx = id == 0 ? ic01.x : (id == 1 ? ic01.z : (id == 2 ? ic23.x : ic23.z));
-							float cy = id == 0 ? ic01.y : (id == 1 ? ic01.w : (id == 2 ? ic23.y : ic23.w));
-							stack.push(make_uint2(__float_as_uint(cx), __float_as_uint(cy)));
-						}
+						tri_next = leaf.first; tri_end = leaf.first + leaf.count;
 					}
 				}
 			}
@@ -1348,73 +1243,31 @@ RT_DEV void bvh4_trace_persistent(const RtParams & p, Source & src, int ray_coun
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------
+// The wavefront's queues of bounce `bounce` (its ray cursors: p.ray_cursors[2 * bounce] closest hit, [2 * bounce + 1] shadow),
+// and the AO integrator's occlusion rays (the shadow queue of bounce 0).
+RT_DEV ClosestHitSource  closest_queue(const RtParams & p, int bounce) { return { p.trace[bounce & 1].origin, p.trace[bounce & 1].direction, p.trace[bounce & 1].hits }; }
+RT_DEV ShadowQueueSource shadow_queue (const RtParams & p, int bounce) { return { p.shadow, p.aovs[RT_AOV_RADIANCE], p.aovs[RT_AOV_RADIANCE_DIRECT], p.aovs[RT_AOV_RADIANCE_INDIRECT], bounce }; }
+RT_DEV ShadowAOSource    ao_queue     (const RtParams & p)             { return { p.shadow, p.aovs[RT_AOV_RADIANCE] }; }
 
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh8(RtParams p, int bounce) {
-	ClosestHitSource src { p.trace[bounce & 1].origin, p.trace[bounce & 1].direction, p.trace[bounce & 1].hits };
-	RT_TRACE_ENGINE<false, false>(p, src, p.sizes->trace[bounce], p.xcd_counters + (2 * bounce) * RT_NUM_XCD, nullptr, bounce == 0);
-}
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh8(RtParams p, int bounce) { bvh8_trace_persistent<false, false>(p, closest_queue(p, bounce), p.sizes->trace[bounce], p.ray_cursors + 2 * bounce, nullptr, bounce == 0); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh8(RtParams p, int bounce) { bvh8_trace_persistent<true, false>(p, shadow_queue(p, bounce), p.sizes->shadow[bounce], p.ray_cursors + 2 * bounce + 1); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh8_ao(RtParams p) { bvh8_trace_persistent<true, false>(p, ao_queue(p), p.sizes->shadow[0], p.ray_cursors + 1); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh8_counting(RtParams p, int bounce, unsigned long long * stats) { bvh8_trace_persistent<false, true>(p, closest_queue(p, bounce), p.sizes->trace[bounce], p.ray_cursors + 2 * bounce, stats); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh8_counting(RtParams p, int bounce, unsigned long long * stats) { bvh8_trace_persistent<true, true>(p, shadow_queue(p, bounce), p.sizes->shadow[bounce], p.ray_cursors + 2 * bounce + 1, stats + 5); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh8_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, uint4 * hits, int ray_count, int * retired) { bvh8_trace_persistent<false, false>(p, ClosestHitSource { origin, direction, hits }, ray_count, retired); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh8_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, const float * max_distance, uint8_t * occluded, int ray_count, int * retired) { bvh8_trace_persistent<true, false>(p, ShadowExplicitSource { origin, direction, max_distance, occluded }, ray_count, retired); }
 
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh8(RtParams p, int bounce) {
-	ShadowQueueSource src { p.shadow, p.aovs[RT_AOV_RADIANCE], p.aovs[RT_AOV_RADIANCE_DIRECT], p.aovs[RT_AOV_RADIANCE_INDIRECT], bounce };
-	RT_TRACE_ENGINE<true, false>(p, src, p.sizes->shadow[bounce], p.xcd_counters + (2 * bounce + 1) * RT_NUM_XCD);
-}
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh2(RtParams p, int bounce) { bvh_trace_persistent<Bvh2Step, false>(p, closest_queue(p, bounce), p.sizes->trace[bounce], p.ray_cursors + 2 * bounce); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh2(RtParams p, int bounce) { bvh_trace_persistent<Bvh2Step, true>(p, shadow_queue(p, bounce), p.sizes->shadow[bounce], p.ray_cursors + 2 * bounce + 1); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh2_ao(RtParams p) { bvh_trace_persistent<Bvh2Step, true>(p, ao_queue(p), p.sizes->shadow[0], p.ray_cursors + 1); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh2_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, uint4 * hits, int ray_count, int * retired) { bvh_trace_persistent<Bvh2Step, false>(p, ClosestHitSource { origin, direction, hits }, ray_count, retired); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh2_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, const float * max_distance, uint8_t * occluded, int ray_count, int * retired) { bvh_trace_persistent<Bvh2Step, true>(p, ShadowExplicitSource { origin, direction, max_distance, occluded }, ray_count, retired); }
 
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh2(RtParams p, int bounce) {
-	ClosestHitSource src { p.trace[bounce & 1].origin, p.trace[bounce & 1].direction, p.trace[bounce & 1].hits };
-	bvh2_trace_persistent<false>(p, src, p.sizes->trace[bounce], p.xcd_counters + (2 * bounce) * RT_NUM_XCD);
-}
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh2(RtParams p, int bounce) {
-	ShadowQueueSource src { p.shadow, p.aovs[RT_AOV_RADIANCE], p.aovs[RT_AOV_RADIANCE_DIRECT], p.aovs[RT_AOV_RADIANCE_INDIRECT], bounce };
-	bvh2_trace_persistent<true>(p, src, p.sizes->shadow[bounce], p.xcd_counters + (2 * bounce + 1) * RT_NUM_XCD);
-}
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh2_ao(RtParams p) {
-	ShadowAOSource src { p.shadow, p.aovs[RT_AOV_RADIANCE] };
-	bvh2_trace_persistent<true>(p, src, p.sizes->shadow[0], p.xcd_counters + RT_NUM_XCD);
-}
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh2_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, uint4 * hits, int ray_count, int * retired) {
-	ClosestHitSource src { origin, direction, hits };
-	bvh2_trace_persistent<false>(p, src, ray_count, retired);
-}
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh2_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, const float * max_distance, uint8_t * occluded, int ray_count, int * retired) {
-	ShadowExplicitSource src { origin, direction, max_distance, occluded };
-	bvh2_trace_persistent<true>(p, src, ray_count, retired);
-}
-
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh4(RtParams p, int bounce) {
-	ClosestHitSource src { p.trace[bounce & 1].origin, p.trace[bounce & 1].direction, p.trace[bounce & 1].hits };
-	bvh4_trace_persistent<false>(p, src, p.sizes->trace[bounce], p.xcd_counters + (2 * bounce) * RT_NUM_XCD);
-}
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh4(RtParams p, int bounce) {
-	ShadowQueueSource src { p.shadow, p.aovs[RT_AOV_RADIANCE], p.aovs[RT_AOV_RADIANCE_DIRECT], p.aovs[RT_AOV_RADIANCE_INDIRECT], bounce };
-	bvh4_trace_persistent<true>(p, src, p.sizes->shadow[bounce], p.xcd_counters + (2 * bounce + 1) * RT_NUM_XCD);
-}
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh4_ao(RtParams p) {
-	ShadowAOSource src { p.shadow, p.aovs[RT_AOV_RADIANCE] };
-	bvh4_trace_persistent<true>(p, src, p.sizes->shadow[0], p.xcd_counters + RT_NUM_XCD);
-}
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh4_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, uint4 * hits, int ray_count, int * retired) {
-	ClosestHitSource src { origin, direction, hits };
-	bvh4_trace_persistent<false>(p, src, ray_count, retired);
-}
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh4_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, const float * max_distance, uint8_t * occluded, int ray_count, int * retired) {
-	ShadowExplicitSource src { origin, direction, max_distance, occluded };
-	bvh4_trace_persistent<true>(p, src, ray_count, retired);
-}
-
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh8_ao(RtParams p) {
-	ShadowAOSource src { p.shadow, p.aovs[RT_AOV_RADIANCE] };
-	RT_TRACE_ENGINE<true, false>(p, src, p.sizes->shadow[0], p.xcd_counters + RT_NUM_XCD);
-}
-
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh8_counting(RtParams p, int bounce, unsigned long long * stats) {
-	ClosestHitSource src { p.trace[bounce & 1].origin, p.trace[bounce & 1].direction, p.trace[bounce & 1].hits };
-	RT_TRACE_ENGINE<false, true>(p, src, p.sizes->trace[bounce], p.xcd_counters + (2 * bounce) * RT_NUM_XCD, stats);
-}
-
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh8_counting(RtParams p, int bounce, unsigned long long * stats) {
-	ShadowQueueSource src { p.shadow, p.aovs[RT_AOV_RADIANCE], p.aovs[RT_AOV_RADIANCE_DIRECT], p.aovs[RT_AOV_RADIANCE_INDIRECT], bounce };
-	RT_TRACE_ENGINE<true, true>(p, src, p.sizes->shadow[bounce], p.xcd_counters + (2 * bounce + 1) * RT_NUM_XCD, stats + 5);
-}
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh4(RtParams p, int bounce) { bvh_trace_persistent<Bvh4Step, false>(p, closest_queue(p, bounce), p.sizes->trace[bounce], p.ray_cursors + 2 * bounce); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh4(RtParams p, int bounce) { bvh_trace_persistent<Bvh4Step, true>(p, shadow_queue(p, bounce), p.sizes->shadow[bounce], p.ray_cursors + 2 * bounce + 1); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh4_ao(RtParams p) { bvh_trace_persistent<Bvh4Step, true>(p, ao_queue(p), p.sizes->shadow[0], p.ray_cursors + 1); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh4_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, uint4 * hits, int ray_count, int * retired) { bvh_trace_persistent<Bvh4Step, false>(p, ClosestHitSource { origin, direction, hits }, ray_count, retired); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh4_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, const float * max_distance, uint8_t * occluded, int ray_count, int * retired) { bvh_trace_persistent<Bvh4Step, true>(p, ShadowExplicitSource { origin, direction, max_distance, occluded }, ray_count, retired); }
 
 // The ONE traversal launch of an iteration of the merged wavefront: the closest-hit rays of the iteration (primary rays of
 // the newest submission and the continuation rays of all others) and then, by the same persistent waves as they run out of
@@ -1503,16 +1356,6 @@ __global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_
 	if (rt_skip_walk(p)) trace_stream<true, false, true>(p, stats); else trace_stream<true>(p, stats);
 }
 
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh8_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, uint4 * hits, int ray_count, int * retired) {
-	ClosestHitSource src { origin, direction, hits };
-	RT_TRACE_ENGINE<false, false>(p, src, ray_count, retired);
-}
-
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh8_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, const float * max_distance, uint8_t * occluded, int ray_count, int * retired) {
-	ShadowExplicitSource src { origin, direction, max_distance, occluded };
-	RT_TRACE_ENGINE<true, false>(p, src, ray_count, retired);
-}
-
 // Persistent grid: enough workgroups to fill every CU to the occupancy the kernel reaches,
 // a multiple of 8 so that all XCDs get the same share (block b runs on XCD b % 8).
 static int trace_grid_size(const void * kernel) {
@@ -1529,100 +1372,44 @@ static int trace_grid_size(const void * kernel) {
 	return cus * blocks_per_cu;
 }
 
+// One launch of persistent kernel K. Its grid size is a function-local static of this instantiation: computed once per
+// kernel, also when several submitting threads arrive together (FrameSplit).
+template<auto K, typename... A> static void launch_persistent(hipStream_t stream, const A &... args) {
+	static const int grid = trace_grid_size((const void *)K);
+	hipLaunchKernelGGL(K, dim3(grid), dim3(RT_TRACE_BLOCK), 0, stream, args...);
+}
+// The kernel of the context's BVH type: p.bvh_width 2 or 4, else the CWBVH.
+template<auto K2, auto K4, auto K8, typename... A> static void launch_for_width(const RtParams & p, hipStream_t stream, const A &... args) {
+	if (p.bvh_width == 2) launch_persistent<K2>(stream, p, args...);
+	else if (p.bvh_width == 4) launch_persistent<K4>(stream, p, args...);
+	else launch_persistent<K8>(stream, p, args...);
+}
+
 void rt_launch_trace(const RtParams & p, int bounce, hipStream_t stream) {
-	if (p.bvh_width == 2) {
-		static int grid2 = trace_grid_size((const void *)kernel_trace_bvh2);
-		hipLaunchKernelGGL(kernel_trace_bvh2, dim3(grid2), dim3(RT_TRACE_BLOCK), 0, stream, p, bounce);
-		return;
-	}
-	if (p.bvh_width == 4) {
-		static int grid4 = trace_grid_size((const void *)kernel_trace_bvh4);
-		hipLaunchKernelGGL(kernel_trace_bvh4, dim3(grid4), dim3(RT_TRACE_BLOCK), 0, stream, p, bounce);
-		return;
-	}
-	static int grid = trace_grid_size((const void *)kernel_trace_bvh8);
-	hipLaunchKernelGGL(kernel_trace_bvh8, dim3(grid), dim3(RT_TRACE_BLOCK), 0, stream, p, bounce);
+	launch_for_width<kernel_trace_bvh2, kernel_trace_bvh4, kernel_trace_bvh8>(p, stream, bounce);
 }
 void rt_launch_trace_shadow(const RtParams & p, int bounce, hipStream_t stream) {
-	if (p.bvh_width == 2) {
-		static int grid2 = trace_grid_size((const void *)kernel_trace_shadow_bvh2);
-		hipLaunchKernelGGL(kernel_trace_shadow_bvh2, dim3(grid2), dim3(RT_TRACE_BLOCK), 0, stream, p, bounce);
-		return;
-	}
-	if (p.bvh_width == 4) {
-		static int grid4 = trace_grid_size((const void *)kernel_trace_shadow_bvh4);
-		hipLaunchKernelGGL(kernel_trace_shadow_bvh4, dim3(grid4), dim3(RT_TRACE_BLOCK), 0, stream, p, bounce);
-		return;
-	}
-	static int grid = trace_grid_size((const void *)kernel_trace_shadow_bvh8);
-	hipLaunchKernelGGL(kernel_trace_shadow_bvh8, dim3(grid), dim3(RT_TRACE_BLOCK), 0, stream, p, bounce);
+	launch_for_width<kernel_trace_shadow_bvh2, kernel_trace_shadow_bvh4, kernel_trace_shadow_bvh8>(p, stream, bounce);
 }
 void rt_launch_trace_shadow_ao(const RtParams & p, hipStream_t stream) {
-	if (p.bvh_width == 2) {
-		static int grid2 = trace_grid_size((const void *)kernel_trace_shadow_bvh2_ao);
-		hipLaunchKernelGGL(kernel_trace_shadow_bvh2_ao, dim3(grid2), dim3(RT_TRACE_BLOCK), 0, stream, p);
-		return;
-	}
-	if (p.bvh_width == 4) {
-		static int grid4 = trace_grid_size((const void *)kernel_trace_shadow_bvh4_ao);
-		hipLaunchKernelGGL(kernel_trace_shadow_bvh4_ao, dim3(grid4), dim3(RT_TRACE_BLOCK), 0, stream, p);
-		return;
-	}
-	static int grid = trace_grid_size((const void *)kernel_trace_shadow_bvh8_ao);
-	hipLaunchKernelGGL(kernel_trace_shadow_bvh8_ao, dim3(grid), dim3(RT_TRACE_BLOCK), 0, stream, p);
+	launch_for_width<kernel_trace_shadow_bvh2_ao, kernel_trace_shadow_bvh4_ao, kernel_trace_shadow_bvh8_ao>(p, stream);
 }
 void rt_launch_trace_stream(const RtParams & p, unsigned long long * stats, hipStream_t stream) {
-	if (stats) {
-		static int grid_counting = trace_grid_size((const void *)kernel_trace_stream_bvh8_counting);
-		hipLaunchKernelGGL(kernel_trace_stream_bvh8_counting, dim3(grid_counting), dim3(RT_TRACE_BLOCK), 0, stream, p, stats);
-		return;
-	}
-	if (p.entry_tlas_stack_size == 0 && p.geometry_below_4gib) {   // the whole scene is one world-space tree: the engine without the TLAS / instance code (32-bit offsets; a larger scene walks the general engine from node 0)
-		if (rt_skip_walk(p)) {
-			static int grid_flat_skip = trace_grid_size((const void *)kernel_trace_stream_bvh8_flat_skip);
-			hipLaunchKernelGGL(kernel_trace_stream_bvh8_flat_skip, dim3(grid_flat_skip), dim3(RT_TRACE_BLOCK), 0, stream, p);
-			return;
-		}
-		static int grid_flat = trace_grid_size((const void *)kernel_trace_stream_bvh8_flat);
-		hipLaunchKernelGGL(kernel_trace_stream_bvh8_flat, dim3(grid_flat), dim3(RT_TRACE_BLOCK), 0, stream, p);
-		return;
-	}
-	static int grid = trace_grid_size((const void *)kernel_trace_stream_bvh8);
-	hipLaunchKernelGGL(kernel_trace_stream_bvh8, dim3(grid), dim3(RT_TRACE_BLOCK), 0, stream, p);
+	if (stats) launch_persistent<kernel_trace_stream_bvh8_counting>(stream, p, stats);
+	else if (p.entry_tlas_stack_size == 0 && p.geometry_below_4gib) {   // the whole scene is one world-space tree: the engine without the TLAS / instance code (32-bit offsets; a larger scene walks the general engine from node 0)
+		if (rt_skip_walk(p)) launch_persistent<kernel_trace_stream_bvh8_flat_skip>(stream, p);
+		else launch_persistent<kernel_trace_stream_bvh8_flat>(stream, p);
+	} else launch_persistent<kernel_trace_stream_bvh8>(stream, p);
 }
 void rt_launch_trace_counting(const RtParams & p, int bounce, unsigned long long * stats, hipStream_t stream) {
-	static int grid = trace_grid_size((const void *)kernel_trace_bvh8_counting);
-	hipLaunchKernelGGL(kernel_trace_bvh8_counting, dim3(grid), dim3(RT_TRACE_BLOCK), 0, stream, p, bounce, stats);
+	launch_persistent<kernel_trace_bvh8_counting>(stream, p, bounce, stats);
 }
 void rt_launch_trace_shadow_counting(const RtParams & p, int bounce, unsigned long long * stats, hipStream_t stream) {
-	static int grid = trace_grid_size((const void *)kernel_trace_shadow_bvh8_counting);
-	hipLaunchKernelGGL(kernel_trace_shadow_bvh8_counting, dim3(grid), dim3(RT_TRACE_BLOCK), 0, stream, p, bounce, stats);
+	launch_persistent<kernel_trace_shadow_bvh8_counting>(stream, p, bounce, stats);
 }
 void rt_launch_trace_explicit(const RtParams & p, RtVec3SoA origin, RtVec3SoA direction, uint4 * hits, int ray_count, int * retired_counter, hipStream_t stream) {
-	if (p.bvh_width == 2) {
-		static int grid2 = trace_grid_size((const void *)kernel_trace_bvh2_explicit);
-		hipLaunchKernelGGL(kernel_trace_bvh2_explicit, dim3(grid2), dim3(RT_TRACE_BLOCK), 0, stream, p, origin, direction, hits, ray_count, retired_counter);
-		return;
-	}
-	if (p.bvh_width == 4) {
-		static int grid4 = trace_grid_size((const void *)kernel_trace_bvh4_explicit);
-		hipLaunchKernelGGL(kernel_trace_bvh4_explicit, dim3(grid4), dim3(RT_TRACE_BLOCK), 0, stream, p, origin, direction, hits, ray_count, retired_counter);
-		return;
-	}
-	static int grid = trace_grid_size((const void *)kernel_trace_bvh8_explicit);
-	hipLaunchKernelGGL(kernel_trace_bvh8_explicit, dim3(grid), dim3(RT_TRACE_BLOCK), 0, stream, p, origin, direction, hits, ray_count, retired_counter);
+	launch_for_width<kernel_trace_bvh2_explicit, kernel_trace_bvh4_explicit, kernel_trace_bvh8_explicit>(p, stream, origin, direction, hits, ray_count, retired_counter);
 }
 void rt_launch_trace_shadow_explicit(const RtParams & p, RtVec3SoA origin, RtVec3SoA direction, const float * max_distance, uint8_t * occluded, int ray_count, int * retired_counter, hipStream_t stream) {
-	if (p.bvh_width == 2) {
-		static int grid2 = trace_grid_size((const void *)kernel_trace_shadow_bvh2_explicit);
-		hipLaunchKernelGGL(kernel_trace_shadow_bvh2_explicit, dim3(grid2), dim3(RT_TRACE_BLOCK), 0, stream, p, origin, direction, max_distance, occluded, ray_count, retired_counter);
-		return;
-	}
-	if (p.bvh_width == 4) {
-		static int grid4 = trace_grid_size((const void *)kernel_trace_shadow_bvh4_explicit);
-		hipLaunchKernelGGL(kernel_trace_shadow_bvh4_explicit, dim3(grid4), dim3(RT_TRACE_BLOCK), 0, stream, p, origin, direction, max_distance, occluded, ray_count, retired_counter);
-		return;
-	}
-	static int grid = trace_grid_size((const void *)kernel_trace_shadow_bvh8_explicit);
-	hipLaunchKernelGGL(kernel_trace_shadow_bvh8_explicit, dim3(grid), dim3(RT_TRACE_BLOCK), 0, stream, p, origin, direction, max_distance, occluded, ray_count, retired_counter);
+	launch_for_width<kernel_trace_shadow_bvh2_explicit, kernel_trace_shadow_bvh4_explicit, kernel_trace_shadow_bvh8_explicit>(p, stream, origin, direction, max_distance, occluded, ray_count, retired_counter);
 }

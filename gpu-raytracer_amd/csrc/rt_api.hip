@@ -45,6 +45,7 @@ static void warn_if_streams_share_queues(int streams_needed) {
 // and whose persistent trace launches each end in a tail; a second sample's kernels fill those holes.
 #define RT_MAX_SAMPLE_SLOTS 8
 #define RT_MAX_BATCH_SAMPLES 16
+#define RT_RAY_CURSOR_BYTES (RT_MAX_BOUNCES * 2 * sizeof(int))   // RtParams::ray_cursors of a slot: [RT_MAX_BOUNCES][2 (closest hit, shadow)] ints
 struct SampleSlot {
 	bool created = false;
 	hipStream_t stream = nullptr;      // the sample's launch chain
@@ -53,7 +54,7 @@ struct SampleSlot {
 	RtTraceBuffer trace[2]; RtMaterialBuffer material[4]; RtShadowBuffer shadow;
 	bool queues_allocated = false; size_t queue_capacity = 0;
 	RtBufferSizes * sizes = nullptr;
-	int * xcd_counters = nullptr;
+	int * ray_cursors = nullptr;
 	void * spill[2] = { nullptr, nullptr };  // traversal stack spill of the closest-hit / shadow launch
 	int * counter_totals = nullptr;          // 6 x RT_MAX_BOUNCES ints accumulated over batches
 	RtBufferSizes * pinned_counters = nullptr;
@@ -314,7 +315,7 @@ static int ensure_slot(rt_context * ctx, int index) {
 	RT_HIP(ctx, hipEventRecord(slot.ev_gbuffers, slot.stream));
 	int s = device_alloc(ctx, (void **)&slot.sizes, sizeof(RtBufferSizes)); if (s) return s;
 	s = device_alloc(ctx, (void **)&slot.counter_totals, 6 * RT_MAX_BOUNCES * sizeof(int)); if (s) return s;
-	s = device_alloc(ctx, (void **)&slot.xcd_counters, RT_MAX_BOUNCES * 2 * 8 * sizeof(int)); if (s) return s;
+	s = device_alloc(ctx, (void **)&slot.ray_cursors, RT_RAY_CURSOR_BYTES); if (s) return s;
 	// spill area for traversal stacks deeper than the LDS part: 24 entries x 8 B x (256 CUs x 8 workgroups x 256 lanes),
 	// one per launch that can be resident at the same time
 	for (int k = 0; k < 2; k++) { s = device_alloc(ctx, &slot.spill[k], size_t(24) * 8 * 256 * 8 * 256); if (s) return s; }
@@ -340,7 +341,7 @@ static int ensure_slot(rt_context * ctx, int index) {
 static RtParams slot_params(const rt_context * ctx, const SampleSlot & slot, int index) {
 	RtParams p = ctx->params;
 	memcpy(p.trace, slot.trace, sizeof(p.trace)); memcpy(p.material, slot.material, sizeof(p.material)); p.shadow = slot.shadow;
-	p.sizes = slot.sizes; p.xcd_counters = slot.xcd_counters; p.stack_spill = (uint2 *)slot.spill[0];
+	p.sizes = slot.sizes; p.ray_cursors = slot.ray_cursors; p.stack_spill = (uint2 *)slot.spill[0];
 	if (index > 0) for (int i = 0; i < RT_AOV_COUNT; i++) p.aovs[i].framebuffer = (float4 *)slot.aov_framebuffer[i];
 	if (index > 0 && slot.gbuffers[0]) {
 		p.gbuffer_normal_and_depth        = (float4 *)slot.gbuffers[0];
@@ -461,7 +462,7 @@ int rt_create(int device_ordinal, rt_context ** out_ctx) {
 	ctx->params.pixel_query_pixel = -1;
 	// the kernel-level entry points run on the main stream with slot 0's buffers (after quiesce())
 	ctx->params.sizes        = ctx->slots[0].sizes;
-	ctx->params.xcd_counters = ctx->slots[0].xcd_counters;
+	ctx->params.ray_cursors  = ctx->slots[0].ray_cursors;
 	ctx->params.stack_spill  = (uint2 *)ctx->slots[0].spill[0];
 
 	ctx->params.frame_pixels = 1u << 30; ctx->params.frame_pixels_magic = 5; ctx->params.batch_samples = 1; // until rt_resize
@@ -1875,7 +1876,7 @@ static RtParams stream_params(const rt_context * ctx, int iteration) {
 	const PathStream & s = ctx->path_stream;
 	RtParams p = ctx->params;
 	memcpy(p.trace, s.trace, sizeof(p.trace)); memcpy(p.material, s.material, sizeof(p.material)); p.shadow = s.shadow;
-	p.sizes = nullptr; p.xcd_counters = nullptr; p.stack_spill = (uint2 *)s.spill;
+	p.sizes = nullptr; p.ray_cursors = nullptr; p.stack_spill = (uint2 *)s.spill;
 	p.stream = s.control; p.stream_table = s.table_device; p.stream_iteration = iteration;
 	for (int i = 0; i < RT_AOV_COUNT; i++) p.aovs[i].framebuffer = (float4 *)s.aov_framebuffer[i];
 	if (s.gbuffers[0]) { // x + y * pitch of a VIRTUAL pixel is the virtual pixel: the shade kernels write the set of the path's slot
@@ -2270,7 +2271,7 @@ int rt_render_samples(rt_context * ctx, int sample_index, int sample_count) {
 
 			if (shadow_pending) { RT_HIP(ctx, hipStreamWaitEvent(st, slot.ev_shadowed, 0)); shadow_pending = false; } // the previous batch's queues are reused
 			RT_HIP(ctx, hipMemsetAsync(slot.sizes, 0, sizeof(RtBufferSizes), st));
-			RT_HIP(ctx, hipMemsetAsync(slot.xcd_counters, 0, RT_MAX_BOUNCES * 2 * 8 * sizeof(int), st));
+			RT_HIP(ctx, hipMemsetAsync(slot.ray_cursors, 0, RT_RAY_CURSOR_BYTES, st));
 			stage_mark(ctx, STAGE_GENERATE, st);
 			rt_launch_generate(p, sample_index, pixel_offset, pixel_count, st);
 
@@ -2372,7 +2373,7 @@ int rt_render_ao_sample(rt_context * ctx, int sample_index, float ao_radius) {
 		int pixel_offset = range_offset + (range_count - pixels_left);
 		int pixel_count  = batch_size < pixels_left ? batch_size : pixels_left;
 		RT_HIP(ctx, hipMemsetAsync(slot.sizes, 0, sizeof(RtBufferSizes), st));
-		RT_HIP(ctx, hipMemsetAsync(slot.xcd_counters, 0, RT_MAX_BOUNCES * 2 * 8 * sizeof(int), st));
+		RT_HIP(ctx, hipMemsetAsync(slot.ray_cursors, 0, RT_RAY_CURSOR_BYTES, st));
 		rt_launch_generate(p, sample_index, pixel_offset, pixel_count, st);
 		rt_launch_trace(p, 0, st);
 		rt_launch_ambient_occlusion(p, sample_index, ao_radius, st);

@@ -185,7 +185,7 @@ struct RtParams {
 	RtStreamControl     * stream;
 	const RtStreamTable * stream_table;
 	int stream_iteration;
-	int * xcd_counters;               // [RT_MAX_BOUNCES][2 (closest, shadow)][8 XCDs] ray-fetch cursors
+	int * ray_cursors;                // [RT_MAX_BOUNCES][2 (closest, shadow)] ray-fetch cursors
 	uint2 * stack_spill;                // traversal stack entries beyond the LDS part, [entry][grid lane]
 	// outputs
 	RtAOV    aovs[RT_AOV_COUNT];

@@ -135,8 +135,6 @@ inline unsigned bvh8_node_intersect(const Ray & ray, float3 inv_dir, unsigned oc
 
 	unsigned hit_mask = 0;
 	int32_t least = 0x7fffffff, second = 0x7fffffff;
-	static const int variant = getenv("ORACLE_SKIP_VARIANT") ? atoi(getenv("ORACLE_SKIP_VARIANT")) : 2;
-	int32_t half_min[2] = { 0x7fffffff, 0x7fffffff };
 	for (int i = 0; i < 2; i++) {
 		unsigned meta4 = w[6 + i];
 
@@ -172,7 +170,6 @@ inline unsigned bvh8_node_intersect(const Ray & ray, float3 inv_dir, unsigned oc
 					int32_t key = int32_t((float_as_uint(tmin) & 0xffffff00u) | bit_index);   // tmin >= 0: the bit patterns order like the values (a -0 sorts first: conservative)
 					second = key < least ? least : (key < second ? key : second);           // (the median of the three)
 					least  = key < least ? key : least;
-					if (variant == 4 ? bit_index >= 24 : true) half_min[i] = key < half_min[i] ? key : half_min[i];
 				}
 			}
 		}
@@ -181,7 +178,6 @@ inline unsigned bvh8_node_intersect(const Ray & ray, float3 inv_dir, unsigned oc
 		// the smallest key that is not the key of the child visited first (the highest bit of the mask)
 		int32_t key = (uint32_t(least) & 0x1fu) == (hit_mask ? msb(hit_mask) : 0xffu) ? second : least;
 		*bound_bits = (uint32_t(key) >> 8) & 0x00ffff00u;
-		if (variant >= 3) { int far = (oct_inv4 >> 2) & 1; *bound_bits = (uint32_t(half_min[far]) >> 8) & 0x00ffff00u; }
 	}
 	return hit_mask;
 }
@@ -303,15 +299,7 @@ inline bool bvh8_traverse(const oracle_scene & s, Ray ray, float max_distance, R
 			current_group = stack[--stack_size];
 			// Skip behind the hit: every child left in the group is entered at or beyond the group's bound; at or beyond the hit
 			// already held none of them can be entered (their test would be tmin < tmax <= hit.t), so the group is dropped unvisited.
-			static const int variant = getenv("ORACLE_SKIP_VARIANT") ? atoi(getenv("ORACLE_SKIP_VARIANT")) : 2;
-			while (skip && variant >= 3) {
-				if (int32_t((current_group.y << 8) & 0xffff0000u) >= int32_t(float_as_uint(ray_hit.t))) current_group.y &= ~0x0f000000u;
-				if (current_group.y & 0xff000000u) break;
-				c.groups_skipped++;
-				if (stack_size == 0) return false;
-				current_group = stack[--stack_size];
-			}
-			while (skip && variant < 3 && int32_t((current_group.y << 8) & 0xffff0000u) >= int32_t(float_as_uint(ray_hit.t))) {
+			while (skip && int32_t((current_group.y << 8) & 0xffff0000u) >= int32_t(float_as_uint(ray_hit.t))) {
 				c.groups_skipped++;
 				if (stack_size == 0) return false;
 				current_group = stack[--stack_size];

@@ -335,18 +335,21 @@ def test_sponza_texture_path_albedo_normal_position_aovs(grt, oracle):
     pt.close(); scene.close()
 
 
-@pytest.mark.parametrize("scene_name,w,h,radius", [("cornellbox", 160, 120, 0.5), ("sponza", 320, 180, 2.0)])
-def test_ambient_occlusion_integrator_matches_oracle(grt, oracle, scene_name, w, h, radius):
+@pytest.mark.parametrize("scene_name,w,h,radius,bvh_type", [("cornellbox", 160, 120, 0.5, 8), ("sponza", 320, 180, 2.0, 8),
+                                                             ("cornellbox", 160, 120, 0.5, 2), ("cornellbox", 160, 120, 0.5, 4)])
+def test_ambient_occlusion_integrator_matches_oracle(grt, oracle, scene_name, w, h, radius, bvh_type):
     """The reference's second integrator (AO.cpp / AO.cu) through the host class AO and
     rt_render_ao_sample: 3 progressive samples. Occlusion is binary per sample, so pixels are either
     equal to ~1e-7 or differ by a multiple of 1/n; the occlusion-ray count must agree within the queue
-    tolerance and all but 0.1 % of the pixels must agree."""
+    tolerance and all but 0.1 % of the pixels must agree. bvh_type 2 / 4 run kernel_trace_shadow_bvh2_ao /
+    kernel_trace_shadow_bvh4_ao."""
     grt.config_reset()
+    grt.config_set(bvh_type=bvh_type)
     scene = grt.Scene(grt.scene_path(scene_name))
     ao = grt.AO(scene, w, h, device=0, radius=radius)
     ao.aov_enable(grt.AOV_NORMAL); ao.aov_enable(grt.AOV_POSITION)
     ao.update()
-    view = oracle.SceneView(ao); frame = oracle.Frame(view)
+    view = oracle.SceneView(ao, bvh_type=bvh_type); frame = oracle.Frame(view)
     for f in range(3):
         if f:
             ao.update()
