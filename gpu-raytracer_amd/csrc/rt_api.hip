@@ -46,13 +46,43 @@ static void warn_if_streams_share_queues(int streams_needed) {
 #define RT_MAX_SAMPLE_SLOTS 8
 #define RT_MAX_BATCH_SAMPLES 16
 #define RT_RAY_CURSOR_BYTES (RT_MAX_BOUNCES * 2 * sizeof(int))   // RtParams::ray_cursors of a slot: [RT_MAX_BOUNCES][2 (closest hit, shadow)] ints
+
+// SVGF g-buffers, bytes per pixel: normal + depth (float4), mesh + triangle id (int2), previous screen position (float2)
+static const size_t gbuffer_pixel_bytes[3] = { 16, 8, 8 };
+
+// The queues of one wavefront, `capacity` entries each: two trace queues (this bounce's and the next), one per material,
+// one of shadow rays. Each scheduler owns one set (SampleSlot, PathStream); queues_allocate / queues_free handle a set.
+struct WavefrontQueues {
+	RtTraceBuffer trace[2] = { }; RtMaterialBuffer material[4] = { }; RtShadowBuffer shadow = { };
+	size_t capacity = 0;
+	bool allocated = false;
+};
+
+// Every device array of a queue set as (pointer, bytes per entry), in declaration order, which is the allocation order.
+template<typename Visit> static void for_each_queue_array(WavefrontQueues & q, Visit && visit) {
+	auto vec3 = [&](RtVec3SoA & v) { visit((void **)&v.x, 4); visit((void **)&v.y, 4); visit((void **)&v.z, 4); };
+	for (RtTraceBuffer & t : q.trace) {
+		vec3(t.origin); vec3(t.direction); visit((void **)&t.hits, 16); visit((void **)&t.cone_angle, 4); visit((void **)&t.cone_width, 4);
+		visit((void **)&t.medium, 4); visit((void **)&t.pixel_index_and_flags, 4); vec3(t.throughput); visit((void **)&t.last_pdf, 4);
+	}
+	for (RtMaterialBuffer & m : q.material) {
+		vec3(m.direction); visit((void **)&m.hits, 16); visit((void **)&m.cone_angle, 4); visit((void **)&m.cone_width, 4);
+		visit((void **)&m.medium, 4); visit((void **)&m.pixel_index_and_flags, 4); vec3(m.throughput);
+	}
+	vec3(q.shadow.origin); vec3(q.shadow.direction); visit((void **)&q.shadow.max_distance, 4); visit((void **)&q.shadow.illumination_and_pixel_index, 16);
+}
+
+// The kernels see a queue set through the parameter block.
+static void use_queues(RtParams & p, const WavefrontQueues & q) {
+	memcpy(p.trace, q.trace, sizeof(p.trace)); memcpy(p.material, q.material, sizeof(p.material)); p.shadow = q.shadow;
+}
+
 struct SampleSlot {
 	bool created = false;
 	hipStream_t stream = nullptr;      // the sample's launch chain
 	hipStream_t side   = nullptr;      // shadow rays of bounce b, concurrent with the closest-hit trace of bounce b+1
 	hipEvent_t ev_shaded = nullptr, ev_shadowed = nullptr, ev_done = nullptr, ev_frame_start = nullptr, ev_frame_end = nullptr;
-	RtTraceBuffer trace[2]; RtMaterialBuffer material[4]; RtShadowBuffer shadow;
-	bool queues_allocated = false; size_t queue_capacity = 0;
+	WavefrontQueues queues;
 	RtBufferSizes * sizes = nullptr;
 	int * ray_cursors = nullptr;
 	void * spill[2] = { nullptr, nullptr };  // traversal stack spill of the closest-hit / shadow launch
@@ -123,8 +153,7 @@ struct PathStream {
 	bool created = false;
 	hipStream_t stream = nullptr;
 	hipEvent_t ev_idle = nullptr;         // after the last completion enqueued so far: what main-stream consumers wait for
-	RtTraceBuffer trace[2]; RtMaterialBuffer material[4]; RtShadowBuffer shadow;
-	bool queues_allocated = false; size_t capacity = 0;
+	WavefrontQueues queues;
 	RtStreamControl * control = nullptr;
 	RtStreamTable * table_device = nullptr;
 	RtStreamTable table_host;             // what the device table will hold once the copies enqueued so far have run
@@ -171,7 +200,6 @@ struct rt_context {
 	bool frame_pipelining = false;     // rt_pack_pixels / rt_unpack_pixels follow the completed submissions only (rt_set_frame_pipelining)
 	long long stream_batch_paths = 0;  // paths the submissions of one iteration may bring (rt_set_stream_batch); 0: RT_STREAM_BATCH_PATHS
 	int samples_in_flight = 3;
-	bool overlap_shadows = true;
 	unsigned render_counter = 0;
 	int last_slot = -1;
 
@@ -256,6 +284,18 @@ static void device_free(rt_context * ctx, void * p) {
 	for (size_t i = 0; i < ctx->owned.size(); i++) if (ctx->owned[i] == p) { ctx->owned[i] = ctx->owned.back(); ctx->owned.pop_back(); break; }
 	(void)hipFree(p);
 }
+static int queues_allocate(rt_context * ctx, WavefrontQueues & q, size_t entries) {
+	int status = RT_OK;
+	for_each_queue_array(q, [&](void ** p, size_t bytes) { if (status == RT_OK) status = device_alloc(ctx, p, entries * bytes); });
+	if (status) return status;
+	q.capacity = entries;
+	q.allocated = true;
+	return RT_OK;
+}
+static void queues_free(rt_context * ctx, WavefrontQueues & q) {
+	for_each_queue_array(q, [&](void ** p, size_t) { device_free(ctx, *p); *p = nullptr; });
+	q.allocated = false;
+}
 // (re)allocate + synchronous upload
 static hipError_t quiesce(rt_context * ctx);
 static int upload(rt_context * ctx, void ** slot, const void * src, size_t bytes) {
@@ -302,7 +342,6 @@ static int ensure_slot(rt_context * ctx, int index) {
 	SampleSlot & slot = ctx->slots[index];
 	if (slot.created) return RT_OK;
 	if (index > 0) warn_if_streams_share_queues(2 * (index + 1) + 2);   // two streams per slot, the main stream, the merged wavefront's
-	memset(slot.trace, 0, sizeof(slot.trace)); memset(slot.material, 0, sizeof(slot.material)); memset(&slot.shadow, 0, sizeof(slot.shadow));
 	RT_HIP(ctx, hipStreamCreateWithFlags(&slot.stream, hipStreamNonBlocking));
 	RT_HIP(ctx, hipStreamCreateWithFlags(&slot.side,   hipStreamNonBlocking));
 	RT_HIP(ctx, hipEventCreateWithFlags(&slot.ev_shaded,   hipEventDisableTiming));
@@ -326,12 +365,9 @@ static int ensure_slot(rt_context * ctx, int index) {
 		s = device_alloc(ctx, &slot.aov_framebuffer[i], bytes); if (s) return s;
 		RT_HIP(ctx, hipMemset(slot.aov_framebuffer[i], 0, bytes));
 	}
-	if (index > 0 && ctx->svgf_allocated) {
-		const size_t elem[3] = { 16, 8, 8 };
-		for (int i = 0; i < 3; i++) {
-			s = device_alloc(ctx, &slot.gbuffers[i], ctx->frame_pixels * elem[i]); if (s) return s;
-			RT_HIP(ctx, hipMemset(slot.gbuffers[i], 0, ctx->frame_pixels * elem[i]));
-		}
+	if (index > 0 && ctx->svgf_allocated) for (int i = 0; i < 3; i++) {
+		s = device_alloc(ctx, &slot.gbuffers[i], ctx->frame_pixels * gbuffer_pixel_bytes[i]); if (s) return s;
+		RT_HIP(ctx, hipMemset(slot.gbuffers[i], 0, ctx->frame_pixels * gbuffer_pixel_bytes[i]));
 	}
 	slot.created = true;
 	return RT_OK;
@@ -340,7 +376,7 @@ static int ensure_slot(rt_context * ctx, int index) {
 // The kernels get RtParams by value: the context's block with one slot's per-sample pointers patched in.
 static RtParams slot_params(const rt_context * ctx, const SampleSlot & slot, int index) {
 	RtParams p = ctx->params;
-	memcpy(p.trace, slot.trace, sizeof(p.trace)); memcpy(p.material, slot.material, sizeof(p.material)); p.shadow = slot.shadow;
+	use_queues(p, slot.queues);
 	p.sizes = slot.sizes; p.ray_cursors = slot.ray_cursors; p.stack_spill = (uint2 *)slot.spill[0];
 	if (index > 0) for (int i = 0; i < RT_AOV_COUNT; i++) p.aovs[i].framebuffer = (float4 *)slot.aov_framebuffer[i];
 	if (index > 0 && slot.gbuffers[0]) {
@@ -416,6 +452,42 @@ static bool bvh_nodes_present(const rt_context * ctx) {
 	return ctx->bvh_width == 8 ? p.bvh8_nodes != nullptr : (ctx->bvh_width == 4 ? p.bvh4_nodes != nullptr : p.bvh2_nodes != nullptr);
 }
 
+// What a render or trace entry point needs uploaded before it launches anything. NEED_SCENE reports missing geometry
+// and missing instances apart; NEED_SCENE_JOINT (the explicit-ray entry points) reports them as one.
+enum { NEED_SCENE = 1, NEED_SCENE_JOINT = 2, NEED_MATERIALS = 4, NEED_RNG = 8, NEED_SKY = 16, NEED_FRAME = 32 };
+static int check_ready(rt_context * ctx, const char * caller, int needs) {
+	const RtParams & p = ctx->params;
+	const bool geometry = p.triangles && bvh_nodes_present(ctx), instances = p.mesh_bvh_root_indices != nullptr;
+	const struct { int need; bool missing; const char * what; } checks[] = {
+		{ NEED_SCENE,       !geometry,                        "geometry not uploaded" },
+		{ NEED_SCENE,       !instances,                       "instances not uploaded" },
+		{ NEED_SCENE_JOINT, !geometry || !instances,          "geometry / instances not uploaded" },
+		{ NEED_MATERIALS,   !p.materials,                     "materials not uploaded" },
+		{ NEED_RNG,         !p.pmj_samples || !p.blue_noise,  "RNG tables not uploaded" },
+		{ NEED_SKY,         !p.sky,                           "sky not set" },
+		{ NEED_FRAME,       ctx->frame_pixels == 0,           "rt_resize was not called" },
+	};
+	for (const auto & c : checks) if ((needs & c.need) && c.missing) return fail(ctx, RT_ERROR_NOT_READY, "%s: %s", caller, c.what);
+	return RT_OK;
+}
+
+// The pixels a render call covers: rt_set_pixel_range's (offset, count) -- the rest of the frame for a negative count --
+// or, in tile mode, local pixels 0 .. count-1, which rt_map_pixel maps to this context's tiles.
+static int resolve_pixel_range(rt_context * ctx, const char * caller, int * out_offset, int * out_count) {
+	const RtParams & p = ctx->params;
+	const int frame = p.screen_width * p.screen_height;
+	int offset = ctx->pixel_offset, count = ctx->pixel_count < 0 ? frame - offset : ctx->pixel_count;
+	if (p.tile_pixels > 0) {
+		int tiles_total = (frame + p.tile_pixels - 1) / p.tile_pixels;
+		int owned = p.tile_first < tiles_total ? (tiles_total - p.tile_first + p.tile_stride - 1) / p.tile_stride : 0;
+		offset = 0; count = owned * p.tile_pixels;
+		int last_tile = p.tile_first + (owned - 1) * p.tile_stride;
+		if (owned > 0 && last_tile == tiles_total - 1) count -= tiles_total * p.tile_pixels - frame; // clipped last tile
+	} else if (offset + count > frame) return fail(ctx, RT_ERROR_OUT_OF_RANGE, "%s: pixel range [%d,%d) exceeds the %d pixel frame", caller, offset, offset + count, frame);
+	*out_offset = offset; *out_count = count;
+	return RT_OK;
+}
+
 enum { STAGE_GENERATE = 0, STAGE_TRACE, STAGE_SORT, STAGE_SHADE, STAGE_SHADOW, STAGE_POST, STAGE_END };
 // what a [begin, end] event pair of rt_set_profiling(ctx, 2 / 3) brackets (the `kind` of rt_get_launch_timings)
 enum { SPAN_TRACE = RT_TIMING_TRACE, SPAN_SHADOW = RT_TIMING_SHADOW, SPAN_SORT = RT_TIMING_SORT, SPAN_GENERATE = RT_TIMING_GENERATE, SPAN_ACCUMULATE = RT_TIMING_ACCUMULATE,
@@ -443,16 +515,12 @@ int rt_create(int device_ordinal, rt_context ** out_ctx) {
 	ctx->params.entry_tlas_stack_size = RT_INVALID;
 	ctx->params.svgf_tiles = 1;
 	ctx->params.skip_behind_hit = 1;
-	if (const char * e = getenv("GRT_SKIP_BEHIND_HIT")) ctx->params.skip_behind_hit = atoi(e) != 0;   // (A / B runs of one command: bench.py, tools/)
 	memset(&ctx->last_counters, 0, sizeof(ctx->last_counters));
 	RT_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
 	RT_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_main, hipEventDisableTiming));
 	RT_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_interop, hipEventDisableTiming));
 	RT_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_scene, hipEventDisableTiming));
 	RT_HIP(ctx, hipEventRecord(ctx->ev_scene, ctx->stream));
-	if (const char * e = getenv("GRT_SAMPLES_IN_FLIGHT")) { int n = atoi(e); if (n >= 1 && n <= RT_MAX_SAMPLE_SLOTS) ctx->samples_in_flight = n; }
-	if (const char * e = getenv("GRT_OVERLAP_SHADOWS")) ctx->overlap_shadows = atoi(e) != 0;
-	if (const char * e = getenv("GRT_SCHEDULER")) ctx->scheduler = strcmp(e, "slots") == 0 ? RT_SCHEDULER_SLOTS : RT_SCHEDULER_MERGED;
 
 	int s = ensure_slot(ctx, 0); if (s) return s;
 	s = device_alloc(ctx, (void **)&ctx->explicit_retired, 8 * sizeof(int)); if (s) return s;
@@ -521,20 +589,65 @@ int rt_geometry_fits_flat_engine(size_t node_count, size_t triangle_count) {
 	return node_count < (size_t(1) << 24) && triangle_count * 48 < (1ull << 32) ? 1 : 0;
 }
 
-int rt_upload_geometry(rt_context * ctx, const void * triangles, size_t triangle_count, const void * bvh8_nodes, size_t node_count) {
-	RT_REQUIRE(ctx, ctx && triangles && bvh8_nodes, "rt_upload_geometry: NULL argument");
-	ctx->build_boxes.clear(); ctx->build_boxes_first = 0;   // (boxes set for a build that never came do not wait for another geometry's)
+} // extern "C"
+
+// The node array of one BVH width as the context holds it: 80-byte CWBVH nodes (8), 32-byte binary (2) or 128-byte 4-wide (4) nodes.
+struct NodeArray { void * & device; size_t & count; const float4 * & param; size_t node_bytes; };
+static NodeArray node_array(rt_context * ctx, int width) {
+	if (width == 2) return { ctx->bvh2_nodes, ctx->bvh2_node_count, ctx->params.bvh2_nodes, 32 };
+	if (width == 4) return { ctx->bvh4_nodes, ctx->bvh4_node_count, ctx->params.bvh4_nodes, 128 };
+	return { ctx->bvh8_nodes, ctx->bvh8_node_count, ctx->params.bvh8_nodes, 80 };
+}
+
+static int upload_geometry(rt_context * ctx, const char * caller, int width, const void * triangles, size_t triangle_count, const void * nodes, size_t node_count) {
+	if (!ctx || !triangles || !nodes) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: NULL argument", caller);
+	NodeArray a = node_array(ctx, width);
+	if (width == 8) { ctx->build_boxes.clear(); ctx->build_boxes_first = 0; }   // (boxes set for a build that never came do not wait for another geometry's)
 	(void)hipSetDevice(ctx->device);
 	int s = upload(ctx, &ctx->triangles, triangles, triangle_count * 96); if (s) return s;
-	s = upload(ctx, &ctx->bvh8_nodes, bvh8_nodes, node_count * 80); if (s) return s;
+	s = upload(ctx, &a.device, nodes, node_count * a.node_bytes); if (s) return s;
 	s = upload_triangle_positions(ctx, triangles, triangle_count); if (s) return s;
-	ctx->triangle_count = triangle_count; ctx->bvh8_node_count = node_count;
-	ctx->tlas_version_in_nodes = ~0ull;
-	ctx->params.triangles  = (const float4 *)ctx->triangles;
-	ctx->params.bvh8_nodes = (const float4 *)ctx->bvh8_nodes;
-	ctx->params.geometry_below_4gib = rt_geometry_fits_flat_engine(node_count, triangle_count);
+	ctx->triangle_count = triangle_count; a.count = node_count;
+	ctx->params.triangles = (const float4 *)ctx->triangles;
+	a.param = (const float4 *)a.device;
+	if (width == 8) {   // what only the CWBVH has: the merged wavefront's TLAS copy in its node array, the flattened scene's engine
+		ctx->tlas_version_in_nodes = ~0ull;
+		ctx->params.geometry_below_4gib = rt_geometry_fits_flat_engine(node_count, triangle_count);
+	}
 	return RT_OK;
 }
+
+// A new version of the TLAS, in the node format of `width`
+static int upload_tlas(rt_context * ctx, const char * caller, int width, const void * tlas_nodes, size_t tlas_node_count) {
+	if (!ctx || !tlas_nodes) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: NULL argument", caller);
+	NodeArray a = node_array(ctx, width);
+	if (!a.device || tlas_node_count > a.count) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: geometry not uploaded or TLAS larger than the node array", caller);
+	(void)hipSetDevice(ctx->device);
+	void * staging = nullptr;
+	int s = ring_begin(ctx, ctx->tlas_ring, tlas_node_count * a.node_bytes, &staging); if (s) return s;
+	memcpy(staging, tlas_nodes, tlas_node_count * a.node_bytes);
+	s = ring_commit(ctx, ctx->tlas_ring); if (s) return s;
+	ctx->params.tlas_nodes = (const float4 *)ctx->tlas_ring.device[ctx->tlas_ring.current];
+	ctx->params.tlas_node_count = int(tlas_node_count);
+	ctx->tlas_node_bytes = a.node_bytes;
+	ctx->tlas_version++;
+	return RT_OK;
+}
+
+extern "C" {
+
+int rt_upload_geometry(rt_context * ctx, const void * triangles, size_t triangle_count, const void * bvh8_nodes, size_t node_count) {
+	return upload_geometry(ctx, "rt_upload_geometry", 8, triangles, triangle_count, bvh8_nodes, node_count);
+}
+int rt_upload_geometry_bvh2(rt_context * ctx, const void * triangles, size_t triangle_count, const void * bvh2_nodes, size_t node_count) {
+	return upload_geometry(ctx, "rt_upload_geometry_bvh2", 2, triangles, triangle_count, bvh2_nodes, node_count);
+}
+int rt_upload_geometry_bvh4(rt_context * ctx, const void * triangles, size_t triangle_count, const void * bvh4_nodes, size_t node_count) {
+	return upload_geometry(ctx, "rt_upload_geometry_bvh4", 4, triangles, triangle_count, bvh4_nodes, node_count);
+}
+int rt_upload_tlas(rt_context * ctx, const void * tlas_nodes, size_t tlas_node_count) { return upload_tlas(ctx, "rt_upload_tlas", 8, tlas_nodes, tlas_node_count); }
+int rt_upload_tlas_bvh2(rt_context * ctx, const void * tlas_nodes, size_t tlas_node_count) { return upload_tlas(ctx, "rt_upload_tlas_bvh2", 2, tlas_nodes, tlas_node_count); }
+int rt_upload_tlas_bvh4(rt_context * ctx, const void * tlas_nodes, size_t tlas_node_count) { return upload_tlas(ctx, "rt_upload_tlas_bvh4", 4, tlas_nodes, tlas_node_count); }
 
 // Static geometry flattened into one BLAS: its triangles are COPIES of triangles that other BLASes own, and a hit on a copy is
 // reported as the instance and the triangle it was copied from (kernels_trace.hip translates once per ray, when the ray is done).
@@ -739,64 +852,6 @@ int rt_read_geometry(rt_context * ctx, void * out_triangles, void * out_bvh8_nod
 	if (out_triangles)  RT_HIP(ctx, hipMemcpy(out_triangles,  ctx->triangles,  ctx->triangle_count * 96, hipMemcpyDeviceToHost));
 	if (out_bvh8_nodes) RT_HIP(ctx, hipMemcpy(out_bvh8_nodes, ctx->bvh8_nodes, ctx->bvh8_node_count * 80, hipMemcpyDeviceToHost));
 	return RT_OK;
-}
-
-// TLAS of the selected BVH type: node_bytes = 80 (CWBVH), 32 (binary) or 128 (4-wide)
-static int upload_tlas_version(rt_context * ctx, const void * tlas_nodes, size_t tlas_node_count, size_t node_bytes) {
-	void * staging = nullptr;
-	int s = ring_begin(ctx, ctx->tlas_ring, tlas_node_count * node_bytes, &staging); if (s) return s;
-	memcpy(staging, tlas_nodes, tlas_node_count * node_bytes);
-	s = ring_commit(ctx, ctx->tlas_ring); if (s) return s;
-	ctx->params.tlas_nodes = (const float4 *)ctx->tlas_ring.device[ctx->tlas_ring.current];
-	ctx->params.tlas_node_count = int(tlas_node_count);
-	ctx->tlas_node_bytes = node_bytes;
-	ctx->tlas_version++;
-	return RT_OK;
-}
-
-int rt_upload_tlas(rt_context * ctx, const void * tlas_nodes, size_t tlas_node_count) {
-	RT_REQUIRE(ctx, ctx && tlas_nodes, "rt_upload_tlas: NULL argument");
-	RT_REQUIRE(ctx, ctx->bvh8_nodes && tlas_node_count <= ctx->bvh8_node_count, "rt_upload_tlas: geometry not uploaded or TLAS larger than the node array");
-	(void)hipSetDevice(ctx->device);
-	return upload_tlas_version(ctx, tlas_nodes, tlas_node_count, 80);
-}
-
-int rt_upload_geometry_bvh2(rt_context * ctx, const void * triangles, size_t triangle_count, const void * bvh2_nodes, size_t node_count) {
-	RT_REQUIRE(ctx, ctx && triangles && bvh2_nodes, "rt_upload_geometry_bvh2: NULL argument");
-	(void)hipSetDevice(ctx->device);
-	int s = upload(ctx, &ctx->triangles, triangles, triangle_count * 96); if (s) return s;
-	s = upload(ctx, &ctx->bvh2_nodes, bvh2_nodes, node_count * 32); if (s) return s;
-	s = upload_triangle_positions(ctx, triangles, triangle_count); if (s) return s;
-	ctx->triangle_count = triangle_count; ctx->bvh2_node_count = node_count;
-	ctx->params.triangles  = (const float4 *)ctx->triangles;
-	ctx->params.bvh2_nodes = (const float4 *)ctx->bvh2_nodes;
-	return RT_OK;
-}
-
-int rt_upload_tlas_bvh2(rt_context * ctx, const void * tlas_nodes, size_t tlas_node_count) {
-	RT_REQUIRE(ctx, ctx && tlas_nodes, "rt_upload_tlas_bvh2: NULL argument");
-	RT_REQUIRE(ctx, ctx->bvh2_nodes && tlas_node_count <= ctx->bvh2_node_count, "rt_upload_tlas_bvh2: geometry not uploaded or TLAS larger than the node array");
-	(void)hipSetDevice(ctx->device);
-	return upload_tlas_version(ctx, tlas_nodes, tlas_node_count, 32);
-}
-
-int rt_upload_geometry_bvh4(rt_context * ctx, const void * triangles, size_t triangle_count, const void * bvh4_nodes, size_t node_count) {
-	RT_REQUIRE(ctx, ctx && triangles && bvh4_nodes, "rt_upload_geometry_bvh4: NULL argument");
-	(void)hipSetDevice(ctx->device);
-	int s = upload(ctx, &ctx->triangles, triangles, triangle_count * 96); if (s) return s;
-	s = upload(ctx, &ctx->bvh4_nodes, bvh4_nodes, node_count * 128); if (s) return s;
-	s = upload_triangle_positions(ctx, triangles, triangle_count); if (s) return s;
-	ctx->triangle_count = triangle_count; ctx->bvh4_node_count = node_count;
-	ctx->params.triangles  = (const float4 *)ctx->triangles;
-	ctx->params.bvh4_nodes = (const float4 *)ctx->bvh4_nodes;
-	return RT_OK;
-}
-
-int rt_upload_tlas_bvh4(rt_context * ctx, const void * tlas_nodes, size_t tlas_node_count) {
-	RT_REQUIRE(ctx, ctx && tlas_nodes, "rt_upload_tlas_bvh4: NULL argument");
-	RT_REQUIRE(ctx, ctx->bvh4_nodes && tlas_node_count <= ctx->bvh4_node_count, "rt_upload_tlas_bvh4: geometry not uploaded or TLAS larger than the node array");
-	(void)hipSetDevice(ctx->device);
-	return upload_tlas_version(ctx, tlas_nodes, tlas_node_count, 128);
 }
 
 int rt_set_bvh_type(rt_context * ctx, int bvh_width) {
@@ -1051,12 +1106,6 @@ int rt_set_sky(rt_context * ctx, const float * rgba, int width, int height, floa
 
 // ---- frame state ---------------------------------------------------------------------------------------
 
-static int alloc_vec3(rt_context * ctx, RtVec3SoA & v, size_t n) {
-	int s = device_alloc(ctx, (void **)&v.x, n * 4); if (s) return s;
-	s = device_alloc(ctx, (void **)&v.y, n * 4); if (s) return s;
-	return device_alloc(ctx, (void **)&v.z, n * 4);
-}
-
 static size_t wanted_batch_size(const rt_context * ctx) {
 	size_t frame = size_t(ctx->params.screen_width) * ctx->params.screen_height;
 	size_t n = ctx->batch_size_request > 0 ? size_t(ctx->batch_size_request) : frame;
@@ -1067,46 +1116,13 @@ static size_t wanted_batch_size(const rt_context * ctx) {
 static int ensure_queues(rt_context * ctx, int slot_index = 0, size_t pixels = 0) {
 	SampleSlot & slot = ctx->slots[slot_index];
 	size_t n = pixels > 0 ? pixels : wanted_batch_size(ctx); // entries: pixels of a batch x samples per batch
-	if (slot.queues_allocated && slot.queue_capacity >= n) return RT_OK;
-	if (slot.queues_allocated) { // grow: release the old queues
+	if (slot.queues.allocated && slot.queues.capacity >= n) return RT_OK;
+	if (slot.queues.allocated) { // grow: release the old queues
 		RT_HIP(ctx, quiesce(ctx));
-		auto free3 = [&](RtVec3SoA & v) { device_free(ctx, v.x); device_free(ctx, v.y); device_free(ctx, v.z); };
-		for (int i = 0; i < 2; i++) { RtTraceBuffer & t = slot.trace[i]; free3(t.origin); free3(t.direction); device_free(ctx, t.hits); device_free(ctx, t.cone_angle); device_free(ctx, t.cone_width); device_free(ctx, t.medium); device_free(ctx, t.pixel_index_and_flags); free3(t.throughput); device_free(ctx, t.last_pdf); }
-		for (int i = 0; i < 4; i++) { RtMaterialBuffer & m = slot.material[i]; free3(m.direction); device_free(ctx, m.hits); device_free(ctx, m.cone_angle); device_free(ctx, m.cone_width); device_free(ctx, m.medium); device_free(ctx, m.pixel_index_and_flags); free3(m.throughput); }
-		RtShadowBuffer & sh = slot.shadow; free3(sh.origin); free3(sh.direction); device_free(ctx, sh.max_distance); device_free(ctx, sh.illumination_and_pixel_index);
-		slot.queues_allocated = false;
+		queues_free(ctx, slot.queues);
 	}
-	slot.queue_capacity = n;
-	int s;
-	for (int i = 0; i < 2; i++) {
-		RtTraceBuffer & t = slot.trace[i];
-		if ((s = alloc_vec3(ctx, t.origin, n))) return s;
-		if ((s = alloc_vec3(ctx, t.direction, n))) return s;
-		if ((s = device_alloc(ctx, (void **)&t.hits, n * 16))) return s;
-		if ((s = device_alloc(ctx, (void **)&t.cone_angle, n * 4))) return s;
-		if ((s = device_alloc(ctx, (void **)&t.cone_width, n * 4))) return s;
-		if ((s = device_alloc(ctx, (void **)&t.medium, n * 4))) return s;
-		if ((s = device_alloc(ctx, (void **)&t.pixel_index_and_flags, n * 4))) return s;
-		if ((s = alloc_vec3(ctx, t.throughput, n))) return s;
-		if ((s = device_alloc(ctx, (void **)&t.last_pdf, n * 4))) return s;
-	}
-	for (int i = 0; i < 4; i++) {
-		RtMaterialBuffer & m = slot.material[i];
-		if ((s = alloc_vec3(ctx, m.direction, n))) return s;
-		if ((s = device_alloc(ctx, (void **)&m.hits, n * 16))) return s;
-		if ((s = device_alloc(ctx, (void **)&m.cone_angle, n * 4))) return s;
-		if ((s = device_alloc(ctx, (void **)&m.cone_width, n * 4))) return s;
-		if ((s = device_alloc(ctx, (void **)&m.medium, n * 4))) return s;
-		if ((s = device_alloc(ctx, (void **)&m.pixel_index_and_flags, n * 4))) return s;
-		if ((s = alloc_vec3(ctx, m.throughput, n))) return s;
-	}
-	RtShadowBuffer & sh = slot.shadow;
-	if ((s = alloc_vec3(ctx, sh.origin, n))) return s;
-	if ((s = alloc_vec3(ctx, sh.direction, n))) return s;
-	if ((s = device_alloc(ctx, (void **)&sh.max_distance, n * 4))) return s;
-	if ((s = device_alloc(ctx, (void **)&sh.illumination_and_pixel_index, n * 16))) return s;
-	slot.queues_allocated = true;
-	if (slot_index == 0) { memcpy(ctx->params.trace, slot.trace, sizeof(slot.trace)); memcpy(ctx->params.material, slot.material, sizeof(slot.material)); ctx->params.shadow = slot.shadow; }
+	int s = queues_allocate(ctx, slot.queues, n); if (s) return s;
+	if (slot_index == 0) use_queues(ctx->params, slot.queues);
 	return RT_OK;
 }
 
@@ -1164,15 +1180,15 @@ static int sync_svgf(rt_context * ctx) {
 	if (want == ctx->svgf_allocated || ctx->frame_pixels == 0) return RT_OK;
 	if (want) {
 		// gbuffers (float4, int2, float2), moment, history x5 (length is int), taa x2, decoded normal + depth, variance pairs x2
-		const size_t elem[15] = { 16, 8, 8, 16, 4, 16, 16, 16, 16, 16, 16, 16, 8, 8, 16 };
+		const size_t elem[15] = { gbuffer_pixel_bytes[0], gbuffer_pixel_bytes[1], gbuffer_pixel_bytes[2], 16, 4, 16, 16, 16, 16, 16, 16, 16, 8, 8, 16 };
 		for (int i = 0; i < 15; i++) {
 			int s = device_alloc(ctx, &ctx->svgf_buffers[i], ctx->frame_pixels * elem[i]); if (s) return s;
 			RT_HIP(ctx, hipMemsetAsync(ctx->svgf_buffers[i], 0, ctx->frame_pixels * elem[i], ctx->stream));
 		}
 		{ int s = device_alloc(ctx, &ctx->svgf_buffers[15], (RT_SVGF_YOUNG_HEADER + ctx->frame_pixels) * 4); if (s) return s; RT_HIP(ctx, hipMemsetAsync(ctx->svgf_buffers[15], 0, RT_SVGF_YOUNG_HEADER * 4, ctx->stream)); }
 		for (int k = 1; k < RT_MAX_SAMPLE_SLOTS; k++) if (ctx->slots[k].created) for (int i = 0; i < 3; i++) {
-			int s = device_alloc(ctx, &ctx->slots[k].gbuffers[i], ctx->frame_pixels * elem[i]); if (s) return s;
-			RT_HIP(ctx, hipMemsetAsync(ctx->slots[k].gbuffers[i], 0, ctx->frame_pixels * elem[i], ctx->stream));
+			int s = device_alloc(ctx, &ctx->slots[k].gbuffers[i], ctx->frame_pixels * gbuffer_pixel_bytes[i]); if (s) return s;
+			RT_HIP(ctx, hipMemsetAsync(ctx->slots[k].gbuffers[i], 0, ctx->frame_pixels * gbuffer_pixel_bytes[i], ctx->stream));
 		}
 		// The filter keeps (direct.w, indirect.w) of the radiance accumulators mirrored in svgf_variance[1] and writes both only where it
 		// filters (not at sky pixels). The mirror starts at zero, so the accumulators' .w have to: radiance accumulated WITHOUT the filter
@@ -1737,7 +1753,6 @@ static int stream_create(rt_context * ctx) {
 	PathStream & s = ctx->path_stream;
 	if (s.created) return RT_OK;
 	if (!ctx->stream_history) RT_HIP(ctx, hipHostMalloc((void **)&ctx->stream_history, sizeof(unsigned long long) * 10 * RT_STREAM_HISTORY_ROWS));
-	memset(s.trace, 0, sizeof(s.trace)); memset(s.material, 0, sizeof(s.material)); memset(&s.shadow, 0, sizeof(s.shadow));
 	RT_HIP(ctx, hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
 	RT_HIP(ctx, hipEventCreateWithFlags(&s.ev_idle, hipEventDisableTiming));
 	RT_HIP(ctx, hipEventRecord(s.ev_idle, s.stream));
@@ -1780,12 +1795,11 @@ static void stream_destroy(rt_context * ctx) {
 // SVGF: a frame starts from a copy of the g-buffers of the frame before it (the reference has ONE set that every frame
 // overwrites where its primary rays hit something). Before the sets of the sample slots are freed or re-allocated the
 // latest one moves to the set of slot 0 of the slot scheduler, where the next frame of either scheduler finds it.
-static const size_t stream_gbuffer_elem[3] = { 16, 8, 8 };
 static void stream_save_gbuffers(rt_context * ctx) {
 	PathStream & s = ctx->path_stream;
 	if (s.last_gbuffer_slot >= 0 && s.gbuffers[0] && ctx->svgf_buffers[0]) {
 		(void)hipDeviceSynchronize();
-		for (int i = 0; i < 3; i++) (void)hipMemcpy(ctx->svgf_buffers[i], (char *)s.gbuffers[i] + ctx->frame_pixels * stream_gbuffer_elem[i] * size_t(s.last_gbuffer_slot), ctx->frame_pixels * stream_gbuffer_elem[i], hipMemcpyDeviceToDevice);
+		for (int i = 0; i < 3; i++) (void)hipMemcpy(ctx->svgf_buffers[i], (char *)s.gbuffers[i] + ctx->frame_pixels * gbuffer_pixel_bytes[i] * size_t(s.last_gbuffer_slot), ctx->frame_pixels * gbuffer_pixel_bytes[i], hipMemcpyDeviceToDevice);
 		ctx->last_slot = 0;
 	}
 	s.last_gbuffer_slot = -1;
@@ -1819,8 +1833,8 @@ static int stream_ensure_frames(rt_context * ctx, int wanted_slots) {
 		RT_HIP(ctx, hipMemset(s.aov_framebuffer[i], 0, bytes));
 	}
 	if (ctx->svgf_allocated) for (int i = 0; i < 3; i++) {
-		int status = device_alloc(ctx, &s.gbuffers[i], ctx->frame_pixels * stream_gbuffer_elem[i] * size_t(slots)); if (status) return status;
-		RT_HIP(ctx, hipMemset(s.gbuffers[i], 0, ctx->frame_pixels * stream_gbuffer_elem[i] * size_t(slots)));
+		int status = device_alloc(ctx, &s.gbuffers[i], ctx->frame_pixels * gbuffer_pixel_bytes[i] * size_t(slots)); if (status) return status;
+		RT_HIP(ctx, hipMemset(s.gbuffers[i], 0, ctx->frame_pixels * gbuffer_pixel_bytes[i] * size_t(slots)));
 	}
 	s.frame_slots = slots;
 	for (bool & used : s.slot_used) used = false;
@@ -1830,44 +1844,10 @@ static int stream_ensure_frames(rt_context * ctx, int wanted_slots) {
 
 static int stream_ensure_queues(rt_context * ctx, size_t entries) {
 	PathStream & s = ctx->path_stream;
-	if (s.queues_allocated && s.capacity >= entries) return RT_OK;
+	if (s.queues.allocated && s.queues.capacity >= entries) return RT_OK;
 	RT_HIP(ctx, quiesce(ctx));
-	auto free3 = [&](RtVec3SoA & v) { device_free(ctx, v.x); device_free(ctx, v.y); device_free(ctx, v.z); };
-	if (s.queues_allocated) {
-		for (RtTraceBuffer & t : s.trace) { free3(t.origin); free3(t.direction); device_free(ctx, t.hits); device_free(ctx, t.cone_angle); device_free(ctx, t.cone_width); device_free(ctx, t.medium); device_free(ctx, t.pixel_index_and_flags); free3(t.throughput); device_free(ctx, t.last_pdf); }
-		for (RtMaterialBuffer & m : s.material) { free3(m.direction); device_free(ctx, m.hits); device_free(ctx, m.cone_angle); device_free(ctx, m.cone_width); device_free(ctx, m.medium); device_free(ctx, m.pixel_index_and_flags); free3(m.throughput); }
-		free3(s.shadow.origin); free3(s.shadow.direction); device_free(ctx, s.shadow.max_distance); device_free(ctx, s.shadow.illumination_and_pixel_index);
-		s.queues_allocated = false;
-	}
-	size_t n = entries;
-	int status;
-	for (RtTraceBuffer & t : s.trace) {
-		if ((status = alloc_vec3(ctx, t.origin, n))) return status;
-		if ((status = alloc_vec3(ctx, t.direction, n))) return status;
-		if ((status = device_alloc(ctx, (void **)&t.hits, n * 16))) return status;
-		if ((status = device_alloc(ctx, (void **)&t.cone_angle, n * 4))) return status;
-		if ((status = device_alloc(ctx, (void **)&t.cone_width, n * 4))) return status;
-		if ((status = device_alloc(ctx, (void **)&t.medium, n * 4))) return status;
-		if ((status = device_alloc(ctx, (void **)&t.pixel_index_and_flags, n * 4))) return status;
-		if ((status = alloc_vec3(ctx, t.throughput, n))) return status;
-		if ((status = device_alloc(ctx, (void **)&t.last_pdf, n * 4))) return status;
-	}
-	for (RtMaterialBuffer & m : s.material) {
-		if ((status = alloc_vec3(ctx, m.direction, n))) return status;
-		if ((status = device_alloc(ctx, (void **)&m.hits, n * 16))) return status;
-		if ((status = device_alloc(ctx, (void **)&m.cone_angle, n * 4))) return status;
-		if ((status = device_alloc(ctx, (void **)&m.cone_width, n * 4))) return status;
-		if ((status = device_alloc(ctx, (void **)&m.medium, n * 4))) return status;
-		if ((status = device_alloc(ctx, (void **)&m.pixel_index_and_flags, n * 4))) return status;
-		if ((status = alloc_vec3(ctx, m.throughput, n))) return status;
-	}
-	if ((status = alloc_vec3(ctx, s.shadow.origin, n))) return status;
-	if ((status = alloc_vec3(ctx, s.shadow.direction, n))) return status;
-	if ((status = device_alloc(ctx, (void **)&s.shadow.max_distance, n * 4))) return status;
-	if ((status = device_alloc(ctx, (void **)&s.shadow.illumination_and_pixel_index, n * 16))) return status;
-	s.queues_allocated = true;
-	s.capacity = n;
-	return RT_OK;
+	if (s.queues.allocated) queues_free(ctx, s.queues);
+	return queues_allocate(ctx, s.queues, entries);
 }
 
 // The parameter block of iteration `iteration`: the context's block with the stream's queues, control block and
@@ -1875,7 +1855,7 @@ static int stream_ensure_queues(rt_context * ctx, size_t entries) {
 static RtParams stream_params(const rt_context * ctx, int iteration) {
 	const PathStream & s = ctx->path_stream;
 	RtParams p = ctx->params;
-	memcpy(p.trace, s.trace, sizeof(p.trace)); memcpy(p.material, s.material, sizeof(p.material)); p.shadow = s.shadow;
+	use_queues(p, s.queues);
 	p.sizes = nullptr; p.ray_cursors = nullptr; p.stack_spill = (uint2 *)s.spill;
 	p.stream = s.control; p.stream_table = s.table_device; p.stream_iteration = iteration;
 	for (int i = 0; i < RT_AOV_COUNT; i++) p.aovs[i].framebuffer = (float4 *)s.aov_framebuffer[i];
@@ -2003,12 +1983,11 @@ static int stream_generate(rt_context * ctx, const StreamSubmission & sub) {
 	stage_mark(ctx, STAGE_GENERATE, st);
 	span_mark(ctx, SPAN_GENERATE, st);
 	// Queue order of the primary rays: 8 x 8 pixel patches along bands of 8 scan lines when the submission's pixel list is made of whole bands
-	// (the whole frame, or tiles of whole bands: rt_map_pixel keeps a band together); scan lines otherwise. GRT_PRIMARY_ORDER=WxH / 0 for A / B runs.
-	static const int order_width = [] { const char * e = getenv("GRT_PRIMARY_ORDER"); return e ? atoi(e) : 8; }();
-	static const int order_rows  = [] { const char * e = getenv("GRT_PRIMARY_ORDER"); const char * x = e ? strchr(e, 'x') : nullptr; return e ? (x ? atoi(x + 1) : atoi(e)) : 8; }();
+	// (the whole frame, or tiles of whole bands: rt_map_pixel keeps a band together); scan lines otherwise.
+	const int order = 8;
 	const int frame = pg.screen_width * pg.screen_height;
-	const bool whole_bands = order_width > 0 && order_rows > 0 && (sub.tile_pixels > 0 ? sub.tile_pixels % (order_rows * pg.screen_width) == 0 : (sub.range_offset == 0 && sub.range_count == frame));
-	rt_launch_generate_stream(pg, sub.first_sample, sub.range_offset, sub.range_count, sub.slot_base, int(s.pending_paths), whole_bands ? order_width : 0, whole_bands ? order_rows : 0, st);
+	const bool whole_bands = sub.tile_pixels > 0 ? sub.tile_pixels % (order * pg.screen_width) == 0 : (sub.range_offset == 0 && sub.range_count == frame);
+	rt_launch_generate_stream(pg, sub.first_sample, sub.range_offset, sub.range_count, sub.slot_base, int(s.pending_paths), whole_bands ? order : 0, whole_bands ? order : 0, st);
 	span_mark(ctx, SPAN_GENERATE, st);
 	s.pending++; s.pending_paths += sub.paths;
 	return RT_OK;
@@ -2092,11 +2071,10 @@ static int stream_submit(rt_context * ctx, int sample_index, int sample_count, i
 	const int batch = (ctx->frame_pipelining && !ctx->params.config.enable_svgf) ? int(std::min<long long>(RT_STREAM_MAX_BATCH, (batch_paths + paths - 1) / paths)) : 1;
 	status = stream_ensure_frames(ctx, sample_count * (num_bounces + 1) * batch); if (status) return status;
 	if (sample_count > s.frame_slots) return fail(ctx, RT_ERROR_OUT_OF_RANGE, "rt_render_samples: %d samples of a %zu pixel frame exceed the %d sample slots of the merged wavefront", sample_count, ctx->frame_pixels, s.frame_slots);
-	static const double factor = getenv("GRT_STREAM_CAPACITY_FACTOR") ? atof(getenv("GRT_STREAM_CAPACITY_FACTOR")) : 4.0;
 	// room for four iterations' worth of new paths -- or, for a declared burst of whole frames (rt_set_stream_batch), for the burst and a quarter: its frames
 	// enter together and only die from then on (412 bytes per path: 21 GB for five 4-sample frames at 1080p instead of 68)
-	const double room = batch_paths > (long long)RT_STREAM_BATCH_PATHS && paths * batch > (long long)RT_STREAM_BATCH_PATHS ? 1.25 : (factor < 1.0 ? 1.0 : factor);
-	if (size_t(paths * batch) > s.capacity || !s.queues_allocated) { status = stream_ensure_queues(ctx, size_t(double(paths * batch) * room) + 1024); if (status) return status; }
+	const double room = batch_paths > (long long)RT_STREAM_BATCH_PATHS && paths * batch > (long long)RT_STREAM_BATCH_PATHS ? 1.25 : 4.0;
+	if (size_t(paths * batch) > s.queues.capacity || !s.queues.allocated) { status = stream_ensure_queues(ctx, size_t(double(paths * batch) * room) + 1024); if (status) return status; }
 
 	// admission: sample slots, a statistics ring entry, and room in the queues
 	int slot_base = -1;
@@ -2110,13 +2088,13 @@ static int stream_submit(rt_context * ctx, int sample_index, int sample_count, i
 			for (int k = 0; k < sample_count; k++) if (s.slot_used[candidate + k]) { free_run = false; break; }
 			if (free_run) slot_base = candidate;
 		}
-		bool fits = stream_bound(s) + s.pending_paths + paths <= (long long)s.capacity;   // (with the submissions already waiting for the next iteration)
+		bool fits = stream_bound(s) + s.pending_paths + paths <= (long long)s.queues.capacity;   // (with the submissions already waiting for the next iteration)
 		if (ring_free && slot_base >= 0 && fits) break;
 		if (!fits && s.known_iteration < s.iteration - 1 && s.iteration > s.base_iteration) { // the bound is stale: let the device catch up
 			RT_HIP(ctx, hipEventSynchronize(s.iteration_done[(s.iteration - 1) % RT_STREAM_PROGRESS_RING]));
 			continue;
 		}
-		if (s.in_flight.empty()) return fail(ctx, RT_ERROR_OUT_OF_RANGE, "rt_render_samples: the merged wavefront cannot take %lld paths (capacity %zu, %d sample slots)", paths, s.capacity, s.frame_slots);
+		if (s.in_flight.empty()) return fail(ctx, RT_ERROR_OUT_OF_RANGE, "rt_render_samples: the merged wavefront cannot take %lld paths (capacity %zu, %d sample slots)", paths, s.queues.capacity, s.frame_slots);
 		status = stream_enqueue_iteration(ctx); if (status) return status;   // advance (with the submissions waiting, if any): paths die, submissions complete
 	}
 
@@ -2144,10 +2122,10 @@ static int stream_submit(rt_context * ctx, int sample_index, int sample_count, i
 	if (ctx->params.config.enable_svgf && s.gbuffers[0]) { // the frame starts from the g-buffers of the frame before it
 		const void * from[3];
 		for (int i = 0; i < 3; i++) {
-			if (s.last_gbuffer_slot >= 0) from[i] = (char *)s.gbuffers[i] + ctx->frame_pixels * stream_gbuffer_elem[i] * size_t(s.last_gbuffer_slot);
+			if (s.last_gbuffer_slot >= 0) from[i] = (char *)s.gbuffers[i] + ctx->frame_pixels * gbuffer_pixel_bytes[i] * size_t(s.last_gbuffer_slot);
 			else from[i] = (ctx->last_slot > 0 && ctx->slots[ctx->last_slot].gbuffers[i]) ? ctx->slots[ctx->last_slot].gbuffers[i] : ctx->svgf_buffers[i]; // (the slot scheduler is drained)
-			void * to = (char *)s.gbuffers[i] + ctx->frame_pixels * stream_gbuffer_elem[i] * size_t(slot_base);
-			if (from[i] && from[i] != to) RT_HIP(ctx, hipMemcpyAsync(to, from[i], ctx->frame_pixels * stream_gbuffer_elem[i], hipMemcpyDeviceToDevice, s.stream));
+			void * to = (char *)s.gbuffers[i] + ctx->frame_pixels * gbuffer_pixel_bytes[i] * size_t(slot_base);
+			if (from[i] && from[i] != to) RT_HIP(ctx, hipMemcpyAsync(to, from[i], ctx->frame_pixels * gbuffer_pixel_bytes[i], hipMemcpyDeviceToDevice, s.stream));
 		}
 		s.last_gbuffer_slot = slot_base;
 	}
@@ -2155,6 +2133,20 @@ static int stream_submit(rt_context * ctx, int sample_index, int sample_count, i
 	status = stream_generate(ctx, sub); if (status) return status;
 	if (s.pending < batch && s.pending_paths < batch_paths) return RT_OK;   // wait for more of the same size
 	return stream_enqueue_iteration(ctx);
+}
+
+// The end of a slot-scheduler submission on slot `slot_index`: its counters travel to pinned memory, its end is recorded,
+// and the scene versions it read stay in use until it is done.
+static int finish_slot_submission(rt_context * ctx, int slot_index) {
+	SampleSlot & slot = ctx->slots[slot_index];
+	hipStream_t st = slot.stream;
+	RT_HIP(ctx, hipMemcpyAsync(slot.pinned_counters, slot.counter_totals, 6 * RT_MAX_BOUNCES * sizeof(int), hipMemcpyDeviceToHost, st));
+	RT_HIP(ctx, hipEventRecord(slot.ev_frame_end, st));
+	RT_HIP(ctx, hipEventRecord(slot.ev_done, st));
+	int status = mark_scene_versions_in_use(ctx, slot_index, st); if (status) return status;
+	ctx->last_slot = slot_index;
+	RT_HIP(ctx, hipGetLastError());
+	return RT_OK;
 }
 
 extern "C" {
@@ -2165,13 +2157,7 @@ int rt_render_samples(rt_context * ctx, int sample_index, int sample_count) {
 	RT_REQUIRE(ctx, ctx, "rt_render_sample: NULL context");
 	RT_REQUIRE(ctx, sample_count >= 1 && sample_count <= RT_MAX_BATCH_SAMPLES, "rt_render_samples: sample_count must be 1..16");
 	(void)hipSetDevice(ctx->device);
-	const RtParams & base = ctx->params;
-	if (!base.triangles || !bvh_nodes_present(ctx)) return fail(ctx, RT_ERROR_NOT_READY, "rt_render_sample: geometry not uploaded");
-	if (!base.mesh_bvh_root_indices)        return fail(ctx, RT_ERROR_NOT_READY, "rt_render_sample: instances not uploaded");
-	if (!base.materials)                    return fail(ctx, RT_ERROR_NOT_READY, "rt_render_sample: materials not uploaded");
-	if (!base.pmj_samples || !base.blue_noise) return fail(ctx, RT_ERROR_NOT_READY, "rt_render_sample: RNG tables not uploaded");
-	if (!base.sky)                          return fail(ctx, RT_ERROR_NOT_READY, "rt_render_sample: sky not set");
-	if (ctx->frame_pixels == 0)          return fail(ctx, RT_ERROR_NOT_READY, "rt_render_sample: rt_resize was not called");
+	int s = check_ready(ctx, "rt_render_sample", NEED_SCENE | NEED_MATERIALS | NEED_RNG | NEED_SKY | NEED_FRAME); if (s) return s;
 	if (ctx->bvh_width != 8 && ctx->trace_statistics) return fail(ctx, RT_ERROR_NOT_READY, "rt_render_sample: trace statistics exist for the CWBVH kernels only");
 	// Slot choice: round-robin over the samples in flight. Profiling / statistics passes use one slot,
 	// serialised. SVGF frames pipeline like plain samples under either scheduler: only their filter stage is ordered.
@@ -2181,51 +2167,25 @@ int rt_render_samples(rt_context * ctx, int sample_index, int sample_count) {
 	                    && !(ctx->batch_size_request > 0); // explicit pixel batches (a VRAM bound of the reference) are a slot-scheduler feature
 	if (ctx->params.config.enable_svgf && sample_count != 1) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_render_samples: SVGF frames are rendered one sample at a time");
 	if (merged != ctx->last_render_merged) { RT_HIP(ctx, quiesce(ctx)); ctx->last_render_merged = merged; }
+	if (ctx->has_material[2] || ctx->has_material[3]) { s = ensure_luts(ctx); if (s) return s; }
+	if (size_t(sample_count) * ctx->frame_pixels >= (1u << 30)) return fail(ctx, RT_ERROR_OUT_OF_RANGE, "rt_render_samples: %d samples of a %zu pixel frame exceed the 30-bit path index", sample_count, ctx->frame_pixels);
+	int range_offset = 0, range_count = 0;
+	s = resolve_pixel_range(ctx, "rt_render_sample", &range_offset, &range_count); if (s) return s;
 	if (merged) {
-		if (ctx->has_material[2] || ctx->has_material[3]) { int ls = ensure_luts(ctx); if (ls) return ls; }
-		if (size_t(sample_count) * ctx->frame_pixels >= (1u << 30)) return fail(ctx, RT_ERROR_OUT_OF_RANGE, "rt_render_samples: %d samples of a %zu pixel frame exceed the 30-bit path index", sample_count, ctx->frame_pixels);
-		const RtParams & cp = ctx->params;
-		int frame = cp.screen_width * cp.screen_height;
-		int offset = ctx->pixel_offset, count = ctx->pixel_count < 0 ? frame - offset : ctx->pixel_count;
-		if (cp.tile_pixels > 0) { // tile mode: local pixels 0..count-1 are mapped to this context's tiles by rt_map_pixel
-			int tiles_total = (frame + cp.tile_pixels - 1) / cp.tile_pixels;
-			int owned = cp.tile_first < tiles_total ? (tiles_total - cp.tile_first + cp.tile_stride - 1) / cp.tile_stride : 0;
-			offset = 0; count = owned * cp.tile_pixels;
-			int last_tile = cp.tile_first + (owned - 1) * cp.tile_stride;
-			if (owned > 0 && last_tile == tiles_total - 1) count -= tiles_total * cp.tile_pixels - frame; // clipped last tile
-		}
-		if (cp.tile_pixels == 0 && offset + count > frame) return fail(ctx, RT_ERROR_OUT_OF_RANGE, "rt_render_sample: pixel range [%d,%d) exceeds the %d pixel frame", offset, offset + count, frame);
 		ctx->time_this_sample = ctx->launch_timing;
-		return stream_submit(ctx, sample_index, sample_count, offset, count);
+		return stream_submit(ctx, sample_index, sample_count, range_offset, range_count);
 	}
 	bool exclusive = ctx->profiling || ctx->trace_statistics || ctx->defer_filter;
 	int slot_index = exclusive ? 0 : int(ctx->render_counter++ % unsigned(ctx->samples_in_flight));
-	int s = ensure_slot(ctx, slot_index); if (s) return s;
-	if (ctx->has_material[2] || ctx->has_material[3]) { s = ensure_luts(ctx); if (s) return s; }
+	s = ensure_slot(ctx, slot_index); if (s) return s;
 	SampleSlot & slot = ctx->slots[slot_index];
-	if (size_t(sample_count) * ctx->frame_pixels >= (1u << 30)) return fail(ctx, RT_ERROR_OUT_OF_RANGE, "rt_render_samples: %d samples of a %zu pixel frame exceed the 30-bit path index", sample_count, ctx->frame_pixels);
 	s = ensure_aov_batch(ctx, slot_index, sample_count); if (s) return s;
-	RtParams p = slot_params(ctx, slot, slot_index);
-	p.batch_samples = sample_count;
-	RtParams p_shadow = p; // the shadow launch may be resident together with the next closest-hit launch
-
-	int frame_pixels = p.screen_width * p.screen_height;
-	int range_offset = ctx->pixel_offset;
-	int range_count  = ctx->pixel_count < 0 ? frame_pixels - range_offset : ctx->pixel_count;
-	if (p.tile_pixels > 0) { // tile mode: local pixels 0..count-1 are mapped to this context's tiles by rt_map_pixel
-		int tiles_total = (frame_pixels + p.tile_pixels - 1) / p.tile_pixels;
-		int owned = p.tile_first < tiles_total ? (tiles_total - p.tile_first + p.tile_stride - 1) / p.tile_stride : 0;
-		range_offset = 0;
-		range_count = owned * p.tile_pixels;
-		int last_tile = p.tile_first + (owned - 1) * p.tile_stride;
-		if (owned > 0 && last_tile == tiles_total - 1) range_count -= tiles_total * p.tile_pixels - frame_pixels; // clipped last tile
-	}
-	if (p.tile_pixels == 0 && range_offset + range_count > frame_pixels) return fail(ctx, RT_ERROR_OUT_OF_RANGE, "rt_render_sample: pixel range [%d,%d) exceeds the %d pixel frame", range_offset, range_offset + range_count, frame_pixels);
 	int batch_limit = int(wanted_batch_size(ctx));
 	int batch_size  = range_count < batch_limit ? range_count : batch_limit; // pixels per wavefront batch; each carries sample_count paths
 	s = ensure_queues(ctx, slot_index, size_t(batch_size > 0 ? batch_size : 1) * sample_count); if (s) return s;
-	memcpy(p.trace, slot.trace, sizeof(p.trace)); memcpy(p.material, slot.material, sizeof(p.material)); p.shadow = slot.shadow; // (re)allocated just now
-	p_shadow = p; p_shadow.stack_spill = (uint2 *)slot.spill[1];
+	RtParams p = slot_params(ctx, slot, slot_index);
+	p.batch_samples = sample_count;
+	RtParams p_shadow = p; p_shadow.stack_spill = (uint2 *)slot.spill[1]; // the shadow launch may be resident together with the next closest-hit launch
 
 	ctx->time_this_sample = ctx->launch_timing;
 	hipStream_t st = slot.stream;
@@ -2248,66 +2208,60 @@ int rt_render_samples(rt_context * ctx, int sample_index, int sample_count) {
 		SampleSlot & prev = ctx->slots[ctx->last_slot];
 		void * from[3] = { ctx->last_slot == 0 ? ctx->svgf_buffers[0] : prev.gbuffers[0], ctx->last_slot == 0 ? ctx->svgf_buffers[1] : prev.gbuffers[1], ctx->last_slot == 0 ? ctx->svgf_buffers[2] : prev.gbuffers[2] };
 		void * to[3]   = { p.gbuffer_normal_and_depth, p.gbuffer_mesh_id_and_triangle_id, p.gbuffer_screen_position_prev };
-		const size_t elem[3] = { 16, 8, 8 };
 		if (prev.created) RT_HIP(ctx, hipStreamWaitEvent(st, prev.ev_gbuffers, 0));
-		for (int i = 0; i < 3; i++) if (from[i] && to[i] && from[i] != to[i]) RT_HIP(ctx, hipMemcpyAsync(to[i], from[i], ctx->frame_pixels * elem[i], hipMemcpyDeviceToDevice, st));
+		for (int i = 0; i < 3; i++) if (from[i] && to[i] && from[i] != to[i]) RT_HIP(ctx, hipMemcpyAsync(to[i], from[i], ctx->frame_pixels * gbuffer_pixel_bytes[i], hipMemcpyDeviceToDevice, st));
 	}
 
 	bool trace_shadows = ctx->has_lights && p.config.enable_next_event_estimation && p.lights_total_weight > 0.0f;
 	// Shadow rays of bounce b only feed the frame buffers, so they run on the side stream while the
 	// main chain traces bounce b+1; they are joined before the next kernel that touches the frame
 	// buffers (sort: sky / emissive hits), which keeps the order of the float additions per pixel.
-	bool overlap = trace_shadows && ctx->overlap_shadows && !ctx->profiling && !ctx->trace_statistics;
+	bool overlap = trace_shadows && !ctx->profiling && !ctx->trace_statistics;
 
 	// generate -> (trace, sort, shade, shadow) x bounces for every batch of the range, on st (+ side)
-	auto submit_wavefront = [&]() -> int {
-		RT_HIP(ctx, hipMemsetAsync(slot.counter_totals, 0, 6 * RT_MAX_BOUNCES * sizeof(int), st));
-		if (ctx->trace_statistics) RT_HIP(ctx, hipMemsetAsync(ctx->trace_stats, 0, 10 * sizeof(unsigned long long), st));
-		int pixels_left = range_count;
-		bool shadow_pending = false;
-		while (pixels_left > 0) {
-			int pixel_offset = range_offset + (range_count - pixels_left);
-			int pixel_count  = batch_size < pixels_left ? batch_size : pixels_left;
+	RT_HIP(ctx, hipMemsetAsync(slot.counter_totals, 0, 6 * RT_MAX_BOUNCES * sizeof(int), st));
+	if (ctx->trace_statistics) RT_HIP(ctx, hipMemsetAsync(ctx->trace_stats, 0, 10 * sizeof(unsigned long long), st));
+	int pixels_left = range_count;
+	bool shadow_pending = false;
+	while (pixels_left > 0) {
+		int pixel_offset = range_offset + (range_count - pixels_left);
+		int pixel_count  = batch_size < pixels_left ? batch_size : pixels_left;
 
-			if (shadow_pending) { RT_HIP(ctx, hipStreamWaitEvent(st, slot.ev_shadowed, 0)); shadow_pending = false; } // the previous batch's queues are reused
-			RT_HIP(ctx, hipMemsetAsync(slot.sizes, 0, sizeof(RtBufferSizes), st));
-			RT_HIP(ctx, hipMemsetAsync(slot.ray_cursors, 0, RT_RAY_CURSOR_BYTES, st));
-			stage_mark(ctx, STAGE_GENERATE, st);
-			rt_launch_generate(p, sample_index, pixel_offset, pixel_count, st);
+		if (shadow_pending) { RT_HIP(ctx, hipStreamWaitEvent(st, slot.ev_shadowed, 0)); shadow_pending = false; } // the previous batch's queues are reused
+		RT_HIP(ctx, hipMemsetAsync(slot.sizes, 0, sizeof(RtBufferSizes), st));
+		RT_HIP(ctx, hipMemsetAsync(slot.ray_cursors, 0, RT_RAY_CURSOR_BYTES, st));
+		stage_mark(ctx, STAGE_GENERATE, st);
+		rt_launch_generate(p, sample_index, pixel_offset, pixel_count, st);
 
-			for (int bounce = 0; bounce < p.config.num_bounces; bounce++) {
-				stage_mark(ctx, STAGE_TRACE, st);
-				if (ctx->trace_statistics) rt_launch_trace_counting(p, bounce, ctx->trace_stats, st);
-				else { span_mark(ctx, SPAN_TRACE, st); rt_launch_trace(p, bounce, st); span_mark(ctx, SPAN_TRACE, st); }
-				if (shadow_pending) { RT_HIP(ctx, hipStreamWaitEvent(st, slot.ev_shadowed, 0)); shadow_pending = false; }
-				stage_mark(ctx, STAGE_SORT, st);
-				rt_launch_sort(p, bounce, sample_index, st);
-				stage_mark(ctx, STAGE_SHADE, st);
-				for (int m = 0; m < 4; m++) if (ctx->has_material[m]) rt_launch_material(p, m, bounce, sample_index, st);
-				if (svgf && bounce == 0 && pixels_left <= batch_size) RT_HIP(ctx, hipEventRecord(slot.ev_gbuffers, st)); // last pixel batch: the g-buffers of this frame are complete
-				if (trace_shadows) {
-					stage_mark(ctx, STAGE_SHADOW, st);
-					if (ctx->trace_statistics) rt_launch_trace_shadow_counting(p, bounce, ctx->trace_stats, st);
-					else if (!overlap) rt_launch_trace_shadow(p, bounce, st);
-					else {
-						RT_HIP(ctx, hipEventRecord(slot.ev_shaded, st));
-						RT_HIP(ctx, hipStreamWaitEvent(slot.side, slot.ev_shaded, 0));
-						span_mark(ctx, SPAN_SHADOW, slot.side);
-						rt_launch_trace_shadow(p_shadow, bounce, slot.side);
-						span_mark(ctx, SPAN_SHADOW, slot.side);
-						RT_HIP(ctx, hipEventRecord(slot.ev_shadowed, slot.side));
-						shadow_pending = true;
-					}
+		for (int bounce = 0; bounce < p.config.num_bounces; bounce++) {
+			stage_mark(ctx, STAGE_TRACE, st);
+			if (ctx->trace_statistics) rt_launch_trace_counting(p, bounce, ctx->trace_stats, st);
+			else { span_mark(ctx, SPAN_TRACE, st); rt_launch_trace(p, bounce, st); span_mark(ctx, SPAN_TRACE, st); }
+			if (shadow_pending) { RT_HIP(ctx, hipStreamWaitEvent(st, slot.ev_shadowed, 0)); shadow_pending = false; }
+			stage_mark(ctx, STAGE_SORT, st);
+			rt_launch_sort(p, bounce, sample_index, st);
+			stage_mark(ctx, STAGE_SHADE, st);
+			for (int m = 0; m < 4; m++) if (ctx->has_material[m]) rt_launch_material(p, m, bounce, sample_index, st);
+			if (svgf && bounce == 0 && pixels_left <= batch_size) RT_HIP(ctx, hipEventRecord(slot.ev_gbuffers, st)); // last pixel batch: the g-buffers of this frame are complete
+			if (trace_shadows) {
+				stage_mark(ctx, STAGE_SHADOW, st);
+				if (ctx->trace_statistics) rt_launch_trace_shadow_counting(p, bounce, ctx->trace_stats, st);
+				else if (!overlap) rt_launch_trace_shadow(p, bounce, st);
+				else {
+					RT_HIP(ctx, hipEventRecord(slot.ev_shaded, st));
+					RT_HIP(ctx, hipStreamWaitEvent(slot.side, slot.ev_shaded, 0));
+					span_mark(ctx, SPAN_SHADOW, slot.side);
+					rt_launch_trace_shadow(p_shadow, bounce, slot.side);
+					span_mark(ctx, SPAN_SHADOW, slot.side);
+					RT_HIP(ctx, hipEventRecord(slot.ev_shadowed, slot.side));
+					shadow_pending = true;
 				}
 			}
-			hipLaunchKernelGGL(kernel_accumulate_counters, dim3(1), dim3(RT_MAX_BOUNCES), 0, st, slot.sizes, slot.counter_totals);
-			pixels_left -= batch_size;
 		}
-		if (shadow_pending) RT_HIP(ctx, hipStreamWaitEvent(st, slot.ev_shadowed, 0));
-		return RT_OK;
-	};
-
-	{ int status = submit_wavefront(); if (status) return status; }
+		hipLaunchKernelGGL(kernel_accumulate_counters, dim3(1), dim3(RT_MAX_BOUNCES), 0, st, slot.sizes, slot.counter_totals);
+		pixels_left -= batch_size;
+	}
+	if (shadow_pending) RT_HIP(ctx, hipStreamWaitEvent(st, slot.ev_shadowed, 0));
 
 	// The accumulate step folds this sample into the shared accumulators: strictly in sample order.
 	RT_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_main, 0));
@@ -2321,14 +2275,7 @@ int rt_render_samples(rt_context * ctx, int sample_index, int sample_count) {
 
 	// aovs_clear_to_zero (Integrator.cpp:379-385)
 	if (!deferred) for (int i = 0; i < RT_AOV_COUNT; i++) if (p.aovs[i].framebuffer) RT_HIP(ctx, hipMemsetAsync(p.aovs[i].framebuffer, 0, ctx->frame_pixels * 16 * sample_count, st));
-
-	RT_HIP(ctx, hipMemcpyAsync(slot.pinned_counters, slot.counter_totals, 6 * RT_MAX_BOUNCES * sizeof(int), hipMemcpyDeviceToHost, st));
-	RT_HIP(ctx, hipEventRecord(slot.ev_frame_end, st));
-	RT_HIP(ctx, hipEventRecord(slot.ev_done, st));
-	{ int status = mark_scene_versions_in_use(ctx, slot_index, st); if (status) return status; }
-	ctx->last_slot = slot_index;
-	RT_HIP(ctx, hipGetLastError());
-	return RT_OK;
+	return finish_slot_submission(ctx, slot_index);
 }
 
 // Ambient-occlusion integrator (AO::render, Integrators/AO.cpp:148-200): generate -> trace ->
@@ -2338,20 +2285,13 @@ int rt_render_ao_sample(rt_context * ctx, int sample_index, float ao_radius) {
 	RT_REQUIRE(ctx, ctx, "rt_render_ao_sample: NULL context");
 	RT_REQUIRE(ctx, ao_radius > 0.0f, "rt_render_ao_sample: ao_radius must be positive");
 	(void)hipSetDevice(ctx->device);
-	const RtParams & base = ctx->params;
-	if (!base.triangles || !bvh_nodes_present(ctx)) return fail(ctx, RT_ERROR_NOT_READY, "rt_render_ao_sample: geometry not uploaded");
-	if (!base.mesh_bvh_root_indices)           return fail(ctx, RT_ERROR_NOT_READY, "rt_render_ao_sample: instances not uploaded");
-	if (!base.pmj_samples || !base.blue_noise) return fail(ctx, RT_ERROR_NOT_READY, "rt_render_ao_sample: RNG tables not uploaded");
-	if (ctx->frame_pixels == 0)                return fail(ctx, RT_ERROR_NOT_READY, "rt_render_ao_sample: rt_resize was not called");
-	if (base.tile_pixels > 0)                  return fail(ctx, RT_ERROR_INVALID_ARG, "rt_render_ao_sample: tile mode is not supported, use rt_set_pixel_range");
-
-	int frame_pixels = base.screen_width * base.screen_height;
-	int range_offset = ctx->pixel_offset;
-	int range_count  = ctx->pixel_count < 0 ? frame_pixels - range_offset : ctx->pixel_count;
-	if (range_offset + range_count > frame_pixels) return fail(ctx, RT_ERROR_OUT_OF_RANGE, "rt_render_ao_sample: pixel range [%d,%d) exceeds the %d pixel frame", range_offset, range_offset + range_count, frame_pixels);
+	int s = check_ready(ctx, "rt_render_ao_sample", NEED_SCENE | NEED_RNG | NEED_FRAME); if (s) return s;
+	if (ctx->params.tile_pixels > 0) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_render_ao_sample: tile mode is not supported, use rt_set_pixel_range");
+	int range_offset = 0, range_count = 0;
+	s = resolve_pixel_range(ctx, "rt_render_ao_sample", &range_offset, &range_count); if (s) return s;
 
 	if (ctx->last_render_merged) { RT_HIP(ctx, quiesce(ctx)); ctx->last_render_merged = false; } // this integrator runs on slot 0
-	int s = ensure_slot(ctx, 0); if (s) return s;
+	s = ensure_slot(ctx, 0); if (s) return s;
 	int batch_limit = int(wanted_batch_size(ctx));
 	int batch_size  = range_count < batch_limit ? range_count : batch_limit;
 	s = ensure_queues(ctx, 0, size_t(batch_size > 0 ? batch_size : 1)); if (s) return s;
@@ -2385,13 +2325,7 @@ int rt_render_ao_sample(rt_context * ctx, int sample_index, float ao_radius) {
 	p_acc.aovs[RT_AOV_ALBEDO].framebuffer = nullptr;
 	rt_launch_accumulate(p_acc, float(sample_index), range_offset, range_count, st);
 	for (int i = 0; i < RT_AOV_COUNT; i++) if (p.aovs[i].framebuffer) RT_HIP(ctx, hipMemsetAsync(p.aovs[i].framebuffer, 0, ctx->frame_pixels * 16, st));
-	RT_HIP(ctx, hipMemcpyAsync(slot.pinned_counters, slot.counter_totals, 6 * RT_MAX_BOUNCES * sizeof(int), hipMemcpyDeviceToHost, st));
-	RT_HIP(ctx, hipEventRecord(slot.ev_frame_end, st));
-	RT_HIP(ctx, hipEventRecord(slot.ev_done, st));
-	{ int status = mark_scene_versions_in_use(ctx, 0, st); if (status) return status; }
-	ctx->last_slot = 0;
-	RT_HIP(ctx, hipGetLastError());
-	return RT_OK;
+	return finish_slot_submission(ctx, 0);
 }
 
 int rt_set_pixel_query(rt_context * ctx, int pixel_index) {
@@ -2551,29 +2485,18 @@ struct TempBuffers {
 	}
 };
 
+} // extern "C"
 
-
-int rt_trace_rays(rt_context * ctx, const float * ox, const float * oy, const float * oz,
-                  const float * dx, const float * dy, const float * dz, size_t ray_count,
-                  uint32_t * hits, int repeat, float * out_ms) {
-	RT_REQUIRE(ctx, ctx && ox && oy && oz && dx && dy && dz && hits, "rt_trace_rays: NULL argument");
-	(void)hipSetDevice(ctx->device);
-	RT_HIP(ctx, quiesce(ctx)); // slot 0's spill area and cursors are borrowed
-	if (!ctx->params.triangles || !bvh_nodes_present(ctx) || !ctx->params.mesh_bvh_root_indices) return fail(ctx, RT_ERROR_NOT_READY, "rt_trace_rays: geometry / instances not uploaded");
-	TempBuffers tmp(ctx);
-	size_t bytes = ray_count * 4;
-	RtVec3SoA o = { (float *)tmp.get(bytes, ox), (float *)tmp.get(bytes, oy), (float *)tmp.get(bytes, oz) };
-	RtVec3SoA d = { (float *)tmp.get(bytes, dx), (float *)tmp.get(bytes, dy), (float *)tmp.get(bytes, dz) };
-	uint4 * dev_hits = (uint4 *)tmp.get(ray_count * 16, nullptr);
-	if (!o.x || !o.y || !o.z || !d.x || !d.y || !d.z || !dev_hits) return fail(ctx, RT_ERROR_HIP, "rt_trace_rays: device allocation failed");
-
+// The repeat / timing loop of the explicit-ray entry points around `launch` (one traversal on the main stream):
+// *out_ms gets the mean time of `repeat` launches.
+template<typename Launch> static int time_explicit_launches(rt_context * ctx, int repeat, float * out_ms, Launch && launch) {
 	if (repeat < 1) repeat = 1;
 	hipEvent_t e0, e1; RT_HIP(ctx, hipEventCreate(&e0)); RT_HIP(ctx, hipEventCreate(&e1));
 	float total = 0.0f;
 	for (int r = 0; r < repeat; r++) {
 		RT_HIP(ctx, hipMemsetAsync(ctx->explicit_retired, 0, 8 * sizeof(int), ctx->stream));
 		RT_HIP(ctx, hipEventRecord(e0, ctx->stream));
-		rt_launch_trace_explicit(ctx->params, o, d, dev_hits, int(ray_count), ctx->explicit_retired, ctx->stream);
+		launch();
 		RT_HIP(ctx, hipEventRecord(e1, ctx->stream));
 		RT_HIP(ctx, quiesce(ctx));
 		float ms = 0.0f; RT_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
@@ -2582,6 +2505,26 @@ int rt_trace_rays(rt_context * ctx, const float * ox, const float * oy, const fl
 	(void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
 	RT_HIP(ctx, hipGetLastError());
 	if (out_ms) *out_ms = total / float(repeat);
+	return RT_OK;
+}
+
+extern "C" {
+
+int rt_trace_rays(rt_context * ctx, const float * ox, const float * oy, const float * oz,
+                  const float * dx, const float * dy, const float * dz, size_t ray_count,
+                  uint32_t * hits, int repeat, float * out_ms) {
+	RT_REQUIRE(ctx, ctx && ox && oy && oz && dx && dy && dz && hits, "rt_trace_rays: NULL argument");
+	(void)hipSetDevice(ctx->device);
+	RT_HIP(ctx, quiesce(ctx)); // slot 0's spill area and cursors are borrowed
+	int s = check_ready(ctx, "rt_trace_rays", NEED_SCENE_JOINT); if (s) return s;
+	TempBuffers tmp(ctx);
+	size_t bytes = ray_count * 4;
+	RtVec3SoA o = { (float *)tmp.get(bytes, ox), (float *)tmp.get(bytes, oy), (float *)tmp.get(bytes, oz) };
+	RtVec3SoA d = { (float *)tmp.get(bytes, dx), (float *)tmp.get(bytes, dy), (float *)tmp.get(bytes, dz) };
+	uint4 * dev_hits = (uint4 *)tmp.get(ray_count * 16, nullptr);
+	if (!o.x || !o.y || !o.z || !d.x || !d.y || !d.z || !dev_hits) return fail(ctx, RT_ERROR_HIP, "rt_trace_rays: device allocation failed");
+
+	s = time_explicit_launches(ctx, repeat, out_ms, [&] { rt_launch_trace_explicit(ctx->params, o, d, dev_hits, int(ray_count), ctx->explicit_retired, ctx->stream); }); if (s) return s;
 	RT_HIP(ctx, hipMemcpy(hits, dev_hits, ray_count * 16, hipMemcpyDeviceToHost));
 	return RT_OK;
 }
@@ -2592,7 +2535,7 @@ int rt_trace_shadow_rays(rt_context * ctx, const float * ox, const float * oy, c
 	RT_REQUIRE(ctx, ctx && ox && oy && oz && dx && dy && dz && max_distance && occluded, "rt_trace_shadow_rays: NULL argument");
 	(void)hipSetDevice(ctx->device);
 	RT_HIP(ctx, quiesce(ctx)); // slot 0's spill area and cursors are borrowed
-	if (!ctx->params.triangles || !bvh_nodes_present(ctx) || !ctx->params.mesh_bvh_root_indices) return fail(ctx, RT_ERROR_NOT_READY, "rt_trace_shadow_rays: geometry / instances not uploaded");
+	int s = check_ready(ctx, "rt_trace_shadow_rays", NEED_SCENE_JOINT); if (s) return s;
 	TempBuffers tmp(ctx);
 	size_t bytes = ray_count * 4;
 	RtVec3SoA o = { (float *)tmp.get(bytes, ox), (float *)tmp.get(bytes, oy), (float *)tmp.get(bytes, oz) };
@@ -2601,21 +2544,7 @@ int rt_trace_shadow_rays(rt_context * ctx, const float * ox, const float * oy, c
 	uint8_t * dev_occ = (uint8_t *)tmp.get(ray_count, nullptr);
 	if (!o.x || !o.y || !o.z || !d.x || !d.y || !d.z || !dev_max || !dev_occ) return fail(ctx, RT_ERROR_HIP, "rt_trace_shadow_rays: device allocation failed");
 
-	if (repeat < 1) repeat = 1;
-	hipEvent_t e0, e1; RT_HIP(ctx, hipEventCreate(&e0)); RT_HIP(ctx, hipEventCreate(&e1));
-	float total = 0.0f;
-	for (int r = 0; r < repeat; r++) {
-		RT_HIP(ctx, hipMemsetAsync(ctx->explicit_retired, 0, 8 * sizeof(int), ctx->stream));
-		RT_HIP(ctx, hipEventRecord(e0, ctx->stream));
-		rt_launch_trace_shadow_explicit(ctx->params, o, d, dev_max, dev_occ, int(ray_count), ctx->explicit_retired, ctx->stream);
-		RT_HIP(ctx, hipEventRecord(e1, ctx->stream));
-		RT_HIP(ctx, quiesce(ctx));
-		float ms = 0.0f; RT_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
-		total += ms;
-	}
-	(void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-	RT_HIP(ctx, hipGetLastError());
-	if (out_ms) *out_ms = total / float(repeat);
+	s = time_explicit_launches(ctx, repeat, out_ms, [&] { rt_launch_trace_shadow_explicit(ctx->params, o, d, dev_max, dev_occ, int(ray_count), ctx->explicit_retired, ctx->stream); }); if (s) return s;
 	RT_HIP(ctx, hipMemcpy(occluded, dev_occ, ray_count, hipMemcpyDeviceToHost));
 	return RT_OK;
 }
@@ -2628,7 +2557,7 @@ int rt_generate_rays(rt_context * ctx, int sample_index, int pixel_offset, int p
 	if (!ctx->params.pmj_samples || ctx->frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_generate_rays: RNG tables not uploaded or rt_resize not called");
 	RT_HIP(ctx, quiesce(ctx)); // slot 0's queues are borrowed
 	int s = ensure_queues(ctx); if (s) return s;
-	if (size_t(pixel_count) > ctx->slots[0].queue_capacity) return fail(ctx, RT_ERROR_OUT_OF_RANGE, "rt_generate_rays: pixel_count %d exceeds the queue capacity %zu", pixel_count, ctx->slots[0].queue_capacity);
+	if (size_t(pixel_count) > ctx->slots[0].queues.capacity) return fail(ctx, RT_ERROR_OUT_OF_RANGE, "rt_generate_rays: pixel_count %d exceeds the queue capacity %zu", pixel_count, ctx->slots[0].queues.capacity);
 	rt_launch_generate(ctx->params, sample_index, pixel_offset, pixel_count, ctx->stream);
 	RT_HIP(ctx, hipGetLastError());
 	RT_HIP(ctx, quiesce(ctx));
