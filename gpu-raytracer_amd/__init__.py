@@ -70,8 +70,8 @@ def device_lib():
         if not os.path.exists(DEVICE_LIB_PATH):
             raise DeviceLibraryMissing("%s is missing -- run `python __graft_entry__.py` (build()) first" % DEVICE_LIB_PATH)
         lib = ctypes.CDLL(DEVICE_LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        if hasattr(lib, "rt_abi_version") and lib.rt_abi_version() != 8:
-            raise DeviceLibraryMissing("%s has ABI version %d, this front end was written for 8 -- rebuild (python __graft_entry__.py)" % (DEVICE_LIB_PATH, lib.rt_abi_version()))
+        if hasattr(lib, "rt_abi_version") and lib.rt_abi_version() != 9:
+            raise DeviceLibraryMissing("%s has ABI version %d, this front end was written for 9 -- rebuild (python __graft_entry__.py)" % (DEVICE_LIB_PATH, lib.rt_abi_version()))
         lib.rt_last_error.restype = c_char_p
         lib.rt_last_error.argtypes = [c_void_p]
         lib.rt_version.restype = c_char_p
@@ -82,6 +82,9 @@ def device_lib():
         lib.rt_trace_shadow_rays.argtypes = [c_void_p] + [c_void_p] * 7 + [c_size_t, c_void_p, c_int, POINTER(c_float)]
         lib.rt_generate_rays.argtypes = [c_void_p, c_int, c_int, c_int] + [c_void_p] * 7
         lib.rt_random_samples.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_uint32, c_uint32, c_void_p]
+        lib.rt_sample_texture.argtypes = [c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]
+        lib.rt_sample_table.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]
+        lib.rt_sample_sky.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
         lib.rt_measure_stream_bandwidth.argtypes = [c_void_p, c_size_t, c_int, POINTER(c_float)]
         lib.rt_set_profiling.argtypes = [c_void_p, c_int]
         lib.rt_set_samples_in_flight.argtypes = [c_void_p, c_int]
@@ -838,6 +841,36 @@ def random_samples(ctx, dimension, pixel_indices, bounce, sample_index):
     px = np.ascontiguousarray(pixel_indices, dtype=np.uint32)
     out = np.zeros((px.size, 2), np.float32)
     _dev_check(ctx, device_lib().rt_random_samples(ctx, dimension, px.ctypes.data, px.size, bounce, sample_index, out.ctypes.data))
+    return out
+
+
+def sample_texture(ctx, texture_index, filter, args):
+    """rt_sample_texture: args is (N, 8) {s, t, lod, dx.x, dx.y, dy.x, dy.y, pad}; filter 0 = level 0, 1 = lod, 2 = gradients.
+    Returns (N, 4) float32 RGBA."""
+    a = _f32(args).reshape(-1, 8)
+    out = np.zeros((a.shape[0], 4), np.float32)
+    _dev_check(ctx, device_lib().rt_sample_texture(ctx, texture_index, filter, a.ctypes.data, a.shape[0], out.ctypes.data))
+    return out
+
+
+def sample_table(ctx, table, coords):
+    """rt_sample_table: lut_get_1d / _2d / _3d on `table`, a 1-, 2- or 3-d array indexed [z][y][x]; coords is (N, dims).
+    Returns (N,) float32."""
+    t = _f32(table)
+    dims = t.ndim
+    shape = t.shape[::-1] + (1,) * (3 - dims)   # nx, ny, nz
+    c = np.zeros((np.asarray(coords).reshape(-1, dims).shape[0], 3), np.float32)
+    c[:, :dims] = np.asarray(coords, np.float32).reshape(-1, dims)
+    out = np.zeros(c.shape[0], np.float32)
+    _dev_check(ctx, device_lib().rt_sample_table(ctx, t.ctypes.data, shape[0], shape[1], shape[2], dims, c.ctypes.data, c.shape[0], out.ctypes.data))
+    return out
+
+
+def sample_sky(ctx, directions):
+    """rt_sample_sky: sample_sky on the context's sky for (N, 3) unit directions. Returns (N, 3) float32."""
+    d = _f32(directions).reshape(-1, 3)
+    out = np.zeros((d.shape[0], 3), np.float32)
+    _dev_check(ctx, device_lib().rt_sample_sky(ctx, d.ctypes.data, d.shape[0], out.ctypes.data))
     return out
 
 

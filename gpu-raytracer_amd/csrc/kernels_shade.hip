@@ -199,6 +199,35 @@ __global__ void kernel_random(RtParams p, int dimension, const unsigned * pixel_
 	out[i] = make_float2(r.x, r.y);
 }
 
+// rt_sample_texture / rt_sample_table / rt_sample_sky: the software texture unit on caller-supplied coordinates, through the very
+// functions the shade kernels call. args: 8 floats per probe {s, t, lod, dx.x, dx.y, dy.x, dy.y, pad}; filter 0 texture_get,
+// 1 texture_get_lod, 2 texture_get_grad. COMPRESSED is picked from p.textures_compressed as rt_launch_material does.
+template<bool COMPRESSED>
+__global__ void kernel_sample_texture(RtParams p, int texture_index, int filter, const float * args, int count, float4 * out) {
+	int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= count) return;
+	const RtTexture tex = p.textures[texture_index];
+	const float * a = args + size_t(i) * 8;
+	f4 c = filter == 0 ? texture_get<COMPRESSED>(tex, a[0], a[1])
+	     : filter == 1 ? texture_get_lod<COMPRESSED>(tex, a[0], a[1], a[2])
+	     :               texture_get_grad<COMPRESSED>(tex, a[0], a[1], mk2(a[3], a[4]), mk2(a[5], a[6]));
+	out[i] = make_float4(c.x, c.y, c.z, c.w);
+}
+// dims 1..3: lut_get_1d / _2d / _3d; coords: 3 floats per probe {s, t, r}
+__global__ void kernel_sample_table(const float * table, int nx, int ny, int nz, int dims, const float * coords, int count, float * out) {
+	int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= count) return;
+	const float * c = coords + size_t(i) * 3;
+	out[i] = dims == 1 ? lut_get_1d(table, nx, c[0]) : dims == 2 ? lut_get_2d(table, nx, ny, c[0], c[1]) : lut_get_3d(table, nx, ny, nz, c[0], c[1], c[2]);
+}
+__global__ void kernel_sample_sky(RtParams p, const float * directions, int count, float * out) {
+	int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= count) return;
+	const float * d = directions + size_t(i) * 3;
+	f3 c = sample_sky(p, mk3(d[0], d[1], d[2]));
+	out[3 * size_t(i)] = c.x; out[3 * size_t(i) + 1] = c.y; out[3 * size_t(i) + 2] = c.z;
+}
+
 // ---- kernel_sort -----------------------------------------------------------------------------------
 
 // Returns true if the path terminates (Pathtracer.cu:199-218)
@@ -1246,4 +1275,14 @@ void rt_launch_ambient_occlusion(const RtParams & p, int sample_index, float ao_
 }
 void rt_launch_random(const RtParams & p, int dimension, const unsigned * pixel_indices, int count, unsigned bounce, unsigned sample_index, float2 * out, hipStream_t stream) {
 	hipLaunchKernelGGL(kernel_random, dim3((count + 255) / 256), dim3(256), 0, stream, p, dimension, pixel_indices, count, bounce, sample_index, out);
+}
+void rt_launch_sample_texture(const RtParams & p, int texture_index, int filter, const float * args, int count, float4 * out, hipStream_t stream) {
+	if (p.textures_compressed) hipLaunchKernelGGL(kernel_sample_texture<true>, dim3((count + 255) / 256), dim3(256), 0, stream, p, texture_index, filter, args, count, out);
+	else hipLaunchKernelGGL(kernel_sample_texture<false>, dim3((count + 255) / 256), dim3(256), 0, stream, p, texture_index, filter, args, count, out);
+}
+void rt_launch_sample_table(const float * table, int nx, int ny, int nz, int dims, const float * coords, int count, float * out, hipStream_t stream) {
+	hipLaunchKernelGGL(kernel_sample_table, dim3((count + 255) / 256), dim3(256), 0, stream, table, nx, ny, nz, dims, coords, count, out);
+}
+void rt_launch_sample_sky(const RtParams & p, const float * directions, int count, float * out, hipStream_t stream) {
+	hipLaunchKernelGGL(kernel_sample_sky, dim3((count + 255) / 256), dim3(256), 0, stream, p, directions, count, out);
 }

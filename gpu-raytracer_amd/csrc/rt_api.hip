@@ -2588,6 +2588,62 @@ int rt_random_samples(rt_context * ctx, int dimension, const uint32_t * pixel_in
 	return RT_OK;
 }
 
+int rt_sample_texture(rt_context * ctx, int texture_index, int filter, const float * args, size_t count, float * out_rgba) {
+	RT_REQUIRE(ctx, ctx && args && out_rgba, "rt_sample_texture: NULL argument");
+	RT_REQUIRE(ctx, texture_index >= 0 && size_t(texture_index) < ctx->texture_data.size(), "rt_sample_texture: texture index out of range");
+	RT_REQUIRE(ctx, filter >= 0 && filter <= 2, "rt_sample_texture: filter must be 0 (level 0), 1 (lod) or 2 (gradients)");
+	RT_REQUIRE(ctx, count <= size_t(1) << 28, "rt_sample_texture: more than 2^28 probes");
+	(void)hipSetDevice(ctx->device);
+	if (count == 0) return RT_OK;
+	TempBuffers tmp(ctx);
+	float * dev_args = (float *)tmp.get(count * 32, args);
+	float4 * dev_out = (float4 *)tmp.get(count * 16, nullptr);
+	if (!dev_args || !dev_out) return fail(ctx, RT_ERROR_HIP, "rt_sample_texture: device allocation failed");
+	rt_launch_sample_texture(ctx->params, texture_index, filter, dev_args, int(count), dev_out, ctx->stream);
+	RT_HIP(ctx, hipGetLastError());
+	RT_HIP(ctx, quiesce(ctx));
+	RT_HIP(ctx, hipMemcpy(out_rgba, dev_out, count * 16, hipMemcpyDeviceToHost));
+	return RT_OK;
+}
+
+int rt_sample_table(rt_context * ctx, const float * table, int nx, int ny, int nz, int dims, const float * coords, size_t count, float * out) {
+	RT_REQUIRE(ctx, ctx && table && coords && out, "rt_sample_table: NULL argument");
+	RT_REQUIRE(ctx, dims >= 1 && dims <= 3, "rt_sample_table: dims must be 1, 2 or 3");
+	RT_REQUIRE(ctx, nx >= 1 && nx <= 65536 && (dims < 2 || (ny >= 1 && ny <= 65536)) && (dims < 3 || (nz >= 1 && nz <= 65536)), "rt_sample_table: a table side is outside [1, 65536]");
+	RT_REQUIRE(ctx, count <= size_t(1) << 28, "rt_sample_table: more than 2^28 probes");
+	size_t entries = size_t(nx) * (dims >= 2 ? size_t(ny) : 1) * (dims >= 3 ? size_t(nz) : 1);
+	RT_REQUIRE(ctx, entries <= size_t(1) << 28, "rt_sample_table: more than 2^28 table entries");
+	(void)hipSetDevice(ctx->device);
+	if (count == 0) return RT_OK;
+	TempBuffers tmp(ctx);
+	float * dev_table = (float *)tmp.get(entries * 4, table);
+	float * dev_coords = (float *)tmp.get(count * 12, coords);
+	float * dev_out = (float *)tmp.get(count * 4, nullptr);
+	if (!dev_table || !dev_coords || !dev_out) return fail(ctx, RT_ERROR_HIP, "rt_sample_table: device allocation failed");
+	rt_launch_sample_table(dev_table, nx, dims >= 2 ? ny : 1, dims >= 3 ? nz : 1, dims, dev_coords, int(count), dev_out, ctx->stream);
+	RT_HIP(ctx, hipGetLastError());
+	RT_HIP(ctx, quiesce(ctx));
+	RT_HIP(ctx, hipMemcpy(out, dev_out, count * 4, hipMemcpyDeviceToHost));
+	return RT_OK;
+}
+
+int rt_sample_sky(rt_context * ctx, const float * directions, size_t count, float * out_rgb) {
+	RT_REQUIRE(ctx, ctx && directions && out_rgb, "rt_sample_sky: NULL argument");
+	RT_REQUIRE(ctx, ctx->params.sky, "rt_sample_sky: no sky uploaded (rt_set_sky)");
+	RT_REQUIRE(ctx, count <= size_t(1) << 28, "rt_sample_sky: more than 2^28 probes");
+	(void)hipSetDevice(ctx->device);
+	if (count == 0) return RT_OK;
+	TempBuffers tmp(ctx);
+	float * dev_dirs = (float *)tmp.get(count * 12, directions);
+	float * dev_out = (float *)tmp.get(count * 12, nullptr);
+	if (!dev_dirs || !dev_out) return fail(ctx, RT_ERROR_HIP, "rt_sample_sky: device allocation failed");
+	rt_launch_sample_sky(ctx->params, dev_dirs, int(count), dev_out, ctx->stream);
+	RT_HIP(ctx, hipGetLastError());
+	RT_HIP(ctx, quiesce(ctx));
+	RT_HIP(ctx, hipMemcpy(out_rgb, dev_out, count * 12, hipMemcpyDeviceToHost));
+	return RT_OK;
+}
+
 int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps) {
 	RT_REQUIRE(ctx, ctx && out_gbps && bytes >= 1024, "rt_measure_stream_bandwidth: invalid argument");
 	(void)hipSetDevice(ctx->device);

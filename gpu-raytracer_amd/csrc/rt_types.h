@@ -266,6 +266,10 @@ void rt_launch_accumulate_group(const RtParams & p, const RtAccumulateGroup & gr
 // mark(user, k, stream), if given, is called before and after kernel k = 0 reproject, 1 variance, 2 a-trous (each pass), 3 finalize, 4 TAA, 5 TAA finalize
 void rt_launch_svgf_taa(const RtParams & p, int sample_index, hipStream_t stream, void (*mark)(void * user, int svgf_kernel, hipStream_t stream) = nullptr, void * user = nullptr);
 void rt_launch_random(const RtParams & p, int dimension, const unsigned * pixel_indices, int count, unsigned bounce, unsigned sample_index, float2 * out, hipStream_t stream);
+// Test support: the software texture unit on explicit coordinates (rt_sample_texture / rt_sample_table / rt_sample_sky)
+void rt_launch_sample_texture(const RtParams & p, int texture_index, int filter, const float * args, int count, float4 * out, hipStream_t stream);
+void rt_launch_sample_table(const float * table, int nx, int ny, int nz, int dims, const float * coords, int count, float * out, hipStream_t stream);
+void rt_launch_sample_sky(const RtParams & p, const float * directions, int count, float * out, hipStream_t stream);
 void rt_launch_integrate_luts(const RtParams & p, float * dielectric_dir_enter, float * dielectric_dir_leave, float * dielectric_enter, float * dielectric_leave,
                               float * conductor_dir, float * conductor, hipStream_t stream);
 void rt_launch_pack_pixels(const RtParams & p, float4 * dst, int tile_pixels, int tile_first, int tile_stride, int tiles, hipStream_t stream);

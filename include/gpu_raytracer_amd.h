@@ -147,8 +147,9 @@ const char * rt_version(void);
  *      both measured slower than the 80-byte walk on MI355X (profiles/r04_traversal_experiments.txt items 2 and 4) and were off by default;
  *      rt_set_build_boxes added
  *   8  rt_set_skip_behind_hit, rt_get_skip_behind_hit, rt_geometry_fits_flat_engine, rt_update_nodes (additions only)
+ *   9  rt_sample_texture, rt_sample_table, rt_sample_sky (additions only)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
-#define RT_ABI_VERSION 8
+#define RT_ABI_VERSION 9
 int rt_abi_version(void);
 
 /* ---- scene upload ------------------------------------------------------------------- */
@@ -499,6 +500,16 @@ int rt_generate_rays(rt_context * ctx, int sample_index, int pixel_offset, int p
 /* random<Dim>() (CUDA/Sampling.h:44-84) for `count` (pixel_index) values: out = float2 each. */
 int rt_random_samples(rt_context * ctx, int dimension, const uint32_t * pixel_indices, size_t count,
                       uint32_t bounce, uint32_t sample_index, float * out_xy);
+/* The software texture unit (rt_shading.h) on explicit coordinates; synchronous.
+ * rt_sample_texture: texture `texture_index` of the last rt_upload_textures. filter 0 = texture_get (level 0),
+ * 1 = texture_get_lod, 2 = texture_get_grad. args: count x 8 floats {s, t, lod, dx.x, dx.y, dy.x, dy.y, pad}
+ * (filter 0 reads s, t; 1 also lod; 2 the gradients, not lod). out_rgba: count x 4 floats.
+ * rt_sample_table: lut_get_1d / _2d / _3d (dims 1, 2, 3) on a caller-supplied nx [x ny [x nz]] float table,
+ * x fastest. coords: count x 3 floats {s, t, r}, the unused ones ignored. out: count floats.
+ * rt_sample_sky: sample_sky on what rt_set_sky uploaded. directions: count x 3 floats (unit length); out_rgb: count x 3. */
+int rt_sample_texture(rt_context * ctx, int texture_index, int filter, const float * args, size_t count, float * out_rgba);
+int rt_sample_table(rt_context * ctx, const float * table, int nx, int ny, int nz, int dims, const float * coords, size_t count, float * out);
+int rt_sample_sky(rt_context * ctx, const float * directions, size_t count, float * out_rgb);
 /* Streaming-read bandwidth probe used as the measured HBM roofline (GB/s).                 */
 int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps);
 

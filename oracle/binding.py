@@ -110,6 +110,18 @@ def lib():
         l.oracle_integrate_conductor_cells.argtypes = [POINTER(OracleScene), c_int, c_int, c_int, c_void_p, c_int]
         l.oracle_average_dielectric.argtypes = [c_void_p, c_void_p]
         l.oracle_average_conductor.argtypes = [c_void_p, c_void_p]
+        tex_p = POINTER(OracleTexture)
+        l.oracle_tex2d.argtypes = [tex_p, c_float, c_float, c_void_p]
+        l.oracle_tex2d_lod.argtypes = [tex_p, c_float, c_float, c_float, c_void_p]
+        l.oracle_tex2d_grad.argtypes = [tex_p, c_float, c_float, c_void_p, c_void_p, c_void_p]
+        l.oracle_tex2d_batch.argtypes = [tex_p, c_int, c_void_p, c_size_t, c_void_p]
+        for name, n in (("oracle_lut_1d", 1), ("oracle_lut_2d", 2), ("oracle_lut_3d", 3)):
+            getattr(l, name).argtypes = [c_void_p] + [c_int] * n + [c_float] * n
+            getattr(l, name).restype = c_float
+        l.oracle_lut_batch.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]
+        l.oracle_image_bilinear_clamp.argtypes = [c_void_p, c_int, c_int, c_float, c_float, c_void_p]
+        l.oracle_sample_sky.argtypes = [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]
+        l.oracle_sample_sky_batch.argtypes = [c_void_p, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]
         _lib = l
     return _lib
 
@@ -497,6 +509,75 @@ def ref_build_optimized(tris24, sbvh, max_batches):
         out["bvh8_indices"] = np.zeros(r.ref_bvh8_index_count(h), np.int32); r.ref_bvh8_copy_indices(h, out["bvh8_indices"].ctypes.data)
     out["ms_bvh2"] = r.ref_bvh_ms_bvh2(h)
     r.ref_bvh_free(h)
+    return out
+
+
+# ---- the software texture unit (oracle_texture_api.cpp) on explicit coordinates ----------------------
+
+def _texture_struct(texels, width, height, mip_levels):
+    t = OracleTexture()
+    t.texels = texels.ctypes.data; t.width = width; t.height = height; t.mip_levels = mip_levels
+    return t
+
+
+def tex2d(texels, width, height, mip_levels, filter, args):
+    """oracle_tex2d / _lod / _grad (filter 0, 1, 2) on an RGBA8 chain (uint8, levels back to back).
+    args: (N, 8) {s, t, lod, dx.x, dx.y, dy.x, dy.y, pad}. Returns (N, 4) float32."""
+    texels = np.ascontiguousarray(texels, dtype=np.uint8)
+    a = np.ascontiguousarray(args, dtype=np.float32).reshape(-1, 8)
+    out = np.zeros((a.shape[0], 4), np.float32)
+    t = _texture_struct(texels, width, height, mip_levels)
+    lib().oracle_tex2d_batch(byref(t), filter, a.ctypes.data, a.shape[0], out.ctypes.data)
+    return out
+
+
+def tex2d_one(texels, width, height, mip_levels, filter, s, t, lod=0.0, dx=(0.0, 0.0), dy=(0.0, 0.0)):
+    """One probe through the unbatched oracle_tex2d / _lod / _grad."""
+    texels = np.ascontiguousarray(texels, dtype=np.uint8)
+    tex = _texture_struct(texels, width, height, mip_levels)
+    out = (c_float * 4)()
+    if filter == 0:
+        lib().oracle_tex2d(byref(tex), s, t, out)
+    elif filter == 1:
+        lib().oracle_tex2d_lod(byref(tex), s, t, lod, out)
+    else:
+        lib().oracle_tex2d_grad(byref(tex), s, t, (c_float * 2)(*dx), (c_float * 2)(*dy), out)
+    return np.array(out, np.float32)
+
+
+def lut(table, coords):
+    """oracle_lut_1d / _2d / _3d on `table` (1-, 2- or 3-d, indexed [z][y][x]); coords (N, dims). Returns (N,) float32."""
+    t = np.ascontiguousarray(table, dtype=np.float32)
+    dims = t.ndim
+    nx, ny, nz = t.shape[::-1] + (1,) * (3 - dims)
+    c = np.zeros((np.asarray(coords).reshape(-1, dims).shape[0], 3), np.float32)
+    c[:, :dims] = np.asarray(coords, np.float32).reshape(-1, dims)
+    out = np.zeros(c.shape[0], np.float32)
+    lib().oracle_lut_batch(t.ctypes.data, nx, ny, nz, dims, c.ctypes.data, c.shape[0], out.ctypes.data)
+    return out
+
+
+def lut_one(table, *coords):
+    """One probe through the unbatched oracle_lut_1d / _2d / _3d."""
+    t = np.ascontiguousarray(table, dtype=np.float32)
+    sizes = t.shape[::-1]
+    return float(getattr(lib(), "oracle_lut_%dd" % t.ndim)(t.ctypes.data, *sizes, *coords))
+
+
+def image_bilinear_clamp(rgba, u, v):
+    """oracle_image_bilinear_clamp: clamp-addressed bilinear fetch of an (h, w, 4) float image at (u, v)."""
+    img = np.ascontiguousarray(rgba, dtype=np.float32)
+    out = (c_float * 4)()
+    lib().oracle_image_bilinear_clamp(img.ctypes.data, img.shape[1], img.shape[0], u, v, out)
+    return np.array(out, np.float32)
+
+
+def sample_sky(rgba, scale, directions):
+    """oracle_sample_sky (Sky.h:7-16) on an (h, w, 4) float image for (N, 3) directions. Returns (N, 3) float32."""
+    img = np.ascontiguousarray(rgba, dtype=np.float32)
+    d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros((d.shape[0], 3), np.float32)
+    lib().oracle_sample_sky_batch(img.ctypes.data, img.shape[1], img.shape[0], scale, d.ctypes.data, d.shape[0], out.ctypes.data)
     return out
 
 
