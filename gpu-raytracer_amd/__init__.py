@@ -70,8 +70,8 @@ def device_lib():
         if not os.path.exists(DEVICE_LIB_PATH):
             raise DeviceLibraryMissing("%s is missing -- run `python __graft_entry__.py` (build()) first" % DEVICE_LIB_PATH)
         lib = ctypes.CDLL(DEVICE_LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        if hasattr(lib, "rt_abi_version") and lib.rt_abi_version() != 9:
-            raise DeviceLibraryMissing("%s has ABI version %d, this front end was written for 9 -- rebuild (python __graft_entry__.py)" % (DEVICE_LIB_PATH, lib.rt_abi_version()))
+        if hasattr(lib, "rt_abi_version") and lib.rt_abi_version() != 10:
+            raise DeviceLibraryMissing("%s has ABI version %d, this front end was written for 10 -- rebuild (python __graft_entry__.py)" % (DEVICE_LIB_PATH, lib.rt_abi_version()))
         lib.rt_last_error.restype = c_char_p
         lib.rt_last_error.argtypes = [c_void_p]
         lib.rt_version.restype = c_char_p
@@ -98,6 +98,7 @@ def device_lib():
         lib.rt_read_aov.argtypes = [c_void_p, c_int, c_void_p, c_int]
         lib.rt_framebuffer_device_ptr.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t)]
         lib.rt_screen_pitch.argtypes = [c_void_p]
+        lib.rt_read_svgf_state.argtypes = [c_void_p, c_int, c_void_p]
         lib.rt_read_luts.argtypes = [c_void_p] + [c_void_p] * 6
         lib.rt_set_config.argtypes = [c_void_p, POINTER(GPUConfig)]
         _device = lib
@@ -871,6 +872,28 @@ def sample_sky(ctx, directions):
     d = _f32(directions).reshape(-1, 3)
     out = np.zeros((d.shape[0], 3), np.float32)
     _dev_check(ctx, device_lib().rt_sample_sky(ctx, d.ctypes.data, d.shape[0], out.ctypes.data))
+    return out
+
+
+SVGF_STATE_HISTORY_LENGTH, SVGF_STATE_HISTORY_DIRECT, SVGF_STATE_HISTORY_INDIRECT, SVGF_STATE_HISTORY_MOMENT, \
+    SVGF_STATE_HISTORY_NORMAL_AND_DEPTH, SVGF_STATE_FRAME_MOMENT, SVGF_STATE_TAA_HISTORY, SVGF_STATE_TAA_CURRENT = range(8)   # RT_SVGF_STATE_*
+
+
+def read_svgf_state(ctx, which):
+    """rt_read_svgf_state: one of the SVGF / TAA filter's persistent images after the frames filtered so far, as a
+    (height, pitch, C) array -- int32 with C = 1 for SVGF_STATE_HISTORY_LENGTH, float32 with C = 4 for the others."""
+    lib = device_lib()
+    # The ABI has no height query: every filter image has the final image's pitch x height pixels, and
+    # rt_framebuffer_device_ptr gives that image's size in bytes (16 per pixel).
+    ptr, nbytes = c_void_p(), c_size_t()
+    _dev_check(ctx, lib.rt_framebuffer_device_ptr(ctx, byref(ptr), byref(nbytes)))
+    pitch = lib.rt_screen_pitch(ctx)
+    height = nbytes.value // (16 * pitch)
+    if which == SVGF_STATE_HISTORY_LENGTH:
+        out = np.zeros((height, pitch, 1), np.int32)
+    else:
+        out = np.zeros((height, pitch, 4), np.float32)
+    _dev_check(ctx, lib.rt_read_svgf_state(ctx, int(which), out.ctypes.data))
     return out
 
 

@@ -1369,6 +1369,29 @@ int rt_filter_frame(rt_context * ctx, int sample_index) {
 	return RT_OK;
 }
 
+int rt_read_svgf_state(rt_context * ctx, int which, void * dst) {
+	RT_REQUIRE(ctx, ctx && dst, "rt_read_svgf_state: NULL argument");
+	RT_REQUIRE(ctx, which >= 0 && which < RT_SVGF_STATE_COUNT, "rt_read_svgf_state: unknown image (which is not one of RT_SVGF_STATE_*)");
+	(void)hipSetDevice(ctx->device);
+	if (!ctx->svgf_allocated) return fail(ctx, RT_ERROR_NOT_READY, "rt_read_svgf_state: SVGF is not allocated");
+	const RtParams & p = ctx->params;
+	const void * src = nullptr;
+	size_t bytes = 16;
+	switch (which) {
+		case RT_SVGF_STATE_HISTORY_LENGTH:           src = p.history_length; bytes = 4; break;
+		case RT_SVGF_STATE_HISTORY_DIRECT:           src = p.history_direct; break;
+		case RT_SVGF_STATE_HISTORY_INDIRECT:         src = p.history_indirect; break;
+		case RT_SVGF_STATE_HISTORY_MOMENT:           src = p.history_moment; break;
+		case RT_SVGF_STATE_HISTORY_NORMAL_AND_DEPTH: src = p.history_normal_and_depth; break;
+		case RT_SVGF_STATE_FRAME_MOMENT:             src = p.frame_buffer_moment; break;
+		case RT_SVGF_STATE_TAA_HISTORY:              src = p.taa_frame_prev; break;   // (swapped with taa_frame_next after every filtered frame)
+		case RT_SVGF_STATE_TAA_CURRENT:              src = p.taa_frame_curr; break;
+	}
+	RT_HIP(ctx, quiesce(ctx));
+	RT_HIP(ctx, hipMemcpy(dst, src, ctx->frame_pixels * bytes, hipMemcpyDeviceToHost));
+	return RT_OK;
+}
+
 // ---- frame exchange of the tile split without Python ----------------------------------------------------
 // One communicator per context. RCCL is bound at RUN TIME (dlopen, RTLD_LOCAL): a process that also hosts PyTorch already
 // has torch's own copy of librccl mapped, and a link-time dependency would make every user of this library load a

@@ -148,8 +148,9 @@ const char * rt_version(void);
  *      rt_set_build_boxes added
  *   8  rt_set_skip_behind_hit, rt_get_skip_behind_hit, rt_geometry_fits_flat_engine, rt_update_nodes (additions only)
  *   9  rt_sample_texture, rt_sample_table, rt_sample_sky (additions only)
+ *  10  rt_read_svgf_state and the RT_SVGF_STATE_* images it reads (additions only)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
-#define RT_ABI_VERSION 9
+#define RT_ABI_VERSION 10
 int rt_abi_version(void);
 
 /* ---- scene upload ------------------------------------------------------------------- */
@@ -350,6 +351,26 @@ int rt_render_sample_unfiltered(rt_context * ctx, int sample_index);
 int rt_pack_svgf_inputs(rt_context * ctx, void * dst_device, int tile_pixels, int first_tile, int tile_stride, int tiles);
 int rt_unpack_svgf_inputs(rt_context * ctx, const void * src_device, int tile_pixels, int world, int tiles_per_rank);
 int rt_filter_frame(rt_context * ctx, int sample_index);
+/* Copies one of the SVGF / TAA filter's persistent images, pitch*height elements, to dst (host). Synchronous: waits for the
+ * filter work already enqueued (slot 0 included). `which` is one of RT_SVGF_STATE_*; element types:
+ *   HISTORY_LENGTH           int32   frames of history per pixel after the last filtered frame
+ *   HISTORY_DIRECT/INDIRECT  float4  what the next frame reprojects from (after the feedback a-trous iteration)
+ *   HISTORY_MOMENT           float4  luminance moments (l_d, l_i, l_d^2, l_i^2) the next frame reprojects from
+ *   HISTORY_NORMAL_AND_DEPTH float4  the last frame's DECODED normal in .xyz and depth in .w
+ *   FRAME_MOMENT             float4  the last frame's temporally integrated moments
+ *   TAA_HISTORY              float4  the resolved colour the next frame's TAA reads (tone-mapped)
+ *   TAA_CURRENT              float4  the last frame's filtered colour, tone-mapped, as its TAA resolve read it
+ * Refused: a NULL context or dst, an unknown `which`, SVGF not allocated. */
+#define RT_SVGF_STATE_HISTORY_LENGTH           0
+#define RT_SVGF_STATE_HISTORY_DIRECT           1
+#define RT_SVGF_STATE_HISTORY_INDIRECT         2
+#define RT_SVGF_STATE_HISTORY_MOMENT           3
+#define RT_SVGF_STATE_HISTORY_NORMAL_AND_DEPTH 4
+#define RT_SVGF_STATE_FRAME_MOMENT             5
+#define RT_SVGF_STATE_TAA_HISTORY              6
+#define RT_SVGF_STATE_TAA_CURRENT              7
+#define RT_SVGF_STATE_COUNT                    8
+int rt_read_svgf_state(rt_context * ctx, int which, void * dst);
 int rt_stream_wait_for_context(rt_context * ctx, void * stream);
 int rt_context_wait_for_stream(rt_context * ctx, void * stream);
 
