@@ -70,8 +70,8 @@ def device_lib():
         if not os.path.exists(DEVICE_LIB_PATH):
             raise DeviceLibraryMissing("%s is missing -- run `python __graft_entry__.py` (build()) first" % DEVICE_LIB_PATH)
         lib = ctypes.CDLL(DEVICE_LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        if hasattr(lib, "rt_abi_version") and lib.rt_abi_version() != 10:
-            raise DeviceLibraryMissing("%s has ABI version %d, this front end was written for 10 -- rebuild (python __graft_entry__.py)" % (DEVICE_LIB_PATH, lib.rt_abi_version()))
+        if hasattr(lib, "rt_abi_version") and lib.rt_abi_version() != 11:
+            raise DeviceLibraryMissing("%s has ABI version %d, this front end was written for 11 -- rebuild (python __graft_entry__.py)" % (DEVICE_LIB_PATH, lib.rt_abi_version()))
         lib.rt_last_error.restype = c_char_p
         lib.rt_last_error.argtypes = [c_void_p]
         lib.rt_version.restype = c_char_p
@@ -85,6 +85,10 @@ def device_lib():
         lib.rt_sample_texture.argtypes = [c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]
         lib.rt_sample_table.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]
         lib.rt_sample_sky.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
+        lib.rt_sample_sky_distribution.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
+        lib.rt_sky_pdf.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
+        lib.rt_set_sky_sampling.argtypes = [c_void_p, c_float]
+        lib.rt_get_sky_sampling.argtypes = [c_void_p, POINTER(c_float)]
         lib.rt_measure_stream_bandwidth.argtypes = [c_void_p, c_size_t, c_int, POINTER(c_float)]
         lib.rt_set_profiling.argtypes = [c_void_p, c_int]
         lib.rt_set_samples_in_flight.argtypes = [c_void_p, c_int]
@@ -872,6 +876,23 @@ def sample_sky(ctx, directions):
     d = _f32(directions).reshape(-1, 3)
     out = np.zeros((d.shape[0], 3), np.float32)
     _dev_check(ctx, device_lib().rt_sample_sky(ctx, d.ctypes.data, d.shape[0], out.ctypes.data))
+    return out
+
+
+def sample_sky_distribution(ctx, uv):
+    """rt_sample_sky_distribution: the sky importance sampling's inversion for (N, 2) points of [0, 1)^2 (u: column, v: row).
+    Returns (N, 4) float32: the direction and its pdf in solid angle."""
+    p = _f32(uv).reshape(-1, 2)
+    out = np.zeros((p.shape[0], 4), np.float32)
+    _dev_check(ctx, device_lib().rt_sample_sky_distribution(ctx, p.ctypes.data, p.shape[0], out.ctypes.data))
+    return out
+
+
+def sky_pdf(ctx, directions):
+    """rt_sky_pdf: the pdf (solid angle) the sky importance sampling gives (N, 3) unit directions. Returns (N,) float32."""
+    d = _f32(directions).reshape(-1, 3)
+    out = np.zeros(d.shape[0], np.float32)
+    _dev_check(ctx, device_lib().rt_sky_pdf(ctx, d.ctypes.data, d.shape[0], out.ctypes.data))
     return out
 
 

@@ -360,7 +360,9 @@ RT_DEV void stream_stats_flush(const RtParams & p, StreamStatsLDS & lds) {
 
 // MERGED: the launch processes the trace queue of iteration p.stream_iteration, whose entries are at different
 // bounces and belong to different samples (rt_stream_path_info); the launch arguments are ignored.
-template<bool MERGED>
+// SKY: sky importance sampling is active (RtParams::sky_nee_share > 0): what a BSDF-sampled ray finds of the sky and of the emitters is weighed
+// against the light samples' pdfs, which now include the sky's share.
+template<bool MERGED, bool SKY = false>
 RT_DEV void sort_rays(const RtParams & p, int launch_bounce, int launch_sample_index) {
 	const int q = MERGED ? (p.stream_iteration & 1) : (launch_bounce & 1);
 	const int ray_count = MERGED ? p.stream->trace_count[q] : p.sizes->trace[launch_bounce];
@@ -464,6 +466,10 @@ RT_DEV void sort_rays(const RtParams & p, int launch_bounce, int launch_sample_i
 
 		if (hit.triangle_id == RT_INVALID) { // miss: sky
 			f3 illumination = throughput * sample_sky(p, ray_direction);
+			if (SKY && allow_nee) {   // the light samples reach the sky too: MIS against them, or (MIS off) leave the sky to them
+				if (!p.config.enable_multiple_importance_sampling) return -1;
+				illumination *= power_heuristic(in.last_pdf[index], p.sky_nee_share * sky_pdf(p, ray_direction));
+			}
 			add_radiance(p, bounce, pixel_index, illumination, illumination);
 			return -1;
 		}
@@ -495,6 +501,7 @@ RT_DEV void sort_rays(const RtParams & p, int launch_bounce, int launch_sample_i
 			f3 emission = mk3(p.materials[2 * material_id]);
 
 			bool count_light = p.config.enable_next_event_estimation ? !allow_nee : true;
+			if (SKY && p.sky_nee_share >= 1.0f) count_light = true;   // every light sample goes to the sky: emitters are found by BSDF sampling alone
 			if (count_light) {
 				add_radiance(p, bounce, pixel_index, throughput * emission, emission);
 				return -1;
@@ -505,6 +512,7 @@ RT_DEV void sort_rays(const RtParams & p, int launch_bounce, int launch_sample_i
 				float brdf_pdf = in.last_pdf[index];
 				float light_power = luminance(emission.x, emission.y, emission.z);
 				float light_pdf = light_power * distance_to_light_squared / (cos_theta_light * p.lights_total_weight);
+				if (SKY) light_pdf *= 1.0f - p.sky_nee_share;
 				if (!pdf_is_valid(light_pdf)) return -1;
 				float mis_weight = power_heuristic(brdf_pdf, light_pdf);
 				f3 illumination = throughput * emission * mis_weight;
@@ -540,6 +548,8 @@ RT_DEV void sort_rays(const RtParams & p, int launch_bounce, int launch_sample_i
 
 __global__ void __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES) kernel_sort(RtParams p, int bounce, int sample_index) { sort_rays<false>(p, bounce, sample_index); }
 __global__ void __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES) kernel_sort_stream(RtParams p) { sort_rays<true>(p, 0, 0); }
+__global__ void __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES) kernel_sort_sky(RtParams p, int bounce, int sample_index) { sort_rays<false, true>(p, bounce, sample_index); }
+__global__ void __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES) kernel_sort_stream_sky(RtParams p) { sort_rays<true, true>(p, 0, 0); }
 
 // ---- BSDFs (CUDA/BSDF.h) ----------------------------------------------------------------------------------
 
@@ -874,10 +884,7 @@ struct ShadowRay { f3 origin, direction; float max_distance; f3 illumination; };
 // It depends on the path's random numbers alone, not on the surface. (Measured, profiles/r04_shade_stage.txt 5.: taking it BEFORE the surface
 // set-up, so that its loads run beside the hit's own chain, changes nothing -- the material kernels are not waiting on that chain.)
 struct LightSample { f3 point, geometric_normal, emission; };
-RT_DEV LightSample nee_pick_light(const RtParams & p, const LightTablesLDS * light_lds, const RandomPath & rng, int bounce) {
-	f2 rand_light    = random_sample(p, rng, DIM_NEE_LIGHT,    unsigned(bounce));
-	f2 rand_triangle = random_sample(p, rng, DIM_NEE_TRIANGLE, unsigned(bounce));
-
+RT_DEV LightSample nee_pick_light(const RtParams & p, const LightTablesLDS * light_lds, f2 rand_light, f2 rand_triangle) {
 	int light_mesh_id;
 	int light_triangle_id = sample_light(p, light_lds, rand_light.x, rand_light.y, light_mesh_id);
 	f2 light_uv = sample_triangle(rand_triangle.x, rand_triangle.y);
@@ -897,9 +904,26 @@ RT_DEV LightSample nee_pick_light(const RtParams & p, const LightTablesLDS * lig
 	return light;
 }
 
+// The tail of every light sample: the BSDF towards it, the MIS weight, the shadow ray. `light_pdf` is the sample's pdf in solid angle; an emitter's
+// has to pass pdf_is_valid (the reference's rule), the sky's only has to be positive and finite (the BSDF-miss side weighs every sky direction).
+template<bool EMITTER, typename BSDF>
+RT_DEV bool nee_finish(const RtParams & p, const BSDF & bsdf, f3 origin, f3 to_light, float max_distance, float cos_theta_hit, f3 radiance, float light_pdf, f3 throughput, ShadowRay & shadow) {
+	f3 bsdf_value; float bsdf_pdf;
+	if (!bsdf.eval(p, to_light, cos_theta_hit, bsdf_value, bsdf_pdf)) return false;
+	if (EMITTER ? !pdf_is_valid(light_pdf) : !(light_pdf > 0.0f && isfinite(light_pdf))) return false;
+
+	float mis_weight = p.config.enable_multiple_importance_sampling ? power_heuristic(light_pdf, bsdf_pdf) : 1.0f;
+	shadow.illumination = throughput * bsdf_value * radiance * mis_weight / light_pdf;
+	shadow.origin = origin;
+	shadow.direction = to_light;
+	shadow.max_distance = max_distance;
+	return true;
+}
+
 // Connects a hit with its light sample. Returns true and fills `shadow` when the sample has to be traced (the caller appends it).
-template<typename BSDF>
-RT_DEV bool nee_connect(const RtParams & p, const LightSample & light, const BSDF & bsdf, f3 hit_point, f3 normal, f3 geometric_normal, f3 throughput, ShadowRay & shadow) {
+// `selection`: the probability that the light sample went to the emitters (1 - the sky's share; 1 without sky sampling).
+template<bool SKY, typename BSDF>
+RT_DEV bool nee_connect(const RtParams & p, const LightSample & light, const BSDF & bsdf, f3 hit_point, f3 normal, f3 geometric_normal, f3 throughput, float selection, ShadowRay & shadow) {
 	f3 light_point = light.point, light_geometric_normal = light.geometric_normal;
 	hit_point   = ray_origin_epsilon_offset(hit_point,   light_point - hit_point, geometric_normal);
 	light_point = ray_origin_epsilon_offset(light_point, hit_point - light_point, light_geometric_normal);
@@ -912,24 +936,30 @@ RT_DEV bool nee_connect(const RtParams & p, const LightSample & light, const BSD
 	float cos_theta_hit = dot(to_light, normal);
 
 	f3 emission = light.emission;
-
-	f3 bsdf_value; float bsdf_pdf;
-	if (!bsdf.eval(p, to_light, cos_theta_hit, bsdf_value, bsdf_pdf)) return false;
-
 	float light_power = luminance(emission.x, emission.y, emission.z);
 	float light_pdf   = light_power * square(distance_to_light) / (cos_theta_light * p.lights_total_weight);
-	if (!pdf_is_valid(light_pdf)) return false;
-
-	float mis_weight = p.config.enable_multiple_importance_sampling ? power_heuristic(light_pdf, bsdf_pdf) : 1.0f;
-	shadow.illumination = throughput * bsdf_value * emission * mis_weight / light_pdf;
-	shadow.origin = hit_point;
-	shadow.direction = to_light;
-	shadow.max_distance = distance_to_light;
-	return true;
+	if (SKY) light_pdf *= selection;
+	return nee_finish<true>(p, bsdf, hit_point, to_light, distance_to_light, cos_theta_hit, emission, light_pdf, throughput, shadow);
 }
+// The sky as the light sample (sky importance sampling): a direction from the sky's tables, traced to infinity.
 template<typename BSDF>
+RT_DEV bool nee_connect_sky(const RtParams & p, const BSDF & bsdf, f3 hit_point, f3 normal, f3 geometric_normal, f3 throughput, f2 rand_direction, ShadowRay & shadow) {
+	float sky_pdf_value;
+	f3 to_sky = sky_sample_direction(p, rand_direction.x, rand_direction.y, sky_pdf_value);
+	f3 origin = ray_origin_epsilon_offset(hit_point, to_sky, geometric_normal);
+	return nee_finish<false>(p, bsdf, origin, to_sky, RT_INFINITY, dot(to_sky, normal), sample_sky(p, to_sky), p.sky_nee_share * sky_pdf_value, throughput, shadow);
+}
+// SKY: the light sample goes to the sky with probability p.sky_nee_share (DIM_NEE_LIGHT.x below it; its direction from the DIM_NEE_TRIANGLE
+// pair), else to the emitters, with DIM_NEE_LIGHT.x rescaled to [0, 1) -- the same random dimensions either way.
+template<bool SKY, typename BSDF>
 RT_DEV bool next_event_estimation(const RtParams & p, const LightTablesLDS * light_lds, int pixel_index, int bounce, int sample_index, const BSDF & bsdf, f3 hit_point, f3 normal, f3 geometric_normal, f3 throughput, ShadowRay & shadow) {
-	return nee_connect(p, nee_pick_light(p, light_lds, bsdf.rng, bounce), bsdf, hit_point, normal, geometric_normal, throughput, shadow);
+	f2 rand_light    = random_sample(p, bsdf.rng, DIM_NEE_LIGHT,    unsigned(bounce));
+	f2 rand_triangle = random_sample(p, bsdf.rng, DIM_NEE_TRIANGLE, unsigned(bounce));
+	if (!SKY) return nee_connect<false>(p, nee_pick_light(p, light_lds, rand_light, rand_triangle), bsdf, hit_point, normal, geometric_normal, throughput, 1.0f, shadow);
+	const float share = p.sky_nee_share;   // (0, 1]: the _sky kernels run only while sampling is active
+	if (rand_light.x < share) return nee_connect_sky(p, bsdf, hit_point, normal, geometric_normal, throughput, rand_triangle, shadow);
+	rand_light.x = fminf((rand_light.x - share) / (1.0f - share), 0x1.fffffep-1f);   // (share < 1 here)
+	return nee_connect<true>(p, nee_pick_light(p, light_lds, rand_light, rand_triangle), bsdf, hit_point, normal, geometric_normal, throughput, 1.0f - share, shadow);
 }
 
 // ---- shade_material<BSDF> (Pathtracer.cu:557-757) -------------------------------------------------------------
@@ -962,7 +992,8 @@ RT_DEV float ray_cone_get_lod(f3 ray_direction, f3 geometric_normal, float cone_
 
 // MERGED: the queue holds the surface hits of every submission in flight (see sort_rays); bounce and sample come
 // from the slot table, the launch arguments are ignored.
-template<typename BSDF, int SLOT, bool MERGED>
+// SKY: sky importance sampling is active (RtParams::sky_nee_share > 0): light samples go to the sky or the emitters, see next_event_estimation.
+template<typename BSDF, int SLOT, bool MERGED, bool SKY = false>
 RT_DEV void shade_material(const RtParams & p, int launch_bounce, int launch_sample_index) {
 	const RtMaterialBuffer & q = p.material[SLOT];
 	const int iq = MERGED ? (p.stream_iteration & 1) : (launch_bounce & 1);
@@ -977,10 +1008,10 @@ RT_DEV void shade_material(const RtParams & p, int launch_bounce, int launch_sam
 	__shared__ StreamStatsLDS stats_lds;
 	int * const shadow_counter = MERGED ? &p.stream->shadow_count[iq]    : &p.sizes->shadow[launch_bounce];
 	int * const trace_counter  = MERGED ? &p.stream->trace_count[iq ^ 1] : &p.sizes->trace[launch_bounce + 1];
-	const bool nee_enabled = p.config.enable_next_event_estimation && p.lights_total_weight > 0.0f; // uniform
+	const bool nee_enabled = SKY || (p.config.enable_next_event_estimation && p.lights_total_weight > 0.0f); // uniform
 #if RT_LIGHT_TABLES_LDS
 	__shared__ LightTablesLDS light_lds;
-	if (nee_enabled && blockIdx.x * blockDim.x < unsigned(buffer_size)) light_tables_to_lds(p, light_lds);
+	if (nee_enabled && (!SKY || p.lights_total_weight > 0.0f) && blockIdx.x * blockDim.x < unsigned(buffer_size)) light_tables_to_lds(p, light_lds);
 	const LightTablesLDS * const light_tables = &light_lds;
 #else
 	const LightTablesLDS * const light_tables = nullptr;
@@ -1091,7 +1122,7 @@ RT_DEV void shade_material(const RtParams & p, int launch_bounce, int launch_sam
 		}
 
 		if (nee_enabled && bsdf.allow_nee()) {
-			has_shadow_ray = next_event_estimation(p, light_tables, pixel_index, bounce, sample_index, bsdf, hit_point, normal, geometric_normal, throughput, shadow);
+			has_shadow_ray = next_event_estimation<SKY>(p, light_tables, pixel_index, bounce, sample_index, bsdf, hit_point, normal, geometric_normal, throughput, shadow);
 		}
 		return true;
 		};
@@ -1163,6 +1194,19 @@ __global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_materia
 __global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic_stream(RtParams p)    { shade_material<BSDFPlastic,    1, true>(p, 0, 0); }
 __global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_dielectric_stream(RtParams p) { shade_material<BSDFDielectric, 2, true>(p, 0, 0); }
 __global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_conductor_stream(RtParams p)  { shade_material<BSDFConductor,  3, true>(p, 0, 0); }
+// ..._sky: the same kernels with sky importance sampling (RtParams::sky_nee_share > 0), launched only while it is active
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_diffuse_sky(RtParams p, int bounce, int sample_index)          { shade_material<BSDFDiffuse,         0, false, true>(p, bounce, sample_index); }
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic_sky(RtParams p, int bounce, int sample_index)          { shade_material<BSDFPlastic,         1, false, true>(p, bounce, sample_index); }
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_dielectric_sky(RtParams p, int bounce, int sample_index)       { shade_material<BSDFDielectric,      2, false, true>(p, bounce, sample_index); }
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_conductor_sky(RtParams p, int bounce, int sample_index)        { shade_material<BSDFConductor,       3, false, true>(p, bounce, sample_index); }
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_diffuse_texels_sky(RtParams p, int bounce, int sample_index)   { shade_material<BSDFDiffuseT<false>, 0, false, true>(p, bounce, sample_index); }
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic_texels_sky(RtParams p, int bounce, int sample_index)   { shade_material<BSDFPlasticT<false>, 1, false, true>(p, bounce, sample_index); }
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES_DIFFUSE) kernel_material_diffuse_stream_texels_sky(RtParams p)            { shade_material<BSDFDiffuseT<false>, 0, true, true>(p, 0, 0); }
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic_stream_texels_sky(RtParams p)                   { shade_material<BSDFPlasticT<false>, 1, true, true>(p, 0, 0); }
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_diffuse_stream_sky(RtParams p)                          { shade_material<BSDFDiffuse,         0, true, true>(p, 0, 0); }
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic_stream_sky(RtParams p)                          { shade_material<BSDFPlastic,         1, true, true>(p, 0, 0); }
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_dielectric_stream_sky(RtParams p)                       { shade_material<BSDFDielectric,      2, true, true>(p, 0, 0); }
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_conductor_stream_sky(RtParams p)                        { shade_material<BSDFConductor,       3, true, true>(p, 0, 0); }
 
 // ---- ambient occlusion (CUDA/AO.cu:103-159) -------------------------------------------------------
 // One cosine-weighted occlusion ray of length ao_radius per primary hit; the AO shadow kernel sets
@@ -1233,11 +1277,21 @@ static int streaming_grid(int work_items) {
 void rt_launch_generate(const RtParams & p, int sample_index, int pixel_offset, int pixel_count, hipStream_t stream) {
 	hipLaunchKernelGGL(kernel_generate, dim3(streaming_grid(pixel_count)), dim3(RT_SHADE_BLOCK), 0, stream, p, sample_index, pixel_offset, pixel_count);
 }
+// (the sort and material launchers take the ..._sky instances while sky importance sampling is active: RtParams::sky_nee_share > 0)
 void rt_launch_sort(const RtParams & p, int bounce, int sample_index, hipStream_t stream) {
-	hipLaunchKernelGGL(kernel_sort, dim3(2048 * RT_SHADE_BLOCK / RT_SORT_BLOCK), dim3(RT_SORT_BLOCK), 0, stream, p, bounce, sample_index);
+	hipLaunchKernelGGL(p.sky_nee_share > 0.0f ? kernel_sort_sky : kernel_sort, dim3(2048 * RT_SHADE_BLOCK / RT_SORT_BLOCK), dim3(RT_SORT_BLOCK), 0, stream, p, bounce, sample_index);
 }
 void rt_launch_material(const RtParams & p, int material_slot, int bounce, int sample_index, hipStream_t stream) {
 	dim3 grid(2048), block(RT_SHADE_BLOCK);
+	if (p.sky_nee_share > 0.0f) {
+		switch (material_slot) {
+			case 0: hipLaunchKernelGGL(p.textures_compressed ? kernel_material_diffuse_sky : kernel_material_diffuse_texels_sky, grid, block, 0, stream, p, bounce, sample_index); break;
+			case 1: hipLaunchKernelGGL(p.textures_compressed ? kernel_material_plastic_sky : kernel_material_plastic_texels_sky, grid, block, 0, stream, p, bounce, sample_index); break;
+			case 2: hipLaunchKernelGGL(kernel_material_dielectric_sky, grid, block, 0, stream, p, bounce, sample_index); break;
+			case 3: hipLaunchKernelGGL(kernel_material_conductor_sky,  grid, block, 0, stream, p, bounce, sample_index); break;
+		}
+		return;
+	}
 	switch (material_slot) {
 		case 0: if (p.textures_compressed) hipLaunchKernelGGL(kernel_material_diffuse, grid, block, 0, stream, p, bounce, sample_index); else hipLaunchKernelGGL(kernel_material_diffuse_texels, grid, block, 0, stream, p, bounce, sample_index); break;
 		case 1: if (p.textures_compressed) hipLaunchKernelGGL(kernel_material_plastic, grid, block, 0, stream, p, bounce, sample_index); else hipLaunchKernelGGL(kernel_material_plastic_texels, grid, block, 0, stream, p, bounce, sample_index); break;
@@ -1259,10 +1313,19 @@ void rt_launch_stream_advance(RtStreamControl * control, int iteration, int gene
 #define RT_STREAM_SORT_GRID 2048    // ... and of its sort launch (in units of RT_SHADE_BLOCK threads)
 #endif
 void rt_launch_sort_stream(const RtParams & p, hipStream_t stream) {
-	hipLaunchKernelGGL(kernel_sort_stream, dim3(RT_STREAM_SORT_GRID * RT_SHADE_BLOCK / RT_SORT_BLOCK), dim3(RT_SORT_BLOCK), 0, stream, p);
+	hipLaunchKernelGGL(p.sky_nee_share > 0.0f ? kernel_sort_stream_sky : kernel_sort_stream, dim3(RT_STREAM_SORT_GRID * RT_SHADE_BLOCK / RT_SORT_BLOCK), dim3(RT_SORT_BLOCK), 0, stream, p);
 }
 void rt_launch_material_stream(const RtParams & p, int material_slot, hipStream_t stream) {
 	dim3 grid(RT_STREAM_SHADE_GRID), block(RT_SHADE_BLOCK);
+	if (p.sky_nee_share > 0.0f) {
+		switch (material_slot) {
+			case 0: hipLaunchKernelGGL(p.textures_compressed ? kernel_material_diffuse_stream_sky : kernel_material_diffuse_stream_texels_sky, grid, block, 0, stream, p); break;
+			case 1: hipLaunchKernelGGL(p.textures_compressed ? kernel_material_plastic_stream_sky : kernel_material_plastic_stream_texels_sky, grid, block, 0, stream, p); break;
+			case 2: hipLaunchKernelGGL(kernel_material_dielectric_stream_sky, grid, block, 0, stream, p); break;
+			case 3: hipLaunchKernelGGL(kernel_material_conductor_stream_sky,  grid, block, 0, stream, p); break;
+		}
+		return;
+	}
 	switch (material_slot) {
 		case 0: if (p.textures_compressed) hipLaunchKernelGGL(kernel_material_diffuse_stream, grid, block, 0, stream, p); else hipLaunchKernelGGL(kernel_material_diffuse_stream_texels, grid, block, 0, stream, p); break;
 		case 1: if (p.textures_compressed) hipLaunchKernelGGL(kernel_material_plastic_stream, grid, block, 0, stream, p); else hipLaunchKernelGGL(kernel_material_plastic_stream_texels, grid, block, 0, stream, p); break;

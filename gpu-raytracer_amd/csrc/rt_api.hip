@@ -10,6 +10,7 @@
 #include "rt_tlas_build.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -226,6 +227,12 @@ struct rt_context {
 	void * texture_table = nullptr; std::vector<void *> texture_data;
 	void * pmj = nullptr, * blue_noise = nullptr;
 	void * sky = nullptr;
+	// sky importance sampling (rt_set_sky_sampling; kernels_sky.hip): the tables are built at the first render that wants them after rt_set_sky
+	float sky_sampling = 0.0f;               // 0: off (the reference's estimator); (0, 1]: the sky's share of the light samples when emitters exist
+	void * sky_tables = nullptr;             // floats: marginal CDF [H], conditional CDFs [H * W], cell pdfs [H * W]
+	void * sky_table_sums = nullptr;         // doubles: row totals [H], total [1]
+	bool sky_tables_ready = false;
+	double sky_total = 0.0;                  // the sum of the cell weights (0: a black sky, sampling stays inactive; not finite: an error)
 	void * luts[6] = { }; bool luts_ready = false;
 	int bvh_width = 8;
 
@@ -728,6 +735,18 @@ int rt_set_skip_behind_hit(rt_context * ctx, int32_t enable) {
 }
 int rt_get_skip_behind_hit(const rt_context * ctx) { return ctx && rt_skip_walk(ctx->params) ? 1 : 0; }
 
+int rt_set_sky_sampling(rt_context * ctx, float probability) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_set_sky_sampling: NULL context");
+	RT_REQUIRE(ctx, probability == 0.0f || (probability > 0.0f && probability <= 1.0f), "rt_set_sky_sampling: the probability must be 0 (off) or in (0, 1]");
+	ctx->sky_sampling = probability;   // (takes effect at the next render, see sky_sampling_prepare)
+	return RT_OK;
+}
+int rt_get_sky_sampling(const rt_context * ctx, float * out_probability) {
+	if (!ctx || !out_probability) return fail(nullptr, RT_ERROR_INVALID_ARG, "rt_get_sky_sampling: NULL argument");
+	*out_probability = ctx->sky_sampling;
+	return RT_OK;
+}
+
 // ---- BLAS build on the device (kernels_blas.hip) ---------------------------------------------------------------------
 } // extern "C"
 struct BlasBuildArgs { // must match kernels_blas.hip
@@ -1101,6 +1120,49 @@ int rt_set_sky(rt_context * ctx, const float * rgba, int width, int height, floa
 	int s = upload(ctx, &ctx->sky, rgba, size_t(width) * height * 16); if (s) return s;
 	ctx->params.sky = (const float4 *)ctx->sky;
 	ctx->params.sky_width = width; ctx->params.sky_height = height; ctx->params.sky_scale = scale;
+	// (upload drained the context) the sampling tables belong to the old sky
+	device_free(ctx, ctx->sky_tables); device_free(ctx, ctx->sky_table_sums);
+	ctx->sky_tables = ctx->sky_table_sums = nullptr;
+	ctx->sky_tables_ready = false;
+	ctx->params.sky_marginal_cdf = ctx->params.sky_conditional_cdf = ctx->params.sky_cell_pdf = nullptr;
+	ctx->params.sky_nee_share = 0.0f;
+	return RT_OK;
+}
+
+// The sky's sampling tables (kernels_sky.hip), built once per rt_set_sky; synchronous (it reads the total back).
+static int sky_tables_build(rt_context * ctx, const char * caller) {
+	RtParams & p = ctx->params;
+	if (!ctx->sky_tables_ready) {
+		const size_t w = size_t(p.sky_width), h = size_t(p.sky_height);
+		int s = device_alloc(ctx, &ctx->sky_tables, (h + 2 * w * h) * sizeof(float)); if (s) return s;
+		s = device_alloc(ctx, &ctx->sky_table_sums, (h + 1) * sizeof(double)); if (s) return s;
+		float * tables = (float *)ctx->sky_tables;
+		double * sums = (double *)ctx->sky_table_sums;
+		rt_launch_sky_build(p.sky, p.sky_width, p.sky_height, tables, tables + h, tables + h + w * h, sums, sums + h, ctx->stream);
+		RT_HIP(ctx, hipGetLastError());
+		RT_HIP(ctx, hipMemcpyAsync(&ctx->sky_total, sums + h, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+		RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		p.sky_marginal_cdf = tables; p.sky_conditional_cdf = tables + h; p.sky_cell_pdf = tables + h + w * h;
+		ctx->sky_tables_ready = true;
+	}
+	if (!std::isfinite(ctx->sky_total) || !std::isfinite(p.sky_scale))
+		return fail(ctx, RT_ERROR_INVALID_ARG, "%s: sky sampling needs a finite sky (the %dx%d sky has NaN or infinite texels, or its scale is not finite)", caller, p.sky_width, p.sky_height);
+	return RT_OK;
+}
+
+// Before a render: the sky's share of the light samples for this render (RtParams::sky_nee_share), building the tables if sampling is wanted.
+// 0 -- sampling off, NEE off, or a sky without weight -- keeps every kernel on the reference's estimator.
+static int sky_sampling_prepare(rt_context * ctx, const char * caller) {
+	RtParams & p = ctx->params;
+	float share = 0.0f;
+	if (ctx->sky_sampling > 0.0f && p.config.enable_next_event_estimation) {
+		int s = sky_tables_build(ctx, caller); if (s) return s;
+		if (ctx->sky_total > 0.0 && p.sky_scale != 0.0f) share = p.lights_total_weight > 0.0f ? ctx->sky_sampling : 1.0f;
+	}
+	if (share != p.sky_nee_share) {
+		RT_HIP(ctx, quiesce(ctx));   // (paths in flight were shaded under the other estimator)
+		p.sky_nee_share = share;
+	}
 	return RT_OK;
 }
 
@@ -2191,6 +2253,7 @@ int rt_render_samples(rt_context * ctx, int sample_index, int sample_count) {
 	if (ctx->params.config.enable_svgf && sample_count != 1) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_render_samples: SVGF frames are rendered one sample at a time");
 	if (merged != ctx->last_render_merged) { RT_HIP(ctx, quiesce(ctx)); ctx->last_render_merged = merged; }
 	if (ctx->has_material[2] || ctx->has_material[3]) { s = ensure_luts(ctx); if (s) return s; }
+	s = sky_sampling_prepare(ctx, "rt_render_sample"); if (s) return s;
 	if (size_t(sample_count) * ctx->frame_pixels >= (1u << 30)) return fail(ctx, RT_ERROR_OUT_OF_RANGE, "rt_render_samples: %d samples of a %zu pixel frame exceed the 30-bit path index", sample_count, ctx->frame_pixels);
 	int range_offset = 0, range_count = 0;
 	s = resolve_pixel_range(ctx, "rt_render_sample", &range_offset, &range_count); if (s) return s;
@@ -2235,7 +2298,7 @@ int rt_render_samples(rt_context * ctx, int sample_index, int sample_count) {
 		for (int i = 0; i < 3; i++) if (from[i] && to[i] && from[i] != to[i]) RT_HIP(ctx, hipMemcpyAsync(to[i], from[i], ctx->frame_pixels * gbuffer_pixel_bytes[i], hipMemcpyDeviceToDevice, st));
 	}
 
-	bool trace_shadows = ctx->has_lights && p.config.enable_next_event_estimation && p.lights_total_weight > 0.0f;
+	bool trace_shadows = p.config.enable_next_event_estimation && ((ctx->has_lights && p.lights_total_weight > 0.0f) || p.sky_nee_share > 0.0f);   // (sky importance sampling: shadow rays without emitters)
 	// Shadow rays of bounce b only feed the frame buffers, so they run on the side stream while the
 	// main chain traces bounce b+1; they are joined before the next kernel that touches the frame
 	// buffers (sort: sky / emissive hits), which keeps the order of the float additions per pixel.
@@ -2664,6 +2727,43 @@ int rt_sample_sky(rt_context * ctx, const float * directions, size_t count, floa
 	RT_HIP(ctx, hipGetLastError());
 	RT_HIP(ctx, quiesce(ctx));
 	RT_HIP(ctx, hipMemcpy(out_rgb, dev_out, count * 12, hipMemcpyDeviceToHost));
+	return RT_OK;
+}
+
+int rt_sample_sky_distribution(rt_context * ctx, const float * uv, size_t count, float * out_xyz_pdf) {
+	RT_REQUIRE(ctx, ctx && uv && out_xyz_pdf, "rt_sample_sky_distribution: NULL argument");
+	RT_REQUIRE(ctx, ctx->params.sky, "rt_sample_sky_distribution: no sky uploaded (rt_set_sky)");
+	RT_REQUIRE(ctx, count <= size_t(1) << 28, "rt_sample_sky_distribution: more than 2^28 probes");
+	(void)hipSetDevice(ctx->device);
+	int s = sky_tables_build(ctx, "rt_sample_sky_distribution"); if (s) return s;
+	RT_REQUIRE(ctx, ctx->sky_total > 0.0, "rt_sample_sky_distribution: the sky has no weight to sample");
+	if (count == 0) return RT_OK;
+	TempBuffers tmp(ctx);
+	float * dev_uv = (float *)tmp.get(count * 8, uv);
+	float * dev_out = (float *)tmp.get(count * 16, nullptr);
+	if (!dev_uv || !dev_out) return fail(ctx, RT_ERROR_HIP, "rt_sample_sky_distribution: device allocation failed");
+	rt_launch_sample_sky_distribution(ctx->params, dev_uv, int(count), dev_out, ctx->stream);
+	RT_HIP(ctx, hipGetLastError());
+	RT_HIP(ctx, quiesce(ctx));
+	RT_HIP(ctx, hipMemcpy(out_xyz_pdf, dev_out, count * 16, hipMemcpyDeviceToHost));
+	return RT_OK;
+}
+
+int rt_sky_pdf(rt_context * ctx, const float * directions, size_t count, float * out_pdf) {
+	RT_REQUIRE(ctx, ctx && directions && out_pdf, "rt_sky_pdf: NULL argument");
+	RT_REQUIRE(ctx, ctx->params.sky, "rt_sky_pdf: no sky uploaded (rt_set_sky)");
+	RT_REQUIRE(ctx, count <= size_t(1) << 28, "rt_sky_pdf: more than 2^28 probes");
+	(void)hipSetDevice(ctx->device);
+	int s = sky_tables_build(ctx, "rt_sky_pdf"); if (s) return s;
+	if (count == 0) return RT_OK;
+	TempBuffers tmp(ctx);
+	float * dev_dirs = (float *)tmp.get(count * 12, directions);
+	float * dev_out = (float *)tmp.get(count * 4, nullptr);
+	if (!dev_dirs || !dev_out) return fail(ctx, RT_ERROR_HIP, "rt_sky_pdf: device allocation failed");
+	rt_launch_sky_pdf(ctx->params, dev_dirs, int(count), dev_out, ctx->stream);
+	RT_HIP(ctx, hipGetLastError());
+	RT_HIP(ctx, quiesce(ctx));
+	RT_HIP(ctx, hipMemcpy(out_pdf, dev_out, count * 4, hipMemcpyDeviceToHost));
 	return RT_OK;
 }
 

@@ -373,6 +373,62 @@ RT_DEV f3 sample_sky(const RtParams & p, f3 direction) {
 	return p.sky_scale * mk3(c);
 }
 
+// ---- sky importance sampling (rt_set_sky_sampling; the tables: kernels_sky.hip, DESIGN.md "Sky importance sampling") ----------------
+// A cell is one sky texel in sample_sky's mapping; inside a cell a direction is uniform in phi and in cos(theta), so the density of every
+// direction of the cell is the one number sky_cell_pdf holds for it. Sampling and evaluation both read that table through sky_pdf.
+
+// The cell sample_sky's (u, v) of `direction` falls in (the same float operations as sample_sky).
+RT_DEV int sky_cell(const RtParams & p, f3 direction) {
+	float phi   = atan2f(-direction.z, direction.x);
+	float theta = acosf(clampf(direction.y, -1.0f, 1.0f));
+	float u = phi   * RT_ONE_OVER_TWO_PI + 0.5f;
+	float v = theta * RT_ONE_OVER_PI;
+	int column = min(max(int(u * float(p.sky_width)),  0), p.sky_width  - 1);
+	int row    = min(max(int(v * float(p.sky_height)), 0), p.sky_height - 1);
+	return column + row * p.sky_width;
+}
+RT_DEV float sky_pdf(const RtParams & p, f3 direction) { return p.sky_cell_pdf[sky_cell(p, direction)]; }
+
+// First entry of an inclusive CDF that exceeds u (entries of empty cells equal their predecessor and are never chosen), and where u lies
+// between that entry and the one before: the inversion stays monotone in u, so stratified samples stay stratified.
+RT_DEV int sky_cdf_invert(const float * __restrict__ cdf, int n, float u, float & fraction) {
+	int lo = 0, hi = n - 1;
+	while (lo < hi) {
+		int mid = (lo + hi) >> 1;
+		if (cdf[mid] > u) hi = mid; else lo = mid + 1;
+	}
+	float c0 = lo > 0 ? cdf[lo - 1] : 0.0f;
+	float f = (u - c0) / (cdf[lo] - c0);
+	fraction = fminf(fmaxf(f, 0.0f), 0x1.fffffep-1f);   // (fmaxf also turns the NaN of an empty last cell into 0)
+	return lo;
+}
+
+// Direction for (u1, u2) in [0, 1)^2: u2 picks the row (marginal CDF), u1 the column in it; returns the direction and its pdf.
+RT_DEV f3 sky_sample_direction(const RtParams & p, float u1, float u2, float & pdf) {
+	const int width = p.sky_width, height = p.sky_height;
+	float fy, fx;
+	int row    = sky_cdf_invert(p.sky_marginal_cdf, height, u2, fy);
+	int column = sky_cdf_invert(p.sky_conditional_cdf + size_t(row) * width, width, u1, fx);
+	float phi = ((float(column) + fx) / float(width) - 0.5f) * RT_TWO_PI;
+	// cos(theta) uniform between the row's edges, interpolated as 1 - cos (upper half) or 1 + cos (lower half): no cancellation near a pole
+	float half_0 = 0.5f * RT_PI * float(row) / float(height), half_1 = 0.5f * RT_PI * float(row + 1) / float(height);
+	float cos_theta, sin_theta;
+	if (2 * row + 1 <= height) {
+		float s0 = sinf(half_0), s1 = sinf(half_1);
+		float a0 = 2.0f * s0 * s0, a1 = 2.0f * s1 * s1;
+		float a = a0 + fy * (a1 - a0);
+		cos_theta = 1.0f - a; sin_theta = sqrtf(fmaxf(a * (2.0f - a), 0.0f));
+	} else {
+		float c0 = cosf(half_0), c1 = cosf(half_1);
+		float b0 = 2.0f * c0 * c0, b1 = 2.0f * c1 * c1;
+		float b = b0 + fy * (b1 - b0);
+		cos_theta = b - 1.0f; sin_theta = sqrtf(fmaxf(b * (2.0f - b), 0.0f));
+	}
+	f3 direction = mk3(sin_theta * cosf(phi), cos_theta, -sin_theta * sinf(phi));
+	pdf = sky_pdf(p, direction);   // the table's value for the cell the direction lies in, as a BSDF ray in that direction would look it up
+	return direction;
+}
+
 // CUDA/Medium.h
 struct HomogeneousMedium { f3 sigma_a, sigma_s; float g; };
 RT_DEV HomogeneousMedium medium_as_homogeneous(const RtParams & p, int medium_id) {

@@ -201,6 +201,12 @@ struct RtParams {
 	int * svgf_young_pixels;          // [0]: how many pixels this frame's kernel_svgf_reproject left with fewer than 4 frames of history, [RT_SVGF_YOUNG_HEADER ...]: their indices (kernel_svgf_variance_listed); emptied by kernel_svgf_finalize
 	float2 * svgf_variance[2];        // (direct.w, indirect.w) of the radiance framebuffers [0] and accumulators [1], kept in step by the filter kernels
 	float4 * svgf_normal_and_depth;   // (normal, depth) of the frame being filtered: decoded once by kernel_svgf_reproject for the variance / a-trous taps
+	// Sky importance sampling (rt_set_sky_sampling; tables built by kernels_sky.hip, one cell per sky texel, row-major). Opt-in: while
+	// sky_nee_share is 0 the tables may be null and every kernel takes the reference's estimator (the ..._sky kernel instances are not launched).
+	const float * sky_marginal_cdf;     // [sky_height]: inclusive, normalised CDF over rows; last entry 1
+	const float * sky_conditional_cdf;  // [sky_height][sky_width]: inclusive, normalised CDF of each row; last entry 1
+	const float * sky_cell_pdf;         // [sky_height][sky_width]: pdf (solid angle) of every direction in the cell
+	float sky_nee_share;                // probability that a light sample goes to the sky: 0 off / inactive; rt_set_sky_sampling's value with triangle emitters, 1 without
 };
 // "Skip behind the hit" (kernels_trace.hip): closest-hit rays drop stacked groups of children that lie behind the hit they hold. Taken when the context wants it
 // (rt_set_skip_behind_hit) AND the scene is ONE tree the flattened scene's engine walks (rt_set_static_geometry(ctx, 1), arrays below 4 GiB): every CWBVH
@@ -270,6 +276,11 @@ void rt_launch_random(const RtParams & p, int dimension, const unsigned * pixel_
 void rt_launch_sample_texture(const RtParams & p, int texture_index, int filter, const float * args, int count, float4 * out, hipStream_t stream);
 void rt_launch_sample_table(const float * table, int nx, int ny, int nz, int dims, const float * coords, int count, float * out, hipStream_t stream);
 void rt_launch_sample_sky(const RtParams & p, const float * directions, int count, float * out, hipStream_t stream);
+// Sky importance sampling (kernels_sky.hip). build: the three tables of RtParams from the sky; row_total: sky_height doubles, total: one double (the
+// sum of all cell weights, read back by the host). sample / pdf: the device functions of rt_shading.h on explicit arguments (test support).
+void rt_launch_sky_build(const float4 * sky, int width, int height, float * marginal_cdf, float * conditional_cdf, float * cell_pdf, double * row_total, double * total, hipStream_t stream);
+void rt_launch_sample_sky_distribution(const RtParams & p, const float * uv, int count, float * out_xyz_pdf, hipStream_t stream);
+void rt_launch_sky_pdf(const RtParams & p, const float * directions, int count, float * out_pdf, hipStream_t stream);
 void rt_launch_integrate_luts(const RtParams & p, float * dielectric_dir_enter, float * dielectric_dir_leave, float * dielectric_enter, float * dielectric_leave,
                               float * conductor_dir, float * conductor, hipStream_t stream);
 void rt_launch_pack_pixels(const RtParams & p, float4 * dst, int tile_pixels, int tile_first, int tile_stride, int tiles, hipStream_t stream);

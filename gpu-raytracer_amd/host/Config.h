@@ -103,6 +103,9 @@ struct CPUConfig {
 	// Closest-hit rays of a one-tree scene drop stacked groups of children that lie behind the hit they already hold (rt_set_skip_behind_hit): same hits,
 	// 12 % fewer node visits on Sponza. false: the reference's walk, node for node.
 	bool  skip_behind_hit = true;
+	// Sky importance sampling for next-event estimation (rt_set_sky_sampling): 0 = off, the reference's estimator; (0, 1] = the sky's share
+	// of the light samples when the scene has emitters (all of them when it has none). Same expectation, less noise under a sky with a sun.
+	float sky_sampling = 0.0f;
 	int   static_slot_learning_viewpoint = 1;   // a quarter of those rays are paths from the camera as it stands when the tree is built (0: none are; half come from points of the free space, the rest from the surface, either way)
 	// ... and early split clipping (StaticBVHBuilder::presplit, as in front of the device build) in front of that builder's own SAH + spatial splits: fraction of
 	// the geometry's longest side above which a triangle is cut blindly first. 0: off.

@@ -811,6 +811,7 @@ void Integrator::update(float delta) {
 		scheduler_for_scene_updates = cpu_config.enable_scene_update;
 		check(rt_set_scheduler(ctx, scheduler_for_scene_updates ? RT_SCHEDULER_SLOTS : RT_SCHEDULER_MERGED));
 	}
+	if (ctx) check(rt_set_sky_sampling(ctx, cpu_config.sky_sampling));   // (a value; the device applies it at the next render)
 	if (cpu_config.enable_scene_update) {
 		if (!scene_advanced_by_another_integrator) scene.update(delta);
 		invalidated_scene = true;

@@ -74,6 +74,10 @@ int grt_config_set(const char * key, double value) {
 	else if (k == "static_slot_learning_rays")           cpu_config.static_slot_learning_rays = int(value);
 	else if (k == "static_slot_learning_viewpoint")      cpu_config.static_slot_learning_viewpoint = int(value);
 	else if (k == "skip_behind_hit")                     cpu_config.skip_behind_hit = value != 0;
+	else if (k == "sky_sampling") {   // 0 (off) or (0, 1]: the sky's share of the light samples (rt_set_sky_sampling)
+		if (!(value == 0.0 || (value > 0.0 && value <= 1.0))) { g_host_error = "sky_sampling must be 0 (off) or in (0, 1]"; return -1; }
+		cpu_config.sky_sampling = float(value);
+	}
 	else if (k == "static_reseat_distance")              cpu_config.static_reseat_distance = float(value);
 	else if (k == "static_mesh_copy_limit_mb")           cpu_config.static_mesh_copy_limit_mb = int(value);
 	else if (k == "static_copy_budget_mb")               cpu_config.static_copy_budget_mb = int(value);
@@ -91,6 +95,7 @@ double grt_config_get(const char * key) {
 	if (k == "aov_mask")       return gpu_config.aov_mask;
 	if (k == "enable_svgf")    return gpu_config.enable_svgf;
 	if (k == "skip_behind_hit") return cpu_config.skip_behind_hit;
+	if (k == "sky_sampling")   return cpu_config.sky_sampling;
 	return -1.0;
 }
 

@@ -92,6 +92,11 @@ std::vector<Option> make_options(CommandLine & cl) {
 	} });
 	o.push_back({ nullptr, "nee", "Enables or disables Next Event Estimation",        1, [](const char * v) { gpu_config.enable_next_event_estimation        = parse_bool(v); } });
 	o.push_back({ nullptr, "mis", "Enables or disables Multiple Importance Sampling", 1, [](const char * v) { gpu_config.enable_multiple_importance_sampling = parse_bool(v); } });
+	o.push_back({ nullptr, "sky-sampling", "Importance-samples the sky in NEE: 0 = off (default), (0, 1] = the sky's share of the light samples", 1, [](const char * v) {
+		float p = parse_float(v, "--sky-sampling");
+		if (!(p == 0.0f || (p > 0.0f && p <= 1.0f))) die("--sky-sampling must be 0 (off) or in (0, 1]");
+		cpu_config.sky_sampling = p;
+	} });
 	o.push_back({ nullptr, "force-rebuild", "BVH will not be loaded from disk but rebuilt from scratch", 0, [](const char *) { cpu_config.bvh_force_rebuild = true; } });
 	o.push_back({ "O",  "optimize",    "Enables or disables BVH optimization post-processing step", 1, [](const char * v) { cpu_config.enable_bvh_optimization = parse_bool(v); } });
 	o.push_back({ "Ot", "opt-time",    "Sets time limit for BVH optimization (milliseconds, as the reference stores it)", 1, [](const char * v) { cpu_config.bvh_optimizer_max_time = parse_int(v, "--opt-time"); } });

@@ -149,8 +149,9 @@ const char * rt_version(void);
  *   8  rt_set_skip_behind_hit, rt_get_skip_behind_hit, rt_geometry_fits_flat_engine, rt_update_nodes (additions only)
  *   9  rt_sample_texture, rt_sample_table, rt_sample_sky (additions only)
  *  10  rt_read_svgf_state and the RT_SVGF_STATE_* images it reads (additions only)
+ *  11  rt_set_sky_sampling, rt_get_sky_sampling, rt_sample_sky_distribution, rt_sky_pdf (additions only; sky importance sampling, off by default)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
-#define RT_ABI_VERSION 10
+#define RT_ABI_VERSION 11
 int rt_abi_version(void);
 
 /* ---- scene upload ------------------------------------------------------------------- */
@@ -196,6 +197,14 @@ int rt_update_nodes(rt_context * ctx, const void * nodes, size_t first_node, siz
  * reference's way. Drains the context when the value changes. rt_get_skip_behind_hit: 1 while the walk is in effect (wish AND one-tree scene).  */
 int rt_set_skip_behind_hit(rt_context * ctx, int32_t enable);
 int rt_get_skip_behind_hit(const rt_context * ctx);
+/* Sky importance sampling for next-event estimation (DESIGN.md "Sky importance sampling"). probability 0: off, the default -- the
+ * reference's estimator, every frame as before. (0, 1]: light samples also go to the sky, drawn from a distribution over its texels
+ * (tables built on the device at the first render after rt_set_sky that wants them); with triangle emitters the sky gets this share
+ * of the light samples, without them all. Same expectation, less noise under skies with a sun. Needs NEE on; a black sky leaves it
+ * inactive; a sky with NaN / infinite texels makes the render return RT_ERROR_INVALID_ARG. Anything outside {0} u (0, 1], NaN
+ * included: RT_ERROR_INVALID_ARG. Takes effect at the next render.                                                                */
+int rt_set_sky_sampling(rt_context * ctx, float probability);
+int rt_get_sky_sampling(const rt_context * ctx, float * out_probability);
 /* Replaces the per-frame TLAS memcpy into the front of `bvh8_nodes` (Integrator.cpp:404-409). The
  * TLAS, the instance tables (rt_upload_instances) and the light tables (rt_upload_lights) are
  * versioned on the device: the call copies the host data into pinned staging and returns (the
@@ -531,6 +540,12 @@ int rt_random_samples(rt_context * ctx, int dimension, const uint32_t * pixel_in
 int rt_sample_texture(rt_context * ctx, int texture_index, int filter, const float * args, size_t count, float * out_rgba);
 int rt_sample_table(rt_context * ctx, const float * table, int nx, int ny, int nz, int dims, const float * coords, size_t count, float * out);
 int rt_sample_sky(rt_context * ctx, const float * directions, size_t count, float * out_rgb);
+/* Sky importance sampling on explicit arguments (builds the tables if needed; synchronous).
+ * rt_sample_sky_distribution: uv: count x 2 floats in [0, 1) (u picks the column, v the row); out_xyz_pdf: count x 4 floats
+ * {direction, pdf in solid angle}. RT_ERROR_INVALID_ARG for a sky without weight.
+ * rt_sky_pdf: the pdf (solid angle) the distribution gives each of `count` unit directions (count x 3 floats); out_pdf: count. */
+int rt_sample_sky_distribution(rt_context * ctx, const float * uv, size_t count, float * out_xyz_pdf);
+int rt_sky_pdf(rt_context * ctx, const float * directions, size_t count, float * out_pdf);
 /* Streaming-read bandwidth probe used as the measured HBM roofline (GB/s).                 */
 int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps);
 
