@@ -70,8 +70,8 @@ def device_lib():
         if not os.path.exists(DEVICE_LIB_PATH):
             raise DeviceLibraryMissing("%s is missing -- run `python __graft_entry__.py` (build()) first" % DEVICE_LIB_PATH)
         lib = ctypes.CDLL(DEVICE_LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        if hasattr(lib, "rt_abi_version") and lib.rt_abi_version() != 11:
-            raise DeviceLibraryMissing("%s has ABI version %d, this front end was written for 11 -- rebuild (python __graft_entry__.py)" % (DEVICE_LIB_PATH, lib.rt_abi_version()))
+        if hasattr(lib, "rt_abi_version") and lib.rt_abi_version() != 12:
+            raise DeviceLibraryMissing("%s has ABI version %d, this front end was written for 12 -- rebuild (python __graft_entry__.py)" % (DEVICE_LIB_PATH, lib.rt_abi_version()))
         lib.rt_last_error.restype = c_char_p
         lib.rt_last_error.argtypes = [c_void_p]
         lib.rt_version.restype = c_char_p
@@ -87,6 +87,8 @@ def device_lib():
         lib.rt_sample_sky.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
         lib.rt_sample_sky_distribution.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
         lib.rt_sky_pdf.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
+        lib.rt_bsdf_eval.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p]
+        lib.rt_bsdf_sample.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p]
         lib.rt_set_sky_sampling.argtypes = [c_void_p, c_float]
         lib.rt_get_sky_sampling.argtypes = [c_void_p, POINTER(c_float)]
         lib.rt_measure_stream_bandwidth.argtypes = [c_void_p, c_size_t, c_int, POINTER(c_float)]
@@ -893,6 +895,28 @@ def sky_pdf(ctx, directions):
     d = _f32(directions).reshape(-1, 3)
     out = np.zeros(d.shape[0], np.float32)
     _dev_check(ctx, device_lib().rt_sky_pdf(ctx, d.ctypes.data, d.shape[0], out.ctypes.data))
+    return out
+
+
+BSDF_PROBE_IN, BSDF_PROBE_OUT = 24, 12   # floats per probe record of rt_bsdf_eval / rt_bsdf_sample
+
+
+def bsdf_eval(ctx, material_type, probes):
+    """rt_bsdf_eval: the shade kernels' BSDF `material_type` (MATERIAL_DIFFUSE .. MATERIAL_CONDUCTOR) evaluated on (N, 24) probe
+    records (see include/gpu_raytracer_amd.h). Returns (N, 12) float32 {ok, pdf, bsdf[3], to_light[3], medium, allow_nee, omega_i.z, pad}."""
+    return _bsdf_probe(ctx, device_lib().rt_bsdf_eval, material_type, probes)
+
+
+def bsdf_sample(ctx, material_type, probes):
+    """rt_bsdf_sample: the same BSDF's sample on (N, 24) probe records. Returns (N, 12) float32 {ok, pdf, throughput factor[3],
+    direction[3], medium, allow_nee, omega_i.z, pad}."""
+    return _bsdf_probe(ctx, device_lib().rt_bsdf_sample, material_type, probes)
+
+
+def _bsdf_probe(ctx, fn, material_type, probes):
+    p = _f32(probes).reshape(-1, BSDF_PROBE_IN)
+    out = np.zeros((p.shape[0], BSDF_PROBE_OUT), np.float32)
+    _dev_check(ctx, fn(ctx, int(material_type), p.ctypes.data, p.shape[0], out.ctypes.data))
     return out
 
 

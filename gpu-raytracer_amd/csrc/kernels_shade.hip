@@ -847,6 +847,54 @@ struct BSDFConductor : BSDFCommon {
 	RT_DEV bool allow_nee() const { return linear_roughness >= RT_ROUGHNESS_CUTOFF; }
 };
 
+// rt_bsdf_eval / rt_bsdf_sample: one BSDF set up as set_up_surface sets it up, then its own eval or sample. Probe i reads material i
+// of p.materials (the per-call table rt_api.hip uploads). Record in: RT_BSDF_PROBE_IN floats {material[8], normal[3], direction[3],
+// entering, to_light[3], cos_theta_o, pixel, sample, bounce (uint32 bits), pad[2]}; out: RT_BSDF_PROBE_OUT floats {ok (1, 0, or -1:
+// omega_i.z <= 0), pdf, bsdf or throughput[3], direction out[3], medium id, allow_nee, omega_i.z, pad}.
+template<typename BSDF, bool EVAL>
+__global__ void kernel_bsdf_probe(RtParams p, const float * probes, int count, float * out) {
+	int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= count) return;
+	const float * a = probes + size_t(i) * RT_BSDF_PROBE_IN;
+	float * o = out + size_t(i) * RT_BSDF_PROBE_OUT;
+	for (int k = 0; k < RT_BSDF_PROBE_OUT; k++) o[k] = 0.0f;
+	f3 normal = mk3(a[8], a[9], a[10]), ray_direction = mk3(a[11], a[12], a[13]);
+	bool entering_material = a[14] != 0.0f;
+	f3 tangent, bitangent;
+	orthonormal_basis(normal, tangent, bitangent);
+	f3 omega_i = world_to_local(-ray_direction, tangent, bitangent, normal);
+	o[10] = omega_i.z;
+	if (omega_i.z <= 0.0f) { o[0] = -1.0f; return; }
+
+	unsigned pixel_index = __float_as_uint(a[19]), sample_index = __float_as_uint(a[20]), bounce = __float_as_uint(a[21]);
+	BSDF bsdf;
+	bsdf.pixel_index = int(pixel_index); bsdf.bounce = int(bounce); bsdf.sample_index = int(sample_index); bsdf.rng = random_path(p, pixel_index, sample_index);
+	bsdf.tangent = tangent; bsdf.bitangent = bitangent; bsdf.normal = normal; bsdf.omega_i = omega_i;
+	bsdf.init(p, entering_material, i);
+	f3 throughput = mk3(1.0f);
+	if (BSDF::HAS_ALBEDO) {
+		TextureLOD lod = { mk2(0.0f, 0.0f), mk2(0.0f, 0.0f), 0.0f };
+		bsdf.calc_albedo(p, throughput, mk2(0.0f, 0.0f), lod);
+	}
+
+	bool ok; float pdf = 0.0f; f3 value, direction_out; int medium_id = RT_INVALID;
+	if (EVAL) {
+		value = mk3(0.0f);
+		direction_out = mk3(a[15], a[16], a[17]);
+		ok = bsdf.eval(p, direction_out, a[18], value, pdf);
+	} else {
+		direction_out = mk3(0.0f);
+		ok = bsdf.sample(p, throughput, medium_id, direction_out, pdf);
+		value = throughput;
+	}
+	o[0] = ok ? 1.0f : 0.0f;
+	o[1] = pdf;
+	o[2] = value.x; o[3] = value.y; o[4] = value.z;
+	o[5] = direction_out.x; o[6] = direction_out.y; o[7] = direction_out.z;
+	o[8] = float(medium_id);
+	o[9] = bsdf.allow_nee() ? 1.0f : 0.0f;
+}
+
 // ---- next event estimation (Pathtracer.cu:465-555) ----------------------------------------------------------
 
 // The two cumulative tables of light sampling, copied into LDS by the workgroup when they fit (Sponza: 2 meshes, 480 triangles):
@@ -1348,4 +1396,19 @@ void rt_launch_sample_table(const float * table, int nx, int ny, int nz, int dim
 }
 void rt_launch_sample_sky(const RtParams & p, const float * directions, int count, float * out, hipStream_t stream) {
 	hipLaunchKernelGGL(kernel_sample_sky, dim3((count + 255) / 256), dim3(256), 0, stream, p, directions, count, out);
+}
+// diffuse and plastic: the COMPRESSED instantiations the textureless material kernels launch (no texture is read either way)
+template<bool EVAL>
+static void launch_bsdf_probe(const RtParams & p, int material_type, const float * probes, int count, float * out, hipStream_t stream) {
+	dim3 grid((count + 255) / 256), block(256);
+	switch (material_type) {
+		case RT_MATERIAL_DIFFUSE:    hipLaunchKernelGGL((kernel_bsdf_probe<BSDFDiffuse,    EVAL>), grid, block, 0, stream, p, probes, count, out); break;
+		case RT_MATERIAL_PLASTIC:    hipLaunchKernelGGL((kernel_bsdf_probe<BSDFPlastic,    EVAL>), grid, block, 0, stream, p, probes, count, out); break;
+		case RT_MATERIAL_DIELECTRIC: hipLaunchKernelGGL((kernel_bsdf_probe<BSDFDielectric, EVAL>), grid, block, 0, stream, p, probes, count, out); break;
+		case RT_MATERIAL_CONDUCTOR:  hipLaunchKernelGGL((kernel_bsdf_probe<BSDFConductor,  EVAL>), grid, block, 0, stream, p, probes, count, out); break;
+	}
+}
+void rt_launch_bsdf_probe(const RtParams & p, int material_type, bool eval, const float * probes, int count, float * out, hipStream_t stream) {
+	if (eval) launch_bsdf_probe<true>(p, material_type, probes, count, out, stream);
+	else      launch_bsdf_probe<false>(p, material_type, probes, count, out, stream);
 }

@@ -2767,6 +2767,49 @@ int rt_sky_pdf(rt_context * ctx, const float * directions, size_t count, float *
 	return RT_OK;
 }
 
+// rt_bsdf_eval / rt_bsdf_sample: a copy of the parameters whose material table is the probes' own materials (probe i: material i),
+// with the Kulla-Conty tables of the context, no AOV and SVGF off, so that nothing of a frame is read or written.
+static int bsdf_probe(rt_context * ctx, const char * name, bool eval, int material_type, const float * probes, size_t count, float * out) {
+	if (!ctx || !probes || !out) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: NULL argument", name);
+	if (material_type < RT_MATERIAL_DIFFUSE || material_type > RT_MATERIAL_CONDUCTOR)
+		return fail(ctx, RT_ERROR_INVALID_ARG, "%s: material_type must be diffuse (1), plastic (2), dielectric (3) or conductor (4)", name);
+	if (count > size_t(1) << 24) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: more than 2^24 probes", name);
+	if (material_type == RT_MATERIAL_DIFFUSE || material_type == RT_MATERIAL_PLASTIC) {
+		for (size_t i = 0; i < count; i++) {
+			int32_t texture_id; memcpy(&texture_id, probes + i * RT_BSDF_PROBE_IN + 3, 4);
+			if (texture_id != RT_INVALID) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: probe %zu names texture %d (only RT_INVALID is probed)", name, i, texture_id);
+		}
+	}
+	(void)hipSetDevice(ctx->device);
+	if (!ctx->params.pmj_samples || ctx->params.screen_pitch == 0) return fail(ctx, RT_ERROR_NOT_READY, "%s: RNG tables not uploaded or rt_resize not called", name);
+	int s = ensure_luts(ctx); if (s) return s;
+	if (count == 0) return RT_OK;
+	std::vector<float> materials(count * 8);
+	for (size_t i = 0; i < count; i++) memcpy(&materials[i * 8], probes + i * RT_BSDF_PROBE_IN, 32);
+	TempBuffers tmp(ctx);
+	float * dev_materials = (float *)tmp.get(count * 32, materials.data());
+	float * dev_probes = (float *)tmp.get(count * RT_BSDF_PROBE_IN * 4, probes);
+	float * dev_out = (float *)tmp.get(count * RT_BSDF_PROBE_OUT * 4, nullptr);
+	if (!dev_materials || !dev_probes || !dev_out) return fail(ctx, RT_ERROR_HIP, "%s: device allocation failed", name);
+	RtParams p = ctx->params;
+	p.materials = (const float4 *)dev_materials;
+	p.textures = nullptr;
+	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = p.aovs[a].accumulator = nullptr;
+	p.config.enable_svgf = 0;
+	rt_launch_bsdf_probe(p, material_type, eval, dev_probes, int(count), dev_out, ctx->stream);
+	RT_HIP(ctx, hipGetLastError());
+	RT_HIP(ctx, quiesce(ctx));
+	RT_HIP(ctx, hipMemcpy(out, dev_out, count * RT_BSDF_PROBE_OUT * 4, hipMemcpyDeviceToHost));
+	return RT_OK;
+}
+
+int rt_bsdf_eval(rt_context * ctx, int material_type, const float * probes, size_t count, float * out) {
+	return bsdf_probe(ctx, "rt_bsdf_eval", true, material_type, probes, count, out);
+}
+int rt_bsdf_sample(rt_context * ctx, int material_type, const float * probes, size_t count, float * out) {
+	return bsdf_probe(ctx, "rt_bsdf_sample", false, material_type, probes, count, out);
+}
+
 int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps) {
 	RT_REQUIRE(ctx, ctx && out_gbps && bytes >= 1024, "rt_measure_stream_bandwidth: invalid argument");
 	(void)hipSetDevice(ctx->device);

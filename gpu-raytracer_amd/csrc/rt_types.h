@@ -276,6 +276,10 @@ void rt_launch_random(const RtParams & p, int dimension, const unsigned * pixel_
 void rt_launch_sample_texture(const RtParams & p, int texture_index, int filter, const float * args, int count, float4 * out, hipStream_t stream);
 void rt_launch_sample_table(const float * table, int nx, int ny, int nz, int dims, const float * coords, int count, float * out, hipStream_t stream);
 void rt_launch_sample_sky(const RtParams & p, const float * directions, int count, float * out, hipStream_t stream);
+// Test support: one BSDF's eval or sample on explicit probes (rt_bsdf_eval / rt_bsdf_sample); probe i uses material i of p.materials
+#define RT_BSDF_PROBE_IN  24
+#define RT_BSDF_PROBE_OUT 12
+void rt_launch_bsdf_probe(const RtParams & p, int material_type, bool eval, const float * probes, int count, float * out, hipStream_t stream);
 // Sky importance sampling (kernels_sky.hip). build: the three tables of RtParams from the sky; row_total: sky_height doubles, total: one double (the
 // sum of all cell weights, read back by the host). sample / pdf: the device functions of rt_shading.h on explicit arguments (test support).
 void rt_launch_sky_build(const float4 * sky, int width, int height, float * marginal_cdf, float * conditional_cdf, float * cell_pdf, double * row_total, double * total, hipStream_t stream);

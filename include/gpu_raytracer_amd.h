@@ -150,8 +150,9 @@ const char * rt_version(void);
  *   9  rt_sample_texture, rt_sample_table, rt_sample_sky (additions only)
  *  10  rt_read_svgf_state and the RT_SVGF_STATE_* images it reads (additions only)
  *  11  rt_set_sky_sampling, rt_get_sky_sampling, rt_sample_sky_distribution, rt_sky_pdf (additions only; sky importance sampling, off by default)
+ *  12  rt_bsdf_eval, rt_bsdf_sample (additions only)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
-#define RT_ABI_VERSION 11
+#define RT_ABI_VERSION 12
 int rt_abi_version(void);
 
 /* ---- scene upload ------------------------------------------------------------------- */
@@ -546,6 +547,16 @@ int rt_sample_sky(rt_context * ctx, const float * directions, size_t count, floa
  * rt_sky_pdf: the pdf (solid angle) the distribution gives each of `count` unit directions (count x 3 floats); out_pdf: count. */
 int rt_sample_sky_distribution(rt_context * ctx, const float * uv, size_t count, float * out_xyz_pdf);
 int rt_sky_pdf(rt_context * ctx, const float * directions, size_t count, float * out_pdf);
+/* One BSDF of the shade kernels on explicit probes (synchronous): set up as a material kernel sets up a hit (tangent frame of the normal,
+ * omega_i, the path's random numbers, init, albedo on a throughput of 1), then its own eval (rt_bsdf_eval) or sample (rt_bsdf_sample).
+ * material_type: RT_MATERIAL_DIFFUSE .. RT_MATERIAL_CONDUCTOR; the Kulla-Conty tables are the context's (integrated if need be).
+ * probes: count x 24 floats {material (the 32-byte record of rt_upload_materials; texture id RT_INVALID only), shading normal[3]
+ * (flipped to the side the ray arrives from), ray direction[3], entering_material (0 / 1), to_light[3], cos_theta_o (eval only),
+ * pixel index, sample index, bounce (uint32 bits; sample only), pad[2]}.
+ * out: count x 12 floats {ok (1 / 0; -1: refused, omega_i.z <= 0, as the shade kernels refuse it), pdf, bsdf (eval) or throughput
+ * factor (sample)[3], direction (to_light, or the sampled one)[3], medium id, allow_nee, omega_i.z, pad}. Writes no frame buffer. */
+int rt_bsdf_eval(rt_context * ctx, int material_type, const float * probes, size_t count, float * out);
+int rt_bsdf_sample(rt_context * ctx, int material_type, const float * probes, size_t count, float * out);
 /* Streaming-read bandwidth probe used as the measured HBM roofline (GB/s).                 */
 int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps);
 

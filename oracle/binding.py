@@ -109,6 +109,8 @@ def lib():
         l.oracle_integrate_dielectric_cells.argtypes = [POINTER(OracleScene), c_int, c_int, c_int, c_int, c_void_p, c_int]
         l.oracle_integrate_conductor_cells.argtypes = [POINTER(OracleScene), c_int, c_int, c_int, c_void_p, c_int]
         l.oracle_average_dielectric.argtypes = [c_void_p, c_void_p]
+        l.oracle_bsdf_eval.argtypes = [POINTER(OracleScene), c_int, c_void_p, c_size_t, c_void_p]
+        l.oracle_bsdf_sample.argtypes = [POINTER(OracleScene), c_int, c_void_p, c_size_t, c_void_p]
         l.oracle_average_conductor.argtypes = [c_void_p, c_void_p]
         tex_p = POINTER(OracleTexture)
         l.oracle_tex2d.argtypes = [tex_p, c_float, c_float, c_void_p]
@@ -667,6 +669,22 @@ class SceneView:
     def integrate_conductor_cells(self, first_cell, cell_count, num_samples=100000, threads=0):
         out = np.zeros(cell_count, np.float32)
         lib().oracle_integrate_conductor_cells(byref(self.scene), num_samples, first_cell, cell_count, out.ctypes.data, threads)
+        return out
+
+    def bsdf_eval(self, material_type, probes):
+        """oracle_bsdf_eval on (N, 24) probe records (rt_bsdf_eval's layout); the scene needs its LUTs (luts=) for the
+        dielectric and the conductor. Returns (N, 12) float32."""
+        return self._bsdf_probe(lib().oracle_bsdf_eval, material_type, probes)
+
+    def bsdf_sample(self, material_type, probes):
+        """oracle_bsdf_sample on (N, 24) probe records (rt_bsdf_sample's layout). Returns (N, 12) float32."""
+        return self._bsdf_probe(lib().oracle_bsdf_sample, material_type, probes)
+
+    def _bsdf_probe(self, fn, material_type, probes):
+        p = np.ascontiguousarray(probes, np.float32).reshape(-1, 24)
+        out = np.zeros((p.shape[0], 12), np.float32)
+        if fn(byref(self.scene), int(material_type), p.ctypes.data, p.shape[0], out.ctypes.data) != 0:
+            raise ValueError("unknown material type %r" % material_type)
         return out
 
     def random(self, dimension, pixel_indices, bounce, sample_index):

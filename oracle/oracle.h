@@ -158,6 +158,10 @@ void oracle_generate(const oracle_scene * scene, int sample_index, int pixel_off
 /* random<Dim> (Sampling.h:44-84) */
 void oracle_random(const oracle_scene * scene, int dimension, const uint32_t * pixel_indices, size_t count,
                    uint32_t bounce, uint32_t sample_index, float * out_xy);
+/* BSDF.h: one BSDF's eval / sample on the probe records of rt_bsdf_eval / rt_bsdf_sample (24 floats in, 12 out per probe), set up as
+ * shade_material sets it up; the scene gives the random numbers and the Kulla-Conty tables. -1 for an unknown material_type. */
+int oracle_bsdf_eval(const oracle_scene * scene, int material_type, const float * probes, size_t count, float * out);
+int oracle_bsdf_sample(const oracle_scene * scene, int material_type, const float * probes, size_t count, float * out);
 /* Pathtracer::render for one sample over pixels [pixel_offset, pixel_offset+pixel_count)
  * (Pathtracer.cpp:738-855): batches, bounces, accumulate or SVGF/TAA. */
 void oracle_render_sample(const oracle_scene * scene, oracle_frame * frame, int sample_index,

@@ -411,6 +411,66 @@ struct BSDFConductor : BSDFBase { // BSDF.h:405-525
 	bool allow_nee() const { return linear_roughness >= ROUGHNESS_CUTOFF; }
 };
 
+// oracle_bsdf_eval / oracle_bsdf_sample: the probe records of rt_bsdf_eval / rt_bsdf_sample (24 floats in, 12 out; see
+// include/gpu_raytracer_amd.h), each BSDF set up as shade_material sets it up, then its own eval or sample.
+template<typename BSDF, bool EVAL>
+void bsdf_probe(const oracle_scene & scene, const float * probes, size_t count, float * out) {
+	oracle_scene s = scene;
+	s.config.enable_svgf = 0;
+	oracle_frame no_frame = { };
+	Context c(s, no_frame);
+	for (size_t i = 0; i < count; i++) {
+		const float * a = probes + i * 24;
+		float * o = out + i * 12;
+		for (int k = 0; k < 12; k++) o[k] = 0.0f;
+		float3 normal = make_float3(a[8], a[9], a[10]), ray_direction = make_float3(a[11], a[12], a[13]);
+		bool entering_material = a[14] != 0.0f;
+		float3 tangent, bitangent;
+		orthonormal_basis(normal, tangent, bitangent);
+		float3 omega_i = world_to_local(-ray_direction, tangent, bitangent, normal);
+		o[10] = omega_i.z;
+		if (omega_i.z <= 0.0f) { o[0] = -1.0f; continue; }
+
+		BSDF bsdf;
+		bsdf.c = &c;
+		bsdf.pixel_index = int(float_as_uint(a[19])); bsdf.sample_index = int(float_as_uint(a[20])); bsdf.bounce = int(float_as_uint(a[21]));
+		bsdf.tangent = tangent; bsdf.bitangent = bitangent; bsdf.normal = normal; bsdf.omega_i = omega_i;
+		bsdf.material = a;
+		bsdf.init(entering_material);
+		float3 throughput = make_float3(1.0f);
+		if (BSDF::HAS_ALBEDO) {
+			TextureLOD lod = { make_float2(0.0f, 0.0f), make_float2(0.0f, 0.0f), 0.0f };
+			bsdf.calc_albedo(throughput, make_float2(0.0f, 0.0f), lod);
+		}
+		bool ok; float pdf = 0.0f; float3 value, direction_out; int medium_id = RT_INVALID;
+		if (EVAL) {
+			value = make_float3(0.0f);
+			direction_out = make_float3(a[15], a[16], a[17]);
+			ok = bsdf.eval(direction_out, a[18], value, pdf);
+		} else {
+			direction_out = make_float3(0.0f);
+			ok = bsdf.sample(throughput, medium_id, direction_out, pdf);
+			value = throughput;
+		}
+		o[0] = ok ? 1.0f : 0.0f;
+		o[1] = pdf;
+		o[2] = value.x; o[3] = value.y; o[4] = value.z;
+		o[5] = direction_out.x; o[6] = direction_out.y; o[7] = direction_out.z;
+		o[8] = float(medium_id);
+		o[9] = bsdf.allow_nee() ? 1.0f : 0.0f;
+	}
+}
+template<bool EVAL>
+int bsdf_probe(const oracle_scene & s, int material_type, const float * probes, size_t count, float * out) {
+	switch (material_type) {
+		case RT_MATERIAL_DIFFUSE:    bsdf_probe<BSDFDiffuse,    EVAL>(s, probes, count, out); return 0;
+		case RT_MATERIAL_PLASTIC:    bsdf_probe<BSDFPlastic,    EVAL>(s, probes, count, out); return 0;
+		case RT_MATERIAL_DIELECTRIC: bsdf_probe<BSDFDielectric, EVAL>(s, probes, count, out); return 0;
+		case RT_MATERIAL_CONDUCTOR:  bsdf_probe<BSDFConductor,  EVAL>(s, probes, count, out); return 0;
+	}
+	return -1;
+}
+
 // ---- SVGF g-buffers (SVGF.h:61-84), filled during shading ---------------------------------------------
 inline float2 oct_encode_normal(float3 n) { // Util.h:238-248
 	n /= (fabsf(n.x) + fabsf(n.y) + fabsf(n.z));
@@ -905,6 +965,13 @@ void oracle_generate(const oracle_scene * scene, int sample_index, int pixel_off
 		dx[index] = d.x; dy[index] = d.y; dz[index] = d.z;
 		pixel_index_and_flags[index] = uint32_t(pixel_index);
 	}
+}
+
+int oracle_bsdf_eval(const oracle_scene * scene, int material_type, const float * probes, size_t count, float * out) {
+	return bsdf_probe<true>(*scene, material_type, probes, count, out);
+}
+int oracle_bsdf_sample(const oracle_scene * scene, int material_type, const float * probes, size_t count, float * out) {
+	return bsdf_probe<false>(*scene, material_type, probes, count, out);
 }
 
 void oracle_random(const oracle_scene * scene, int dimension, const uint32_t * pixel_indices, size_t count,
