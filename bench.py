@@ -2,8 +2,14 @@
 """Headline benchmark: Mrays/s (primary + secondary) and ms/frame on Sponza 1920x1080, BVH8,
 diffuse + plastic materials, NEE + MIS + Russian roulette, 10 bounces, samples 0..3 (4 spp).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline needs and nothing else: it stages the scene, warms up, times the K steps, writes
+--dump-outputs and prints the line. --full adds every section that takes runs of its own after the timed region: the
+per-stage rooflines, the stream-bandwidth probe, the 9 points of view, the CPU baseline, BASELINE config 3, the
+reference's layout and the viewpoint-free seating, the hardware-counter passes and the one-GPU bound of the tile split
+(each can still be left out with its --no-* option).
 
 A "step" is one pass of the hot path over the whole frame = one sample per pixel:
 generate -> (trace, sort, shade, shadow-trace) x bounces -> accumulate (Pathtracer::render of the
@@ -22,7 +28,7 @@ separately in `config`.  `roofline` prices the dominant kernel (kernel_trace_bvh
 bytes (40 B per ray + 80 B per BVH8 node fetched + 48 B per triangle tested + 52 B
 per transformed instance entry + 4 B per identity entry, the node / triangle counts measured by the
 counting variant of the same kernel on the same rays) over its HIP-event time, against the 8 TB/s
-HBM3E peak of MI355X.  `cpu_baseline` times the CPU oracle (a port of the reference's device
+HBM3E peak of MI355X (its counter, stage and stream-bandwidth parts with --full).  `cpu_baseline` (--full) times the CPU oracle (a port of the reference's device
 traversal, OpenMP over rays) on a bounded sample of the same rays on this box's host cores, and
 the reference's own BVH builder (oracle/_ref, compiled verbatim) where it has been built.
 """
@@ -483,6 +489,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)   # 16 frames of 4 spp: the 9 fill / drain iterations of the wavefront are a small part of the launches
     ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every section that takes runs of its own (per-stage rooflines, stream bandwidth, points of view, CPU baseline, "
+                                                       "config 3, the reference's layout, hardware counters, the tile-split bound); the --no-* options below leave single sections out of a full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the hardware-counter passes (rocprofv3 --pmc re-runs of this benchmark: HBM traffic, VALU busy; N = 1 only)")
     ap.add_argument("--no-config3", action="store_true", help="skip the SVGF + TAA frames of BASELINE config 3 (N = 1 only)")
@@ -677,6 +685,8 @@ def main():
             grt.advance(ctx)
             drain_completions()
 
+    # Everything up to the timed region runs without --full too: the statistics pass counts the rays of the headline, and the untimed
+    # pass of the timed plan and the two profiled frames leave the wavefront (queues sized for the burst) as the timed steps expect it.
     # ---- untimed priming + warm-up: queues, sample frames and streams are allocated on first use (GBs of hipMalloc)
     run(submissions(max(args.warmup, SPP)))
     check(lib.rt_synchronize(ctx))
@@ -748,7 +758,7 @@ def main():
     elapsed = time.perf_counter() - t0
     if args.dump_outputs and rank == 0:   # before anything below renders into the framebuffer again
         dump_outputs(args.dump_outputs, pt)
-    if not events_in_timed_region and not os.environ.get("BENCH_NO_LAUNCH_TIMING"):
+    if args.full and not events_in_timed_region and not os.environ.get("BENCH_NO_LAUNCH_TIMING"):
         grt.set_profiling(ctx, 2)
         run(plan)
         check(lib.rt_synchronize(ctx))
@@ -758,7 +768,7 @@ def main():
 
     # ---- untimed repeat of the plan with HIP events around EVERY launch: what each stage of the step costs
     stages_raw = None
-    if merged and world == 1 and split_world == 1 and not args.no_stages:
+    if args.full and merged and world == 1 and split_world == 1 and not args.no_stages:
         grt.set_profiling(ctx, 3)
         run(plan)
         check(lib.rt_synchronize(ctx))
@@ -783,7 +793,9 @@ def main():
         # command (pmc_section: roofline.binding); every fraction in the record is <= 1. SURVEY 8d's figure -- algorithmic bytes over launch time over the HBM
         # peak -- is cache-served bytes here (a 31 MB tree) and lives under its own name, algorithmic_bytes_over_hbm_peak.
         roofline = {"bound": None, "achieved": None, "peak": None, "unit": None, "frac": None, "traffic": None}
-        if merged and len(launch_ms) == len(launch_bytes):
+        if not len(launch_ms):   # (a split run times its plan without per-launch events: their untimed repeat is part of --full)
+            roofline["note"] = "no per-launch durations: the timed region ran without HIP events around its launches and the untimed repeat that carries them runs with --full"
+        elif merged and len(launch_ms) == len(launch_bytes):
             # the dominant kernel: ONE fused traversal launch per iteration (closest-hit rays of every submission in flight +
             # the shadow rays of the previous iteration); bytes per launch from the counting variant of the same launches
             achieved = launch_bytes.sum() / (launch_ms.sum() * 1e-3) / 1e9
@@ -821,11 +833,11 @@ def main():
             "nodes_per_shadow_ray": round(sum(s["shadow"]["nodes"] for s in trace_rays_stat) / max(sum(shadow_per_sample), 1), 2),
             "triangles_per_shadow_ray": round(sum(s["shadow"]["triangles"] for s in trace_rays_stat) / max(sum(shadow_per_sample), 1), 2),
             "frame_alone_trace_ms_per_step": round(alone_trace_ms / SPP, 4),
-            "measured_stream_read_gbps": round(grt.measure_stream_bandwidth(ctx, 1 << 30, 5), 1),
         })
-        stream_gbps = roofline["measured_stream_read_gbps"]
-        if roofline.get("algorithmic_gbps"):   # the denominator SURVEY 8d names: what a streaming read reaches on THIS GPU
-            roofline["algorithmic_bytes_over_measured_stream_cache_served"] = round(roofline["algorithmic_gbps"] / stream_gbps, 4)
+        if args.full:   # (a probe of its own: five streaming reads of 1 GiB)
+            stream_gbps = roofline["measured_stream_read_gbps"] = round(grt.measure_stream_bandwidth(ctx, 1 << 30, 5), 1)
+            if roofline.get("algorithmic_gbps"):   # the denominator SURVEY 8d names: what a streaming read reaches on THIS GPU
+                roofline["algorithmic_bytes_over_measured_stream_cache_served"] = round(roofline["algorithmic_gbps"] / stream_gbps, 4)
         if stages_raw:
             trace_ms = float(grt.launch_timings(ctx, "trace").sum())
             stages = stage_rooflines(grt, ctx, counters_per_sample, plan, args.steps, stream_gbps)
@@ -861,7 +873,7 @@ def main():
             },
             "roofline": roofline,
         }
-        if world == 1 and split_world == 1 and not args.no_povs:
+        if args.full and world == 1 and split_world == 1 and not args.no_povs:
             # the reference's perf harness (Util/PerfTest.h): the same frame loop at its 9 fixed points of view
             povs = []
             camera_before = scene.get_camera()
@@ -885,19 +897,19 @@ def main():
                               "mrays_s_avg": round(float(mr_all.mean()), 1), "mrays_s_stddev": round(float(mr_all.std()), 1)}
         # (after the sweep: the oracle's 32 OpenMP threads linger on the host cores for a while, and a frame loop that shares them with the seating worker of the sweep
         # once showed one point of view at 4.7 ms per step for 1.25: profiles/r06_bench_run27.json)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(grt, pt, scene)
-        if world == 1 and split_world == 1 and merged and not args.no_config3 and (not os.environ.get("BENCH_PMC_CHILD") or os.environ.get("BENCH_PMC_CONFIG3")):   # (tools/svgf_counters.py profiles this section)
+        if args.full and world == 1 and split_world == 1 and merged and not args.no_config3 and (not os.environ.get("BENCH_PMC_CHILD") or os.environ.get("BENCH_PMC_CONFIG3")):   # (tools/svgf_counters.py profiles this section)
             pt.close(); pt = None   # (its queues and sample frames go back first)
             result["config3"] = config3_section(grt, scene, local_rank, stream_gbps)
-        if world == 1 and split_world == 1 and merged and args.merge_static and not args.no_reference_layout and not os.environ.get("BENCH_PMC_CHILD"):
+        if args.full and world == 1 and split_world == 1 and merged and args.merge_static and not args.no_reference_layout and not os.environ.get("BENCH_PMC_CHILD"):
             if pt is not None:
                 pt.close(); pt = None
             result["flatten_build_s"] = round(float(flatten_build_s), 3)
             result["reference_layout"] = reference_layout_section(grt, local_rank, args.steps, args.warmup)
             result["seating_without_viewpoint"] = viewpoint_free_section(grt, local_rank, args.steps, args.warmup)
             result["ms_per_step_seating_without_viewpoint"] = result["seating_without_viewpoint"]["ms_per_step"]   # (next to value / ms_per_step: VERDICT round 5, weak 7)
-        if world == 1 and split_world == 1 and merged and not args.no_pmc and not os.environ.get("BENCH_PMC_CHILD"):
+        if args.full and world == 1 and split_world == 1 and merged and not args.no_pmc and not os.environ.get("BENCH_PMC_CHILD"):
             # hardware counters of the same command (separate rocprofv3 --pmc passes); this process lets go of the GPU first
             if pt is not None:
                 pt.close()
@@ -936,7 +948,7 @@ def main():
                     r.update({"bound": "valu issue, mix-aware", "achieved": round(1.0 / mix["measured_cycles_per_instruction"], 4), "peak": round(1.0 / mix["best_cycles_per_instruction"]["classes_serial"], 4),
                               "unit": "vector wave-instructions per cycle and SIMD (x lane utilisation in frac)", "frac": mix["frac_classes_serial"]})
                 r["bound_is"] = "the unit of the dominant kernel closest to its roof (roofline.binding.utilisation_by_unit); no unit is saturated -- the launch is a chain of dependent node and triangle fetches"
-        if world == 1 and split_world == 1 and merged and not args.no_tile_split_bound and not os.environ.get("BENCH_PMC_CHILD"):
+        if args.full and world == 1 and split_world == 1 and merged and not args.no_tile_split_bound and not os.environ.get("BENCH_PMC_CHILD"):
             # No multi-GPU hardware has run this benchmark in any round (SCALE records: skipped). What ONE GPU can say about the tile split: rank 0's share of an N-way
             # split rendered alone (--emulate-world N: its tiles, pack + unpack of the exchange, no collective) -- the whole frame's ms per step over the rank's is a BOUND
             # of the speed-up N ranks can reach on this command (the all-gather itself, 33 MB per frame, comes on top). Child processes of this command, one at a time,
@@ -947,9 +959,9 @@ def main():
                 scene.close(); closed = True
             import subprocess
             bound = {"note": "rank 0's share of an N-way tile split rendered on this one GPU (bench.py --emulate-world N, same steps / warm-up); speedup_bound = this line's ms_per_step / the rank's: an upper bound, the collective is not in it", "ranks": []}
-            for n in (2, 4, 8):
+            for n in (2, 4, 8):   # (plain runs: without --full a child times its plan and prints its line, nothing else)
                 cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup), "--emulate-world", str(n), "--burst", str(args.burst),
-                       "--no-cpu-baseline", "--no-povs", "--no-pmc", "--no-config3", "--no-reference-layout", "--no-stages", "--no-tile-split-bound", "--merge-static", str(args.merge_static)]
+                       "--merge-static", str(args.merge_static)]
                 try:
                     child = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True, timeout=300, env=dict(os.environ, BENCH_PMC_CHILD="1"))
                     line = [l for l in child.stdout.splitlines() if l.startswith("{")]

@@ -7,7 +7,7 @@ and sums the counters per kernel from the rocpd database. bench.py calls run_pas
 
 HBM bytes: FETCH_SIZE / WRITE_SIZE are the L2's memory-side request counters in KB; on gfx950 a 128-B read request is
 tallied as 64 B (guide, "HBM"), other widths are uncalibrated -- so both are calibrated IN THE SAME RUN on kernels whose
-bytes are known: kernel_stream_read (1 GiB read by the stream-bandwidth probe of bench.py) and kernel_generate_stream
+bytes are known: kernel_stream_read (1 GiB read by the stream-bandwidth probe of bench.py --full) and kernel_generate_stream
 (28 B written per primary ray)."""
 import glob
 import json
@@ -69,7 +69,7 @@ def run_pass(counters, bench_args, timeout_s=240):
 def run_passes(steps, warmup, groups=None, extra_args=()):
     """Returns {"kernels": {kernel: {counter: [dispatches, sum]}}, "errors": [...]} over all passes."""
     merged, errors = {}, []
-    bench_args = ["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline", "--no-povs", "--no-pmc", "--no-stages", "--no-config3", "--no-reference-layout"] + list(extra_args)
+    bench_args = ["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--full", "--no-cpu-baseline", "--no-povs", "--no-pmc", "--no-stages", "--no-config3", "--no-reference-layout"] + list(extra_args)
     for group in (groups or DEFAULT_GROUPS):
         result, error = run_pass(group, bench_args)
         if result is None:

@@ -9,7 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import pmc_pass  # noqa: E402
 
-ARGS = ["--gpus", "1", "--steps", "4", "--warmup", "4", "--no-cpu-baseline", "--no-povs", "--no-pmc", "--no-stages", "--no-reference-layout"]
+ARGS = ["--gpus", "1", "--steps", "4", "--warmup", "4", "--full", "--no-cpu-baseline", "--no-povs", "--no-pmc", "--no-stages", "--no-reference-layout"]
 GROUPS = ["TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum", "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU SQ_WAIT_ANY GRBM_GUI_ACTIVE", "SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR"]
 PIXELS = 1920 * 1080
 
