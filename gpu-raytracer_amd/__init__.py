@@ -70,8 +70,8 @@ def device_lib():
         if not os.path.exists(DEVICE_LIB_PATH):
             raise DeviceLibraryMissing("%s is missing -- run `python __graft_entry__.py` (build()) first" % DEVICE_LIB_PATH)
         lib = ctypes.CDLL(DEVICE_LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        if hasattr(lib, "rt_abi_version") and lib.rt_abi_version() != 12:
-            raise DeviceLibraryMissing("%s has ABI version %d, this front end was written for 12 -- rebuild (python __graft_entry__.py)" % (DEVICE_LIB_PATH, lib.rt_abi_version()))
+        if hasattr(lib, "rt_abi_version") and lib.rt_abi_version() != 13:
+            raise DeviceLibraryMissing("%s has ABI version %d, this front end was written for 13 -- rebuild (python __graft_entry__.py)" % (DEVICE_LIB_PATH, lib.rt_abi_version()))
         lib.rt_last_error.restype = c_char_p
         lib.rt_last_error.argtypes = [c_void_p]
         lib.rt_version.restype = c_char_p
@@ -80,6 +80,7 @@ def device_lib():
         fp, u32p, u8p = POINTER(c_float), POINTER(c_uint32), POINTER(c_uint8)
         lib.rt_trace_rays.argtypes = [c_void_p] + [c_void_p] * 6 + [c_size_t, c_void_p, c_int, POINTER(c_float)]
         lib.rt_trace_shadow_rays.argtypes = [c_void_p] + [c_void_p] * 7 + [c_size_t, c_void_p, c_int, POINTER(c_float)]
+        lib.rt_trace_stream_rays.argtypes = [c_void_p, c_int] + [c_void_p] * 6 + [c_size_t, c_void_p] + [c_void_p] * 7 + [c_size_t, c_void_p, c_void_p, c_void_p]
         lib.rt_generate_rays.argtypes = [c_void_p, c_int, c_int, c_int] + [c_void_p] * 7
         lib.rt_random_samples.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_uint32, c_uint32, c_void_p]
         lib.rt_sample_texture.argtypes = [c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]
@@ -834,6 +835,28 @@ def trace_shadow_rays(ctx, origin, direction, max_distance, repeat=1):
     ms = c_float()
     _dev_check(ctx, device_lib().rt_trace_shadow_rays(ctx, o[0].ctypes.data, o[1].ctypes.data, o[2].ctypes.data, d[0].ctypes.data, d[1].ctypes.data, d[2].ctypes.data, m.ctypes.data, n, occluded.ctypes.data, repeat, byref(ms)))
     return occluded, ms.value
+
+
+def trace_stream_rays(ctx, iteration, origin, direction, hits, shadow_origin, shadow_direction, max_distance, counting=False):
+    """rt_trace_stream_rays: the merged wavefront's traversal launch on explicit rays. origin/direction (3, N) and shadow_origin /
+    shadow_direction (3, M) float32 SoA, max_distance (M,); `hits` (N, 4) uint32 is what the hit records hold before the launch.
+    Returns (hits, shadow_light float32[M], stats dict as get_trace_statistics or None, info int32[4])."""
+    o, d = _f32(origin).reshape(3, -1), _f32(direction).reshape(3, -1)
+    so, sd, m = _f32(shadow_origin).reshape(3, -1), _f32(shadow_direction).reshape(3, -1), _f32(max_distance).reshape(-1)
+    n, k = o.shape[1], so.shape[1]
+    if d.shape[1] != n or sd.shape[1] != k or m.size != k:
+        raise ValueError("trace_stream_rays: ray arrays of different lengths")
+    out = np.array(hits, np.uint32, order="C", copy=True).reshape(n, 4)
+    light = np.zeros(k, np.float32)
+    stats = np.zeros(10, np.uint64) if counting else None
+    info = np.zeros(4, np.int32)
+    _dev_check(ctx, device_lib().rt_trace_stream_rays(ctx, iteration, o[0].ctypes.data, o[1].ctypes.data, o[2].ctypes.data, d[0].ctypes.data, d[1].ctypes.data, d[2].ctypes.data, n, out.ctypes.data,
+                                                      so[0].ctypes.data, so[1].ctypes.data, so[2].ctypes.data, sd[0].ctypes.data, sd[1].ctypes.data, sd[2].ctypes.data, m.ctypes.data, k, light.ctypes.data,
+                                                      stats.ctypes.data if counting else None, info.ctypes.data))
+    if counting:
+        names = ("nodes", "triangles", "instances_transformed", "instances_identity", "rays")
+        stats = {kind: {name: int(stats[5 * j + i]) for i, name in enumerate(names)} for j, kind in enumerate(("closest", "shadow"))}
+    return out, light, stats, info
 
 
 def generate_rays(ctx, sample_index, pixel_offset, pixel_count):

@@ -1373,9 +1373,12 @@ static int trace_grid_size(const void * kernel) {
 
 // One launch of persistent kernel K. Its grid size is a function-local static of this instantiation: computed once per
 // kernel, also when several submitting threads arrive together (FrameSplit).
-template<auto K, typename... A> static void launch_persistent(hipStream_t stream, const A &... args) {
+template<auto K> static int persistent_grid() {
 	static const int grid = trace_grid_size((const void *)K);
-	hipLaunchKernelGGL(K, dim3(grid), dim3(RT_TRACE_BLOCK), 0, stream, args...);
+	return grid;
+}
+template<auto K, typename... A> static void launch_persistent(hipStream_t stream, const A &... args) {
+	hipLaunchKernelGGL(K, dim3(persistent_grid<K>()), dim3(RT_TRACE_BLOCK), 0, stream, args...);
 }
 // The kernel of the context's BVH type: p.bvh_width 2 or 4, else the CWBVH.
 template<auto K2, auto K4, auto K8, typename... A> static void launch_for_width(const RtParams & p, hipStream_t stream, const A &... args) {
@@ -1399,6 +1402,17 @@ void rt_launch_trace_stream(const RtParams & p, unsigned long long * stats, hipS
 		if (rt_skip_walk(p)) launch_persistent<kernel_trace_stream_bvh8_flat_skip>(stream, p);
 		else launch_persistent<kernel_trace_stream_bvh8_flat>(stream, p);
 	} else launch_persistent<kernel_trace_stream_bvh8>(stream, p);
+}
+// What rt_launch_trace_stream launches for p (the same choice, made on the host): info[0] the kernel (RT_STREAM_KERNEL_*), info[1] the waves
+// of its persistent grid, info[2] RT_NARROW_MAX_RAYS, info[3] RT_MIXED_MAX_RAYS. For rt_trace_stream_rays, which reports it to tests.
+void rt_trace_stream_launch_info(const RtParams & p, bool stats, int32_t * info) {
+	int kernel, grid;
+	if (stats) { kernel = RT_STREAM_KERNEL_COUNTING; grid = persistent_grid<kernel_trace_stream_bvh8_counting>(); }
+	else if (p.entry_tlas_stack_size == 0 && p.geometry_below_4gib) {
+		if (rt_skip_walk(p)) { kernel = RT_STREAM_KERNEL_FLAT_SKIP; grid = persistent_grid<kernel_trace_stream_bvh8_flat_skip>(); }
+		else { kernel = RT_STREAM_KERNEL_FLAT; grid = persistent_grid<kernel_trace_stream_bvh8_flat>(); }
+	} else { kernel = RT_STREAM_KERNEL_GENERAL; grid = persistent_grid<kernel_trace_stream_bvh8>(); }
+	info[0] = kernel; info[1] = grid * (RT_TRACE_BLOCK / RT_WAVE_SIZE); info[2] = RT_NARROW_MAX_RAYS; info[3] = RT_MIXED_MAX_RAYS;
 }
 void rt_launch_trace_counting(const RtParams & p, int bounce, unsigned long long * stats, hipStream_t stream) {
 	launch_persistent<kernel_trace_bvh8_counting>(stream, p, bounce, stats);

@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -2632,6 +2633,81 @@ int rt_trace_shadow_rays(rt_context * ctx, const float * ox, const float * oy, c
 
 	s = time_explicit_launches(ctx, repeat, out_ms, [&] { rt_launch_trace_shadow_explicit(ctx->params, o, d, dev_max, dev_occ, int(ray_count), ctx->explicit_retired, ctx->stream); }); if (s) return s;
 	RT_HIP(ctx, hipMemcpy(occluded, dev_occ, ray_count, hipMemcpyDeviceToHost));
+	return RT_OK;
+}
+
+// rt_trace_stream_rays: the merged wavefront's traversal launch (rt_launch_trace_stream, as stream_enqueue_iteration calls it) on explicit
+// rays. The parameter block is stream_params(ctx, iteration) with the closest-hit queue of parity iteration & 1, the shadow queue, the
+// control block and the radiance frame replaced by buffers of this call; every shadow ray i carries illumination (1, 0, 0) for pixel i,
+// so what the launch adds to pixel i tells how often ray i reached its light unoccluded. Runs on the wavefront's own stream with its own
+// spill area, after quiesce(); nothing of the context changes but what the scheduler would set up itself (stream_create, stream_sync_tlas).
+int rt_trace_stream_rays(rt_context * ctx, int iteration,
+                         const float * ox, const float * oy, const float * oz, const float * dx, const float * dy, const float * dz,
+                         size_t closest_count, uint32_t * hits,
+                         const float * sox, const float * soy, const float * soz, const float * sdx, const float * sdy, const float * sdz,
+                         const float * max_distance, size_t shadow_count, float * shadow_light,
+                         uint64_t * stats10, int32_t * info) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_trace_stream_rays: NULL context");
+	RT_REQUIRE(ctx, info != nullptr, "rt_trace_stream_rays: NULL info");
+	RT_REQUIRE(ctx, iteration >= 0, "rt_trace_stream_rays: negative iteration");
+	RT_REQUIRE(ctx, closest_count == 0 || (ox && oy && oz && dx && dy && dz && hits), "rt_trace_stream_rays: NULL closest-hit ray or hit array");
+	RT_REQUIRE(ctx, shadow_count == 0 || (sox && soy && soz && sdx && sdy && sdz && max_distance && shadow_light), "rt_trace_stream_rays: NULL shadow ray, max_distance or shadow_light array");
+	RT_REQUIRE(ctx, closest_count + shadow_count <= size_t(1) << 28, "rt_trace_stream_rays: more than 2^28 rays in one launch");
+	(void)hipSetDevice(ctx->device);
+	RT_HIP(ctx, quiesce(ctx)); // the wavefront's stream and spill area are borrowed
+	int s = check_ready(ctx, "rt_trace_stream_rays", NEED_SCENE_JOINT); if (s) return s;
+	if (ctx->params.bvh_width != 8) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_trace_stream_rays: the merged wavefront's launch walks the CWBVH (bvh_width %d)", ctx->params.bvh_width);
+	s = stream_create(ctx); if (s) return s;
+	s = stream_sync_tlas(ctx); if (s) return s;
+	PathStream & ps = ctx->path_stream;
+	const int q = iteration & 1;
+
+	TempBuffers tmp(ctx);
+	const size_t cb = closest_count * 4, sb = shadow_count * 4;
+	RtTraceBuffer trace = { };
+	trace.origin    = { (float *)tmp.get(cb, ox), (float *)tmp.get(cb, oy), (float *)tmp.get(cb, oz) };
+	trace.direction = { (float *)tmp.get(cb, dx), (float *)tmp.get(cb, dy), (float *)tmp.get(cb, dz) };
+	trace.hits = (uint4 *)tmp.get(closest_count * 16, hits);   // the caller's values: a sentinel shows a ray the launch never dealt
+	std::vector<float4> light(shadow_count);
+	for (size_t i = 0; i < shadow_count; i++) {   // (i < 2^28: RT_SHADOW_FLAG_BOUNCE_0 clear)
+		uint32_t pixel_word = uint32_t(i); float w; memcpy(&w, &pixel_word, 4);
+		light[i] = make_float4(1.0f, 0.0f, 0.0f, w);
+	}
+	RtShadowBuffer shadow = { };
+	shadow.origin    = { (float *)tmp.get(sb, sox), (float *)tmp.get(sb, soy), (float *)tmp.get(sb, soz) };
+	shadow.direction = { (float *)tmp.get(sb, sdx), (float *)tmp.get(sb, sdy), (float *)tmp.get(sb, sdz) };
+	shadow.max_distance = (float *)tmp.get(sb, max_distance);
+	shadow.illumination_and_pixel_index = (float4 *)tmp.get(shadow_count * 16, light.data());
+	float4 * radiance = (float4 *)tmp.get(shadow_count * 16, nullptr);
+	std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());   // (value-initialised: zero cursors and region words)
+	control_host->trace_count[q] = int(closest_count);
+	control_host->shadow_count[q ^ 1] = int(shadow_count);
+	RtStreamControl * control = (RtStreamControl *)tmp.get(sizeof(RtStreamControl), control_host.get());
+	unsigned long long * stats = stats10 ? (unsigned long long *)tmp.get(10 * sizeof(unsigned long long), nullptr) : nullptr;
+	if (!trace.origin.x || !trace.origin.y || !trace.origin.z || !trace.direction.x || !trace.direction.y || !trace.direction.z || !trace.hits ||
+	    !shadow.origin.x || !shadow.origin.y || !shadow.origin.z || !shadow.direction.x || !shadow.direction.y || !shadow.direction.z ||
+	    !shadow.max_distance || !shadow.illumination_and_pixel_index || !radiance || !control || (stats10 && !stats))
+		return fail(ctx, RT_ERROR_HIP, "rt_trace_stream_rays: device allocation failed");
+	if (shadow_count) RT_HIP(ctx, hipMemset(radiance, 0, shadow_count * 16));
+	if (stats) RT_HIP(ctx, hipMemset(stats, 0, 10 * sizeof(unsigned long long)));
+
+	RtParams p = stream_params(ctx, iteration);
+	p.trace[q] = trace;
+	p.shadow = shadow;
+	p.stream = control;
+	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = nullptr;
+	p.aovs[RT_AOV_RADIANCE].framebuffer = radiance;
+	rt_trace_stream_launch_info(p, stats != nullptr, info);
+	rt_launch_trace_stream(p, stats, ps.stream);
+	RT_HIP(ctx, hipGetLastError());
+	RT_HIP(ctx, hipStreamSynchronize(ps.stream));
+	if (closest_count) RT_HIP(ctx, hipMemcpy(hits, trace.hits, closest_count * 16, hipMemcpyDeviceToHost));
+	if (shadow_count) {
+		std::vector<float4> added(shadow_count);
+		RT_HIP(ctx, hipMemcpy(added.data(), radiance, shadow_count * 16, hipMemcpyDeviceToHost));
+		for (size_t i = 0; i < shadow_count; i++) shadow_light[i] = added[i].x;
+	}
+	if (stats10) RT_HIP(ctx, hipMemcpy(stats10, stats, 10 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
 	return RT_OK;
 }
 

@@ -257,6 +257,8 @@ void rt_launch_trace(const RtParams & p, int bounce, hipStream_t stream);
 void rt_launch_generate_stream(const RtParams & p, int sample_index, int pixel_offset, int pixel_count, int slot_base, int queue_offset, int block_width, int band_rows, hipStream_t stream);
 void rt_launch_stream_advance(RtStreamControl * control, int iteration, int generated, int * progress, int reset_ring_first, int reset_ring_count, hipStream_t stream);
 void rt_launch_trace_stream(const RtParams & p, unsigned long long * stats, hipStream_t stream);
+enum { RT_STREAM_KERNEL_GENERAL = 0, RT_STREAM_KERNEL_FLAT = 1, RT_STREAM_KERNEL_FLAT_SKIP = 2, RT_STREAM_KERNEL_COUNTING = 3 };
+void rt_trace_stream_launch_info(const RtParams & p, bool stats, int32_t * info);   // the kernel rt_launch_trace_stream picks, its grid in waves, the two engine limits
 void rt_launch_sort_stream(const RtParams & p, hipStream_t stream);
 void rt_launch_material_stream(const RtParams & p, int material_slot, hipStream_t stream);
 void rt_launch_trace_shadow(const RtParams & p, int bounce, hipStream_t stream);

@@ -151,8 +151,9 @@ const char * rt_version(void);
  *  10  rt_read_svgf_state and the RT_SVGF_STATE_* images it reads (additions only)
  *  11  rt_set_sky_sampling, rt_get_sky_sampling, rt_sample_sky_distribution, rt_sky_pdf (additions only; sky importance sampling, off by default)
  *  12  rt_bsdf_eval, rt_bsdf_sample (additions only)
+ *  13  rt_trace_stream_rays (additions only)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
-#define RT_ABI_VERSION 12
+#define RT_ABI_VERSION 13
 int rt_abi_version(void);
 
 /* ---- scene upload ------------------------------------------------------------------- */
@@ -524,6 +525,19 @@ int rt_trace_rays(rt_context * ctx, const float * ox, const float * oy, const fl
 int rt_trace_shadow_rays(rt_context * ctx, const float * ox, const float * oy, const float * oz,
                          const float * dx, const float * dy, const float * dz, const float * max_distance,
                          size_t ray_count, uint8_t * occluded, int repeat, float * out_ms);
+/* The merged wavefront's traversal launch (the frame's own kernel and engine choice) on explicit rays (synchronous; CWBVH only).
+ * `iteration`: its parity picks the queue and cursor halves. closest_count rays (ox..dz) write hits (uint32[4] each as
+ * rt_trace_rays; the array is uploaded first, so a value the launch never overwrites stays). shadow_count rays (sox..sdz,
+ * max_distance) each carry illumination (1, 0, 0) for pixel i: shadow_light[i] is what the launch added, 0 occluded, 1 not
+ * (2 or more: the ray was dealt twice). stats10: NULL for the frame's kernel, else the counting kernel runs and its 10 counters
+ * ({nodes, triangles, transformed, identity instance entries, rays} x {closest, shadow}) are returned. info: 4 ints {kernel (0 general,
+ * 1 flat, 2 flat skipping, 3 counting), waves of its persistent grid, RT_NARROW_MAX_RAYS, RT_MIXED_MAX_RAYS}. Leaves no state a frame reads. */
+int rt_trace_stream_rays(rt_context * ctx, int iteration,
+                         const float * ox, const float * oy, const float * oz, const float * dx, const float * dy, const float * dz,
+                         size_t closest_count, uint32_t * hits,
+                         const float * sox, const float * soy, const float * soz, const float * sdx, const float * sdy, const float * sdz,
+                         const float * max_distance, size_t shadow_count, float * shadow_light,
+                         uint64_t * stats10, int32_t * info);
 /* kernel_generate only: writes the primary rays of pixels [offset, offset+count).          */
 int rt_generate_rays(rt_context * ctx, int sample_index, int pixel_offset, int pixel_count,
                      float * ox, float * oy, float * oz, float * dx, float * dy, float * dz,

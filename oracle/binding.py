@@ -100,6 +100,8 @@ def lib():
         l = ctypes.CDLL(ORACLE_LIB_PATH)
         l.oracle_trace.argtypes = [POINTER(OracleScene)] + [c_void_p] * 6 + [c_size_t, c_void_p, POINTER(TraceStats), c_int]
         l.oracle_trace_shadow.argtypes = [POINTER(OracleScene)] + [c_void_p] * 7 + [c_size_t, c_void_p, POINTER(TraceStats), c_int]
+        l.oracle_trace_with_depth.argtypes = [POINTER(OracleScene)] + [c_void_p] * 6 + [c_size_t, c_void_p, POINTER(TraceStats), POINTER(c_uint64), c_int]
+        l.oracle_trace_shadow_with_depth.argtypes = [POINTER(OracleScene)] + [c_void_p] * 7 + [c_size_t, c_void_p, POINTER(TraceStats), POINTER(c_uint64), c_int]
         l.oracle_generate.argtypes = [POINTER(OracleScene), c_int, c_int, c_int] + [c_void_p] * 7
         l.oracle_random.argtypes = [POINTER(OracleScene), c_int, c_void_p, c_size_t, c_uint32, c_uint32, c_void_p]
         l.oracle_render_sample.argtypes = [POINTER(OracleScene), POINTER(OracleFrame), c_int, c_int, c_int, POINTER(OracleCounters), c_int]
@@ -644,16 +646,18 @@ class SceneView:
         o = np.ascontiguousarray(origin, np.float32); d = np.ascontiguousarray(direction, np.float32)
         n = o.shape[1]
         hits = np.zeros((n, 4), np.uint32)
-        stats = TraceStats()
-        lib().oracle_trace(byref(self.scene), o[0].ctypes.data, o[1].ctypes.data, o[2].ctypes.data, d[0].ctypes.data, d[1].ctypes.data, d[2].ctypes.data, n, hits.ctypes.data, byref(stats), threads)
+        stats = TraceStats(); depth = c_uint64()
+        lib().oracle_trace_with_depth(byref(self.scene), o[0].ctypes.data, o[1].ctypes.data, o[2].ctypes.data, d[0].ctypes.data, d[1].ctypes.data, d[2].ctypes.data, n, hits.ctypes.data, byref(stats), byref(depth), threads)
+        stats.max_stack = depth.value   # the deepest traversal stack of any ray (oracle.h: oracle_trace_with_depth)
         return hits, stats
 
     def trace_shadow(self, origin, direction, max_distance, threads=0):
         o = np.ascontiguousarray(origin, np.float32); d = np.ascontiguousarray(direction, np.float32); m = np.ascontiguousarray(max_distance, np.float32)
         n = o.shape[1]
         occ = np.zeros(n, np.uint8)
-        stats = TraceStats()
-        lib().oracle_trace_shadow(byref(self.scene), o[0].ctypes.data, o[1].ctypes.data, o[2].ctypes.data, d[0].ctypes.data, d[1].ctypes.data, d[2].ctypes.data, m.ctypes.data, n, occ.ctypes.data, byref(stats), threads)
+        stats = TraceStats(); depth = c_uint64()
+        lib().oracle_trace_shadow_with_depth(byref(self.scene), o[0].ctypes.data, o[1].ctypes.data, o[2].ctypes.data, d[0].ctypes.data, d[1].ctypes.data, d[2].ctypes.data, m.ctypes.data, n, occ.ctypes.data, byref(stats), byref(depth), threads)
+        stats.max_stack = depth.value
         return occ, stats
 
     def generate(self, sample_index, pixel_offset, pixel_count):

@@ -148,6 +148,16 @@ void oracle_trace(const oracle_scene * scene, const float * ox, const float * oy
 void oracle_trace_shadow(const oracle_scene * scene, const float * ox, const float * oy, const float * oz,
                          const float * dx, const float * dy, const float * dz, const float * max_distance,
                          size_t ray_count, uint8_t * occluded, oracle_trace_stats * stats, int threads);
+/* The same two walks, and *max_stack = the deepest traversal stack any ray of the batch reached, TLAS entries included. For the
+ * CWBVH that is what the device's per-lane stack holds (kernels_trace.hip pushes at the same two sites, in the wide and the narrow
+ * engine alike), which must stay within RT_STACK_SIZE = 32: the device does not check its spill index. BVH2 / BVH4: the depth of
+ * their own stacks. (A separate out-parameter: oracle_trace_stats and oracle_counters keep their layout.) */
+void oracle_trace_with_depth(const oracle_scene * scene, const float * ox, const float * oy, const float * oz,
+                             const float * dx, const float * dy, const float * dz, size_t ray_count,
+                             uint32_t * hits, oracle_trace_stats * stats, uint64_t * max_stack, int threads);
+void oracle_trace_shadow_with_depth(const oracle_scene * scene, const float * ox, const float * oy, const float * oz,
+                                    const float * dx, const float * dy, const float * dz, const float * max_distance,
+                                    size_t ray_count, uint8_t * occluded, oracle_trace_stats * stats, uint64_t * max_stack, int threads);
 /* Threads a call with threads <= 0 uses: ORACLE_THREADS, else min(omp_get_max_threads(), 32). (A GPU box shows 256 logical
  * CPUs to the container and gives it about 16 cores' worth: the traversal loop peaks at 16-32 threads, 8 Mrays/s, and
  * falls to 3.5 Mrays/s at 256.) */

@@ -61,7 +61,7 @@ inline unsigned ray_get_octant_inv4(float3 d) {
 	return (d.x < 0.0f ? 0 : 0x04040404) | (d.y < 0.0f ? 0 : 0x02020202) | (d.z < 0.0f ? 0 : 0x01010101);
 }
 
-struct Counters { uint64_t nodes = 0, triangles = 0, inst_xform = 0, inst_ident = 0, groups_skipped = 0; };
+struct Counters { uint64_t nodes = 0, triangles = 0, inst_xform = 0, inst_ident = 0, groups_skipped = 0; int max_stack = 0; };
 
 // Triangle.h:148-174. f = 1/a is an IEEE division (the reference's fast-math reciprocal
 // is not specified); acceptance tests are literal: 0<=u<=1, v>=0, u+v<=1, 0<t<t_best.
@@ -206,7 +206,11 @@ inline bool bvh8_traverse(const oracle_scene & s, Ray ray, float max_distance, R
 	int  mesh_id = 0;
 	bool mesh_has_identity_transform = true;
 
-	auto push = [&](Group g) { if (stack_size >= ORACLE_STACK_SIZE) { fprintf(stderr, "oracle: traversal stack overflow\n"); abort(); } stack[stack_size++] = g; };
+	auto push = [&](Group g) {
+		if (stack_size >= ORACLE_STACK_SIZE) { fprintf(stderr, "oracle: traversal stack overflow\n"); abort(); }
+		stack[stack_size++] = g;
+		if (stack_size > c.max_stack) c.max_stack = stack_size;
+	};
 
 	if (s.static_whole_scene) tlas_stack_size = 0; // rt_set_static_geometry: node 0 is the root of the one world-space tree, the ray is inside it (row 0) from the start
 
@@ -327,6 +331,7 @@ inline bool bvh2_traverse(const oracle_scene & s, Ray ray, float max_distance, R
 	int stack[ORACLE_STACK_SIZE];
 	int stack_size = 1;
 	stack[0] = 0;
+	c.max_stack = c.max_stack > 1 ? c.max_stack : 1;
 
 	Ray ray_untransformed = ray;
 	float3 inv_dir = reciprocal(ray.direction);
@@ -363,6 +368,7 @@ inline bool bvh2_traverse(const oracle_scene & s, Ray ray, float max_distance, R
 						c.inst_xform++;
 					} else c.inst_ident++;
 					stack[stack_size++] = int(root & 0x7fffffffu);
+					if (stack_size > c.max_stack) c.max_stack = stack_size;
 				} else {
 					for (int i = node.left_or_first; i < node.left_or_first + int(count); i++) {
 						c.triangles++;
@@ -378,6 +384,7 @@ inline bool bvh2_traverse(const oracle_scene & s, Ray ray, float max_distance, R
 				if (stack_size + 2 > ORACLE_STACK_SIZE) { fprintf(stderr, "oracle: traversal stack overflow\n"); abort(); }
 				stack[stack_size++] = second;
 				stack[stack_size++] = first;
+				if (stack_size > c.max_stack) c.max_stack = stack_size;
 			}
 		}
 		if (stack_size == 0) return false;
@@ -414,6 +421,7 @@ inline bool bvh4_traverse(const oracle_scene & s, Ray ray, float max_distance, R
 	unsigned stack[ORACLE_STACK_SIZE];
 	int stack_size = 1;
 	stack[0] = 1; // node 1, child 0: the entry point whose child is the root (BVH4Converter.cpp:8-12)
+	c.max_stack = c.max_stack > 1 ? c.max_stack : 1;
 
 	Ray ray_untransformed = ray;
 	float3 inv_dir = reciprocal(ray.direction);
@@ -448,6 +456,7 @@ inline bool bvh4_traverse(const oracle_scene & s, Ray ray, float max_distance, R
 					c.inst_xform++;
 				} else c.inst_ident++;
 				stack[stack_size++] = (root & 0x7fffffffu) + 1u; // the BLAS's own entry node
+				if (stack_size > c.max_stack) c.max_stack = stack_size;
 			} else {
 				for (int j = index; j < index + count; j++) {
 					c.triangles++;
@@ -466,6 +475,7 @@ inline bool bvh4_traverse(const oracle_scene & s, Ray ray, float max_distance, R
 				if (hits.hit[id]) {
 					if (stack_size + 1 > ORACLE_STACK_SIZE) { fprintf(stderr, "oracle: traversal stack overflow\n"); abort(); }
 					stack[stack_size++] = (unsigned(id) << 30) | unsigned(child);
+					if (stack_size > c.max_stack) c.max_stack = stack_size;
 				}
 			}
 		}
@@ -480,8 +490,8 @@ inline void store_hit(uint32_t * out, const RayHit & h) { // Buffers.h:25-32
 
 } // namespace
 
-// Exposed to the path tracing restatement (oracle_pathtrace.cpp)
-void oracle_trace_one(const oracle_scene & s, float3 origin, float3 direction, uint32_t * hit4, oracle_trace_stats * stats) {
+// One ray; *depth (if given) rises to the deepest stack the walk reached
+static void trace_one(const oracle_scene & s, float3 origin, float3 direction, uint32_t * hit4, oracle_trace_stats * stats, int * depth) {
 	Ray ray = { origin, direction };
 	RayHit hit; hit.t = INFINITY; hit.u = 0.0f; hit.v = 0.0f; hit.mesh_id = 0; hit.triangle_id = RT_INVALID;
 	Counters c;
@@ -492,55 +502,79 @@ void oracle_trace_one(const oracle_scene & s, float3 origin, float3 direction, u
 	}
 	store_hit(hit4, hit);
 	if (stats) { stats->nodes += c.nodes; stats->triangles += c.triangles; stats->instances_transformed += c.inst_xform; stats->instances_identity += c.inst_ident; stats->rays++; }
+	if (depth && c.max_stack > *depth) *depth = c.max_stack;
 }
 
-bool oracle_trace_shadow_one(const oracle_scene & s, float3 origin, float3 direction, float max_distance, oracle_trace_stats * stats) {
+static bool trace_shadow_one(const oracle_scene & s, float3 origin, float3 direction, float max_distance, oracle_trace_stats * stats, int * depth) {
 	Ray ray = { origin, direction };
 	RayHit hit; hit.t = INFINITY; hit.u = hit.v = 0.0f; hit.mesh_id = 0; hit.triangle_id = RT_INVALID;
 	Counters c;
 	bool occluded = s.bvh_type == 2 ? bvh2_traverse<true>(s, ray, max_distance, hit, c) : (s.bvh_type == 4 ? bvh4_traverse<true>(s, ray, max_distance, hit, c) : bvh8_traverse<true>(s, ray, max_distance, hit, c));
 	if (stats) { stats->nodes += c.nodes; stats->triangles += c.triangles; stats->instances_transformed += c.inst_xform; stats->instances_identity += c.inst_ident; stats->rays++; }
+	if (depth && c.max_stack > *depth) *depth = c.max_stack;
 	return occluded;
 }
+
+// Exposed to the path tracing restatement (oracle_pathtrace.cpp)
+void oracle_trace_one(const oracle_scene & s, float3 origin, float3 direction, uint32_t * hit4, oracle_trace_stats * stats) { trace_one(s, origin, direction, hit4, stats, nullptr); }
+bool oracle_trace_shadow_one(const oracle_scene & s, float3 origin, float3 direction, float max_distance, oracle_trace_stats * stats) { return trace_shadow_one(s, origin, direction, max_distance, stats, nullptr); }
 
 extern "C" {
 
 const char * oracle_version(void) { return "gpu-raytracer oracle 0.1 (CPU restatement; test infrastructure)"; }
 
-void oracle_trace(const oracle_scene * scene, const float * ox, const float * oy, const float * oz,
-                  const float * dx, const float * dy, const float * dz, size_t ray_count,
-                  uint32_t * hits, oracle_trace_stats * stats, int threads) {
+void oracle_trace_with_depth(const oracle_scene * scene, const float * ox, const float * oy, const float * oz,
+                             const float * dx, const float * dy, const float * dz, size_t ray_count,
+                             uint32_t * hits, oracle_trace_stats * stats, uint64_t * max_stack, int threads) {
 	if (threads <= 0) threads = oracle_default_threads();
 	oracle_trace_stats total = { 0, 0, 0, 0, 0 };
+	int deepest = 0;
 	#pragma omp parallel num_threads(threads)
 	{
 		oracle_trace_stats local = { 0, 0, 0, 0, 0 };
+		int local_depth = 0;
 		#pragma omp for schedule(dynamic, 1024)
 		for (long long i = 0; i < (long long)ray_count; i++) {
-			oracle_trace_one(*scene, make_float3(ox[i], oy[i], oz[i]), make_float3(dx[i], dy[i], dz[i]), hits + 4 * i, &local);
+			trace_one(*scene, make_float3(ox[i], oy[i], oz[i]), make_float3(dx[i], dy[i], dz[i]), hits + 4 * i, &local, &local_depth);
 		}
 		#pragma omp critical
-		{ total.nodes += local.nodes; total.triangles += local.triangles; total.instances_transformed += local.instances_transformed; total.instances_identity += local.instances_identity; total.rays += local.rays; }
+		{ total.nodes += local.nodes; total.triangles += local.triangles; total.instances_transformed += local.instances_transformed; total.instances_identity += local.instances_identity; total.rays += local.rays; if (local_depth > deepest) deepest = local_depth; }
 	}
 	if (stats) *stats = total;
+	if (max_stack) *max_stack = uint64_t(deepest);
+}
+
+void oracle_trace(const oracle_scene * scene, const float * ox, const float * oy, const float * oz,
+                  const float * dx, const float * dy, const float * dz, size_t ray_count,
+                  uint32_t * hits, oracle_trace_stats * stats, int threads) {
+	oracle_trace_with_depth(scene, ox, oy, oz, dx, dy, dz, ray_count, hits, stats, nullptr, threads);
+}
+
+void oracle_trace_shadow_with_depth(const oracle_scene * scene, const float * ox, const float * oy, const float * oz,
+                                    const float * dx, const float * dy, const float * dz, const float * max_distance,
+                                    size_t ray_count, uint8_t * occluded, oracle_trace_stats * stats, uint64_t * max_stack, int threads) {
+	if (threads <= 0) threads = oracle_default_threads();
+	oracle_trace_stats total = { 0, 0, 0, 0, 0 };
+	int deepest = 0;
+	#pragma omp parallel num_threads(threads)
+	{
+		oracle_trace_stats local = { 0, 0, 0, 0, 0 };
+		int local_depth = 0;
+		#pragma omp for schedule(dynamic, 1024)
+		for (long long i = 0; i < (long long)ray_count; i++) {
+			occluded[i] = trace_shadow_one(*scene, make_float3(ox[i], oy[i], oz[i]), make_float3(dx[i], dy[i], dz[i]), max_distance[i], &local, &local_depth) ? 1 : 0;
+		}
+		#pragma omp critical
+		{ total.nodes += local.nodes; total.triangles += local.triangles; total.instances_transformed += local.instances_transformed; total.instances_identity += local.instances_identity; total.rays += local.rays; if (local_depth > deepest) deepest = local_depth; }
+	}
+	if (stats) *stats = total;
+	if (max_stack) *max_stack = uint64_t(deepest);
 }
 
 void oracle_trace_shadow(const oracle_scene * scene, const float * ox, const float * oy, const float * oz,
                          const float * dx, const float * dy, const float * dz, const float * max_distance,
                          size_t ray_count, uint8_t * occluded, oracle_trace_stats * stats, int threads) {
-	if (threads <= 0) threads = oracle_default_threads();
-	oracle_trace_stats total = { 0, 0, 0, 0, 0 };
-	#pragma omp parallel num_threads(threads)
-	{
-		oracle_trace_stats local = { 0, 0, 0, 0, 0 };
-		#pragma omp for schedule(dynamic, 1024)
-		for (long long i = 0; i < (long long)ray_count; i++) {
-			occluded[i] = oracle_trace_shadow_one(*scene, make_float3(ox[i], oy[i], oz[i]), make_float3(dx[i], dy[i], dz[i]), max_distance[i], &local) ? 1 : 0;
-		}
-		#pragma omp critical
-		{ total.nodes += local.nodes; total.triangles += local.triangles; total.instances_transformed += local.instances_transformed; total.instances_identity += local.instances_identity; total.rays += local.rays; }
-	}
-	if (stats) *stats = total;
+	oracle_trace_shadow_with_depth(scene, ox, oy, oz, dx, dy, dz, max_distance, ray_count, occluded, stats, nullptr, threads);
 }
 
 } // extern "C"
