@@ -70,8 +70,8 @@ def device_lib():
         if not os.path.exists(DEVICE_LIB_PATH):
             raise DeviceLibraryMissing("%s is missing -- run `python __graft_entry__.py` (build()) first" % DEVICE_LIB_PATH)
         lib = ctypes.CDLL(DEVICE_LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        if hasattr(lib, "rt_abi_version") and lib.rt_abi_version() != 13:
-            raise DeviceLibraryMissing("%s has ABI version %d, this front end was written for 13 -- rebuild (python __graft_entry__.py)" % (DEVICE_LIB_PATH, lib.rt_abi_version()))
+        if hasattr(lib, "rt_abi_version") and lib.rt_abi_version() != 14:
+            raise DeviceLibraryMissing("%s has ABI version %d, this front end was written for 14 -- rebuild (python __graft_entry__.py)" % (DEVICE_LIB_PATH, lib.rt_abi_version()))
         lib.rt_last_error.restype = c_char_p
         lib.rt_last_error.argtypes = [c_void_p]
         lib.rt_version.restype = c_char_p
@@ -90,6 +90,8 @@ def device_lib():
         lib.rt_sky_pdf.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
         lib.rt_bsdf_eval.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p]
         lib.rt_bsdf_sample.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p]
+        lib.rt_upload_material_normal_maps.argtypes = [c_void_p, c_void_p, c_size_t]
+        lib.rt_perturb_normals.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p]
         lib.rt_set_sky_sampling.argtypes = [c_void_p, c_float]
         lib.rt_get_sky_sampling.argtypes = [c_void_p, POINTER(c_float)]
         lib.rt_measure_stream_bandwidth.argtypes = [c_void_p, c_size_t, c_int, POINTER(c_float)]
@@ -136,6 +138,10 @@ def host_lib():
         lib.grt_scene_get_camera.argtypes = [c_void_p, POINTER(c_float), POINTER(c_float), POINTER(c_float)]
         lib.grt_scene_set_material.argtypes = [c_void_p, c_int, c_int, POINTER(c_float), c_float]
         lib.grt_scene_material_type.argtypes = [c_void_p, c_int]
+        lib.grt_scene_material_normal_map.argtypes = [c_void_p, c_int]
+        lib.grt_scene_set_material_normal_map.argtypes = [c_void_p, c_int, c_int]
+        lib.grt_scene_add_texture.argtypes = [c_void_p, c_char_p, c_int]
+        lib.grt_scene_texture_compressed.argtypes = [c_void_p, c_int]
         lib.grt_mesh_data_array.restype = c_void_p
         lib.grt_mesh_data_array.argtypes = [c_void_p, c_int, c_char_p, POINTER(c_size_t)]
         lib.grt_scene_set_mesh_transform.argtypes = [c_void_p, c_int, POINTER(c_float), POINTER(c_float), c_float]
@@ -526,6 +532,33 @@ class Scene:
 
     def material_type(self, index):
         return host_lib().grt_scene_material_type(self.handle, index)
+
+    def material_normal_map(self, index):
+        """The texture index of material `index`'s tangent-space normal map, -1 for none (kept out of describe())."""
+        t = host_lib().grt_scene_material_normal_map(self.handle, index)
+        if t < -1:
+            raise RuntimeError(host_lib().grt_last_error().decode(errors="replace"))
+        return t
+
+    def set_material_normal_map(self, index, texture):
+        """Give material `index` the normal map `texture` (a texture index of this scene; -1: none). A Pathtracer sees it after
+        invalidate("materials") and update()."""
+        _host_check(host_lib().grt_scene_set_material_normal_map(self.handle, index, int(texture)))
+
+    def add_texture(self, filename, normal_map=False):
+        """Add an image file as a texture; normal_map=True loads it as data (no sRGB decode, never block-compressed). Returns its
+        index. Textures reach the device when a Pathtracer is created: add them before."""
+        t = host_lib().grt_scene_add_texture(self.handle, os.fsencode(filename), 1 if normal_map else 0)
+        if t < 0:
+            raise RuntimeError(host_lib().grt_last_error().decode(errors="replace"))
+        return t
+
+    def texture_compressed(self, index):
+        """True when texture `index` is kept as BC1 blocks (block compression), False for RGBA8 texels."""
+        c = host_lib().grt_scene_texture_compressed(self.handle, index)
+        if c < 0:
+            raise RuntimeError(host_lib().grt_last_error().decode(errors="replace"))
+        return bool(c)
 
 
 _ARRAY_DTYPES = {
@@ -934,6 +967,24 @@ def bsdf_sample(ctx, material_type, probes):
     """rt_bsdf_sample: the same BSDF's sample on (N, 24) probe records. Returns (N, 12) float32 {ok, pdf, throughput factor[3],
     direction[3], medium, allow_nee, omega_i.z, pad}."""
     return _bsdf_probe(ctx, device_lib().rt_bsdf_sample, material_type, probes)
+
+
+NORMAL_PROBE_IN = 48   # floats per probe record of rt_perturb_normals
+
+
+def perturb_normals(ctx, texture_index, probes):
+    """rt_perturb_normals: the shade kernels' normal-map perturbation with texture `texture_index` as the map, on (N, 48) probe
+    records (see include/gpu_raytracer_amd.h). Returns (N, 4) float32 {world shading normal[3], fell back (1) or mapped (0)}."""
+    p = _f32(probes).reshape(-1, NORMAL_PROBE_IN)
+    out = np.zeros((p.shape[0], 4), np.float32)
+    _dev_check(ctx, device_lib().rt_perturb_normals(ctx, int(texture_index), p.ctypes.data, p.shape[0], out.ctypes.data))
+    return out
+
+
+def upload_material_normal_maps(ctx, texture_ids):
+    """rt_upload_material_normal_maps: one texture id (-1: none) per uploaded material. Returns the status (0: RT_OK)."""
+    ids = np.ascontiguousarray(texture_ids, dtype=np.int32)
+    return device_lib().rt_upload_material_normal_maps(ctx, ids.ctypes.data if ids.size else None, ids.size)
 
 
 def _bsdf_probe(ctx, fn, material_type, probes):

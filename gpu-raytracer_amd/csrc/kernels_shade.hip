@@ -581,6 +581,7 @@ struct BSDFCommon {
 template<bool COMPRESSED>
 struct BSDFDiffuseT : BSDFCommon {
 	static constexpr bool HAS_ALBEDO = true;
+	static constexpr bool MAP_COMPRESSED = COMPRESSED;   // the texture instantiation a normal map is read with (the _nmap instances)
 	f3 diffuse; int texture_id; f3 albedo;
 	RT_DEV void init(const RtParams & p, bool, int material_id) { float4 m = p.materials[2 * material_id]; diffuse = mk3(m.x, m.y, m.z); texture_id = __float_as_int(m.w); }
 	RT_DEV void calc_albedo(const RtParams & p, f3 & throughput, f2 tex_coord, const TextureLOD & lod) {
@@ -610,6 +611,7 @@ typedef BSDFDiffuseT<true> BSDFDiffuse;
 template<bool COMPRESSED>
 struct BSDFPlasticT : BSDFCommon {
 	static constexpr bool HAS_ALBEDO = true;
+	static constexpr bool MAP_COMPRESSED = COMPRESSED;
 	static constexpr float IOR = 1.5f;
 	static constexpr float ETA = 1.0f / IOR;
 	f3 diffuse; int texture_id; float linear_roughness; f3 albedo;
@@ -692,6 +694,7 @@ typedef BSDFPlasticT<true> BSDFPlastic;
 
 struct BSDFDielectric : BSDFCommon {
 	static constexpr bool HAS_ALBEDO = false;
+	static constexpr bool MAP_COMPRESSED = false;   // (normal maps are RGBA8: rt_upload_material_normal_maps)
 	int medium_id_material; float ior, linear_roughness, eta;
 	RT_DEV void init(const RtParams & p, bool entering_material, int material_id) {
 		float4 m = p.materials[2 * material_id];
@@ -789,6 +792,7 @@ struct BSDFDielectric : BSDFCommon {
 
 struct BSDFConductor : BSDFCommon {
 	static constexpr bool HAS_ALBEDO = false;
+	static constexpr bool MAP_COMPRESSED = false;
 	f3 eta3, k3; float linear_roughness;
 	RT_DEV void init(const RtParams & p, bool, int material_id) {
 		float4 a = p.materials[2 * material_id], b = p.materials[2 * material_id + 1];
@@ -1041,7 +1045,9 @@ RT_DEV float ray_cone_get_lod(f3 ray_direction, f3 geometric_normal, float cone_
 // MERGED: the queue holds the surface hits of every submission in flight (see sort_rays); bounce and sample come
 // from the slot table, the launch arguments are ignored.
 // SKY: sky importance sampling is active (RtParams::sky_nee_share > 0): light samples go to the sky or the emitters, see next_event_estimation.
-template<typename BSDF, int SLOT, bool MERGED, bool SKY = false>
+// NMAP: some material of this slot has a normal map (RtParams::normal_map_slots): a hit whose material has one shades with the mapped
+// normal (normal_map_perturb); a hit whose material has none runs the arithmetic of the plain instance.
+template<typename BSDF, int SLOT, bool MERGED, bool SKY = false, bool NMAP = false>
 RT_DEV void shade_material(const RtParams & p, int launch_bounce, int launch_sample_index) {
 	const RtMaterialBuffer & q = p.material[SLOT];
 	const int iq = MERGED ? (p.stream_iteration & 1) : (launch_bounce & 1);
@@ -1116,6 +1122,13 @@ RT_DEV void shade_material(const RtParams & p, int launch_bounce, int launch_sam
 			curvature = triangle_get_curvature(tri.position_edge_1, tri.position_edge_2, tri.normal_edge_1, tri.normal_edge_2) * mesh_scale_inv;
 		}
 
+		// the normal map of the hit's material, and its tangent from the object-space triangle (before the edges go to world space)
+		int normal_map_id = RT_INVALID; f3 dpdu = mk3(0.0f); float uv_det = 0.0f;
+		if (NMAP) {
+			normal_map_id = p.material_normal_maps[p.mesh_material_ids[hit.mesh_id]];
+			if (normal_map_id != RT_INVALID) dpdu = m_direction(world, normal_map_dpdu(tri.position_edge_1, tri.position_edge_2, tri.tex_coord_edge_1, tri.tex_coord_edge_2, uv_det));
+		}
+
 		tri.position_edge_1 = m_direction(world, tri.position_edge_1);
 		tri.position_edge_2 = m_direction(world, tri.position_edge_2);
 
@@ -1126,38 +1139,53 @@ RT_DEV void shade_material(const RtParams & p, int launch_bounce, int launch_sam
 		bool entering_material = dot(ray_direction, geometric_normal) < 0.0f;
 		if (!entering_material) { normal = -normal; curvature = -curvature; }
 
+		// The texture footprint of the hit (ray cones): gradients at bounce 0, a level of detail after that. Computed once, for the
+		// albedo and the normal map alike.
+		TextureLOD lod = { mk2(0.0f, 0.0f), mk2(0.0f, 0.0f), 0.0f };
+		bool have_footprint = false;
+		auto footprint = [&]() {
+			if (bounce == 0) {
+				f3 axis_1, axis_2;
+				ray_cone_get_ellipse_axes(ray_direction, geometric_normal, cone_width, axis_1, axis_2);
+				lod.gradient_1 = ray_cone_ellipse_axis_to_gradient(tri, triangle_double_area_inv, geometric_normal, hit_point, tex_coord, axis_1);
+				lod.gradient_2 = ray_cone_ellipse_axis_to_gradient(tri, triangle_double_area_inv, geometric_normal, hit_point, tex_coord, axis_2);
+			} else {
+				float lod_triangle = triangle_get_lod(triangle_double_area_inv, tri.tex_coord_edge_1, tri.tex_coord_edge_2);
+				float lod_ray_cone = ray_cone_get_lod(ray_direction, geometric_normal, cone_width);
+				lod.lod = log2f(lod_triangle * lod_ray_cone);
+			}
+		};
+
+		// What the BSDF frame, next-event estimation, the NORMAL AOV and the SVGF g-buffer see; `normal` stays the interpolated
+		// normal, which the ray cone's curvature term keeps.
+		f3 shading_normal = normal;
+		if (NMAP && normal_map_id != RT_INVALID) {
+			if (p.config.enable_mipmapping) { footprint(); have_footprint = true; }
+			const int filter = !p.config.enable_mipmapping ? 0 : bounce == 0 ? 2 : 1;
+			normal_map_perturb<BSDF::MAP_COMPRESSED>(p.textures[normal_map_id], filter, tex_coord, lod.lod, lod.gradient_1, lod.gradient_2, dpdu, uv_det,
+			                                         entering_material ? normal : -normal, geometric_normal, entering_material, ray_direction, shading_normal);
+		}
+
 		f3 tangent, bitangent;
-		orthonormal_basis(normal, tangent, bitangent);
-		f3 omega_i = world_to_local(-ray_direction, tangent, bitangent, normal);
+		orthonormal_basis(shading_normal, tangent, bitangent);
+		f3 omega_i = world_to_local(-ray_direction, tangent, bitangent, shading_normal);
 		if (omega_i.z <= 0.0f) return false;
 
 		int material_id = p.mesh_material_ids[hit.mesh_id];
 
 		bsdf.pixel_index = pixel_index; bsdf.bounce = bounce; bsdf.sample_index = sample_index; bsdf.rng = random_path(p, unsigned(pixel_index), unsigned(sample_index));
-		bsdf.tangent = tangent; bsdf.bitangent = bitangent; bsdf.normal = normal; bsdf.omega_i = omega_i;
+		bsdf.tangent = tangent; bsdf.bitangent = bitangent; bsdf.normal = shading_normal; bsdf.omega_i = omega_i;
 		bsdf.init(p, entering_material, material_id);
 
 		if (BSDF::HAS_ALBEDO) {
-			TextureLOD lod = { mk2(0.0f, 0.0f), mk2(0.0f, 0.0f), 0.0f };
-			if (p.config.enable_mipmapping && bsdf.has_texture()) {
-				if (bounce == 0) {
-					f3 axis_1, axis_2;
-					ray_cone_get_ellipse_axes(ray_direction, geometric_normal, cone_width, axis_1, axis_2);
-					lod.gradient_1 = ray_cone_ellipse_axis_to_gradient(tri, triangle_double_area_inv, geometric_normal, hit_point, tex_coord, axis_1);
-					lod.gradient_2 = ray_cone_ellipse_axis_to_gradient(tri, triangle_double_area_inv, geometric_normal, hit_point, tex_coord, axis_2);
-				} else {
-					float lod_triangle = triangle_get_lod(triangle_double_area_inv, tri.tex_coord_edge_1, tri.tex_coord_edge_2);
-					float lod_ray_cone = ray_cone_get_lod(ray_direction, geometric_normal, cone_width);
-					lod.lod = log2f(lod_triangle * lod_ray_cone);
-				}
-			}
+			if (p.config.enable_mipmapping && bsdf.has_texture() && !have_footprint) footprint();
 			bsdf.calc_albedo(p, throughput, tex_coord, lod);
 		} else if (bounce == 0) {
 			aov_set(p, RT_AOV_ALBEDO, pixel_index, mk4(1.0f));
 		}
 
 		if (bounce == 0) {
-			aov_set(p, RT_AOV_NORMAL,   pixel_index, mk4(normal));
+			aov_set(p, RT_AOV_NORMAL,   pixel_index, mk4(shading_normal));
 			aov_set(p, RT_AOV_POSITION, pixel_index, mk4(hit_point));
 		}
 
@@ -1166,11 +1194,11 @@ RT_DEV void shade_material(const RtParams & p, int launch_bounce, int launch_sam
 		if (bounce == 0 && p.config.enable_svgf) {
 			f3 hit_point_prev = m_position(p.mesh_transforms_prev + size_t(hit.mesh_id) * 3, hit_point_local);
 			int x = pixel_index % p.screen_pitch, y = pixel_index / p.screen_pitch;
-			svgf_set_gbuffers(p, x, y, hit, hit_point, normal, hit_point_prev);
+			svgf_set_gbuffers(p, x, y, hit, hit_point, shading_normal, hit_point_prev);
 		}
 
 		if (nee_enabled && bsdf.allow_nee()) {
-			has_shadow_ray = next_event_estimation<SKY>(p, light_tables, pixel_index, bounce, sample_index, bsdf, hit_point, normal, geometric_normal, throughput, shadow);
+			has_shadow_ray = next_event_estimation<SKY>(p, light_tables, pixel_index, bounce, sample_index, bsdf, hit_point, shading_normal, geometric_normal, throughput, shadow);
 		}
 		return true;
 		};
@@ -1255,6 +1283,55 @@ __global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_materia
 __global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic_stream_sky(RtParams p)                          { shade_material<BSDFPlastic,         1, true, true>(p, 0, 0); }
 __global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_dielectric_stream_sky(RtParams p)                       { shade_material<BSDFDielectric,      2, true, true>(p, 0, 0); }
 __global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_conductor_stream_sky(RtParams p)                        { shade_material<BSDFConductor,       3, true, true>(p, 0, 0); }
+// ..._nmap: the same kernels for a slot some of whose materials have a normal map (RtParams::normal_map_slots), launched only then
+#define RT_NMAP_KERNELS(SUFFIX, SKY) \
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_diffuse##SUFFIX(RtParams p, int bounce, int sample_index)        { shade_material<BSDFDiffuse,         0, false, SKY, true>(p, bounce, sample_index); } \
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic##SUFFIX(RtParams p, int bounce, int sample_index)        { shade_material<BSDFPlastic,         1, false, SKY, true>(p, bounce, sample_index); } \
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_dielectric##SUFFIX(RtParams p, int bounce, int sample_index)     { shade_material<BSDFDielectric,      2, false, SKY, true>(p, bounce, sample_index); } \
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_conductor##SUFFIX(RtParams p, int bounce, int sample_index)      { shade_material<BSDFConductor,       3, false, SKY, true>(p, bounce, sample_index); } \
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_diffuse_texels##SUFFIX(RtParams p, int bounce, int sample_index) { shade_material<BSDFDiffuseT<false>, 0, false, SKY, true>(p, bounce, sample_index); } \
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic_texels##SUFFIX(RtParams p, int bounce, int sample_index) { shade_material<BSDFPlasticT<false>, 1, false, SKY, true>(p, bounce, sample_index); } \
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES_DIFFUSE) kernel_material_diffuse_stream_texels##SUFFIX(RtParams p) { shade_material<BSDFDiffuseT<false>, 0, true, SKY, true>(p, 0, 0); } \
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic_stream_texels##SUFFIX(RtParams p)        { shade_material<BSDFPlasticT<false>, 1, true, SKY, true>(p, 0, 0); } \
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_diffuse_stream##SUFFIX(RtParams p)               { shade_material<BSDFDiffuse,         0, true, SKY, true>(p, 0, 0); } \
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic_stream##SUFFIX(RtParams p)               { shade_material<BSDFPlastic,         1, true, SKY, true>(p, 0, 0); } \
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_dielectric_stream##SUFFIX(RtParams p)            { shade_material<BSDFDielectric,      2, true, SKY, true>(p, 0, 0); } \
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_conductor_stream##SUFFIX(RtParams p)             { shade_material<BSDFConductor,       3, true, SKY, true>(p, 0, 0); }
+RT_NMAP_KERNELS(_nmap, false)
+RT_NMAP_KERNELS(_sky_nmap, true)
+#undef RT_NMAP_KERNELS
+
+// rt_perturb_normals: normal_map_perturb on explicit hits, the surface set up as set_up_surface sets it up (RT_NORMAL_PROBE_IN floats per
+// probe, layout in gpu_raytracer_amd.h; out: 4 floats {normal[3], fell back}). COMPRESSED is picked as for the material kernels.
+template<bool COMPRESSED>
+__global__ void kernel_perturb_normals(RtParams p, int texture_index, const float * probes, int count, float * out) {
+	int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= count) return;
+	const float * a = probes + size_t(i) * RT_NORMAL_PROBE_IN;
+	TriangleFull tri;
+	tri.position_0 = mk3(a[0], a[1], a[2]); tri.position_edge_1 = mk3(a[3], a[4], a[5]); tri.position_edge_2 = mk3(a[6], a[7], a[8]);
+	tri.normal_0 = mk3(a[9], a[10], a[11]); tri.normal_edge_1 = mk3(a[12], a[13], a[14]); tri.normal_edge_2 = mk3(a[15], a[16], a[17]);
+	tri.tex_coord_0 = mk2(a[18], a[19]); tri.tex_coord_edge_1 = mk2(a[20], a[21]); tri.tex_coord_edge_2 = mk2(a[22], a[23]);
+	const float u = a[24], v = a[25];
+	const float4 world[3] = { make_float4(a[26], a[27], a[28], a[29]), make_float4(a[30], a[31], a[32], a[33]), make_float4(a[34], a[35], a[36], a[37]) };
+	const f3 ray_direction = mk3(a[38], a[39], a[40]);
+	const int filter = int(a[41]);
+
+	f3 normal    = barycentric(u, v, tri.normal_0,    tri.normal_edge_1,    tri.normal_edge_2);
+	f2 tex_coord = barycentric(u, v, tri.tex_coord_0, tri.tex_coord_edge_1, tri.tex_coord_edge_2);
+	normal = normalize(m_direction(world, normal));
+	float uv_det;
+	f3 dpdu = m_direction(world, normal_map_dpdu(tri.position_edge_1, tri.position_edge_2, tri.tex_coord_edge_1, tri.tex_coord_edge_2, uv_det));
+	f3 geometric_normal = cross(m_direction(world, tri.position_edge_1), m_direction(world, tri.position_edge_2));
+	geometric_normal *= 1.0f / length(geometric_normal);
+	bool entering_material = dot(ray_direction, geometric_normal) < 0.0f;
+
+	f3 shading_normal = entering_material ? normal : -normal;
+	bool mapped = normal_map_perturb<COMPRESSED>(p.textures[texture_index], filter, tex_coord, a[42], mk2(a[43], a[44]), mk2(a[45], a[46]), dpdu, uv_det,
+	                                             normal, geometric_normal, entering_material, ray_direction, shading_normal);
+	float * o = out + size_t(i) * 4;
+	o[0] = shading_normal.x; o[1] = shading_normal.y; o[2] = shading_normal.z; o[3] = mapped ? 0.0f : 1.0f;
+}
 
 // ---- ambient occlusion (CUDA/AO.cu:103-159) -------------------------------------------------------
 // One cosine-weighted occlusion ray of length ao_radius per primary hit; the AO shadow kernel sets
@@ -1329,8 +1406,20 @@ void rt_launch_generate(const RtParams & p, int sample_index, int pixel_offset, 
 void rt_launch_sort(const RtParams & p, int bounce, int sample_index, hipStream_t stream) {
 	hipLaunchKernelGGL(p.sky_nee_share > 0.0f ? kernel_sort_sky : kernel_sort, dim3(2048 * RT_SHADE_BLOCK / RT_SORT_BLOCK), dim3(RT_SORT_BLOCK), 0, stream, p, bounce, sample_index);
 }
+// (... and the ..._nmap instances for a slot some of whose materials have a normal map: RtParams::normal_map_slots)
+static void launch_material_nmap(const RtParams & p, int material_slot, int bounce, int sample_index, hipStream_t stream) {
+	dim3 grid(2048), block(RT_SHADE_BLOCK);
+	const bool sky = p.sky_nee_share > 0.0f, compressed = p.textures_compressed != 0;
+	switch (material_slot) {
+		case 0: hipLaunchKernelGGL(sky ? (compressed ? kernel_material_diffuse_sky_nmap : kernel_material_diffuse_texels_sky_nmap) : (compressed ? kernel_material_diffuse_nmap : kernel_material_diffuse_texels_nmap), grid, block, 0, stream, p, bounce, sample_index); break;
+		case 1: hipLaunchKernelGGL(sky ? (compressed ? kernel_material_plastic_sky_nmap : kernel_material_plastic_texels_sky_nmap) : (compressed ? kernel_material_plastic_nmap : kernel_material_plastic_texels_nmap), grid, block, 0, stream, p, bounce, sample_index); break;
+		case 2: hipLaunchKernelGGL(sky ? kernel_material_dielectric_sky_nmap : kernel_material_dielectric_nmap, grid, block, 0, stream, p, bounce, sample_index); break;
+		case 3: hipLaunchKernelGGL(sky ? kernel_material_conductor_sky_nmap  : kernel_material_conductor_nmap,  grid, block, 0, stream, p, bounce, sample_index); break;
+	}
+}
 void rt_launch_material(const RtParams & p, int material_slot, int bounce, int sample_index, hipStream_t stream) {
 	dim3 grid(2048), block(RT_SHADE_BLOCK);
+	if (p.normal_map_slots & (1 << material_slot)) { launch_material_nmap(p, material_slot, bounce, sample_index, stream); return; }
 	if (p.sky_nee_share > 0.0f) {
 		switch (material_slot) {
 			case 0: hipLaunchKernelGGL(p.textures_compressed ? kernel_material_diffuse_sky : kernel_material_diffuse_texels_sky, grid, block, 0, stream, p, bounce, sample_index); break;
@@ -1363,8 +1452,19 @@ void rt_launch_stream_advance(RtStreamControl * control, int iteration, int gene
 void rt_launch_sort_stream(const RtParams & p, hipStream_t stream) {
 	hipLaunchKernelGGL(p.sky_nee_share > 0.0f ? kernel_sort_stream_sky : kernel_sort_stream, dim3(RT_STREAM_SORT_GRID * RT_SHADE_BLOCK / RT_SORT_BLOCK), dim3(RT_SORT_BLOCK), 0, stream, p);
 }
+static void launch_material_stream_nmap(const RtParams & p, int material_slot, hipStream_t stream) {
+	dim3 grid(RT_STREAM_SHADE_GRID), block(RT_SHADE_BLOCK);
+	const bool sky = p.sky_nee_share > 0.0f, compressed = p.textures_compressed != 0;
+	switch (material_slot) {
+		case 0: hipLaunchKernelGGL(sky ? (compressed ? kernel_material_diffuse_stream_sky_nmap : kernel_material_diffuse_stream_texels_sky_nmap) : (compressed ? kernel_material_diffuse_stream_nmap : kernel_material_diffuse_stream_texels_nmap), grid, block, 0, stream, p); break;
+		case 1: hipLaunchKernelGGL(sky ? (compressed ? kernel_material_plastic_stream_sky_nmap : kernel_material_plastic_stream_texels_sky_nmap) : (compressed ? kernel_material_plastic_stream_nmap : kernel_material_plastic_stream_texels_nmap), grid, block, 0, stream, p); break;
+		case 2: hipLaunchKernelGGL(sky ? kernel_material_dielectric_stream_sky_nmap : kernel_material_dielectric_stream_nmap, grid, block, 0, stream, p); break;
+		case 3: hipLaunchKernelGGL(sky ? kernel_material_conductor_stream_sky_nmap  : kernel_material_conductor_stream_nmap,  grid, block, 0, stream, p); break;
+	}
+}
 void rt_launch_material_stream(const RtParams & p, int material_slot, hipStream_t stream) {
 	dim3 grid(RT_STREAM_SHADE_GRID), block(RT_SHADE_BLOCK);
+	if (p.normal_map_slots & (1 << material_slot)) { launch_material_stream_nmap(p, material_slot, stream); return; }
 	if (p.sky_nee_share > 0.0f) {
 		switch (material_slot) {
 			case 0: hipLaunchKernelGGL(p.textures_compressed ? kernel_material_diffuse_stream_sky : kernel_material_diffuse_stream_texels_sky, grid, block, 0, stream, p); break;
@@ -1396,6 +1496,10 @@ void rt_launch_sample_table(const float * table, int nx, int ny, int nz, int dim
 }
 void rt_launch_sample_sky(const RtParams & p, const float * directions, int count, float * out, hipStream_t stream) {
 	hipLaunchKernelGGL(kernel_sample_sky, dim3((count + 255) / 256), dim3(256), 0, stream, p, directions, count, out);
+}
+void rt_launch_perturb_normals(const RtParams & p, int texture_index, const float * probes, int count, float * out, hipStream_t stream) {
+	if (p.textures_compressed) hipLaunchKernelGGL(kernel_perturb_normals<true>, dim3((count + 255) / 256), dim3(256), 0, stream, p, texture_index, probes, count, out);
+	else hipLaunchKernelGGL(kernel_perturb_normals<false>, dim3((count + 255) / 256), dim3(256), 0, stream, p, texture_index, probes, count, out);
 }
 // diffuse and plastic: the COMPRESSED instantiations the textureless material kernels launch (no texture is read either way)
 template<bool EVAL>

@@ -224,6 +224,9 @@ struct rt_context {
 	hipEvent_t ev_scene = nullptr;  // the last asynchronous scene upload on the main stream
 	void * material_types = nullptr, * materials = nullptr, * media = nullptr;
 	bool has_material[4] = { false, false, false, false };
+	std::vector<uint8_t> material_type_list;   // what rt_upload_materials uploaded (rt_upload_material_normal_maps checks against it)
+	void * material_normal_maps = nullptr;     // int per material (rt_upload_material_normal_maps)
+	std::vector<int> texture_formats;          // the device format of every texture of rt_upload_textures
 	bool has_lights = false;
 	void * texture_table = nullptr; std::vector<void *> texture_data;
 	void * pmj = nullptr, * blue_noise = nullptr;
@@ -1006,6 +1009,9 @@ int rt_upload_materials(rt_context * ctx, const uint8_t * types, const void * ma
 	s = upload(ctx, &ctx->materials, materials, count * 32); if (s) return s;
 	ctx->params.material_types = (const uint8_t *)ctx->material_types;
 	ctx->params.materials      = (const float4 *)ctx->materials;
+	ctx->material_type_list.assign(types, types + count);
+	ctx->params.material_normal_maps = nullptr;   // new materials: no normal maps until rt_upload_material_normal_maps
+	ctx->params.normal_map_slots = 0;
 
 	// Scene::check_materials (Scene.cpp:50-70): which material kernels have to run at all
 	for (bool & h : ctx->has_material) h = false;
@@ -1024,6 +1030,35 @@ int rt_upload_materials(rt_context * ctx, const uint8_t * types, const void * ma
 	return RT_OK;
 }
 
+int rt_upload_material_normal_maps(rt_context * ctx, const int32_t * texture_ids, size_t count) {
+	RT_REQUIRE(ctx, ctx && (texture_ids || count == 0), "rt_upload_material_normal_maps: NULL argument");
+	RT_REQUIRE(ctx, ctx->params.materials, "rt_upload_material_normal_maps: no materials uploaded");
+	if (count != ctx->material_type_list.size())
+		return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_material_normal_maps: %zu ids for %zu materials", count, ctx->material_type_list.size());
+	int slots = 0;
+	for (size_t i = 0; i < count; i++) {
+		int id = texture_ids[i];
+		if (id == RT_INVALID) continue;
+		if (id < 0 || size_t(id) >= ctx->texture_formats.size())
+			return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_material_normal_maps: material %zu names texture %d of %zu", i, id, ctx->texture_formats.size());
+		if (ctx->texture_formats[id] != RT_TEXTURE_RGBA8)
+			return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_material_normal_maps: material %zu names texture %d, which is not RT_TEXTURE_RGBA8", i, id);
+		int type = ctx->material_type_list[i];
+		if (type >= RT_MATERIAL_DIFFUSE && type <= RT_MATERIAL_CONDUCTOR) slots |= 1 << (type - RT_MATERIAL_DIFFUSE);
+	}
+	(void)hipSetDevice(ctx->device);
+	if (slots == 0) {   // none (or only on lights): every launch keeps its plain instance
+		RT_HIP(ctx, quiesce(ctx));
+		ctx->params.material_normal_maps = nullptr;
+		ctx->params.normal_map_slots = 0;
+		return RT_OK;
+	}
+	int s = upload(ctx, &ctx->material_normal_maps, texture_ids, count * sizeof(int32_t)); if (s) return s;
+	ctx->params.material_normal_maps = (const int *)ctx->material_normal_maps;
+	ctx->params.normal_map_slots = slots;
+	return RT_OK;
+}
+
 int rt_upload_media(rt_context * ctx, const void * media, size_t count) {
 	RT_REQUIRE(ctx, ctx && (media || count == 0), "rt_upload_media: NULL argument");
 	(void)hipSetDevice(ctx->device);
@@ -1036,7 +1071,7 @@ int rt_upload_textures(rt_context * ctx, const rt_texture_desc * descs, size_t c
 	RT_REQUIRE(ctx, ctx && (descs || count == 0), "rt_upload_textures: NULL argument");
 	(void)hipSetDevice(ctx->device);
 	for (void * p : ctx->texture_data) device_free(ctx, p);
-	ctx->texture_data.clear(); ctx->texture_bytes = 0;
+	ctx->texture_data.clear(); ctx->texture_bytes = 0; ctx->texture_formats.clear();
 	std::vector<RtTexture> table(count);
 	for (size_t i = 0; i < count; i++) {
 		const rt_texture_desc & d = descs[i];
@@ -1064,12 +1099,15 @@ int rt_upload_textures(rt_context * ctx, const rt_texture_desc * descs, size_t c
 		table[i].texels = (const uchar4 *)dev;
 		table[i].width = d.width; table[i].height = d.height; table[i].mip_levels = d.mip_levels;
 		table[i].format = device_format; table[i].pad = 0;
+		ctx->texture_formats.push_back(device_format);
 		int lod_width  = d.lod_width  > 0 ? d.lod_width  : d.width;
 		int lod_height = d.lod_height > 0 ? d.lod_height : d.height;
 		table[i].lod_bias = 0.5f * log2f(float(lod_width * lod_height)); // Integrator.cpp:95
 	}
 	int s = upload(ctx, &ctx->texture_table, table.data(), count * sizeof(RtTexture)); if (s) return s;
 	ctx->params.textures = (const RtTexture *)ctx->texture_table;
+	ctx->params.material_normal_maps = nullptr;   // the maps named textures of the old table
+	ctx->params.normal_map_slots = 0;
 	ctx->params.textures_compressed = 0;
 	for (const RtTexture & t : table) if (t.format == RT_TEXTURE_BC1) ctx->params.textures_compressed = 1;
 	return RT_OK;
@@ -2884,6 +2922,28 @@ int rt_bsdf_eval(rt_context * ctx, int material_type, const float * probes, size
 }
 int rt_bsdf_sample(rt_context * ctx, int material_type, const float * probes, size_t count, float * out) {
 	return bsdf_probe(ctx, "rt_bsdf_sample", false, material_type, probes, count, out);
+}
+
+int rt_perturb_normals(rt_context * ctx, int texture_index, const float * probes, size_t count, float * out) {
+	RT_REQUIRE(ctx, ctx && probes && out, "rt_perturb_normals: NULL argument");
+	RT_REQUIRE(ctx, texture_index >= 0 && size_t(texture_index) < ctx->texture_formats.size(), "rt_perturb_normals: texture index out of range");
+	RT_REQUIRE(ctx, ctx->texture_formats[texture_index] == RT_TEXTURE_RGBA8, "rt_perturb_normals: the map must be an RT_TEXTURE_RGBA8 texture");
+	RT_REQUIRE(ctx, count <= size_t(1) << 24, "rt_perturb_normals: more than 2^24 probes");
+	for (size_t i = 0; i < count; i++) {
+		float filter = probes[i * RT_NORMAL_PROBE_IN + 41];
+		RT_REQUIRE(ctx, filter == 0.0f || filter == 1.0f || filter == 2.0f, "rt_perturb_normals: filter must be 0 (level 0), 1 (lod) or 2 (gradients)");
+	}
+	(void)hipSetDevice(ctx->device);
+	if (count == 0) return RT_OK;
+	TempBuffers tmp(ctx);
+	float * dev_probes = (float *)tmp.get(count * RT_NORMAL_PROBE_IN * 4, probes);
+	float * dev_out = (float *)tmp.get(count * 16, nullptr);
+	if (!dev_probes || !dev_out) return fail(ctx, RT_ERROR_HIP, "rt_perturb_normals: device allocation failed");
+	rt_launch_perturb_normals(ctx->params, texture_index, dev_probes, int(count), dev_out, ctx->stream);
+	RT_HIP(ctx, hipGetLastError());
+	RT_HIP(ctx, quiesce(ctx));
+	RT_HIP(ctx, hipMemcpy(out, dev_out, count * 16, hipMemcpyDeviceToHost));
+	return RT_OK;
 }
 
 int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps) {

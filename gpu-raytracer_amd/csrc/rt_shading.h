@@ -373,6 +373,51 @@ RT_DEV f3 sample_sky(const RtParams & p, f3 direction) {
 	return p.sky_scale * mk3(c);
 }
 
+// ---- tangent-space normal maps (rt_upload_material_normal_maps) ---------------------------------------------------------
+// Shared by the shade kernels' _nmap instances and rt_perturb_normals.
+
+#define RT_NORMAL_MAP_VIEW_EPSILON 1e-2f   // the view guard: a mapped normal keeps at least this cosine with the direction to the viewer
+
+// dp/du of a triangle from its object-space edges e1, e2 and texture-coordinate edges duv1, duv2; det = du1 dv2 - du2 dv1
+RT_DEV f3 normal_map_dpdu(f3 e1, f3 e2, f2 duv1, f2 duv2, float & det) {
+	det = duv1.x * duv2.y - duv2.x * duv1.y;
+	return (duv2.y * e1 - duv1.y * e2) / det;
+}
+
+// The mapped shading normal of a hit. n: the interpolated world normal (unit, before the side flip); dpdu: normal_map_dpdu moved to
+// world space, det its determinant; geometric_normal: the unit normal of the world-space triangle, cross(e1, e2), on its winding's side.
+// filter: 0 level 0, 1 lod (the map's own lod_bias added), 2 gradients -- the albedo's rule.
+// Frame: T = normalize(dpdu - n (n . dpdu)), B = s cross(n, T) with s = sign(det), negated where the triangle is wound clockwise about n
+// (s is the sign of (dp/du x dp/dv) . n, so that B follows dp/dv): Mitsuba 3's frame for unmirrored texture coordinates, kept right-handed
+// for mirrored ones whatever the winding. m = normalize(t.x T + t.y B + t.z n) with t = 2 rgb - 1. Then the side flip of the interpolated normal and the view
+// guard: with w = -ray_direction, dot(m, w) < eps moves m towards w until the two make a cosine of eps (before normalising).
+// Returns false and leaves `normal` alone (the flipped interpolated normal) when det is 0 or not finite, T or m degenerates.
+template<bool COMPRESSED>
+RT_DEV bool normal_map_perturb(const RtTexture & tex, int filter, f2 tex_coord, float lod, f2 gradient_1, f2 gradient_2,
+                               f3 dpdu, float det, f3 n, f3 geometric_normal, bool entering_material, f3 ray_direction, f3 & normal) {
+	if (!(det != 0.0f && isfinite(det))) return false;
+	f3 t = dpdu - n * dot(n, dpdu);
+	float t_length_squared = dot(t, t);
+	if (!(t_length_squared > 1e-8f * dot(dpdu, dpdu) && isfinite(t_length_squared))) return false;   // dp/du (nearly) along n, or overflowed
+	t = t / sqrtf(t_length_squared);
+	f3 b = cross(n, t);
+	if ((det < 0.0f) != (dot(geometric_normal, n) < 0.0f)) b = -b;
+	f4 c = filter == 0 ? texture_get<COMPRESSED>(tex, tex_coord.x, tex_coord.y)
+	     : filter == 1 ? texture_get_lod<COMPRESSED>(tex, tex_coord.x, tex_coord.y, lod + tex.lod_bias)
+	     :               texture_get_grad<COMPRESSED>(tex, tex_coord.x, tex_coord.y, gradient_1, gradient_2);
+	f3 v = mk3(2.0f * c.x - 1.0f, 2.0f * c.y - 1.0f, 2.0f * c.z - 1.0f);
+	f3 m = v.x * t + v.y * b + v.z * n;
+	float m_length_squared = dot(m, m);
+	if (!(m_length_squared > 0.0f)) return false;
+	m = m / sqrtf(m_length_squared);
+	if (!entering_material) m = -m;
+	f3 w = -ray_direction;
+	float cos_view = dot(m, w);
+	if (cos_view < RT_NORMAL_MAP_VIEW_EPSILON) m = normalize(m + (RT_NORMAL_MAP_VIEW_EPSILON - cos_view) * w);
+	normal = m;
+	return true;
+}
+
 // ---- sky importance sampling (rt_set_sky_sampling; the tables: kernels_sky.hip, DESIGN.md "Sky importance sampling") ----------------
 // A cell is one sky texel in sample_sky's mapping; inside a cell a direction is uniform in phi and in cos(theta), so the density of every
 // direction of the cell is the one number sky_cell_pdf holds for it. Sampling and evaluation both read that table through sky_pdf.

@@ -207,6 +207,10 @@ struct RtParams {
 	const float * sky_conditional_cdf;  // [sky_height][sky_width]: inclusive, normalised CDF of each row; last entry 1
 	const float * sky_cell_pdf;         // [sky_height][sky_width]: pdf (solid angle) of every direction in the cell
 	float sky_nee_share;                // probability that a light sample goes to the sky: 0 off / inactive; rt_set_sky_sampling's value with triangle emitters, 1 without
+	// Tangent-space normal maps (rt_upload_material_normal_maps): the map of each material (RT_INVALID: none), and bit s set
+	// when some material of slot s (diffuse, plastic, dielectric, conductor) has one -- only then does the launcher take that slot's _nmap instance.
+	const int * material_normal_maps;
+	int normal_map_slots;
 };
 // "Skip behind the hit" (kernels_trace.hip): closest-hit rays drop stacked groups of children that lie behind the hit they hold. Taken when the context wants it
 // (rt_set_skip_behind_hit) AND the scene is ONE tree the flattened scene's engine walks (rt_set_static_geometry(ctx, 1), arrays below 4 GiB): every CWBVH
@@ -282,6 +286,8 @@ void rt_launch_sample_sky(const RtParams & p, const float * directions, int coun
 #define RT_BSDF_PROBE_IN  24
 #define RT_BSDF_PROBE_OUT 12
 void rt_launch_bsdf_probe(const RtParams & p, int material_type, bool eval, const float * probes, int count, float * out, hipStream_t stream);
+// Test support: normal_map_perturb on explicit hits (rt_perturb_normals); RT_NORMAL_PROBE_IN floats in, 4 out per probe
+void rt_launch_perturb_normals(const RtParams & p, int texture_index, const float * probes, int count, float * out, hipStream_t stream);
 // Sky importance sampling (kernels_sky.hip). build: the three tables of RtParams from the sky; row_total: sky_height doubles, total: one double (the
 // sum of all cell weights, read back by the host). sample / pdf: the device functions of rt_shading.h on explicit arguments (test support).
 void rt_launch_sky_build(const float4 * sky, int width, int height, float * marginal_cdf, float * conditional_cdf, float * cell_pdf, double * row_total, double * total, hipStream_t stream);

@@ -19,6 +19,9 @@ struct Texture {
 	// texture: what the device stores and decodes in its texel fetch. `texels` then holds the decoded levels --
 	// the same values, for the host-side consumers (exporters, the parity checker).
 	std::vector<unsigned char> bc1_blocks;
+	// A data texture (a tangent-space normal map): texels are the file's bytes as stored -- no sRGB decode, mips filtered on
+	// the raw values, never block-compressed.
+	bool data = false;
 
 	int mip_levels() const { return int(mip_offsets.size()); }
 };
@@ -57,6 +60,7 @@ struct Material {
 
 	Vector3         diffuse = Vector3(1.0f, 1.0f, 1.0f);
 	Handle<Texture> texture_handle;
+	Handle<Texture> normal_map_handle;   // tangent-space normal map (a data texture), INVALID: none
 
 	Handle<Medium> medium_handle;
 	float          index_of_refraction = 1.33f;

@@ -133,7 +133,7 @@ const BsdfModel BSDF_MODELS[] = {
 	{ "thindielectric",  Material::Type::DIELECTRIC, nullptr,              Roughness::SMOOTH,         Optics::DIELECTRIC },
 	{ "roughdielectric", Material::Type::DIELECTRIC, nullptr,              Roughness::ALPHA,          Optics::DIELECTRIC },
 };
-const char * const BSDF_WRAPPERS[] = { "twosided", "mask", "bumpmap", "coating" };   // only what they wrap matters
+const char * const BSDF_WRAPPERS[] = { "twosided", "mask", "bumpmap", "coating", "normalmap" };   // only what they wrap matters -- and a normalmap's map
 
 // named indices of refraction (Mitsuba 0.5 documentation, page 58)
 const struct { const char * medium; float index; } NAMED_IOR[] = {
@@ -175,7 +175,7 @@ struct SceneFile {
 	SceneFile(Scene & scene, const std::string & filename) : scene(scene), folder(PathName::folder(filename)) { }
 
 	// -- textures and colours
-	Handle<Texture> texture(const XMLNode * node, Vector3 & tint) {
+	Handle<Texture> texture(const XMLNode * node, Vector3 & tint, AssetManager::TextureKind texture_kind = AssetManager::TextureKind::COLOUR) {
 		std::string_view kind = plugin(*node);
 		if (kind == "scale") { // a scale node multiplies the colour and wraps the real texture
 			if (const XMLNode * factor = node->get_child_by_name("scale")) {
@@ -189,8 +189,9 @@ struct SceneFile {
 		}
 		if (kind != "bitmap") { complain(*node, "only bitmap textures are supported"); return Handle<Texture> { INVALID }; }
 		std::string path = PathName::below(folder, node->require_child_by_name("filename").get_attribute_value("value"));
-		Handle<Texture> handle = scene.asset_manager.add_texture(path, PathName::leaf(path));
-		if (const XMLAttribute * id = node->get_attribute("id")) textures[id->value] = handle;
+		Handle<Texture> handle = scene.asset_manager.add_texture(path, PathName::leaf(path), texture_kind);
+		if (texture_kind == AssetManager::TextureKind::COLOUR)
+			if (const XMLAttribute * id = node->get_attribute("id")) textures[id->value] = handle;
 		return handle;
 	}
 
@@ -230,6 +231,21 @@ struct SceneFile {
 		return Handle<Material>::get_default();
 	}
 
+	// The tangent-space map of a <bsdf type="normalmap"> (Mitsuba 3: <texture name="normalmap" type="bitmap">); its `raw` flag is
+	// ignored, a normal map is always read raw. INVALID, with one warning per scene file, when it names no bitmap.
+	bool warned_normalmap_without_bitmap = false;
+	Handle<Texture> normal_map(const XMLNode & wrapper) {
+		const XMLNode * given = wrapper.get_child_by_name("normalmap");
+		if (!given || given->tag != "texture") given = wrapper.get_child_by_tag("texture");
+		if (given && plugin(*given) == "bitmap" && given->get_child_by_name("filename")) {
+			Vector3 unused(1.0f);
+			return texture(given, unused, AssetManager::TextureKind::DATA);
+		}
+		if (!warned_normalmap_without_bitmap) complain(wrapper, "normalmap without a bitmap texture: loaded as the BSDF it wraps");
+		warned_normalmap_without_bitmap = true;
+		return Handle<Texture> { INVALID };
+	}
+
 	// The material of `owner`: a <bsdf> itself, or a shape (whose <emitter> wins over a <ref>, which wins over an inline <bsdf>)
 	Handle<Material> material(const XMLNode & owner) {
 		const XMLNode * bsdf = &owner;
@@ -240,14 +256,26 @@ struct SceneFile {
 			if (!bsdf) { complain(owner, "unable to parse BSDF"); return Handle<Material>::get_default(); }
 		}
 
-		// peel the wrappers; the name is the outermost id there is
+		// peel the wrappers; the name is the outermost id there is. A normalmap anywhere in the chain gives its map to what it wraps.
 		const XMLAttribute * id = bsdf->get_attribute("id");
 		auto is_wrapper = [](std::string_view kind) { for (const char * w : BSDF_WRAPPERS) if (kind == w) return true; return false; };
+		Handle<Texture> normal_map_handle { INVALID };
 		while (is_wrapper(plugin(*bsdf))) {
+			if (plugin(*bsdf) == "normalmap") {
+				Handle<Texture> map = normal_map(*bsdf);
+				if (map.handle != INVALID) normal_map_handle = map;
+			}
 			const XMLNode * wrapped = bsdf->get_child_by_tag("bsdf");
 			if (!wrapped) {
 				const XMLNode * ref = bsdf->get_child_by_tag("ref");
-				return ref ? referenced_material(*ref) : Handle<Material>::get_default();
+				if (!ref) return Handle<Material>::get_default();
+				Handle<Material> referenced = referenced_material(*ref);
+				if (normal_map_handle.handle == INVALID) return referenced;
+				// a copy of the referenced material carries the map; the original, and whoever else refers to it, stays as it is
+				Material copy = scene.asset_manager.get_material(referenced);
+				copy.normal_map_handle = normal_map_handle;
+				if (id) copy.name = id->value;
+				return scene.asset_manager.add_material(std::move(copy));
 			}
 			bsdf = wrapped;
 			if (!id) id = bsdf->get_attribute("id");
@@ -261,6 +289,7 @@ struct SceneFile {
 		Material made;
 		made.name = id ? id->value : "Material";
 		made.type = model->material;
+		made.normal_map_handle = normal_map_handle;
 		if (model->colour) colour(*bsdf, model->colour, made.diffuse, made.texture_handle);
 		if (model->optics == Optics::DIELECTRIC) { // (before the roughness: an unknown named index of refraction ends the load)
 			float inside = index_of_refraction(*bsdf, "intIOR", 1.33f), outside = index_of_refraction(*bsdf, "extIOR", 1.0f);

@@ -165,6 +165,10 @@ void Pathtracer::update(float delta) {
 			}
 		}
 		if (ctx) check(rt_upload_materials(ctx, material_types.data(), materials.data(), materials.size()));
+		// tangent-space normal maps: their own table beside the 32-byte records (rt_upload_materials has reset it to none)
+		std::vector<int32_t> normal_maps(scene_materials.size(), INVALID);
+		for (size_t i = 0; i < scene_materials.size(); i++) normal_maps[i] = scene_materials[i].normal_map_handle.handle;
+		if (ctx) check(rt_upload_material_normal_maps(ctx, normal_maps.data(), normal_maps.size()));
 
 		bool had_lights = scene.has_lights;
 		scene.check_materials();

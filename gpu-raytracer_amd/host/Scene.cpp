@@ -190,16 +190,32 @@ Handle<Medium> AssetManager::add_medium(Medium medium) {
 	return handle;
 }
 
-Handle<Texture> AssetManager::add_texture(const std::string & filename, const std::string & name) {
-	auto it = texture_cache.find(filename);
+Handle<Texture> AssetManager::add_texture(const std::string & filename, const std::string & name, TextureKind kind) {
+	auto it = texture_cache.find({ filename, kind });
 	if (it != texture_cache.end()) return it->second;
 
 	Handle<Texture> handle { int(textures.size()) };
 	textures.emplace_back();
 	textures.back().name = name;
-	texture_cache[filename] = handle;
+	textures.back().data = kind == TextureKind::DATA;
+	if (assets_loaded) { load_texture(textures.back(), filename); return handle; }
+	texture_cache[{ filename, kind }] = handle;
 	pending_textures.push_back({ handle.handle, filename });
 	return handle;
+}
+
+void AssetManager::load_texture(Texture & texture, const std::string & filename) {
+	bool loaded = false;
+	try { loaded = TextureLoader::load(filename, &texture); } catch (const std::exception &) { /* e.g. out of memory on a hostile header: fall back */ }
+	if (!loaded) {
+		fprintf(stderr, "WARNING: Failed to load Texture '%s'!\n", filename.c_str());
+		// 1x1 fallback (reference: AssetManager.cpp:157-169). The reference means it to be pink but stores the
+		// colour as a float4 in a texture it then uploads as RGBA8: the one texel the device gets is the first
+		// four bytes of the float 1.0f. Same texel here, so that a scene with a missing map renders alike.
+		texture.width = texture.height = 1;
+		texture.texels = { 0x00, 0x00, 0x80, 0x3f };
+		texture.mip_offsets = { 0 };
+	}
 }
 
 void AssetManager::wait_until_loaded() {
@@ -243,18 +259,7 @@ void AssetManager::wait_until_loaded() {
 				size_t i = next.fetch_add(1);
 				if (i >= pending_textures.size()) break;
 				PendingTexture & job = pending_textures[i];
-				Texture & texture = textures[job.handle];
-				bool loaded = false;
-				try { loaded = TextureLoader::load(job.filename, &texture); } catch (const std::exception &) { /* e.g. out of memory on a hostile header: fall back */ }
-				if (!loaded) {
-					fprintf(stderr, "WARNING: Failed to load Texture '%s'!\n", job.filename.c_str());
-					// 1x1 fallback (reference: AssetManager.cpp:157-169). The reference means it to be pink but stores the
-					// colour as a float4 in a texture it then uploads as RGBA8: the one texel the device gets is the first
-					// four bytes of the float 1.0f. Same texel here, so that a scene with a missing map renders alike.
-					texture.width = texture.height = 1;
-					texture.texels = { 0x00, 0x00, 0x80, 0x3f };
-					texture.mip_offsets = { 0 };
-				}
+				load_texture(textures[job.handle], job.filename);
 			}
 		};
 		std::vector<std::thread> workers;

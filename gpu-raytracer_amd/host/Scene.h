@@ -38,7 +38,10 @@ struct AssetManager {
 	Handle<MeshData> add_mesh_data(std::vector<Triangle> triangles);
 	Handle<Material> add_material(Material material);
 	Handle<Medium>   add_medium(Medium medium);
-	Handle<Texture>  add_texture(const std::string & filename, const std::string & name);
+	// kind DATA: the texels are values, not colours (normal maps), see Texture::data; a file is cached once per kind.
+	// Once the assets are loaded a new texture is decoded right away.
+	enum struct TextureKind { COLOUR, DATA };
+	Handle<Texture>  add_texture(const std::string & filename, const std::string & name, TextureKind kind = TextureKind::COLOUR);
 
 	// Builds every pending BLAS (one job per mesh file on a thread pool) and decodes textures.
 	void wait_until_loaded();
@@ -55,10 +58,11 @@ struct AssetManager {
 
 private:
 	std::map<std::string, Handle<MeshData>> mesh_data_cache;
-	std::map<std::string, Handle<Texture>>  texture_cache;
+	std::map<std::pair<std::string, TextureKind>, Handle<Texture>> texture_cache;
 
 	struct PendingMesh    { int handle; std::string filename; FallbackLoader loader; std::string bvh_filename; };
 	struct PendingTexture { int handle; std::string filename; };
+	static void load_texture(Texture & texture, const std::string & filename);
 	std::vector<PendingMesh>    pending_meshes;
 	std::vector<PendingTexture> pending_textures;
 	bool assets_loaded = false;
@@ -92,6 +96,7 @@ namespace SerializedLoader { std::vector<Triangle> load(const std::string & file
 namespace MitshairLoader   { std::vector<Triangle> load(const std::string & filename, float radius); }
 namespace MitsubaLoader { void load(const std::string & filename, Scene & scene); }
 namespace TextureLoader {
+	// texture->data on entry: load as a data texture (no sRGB decode, no block compression; DDS files are refused)
 	bool load(const std::string & filename, Texture * texture);
 	// One mip step with the box / lanczos / kaiser kernel of the reference (Src/Math/Mipmap.cpp)
 	void downsample(MipmapFilterType filter, int w_src, int h_src, int w_dst, int h_dst, const Vector4 * src, Vector4 * dst, std::vector<Vector4> & temp);

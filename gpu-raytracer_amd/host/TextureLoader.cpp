@@ -273,6 +273,10 @@ bool TextureLoader::load(const std::string & filename, Texture * texture) {
 	// conversion, no re-filtering (reference: TextureLoader.cpp:19-106)
 	std::vector<std::vector<unsigned char>> dds_levels;
 	if (ImageDecoders::decode_dds(file, width, height, dds_levels)) {
+		if (texture->data) {   // its levels are block-compressed colours: not a normal map this renderer can read
+			fprintf(stderr, "WARNING: DDS file '%s' cannot be a normal map\n", filename.c_str());
+			return false;
+		}
 		// The reference walks the chain by halving the BLOCK counts and stops when one reaches zero (:92-104): levels
 		// narrower or lower than one full block of the previous halving -- the 2x2 and 1x1 tail -- are never used
 		size_t kept = 0;
@@ -309,6 +313,10 @@ bool TextureLoader::load(const std::string & filename, Texture * texture) {
 
 	std::vector<Vector4> linear(total);
 	for (size_t i = 0; i < size_t(width) * height; i++) {
+		if (texture->data) {   // values, not colours: filtered as stored
+			linear[i] = Vector4(float(rgba8[4 * i + 0]) / 255.0f, float(rgba8[4 * i + 1]) / 255.0f, float(rgba8[4 * i + 2]) / 255.0f, float(rgba8[4 * i + 3]) / 255.0f);
+			continue;
+		}
 		linear[i] = Vector4(
 			Math::gamma_to_linear(float(rgba8[4 * i + 0]) / 255.0f),
 			Math::gamma_to_linear(float(rgba8[4 * i + 1]) / 255.0f),
@@ -347,7 +355,7 @@ bool TextureLoader::load(const std::string & filename, Texture * texture) {
 	// again right away. The compressed chain ends at the level that is one block in size, and the LOD bias
 	// is derived from the block counts (see Texture::lod_width).
 	auto is_power_of_two = [](int x) { return x > 0 && (x & (x - 1)) == 0; };
-	if (cpu_config.enable_block_compression && is_power_of_two(width) && is_power_of_two(height)) {
+	if (cpu_config.enable_block_compression && !texture->data && is_power_of_two(width) && is_power_of_two(height)) {
 		int blocks_w = (width + 3) / 4, blocks_h = (height + 3) / 4;
 		size_t kept_levels = 0;
 		for (int w = blocks_w, h = blocks_h;;) {

@@ -166,6 +166,39 @@ int grt_scene_set_material(void * scene, int index, int type, const float * diff
 }
 int grt_scene_material_type(void * scene, int index) { return int(((Scene *)scene)->asset_manager.materials[index].type); }
 
+// Tangent-space normal maps, kept out of grt_scene_describe (whose listing is pinned for scenes without them).
+// texture: an index of the scene's textures, or -1 (none); takes effect at the next update after invalidate("materials").
+int grt_scene_material_normal_map(void * scene, int index) {
+	Scene * s = (Scene *)scene;
+	if (index < 0 || index >= int(s->asset_manager.materials.size())) { g_host_error = "grt_scene_material_normal_map: material index out of range"; return -2; }
+	return s->asset_manager.materials[index].normal_map_handle.handle;
+}
+int grt_scene_set_material_normal_map(void * scene, int index, int texture) {
+	Scene * s = (Scene *)scene;
+	if (index < 0 || index >= int(s->asset_manager.materials.size())) { g_host_error = "grt_scene_set_material_normal_map: material index out of range"; return -1; }
+	if (texture < -1 || texture >= int(s->asset_manager.textures.size())) { g_host_error = "grt_scene_set_material_normal_map: texture index out of range"; return -1; }
+	s->asset_manager.materials[index].normal_map_handle.handle = texture;
+	return 0;
+}
+// Adds a texture file to the scene; data != 0: a data texture (normal map, see Texture::data). Textures reach the device when a
+// Pathtracer is created, so add them before. Returns the texture index, -1 on failure.
+int grt_scene_add_texture(void * scene, const char * filename, int data) {
+	GRT_TRY
+		Scene * s = (Scene *)scene;
+		std::string path(filename);
+		size_t slash = path.find_last_of("/\\");
+		Handle<Texture> h = s->asset_manager.add_texture(path, slash == std::string::npos ? path : path.substr(slash + 1),
+		                                                 data ? AssetManager::TextureKind::DATA : AssetManager::TextureKind::COLOUR);
+		return h.handle;
+	GRT_CATCH(-1)
+}
+// 1: the texture is kept as BC1 blocks (block compression), 0: RGBA8 texels
+int grt_scene_texture_compressed(void * scene, int texture) {
+	GRT_TRY
+		return ((Scene *)scene)->asset_manager.textures.at(texture).bc1_blocks.empty() ? 0 : 1;
+	GRT_CATCH(-1)
+}
+
 // A line-per-object listing of what the loaders produced (camera, meshes, materials, media, texture names, sky size),
 // floats as bit patterns: `pathtracer`-independent way to diff two loads of a scene. Returns the length needed.
 static void describe_floats(std::string & s, const char * key, const float * v, int n) {

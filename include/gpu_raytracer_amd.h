@@ -152,8 +152,9 @@ const char * rt_version(void);
  *  11  rt_set_sky_sampling, rt_get_sky_sampling, rt_sample_sky_distribution, rt_sky_pdf (additions only; sky importance sampling, off by default)
  *  12  rt_bsdf_eval, rt_bsdf_sample (additions only)
  *  13  rt_trace_stream_rays (additions only)
+ *  14  rt_upload_material_normal_maps, rt_perturb_normals (additions only; tangent-space normal maps)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
-#define RT_ABI_VERSION 13
+#define RT_ABI_VERSION 14
 int rt_abi_version(void);
 
 /* ---- scene upload ------------------------------------------------------------------- */
@@ -268,6 +269,11 @@ int rt_upload_instances(rt_context * ctx, const int32_t * root_indices, const in
 /* Replaces material_types / materials (Pathtracer.cpp:545-589): types = 1 B each,
  * materials = 32 B each in the union layout of CUDA/Material.h:21-39.                    */
 int rt_upload_materials(rt_context * ctx, const uint8_t * types, const void * materials, size_t count);
+/* Tangent-space normal maps, beside the 32-byte records: texture_ids[i] is the map of material i of the last
+ * rt_upload_materials, or -1 (none). count must equal that upload's material count and every id must name an RT_TEXTURE_RGBA8
+ * texture of the last rt_upload_textures; otherwise RT_ERROR_INVALID_ARG and the table stays as it was. rt_upload_materials
+ * and rt_upload_textures reset the table to none. Only materials of the four surface types use their map.                                       */
+int rt_upload_material_normal_maps(rt_context * ctx, const int32_t * texture_ids, size_t count);
 /* Replaces `media` (Pathtracer.cpp:681-697): 32 B each {sigma_a.xyz, g, sigma_s.xyz, pad}. */
 int rt_upload_media(rt_context * ctx, const void * media, size_t count);
 /* Replaces `textures` (Integrator.cpp:33-98). */
@@ -571,6 +577,15 @@ int rt_sky_pdf(rt_context * ctx, const float * directions, size_t count, float *
  * factor (sample)[3], direction (to_light, or the sampled one)[3], medium id, allow_nee, omega_i.z, pad}. Writes no frame buffer. */
 int rt_bsdf_eval(rt_context * ctx, int material_type, const float * probes, size_t count, float * out);
 int rt_bsdf_sample(rt_context * ctx, int material_type, const float * probes, size_t count, float * out);
+/* The shade kernels' normal-map perturbation (normal_map_perturb, rt_shading.h) on explicit hits (synchronous), with texture
+ * `texture_index` (RT_TEXTURE_RGBA8) of the last rt_upload_textures as the map. probes: count x RT_NORMAL_PROBE_IN floats
+ * {p0[3], e1[3], e2[3] (object-space triangle: vertex 0 and the two edges), n0[3], ne1[3], ne2[3] (vertex normal 0 and its
+ * edges), uv0[2], uve1[2], uve2[2], u, v (barycentrics), world[12] (3x4 row-major: rotation and uniform scale), ray direction[3],
+ * filter (0: level 0, 1: lod, 2: gradients), lod (filter 1; the texture's lod bias is added as in the shade kernels),
+ * gradient_1[2], gradient_2[2] (filter 2), pad}. out: count x 4 floats {world shading normal[3] (on the side the ray arrives
+ * from, after the view guard), 1 if the hit fell back to the interpolated normal else 0}.                                 */
+#define RT_NORMAL_PROBE_IN 48
+int rt_perturb_normals(rt_context * ctx, int texture_index, const float * probes, size_t count, float * out);
 /* Streaming-read bandwidth probe used as the measured HBM roofline (GB/s).                 */
 int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps);
 
