@@ -70,8 +70,8 @@ def device_lib():
         if not os.path.exists(DEVICE_LIB_PATH):
             raise DeviceLibraryMissing("%s is missing -- run `python __graft_entry__.py` (build()) first" % DEVICE_LIB_PATH)
         lib = ctypes.CDLL(DEVICE_LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        if hasattr(lib, "rt_abi_version") and lib.rt_abi_version() != 14:
-            raise DeviceLibraryMissing("%s has ABI version %d, this front end was written for 14 -- rebuild (python __graft_entry__.py)" % (DEVICE_LIB_PATH, lib.rt_abi_version()))
+        if hasattr(lib, "rt_abi_version") and lib.rt_abi_version() != 15:
+            raise DeviceLibraryMissing("%s has ABI version %d, this front end was written for 15 -- rebuild (python __graft_entry__.py)" % (DEVICE_LIB_PATH, lib.rt_abi_version()))
         lib.rt_last_error.restype = c_char_p
         lib.rt_last_error.argtypes = [c_void_p]
         lib.rt_version.restype = c_char_p
@@ -90,6 +90,8 @@ def device_lib():
         lib.rt_sky_pdf.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
         lib.rt_bsdf_eval.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p]
         lib.rt_bsdf_sample.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p]
+        lib.rt_sample_lights.argtypes = [c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+        lib.rt_upload_lights.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_float]
         lib.rt_upload_material_normal_maps.argtypes = [c_void_p, c_void_p, c_size_t]
         lib.rt_perturb_normals.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p]
         lib.rt_set_sky_sampling.argtypes = [c_void_p, c_float]
@@ -967,6 +969,30 @@ def bsdf_sample(ctx, material_type, probes):
     """rt_bsdf_sample: the same BSDF's sample on (N, 24) probe records. Returns (N, 12) float32 {ok, pdf, throughput factor[3],
     direction[3], medium, allow_nee, omega_i.z, pad}."""
     return _bsdf_probe(ctx, device_lib().rt_bsdf_sample, material_type, probes)
+
+
+LIGHT_SAMPLE_OUT = 16   # floats per output record of rt_sample_lights
+
+
+def sample_lights(ctx, probes, use_lds=True):
+    """rt_sample_lights: the shade kernels' nee_pick_light on (N, 4) {u_mesh, u_triangle, u_1, u_2} in [0, 1), on the light tables
+    the context holds; use_lds: tables chosen as the shade kernels choose them (LDS when they fit), else global memory. Returns
+    (N, 16) float32 {entry, transform id, triangle, read LDS (int32 bits: .view(np.int32)), point[3], normal[3], emission[3], pad[3]}."""
+    p = _f32(probes).reshape(-1, 4)
+    out = np.zeros((p.shape[0], LIGHT_SAMPLE_OUT), np.float32)
+    _dev_check(ctx, device_lib().rt_sample_lights(ctx, p.ctypes.data, p.shape[0], 1 if use_lds else 0, out.ctypes.data))
+    return out
+
+
+def upload_lights(ctx, triangle_indices, triangle_cdf, mesh_cdf, mesh_spans, mesh_transform_indices, total_weight):
+    """rt_upload_lights on numpy tables (mesh_spans: (M, 2) {first, last}). Returns the status (0: RT_OK); the message of a
+    refusal is rt_last_error's."""
+    ti = np.ascontiguousarray(triangle_indices, dtype=np.int32); tc = _f32(triangle_cdf)
+    mc = _f32(mesh_cdf); ms = np.ascontiguousarray(mesh_spans, dtype=np.int32); mt = np.ascontiguousarray(mesh_transform_indices, dtype=np.int32)
+    if tc.size != ti.size or ms.size != 2 * mc.size or mt.size != mc.size:
+        raise ValueError("upload_lights: tables of different lengths")
+    ptr = lambda a: a.ctypes.data if a.size else None
+    return device_lib().rt_upload_lights(ctx, ptr(ti), ptr(tc), ti.size, ptr(mc), ptr(ms), ptr(mt), mc.size, float(total_weight))
 
 
 NORMAL_PROBE_IN = 48   # floats per probe record of rt_perturb_normals

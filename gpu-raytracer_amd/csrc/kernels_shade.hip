@@ -1014,6 +1014,33 @@ RT_DEV bool next_event_estimation(const RtParams & p, const LightTablesLDS * lig
 	return nee_connect<true>(p, nee_pick_light(p, light_lds, rand_light, rand_triangle), bsdf, hit_point, normal, geometric_normal, throughput, 1.0f - share, shadow);
 }
 
+// rt_sample_lights: nee_pick_light on explicit random numbers, with the tables chosen as shade_material chooses them (use_lds: the
+// workgroup of RT_SHADE_BLOCK threads copies them with light_tables_to_lds and passes the copy) or from global memory (nullptr).
+// Record in: {u_mesh, u_triangle, u_1, u_2}; out: RT_LIGHT_SAMPLE_OUT floats {light-mesh entry, transform id (after the mesh_position
+// remap), triangle index, 1 if the searches read LDS else 0 (int32 bits), point[3], geometric normal[3], emission[3], pad[3]}.
+// The transform id and the triangle are sample_light's own; the entry is the first of its two searches made again on the same table.
+__global__ void kernel_sample_lights(RtParams p, const float * probes, int count, int use_lds, float * out) {
+	__shared__ LightTablesLDS light_lds;
+	if (use_lds) light_tables_to_lds(p, light_lds);
+	__syncthreads();
+	const LightTablesLDS * const light_tables = use_lds ? &light_lds : nullptr;
+	int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= count) return;
+	const float * a = probes + size_t(i) * 4;
+	float * o = out + size_t(i) * RT_LIGHT_SAMPLE_OUT;
+	const bool from_lds = light_tables != nullptr && light_tables_fit_lds(p);
+	int entry = from_lds ? binary_search((LdsFloatTable)light_tables->mesh_cdf, 0, p.light_mesh_count - 1, a[0])
+	                     : binary_search(p.light_mesh_cumulative_probability, 0, p.light_mesh_count - 1, a[0]);
+	int transform_id;
+	int triangle_id = sample_light(p, light_tables, a[0], a[1], transform_id);
+	LightSample light = nee_pick_light(p, light_tables, mk2(a[0], a[1]), mk2(a[2], a[3]));
+	o[0] = __int_as_float(entry); o[1] = __int_as_float(transform_id); o[2] = __int_as_float(triangle_id); o[3] = __int_as_float(from_lds ? 1 : 0);
+	o[4] = light.point.x; o[5] = light.point.y; o[6] = light.point.z;
+	o[7] = light.geometric_normal.x; o[8] = light.geometric_normal.y; o[9] = light.geometric_normal.z;
+	o[10] = light.emission.x; o[11] = light.emission.y; o[12] = light.emission.z;
+	o[13] = o[14] = o[15] = 0.0f;
+}
+
 // ---- shade_material<BSDF> (Pathtracer.cu:557-757) -------------------------------------------------------------
 
 RT_DEV float triangle_get_lod(float double_area_world_inv, f2 te1, f2 te2) {
@@ -1512,7 +1539,10 @@ static void launch_bsdf_probe(const RtParams & p, int material_type, const float
 		case RT_MATERIAL_CONDUCTOR:  hipLaunchKernelGGL((kernel_bsdf_probe<BSDFConductor,  EVAL>), grid, block, 0, stream, p, probes, count, out); break;
 	}
 }
-void rt_launch_bsdf_probe(const RtParams & p, int material_type, bool eval, const float * probes, int count, float * out, hipStream_t stream) {
+void rt_launch_sample_lights(const RtParams & p, const float * probes, int count, bool use_lds, float * out, hipStream_t stream) {
+	hipLaunchKernelGGL(kernel_sample_lights, dim3((count + RT_SHADE_BLOCK - 1) / RT_SHADE_BLOCK), dim3(RT_SHADE_BLOCK), 0, stream, p, probes, count, use_lds ? 1 : 0, out);
+}
+void rt_launch_bsdf_probe(const RtParams & p, int material_type, bool eval,const float * probes, int count, float * out, hipStream_t stream) {
 	if (eval) launch_bsdf_probe<true>(p, material_type, probes, count, out, stream);
 	else      launch_bsdf_probe<false>(p, material_type, probes, count, out, stream);
 }

@@ -1113,11 +1113,46 @@ int rt_upload_textures(rt_context * ctx, const rt_texture_desc * descs, size_t c
 	return RT_OK;
 }
 
+// binary_search (rt_shading.h) ends inside its span only if the span's last entry is >= the searched value, and it is searched with numbers
+// below 1: a table that ends lower sends every lane that draws a larger number past its end, for good. So the mesh table and every span a mesh
+// entry names are checked here, on the host, before anything is staged. Triangle entries no mesh refers to are left alone: an emitter of zero
+// emission or zero area has no mesh entry, and its stretch of the triangle table may hold NaN (0 / 0).
+static int check_cumulative_table(rt_context * ctx, const char * what, const float * cdf, size_t first, size_t last) {
+	for (size_t i = first; i <= last; i++) {
+		if (std::isnan(cdf[i])) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_lights: %s: entry %zu is NaN", what, i);
+		if (i > first && cdf[i] < cdf[i - 1]) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_lights: %s: entry %zu (%.9g) is below entry %zu (%.9g)", what, i, double(cdf[i]), i - 1, double(cdf[i - 1]));
+	}
+	if (cdf[last] < 1.0f) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_lights: %s: its last entry, %zu, is %.9g, below 1: a search for a larger number would not end", what, last, double(cdf[last]));
+	return RT_OK;
+}
+static int check_light_tables(rt_context * ctx, const int32_t * triangle_indices, const float * triangle_cdf, size_t triangle_count,
+                              const float * mesh_cdf, const int32_t * mesh_span, const int32_t * mesh_transform_indices, size_t mesh_count, float total_weight) {
+	if (triangle_count > size_t(INT32_MAX) || mesh_count > size_t(INT32_MAX)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_lights: more than 2^31 - 1 table entries");
+	if (!std::isfinite(total_weight) || total_weight < 0.0f) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_lights: lights_total_weight is %.9g (it must be finite and not negative)", double(total_weight));
+	if (triangle_count > 0 && (!triangle_indices || !triangle_cdf)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_lights: NULL triangle table with light_triangle_count = %zu", triangle_count);
+	if (mesh_count == 0) return RT_OK;
+	if (!mesh_cdf || !mesh_span || !mesh_transform_indices) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_lights: NULL mesh table with light_mesh_count = %zu", mesh_count);
+	if (!(total_weight > 0.0f)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_lights: lights_total_weight is 0 with %zu light mesh entries", mesh_count);
+	int s = check_cumulative_table(ctx, "the light mesh table", mesh_cdf, 0, mesh_count - 1); if (s) return s;
+	for (size_t m = 0; m < mesh_count; m++) {
+		long long first = mesh_span[2 * m], last = mesh_span[2 * m + 1];
+		if (first < 0 || last >= (long long)triangle_count || first > last)
+			return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_lights: light mesh entry %zu: its triangle span [%lld, %lld] is not inside [0, %zu) with first <= last", m, first, last, triangle_count);
+		if (m > 0 && mesh_span[2 * m] == mesh_span[2 * m - 2] && mesh_span[2 * m + 1] == mesh_span[2 * m - 1]) continue;   // (instances of one mesh data: the span just checked)
+		char what[96]; snprintf(what, sizeof(what), "the triangle table in the span [%lld, %lld] of light mesh entry %zu", first, last, m);
+		s = check_cumulative_table(ctx, what, triangle_cdf, size_t(first), size_t(last)); if (s) return s;
+	}
+	return RT_OK;
+}
+
 int rt_upload_lights(rt_context * ctx,
                      const int32_t * light_triangle_indices, const float * light_triangle_cumulative_probability, size_t light_triangle_count,
                      const float * light_mesh_cumulative_probability, const int32_t * light_mesh_triangle_span,
                      const int32_t * light_mesh_transform_indices, size_t light_mesh_count, float lights_total_weight) {
 	RT_REQUIRE(ctx, ctx, "rt_upload_lights: NULL context");
+	int s = check_light_tables(ctx, light_triangle_indices, light_triangle_cumulative_probability, light_triangle_count,
+	                           light_mesh_cumulative_probability, light_mesh_triangle_span, light_mesh_transform_indices, light_mesh_count, lights_total_weight);
+	if (s) return s;   // (nothing staged: the tables uploaded before stay in force)
 	(void)hipSetDevice(ctx->device);
 	// the per-mesh tables change with every TLAS rebuild (they are in TLAS order): versioned like the TLAS itself
 	const void * src[5] = { light_triangle_indices, light_triangle_cumulative_probability, light_mesh_cumulative_probability, light_mesh_triangle_span, light_mesh_transform_indices };
@@ -1125,7 +1160,7 @@ int rt_upload_lights(rt_context * ctx,
 	size_t offset[6] = { 0 };
 	for (int i = 0; i < 5; i++) offset[i + 1] = offset[i] + ((src[i] ? bytes[i] : 0) + 15) / 16 * 16;
 	void * staging = nullptr;
-	int s = ring_begin(ctx, ctx->light_ring, offset[5], &staging); if (s) return s;
+	s = ring_begin(ctx, ctx->light_ring, offset[5], &staging); if (s) return s;
 	for (int i = 0; i < 5; i++) if (src[i] && bytes[i]) memcpy((char *)staging + offset[i], src[i], bytes[i]);
 	s = ring_commit(ctx, ctx->light_ring); if (s) return s;
 	const char * base = (const char *)ctx->light_ring.device[ctx->light_ring.current];
@@ -2922,6 +2957,31 @@ int rt_bsdf_eval(rt_context * ctx, int material_type, const float * probes, size
 }
 int rt_bsdf_sample(rt_context * ctx, int material_type, const float * probes, size_t count, float * out) {
 	return bsdf_probe(ctx, "rt_bsdf_sample", false, material_type, probes, count, out);
+}
+
+int rt_sample_lights(rt_context * ctx, const float * probes, size_t count, int use_lds, float * out) {
+	RT_REQUIRE(ctx, ctx && probes && out, "rt_sample_lights: NULL argument");
+	RT_REQUIRE(ctx, count <= size_t(1) << 24, "rt_sample_lights: more than 2^24 probes");
+	RT_REQUIRE(ctx, use_lds == 0 || use_lds == 1, "rt_sample_lights: use_lds must be 0 (global memory) or 1 (as the shade kernels choose)");
+	const RtParams & p = ctx->params;
+	if (p.light_mesh_count <= 0 || p.light_triangle_count <= 0 || !(p.lights_total_weight > 0.0f))
+		return fail(ctx, RT_ERROR_NOT_READY, "rt_sample_lights: no lights uploaded (rt_upload_lights with at least one light mesh entry)");
+	if (!p.triangles || !p.mesh_transforms || !p.mesh_material_ids || !p.materials)
+		return fail(ctx, RT_ERROR_NOT_READY, "rt_sample_lights: geometry, instance tables or materials not uploaded");
+	for (size_t i = 0; i < count * 4; i++)   // (the searches end only for numbers up to the tables' last entry, 1)
+		if (!(probes[i] >= 0.0f && probes[i] < 1.0f)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sample_lights: probe %zu: random number %zu is %.9g, outside [0, 1)", i / 4, i % 4, double(probes[i]));
+	(void)hipSetDevice(ctx->device);
+	int s = sky_sampling_prepare(ctx, "rt_sample_lights"); if (s) return s;   // (as a render settles it; the selection does not read it)
+	if (count == 0) return RT_OK;
+	TempBuffers tmp(ctx);
+	float * dev_probes = (float *)tmp.get(count * 16, probes);
+	float * dev_out = (float *)tmp.get(count * RT_LIGHT_SAMPLE_OUT * 4, nullptr);
+	if (!dev_probes || !dev_out) return fail(ctx, RT_ERROR_HIP, "rt_sample_lights: device allocation failed");
+	rt_launch_sample_lights(p, dev_probes, int(count), use_lds != 0, dev_out, ctx->stream);
+	RT_HIP(ctx, hipGetLastError());
+	RT_HIP(ctx, quiesce(ctx));
+	RT_HIP(ctx, hipMemcpy(out, dev_out, count * RT_LIGHT_SAMPLE_OUT * 4, hipMemcpyDeviceToHost));
+	return RT_OK;
 }
 
 int rt_perturb_normals(rt_context * ctx, int texture_index, const float * probes, size_t count, float * out) {

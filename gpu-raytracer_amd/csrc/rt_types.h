@@ -286,6 +286,8 @@ void rt_launch_sample_sky(const RtParams & p, const float * directions, int coun
 #define RT_BSDF_PROBE_IN  24
 #define RT_BSDF_PROBE_OUT 12
 void rt_launch_bsdf_probe(const RtParams & p, int material_type, bool eval, const float * probes, int count, float * out, hipStream_t stream);
+// Test support: nee_pick_light on explicit random numbers (rt_sample_lights); 4 floats in, RT_LIGHT_SAMPLE_OUT out per probe
+void rt_launch_sample_lights(const RtParams & p, const float * probes, int count, bool use_lds, float * out, hipStream_t stream);
 // Test support: normal_map_perturb on explicit hits (rt_perturb_normals); RT_NORMAL_PROBE_IN floats in, 4 out per probe
 void rt_launch_perturb_normals(const RtParams & p, int texture_index, const float * probes, int count, float * out, hipStream_t stream);
 // Sky importance sampling (kernels_sky.hip). build: the three tables of RtParams from the sky; row_total: sky_height doubles, total: one double (the

@@ -153,8 +153,9 @@ const char * rt_version(void);
  *  12  rt_bsdf_eval, rt_bsdf_sample (additions only)
  *  13  rt_trace_stream_rays (additions only)
  *  14  rt_upload_material_normal_maps, rt_perturb_normals (additions only; tangent-space normal maps)
+ *  15  rt_sample_lights (addition); rt_upload_lights refuses tables on which the light search would not end (see there)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
-#define RT_ABI_VERSION 14
+#define RT_ABI_VERSION 15
 int rt_abi_version(void);
 
 /* ---- scene upload ------------------------------------------------------------------- */
@@ -287,7 +288,13 @@ int rt_upload_textures(rt_context * ctx, const rt_texture_desc * descs, size_t c
  * images. Takes effect at the next rt_upload_textures. rt_texture_bytes: device bytes the uploaded textures occupy.          */
 int rt_set_texture_expansion(rt_context * ctx, int enable);
 size_t rt_texture_bytes(rt_context * ctx);
-/* Replaces light_* globals and lights_total_weight (Pathtracer.cpp:455-534).             */
+/* Replaces light_* globals and lights_total_weight (Pathtracer.cpp:455-534).
+ * The kernels' search of a cumulative table (binary_search) ends inside its span only if the span's last entry is >= the number
+ * searched for, so the tables are checked on the host before anything is staged: the mesh table, and every span of the triangle
+ * table that a mesh entry names (entries no mesh refers to are not looked at), must hold no NaN, must never decrease and must
+ * end in an entry >= 1.0f; every span must satisfy 0 <= first <= last < light_triangle_count; lights_total_weight must be finite
+ * and >= 0, and > 0 when there are mesh entries. Otherwise RT_ERROR_INVALID_ARG with a message that names the entry, and the
+ * tables uploaded before stay in force. Empty tables (no emitters) are valid.                                                  */
 int rt_upload_lights(rt_context * ctx,
                      const int32_t * light_triangle_indices, const float * light_triangle_cumulative_probability, size_t light_triangle_count,
                      const float * light_mesh_cumulative_probability, const int32_t * light_mesh_triangle_span /* 2 per mesh */,
@@ -577,6 +584,15 @@ int rt_sky_pdf(rt_context * ctx, const float * directions, size_t count, float *
  * factor (sample)[3], direction (to_light, or the sampled one)[3], medium id, allow_nee, omega_i.z, pad}. Writes no frame buffer. */
 int rt_bsdf_eval(rt_context * ctx, int material_type, const float * probes, size_t count, float * out);
 int rt_bsdf_sample(rt_context * ctx, int material_type, const float * probes, size_t count, float * out);
+/* The shade kernels' light selection on explicit random numbers (synchronous): nee_pick_light -- sample_light's two table searches,
+ * sample_triangle, the point, normal and emission of the emitter -- on the light tables, triangles, transforms and materials the context
+ * holds. probes: count x 4 floats {u_mesh, u_triangle, u_1, u_2}, each in [0, 1). use_lds = 1: the tables are chosen as the shade
+ * kernels choose them (a workgroup copies them into LDS when there are at most 64 mesh entries and 2048 triangle entries, else global
+ * memory); 0: global memory. out: count x RT_LIGHT_SAMPLE_OUT floats {light-mesh entry, transform id (row of the instance tables, after
+ * the device-built TLAS's remapping), triangle index, 1 if the searches read LDS else 0 (these four int32 bits), point[3], geometric
+ * normal[3], emission[3], pad[3]}. RT_ERROR_NOT_READY without emitters. Writes no frame buffer.                                      */
+#define RT_LIGHT_SAMPLE_OUT 16
+int rt_sample_lights(rt_context * ctx, const float * probes, size_t count, int use_lds, float * out);
 /* The shade kernels' normal-map perturbation (normal_map_perturb, rt_shading.h) on explicit hits (synchronous), with texture
  * `texture_index` (RT_TEXTURE_RGBA8) of the last rt_upload_textures as the map. probes: count x RT_NORMAL_PROBE_IN floats
  * {p0[3], e1[3], e2[3] (object-space triangle: vertex 0 and the two edges), n0[3], ne1[3], ne2[3] (vertex normal 0 and its

@@ -113,6 +113,7 @@ def lib():
         l.oracle_average_dielectric.argtypes = [c_void_p, c_void_p]
         l.oracle_bsdf_eval.argtypes = [POINTER(OracleScene), c_int, c_void_p, c_size_t, c_void_p]
         l.oracle_bsdf_sample.argtypes = [POINTER(OracleScene), c_int, c_void_p, c_size_t, c_void_p]
+        l.oracle_sample_lights.argtypes = [POINTER(OracleScene), c_void_p, c_size_t, c_void_p]
         l.oracle_average_conductor.argtypes = [c_void_p, c_void_p]
         tex_p = POINTER(OracleTexture)
         l.oracle_tex2d.argtypes = [tex_p, c_float, c_float, c_void_p]
@@ -585,6 +586,40 @@ def sample_sky(rgba, scale, directions):
     return out
 
 
+def check_light_tables(triangle_cdf, mesh_cdf, mesh_spans, total_weight):
+    """The rules of rt_upload_lights (include/gpu_raytracer_amd.h): the oracle's binary_search, like the device's, ends inside a span
+    only if the span's last entry is >= the searched number. Looks at the mesh table and at the spans it names, at nothing else.
+    Raises ValueError naming the entry."""
+    triangle_cdf = np.asarray(triangle_cdf, np.float32).reshape(-1); mesh_cdf = np.asarray(mesh_cdf, np.float32).reshape(-1)
+    spans = np.asarray(mesh_spans, np.int64).reshape(-1, 2)
+
+    def table(what, cdf, first, last):
+        span = cdf[first:last + 1]
+        if np.isnan(span).any():
+            raise ValueError("light tables: %s: entry %d of its cumulative table is NaN" % (what, first + int(np.isnan(span).argmax())))
+        down = np.nonzero(span[1:] < span[:-1])[0]
+        if down.size:
+            raise ValueError("light tables: %s: entry %d of its cumulative table is below entry %d" % (what, first + down[0] + 1, first + down[0]))
+        if span[-1] < np.float32(1.0):
+            raise ValueError("light tables: %s: the last entry of its cumulative table, %d, is %.9g, below 1" % (what, last, span[-1]))
+
+    if not np.isfinite(total_weight) or total_weight < 0:
+        raise ValueError("light tables: lights_total_weight is %r" % total_weight)
+    if mesh_cdf.size == 0:
+        return
+    if spans.shape[0] != mesh_cdf.size:
+        raise ValueError("light tables: %d spans for %d light mesh entries" % (spans.shape[0], mesh_cdf.size))
+    if not total_weight > 0:
+        raise ValueError("light tables: lights_total_weight is 0 with %d light mesh entries" % mesh_cdf.size)
+    table("light meshes", mesh_cdf, 0, mesh_cdf.size - 1)
+    for m, (first, last) in enumerate(spans):
+        if first < 0 or last >= triangle_cdf.size or first > last:
+            raise ValueError("light tables: light mesh entry %d: its triangle span [%d, %d] is not inside [0, %d) with first <= last" % (m, first, last, triangle_cdf.size))
+        if m > 0 and (spans[m] == spans[m - 1]).all():
+            continue
+        table("light mesh entry %d" % m, triangle_cdf, int(first), int(last))
+
+
 class SceneView:
     """Keeps the numpy arrays alive that an OracleScene points into."""
 
@@ -623,6 +658,8 @@ class SceneView:
         s.light_mesh_cumulative_probability = arr("light_mesh_cumulative_probability"); s.light_mesh_triangle_span = arr("light_mesh_triangle_span")
         s.light_mesh_transform_indices = arr("light_mesh_transform_indices"); s.light_mesh_count = self.keep["light_mesh_transform_indices"].size
         s.lights_total_weight = pt.lights_total_weight
+        check_light_tables(self.keep["light_triangle_cumulative_probability"], self.keep["light_mesh_cumulative_probability"],
+                           self.keep["light_mesh_triangle_span"], s.lights_total_weight)
         s.pmj_samples = arr("pmj_samples"); s.blue_noise = arr("blue_noise")
 
         if luts is not None:
@@ -689,6 +726,15 @@ class SceneView:
         out = np.zeros((p.shape[0], 12), np.float32)
         if fn(byref(self.scene), int(material_type), p.ctypes.data, p.shape[0], out.ctypes.data) != 0:
             raise ValueError("unknown material type %r" % material_type)
+        return out
+
+    def sample_lights(self, probes):
+        """oracle_sample_lights on (N, 4) {u_mesh, u_triangle, u_1, u_2} (rt_sample_lights's records). Returns (N, 16) float32."""
+        p = np.ascontiguousarray(probes, np.float32).reshape(-1, 4)
+        out = np.zeros((p.shape[0], 16), np.float32)
+        status = lib().oracle_sample_lights(byref(self.scene), p.ctypes.data, p.shape[0], out.ctypes.data)
+        if status != 0:
+            raise ValueError("oracle_sample_lights: %s" % {-1: "the scene has no light tables", -2: "a random number outside [0, 1)"}.get(status, status))
         return out
 
     def random(self, dimension, pixel_indices, bounce, sample_index):

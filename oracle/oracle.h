@@ -172,6 +172,10 @@ void oracle_random(const oracle_scene * scene, int dimension, const uint32_t * p
  * shade_material sets it up; the scene gives the random numbers and the Kulla-Conty tables. -1 for an unknown material_type. */
 int oracle_bsdf_eval(const oracle_scene * scene, int material_type, const float * probes, size_t count, float * out);
 int oracle_bsdf_sample(const oracle_scene * scene, int material_type, const float * probes, size_t count, float * out);
+/* The light selection of next_event_estimation (Pathtracer.cu:472-493) on the records of rt_sample_lights: 4 floats in {u_mesh,
+ * u_triangle, u_1, u_2}, 16 out {light-mesh entry, transform id, triangle index, 0 (int32 bits), point[3], geometric normal[3],
+ * emission[3], pad[3]}. -1: the scene has no light tables; -2: a random number outside [0, 1). */
+int oracle_sample_lights(const oracle_scene * scene, const float * probes, size_t count, float * out);
 /* Pathtracer::render for one sample over pixels [pixel_offset, pixel_offset+pixel_count)
  * (Pathtracer.cpp:738-855): batches, bounces, accumulate or SVGF/TAA. */
 void oracle_render_sample(const oracle_scene * scene, oracle_frame * frame, int sample_index,

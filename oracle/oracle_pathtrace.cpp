@@ -749,13 +749,11 @@ inline int sample_light(const oracle_scene & s, float u1, float u2, int & transf
 	return s.light_triangle_indices[light_triangle_id];
 }
 
-// next_event_estimation, Pathtracer.cu:465-555
-template<typename BSDF>
-void next_event_estimation(Context & c, Wavefront & w, int pixel_index, int bounce, int sample_index, const BSDF & bsdf, float3 hit_point, float3 normal, float3 geometric_normal, float3 throughput) {
-	const oracle_scene & s = c.s;
-	float2 rand_light    = c.random(DIM_NEE_LIGHT,    pixel_index, bounce, sample_index);
-	float2 rand_triangle = c.random(DIM_NEE_TRIANGLE, pixel_index, bounce, sample_index);
-
+// The first part of next_event_estimation (Pathtracer.cu:472-493, 509-511): the emitter's point, normal and emission the random numbers select.
+// It does not depend on the surface; next_event_estimation and oracle_sample_lights both call it.
+struct LightPick { int transform_id, triangle_id; float3 point, geometric_normal, emission; };
+inline LightPick pick_light(const oracle_scene & s, float2 rand_light, float2 rand_triangle) {
+	LightPick light;
 	int light_mesh_id;
 	int light_triangle_id = sample_light(s, rand_light.x, rand_light.y, light_mesh_id);
 	float2 light_uv = sample_triangle(rand_triangle.x, rand_triangle.y);
@@ -765,8 +763,25 @@ void next_event_estimation(Context & c, Wavefront & w, int pixel_index, int boun
 	float3 light_geometric_normal = cross(tri.position_edge_1, tri.position_edge_2);
 
 	const float * light_world = mesh_transform(s, light_mesh_id);
-	light_point = m_position(light_world, light_point);
-	light_geometric_normal = normalize(m_direction(light_world, light_geometric_normal));
+	light.point = m_position(light_world, light_point);
+	light.geometric_normal = normalize(m_direction(light_world, light_geometric_normal));
+
+	int light_material_id = s.mesh_material_ids[light_mesh_id];
+	const float * lm = s.materials + size_t(light_material_id) * 8;
+	light.emission = make_float3(lm[0], lm[1], lm[2]);
+	light.transform_id = light_mesh_id; light.triangle_id = light_triangle_id;
+	return light;
+}
+
+// next_event_estimation, Pathtracer.cu:465-555
+template<typename BSDF>
+void next_event_estimation(Context & c, Wavefront & w, int pixel_index, int bounce, int sample_index, const BSDF & bsdf, float3 hit_point, float3 normal, float3 geometric_normal, float3 throughput) {
+	const oracle_scene & s = c.s;
+	float2 rand_light    = c.random(DIM_NEE_LIGHT,    pixel_index, bounce, sample_index);
+	float2 rand_triangle = c.random(DIM_NEE_TRIANGLE, pixel_index, bounce, sample_index);
+
+	LightPick light = pick_light(s, rand_light, rand_triangle);
+	float3 light_point = light.point, light_geometric_normal = light.geometric_normal;
 
 	hit_point   = ray_origin_epsilon_offset(hit_point,   light_point - hit_point, geometric_normal);
 	light_point = ray_origin_epsilon_offset(light_point, hit_point - light_point, light_geometric_normal);
@@ -778,9 +793,7 @@ void next_event_estimation(Context & c, Wavefront & w, int pixel_index, int boun
 	float cos_theta_light = abs_dot(to_light, light_geometric_normal);
 	float cos_theta_hit = dot(to_light, normal);
 
-	int light_material_id = s.mesh_material_ids[light_mesh_id];
-	const float * lm = s.materials + size_t(light_material_id) * 8;
-	float3 emission = make_float3(lm[0], lm[1], lm[2]);
+	float3 emission = light.emission;
 
 	float3 bsdf_value; float bsdf_pdf;
 	if (!bsdf.eval(to_light, cos_theta_hit, bsdf_value, bsdf_pdf)) return;
@@ -972,6 +985,26 @@ int oracle_bsdf_eval(const oracle_scene * scene, int material_type, const float 
 }
 int oracle_bsdf_sample(const oracle_scene * scene, int material_type, const float * probes, size_t count, float * out) {
 	return bsdf_probe<false>(*scene, material_type, probes, count, out);
+}
+
+// oracle_sample_lights: pick_light on the records of rt_sample_lights (4 floats in, 16 out). No LDS here: the path flag is 0.
+int oracle_sample_lights(const oracle_scene * scene, const float * probes, size_t count, float * out) {
+	const oracle_scene & s = *scene;
+	if (s.light_mesh_count <= 0 || s.light_triangle_count <= 0) return -1;
+	for (size_t i = 0; i < count * 4; i++) if (!(probes[i] >= 0.0f && probes[i] < 1.0f)) return -2;
+	for (size_t i = 0; i < count; i++) {
+		const float * a = probes + i * 4;
+		float * o = out + i * 16;
+		LightPick light = pick_light(s, make_float2(a[0], a[1]), make_float2(a[2], a[3]));
+		int entry = binary_search(s.light_mesh_cumulative_probability, 0, s.light_mesh_count - 1, a[0]);   // (sample_light's first search again)
+		int32_t ids[4] = { entry, light.transform_id, light.triangle_id, 0 };
+		memcpy(o, ids, 16);
+		o[4] = light.point.x; o[5] = light.point.y; o[6] = light.point.z;
+		o[7] = light.geometric_normal.x; o[8] = light.geometric_normal.y; o[9] = light.geometric_normal.z;
+		o[10] = light.emission.x; o[11] = light.emission.y; o[12] = light.emission.z;
+		o[13] = o[14] = o[15] = 0.0f;
+	}
+	return 0;
 }
 
 void oracle_random(const oracle_scene * scene, int dimension, const uint32_t * pixel_indices, size_t count,
