@@ -70,8 +70,8 @@ def device_lib():
         if not os.path.exists(DEVICE_LIB_PATH):
             raise DeviceLibraryMissing("%s is missing -- run `python __graft_entry__.py` (build()) first" % DEVICE_LIB_PATH)
         lib = ctypes.CDLL(DEVICE_LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        if hasattr(lib, "rt_abi_version") and lib.rt_abi_version() != 15:
-            raise DeviceLibraryMissing("%s has ABI version %d, this front end was written for 15 -- rebuild (python __graft_entry__.py)" % (DEVICE_LIB_PATH, lib.rt_abi_version()))
+        if hasattr(lib, "rt_abi_version") and lib.rt_abi_version() != 16:
+            raise DeviceLibraryMissing("%s has ABI version %d, this front end was written for 16 -- rebuild (python __graft_entry__.py)" % (DEVICE_LIB_PATH, lib.rt_abi_version()))
         lib.rt_last_error.restype = c_char_p
         lib.rt_last_error.argtypes = [c_void_p]
         lib.rt_version.restype = c_char_p
@@ -91,10 +91,17 @@ def device_lib():
         lib.rt_bsdf_eval.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p]
         lib.rt_bsdf_sample.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p]
         lib.rt_sample_lights.argtypes = [c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+        lib.rt_sort_rays.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_uint32] + [c_void_p] * 9
         lib.rt_upload_lights.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_float]
         lib.rt_upload_material_normal_maps.argtypes = [c_void_p, c_void_p, c_size_t]
         lib.rt_perturb_normals.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p]
         lib.rt_set_sky_sampling.argtypes = [c_void_p, c_float]
+        lib.rt_set_sky.argtypes = [c_void_p, c_void_p, c_int, c_int, c_float]
+        lib.rt_upload_media.argtypes = [c_void_p, c_void_p, c_size_t]
+        lib.rt_upload_instances.argtypes = [c_void_p] + [c_void_p] * 5 + [c_size_t]
+        lib.rt_upload_materials.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t]
+        lib.rt_set_pixel_query.argtypes = [c_void_p, c_int]
+        lib.rt_set_svgf_matrices.argtypes = [c_void_p, c_void_p, c_void_p]
         lib.rt_get_sky_sampling.argtypes = [c_void_p, POINTER(c_float)]
         lib.rt_measure_stream_bandwidth.argtypes = [c_void_p, c_size_t, c_int, POINTER(c_float)]
         lib.rt_set_profiling.argtypes = [c_void_p, c_int]
@@ -969,6 +976,47 @@ def bsdf_sample(ctx, material_type, probes):
     """rt_bsdf_sample: the same BSDF's sample on (N, 24) probe records. Returns (N, 12) float32 {ok, pdf, throughput factor[3],
     direction[3], medium, allow_nee, omega_i.z, pad}."""
     return _bsdf_probe(ctx, device_lib().rt_bsdf_sample, material_type, probes)
+
+SORT_TRACE_WORDS, SORT_MATERIAL_WORDS = 20, 16   # RT_SORT_TRACE_WORDS, RT_SORT_MATERIAL_WORDS
+STREAM_SUBMISSIONS, STAT_KINDS, MAX_BOUNCES = 128, 6, 128
+
+
+class SortResult:
+    """What one sort launch left behind (rt_sort_rays): trace_out (capacity, 20) and material_out (4, capacity, 16) uint32 records read
+    back to their capacity, counters int32[6] {diffuse, plastic, dielectric, conductor, next trace, this trace}, aov (4, P, 4) float32
+    (RADIANCE, DIRECT, INDIRECT, ALBEDO), gbuffer_normal_and_depth (P, 4), gbuffer_ids (P, 2) int32, gbuffer_screen_prev (P, 2),
+    pixel_query int32[2], stats (128, 6, 128) int32 (merged form, else None)."""
+
+
+def sort_rays(ctx, trace_in, frame_pixels, frame_slots, bounce=None, sample_index=0, iteration=None, slot_table=None, submission_birth=None,
+              capacity=None, sentinel=0xFFC0DE42, aov=None, gbuffer_normal_and_depth=None, gbuffer_ids=None, gbuffer_screen_prev=None, pixel_query=None):
+    """rt_sort_rays: the production sort launch on explicit entries. trace_in: (N, 20) uint32 records. Per-bounce form: bounce and
+    sample_index; merged form: iteration, slot_table (S, 4) int32 and submission_birth int32[128]. The frames hold frame_slots *
+    frame_pixels pixels; aov / g-buffers / pixel_query are their contents before the launch (zeros / the sentinel when None)."""
+    t = np.ascontiguousarray(trace_in, np.uint32).reshape(-1, SORT_TRACE_WORDS)
+    n = t.shape[0]
+    merged = iteration is not None
+    capacity = max(n, 1) if capacity is None else int(capacity)
+    pixels = int(frame_pixels) * int(frame_slots)
+    r = SortResult()
+    r.trace_out = np.zeros((capacity, SORT_TRACE_WORDS), np.uint32)
+    r.material_out = np.zeros((4, capacity, SORT_MATERIAL_WORDS), np.uint32)
+    r.counters = np.zeros(6, np.int32)
+    r.aov = np.zeros((4, pixels, 4), np.float32) if aov is None else np.array(aov, np.float32, order="C", copy=True).reshape(4, pixels, 4)
+    r.gbuffer_normal_and_depth = np.zeros((pixels, 4), np.float32) if gbuffer_normal_and_depth is None else np.array(gbuffer_normal_and_depth, np.float32, order="C", copy=True).reshape(pixels, 4)
+    r.gbuffer_ids = np.zeros((pixels, 2), np.int32) if gbuffer_ids is None else np.array(gbuffer_ids, np.int32, order="C", copy=True).reshape(pixels, 2)
+    r.gbuffer_screen_prev = np.zeros((pixels, 2), np.float32) if gbuffer_screen_prev is None else np.array(gbuffer_screen_prev, np.float32, order="C", copy=True).reshape(pixels, 2)
+    r.pixel_query = np.full(2, sentinel, np.uint32).view(np.int32) if pixel_query is None else np.array(pixel_query, np.int32, copy=True).reshape(2)
+    r.stats = np.zeros((STREAM_SUBMISSIONS, STAT_KINDS, MAX_BOUNCES), np.int32) if merged else None
+    if merged:
+        slots = np.ascontiguousarray(slot_table, np.int32).reshape(-1, 4)
+        births = np.ascontiguousarray(submission_birth, np.int32).reshape(STREAM_SUBMISSIONS)
+    _dev_check(ctx, device_lib().rt_sort_rays(ctx, 1 if merged else 0, int(iteration if merged else bounce), int(sample_index), t.ctypes.data if n else None, n,
+                                              slots.ctypes.data if merged else None, slots.shape[0] if merged else 0, births.ctypes.data if merged else None,
+                                              capacity, int(frame_slots), int(sentinel), r.trace_out.ctypes.data, r.material_out.ctypes.data, r.counters.ctypes.data,
+                                              r.aov.ctypes.data, r.gbuffer_normal_and_depth.ctypes.data, r.gbuffer_ids.ctypes.data, r.gbuffer_screen_prev.ctypes.data,
+                                              r.pixel_query.ctypes.data, r.stats.ctypes.data if merged else None))
+    return r
 
 
 LIGHT_SAMPLE_OUT = 16   # floats per output record of rt_sample_lights

@@ -223,6 +223,7 @@ struct rt_context {
 	int * device_tlas_order = nullptr, * device_tlas_node_count = nullptr; // current TLAS built by rt_build_tlas (else null)
 	hipEvent_t ev_scene = nullptr;  // the last asynchronous scene upload on the main stream
 	void * material_types = nullptr, * materials = nullptr, * media = nullptr;
+	size_t medium_count = 0;                   // entries of rt_upload_media's table (rt_sort_rays checks medium ids against it)
 	bool has_material[4] = { false, false, false, false };
 	std::vector<uint8_t> material_type_list;   // what rt_upload_materials uploaded (rt_upload_material_normal_maps checks against it)
 	void * material_normal_maps = nullptr;     // int per material (rt_upload_material_normal_maps)
@@ -1064,6 +1065,7 @@ int rt_upload_media(rt_context * ctx, const void * media, size_t count) {
 	(void)hipSetDevice(ctx->device);
 	int s = upload(ctx, &ctx->media, media, count * 32); if (s) return s;
 	ctx->params.media = (const float4 *)ctx->media;
+	ctx->medium_count = count;
 	return RT_OK;
 }
 
@@ -3003,6 +3005,183 @@ int rt_perturb_normals(rt_context * ctx, int texture_index, const float * probes
 	RT_HIP(ctx, hipGetLastError());
 	RT_HIP(ctx, quiesce(ctx));
 	RT_HIP(ctx, hipMemcpy(out, dev_out, count * 16, hipMemcpyDeviceToHost));
+	return RT_OK;
+}
+
+// rt_sort_rays: the sort launch (rt_launch_sort or rt_launch_sort_stream, as the per-bounce loop and stream_enqueue_iteration call them) on an
+// explicit trace queue. The parameter block is the context's (ctx->params, or stream_params(ctx, iteration)) with both trace queues, the four
+// material queues, the counters (RtBufferSizes) or the control block and slot table, the AOV frames, the g-buffers and the pixel-query word
+// replaced by buffers of this call, every output array filled with the caller's sentinel. Runs on the main stream after quiesce().
+int rt_sort_rays(rt_context * ctx, int merged, int step, int sample_index, const uint32_t * trace_in, size_t count,
+                 const int32_t * slot_table, size_t slot_count, const int32_t * submission_birth,
+                 size_t capacity, size_t frame_slots, uint32_t sentinel,
+                 uint32_t * trace_out, uint32_t * material_out, int32_t * counters6,
+                 float * aov_frames, float * gbuffer_normal_and_depth, int32_t * gbuffer_mesh_id_and_triangle_id, float * gbuffer_screen_position_prev,
+                 int32_t * pixel_query2, int32_t * stats) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_sort_rays: NULL context");
+	RT_REQUIRE(ctx, merged == 0 || merged == 1, "rt_sort_rays: merged must be 0 (per-bounce launch) or 1 (merged wavefront)");
+	RT_REQUIRE(ctx, (trace_in || count == 0) && trace_out && material_out && counters6 && aov_frames && gbuffer_normal_and_depth &&
+	                gbuffer_mesh_id_and_triangle_id && gbuffer_screen_position_prev && pixel_query2, "rt_sort_rays: NULL array");
+	RT_REQUIRE(ctx, !merged || (slot_table && submission_birth && stats), "rt_sort_rays: NULL slot table, submission births or statistics (merged form)");
+	RT_REQUIRE(ctx, step >= 0 && (merged || step < RT_MAX_BOUNCES), merged ? "rt_sort_rays: negative iteration" : "rt_sort_rays: bounce outside [0, RT_MAX_BOUNCES)");
+	RT_REQUIRE(ctx, capacity >= 1 && capacity <= size_t(1) << 28, "rt_sort_rays: capacity must be in [1, 2^28]");
+	RT_REQUIRE(ctx, count <= capacity, "rt_sort_rays: more entries than the queue capacity");
+	// a bounce the path length does not reach is refused too: beyond it the per-bounce counter of the next trace queue runs into the next array of RtBufferSizes
+	RT_REQUIRE(ctx, merged || step < ctx->params.config.num_bounces, "rt_sort_rays: bounce outside [0, num_bounces)");
+	(void)hipSetDevice(ctx->device);
+	int s = check_ready(ctx, "rt_sort_rays", NEED_SCENE_JOINT | NEED_MATERIALS | NEED_RNG | NEED_SKY | NEED_FRAME); if (s) return s;
+	const size_t frame_pixels = ctx->frame_pixels;
+	RT_REQUIRE(ctx, frame_slots >= 1 && frame_slots <= size_t(RT_STREAM_SAMPLE_SLOTS) && frame_slots * frame_pixels < size_t(1) << 30,
+	           "rt_sort_rays: frame_slots must be in [1, 512] and frame_slots * frame_pixels below 2^30");
+	RT_REQUIRE(ctx, !merged || (slot_count >= 1 && slot_count <= size_t(RT_STREAM_SAMPLE_SLOTS)), "rt_sort_rays: slot_count must be in [1, 512]");
+	const size_t pixels = frame_slots * frame_pixels;
+	if (merged) for (size_t k = 0; k < slot_count; k++) {
+		const int32_t * e = slot_table + 4 * k;
+		if (e[2] < 0 || e[2] >= RT_STREAM_SUBMISSIONS) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: slot %zu: submission %d outside [0, %d)", k, e[2], RT_STREAM_SUBMISSIONS);
+		if (e[1] != submission_birth[e[2]]) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: slot %zu: birth iteration %d is not its submission's (%d)", k, e[1], submission_birth[e[2]]);
+	}
+	{	// every index the kernel forms from an entry stays inside the call's buffers and the context's tables
+		std::vector<uint8_t> seen((pixels + 7) / 8, 0);
+		for (size_t i = 0; i < count; i++) {
+			const uint32_t * r = trace_in + i * RT_SORT_TRACE_WORDS;
+			const uint32_t v = r[10] & ~RT_FLAGS_ALL;
+			if (v >= pixels) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: virtual pixel %u beyond the %zu pixels of the frames", i, v, pixels);
+			if (seen[v >> 3] & (1u << (v & 7))) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: virtual pixel %u appears twice", i, v);
+			seen[v >> 3] |= uint8_t(1u << (v & 7));
+			const int32_t mesh_id = int32_t(r[6]), triangle_id = int32_t(r[7]);
+			if (triangle_id != RT_INVALID) {
+				if (triangle_id < 0 || size_t(triangle_id) >= ctx->triangle_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: triangle id %d beyond the %zu triangles", i, triangle_id, ctx->triangle_count);
+				if (mesh_id < 0 || size_t(mesh_id) >= ctx->mesh_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: mesh id %d beyond the %zu instances", i, mesh_id, ctx->mesh_count);
+			}
+			if (r[10] & RT_FLAG_INSIDE_MEDIUM) {
+				const int32_t medium = int32_t(r[15]);
+				if (medium < 0 || size_t(medium) >= ctx->medium_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: medium id %d beyond the %zu media", i, medium, ctx->medium_count);
+			}
+			if (merged) {
+				const size_t slot = v / frame_pixels;
+				if (slot >= slot_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: slot %zu beyond the %zu slots of the table", i, slot, slot_count);
+				const int bounce = step - slot_table[4 * slot + 1];
+				if (bounce < 0 || bounce >= RT_MAX_BOUNCES || bounce >= ctx->params.config.num_bounces)
+					return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: bounce %d outside [0, min(RT_MAX_BOUNCES, num_bounces))", i, bounce);
+			}
+		}
+	}
+	RT_HIP(ctx, quiesce(ctx));
+	s = sky_sampling_prepare(ctx, "rt_sort_rays"); if (s) return s;   // (as a render settles it: it decides the instance)
+
+	TempBuffers tmp(ctx);
+	bool ok = true;
+	std::vector<uint32_t> column(std::max(capacity, size_t(1)) * 4);
+	// one component array of a queue: word `word` (`words` of them, consecutive) of `n` records of `stride` words; the rest of the array holds the sentinel
+	auto upload_column = [&](const uint32_t * records, size_t n, size_t stride, size_t word, size_t words) -> void * {
+		std::fill(column.begin(), column.begin() + capacity * words, sentinel);
+		for (size_t i = 0; i < n; i++) for (size_t w = 0; w < words; w++) column[i * words + w] = records[i * stride + word + w];
+		void * d = tmp.get(capacity * words * 4, column.data());
+		if (!d) ok = false;
+		return d;
+	};
+	auto download_column = [&](const void * device, uint32_t * records, size_t stride, size_t word, size_t words) -> bool {
+		if (hipMemcpy(column.data(), device, capacity * words * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
+		for (size_t i = 0; i < capacity; i++) for (size_t w = 0; w < words; w++) records[i * stride + word + w] = column[i * words + w];
+		return true;
+	};
+	auto vec3 = [&](const uint32_t * records, size_t n, size_t stride, size_t word) -> RtVec3SoA {
+		RtVec3SoA v; v.x = (float *)upload_column(records, n, stride, word, 1); v.y = (float *)upload_column(records, n, stride, word + 1, 1); v.z = (float *)upload_column(records, n, stride, word + 2, 1);
+		return v;
+	};
+	auto trace_buffer = [&](const uint32_t * records, size_t n) -> RtTraceBuffer {
+		const size_t W = RT_SORT_TRACE_WORDS;
+		RtTraceBuffer t = { };
+		t.origin = vec3(records, n, W, 0); t.direction = vec3(records, n, W, 3);
+		t.hits = (uint4 *)upload_column(records, n, W, 6, 4);
+		t.pixel_index_and_flags = (unsigned *)upload_column(records, n, W, 10, 1);
+		t.throughput = vec3(records, n, W, 11);
+		t.last_pdf = (float *)upload_column(records, n, W, 14, 1);
+		t.medium = (int *)upload_column(records, n, W, 15, 1);
+		t.cone_angle = (float *)upload_column(records, n, W, 16, 1); t.cone_width = (float *)upload_column(records, n, W, 17, 1);
+		return t;
+	};
+	const int q = step & 1;
+	RtTraceBuffer in = trace_buffer(trace_in, count), out = trace_buffer(nullptr, 0);
+	RtMaterialBuffer material[4];
+	for (RtMaterialBuffer & m : material) {
+		m = { };
+		m.direction = vec3(nullptr, 0, 0, 0); m.hits = (uint4 *)upload_column(nullptr, 0, 0, 0, 4);
+		m.pixel_index_and_flags = (unsigned *)upload_column(nullptr, 0, 0, 0, 1); m.throughput = vec3(nullptr, 0, 0, 0);
+		m.medium = (int *)upload_column(nullptr, 0, 0, 0, 1);
+		m.cone_angle = (float *)upload_column(nullptr, 0, 0, 0, 1); m.cone_width = (float *)upload_column(nullptr, 0, 0, 0, 1);
+	}
+	float4 * frames[4]; const int frame_aov[4] = { RT_AOV_RADIANCE, RT_AOV_RADIANCE_DIRECT, RT_AOV_RADIANCE_INDIRECT, RT_AOV_ALBEDO };
+	for (int k = 0; k < 4; k++) { frames[k] = (float4 *)tmp.get(pixels * 16, aov_frames + size_t(k) * pixels * 4); ok = ok && frames[k]; }
+	float4 * g_nd = (float4 *)tmp.get(pixels * 16, gbuffer_normal_and_depth);
+	int2 * g_id = (int2 *)tmp.get(pixels * 8, gbuffer_mesh_id_and_triangle_id);
+	float2 * g_sp = (float2 *)tmp.get(pixels * 8, gbuffer_screen_position_prev);
+	int * query = (int *)tmp.get(8, pixel_query2);
+	RtBufferSizes * sizes = nullptr; RtStreamControl * control = nullptr; RtStreamTable * table = nullptr;
+	if (merged) {
+		std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());
+		control_host->trace_count[q] = int(count);
+		control = (RtStreamControl *)tmp.get(sizeof(RtStreamControl), control_host.get());
+		std::unique_ptr<RtStreamTable> table_host(new RtStreamTable());
+		memcpy(table_host->slots, slot_table, slot_count * sizeof(RtStreamSlot));
+		memcpy(table_host->submission_birth, submission_birth, sizeof(table_host->submission_birth));
+		table = (RtStreamTable *)tmp.get(sizeof(RtStreamTable), table_host.get());
+		ok = ok && control && table;
+	} else {
+		RtBufferSizes sizes_host = { };
+		sizes_host.trace[step] = int(count);
+		sizes = (RtBufferSizes *)tmp.get(sizeof(RtBufferSizes), &sizes_host);
+		ok = ok && sizes;
+	}
+	if (!ok || !g_nd || !g_id || !g_sp || !query) return fail(ctx, RT_ERROR_HIP, "rt_sort_rays: device allocation failed");
+
+	RtParams p = merged ? stream_params(ctx, step) : ctx->params;
+	p.trace[q] = in; p.trace[q ^ 1] = out;
+	for (int m = 0; m < 4; m++) p.material[m] = material[m];
+	p.sizes = sizes; p.stream = control; p.stream_table = table;
+	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = nullptr;
+	for (int k = 0; k < 4; k++) if (ctx->aov_buffers[frame_aov[k]][0]) p.aovs[frame_aov[k]].framebuffer = frames[k];
+	p.gbuffer_normal_and_depth = g_nd; p.gbuffer_mesh_id_and_triangle_id = g_id; p.gbuffer_screen_position_prev = g_sp;
+	p.pixel_query_out = query;
+	if (merged) rt_launch_sort_stream(p, ctx->stream); else rt_launch_sort(p, step, sample_index, ctx->stream);
+	RT_HIP(ctx, hipGetLastError());
+	RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+
+	const size_t TW = RT_SORT_TRACE_WORDS, MW = RT_SORT_MATERIAL_WORDS;
+	for (size_t i = 0; i < capacity * TW; i++) trace_out[i] = sentinel;
+	for (size_t i = 0; i < 4 * capacity * MW; i++) material_out[i] = sentinel;
+	bool read = true;
+	const float * const out_vec[3][3] = { { out.origin.x, out.origin.y, out.origin.z }, { out.direction.x, out.direction.y, out.direction.z }, { out.throughput.x, out.throughput.y, out.throughput.z } };
+	const size_t out_word[3] = { 0, 3, 11 };
+	for (int v = 0; v < 3; v++) for (int c = 0; c < 3; c++) read = read && download_column(out_vec[v][c], trace_out, TW, out_word[v] + c, 1);
+	read = read && download_column(out.hits, trace_out, TW, 6, 4) && download_column(out.pixel_index_and_flags, trace_out, TW, 10, 1) && download_column(out.last_pdf, trace_out, TW, 14, 1)
+	            && download_column(out.medium, trace_out, TW, 15, 1) && download_column(out.cone_angle, trace_out, TW, 16, 1) && download_column(out.cone_width, trace_out, TW, 17, 1);
+	for (int m = 0; m < 4; m++) {
+		uint32_t * records = material_out + size_t(m) * capacity * MW;
+		const RtMaterialBuffer & b = material[m];
+		read = read && download_column(b.direction.x, records, MW, 0, 1) && download_column(b.direction.y, records, MW, 1, 1) && download_column(b.direction.z, records, MW, 2, 1)
+		            && download_column(b.hits, records, MW, 3, 4) && download_column(b.pixel_index_and_flags, records, MW, 7, 1)
+		            && download_column(b.throughput.x, records, MW, 8, 1) && download_column(b.throughput.y, records, MW, 9, 1) && download_column(b.throughput.z, records, MW, 10, 1)
+		            && download_column(b.medium, records, MW, 11, 1) && download_column(b.cone_angle, records, MW, 12, 1) && download_column(b.cone_width, records, MW, 13, 1);
+	}
+	if (!read) return fail(ctx, RT_ERROR_HIP, "rt_sort_rays: reading the queues back failed");
+	if (merged) {
+		std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());
+		RT_HIP(ctx, hipMemcpy(control_host.get(), control, sizeof(RtStreamControl), hipMemcpyDeviceToHost));
+		for (int m = 0; m < 4; m++) counters6[m] = control_host->material_count[m];
+		counters6[4] = control_host->trace_count[q ^ 1]; counters6[5] = control_host->trace_count[q];
+		memcpy(stats, control_host->stats, sizeof(control_host->stats));
+	} else {
+		RtBufferSizes sizes_host;
+		RT_HIP(ctx, hipMemcpy(&sizes_host, sizes, sizeof(RtBufferSizes), hipMemcpyDeviceToHost));
+		counters6[0] = sizes_host.diffuse[step]; counters6[1] = sizes_host.plastic[step]; counters6[2] = sizes_host.dielectric[step]; counters6[3] = sizes_host.conductor[step];
+		counters6[4] = step + 1 < RT_MAX_BOUNCES ? sizes_host.trace[step + 1] : 0; counters6[5] = sizes_host.trace[step];
+	}
+	for (int k = 0; k < 4; k++) RT_HIP(ctx, hipMemcpy(aov_frames + size_t(k) * pixels * 4, frames[k], pixels * 16, hipMemcpyDeviceToHost));
+	RT_HIP(ctx, hipMemcpy(gbuffer_normal_and_depth, g_nd, pixels * 16, hipMemcpyDeviceToHost));
+	RT_HIP(ctx, hipMemcpy(gbuffer_mesh_id_and_triangle_id, g_id, pixels * 8, hipMemcpyDeviceToHost));
+	RT_HIP(ctx, hipMemcpy(gbuffer_screen_position_prev, g_sp, pixels * 8, hipMemcpyDeviceToHost));
+	RT_HIP(ctx, hipMemcpy(pixel_query2, query, 8, hipMemcpyDeviceToHost));
 	return RT_OK;
 }
 

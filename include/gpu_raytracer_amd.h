@@ -154,8 +154,9 @@ const char * rt_version(void);
  *  13  rt_trace_stream_rays (additions only)
  *  14  rt_upload_material_normal_maps, rt_perturb_normals (additions only; tangent-space normal maps)
  *  15  rt_sample_lights (addition); rt_upload_lights refuses tables on which the light search would not end (see there)
+ *  16  rt_sort_rays (addition)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
-#define RT_ABI_VERSION 15
+#define RT_ABI_VERSION 16
 int rt_abi_version(void);
 
 /* ---- scene upload ------------------------------------------------------------------- */
@@ -602,6 +603,37 @@ int rt_sample_lights(rt_context * ctx, const float * probes, size_t count, int u
  * from, after the view guard), 1 if the hit fell back to the interpolated normal else 0}.                                 */
 #define RT_NORMAL_PROBE_IN 48
 int rt_perturb_normals(rt_context * ctx, int texture_index, const float * probes, size_t count, float * out);
+/* The sort launch on an explicit trace queue (synchronous): the production launcher -- the per-bounce one (merged = 0: `step` is the
+ * bounce, sample_index the launch's) or the merged wavefront's (merged = 1: `step` is the iteration; bounce and sample of an entry come
+ * out of slot_table / submission_birth) -- so the instance (plain or _sky) and the grid are the shipped ones, on the context's own
+ * parameter block with the queues, the counters / control block, the slot table, the four AOV frames the launch touches, the g-buffers
+ * and the pixel-query word replaced by buffers of this call. Nothing of the context changes but what a render would settle (the sky
+ * tables when sky sampling is wanted).
+ * Records are 32-bit words. trace_in: count x RT_SORT_TRACE_WORDS {origin[3], direction[3], hit[4] (as rt_trace_rays), pixel_index_and_flags,
+ * throughput[3], last_pdf, medium, cone_angle, cone_width, pad[2]}. The pixel is a VIRTUAL pixel v = slot * frame_pixels + pixel
+ * (frame_pixels = rt_screen_pitch x height) with slot < frame_slots <= 512; the frames below hold frame_slots * frame_pixels pixels.
+ * slot_table (merged): slot_count x 4 ints {sample_index, birth_iteration, submission, index_in_submission}; submission_birth: 128 ints.
+ * trace_out: capacity x RT_SORT_TRACE_WORDS (the next trace queue) and material_out: 4 x capacity x RT_SORT_MATERIAL_WORDS {direction[3],
+ * hit[4], pixel_index_and_flags, throughput[3], medium, cone_angle, cone_width, pad[2]} (diffuse, plastic, dielectric, conductor): every
+ * device array is filled with `sentinel` first and read back to its capacity, so a word the launch did not write holds the sentinel.
+ * counters6: {diffuse, plastic, dielectric, conductor, next trace queue, this trace queue} after the launch. aov_frames (in / out):
+ * 4 x frame_slots * frame_pixels x 4 floats, RT_AOV_RADIANCE, _DIRECT, _INDIRECT, _ALBEDO; a frame the context has disabled is not
+ * given to the kernel. gbuffer_* (in / out): 4 floats, 2 ints, 2 floats per pixel. pixel_query2 (in / out): what the launch answers
+ * for the pixel of rt_set_pixel_query. stats (merged; out): 128 x 6 x RT_MAX_BOUNCES ints, rays per (submission, queue kind, bounce).
+ * RT_ERROR_INVALID_ARG with a message, before anything is launched, for whatever could make the kernel read or write outside these
+ * buffers or the context's tables: NULL arrays, count > capacity, a bounce outside [0, RT_MAX_BOUNCES) or not below num_bounces, a virtual pixel beyond the frames,
+ * two entries with one virtual pixel (the AOV updates are plain read-modify-writes: one path per pixel and launch), a mesh id beyond
+ * the instance table, a triangle id beyond the triangle array (other than RT_INVALID), a medium id beyond rt_upload_media's table on
+ * an entry flagged inside a medium, a slot beyond the table, a submission beyond 128, an entry's bounce outside [0, min(RT_MAX_BOUNCES, num_bounces))
+ * or a slot whose birth is not its submission's.                                                                              */
+#define RT_SORT_TRACE_WORDS    20
+#define RT_SORT_MATERIAL_WORDS 16
+int rt_sort_rays(rt_context * ctx, int merged, int step, int sample_index, const uint32_t * trace_in, size_t count,
+                 const int32_t * slot_table, size_t slot_count, const int32_t * submission_birth,
+                 size_t capacity, size_t frame_slots, uint32_t sentinel,
+                 uint32_t * trace_out, uint32_t * material_out, int32_t * counters6,
+                 float * aov_frames, float * gbuffer_normal_and_depth, int32_t * gbuffer_mesh_id_and_triangle_id, float * gbuffer_screen_position_prev,
+                 int32_t * pixel_query2, int32_t * stats);
 /* Streaming-read bandwidth probe used as the measured HBM roofline (GB/s).                 */
 int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps);
 

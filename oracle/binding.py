@@ -114,6 +114,7 @@ def lib():
         l.oracle_bsdf_eval.argtypes = [POINTER(OracleScene), c_int, c_void_p, c_size_t, c_void_p]
         l.oracle_bsdf_sample.argtypes = [POINTER(OracleScene), c_int, c_void_p, c_size_t, c_void_p]
         l.oracle_sample_lights.argtypes = [POINTER(OracleScene), c_void_p, c_size_t, c_void_p]
+        l.oracle_sort.argtypes = [POINTER(OracleScene), POINTER(OracleFrame), c_int, c_int, c_void_p, c_size_t, c_uint32, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_float, c_void_p, c_void_p]
         l.oracle_average_conductor.argtypes = [c_void_p, c_void_p]
         tex_p = POINTER(OracleTexture)
         l.oracle_tex2d.argtypes = [tex_p, c_float, c_float, c_void_p]
@@ -736,6 +737,33 @@ class SceneView:
         if status != 0:
             raise ValueError("oracle_sample_lights: %s" % {-1: "the scene has no light tables", -2: "a random number outside [0, 1)"}.get(status, status))
         return out
+
+    def sort(self, trace_in, bounce, sample_index, aov, gbuffer_normal_and_depth, gbuffer_ids, gbuffer_screen_prev, sentinel=0xFFC0DE42,
+             aov_enabled=(True, True, True, True), pixel_query_pixel=-1, pixel_query=None, sky_share=0.0, sky_cell_pdf=None):
+        """oracle_sort: kernel_sort on (N, 20) uint32 records of ONE sample (pixels of one frame) at one bounce. aov (4, P, 4) float32
+        {RADIANCE, DIRECT, INDIRECT, ALBEDO}, the g-buffers (P, 4) / (P, 2) int32 / (P, 2) and pixel_query int32[2] are updated IN PLACE
+        (P = pitch * height; they must be C-contiguous arrays of those types). Returns (trace_out (N, 20), material_out (4, N, 16), counts int32[5], internals
+        (N, 8) float32: the intermediates of oracle.h, NaN where an entry computes none)."""
+        t = np.ascontiguousarray(trace_in, np.uint32).reshape(-1, 20)
+        n = t.shape[0]
+        f = OracleFrame()
+        for k in range(4):
+            assert aov[k].flags.c_contiguous and aov[k].dtype == np.float32
+            if aov_enabled[k]:
+                f.framebuffer[k] = aov[k].ctypes.data
+        for a, dtype in ((gbuffer_normal_and_depth, np.float32), (gbuffer_ids, np.int32), (gbuffer_screen_prev, np.float32)):
+            assert a.flags.c_contiguous and a.dtype == dtype
+        f.gbuffer_normal_and_depth = gbuffer_normal_and_depth.ctypes.data; f.gbuffer_mesh_id_and_triangle_id = gbuffer_ids.ctypes.data
+        f.gbuffer_screen_position_prev = gbuffer_screen_prev.ctypes.data
+        trace_out = np.zeros((n, 20), np.uint32); material_out = np.zeros((4, n, 16), np.uint32); counts = np.zeros(5, np.int32)
+        table = None if sky_cell_pdf is None else np.ascontiguousarray(sky_cell_pdf, np.float32)
+        internals = np.full((n, 8), np.nan, np.float32)   # what an entry does not compute stays NaN
+        status = lib().oracle_sort(byref(self.scene), byref(f), int(bounce), int(sample_index), t.ctypes.data if n else None, n, int(sentinel),
+                                   trace_out.ctypes.data, material_out.ctypes.data, counts.ctypes.data, int(pixel_query_pixel),
+                                   None if pixel_query is None else pixel_query.ctypes.data, float(sky_share), None if table is None else table.ctypes.data, internals.ctypes.data)
+        if status != 0:
+            raise ValueError("oracle_sort: status %d" % status)
+        return trace_out, material_out, counts, internals
 
     def random(self, dimension, pixel_indices, bounce, sample_index):
         px = np.ascontiguousarray(pixel_indices, np.uint32)

@@ -176,6 +176,18 @@ int oracle_bsdf_sample(const oracle_scene * scene, int material_type, const floa
  * u_triangle, u_1, u_2}, 16 out {light-mesh entry, transform id, triangle index, 0 (int32 bits), point[3], geometric normal[3],
  * emission[3], pad[3]}. -1: the scene has no light tables; -2: a random number outside [0, 1). */
 int oracle_sample_lights(const oracle_scene * scene, const float * probes, size_t count, float * out);
+/* kernel_sort (Pathtracer.cu:220-463) on the records of rt_sort_rays (include/gpu_raytracer_amd.h: 20 words per trace entry, 16 per material
+ * entry), at one bounce of one sample: the pixel of an entry is a pixel of `frame` (the caller splits a launch over several sample slots into one call
+ * per slot). One chunk, so queue order = input order. trace_out: count x 20, material_out: 4 x count x 16 words, `sentinel` wherever the kernel stores
+ * nothing; counts5: {diffuse, plastic, dielectric, conductor, next trace queue}. pixel_query2: NULL, or what the launch answers for pixel_query_pixel.
+ * This entry alone knows the sky importance sampling of the device (no counterpart in the reference): sky_share in (0, 1] and the table of cell pdfs
+ * (sky_height x sky_width) restate the two places sort_rays<*, true> differs; 0 / NULL: the reference's estimator.
+ * internals: NULL, or count x 8 floats, pre-filled by the caller, into which an entry writes the float32 intermediates its decisions compare, where it computes
+ * them: {scatter_distance, rand_scatter.x * throughput_sum, survival_probability, light_pdf, MIS weight (emitter or sky), sky u, sky v, cos_theta_light}.
+ * -1: bad argument, -2 / -3 / -4: an entry's pixel / hit ids / medium id outside the frame / the scene's tables. */
+int oracle_sort(const oracle_scene * scene, oracle_frame * frame, int bounce, int sample_index, const uint32_t * trace_in, size_t count, uint32_t sentinel,
+                uint32_t * trace_out, uint32_t * material_out, int32_t * counts5, int pixel_query_pixel, int32_t * pixel_query2,
+                float sky_share, const float * sky_cell_pdf, float * internals);
 /* Pathtracer::render for one sample over pixels [pixel_offset, pixel_offset+pixel_count)
  * (Pathtracer.cpp:738-855): batches, bounces, accumulate or SVGF/TAA. */
 void oracle_render_sample(const oracle_scene * scene, oracle_frame * frame, int sample_index,

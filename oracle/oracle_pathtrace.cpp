@@ -9,6 +9,7 @@
 #include "oracle.h"
 #include "oracle_shading.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -572,7 +573,7 @@ inline void camera_generate_ray(Context & c, int pixel_index, int sample_index, 
 }
 
 // Pathtracer.cu:199-218
-inline bool russian_roulette(Context & c, int pixel_index, int bounce, int sample_index, float3 & throughput) {
+inline bool russian_roulette(Context & c, int pixel_index, int bounce, int sample_index, float3 & throughput, float * survival_out = nullptr) {
 	const rt_gpu_config & cfg = c.s.config;
 	if (bounce == cfg.num_bounces - 1) return true;
 	if (cfg.enable_russian_roulette && bounce > 0) {
@@ -580,6 +581,7 @@ inline bool russian_roulette(Context & c, int pixel_index, int bounce, int sampl
 		if (cfg.enable_svgf) t *= make_float3(c.aov_get(RT_AOV_ALBEDO, pixel_index));
 		float survival_probability = saturate(fmaxf(fmaxf(t.x, t.y), t.z));
 		float r = c.random(DIM_RUSSIAN_ROULETTE, pixel_index, bounce, sample_index).x;
+		if (survival_out) *survival_out = survival_probability;
 		if (r > survival_probability) return true;
 		throughput /= survival_probability;
 	}
@@ -601,14 +603,38 @@ inline void add_radiance(Context & c, int bounce, int pixel_index, float3 illumi
 	}
 }
 
+// What oracle_sort adds to kernel_sort, and oracle_render_sample never uses: the pixel query (Pathtracer.cu:345-348), and the two places where the
+// device's sort_rays<*, true> (sky importance sampling, no counterpart in the reference) differs -- restated from kernels_shade.hip / rt_shading.h.
+struct SortExtras {
+	int pixel_query_pixel; int32_t * pixel_query_out;   // RT_INVALID / null: no query
+	float sky_share; const float * sky_cell_pdf;        // 0: the reference's estimator
+	// null, or 8 floats per entry that receive the float32 intermediates the kernel's decisions compare (the caller pre-fills them; an entry writes only what it
+	// computes): scatter_distance, rand_scatter.x * throughput_sum, survival_probability, light_pdf, MIS weight (emitter or sky), sky u, sky v, cos_theta_light
+	float * internals;
+};
+// sky_cell / sky_pdf (rt_shading.h): the cell sample_sky's (u, v) of the direction falls in, and the table's value for it
+inline float sky_pdf(const oracle_scene & s, const float * cell_pdf, float3 direction, float * uv_out) {
+	float phi   = atan2f(-direction.z, direction.x);
+	float theta = acosf(clampf(direction.y, -1.0f, 1.0f));
+	float u = phi   * O_ONE_OVER_TWO_PI + 0.5f;
+	float v = theta * O_ONE_OVER_PI;
+	uv_out[0] = u; uv_out[1] = v;
+	int column = std::min(std::max(int(u * float(s.sky_width)),  0), s.sky_width  - 1);
+	int row    = std::min(std::max(int(v * float(s.sky_height)), 0), s.sky_height - 1);
+	return cell_pdf[column + row * s.sky_width];
+}
+
 // kernel_sort, Pathtracer.cu:220-463
-void kernel_sort(Context & c, const std::vector<TraceRay> & in, size_t begin, size_t end, Wavefront & w, int bounce, int sample_index) {
+void kernel_sort(Context & c, const std::vector<TraceRay> & in, size_t begin, size_t end, Wavefront & w, int bounce, int sample_index, const SortExtras * extras = nullptr) {
 	const oracle_scene & s = c.s;
+	const bool sky_sampling = extras && extras->sky_share > 0.0f;
 	const rt_gpu_config & cfg = s.config;
 	std::vector<TraceRay> & out = w.trace[(bounce + 1) & 1];
 
+	float unused_internals[8];
 	for (size_t index = begin; index < end; index++) {
 		const TraceRay & r = in[index];
+		float * internals = extras && extras->internals ? extras->internals + index * 8 : unused_internals;
 		float3 ray_direction = r.direction;
 		RayHit hit = unpack_hit(r.hit);
 
@@ -645,11 +671,12 @@ void kernel_sort(Context & c, const std::vector<TraceRay> & in, size_t begin, si
 
 				float scatter_distance = sample_exp(sigma_t_used, rand_scatter.y);
 				float3 transmittance = beer_lambert(sigma_t, fminf(scatter_distance, hit.t));
+				internals[0] = scatter_distance; internals[1] = rand_scatter.x * throughput_sum;
 
 				if (scatter_distance < hit.t) {
 					float3 pdf = wavelength_pdf * sigma_t * transmittance;
 					throughput *= medium.sigma_s * transmittance / (pdf.x + pdf.y + pdf.z);
-					if (russian_roulette(c, pixel_index, bounce, sample_index, throughput)) continue;
+					if (russian_roulette(c, pixel_index, bounce, sample_index, throughput, internals + 2)) continue;
 
 					float3 direction_out = sample_henyey_greenstein(-ray_direction, medium.g, rand_phase.x, rand_phase.y);
 					float3 origin_out = r.origin + scatter_distance * ray_direction;
@@ -675,8 +702,19 @@ void kernel_sort(Context & c, const std::vector<TraceRay> & in, size_t begin, si
 
 		if (hit.triangle_id == RT_INVALID) { // miss: sky
 			float3 illumination = throughput * sample_sky(s, ray_direction);
+			if (sky_sampling && allow_nee) {   // sort_rays<*, true>: the light samples reach the sky too
+				if (!cfg.enable_multiple_importance_sampling) continue;
+				float weight = power_heuristic(r.last_pdf, extras->sky_share * sky_pdf(s, extras->sky_cell_pdf, ray_direction, internals + 5));
+				internals[4] = weight;
+				illumination *= weight;
+			}
 			add_radiance(c, bounce, pixel_index, illumination, illumination);
 			continue;
+		}
+
+		if (extras && extras->pixel_query_out && bounce == 0 && extras->pixel_query_pixel == pixel_index) { // Pathtracer.cu:345-348
+			extras->pixel_query_out[0] = hit.mesh_id;
+			extras->pixel_query_out[1] = hit.triangle_id;
 		}
 
 		int material_id = s.mesh_material_ids[hit.mesh_id];
@@ -701,6 +739,7 @@ void kernel_sort(Context & c, const std::vector<TraceRay> & in, size_t begin, si
 			float3 emission = make_float3(lm[0], lm[1], lm[2]);
 
 			bool count_light = cfg.enable_next_event_estimation ? !allow_nee : true;
+			if (sky_sampling && extras->sky_share >= 1.0f) count_light = true;   // sort_rays<*, true>: every light sample goes to the sky
 			if (count_light) {
 				add_radiance(c, bounce, pixel_index, throughput * emission, emission);
 				continue;
@@ -711,8 +750,11 @@ void kernel_sort(Context & c, const std::vector<TraceRay> & in, size_t begin, si
 				float brdf_pdf = r.last_pdf;
 				float light_power = luminance(emission.x, emission.y, emission.z);
 				float light_pdf = light_power * distance_to_light_squared / (cos_theta_light * s.lights_total_weight);
+				if (sky_sampling) light_pdf *= 1.0f - extras->sky_share;   // sort_rays<*, true>
+				internals[3] = light_pdf; internals[7] = cos_theta_light;
 				if (!pdf_is_valid(light_pdf)) continue;
 				float mis_weight = power_heuristic(brdf_pdf, light_pdf);
+				internals[4] = mis_weight;
 				float3 illumination = throughput * emission * mis_weight;
 				c.aov_add(RT_AOV_RADIANCE, pixel_index, make_float4(illumination));
 				if (bounce == 1) c.aov_add(RT_AOV_RADIANCE_DIRECT,   pixel_index, make_float4(illumination));
@@ -721,7 +763,7 @@ void kernel_sort(Context & c, const std::vector<TraceRay> & in, size_t begin, si
 			continue;
 		}
 
-		if (russian_roulette(c, pixel_index, bounce, sample_index, throughput)) continue;
+		if (russian_roulette(c, pixel_index, bounce, sample_index, throughput, internals + 2)) continue;
 
 		MaterialRay m = { };
 		m.direction = ray_direction;
@@ -1004,6 +1046,58 @@ int oracle_sample_lights(const oracle_scene * scene, const float * probes, size_
 		o[10] = light.emission.x; o[11] = light.emission.y; o[12] = light.emission.z;
 		o[13] = o[14] = o[15] = 0.0f;
 	}
+	return 0;
+}
+
+// oracle_sort: kernel_sort on the records of rt_sort_rays, one chunk, queue order = input order. What a queue entry holds where the kernel
+// stores nothing (Pathtracer.cu:446-461: the medium of an entry outside a medium, the cone of bounce 0 or without mip-mapping, the throughput
+// of bounce 0; the hit and last_pdf of a continuation ray) is the caller's sentinel, as on the device.
+int oracle_sort(const oracle_scene * scene, oracle_frame * frame, int bounce, int sample_index, const uint32_t * trace_in, size_t count, uint32_t sentinel,
+                uint32_t * trace_out, uint32_t * material_out, int32_t * counts5, int pixel_query_pixel, int32_t * pixel_query2,
+                float sky_share, const float * sky_cell_pdf, float * internals) {
+	const oracle_scene & s = *scene;
+	if (bounce < 0 || bounce >= RT_MAX_BOUNCES || !frame || !counts5 || (count && (!trace_in || !trace_out || !material_out))) return -1;
+	if (sky_share < 0.0f || sky_share > 1.0f || (sky_share > 0.0f && !sky_cell_pdf)) return -1;
+	const size_t pixels = size_t(s.screen_pitch) * size_t(s.screen_height);
+	std::vector<TraceRay> in(count);
+	for (size_t i = 0; i < count; i++) {
+		const uint32_t * r = trace_in + i * 20;
+		TraceRay & t = in[i];
+		if ((r[10] & ~FLAGS_ALL) >= pixels) return -2;
+		if (int32_t(r[7]) != RT_INVALID && (int32_t(r[7]) < 0 || int32_t(r[7]) >= s.triangle_count || int32_t(r[6]) < 0 || int32_t(r[6]) >= s.mesh_count)) return -3;
+		if ((r[10] & FLAG_INSIDE_MEDIUM) && (int32_t(r[15]) < 0 || int32_t(r[15]) >= s.medium_count)) return -4;
+		t.origin = make_float3(uint_as_float(r[0]), uint_as_float(r[1]), uint_as_float(r[2]));
+		t.direction = make_float3(uint_as_float(r[3]), uint_as_float(r[4]), uint_as_float(r[5]));
+		memcpy(t.hit, r + 6, 16);
+		t.pixel_index_and_flags = r[10];
+		t.throughput = make_float3(uint_as_float(r[11]), uint_as_float(r[12]), uint_as_float(r[13]));
+		t.last_pdf = uint_as_float(r[14]); t.medium = int32_t(r[15]); t.cone_angle = uint_as_float(r[16]); t.cone_width = uint_as_float(r[17]);
+	}
+	Context c(s, *frame);
+	Wavefront w;
+	SortExtras extras = { pixel_query2 ? pixel_query_pixel : RT_INVALID, pixel_query2, sky_share, sky_cell_pdf, internals };
+	kernel_sort(c, in, 0, count, w, bounce, sample_index, &extras);
+
+	for (size_t i = 0; i < count * 20; i++) trace_out[i] = sentinel;
+	for (size_t i = 0; i < 4 * count * 16; i++) material_out[i] = sentinel;
+	const bool cones = s.config.enable_mipmapping != 0;
+	auto put3 = [](uint32_t * o, float3 v) { o[0] = float_as_uint(v.x); o[1] = float_as_uint(v.y); o[2] = float_as_uint(v.z); };
+	const std::vector<TraceRay> & next = w.trace[(bounce + 1) & 1];
+	for (size_t i = 0; i < next.size(); i++) {
+		uint32_t * o = trace_out + i * 20; const TraceRay & t = next[i];
+		put3(o, t.origin); put3(o + 3, t.direction); o[10] = t.pixel_index_and_flags; put3(o + 11, t.throughput);
+		o[15] = uint32_t(t.medium);
+		if (cones) { o[16] = float_as_uint(t.cone_angle); o[17] = float_as_uint(t.cone_width); }
+	}
+	for (int m = 0; m < 4; m++) for (size_t i = 0; i < w.material[m].size(); i++) {
+		uint32_t * o = material_out + (size_t(m) * count + i) * 16; const MaterialRay & t = w.material[m][i];
+		put3(o, t.direction); memcpy(o + 3, t.hit, 16); o[7] = t.pixel_index_and_flags;
+		if (bounce > 0) put3(o + 8, t.throughput);
+		if (t.medium != RT_INVALID) o[11] = uint32_t(t.medium);
+		if (bounce > 0 && cones) { o[12] = float_as_uint(t.cone_angle); o[13] = float_as_uint(t.cone_width); }
+	}
+	for (int m = 0; m < 4; m++) counts5[m] = int32_t(w.material[m].size());
+	counts5[4] = int32_t(next.size());
 	return 0;
 }
 
