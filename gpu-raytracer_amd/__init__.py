@@ -70,8 +70,8 @@ def device_lib():
         if not os.path.exists(DEVICE_LIB_PATH):
             raise DeviceLibraryMissing("%s is missing -- run `python __graft_entry__.py` (build()) first" % DEVICE_LIB_PATH)
         lib = ctypes.CDLL(DEVICE_LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        if hasattr(lib, "rt_abi_version") and lib.rt_abi_version() != 16:
-            raise DeviceLibraryMissing("%s has ABI version %d, this front end was written for 16 -- rebuild (python __graft_entry__.py)" % (DEVICE_LIB_PATH, lib.rt_abi_version()))
+        if hasattr(lib, "rt_abi_version") and lib.rt_abi_version() != 17:
+            raise DeviceLibraryMissing("%s has ABI version %d, this front end was written for 17 -- rebuild (python __graft_entry__.py)" % (DEVICE_LIB_PATH, lib.rt_abi_version()))
         lib.rt_last_error.restype = c_char_p
         lib.rt_last_error.argtypes = [c_void_p]
         lib.rt_version.restype = c_char_p
@@ -94,6 +94,9 @@ def device_lib():
         lib.rt_sort_rays.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_uint32] + [c_void_p] * 9
         lib.rt_upload_lights.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_float]
         lib.rt_upload_material_normal_maps.argtypes = [c_void_p, c_void_p, c_size_t]
+        lib.rt_set_bvh_type.argtypes = [c_void_p, c_int]
+        lib.rt_upload_material_opacity.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]
+        lib.rt_read_material_opacity.argtypes = [c_void_p, c_int, c_void_p, c_size_t, POINTER(c_int), POINTER(c_int)]
         lib.rt_perturb_normals.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p]
         lib.rt_set_sky_sampling.argtypes = [c_void_p, c_float]
         lib.rt_set_sky.argtypes = [c_void_p, c_void_p, c_int, c_int, c_float]
@@ -149,6 +152,8 @@ def host_lib():
         lib.grt_scene_material_type.argtypes = [c_void_p, c_int]
         lib.grt_scene_material_normal_map.argtypes = [c_void_p, c_int]
         lib.grt_scene_set_material_normal_map.argtypes = [c_void_p, c_int, c_int]
+        lib.grt_scene_material_opacity_map.argtypes = [c_void_p, c_int, POINTER(c_int), POINTER(c_float)]
+        lib.grt_scene_set_material_opacity_map.argtypes = [c_void_p, c_int, c_int, c_int, c_float]
         lib.grt_scene_add_texture.argtypes = [c_void_p, c_char_p, c_int]
         lib.grt_scene_texture_compressed.argtypes = [c_void_p, c_int]
         lib.grt_mesh_data_array.restype = c_void_p
@@ -553,6 +558,21 @@ class Scene:
         """Give material `index` the normal map `texture` (a texture index of this scene; -1: none). A Pathtracer sees it after
         invalidate("materials") and update()."""
         _host_check(host_lib().grt_scene_set_material_normal_map(self.handle, index, int(texture)))
+
+    def material_opacity_map(self, index):
+        """The opacity mask of material `index`: (texture index, channel 0..3, threshold), or None (kept out of
+        describe()). Decodes the scene's textures first: the channel of a loaded `mask` is alpha when its file has four channels."""
+        channel, threshold = c_int(), c_float()
+        t = host_lib().grt_scene_material_opacity_map(self.handle, index, byref(channel), byref(threshold))
+        if t < -1:
+            raise RuntimeError(host_lib().grt_last_error().decode(errors="replace"))
+        return None if t < 0 else (t, channel.value, threshold.value)
+
+    def set_material_opacity_map(self, index, texture, channel=3, threshold=0.5):
+        """Cut material `index` out by level 0 of `texture` (a data texture of this scene, add_texture(..., normal_map=True); -1: none):
+        texels whose `channel` byte is below ceil(threshold * 255) let rays through. A Pathtracer sees it after invalidate("materials")
+        and update()."""
+        _host_check(host_lib().grt_scene_set_material_opacity_map(self.handle, index, int(texture), int(channel), float(threshold)))
 
     def add_texture(self, filename, normal_map=False):
         """Add an image file as a texture; normal_map=True loads it as data (no sRGB decode, never block-compressed). Returns its
@@ -1053,6 +1073,34 @@ def perturb_normals(ctx, texture_index, probes):
     out = np.zeros((p.shape[0], 4), np.float32)
     _dev_check(ctx, device_lib().rt_perturb_normals(ctx, int(texture_index), p.ctypes.data, p.shape[0], out.ctypes.data))
     return out
+
+
+def upload_material_opacity(ctx, texture_ids, channels, thresholds):
+    """rt_upload_material_opacity: per uploaded material a texture id (-1: none), a channel (0..3) and a threshold in (0, 1];
+    texture_ids None clears the masks. Returns the status (0: RT_OK)."""
+    if texture_ids is None:
+        return device_lib().rt_upload_material_opacity(ctx, None, None, None, 0)
+    ids = np.ascontiguousarray(texture_ids, dtype=np.int32).reshape(-1)
+    ch = np.ascontiguousarray(channels, dtype=np.int32).reshape(-1)
+    th = np.ascontiguousarray(thresholds, dtype=np.float32).reshape(-1)
+    if ch.size != ids.size or th.size != ids.size:
+        raise ValueError("upload_material_opacity: arrays of different lengths")
+    keep = np.zeros(1, np.int32)   # (a non-NULL pointer for an empty table: NULL ids mean "clear")
+    return device_lib().rt_upload_material_opacity(ctx, ids.ctypes.data if ids.size else keep.ctypes.data, ch.ctypes.data if ids.size else keep.ctypes.data,
+                                                   th.ctypes.data if ids.size else keep.ctypes.data, ids.size)
+
+
+def read_material_opacity(ctx, material):
+    """rt_read_material_opacity: the mask of uploaded material `material` as a bool array [H, W] (True: opaque)."""
+    w, h = c_int(), c_int()
+    lib = device_lib()
+    lib.rt_read_material_opacity(ctx, int(material), None, 0, byref(w), byref(h))   # (the size; fails for want of capacity)
+    if w.value <= 0 or h.value <= 0:
+        raise RuntimeError("device layer: " + lib.rt_last_error(ctx).decode())
+    words = np.zeros((w.value * h.value + 31) // 32, np.uint32)
+    _dev_check(ctx, lib.rt_read_material_opacity(ctx, int(material), words.ctypes.data, words.size, byref(w), byref(h)))
+    bits = np.unpackbits(words.view(np.uint8), bitorder="little")[:w.value * h.value]
+    return bits.reshape(h.value, w.value).astype(bool)
 
 
 def upload_material_normal_maps(ctx, texture_ids):

@@ -429,10 +429,42 @@ RT_DEV bool triangle_test_loaded(float4 part_0, float4 part_1, float4 part_2, in
 	return false;
 }
 
+// ---- alpha-tested opacity masks (rt_upload_material_opacity; the MASK instances only) ----------------------------
+// A candidate that passed Moeller-Trumbore and t < hit.t is accepted only where the mask of its instance's material has a 1 at the
+// hit's texture coordinate; a rejected candidate leaves the ray as if the triangle had not been tested (hit untouched, a shadow ray
+// not occluded). The material is the one the hit would be reported with: a copy in the flattened static BLAS stands for the
+// (instance, triangle) named in its position record. (s, t) = uv_0 + u * uv_edge_1 + v * uv_edge_2 of the 96-byte shading triangle
+// (floats 18..23) in float32, the expression of barycentric() in kernels_shade.hip; the texel is the one whose centre
+// texture_bilinear puts at (x + 1/2) / W. Reached by the few candidates that got this far, so its loads (dependent: alias,
+// material, mask index, mask, texture coordinates, word) stay out of the walk of every other candidate, and it addresses with
+// 64-bit offsets: the 96-byte array is twice as long as the one RtParams::geometry_below_4gib vouches for.
+RT_DEV int opacity_wrap(int i, int n) { if ((n & (n - 1)) == 0) return i & (n - 1); int r = i % n; return r < 0 ? r + n : r; }
+RT_DEV bool opacity_accepts(const RtParams & p, int instance, int triangle_id, float u, float v) {
+	if (p.has_triangle_aliases) {
+		float4 names = p.triangle_positions[size_t(triangle_id) * 3 + 2];
+		if (__float_as_int(names.z) >= 0) { instance = __float_as_int(names.z); triangle_id = __float_as_int(names.w); }
+	}
+	int material = p.mesh_material_ids[instance];
+	if (material < 0) return true;   // (a row without a material of its own)
+	int mask_index = p.material_opacity[material];
+	if (mask_index == RT_INVALID) return true;
+	RtOpacityMask mask = p.opacity_masks[mask_index];
+	const float4 * shading = p.triangles + size_t(triangle_id) * 6;
+	float4 a = shading[4], b = shading[5];   // (.., uv_0) and (uv_edge_1, uv_edge_2)
+	float s = a.z + u * b.x + v * b.z;
+	float t = a.w + u * b.y + v * b.w;
+	int x = opacity_wrap(int(floorf(s * float(mask.width))),  mask.width);
+	int y = opacity_wrap(int(floorf(t * float(mask.height))), mask.height);
+	unsigned i = unsigned(y) * unsigned(mask.width) + unsigned(x);
+	return (mask.bits[i >> 5] >> (i & 31u)) & 1u;
+}
+
 // The same test with the ray kind decided per lane (the mixed engine of the merged wavefront); with a compile-time
 // constant `shadow` it folds to triangle_test_loaded<SHADOW>.
 // hit.t is the far limit of either kind: the closest hit so far, or a shadow ray's maximum distance.
-RT_DEV bool triangle_test_kind(bool shadow, float4 part_0, float4 part_1, float4 part_2, int mesh_id, int triangle_id, const Ray3 & ray, HitRecord & hit) {
+// MASK (with p): the candidate must also pass opacity_accepts.
+template<bool MASK = false>
+RT_DEV bool triangle_test_kind(bool shadow, float4 part_0, float4 part_1, float4 part_2, int mesh_id, int triangle_id, const Ray3 & ray, HitRecord & hit, const RtParams * p = nullptr) {
 	f3 p0 = mk3(part_0.x, part_0.y, part_0.z);
 	f3 e1 = mk3(part_0.w, part_1.x, part_1.y);
 	f3 e2 = mk3(part_1.z, part_1.w, part_2.x);
@@ -448,6 +480,7 @@ RT_DEV bool triangle_test_kind(bool shadow, float4 part_0, float4 part_1, float4
 		if (v >= 0.0f && u + v <= 1.0f) {
 			float t = f * dot_fma(e2, q);
 			if (t > 0.0f && t < hit.t) {
+				if (MASK && !opacity_accepts(*p, mesh_id, triangle_id, u, v)) return false;
 				if (shadow) return true;
 				hit.t = t; hit.u = u; hit.v = v;
 				hit.mesh_id = mesh_id;
@@ -537,7 +570,9 @@ template<int MODE, typename Source> RT_DEV void source_finish(const Source & src
 // to enter or leave, no object-space ray -- the code for those and the three registers that track them are compiled out.
 // SKIP: "skip behind the hit" (above; rt_set_skip_behind_hit) -- only for scenes that are ONE tree (p.entry_tlas_stack_size == 0): a stack entry
 // is then always a group of inner children of that tree.
-template<int MODE, bool COUNT, bool NARROW, bool UNIFIED = false, bool FLAT = false, bool SKIP = false, typename Source>
+// MASK: opacity masks (opacity_accepts above; launched only while p.opacity_active). A rejected candidate moves nothing, so the skipping walk needs
+// nothing else: hit.t only ever moves on accepted hits.
+template<int MODE, bool COUNT, bool NARROW, bool UNIFIED = false, bool FLAT = false, bool SKIP = false, bool MASK = false, typename Source>
 RT_DEV void bvh8_trace_engine(const RtParams & p, Source & src, int ray_count, int * cursor, unsigned long long * stats = nullptr, int ray_count_2 = 0, int * cursor_2 = nullptr, int * regions = nullptr) {
 	constexpr bool SHADOW = MODE == RT_TRACE_SHADOW;   // the kind of every ray, unless MODE == RT_TRACE_MIXED: then lane_shadow
 	bool lane_shadow = SHADOW;
@@ -835,6 +870,7 @@ RT_DEV void bvh8_trace_engine(const RtParams & p, Source & src, int ray_count, i
 							my_triangle = int(triangle_group.x) + my_bit;
 							const float4 * tri = triangles + size_t(my_triangle) * 3;
 							valid = triangle_test_values(tri[0], tri[1], tri[2].x, ray, t, u, v) && t < hit.t;
+							if (MASK && valid) valid = opacity_accepts(p, FLAT ? 0 : mesh_id, my_triangle, u, v);
 						}
 						if (RT_IS_SHADOW) {   // (a group's lanes share one ray, so the kind is uniform within the group)
 							if ((__ballot(valid) >> group_base) & 0xffull) occluded = true;
@@ -873,7 +909,7 @@ RT_DEV void bvh8_trace_engine(const RtParams & p, Source & src, int ray_count, i
 					for (int k = 0; k < RT_TRI_BATCH; k++) {
 						if (tri_id[k] != RT_INVALID && !occluded) {
 							if (COUNT) count_triangles++;
-							if (triangle_test_kind(RT_IS_SHADOW, tri_a[k], tri_b[k], make_float4(tri_c[k], 0.0f, 0.0f, 0.0f), FLAT ? 0 : mesh_id, tri_id[k], ray, hit)) occluded = true;
+							if (triangle_test_kind<MASK>(RT_IS_SHADOW, tri_a[k], tri_b[k], make_float4(tri_c[k], 0.0f, 0.0f, 0.0f), FLAT ? 0 : mesh_id, tri_id[k], ray, hit, MASK ? &p : nullptr)) occluded = true;
 						}
 					}
 				}
@@ -944,16 +980,16 @@ RT_DEV void bvh8_trace_engine(const RtParams & p, Source & src, int ray_count, i
 // One kernel, two instantiations: the ray count is only known on the device.
 // `coherent`: primary rays keep one ray per lane at any count (neighbouring lanes walk the same nodes).
 // (closest-hit rays of a one-tree scene take the skipping walk when the context asks for it -- rt_skip_walk, rt_types.h; uniform over the launch)
-template<bool SHADOW, bool COUNT, typename Source>
+template<bool SHADOW, bool COUNT, bool MASK = false, typename Source>
 RT_DEV void bvh8_trace_persistent(const RtParams & p, const Source & src, int ray_count, int * cursor, unsigned long long * stats = nullptr, bool coherent = false) {
 	const bool narrow = !COUNT && !coherent && ray_count <= RT_NARROW_MAX_RAYS;
 	if (!SHADOW && rt_skip_walk(p)) {
-		if (narrow) bvh8_trace_engine<RT_TRACE_CLOSEST, false, true, false, false, true>(p, src, ray_count, cursor);
-		else bvh8_trace_engine<RT_TRACE_CLOSEST, COUNT, false, false, false, true>(p, src, ray_count, cursor, stats);
+		if (narrow) bvh8_trace_engine<RT_TRACE_CLOSEST, false, true, false, false, true, MASK>(p, src, ray_count, cursor);
+		else bvh8_trace_engine<RT_TRACE_CLOSEST, COUNT, false, false, false, true, MASK>(p, src, ray_count, cursor, stats);
 		return;
 	}
-	if (narrow) bvh8_trace_engine<SHADOW ? RT_TRACE_SHADOW : RT_TRACE_CLOSEST, false, true>(p, src, ray_count, cursor);
-	else bvh8_trace_engine<SHADOW ? RT_TRACE_SHADOW : RT_TRACE_CLOSEST, COUNT, false>(p, src, ray_count, cursor, stats);
+	if (narrow) bvh8_trace_engine<SHADOW ? RT_TRACE_SHADOW : RT_TRACE_CLOSEST, false, true, false, false, false, MASK>(p, src, ray_count, cursor);
+	else bvh8_trace_engine<SHADOW ? RT_TRACE_SHADOW : RT_TRACE_CLOSEST, COUNT, false, false, false, false, MASK>(p, src, ray_count, cursor, stats);
 }
 
 RT_DEV uint4 pack_hit(const HitRecord & h) { // Buffers.h:25-32
@@ -1257,6 +1293,18 @@ __global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_
 __global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh8_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, uint4 * hits, int ray_count, int * retired) { bvh8_trace_persistent<false, false>(p, ClosestHitSource { origin, direction, hits }, ray_count, retired); }
 __global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh8_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, const float * max_distance, uint8_t * occluded, int ray_count, int * retired) { bvh8_trace_persistent<true, false>(p, ShadowExplicitSource { origin, direction, max_distance, occluded }, ray_count, retired); }
 
+// The same seven with opacity masks (launched iff p.opacity_active). Register budget: RT_MASK_WAVES, below.
+#ifndef RT_MASK_WAVES
+#define RT_MASK_WAVES RT_TRACE_LAUNCH_WAVES
+#endif
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_MASK_WAVES) kernel_trace_bvh8_mask(RtParams p, int bounce) { bvh8_trace_persistent<false, false, true>(p, closest_queue(p, bounce), p.sizes->trace[bounce], p.ray_cursors + 2 * bounce, nullptr, bounce == 0); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_MASK_WAVES) kernel_trace_shadow_bvh8_mask(RtParams p, int bounce) { bvh8_trace_persistent<true, false, true>(p, shadow_queue(p, bounce), p.sizes->shadow[bounce], p.ray_cursors + 2 * bounce + 1); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_MASK_WAVES) kernel_trace_shadow_bvh8_ao_mask(RtParams p) { bvh8_trace_persistent<true, false, true>(p, ao_queue(p), p.sizes->shadow[0], p.ray_cursors + 1); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_MASK_WAVES) kernel_trace_bvh8_counting_mask(RtParams p, int bounce, unsigned long long * stats) { bvh8_trace_persistent<false, true, true>(p, closest_queue(p, bounce), p.sizes->trace[bounce], p.ray_cursors + 2 * bounce, stats); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_MASK_WAVES) kernel_trace_shadow_bvh8_counting_mask(RtParams p, int bounce, unsigned long long * stats) { bvh8_trace_persistent<true, true, true>(p, shadow_queue(p, bounce), p.sizes->shadow[bounce], p.ray_cursors + 2 * bounce + 1, stats + 5); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_MASK_WAVES) kernel_trace_bvh8_explicit_mask(RtParams p, RtVec3SoA origin, RtVec3SoA direction, uint4 * hits, int ray_count, int * retired) { bvh8_trace_persistent<false, false, true>(p, ClosestHitSource { origin, direction, hits }, ray_count, retired); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_MASK_WAVES) kernel_trace_shadow_bvh8_explicit_mask(RtParams p, RtVec3SoA origin, RtVec3SoA direction, const float * max_distance, uint8_t * occluded, int ray_count, int * retired) { bvh8_trace_persistent<true, false, true>(p, ShadowExplicitSource { origin, direction, max_distance, occluded }, ray_count, retired); }
+
 __global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh2(RtParams p, int bounce) { bvh_trace_persistent<Bvh2Step, false>(p, closest_queue(p, bounce), p.sizes->trace[bounce], p.ray_cursors + 2 * bounce); }
 __global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh2(RtParams p, int bounce) { bvh_trace_persistent<Bvh2Step, true>(p, shadow_queue(p, bounce), p.sizes->shadow[bounce], p.ray_cursors + 2 * bounce + 1); }
 __global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh2_ao(RtParams p) { bvh_trace_persistent<Bvh2Step, true>(p, ao_queue(p), p.sizes->shadow[0], p.ray_cursors + 1); }
@@ -1291,12 +1339,12 @@ extern "C" int rt_debug_read_wave_clock(void * clocks, void * meta) {
 	if (hipMemcpyFromSymbol(clocks, HIP_SYMBOL(grt_wave_clock), sizeof(grt_wave_clock)) != hipSuccess) return 1;
 	return hipMemcpyFromSymbol(meta, HIP_SYMBOL(grt_wave_clock_meta), sizeof(grt_wave_clock_meta)) != hipSuccess;
 }
-template<bool COUNT, bool FLAT = false, bool SKIP = false> RT_DEV void trace_stream_probed(const RtParams & p, unsigned long long * stats, unsigned long long * mid);
-template<bool COUNT, bool FLAT = false, bool SKIP = false>
+template<bool COUNT, bool FLAT = false, bool SKIP = false, bool MASK = false> RT_DEV void trace_stream_probed(const RtParams & p, unsigned long long * stats, unsigned long long * mid);
+template<bool COUNT, bool FLAT = false, bool SKIP = false, bool MASK = false>
 RT_DEV void trace_stream(const RtParams & p, unsigned long long * stats) {
 	const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
 	unsigned long long t1 = 0;
-	trace_stream_probed<COUNT, FLAT, SKIP>(p, stats, &t1);
+	trace_stream_probed<COUNT, FLAT, SKIP, MASK>(p, stats, &t1);
 	const unsigned long long t2 = __builtin_amdgcn_s_memrealtime();
 	if ((threadIdx.x & 63) == 0) {
 		const int slot = p.stream_iteration % RT_WAVE_CLOCK_SLOTS, wave = blockIdx.x * (RT_TRACE_BLOCK / RT_WAVE_SIZE) + threadIdx.x / RT_WAVE_SIZE;
@@ -1308,12 +1356,12 @@ RT_DEV void trace_stream(const RtParams & p, unsigned long long * stats) {
 #define RT_WAVE_CLOCK_MID , unsigned long long * mid
 #define RT_WAVE_CLOCK_MARK *mid = __builtin_amdgcn_s_memrealtime();
 #else
-template<bool COUNT, bool FLAT = false, bool SKIP = false> RT_DEV void trace_stream(const RtParams & p, unsigned long long * stats);
+template<bool COUNT, bool FLAT = false, bool SKIP = false, bool MASK = false> RT_DEV void trace_stream(const RtParams & p, unsigned long long * stats);
 #define trace_stream_body trace_stream
 #define RT_WAVE_CLOCK_MID
 #define RT_WAVE_CLOCK_MARK
 #endif
-template<bool COUNT, bool FLAT, bool SKIP>
+template<bool COUNT, bool FLAT, bool SKIP, bool MASK>
 RT_DEV void trace_stream_body(const RtParams & p, unsigned long long * stats RT_WAVE_CLOCK_MID) {
 	const int q = p.stream_iteration & 1;
 	MixedStreamSource src { { p.trace[q].origin, p.trace[q].direction, p.trace[q].hits },
@@ -1332,13 +1380,13 @@ RT_DEV void trace_stream_body(const RtParams & p, unsigned long long * stats RT_
 	//     where it was a compile-time constant) and a 25 M-ray launch has little to gain from it (0.87 -> 0.83 when mixed).
 	//   profiles/r02_mixed_engine.txt
 	if (!COUNT && closest_count + shadow_count <= RT_NARROW_MAX_RAYS)
-		bvh8_trace_engine<RT_TRACE_MIXED, false, true, true, FLAT, SKIP>(p, src, closest_count, &p.stream->cursor[q][0], nullptr, shadow_count, &p.stream->cursor[q][1]);
+		bvh8_trace_engine<RT_TRACE_MIXED, false, true, true, FLAT, SKIP, MASK>(p, src, closest_count, &p.stream->cursor[q][0], nullptr, shadow_count, &p.stream->cursor[q][1]);
 	else if (COUNT || closest_count + shadow_count <= RT_MIXED_MAX_RAYS)
-		bvh8_trace_engine<RT_TRACE_MIXED, COUNT, false, true, FLAT, SKIP>(p, src, closest_count, &p.stream->cursor[q][0], stats, shadow_count, &p.stream->cursor[q][1], RT_ENDGAME ? &p.stream->endgame[q][0][0] : nullptr);
+		bvh8_trace_engine<RT_TRACE_MIXED, COUNT, false, true, FLAT, SKIP, MASK>(p, src, closest_count, &p.stream->cursor[q][0], stats, shadow_count, &p.stream->cursor[q][1], RT_ENDGAME ? &p.stream->endgame[q][0][0] : nullptr);
 	else {
-		bvh8_trace_engine<RT_TRACE_CLOSEST, false, false, true, FLAT, SKIP>(p, src.closest, closest_count, &p.stream->cursor[q][0], nullptr, 0, nullptr, RT_ENDGAME ? &p.stream->endgame[q][0][0] : nullptr);
+		bvh8_trace_engine<RT_TRACE_CLOSEST, false, false, true, FLAT, SKIP, MASK>(p, src.closest, closest_count, &p.stream->cursor[q][0], nullptr, 0, nullptr, RT_ENDGAME ? &p.stream->endgame[q][0][0] : nullptr);
 		RT_WAVE_CLOCK_MARK
-		bvh8_trace_engine<RT_TRACE_SHADOW,  false, false, true, FLAT>(p, src.shadow,  shadow_count,  &p.stream->cursor[q][1], nullptr, 0, nullptr, RT_ENDGAME ? &p.stream->endgame[q][1][0] : nullptr);   // (a shadow ray's limit never moves: nothing to skip)
+		bvh8_trace_engine<RT_TRACE_SHADOW,  false, false, true, FLAT, false, MASK>(p, src.shadow,  shadow_count,  &p.stream->cursor[q][1], nullptr, 0, nullptr, RT_ENDGAME ? &p.stream->endgame[q][1][0] : nullptr);   // (a shadow ray's limit never moves: nothing to skip)
 	}
 }
 __global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_stream_bvh8(RtParams p) { trace_stream<false>(p, nullptr); }
@@ -1354,6 +1402,13 @@ __global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_FLAT_WAVES) kernel_trace_st
 __global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_FLAT_SKIP_WAVES) kernel_trace_stream_bvh8_flat_skip(RtParams p) { trace_stream<false, true, true>(p, nullptr); }
 __global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_stream_bvh8_counting(RtParams p, unsigned long long * stats) {
 	if (rt_skip_walk(p)) trace_stream<true, false, true>(p, stats); else trace_stream<true>(p, stats);
+}
+// The four with opacity masks (launched iff p.opacity_active)
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_MASK_WAVES) kernel_trace_stream_bvh8_mask(RtParams p) { trace_stream<false, false, false, true>(p, nullptr); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_MASK_WAVES) kernel_trace_stream_bvh8_flat_mask(RtParams p) { trace_stream<false, true, false, true>(p, nullptr); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_MASK_WAVES) kernel_trace_stream_bvh8_flat_skip_mask(RtParams p) { trace_stream<false, true, true, true>(p, nullptr); }
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_MASK_WAVES) kernel_trace_stream_bvh8_counting_mask(RtParams p, unsigned long long * stats) {
+	if (rt_skip_walk(p)) trace_stream<true, false, true, true>(p, stats); else trace_stream<true, false, false, true>(p, stats);
 }
 
 // Persistent grid: enough workgroups to fill every CU to the occupancy the kernel reaches,
@@ -1380,23 +1435,33 @@ template<auto K> static int persistent_grid() {
 template<auto K, typename... A> static void launch_persistent(hipStream_t stream, const A &... args) {
 	hipLaunchKernelGGL(K, dim3(persistent_grid<K>()), dim3(RT_TRACE_BLOCK), 0, stream, args...);
 }
-// The kernel of the context's BVH type: p.bvh_width 2 or 4, else the CWBVH.
-template<auto K2, auto K4, auto K8, typename... A> static void launch_for_width(const RtParams & p, hipStream_t stream, const A &... args) {
+// The kernel of the context's BVH type: p.bvh_width 2 or 4, else the CWBVH -- its _mask instance K8M iff the context holds opacity masks
+// (the entry points of rt_api.hip refuse masks with the other two widths before any launch).
+template<auto K2, auto K4, auto K8, auto K8M, typename... A> static void launch_for_width(const RtParams & p, hipStream_t stream, const A &... args) {
 	if (p.bvh_width == 2) launch_persistent<K2>(stream, p, args...);
 	else if (p.bvh_width == 4) launch_persistent<K4>(stream, p, args...);
+	else if (p.opacity_active) launch_persistent<K8M>(stream, p, args...);
 	else launch_persistent<K8>(stream, p, args...);
 }
 
 void rt_launch_trace(const RtParams & p, int bounce, hipStream_t stream) {
-	launch_for_width<kernel_trace_bvh2, kernel_trace_bvh4, kernel_trace_bvh8>(p, stream, bounce);
+	launch_for_width<kernel_trace_bvh2, kernel_trace_bvh4, kernel_trace_bvh8, kernel_trace_bvh8_mask>(p, stream, bounce);
 }
 void rt_launch_trace_shadow(const RtParams & p, int bounce, hipStream_t stream) {
-	launch_for_width<kernel_trace_shadow_bvh2, kernel_trace_shadow_bvh4, kernel_trace_shadow_bvh8>(p, stream, bounce);
+	launch_for_width<kernel_trace_shadow_bvh2, kernel_trace_shadow_bvh4, kernel_trace_shadow_bvh8, kernel_trace_shadow_bvh8_mask>(p, stream, bounce);
 }
 void rt_launch_trace_shadow_ao(const RtParams & p, hipStream_t stream) {
-	launch_for_width<kernel_trace_shadow_bvh2_ao, kernel_trace_shadow_bvh4_ao, kernel_trace_shadow_bvh8_ao>(p, stream);
+	launch_for_width<kernel_trace_shadow_bvh2_ao, kernel_trace_shadow_bvh4_ao, kernel_trace_shadow_bvh8_ao, kernel_trace_shadow_bvh8_ao_mask>(p, stream);
 }
 void rt_launch_trace_stream(const RtParams & p, unsigned long long * stats, hipStream_t stream) {
+	if (p.opacity_active) {   // the same choice among the _mask instances
+		if (stats) launch_persistent<kernel_trace_stream_bvh8_counting_mask>(stream, p, stats);
+		else if (p.entry_tlas_stack_size == 0 && p.geometry_below_4gib) {
+			if (rt_skip_walk(p)) launch_persistent<kernel_trace_stream_bvh8_flat_skip_mask>(stream, p);
+			else launch_persistent<kernel_trace_stream_bvh8_flat_mask>(stream, p);
+		} else launch_persistent<kernel_trace_stream_bvh8_mask>(stream, p);
+		return;
+	}
 	if (stats) launch_persistent<kernel_trace_stream_bvh8_counting>(stream, p, stats);
 	else if (p.entry_tlas_stack_size == 0 && p.geometry_below_4gib) {   // the whole scene is one world-space tree: the engine without the TLAS / instance code (32-bit offsets; a larger scene walks the general engine from node 0)
 		if (rt_skip_walk(p)) launch_persistent<kernel_trace_stream_bvh8_flat_skip>(stream, p);
@@ -1407,6 +1472,13 @@ void rt_launch_trace_stream(const RtParams & p, unsigned long long * stats, hipS
 // of its persistent grid, info[2] RT_NARROW_MAX_RAYS, info[3] RT_MIXED_MAX_RAYS. For rt_trace_stream_rays, which reports it to tests.
 void rt_trace_stream_launch_info(const RtParams & p, bool stats, int32_t * info) {
 	int kernel, grid;
+	if (p.opacity_active) {
+		if (stats) { kernel = RT_STREAM_KERNEL_COUNTING_MASK; grid = persistent_grid<kernel_trace_stream_bvh8_counting_mask>(); }
+		else if (p.entry_tlas_stack_size == 0 && p.geometry_below_4gib) {
+			if (rt_skip_walk(p)) { kernel = RT_STREAM_KERNEL_FLAT_SKIP_MASK; grid = persistent_grid<kernel_trace_stream_bvh8_flat_skip_mask>(); }
+			else { kernel = RT_STREAM_KERNEL_FLAT_MASK; grid = persistent_grid<kernel_trace_stream_bvh8_flat_mask>(); }
+		} else { kernel = RT_STREAM_KERNEL_GENERAL_MASK; grid = persistent_grid<kernel_trace_stream_bvh8_mask>(); }
+	} else
 	if (stats) { kernel = RT_STREAM_KERNEL_COUNTING; grid = persistent_grid<kernel_trace_stream_bvh8_counting>(); }
 	else if (p.entry_tlas_stack_size == 0 && p.geometry_below_4gib) {
 		if (rt_skip_walk(p)) { kernel = RT_STREAM_KERNEL_FLAT_SKIP; grid = persistent_grid<kernel_trace_stream_bvh8_flat_skip>(); }
@@ -1415,14 +1487,16 @@ void rt_trace_stream_launch_info(const RtParams & p, bool stats, int32_t * info)
 	info[0] = kernel; info[1] = grid * (RT_TRACE_BLOCK / RT_WAVE_SIZE); info[2] = RT_NARROW_MAX_RAYS; info[3] = RT_MIXED_MAX_RAYS;
 }
 void rt_launch_trace_counting(const RtParams & p, int bounce, unsigned long long * stats, hipStream_t stream) {
-	launch_persistent<kernel_trace_bvh8_counting>(stream, p, bounce, stats);
+	if (p.opacity_active) launch_persistent<kernel_trace_bvh8_counting_mask>(stream, p, bounce, stats);
+	else launch_persistent<kernel_trace_bvh8_counting>(stream, p, bounce, stats);
 }
 void rt_launch_trace_shadow_counting(const RtParams & p, int bounce, unsigned long long * stats, hipStream_t stream) {
-	launch_persistent<kernel_trace_shadow_bvh8_counting>(stream, p, bounce, stats);
+	if (p.opacity_active) launch_persistent<kernel_trace_shadow_bvh8_counting_mask>(stream, p, bounce, stats);
+	else launch_persistent<kernel_trace_shadow_bvh8_counting>(stream, p, bounce, stats);
 }
 void rt_launch_trace_explicit(const RtParams & p, RtVec3SoA origin, RtVec3SoA direction, uint4 * hits, int ray_count, int * retired_counter, hipStream_t stream) {
-	launch_for_width<kernel_trace_bvh2_explicit, kernel_trace_bvh4_explicit, kernel_trace_bvh8_explicit>(p, stream, origin, direction, hits, ray_count, retired_counter);
+	launch_for_width<kernel_trace_bvh2_explicit, kernel_trace_bvh4_explicit, kernel_trace_bvh8_explicit, kernel_trace_bvh8_explicit_mask>(p, stream, origin, direction, hits, ray_count, retired_counter);
 }
 void rt_launch_trace_shadow_explicit(const RtParams & p, RtVec3SoA origin, RtVec3SoA direction, const float * max_distance, uint8_t * occluded, int ray_count, int * retired_counter, hipStream_t stream) {
-	launch_for_width<kernel_trace_shadow_bvh2_explicit, kernel_trace_shadow_bvh4_explicit, kernel_trace_shadow_bvh8_explicit>(p, stream, origin, direction, max_distance, occluded, ray_count, retired_counter);
+	launch_for_width<kernel_trace_shadow_bvh2_explicit, kernel_trace_shadow_bvh4_explicit, kernel_trace_shadow_bvh8_explicit, kernel_trace_shadow_bvh8_explicit_mask>(p, stream, origin, direction, max_distance, occluded, ray_count, retired_counter);
 }

@@ -228,6 +228,10 @@ struct rt_context {
 	std::vector<uint8_t> material_type_list;   // what rt_upload_materials uploaded (rt_upload_material_normal_maps checks against it)
 	void * material_normal_maps = nullptr;     // int per material (rt_upload_material_normal_maps)
 	std::vector<int> texture_formats;          // the device format of every texture of rt_upload_textures
+	std::vector<RtTexture> texture_records;    // ... and its record (device pointer, size), as uploaded
+	// opacity masks (rt_upload_material_opacity): the two device tables and the bits of all masks in one allocation; host copies for rt_read_material_opacity
+	void * material_opacity = nullptr, * opacity_masks = nullptr, * opacity_bits = nullptr;
+	std::vector<int> material_opacity_list; std::vector<RtOpacityMask> opacity_mask_list;
 	bool has_lights = false;
 	void * texture_table = nullptr; std::vector<void *> texture_data;
 	void * pmj = nullptr, * blue_noise = nullptr;
@@ -469,6 +473,8 @@ static bool bvh_nodes_present(const rt_context * ctx) {
 enum { NEED_SCENE = 1, NEED_SCENE_JOINT = 2, NEED_MATERIALS = 4, NEED_RNG = 8, NEED_SKY = 16, NEED_FRAME = 32 };
 static int check_ready(rt_context * ctx, const char * caller, int needs) {
 	const RtParams & p = ctx->params;
+	if ((needs & (NEED_SCENE | NEED_SCENE_JOINT)) && p.opacity_active && ctx->bvh_width != 8)
+		return fail(ctx, RT_ERROR_INVALID_ARG, "%s: opacity masks are uploaded (rt_upload_material_opacity) and only the CWBVH kernels test them; rt_set_bvh_type is %d", caller, ctx->bvh_width);
 	const bool geometry = p.triangles && bvh_nodes_present(ctx), instances = p.mesh_bvh_root_indices != nullptr;
 	const struct { int need; bool missing; const char * what; } checks[] = {
 		{ NEED_SCENE,       !geometry,                        "geometry not uploaded" },
@@ -666,6 +672,29 @@ int rt_upload_tlas_bvh4(rt_context * ctx, const void * tlas_nodes, size_t tlas_n
 // The two names are the last 8 bytes of the 48-byte position record (36 B of positions + 12 B of padding), so the translation
 // costs one load from a line the triangle test has touched.
 } // extern "C"
+// Opacity masks: word w of a mask holds texels [32 w, 32 w + 32) of level 0, bit k set iff byte `channel` of texel 32 w + k is >= cut.
+// One thread per word, a plain store, no atomics: the bits are the same on every run. The tail word's bits past the last texel stay 0
+// (texel_count is below 2^30, see rt_upload_material_opacity: every comparison is between non-negative ints).
+__global__ void kernel_build_opacity_bits(const unsigned * texels, unsigned * words, int texel_count, int word_count, int channel, int cut) {
+	int w = blockIdx.x * blockDim.x + threadIdx.x;
+	if (w >= word_count) return;
+	int first = w * 32;
+	unsigned bits = 0;
+	for (int k = 0; k < 32; k++) {
+		if (first + k < texel_count && int((texels[first + k] >> (8 * channel)) & 0xffu) >= cut) bits |= 1u << k;
+	}
+	words[w] = bits;
+}
+// Drops the masks (drains first: rays in flight read them). The next launches take the plain instances again.
+static int opacity_clear(rt_context * ctx) {
+	if (!ctx->material_opacity && !ctx->opacity_masks && !ctx->opacity_bits) return RT_OK;
+	RT_HIP(ctx, quiesce(ctx));
+	device_free(ctx, ctx->material_opacity); device_free(ctx, ctx->opacity_masks); device_free(ctx, ctx->opacity_bits);
+	ctx->material_opacity = ctx->opacity_masks = ctx->opacity_bits = nullptr;
+	ctx->material_opacity_list.clear(); ctx->opacity_mask_list.clear();
+	ctx->params.material_opacity = nullptr; ctx->params.opacity_masks = nullptr; ctx->params.opacity_active = 0;
+	return RT_OK;
+}
 __global__ void kernel_name_triangles(float4 * positions, const int2 * names, int count) {
 	int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= count) return;
@@ -1013,6 +1042,7 @@ int rt_upload_materials(rt_context * ctx, const uint8_t * types, const void * ma
 	ctx->material_type_list.assign(types, types + count);
 	ctx->params.material_normal_maps = nullptr;   // new materials: no normal maps until rt_upload_material_normal_maps
 	ctx->params.normal_map_slots = 0;
+	s = opacity_clear(ctx); if (s) return s;      // ... and no opacity masks until rt_upload_material_opacity
 
 	// Scene::check_materials (Scene.cpp:50-70): which material kernels have to run at all
 	for (bool & h : ctx->has_material) h = false;
@@ -1060,6 +1090,80 @@ int rt_upload_material_normal_maps(rt_context * ctx, const int32_t * texture_ids
 	return RT_OK;
 }
 
+// Opacity masks. Everything is checked before anything changes; then the context is drained (rays in flight hold no mask
+// state, but the launches that carry them read the tables), the old masks are freed and one mask per distinct (texture, channel, cut) is
+// built on the device. A mask on a light material is ignored: masks act in traversal, and emitters are sampled whole.
+int rt_upload_material_opacity(rt_context * ctx, const int32_t * texture_ids, const int32_t * channels, const float * thresholds, size_t count) {
+	RT_REQUIRE(ctx, ctx, "rt_upload_material_opacity: NULL context");
+	(void)hipSetDevice(ctx->device);
+	if (!texture_ids) return opacity_clear(ctx);
+	RT_REQUIRE(ctx, channels && thresholds, "rt_upload_material_opacity: NULL channels or thresholds");
+	RT_REQUIRE(ctx, ctx->params.materials, "rt_upload_material_opacity: no materials uploaded");
+	if (count != ctx->material_type_list.size())
+		return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_material_opacity: %zu entries for %zu materials", count, ctx->material_type_list.size());
+	struct Key { int texture, channel, cut; size_t first_word; };
+	std::vector<Key> keys; std::vector<int> mask_of_material(count, RT_INVALID);
+	size_t total_words = 0;
+	for (size_t i = 0; i < count; i++) {
+		int id = texture_ids[i];
+		if (id == RT_INVALID) continue;
+		if (id < 0 || size_t(id) >= ctx->texture_records.size())
+			return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_material_opacity: material %zu names texture %d of %zu", i, id, ctx->texture_records.size());
+		if (ctx->texture_formats[id] != RT_TEXTURE_RGBA8)
+			return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_material_opacity: material %zu names texture %d, which is not RT_TEXTURE_RGBA8", i, id);
+		if (channels[i] < 0 || channels[i] > 3)
+			return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_material_opacity: material %zu: channel %d is not in 0..3", i, channels[i]);
+		if (!(thresholds[i] > 0.0f && thresholds[i] <= 1.0f))   // (false for NaN)
+			return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_material_opacity: material %zu: threshold %.9g is not in (0, 1]", i, double(thresholds[i]));
+		const RtTexture & t = ctx->texture_records[id];
+		if ((long long)t.width * t.height >= (1ll << 30))
+			return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_material_opacity: material %zu: texture %d has 2^30 texels or more", i, id);
+		if (ctx->material_type_list[i] == RT_MATERIAL_LIGHT) continue;
+		int cut = int(ceilf(thresholds[i] * 255.0f)); cut = cut < 0 ? 0 : (cut > 255 ? 255 : cut);
+		size_t k = 0;
+		while (k < keys.size() && !(keys[k].texture == id && keys[k].channel == channels[i] && keys[k].cut == cut)) k++;
+		if (k == keys.size()) { keys.push_back({ id, channels[i], cut, total_words }); total_words += (size_t(t.width) * t.height + 31) / 32; }
+		mask_of_material[i] = int(k);
+	}
+	int s = opacity_clear(ctx); if (s) return s;
+	if (keys.empty()) { RT_HIP(ctx, quiesce(ctx)); return RT_OK; }
+	RT_HIP(ctx, quiesce(ctx));
+	s = device_alloc(ctx, &ctx->opacity_bits, total_words * 4); if (s) return s;
+	std::vector<RtOpacityMask> masks(keys.size());
+	for (size_t k = 0; k < keys.size(); k++) {
+		const RtTexture & t = ctx->texture_records[keys[k].texture];
+		int texel_count = t.width * t.height, word_count = (texel_count + 31) / 32;
+		unsigned * words = (unsigned *)ctx->opacity_bits + keys[k].first_word;
+		kernel_build_opacity_bits<<<unsigned((word_count + 255) / 256), 256, 0, ctx->stream>>>((const unsigned *)t.texels, words, texel_count, word_count, keys[k].channel, keys[k].cut);
+		hipError_t e = hipGetLastError();
+		if (e != hipSuccess) { (void)opacity_clear(ctx); return fail(ctx, RT_ERROR_HIP, "rt_upload_material_opacity: building the bits failed: %s", hipGetErrorString(e)); }
+		masks[k] = { words, t.width, t.height };
+	}
+	hipError_t e = hipStreamSynchronize(ctx->stream);
+	if (e != hipSuccess) { (void)opacity_clear(ctx); return fail(ctx, RT_ERROR_HIP, "rt_upload_material_opacity: building the bits failed: %s", hipGetErrorString(e)); }
+	s = upload(ctx, &ctx->opacity_masks, masks.data(), masks.size() * sizeof(RtOpacityMask)); if (s) { (void)opacity_clear(ctx); return s; }
+	s = upload(ctx, &ctx->material_opacity, mask_of_material.data(), count * sizeof(int)); if (s) { (void)opacity_clear(ctx); return s; }
+	ctx->material_opacity_list = mask_of_material; ctx->opacity_mask_list = masks;
+	ctx->params.material_opacity = (const int *)ctx->material_opacity;
+	ctx->params.opacity_masks = (const RtOpacityMask *)ctx->opacity_masks;
+	ctx->params.opacity_active = 1;
+	return RT_OK;
+}
+int rt_read_material_opacity(rt_context * ctx, int material, uint32_t * words, size_t capacity_words, int32_t * out_width, int32_t * out_height) {
+	RT_REQUIRE(ctx, ctx, "rt_read_material_opacity: NULL context");
+	if (material < 0 || size_t(material) >= ctx->material_opacity_list.size() || ctx->material_opacity_list[material] == RT_INVALID)
+		return fail(ctx, RT_ERROR_INVALID_ARG, "rt_read_material_opacity: material %d has no opacity mask", material);
+	const RtOpacityMask & m = ctx->opacity_mask_list[ctx->material_opacity_list[material]];
+	size_t word_count = (size_t(m.width) * m.height + 31) / 32;
+	if (out_width) *out_width = m.width;
+	if (out_height) *out_height = m.height;
+	if (!words || capacity_words < word_count)
+		return fail(ctx, RT_ERROR_INVALID_ARG, "rt_read_material_opacity: the %d x %d mask of material %d takes %zu words, capacity %zu", m.width, m.height, material, word_count, capacity_words);
+	(void)hipSetDevice(ctx->device);
+	RT_HIP(ctx, hipMemcpy(words, m.bits, word_count * 4, hipMemcpyDeviceToHost));
+	return RT_OK;
+}
+
 int rt_upload_media(rt_context * ctx, const void * media, size_t count) {
 	RT_REQUIRE(ctx, ctx && (media || count == 0), "rt_upload_media: NULL argument");
 	(void)hipSetDevice(ctx->device);
@@ -1073,7 +1177,8 @@ int rt_upload_textures(rt_context * ctx, const rt_texture_desc * descs, size_t c
 	RT_REQUIRE(ctx, ctx && (descs || count == 0), "rt_upload_textures: NULL argument");
 	(void)hipSetDevice(ctx->device);
 	for (void * p : ctx->texture_data) device_free(ctx, p);
-	ctx->texture_data.clear(); ctx->texture_bytes = 0; ctx->texture_formats.clear();
+	ctx->texture_data.clear(); ctx->texture_bytes = 0; ctx->texture_formats.clear(); ctx->texture_records.clear();
+	{ int cleared = opacity_clear(ctx); if (cleared) return cleared; }   // the masks were built from textures of the old table
 	std::vector<RtTexture> table(count);
 	for (size_t i = 0; i < count; i++) {
 		const rt_texture_desc & d = descs[i];
@@ -1108,6 +1213,7 @@ int rt_upload_textures(rt_context * ctx, const rt_texture_desc * descs, size_t c
 	}
 	int s = upload(ctx, &ctx->texture_table, table.data(), count * sizeof(RtTexture)); if (s) return s;
 	ctx->params.textures = (const RtTexture *)ctx->texture_table;
+	ctx->texture_records = table;
 	ctx->params.material_normal_maps = nullptr;   // the maps named textures of the old table
 	ctx->params.normal_map_slots = 0;
 	ctx->params.textures_compressed = 0;

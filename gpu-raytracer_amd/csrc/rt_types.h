@@ -105,6 +105,10 @@ struct RtTexture {
 
 struct RtAOV { float4 * framebuffer, * accumulator; };
 
+// Opacity mask of a material (rt_upload_material_opacity): one bit per texel of level 0 of a texture, bit y * width + x
+// in word (y * width + x) >> 5, no row padding; 1: opaque. Built once on the device; the traversal kernels read nothing else of the texture.
+struct RtOpacityMask { const unsigned * bits; int width, height; };
+
 // Everything a kernel needs, passed BY VALUE as kernel argument (lives in the kernarg
 // segment and is read with scalar loads; no __constant__ symbols, so several contexts
 // can coexist in one process).
@@ -211,6 +215,11 @@ struct RtParams {
 	// when some material of slot s (diffuse, plastic, dielectric, conductor) has one -- only then does the launcher take that slot's _nmap instance.
 	const int * material_normal_maps;
 	int normal_map_slots;
+	// Alpha-tested opacity masks (rt_upload_material_opacity): the mask of each material as an index into opacity_masks (RT_INVALID: none).
+	// opacity_active: some material has one -- only then do the launchers take the CWBVH kernels' _mask instances, the only code that reads these fields.
+	const int * material_opacity;
+	const RtOpacityMask * opacity_masks;
+	int opacity_active;
 };
 // "Skip behind the hit" (kernels_trace.hip): closest-hit rays drop stacked groups of children that lie behind the hit they hold. Taken when the context wants it
 // (rt_set_skip_behind_hit) AND the scene is ONE tree the flattened scene's engine walks (rt_set_static_geometry(ctx, 1), arrays below 4 GiB): every CWBVH
@@ -261,7 +270,8 @@ void rt_launch_trace(const RtParams & p, int bounce, hipStream_t stream);
 void rt_launch_generate_stream(const RtParams & p, int sample_index, int pixel_offset, int pixel_count, int slot_base, int queue_offset, int block_width, int band_rows, hipStream_t stream);
 void rt_launch_stream_advance(RtStreamControl * control, int iteration, int generated, int * progress, int reset_ring_first, int reset_ring_count, hipStream_t stream);
 void rt_launch_trace_stream(const RtParams & p, unsigned long long * stats, hipStream_t stream);
-enum { RT_STREAM_KERNEL_GENERAL = 0, RT_STREAM_KERNEL_FLAT = 1, RT_STREAM_KERNEL_FLAT_SKIP = 2, RT_STREAM_KERNEL_COUNTING = 3 };
+enum { RT_STREAM_KERNEL_GENERAL = 0, RT_STREAM_KERNEL_FLAT = 1, RT_STREAM_KERNEL_FLAT_SKIP = 2, RT_STREAM_KERNEL_COUNTING = 3,
+       RT_STREAM_KERNEL_GENERAL_MASK = 4, RT_STREAM_KERNEL_FLAT_MASK = 5, RT_STREAM_KERNEL_FLAT_SKIP_MASK = 6, RT_STREAM_KERNEL_COUNTING_MASK = 7 };   // (_MASK: p.opacity_active)
 void rt_trace_stream_launch_info(const RtParams & p, bool stats, int32_t * info);   // the kernel rt_launch_trace_stream picks, its grid in waves, the two engine limits
 void rt_launch_sort_stream(const RtParams & p, hipStream_t stream);
 void rt_launch_material_stream(const RtParams & p, int material_slot, hipStream_t stream);

@@ -106,6 +106,9 @@ struct CPUConfig {
 	// Sky importance sampling for next-event estimation (rt_set_sky_sampling): 0 = off, the reference's estimator; (0, 1] = the sky's share
 	// of the light samples when the scene has emitters (all of them when it has none). Same expectation, less noise under a sky with a sun.
 	float sky_sampling = 0.0f;
+	// Alpha-tested cut-outs from the albedo textures: 1 = every surface material whose albedo FILE has an alpha channel that is not constant gets an
+	// opacity mask from it (channel a, threshold 0.5; an explicit <bsdf type="mask"> wins). Read when a scene is loaded. 0: off, as the reference renders them.
+	int   alpha_masks = 0;
 	int   static_slot_learning_viewpoint = 1;   // a quarter of those rays are paths from the camera as it stands when the tree is built (0: none are; half come from points of the free space, the rest from the surface, either way)
 	// ... and early split clipping (StaticBVHBuilder::presplit, as in front of the device build) in front of that builder's own SAH + spatial splits: fraction of
 	// the geometry's longest side above which a triangle is cut blindly first. 0: off.

@@ -22,6 +22,9 @@ struct Texture {
 	// A data texture (a tangent-space normal map): texels are the file's bytes as stored -- no sRGB decode, mips filtered on
 	// the raw values, never block-compressed.
 	bool data = false;
+	// The file it was decoded from, and whether that file stores an alpha (fourth) channel -- what an opacity mask reads (Material::opacity_handle)
+	std::string filename;
+	bool file_alpha = false;
 
 	int mip_levels() const { return int(mip_offsets.size()); }
 };
@@ -61,6 +64,14 @@ struct Material {
 	Vector3         diffuse = Vector3(1.0f, 1.0f, 1.0f);
 	Handle<Texture> texture_handle;
 	Handle<Texture> normal_map_handle;   // tangent-space normal map (a data texture), INVALID: none
+	// Opacity mask: a data texture whose level 0 cuts holes into the surface -- texels whose `opacity_channel` byte is below
+	// ceil(opacity_threshold * 255) let rays through. INVALID: none. Channel -1: alpha when the file has four channels, red otherwise
+	// (known once the file is decoded: resolved_opacity_channel). opacity_from_albedo: set by cpu_config.alpha_masks, kept only if the file's alpha
+	// turns out to vary (AssetManager::wait_until_loaded drops it otherwise).
+	Handle<Texture> opacity_handle;
+	int   opacity_channel = -1;
+	float opacity_threshold = 0.5f;
+	bool  opacity_from_albedo = false;
 
 	Handle<Medium> medium_handle;
 	float          index_of_refraction = 1.33f;

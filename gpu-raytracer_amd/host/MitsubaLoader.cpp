@@ -133,7 +133,7 @@ const BsdfModel BSDF_MODELS[] = {
 	{ "thindielectric",  Material::Type::DIELECTRIC, nullptr,              Roughness::SMOOTH,         Optics::DIELECTRIC },
 	{ "roughdielectric", Material::Type::DIELECTRIC, nullptr,              Roughness::ALPHA,          Optics::DIELECTRIC },
 };
-const char * const BSDF_WRAPPERS[] = { "twosided", "mask", "bumpmap", "coating", "normalmap" };   // only what they wrap matters -- and a normalmap's map
+const char * const BSDF_WRAPPERS[] = { "twosided", "mask", "bumpmap", "coating", "normalmap" };   // only what they wrap matters -- and a normalmap's map and a mask's opacity bitmap
 
 // named indices of refraction (Mitsuba 0.5 documentation, page 58)
 const struct { const char * medium; float index; } NAMED_IOR[] = {
@@ -233,6 +233,25 @@ struct SceneFile {
 
 	// The tangent-space map of a <bsdf type="normalmap"> (Mitsuba 3: <texture name="normalmap" type="bitmap">); its `raw` flag is
 	// ignored, a normal map is always read raw. INVALID, with one warning per scene file, when it names no bitmap.
+	// The opacity of a <bsdf type="mask">: a <texture name="opacity" type="bitmap"> is recorded as a data texture (a binary cut-out at
+	// threshold 0.5 of the file's alpha channel, or of red when it has none); a float / rgb opacity, or none, leaves the wrapped BSDF as it always loaded.
+	Handle<Texture> opacity_map(const XMLNode & wrapper) {
+		const XMLNode * given = wrapper.get_child_by_name("opacity");
+		if (given && given->tag == "texture" && plugin(*given) == "bitmap" && given->get_child_by_name("filename")) {
+			Vector3 unused(1.0f);
+			return texture(given, unused, AssetManager::TextureKind::DATA);
+		}
+		return Handle<Texture> { INVALID };
+	}
+	bool warned_mask_on_light = false;
+	void set_opacity(Material & material, Handle<Texture> map, const XMLNode & where) {
+		if (material.type == Material::Type::LIGHT) {   // emitters are sampled whole (NEE): a mask on one is ignored
+			if (!warned_mask_on_light) complain(where, "opacity mask on an emitter: ignored");
+			warned_mask_on_light = true;
+			return;
+		}
+		material.opacity_handle = map; material.opacity_channel = -1; material.opacity_threshold = 0.5f; material.opacity_from_albedo = false;
+	}
 	bool warned_normalmap_without_bitmap = false;
 	Handle<Texture> normal_map(const XMLNode & wrapper) {
 		const XMLNode * given = wrapper.get_child_by_name("normalmap");
@@ -250,30 +269,41 @@ struct SceneFile {
 	Handle<Material> material(const XMLNode & owner) {
 		const XMLNode * bsdf = &owner;
 		if (owner.tag != "bsdf") {
-			if (const XMLNode * emitter = owner.get_child_by_tag("emitter")) return emitter_material(*emitter, "emitter");
+			if (const XMLNode * emitter = owner.get_child_by_tag("emitter")) {
+				const XMLNode * inline_bsdf = owner.get_child_by_tag("bsdf");
+				const XMLNode * opacity = inline_bsdf && plugin(*inline_bsdf) == "mask" ? inline_bsdf->get_child_by_name("opacity") : nullptr;
+				if (opacity && opacity->tag == "texture" && !warned_mask_on_light) {
+					complain(*inline_bsdf, "opacity mask on an emitter: ignored");
+					warned_mask_on_light = true;
+				}
+				return emitter_material(*emitter, "emitter");
+			}
 			if (const XMLNode * ref = owner.get_child_by_tag("ref")) return referenced_material(*ref);
 			bsdf = owner.get_child_by_tag("bsdf");
 			if (!bsdf) { complain(owner, "unable to parse BSDF"); return Handle<Material>::get_default(); }
 		}
 
-		// peel the wrappers; the name is the outermost id there is. A normalmap anywhere in the chain gives its map to what it wraps.
+		// peel the wrappers; the name is the outermost id there is. A normalmap anywhere in the chain gives its map to what it wraps, a mask its opacity bitmap.
 		const XMLAttribute * id = bsdf->get_attribute("id");
 		auto is_wrapper = [](std::string_view kind) { for (const char * w : BSDF_WRAPPERS) if (kind == w) return true; return false; };
 		Handle<Texture> normal_map_handle { INVALID };
+		Handle<Texture> opacity_handle { INVALID };   // the outermost mask with a bitmap wins
 		while (is_wrapper(plugin(*bsdf))) {
 			if (plugin(*bsdf) == "normalmap") {
 				Handle<Texture> map = normal_map(*bsdf);
 				if (map.handle != INVALID) normal_map_handle = map;
 			}
+			if (plugin(*bsdf) == "mask" && opacity_handle.handle == INVALID) opacity_handle = opacity_map(*bsdf);
 			const XMLNode * wrapped = bsdf->get_child_by_tag("bsdf");
 			if (!wrapped) {
 				const XMLNode * ref = bsdf->get_child_by_tag("ref");
 				if (!ref) return Handle<Material>::get_default();
 				Handle<Material> referenced = referenced_material(*ref);
-				if (normal_map_handle.handle == INVALID) return referenced;
+				if (normal_map_handle.handle == INVALID && opacity_handle.handle == INVALID) return referenced;
 				// a copy of the referenced material carries the map; the original, and whoever else refers to it, stays as it is
 				Material copy = scene.asset_manager.get_material(referenced);
-				copy.normal_map_handle = normal_map_handle;
+				if (normal_map_handle.handle != INVALID) copy.normal_map_handle = normal_map_handle;
+				if (opacity_handle.handle != INVALID) set_opacity(copy, opacity_handle, *bsdf);
 				if (id) copy.name = id->value;
 				return scene.asset_manager.add_material(std::move(copy));
 			}
@@ -290,6 +320,7 @@ struct SceneFile {
 		made.name = id ? id->value : "Material";
 		made.type = model->material;
 		made.normal_map_handle = normal_map_handle;
+		if (opacity_handle.handle != INVALID) set_opacity(made, opacity_handle, *bsdf);
 		if (model->colour) colour(*bsdf, model->colour, made.diffuse, made.texture_handle);
 		if (model->optics == Optics::DIELECTRIC) { // (before the roughness: an unknown named index of refraction ends the load)
 			float inside = index_of_refraction(*bsdf, "intIOR", 1.33f), outside = index_of_refraction(*bsdf, "extIOR", 1.0f);

@@ -169,6 +169,26 @@ void Pathtracer::update(float delta) {
 		std::vector<int32_t> normal_maps(scene_materials.size(), INVALID);
 		for (size_t i = 0; i < scene_materials.size(); i++) normal_maps[i] = scene_materials[i].normal_map_handle.handle;
 		if (ctx) check(rt_upload_material_normal_maps(ctx, normal_maps.data(), normal_maps.size()));
+		// opacity masks: built on the device from level 0 of the named data textures (rt_upload_materials has reset them to none).
+		// Only the CWBVH kernels test them: under another BVH type the scene renders without its cut-outs.
+		std::vector<int32_t> opacity_textures(scene_materials.size(), INVALID), opacity_channels(scene_materials.size(), 0);
+		std::vector<float> opacity_thresholds(scene_materials.size(), 0.5f);
+		bool any_opacity = false;
+		for (size_t i = 0; i < scene_materials.size(); i++) {
+			const Material & m = scene_materials[i];
+			if (m.opacity_handle.handle == INVALID || m.type == Material::Type::LIGHT) continue;
+			const Texture & t = scene.asset_manager.textures[m.opacity_handle.handle];
+			if (!t.bc1_blocks.empty()) continue;   // (a colour texture named through the API: not a mask the device can build)
+			opacity_textures[i] = m.opacity_handle.handle;
+			opacity_channels[i] = m.opacity_channel >= 0 ? m.opacity_channel : (t.file_alpha ? 3 : 0);
+			opacity_thresholds[i] = m.opacity_threshold;
+			any_opacity = true;
+		}
+		if (any_opacity && cpu_config.bvh_type != BVHType::BVH8) {
+			fprintf(stderr, "WARNING: opacity masks are only tested by the CWBVH kernels (bvh_type 8): rendering without them\n");
+			any_opacity = false;
+		}
+		if (ctx && any_opacity) check(rt_upload_material_opacity(ctx, opacity_textures.data(), opacity_channels.data(), opacity_thresholds.data(), opacity_textures.size()));
 
 		bool had_lights = scene.has_lights;
 		scene.check_materials();

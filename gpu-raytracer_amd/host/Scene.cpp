@@ -198,6 +198,7 @@ Handle<Texture> AssetManager::add_texture(const std::string & filename, const st
 	textures.emplace_back();
 	textures.back().name = name;
 	textures.back().data = kind == TextureKind::DATA;
+	textures.back().filename = filename;
 	if (assets_loaded) { load_texture(textures.back(), filename); return handle; }
 	texture_cache[{ filename, kind }] = handle;
 	pending_textures.push_back({ handle.handle, filename });
@@ -272,6 +273,30 @@ void AssetManager::wait_until_loaded() {
 	mesh_data_cache.clear();
 	texture_cache.clear();
 	assets_loaded = true;
+	resolve_alpha_masks();
+}
+
+// cpu_config.alpha_masks: every surface material with an albedo texture and no explicit mask takes its cut-outs from that file's alpha
+// channel -- the file a second time, as a data texture, so that the mask sees the stored bytes. Files without an alpha channel are not loaded again.
+void AssetManager::add_alpha_masks() {
+	for (Material & material : materials) {
+		if (material.type == Material::Type::LIGHT || material.texture_handle.handle == INVALID || material.opacity_handle.handle != INVALID) continue;
+		const std::string filename = textures[material.texture_handle.handle].filename, name = textures[material.texture_handle.handle].name;   // (copies: add_texture grows the table)
+		if (filename.empty() || !TextureLoader::file_has_alpha(filename)) continue;
+		material.opacity_handle = add_texture(filename, name, TextureKind::DATA);
+		material.opacity_channel = 3; material.opacity_threshold = 0.5f; material.opacity_from_albedo = true;
+	}
+}
+// ... and a mask that came that way stays only if the alpha of level 0 is not constant.
+void AssetManager::resolve_alpha_masks() {
+	for (Material & material : materials) {
+		if (!material.opacity_from_albedo || material.opacity_handle.handle == INVALID) continue;
+		const Texture & t = textures[material.opacity_handle.handle];
+		bool varies = false;
+		size_t count = size_t(t.width) * t.height;
+		for (size_t i = 1; i < count && 4 * i + 3 < t.texels.size() && !varies; i++) varies = t.texels[4 * i + 3] != t.texels[3];
+		if (!t.file_alpha || !varies) { material.opacity_handle.handle = INVALID; material.opacity_from_albedo = false; }
+	}
 }
 
 // ---- Sky --------------------------------------------------------------------------------------
@@ -343,6 +368,7 @@ Scene::Scene() : camera(Math::deg_to_rad(85.0f)) {
 		}
 	}
 	sky.load(cpu_config.sky_filename);
+	if (cpu_config.alpha_masks) asset_manager.add_alpha_masks();
 }
 
 Mesh & Scene::add_mesh(std::string name, Handle<MeshData> mesh_data_handle, Handle<Material> material_handle) {

@@ -45,6 +45,7 @@ struct AssetManager {
 
 	// Builds every pending BLAS (one job per mesh file on a thread pool) and decodes textures.
 	void wait_until_loaded();
+	void add_alpha_masks();   // cpu_config.alpha_masks: masks from the albedo files' alpha channels (before the assets are loaded)
 	void prepare_device_bvhs(BVHType type); // builds MeshData::device_bvh* for a non-BVH8 type, in parallel
 
 	MeshData & get_mesh_data(Handle<MeshData> h) { return mesh_datas[h.handle]; }
@@ -63,6 +64,7 @@ private:
 	struct PendingMesh    { int handle; std::string filename; FallbackLoader loader; std::string bvh_filename; };
 	struct PendingTexture { int handle; std::string filename; };
 	static void load_texture(Texture & texture, const std::string & filename);
+	void resolve_alpha_masks();
 	std::vector<PendingMesh>    pending_meshes;
 	std::vector<PendingTexture> pending_textures;
 	bool assets_loaded = false;
@@ -98,6 +100,9 @@ namespace MitsubaLoader { void load(const std::string & filename, Scene & scene)
 namespace TextureLoader {
 	// texture->data on entry: load as a data texture (no sRGB decode, no block compression; DDS files are refused)
 	bool load(const std::string & filename, Texture * texture);
+	// Whether the image file stores an alpha channel, by its header: PNG colour types 4 and 6, 32-bit BMP, TGA with 32-bit pixels or palette entries or
+	// 16-bit grey + alpha; JPEG, PNM and DDS never. False for a file that cannot be read.
+	bool file_has_alpha(const std::string & filename);
 	// One mip step with the box / lanczos / kaiser kernel of the reference (Src/Math/Mipmap.cpp)
 	void downsample(MipmapFilterType filter, int w_src, int h_src, int w_dst, int h_dst, const Vector4 * src, Vector4 * dst, std::vector<Vector4> & temp);
 }

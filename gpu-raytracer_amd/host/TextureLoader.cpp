@@ -263,9 +263,27 @@ unsigned char quantise(float v) { return (unsigned char)(Math::clamp(v * 255.0f,
 
 } // namespace
 
+static bool header_has_alpha(const std::vector<unsigned char> & file) {
+	if (file.size() >= 26 && memcmp(file.data(), "\x89PNG\r\n\x1a\n", 8) == 0) return file[25] == 4 || file[25] == 6;
+	if (file.size() >= 30 && file[0] == 'B' && file[1] == 'M') return (file[28] | (file[29] << 8)) == 32;
+	if (file.size() >= 2 && file[0] == 0xff && file[1] == 0xd8) return false;                         // JPEG
+	if (file.size() >= 2 && file[0] == 'P' && (file[1] == '5' || file[1] == '6')) return false;      // PNM
+	if (file.size() >= 4 && memcmp(file.data(), "DDS ", 4) == 0) return false;
+	if (file.size() >= 18) {   // TGA (no magic: what is left)
+		int indexed = file[1], image_type = file[2] & 7, bits = indexed ? file[7] : file[16];
+		return bits == 32 || (!indexed && image_type == 3 && bits == 16);
+	}
+	return false;
+}
+bool TextureLoader::file_has_alpha(const std::string & filename) {
+	std::vector<unsigned char> file;
+	return read_file(filename, file) && header_has_alpha(file);
+}
+
 bool TextureLoader::load(const std::string & filename, Texture * texture) {
 	std::vector<unsigned char> file, rgba8;
 	if (!read_file(filename, file)) return false;
+	texture->file_alpha = header_has_alpha(file);
 
 	int width = 0, height = 0;
 

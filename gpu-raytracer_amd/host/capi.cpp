@@ -74,6 +74,7 @@ int grt_config_set(const char * key, double value) {
 	else if (k == "static_slot_learning_rays")           cpu_config.static_slot_learning_rays = int(value);
 	else if (k == "static_slot_learning_viewpoint")      cpu_config.static_slot_learning_viewpoint = int(value);
 	else if (k == "skip_behind_hit")                     cpu_config.skip_behind_hit = value != 0;
+	else if (k == "alpha_masks")                         cpu_config.alpha_masks = value != 0 ? 1 : 0;
 	else if (k == "sky_sampling") {   // 0 (off) or (0, 1]: the sky's share of the light samples (rt_set_sky_sampling)
 		if (!(value == 0.0 || (value > 0.0 && value <= 1.0))) { g_host_error = "sky_sampling must be 0 (off) or in (0, 1]"; return -1; }
 		cpu_config.sky_sampling = float(value);
@@ -96,6 +97,7 @@ double grt_config_get(const char * key) {
 	if (k == "enable_svgf")    return gpu_config.enable_svgf;
 	if (k == "skip_behind_hit") return cpu_config.skip_behind_hit;
 	if (k == "sky_sampling")   return cpu_config.sky_sampling;
+	if (k == "alpha_masks")    return cpu_config.alpha_masks;
 	return -1.0;
 }
 
@@ -178,6 +180,30 @@ int grt_scene_set_material_normal_map(void * scene, int index, int texture) {
 	if (index < 0 || index >= int(s->asset_manager.materials.size())) { g_host_error = "grt_scene_set_material_normal_map: material index out of range"; return -1; }
 	if (texture < -1 || texture >= int(s->asset_manager.textures.size())) { g_host_error = "grt_scene_set_material_normal_map: texture index out of range"; return -1; }
 	s->asset_manager.materials[index].normal_map_handle.handle = texture;
+	return 0;
+}
+// Opacity masks, kept out of grt_scene_describe like the normal maps. The getter decodes the scene's textures first: which channel a
+// mask reads, and whether cpu_config.alpha_masks found a varying alpha, is only known then. out: { channel, threshold } (optional).
+int grt_scene_material_opacity_map(void * scene, int index, int * out_channel, float * out_threshold) {
+	GRT_TRY
+		Scene * s = (Scene *)scene;
+		if (index < 0 || index >= int(s->asset_manager.materials.size())) { g_host_error = "grt_scene_material_opacity_map: material index out of range"; return -2; }
+		s->asset_manager.wait_until_loaded();
+		const Material & m = s->asset_manager.materials[index];
+		if (m.opacity_handle.handle == INVALID) return INVALID;
+		if (out_channel) *out_channel = m.opacity_channel >= 0 ? m.opacity_channel : (s->asset_manager.textures[m.opacity_handle.handle].file_alpha ? 3 : 0);
+		if (out_threshold) *out_threshold = m.opacity_threshold;
+		return m.opacity_handle.handle;
+	GRT_CATCH(-2)
+}
+int grt_scene_set_material_opacity_map(void * scene, int index, int texture, int channel, float threshold) {
+	Scene * s = (Scene *)scene;
+	if (index < 0 || index >= int(s->asset_manager.materials.size())) { g_host_error = "grt_scene_set_material_opacity_map: material index out of range"; return -1; }
+	if (texture < -1 || texture >= int(s->asset_manager.textures.size())) { g_host_error = "grt_scene_set_material_opacity_map: texture index out of range"; return -1; }
+	if (channel < 0 || channel > 3) { g_host_error = "grt_scene_set_material_opacity_map: channel must be 0..3 (r, g, b, a)"; return -1; }
+	if (!(threshold > 0.0f && threshold <= 1.0f)) { g_host_error = "grt_scene_set_material_opacity_map: threshold must be in (0, 1]"; return -1; }
+	Material & m = s->asset_manager.materials[index];
+	m.opacity_handle.handle = texture; m.opacity_channel = channel; m.opacity_threshold = threshold; m.opacity_from_albedo = false;
 	return 0;
 }
 // Adds a texture file to the scene; data != 0: a data texture (normal map, see Texture::data). Textures reach the device when a

@@ -155,8 +155,9 @@ const char * rt_version(void);
  *  14  rt_upload_material_normal_maps, rt_perturb_normals (additions only; tangent-space normal maps)
  *  15  rt_sample_lights (addition); rt_upload_lights refuses tables on which the light search would not end (see there)
  *  16  rt_sort_rays (addition)
+ *  17  rt_upload_material_opacity, rt_read_material_opacity (additions only; alpha-tested opacity masks, off until a mask is uploaded)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
-#define RT_ABI_VERSION 16
+#define RT_ABI_VERSION 17
 int rt_abi_version(void);
 
 /* ---- scene upload ------------------------------------------------------------------- */
@@ -276,6 +277,21 @@ int rt_upload_materials(rt_context * ctx, const uint8_t * types, const void * ma
  * texture of the last rt_upload_textures; otherwise RT_ERROR_INVALID_ARG and the table stays as it was. rt_upload_materials
  * and rt_upload_textures reset the table to none. Only materials of the four surface types use their map.                                       */
 int rt_upload_material_normal_maps(rt_context * ctx, const int32_t * texture_ids, size_t count);
+/* Alpha-tested opacity masks: binary cut-outs tested inside the CWBVH traversal, for closest-hit and shadow rays alike.
+ * texture_ids[i] is the texture whose level 0 masks material i of the last rt_upload_materials, or -1 (none); channels[i] in 0..3
+ * (r, g, b, a) and thresholds[i] in (0, 1] say which texels are opaque: those whose byte of that channel is >= ceil(threshold * 255).
+ * The bits (one per texel) are built on the device by this call, which drains the context first. RT_ERROR_INVALID_ARG, with the
+ * tables left as they were, when count differs from that upload's material count, an id is out of range or names a texture that is
+ * not RT_TEXTURE_RGBA8, a channel is outside 0..3 or a threshold is NaN or outside (0, 1]. NULL texture_ids clears the masks;
+ * rt_upload_materials and rt_upload_textures reset them to none. A mask on a light material is ignored. A ray / triangle candidate
+ * is accepted only where the mask of its instance's material is 1 at the texel that holds (s, t) = uv_0 + u uv_edge_1 + v uv_edge_2,
+ * wrapped; shading and light sampling never look at masks. CWBVH kernels only: with rt_set_bvh_type 2 or 4 and a mask uploaded every
+ * render / trace entry point returns RT_ERROR_INVALID_ARG before any launch.                                                         */
+int rt_upload_material_opacity(rt_context * ctx, const int32_t * texture_ids, const int32_t * channels, const float * thresholds, size_t count);
+/* The packed bits of material `material`'s mask: bit y * width + x of the texel (x, y) in word (y * width + x) >> 5, bit & 31, no row
+ * padding, unused bits of the last word 0. out_width / out_height (optional) are set whenever the material has a mask.
+ * RT_ERROR_INVALID_ARG for a material without a mask or when capacity_words < ceil(width * height / 32).                             */
+int rt_read_material_opacity(rt_context * ctx, int material, uint32_t * words, size_t capacity_words, int32_t * out_width, int32_t * out_height);
 /* Replaces `media` (Pathtracer.cpp:681-697): 32 B each {sigma_a.xyz, g, sigma_s.xyz, pad}. */
 int rt_upload_media(rt_context * ctx, const void * media, size_t count);
 /* Replaces `textures` (Integrator.cpp:33-98). */
@@ -545,7 +561,7 @@ int rt_trace_shadow_rays(rt_context * ctx, const float * ox, const float * oy, c
  * max_distance) each carry illumination (1, 0, 0) for pixel i: shadow_light[i] is what the launch added, 0 occluded, 1 not
  * (2 or more: the ray was dealt twice). stats10: NULL for the frame's kernel, else the counting kernel runs and its 10 counters
  * ({nodes, triangles, transformed, identity instance entries, rays} x {closest, shadow}) are returned. info: 4 ints {kernel (0 general,
- * 1 flat, 2 flat skipping, 3 counting), waves of its persistent grid, RT_NARROW_MAX_RAYS, RT_MIXED_MAX_RAYS}. Leaves no state a frame reads. */
+ * 1 flat, 2 flat skipping, 3 counting; with opacity masks uploaded 4 general, 5 flat, 6 flat skipping, 7 counting: their _mask instances), waves of its persistent grid, RT_NARROW_MAX_RAYS, RT_MIXED_MAX_RAYS}. Leaves no state a frame reads. */
 int rt_trace_stream_rays(rt_context * ctx, int iteration,
                          const float * ox, const float * oy, const float * oz, const float * dx, const float * dy, const float * dz,
                          size_t closest_count, uint32_t * hits,
