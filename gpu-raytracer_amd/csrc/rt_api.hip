@@ -1,13 +1,11 @@
-// rt_api.hip -- implementation of the C ABI in include/gpu_raytracer_amd.h.
-//
+// rt_api.hip -- implementation of the C ABI in include/gpu_raytracer_amd.h, except the kernel-level entry points
+// (rt_probes.hip) and the frame exchange of the tile split (rt_exchange.hip); rt_context.h is what the three share.
 // One rt_context owns one HIP device: a stream, every device buffer, and the RtParams block
 // handed to the kernels by value. It plays the role of the reference's Device/ layer plus the
 // device half of Integrator/Pathtracer (buffer ownership, `buffer_sizes` handling, the
 // wavefront launch loop of Pathtracer::render, Pathtracer.cpp:738-855).
 #include "rt_tlas_build.h"
-#include <dlfcn.h>
-#include "rt_types.h"
-#include "rt_tlas_build.h"
+#include "rt_context.h"
 
 #include <algorithm>
 #include <cmath>
@@ -15,10 +13,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
-#include <memory>
-#include <string>
-#include <vector>
 
 static thread_local std::string g_global_error;
 
@@ -40,25 +34,11 @@ static void warn_if_streams_share_queues(int streams_needed) {
 	                "the merged scheduler (the default) needs two streams\n", streams_needed, value ? value : "(unset, 4)", queues);
 }
 
-// Everything one sample per pixel owns while it is in flight. Up to RT_MAX_SAMPLE_SLOTS samples
-// are rendered concurrently (rt_set_samples_in_flight): consecutive rt_render_sample calls take the
-// slots round-robin, each on its own stream, and only the accumulate step is ordered between them.
-// Why: a wavefront pass is a chain of ~40 launches whose deep bounces are too small to fill 256 CUs
-// and whose persistent trace launches each end in a tail; a second sample's kernels fill those holes.
-#define RT_MAX_SAMPLE_SLOTS 8
 #define RT_MAX_BATCH_SAMPLES 16
 #define RT_RAY_CURSOR_BYTES (RT_MAX_BOUNCES * 2 * sizeof(int))   // RtParams::ray_cursors of a slot: [RT_MAX_BOUNCES][2 (closest hit, shadow)] ints
 
 // SVGF g-buffers, bytes per pixel: normal + depth (float4), mesh + triangle id (int2), previous screen position (float2)
 static const size_t gbuffer_pixel_bytes[3] = { 16, 8, 8 };
-
-// The queues of one wavefront, `capacity` entries each: two trace queues (this bounce's and the next), one per material,
-// one of shadow rays. Each scheduler owns one set (SampleSlot, PathStream); queues_allocate / queues_free handle a set.
-struct WavefrontQueues {
-	RtTraceBuffer trace[2] = { }; RtMaterialBuffer material[4] = { }; RtShadowBuffer shadow = { };
-	size_t capacity = 0;
-	bool allocated = false;
-};
 
 // Every device array of a queue set as (pointer, bytes per entry), in declaration order, which is the allocation order.
 template<typename Visit> static void for_each_queue_array(WavefrontQueues & q, Visit && visit) {
@@ -79,206 +59,7 @@ static void use_queues(RtParams & p, const WavefrontQueues & q) {
 	memcpy(p.trace, q.trace, sizeof(p.trace)); memcpy(p.material, q.material, sizeof(p.material)); p.shadow = q.shadow;
 }
 
-struct SampleSlot {
-	bool created = false;
-	hipStream_t stream = nullptr;      // the sample's launch chain
-	hipStream_t side   = nullptr;      // shadow rays of bounce b, concurrent with the closest-hit trace of bounce b+1
-	hipEvent_t ev_shaded = nullptr, ev_shadowed = nullptr, ev_done = nullptr, ev_frame_start = nullptr, ev_frame_end = nullptr;
-	WavefrontQueues queues;
-	RtBufferSizes * sizes = nullptr;
-	int * ray_cursors = nullptr;
-	void * spill[2] = { nullptr, nullptr };  // traversal stack spill of the closest-hit / shadow launch
-	int * counter_totals = nullptr;          // 6 x RT_MAX_BOUNCES ints accumulated over batches
-	RtBufferSizes * pinned_counters = nullptr;
-	void * aov_framebuffer[RT_AOV_COUNT] = { };  // slots 1..: per-sample frame buffers (slot 0 uses ctx->aov_buffers[i][0])
-	int aov_samples = 1;                         // samples per batch the frame buffers of this slot are sized for
-	// SVGF g-buffers (normal+depth, mesh+triangle id, previous screen position) are written by the
-	// bounce-0 kernels of a frame and read by its filter stage: one set per slot lets frame n+1 be
-	// traced while frame n is filtered. Pixels that miss all geometry keep the value of the last
-	// frame that hit something (the reference never clears them), so a frame starts from a copy of
-	// its predecessor's set, taken as soon as that frame's bounce-0 shading is done (ev_gbuffers).
-	void * gbuffers[3] = { };                    // slots 1..; slot 0 uses ctx->svgf_buffers[0..2]
-	hipEvent_t ev_gbuffers = nullptr;
-};
-
-// Per-frame scene data (the TLAS and the five per-instance tables, rebuilt by Integrator::build_tlas for
-// every frame of an animated scene) lives in a ring of versions: an upload fills the next version
-// through pinned staging with an asynchronous copy, the kernels of later samples get its address (the
-// parameter block is passed by value), samples already in flight keep reading theirs. No upload of this
-// kind drains the pipeline; a version is only waited for when the ring wraps around onto a sample
-// that still uses it.
-#define RT_SCENE_VERSIONS 12
-struct SceneRing {
-	void * device[RT_SCENE_VERSIONS] = { };
-	void * pinned[RT_SCENE_VERSIONS] = { };
-	hipEvent_t copied[RT_SCENE_VERSIONS] = { };
-	size_t capacity = 0;   // bytes allocated per version (grows only)
-	size_t bytes = 0;      // bytes of the current version
-	int current = -1;
-	// Sample slots that have submitted work reading a version since it was last written. (A slot used to remember only the
-	// version of its LAST submission: with the host several frames ahead of the device, an older submission still queued
-	// on the same slot lost its claim and the ring wrapped around onto the version it was about to read -- found with 1 500
-	// moving instances and 48 frames, tools/animation_bench.py: a TLAS overwritten under a running traversal.)
-	unsigned users[RT_SCENE_VERSIONS] = { };
-	hipEvent_t last_use[RT_SCENE_VERSIONS][RT_MAX_SAMPLE_SLOTS] = { }; // end of the slot's latest submission that reads the version
-};
-
-// ---- merged wavefront (RT_SCHEDULER_MERGED; the idea is described at RtStreamSlot in rt_types.h) -------------------
-// Host side: ONE stream, one set of queues sized for `capacity` rays. A submission (one rt_render_samples call) gets a
-// run of sample slots, generates its primary rays into the current trace queue and advances the wavefront by one
-// iteration; it is complete -- accumulated into the shared accumulators, in submission order -- after the iteration in
-// which it reaches its last bounce. What bounds the queues: every path in flight occupies at most one entry of a
-// queue, paths only die, so (wavefront size reported by an earlier iteration) + (rays generated since) bounds the
-// entries any queue can receive; the host stays RT_STREAM_RUN_AHEAD iterations ahead of the device at most, reads the
-// reported sizes from pinned memory without blocking, and runs iterations without new samples while a new
-// submission would not fit.
-// Small submissions (the tiles of one rank of a multi-GPU split: 1/8 of a frame) would make small iterations again --
-// launches that do not fill the machine, fixed costs per iteration that no longer disappear behind the rays. When the
-// application pipelines frames (rt_set_frame_pipelining) a submission therefore generates its rays at once but the
-// iteration is only enqueued when RT_STREAM_BATCH_PATHS paths have been generated for it (or RT_STREAM_MAX_BATCH
-// submissions), so the iterations of a 1/8 split carry 8 frames and are as large as those of a whole frame. Anything that
-// needs progress -- rt_advance, every call that flushes, a change of camera -- enqueues the iteration with what is there.
-#define RT_STREAM_BATCH_PATHS     (1920 * 1080 * 4)
-#define RT_STREAM_MAX_BATCH       8
-#define RT_STREAM_PROGRESS_RING   64
-#define RT_STREAM_RUN_AHEAD       4
-#define RT_STREAM_TABLE_SNAPSHOTS 8
-#define RT_STREAM_HISTORY_ROWS    4096
-#define RT_STREAM_STATS_ROW       (RT_STAT_KINDS * RT_MAX_BOUNCES)   // ints per submission
-
-struct StreamSubmission {
-	int first_sample, sample_count, slot_base, ring, birth, last, paths;
-	int range_offset, range_count, tile_pixels, tile_first, tile_stride;
-};
-
-struct PathStream {
-	bool created = false;
-	hipStream_t stream = nullptr;
-	hipEvent_t ev_idle = nullptr;         // after the last completion enqueued so far: what main-stream consumers wait for
-	WavefrontQueues queues;
-	RtStreamControl * control = nullptr;
-	RtStreamTable * table_device = nullptr;
-	RtStreamTable table_host;             // what the device table will hold once the copies enqueued so far have run
-	RtStreamTable * table_staging = nullptr; hipEvent_t table_copied[RT_STREAM_TABLE_SNAPSHOTS] = { }; int table_next = 0;
-	void * spill = nullptr;
-	void * aov_framebuffer[RT_AOV_COUNT] = { }; int frame_slots = 0;   // per-sample frames, one per sample slot
-	void * gbuffers[3] = { };             // SVGF: one g-buffer set (float4, int2, float2 per pixel) per sample slot
-	int last_gbuffer_slot = -1;           // the set of the frame submitted last, if that was a frame of this wavefront
-	bool slot_used[RT_STREAM_SAMPLE_SLOTS] = { };
-	int next_slot = 0, next_ring = 0;
-	int iteration = 0;                    // the next iteration to enqueue
-	int base_iteration = 0;               // nothing generated before it is still in flight
-	std::deque<StreamSubmission> in_flight;
-	int pending = 0; long long pending_paths = 0;   // the newest submissions: rays generated, iteration not enqueued yet
-	// ... their slot-table entries and statistics rows reach the device ONCE, with the iteration that first needs them (one copy and the advance launch instead
-	// of a copy and a fill per submission: a rank of an 8-GPU split spent 0.1 ms of its 5.4 ms burst on five such pairs, profiles/r05_rank_timeline.txt)
-	bool table_dirty = false; int reset_ring_first = 0, reset_ring_count = 0;
-	int * progress = nullptr;             // pinned [RING][2] = { iteration, wavefront size }, written by kernel_stream_advance
-	hipEvent_t iteration_done[RT_STREAM_PROGRESS_RING] = { };
-	int generated[RT_STREAM_PROGRESS_RING] = { };
-	int known_iteration = -1; long long known_size = 0;
-	unsigned long long submissions_completed = 0;
-	int * stats_host = nullptr;           // pinned [RT_STREAM_SUBMISSIONS][RT_STREAM_STATS_ROW]
-	hipEvent_t ev_begin[RT_STREAM_SUBMISSIONS] = { }, ev_end[RT_STREAM_SUBMISSIONS] = { };
-	int last_completed_ring = -1;
-};
-
-struct rt_context {
-	int device = 0;
-	hipStream_t stream = nullptr;      // "main": uploads, read-backs, pack/unpack, kernel-level entry points
-	hipEvent_t ev_main = nullptr, ev_interop = nullptr;
-	std::string error;
-
-	SampleSlot slots[RT_MAX_SAMPLE_SLOTS];
-	// (Two such wavefronts taking the submissions in turns, their traversal launches serialised by an event chain so that
-	// one pipeline's sort / shade kernels would run beside the other's traversal, were built and measured: 3.23 ms per step
-	// against 3.02 ms with one -- the persistent traversal launch holds every wave slot of the machine until its queue is
-	// drained, nothing can start beside it. Removed; profiles/r02_two_pipelines_*.)
-	PathStream path_stream;
-	unsigned long long * stream_history = nullptr; int stream_history_rows = 0;   // pinned [ROWS][10]: trace statistics after each traversal launch
-	int scheduler = RT_SCHEDULER_MERGED;
-	bool last_render_merged = false;
-	bool defer_filter = false;         // rt_render_sample_unfiltered: an SVGF frame stops before its filter stage (tile split)
-	bool frame_pipelining = false;     // rt_pack_pixels / rt_unpack_pixels follow the completed submissions only (rt_set_frame_pipelining)
-	long long stream_batch_paths = 0;  // paths the submissions of one iteration may bring (rt_set_stream_batch); 0: RT_STREAM_BATCH_PATHS
-	int samples_in_flight = 3;
-	unsigned render_counter = 0;
-	int last_slot = -1;
-
-	RtParams params;               // zero-initialised in rt_create
-	std::vector<void *> owned;     // every hipMalloc'd pointer, freed in rt_destroy
-
-	// named allocations that get replaced on re-upload
-	void * triangles = nullptr, * triangle_positions = nullptr, * bvh8_nodes = nullptr, * bvh2_nodes = nullptr, * bvh4_nodes = nullptr;
-	size_t tlas_node_bytes = 80;        // what the current TLAS version was uploaded as (80 CWBVH, 32 binary, 128 4-wide)
-	int lowest_blas_root = 0x7fffffff;  // over the instances uploaded last: the node slots below it are free for the TLAS copy of the merged wavefront
-	unsigned long long tlas_version = 0, tlas_version_in_nodes = ~0ull;   // the merged wavefront traces a copy of the TLAS inside the BLAS node array (stream_sync_tlas)
-	bool expand_bc1 = true;   // rt_set_texture_expansion: BC1 textures are decoded once, at upload (rt_types.h: RT_TEXTURE_BC1_EXPANDED)
-	size_t texture_bytes = 0; // what rt_upload_textures holds on the device
-	std::vector<float> build_boxes; size_t build_boxes_first = 0;   // rt_set_build_boxes: consumed by the next rt_build_geometry
-	size_t bvh4_node_count = 0;
-	size_t bvh8_node_count = 0, bvh2_node_count = 0, triangle_count = 0;
-	size_t mesh_count = 0;
-	SceneRing tlas_ring, instance_ring, light_ring;
-	int * device_tlas_order = nullptr, * device_tlas_node_count = nullptr; // current TLAS built by rt_build_tlas (else null)
-	hipEvent_t ev_scene = nullptr;  // the last asynchronous scene upload on the main stream
-	void * material_types = nullptr, * materials = nullptr, * media = nullptr;
-	size_t medium_count = 0;                   // entries of rt_upload_media's table (rt_sort_rays checks medium ids against it)
-	bool has_material[4] = { false, false, false, false };
-	std::vector<uint8_t> material_type_list;   // what rt_upload_materials uploaded (rt_upload_material_normal_maps checks against it)
-	void * material_normal_maps = nullptr;     // int per material (rt_upload_material_normal_maps)
-	std::vector<int> texture_formats;          // the device format of every texture of rt_upload_textures
-	std::vector<RtTexture> texture_records;    // ... and its record (device pointer, size), as uploaded
-	// opacity masks (rt_upload_material_opacity): the two device tables and the bits of all masks in one allocation; host copies for rt_read_material_opacity
-	void * material_opacity = nullptr, * opacity_masks = nullptr, * opacity_bits = nullptr;
-	std::vector<int> material_opacity_list; std::vector<RtOpacityMask> opacity_mask_list;
-	bool has_lights = false;
-	void * texture_table = nullptr; std::vector<void *> texture_data;
-	void * pmj = nullptr, * blue_noise = nullptr;
-	void * sky = nullptr;
-	// sky importance sampling (rt_set_sky_sampling; kernels_sky.hip): the tables are built at the first render that wants them after rt_set_sky
-	float sky_sampling = 0.0f;               // 0: off (the reference's estimator); (0, 1]: the sky's share of the light samples when emitters exist
-	void * sky_tables = nullptr;             // floats: marginal CDF [H], conditional CDFs [H * W], cell pdfs [H * W]
-	void * sky_table_sums = nullptr;         // doubles: row totals [H], total [1]
-	bool sky_tables_ready = false;
-	double sky_total = 0.0;                  // the sum of the cell weights (0: a black sky, sampling stays inactive; not finite: an error)
-	void * luts[6] = { }; bool luts_ready = false;
-	int bvh_width = 8;
-
-	// frame resources
-	void * aov_buffers[RT_AOV_COUNT][2] = { };
-	void * final_image = nullptr;
-	void * svgf_buffers[16] = { }; bool svgf_allocated = false;   // [15]: RtParams::svgf_young_pixels
-	size_t frame_pixels = 0; // pitch * height
-
-	// frame exchange of the tile split (rt_comm_*): this context's rank in a group of `world` contexts, each on its own GPU
-	// (RCCL communicator) or, for tests on one GPU, several in one process (peer copies)
-	struct FrameExchange {
-		int rank = 0, world = 1;
-		void * comm = nullptr;                       // ncclComm_t
-		std::vector<rt_context *> peers;             // in-process transport: all contexts of the group, by rank
-		float4 * packed = nullptr, * gathered = nullptr; size_t packed_pixels = 0;   // per pixel `channels` float4
-		hipEvent_t ev_packed = nullptr, ev_copied = nullptr;
-	} exchange;
-
-	int * explicit_retired = nullptr;
-	int * pixel_query_out = nullptr;   // device { mesh_id, triangle_id }
-	int batch_size_request = 0;              // 0 = whole frame (288 GB of HBM: no reason to cut a frame into pieces)
-	int pixel_offset = 0, pixel_count = -1;  // -1 = whole frame
-
-	rt_counters last_counters;
-	bool profiling = false;          // mode 1: per-stage events, one sample at a time
-	bool launch_timing = false;      // mode 2: events around every traversal launch, concurrency untouched
-	bool launch_timing_all = false;  // mode 3: ... and around every other launch of the merged wavefront
-	bool time_this_sample = false;
-	std::vector<hipEvent_t> span_events; std::vector<int> span_kinds; size_t span_used = 0; // mode 2: [begin, end] pairs
-	bool trace_statistics = false;
-	unsigned long long * trace_stats = nullptr;    // device, 10 x u64
-	unsigned long long host_trace_stats[10] = { };
-	std::vector<hipEvent_t> stage_events; std::vector<int> stage_kinds; size_t stage_used = 0;
-};
-
-static int fail(rt_context * ctx, int status, const char * fmt, ...) {
+int fail(rt_context * ctx, int status, const char * fmt, ...) {
 	char buffer[512];
 	va_list args; va_start(args, fmt); vsnprintf(buffer, sizeof(buffer), fmt, args); va_end(args);
 	if (ctx) ctx->error = buffer;
@@ -286,16 +67,13 @@ static int fail(rt_context * ctx, int status, const char * fmt, ...) {
 	return status;
 }
 
-#define RT_HIP(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(ctx, RT_ERROR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
-#define RT_REQUIRE(ctx, cond, msg) do { if (!(cond)) return fail(ctx, RT_ERROR_INVALID_ARG, "%s", msg); } while (0)
-
-static int device_alloc(rt_context * ctx, void ** out, size_t bytes) {
+int device_alloc(rt_context * ctx, void ** out, size_t bytes) {
 	if (bytes == 0) bytes = 16;
 	RT_HIP(ctx, hipMalloc(out, bytes));
 	ctx->owned.push_back(*out);
 	return RT_OK;
 }
-static void device_free(rt_context * ctx, void * p) {
+void device_free(rt_context * ctx, void * p) {
 	if (!p) return;
 	for (size_t i = 0; i < ctx->owned.size(); i++) if (ctx->owned[i] == p) { ctx->owned[i] = ctx->owned.back(); ctx->owned.pop_back(); break; }
 	(void)hipFree(p);
@@ -313,7 +91,6 @@ static void queues_free(rt_context * ctx, WavefrontQueues & q) {
 	q.allocated = false;
 }
 // (re)allocate + synchronous upload
-static hipError_t quiesce(rt_context * ctx);
 static int upload(rt_context * ctx, void ** slot, const void * src, size_t bytes) {
 	RT_HIP(ctx, quiesce(ctx)); // samples in flight may still read the old buffer
 	device_free(ctx, *slot);
@@ -330,7 +107,7 @@ static hipError_t stream_flush(rt_context * ctx);
 static int stream_launch_pending(rt_context * ctx);
 static void stream_destroy(rt_context * ctx);
 static void stream_release_frames(rt_context * ctx);
-static hipError_t quiesce(rt_context * ctx) {
+hipError_t quiesce(rt_context * ctx) {
 	if (ctx->path_stream.created) {
 		hipError_t e = stream_flush(ctx);                            if (e != hipSuccess) return e;
 		e = hipStreamSynchronize(ctx->path_stream.stream);           if (e != hipSuccess) return e;
@@ -343,7 +120,7 @@ static hipError_t quiesce(rt_context * ctx) {
 }
 
 // Main-stream work that reads or writes frame results is ordered after every sample already submitted.
-static hipError_t main_waits_for_samples(rt_context * ctx) {
+hipError_t main_waits_for_samples(rt_context * ctx) {
 	if (ctx->path_stream.created) {
 		if (!ctx->frame_pipelining) { hipError_t e = stream_flush(ctx); if (e != hipSuccess) return e; }
 		hipError_t e = hipStreamWaitEvent(ctx->stream, ctx->path_stream.ev_idle, 0); if (e != hipSuccess) return e;
@@ -390,7 +167,7 @@ static int ensure_slot(rt_context * ctx, int index) {
 }
 
 // The kernels get RtParams by value: the context's block with one slot's per-sample pointers patched in.
-static RtParams slot_params(const rt_context * ctx, const SampleSlot & slot, int index) {
+RtParams slot_params(const rt_context * ctx, const SampleSlot & slot, int index) {
 	RtParams p = ctx->params;
 	use_queues(p, slot.queues);
 	p.sizes = slot.sizes; p.ray_cursors = slot.ray_cursors; p.stack_spill = (uint2 *)slot.spill[0];
@@ -468,10 +245,7 @@ static bool bvh_nodes_present(const rt_context * ctx) {
 	return ctx->bvh_width == 8 ? p.bvh8_nodes != nullptr : (ctx->bvh_width == 4 ? p.bvh4_nodes != nullptr : p.bvh2_nodes != nullptr);
 }
 
-// What a render or trace entry point needs uploaded before it launches anything. NEED_SCENE reports missing geometry
-// and missing instances apart; NEED_SCENE_JOINT (the explicit-ray entry points) reports them as one.
-enum { NEED_SCENE = 1, NEED_SCENE_JOINT = 2, NEED_MATERIALS = 4, NEED_RNG = 8, NEED_SKY = 16, NEED_FRAME = 32 };
-static int check_ready(rt_context * ctx, const char * caller, int needs) {
+int check_ready(rt_context * ctx, const char * caller, int needs) {
 	const RtParams & p = ctx->params;
 	if ((needs & (NEED_SCENE | NEED_SCENE_JOINT)) && p.opacity_active && ctx->bvh_width != 8)
 		return fail(ctx, RT_ERROR_INVALID_ARG, "%s: opacity masks are uploaded (rt_upload_material_opacity) and only the CWBVH kernels test them; rt_set_bvh_type is %d", caller, ctx->bvh_width);
@@ -1283,8 +1057,6 @@ int rt_upload_lights(rt_context * ctx,
 	return RT_OK;
 }
 
-static int ensure_luts(rt_context * ctx); // needs the RNG tables
-
 int rt_upload_rng(rt_context * ctx, const float * pmj_samples, const uint8_t * blue_noise) {
 	RT_REQUIRE(ctx, ctx && pmj_samples && blue_noise, "rt_upload_rng: NULL argument");
 	(void)hipSetDevice(ctx->device);
@@ -1312,7 +1084,7 @@ int rt_set_sky(rt_context * ctx, const float * rgba, int width, int height, floa
 }
 
 // The sky's sampling tables (kernels_sky.hip), built once per rt_set_sky; synchronous (it reads the total back).
-static int sky_tables_build(rt_context * ctx, const char * caller) {
+int sky_tables_build(rt_context * ctx, const char * caller) {
 	RtParams & p = ctx->params;
 	if (!ctx->sky_tables_ready) {
 		const size_t w = size_t(p.sky_width), h = size_t(p.sky_height);
@@ -1334,7 +1106,7 @@ static int sky_tables_build(rt_context * ctx, const char * caller) {
 
 // Before a render: the sky's share of the light samples for this render (RtParams::sky_nee_share), building the tables if sampling is wanted.
 // 0 -- sampling off, NEE off, or a sky without weight -- keeps every kernel on the reference's estimator.
-static int sky_sampling_prepare(rt_context * ctx, const char * caller) {
+int sky_sampling_prepare(rt_context * ctx, const char * caller) {
 	RtParams & p = ctx->params;
 	float share = 0.0f;
 	if (ctx->sky_sampling > 0.0f && p.config.enable_next_event_estimation) {
@@ -1357,7 +1129,7 @@ static size_t wanted_batch_size(const rt_context * ctx) {
 	return n;
 }
 
-static int ensure_queues(rt_context * ctx, int slot_index = 0, size_t pixels = 0) {
+int ensure_queues(rt_context * ctx, int slot_index, size_t pixels) {
 	SampleSlot & slot = ctx->slots[slot_index];
 	size_t n = pixels > 0 ? pixels : wanted_batch_size(ctx); // entries: pixels of a batch x samples per batch
 	if (slot.queues.allocated && slot.queues.capacity >= n) return RT_OK;
@@ -1636,215 +1408,6 @@ int rt_read_svgf_state(rt_context * ctx, int which, void * dst) {
 	return RT_OK;
 }
 
-// ---- frame exchange of the tile split without Python ----------------------------------------------------
-// One communicator per context. RCCL is bound at RUN TIME (dlopen, RTLD_LOCAL): a process that also hosts PyTorch already
-// has torch's own copy of librccl mapped, and a link-time dependency would make every user of this library load a
-// collective library most of them never call. Contexts that share a GPU (tests; RCCL refuses a device twice in one
-// communicator) exchange by stream-ordered peer copies instead -- the same pack / unpack kernels either way.
-extern "C++" {
-namespace {
-struct RcclUniqueId { char internal[128]; };            // ncclUniqueId (rccl.h)
-enum { RCCL_FLOAT32 = 7 };                              // ncclFloat32
-struct RcclApi {
-	void * handle = nullptr;
-	int (*get_unique_id)(RcclUniqueId *) = nullptr;
-	int (*comm_init_rank)(void **, int, RcclUniqueId, int) = nullptr;
-	int (*comm_init_all)(void **, int, const int *) = nullptr;
-	int (*comm_destroy)(void *) = nullptr;
-	int (*all_gather)(const void *, void *, size_t, int, void *, hipStream_t) = nullptr;
-	int (*group_start)() = nullptr; int (*group_end)() = nullptr;
-	const char * (*error_string)(int) = nullptr;
-};
-RcclApi * rccl_api(std::string & why) {
-	static RcclApi api; static bool tried = false; static std::string failure;
-	if (!tried) {
-		tried = true;
-		// GRT_COLLECTIVE_LIBRARY: another library with RCCL's entry points, tried first. tests/support/libloopback_ccl.so uses it to run this very code with two
-		// ranks on a box with one GPU (RCCL refuses a device twice); a deployment could name a site's own RCCL build the same way.
-		if (const char * named = getenv("GRT_COLLECTIVE_LIBRARY")) { if (named[0] && !(api.handle = dlopen(named, RTLD_NOW | RTLD_LOCAL))) failure = std::string("GRT_COLLECTIVE_LIBRARY: ") + dlerror(); }
-		if (!api.handle && failure.empty()) for (const char * name : { "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1" }) if ((api.handle = dlopen(name, RTLD_NOW | RTLD_LOCAL))) break;
-		if (!api.handle) { if (failure.empty()) failure = std::string("librccl.so not found: ") + dlerror(); }
-		else {
-			#define RT_BIND(member, symbol) { *(void **)&api.member = dlsym(api.handle, symbol); if (!api.member) failure = std::string("librccl.so lacks ") + symbol; }
-			RT_BIND(get_unique_id, "ncclGetUniqueId") RT_BIND(comm_init_rank, "ncclCommInitRank") RT_BIND(comm_init_all, "ncclCommInitAll") RT_BIND(comm_destroy, "ncclCommDestroy")
-			RT_BIND(all_gather, "ncclAllGather") RT_BIND(group_start, "ncclGroupStart") RT_BIND(group_end, "ncclGroupEnd") RT_BIND(error_string, "ncclGetErrorString")
-			#undef RT_BIND
-		}
-	}
-	why = failure;
-	return failure.empty() ? &api : nullptr;
-}
-// this rank's share of the frame in float4 pixels, padded so that every rank sends the same amount
-size_t exchange_tiles_per_rank(const rt_context * ctx, int tile_pixels, int world) {
-	size_t frame = size_t(ctx->params.screen_width) * ctx->params.screen_height;
-	size_t tiles = (frame + tile_pixels - 1) / tile_pixels;
-	return (tiles + world - 1) / world;
-}
-int exchange_buffers(rt_context * ctx, size_t pixels) {
-	rt_context::FrameExchange & x = ctx->exchange;
-	if (x.packed_pixels >= pixels) return RT_OK;
-	if (x.packed)   device_free(ctx, x.packed);
-	if (x.gathered) device_free(ctx, x.gathered);
-	x.packed = x.gathered = nullptr; x.packed_pixels = 0;
-	int status = device_alloc(ctx, (void **)&x.packed, pixels * 16); if (status) return status;
-	status = device_alloc(ctx, (void **)&x.gathered, pixels * 16 * size_t(x.world)); if (status) return status;
-	x.packed_pixels = pixels;
-	if (!x.ev_packed) { RT_HIP(ctx, hipEventCreateWithFlags(&x.ev_packed, hipEventDisableTiming)); RT_HIP(ctx, hipEventCreateWithFlags(&x.ev_copied, hipEventDisableTiming)); }
-	return RT_OK;
-}
-} // namespace
-} // extern "C++"
-
-int rt_comm_unique_id(void * out_id_128_bytes) {
-	if (!out_id_128_bytes) return RT_ERROR_INVALID_ARG;
-	std::string why; RcclApi * api = rccl_api(why);
-	if (!api) return RT_ERROR_NOT_READY;
-	return api->get_unique_id((RcclUniqueId *)out_id_128_bytes) == 0 ? RT_OK : RT_ERROR_HIP;
-}
-
-int rt_comm_init_rank(rt_context * ctx, const void * unique_id_128_bytes, int rank, int world) {
-	RT_REQUIRE(ctx, ctx && unique_id_128_bytes && world >= 1 && rank >= 0 && rank < world, "rt_comm_init_rank: invalid argument");
-	(void)hipSetDevice(ctx->device);
-	(void)rt_comm_destroy(ctx);
-	std::string why; RcclApi * api = rccl_api(why);
-	if (!api) return fail(ctx, RT_ERROR_NOT_READY, "rt_comm_init_rank: %s", why.c_str());
-	RcclUniqueId id; memcpy(&id, unique_id_128_bytes, sizeof(id));
-	int rc = api->comm_init_rank(&ctx->exchange.comm, world, id, rank);
-	if (rc != 0) { ctx->exchange.comm = nullptr; return fail(ctx, RT_ERROR_HIP, "rt_comm_init_rank: ncclCommInitRank: %s", api->error_string(rc)); }
-	ctx->exchange.rank = rank; ctx->exchange.world = world;
-	return RT_OK;
-}
-
-int rt_comm_init_all(rt_context ** contexts, int count) {
-	if (!contexts || count < 1) return RT_ERROR_INVALID_ARG;
-	for (int i = 0; i < count; i++) if (!contexts[i]) return RT_ERROR_INVALID_ARG;
-	bool distinct = true;
-	for (int i = 0; i < count; i++) for (int j = 0; j < i; j++) if (contexts[i]->device == contexts[j]->device) distinct = false;
-	for (int i = 0; i < count; i++) { (void)rt_comm_destroy(contexts[i]); contexts[i]->exchange.rank = i; contexts[i]->exchange.world = count; }
-	if (distinct && count > 1) {   // one communicator over the GPUs of this process (ncclCommInitAll)
-		std::string why; RcclApi * api = rccl_api(why);
-		if (!api) return fail(contexts[0], RT_ERROR_NOT_READY, "rt_comm_init_all: %s", why.c_str());
-		std::vector<void *> comms(count, nullptr); std::vector<int> devices(count);
-		for (int i = 0; i < count; i++) devices[i] = contexts[i]->device;
-		int rc = api->comm_init_all(comms.data(), count, devices.data());
-		if (rc != 0) return fail(contexts[0], RT_ERROR_HIP, "rt_comm_init_all: ncclCommInitAll: %s", api->error_string(rc));
-		for (int i = 0; i < count; i++) contexts[i]->exchange.comm = comms[i];
-	} else {                       // contexts sharing a GPU: stream-ordered copies between them
-		for (int i = 0; i < count; i++) contexts[i]->exchange.peers.assign(contexts, contexts + count);
-	}
-	return RT_OK;
-}
-
-int rt_comm_destroy(rt_context * ctx) {
-	if (!ctx) return RT_ERROR_INVALID_ARG;
-	rt_context::FrameExchange & x = ctx->exchange;
-	if (x.comm) { std::string why; if (RcclApi * api = rccl_api(why)) (void)api->comm_destroy(x.comm); x.comm = nullptr; }
-	for (rt_context * peer : x.peers) if (peer && peer != ctx) {   // the others of an in-process group lose this member
-		for (rt_context *& p : peer->exchange.peers) if (p == ctx) p = nullptr;
-	}
-	x.peers.clear();
-	if (x.ev_packed || x.packed) {   // (a later group may have another world size: its buffers and events are made again, exchange_buffers)
-		(void)hipSetDevice(ctx->device);
-		(void)hipStreamSynchronize(ctx->stream);
-	}
-	if (x.ev_packed) { (void)hipEventDestroy(x.ev_packed); (void)hipEventDestroy(x.ev_copied); x.ev_packed = x.ev_copied = nullptr; }
-	if (x.packed)   device_free(ctx, x.packed);
-	if (x.gathered) device_free(ctx, x.gathered);
-	x.packed = x.gathered = nullptr; x.packed_pixels = 0;
-	x.rank = 0; x.world = 1;
-	return RT_OK;
-}
-
-// what: 0 = the final image (1 float4 per pixel), 1 = the inputs of the SVGF filter stage (5 float4 per pixel)
-static int exchange_group(rt_context ** contexts, int count, int what) {
-	const int channels = what == 0 ? 1 : 5;
-	std::string why; RcclApi * api = nullptr;
-	// pack: every context's own tiles (the tile layout is the one rt_set_pixel_tiles gave it)
-	for (int i = 0; i < count; i++) {
-		rt_context * ctx = contexts[i];
-		rt_context::FrameExchange & x = ctx->exchange;
-		RT_REQUIRE(ctx, x.world == count || x.comm, "rt_all_gather: the contexts are not one communicator group");
-		RT_REQUIRE(ctx, ctx->params.tile_pixels > 0 && ctx->params.tile_stride == x.world && ctx->params.tile_first == x.rank, "rt_all_gather: rt_set_pixel_tiles(tile_pixels, rank, world) first");
-		(void)hipSetDevice(ctx->device);
-		const size_t per_rank = exchange_tiles_per_rank(ctx, ctx->params.tile_pixels, x.world) * size_t(ctx->params.tile_pixels) * channels;
-		int status = exchange_buffers(ctx, per_rank); if (status) return status;
-		RT_HIP(ctx, main_waits_for_samples(ctx));
-		if (!x.peers.empty()) RT_HIP(ctx, hipStreamWaitEvent(ctx->stream, x.ev_copied, 0));   // the peers have read the previous frame's tiles (see below)
-		const int tiles = int(per_rank / size_t(ctx->params.tile_pixels) / channels);
-		if (what == 0) rt_launch_pack_pixels(ctx->params, x.packed, ctx->params.tile_pixels, x.rank, x.world, tiles, ctx->stream);
-		else { if (!ctx->svgf_allocated) return fail(ctx, RT_ERROR_NOT_READY, "rt_all_gather_svgf_inputs: SVGF is not enabled"); rt_launch_pack_svgf(slot_params(ctx, ctx->slots[0], 0), x.packed, ctx->params.tile_pixels, x.rank, x.world, tiles, ctx->stream); }
-		RT_HIP(ctx, hipEventRecord(x.ev_packed, ctx->stream));
-		if (x.comm && !api) { api = rccl_api(why); if (!api) return fail(ctx, RT_ERROR_NOT_READY, "rt_all_gather: %s", why.c_str()); }
-	}
-	// exchange
-	if (api) {
-		if (count > 1) api->group_start();
-		for (int i = 0; i < count; i++) {
-			rt_context * ctx = contexts[i]; rt_context::FrameExchange & x = ctx->exchange;
-			(void)hipSetDevice(ctx->device);
-			const size_t per_rank = exchange_tiles_per_rank(ctx, ctx->params.tile_pixels, x.world) * size_t(ctx->params.tile_pixels) * channels;
-			int rc = api->all_gather(x.packed, x.gathered, per_rank * 4, RCCL_FLOAT32, x.comm, ctx->stream);
-			if (rc != 0) { if (count > 1) api->group_end(); return fail(ctx, RT_ERROR_HIP, "rt_all_gather: ncclAllGather: %s", api->error_string(rc)); }
-		}
-		if (count > 1) { int rc = api->group_end(); if (rc != 0) return fail(contexts[0], RT_ERROR_HIP, "rt_all_gather: ncclGroupEnd: %s", api->error_string(rc)); }
-	} else {
-		for (int i = 0; i < count; i++) {
-			rt_context * ctx = contexts[i]; rt_context::FrameExchange & x = ctx->exchange;
-			RT_REQUIRE(ctx, int(x.peers.size()) == x.world && count == x.world, "rt_all_gather: an in-process group exchanges all its contexts in one call (rt_all_gather_framebuffers)");
-			(void)hipSetDevice(ctx->device);
-			const size_t per_rank = exchange_tiles_per_rank(ctx, ctx->params.tile_pixels, x.world) * size_t(ctx->params.tile_pixels) * channels;
-			for (int r = 0; r < x.world; r++) {
-				rt_context * peer = x.peers[r];
-				RT_REQUIRE(ctx, peer && peer->exchange.packed_pixels >= per_rank, "rt_all_gather: a member of the group is gone");
-				RT_HIP(ctx, hipStreamWaitEvent(ctx->stream, peer->exchange.ev_packed, 0));
-				if (peer->device == ctx->device) RT_HIP(ctx, hipMemcpyAsync(x.gathered + size_t(r) * per_rank, peer->exchange.packed, per_rank * 16, hipMemcpyDeviceToDevice, ctx->stream));
-				else RT_HIP(ctx, hipMemcpyPeerAsync(x.gathered + size_t(r) * per_rank, ctx->device, peer->exchange.packed, peer->device, per_rank * 16, ctx->stream));
-			}
-		}
-		// a context may pack its next frame only when every peer has copied this one: one event per context, recorded on a
-		// stream that has waited for all the copies (its own stream does: the peers' copy streams are joined through ev_packed
-		// of the NEXT round only, so join them here explicitly)
-		for (int i = 0; i < count; i++) {
-			rt_context * ctx = contexts[i];
-			(void)hipSetDevice(ctx->device);
-			RT_HIP(ctx, hipEventRecord(ctx->ev_interop, ctx->stream));
-		}
-		for (int i = 0; i < count; i++) {
-			rt_context * ctx = contexts[i];
-			(void)hipSetDevice(ctx->device);
-			for (int r = 0; r < count; r++) if (r != i) RT_HIP(ctx, hipStreamWaitEvent(ctx->stream, contexts[r]->ev_interop, 0));
-			RT_HIP(ctx, hipEventRecord(ctx->exchange.ev_copied, ctx->stream));
-		}
-	}
-	// unpack: the gathered tiles become every context's whole frame
-	for (int i = 0; i < count; i++) {
-		rt_context * ctx = contexts[i]; rt_context::FrameExchange & x = ctx->exchange;
-		(void)hipSetDevice(ctx->device);
-		const int tiles = int(exchange_tiles_per_rank(ctx, ctx->params.tile_pixels, x.world));
-		if (what == 0) rt_launch_unpack_pixels(ctx->params, x.gathered, ctx->params.tile_pixels, x.world, tiles, ctx->stream);
-		else rt_launch_unpack_svgf(slot_params(ctx, ctx->slots[0], 0), x.gathered, ctx->params.tile_pixels, x.world, tiles, ctx->stream);
-		RT_HIP(ctx, hipGetLastError());
-	}
-	return RT_OK;
-}
-
-int rt_all_gather_framebuffer(rt_context * ctx) {
-	RT_REQUIRE(ctx, ctx, "rt_all_gather_framebuffer: NULL context");
-	if (ctx->exchange.world == 1 && !ctx->exchange.comm) return RT_OK;   // (a 1-rank communicator does run its ncclAllGather: tests/test_gpu_rccl.py)
-	RT_REQUIRE(ctx, ctx->exchange.comm, "rt_all_gather_framebuffer: no communicator (rt_comm_init_rank), or an in-process group (use rt_all_gather_framebuffers)");
-	return exchange_group(&ctx, 1, 0);
-}
-int rt_all_gather_framebuffers(rt_context ** contexts, int count) {
-	if (!contexts || count < 1) return RT_ERROR_INVALID_ARG;
-	if (count == 1 && contexts[0] && contexts[0]->exchange.world == 1) return RT_OK;
-	return exchange_group(contexts, count, 0);
-}
-int rt_all_gather_svgf_inputs(rt_context ** contexts, int count) {
-	if (!contexts || count < 1) return RT_ERROR_INVALID_ARG;
-	if (count == 1 && contexts[0] && contexts[0]->exchange.world == 1) return RT_OK;
-	return exchange_group(contexts, count, 1);
-}
-
 int rt_stream_wait_for_context(rt_context * ctx, void * stream) {
 	RT_REQUIRE(ctx, ctx, "rt_stream_wait_for_context: NULL context");
 	(void)hipSetDevice(ctx->device);
@@ -1962,7 +1525,7 @@ int rt_get_trace_statistics_history(rt_context * ctx, uint64_t * out_rows10, int
 
 // ---- render ------------------------------------------------------------------------------------------------
 
-static int ensure_luts(rt_context * ctx) {
+int ensure_luts(rt_context * ctx) {
 	if (ctx->luts_ready) return RT_OK;
 	const size_t bytes[6] = { 4096 * 4, 4096 * 4, 256 * 4, 256 * 4, 1024 * 4, 32 * 4 };
 	for (int i = 0; i < 6; i++) if (!ctx->luts[i]) { int s = device_alloc(ctx, &ctx->luts[i], bytes[i]); if (s) return s; }
@@ -2016,7 +1579,7 @@ __global__ void kernel_accumulate_counters(const RtBufferSizes * sizes, int * to
 
 // ---- merged wavefront: host side ---------------------------------------------------------------------------------
 
-static int stream_create(rt_context * ctx) {
+int stream_create(rt_context * ctx) {
 	PathStream & s = ctx->path_stream;
 	if (s.created) return RT_OK;
 	if (!ctx->stream_history) RT_HIP(ctx, hipHostMalloc((void **)&ctx->stream_history, sizeof(unsigned long long) * 10 * RT_STREAM_HISTORY_ROWS));
@@ -2119,7 +1682,7 @@ static int stream_ensure_queues(rt_context * ctx, size_t entries) {
 
 // The parameter block of iteration `iteration`: the context's block with the stream's queues, control block and
 // per-sample frames patched in.
-static RtParams stream_params(const rt_context * ctx, int iteration) {
+RtParams stream_params(const rt_context * ctx, int iteration) {
 	const PathStream & s = ctx->path_stream;
 	RtParams p = ctx->params;
 	use_queues(p, s.queues);
@@ -2219,7 +1782,7 @@ static int stream_complete(rt_context * ctx, const StreamSubmission * subs, int 
 // per-submission chains that keep frames of different scene versions in flight) is copied into the slots [0, node count)
 // that the BLAS node array reserves for it -- node indices below the TLAS size never name BLAS nodes. Nothing of the merged
 // wavefront is in flight when the TLAS changes (every upload completes it first), and the other kernels never read those slots.
-static int stream_sync_tlas(rt_context * ctx) {
+int stream_sync_tlas(rt_context * ctx) {
 	if (ctx->tlas_version_in_nodes == ctx->tlas_version) return RT_OK;
 	if (!ctx->params.tlas_nodes || ctx->params.tlas_node_count <= 0) {   // one BVH, no TLAS: node 0 is its root
 		ctx->tlas_version_in_nodes = ctx->tlas_version; return RT_OK;
@@ -2735,585 +2298,6 @@ int rt_read_luts(rt_context * ctx, float * dielectric_dir_enter, float * dielect
 	float * dst[6] = { dielectric_dir_enter, dielectric_dir_leave, dielectric_enter, dielectric_leave, conductor_dir, conductor };
 	const size_t bytes[6] = { 4096 * 4, 4096 * 4, 256 * 4, 256 * 4, 1024 * 4, 32 * 4 };
 	for (int i = 0; i < 6; i++) if (dst[i]) RT_HIP(ctx, hipMemcpy(dst[i], ctx->luts[i], bytes[i], hipMemcpyDeviceToHost));
-	return RT_OK;
-}
-
-// ---- kernel-level entry points ------------------------------------------------------------------------------------
-
-struct TempBuffers {
-	rt_context * ctx; std::vector<void *> ptrs;
-	explicit TempBuffers(rt_context * c) : ctx(c) { }
-	~TempBuffers() { for (void * p : ptrs) (void)hipFree(p); }
-	void * get(size_t bytes, const void * src) {
-		void * p = nullptr;
-		if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return nullptr;
-		ptrs.push_back(p);
-		if (src && bytes && hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-		return p;
-	}
-};
-
-} // extern "C"
-
-// The repeat / timing loop of the explicit-ray entry points around `launch` (one traversal on the main stream):
-// *out_ms gets the mean time of `repeat` launches.
-template<typename Launch> static int time_explicit_launches(rt_context * ctx, int repeat, float * out_ms, Launch && launch) {
-	if (repeat < 1) repeat = 1;
-	hipEvent_t e0, e1; RT_HIP(ctx, hipEventCreate(&e0)); RT_HIP(ctx, hipEventCreate(&e1));
-	float total = 0.0f;
-	for (int r = 0; r < repeat; r++) {
-		RT_HIP(ctx, hipMemsetAsync(ctx->explicit_retired, 0, 8 * sizeof(int), ctx->stream));
-		RT_HIP(ctx, hipEventRecord(e0, ctx->stream));
-		launch();
-		RT_HIP(ctx, hipEventRecord(e1, ctx->stream));
-		RT_HIP(ctx, quiesce(ctx));
-		float ms = 0.0f; RT_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
-		total += ms;
-	}
-	(void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-	RT_HIP(ctx, hipGetLastError());
-	if (out_ms) *out_ms = total / float(repeat);
-	return RT_OK;
-}
-
-extern "C" {
-
-int rt_trace_rays(rt_context * ctx, const float * ox, const float * oy, const float * oz,
-                  const float * dx, const float * dy, const float * dz, size_t ray_count,
-                  uint32_t * hits, int repeat, float * out_ms) {
-	RT_REQUIRE(ctx, ctx && ox && oy && oz && dx && dy && dz && hits, "rt_trace_rays: NULL argument");
-	(void)hipSetDevice(ctx->device);
-	RT_HIP(ctx, quiesce(ctx)); // slot 0's spill area and cursors are borrowed
-	int s = check_ready(ctx, "rt_trace_rays", NEED_SCENE_JOINT); if (s) return s;
-	TempBuffers tmp(ctx);
-	size_t bytes = ray_count * 4;
-	RtVec3SoA o = { (float *)tmp.get(bytes, ox), (float *)tmp.get(bytes, oy), (float *)tmp.get(bytes, oz) };
-	RtVec3SoA d = { (float *)tmp.get(bytes, dx), (float *)tmp.get(bytes, dy), (float *)tmp.get(bytes, dz) };
-	uint4 * dev_hits = (uint4 *)tmp.get(ray_count * 16, nullptr);
-	if (!o.x || !o.y || !o.z || !d.x || !d.y || !d.z || !dev_hits) return fail(ctx, RT_ERROR_HIP, "rt_trace_rays: device allocation failed");
-
-	s = time_explicit_launches(ctx, repeat, out_ms, [&] { rt_launch_trace_explicit(ctx->params, o, d, dev_hits, int(ray_count), ctx->explicit_retired, ctx->stream); }); if (s) return s;
-	RT_HIP(ctx, hipMemcpy(hits, dev_hits, ray_count * 16, hipMemcpyDeviceToHost));
-	return RT_OK;
-}
-
-int rt_trace_shadow_rays(rt_context * ctx, const float * ox, const float * oy, const float * oz,
-                         const float * dx, const float * dy, const float * dz, const float * max_distance,
-                         size_t ray_count, uint8_t * occluded, int repeat, float * out_ms) {
-	RT_REQUIRE(ctx, ctx && ox && oy && oz && dx && dy && dz && max_distance && occluded, "rt_trace_shadow_rays: NULL argument");
-	(void)hipSetDevice(ctx->device);
-	RT_HIP(ctx, quiesce(ctx)); // slot 0's spill area and cursors are borrowed
-	int s = check_ready(ctx, "rt_trace_shadow_rays", NEED_SCENE_JOINT); if (s) return s;
-	TempBuffers tmp(ctx);
-	size_t bytes = ray_count * 4;
-	RtVec3SoA o = { (float *)tmp.get(bytes, ox), (float *)tmp.get(bytes, oy), (float *)tmp.get(bytes, oz) };
-	RtVec3SoA d = { (float *)tmp.get(bytes, dx), (float *)tmp.get(bytes, dy), (float *)tmp.get(bytes, dz) };
-	float * dev_max = (float *)tmp.get(bytes, max_distance);
-	uint8_t * dev_occ = (uint8_t *)tmp.get(ray_count, nullptr);
-	if (!o.x || !o.y || !o.z || !d.x || !d.y || !d.z || !dev_max || !dev_occ) return fail(ctx, RT_ERROR_HIP, "rt_trace_shadow_rays: device allocation failed");
-
-	s = time_explicit_launches(ctx, repeat, out_ms, [&] { rt_launch_trace_shadow_explicit(ctx->params, o, d, dev_max, dev_occ, int(ray_count), ctx->explicit_retired, ctx->stream); }); if (s) return s;
-	RT_HIP(ctx, hipMemcpy(occluded, dev_occ, ray_count, hipMemcpyDeviceToHost));
-	return RT_OK;
-}
-
-// rt_trace_stream_rays: the merged wavefront's traversal launch (rt_launch_trace_stream, as stream_enqueue_iteration calls it) on explicit
-// rays. The parameter block is stream_params(ctx, iteration) with the closest-hit queue of parity iteration & 1, the shadow queue, the
-// control block and the radiance frame replaced by buffers of this call; every shadow ray i carries illumination (1, 0, 0) for pixel i,
-// so what the launch adds to pixel i tells how often ray i reached its light unoccluded. Runs on the wavefront's own stream with its own
-// spill area, after quiesce(); nothing of the context changes but what the scheduler would set up itself (stream_create, stream_sync_tlas).
-int rt_trace_stream_rays(rt_context * ctx, int iteration,
-                         const float * ox, const float * oy, const float * oz, const float * dx, const float * dy, const float * dz,
-                         size_t closest_count, uint32_t * hits,
-                         const float * sox, const float * soy, const float * soz, const float * sdx, const float * sdy, const float * sdz,
-                         const float * max_distance, size_t shadow_count, float * shadow_light,
-                         uint64_t * stats10, int32_t * info) {
-	RT_REQUIRE(ctx, ctx != nullptr, "rt_trace_stream_rays: NULL context");
-	RT_REQUIRE(ctx, info != nullptr, "rt_trace_stream_rays: NULL info");
-	RT_REQUIRE(ctx, iteration >= 0, "rt_trace_stream_rays: negative iteration");
-	RT_REQUIRE(ctx, closest_count == 0 || (ox && oy && oz && dx && dy && dz && hits), "rt_trace_stream_rays: NULL closest-hit ray or hit array");
-	RT_REQUIRE(ctx, shadow_count == 0 || (sox && soy && soz && sdx && sdy && sdz && max_distance && shadow_light), "rt_trace_stream_rays: NULL shadow ray, max_distance or shadow_light array");
-	RT_REQUIRE(ctx, closest_count + shadow_count <= size_t(1) << 28, "rt_trace_stream_rays: more than 2^28 rays in one launch");
-	(void)hipSetDevice(ctx->device);
-	RT_HIP(ctx, quiesce(ctx)); // the wavefront's stream and spill area are borrowed
-	int s = check_ready(ctx, "rt_trace_stream_rays", NEED_SCENE_JOINT); if (s) return s;
-	if (ctx->params.bvh_width != 8) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_trace_stream_rays: the merged wavefront's launch walks the CWBVH (bvh_width %d)", ctx->params.bvh_width);
-	s = stream_create(ctx); if (s) return s;
-	s = stream_sync_tlas(ctx); if (s) return s;
-	PathStream & ps = ctx->path_stream;
-	const int q = iteration & 1;
-
-	TempBuffers tmp(ctx);
-	const size_t cb = closest_count * 4, sb = shadow_count * 4;
-	RtTraceBuffer trace = { };
-	trace.origin    = { (float *)tmp.get(cb, ox), (float *)tmp.get(cb, oy), (float *)tmp.get(cb, oz) };
-	trace.direction = { (float *)tmp.get(cb, dx), (float *)tmp.get(cb, dy), (float *)tmp.get(cb, dz) };
-	trace.hits = (uint4 *)tmp.get(closest_count * 16, hits);   // the caller's values: a sentinel shows a ray the launch never dealt
-	std::vector<float4> light(shadow_count);
-	for (size_t i = 0; i < shadow_count; i++) {   // (i < 2^28: RT_SHADOW_FLAG_BOUNCE_0 clear)
-		uint32_t pixel_word = uint32_t(i); float w; memcpy(&w, &pixel_word, 4);
-		light[i] = make_float4(1.0f, 0.0f, 0.0f, w);
-	}
-	RtShadowBuffer shadow = { };
-	shadow.origin    = { (float *)tmp.get(sb, sox), (float *)tmp.get(sb, soy), (float *)tmp.get(sb, soz) };
-	shadow.direction = { (float *)tmp.get(sb, sdx), (float *)tmp.get(sb, sdy), (float *)tmp.get(sb, sdz) };
-	shadow.max_distance = (float *)tmp.get(sb, max_distance);
-	shadow.illumination_and_pixel_index = (float4 *)tmp.get(shadow_count * 16, light.data());
-	float4 * radiance = (float4 *)tmp.get(shadow_count * 16, nullptr);
-	std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());   // (value-initialised: zero cursors and region words)
-	control_host->trace_count[q] = int(closest_count);
-	control_host->shadow_count[q ^ 1] = int(shadow_count);
-	RtStreamControl * control = (RtStreamControl *)tmp.get(sizeof(RtStreamControl), control_host.get());
-	unsigned long long * stats = stats10 ? (unsigned long long *)tmp.get(10 * sizeof(unsigned long long), nullptr) : nullptr;
-	if (!trace.origin.x || !trace.origin.y || !trace.origin.z || !trace.direction.x || !trace.direction.y || !trace.direction.z || !trace.hits ||
-	    !shadow.origin.x || !shadow.origin.y || !shadow.origin.z || !shadow.direction.x || !shadow.direction.y || !shadow.direction.z ||
-	    !shadow.max_distance || !shadow.illumination_and_pixel_index || !radiance || !control || (stats10 && !stats))
-		return fail(ctx, RT_ERROR_HIP, "rt_trace_stream_rays: device allocation failed");
-	if (shadow_count) RT_HIP(ctx, hipMemset(radiance, 0, shadow_count * 16));
-	if (stats) RT_HIP(ctx, hipMemset(stats, 0, 10 * sizeof(unsigned long long)));
-
-	RtParams p = stream_params(ctx, iteration);
-	p.trace[q] = trace;
-	p.shadow = shadow;
-	p.stream = control;
-	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = nullptr;
-	p.aovs[RT_AOV_RADIANCE].framebuffer = radiance;
-	rt_trace_stream_launch_info(p, stats != nullptr, info);
-	rt_launch_trace_stream(p, stats, ps.stream);
-	RT_HIP(ctx, hipGetLastError());
-	RT_HIP(ctx, hipStreamSynchronize(ps.stream));
-	if (closest_count) RT_HIP(ctx, hipMemcpy(hits, trace.hits, closest_count * 16, hipMemcpyDeviceToHost));
-	if (shadow_count) {
-		std::vector<float4> added(shadow_count);
-		RT_HIP(ctx, hipMemcpy(added.data(), radiance, shadow_count * 16, hipMemcpyDeviceToHost));
-		for (size_t i = 0; i < shadow_count; i++) shadow_light[i] = added[i].x;
-	}
-	if (stats10) RT_HIP(ctx, hipMemcpy(stats10, stats, 10 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-	return RT_OK;
-}
-
-int rt_generate_rays(rt_context * ctx, int sample_index, int pixel_offset, int pixel_count,
-                     float * ox, float * oy, float * oz, float * dx, float * dy, float * dz, uint32_t * pixel_index_and_flags) {
-	RT_REQUIRE(ctx, ctx && ox && oy && oz && dx && dy && dz && pixel_index_and_flags, "rt_generate_rays: NULL argument");
-	RT_REQUIRE(ctx, pixel_count >= 0, "rt_generate_rays: negative pixel_count");
-	(void)hipSetDevice(ctx->device);
-	if (!ctx->params.pmj_samples || ctx->frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_generate_rays: RNG tables not uploaded or rt_resize not called");
-	RT_HIP(ctx, quiesce(ctx)); // slot 0's queues are borrowed
-	int s = ensure_queues(ctx); if (s) return s;
-	if (size_t(pixel_count) > ctx->slots[0].queues.capacity) return fail(ctx, RT_ERROR_OUT_OF_RANGE, "rt_generate_rays: pixel_count %d exceeds the queue capacity %zu", pixel_count, ctx->slots[0].queues.capacity);
-	rt_launch_generate(ctx->params, sample_index, pixel_offset, pixel_count, ctx->stream);
-	RT_HIP(ctx, hipGetLastError());
-	RT_HIP(ctx, quiesce(ctx));
-	const RtTraceBuffer & t = ctx->params.trace[0];
-	size_t bytes = size_t(pixel_count) * 4;
-	RT_HIP(ctx, hipMemcpy(ox, t.origin.x, bytes, hipMemcpyDeviceToHost));
-	RT_HIP(ctx, hipMemcpy(oy, t.origin.y, bytes, hipMemcpyDeviceToHost));
-	RT_HIP(ctx, hipMemcpy(oz, t.origin.z, bytes, hipMemcpyDeviceToHost));
-	RT_HIP(ctx, hipMemcpy(dx, t.direction.x, bytes, hipMemcpyDeviceToHost));
-	RT_HIP(ctx, hipMemcpy(dy, t.direction.y, bytes, hipMemcpyDeviceToHost));
-	RT_HIP(ctx, hipMemcpy(dz, t.direction.z, bytes, hipMemcpyDeviceToHost));
-	RT_HIP(ctx, hipMemcpy(pixel_index_and_flags, t.pixel_index_and_flags, bytes, hipMemcpyDeviceToHost));
-	return RT_OK;
-}
-
-int rt_random_samples(rt_context * ctx, int dimension, const uint32_t * pixel_indices, size_t count, uint32_t bounce, uint32_t sample_index, float * out_xy) {
-	RT_REQUIRE(ctx, ctx && pixel_indices && out_xy && dimension >= 0 && dimension < 7, "rt_random_samples: invalid argument");
-	(void)hipSetDevice(ctx->device);
-	if (!ctx->params.pmj_samples || ctx->params.screen_pitch == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_random_samples: RNG tables not uploaded or rt_resize not called");
-	TempBuffers tmp(ctx);
-	unsigned * dev_px = (unsigned *)tmp.get(count * 4, pixel_indices);
-	float2 * dev_out = (float2 *)tmp.get(count * 8, nullptr);
-	if (!dev_px || !dev_out) return fail(ctx, RT_ERROR_HIP, "rt_random_samples: device allocation failed");
-	rt_launch_random(ctx->params, dimension, dev_px, int(count), bounce, sample_index, dev_out, ctx->stream);
-	RT_HIP(ctx, hipGetLastError());
-	RT_HIP(ctx, quiesce(ctx));
-	RT_HIP(ctx, hipMemcpy(out_xy, dev_out, count * 8, hipMemcpyDeviceToHost));
-	return RT_OK;
-}
-
-int rt_sample_texture(rt_context * ctx, int texture_index, int filter, const float * args, size_t count, float * out_rgba) {
-	RT_REQUIRE(ctx, ctx && args && out_rgba, "rt_sample_texture: NULL argument");
-	RT_REQUIRE(ctx, texture_index >= 0 && size_t(texture_index) < ctx->texture_data.size(), "rt_sample_texture: texture index out of range");
-	RT_REQUIRE(ctx, filter >= 0 && filter <= 2, "rt_sample_texture: filter must be 0 (level 0), 1 (lod) or 2 (gradients)");
-	RT_REQUIRE(ctx, count <= size_t(1) << 28, "rt_sample_texture: more than 2^28 probes");
-	(void)hipSetDevice(ctx->device);
-	if (count == 0) return RT_OK;
-	TempBuffers tmp(ctx);
-	float * dev_args = (float *)tmp.get(count * 32, args);
-	float4 * dev_out = (float4 *)tmp.get(count * 16, nullptr);
-	if (!dev_args || !dev_out) return fail(ctx, RT_ERROR_HIP, "rt_sample_texture: device allocation failed");
-	rt_launch_sample_texture(ctx->params, texture_index, filter, dev_args, int(count), dev_out, ctx->stream);
-	RT_HIP(ctx, hipGetLastError());
-	RT_HIP(ctx, quiesce(ctx));
-	RT_HIP(ctx, hipMemcpy(out_rgba, dev_out, count * 16, hipMemcpyDeviceToHost));
-	return RT_OK;
-}
-
-int rt_sample_table(rt_context * ctx, const float * table, int nx, int ny, int nz, int dims, const float * coords, size_t count, float * out) {
-	RT_REQUIRE(ctx, ctx && table && coords && out, "rt_sample_table: NULL argument");
-	RT_REQUIRE(ctx, dims >= 1 && dims <= 3, "rt_sample_table: dims must be 1, 2 or 3");
-	RT_REQUIRE(ctx, nx >= 1 && nx <= 65536 && (dims < 2 || (ny >= 1 && ny <= 65536)) && (dims < 3 || (nz >= 1 && nz <= 65536)), "rt_sample_table: a table side is outside [1, 65536]");
-	RT_REQUIRE(ctx, count <= size_t(1) << 28, "rt_sample_table: more than 2^28 probes");
-	size_t entries = size_t(nx) * (dims >= 2 ? size_t(ny) : 1) * (dims >= 3 ? size_t(nz) : 1);
-	RT_REQUIRE(ctx, entries <= size_t(1) << 28, "rt_sample_table: more than 2^28 table entries");
-	(void)hipSetDevice(ctx->device);
-	if (count == 0) return RT_OK;
-	TempBuffers tmp(ctx);
-	float * dev_table = (float *)tmp.get(entries * 4, table);
-	float * dev_coords = (float *)tmp.get(count * 12, coords);
-	float * dev_out = (float *)tmp.get(count * 4, nullptr);
-	if (!dev_table || !dev_coords || !dev_out) return fail(ctx, RT_ERROR_HIP, "rt_sample_table: device allocation failed");
-	rt_launch_sample_table(dev_table, nx, dims >= 2 ? ny : 1, dims >= 3 ? nz : 1, dims, dev_coords, int(count), dev_out, ctx->stream);
-	RT_HIP(ctx, hipGetLastError());
-	RT_HIP(ctx, quiesce(ctx));
-	RT_HIP(ctx, hipMemcpy(out, dev_out, count * 4, hipMemcpyDeviceToHost));
-	return RT_OK;
-}
-
-int rt_sample_sky(rt_context * ctx, const float * directions, size_t count, float * out_rgb) {
-	RT_REQUIRE(ctx, ctx && directions && out_rgb, "rt_sample_sky: NULL argument");
-	RT_REQUIRE(ctx, ctx->params.sky, "rt_sample_sky: no sky uploaded (rt_set_sky)");
-	RT_REQUIRE(ctx, count <= size_t(1) << 28, "rt_sample_sky: more than 2^28 probes");
-	(void)hipSetDevice(ctx->device);
-	if (count == 0) return RT_OK;
-	TempBuffers tmp(ctx);
-	float * dev_dirs = (float *)tmp.get(count * 12, directions);
-	float * dev_out = (float *)tmp.get(count * 12, nullptr);
-	if (!dev_dirs || !dev_out) return fail(ctx, RT_ERROR_HIP, "rt_sample_sky: device allocation failed");
-	rt_launch_sample_sky(ctx->params, dev_dirs, int(count), dev_out, ctx->stream);
-	RT_HIP(ctx, hipGetLastError());
-	RT_HIP(ctx, quiesce(ctx));
-	RT_HIP(ctx, hipMemcpy(out_rgb, dev_out, count * 12, hipMemcpyDeviceToHost));
-	return RT_OK;
-}
-
-int rt_sample_sky_distribution(rt_context * ctx, const float * uv, size_t count, float * out_xyz_pdf) {
-	RT_REQUIRE(ctx, ctx && uv && out_xyz_pdf, "rt_sample_sky_distribution: NULL argument");
-	RT_REQUIRE(ctx, ctx->params.sky, "rt_sample_sky_distribution: no sky uploaded (rt_set_sky)");
-	RT_REQUIRE(ctx, count <= size_t(1) << 28, "rt_sample_sky_distribution: more than 2^28 probes");
-	(void)hipSetDevice(ctx->device);
-	int s = sky_tables_build(ctx, "rt_sample_sky_distribution"); if (s) return s;
-	RT_REQUIRE(ctx, ctx->sky_total > 0.0, "rt_sample_sky_distribution: the sky has no weight to sample");
-	if (count == 0) return RT_OK;
-	TempBuffers tmp(ctx);
-	float * dev_uv = (float *)tmp.get(count * 8, uv);
-	float * dev_out = (float *)tmp.get(count * 16, nullptr);
-	if (!dev_uv || !dev_out) return fail(ctx, RT_ERROR_HIP, "rt_sample_sky_distribution: device allocation failed");
-	rt_launch_sample_sky_distribution(ctx->params, dev_uv, int(count), dev_out, ctx->stream);
-	RT_HIP(ctx, hipGetLastError());
-	RT_HIP(ctx, quiesce(ctx));
-	RT_HIP(ctx, hipMemcpy(out_xyz_pdf, dev_out, count * 16, hipMemcpyDeviceToHost));
-	return RT_OK;
-}
-
-int rt_sky_pdf(rt_context * ctx, const float * directions, size_t count, float * out_pdf) {
-	RT_REQUIRE(ctx, ctx && directions && out_pdf, "rt_sky_pdf: NULL argument");
-	RT_REQUIRE(ctx, ctx->params.sky, "rt_sky_pdf: no sky uploaded (rt_set_sky)");
-	RT_REQUIRE(ctx, count <= size_t(1) << 28, "rt_sky_pdf: more than 2^28 probes");
-	(void)hipSetDevice(ctx->device);
-	int s = sky_tables_build(ctx, "rt_sky_pdf"); if (s) return s;
-	if (count == 0) return RT_OK;
-	TempBuffers tmp(ctx);
-	float * dev_dirs = (float *)tmp.get(count * 12, directions);
-	float * dev_out = (float *)tmp.get(count * 4, nullptr);
-	if (!dev_dirs || !dev_out) return fail(ctx, RT_ERROR_HIP, "rt_sky_pdf: device allocation failed");
-	rt_launch_sky_pdf(ctx->params, dev_dirs, int(count), dev_out, ctx->stream);
-	RT_HIP(ctx, hipGetLastError());
-	RT_HIP(ctx, quiesce(ctx));
-	RT_HIP(ctx, hipMemcpy(out_pdf, dev_out, count * 4, hipMemcpyDeviceToHost));
-	return RT_OK;
-}
-
-// rt_bsdf_eval / rt_bsdf_sample: a copy of the parameters whose material table is the probes' own materials (probe i: material i),
-// with the Kulla-Conty tables of the context, no AOV and SVGF off, so that nothing of a frame is read or written.
-static int bsdf_probe(rt_context * ctx, const char * name, bool eval, int material_type, const float * probes, size_t count, float * out) {
-	if (!ctx || !probes || !out) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: NULL argument", name);
-	if (material_type < RT_MATERIAL_DIFFUSE || material_type > RT_MATERIAL_CONDUCTOR)
-		return fail(ctx, RT_ERROR_INVALID_ARG, "%s: material_type must be diffuse (1), plastic (2), dielectric (3) or conductor (4)", name);
-	if (count > size_t(1) << 24) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: more than 2^24 probes", name);
-	if (material_type == RT_MATERIAL_DIFFUSE || material_type == RT_MATERIAL_PLASTIC) {
-		for (size_t i = 0; i < count; i++) {
-			int32_t texture_id; memcpy(&texture_id, probes + i * RT_BSDF_PROBE_IN + 3, 4);
-			if (texture_id != RT_INVALID) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: probe %zu names texture %d (only RT_INVALID is probed)", name, i, texture_id);
-		}
-	}
-	(void)hipSetDevice(ctx->device);
-	if (!ctx->params.pmj_samples || ctx->params.screen_pitch == 0) return fail(ctx, RT_ERROR_NOT_READY, "%s: RNG tables not uploaded or rt_resize not called", name);
-	int s = ensure_luts(ctx); if (s) return s;
-	if (count == 0) return RT_OK;
-	std::vector<float> materials(count * 8);
-	for (size_t i = 0; i < count; i++) memcpy(&materials[i * 8], probes + i * RT_BSDF_PROBE_IN, 32);
-	TempBuffers tmp(ctx);
-	float * dev_materials = (float *)tmp.get(count * 32, materials.data());
-	float * dev_probes = (float *)tmp.get(count * RT_BSDF_PROBE_IN * 4, probes);
-	float * dev_out = (float *)tmp.get(count * RT_BSDF_PROBE_OUT * 4, nullptr);
-	if (!dev_materials || !dev_probes || !dev_out) return fail(ctx, RT_ERROR_HIP, "%s: device allocation failed", name);
-	RtParams p = ctx->params;
-	p.materials = (const float4 *)dev_materials;
-	p.textures = nullptr;
-	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = p.aovs[a].accumulator = nullptr;
-	p.config.enable_svgf = 0;
-	rt_launch_bsdf_probe(p, material_type, eval, dev_probes, int(count), dev_out, ctx->stream);
-	RT_HIP(ctx, hipGetLastError());
-	RT_HIP(ctx, quiesce(ctx));
-	RT_HIP(ctx, hipMemcpy(out, dev_out, count * RT_BSDF_PROBE_OUT * 4, hipMemcpyDeviceToHost));
-	return RT_OK;
-}
-
-int rt_bsdf_eval(rt_context * ctx, int material_type, const float * probes, size_t count, float * out) {
-	return bsdf_probe(ctx, "rt_bsdf_eval", true, material_type, probes, count, out);
-}
-int rt_bsdf_sample(rt_context * ctx, int material_type, const float * probes, size_t count, float * out) {
-	return bsdf_probe(ctx, "rt_bsdf_sample", false, material_type, probes, count, out);
-}
-
-int rt_sample_lights(rt_context * ctx, const float * probes, size_t count, int use_lds, float * out) {
-	RT_REQUIRE(ctx, ctx && probes && out, "rt_sample_lights: NULL argument");
-	RT_REQUIRE(ctx, count <= size_t(1) << 24, "rt_sample_lights: more than 2^24 probes");
-	RT_REQUIRE(ctx, use_lds == 0 || use_lds == 1, "rt_sample_lights: use_lds must be 0 (global memory) or 1 (as the shade kernels choose)");
-	const RtParams & p = ctx->params;
-	if (p.light_mesh_count <= 0 || p.light_triangle_count <= 0 || !(p.lights_total_weight > 0.0f))
-		return fail(ctx, RT_ERROR_NOT_READY, "rt_sample_lights: no lights uploaded (rt_upload_lights with at least one light mesh entry)");
-	if (!p.triangles || !p.mesh_transforms || !p.mesh_material_ids || !p.materials)
-		return fail(ctx, RT_ERROR_NOT_READY, "rt_sample_lights: geometry, instance tables or materials not uploaded");
-	for (size_t i = 0; i < count * 4; i++)   // (the searches end only for numbers up to the tables' last entry, 1)
-		if (!(probes[i] >= 0.0f && probes[i] < 1.0f)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sample_lights: probe %zu: random number %zu is %.9g, outside [0, 1)", i / 4, i % 4, double(probes[i]));
-	(void)hipSetDevice(ctx->device);
-	int s = sky_sampling_prepare(ctx, "rt_sample_lights"); if (s) return s;   // (as a render settles it; the selection does not read it)
-	if (count == 0) return RT_OK;
-	TempBuffers tmp(ctx);
-	float * dev_probes = (float *)tmp.get(count * 16, probes);
-	float * dev_out = (float *)tmp.get(count * RT_LIGHT_SAMPLE_OUT * 4, nullptr);
-	if (!dev_probes || !dev_out) return fail(ctx, RT_ERROR_HIP, "rt_sample_lights: device allocation failed");
-	rt_launch_sample_lights(p, dev_probes, int(count), use_lds != 0, dev_out, ctx->stream);
-	RT_HIP(ctx, hipGetLastError());
-	RT_HIP(ctx, quiesce(ctx));
-	RT_HIP(ctx, hipMemcpy(out, dev_out, count * RT_LIGHT_SAMPLE_OUT * 4, hipMemcpyDeviceToHost));
-	return RT_OK;
-}
-
-int rt_perturb_normals(rt_context * ctx, int texture_index, const float * probes, size_t count, float * out) {
-	RT_REQUIRE(ctx, ctx && probes && out, "rt_perturb_normals: NULL argument");
-	RT_REQUIRE(ctx, texture_index >= 0 && size_t(texture_index) < ctx->texture_formats.size(), "rt_perturb_normals: texture index out of range");
-	RT_REQUIRE(ctx, ctx->texture_formats[texture_index] == RT_TEXTURE_RGBA8, "rt_perturb_normals: the map must be an RT_TEXTURE_RGBA8 texture");
-	RT_REQUIRE(ctx, count <= size_t(1) << 24, "rt_perturb_normals: more than 2^24 probes");
-	for (size_t i = 0; i < count; i++) {
-		float filter = probes[i * RT_NORMAL_PROBE_IN + 41];
-		RT_REQUIRE(ctx, filter == 0.0f || filter == 1.0f || filter == 2.0f, "rt_perturb_normals: filter must be 0 (level 0), 1 (lod) or 2 (gradients)");
-	}
-	(void)hipSetDevice(ctx->device);
-	if (count == 0) return RT_OK;
-	TempBuffers tmp(ctx);
-	float * dev_probes = (float *)tmp.get(count * RT_NORMAL_PROBE_IN * 4, probes);
-	float * dev_out = (float *)tmp.get(count * 16, nullptr);
-	if (!dev_probes || !dev_out) return fail(ctx, RT_ERROR_HIP, "rt_perturb_normals: device allocation failed");
-	rt_launch_perturb_normals(ctx->params, texture_index, dev_probes, int(count), dev_out, ctx->stream);
-	RT_HIP(ctx, hipGetLastError());
-	RT_HIP(ctx, quiesce(ctx));
-	RT_HIP(ctx, hipMemcpy(out, dev_out, count * 16, hipMemcpyDeviceToHost));
-	return RT_OK;
-}
-
-// rt_sort_rays: the sort launch (rt_launch_sort or rt_launch_sort_stream, as the per-bounce loop and stream_enqueue_iteration call them) on an
-// explicit trace queue. The parameter block is the context's (ctx->params, or stream_params(ctx, iteration)) with both trace queues, the four
-// material queues, the counters (RtBufferSizes) or the control block and slot table, the AOV frames, the g-buffers and the pixel-query word
-// replaced by buffers of this call, every output array filled with the caller's sentinel. Runs on the main stream after quiesce().
-int rt_sort_rays(rt_context * ctx, int merged, int step, int sample_index, const uint32_t * trace_in, size_t count,
-                 const int32_t * slot_table, size_t slot_count, const int32_t * submission_birth,
-                 size_t capacity, size_t frame_slots, uint32_t sentinel,
-                 uint32_t * trace_out, uint32_t * material_out, int32_t * counters6,
-                 float * aov_frames, float * gbuffer_normal_and_depth, int32_t * gbuffer_mesh_id_and_triangle_id, float * gbuffer_screen_position_prev,
-                 int32_t * pixel_query2, int32_t * stats) {
-	RT_REQUIRE(ctx, ctx != nullptr, "rt_sort_rays: NULL context");
-	RT_REQUIRE(ctx, merged == 0 || merged == 1, "rt_sort_rays: merged must be 0 (per-bounce launch) or 1 (merged wavefront)");
-	RT_REQUIRE(ctx, (trace_in || count == 0) && trace_out && material_out && counters6 && aov_frames && gbuffer_normal_and_depth &&
-	                gbuffer_mesh_id_and_triangle_id && gbuffer_screen_position_prev && pixel_query2, "rt_sort_rays: NULL array");
-	RT_REQUIRE(ctx, !merged || (slot_table && submission_birth && stats), "rt_sort_rays: NULL slot table, submission births or statistics (merged form)");
-	RT_REQUIRE(ctx, step >= 0 && (merged || step < RT_MAX_BOUNCES), merged ? "rt_sort_rays: negative iteration" : "rt_sort_rays: bounce outside [0, RT_MAX_BOUNCES)");
-	RT_REQUIRE(ctx, capacity >= 1 && capacity <= size_t(1) << 28, "rt_sort_rays: capacity must be in [1, 2^28]");
-	RT_REQUIRE(ctx, count <= capacity, "rt_sort_rays: more entries than the queue capacity");
-	// a bounce the path length does not reach is refused too: beyond it the per-bounce counter of the next trace queue runs into the next array of RtBufferSizes
-	RT_REQUIRE(ctx, merged || step < ctx->params.config.num_bounces, "rt_sort_rays: bounce outside [0, num_bounces)");
-	(void)hipSetDevice(ctx->device);
-	int s = check_ready(ctx, "rt_sort_rays", NEED_SCENE_JOINT | NEED_MATERIALS | NEED_RNG | NEED_SKY | NEED_FRAME); if (s) return s;
-	const size_t frame_pixels = ctx->frame_pixels;
-	RT_REQUIRE(ctx, frame_slots >= 1 && frame_slots <= size_t(RT_STREAM_SAMPLE_SLOTS) && frame_slots * frame_pixels < size_t(1) << 30,
-	           "rt_sort_rays: frame_slots must be in [1, 512] and frame_slots * frame_pixels below 2^30");
-	RT_REQUIRE(ctx, !merged || (slot_count >= 1 && slot_count <= size_t(RT_STREAM_SAMPLE_SLOTS)), "rt_sort_rays: slot_count must be in [1, 512]");
-	const size_t pixels = frame_slots * frame_pixels;
-	if (merged) for (size_t k = 0; k < slot_count; k++) {
-		const int32_t * e = slot_table + 4 * k;
-		if (e[2] < 0 || e[2] >= RT_STREAM_SUBMISSIONS) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: slot %zu: submission %d outside [0, %d)", k, e[2], RT_STREAM_SUBMISSIONS);
-		if (e[1] != submission_birth[e[2]]) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: slot %zu: birth iteration %d is not its submission's (%d)", k, e[1], submission_birth[e[2]]);
-	}
-	{	// every index the kernel forms from an entry stays inside the call's buffers and the context's tables
-		std::vector<uint8_t> seen((pixels + 7) / 8, 0);
-		for (size_t i = 0; i < count; i++) {
-			const uint32_t * r = trace_in + i * RT_SORT_TRACE_WORDS;
-			const uint32_t v = r[10] & ~RT_FLAGS_ALL;
-			if (v >= pixels) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: virtual pixel %u beyond the %zu pixels of the frames", i, v, pixels);
-			if (seen[v >> 3] & (1u << (v & 7))) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: virtual pixel %u appears twice", i, v);
-			seen[v >> 3] |= uint8_t(1u << (v & 7));
-			const int32_t mesh_id = int32_t(r[6]), triangle_id = int32_t(r[7]);
-			if (triangle_id != RT_INVALID) {
-				if (triangle_id < 0 || size_t(triangle_id) >= ctx->triangle_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: triangle id %d beyond the %zu triangles", i, triangle_id, ctx->triangle_count);
-				if (mesh_id < 0 || size_t(mesh_id) >= ctx->mesh_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: mesh id %d beyond the %zu instances", i, mesh_id, ctx->mesh_count);
-			}
-			if (r[10] & RT_FLAG_INSIDE_MEDIUM) {
-				const int32_t medium = int32_t(r[15]);
-				if (medium < 0 || size_t(medium) >= ctx->medium_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: medium id %d beyond the %zu media", i, medium, ctx->medium_count);
-			}
-			if (merged) {
-				const size_t slot = v / frame_pixels;
-				if (slot >= slot_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: slot %zu beyond the %zu slots of the table", i, slot, slot_count);
-				const int bounce = step - slot_table[4 * slot + 1];
-				if (bounce < 0 || bounce >= RT_MAX_BOUNCES || bounce >= ctx->params.config.num_bounces)
-					return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: bounce %d outside [0, min(RT_MAX_BOUNCES, num_bounces))", i, bounce);
-			}
-		}
-	}
-	RT_HIP(ctx, quiesce(ctx));
-	s = sky_sampling_prepare(ctx, "rt_sort_rays"); if (s) return s;   // (as a render settles it: it decides the instance)
-
-	TempBuffers tmp(ctx);
-	bool ok = true;
-	std::vector<uint32_t> column(std::max(capacity, size_t(1)) * 4);
-	// one component array of a queue: word `word` (`words` of them, consecutive) of `n` records of `stride` words; the rest of the array holds the sentinel
-	auto upload_column = [&](const uint32_t * records, size_t n, size_t stride, size_t word, size_t words) -> void * {
-		std::fill(column.begin(), column.begin() + capacity * words, sentinel);
-		for (size_t i = 0; i < n; i++) for (size_t w = 0; w < words; w++) column[i * words + w] = records[i * stride + word + w];
-		void * d = tmp.get(capacity * words * 4, column.data());
-		if (!d) ok = false;
-		return d;
-	};
-	auto download_column = [&](const void * device, uint32_t * records, size_t stride, size_t word, size_t words) -> bool {
-		if (hipMemcpy(column.data(), device, capacity * words * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
-		for (size_t i = 0; i < capacity; i++) for (size_t w = 0; w < words; w++) records[i * stride + word + w] = column[i * words + w];
-		return true;
-	};
-	auto vec3 = [&](const uint32_t * records, size_t n, size_t stride, size_t word) -> RtVec3SoA {
-		RtVec3SoA v; v.x = (float *)upload_column(records, n, stride, word, 1); v.y = (float *)upload_column(records, n, stride, word + 1, 1); v.z = (float *)upload_column(records, n, stride, word + 2, 1);
-		return v;
-	};
-	auto trace_buffer = [&](const uint32_t * records, size_t n) -> RtTraceBuffer {
-		const size_t W = RT_SORT_TRACE_WORDS;
-		RtTraceBuffer t = { };
-		t.origin = vec3(records, n, W, 0); t.direction = vec3(records, n, W, 3);
-		t.hits = (uint4 *)upload_column(records, n, W, 6, 4);
-		t.pixel_index_and_flags = (unsigned *)upload_column(records, n, W, 10, 1);
-		t.throughput = vec3(records, n, W, 11);
-		t.last_pdf = (float *)upload_column(records, n, W, 14, 1);
-		t.medium = (int *)upload_column(records, n, W, 15, 1);
-		t.cone_angle = (float *)upload_column(records, n, W, 16, 1); t.cone_width = (float *)upload_column(records, n, W, 17, 1);
-		return t;
-	};
-	const int q = step & 1;
-	RtTraceBuffer in = trace_buffer(trace_in, count), out = trace_buffer(nullptr, 0);
-	RtMaterialBuffer material[4];
-	for (RtMaterialBuffer & m : material) {
-		m = { };
-		m.direction = vec3(nullptr, 0, 0, 0); m.hits = (uint4 *)upload_column(nullptr, 0, 0, 0, 4);
-		m.pixel_index_and_flags = (unsigned *)upload_column(nullptr, 0, 0, 0, 1); m.throughput = vec3(nullptr, 0, 0, 0);
-		m.medium = (int *)upload_column(nullptr, 0, 0, 0, 1);
-		m.cone_angle = (float *)upload_column(nullptr, 0, 0, 0, 1); m.cone_width = (float *)upload_column(nullptr, 0, 0, 0, 1);
-	}
-	float4 * frames[4]; const int frame_aov[4] = { RT_AOV_RADIANCE, RT_AOV_RADIANCE_DIRECT, RT_AOV_RADIANCE_INDIRECT, RT_AOV_ALBEDO };
-	for (int k = 0; k < 4; k++) { frames[k] = (float4 *)tmp.get(pixels * 16, aov_frames + size_t(k) * pixels * 4); ok = ok && frames[k]; }
-	float4 * g_nd = (float4 *)tmp.get(pixels * 16, gbuffer_normal_and_depth);
-	int2 * g_id = (int2 *)tmp.get(pixels * 8, gbuffer_mesh_id_and_triangle_id);
-	float2 * g_sp = (float2 *)tmp.get(pixels * 8, gbuffer_screen_position_prev);
-	int * query = (int *)tmp.get(8, pixel_query2);
-	RtBufferSizes * sizes = nullptr; RtStreamControl * control = nullptr; RtStreamTable * table = nullptr;
-	if (merged) {
-		std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());
-		control_host->trace_count[q] = int(count);
-		control = (RtStreamControl *)tmp.get(sizeof(RtStreamControl), control_host.get());
-		std::unique_ptr<RtStreamTable> table_host(new RtStreamTable());
-		memcpy(table_host->slots, slot_table, slot_count * sizeof(RtStreamSlot));
-		memcpy(table_host->submission_birth, submission_birth, sizeof(table_host->submission_birth));
-		table = (RtStreamTable *)tmp.get(sizeof(RtStreamTable), table_host.get());
-		ok = ok && control && table;
-	} else {
-		RtBufferSizes sizes_host = { };
-		sizes_host.trace[step] = int(count);
-		sizes = (RtBufferSizes *)tmp.get(sizeof(RtBufferSizes), &sizes_host);
-		ok = ok && sizes;
-	}
-	if (!ok || !g_nd || !g_id || !g_sp || !query) return fail(ctx, RT_ERROR_HIP, "rt_sort_rays: device allocation failed");
-
-	RtParams p = merged ? stream_params(ctx, step) : ctx->params;
-	p.trace[q] = in; p.trace[q ^ 1] = out;
-	for (int m = 0; m < 4; m++) p.material[m] = material[m];
-	p.sizes = sizes; p.stream = control; p.stream_table = table;
-	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = nullptr;
-	for (int k = 0; k < 4; k++) if (ctx->aov_buffers[frame_aov[k]][0]) p.aovs[frame_aov[k]].framebuffer = frames[k];
-	p.gbuffer_normal_and_depth = g_nd; p.gbuffer_mesh_id_and_triangle_id = g_id; p.gbuffer_screen_position_prev = g_sp;
-	p.pixel_query_out = query;
-	if (merged) rt_launch_sort_stream(p, ctx->stream); else rt_launch_sort(p, step, sample_index, ctx->stream);
-	RT_HIP(ctx, hipGetLastError());
-	RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-
-	const size_t TW = RT_SORT_TRACE_WORDS, MW = RT_SORT_MATERIAL_WORDS;
-	for (size_t i = 0; i < capacity * TW; i++) trace_out[i] = sentinel;
-	for (size_t i = 0; i < 4 * capacity * MW; i++) material_out[i] = sentinel;
-	bool read = true;
-	const float * const out_vec[3][3] = { { out.origin.x, out.origin.y, out.origin.z }, { out.direction.x, out.direction.y, out.direction.z }, { out.throughput.x, out.throughput.y, out.throughput.z } };
-	const size_t out_word[3] = { 0, 3, 11 };
-	for (int v = 0; v < 3; v++) for (int c = 0; c < 3; c++) read = read && download_column(out_vec[v][c], trace_out, TW, out_word[v] + c, 1);
-	read = read && download_column(out.hits, trace_out, TW, 6, 4) && download_column(out.pixel_index_and_flags, trace_out, TW, 10, 1) && download_column(out.last_pdf, trace_out, TW, 14, 1)
-	            && download_column(out.medium, trace_out, TW, 15, 1) && download_column(out.cone_angle, trace_out, TW, 16, 1) && download_column(out.cone_width, trace_out, TW, 17, 1);
-	for (int m = 0; m < 4; m++) {
-		uint32_t * records = material_out + size_t(m) * capacity * MW;
-		const RtMaterialBuffer & b = material[m];
-		read = read && download_column(b.direction.x, records, MW, 0, 1) && download_column(b.direction.y, records, MW, 1, 1) && download_column(b.direction.z, records, MW, 2, 1)
-		            && download_column(b.hits, records, MW, 3, 4) && download_column(b.pixel_index_and_flags, records, MW, 7, 1)
-		            && download_column(b.throughput.x, records, MW, 8, 1) && download_column(b.throughput.y, records, MW, 9, 1) && download_column(b.throughput.z, records, MW, 10, 1)
-		            && download_column(b.medium, records, MW, 11, 1) && download_column(b.cone_angle, records, MW, 12, 1) && download_column(b.cone_width, records, MW, 13, 1);
-	}
-	if (!read) return fail(ctx, RT_ERROR_HIP, "rt_sort_rays: reading the queues back failed");
-	if (merged) {
-		std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());
-		RT_HIP(ctx, hipMemcpy(control_host.get(), control, sizeof(RtStreamControl), hipMemcpyDeviceToHost));
-		for (int m = 0; m < 4; m++) counters6[m] = control_host->material_count[m];
-		counters6[4] = control_host->trace_count[q ^ 1]; counters6[5] = control_host->trace_count[q];
-		memcpy(stats, control_host->stats, sizeof(control_host->stats));
-	} else {
-		RtBufferSizes sizes_host;
-		RT_HIP(ctx, hipMemcpy(&sizes_host, sizes, sizeof(RtBufferSizes), hipMemcpyDeviceToHost));
-		counters6[0] = sizes_host.diffuse[step]; counters6[1] = sizes_host.plastic[step]; counters6[2] = sizes_host.dielectric[step]; counters6[3] = sizes_host.conductor[step];
-		counters6[4] = step + 1 < RT_MAX_BOUNCES ? sizes_host.trace[step + 1] : 0; counters6[5] = sizes_host.trace[step];
-	}
-	for (int k = 0; k < 4; k++) RT_HIP(ctx, hipMemcpy(aov_frames + size_t(k) * pixels * 4, frames[k], pixels * 16, hipMemcpyDeviceToHost));
-	RT_HIP(ctx, hipMemcpy(gbuffer_normal_and_depth, g_nd, pixels * 16, hipMemcpyDeviceToHost));
-	RT_HIP(ctx, hipMemcpy(gbuffer_mesh_id_and_triangle_id, g_id, pixels * 8, hipMemcpyDeviceToHost));
-	RT_HIP(ctx, hipMemcpy(gbuffer_screen_position_prev, g_sp, pixels * 8, hipMemcpyDeviceToHost));
-	RT_HIP(ctx, hipMemcpy(pixel_query2, query, 8, hipMemcpyDeviceToHost));
-	return RT_OK;
-}
-
-int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps) {
-	RT_REQUIRE(ctx, ctx && out_gbps && bytes >= 1024, "rt_measure_stream_bandwidth: invalid argument");
-	(void)hipSetDevice(ctx->device);
-	TempBuffers tmp(ctx);
-	size_t count = bytes / 16;
-	float4 * src = (float4 *)tmp.get(count * 16, nullptr);
-	float * sink = (float *)tmp.get(16, nullptr);
-	if (!src || !sink) return fail(ctx, RT_ERROR_HIP, "rt_measure_stream_bandwidth: device allocation failed");
-	RT_HIP(ctx, hipMemsetAsync(src, 0x3c, count * 16, ctx->stream));
-	if (repeat < 1) repeat = 1;
-	hipEvent_t e0, e1; RT_HIP(ctx, hipEventCreate(&e0)); RT_HIP(ctx, hipEventCreate(&e1));
-	rt_launch_stream_read(src, count, sink, ctx->stream); // warm-up
-	float best = 1e30f;
-	for (int r = 0; r < repeat; r++) {
-		RT_HIP(ctx, hipEventRecord(e0, ctx->stream));
-		rt_launch_stream_read(src, count, sink, ctx->stream);
-		RT_HIP(ctx, hipEventRecord(e1, ctx->stream));
-		RT_HIP(ctx, quiesce(ctx));
-		float ms = 0.0f; RT_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
-		if (ms < best) best = ms;
-	}
-	(void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-	*out_gbps = float(double(count * 16) / (double(best) * 1e-3) / 1e9);
 	return RT_OK;
 }
 

@@ -1,0 +1,250 @@
+// rt_context.h -- what the units of the C ABI (rt_api.hip, rt_exchange.hip, rt_probes.hip) share: the context and the structs it is made of,
+// error handling, and the internal functions that cross a unit boundary. Private to csrc/.
+#pragma once
+#include "rt_types.h"
+
+#include <deque>
+#include <string>
+#include <vector>
+
+// Everything one sample per pixel owns while it is in flight. Up to RT_MAX_SAMPLE_SLOTS samples
+// are rendered concurrently (rt_set_samples_in_flight): consecutive rt_render_sample calls take the
+// slots round-robin, each on its own stream, and only the accumulate step is ordered between them.
+// Why: a wavefront pass is a chain of ~40 launches whose deep bounces are too small to fill 256 CUs
+// and whose persistent trace launches each end in a tail; a second sample's kernels fill those holes.
+#define RT_MAX_SAMPLE_SLOTS 8
+
+// The queues of one wavefront, `capacity` entries each: two trace queues (this bounce's and the next), one per material,
+// one of shadow rays. Each scheduler owns one set (SampleSlot, PathStream); queues_allocate / queues_free handle a set.
+struct WavefrontQueues {
+	RtTraceBuffer trace[2] = { }; RtMaterialBuffer material[4] = { }; RtShadowBuffer shadow = { };
+	size_t capacity = 0;
+	bool allocated = false;
+};
+
+struct SampleSlot {
+	bool created = false;
+	hipStream_t stream = nullptr;      // the sample's launch chain
+	hipStream_t side   = nullptr;      // shadow rays of bounce b, concurrent with the closest-hit trace of bounce b+1
+	hipEvent_t ev_shaded = nullptr, ev_shadowed = nullptr, ev_done = nullptr, ev_frame_start = nullptr, ev_frame_end = nullptr;
+	WavefrontQueues queues;
+	RtBufferSizes * sizes = nullptr;
+	int * ray_cursors = nullptr;
+	void * spill[2] = { nullptr, nullptr };  // traversal stack spill of the closest-hit / shadow launch
+	int * counter_totals = nullptr;          // 6 x RT_MAX_BOUNCES ints accumulated over batches
+	RtBufferSizes * pinned_counters = nullptr;
+	void * aov_framebuffer[RT_AOV_COUNT] = { };  // slots 1..: per-sample frame buffers (slot 0 uses ctx->aov_buffers[i][0])
+	int aov_samples = 1;                         // samples per batch the frame buffers of this slot are sized for
+	// SVGF g-buffers (normal+depth, mesh+triangle id, previous screen position) are written by the
+	// bounce-0 kernels of a frame and read by its filter stage: one set per slot lets frame n+1 be
+	// traced while frame n is filtered. Pixels that miss all geometry keep the value of the last
+	// frame that hit something (the reference never clears them), so a frame starts from a copy of
+	// its predecessor's set, taken as soon as that frame's bounce-0 shading is done (ev_gbuffers).
+	void * gbuffers[3] = { };                    // slots 1..; slot 0 uses ctx->svgf_buffers[0..2]
+	hipEvent_t ev_gbuffers = nullptr;
+};
+
+// Per-frame scene data (the TLAS and the five per-instance tables, rebuilt by Integrator::build_tlas for
+// every frame of an animated scene) lives in a ring of versions: an upload fills the next version
+// through pinned staging with an asynchronous copy, the kernels of later samples get its address (the
+// parameter block is passed by value), samples already in flight keep reading theirs. No upload of this
+// kind drains the pipeline; a version is only waited for when the ring wraps around onto a sample
+// that still uses it.
+#define RT_SCENE_VERSIONS 12
+struct SceneRing {
+	void * device[RT_SCENE_VERSIONS] = { };
+	void * pinned[RT_SCENE_VERSIONS] = { };
+	hipEvent_t copied[RT_SCENE_VERSIONS] = { };
+	size_t capacity = 0;   // bytes allocated per version (grows only)
+	size_t bytes = 0;      // bytes of the current version
+	int current = -1;
+	// Sample slots that have submitted work reading a version since it was last written. (A slot used to remember only the
+	// version of its LAST submission: with the host several frames ahead of the device, an older submission still queued
+	// on the same slot lost its claim and the ring wrapped around onto the version it was about to read -- found with 1 500
+	// moving instances and 48 frames, tools/animation_bench.py: a TLAS overwritten under a running traversal.)
+	unsigned users[RT_SCENE_VERSIONS] = { };
+	hipEvent_t last_use[RT_SCENE_VERSIONS][RT_MAX_SAMPLE_SLOTS] = { }; // end of the slot's latest submission that reads the version
+};
+
+// ---- merged wavefront (RT_SCHEDULER_MERGED; the idea is described at RtStreamSlot in rt_types.h) -------------------
+// Host side: ONE stream, one set of queues sized for `capacity` rays. A submission (one rt_render_samples call) gets a
+// run of sample slots, generates its primary rays into the current trace queue and advances the wavefront by one
+// iteration; it is complete -- accumulated into the shared accumulators, in submission order -- after the iteration in
+// which it reaches its last bounce. What bounds the queues: every path in flight occupies at most one entry of a
+// queue, paths only die, so (wavefront size reported by an earlier iteration) + (rays generated since) bounds the
+// entries any queue can receive; the host stays RT_STREAM_RUN_AHEAD iterations ahead of the device at most, reads the
+// reported sizes from pinned memory without blocking, and runs iterations without new samples while a new
+// submission would not fit.
+// Small submissions (the tiles of one rank of a multi-GPU split: 1/8 of a frame) would make small iterations again --
+// launches that do not fill the machine, fixed costs per iteration that no longer disappear behind the rays. When the
+// application pipelines frames (rt_set_frame_pipelining) a submission therefore generates its rays at once but the
+// iteration is only enqueued when RT_STREAM_BATCH_PATHS paths have been generated for it (or RT_STREAM_MAX_BATCH
+// submissions), so the iterations of a 1/8 split carry 8 frames and are as large as those of a whole frame. Anything that
+// needs progress -- rt_advance, every call that flushes, a change of camera -- enqueues the iteration with what is there.
+#define RT_STREAM_BATCH_PATHS     (1920 * 1080 * 4)
+#define RT_STREAM_MAX_BATCH       8
+#define RT_STREAM_PROGRESS_RING   64
+#define RT_STREAM_RUN_AHEAD       4
+#define RT_STREAM_TABLE_SNAPSHOTS 8
+#define RT_STREAM_HISTORY_ROWS    4096
+#define RT_STREAM_STATS_ROW       (RT_STAT_KINDS * RT_MAX_BOUNCES)   // ints per submission
+
+struct StreamSubmission {
+	int first_sample, sample_count, slot_base, ring, birth, last, paths;
+	int range_offset, range_count, tile_pixels, tile_first, tile_stride;
+};
+
+struct PathStream {
+	bool created = false;
+	hipStream_t stream = nullptr;
+	hipEvent_t ev_idle = nullptr;         // after the last completion enqueued so far: what main-stream consumers wait for
+	WavefrontQueues queues;
+	RtStreamControl * control = nullptr;
+	RtStreamTable * table_device = nullptr;
+	RtStreamTable table_host;             // what the device table will hold once the copies enqueued so far have run
+	RtStreamTable * table_staging = nullptr; hipEvent_t table_copied[RT_STREAM_TABLE_SNAPSHOTS] = { }; int table_next = 0;
+	void * spill = nullptr;
+	void * aov_framebuffer[RT_AOV_COUNT] = { }; int frame_slots = 0;   // per-sample frames, one per sample slot
+	void * gbuffers[3] = { };             // SVGF: one g-buffer set (float4, int2, float2 per pixel) per sample slot
+	int last_gbuffer_slot = -1;           // the set of the frame submitted last, if that was a frame of this wavefront
+	bool slot_used[RT_STREAM_SAMPLE_SLOTS] = { };
+	int next_slot = 0, next_ring = 0;
+	int iteration = 0;                    // the next iteration to enqueue
+	int base_iteration = 0;               // nothing generated before it is still in flight
+	std::deque<StreamSubmission> in_flight;
+	int pending = 0; long long pending_paths = 0;   // the newest submissions: rays generated, iteration not enqueued yet
+	// ... their slot-table entries and statistics rows reach the device ONCE, with the iteration that first needs them (one copy and the advance launch instead
+	// of a copy and a fill per submission: a rank of an 8-GPU split spent 0.1 ms of its 5.4 ms burst on five such pairs, profiles/r05_rank_timeline.txt)
+	bool table_dirty = false; int reset_ring_first = 0, reset_ring_count = 0;
+	int * progress = nullptr;             // pinned [RING][2] = { iteration, wavefront size }, written by kernel_stream_advance
+	hipEvent_t iteration_done[RT_STREAM_PROGRESS_RING] = { };
+	int generated[RT_STREAM_PROGRESS_RING] = { };
+	int known_iteration = -1; long long known_size = 0;
+	unsigned long long submissions_completed = 0;
+	int * stats_host = nullptr;           // pinned [RT_STREAM_SUBMISSIONS][RT_STREAM_STATS_ROW]
+	hipEvent_t ev_begin[RT_STREAM_SUBMISSIONS] = { }, ev_end[RT_STREAM_SUBMISSIONS] = { };
+	int last_completed_ring = -1;
+};
+
+struct rt_context {
+	int device = 0;
+	hipStream_t stream = nullptr;      // "main": uploads, read-backs, pack/unpack, kernel-level entry points
+	hipEvent_t ev_main = nullptr, ev_interop = nullptr;
+	std::string error;
+
+	SampleSlot slots[RT_MAX_SAMPLE_SLOTS];
+	// (Two such wavefronts taking the submissions in turns, their traversal launches serialised by an event chain so that
+	// one pipeline's sort / shade kernels would run beside the other's traversal, were built and measured: 3.23 ms per step
+	// against 3.02 ms with one -- the persistent traversal launch holds every wave slot of the machine until its queue is
+	// drained, nothing can start beside it. Removed; profiles/r02_two_pipelines_*.)
+	PathStream path_stream;
+	unsigned long long * stream_history = nullptr; int stream_history_rows = 0;   // pinned [ROWS][10]: trace statistics after each traversal launch
+	int scheduler = RT_SCHEDULER_MERGED;
+	bool last_render_merged = false;
+	bool defer_filter = false;         // rt_render_sample_unfiltered: an SVGF frame stops before its filter stage (tile split)
+	bool frame_pipelining = false;     // rt_pack_pixels / rt_unpack_pixels follow the completed submissions only (rt_set_frame_pipelining)
+	long long stream_batch_paths = 0;  // paths the submissions of one iteration may bring (rt_set_stream_batch); 0: RT_STREAM_BATCH_PATHS
+	int samples_in_flight = 3;
+	unsigned render_counter = 0;
+	int last_slot = -1;
+
+	RtParams params;               // zero-initialised in rt_create
+	std::vector<void *> owned;     // every hipMalloc'd pointer, freed in rt_destroy
+
+	// named allocations that get replaced on re-upload
+	void * triangles = nullptr, * triangle_positions = nullptr, * bvh8_nodes = nullptr, * bvh2_nodes = nullptr, * bvh4_nodes = nullptr;
+	size_t tlas_node_bytes = 80;        // what the current TLAS version was uploaded as (80 CWBVH, 32 binary, 128 4-wide)
+	int lowest_blas_root = 0x7fffffff;  // over the instances uploaded last: the node slots below it are free for the TLAS copy of the merged wavefront
+	unsigned long long tlas_version = 0, tlas_version_in_nodes = ~0ull;   // the merged wavefront traces a copy of the TLAS inside the BLAS node array (stream_sync_tlas)
+	bool expand_bc1 = true;   // rt_set_texture_expansion: BC1 textures are decoded once, at upload (rt_types.h: RT_TEXTURE_BC1_EXPANDED)
+	size_t texture_bytes = 0; // what rt_upload_textures holds on the device
+	std::vector<float> build_boxes; size_t build_boxes_first = 0;   // rt_set_build_boxes: consumed by the next rt_build_geometry
+	size_t bvh4_node_count = 0;
+	size_t bvh8_node_count = 0, bvh2_node_count = 0, triangle_count = 0;
+	size_t mesh_count = 0;
+	SceneRing tlas_ring, instance_ring, light_ring;
+	int * device_tlas_order = nullptr, * device_tlas_node_count = nullptr; // current TLAS built by rt_build_tlas (else null)
+	hipEvent_t ev_scene = nullptr;  // the last asynchronous scene upload on the main stream
+	void * material_types = nullptr, * materials = nullptr, * media = nullptr;
+	size_t medium_count = 0;                   // entries of rt_upload_media's table (rt_sort_rays checks medium ids against it)
+	bool has_material[4] = { false, false, false, false };
+	std::vector<uint8_t> material_type_list;   // what rt_upload_materials uploaded (rt_upload_material_normal_maps checks against it)
+	void * material_normal_maps = nullptr;     // int per material (rt_upload_material_normal_maps)
+	std::vector<int> texture_formats;          // the device format of every texture of rt_upload_textures
+	std::vector<RtTexture> texture_records;    // ... and its record (device pointer, size), as uploaded
+	// opacity masks (rt_upload_material_opacity): the two device tables and the bits of all masks in one allocation; host copies for rt_read_material_opacity
+	void * material_opacity = nullptr, * opacity_masks = nullptr, * opacity_bits = nullptr;
+	std::vector<int> material_opacity_list; std::vector<RtOpacityMask> opacity_mask_list;
+	bool has_lights = false;
+	void * texture_table = nullptr; std::vector<void *> texture_data;
+	void * pmj = nullptr, * blue_noise = nullptr;
+	void * sky = nullptr;
+	// sky importance sampling (rt_set_sky_sampling; kernels_sky.hip): the tables are built at the first render that wants them after rt_set_sky
+	float sky_sampling = 0.0f;               // 0: off (the reference's estimator); (0, 1]: the sky's share of the light samples when emitters exist
+	void * sky_tables = nullptr;             // floats: marginal CDF [H], conditional CDFs [H * W], cell pdfs [H * W]
+	void * sky_table_sums = nullptr;         // doubles: row totals [H], total [1]
+	bool sky_tables_ready = false;
+	double sky_total = 0.0;                  // the sum of the cell weights (0: a black sky, sampling stays inactive; not finite: an error)
+	void * luts[6] = { }; bool luts_ready = false;
+	int bvh_width = 8;
+
+	// frame resources
+	void * aov_buffers[RT_AOV_COUNT][2] = { };
+	void * final_image = nullptr;
+	void * svgf_buffers[16] = { }; bool svgf_allocated = false;   // [15]: RtParams::svgf_young_pixels
+	size_t frame_pixels = 0; // pitch * height
+
+	// frame exchange of the tile split (rt_comm_*): this context's rank in a group of `world` contexts, each on its own GPU
+	// (RCCL communicator) or, for tests on one GPU, several in one process (peer copies)
+	struct FrameExchange {
+		int rank = 0, world = 1;
+		void * comm = nullptr;                       // ncclComm_t
+		std::vector<rt_context *> peers;             // in-process transport: all contexts of the group, by rank
+		float4 * packed = nullptr, * gathered = nullptr; size_t packed_pixels = 0;   // per pixel `channels` float4
+		hipEvent_t ev_packed = nullptr, ev_copied = nullptr;
+	} exchange;
+
+	int * explicit_retired = nullptr;
+	int * pixel_query_out = nullptr;   // device { mesh_id, triangle_id }
+	int batch_size_request = 0;              // 0 = whole frame (288 GB of HBM: no reason to cut a frame into pieces)
+	int pixel_offset = 0, pixel_count = -1;  // -1 = whole frame
+
+	rt_counters last_counters;
+	bool profiling = false;          // mode 1: per-stage events, one sample at a time
+	bool launch_timing = false;      // mode 2: events around every traversal launch, concurrency untouched
+	bool launch_timing_all = false;  // mode 3: ... and around every other launch of the merged wavefront
+	bool time_this_sample = false;
+	std::vector<hipEvent_t> span_events; std::vector<int> span_kinds; size_t span_used = 0; // mode 2: [begin, end] pairs
+	bool trace_statistics = false;
+	unsigned long long * trace_stats = nullptr;    // device, 10 x u64
+	unsigned long long host_trace_stats[10] = { };
+	std::vector<hipEvent_t> stage_events; std::vector<int> stage_kinds; size_t stage_used = 0;
+};
+
+// Internal functions that cross a unit boundary, all defined in rt_api.hip (where each is described). Hidden: the library exports the C ABI only.
+// C linkage because some are defined between the entry points, inside their extern "C" blocks.
+#pragma GCC visibility push(hidden)
+extern "C" {
+int fail(rt_context * ctx, int status, const char * fmt, ...);
+int device_alloc(rt_context * ctx, void ** out, size_t bytes);
+void device_free(rt_context * ctx, void * p);
+hipError_t quiesce(rt_context * ctx);
+hipError_t main_waits_for_samples(rt_context * ctx);
+RtParams slot_params(const rt_context * ctx, const SampleSlot & slot, int index);
+int check_ready(rt_context * ctx, const char * caller, int needs);
+int sky_tables_build(rt_context * ctx, const char * caller);
+int sky_sampling_prepare(rt_context * ctx, const char * caller);
+int ensure_queues(rt_context * ctx, int slot_index = 0, size_t pixels = 0);
+int ensure_luts(rt_context * ctx);
+int stream_create(rt_context * ctx);
+RtParams stream_params(const rt_context * ctx, int iteration);
+int stream_sync_tlas(rt_context * ctx);
+}
+#pragma GCC visibility pop
+
+#define RT_HIP(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(ctx, RT_ERROR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
+#define RT_REQUIRE(ctx, cond, msg) do { if (!(cond)) return fail(ctx, RT_ERROR_INVALID_ARG, "%s", msg); } while (0)
+
+// What a render or trace entry point needs uploaded before it launches anything. NEED_SCENE reports missing geometry
+// and missing instances apart; NEED_SCENE_JOINT (the explicit-ray entry points) reports them as one.
+enum { NEED_SCENE = 1, NEED_SCENE_JOINT = 2, NEED_MATERIALS = 4, NEED_RNG = 8, NEED_SKY = 16, NEED_FRAME = 32 };

@@ -1,0 +1,547 @@
+// rt_probes.hip -- the kernel-level entry points of include/gpu_raytracer_amd.h ("probes"): one kernel, or one launch of a frame, on explicit
+// arguments, for the tests and for bench.py. All are synchronous.
+#include "rt_context.h"
+
+#include <algorithm>
+#include <cstring>
+#include <memory>
+
+// What every probe does around its launch, written once: device copies of the caller's arrays and device arrays for the results, ONE check that
+// they all exist, the end of the launch, the read-backs, and a pair of timing events. Everything is released on every path.
+namespace {
+struct Probe {
+	rt_context * ctx; const char * name;   // the entry point's, for its messages
+	std::vector<void *> arrays; bool failed = false;
+	hipEvent_t begin = nullptr, end = nullptr;
+	Probe(rt_context * c, const char * n) : ctx(c), name(n) { }
+	~Probe() { for (void * p : arrays) (void)hipFree(p); for (hipEvent_t e : { begin, end }) if (e) (void)hipEventDestroy(e); }
+	// `count` elements on the device: a copy of the caller's `src`, or room for a result (src == nullptr)
+	template<typename T> T * array(size_t count, const void * src = nullptr) {
+		void * p = nullptr; const size_t bytes = count * sizeof(T);
+		if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { failed = true; return nullptr; }
+		arrays.push_back(p);
+		if (src && bytes && hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) != hipSuccess) failed = true;
+		return (T *)p;
+	}
+	RtVec3SoA vec3(size_t count, const float * x, const float * y, const float * z) { return { array<float>(count, x), array<float>(count, y), array<float>(count, z) }; }
+	// the one check after the last array()
+	int allocated() { return failed ? fail(ctx, RT_ERROR_HIP, "%s: device allocation failed", name) : RT_OK; }
+	// after the launch: its error, then the wait -- for everything the context has in flight (the probes on the main stream), or for `own` alone
+	int finish(hipStream_t own = nullptr) {
+		RT_HIP(ctx, hipGetLastError());
+		if (own) RT_HIP(ctx, hipStreamSynchronize(own)); else RT_HIP(ctx, quiesce(ctx));
+		return RT_OK;
+	}
+	int read(void * dst, const void * src, size_t bytes) { RT_HIP(ctx, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); return RT_OK; }
+	int finish_and_read(void * dst, const void * src, size_t bytes) { int s = finish(); return s ? s : read(dst, src, bytes); }   // (main stream, one result)
+	// *ms: the time of `launch` (main stream), waited for
+	template<typename Launch> int time(float * ms, Launch && launch) {
+		if (!begin) RT_HIP(ctx, hipEventCreate(&begin));
+		if (!end) RT_HIP(ctx, hipEventCreate(&end));
+		RT_HIP(ctx, hipEventRecord(begin, ctx->stream));
+		launch();
+		RT_HIP(ctx, hipEventRecord(end, ctx->stream));
+		RT_HIP(ctx, quiesce(ctx));
+		RT_HIP(ctx, hipEventElapsedTime(ms, begin, end));
+		return RT_OK;
+	}
+};
+} // namespace
+
+// The repeat / timing loop of the explicit-ray entry points around `launch` (one traversal on the main stream):
+// *out_ms gets the mean time of `repeat` launches.
+template<typename Launch> static int time_explicit_launches(Probe & probe, int repeat, float * out_ms, Launch && launch) {
+	rt_context * ctx = probe.ctx;
+	if (repeat < 1) repeat = 1;
+	float total = 0.0f;
+	for (int r = 0; r < repeat; r++) {
+		RT_HIP(ctx, hipMemsetAsync(ctx->explicit_retired, 0, 8 * sizeof(int), ctx->stream));
+		float ms = 0.0f; int s = probe.time(&ms, launch); if (s) return s;
+		total += ms;
+	}
+	RT_HIP(ctx, hipGetLastError());
+	if (out_ms) *out_ms = total / float(repeat);
+	return RT_OK;
+}
+
+extern "C" {
+
+int rt_trace_rays(rt_context * ctx, const float * ox, const float * oy, const float * oz,
+                  const float * dx, const float * dy, const float * dz, size_t ray_count,
+                  uint32_t * hits, int repeat, float * out_ms) {
+	RT_REQUIRE(ctx, ctx && ox && oy && oz && dx && dy && dz && hits, "rt_trace_rays: NULL argument");
+	(void)hipSetDevice(ctx->device);
+	RT_HIP(ctx, quiesce(ctx)); // slot 0's spill area and cursors are borrowed
+	int s = check_ready(ctx, "rt_trace_rays", NEED_SCENE_JOINT); if (s) return s;
+	Probe probe(ctx, "rt_trace_rays");
+	RtVec3SoA o = probe.vec3(ray_count, ox, oy, oz), d = probe.vec3(ray_count, dx, dy, dz);
+	uint4 * dev_hits = probe.array<uint4>(ray_count);
+	if ((s = probe.allocated())) return s;
+	s = time_explicit_launches(probe, repeat, out_ms, [&] { rt_launch_trace_explicit(ctx->params, o, d, dev_hits, int(ray_count), ctx->explicit_retired, ctx->stream); }); if (s) return s;
+	return probe.read(hits, dev_hits, ray_count * 16);
+}
+
+int rt_trace_shadow_rays(rt_context * ctx, const float * ox, const float * oy, const float * oz,
+                         const float * dx, const float * dy, const float * dz, const float * max_distance,
+                         size_t ray_count, uint8_t * occluded, int repeat, float * out_ms) {
+	RT_REQUIRE(ctx, ctx && ox && oy && oz && dx && dy && dz && max_distance && occluded, "rt_trace_shadow_rays: NULL argument");
+	(void)hipSetDevice(ctx->device);
+	RT_HIP(ctx, quiesce(ctx)); // slot 0's spill area and cursors are borrowed
+	int s = check_ready(ctx, "rt_trace_shadow_rays", NEED_SCENE_JOINT); if (s) return s;
+	Probe probe(ctx, "rt_trace_shadow_rays");
+	RtVec3SoA o = probe.vec3(ray_count, ox, oy, oz), d = probe.vec3(ray_count, dx, dy, dz);
+	float * dev_max = probe.array<float>(ray_count, max_distance);
+	uint8_t * dev_occ = probe.array<uint8_t>(ray_count);
+	if ((s = probe.allocated())) return s;
+	s = time_explicit_launches(probe, repeat, out_ms, [&] { rt_launch_trace_shadow_explicit(ctx->params, o, d, dev_max, dev_occ, int(ray_count), ctx->explicit_retired, ctx->stream); }); if (s) return s;
+	return probe.read(occluded, dev_occ, ray_count);
+}
+
+// rt_trace_stream_rays: the merged wavefront's traversal launch (rt_launch_trace_stream, as stream_enqueue_iteration calls it) on explicit
+// rays. The parameter block is stream_params(ctx, iteration) with the closest-hit queue of parity iteration & 1, the shadow queue, the
+// control block and the radiance frame replaced by buffers of this call; every shadow ray i carries illumination (1, 0, 0) for pixel i,
+// so what the launch adds to pixel i tells how often ray i reached its light unoccluded. Runs on the wavefront's own stream with its own
+// spill area, after quiesce(); nothing of the context changes but what the scheduler would set up itself (stream_create, stream_sync_tlas).
+int rt_trace_stream_rays(rt_context * ctx, int iteration,
+                         const float * ox, const float * oy, const float * oz, const float * dx, const float * dy, const float * dz,
+                         size_t closest_count, uint32_t * hits,
+                         const float * sox, const float * soy, const float * soz, const float * sdx, const float * sdy, const float * sdz,
+                         const float * max_distance, size_t shadow_count, float * shadow_light,
+                         uint64_t * stats10, int32_t * info) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_trace_stream_rays: NULL context");
+	RT_REQUIRE(ctx, info != nullptr, "rt_trace_stream_rays: NULL info");
+	RT_REQUIRE(ctx, iteration >= 0, "rt_trace_stream_rays: negative iteration");
+	RT_REQUIRE(ctx, closest_count == 0 || (ox && oy && oz && dx && dy && dz && hits), "rt_trace_stream_rays: NULL closest-hit ray or hit array");
+	RT_REQUIRE(ctx, shadow_count == 0 || (sox && soy && soz && sdx && sdy && sdz && max_distance && shadow_light), "rt_trace_stream_rays: NULL shadow ray, max_distance or shadow_light array");
+	RT_REQUIRE(ctx, closest_count + shadow_count <= size_t(1) << 28, "rt_trace_stream_rays: more than 2^28 rays in one launch");
+	(void)hipSetDevice(ctx->device);
+	RT_HIP(ctx, quiesce(ctx)); // the wavefront's stream and spill area are borrowed
+	int s = check_ready(ctx, "rt_trace_stream_rays", NEED_SCENE_JOINT); if (s) return s;
+	if (ctx->params.bvh_width != 8) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_trace_stream_rays: the merged wavefront's launch walks the CWBVH (bvh_width %d)", ctx->params.bvh_width);
+	s = stream_create(ctx); if (s) return s;
+	s = stream_sync_tlas(ctx); if (s) return s;
+	PathStream & ps = ctx->path_stream;
+	const int q = iteration & 1;
+
+	Probe probe(ctx, "rt_trace_stream_rays");
+	RtTraceBuffer trace = { };
+	trace.origin = probe.vec3(closest_count, ox, oy, oz); trace.direction = probe.vec3(closest_count, dx, dy, dz);
+	trace.hits = probe.array<uint4>(closest_count, hits);   // the caller's values: a sentinel shows a ray the launch never dealt
+	std::vector<float4> light(shadow_count);
+	for (size_t i = 0; i < shadow_count; i++) {   // (i < 2^28: RT_SHADOW_FLAG_BOUNCE_0 clear)
+		uint32_t pixel_word = uint32_t(i); float w; memcpy(&w, &pixel_word, 4);
+		light[i] = make_float4(1.0f, 0.0f, 0.0f, w);
+	}
+	RtShadowBuffer shadow = { };
+	shadow.origin = probe.vec3(shadow_count, sox, soy, soz); shadow.direction = probe.vec3(shadow_count, sdx, sdy, sdz);
+	shadow.max_distance = probe.array<float>(shadow_count, max_distance);
+	shadow.illumination_and_pixel_index = probe.array<float4>(shadow_count, light.data());
+	float4 * radiance = probe.array<float4>(shadow_count);
+	std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());   // (value-initialised: zero cursors and region words)
+	control_host->trace_count[q] = int(closest_count);
+	control_host->shadow_count[q ^ 1] = int(shadow_count);
+	RtStreamControl * control = probe.array<RtStreamControl>(1, control_host.get());
+	unsigned long long * stats = stats10 ? probe.array<unsigned long long>(10) : nullptr;
+	if ((s = probe.allocated())) return s;
+	if (shadow_count) RT_HIP(ctx, hipMemset(radiance, 0, shadow_count * 16));
+	if (stats) RT_HIP(ctx, hipMemset(stats, 0, 10 * sizeof(unsigned long long)));
+
+	RtParams p = stream_params(ctx, iteration);
+	p.trace[q] = trace;
+	p.shadow = shadow;
+	p.stream = control;
+	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = nullptr;
+	p.aovs[RT_AOV_RADIANCE].framebuffer = radiance;
+	rt_trace_stream_launch_info(p, stats != nullptr, info);
+	rt_launch_trace_stream(p, stats, ps.stream);
+	if ((s = probe.finish(ps.stream))) return s;
+	if (closest_count && (s = probe.read(hits, trace.hits, closest_count * 16))) return s;
+	if (shadow_count) {
+		std::vector<float4> added(shadow_count);
+		if ((s = probe.read(added.data(), radiance, shadow_count * 16))) return s;
+		for (size_t i = 0; i < shadow_count; i++) shadow_light[i] = added[i].x;
+	}
+	return stats10 ? probe.read(stats10, stats, 10 * sizeof(unsigned long long)) : RT_OK;
+}
+
+int rt_generate_rays(rt_context * ctx, int sample_index, int pixel_offset, int pixel_count,
+                     float * ox, float * oy, float * oz, float * dx, float * dy, float * dz, uint32_t * pixel_index_and_flags) {
+	RT_REQUIRE(ctx, ctx && ox && oy && oz && dx && dy && dz && pixel_index_and_flags, "rt_generate_rays: NULL argument");
+	RT_REQUIRE(ctx, pixel_count >= 0, "rt_generate_rays: negative pixel_count");
+	(void)hipSetDevice(ctx->device);
+	if (!ctx->params.pmj_samples || ctx->frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_generate_rays: RNG tables not uploaded or rt_resize not called");
+	RT_HIP(ctx, quiesce(ctx)); // slot 0's queues are borrowed
+	int s = ensure_queues(ctx); if (s) return s;
+	if (size_t(pixel_count) > ctx->slots[0].queues.capacity) return fail(ctx, RT_ERROR_OUT_OF_RANGE, "rt_generate_rays: pixel_count %d exceeds the queue capacity %zu", pixel_count, ctx->slots[0].queues.capacity);
+	Probe probe(ctx, "rt_generate_rays");   // (no array of its own: the rays are read from slot 0's queue)
+	rt_launch_generate(ctx->params, sample_index, pixel_offset, pixel_count, ctx->stream);
+	if ((s = probe.finish())) return s;
+	const RtTraceBuffer & t = ctx->params.trace[0];
+	void * const dst[7] = { ox, oy, oz, dx, dy, dz, pixel_index_and_flags };
+	const void * const src[7] = { t.origin.x, t.origin.y, t.origin.z, t.direction.x, t.direction.y, t.direction.z, t.pixel_index_and_flags };
+	for (int i = 0; i < 7 && s == RT_OK; i++) s = probe.read(dst[i], src[i], size_t(pixel_count) * 4);
+	return s;
+}
+
+int rt_random_samples(rt_context * ctx, int dimension, const uint32_t * pixel_indices, size_t count, uint32_t bounce, uint32_t sample_index, float * out_xy) {
+	RT_REQUIRE(ctx, ctx && pixel_indices && out_xy && dimension >= 0 && dimension < 7, "rt_random_samples: invalid argument");
+	(void)hipSetDevice(ctx->device);
+	if (!ctx->params.pmj_samples || ctx->params.screen_pitch == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_random_samples: RNG tables not uploaded or rt_resize not called");
+	Probe probe(ctx, "rt_random_samples");
+	unsigned * dev_px = probe.array<unsigned>(count, pixel_indices);
+	float2 * dev_out = probe.array<float2>(count);
+	int s = probe.allocated(); if (s) return s;
+	rt_launch_random(ctx->params, dimension, dev_px, int(count), bounce, sample_index, dev_out, ctx->stream);
+	return probe.finish_and_read(out_xy, dev_out, count * 8);
+}
+
+int rt_sample_texture(rt_context * ctx, int texture_index, int filter, const float * args, size_t count, float * out_rgba) {
+	RT_REQUIRE(ctx, ctx && args && out_rgba, "rt_sample_texture: NULL argument");
+	RT_REQUIRE(ctx, texture_index >= 0 && size_t(texture_index) < ctx->texture_data.size(), "rt_sample_texture: texture index out of range");
+	RT_REQUIRE(ctx, filter >= 0 && filter <= 2, "rt_sample_texture: filter must be 0 (level 0), 1 (lod) or 2 (gradients)");
+	RT_REQUIRE(ctx, count <= size_t(1) << 28, "rt_sample_texture: more than 2^28 probes");
+	(void)hipSetDevice(ctx->device);
+	if (count == 0) return RT_OK;
+	Probe probe(ctx, "rt_sample_texture");
+	float * dev_args = probe.array<float>(count * 8, args);
+	float4 * dev_out = probe.array<float4>(count);
+	int s = probe.allocated(); if (s) return s;
+	rt_launch_sample_texture(ctx->params, texture_index, filter, dev_args, int(count), dev_out, ctx->stream);
+	return probe.finish_and_read(out_rgba, dev_out, count * 16);
+}
+
+int rt_sample_table(rt_context * ctx, const float * table, int nx, int ny, int nz, int dims, const float * coords, size_t count, float * out) {
+	RT_REQUIRE(ctx, ctx && table && coords && out, "rt_sample_table: NULL argument");
+	RT_REQUIRE(ctx, dims >= 1 && dims <= 3, "rt_sample_table: dims must be 1, 2 or 3");
+	RT_REQUIRE(ctx, nx >= 1 && nx <= 65536 && (dims < 2 || (ny >= 1 && ny <= 65536)) && (dims < 3 || (nz >= 1 && nz <= 65536)), "rt_sample_table: a table side is outside [1, 65536]");
+	RT_REQUIRE(ctx, count <= size_t(1) << 28, "rt_sample_table: more than 2^28 probes");
+	size_t entries = size_t(nx) * (dims >= 2 ? size_t(ny) : 1) * (dims >= 3 ? size_t(nz) : 1);
+	RT_REQUIRE(ctx, entries <= size_t(1) << 28, "rt_sample_table: more than 2^28 table entries");
+	(void)hipSetDevice(ctx->device);
+	if (count == 0) return RT_OK;
+	Probe probe(ctx, "rt_sample_table");
+	float * dev_table = probe.array<float>(entries, table);
+	float * dev_coords = probe.array<float>(count * 3, coords);
+	float * dev_out = probe.array<float>(count);
+	int s = probe.allocated(); if (s) return s;
+	rt_launch_sample_table(dev_table, nx, dims >= 2 ? ny : 1, dims >= 3 ? nz : 1, dims, dev_coords, int(count), dev_out, ctx->stream);
+	return probe.finish_and_read(out, dev_out, count * 4);
+}
+
+int rt_sample_sky(rt_context * ctx, const float * directions, size_t count, float * out_rgb) {
+	RT_REQUIRE(ctx, ctx && directions && out_rgb, "rt_sample_sky: NULL argument");
+	RT_REQUIRE(ctx, ctx->params.sky, "rt_sample_sky: no sky uploaded (rt_set_sky)");
+	RT_REQUIRE(ctx, count <= size_t(1) << 28, "rt_sample_sky: more than 2^28 probes");
+	(void)hipSetDevice(ctx->device);
+	if (count == 0) return RT_OK;
+	Probe probe(ctx, "rt_sample_sky");
+	float * dev_dirs = probe.array<float>(count * 3, directions);
+	float * dev_out = probe.array<float>(count * 3);
+	int s = probe.allocated(); if (s) return s;
+	rt_launch_sample_sky(ctx->params, dev_dirs, int(count), dev_out, ctx->stream);
+	return probe.finish_and_read(out_rgb, dev_out, count * 12);
+}
+
+int rt_sample_sky_distribution(rt_context * ctx, const float * uv, size_t count, float * out_xyz_pdf) {
+	RT_REQUIRE(ctx, ctx && uv && out_xyz_pdf, "rt_sample_sky_distribution: NULL argument");
+	RT_REQUIRE(ctx, ctx->params.sky, "rt_sample_sky_distribution: no sky uploaded (rt_set_sky)");
+	RT_REQUIRE(ctx, count <= size_t(1) << 28, "rt_sample_sky_distribution: more than 2^28 probes");
+	(void)hipSetDevice(ctx->device);
+	int s = sky_tables_build(ctx, "rt_sample_sky_distribution"); if (s) return s;
+	RT_REQUIRE(ctx, ctx->sky_total > 0.0, "rt_sample_sky_distribution: the sky has no weight to sample");
+	if (count == 0) return RT_OK;
+	Probe probe(ctx, "rt_sample_sky_distribution");
+	float * dev_uv = probe.array<float>(count * 2, uv);
+	float * dev_out = probe.array<float>(count * 4);
+	if ((s = probe.allocated())) return s;
+	rt_launch_sample_sky_distribution(ctx->params, dev_uv, int(count), dev_out, ctx->stream);
+	return probe.finish_and_read(out_xyz_pdf, dev_out, count * 16);
+}
+
+int rt_sky_pdf(rt_context * ctx, const float * directions, size_t count, float * out_pdf) {
+	RT_REQUIRE(ctx, ctx && directions && out_pdf, "rt_sky_pdf: NULL argument");
+	RT_REQUIRE(ctx, ctx->params.sky, "rt_sky_pdf: no sky uploaded (rt_set_sky)");
+	RT_REQUIRE(ctx, count <= size_t(1) << 28, "rt_sky_pdf: more than 2^28 probes");
+	(void)hipSetDevice(ctx->device);
+	int s = sky_tables_build(ctx, "rt_sky_pdf"); if (s) return s;
+	if (count == 0) return RT_OK;
+	Probe probe(ctx, "rt_sky_pdf");
+	float * dev_dirs = probe.array<float>(count * 3, directions);
+	float * dev_out = probe.array<float>(count);
+	if ((s = probe.allocated())) return s;
+	rt_launch_sky_pdf(ctx->params, dev_dirs, int(count), dev_out, ctx->stream);
+	return probe.finish_and_read(out_pdf, dev_out, count * 4);
+}
+
+// rt_bsdf_eval / rt_bsdf_sample: a copy of the parameters whose material table is the probes' own materials (probe i: material i),
+// with the Kulla-Conty tables of the context, no AOV and SVGF off, so that nothing of a frame is read or written.
+static int bsdf_probe(rt_context * ctx, const char * name, bool eval, int material_type, const float * probes, size_t count, float * out) {
+	if (!ctx || !probes || !out) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: NULL argument", name);
+	if (material_type < RT_MATERIAL_DIFFUSE || material_type > RT_MATERIAL_CONDUCTOR)
+		return fail(ctx, RT_ERROR_INVALID_ARG, "%s: material_type must be diffuse (1), plastic (2), dielectric (3) or conductor (4)", name);
+	if (count > size_t(1) << 24) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: more than 2^24 probes", name);
+	if (material_type == RT_MATERIAL_DIFFUSE || material_type == RT_MATERIAL_PLASTIC) {
+		for (size_t i = 0; i < count; i++) {
+			int32_t texture_id; memcpy(&texture_id, probes + i * RT_BSDF_PROBE_IN + 3, 4);
+			if (texture_id != RT_INVALID) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: probe %zu names texture %d (only RT_INVALID is probed)", name, i, texture_id);
+		}
+	}
+	(void)hipSetDevice(ctx->device);
+	if (!ctx->params.pmj_samples || ctx->params.screen_pitch == 0) return fail(ctx, RT_ERROR_NOT_READY, "%s: RNG tables not uploaded or rt_resize not called", name);
+	int s = ensure_luts(ctx); if (s) return s;
+	if (count == 0) return RT_OK;
+	std::vector<float> materials(count * 8);
+	for (size_t i = 0; i < count; i++) memcpy(&materials[i * 8], probes + i * RT_BSDF_PROBE_IN, 32);
+	Probe probe(ctx, name);
+	float * dev_materials = probe.array<float>(count * 8, materials.data());
+	float * dev_probes = probe.array<float>(count * RT_BSDF_PROBE_IN, probes);
+	float * dev_out = probe.array<float>(count * RT_BSDF_PROBE_OUT);
+	if ((s = probe.allocated())) return s;
+	RtParams p = ctx->params;
+	p.materials = (const float4 *)dev_materials;
+	p.textures = nullptr;
+	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = p.aovs[a].accumulator = nullptr;
+	p.config.enable_svgf = 0;
+	rt_launch_bsdf_probe(p, material_type, eval, dev_probes, int(count), dev_out, ctx->stream);
+	return probe.finish_and_read(out, dev_out, count * RT_BSDF_PROBE_OUT * 4);
+}
+
+int rt_bsdf_eval(rt_context * ctx, int material_type, const float * probes, size_t count, float * out) {
+	return bsdf_probe(ctx, "rt_bsdf_eval", true, material_type, probes, count, out);
+}
+int rt_bsdf_sample(rt_context * ctx, int material_type, const float * probes, size_t count, float * out) {
+	return bsdf_probe(ctx, "rt_bsdf_sample", false, material_type, probes, count, out);
+}
+
+int rt_sample_lights(rt_context * ctx, const float * probes, size_t count, int use_lds, float * out) {
+	RT_REQUIRE(ctx, ctx && probes && out, "rt_sample_lights: NULL argument");
+	RT_REQUIRE(ctx, count <= size_t(1) << 24, "rt_sample_lights: more than 2^24 probes");
+	RT_REQUIRE(ctx, use_lds == 0 || use_lds == 1, "rt_sample_lights: use_lds must be 0 (global memory) or 1 (as the shade kernels choose)");
+	const RtParams & p = ctx->params;
+	if (p.light_mesh_count <= 0 || p.light_triangle_count <= 0 || !(p.lights_total_weight > 0.0f))
+		return fail(ctx, RT_ERROR_NOT_READY, "rt_sample_lights: no lights uploaded (rt_upload_lights with at least one light mesh entry)");
+	if (!p.triangles || !p.mesh_transforms || !p.mesh_material_ids || !p.materials)
+		return fail(ctx, RT_ERROR_NOT_READY, "rt_sample_lights: geometry, instance tables or materials not uploaded");
+	for (size_t i = 0; i < count * 4; i++)   // (the searches end only for numbers up to the tables' last entry, 1)
+		if (!(probes[i] >= 0.0f && probes[i] < 1.0f)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sample_lights: probe %zu: random number %zu is %.9g, outside [0, 1)", i / 4, i % 4, double(probes[i]));
+	(void)hipSetDevice(ctx->device);
+	int s = sky_sampling_prepare(ctx, "rt_sample_lights"); if (s) return s;   // (as a render settles it; the selection does not read it)
+	if (count == 0) return RT_OK;
+	Probe probe(ctx, "rt_sample_lights");
+	float * dev_probes = probe.array<float>(count * 4, probes);
+	float * dev_out = probe.array<float>(count * RT_LIGHT_SAMPLE_OUT);
+	if ((s = probe.allocated())) return s;
+	rt_launch_sample_lights(p, dev_probes, int(count), use_lds != 0, dev_out, ctx->stream);
+	return probe.finish_and_read(out, dev_out, count * RT_LIGHT_SAMPLE_OUT * 4);
+}
+
+int rt_perturb_normals(rt_context * ctx, int texture_index, const float * probes, size_t count, float * out) {
+	RT_REQUIRE(ctx, ctx && probes && out, "rt_perturb_normals: NULL argument");
+	RT_REQUIRE(ctx, texture_index >= 0 && size_t(texture_index) < ctx->texture_formats.size(), "rt_perturb_normals: texture index out of range");
+	RT_REQUIRE(ctx, ctx->texture_formats[texture_index] == RT_TEXTURE_RGBA8, "rt_perturb_normals: the map must be an RT_TEXTURE_RGBA8 texture");
+	RT_REQUIRE(ctx, count <= size_t(1) << 24, "rt_perturb_normals: more than 2^24 probes");
+	for (size_t i = 0; i < count; i++) {
+		float filter = probes[i * RT_NORMAL_PROBE_IN + 41];
+		RT_REQUIRE(ctx, filter == 0.0f || filter == 1.0f || filter == 2.0f, "rt_perturb_normals: filter must be 0 (level 0), 1 (lod) or 2 (gradients)");
+	}
+	(void)hipSetDevice(ctx->device);
+	if (count == 0) return RT_OK;
+	Probe probe(ctx, "rt_perturb_normals");
+	float * dev_probes = probe.array<float>(count * RT_NORMAL_PROBE_IN, probes);
+	float * dev_out = probe.array<float>(count * 4);
+	int s = probe.allocated(); if (s) return s;
+	rt_launch_perturb_normals(ctx->params, texture_index, dev_probes, int(count), dev_out, ctx->stream);
+	return probe.finish_and_read(out, dev_out, count * 16);
+}
+
+// rt_sort_rays: the sort launch (rt_launch_sort or rt_launch_sort_stream, as the per-bounce loop and stream_enqueue_iteration call them) on an
+// explicit trace queue. The parameter block is the context's (ctx->params, or stream_params(ctx, iteration)) with both trace queues, the four
+// material queues, the counters (RtBufferSizes) or the control block and slot table, the AOV frames, the g-buffers and the pixel-query word
+// replaced by buffers of this call, every output array filled with the caller's sentinel. Runs on the main stream after quiesce().
+int rt_sort_rays(rt_context * ctx, int merged, int step, int sample_index, const uint32_t * trace_in, size_t count,
+                 const int32_t * slot_table, size_t slot_count, const int32_t * submission_birth,
+                 size_t capacity, size_t frame_slots, uint32_t sentinel,
+                 uint32_t * trace_out, uint32_t * material_out, int32_t * counters6,
+                 float * aov_frames, float * gbuffer_normal_and_depth, int32_t * gbuffer_mesh_id_and_triangle_id, float * gbuffer_screen_position_prev,
+                 int32_t * pixel_query2, int32_t * stats) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_sort_rays: NULL context");
+	RT_REQUIRE(ctx, merged == 0 || merged == 1, "rt_sort_rays: merged must be 0 (per-bounce launch) or 1 (merged wavefront)");
+	RT_REQUIRE(ctx, (trace_in || count == 0) && trace_out && material_out && counters6 && aov_frames && gbuffer_normal_and_depth &&
+	                gbuffer_mesh_id_and_triangle_id && gbuffer_screen_position_prev && pixel_query2, "rt_sort_rays: NULL array");
+	RT_REQUIRE(ctx, !merged || (slot_table && submission_birth && stats), "rt_sort_rays: NULL slot table, submission births or statistics (merged form)");
+	RT_REQUIRE(ctx, step >= 0 && (merged || step < RT_MAX_BOUNCES), merged ? "rt_sort_rays: negative iteration" : "rt_sort_rays: bounce outside [0, RT_MAX_BOUNCES)");
+	RT_REQUIRE(ctx, capacity >= 1 && capacity <= size_t(1) << 28, "rt_sort_rays: capacity must be in [1, 2^28]");
+	RT_REQUIRE(ctx, count <= capacity, "rt_sort_rays: more entries than the queue capacity");
+	// a bounce the path length does not reach is refused too: beyond it the per-bounce counter of the next trace queue runs into the next array of RtBufferSizes
+	RT_REQUIRE(ctx, merged || step < ctx->params.config.num_bounces, "rt_sort_rays: bounce outside [0, num_bounces)");
+	(void)hipSetDevice(ctx->device);
+	int s = check_ready(ctx, "rt_sort_rays", NEED_SCENE_JOINT | NEED_MATERIALS | NEED_RNG | NEED_SKY | NEED_FRAME); if (s) return s;
+	const size_t frame_pixels = ctx->frame_pixels;
+	RT_REQUIRE(ctx, frame_slots >= 1 && frame_slots <= size_t(RT_STREAM_SAMPLE_SLOTS) && frame_slots * frame_pixels < size_t(1) << 30,
+	           "rt_sort_rays: frame_slots must be in [1, 512] and frame_slots * frame_pixels below 2^30");
+	RT_REQUIRE(ctx, !merged || (slot_count >= 1 && slot_count <= size_t(RT_STREAM_SAMPLE_SLOTS)), "rt_sort_rays: slot_count must be in [1, 512]");
+	const size_t pixels = frame_slots * frame_pixels;
+	if (merged) for (size_t k = 0; k < slot_count; k++) {
+		const int32_t * e = slot_table + 4 * k;
+		if (e[2] < 0 || e[2] >= RT_STREAM_SUBMISSIONS) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: slot %zu: submission %d outside [0, %d)", k, e[2], RT_STREAM_SUBMISSIONS);
+		if (e[1] != submission_birth[e[2]]) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: slot %zu: birth iteration %d is not its submission's (%d)", k, e[1], submission_birth[e[2]]);
+	}
+	{	// every index the kernel forms from an entry stays inside the call's buffers and the context's tables
+		std::vector<uint8_t> seen((pixels + 7) / 8, 0);
+		for (size_t i = 0; i < count; i++) {
+			const uint32_t * r = trace_in + i * RT_SORT_TRACE_WORDS;
+			const uint32_t v = r[10] & ~RT_FLAGS_ALL;
+			if (v >= pixels) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: virtual pixel %u beyond the %zu pixels of the frames", i, v, pixels);
+			if (seen[v >> 3] & (1u << (v & 7))) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: virtual pixel %u appears twice", i, v);
+			seen[v >> 3] |= uint8_t(1u << (v & 7));
+			const int32_t mesh_id = int32_t(r[6]), triangle_id = int32_t(r[7]);
+			if (triangle_id != RT_INVALID) {
+				if (triangle_id < 0 || size_t(triangle_id) >= ctx->triangle_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: triangle id %d beyond the %zu triangles", i, triangle_id, ctx->triangle_count);
+				if (mesh_id < 0 || size_t(mesh_id) >= ctx->mesh_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: mesh id %d beyond the %zu instances", i, mesh_id, ctx->mesh_count);
+			}
+			if (r[10] & RT_FLAG_INSIDE_MEDIUM) {
+				const int32_t medium = int32_t(r[15]);
+				if (medium < 0 || size_t(medium) >= ctx->medium_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: medium id %d beyond the %zu media", i, medium, ctx->medium_count);
+			}
+			if (merged) {
+				const size_t slot = v / frame_pixels;
+				if (slot >= slot_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: slot %zu beyond the %zu slots of the table", i, slot, slot_count);
+				const int bounce = step - slot_table[4 * slot + 1];
+				if (bounce < 0 || bounce >= RT_MAX_BOUNCES || bounce >= ctx->params.config.num_bounces)
+					return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: bounce %d outside [0, min(RT_MAX_BOUNCES, num_bounces))", i, bounce);
+			}
+		}
+	}
+	RT_HIP(ctx, quiesce(ctx));
+	s = sky_sampling_prepare(ctx, "rt_sort_rays"); if (s) return s;   // (as a render settles it: it decides the instance)
+
+	Probe probe(ctx, "rt_sort_rays");
+	std::vector<uint32_t> column(std::max(capacity, size_t(1)) * 4);
+	// one component array of a queue: word `word` (`words` of them, consecutive) of `n` records of `stride` words; the rest of the array holds the sentinel
+	auto upload_column = [&](const uint32_t * records, size_t n, size_t stride, size_t word, size_t words) -> void * {
+		std::fill(column.begin(), column.begin() + capacity * words, sentinel);
+		for (size_t i = 0; i < n; i++) for (size_t w = 0; w < words; w++) column[i * words + w] = records[i * stride + word + w];
+		return probe.array<uint32_t>(capacity * words, column.data());
+	};
+	auto download_column = [&](const void * device, uint32_t * records, size_t stride, size_t word, size_t words) -> bool {
+		if (probe.read(column.data(), device, capacity * words * 4)) return false;
+		for (size_t i = 0; i < capacity; i++) for (size_t w = 0; w < words; w++) records[i * stride + word + w] = column[i * words + w];
+		return true;
+	};
+	auto vec3 = [&](const uint32_t * records, size_t n, size_t stride, size_t word) -> RtVec3SoA {
+		RtVec3SoA v; v.x = (float *)upload_column(records, n, stride, word, 1); v.y = (float *)upload_column(records, n, stride, word + 1, 1); v.z = (float *)upload_column(records, n, stride, word + 2, 1);
+		return v;
+	};
+	auto trace_buffer = [&](const uint32_t * records, size_t n) -> RtTraceBuffer {
+		const size_t W = RT_SORT_TRACE_WORDS;
+		RtTraceBuffer t = { };
+		t.origin = vec3(records, n, W, 0); t.direction = vec3(records, n, W, 3);
+		t.hits = (uint4 *)upload_column(records, n, W, 6, 4);
+		t.pixel_index_and_flags = (unsigned *)upload_column(records, n, W, 10, 1);
+		t.throughput = vec3(records, n, W, 11);
+		t.last_pdf = (float *)upload_column(records, n, W, 14, 1);
+		t.medium = (int *)upload_column(records, n, W, 15, 1);
+		t.cone_angle = (float *)upload_column(records, n, W, 16, 1); t.cone_width = (float *)upload_column(records, n, W, 17, 1);
+		return t;
+	};
+	const int q = step & 1;
+	RtTraceBuffer in = trace_buffer(trace_in, count), out = trace_buffer(nullptr, 0);
+	RtMaterialBuffer material[4];
+	for (RtMaterialBuffer & m : material) {
+		m = { };
+		m.direction = vec3(nullptr, 0, 0, 0); m.hits = (uint4 *)upload_column(nullptr, 0, 0, 0, 4);
+		m.pixel_index_and_flags = (unsigned *)upload_column(nullptr, 0, 0, 0, 1); m.throughput = vec3(nullptr, 0, 0, 0);
+		m.medium = (int *)upload_column(nullptr, 0, 0, 0, 1);
+		m.cone_angle = (float *)upload_column(nullptr, 0, 0, 0, 1); m.cone_width = (float *)upload_column(nullptr, 0, 0, 0, 1);
+	}
+	float4 * frames[4]; const int frame_aov[4] = { RT_AOV_RADIANCE, RT_AOV_RADIANCE_DIRECT, RT_AOV_RADIANCE_INDIRECT, RT_AOV_ALBEDO };
+	for (int k = 0; k < 4; k++) frames[k] = probe.array<float4>(pixels, aov_frames + size_t(k) * pixels * 4);
+	float4 * g_nd = probe.array<float4>(pixels, gbuffer_normal_and_depth);
+	int2 * g_id = probe.array<int2>(pixels, gbuffer_mesh_id_and_triangle_id);
+	float2 * g_sp = probe.array<float2>(pixels, gbuffer_screen_position_prev);
+	int * query = probe.array<int>(2, pixel_query2);
+	RtBufferSizes * sizes = nullptr; RtStreamControl * control = nullptr; RtStreamTable * table = nullptr;
+	if (merged) {
+		std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());
+		control_host->trace_count[q] = int(count);
+		control = probe.array<RtStreamControl>(1, control_host.get());
+		std::unique_ptr<RtStreamTable> table_host(new RtStreamTable());
+		memcpy(table_host->slots, slot_table, slot_count * sizeof(RtStreamSlot));
+		memcpy(table_host->submission_birth, submission_birth, sizeof(table_host->submission_birth));
+		table = probe.array<RtStreamTable>(1, table_host.get());
+	} else {
+		RtBufferSizes sizes_host = { };
+		sizes_host.trace[step] = int(count);
+		sizes = probe.array<RtBufferSizes>(1, &sizes_host);
+	}
+	if ((s = probe.allocated())) return s;
+
+	RtParams p = merged ? stream_params(ctx, step) : ctx->params;
+	p.trace[q] = in; p.trace[q ^ 1] = out;
+	for (int m = 0; m < 4; m++) p.material[m] = material[m];
+	p.sizes = sizes; p.stream = control; p.stream_table = table;
+	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = nullptr;
+	for (int k = 0; k < 4; k++) if (ctx->aov_buffers[frame_aov[k]][0]) p.aovs[frame_aov[k]].framebuffer = frames[k];
+	p.gbuffer_normal_and_depth = g_nd; p.gbuffer_mesh_id_and_triangle_id = g_id; p.gbuffer_screen_position_prev = g_sp;
+	p.pixel_query_out = query;
+	if (merged) rt_launch_sort_stream(p, ctx->stream); else rt_launch_sort(p, step, sample_index, ctx->stream);
+	if ((s = probe.finish(ctx->stream))) return s;
+
+	const size_t TW = RT_SORT_TRACE_WORDS, MW = RT_SORT_MATERIAL_WORDS;
+	for (size_t i = 0; i < capacity * TW; i++) trace_out[i] = sentinel;
+	for (size_t i = 0; i < 4 * capacity * MW; i++) material_out[i] = sentinel;
+	bool read = true;
+	const float * const out_vec[3][3] = { { out.origin.x, out.origin.y, out.origin.z }, { out.direction.x, out.direction.y, out.direction.z }, { out.throughput.x, out.throughput.y, out.throughput.z } };
+	const size_t out_word[3] = { 0, 3, 11 };
+	for (int v = 0; v < 3; v++) for (int c = 0; c < 3; c++) read = read && download_column(out_vec[v][c], trace_out, TW, out_word[v] + c, 1);
+	read = read && download_column(out.hits, trace_out, TW, 6, 4) && download_column(out.pixel_index_and_flags, trace_out, TW, 10, 1) && download_column(out.last_pdf, trace_out, TW, 14, 1)
+	            && download_column(out.medium, trace_out, TW, 15, 1) && download_column(out.cone_angle, trace_out, TW, 16, 1) && download_column(out.cone_width, trace_out, TW, 17, 1);
+	for (int m = 0; m < 4; m++) {
+		uint32_t * records = material_out + size_t(m) * capacity * MW;
+		const RtMaterialBuffer & b = material[m];
+		read = read && download_column(b.direction.x, records, MW, 0, 1) && download_column(b.direction.y, records, MW, 1, 1) && download_column(b.direction.z, records, MW, 2, 1)
+		            && download_column(b.hits, records, MW, 3, 4) && download_column(b.pixel_index_and_flags, records, MW, 7, 1)
+		            && download_column(b.throughput.x, records, MW, 8, 1) && download_column(b.throughput.y, records, MW, 9, 1) && download_column(b.throughput.z, records, MW, 10, 1)
+		            && download_column(b.medium, records, MW, 11, 1) && download_column(b.cone_angle, records, MW, 12, 1) && download_column(b.cone_width, records, MW, 13, 1);
+	}
+	if (!read) return fail(ctx, RT_ERROR_HIP, "rt_sort_rays: reading the queues back failed");
+	if (merged) {
+		std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());
+		if ((s = probe.read(control_host.get(), control, sizeof(RtStreamControl)))) return s;
+		for (int m = 0; m < 4; m++) counters6[m] = control_host->material_count[m];
+		counters6[4] = control_host->trace_count[q ^ 1]; counters6[5] = control_host->trace_count[q];
+		memcpy(stats, control_host->stats, sizeof(control_host->stats));
+	} else {
+		RtBufferSizes sizes_host;
+		if ((s = probe.read(&sizes_host, sizes, sizeof(RtBufferSizes)))) return s;
+		counters6[0] = sizes_host.diffuse[step]; counters6[1] = sizes_host.plastic[step]; counters6[2] = sizes_host.dielectric[step]; counters6[3] = sizes_host.conductor[step];
+		counters6[4] = step + 1 < RT_MAX_BOUNCES ? sizes_host.trace[step + 1] : 0; counters6[5] = sizes_host.trace[step];
+	}
+	for (int k = 0; k < 4 && s == RT_OK; k++) s = probe.read(aov_frames + size_t(k) * pixels * 4, frames[k], pixels * 16);
+	if (s || (s = probe.read(gbuffer_normal_and_depth, g_nd, pixels * 16)) || (s = probe.read(gbuffer_mesh_id_and_triangle_id, g_id, pixels * 8))
+	      || (s = probe.read(gbuffer_screen_position_prev, g_sp, pixels * 8))) return s;
+	return probe.read(pixel_query2, query, 8);
+}
+
+int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps) {
+	RT_REQUIRE(ctx, ctx && out_gbps && bytes >= 1024, "rt_measure_stream_bandwidth: invalid argument");
+	(void)hipSetDevice(ctx->device);
+	Probe probe(ctx, "rt_measure_stream_bandwidth");
+	size_t count = bytes / 16;
+	float4 * src = probe.array<float4>(count);
+	float * sink = probe.array<float>(4);
+	int s = probe.allocated(); if (s) return s;
+	RT_HIP(ctx, hipMemsetAsync(src, 0x3c, count * 16, ctx->stream));
+	if (repeat < 1) repeat = 1;
+	rt_launch_stream_read(src, count, sink, ctx->stream); // warm-up
+	float best = 1e30f;
+	for (int r = 0; r < repeat; r++) {
+		float ms = 0.0f;
+		s = probe.time(&ms, [&] { rt_launch_stream_read(src, count, sink, ctx->stream); }); if (s) return s;
+		if (ms < best) best = ms;
+	}
+	*out_gbps = float(double(count * 16) / (double(best) * 1e-3) / 1e9);
+	return RT_OK;
+}
+
+} // extern "C"

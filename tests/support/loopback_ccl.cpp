@@ -1,10 +1,10 @@
 // loopback_ccl.cpp -- TEST INFRASTRUCTURE ONLY: a stand-in for librccl.so that lets TWO OR MORE PROCESSES THAT SHARE ONE GPU run the product's native frame
 // exchange (rt_comm_unique_id -> rt_comm_init_rank(rank, world) -> rt_all_gather_framebuffer: pack kernel, ncclAllGather on the context's stream, unpack
-// kernel; gpu-raytracer_amd/csrc/rt_api.hip) with world > 1 on a test box that has one MI355X. RCCL refuses a device twice in one communicator, so on such a
+// kernel; gpu-raytracer_amd/csrc/rt_exchange.hip) with world > 1 on a test box that has one MI355X. RCCL refuses a device twice in one communicator, so on such a
 // box the real ncclAllGather only ever runs in a communicator of one rank (tests/test_gpu_rccl.py); this library implements the same eight entry points with the
 // semantics the product relies on -- rank r's `count` elements land at recvbuff + r * count on every rank, ordered behind the work already on `stream` -- by
 // staging each rank's chunk through a file in /dev/shm. It exists so that the FIRST time rank 1's tiles arrive in rank 0's frame is a test, not the first 8-GPU
-// run. Selected with GRT_COLLECTIVE_LIBRARY=<path of this .so> (rt_api.hip: rccl_api); never loaded otherwise; nothing under gpu-raytracer_amd/ links it.
+// run. Selected with GRT_COLLECTIVE_LIBRARY=<path of this .so> (rt_exchange.hip: rccl_api); never loaded otherwise; nothing under gpu-raytracer_amd/ links it.
 // Not a performance path: every call synchronises the stream and copies through the host.
 //   hipcc -O2 -fPIC -shared -o tests/support/libloopback_ccl.so tests/support/loopback_ccl.cpp      (tests/support/Makefile, __graft_entry__.build())
 #include <hip/hip_runtime.h>
