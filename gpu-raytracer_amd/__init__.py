@@ -92,6 +92,7 @@ def device_lib():
         lib.rt_bsdf_sample.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p]
         lib.rt_sample_lights.argtypes = [c_void_p, c_void_p, c_size_t, c_int, c_void_p]
         lib.rt_sort_rays.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_uint32] + [c_void_p] * 9
+        lib.rt_shade_rays.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_uint32] + [c_void_p] * 8
         lib.rt_upload_lights.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_float]
         lib.rt_upload_material_normal_maps.argtypes = [c_void_p, c_void_p, c_size_t]
         lib.rt_set_bvh_type.argtypes = [c_void_p, c_int]
@@ -1036,6 +1037,46 @@ def sort_rays(ctx, trace_in, frame_pixels, frame_slots, bounce=None, sample_inde
                                               capacity, int(frame_slots), int(sentinel), r.trace_out.ctypes.data, r.material_out.ctypes.data, r.counters.ctypes.data,
                                               r.aov.ctypes.data, r.gbuffer_normal_and_depth.ctypes.data, r.gbuffer_ids.ctypes.data, r.gbuffer_screen_prev.ctypes.data,
                                               r.pixel_query.ctypes.data, r.stats.ctypes.data if merged else None))
+    return r
+
+
+SHADE_SHADOW_WORDS = 11   # RT_SHADE_SHADOW_WORDS
+
+
+class ShadeResult:
+    """What one material launch left behind (rt_shade_rays), every array read back whole as uint32 words: trace_out (capacity, 20), the next
+    trace queue; shadow_out (capacity, 11) {origin, direction, max_distance, illumination, pixel word}; counters int32[3] {next trace,
+    shadow, this material queue}; aov (3, P, 4) (ALBEDO, NORMAL, POSITION); gbuffer_normal_and_depth (P, 4), gbuffer_ids (P, 2),
+    gbuffer_screen_prev (P, 2); stats (128, 6, 128) int32 (merged form, else None). A word the launch did not write holds the sentinel."""
+
+
+def shade_rays(ctx, material_slot, material_in, frame_pixels, frame_slots, bounce=None, sample_index=0, iteration=None, slot_table=None, submission_birth=None,
+               capacity=None, sentinel=0xFFC0DE42):
+    """rt_shade_rays: the production material launch of queue `material_slot` on explicit entries. material_in: (N, 16) uint32 records, one
+    of the queues of SortResult.material_out. Per-bounce form: bounce and sample_index; merged form: iteration, slot_table (S, 4) int32 and
+    submission_birth int32[128]. The frames hold frame_slots * frame_pixels pixels."""
+    m = np.ascontiguousarray(material_in, np.uint32).reshape(-1, SORT_MATERIAL_WORDS)
+    n = m.shape[0]
+    merged = iteration is not None
+    capacity = max(n, 1) if capacity is None else int(capacity)
+    pixels = int(frame_pixels) * int(frame_slots)
+    r = ShadeResult()
+    r.trace_out = np.zeros((capacity, SORT_TRACE_WORDS), np.uint32)
+    r.shadow_out = np.zeros((capacity, SHADE_SHADOW_WORDS), np.uint32)
+    r.counters = np.zeros(3, np.int32)
+    r.aov = np.zeros((3, pixels, 4), np.uint32)
+    r.gbuffer_normal_and_depth = np.zeros((pixels, 4), np.uint32)
+    r.gbuffer_ids = np.zeros((pixels, 2), np.uint32)
+    r.gbuffer_screen_prev = np.zeros((pixels, 2), np.uint32)
+    r.stats = np.zeros((STREAM_SUBMISSIONS, STAT_KINDS, MAX_BOUNCES), np.int32) if merged else None
+    if merged:
+        slots = np.ascontiguousarray(slot_table, np.int32).reshape(-1, 4)
+        births = np.ascontiguousarray(submission_birth, np.int32).reshape(STREAM_SUBMISSIONS)
+    _dev_check(ctx, device_lib().rt_shade_rays(ctx, 1 if merged else 0, int(iteration if merged else bounce), int(sample_index), int(material_slot), m.ctypes.data if n else None, n,
+                                               slots.ctypes.data if merged else None, slots.shape[0] if merged else 0, births.ctypes.data if merged else None,
+                                               capacity, int(frame_slots), int(sentinel), r.trace_out.ctypes.data, r.shadow_out.ctypes.data, r.counters.ctypes.data,
+                                               r.aov.ctypes.data, r.gbuffer_normal_and_depth.ctypes.data, r.gbuffer_ids.ctypes.data, r.gbuffer_screen_prev.ctypes.data,
+                                               r.stats.ctypes.data if merged else None))
     return r
 
 

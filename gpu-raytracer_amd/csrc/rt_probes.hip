@@ -34,6 +34,26 @@ struct Probe {
 	}
 	int read(void * dst, const void * src, size_t bytes) { RT_HIP(ctx, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); return RT_OK; }
 	int finish_and_read(void * dst, const void * src, size_t bytes) { int s = finish(); return s ? s : read(dst, src, bytes); }   // (main stream, one result)
+	// One component array of a queue of `capacity` entries (the launch probes): word `word` (`words` of them, consecutive) of `n` records of `stride`
+	// 32-bit words; the rest of the array holds `sentinel`. records == nullptr: an output array, all sentinel.
+	void * column(const uint32_t * records, size_t n, size_t stride, size_t word, size_t words, size_t capacity, uint32_t sentinel) {
+		staging.assign(std::max(capacity, size_t(1)) * words, sentinel);
+		for (size_t i = 0; i < n; i++) for (size_t w = 0; w < words; w++) staging[i * words + w] = records[i * stride + word + w];
+		return array<uint32_t>(capacity * words, staging.data());
+	}
+	RtVec3SoA column3(const uint32_t * records, size_t n, size_t stride, size_t word, size_t capacity, uint32_t sentinel) {
+		RtVec3SoA v; v.x = (float *)column(records, n, stride, word, 1, capacity, sentinel); v.y = (float *)column(records, n, stride, word + 1, 1, capacity, sentinel);
+		v.z = (float *)column(records, n, stride, word + 2, 1, capacity, sentinel);
+		return v;
+	}
+	// ... and back: the whole array into word `word` of `capacity` records
+	bool column_back(const void * device, uint32_t * records, size_t stride, size_t word, size_t words, size_t capacity) {
+		staging.resize(std::max(capacity, size_t(1)) * words);
+		if (read(staging.data(), device, capacity * words * 4)) return false;
+		for (size_t i = 0; i < capacity; i++) for (size_t w = 0; w < words; w++) records[i * stride + word + w] = staging[i * words + w];
+		return true;
+	}
+	std::vector<uint32_t> staging;
 	// *ms: the time of `launch` (main stream), waited for
 	template<typename Launch> int time(float * ms, Launch && launch) {
 		if (!begin) RT_HIP(ctx, hipEventCreate(&begin));
@@ -416,22 +436,9 @@ int rt_sort_rays(rt_context * ctx, int merged, int step, int sample_index, const
 	s = sky_sampling_prepare(ctx, "rt_sort_rays"); if (s) return s;   // (as a render settles it: it decides the instance)
 
 	Probe probe(ctx, "rt_sort_rays");
-	std::vector<uint32_t> column(std::max(capacity, size_t(1)) * 4);
-	// one component array of a queue: word `word` (`words` of them, consecutive) of `n` records of `stride` words; the rest of the array holds the sentinel
-	auto upload_column = [&](const uint32_t * records, size_t n, size_t stride, size_t word, size_t words) -> void * {
-		std::fill(column.begin(), column.begin() + capacity * words, sentinel);
-		for (size_t i = 0; i < n; i++) for (size_t w = 0; w < words; w++) column[i * words + w] = records[i * stride + word + w];
-		return probe.array<uint32_t>(capacity * words, column.data());
-	};
-	auto download_column = [&](const void * device, uint32_t * records, size_t stride, size_t word, size_t words) -> bool {
-		if (probe.read(column.data(), device, capacity * words * 4)) return false;
-		for (size_t i = 0; i < capacity; i++) for (size_t w = 0; w < words; w++) records[i * stride + word + w] = column[i * words + w];
-		return true;
-	};
-	auto vec3 = [&](const uint32_t * records, size_t n, size_t stride, size_t word) -> RtVec3SoA {
-		RtVec3SoA v; v.x = (float *)upload_column(records, n, stride, word, 1); v.y = (float *)upload_column(records, n, stride, word + 1, 1); v.z = (float *)upload_column(records, n, stride, word + 2, 1);
-		return v;
-	};
+	auto upload_column = [&](const uint32_t * records, size_t n, size_t stride, size_t word, size_t words) { return probe.column(records, n, stride, word, words, capacity, sentinel); };
+	auto download_column = [&](const void * device, uint32_t * records, size_t stride, size_t word, size_t words) { return probe.column_back(device, records, stride, word, words, capacity); };
+	auto vec3 = [&](const uint32_t * records, size_t n, size_t stride, size_t word) { return probe.column3(records, n, stride, word, capacity, sentinel); };
 	auto trace_buffer = [&](const uint32_t * records, size_t n) -> RtTraceBuffer {
 		const size_t W = RT_SORT_TRACE_WORDS;
 		RtTraceBuffer t = { };
@@ -521,6 +528,151 @@ int rt_sort_rays(rt_context * ctx, int merged, int step, int sample_index, const
 	if (s || (s = probe.read(gbuffer_normal_and_depth, g_nd, pixels * 16)) || (s = probe.read(gbuffer_mesh_id_and_triangle_id, g_id, pixels * 8))
 	      || (s = probe.read(gbuffer_screen_position_prev, g_sp, pixels * 8))) return s;
 	return probe.read(pixel_query2, query, 8);
+}
+
+// rt_shade_rays: the material launch (rt_launch_material or rt_launch_material_stream, as the per-bounce loop and stream_enqueue_iteration call them) on an
+// explicit material queue. The parameter block is the context's (ctx->params, or stream_params(ctx, iteration)) with the material queue of `material_slot`,
+// the next trace queue, the shadow queue, the counters (RtBufferSizes) or the control block and slot table, the ALBEDO / NORMAL / POSITION frames and the
+// g-buffers replaced by buffers of this call, every one filled with the caller's sentinel. Runs on the main stream after quiesce().
+int rt_shade_rays(rt_context * ctx, int merged, int step, int sample_index, int material_slot, const uint32_t * material_in, size_t count,
+                  const int32_t * slot_table, size_t slot_count, const int32_t * submission_birth,
+                  size_t capacity, size_t frame_slots, uint32_t sentinel,
+                  uint32_t * trace_out, uint32_t * shadow_out, int32_t * counters3,
+                  uint32_t * aov_frames, uint32_t * gbuffer_normal_and_depth, uint32_t * gbuffer_mesh_id_and_triangle_id, uint32_t * gbuffer_screen_position_prev,
+                  int32_t * stats) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_shade_rays: NULL context");
+	RT_REQUIRE(ctx, merged == 0 || merged == 1, "rt_shade_rays: merged must be 0 (per-bounce launch) or 1 (merged wavefront)");
+	RT_REQUIRE(ctx, material_slot >= 0 && material_slot < 4, "rt_shade_rays: material_slot must be 0 (diffuse), 1 (plastic), 2 (dielectric) or 3 (conductor)");
+	RT_REQUIRE(ctx, (material_in || count == 0) && trace_out && shadow_out && counters3 && aov_frames && gbuffer_normal_and_depth &&
+	                gbuffer_mesh_id_and_triangle_id && gbuffer_screen_position_prev, "rt_shade_rays: NULL array");
+	RT_REQUIRE(ctx, !merged || (slot_table && submission_birth && stats), "rt_shade_rays: NULL slot table, submission births or statistics (merged form)");
+	// (the per-bounce counter of the next trace queue is RtBufferSizes::trace[bounce + 1]: at RT_MAX_BOUNCES - 1 it would be the next array's first word)
+	RT_REQUIRE(ctx, step >= 0 && (merged || step < RT_MAX_BOUNCES - 1), merged ? "rt_shade_rays: negative iteration" : "rt_shade_rays: bounce outside [0, RT_MAX_BOUNCES - 1)");
+	RT_REQUIRE(ctx, capacity >= 1 && capacity <= size_t(1) << 28, "rt_shade_rays: capacity must be in [1, 2^28]");
+	RT_REQUIRE(ctx, count <= capacity, "rt_shade_rays: more entries than the queue capacity");
+	RT_REQUIRE(ctx, merged || step < ctx->params.config.num_bounces, "rt_shade_rays: bounce outside [0, num_bounces)");
+	(void)hipSetDevice(ctx->device);
+	int s = check_ready(ctx, "rt_shade_rays", NEED_SCENE_JOINT | NEED_MATERIALS | NEED_RNG | NEED_SKY | NEED_FRAME); if (s) return s;
+	const size_t frame_pixels = ctx->frame_pixels;
+	RT_REQUIRE(ctx, frame_slots >= 1 && frame_slots <= size_t(RT_STREAM_SAMPLE_SLOTS) && frame_slots * frame_pixels < size_t(1) << 30,
+	           "rt_shade_rays: frame_slots must be in [1, 512] and frame_slots * frame_pixels below 2^30");
+	RT_REQUIRE(ctx, !merged || (slot_count >= 1 && slot_count <= size_t(RT_STREAM_SAMPLE_SLOTS)), "rt_shade_rays: slot_count must be in [1, 512]");
+	const size_t pixels = frame_slots * frame_pixels;
+	if (merged) for (size_t k = 0; k < slot_count; k++) {
+		const int32_t * e = slot_table + 4 * k;
+		if (e[2] < 0 || e[2] >= RT_STREAM_SUBMISSIONS) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: slot %zu: submission %d outside [0, %d)", k, e[2], RT_STREAM_SUBMISSIONS);
+		if (e[1] != submission_birth[e[2]]) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: slot %zu: birth iteration %d is not its submission's (%d)", k, e[1], submission_birth[e[2]]);
+	}
+	RT_HIP(ctx, quiesce(ctx));
+	{	// every index the kernel forms from an entry stays inside the call's buffers and the context's tables, and the entry sits in its material's queue
+		std::vector<int32_t> mesh_material(ctx->mesh_count);
+		if (count) RT_HIP(ctx, hipMemcpy(mesh_material.data(), ctx->params.mesh_material_ids, ctx->mesh_count * 4, hipMemcpyDeviceToHost));
+		std::vector<uint8_t> seen((pixels + 7) / 8, 0);
+		for (size_t i = 0; i < count; i++) {
+			const uint32_t * r = material_in + i * RT_SORT_MATERIAL_WORDS;
+			const uint32_t v = r[7] & ~RT_FLAGS_ALL;
+			if (v >= pixels) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: entry %zu: virtual pixel %u beyond the %zu pixels of the frames", i, v, pixels);
+			if (seen[v >> 3] & (1u << (v & 7))) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: entry %zu: virtual pixel %u appears twice", i, v);
+			seen[v >> 3] |= uint8_t(1u << (v & 7));
+			const int32_t mesh_id = int32_t(r[3]), triangle_id = int32_t(r[4]);
+			if (triangle_id < 0 || size_t(triangle_id) >= ctx->triangle_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: entry %zu: triangle id %d beyond the %zu triangles", i, triangle_id, ctx->triangle_count);
+			if (mesh_id < 0 || size_t(mesh_id) >= ctx->mesh_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: entry %zu: mesh id %d beyond the %zu instances", i, mesh_id, ctx->mesh_count);
+			const int32_t material_id = mesh_material[mesh_id];
+			if (material_id < 0 || size_t(material_id) >= ctx->material_type_list.size() || int(ctx->material_type_list[material_id]) != RT_MATERIAL_DIFFUSE + material_slot)
+				return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: entry %zu: the material of instance %d (material %d) does not belong to queue %d", i, mesh_id, material_id, material_slot);
+			if (r[7] & RT_FLAG_INSIDE_MEDIUM) {
+				const int32_t medium = int32_t(r[11]);
+				if (medium < 0 || size_t(medium) >= ctx->medium_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: entry %zu: medium id %d beyond the %zu media", i, medium, ctx->medium_count);
+			}
+			if (merged) {
+				const size_t slot = v / frame_pixels;
+				if (slot >= slot_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: entry %zu: slot %zu beyond the %zu slots of the table", i, slot, slot_count);
+				const int bounce = step - slot_table[4 * slot + 1];
+				if (bounce < 0 || bounce >= RT_MAX_BOUNCES || bounce >= ctx->params.config.num_bounces)
+					return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: entry %zu: bounce %d outside [0, min(RT_MAX_BOUNCES, num_bounces))", i, bounce);
+			}
+		}
+	}
+	if (material_slot >= 2) { s = ensure_luts(ctx); if (s) return s; }   // (as a render settles them)
+	s = sky_sampling_prepare(ctx, "rt_shade_rays"); if (s) return s;   // (... and this: it decides the instance)
+
+	Probe probe(ctx, "rt_shade_rays");
+	const size_t MW = RT_SORT_MATERIAL_WORDS, TW = RT_SORT_TRACE_WORDS, SW = RT_SHADE_SHADOW_WORDS;
+	auto in_column = [&](size_t word, size_t words) { return probe.column(material_in, count, MW, word, words, capacity, sentinel); };
+	auto out_column = [&](size_t words) { return probe.column(nullptr, 0, 0, 0, words, capacity, sentinel); };
+	auto out_vec3 = [&]() { return probe.column3(nullptr, 0, 0, 0, capacity, sentinel); };
+	RtMaterialBuffer in = { };
+	in.direction = probe.column3(material_in, count, MW, 0, capacity, sentinel); in.hits = (uint4 *)in_column(3, 4);
+	in.pixel_index_and_flags = (unsigned *)in_column(7, 1); in.throughput = probe.column3(material_in, count, MW, 8, capacity, sentinel);
+	in.medium = (int *)in_column(11, 1); in.cone_angle = (float *)in_column(12, 1); in.cone_width = (float *)in_column(13, 1);
+	RtTraceBuffer out = { };
+	out.origin = out_vec3(); out.direction = out_vec3(); out.hits = (uint4 *)out_column(4); out.pixel_index_and_flags = (unsigned *)out_column(1);
+	out.throughput = out_vec3(); out.last_pdf = (float *)out_column(1); out.medium = (int *)out_column(1);
+	out.cone_angle = (float *)out_column(1); out.cone_width = (float *)out_column(1);
+	RtShadowBuffer shadow = { };
+	shadow.origin = out_vec3(); shadow.direction = out_vec3(); shadow.max_distance = (float *)out_column(1); shadow.illumination_and_pixel_index = (float4 *)out_column(4);
+	// the frames and g-buffers, all sentinel: 4 + 4 + 4 words per pixel (ALBEDO, NORMAL, POSITION), then 4, 2, 2
+	float4 * frames[3]; const int frame_aov[3] = { RT_AOV_ALBEDO, RT_AOV_NORMAL, RT_AOV_POSITION };
+	auto filled = [&](size_t words) { probe.staging.assign(pixels * words, sentinel); return probe.array<uint32_t>(pixels * words, probe.staging.data()); };
+	for (int k = 0; k < 3; k++) frames[k] = (float4 *)filled(4);
+	float4 * g_nd = (float4 *)filled(4); int2 * g_id = (int2 *)filled(2); float2 * g_sp = (float2 *)filled(2);
+	const int q = step & 1;
+	RtBufferSizes * sizes = nullptr; RtStreamControl * control = nullptr; RtStreamTable * table = nullptr;
+	if (merged) {
+		std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());
+		control_host->material_count[material_slot] = int(count);
+		control = probe.array<RtStreamControl>(1, control_host.get());
+		std::unique_ptr<RtStreamTable> table_host(new RtStreamTable());
+		memcpy(table_host->slots, slot_table, slot_count * sizeof(RtStreamSlot));
+		memcpy(table_host->submission_birth, submission_birth, sizeof(table_host->submission_birth));
+		table = probe.array<RtStreamTable>(1, table_host.get());
+	} else {
+		RtBufferSizes sizes_host = { };
+		(material_slot == 0 ? sizes_host.diffuse : material_slot == 1 ? sizes_host.plastic : material_slot == 2 ? sizes_host.dielectric : sizes_host.conductor)[step] = int(count);
+		sizes = probe.array<RtBufferSizes>(1, &sizes_host);
+	}
+	if ((s = probe.allocated())) return s;
+
+	RtParams p = merged ? stream_params(ctx, step) : ctx->params;
+	p.trace[q] = RtTraceBuffer { }; p.trace[q ^ 1] = out;   // (the launch appends to the next trace queue and never looks at this bounce's)
+	for (int m = 0; m < 4; m++) p.material[m] = RtMaterialBuffer { };
+	p.material[material_slot] = in;
+	p.shadow = shadow;
+	p.sizes = sizes; p.stream = control; p.stream_table = table;
+	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = nullptr;
+	for (int k = 0; k < 3; k++) if (ctx->aov_buffers[frame_aov[k]][0]) p.aovs[frame_aov[k]].framebuffer = frames[k];
+	p.gbuffer_normal_and_depth = g_nd; p.gbuffer_mesh_id_and_triangle_id = g_id; p.gbuffer_screen_position_prev = g_sp;
+	p.pixel_query_out = nullptr;
+	if (merged) rt_launch_material_stream(p, material_slot, ctx->stream); else rt_launch_material(p, material_slot, step, sample_index, ctx->stream);
+	if ((s = probe.finish(ctx->stream))) return s;
+
+	bool read = true;
+	const RtVec3SoA * const out_vec[3] = { &out.origin, &out.direction, &out.throughput }; const size_t out_word[3] = { 0, 3, 11 };
+	for (int v = 0; v < 3; v++) read = read && probe.column_back(out_vec[v]->x, trace_out, TW, out_word[v], 1, capacity) && probe.column_back(out_vec[v]->y, trace_out, TW, out_word[v] + 1, 1, capacity)
+	                                        && probe.column_back(out_vec[v]->z, trace_out, TW, out_word[v] + 2, 1, capacity);
+	read = read && probe.column_back(out.hits, trace_out, TW, 6, 4, capacity) && probe.column_back(out.pixel_index_and_flags, trace_out, TW, 10, 1, capacity)
+	            && probe.column_back(out.last_pdf, trace_out, TW, 14, 1, capacity) && probe.column_back(out.medium, trace_out, TW, 15, 1, capacity)
+	            && probe.column_back(out.cone_angle, trace_out, TW, 16, 1, capacity) && probe.column_back(out.cone_width, trace_out, TW, 17, 1, capacity);
+	for (size_t i = 0; i < capacity; i++) trace_out[i * TW + 18] = trace_out[i * TW + 19] = sentinel;   // (padding)
+	const RtVec3SoA * const shadow_vec[2] = { &shadow.origin, &shadow.direction };
+	for (int v = 0; v < 2; v++) read = read && probe.column_back(shadow_vec[v]->x, shadow_out, SW, 3 * v, 1, capacity) && probe.column_back(shadow_vec[v]->y, shadow_out, SW, 3 * v + 1, 1, capacity)
+	                                        && probe.column_back(shadow_vec[v]->z, shadow_out, SW, 3 * v + 2, 1, capacity);
+	read = read && probe.column_back(shadow.max_distance, shadow_out, SW, 6, 1, capacity) && probe.column_back(shadow.illumination_and_pixel_index, shadow_out, SW, 7, 4, capacity);
+	if (!read) return fail(ctx, RT_ERROR_HIP, "rt_shade_rays: reading the queues back failed");
+	if (merged) {
+		std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());
+		if ((s = probe.read(control_host.get(), control, sizeof(RtStreamControl)))) return s;
+		counters3[0] = control_host->trace_count[q ^ 1]; counters3[1] = control_host->shadow_count[q]; counters3[2] = control_host->material_count[material_slot];
+		memcpy(stats, control_host->stats, sizeof(control_host->stats));
+	} else {
+		RtBufferSizes sizes_host;
+		if ((s = probe.read(&sizes_host, sizes, sizeof(RtBufferSizes)))) return s;
+		counters3[0] = sizes_host.trace[step + 1]; counters3[1] = sizes_host.shadow[step];
+		counters3[2] = (material_slot == 0 ? sizes_host.diffuse : material_slot == 1 ? sizes_host.plastic : material_slot == 2 ? sizes_host.dielectric : sizes_host.conductor)[step];
+	}
+	for (int k = 0; k < 3 && s == RT_OK; k++) s = probe.read(aov_frames + size_t(k) * pixels * 4, frames[k], pixels * 16);
+	if (s || (s = probe.read(gbuffer_normal_and_depth, g_nd, pixels * 16)) || (s = probe.read(gbuffer_mesh_id_and_triangle_id, g_id, pixels * 8))) return s;
+	return probe.read(gbuffer_screen_position_prev, g_sp, pixels * 8);
 }
 
 int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps) {

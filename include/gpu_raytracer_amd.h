@@ -650,6 +650,33 @@ int rt_sort_rays(rt_context * ctx, int merged, int step, int sample_index, const
                  uint32_t * trace_out, uint32_t * material_out, int32_t * counters6,
                  float * aov_frames, float * gbuffer_normal_and_depth, int32_t * gbuffer_mesh_id_and_triangle_id, float * gbuffer_screen_position_prev,
                  int32_t * pixel_query2, int32_t * stats);
+/* The material launch on an explicit material queue (synchronous): the production launcher -- rt_launch_material (merged = 0: `step` is
+ * the bounce, sample_index the launch's) or rt_launch_material_stream (merged = 1: `step` is the iteration; bounce and sample of an entry
+ * come out of slot_table / submission_birth) -- for queue `material_slot` (0 diffuse, 1 plastic, 2 dielectric, 3 conductor), so the
+ * instance (plain, _texels, _sky, _nmap and their combinations) and the grid are the shipped ones, on the context's own parameter block
+ * with that material queue, the next trace queue, the shadow queue, the counters / control block, the slot table, the three AOV frames
+ * the launch writes and the g-buffers replaced by buffers of this call. Nothing of the context changes but what a render would settle
+ * (the Kulla-Conty tables for slots 2 and 3, the sky tables when sky sampling is wanted).
+ * material_in: count x RT_SORT_MATERIAL_WORDS, exactly one of the four queues rt_sort_rays returns in material_out (virtual pixels, slot
+ * table and frame_slots as there). trace_out: capacity x RT_SORT_TRACE_WORDS, the next trace queue in rt_sort_rays's trace_in layout.
+ * shadow_out: capacity x RT_SHADE_SHADOW_WORDS {origin[3], direction[3], max_distance, illumination[3], pixel word (the virtual pixel;
+ * merged form: | 1 << 30 on a ray emitted at bounce 0)}. counters3: {next trace queue, shadow queue, this material queue} after the
+ * launch. aov_frames: 3 x frame_slots * frame_pixels x 4 words, RT_AOV_ALBEDO, _NORMAL, _POSITION (a frame the context has disabled is
+ * not given to the kernel); gbuffer_*: 4, 2, 2 words per pixel. All of these are OUTPUTS: every device array is filled with `sentinel`
+ * first and read back whole, so a word the launch did not write holds the sentinel. stats (merged; out): 128 x 6 x RT_MAX_BOUNCES ints.
+ * RT_ERROR_INVALID_ARG with a message, before anything is launched, for whatever could make the kernel read or write outside these
+ * buffers or the context's tables: NULL arrays, count > capacity, a bounce outside [0, RT_MAX_BOUNCES - 1) or not below num_bounces, a
+ * virtual pixel beyond the frames, two entries with one virtual pixel, a mesh id beyond the instance table, a triangle id beyond the
+ * triangle array, an instance whose material is not of the queue's type, a medium id beyond rt_upload_media's table on an entry flagged
+ * inside a medium, a slot beyond the table, a submission beyond 128, an entry's bounce outside [0, min(RT_MAX_BOUNCES, num_bounces)) or
+ * a slot whose birth is not its submission's. (An addition that changes no struct: RT_ABI_VERSION stays.)                          */
+#define RT_SHADE_SHADOW_WORDS 11
+int rt_shade_rays(rt_context * ctx, int merged, int step, int sample_index, int material_slot, const uint32_t * material_in, size_t count,
+                  const int32_t * slot_table, size_t slot_count, const int32_t * submission_birth,
+                  size_t capacity, size_t frame_slots, uint32_t sentinel,
+                  uint32_t * trace_out, uint32_t * shadow_out, int32_t * counters3,
+                  uint32_t * aov_frames, uint32_t * gbuffer_normal_and_depth, uint32_t * gbuffer_mesh_id_and_triangle_id, uint32_t * gbuffer_screen_position_prev,
+                  int32_t * stats);
 /* Streaming-read bandwidth probe used as the measured HBM roofline (GB/s).                 */
 int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps);
 

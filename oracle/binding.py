@@ -114,6 +114,7 @@ def lib():
         l.oracle_bsdf_eval.argtypes = [POINTER(OracleScene), c_int, c_void_p, c_size_t, c_void_p]
         l.oracle_bsdf_sample.argtypes = [POINTER(OracleScene), c_int, c_void_p, c_size_t, c_void_p]
         l.oracle_sample_lights.argtypes = [POINTER(OracleScene), c_void_p, c_size_t, c_void_p]
+        l.oracle_shade.argtypes = [POINTER(OracleScene), POINTER(OracleFrame), c_int, c_int, c_int, c_void_p, c_size_t, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]
         l.oracle_sort.argtypes = [POINTER(OracleScene), POINTER(OracleFrame), c_int, c_int, c_void_p, c_size_t, c_uint32, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_float, c_void_p, c_void_p]
         l.oracle_average_conductor.argtypes = [c_void_p, c_void_p]
         tex_p = POINTER(OracleTexture)
@@ -764,6 +765,30 @@ class SceneView:
         if status != 0:
             raise ValueError("oracle_sort: status %d" % status)
         return trace_out, material_out, counts, internals
+
+    def shade(self, material_slot, material_in, bounce, sample_index, aov, gbuffer_normal_and_depth, gbuffer_ids, gbuffer_screen_prev, sentinel=0xFFC0DE42,
+              aov_enabled=(True, True, True)):
+        """oracle_shade: shade_material of queue `material_slot` on (N, 16) uint32 records of ONE sample (pixels of one frame) at one bounce. aov (3, P, 4)
+        {ALBEDO, NORMAL, POSITION} and the g-buffers (P, 4) / (P, 2) / (P, 2) are uint32 word arrays (C-contiguous) updated IN PLACE. Returns (trace_out
+        (N, 20), shadow_out (N, 11), counts int32[2], internals (N, 2) float32 {dot(direction, geometric normal), omega_i.z})."""
+        m = np.ascontiguousarray(material_in, np.uint32).reshape(-1, 16)
+        n = m.shape[0]
+        f = OracleFrame()
+        for k, which in enumerate((RT_AOV_ALBEDO, RT_AOV_NORMAL, RT_AOV_POSITION)):
+            assert aov[k].flags.c_contiguous and aov[k].dtype == np.uint32
+            if aov_enabled[k]:
+                f.framebuffer[which] = aov[k].ctypes.data
+        for a in (gbuffer_normal_and_depth, gbuffer_ids, gbuffer_screen_prev):
+            assert a.flags.c_contiguous and a.dtype == np.uint32
+        f.gbuffer_normal_and_depth = gbuffer_normal_and_depth.ctypes.data; f.gbuffer_mesh_id_and_triangle_id = gbuffer_ids.ctypes.data
+        f.gbuffer_screen_position_prev = gbuffer_screen_prev.ctypes.data
+        trace_out = np.zeros((n, 20), np.uint32); shadow_out = np.zeros((n, 11), np.uint32); counts = np.zeros(2, np.int32)
+        internals = np.full((n, 2), np.nan, np.float32)
+        status = lib().oracle_shade(byref(self.scene), byref(f), int(material_slot), int(bounce), int(sample_index), m.ctypes.data if n else None, n, int(sentinel),
+                                    trace_out.ctypes.data, shadow_out.ctypes.data, counts.ctypes.data, internals.ctypes.data)
+        if status != 0:
+            raise ValueError("oracle_shade: status %d" % status)
+        return trace_out, shadow_out, counts, internals
 
     def random(self, dimension, pixel_indices, bounce, sample_index):
         px = np.ascontiguousarray(pixel_indices, np.uint32)

@@ -188,6 +188,15 @@ int oracle_sample_lights(const oracle_scene * scene, const float * probes, size_
 int oracle_sort(const oracle_scene * scene, oracle_frame * frame, int bounce, int sample_index, const uint32_t * trace_in, size_t count, uint32_t sentinel,
                 uint32_t * trace_out, uint32_t * material_out, int32_t * counts5, int pixel_query_pixel, int32_t * pixel_query2,
                 float sky_share, const float * sky_cell_pdf, float * internals);
+/* shade_material<BSDF> (Pathtracer.cu:557-757) of material queue `material_slot` (0 diffuse .. 3 conductor) on count x 16-word records, exactly one of
+ * the queues oracle_sort returns in material_out, at one bounce of one sample (pixels of `frame`, whose ALBEDO / NORMAL / POSITION frames and g-buffers are
+ * written in place). One chunk, so both output queues are in input order. trace_out: count x 20 words in oracle_sort's trace_in layout; shadow_out: count x
+ * 11 words {origin[3], direction[3], max_distance, illumination[3], pixel}; `sentinel` wherever the kernel stores nothing (the hit of a continuation ray,
+ * last_pdf without ALLOW_NEE, the medium outside a medium, the cone without mip-mapping, the padding). counts2: {next trace queue, shadow queue}.
+ * internals: NULL, or count x 2 floats, pre-filled by the caller: {dot(ray direction, geometric normal), omega_i.z} of every entry, the two numbers the
+ * set-up compares with zero. No sky sampling and no normal maps here. -1: bad argument, -2 / -3 / -4 as for oracle_sort. */
+int oracle_shade(const oracle_scene * scene, oracle_frame * frame, int material_slot, int bounce, int sample_index, const uint32_t * material_in, size_t count, uint32_t sentinel,
+                 uint32_t * trace_out, uint32_t * shadow_out, int32_t * counts2, float * internals);
 /* Pathtracer::render for one sample over pixels [pixel_offset, pixel_offset+pixel_count)
  * (Pathtracer.cpp:738-855): batches, bounces, accumulate or SVGF/TAA. */
 void oracle_render_sample(const oracle_scene * scene, oracle_frame * frame, int sample_index,

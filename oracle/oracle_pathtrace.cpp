@@ -856,7 +856,7 @@ void next_event_estimation(Context & c, Wavefront & w, int pixel_index, int boun
 
 // shade_material<BSDF>, Pathtracer.cu:557-757
 template<typename BSDF>
-void shade_material(Context & c, Wavefront & w, const std::vector<MaterialRay> & queue, size_t begin, size_t end, int bounce, int sample_index) {
+void shade_material(Context & c, Wavefront & w, const std::vector<MaterialRay> & queue, size_t begin, size_t end, int bounce, int sample_index, float * internals = nullptr) {
 	const oracle_scene & s = c.s;
 	const rt_gpu_config & cfg = s.config;
 	std::vector<TraceRay> & out = w.trace[(bounce + 1) & 1];
@@ -905,6 +905,7 @@ void shade_material(Context & c, Wavefront & w, const std::vector<MaterialRay> &
 		float3 tangent, bitangent;
 		orthonormal_basis(normal, tangent, bitangent);
 		float3 omega_i = world_to_local(-ray_direction, tangent, bitangent, normal);
+		if (internals) { internals[2 * index] = dot(ray_direction, geometric_normal); internals[2 * index + 1] = omega_i.z; }   // (oracle_shade: what the two comparisons around here compare)
 		if (omega_i.z <= 0.0f) continue;
 
 		int material_id = s.mesh_material_ids[hit.mesh_id];
@@ -1098,6 +1099,55 @@ int oracle_sort(const oracle_scene * scene, oracle_frame * frame, int bounce, in
 	}
 	for (int m = 0; m < 4; m++) counts5[m] = int32_t(w.material[m].size());
 	counts5[4] = int32_t(next.size());
+	return 0;
+}
+
+// oracle_shade: shade_material<BSDF> of queue `material_slot` on one of the material queues of oracle_sort / rt_sort_rays, one chunk, queue order = input
+// order. What a record holds where the kernel stores nothing (Pathtracer.cu:735-756: last_pdf without ALLOW_NEE, the medium outside a medium, the cone without
+// mip-mapping, the hit of a continuation ray) is the caller's sentinel, as on the device. The frames and g-buffers of `frame` are written in place.
+int oracle_shade(const oracle_scene * scene, oracle_frame * frame, int material_slot, int bounce, int sample_index, const uint32_t * material_in, size_t count, uint32_t sentinel,
+                 uint32_t * trace_out, uint32_t * shadow_out, int32_t * counts2, float * internals) {
+	const oracle_scene & s = *scene;
+	if (bounce < 0 || bounce >= RT_MAX_BOUNCES || material_slot < 0 || material_slot > 3 || !frame || !counts2 || (count && (!material_in || !trace_out || !shadow_out))) return -1;
+	const size_t pixels = size_t(s.screen_pitch) * size_t(s.screen_height);
+	std::vector<MaterialRay> in(count);
+	for (size_t i = 0; i < count; i++) {
+		const uint32_t * r = material_in + i * 16;
+		MaterialRay & m = in[i];
+		if ((r[7] & ~FLAGS_ALL) >= pixels) return -2;
+		if (int32_t(r[4]) < 0 || int32_t(r[4]) >= s.triangle_count || int32_t(r[3]) < 0 || int32_t(r[3]) >= s.mesh_count) return -3;
+		if ((r[7] & FLAG_INSIDE_MEDIUM) && (int32_t(r[11]) < 0 || int32_t(r[11]) >= s.medium_count)) return -4;
+		m.direction = make_float3(uint_as_float(r[0]), uint_as_float(r[1]), uint_as_float(r[2]));
+		memcpy(m.hit, r + 3, 16);
+		m.pixel_index_and_flags = r[7];
+		m.throughput = make_float3(uint_as_float(r[8]), uint_as_float(r[9]), uint_as_float(r[10]));
+		m.medium = int32_t(r[11]); m.cone_angle = uint_as_float(r[12]); m.cone_width = uint_as_float(r[13]);
+	}
+	Context c(s, *frame);
+	Wavefront w;
+	switch (material_slot) {
+		case 0: shade_material<BSDFDiffuse>(c, w, in, 0, count, bounce, sample_index, internals); break;
+		case 1: shade_material<BSDFPlastic>(c, w, in, 0, count, bounce, sample_index, internals); break;
+		case 2: shade_material<BSDFDielectric>(c, w, in, 0, count, bounce, sample_index, internals); break;
+		default: shade_material<BSDFConductor>(c, w, in, 0, count, bounce, sample_index, internals); break;
+	}
+	for (size_t i = 0; i < count * 20; i++) trace_out[i] = sentinel;
+	for (size_t i = 0; i < count * 11; i++) shadow_out[i] = sentinel;
+	const bool cones = s.config.enable_mipmapping != 0;
+	auto put3 = [](uint32_t * o, float3 v) { o[0] = float_as_uint(v.x); o[1] = float_as_uint(v.y); o[2] = float_as_uint(v.z); };
+	const std::vector<TraceRay> & next = w.trace[(bounce + 1) & 1];
+	for (size_t i = 0; i < next.size(); i++) {
+		uint32_t * o = trace_out + i * 20; const TraceRay & t = next[i];
+		put3(o, t.origin); put3(o + 3, t.direction); o[10] = t.pixel_index_and_flags; put3(o + 11, t.throughput);
+		if (t.pixel_index_and_flags & FLAG_ALLOW_NEE) o[14] = float_as_uint(t.last_pdf);
+		if (t.medium != RT_INVALID) o[15] = uint32_t(t.medium);
+		if (cones) { o[16] = float_as_uint(t.cone_angle); o[17] = float_as_uint(t.cone_width); }
+	}
+	for (size_t i = 0; i < w.shadow.size(); i++) {
+		uint32_t * o = shadow_out + i * 11; const ShadowRay & r = w.shadow[i];
+		put3(o, r.origin); put3(o + 3, r.direction); o[6] = float_as_uint(r.max_distance); put3(o + 7, r.illumination); o[10] = uint32_t(r.pixel_index);
+	}
+	counts2[0] = int32_t(next.size()); counts2[1] = int32_t(w.shadow.size());
 	return 0;
 }
 

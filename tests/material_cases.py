@@ -1,0 +1,373 @@
+"""Scene, settings and material queues of the material-launch tests (test_material.py on the CPU, test_gpu_material.py on the device).
+
+The world is sort_cases.World -- textured rough-plastic floor under a scale of 5, two emitters of which one is a rotated, scaled and
+translated file mesh, a rough dielectric sphere holding a medium, a conductor sphere, a diffuse sphere -- in a 64 x 64 frame, plus a
+textured diffuse quad under a rotation, a scale of 0.7 and a translation, and an untextured rough-plastic sphere (so that both textured
+material types also have an instance whose albedo is a constant). Every instance's previous transform differs from its
+current one (World stages them so), so screen_position_prev is not the current position. Spheres interpolate their normals: the
+shading normal is not the geometric one, and the curvature is not zero.
+
+Hits are synthetic, as in sort_cases: (instance, triangle, t, u, v) from the scene's tables, directions uniform over the sphere (so
+about half the entries arrive at the back face). Entries are built in the state the sort leaves them: at bounce 0 the throughput and
+cone words hold the sentinel, outside a medium the medium word holds it, the padding holds it."""
+import ctypes
+
+import numpy as np
+
+import sort_cases
+from sort_cases import SENTINEL, NUM_BOUNCES, SUBMISSIONS, pixels_for, slots_needed, unit_vectors, single_submission_table   # noqa: F401 (the tests' vocabulary)
+from sort_reference import Entries, DIFFUSE, PLASTIC, DIELECTRIC, CONDUCTOR
+
+WIDTH = HEIGHT = 64
+BLOCK = 256                   # RT_SHADE_BLOCK
+GRID, STREAM_GRID = 2048, 8192   # workgroups of rt_launch_material and rt_launch_material_stream
+SLOT_NAMES = ("diffuse", "plastic", "dielectric", "conductor")
+SLOT_TYPES = (DIFFUSE, PLASTIC, DIELECTRIC, CONDUCTOR)
+MATERIAL_WORDS, TRACE_WORDS, SHADOW_WORDS = 16, 20, 11
+AOV_MASK = 1 | (1 << 3) | (1 << 4) | (1 << 5)    # RADIANCE (always on), ALBEDO, NORMAL, POSITION
+ROUGHNESS_WORD = {PLASTIC: 4, DIELECTRIC: 2, CONDUCTOR: 3}   # of the 8-float material record (bsdf_checks.roughness_of)
+MAX_VALUE_ENTRIES = 4096
+ALBEDO_FLOOR = 60.0 / 255.0   # every texel of the world's texture is 64 / 255 or more; a mip level is an average, rounded to 8 bits at most once per level
+
+
+class Setup(sort_cases.Setup):
+    """sort_cases.Setup with the three frames of the launch enabled, and
+    `smooth`: the dielectric and the conductor get a roughness below the cutoff, so that their BSDFs do not allow next-event estimation
+    (no shadow ray, no ALLOW_NEE, no last_pdf);
+    `bc1`: the device holds one more texture, of BC1 blocks decoded per fetch (rt_set_texture_expansion(ctx, 0)), which no material names:
+    the launchers then take the diffuse and plastic instances that can decode (not the _texels ones) for the scene's own RGBA8 texture."""
+
+    def __init__(self, name, config=None, smooth=False, bc1=False, aov_mask=AOV_MASK, **rest):
+        config = dict(config or {}); config.setdefault("aov_mask", aov_mask)
+        super().__init__(name, config, **rest)
+        self.smooth, self.bc1 = smooth, bc1
+
+
+SETUPS = [
+    Setup("default"),
+    Setup("nee_off", {"enable_next_event_estimation": 0}),
+    Setup("mis_off", {"enable_multiple_importance_sampling": 0}),
+    Setup("mipmapping_off", {"enable_mipmapping": 0}),
+    Setup("svgf_on", {"enable_svgf": 1}),
+    Setup("no_lights", lights=False),
+    Setup("smooth", smooth=True),
+    Setup("frames_off", aov_mask=1),
+    Setup("bc1_present", bc1=True),
+]
+SETUP = {s.name: s for s in SETUPS}
+
+
+class World(sort_cases.World):
+    FRAME = (WIDTH, HEIGHT)
+    EXTRA_SHAPES = sort_cases.World.EXTRA_SHAPES + (
+        '<shape type="obj"><string name="filename" value="quad.obj"/><transform name="toWorld"><scale value="0.7"/><rotate y="1" angle="30"/><rotate x="1" angle="-60"/>'
+        '<translate x="2.2" y="1.0" z="-1.0"/></transform><bsdf type="diffuse"><texture type="bitmap" name="reflectance"><string name="filename" value="t.png"/></texture></bsdf></shape>'
+        '<shape type="sphere"><float name="radius" value="0.35"/><transform name="toWorld"><translate x="-0.4" y="0.35" z="2.2"/></transform>'
+        '<bsdf type="roughplastic"><rgb name="diffuseReflectance" value="0.3, 0.55, 0.8"/><float name="alpha" value="0.16"/></bsdf></shape>')
+
+    def prepare(self, directory):
+        """The texture both textured materials use: random texels of 64 / 255 or more in every channel (material_checks.TEXTURED_RELATIVE needs the floor)."""
+        from test_loaders import _png_bytes
+        (directory / "t.png").write_bytes(_png_bytes(np.random.default_rng(3).integers(64, 256, (32, 32, 3)), 2, 8))
+
+    def roughness_of_instance(self, tables):
+        """Linear roughness per instance under the applied setup (1 for diffuse, whose sample is the cosine lobe)."""
+        r = np.ones(tables.materials.shape[0])
+        for kind, word in ROUGHNESS_WORD.items():
+            r[tables.material_types == kind] = tables.materials[tables.material_types == kind, word]
+        return r[tables.material_ids]
+
+    def __init__(self, grt, oracle, directory, device):
+        super().__init__(grt, oracle, directory, device)
+        k = self.view.keep
+        ids = np.asarray(k["mesh_material_ids"], np.int32)
+        textured = self.materials[:, 3].view(np.int32) >= 0     # word 3 of a diffuse or plastic record: its texture
+        for kind in (DIFFUSE, PLASTIC):
+            mine = self.material_types[ids[self.instances[kind]]] == kind
+            assert (mine & textured[ids[self.instances[kind]]]).any(), "no textured material of type %d" % kind
+        for kind in (DIFFUSE, PLASTIC):
+            assert (~textured[ids[self.instances[kind]]]).any(), "no untextured material of type %d" % kind
+        self.textured_instance = textured[ids] & np.isin(self.material_types[ids], (DIFFUSE, PLASTIC))
+        assert (self.materials[textured & np.isin(self.material_types, (DIFFUSE, PLASTIC)), :3] == 1.0).all(), "a textured material scales its texture"
+        rows = np.asarray(k["mesh_transforms"], np.float32).reshape(-1, 3, 4)
+        scale = np.linalg.norm(rows[:, 0, :3].astype(np.float64), axis=1)
+        assert (np.abs(scale - 1.0) > 0.1).sum() >= 3, "fewer than three instances under a non-unit scale"
+        # the Kulla-Conty tables of the dielectric and the conductor: the device's own, or the oracle's integration at 1500 samples a cell (as
+        # test_bsdf.py; both sides of a comparison read the same numbers, but how ill-conditioned 1 - E is depends on them: the bounds measured
+        # on the CPU have to see tables like the device's)
+        if device >= 0:
+            luts = grt.read_luts(self.ctx)
+        else:
+            v = self.view
+            luts = [v.integrate_dielectric_cells(True, 0, 4096, 1500), v.integrate_dielectric_cells(False, 0, 4096, 1500)]
+            luts += [oracle.average_dielectric(luts[0]), oracle.average_dielectric(luts[1])]
+            luts.append(v.integrate_conductor_cells(0, 1024, 1500))
+            luts.append(oracle.average_conductor(luts[4]))
+        k["luts"] = [np.ascontiguousarray(l, dtype=np.float32) for l in luts]
+        s = self.view.scene
+        (s.lut_dielectric_directional_albedo_enter, s.lut_dielectric_directional_albedo_leave, s.lut_dielectric_albedo_enter,
+         s.lut_dielectric_albedo_leave, s.lut_conductor_directional_albedo, s.lut_conductor_albedo) = [l.ctypes.data for l in k["luts"]]
+        import bsdf_reference
+        self.bsdf_tables = bsdf_reference.Tables(k["luts"])
+        self.textures_compressed = False   # the scene's one texture is decoded to texels at upload: the launchers take the _texels instances of the diffuse and plastic kernels
+        self.rough_materials = self.materials
+        self.smooth_materials = self.materials.copy()
+        for kind in (DIELECTRIC, CONDUCTOR):
+            self.smooth_materials[self.material_types == kind, ROUGHNESS_WORD[kind]] = 0.02
+
+    def apply(self, setup):
+        self.materials = self.smooth_materials if getattr(setup, "smooth", False) else self.rough_materials
+        try:
+            tables = super().apply(setup)
+        finally:
+            self.materials = self.rough_materials
+        if self.ctx is not None and bool(getattr(setup, "bc1", False)) != self.textures_compressed:
+            self.upload_textures(bool(setup.bc1))
+        return tables
+
+    def upload_textures(self, with_bc1):
+        """The scene's textures again (rt_upload_textures), with or without a BC1 texture behind them that is decoded per fetch."""
+        from texture_cases import bc1_texture
+        from test_gpu_texture_unit import TextureDesc   # (the texture tests' mirror of rt_texture_desc: one copy)
+        scene_textures = self.pt.textures()
+        extra = bc1_texture(8, 8, 7) if with_bc1 else None
+        descs = (TextureDesc * (len(scene_textures) + 1))()
+        for i, (texels, w, h, levels) in enumerate(scene_textures):
+            descs[i].texels, descs[i].width, descs[i].height, descs[i].mip_levels, descs[i].format = texels.ctypes.data, w, h, levels, 0
+            descs[i].lod_width, descs[i].lod_height = self.pt.texture_lod_size(i)
+        if extra is not None:
+            d = descs[len(scene_textures)]
+            d.texels, d.width, d.height, d.mip_levels, d.format = extra.data.ctypes.data, extra.width, extra.height, extra.mip_levels, extra.format
+        lib = self.lib
+        lib.rt_set_texture_expansion.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        lib.rt_upload_textures.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+        assert lib.rt_set_texture_expansion(self.ctx, 0 if with_bc1 else 1) == 0, lib.rt_last_error(self.ctx)
+        assert lib.rt_upload_textures(self.ctx, descs, len(scene_textures) + (1 if with_bc1 else 0)) == 0, lib.rt_last_error(self.ctx)
+        self.textures_compressed = with_bc1
+
+
+class Launch:
+    """One material launch: the queue of slot `slot`, how its entries' bounce and sample are found (per-bounce form: bounce,
+    sample_index; merged form: iteration, slot_table (S, 4) int32, submission_birth int32[128]), the frames' size."""
+
+    def __init__(self, name, slot, entries, frame_pixels, frame_slots, bounce=None, sample_index=0, iteration=None, slot_table=None, submission_birth=None):
+        self.name, self.slot, self.entries, self.frame_pixels, self.frame_slots = name, int(slot), entries, int(frame_pixels), int(frame_slots)
+        self.bounce, self.sample_index, self.iteration = bounce, sample_index, iteration
+        self.slot_table = None if slot_table is None else np.ascontiguousarray(slot_table, np.int32).reshape(-1, 4)
+        self.submission_birth = None if submission_birth is None else np.ascontiguousarray(submission_birth, np.int32)
+        self.merged = iteration is not None
+
+    def paths(self):
+        """Per entry: sample slot, real pixel, bounce, sample index (the RNG's), submission."""
+        e = self.entries
+        slot = (e.pixel // self.frame_pixels).astype(np.int64)
+        real = (e.pixel % self.frame_pixels).astype(np.uint32)
+        if self.merged:
+            row = self.slot_table[slot]
+            return slot, real, self.iteration - row[:, 1].astype(np.int64), row[:, 0].astype(np.int64), row[:, 2].astype(np.int64)
+        zero = np.zeros(e.n, np.int64)
+        return slot, real, zero + self.bounce, self.sample_index + slot, zero
+
+    def pack(self, garbage=None):
+        """(N, 16) uint32 records as the sort writes them; `garbage` (a float32) replaces the sentinel in the words the sort leaves
+        unwritten at bounce 0 (throughput, cone) -- the launch must not read them."""
+        e = self.entries
+        bounce = self.paths()[2]
+        r = np.full((e.n, MATERIAL_WORDS), SENTINEL, np.uint32)
+        r[:, 0:3] = e.direction.view(np.uint32)
+        r[:, 3] = e.mesh.view(np.uint32); r[:, 4] = e.triangle.view(np.uint32); r[:, 5] = e.t.view(np.uint32); r[:, 6] = (e.u16 & 0xffff) | (e.v16 << 16)
+        r[:, 7] = e.pixel | (e.inside.astype(np.uint32) << 30)
+        later = bounce > 0
+        r[later, 8:11] = e.throughput.view(np.uint32)[later]
+        r[e.inside, 11] = e.medium.view(np.uint32)[e.inside]
+        r[later, 12] = e.cone_angle.view(np.uint32)[later]; r[later, 13] = e.cone_width.view(np.uint32)[later]
+        if garbage is not None:
+            first = ~later
+            r[first, 8:11] = np.float32(garbage).view(np.uint32); r[first, 12:14] = np.float32(garbage).view(np.uint32)
+        return r
+
+
+def make_entries(world, rng, pixels, slot, bounce, inside_share=None):
+    """Random hits on the instances of slot `slot`'s material type, one per pixel, at the given bounce (an int or one per entry).
+    Inside a medium: a third of the dielectric's entries beyond bounce 0, a tenth of the others' (the medium passes through them)."""
+    e = sort_cases.make_entries(world, rng, pixels, bounce, classes=(SLOT_TYPES[slot],),
+                                inside_share=(0.33 if slot == 2 else 0.1) if inside_share is None else inside_share)
+    e.allow_nee[:] = False   # (a material entry carries no such flag)
+    return e
+
+
+def per_bounce(world, name, slot, n, bounce, seed, sample_index=3, slots=None, **kw):
+    rng = np.random.default_rng(seed)
+    slots = slots or slots_needed(n, world.frame_pixels)
+    e = make_entries(world, rng, pixels_for(rng, n, world.frame_pixels, slots), slot, bounce, **kw)
+    return Launch("%s_%s_bounce%d_%d" % (name, SLOT_NAMES[slot], bounce, n), slot, e, world.frame_pixels, slots, bounce=bounce, sample_index=sample_index)
+
+
+def merged(world, name, slot, n, seed, num_bounces=NUM_BOUNCES, **kw):
+    """One launch of the merged wavefront: five sample slots of three submissions at bounces 0, 1 and num_bounces - 1, slots not in
+    submission order, entries of all submissions interleaved."""
+    rng = np.random.default_rng(seed)
+    iteration = num_bounces + 3
+    #          sample, birth,                        submission, index_in_submission
+    table = np.array([(11, iteration - 1,                 9,   1),
+                      (70, iteration,                     3,   0),
+                      (10, iteration - 1,                 9,   0),
+                      (200, iteration - (num_bounces - 1), 64, 0),
+                      (71, iteration,                     3,   1)], np.int32)
+    births = np.full(SUBMISSIONS, iteration + 1000, np.int32)
+    for row in table:
+        births[row[2]] = row[1]
+    slots = table.shape[0]
+    assert n <= slots * world.frame_pixels
+    px = pixels_for(rng, n, world.frame_pixels, slots)
+    bounce = iteration - table[px // world.frame_pixels, 1]
+    e = make_entries(world, rng, px, slot, bounce, **kw)
+    return Launch("%s_%s_merged_%d" % (name, SLOT_NAMES[slot], n), slot, e, world.frame_pixels, slots, iteration=iteration, slot_table=table, submission_birth=births)
+
+
+LENGTHS = (0, 1, 63, 64, 65, 255, 256, 257, 4 * 256 + 3)
+SECOND_ROUND = GRID * BLOCK + 1          # per-bounce: one entry in a second grid-stride round
+BOUNCES = (0, 1, NUM_BOUNCES - 1)
+
+
+def value_launches(world):
+    """The plain and the merged instance of all four slots: per-bounce launches at bounce 0, 1 and the last, one merged launch."""
+    out = []
+    for slot in range(4):
+        for b in BOUNCES:
+            out.append(per_bounce(world, "mixed", slot, 3000, b, seed=1000 + 10 * slot + b))
+        out.append(merged(world, "mixed", slot, 4000, seed=1100 + slot))
+    return out
+
+
+def length_launches(world):
+    """Queue lengths around a wave and a workgroup, per-bounce (bounce 1) and merged, over the slots in turn."""
+    out = []
+    for k, n in enumerate(LENGTHS):
+        out.append(per_bounce(world, "length", k % 4, n, 1, seed=1200 + k, slots=1))
+        out.append(merged(world, "length", (k + 1) % 4, n, seed=1300 + k))
+    return out
+
+
+def small_launches(world):
+    """One small launch per slot and form, for the setups that change one setting."""
+    out = []
+    for slot in range(4):
+        out.append(per_bounce(world, "small", slot, 700, 0, seed=1400 + slot))
+        out.append(per_bounce(world, "small", slot, 700, 2, seed=1410 + slot))
+    out.append(merged(world, "small", 0, 1500, seed=1420))
+    out.append(merged(world, "small", 2, 1500, seed=1421))
+    return out
+
+
+def second_round_launch(world):
+    """2048 x 256 + 1 diffuse entries at bounce 1: the last entry is alone in the second grid-stride round."""
+    return per_bounce(world, "second_round", 0, SECOND_ROUND, 1, seed=1500)
+
+
+def plan(world, setup, tables=None):
+    if setup.name == "default":
+        return value_launches(world) + length_launches(world) + (threshold_launches(world, tables) if tables is not None else [])
+    if setup.name == "svgf_on" and tables is not None:
+        return small_launches(world) + threshold_launches(world, tables)
+    return small_launches(world)
+
+
+def from_records(world, name, slot, records, bounce, sample_index):
+    """A per-bounce launch on (N, 16) material records of a sort launch (rt_sort_rays / oracle_sort), one sample slot."""
+    r = np.ascontiguousarray(records, np.uint32).reshape(-1, MATERIAL_WORDS)
+    e = Entries(r.shape[0])
+    e.direction[:] = r[:, 0:3].view(np.float32)
+    e.mesh[:] = r[:, 3].view(np.int32); e.triangle[:] = r[:, 4].view(np.int32); e.t[:] = r[:, 5].view(np.float32)
+    e.u16[:] = r[:, 6] & 0xffff; e.v16[:] = r[:, 6] >> 16
+    e.pixel[:] = r[:, 7] & 0x3fffffff; e.inside[:] = (r[:, 7] >> 30) & 1
+    e.throughput[:] = r[:, 8:11].view(np.float32); e.medium[:] = r[:, 11].view(np.int32)
+    e.cone_angle[:] = r[:, 12].view(np.float32); e.cone_width[:] = r[:, 13].view(np.float32)
+    return Launch("%s_%s_bounce%d_%d" % (name, SLOT_NAMES[slot], bounce, e.n), slot, e, world.frame_pixels, 1, bounce=bounce, sample_index=sample_index)
+
+
+def threshold_launches(world, tables):
+    """Launches that sit on the set-up's thresholds on purpose, one per slot at bounce 0 (the frames) and at bounce 1, 96 entries each, in
+    groups of eight: a direction in the geometric plane (dot(direction, geometric normal) = 0 as float64 sees it, rounded to float32) and
+    its float neighbours in each component; a direction perpendicular to the shading normal (omega_i.z = 0) and its neighbours; a
+    head-on hit of the back face; a hit at t = 0; a hit on the edge u + v = 1; the rest random. Exempt from the cap on non-robust
+    entries; an entry next to a threshold may go either way, every other entry takes float64's."""
+    import material_reference as ref
+    out = []
+    for slot in range(4):
+        for bounce in (0, 1):
+            launch = per_bounce(world, "threshold", slot, 96, bounce, seed=2000 + 10 * slot + bounce, slots=1, inside_share=0.0)
+            e = launch.entries
+            r = ref.evaluate(world, tables, launch, world.bsdf_tables)
+            k = np.arange(e.n) % 8
+            for group, axis in ((0, r.geometric_normal), (1, r.normal)):
+                for i in np.nonzero(k == group)[0]:
+                    a = axis[i]
+                    tangent = np.cross(a, np.roll(a, 1) + 0.5); tangent /= np.linalg.norm(tangent)
+                    d = tangent.astype(np.float32)
+                    step = (i // 8) % 7   # 0: as rounded; 1..6: one component one float up or down
+                    if step:
+                        c = (step - 1) // 2
+                        d[c] = np.nextafter(d[c], np.float32(2.0 if step % 2 else -2.0))
+                    e.direction[i] = d
+            back = np.nonzero(k == 2)[0]
+            e.direction[back] = r.geometric_normal[back].astype(np.float32)
+            e.t[k == 3] = 0.0
+            edge = np.nonzero(k == 4)[0]
+            e.v16[edge] = 65535 - e.u16[edge]
+            out.append(launch)
+    return out
+
+
+THRESHOLD_LAUNCHES = ("threshold_",)
+
+
+class LightsWorld:
+    """A scene of nee_cases.py -- a diffuse floor under many emitters -- as the material tests need it: the light tables fit the shade
+    kernels' LDS copy (at most 64 mesh entries and 2048 triangle entries) or go beyond it, which decides where nee_pick_light searches.
+    Only the diffuse queue has instances here."""
+
+    def __init__(self, grt, oracle, case, directory, device):
+        import nee_cases
+        import sort_reference
+        self.grt, self.device, self.case = grt, device, case
+        self.scene, self.pt = nee_cases.load(grt, case, directory, device, WIDTH, HEIGHT)
+        self.view = oracle.SceneView(self.pt)
+        self.ctx = self.pt.ctx if device >= 0 else None
+        self.lib = grt.device_lib() if device >= 0 else None
+        s, k = self.view.scene, self.view.keep
+        self.frame_pixels = s.screen_pitch * s.screen_height
+        s.config.aov_mask = AOV_MASK
+        if self.ctx is not None:
+            cfg = grt.GPUConfig()
+            ctypes.memmove(ctypes.byref(cfg), ctypes.byref(s.config), ctypes.sizeof(cfg))
+            assert self.lib.rt_set_config(self.ctx, ctypes.byref(cfg)) == 0, self.lib.rt_last_error(self.ctx)
+        types = np.asarray(k["material_types"], np.uint8)[np.asarray(k["mesh_material_ids"], np.int32)]
+        self.instances = {t: np.nonzero(types == t)[0].astype(np.int32) for t in range(5)}
+        self.triangle_count = np.asarray(k["triangles"]).size // 24
+        self.textured_instance = np.zeros(types.size, bool)
+        self.textures_compressed = False
+        self.bsdf_tables = None
+        self.tables = sort_reference.Tables(self.view)
+
+    def roughness_of_instance(self, tables):
+        return np.ones(tables.material_ids.size)
+
+    def close(self):
+        self.pt.close(); self.scene.close(); self.grt.config_reset()
+
+
+def light_table_launches(world):
+    """Hits on the floor under the emitters, on the floor's own triangles (by far the largest of the scene; the emitters' ribbons are made
+    of slivers, whose geometric normal float32 cannot resolve), at bounce 0 and 2 and in the merged form."""
+    out = [per_bounce(world, "lights", 0, 700, 0, seed=2100, inside_share=0.0), per_bounce(world, "lights", 0, 700, 2, seed=2101, inside_share=0.0),
+           merged(world, "lights", 0, 1500, seed=2102, num_bounces=3, inside_share=0.0)]
+    tri = np.asarray(world.view.keep["triangles"], np.float32).reshape(-1, 24).astype(np.float64)
+    e1, e2 = tri[:, 3:6], tri[:, 6:9]
+    with np.errstate(all="ignore"):
+        area = np.linalg.norm(np.cross(e1, e2), axis=1)
+        good = np.nonzero(area > 0.5 * area.max())[0].astype(np.int32)
+    assert 2 <= good.size <= 4, good
+    for k, launch in enumerate(out):
+        launch.entries.triangle[:] = np.random.default_rng(2110 + k).choice(good, launch.entries.n)
+    return out

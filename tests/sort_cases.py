@@ -76,26 +76,31 @@ SETUP = {s.name: s for s in SETUPS}
 class World:
     """The loaded scene: host pathtracer (device < 0: host only), oracle view, and the tables the queues are drawn from."""
 
+    # what a test module with another frame or more shapes overrides (material_cases.py)
+    FRAME = (WIDTH, HEIGHT)
+    EXTRA_SHAPES = ('<shape type="sphere"><float name="radius" value="0.3"/><transform name="toWorld"><translate x="1.2" y="0.3" z="1.5"/></transform>'
+                    '<bsdf type="diffuse"><rgb name="reflectance" value="0.5, 0.7, 0.3"/></bsdf></shape>')
+
     def __init__(self, grt, oracle, directory, device):
         from scenes import write_scene_with_everything
         from test_loaders import _png_bytes
         path = write_scene_with_everything(directory, _png_bytes)
-        xml = open(path).read().replace("</scene>", '<shape type="sphere"><float name="radius" value="0.3"/><transform name="toWorld"><translate x="1.2" y="0.3" z="1.5"/></transform>'
-                                                    '<bsdf type="diffuse"><rgb name="reflectance" value="0.5, 0.7, 0.3"/></bsdf></shape></scene>')
+        xml = open(path).read().replace("</scene>", self.EXTRA_SHAPES + "</scene>")
         open(path, "w").write(xml)
+        self.prepare(directory)
         self.grt, self.oracle, self.device = grt, oracle, device
         settings = dict(merge_static=0, num_bounces=NUM_BOUNCES)
         grt.config_reset(); grt.config_set(**settings)
         self.scene = grt.Scene(path)
         grt.config_set(**settings)
-        self.pt = grt.Pathtracer(self.scene, WIDTH, HEIGHT, device=device)
+        self.pt = grt.Pathtracer(self.scene, self.FRAME[0], self.FRAME[1], device=device)
         self.pt.update()
         self.view = oracle.SceneView(self.pt)
         self.ctx = self.pt.ctx if device >= 0 else None
         self.lib = grt.device_lib() if device >= 0 else None
         s, k = self.view.scene, self.view.keep
         self.pitch, self.frame_pixels = s.screen_pitch, s.screen_pitch * s.screen_height
-        assert self.pitch == WIDTH
+        assert self.pitch == self.FRAME[0]
         self.base_config = oracle.GPUConfig()
         ctypes.memmove(ctypes.byref(self.base_config), ctypes.byref(s.config), ctypes.sizeof(s.config))
         assert self.base_config.num_bounces == NUM_BOUNCES
@@ -130,6 +135,9 @@ class World:
                                                   k["mesh_transforms_inv"].ctypes.data, prev.ctypes.data, self.mesh_count)
             assert status == 0, self.lib.rt_last_error(self.ctx)
         self.applied = None
+
+    def prepare(self, directory):
+        """Hook: the scene's files are written, nothing is loaded yet."""
 
     def close(self):
         self.pt.close(); self.scene.close(); self.grt.config_reset()

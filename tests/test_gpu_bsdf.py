@@ -28,6 +28,9 @@ from conftest import make_pathtracer
 pytestmark = pytest.mark.gpu
 
 GRIDS = cases.grids(every=3)
+# rt_bsdf_sample against the oracle: (direction absolute, pdf and throughput relative), for roughness >= 0.3 (and diffuse) and below it
+# (see the docstring; test_gpu_material.py holds the material launch's continuation rays to the same two pairs)
+SAMPLE_BOUNDS = {"rough": (1e-5, 1e-3), "smooth": (3e-4, 1e-2)}
 
 
 @pytest.fixture(scope="module")
@@ -66,7 +69,7 @@ def test_device_matches_oracle_and_reference(grt, dev, name, material_type, prob
         name, np.nonzero(differ & ~r.near)[0][:8].tolist())
     both = (got[:, 0] == 1) & ~flipped
     smooth = material_type != ref.DIFFUSE and checks.roughness_of(material_type, probes[0, :8]) < 0.3
-    dir_tol, rel_tol = (3e-4, 1e-2) if smooth else (1e-5, 1e-3)
+    dir_tol, rel_tol = SAMPLE_BOUNDS["smooth" if smooth else "rough"]
     errors = {"direction": np.abs(got[both, 5:8] - want[both, 5:8]).max(1) if both.any() else np.zeros(1)}
     for k, label in ((1, "pdf"), (2, "r"), (3, "g"), (4, "b")):
         errors[label] = np.abs(got[both, k] - want[both, k]) / np.maximum(np.abs(want[both, k]), 1e-30) if both.any() else np.zeros(1)

@@ -1,7 +1,8 @@
 """The host side of the kernel-level entry points ("probes") on one Cornell-box context: refusals the host decides before any HIP work
 (status, message text, output untouched), the empty batch of the nine entry points that return before allocating anything, and a render
-afterwards. No call here launches a probe kernel. The refusals other tests pin (rt_sort_rays in test_gpu_sort.py, the table checks of
-rt_upload_lights in test_gpu_nee.py) are not repeated."""
+afterwards. No call here launches a probe kernel. The refusals other tests pin (rt_sort_rays in test_gpu_sort.py, rt_shade_rays in
+test_gpu_material.py -- here only its checks that need no queue entry --, the table checks of rt_upload_lights in test_gpu_nee.py) are not
+repeated."""
 import ctypes
 from ctypes import byref, c_float, c_int32, c_size_t, c_void_p
 
@@ -60,6 +61,12 @@ def test_refusals_empty_batches_and_a_render_afterwards(grt):
         (lambda: lib.rt_generate_rays(ctx, 0, 0, -1, *[o] * 7), "rt_generate_rays: negative pixel_count"),
         (lambda: lib.rt_random_samples(ctx, 7, z, 1, 0, 0, o), "rt_random_samples: invalid argument"),
         (lambda: lib.rt_measure_stream_bandwidth(ctx, 512, 1, byref(gbps)), "rt_measure_stream_bandwidth: invalid argument"),
+        (lambda: lib.rt_shade_rays(ctx, 2, 0, 0, 0, None, 0, None, 0, None, 1, 1, SENTINEL, *[o] * 7, None), "rt_shade_rays: merged must be 0 (per-bounce launch) or 1 (merged wavefront)"),
+        (lambda: lib.rt_shade_rays(ctx, 0, 0, 0, 4, None, 0, None, 0, None, 1, 1, SENTINEL, *[o] * 7, None), "rt_shade_rays: material_slot must be 0 (diffuse), 1 (plastic), 2 (dielectric) or 3 (conductor)"),
+        (lambda: lib.rt_shade_rays(ctx, 0, 0, 0, 0, None, 0, None, 0, None, 1, 1, SENTINEL, o, None, *[o] * 5, None), "rt_shade_rays: NULL array"),
+        (lambda: lib.rt_shade_rays(ctx, 1, 0, 0, 0, None, 0, None, 0, None, 1, 1, SENTINEL, *[o] * 7, None), "rt_shade_rays: NULL slot table, submission births or statistics (merged form)"),
+        (lambda: lib.rt_shade_rays(ctx, 0, 127, 0, 0, None, 0, None, 0, None, 1, 1, SENTINEL, *[o] * 7, None), "rt_shade_rays: bounce outside [0, RT_MAX_BOUNCES - 1)"),
+        (lambda: lib.rt_shade_rays(ctx, 0, 0, 0, 0, None, 0, None, 0, None, 0, 1, SENTINEL, *[o] * 7, None), "rt_shade_rays: capacity must be in [1, 2^28]"),
     ]
     for call, message in refusals:
         assert call() == RT_ERROR_INVALID_ARG, message

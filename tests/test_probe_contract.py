@@ -1,6 +1,6 @@
 """The kernel-level entry points ("probes") refuse a NULL context before any HIP work: RT_ERROR_INVALID_ARG, and rt_last_error(NULL)
-is the entry point's own message (no GPU needed). Every other pointer is NULL and every count 0, except rt_sort_rays's capacity and
-frame_slots, which are 1."""
+is the entry point's own message (no GPU needed). Every other pointer is NULL and every count 0, except the capacity and frame_slots
+of rt_sort_rays and rt_shade_rays, which are 1."""
 import ctypes
 from ctypes import c_int, c_size_t, c_uint32, c_void_p
 
@@ -26,6 +26,7 @@ PROBES = {
     "rt_sample_lights":            ([P, Z, I, P],                                    [None, 0, 0, None],                                     "NULL argument"),
     "rt_perturb_normals":          ([I, P, Z, P],                                    [0, None, 0, None],                                     "NULL argument"),
     "rt_sort_rays":                ([I, I, I, P, Z, P, Z, P, Z, Z, U] + [P] * 9,     [0, 0, 0, None, 0, None, 0, None, 1, 1, 0] + [None] * 9, "NULL context"),
+    "rt_shade_rays":               ([I, I, I, I, P, Z, P, Z, P, Z, Z, U] + [P] * 8,  [0, 0, 0, 0, None, 0, None, 0, None, 1, 1, 0] + [None] * 8, "NULL context"),
     "rt_measure_stream_bandwidth": ([Z, I, P],                                       [0, 0, None],                                           "invalid argument"),
 }
 
@@ -38,8 +39,8 @@ def lib(grt):
     return lib
 
 
-def test_there_are_sixteen_probes():
-    assert len(PROBES) == 16
+def test_there_are_seventeen_probes():
+    assert len(PROBES) == 17
 
 
 @pytest.mark.parametrize("name", sorted(PROBES))
