@@ -852,7 +852,7 @@ struct BSDFConductor : BSDFCommon {
 };
 
 // rt_bsdf_eval / rt_bsdf_sample: one BSDF set up as set_up_surface sets it up, then its own eval or sample. Probe i reads material i
-// of p.materials (the per-call table rt_api.hip uploads). Record in: RT_BSDF_PROBE_IN floats {material[8], normal[3], direction[3],
+// of p.materials (the per-call table rt_probes.hip uploads). Record in: RT_BSDF_PROBE_IN floats {material[8], normal[3], direction[3],
 // entering, to_light[3], cos_theta_o, pixel, sample, bounce (uint32 bits), pad[2]}; out: RT_BSDF_PROBE_OUT floats {ok (1, 0, or -1:
 // omega_i.z <= 0), pdf, bsdf or throughput[3], direction out[3], medium id, allow_nee, omega_i.z, pad}.
 template<typename BSDF, bool EVAL>
@@ -1281,52 +1281,30 @@ RT_DEV void shade_material(const RtParams & p, int launch_bounce, int launch_sam
 	if (MERGED) stream_stats_flush(p, stats_lds);
 }
 
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_diffuse(RtParams p, int bounce, int sample_index)    { shade_material<BSDFDiffuse,    0, false>(p, bounce, sample_index); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic(RtParams p, int bounce, int sample_index)    { shade_material<BSDFPlastic,    1, false>(p, bounce, sample_index); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_dielectric(RtParams p, int bounce, int sample_index) { shade_material<BSDFDielectric, 2, false>(p, bounce, sample_index); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_conductor(RtParams p, int bounce, int sample_index)  { shade_material<BSDFConductor,  3, false>(p, bounce, sample_index); }
-// ..._texels: no texture on the device holds compressed blocks (RtParams::textures_compressed == 0)
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_diffuse_texels(RtParams p, int bounce, int sample_index) { shade_material<BSDFDiffuseT<false>, 0, false>(p, bounce, sample_index); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic_texels(RtParams p, int bounce, int sample_index) { shade_material<BSDFPlasticT<false>, 1, false>(p, bounce, sample_index); }
+// ---- the material kernels: one list, expanded for the four (SKY, NMAP) combinations ----------------------------------
+// A row: X(material, _texels or nothing, BSDF type, slot, waves per SIMD of the merged instance, ...). Each row yields, per combination,
+// the per-bounce kernel_material_<material><_texels><suffix> and the merged kernel_material_<material>_stream<_texels><suffix>.
+//   ..._texels: no texture on the device holds compressed blocks (RtParams::textures_compressed == 0)
+//   ..._sky:    sky importance sampling is active (RtParams::sky_nee_share > 0), launched only while it is
+//   ..._nmap:   some material of the slot has a normal map (RtParams::normal_map_slots), launched only then
+// The rows' order is material_kernels_for's index: the four slots, then the _texels forms of slots 0 and 1.
 #ifndef RT_SHADE_WAVES_DIFFUSE
 #define RT_SHADE_WAVES_DIFFUSE RT_SHADE_WAVES
 #endif
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES_DIFFUSE) kernel_material_diffuse_stream_texels(RtParams p) { shade_material<BSDFDiffuseT<false>, 0, true>(p, 0, 0); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic_stream_texels(RtParams p) { shade_material<BSDFPlasticT<false>, 1, true>(p, 0, 0); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_diffuse_stream(RtParams p)    { shade_material<BSDFDiffuse,    0, true>(p, 0, 0); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic_stream(RtParams p)    { shade_material<BSDFPlastic,    1, true>(p, 0, 0); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_dielectric_stream(RtParams p) { shade_material<BSDFDielectric, 2, true>(p, 0, 0); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_conductor_stream(RtParams p)  { shade_material<BSDFConductor,  3, true>(p, 0, 0); }
-// ..._sky: the same kernels with sky importance sampling (RtParams::sky_nee_share > 0), launched only while it is active
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_diffuse_sky(RtParams p, int bounce, int sample_index)          { shade_material<BSDFDiffuse,         0, false, true>(p, bounce, sample_index); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic_sky(RtParams p, int bounce, int sample_index)          { shade_material<BSDFPlastic,         1, false, true>(p, bounce, sample_index); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_dielectric_sky(RtParams p, int bounce, int sample_index)       { shade_material<BSDFDielectric,      2, false, true>(p, bounce, sample_index); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_conductor_sky(RtParams p, int bounce, int sample_index)        { shade_material<BSDFConductor,       3, false, true>(p, bounce, sample_index); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_diffuse_texels_sky(RtParams p, int bounce, int sample_index)   { shade_material<BSDFDiffuseT<false>, 0, false, true>(p, bounce, sample_index); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic_texels_sky(RtParams p, int bounce, int sample_index)   { shade_material<BSDFPlasticT<false>, 1, false, true>(p, bounce, sample_index); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES_DIFFUSE) kernel_material_diffuse_stream_texels_sky(RtParams p)            { shade_material<BSDFDiffuseT<false>, 0, true, true>(p, 0, 0); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic_stream_texels_sky(RtParams p)                   { shade_material<BSDFPlasticT<false>, 1, true, true>(p, 0, 0); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_diffuse_stream_sky(RtParams p)                          { shade_material<BSDFDiffuse,         0, true, true>(p, 0, 0); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic_stream_sky(RtParams p)                          { shade_material<BSDFPlastic,         1, true, true>(p, 0, 0); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_dielectric_stream_sky(RtParams p)                       { shade_material<BSDFDielectric,      2, true, true>(p, 0, 0); }
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_conductor_stream_sky(RtParams p)                        { shade_material<BSDFConductor,       3, true, true>(p, 0, 0); }
-// ..._nmap: the same kernels for a slot some of whose materials have a normal map (RtParams::normal_map_slots), launched only then
-#define RT_NMAP_KERNELS(SUFFIX, SKY) \
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_diffuse##SUFFIX(RtParams p, int bounce, int sample_index)        { shade_material<BSDFDiffuse,         0, false, SKY, true>(p, bounce, sample_index); } \
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic##SUFFIX(RtParams p, int bounce, int sample_index)        { shade_material<BSDFPlastic,         1, false, SKY, true>(p, bounce, sample_index); } \
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_dielectric##SUFFIX(RtParams p, int bounce, int sample_index)     { shade_material<BSDFDielectric,      2, false, SKY, true>(p, bounce, sample_index); } \
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_conductor##SUFFIX(RtParams p, int bounce, int sample_index)      { shade_material<BSDFConductor,       3, false, SKY, true>(p, bounce, sample_index); } \
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_diffuse_texels##SUFFIX(RtParams p, int bounce, int sample_index) { shade_material<BSDFDiffuseT<false>, 0, false, SKY, true>(p, bounce, sample_index); } \
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic_texels##SUFFIX(RtParams p, int bounce, int sample_index) { shade_material<BSDFPlasticT<false>, 1, false, SKY, true>(p, bounce, sample_index); } \
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES_DIFFUSE) kernel_material_diffuse_stream_texels##SUFFIX(RtParams p) { shade_material<BSDFDiffuseT<false>, 0, true, SKY, true>(p, 0, 0); } \
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic_stream_texels##SUFFIX(RtParams p)        { shade_material<BSDFPlasticT<false>, 1, true, SKY, true>(p, 0, 0); } \
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_diffuse_stream##SUFFIX(RtParams p)               { shade_material<BSDFDiffuse,         0, true, SKY, true>(p, 0, 0); } \
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_plastic_stream##SUFFIX(RtParams p)               { shade_material<BSDFPlastic,         1, true, SKY, true>(p, 0, 0); } \
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_dielectric_stream##SUFFIX(RtParams p)            { shade_material<BSDFDielectric,      2, true, SKY, true>(p, 0, 0); } \
-__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_conductor_stream##SUFFIX(RtParams p)             { shade_material<BSDFConductor,       3, true, SKY, true>(p, 0, 0); }
-RT_NMAP_KERNELS(_nmap, false)
-RT_NMAP_KERNELS(_sky_nmap, true)
-#undef RT_NMAP_KERNELS
+#define RT_MATERIAL_KERNEL_LIST(X, ...) \
+	X(diffuse,    ,        BSDFDiffuse,         0, RT_SHADE_WAVES,         __VA_ARGS__) \
+	X(plastic,    ,        BSDFPlastic,         1, RT_SHADE_WAVES,         __VA_ARGS__) \
+	X(dielectric, ,        BSDFDielectric,      2, RT_SHADE_WAVES,         __VA_ARGS__) \
+	X(conductor,  ,        BSDFConductor,       3, RT_SHADE_WAVES,         __VA_ARGS__) \
+	X(diffuse,    _texels, BSDFDiffuseT<false>, 0, RT_SHADE_WAVES_DIFFUSE, __VA_ARGS__) \
+	X(plastic,    _texels, BSDFPlasticT<false>, 1, RT_SHADE_WAVES,         __VA_ARGS__)
+#define RT_MATERIAL_KERNEL_VARIANTS(X) RT_MATERIAL_KERNEL_LIST(X, , false, false) RT_MATERIAL_KERNEL_LIST(X, _sky, true, false) RT_MATERIAL_KERNEL_LIST(X, _nmap, false, true) RT_MATERIAL_KERNEL_LIST(X, _sky_nmap, true, true)
+
+#define RT_DEFINE_MATERIAL_KERNELS(MATERIAL, TEXELS, BSDF, SLOT, STREAM_WAVES, SUFFIX, SKY, NMAP) \
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_##MATERIAL##TEXELS##SUFFIX(RtParams p, int bounce, int sample_index) { shade_material<BSDF, SLOT, false, SKY, NMAP>(p, bounce, sample_index); } \
+__global__ void __launch_bounds__(RT_SHADE_BLOCK, STREAM_WAVES) kernel_material_##MATERIAL##_stream##TEXELS##SUFFIX(RtParams p) { shade_material<BSDF, SLOT, true, SKY, NMAP>(p, 0, 0); }
+RT_MATERIAL_KERNEL_VARIANTS(RT_DEFINE_MATERIAL_KERNELS)
+#undef RT_DEFINE_MATERIAL_KERNELS
 
 // rt_perturb_normals: normal_map_perturb on explicit hits, the surface set up as set_up_surface sets it up (RT_NORMAL_PROBE_IN floats per
 // probe, layout in gpu_raytracer_amd.h; out: 4 floats {normal[3], fell back}). COMPRESSED is picked as for the material kernels.
@@ -1429,39 +1407,26 @@ static int streaming_grid(int work_items) {
 void rt_launch_generate(const RtParams & p, int sample_index, int pixel_offset, int pixel_count, hipStream_t stream) {
 	hipLaunchKernelGGL(kernel_generate, dim3(streaming_grid(pixel_count)), dim3(RT_SHADE_BLOCK), 0, stream, p, sample_index, pixel_offset, pixel_count);
 }
-// (the sort and material launchers take the ..._sky instances while sky importance sampling is active: RtParams::sky_nee_share > 0)
+// (the ..._sky instance while sky importance sampling is active, as for the material kernels)
 void rt_launch_sort(const RtParams & p, int bounce, int sample_index, hipStream_t stream) {
 	hipLaunchKernelGGL(p.sky_nee_share > 0.0f ? kernel_sort_sky : kernel_sort, dim3(2048 * RT_SHADE_BLOCK / RT_SORT_BLOCK), dim3(RT_SORT_BLOCK), 0, stream, p, bounce, sample_index);
 }
-// (... and the ..._nmap instances for a slot some of whose materials have a normal map: RtParams::normal_map_slots)
-static void launch_material_nmap(const RtParams & p, int material_slot, int bounce, int sample_index, hipStream_t stream) {
-	dim3 grid(2048), block(RT_SHADE_BLOCK);
-	const bool sky = p.sky_nee_share > 0.0f, compressed = p.textures_compressed != 0;
-	switch (material_slot) {
-		case 0: hipLaunchKernelGGL(sky ? (compressed ? kernel_material_diffuse_sky_nmap : kernel_material_diffuse_texels_sky_nmap) : (compressed ? kernel_material_diffuse_nmap : kernel_material_diffuse_texels_nmap), grid, block, 0, stream, p, bounce, sample_index); break;
-		case 1: hipLaunchKernelGGL(sky ? (compressed ? kernel_material_plastic_sky_nmap : kernel_material_plastic_texels_sky_nmap) : (compressed ? kernel_material_plastic_nmap : kernel_material_plastic_texels_nmap), grid, block, 0, stream, p, bounce, sample_index); break;
-		case 2: hipLaunchKernelGGL(sky ? kernel_material_dielectric_sky_nmap : kernel_material_dielectric_nmap, grid, block, 0, stream, p, bounce, sample_index); break;
-		case 3: hipLaunchKernelGGL(sky ? kernel_material_conductor_sky_nmap  : kernel_material_conductor_nmap,  grid, block, 0, stream, p, bounce, sample_index); break;
-	}
+// The entry points of every row, from the same list: [(NMAP * 2 + SKY) * material_rows + row]
+struct MaterialKernels { void (*bounce)(RtParams, int, int); void (*merged)(RtParams); };
+#define RT_MATERIAL_KERNEL_ENTRY(MATERIAL, TEXELS, BSDF, SLOT, STREAM_WAVES, SUFFIX, SKY, NMAP) { kernel_material_##MATERIAL##TEXELS##SUFFIX, kernel_material_##MATERIAL##_stream##TEXELS##SUFFIX },
+static const MaterialKernels material_kernels[] = { RT_MATERIAL_KERNEL_VARIANTS(RT_MATERIAL_KERNEL_ENTRY) };
+constexpr int material_rows = sizeof(material_kernels) / sizeof(material_kernels[0]) / 4;
+#undef RT_MATERIAL_KERNEL_ENTRY
+#undef RT_MATERIAL_KERNEL_VARIANTS
+#undef RT_MATERIAL_KERNEL_LIST
+// What the material launchers launch for a slot (0 .. 3)
+static const MaterialKernels & material_kernels_for(const RtParams & p, int material_slot) {
+	const int variant = (p.normal_map_slots >> material_slot & 1) * 2 + (p.sky_nee_share > 0.0f ? 1 : 0);
+	const int row = material_slot < 2 && !p.textures_compressed ? 4 + material_slot : material_slot;
+	return material_kernels[variant * material_rows + row];
 }
 void rt_launch_material(const RtParams & p, int material_slot, int bounce, int sample_index, hipStream_t stream) {
-	dim3 grid(2048), block(RT_SHADE_BLOCK);
-	if (p.normal_map_slots & (1 << material_slot)) { launch_material_nmap(p, material_slot, bounce, sample_index, stream); return; }
-	if (p.sky_nee_share > 0.0f) {
-		switch (material_slot) {
-			case 0: hipLaunchKernelGGL(p.textures_compressed ? kernel_material_diffuse_sky : kernel_material_diffuse_texels_sky, grid, block, 0, stream, p, bounce, sample_index); break;
-			case 1: hipLaunchKernelGGL(p.textures_compressed ? kernel_material_plastic_sky : kernel_material_plastic_texels_sky, grid, block, 0, stream, p, bounce, sample_index); break;
-			case 2: hipLaunchKernelGGL(kernel_material_dielectric_sky, grid, block, 0, stream, p, bounce, sample_index); break;
-			case 3: hipLaunchKernelGGL(kernel_material_conductor_sky,  grid, block, 0, stream, p, bounce, sample_index); break;
-		}
-		return;
-	}
-	switch (material_slot) {
-		case 0: if (p.textures_compressed) hipLaunchKernelGGL(kernel_material_diffuse, grid, block, 0, stream, p, bounce, sample_index); else hipLaunchKernelGGL(kernel_material_diffuse_texels, grid, block, 0, stream, p, bounce, sample_index); break;
-		case 1: if (p.textures_compressed) hipLaunchKernelGGL(kernel_material_plastic, grid, block, 0, stream, p, bounce, sample_index); else hipLaunchKernelGGL(kernel_material_plastic_texels, grid, block, 0, stream, p, bounce, sample_index); break;
-		case 2: hipLaunchKernelGGL(kernel_material_dielectric, grid, block, 0, stream, p, bounce, sample_index); break;
-		case 3: hipLaunchKernelGGL(kernel_material_conductor,  grid, block, 0, stream, p, bounce, sample_index); break;
-	}
+	hipLaunchKernelGGL(material_kernels_for(p, material_slot).bounce, dim3(2048), dim3(RT_SHADE_BLOCK), 0, stream, p, bounce, sample_index);
 }
 void rt_launch_generate_stream(const RtParams & p, int sample_index, int pixel_offset, int pixel_count, int slot_base, int queue_offset, int block_width, int band_rows, hipStream_t stream) {
 	hipLaunchKernelGGL(kernel_generate_stream, dim3(streaming_grid(pixel_count * p.batch_samples)), dim3(RT_SHADE_BLOCK), 0, stream, p, sample_index, pixel_offset, pixel_count, slot_base, queue_offset, block_width, band_rows);
@@ -1479,34 +1444,8 @@ void rt_launch_stream_advance(RtStreamControl * control, int iteration, int gene
 void rt_launch_sort_stream(const RtParams & p, hipStream_t stream) {
 	hipLaunchKernelGGL(p.sky_nee_share > 0.0f ? kernel_sort_stream_sky : kernel_sort_stream, dim3(RT_STREAM_SORT_GRID * RT_SHADE_BLOCK / RT_SORT_BLOCK), dim3(RT_SORT_BLOCK), 0, stream, p);
 }
-static void launch_material_stream_nmap(const RtParams & p, int material_slot, hipStream_t stream) {
-	dim3 grid(RT_STREAM_SHADE_GRID), block(RT_SHADE_BLOCK);
-	const bool sky = p.sky_nee_share > 0.0f, compressed = p.textures_compressed != 0;
-	switch (material_slot) {
-		case 0: hipLaunchKernelGGL(sky ? (compressed ? kernel_material_diffuse_stream_sky_nmap : kernel_material_diffuse_stream_texels_sky_nmap) : (compressed ? kernel_material_diffuse_stream_nmap : kernel_material_diffuse_stream_texels_nmap), grid, block, 0, stream, p); break;
-		case 1: hipLaunchKernelGGL(sky ? (compressed ? kernel_material_plastic_stream_sky_nmap : kernel_material_plastic_stream_texels_sky_nmap) : (compressed ? kernel_material_plastic_stream_nmap : kernel_material_plastic_stream_texels_nmap), grid, block, 0, stream, p); break;
-		case 2: hipLaunchKernelGGL(sky ? kernel_material_dielectric_stream_sky_nmap : kernel_material_dielectric_stream_nmap, grid, block, 0, stream, p); break;
-		case 3: hipLaunchKernelGGL(sky ? kernel_material_conductor_stream_sky_nmap  : kernel_material_conductor_stream_nmap,  grid, block, 0, stream, p); break;
-	}
-}
 void rt_launch_material_stream(const RtParams & p, int material_slot, hipStream_t stream) {
-	dim3 grid(RT_STREAM_SHADE_GRID), block(RT_SHADE_BLOCK);
-	if (p.normal_map_slots & (1 << material_slot)) { launch_material_stream_nmap(p, material_slot, stream); return; }
-	if (p.sky_nee_share > 0.0f) {
-		switch (material_slot) {
-			case 0: hipLaunchKernelGGL(p.textures_compressed ? kernel_material_diffuse_stream_sky : kernel_material_diffuse_stream_texels_sky, grid, block, 0, stream, p); break;
-			case 1: hipLaunchKernelGGL(p.textures_compressed ? kernel_material_plastic_stream_sky : kernel_material_plastic_stream_texels_sky, grid, block, 0, stream, p); break;
-			case 2: hipLaunchKernelGGL(kernel_material_dielectric_stream_sky, grid, block, 0, stream, p); break;
-			case 3: hipLaunchKernelGGL(kernel_material_conductor_stream_sky,  grid, block, 0, stream, p); break;
-		}
-		return;
-	}
-	switch (material_slot) {
-		case 0: if (p.textures_compressed) hipLaunchKernelGGL(kernel_material_diffuse_stream, grid, block, 0, stream, p); else hipLaunchKernelGGL(kernel_material_diffuse_stream_texels, grid, block, 0, stream, p); break;
-		case 1: if (p.textures_compressed) hipLaunchKernelGGL(kernel_material_plastic_stream, grid, block, 0, stream, p); else hipLaunchKernelGGL(kernel_material_plastic_stream_texels, grid, block, 0, stream, p); break;
-		case 2: hipLaunchKernelGGL(kernel_material_dielectric_stream, grid, block, 0, stream, p); break;
-		case 3: hipLaunchKernelGGL(kernel_material_conductor_stream,  grid, block, 0, stream, p); break;
-	}
+	hipLaunchKernelGGL(material_kernels_for(p, material_slot).merged, dim3(RT_STREAM_SHADE_GRID), dim3(RT_SHADE_BLOCK), 0, stream, p);
 }
 void rt_launch_ambient_occlusion(const RtParams & p, int sample_index, float ao_radius, hipStream_t stream) {
 	hipLaunchKernelGGL(kernel_ambient_occlusion, dim3(2048), dim3(RT_SHADE_BLOCK), 0, stream, p, sample_index, ao_radius);
@@ -1515,8 +1454,7 @@ void rt_launch_random(const RtParams & p, int dimension, const unsigned * pixel_
 	hipLaunchKernelGGL(kernel_random, dim3((count + 255) / 256), dim3(256), 0, stream, p, dimension, pixel_indices, count, bounce, sample_index, out);
 }
 void rt_launch_sample_texture(const RtParams & p, int texture_index, int filter, const float * args, int count, float4 * out, hipStream_t stream) {
-	if (p.textures_compressed) hipLaunchKernelGGL(kernel_sample_texture<true>, dim3((count + 255) / 256), dim3(256), 0, stream, p, texture_index, filter, args, count, out);
-	else hipLaunchKernelGGL(kernel_sample_texture<false>, dim3((count + 255) / 256), dim3(256), 0, stream, p, texture_index, filter, args, count, out);
+	hipLaunchKernelGGL(p.textures_compressed ? kernel_sample_texture<true> : kernel_sample_texture<false>, dim3((count + 255) / 256), dim3(256), 0, stream, p, texture_index, filter, args, count, out);
 }
 void rt_launch_sample_table(const float * table, int nx, int ny, int nz, int dims, const float * coords, int count, float * out, hipStream_t stream) {
 	hipLaunchKernelGGL(kernel_sample_table, dim3((count + 255) / 256), dim3(256), 0, stream, table, nx, ny, nz, dims, coords, count, out);
@@ -1525,8 +1463,7 @@ void rt_launch_sample_sky(const RtParams & p, const float * directions, int coun
 	hipLaunchKernelGGL(kernel_sample_sky, dim3((count + 255) / 256), dim3(256), 0, stream, p, directions, count, out);
 }
 void rt_launch_perturb_normals(const RtParams & p, int texture_index, const float * probes, int count, float * out, hipStream_t stream) {
-	if (p.textures_compressed) hipLaunchKernelGGL(kernel_perturb_normals<true>, dim3((count + 255) / 256), dim3(256), 0, stream, p, texture_index, probes, count, out);
-	else hipLaunchKernelGGL(kernel_perturb_normals<false>, dim3((count + 255) / 256), dim3(256), 0, stream, p, texture_index, probes, count, out);
+	hipLaunchKernelGGL(p.textures_compressed ? kernel_perturb_normals<true> : kernel_perturb_normals<false>, dim3((count + 255) / 256), dim3(256), 0, stream, p, texture_index, probes, count, out);
 }
 // diffuse and plastic: the COMPRESSED instantiations the textureless material kernels launch (no texture is read either way)
 template<bool EVAL>

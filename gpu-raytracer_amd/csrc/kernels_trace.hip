@@ -1285,37 +1285,32 @@ RT_DEV ClosestHitSource  closest_queue(const RtParams & p, int bounce) { return 
 RT_DEV ShadowQueueSource shadow_queue (const RtParams & p, int bounce) { return { p.shadow, p.aovs[RT_AOV_RADIANCE], p.aovs[RT_AOV_RADIANCE_DIRECT], p.aovs[RT_AOV_RADIANCE_INDIRECT], bounce }; }
 RT_DEV ShadowAOSource    ao_queue     (const RtParams & p)             { return { p.shadow, p.aovs[RT_AOV_RADIANCE] }; }
 
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh8(RtParams p, int bounce) { bvh8_trace_persistent<false, false>(p, closest_queue(p, bounce), p.sizes->trace[bounce], p.ray_cursors + 2 * bounce, nullptr, bounce == 0); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh8(RtParams p, int bounce) { bvh8_trace_persistent<true, false>(p, shadow_queue(p, bounce), p.sizes->shadow[bounce], p.ray_cursors + 2 * bounce + 1); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh8_ao(RtParams p) { bvh8_trace_persistent<true, false>(p, ao_queue(p), p.sizes->shadow[0], p.ray_cursors + 1); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh8_counting(RtParams p, int bounce, unsigned long long * stats) { bvh8_trace_persistent<false, true>(p, closest_queue(p, bounce), p.sizes->trace[bounce], p.ray_cursors + 2 * bounce, stats); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh8_counting(RtParams p, int bounce, unsigned long long * stats) { bvh8_trace_persistent<true, true>(p, shadow_queue(p, bounce), p.sizes->shadow[bounce], p.ray_cursors + 2 * bounce + 1, stats + 5); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh8_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, uint4 * hits, int ray_count, int * retired) { bvh8_trace_persistent<false, false>(p, ClosestHitSource { origin, direction, hits }, ray_count, retired); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh8_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, const float * max_distance, uint8_t * occluded, int ray_count, int * retired) { bvh8_trace_persistent<true, false>(p, ShadowExplicitSource { origin, direction, max_distance, occluded }, ray_count, retired); }
-
-// The same seven with opacity masks (launched iff p.opacity_active). Register budget: RT_MASK_WAVES, below.
+// The seven CWBVH entry points, once plain and once with opacity masks (..._mask: launched iff p.opacity_active; its register budget is its own)
 #ifndef RT_MASK_WAVES
 #define RT_MASK_WAVES RT_TRACE_LAUNCH_WAVES
 #endif
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_MASK_WAVES) kernel_trace_bvh8_mask(RtParams p, int bounce) { bvh8_trace_persistent<false, false, true>(p, closest_queue(p, bounce), p.sizes->trace[bounce], p.ray_cursors + 2 * bounce, nullptr, bounce == 0); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_MASK_WAVES) kernel_trace_shadow_bvh8_mask(RtParams p, int bounce) { bvh8_trace_persistent<true, false, true>(p, shadow_queue(p, bounce), p.sizes->shadow[bounce], p.ray_cursors + 2 * bounce + 1); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_MASK_WAVES) kernel_trace_shadow_bvh8_ao_mask(RtParams p) { bvh8_trace_persistent<true, false, true>(p, ao_queue(p), p.sizes->shadow[0], p.ray_cursors + 1); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_MASK_WAVES) kernel_trace_bvh8_counting_mask(RtParams p, int bounce, unsigned long long * stats) { bvh8_trace_persistent<false, true, true>(p, closest_queue(p, bounce), p.sizes->trace[bounce], p.ray_cursors + 2 * bounce, stats); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_MASK_WAVES) kernel_trace_shadow_bvh8_counting_mask(RtParams p, int bounce, unsigned long long * stats) { bvh8_trace_persistent<true, true, true>(p, shadow_queue(p, bounce), p.sizes->shadow[bounce], p.ray_cursors + 2 * bounce + 1, stats + 5); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_MASK_WAVES) kernel_trace_bvh8_explicit_mask(RtParams p, RtVec3SoA origin, RtVec3SoA direction, uint4 * hits, int ray_count, int * retired) { bvh8_trace_persistent<false, false, true>(p, ClosestHitSource { origin, direction, hits }, ray_count, retired); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_MASK_WAVES) kernel_trace_shadow_bvh8_explicit_mask(RtParams p, RtVec3SoA origin, RtVec3SoA direction, const float * max_distance, uint8_t * occluded, int ray_count, int * retired) { bvh8_trace_persistent<true, false, true>(p, ShadowExplicitSource { origin, direction, max_distance, occluded }, ray_count, retired); }
+#define RT_BVH8_KERNELS(SUFFIX, WAVES, MASK) \
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, WAVES) kernel_trace_bvh8##SUFFIX(RtParams p, int bounce) { bvh8_trace_persistent<false, false, MASK>(p, closest_queue(p, bounce), p.sizes->trace[bounce], p.ray_cursors + 2 * bounce, nullptr, bounce == 0); } \
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, WAVES) kernel_trace_shadow_bvh8##SUFFIX(RtParams p, int bounce) { bvh8_trace_persistent<true, false, MASK>(p, shadow_queue(p, bounce), p.sizes->shadow[bounce], p.ray_cursors + 2 * bounce + 1); } \
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, WAVES) kernel_trace_shadow_bvh8_ao##SUFFIX(RtParams p) { bvh8_trace_persistent<true, false, MASK>(p, ao_queue(p), p.sizes->shadow[0], p.ray_cursors + 1); } \
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, WAVES) kernel_trace_bvh8_counting##SUFFIX(RtParams p, int bounce, unsigned long long * stats) { bvh8_trace_persistent<false, true, MASK>(p, closest_queue(p, bounce), p.sizes->trace[bounce], p.ray_cursors + 2 * bounce, stats); } \
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, WAVES) kernel_trace_shadow_bvh8_counting##SUFFIX(RtParams p, int bounce, unsigned long long * stats) { bvh8_trace_persistent<true, true, MASK>(p, shadow_queue(p, bounce), p.sizes->shadow[bounce], p.ray_cursors + 2 * bounce + 1, stats + 5); } \
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, WAVES) kernel_trace_bvh8_explicit##SUFFIX(RtParams p, RtVec3SoA origin, RtVec3SoA direction, uint4 * hits, int ray_count, int * retired) { bvh8_trace_persistent<false, false, MASK>(p, ClosestHitSource { origin, direction, hits }, ray_count, retired); } \
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, WAVES) kernel_trace_shadow_bvh8_explicit##SUFFIX(RtParams p, RtVec3SoA origin, RtVec3SoA direction, const float * max_distance, uint8_t * occluded, int ray_count, int * retired) { bvh8_trace_persistent<true, false, MASK>(p, ShadowExplicitSource { origin, direction, max_distance, occluded }, ray_count, retired); }
+RT_BVH8_KERNELS(, RT_TRACE_LAUNCH_WAVES, false)
+RT_BVH8_KERNELS(_mask, RT_MASK_WAVES, true)
+#undef RT_BVH8_KERNELS
 
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh2(RtParams p, int bounce) { bvh_trace_persistent<Bvh2Step, false>(p, closest_queue(p, bounce), p.sizes->trace[bounce], p.ray_cursors + 2 * bounce); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh2(RtParams p, int bounce) { bvh_trace_persistent<Bvh2Step, true>(p, shadow_queue(p, bounce), p.sizes->shadow[bounce], p.ray_cursors + 2 * bounce + 1); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh2_ao(RtParams p) { bvh_trace_persistent<Bvh2Step, true>(p, ao_queue(p), p.sizes->shadow[0], p.ray_cursors + 1); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh2_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, uint4 * hits, int ray_count, int * retired) { bvh_trace_persistent<Bvh2Step, false>(p, ClosestHitSource { origin, direction, hits }, ray_count, retired); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh2_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, const float * max_distance, uint8_t * occluded, int ray_count, int * retired) { bvh_trace_persistent<Bvh2Step, true>(p, ShadowExplicitSource { origin, direction, max_distance, occluded }, ray_count, retired); }
-
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh4(RtParams p, int bounce) { bvh_trace_persistent<Bvh4Step, false>(p, closest_queue(p, bounce), p.sizes->trace[bounce], p.ray_cursors + 2 * bounce); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh4(RtParams p, int bounce) { bvh_trace_persistent<Bvh4Step, true>(p, shadow_queue(p, bounce), p.sizes->shadow[bounce], p.ray_cursors + 2 * bounce + 1); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh4_ao(RtParams p) { bvh_trace_persistent<Bvh4Step, true>(p, ao_queue(p), p.sizes->shadow[0], p.ray_cursors + 1); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_bvh4_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, uint4 * hits, int ray_count, int * retired) { bvh_trace_persistent<Bvh4Step, false>(p, ClosestHitSource { origin, direction, hits }, ray_count, retired); }
-__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_bvh4_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, const float * max_distance, uint8_t * occluded, int ray_count, int * retired) { bvh_trace_persistent<Bvh4Step, true>(p, ShadowExplicitSource { origin, direction, max_distance, occluded }, ray_count, retired); }
+// The five entry points of the binary and the 4-wide BVH
+#define RT_BVH_KERNELS(WIDTH, STEP) \
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_##WIDTH(RtParams p, int bounce) { bvh_trace_persistent<STEP, false>(p, closest_queue(p, bounce), p.sizes->trace[bounce], p.ray_cursors + 2 * bounce); } \
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_##WIDTH(RtParams p, int bounce) { bvh_trace_persistent<STEP, true>(p, shadow_queue(p, bounce), p.sizes->shadow[bounce], p.ray_cursors + 2 * bounce + 1); } \
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_##WIDTH##_ao(RtParams p) { bvh_trace_persistent<STEP, true>(p, ao_queue(p), p.sizes->shadow[0], p.ray_cursors + 1); } \
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_##WIDTH##_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, uint4 * hits, int ray_count, int * retired) { bvh_trace_persistent<STEP, false>(p, ClosestHitSource { origin, direction, hits }, ray_count, retired); } \
+__global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_shadow_##WIDTH##_explicit(RtParams p, RtVec3SoA origin, RtVec3SoA direction, const float * max_distance, uint8_t * occluded, int ray_count, int * retired) { bvh_trace_persistent<STEP, true>(p, ShadowExplicitSource { origin, direction, max_distance, occluded }, ray_count, retired); }
+RT_BVH_KERNELS(bvh2, Bvh2Step)
+RT_BVH_KERNELS(bvh4, Bvh4Step)
+#undef RT_BVH_KERNELS
 
 // The ONE traversal launch of an iteration of the merged wavefront: the closest-hit rays of the iteration (primary rays of
 // the newest submission and the continuation rays of all others) and then, by the same persistent waves as they run out of
@@ -1435,13 +1430,17 @@ template<auto K> static int persistent_grid() {
 template<auto K, typename... A> static void launch_persistent(hipStream_t stream, const A &... args) {
 	hipLaunchKernelGGL(K, dim3(persistent_grid<K>()), dim3(RT_TRACE_BLOCK), 0, stream, args...);
 }
-// The kernel of the context's BVH type: p.bvh_width 2 or 4, else the CWBVH -- its _mask instance K8M iff the context holds opacity masks
-// (the entry points of rt_api.hip refuse masks with the other two widths before any launch).
+// The CWBVH kernel of the context: its _mask instance K8M iff the context holds opacity masks ...
+template<auto K8, auto K8M, typename... A> static void launch_for_mask(const RtParams & p, hipStream_t stream, const A &... args) {
+	if (p.opacity_active) launch_persistent<K8M>(stream, p, args...);
+	else launch_persistent<K8>(stream, p, args...);
+}
+// ... and the kernel of the context's BVH type: p.bvh_width 2 or 4, else the CWBVH (the entry points of rt_api.hip refuse masks with the
+// other two widths before any launch).
 template<auto K2, auto K4, auto K8, auto K8M, typename... A> static void launch_for_width(const RtParams & p, hipStream_t stream, const A &... args) {
 	if (p.bvh_width == 2) launch_persistent<K2>(stream, p, args...);
 	else if (p.bvh_width == 4) launch_persistent<K4>(stream, p, args...);
-	else if (p.opacity_active) launch_persistent<K8M>(stream, p, args...);
-	else launch_persistent<K8>(stream, p, args...);
+	else launch_for_mask<K8, K8M>(p, stream, args...);
 }
 
 void rt_launch_trace(const RtParams & p, int bounce, hipStream_t stream) {
@@ -1453,46 +1452,46 @@ void rt_launch_trace_shadow(const RtParams & p, int bounce, hipStream_t stream) 
 void rt_launch_trace_shadow_ao(const RtParams & p, hipStream_t stream) {
 	launch_for_width<kernel_trace_shadow_bvh2_ao, kernel_trace_shadow_bvh4_ao, kernel_trace_shadow_bvh8_ao, kernel_trace_shadow_bvh8_ao_mask>(p, stream);
 }
-void rt_launch_trace_stream(const RtParams & p, unsigned long long * stats, hipStream_t stream) {
-	if (p.opacity_active) {   // the same choice among the _mask instances
-		if (stats) launch_persistent<kernel_trace_stream_bvh8_counting_mask>(stream, p, stats);
-		else if (p.entry_tlas_stack_size == 0 && p.geometry_below_4gib) {
-			if (rt_skip_walk(p)) launch_persistent<kernel_trace_stream_bvh8_flat_skip_mask>(stream, p);
-			else launch_persistent<kernel_trace_stream_bvh8_flat_mask>(stream, p);
-		} else launch_persistent<kernel_trace_stream_bvh8_mask>(stream, p);
-		return;
-	}
-	if (stats) launch_persistent<kernel_trace_stream_bvh8_counting>(stream, p, stats);
-	else if (p.entry_tlas_stack_size == 0 && p.geometry_below_4gib) {   // the whole scene is one world-space tree: the engine without the TLAS / instance code (32-bit offsets; a larger scene walks the general engine from node 0)
-		if (rt_skip_walk(p)) launch_persistent<kernel_trace_stream_bvh8_flat_skip>(stream, p);
-		else launch_persistent<kernel_trace_stream_bvh8_flat>(stream, p);
-	} else launch_persistent<kernel_trace_stream_bvh8>(stream, p);
+// The merged launch: which of its eight kernels p takes (RT_STREAM_KERNEL_*; the four _MASK values follow the four plain ones in their order) ...
+static int stream_kernel_id(const RtParams & p, bool stats) {
+	// flat: the whole scene is one world-space tree, so the engine without the TLAS / instance code (32-bit offsets; a larger scene walks the
+	// general engine from node 0). The counting instances take either scene and branch on rt_skip_walk themselves.
+	const int kernel = stats ? RT_STREAM_KERNEL_COUNTING
+	                 : p.entry_tlas_stack_size == 0 && p.geometry_below_4gib ? (rt_skip_walk(p) ? RT_STREAM_KERNEL_FLAT_SKIP : RT_STREAM_KERNEL_FLAT)
+	                 : RT_STREAM_KERNEL_GENERAL;
+	return p.opacity_active ? kernel + RT_STREAM_KERNEL_GENERAL_MASK : kernel;
 }
-// What rt_launch_trace_stream launches for p (the same choice, made on the host): info[0] the kernel (RT_STREAM_KERNEL_*), info[1] the waves
-// of its persistent grid, info[2] RT_NARROW_MAX_RAYS, info[3] RT_MIXED_MAX_RAYS. For rt_trace_stream_rays, which reports it to tests.
+// ... and, by that id, its launch and its persistent grid: what rt_launch_trace_stream launches and what rt_trace_stream_launch_info reports
+struct StreamKernel { void (*launch)(hipStream_t, const RtParams &, unsigned long long *); int (*grid)(); };
+template<auto K> static void launch_stream(hipStream_t stream, const RtParams & p, unsigned long long *) { launch_persistent<K>(stream, p); }
+template<auto K> static void launch_stream_counting(hipStream_t stream, const RtParams & p, unsigned long long * stats) { launch_persistent<K>(stream, p, stats); }
+static const StreamKernel stream_kernels[] = {   // in the order of RT_STREAM_KERNEL_*
+	{ launch_stream<kernel_trace_stream_bvh8>,                        persistent_grid<kernel_trace_stream_bvh8> },
+	{ launch_stream<kernel_trace_stream_bvh8_flat>,                   persistent_grid<kernel_trace_stream_bvh8_flat> },
+	{ launch_stream<kernel_trace_stream_bvh8_flat_skip>,              persistent_grid<kernel_trace_stream_bvh8_flat_skip> },
+	{ launch_stream_counting<kernel_trace_stream_bvh8_counting>,      persistent_grid<kernel_trace_stream_bvh8_counting> },
+	{ launch_stream<kernel_trace_stream_bvh8_mask>,                   persistent_grid<kernel_trace_stream_bvh8_mask> },
+	{ launch_stream<kernel_trace_stream_bvh8_flat_mask>,              persistent_grid<kernel_trace_stream_bvh8_flat_mask> },
+	{ launch_stream<kernel_trace_stream_bvh8_flat_skip_mask>,         persistent_grid<kernel_trace_stream_bvh8_flat_skip_mask> },
+	{ launch_stream_counting<kernel_trace_stream_bvh8_counting_mask>, persistent_grid<kernel_trace_stream_bvh8_counting_mask> },
+};
+static_assert(RT_STREAM_KERNEL_GENERAL == 0 && RT_STREAM_KERNEL_FLAT == 1 && RT_STREAM_KERNEL_FLAT_SKIP == 2 && RT_STREAM_KERNEL_COUNTING == 3 &&
+              RT_STREAM_KERNEL_GENERAL_MASK == 4 && RT_STREAM_KERNEL_FLAT_MASK == 5 && RT_STREAM_KERNEL_FLAT_SKIP_MASK == 6 && RT_STREAM_KERNEL_COUNTING_MASK == 7 &&
+              sizeof(stream_kernels) / sizeof(stream_kernels[0]) == 8, "stream_kernels is indexed by RT_STREAM_KERNEL_*");
+void rt_launch_trace_stream(const RtParams & p, unsigned long long * stats, hipStream_t stream) {
+	stream_kernels[stream_kernel_id(p, stats != nullptr)].launch(stream, p, stats);
+}
+// What rt_launch_trace_stream launches for p: info[0] the kernel (RT_STREAM_KERNEL_*), info[1] the waves of its persistent grid,
+// info[2] RT_NARROW_MAX_RAYS, info[3] RT_MIXED_MAX_RAYS. For rt_trace_stream_rays, which reports it to tests.
 void rt_trace_stream_launch_info(const RtParams & p, bool stats, int32_t * info) {
-	int kernel, grid;
-	if (p.opacity_active) {
-		if (stats) { kernel = RT_STREAM_KERNEL_COUNTING_MASK; grid = persistent_grid<kernel_trace_stream_bvh8_counting_mask>(); }
-		else if (p.entry_tlas_stack_size == 0 && p.geometry_below_4gib) {
-			if (rt_skip_walk(p)) { kernel = RT_STREAM_KERNEL_FLAT_SKIP_MASK; grid = persistent_grid<kernel_trace_stream_bvh8_flat_skip_mask>(); }
-			else { kernel = RT_STREAM_KERNEL_FLAT_MASK; grid = persistent_grid<kernel_trace_stream_bvh8_flat_mask>(); }
-		} else { kernel = RT_STREAM_KERNEL_GENERAL_MASK; grid = persistent_grid<kernel_trace_stream_bvh8_mask>(); }
-	} else
-	if (stats) { kernel = RT_STREAM_KERNEL_COUNTING; grid = persistent_grid<kernel_trace_stream_bvh8_counting>(); }
-	else if (p.entry_tlas_stack_size == 0 && p.geometry_below_4gib) {
-		if (rt_skip_walk(p)) { kernel = RT_STREAM_KERNEL_FLAT_SKIP; grid = persistent_grid<kernel_trace_stream_bvh8_flat_skip>(); }
-		else { kernel = RT_STREAM_KERNEL_FLAT; grid = persistent_grid<kernel_trace_stream_bvh8_flat>(); }
-	} else { kernel = RT_STREAM_KERNEL_GENERAL; grid = persistent_grid<kernel_trace_stream_bvh8>(); }
-	info[0] = kernel; info[1] = grid * (RT_TRACE_BLOCK / RT_WAVE_SIZE); info[2] = RT_NARROW_MAX_RAYS; info[3] = RT_MIXED_MAX_RAYS;
+	const int kernel = stream_kernel_id(p, stats);
+	info[0] = kernel; info[1] = stream_kernels[kernel].grid() * (RT_TRACE_BLOCK / RT_WAVE_SIZE); info[2] = RT_NARROW_MAX_RAYS; info[3] = RT_MIXED_MAX_RAYS;
 }
 void rt_launch_trace_counting(const RtParams & p, int bounce, unsigned long long * stats, hipStream_t stream) {
-	if (p.opacity_active) launch_persistent<kernel_trace_bvh8_counting_mask>(stream, p, bounce, stats);
-	else launch_persistent<kernel_trace_bvh8_counting>(stream, p, bounce, stats);
+	launch_for_mask<kernel_trace_bvh8_counting, kernel_trace_bvh8_counting_mask>(p, stream, bounce, stats);
 }
 void rt_launch_trace_shadow_counting(const RtParams & p, int bounce, unsigned long long * stats, hipStream_t stream) {
-	if (p.opacity_active) launch_persistent<kernel_trace_shadow_bvh8_counting_mask>(stream, p, bounce, stats);
-	else launch_persistent<kernel_trace_shadow_bvh8_counting>(stream, p, bounce, stats);
+	launch_for_mask<kernel_trace_shadow_bvh8_counting, kernel_trace_shadow_bvh8_counting_mask>(p, stream, bounce, stats);
 }
 void rt_launch_trace_explicit(const RtParams & p, RtVec3SoA origin, RtVec3SoA direction, uint4 * hits, int ray_count, int * retired_counter, hipStream_t stream) {
 	launch_for_width<kernel_trace_bvh2_explicit, kernel_trace_bvh4_explicit, kernel_trace_bvh8_explicit, kernel_trace_bvh8_explicit_mask>(p, stream, origin, direction, hits, ray_count, retired_counter);

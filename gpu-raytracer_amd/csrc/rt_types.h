@@ -58,7 +58,7 @@ struct RtBufferSizes { // Pathtracer.cu:103-114
 	int rays_retired_shadow[RT_MAX_BOUNCES];
 };
 
-// ---- merged wavefront (rt_api.hip, "PathStream") -----------------------------------------------------------
+// ---- merged wavefront (rt_context.h, "PathStream") ---------------------------------------------------------
 // Instead of one launch chain per submission (generate -> (trace, sort, shade, shadow) x bounces), whose launches
 // shrink bounce by bounce until they no longer fill the GPU, consecutive submissions feed ONE wavefront: iteration
 // i traces / sorts / shades the rays of every submission in flight -- the primary rays of the newest next to bounce
@@ -120,7 +120,7 @@ struct RtParams {
 	const float4 * bvh2_nodes;  // 2 float4 per node
 	const float4 * bvh4_nodes;  // 8 float4 per node
 	// The TLAS (node indices [0, tlas_node_count) of whichever BVH type is selected) is versioned per
-	// frame and lives outside the static node arrays, see rt_api.hip (SceneRing).
+	// frame and lives outside the static node arrays, see rt_context.h (SceneRing).
 	const float4 * tlas_nodes;
 	int tlas_node_count;
 	int bvh_width;              // 8: CWBVH kernels (default), 4: 4-wide BVH kernels, 2: binary-BVH kernels
