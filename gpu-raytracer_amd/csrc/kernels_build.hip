@@ -93,6 +93,7 @@ __global__ void __launch_bounds__(RT_BUILD_THREADS) kernel_build_tlas(TlasBuildA
 		for (int w = 0; w < threads / RT_WAVE_SIZE; w++) for (int d = 0; d < 3; d++) { scene.min[d] = fminf(scene.min[d], reduce[w][d]); scene.max[d] = fmaxf(scene.max[d], reduce[w][3 + d]); }
 	}
 	__syncthreads();
+	const float extent_floor = tlas_extent_floor(scene);   // no node grid finer than traversal resolves (rt_tlas_build.h)
 	RT_TLAS_STAMP(0)
 
 	// ---- 2: Morton keys, bitonic sort (padded with the largest key to a power of two)
@@ -223,7 +224,7 @@ __global__ void __launch_bounds__(RT_BUILD_THREADS) kernel_build_tlas(TlasBuildA
 				uint32_t header[4]; uint32_t exponents = 0; float inv_e[3];
 				#pragma unroll
 				for (int d = 0; d < 3; d++) {
-					float extent = tlas_maxf(node.max[d] - node.min[d], 1.0e-30f);
+					float extent = tlas_maxf(node.max[d] - node.min[d], extent_floor);
 					uint32_t bits = __float_as_uint(extent * (1.0f / 255.0f));
 					uint32_t biased = bits >> 23;
 					if (bits & 0x7FFFFFu) biased++;
@@ -231,7 +232,7 @@ __global__ void __launch_bounds__(RT_BUILD_THREADS) kernel_build_tlas(TlasBuildA
 					if (biased > 254u) biased = 254u;
 					inv_e[d] = 1.0f / __uint_as_float(biased << 23);
 					exponents |= biased << (8 * d);
-					header[d] = __float_as_uint(node.min[d]);
+					header[d] = __float_as_uint(node.min[d] + 0.0f);   // (+0.0 for either zero: the lanes of the shuffle union hold different ones)
 				}
 				header[3] = exponents | (inner_mask << 24);
 				#pragma unroll
@@ -247,6 +248,7 @@ __global__ void __launch_bounds__(RT_BUILD_THREADS) kernel_build_tlas(TlasBuildA
 						float lo = floorf((box.min[d] - node.min[d]) * inv_e[d]);
 						float hi = ceilf ((box.max[d] - node.min[d]) * inv_e[d]);
 						lo = tlas_minf(tlas_maxf(lo, 0.0f), 255.0f); hi = tlas_minf(tlas_maxf(hi, 0.0f), 255.0f);
+						tlas_keep_thickness(lo, hi);   // a box quantised to one grid line would never be entered
 						bytes[32 + 16 * d + my_slot]     = uint8_t(lo);
 						bytes[32 + 16 * d + 8 + my_slot] = uint8_t(hi);
 					}

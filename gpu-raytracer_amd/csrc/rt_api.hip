@@ -806,6 +806,23 @@ int rt_read_tlas(rt_context * ctx, int32_t * order, void * nodes, size_t node_ca
 	return RT_OK;
 }
 
+int rt_read_instances(rt_context * ctx, int32_t * root_indices, int32_t * material_ids, float * transforms, float * transforms_inv, float * transforms_prev, int32_t * position) {
+	RT_REQUIRE(ctx, ctx, "rt_read_instances: NULL context");
+	(void)hipSetDevice(ctx->device);
+	const RtParams & p = ctx->params;
+	if (!p.mesh_bvh_root_indices) return fail(ctx, RT_ERROR_NOT_READY, "rt_read_instances: no instance tables on the device (rt_upload_instances, rt_build_tlas)");
+	if (position && !p.mesh_position) return fail(ctx, RT_ERROR_NOT_READY, "rt_read_instances: position[] exists only when the current TLAS was built on the device (rt_build_tlas)");
+	RT_HIP(ctx, quiesce(ctx));
+	const size_t n = ctx->mesh_count;
+	if (root_indices)    RT_HIP(ctx, hipMemcpy(root_indices,    p.mesh_bvh_root_indices, n * 4,  hipMemcpyDeviceToHost));
+	if (material_ids)    RT_HIP(ctx, hipMemcpy(material_ids,    p.mesh_material_ids,     n * 4,  hipMemcpyDeviceToHost));
+	if (transforms)      RT_HIP(ctx, hipMemcpy(transforms,      p.mesh_transforms,       n * 48, hipMemcpyDeviceToHost));
+	if (transforms_inv)  RT_HIP(ctx, hipMemcpy(transforms_inv,  p.mesh_transforms_inv,   n * 48, hipMemcpyDeviceToHost));
+	if (transforms_prev) RT_HIP(ctx, hipMemcpy(transforms_prev, p.mesh_transforms_prev,  n * 48, hipMemcpyDeviceToHost));
+	if (position)        RT_HIP(ctx, hipMemcpy(position,        p.mesh_position,         n * 4,  hipMemcpyDeviceToHost));
+	return RT_OK;
+}
+
 int rt_upload_materials(rt_context * ctx, const uint8_t * types, const void * materials, size_t count) {
 	RT_REQUIRE(ctx, ctx && types && materials, "rt_upload_materials: NULL argument");
 	(void)hipSetDevice(ctx->device);

@@ -127,16 +127,35 @@ RT_HD void tlas_assign_slots(const TlasBox & node, const TlasBox * children, int
 	for (int c = 0; c < count; c++) if (slot_of_child[c] < 0) { int s = 0; while (taken[s]) s++; taken[s] = true; slot_of_child[c] = s; } // NaN boxes
 }
 
+// No flat child boxes: the traversal's node test is `tmin < tmax`, a child box whose lower and upper bound were quantised to the
+// same grid line is never entered and the instance below it is lost (a flat mesh, or one much smaller than a grid step, whose
+// bounds happen to lie on a grid line). Such a box is widened by one grid step: upwards, or downwards at the end of the grid.
+// (kernels_blas.hip has the same lesson for the BLAS build, where it pads the triangle boxes themselves.)
+RT_HD void tlas_keep_thickness(float & lo, float & hi) {
+	if (hi == lo) { if (hi < 255.0f) hi += 1.0f; else lo -= 1.0f; }
+}
+
+// ... and no grid finer than float32 traversal resolves. A node whose children are coplanar (tiles of one floor) has no extent on
+// that axis; on a grid laid over the extent alone (formerly floored at 1e-30) a step is ~1e-32 and the widened child box still
+// vanishes when the node test rounds `q * step / d + (origin - ray origin) / d`. The extent a grid is laid over is therefore at
+// least 1 / 2048 of the largest coordinate of the scene box: a step is then 2^-19 or more of the distances the test subtracts
+// for ray origins within a few scene sizes, some 16 float32 spacings. Nodes of ordinary extent keep their grid.
+RT_HD float tlas_extent_floor(const TlasBox & scene) {
+	float largest = 0.0f;
+	for (int d = 0; d < 3; d++) largest = tlas_maxf(largest, tlas_maxf(fabsf(scene.min[d]), fabsf(scene.max[d])));
+	return tlas_maxf(largest * (1.0f / 2048.0f), 1.0e-30f);
+}
+
 // One CWBVH node (20 words = 5 x float4, BVH8.h:19-25). boxes / is_inner are in SLOT order (is_inner < 0: empty slot,
 // 0: one instance, 1: inner node); inner children occupy consecutive node indices from base_child in slot order, the
 // leaves consecutive instance positions from base_leaf in slot order.
-RT_HD void tlas_encode_node(const TlasBox & node, const TlasBox boxes[8], const int is_inner[8], uint32_t base_child, uint32_t base_leaf, uint32_t out[20]) {
+RT_HD void tlas_encode_node(const TlasBox & node, const TlasBox boxes[8], const int is_inner[8], uint32_t base_child, uint32_t base_leaf, float extent_floor, uint32_t out[20]) {
 	for (int i = 0; i < 20; i++) out[i] = 0;
 	float e[3], inv_e[3];
 	uint32_t exponents = 0;
 	for (int d = 0; d < 3; d++) {
-		// smallest power of two e with extent / e <= 255 (BVH8Converter.cpp:229-253); a flat axis gets the smallest normal scale
-		float extent = tlas_maxf(node.max[d] - node.min[d], 1.0e-30f);
+		// smallest power of two e with extent / e <= 255 (BVH8Converter.cpp:229-253); a flat or very thin axis gets the grid of tlas_extent_floor
+		float extent = tlas_maxf(node.max[d] - node.min[d], extent_floor);
 		union { float f; uint32_t u; } scale;
 		scale.f = extent * (1.0f / 255.0f);
 		uint32_t biased = scale.u >> 23;
@@ -146,7 +165,7 @@ RT_HD void tlas_encode_node(const TlasBox & node, const TlasBox boxes[8], const 
 		scale.u = biased << 23;
 		e[d] = scale.f; inv_e[d] = 1.0f / scale.f;
 		exponents |= biased << (8 * d);
-		union { float f; uint32_t u; } origin; origin.f = node.min[d];
+		union { float f; uint32_t u; } origin; origin.f = node.min[d] + 0.0f;   // -0.0 becomes +0.0: which of two equal zeros a union keeps depends on its order
 		out[d] = origin.u;
 	}
 	uint32_t imask = 0, leaves = 0;
@@ -158,6 +177,7 @@ RT_HD void tlas_encode_node(const TlasBox & node, const TlasBox boxes[8], const 
 			float lo = floorf((boxes[s].min[d] - node.min[d]) * inv_e[d]);
 			float hi = ceilf ((boxes[s].max[d] - node.min[d]) * inv_e[d]);
 			lo = tlas_minf(tlas_maxf(lo, 0.0f), 255.0f); hi = tlas_minf(tlas_maxf(hi, 0.0f), 255.0f);
+			tlas_keep_thickness(lo, hi);
 			q[16 * d + s]     = uint8_t(lo);
 			q[16 * d + 8 + s] = uint8_t(hi);
 		}

@@ -263,6 +263,12 @@ int rt_build_tlas(rt_context * ctx, const int32_t * root_indices, const int32_t 
                   const float * transforms, const float * transforms_inv, const float * transforms_prev,
                   const float * local_boxes, size_t mesh_count);
 int rt_read_tlas(rt_context * ctx, int32_t * order, void * nodes, size_t node_capacity, int32_t * node_count);
+/* The instance tables the kernels read, in TLAS order (tests): mesh_count entries each as rt_upload_instances takes them -- what was
+ * uploaded, or what rt_build_tlas gathered -- and position[scene index] = TLAS position, which exists only while the current TLAS
+ * is the device's (else RT_ERROR_NOT_READY when asked for). Waits for the work in flight; any pointer may be NULL.
+ * (An addition that changes no struct: RT_ABI_VERSION stays.)                                                                     */
+int rt_read_instances(rt_context * ctx, int32_t * root_indices, int32_t * material_ids,
+                      float * transforms, float * transforms_inv, float * transforms_prev, int32_t * position);
 /* Replaces mesh_bvh_root_indices / mesh_material_ids / mesh_transforms{,_inv,_prev}
  * (Integrator.cpp:412-429). Index = TLAS-order mesh id. Matrices are 12 floats, row-major
  * 3x4.  MSB of root_indices[i] = "identity transform" (Integrator.cpp:415).              */

@@ -15,7 +15,7 @@
 //   * the cut of a run: where the highest differing key bit flips (equal keys: the middle);
 //   * up to eight runs per node: cut the widest run (first such) until eight or all single;
 //   * slots: greedy smallest (centre offset . slot diagonal), ties to the lower child, then the lower slot;
-//   * node bytes: as the reference's converter writes them.
+//   * node bytes: as the reference's converter writes them, but no child box of zero thickness (see write_node).
 // tests/test_tlas.py additionally checks the result on its own terms (every instance in exactly one leaf, child boxes
 // contain their instances, inner children consecutive) and tests/test_gpu_tlas.py that tracing it gives the hits of
 // the host-built TLAS, whose builder IS the reference's (Integrator.cpp:399-430) byte for byte.
@@ -134,19 +134,27 @@ uint32_t bits_of(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
 float float_of(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 
 // kind[s]: -1 empty slot, 0 a single instance, 1 an inner node
-void write_node(const Box3 & node, const Box3 slot_box[8], const int kind[8], uint32_t first_child_node, uint32_t first_leaf, uint32_t * words20) {
+// The least extent a node's grid is laid over: a 2048th of the largest coordinate the scene box has (1e-30 for a scene at the origin
+// alone). A finer grid's steps are lost when the traversal's node test rounds its distances, and with them a flat child box.
+float least_grid_extent(const Box3 & scene) {
+	float farthest = 0.0f;
+	for (int a = 0; a < 3; a++) farthest = greater(farthest, greater(std::fabs(scene.lo[a]), std::fabs(scene.hi[a])));
+	return greater(farthest / 2048.0f, 1.0e-30f);
+}
+
+void write_node(const Box3 & node, const Box3 slot_box[8], const int kind[8], uint32_t first_child_node, uint32_t first_leaf, float least_extent, uint32_t * words20) {
 	std::memset(words20, 0, 80);
 	float inverse_scale[3]; uint32_t exponent_bytes = 0;
 	for (int a = 0; a < 3; a++) {
-		// the smallest power of two e with extent / e <= 255; a flat axis gets the smallest normal scale
-		float extent = greater(node.hi[a] - node.lo[a], 1.0e-30f);
+		// the smallest power of two e with extent / e <= 255, the extent not below least_grid_extent
+		float extent = greater(node.hi[a] - node.lo[a], least_extent);
 		uint32_t scale_bits = bits_of(extent * (1.0f / 255.0f));
 		uint32_t exponent = scale_bits >> 23;
 		if (scale_bits & 0x007fffffu) exponent += 1;                 // not a power of two already
 		exponent = std::min(std::max(exponent, 1u), 254u);
 		inverse_scale[a] = 1.0f / float_of(exponent << 23);
 		exponent_bytes |= exponent << (8 * a);
-		words20[a] = bits_of(node.lo[a]);
+		words20[a] = bits_of(node.lo[a] + 0.0f);   // a zero origin is written as +0.0, whichever zero the union met last
 	}
 	uint8_t * meta = reinterpret_cast<uint8_t *>(words20 + 6);
 	uint8_t * planes = reinterpret_cast<uint8_t *>(words20 + 8);   // lo_x[8] hi_x[8] lo_y[8] hi_y[8] lo_z[8] hi_z[8]
@@ -156,8 +164,12 @@ void write_node(const Box3 & node, const Box3 slot_box[8], const int kind[8], ui
 		for (int a = 0; a < 3; a++) {
 			float low  = std::floor((slot_box[s].lo[a] - node.lo[a]) * inverse_scale[a]);
 			float high = std::ceil ((slot_box[s].hi[a] - node.lo[a]) * inverse_scale[a]);
-			planes[16 * a + s]     = uint8_t(lesser(greater(low,  0.0f), 255.0f));
-			planes[16 * a + 8 + s] = uint8_t(lesser(greater(high, 0.0f), 255.0f));
+			int low_line = int(lesser(greater(low, 0.0f), 255.0f)), high_line = int(lesser(greater(high, 0.0f), 255.0f));
+			// a box between two equal grid lines has no thickness and the strict node test never enters it: it takes the next line
+			// above, or the one below where there is none above
+			if (high_line == low_line) { if (high_line == 255) low_line = 254; else high_line = low_line + 1; }
+			planes[16 * a + s]     = uint8_t(low_line);
+			planes[16 * a + 8 + s] = uint8_t(high_line);
 		}
 		if (kind[s] == 1) { meta[s] = uint8_t(0x20 | (24 + s)); inner_mask |= 1u << s; }
 		else              { meta[s] = uint8_t(0x20 | leaves_so_far); leaves_so_far++; }     // unary count 001, offset from first_leaf
@@ -179,6 +191,7 @@ extern "C" int oracle_tlas_build(const float * transforms /* 12 per instance */,
 		world[size_t(i)] = instance_world_box(transforms + 12 * size_t(i), local_boxes + 6 * size_t(i), local_boxes + 6 * size_t(i) + 3);
 		include(scene, world[size_t(i)]);
 	}
+	const float least_extent = least_grid_extent(scene);
 	std::vector<uint64_t> keys(static_cast<size_t>(n));
 	for (int i = 0; i < n; i++) keys[size_t(i)] = (uint64_t(morton_of(world[size_t(i)], scene)) << 32) | uint64_t(uint32_t(i));
 	std::sort(keys.begin(), keys.end());
@@ -221,7 +234,7 @@ extern "C" int oracle_tlas_build(const float * transforms /* 12 per instance */,
 				slot_box[s] = child_box[c]; child_in_slot[s] = c;
 				kind[s] = cut.boundaries[c + 1] - cut.boundaries[c] > 1 ? 1 : 0;
 			}
-			write_node(node_box, slot_box, kind, uint32_t(cut.first_child), uint32_t(cut.first_leaf), nodes + 20 * size_t(level[k].node));
+			write_node(node_box, slot_box, kind, uint32_t(cut.first_child), uint32_t(cut.first_leaf), least_extent, nodes + 20 * size_t(level[k].node));
 			int inner_seen = 0, leaves_seen = 0;
 			for (int s = 0; s < 8; s++) {   // inner children and leaves are numbered in slot order
 				int c = child_in_slot[s];

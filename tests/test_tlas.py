@@ -6,12 +6,23 @@ one leaf, every child box containing the world boxes of its instances, inner chi
 for what it is for: tracing it (oracle traversal) gives the closest hits of the host-built TLAS, whose builder is
 byte-identical to the reference's (Integrator.cpp:399-430), ray for ray and bit for bit.
 GPU part (tests/test_gpu_tlas.py): the kernel reproduces the restatement's bytes, and frames rendered with it match the
-oracle."""
+oracle.
+
+The cases of tests/tlas_cases.py -- launch-shape boundaries, levels wider than the workgroup, degenerate placement, flat child
+boxes, signed zeros -- go through the restatement here and through the kernel there, and both results through the float64
+rules of tests/tlas_reference.py (structure, containment within a derived slack, thickness, tightness, exponents exactly).
+Measured on the restatement (the kernel's bytes are the same): the largest containment error is 0.46 of the slack (uniform_2049);
+child boxes widened by the thickness rule: points_300 372 of 372, plane_2049 2 619 of 2 619, scales_900 29 of 1 195,
+flat_tiles_200 202 of 264, flat_small_200 183 of 266, flat_planes_8 2 of 8 -- before the rule existed these had q_hi == q_lo and
+failed the thickness check (scales_900: 15, on the finer grids its thin nodes then had)."""
 import os
 import sys
 
 import numpy as np
 import pytest
+
+import tlas_cases
+import tlas_reference
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -140,3 +151,38 @@ def test_restated_device_tlas_is_a_valid_tlas_and_traces_like_the_host_built_one
     assert np.array_equal(hits_host[:, 1:], hits_mine[:, 1:])                                             # triangle, t bits, (u, v)
     assert np.array_equal(host_indices[hits_host[hit, 0].astype(np.int64)], order[hits_mine[hit, 0].astype(np.int64)])   # the same instance
     pt.close(); scene.close()
+
+
+def assert_premise(case, nodes):
+    """What a case is for has to be true of it before anything is concluded from it (or launched): the restatement's nodes of a
+    wide-level case have a level wider than the workgroup of its size, the signed-zero case has bounds of both signs, the
+    bounding-plane case meets grid lines 0 and 255."""
+    n = len(case.mesh)
+    if case.wide is not None:
+        widths = tlas_reference.level_widths(nodes)
+        assert (n <= 1024) == (case.wide == 256) and n <= 4096 and max(widths) > case.wide, (case.name, widths)   # 256 threads up to 1 024 instances, 1 024 beyond
+    if case.name.startswith("signed_zeros"):
+        terms = tlas_reference.corner_terms(case.transforms, case.local_boxes)
+        corners = ((terms[..., 0] + terms[..., 1]) + terms[..., 2]) + terms[..., 3]                 # (n, 8, 3) float32
+        lo = corners[:, 0]
+        for c in range(1, 8):
+            lo = np.where(lo < corners[:, c], lo, corners[:, c])                                       # the build's own `a < b ? a : b`
+        zero = lo[:, 1] == 0
+        assert zero.all() and np.signbit(lo[:, 1]).any() and not np.signbit(lo[:, 1]).all()
+    if case.name.startswith("flat_planes"):
+        q = tlas_reference.decode(nodes)[6][0, 1]                                                     # root, y: (lo, hi) x slot
+        pairs = {(int(a), int(b)) for a, b in zip(q[0], q[1])}
+        assert (0, 1) in pairs and (254, 255) in pairs, pairs
+
+
+@pytest.mark.parametrize("name", tlas_cases.names())
+def test_restatement_keeps_the_float64_rules_on_every_case(oracle, name):
+    case = tlas_cases.by_name(name)
+    nodes, order = oracle.tlas_build(case.transforms.reshape(-1, 12), case.local_boxes)
+    assert_premise(case, nodes)
+    found = tlas_reference.check(nodes, order, case.transforms, case.local_boxes)
+    print("%s: %d nodes, level widths %r, containment %.3f of the slack, %d of %d child boxes widened" % (
+        name, len(nodes), tlas_reference.level_widths(nodes), found.containment_in_slacks, found.widened, found.children))
+    check_tlas(nodes, order, world_boxes_of(case.transforms.reshape(-1, 12), case.local_boxes))    # and what the older check asks
+    if case.aim is not None:
+        assert found.widened > 0                                                                     # a flat case has flat boxes
