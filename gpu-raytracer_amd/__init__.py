@@ -95,6 +95,9 @@ def device_lib():
         lib.rt_shade_rays.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_uint32] + [c_void_p] * 8
         lib.rt_upload_lights.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_float]
         lib.rt_upload_material_normal_maps.argtypes = [c_void_p, c_void_p, c_size_t]
+        lib.rt_upload_delta_lights.argtypes = [c_void_p, c_void_p, c_size_t, c_float]
+        lib.rt_read_delta_lights.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, POINTER(c_size_t), POINTER(c_float)]
+        lib.rt_sample_delta_lights.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
         lib.rt_set_bvh_type.argtypes = [c_void_p, c_int]
         lib.rt_upload_material_opacity.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]
         lib.rt_read_material_opacity.argtypes = [c_void_p, c_int, c_void_p, c_size_t, POINTER(c_int), POINTER(c_int)]
@@ -156,6 +159,12 @@ def host_lib():
         lib.grt_scene_material_opacity_map.argtypes = [c_void_p, c_int, POINTER(c_int), POINTER(c_float)]
         lib.grt_scene_set_material_opacity_map.argtypes = [c_void_p, c_int, c_int, c_int, c_float]
         lib.grt_scene_add_texture.argtypes = [c_void_p, c_char_p, c_int]
+        lib.grt_scene_delta_light_count.argtypes = [c_void_p]
+        lib.grt_scene_get_delta_light.argtypes = [c_void_p, c_int, POINTER(c_float)]
+        lib.grt_scene_add_delta_light.argtypes = [c_void_p, POINTER(c_float)]
+        lib.grt_scene_clear_delta_lights.argtypes = [c_void_p]
+        lib.grt_pathtracer_delta_light_share.restype = c_float
+        lib.grt_pathtracer_delta_light_share.argtypes = [c_void_p]
         lib.grt_scene_texture_compressed.argtypes = [c_void_p, c_int]
         lib.grt_mesh_data_array.restype = c_void_p
         lib.grt_mesh_data_array.argtypes = [c_void_p, c_int, c_char_p, POINTER(c_size_t)]
@@ -560,6 +569,39 @@ class Scene:
         invalidate("materials") and update()."""
         _host_check(host_lib().grt_scene_set_material_normal_map(self.handle, index, int(texture)))
 
+    # Delta emitters (DESIGN.md 7.4): lights without area, found by next-event estimation alone. A Pathtracer sees a change after
+    # invalidate("delta_lights") and update(). Kept out of describe().
+    def _add_delta_light(self, kind, position, direction, intensity, cutoff, beam):
+        v = (c_float * 12)(float(kind), *[float(x) for x in position], *[float(x) for x in direction], *[float(x) for x in intensity], float(cutoff), float(beam))
+        index = host_lib().grt_scene_add_delta_light(self.handle, v)
+        if index < 0:
+            raise ValueError(host_lib().grt_last_error().decode(errors="replace"))
+        return index
+
+    def add_point_light(self, position, intensity):
+        """A point light at `position` with RGB `intensity` in W/sr. Returns its index."""
+        return self._add_delta_light(DELTA_LIGHT_POINT, position, (0, 0, 1), intensity, 0.0, 0.0)
+
+    def add_spot_light(self, position, direction, intensity, cutoff, beam=None):
+        """A spot at `position` shining along `direction`: `intensity` (W/sr) inside the angle `beam` from the axis, none outside `cutoff`
+        (radians; beam defaults to 3/4 of the cutoff), linear in the angle between. Returns its index."""
+        return self._add_delta_light(DELTA_LIGHT_SPOT, position, direction, intensity, cutoff, 0.75 * cutoff if beam is None else beam)
+
+    def add_directional_light(self, direction, irradiance):
+        """A directional light whose light travels along `direction`, with RGB `irradiance` in W/m^2 on a surface facing it. Returns its index."""
+        return self._add_delta_light(DELTA_LIGHT_DIRECTIONAL, (0, 0, 0), direction, irradiance, 0.0, 0.0)
+
+    def clear_delta_lights(self):
+        host_lib().grt_scene_clear_delta_lights(self.handle)
+
+    def delta_lights(self):
+        """(N, 12) float32 {type (0 point, 1 spot, 2 directional), position[3], direction[3], intensity[3], cutoff, beam (radians)}."""
+        lib = host_lib()
+        out = np.zeros((lib.grt_scene_delta_light_count(self.handle), 12), np.float32)
+        for i in range(out.shape[0]):
+            _host_check(lib.grt_scene_get_delta_light(self.handle, i, out[i].ctypes.data_as(POINTER(c_float))))
+        return out
+
     def material_opacity_map(self, index):
         """The opacity mask of material `index`: (texture index, channel 0..3, threshold), or None (kept out of
         describe()). Decodes the scene's textures first: the channel of a loaded `mask` is alpha when its file has four channels."""
@@ -603,6 +645,7 @@ _ARRAY_DTYPES = {
     "scene_order_roots": np.int32, "scene_order_materials": np.int32, "scene_order_transforms": np.float32,
     "scene_order_transforms_inv": np.float32, "scene_order_transforms_prev": np.float32, "scene_order_boxes": np.float32,
     "alias_mesh_ids": np.int32, "alias_triangle_ids": np.int32,
+    "delta_light_records": np.float32,   # rt_delta_light, 16 words each; word 0 is the type (int32 bits)
 }
 
 
@@ -709,6 +752,11 @@ class Pathtracer:
     @property
     def lights_total_weight(self):
         return host_lib().grt_pathtracer_lights_total_weight(self.handle)
+
+    @property
+    def delta_light_share(self):
+        """The share that goes with the staged delta-light records (array("delta_light_records")): cpu_config.delta_light_share, or by power."""
+        return host_lib().grt_pathtracer_delta_light_share(self.handle)
 
     def update(self, delta=0.0):
         _host_check(host_lib().grt_pathtracer_update(self.handle, float(delta)))
@@ -1102,6 +1150,51 @@ def upload_lights(ctx, triangle_indices, triangle_cdf, mesh_cdf, mesh_spans, mes
         raise ValueError("upload_lights: tables of different lengths")
     ptr = lambda a: a.ctypes.data if a.size else None
     return device_lib().rt_upload_lights(ctx, ptr(ti), ptr(tc), ti.size, ptr(mc), ptr(ms), ptr(mt), mc.size, float(total_weight))
+
+
+DELTA_LIGHT_POINT, DELTA_LIGHT_SPOT, DELTA_LIGHT_DIRECTIONAL = 0, 1, 2   # RT_DELTA_LIGHT_*
+DELTA_LIGHT_WORDS = 16    # 32-bit words of an rt_delta_light and of a staged record (RT_DELTA_LIGHT_RECORD)
+DELTA_SAMPLE_OUT = 12     # floats per output record of rt_sample_delta_lights
+MAX_DELTA_LIGHTS = 65536  # RT_MAX_DELTA_LIGHTS
+
+
+def delta_light_records(lights, weights):
+    """(N, 16) float32 rt_delta_light records from (N, 12) lights {type, position[3], direction[3], intensity[3], cutoff, beam} and N weights."""
+    l = _f32(lights).reshape(-1, 12)
+    r = np.zeros((l.shape[0], DELTA_LIGHT_WORDS), np.float32)
+    r.view(np.int32)[:, 0] = l[:, 0].astype(np.int32)
+    r[:, 1:12] = l[:, 1:12]
+    r[:, 12] = _f32(weights).reshape(-1)
+    return r
+
+
+def upload_delta_lights(ctx, records, share=1.0):
+    """rt_upload_delta_lights on (N, 16) float32 rt_delta_light records (delta_light_records); records None or empty clears the table.
+    Returns the status (0: RT_OK); the message of a refusal is rt_last_error's."""
+    if records is None:
+        return device_lib().rt_upload_delta_lights(ctx, None, 0, float(share))
+    r = _f32(records).reshape(-1, DELTA_LIGHT_WORDS)
+    return device_lib().rt_upload_delta_lights(ctx, r.ctypes.data if r.size else None, r.shape[0], float(share))
+
+
+def read_delta_lights(ctx):
+    """rt_read_delta_lights: (records (N, 16) float32 {position[3], type (int32 bits), unit direction[3], P_k, intensity[3], cos cutoff,
+    cos beam, cutoff, 1 / (cutoff - beam), pad}, cdf (N,) float32, share) as staged for the kernels."""
+    lib = device_lib()
+    n, share = c_size_t(), c_float()
+    _dev_check(ctx, lib.rt_read_delta_lights(ctx, None, None, 0, byref(n), byref(share)))
+    records = np.zeros((n.value, DELTA_LIGHT_WORDS), np.float32); cdf = np.zeros(n.value, np.float32)
+    _dev_check(ctx, lib.rt_read_delta_lights(ctx, records.ctypes.data, cdf.ctypes.data, n.value, byref(n), byref(share)))
+    return records, cdf, share.value
+
+
+def sample_delta_lights(ctx, probes):
+    """rt_sample_delta_lights: the shade kernels' delta-light sample on (N, 4) {u in [0, 1), origin[3]}. Returns (N, 12) float32 {light index
+    (int32 bits: .view(np.int32)), to_light[3], max_distance, radiance term[3], P_k, ok, pad[2]}."""
+    p = _f32(probes).reshape(-1, 4)
+    out = np.zeros((p.shape[0], DELTA_SAMPLE_OUT), np.float32)
+    _dev_check(ctx, device_lib().rt_sample_delta_lights(ctx, p.ctypes.data, p.shape[0], out.ctypes.data))
+    return out
 
 
 NORMAL_PROBE_IN = 48   # floats per probe record of rt_perturb_normals

@@ -360,9 +360,11 @@ RT_DEV void stream_stats_flush(const RtParams & p, StreamStatsLDS & lds) {
 
 // MERGED: the launch processes the trace queue of iteration p.stream_iteration, whose entries are at different
 // bounces and belong to different samples (rt_stream_path_info); the launch arguments are ignored.
-// SKY: sky importance sampling is active (RtParams::sky_nee_share > 0): what a BSDF-sampled ray finds of the sky and of the emitters is weighed
-// against the light samples' pdfs, which now include the sky's share.
-template<bool MERGED, bool SKY = false>
+// SKY: how the light samples are split (rt_light_split). 1 (the ..._sky instances): sky importance sampling is active (RtParams::sky_nee_share > 0) --
+// what a BSDF-sampled ray finds of the sky and of the emitters is weighed against the light samples' pdfs, which now include the sky's share.
+// 2 (the ..._split instances): delta lights take a share (RtParams::delta_nee_share > 0), with or without the sky -- the pdfs include what both
+// take (RtParams::nee_taken; a delta light itself is never found by a BSDF-sampled ray).
+template<bool MERGED, int SKY = 0>
 RT_DEV void sort_rays(const RtParams & p, int launch_bounce, int launch_sample_index) {
 	const int q = MERGED ? (p.stream_iteration & 1) : (launch_bounce & 1);
 	const int ray_count = MERGED ? p.stream->trace_count[q] : p.sizes->trace[launch_bounce];
@@ -466,7 +468,7 @@ RT_DEV void sort_rays(const RtParams & p, int launch_bounce, int launch_sample_i
 
 		if (hit.triangle_id == RT_INVALID) { // miss: sky
 			f3 illumination = throughput * sample_sky(p, ray_direction);
-			if (SKY && allow_nee) {   // the light samples reach the sky too: MIS against them, or (MIS off) leave the sky to them
+			if (SKY && allow_nee && (SKY == 1 || p.sky_nee_share > 0.0f)) {   // the light samples reach the sky too: MIS against them, or (MIS off) leave the sky to them (delta lights alone: the sky whole, its tables unread)
 				if (!p.config.enable_multiple_importance_sampling) return -1;
 				illumination *= power_heuristic(in.last_pdf[index], p.sky_nee_share * sky_pdf(p, ray_direction));
 			}
@@ -501,7 +503,7 @@ RT_DEV void sort_rays(const RtParams & p, int launch_bounce, int launch_sample_i
 			f3 emission = mk3(p.materials[2 * material_id]);
 
 			bool count_light = p.config.enable_next_event_estimation ? !allow_nee : true;
-			if (SKY && p.sky_nee_share >= 1.0f) count_light = true;   // every light sample goes to the sky: emitters are found by BSDF sampling alone
+			if (SKY && (SKY == 1 ? p.sky_nee_share : p.nee_taken) >= 1.0f) count_light = true;   // every light sample goes to the sky or a delta light: emitters are found by BSDF sampling alone
 			if (count_light) {
 				add_radiance(p, bounce, pixel_index, throughput * emission, emission);
 				return -1;
@@ -512,7 +514,7 @@ RT_DEV void sort_rays(const RtParams & p, int launch_bounce, int launch_sample_i
 				float brdf_pdf = in.last_pdf[index];
 				float light_power = luminance(emission.x, emission.y, emission.z);
 				float light_pdf = light_power * distance_to_light_squared / (cos_theta_light * p.lights_total_weight);
-				if (SKY) light_pdf *= 1.0f - p.sky_nee_share;
+				if (SKY) light_pdf *= 1.0f - (SKY == 1 ? p.sky_nee_share : p.nee_taken);
 				if (!pdf_is_valid(light_pdf)) return -1;
 				float mis_weight = power_heuristic(brdf_pdf, light_pdf);
 				f3 illumination = throughput * emission * mis_weight;
@@ -548,8 +550,10 @@ RT_DEV void sort_rays(const RtParams & p, int launch_bounce, int launch_sample_i
 
 __global__ void __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES) kernel_sort(RtParams p, int bounce, int sample_index) { sort_rays<false>(p, bounce, sample_index); }
 __global__ void __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES) kernel_sort_stream(RtParams p) { sort_rays<true>(p, 0, 0); }
-__global__ void __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES) kernel_sort_sky(RtParams p, int bounce, int sample_index) { sort_rays<false, true>(p, bounce, sample_index); }
-__global__ void __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES) kernel_sort_stream_sky(RtParams p) { sort_rays<true, true>(p, 0, 0); }
+__global__ void __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES) kernel_sort_sky(RtParams p, int bounce, int sample_index) { sort_rays<false, 1>(p, bounce, sample_index); }
+__global__ void __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES) kernel_sort_stream_sky(RtParams p) { sort_rays<true, 1>(p, 0, 0); }
+__global__ void __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES) kernel_sort_split(RtParams p, int bounce, int sample_index) { sort_rays<false, 2>(p, bounce, sample_index); }
+__global__ void __launch_bounds__(RT_SORT_BLOCK, RT_SORT_WAVES) kernel_sort_stream_split(RtParams p) { sort_rays<true, 2>(p, 0, 0); }
 
 // ---- BSDFs (CUDA/BSDF.h) ----------------------------------------------------------------------------------
 
@@ -958,13 +962,14 @@ RT_DEV LightSample nee_pick_light(const RtParams & p, const LightTablesLDS * lig
 
 // The tail of every light sample: the BSDF towards it, the MIS weight, the shadow ray. `light_pdf` is the sample's pdf in solid angle; an emitter's
 // has to pass pdf_is_valid (the reference's rule), the sky's only has to be positive and finite (the BSDF-miss side weighs every sky direction).
-template<bool EMITTER, typename BSDF>
+// DELTA: a delta light -- `light_pdf` is the probability of having picked it, and no BSDF-sampled ray can find it: the MIS weight is 1.
+template<bool EMITTER, bool DELTA = false, typename BSDF>
 RT_DEV bool nee_finish(const RtParams & p, const BSDF & bsdf, f3 origin, f3 to_light, float max_distance, float cos_theta_hit, f3 radiance, float light_pdf, f3 throughput, ShadowRay & shadow) {
 	f3 bsdf_value; float bsdf_pdf;
 	if (!bsdf.eval(p, to_light, cos_theta_hit, bsdf_value, bsdf_pdf)) return false;
 	if (EMITTER ? !pdf_is_valid(light_pdf) : !(light_pdf > 0.0f && isfinite(light_pdf))) return false;
 
-	float mis_weight = p.config.enable_multiple_importance_sampling ? power_heuristic(light_pdf, bsdf_pdf) : 1.0f;
+	float mis_weight = !DELTA && p.config.enable_multiple_importance_sampling ? power_heuristic(light_pdf, bsdf_pdf) : 1.0f;
 	shadow.illumination = throughput * bsdf_value * radiance * mis_weight / light_pdf;
 	shadow.origin = origin;
 	shadow.direction = to_light;
@@ -1001,17 +1006,69 @@ RT_DEV bool nee_connect_sky(const RtParams & p, const BSDF & bsdf, f3 hit_point,
 	f3 origin = ray_origin_epsilon_offset(hit_point, to_sky, geometric_normal);
 	return nee_finish<false>(p, bsdf, origin, to_sky, RT_INFINITY, dot(to_sky, normal), sample_sky(p, to_sky), p.sky_nee_share * sky_pdf_value, throughput, shadow);
 }
-// SKY: the light sample goes to the sky with probability p.sky_nee_share (DIM_NEE_LIGHT.x below it; its direction from the DIM_NEE_TRIANGLE
+// ---- delta emitters ----
+RT_DEV int nee_pick_delta(const RtParams & p, float u) { return binary_search(p.delta_light_cdf, 0, p.delta_light_count - 1, u); }
+// Where the light lies as seen from `point` (not normalised): what the hit's epsilon offset is decided by.
+RT_DEV f3 delta_light_toward(const RtDeltaLight & light, f3 point) {
+	return __float_as_int(light.position_type.w) == RT_DELTA_LIGHT_DIRECTIONAL ? -mk3(light.direction_pdf) : mk3(light.position_type) - point;
+}
+// The sample a delta light offers `origin`: unit direction, the shadow ray's length, and the radiance term (intensity x falloff / d^2, or the
+// irradiance). False -- drop the sample -- when the distance is 0 or not finite, the falloff is 0 or the term is not finite.
+struct DeltaSample { f3 to_light; float max_distance; f3 radiance; };
+RT_DEV bool delta_light_sample(const RtDeltaLight & light, f3 origin, DeltaSample & sample) {
+	const int type = __float_as_int(light.position_type.w);
+	f3 intensity = mk3(light.intensity_cos_cutoff);
+	if (type == RT_DELTA_LIGHT_DIRECTIONAL) {
+		sample.to_light = -mk3(light.direction_pdf);
+		sample.max_distance = RT_INFINITY;
+		sample.radiance = intensity;
+	} else {
+		f3 to_light = mk3(light.position_type) - origin;
+		float d = length(to_light);
+		if (!(d > 0.0f && isfinite(d))) return false;
+		to_light /= d;
+		float falloff = 1.0f;
+		if (type == RT_DELTA_LIGHT_SPOT) {   // Mitsuba's: full inside the beam, none outside the cutoff, linear in the ANGLE between
+			float c = dot(-to_light, mk3(light.direction_pdf));
+			if (c <= light.intensity_cos_cutoff.w && light.intensity_cos_cutoff.w > -1.0f) return false;   // (a cutoff of pi, cosine -1, excludes no direction: not the back axis either)
+			if (c < light.spot.x) falloff = (light.spot.y - acosf(c)) * light.spot.z;
+			if (!(falloff > 0.0f)) return false;
+		}
+		sample.to_light = to_light;
+		sample.max_distance = d;
+		sample.radiance = intensity * falloff / square(d);
+	}
+	return isfinite(sample.radiance.x) && isfinite(sample.radiance.y) && isfinite(sample.radiance.z);
+}
+// A delta light as the light sample: the light from the table's CDF, a shadow ray to it (to infinity for a directional light) from the hit,
+// offset on the hit's side only -- the light has no surface. pdf: the probability of this light, the delta lights' share times the record's P_k.
+template<typename BSDF>
+RT_DEV bool nee_connect_delta(const RtParams & p, const BSDF & bsdf, f3 hit_point, f3 normal, f3 geometric_normal, f3 throughput, float u, ShadowRay & shadow) {
+	const RtDeltaLight light = p.delta_lights[nee_pick_delta(p, u)];
+	f3 origin = ray_origin_epsilon_offset(hit_point, delta_light_toward(light, hit_point), geometric_normal);
+	DeltaSample sample;
+	if (!delta_light_sample(light, origin, sample)) return false;
+	return nee_finish<false, true>(p, bsdf, origin, sample.to_light, sample.max_distance, dot(sample.to_light, normal), sample.radiance, p.delta_nee_share * light.direction_pdf.w, throughput, shadow);
+}
+// SKY 1: the light sample goes to the sky with probability p.sky_nee_share (DIM_NEE_LIGHT.x below it; its direction from the DIM_NEE_TRIANGLE
 // pair), else to the emitters, with DIM_NEE_LIGHT.x rescaled to [0, 1) -- the same random dimensions either way.
-template<bool SKY, typename BSDF>
+// SKY 2: ... and to a delta light with probability p.delta_nee_share (DIM_NEE_LIGHT.x below p.nee_taken, rescaled to [0, 1) for the table's search).
+template<int SKY, typename BSDF>
 RT_DEV bool next_event_estimation(const RtParams & p, const LightTablesLDS * light_lds, int pixel_index, int bounce, int sample_index, const BSDF & bsdf, f3 hit_point, f3 normal, f3 geometric_normal, f3 throughput, ShadowRay & shadow) {
 	f2 rand_light    = random_sample(p, bsdf.rng, DIM_NEE_LIGHT,    unsigned(bounce));
 	f2 rand_triangle = random_sample(p, bsdf.rng, DIM_NEE_TRIANGLE, unsigned(bounce));
 	if (!SKY) return nee_connect<false>(p, nee_pick_light(p, light_lds, rand_light, rand_triangle), bsdf, hit_point, normal, geometric_normal, throughput, 1.0f, shadow);
-	const float share = p.sky_nee_share;   // (0, 1]: the _sky kernels run only while sampling is active
+	if (SKY == 1) {
+		const float share = p.sky_nee_share;   // (0, 1]: the _sky kernels run only while sampling is active
+		if (rand_light.x < share) return nee_connect_sky(p, bsdf, hit_point, normal, geometric_normal, throughput, rand_triangle, shadow);
+		rand_light.x = fminf((rand_light.x - share) / (1.0f - share), 0x1.fffffep-1f);   // (share < 1 here)
+		return nee_connect<true>(p, nee_pick_light(p, light_lds, rand_light, rand_triangle), bsdf, hit_point, normal, geometric_normal, throughput, 1.0f - share, shadow);
+	}
+	const float share = p.sky_nee_share, taken = p.nee_taken;   // taken in (0, 1]: the _split kernels run only while the delta lights take a share
 	if (rand_light.x < share) return nee_connect_sky(p, bsdf, hit_point, normal, geometric_normal, throughput, rand_triangle, shadow);
-	rand_light.x = fminf((rand_light.x - share) / (1.0f - share), 0x1.fffffep-1f);   // (share < 1 here)
-	return nee_connect<true>(p, nee_pick_light(p, light_lds, rand_light, rand_triangle), bsdf, hit_point, normal, geometric_normal, throughput, 1.0f - share, shadow);
+	if (rand_light.x < taken) return nee_connect_delta(p, bsdf, hit_point, normal, geometric_normal, throughput, fminf((rand_light.x - share) / p.delta_nee_share, 0x1.fffffep-1f), shadow);
+	rand_light.x = fminf((rand_light.x - taken) / (1.0f - taken), 0x1.fffffep-1f);   // (taken < 1 here)
+	return nee_connect<true>(p, nee_pick_light(p, light_lds, rand_light, rand_triangle), bsdf, hit_point, normal, geometric_normal, throughput, 1.0f - taken, shadow);
 }
 
 // rt_sample_lights: nee_pick_light on explicit random numbers, with the tables chosen as shade_material chooses them (use_lds: the
@@ -1039,6 +1096,27 @@ __global__ void kernel_sample_lights(RtParams p, const float * probes, int count
 	o[7] = light.geometric_normal.x; o[8] = light.geometric_normal.y; o[9] = light.geometric_normal.z;
 	o[10] = light.emission.x; o[11] = light.emission.y; o[12] = light.emission.z;
 	o[13] = o[14] = o[15] = 0.0f;
+}
+
+// rt_sample_delta_lights: nee_pick_delta and delta_light_sample on explicit probes. Record in: {u, origin[3]}; out: RT_DELTA_SAMPLE_OUT floats
+// {light index (int32 bits), to_light[3], max_distance, radiance term[3], P_k, ok, pad[2]}; a dropped sample reports zeros for direction, distance and term.
+__global__ void kernel_sample_delta_lights(RtParams p, const float * probes, int count, float * out) {
+	int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= count) return;
+	const float * a = probes + size_t(i) * 4;
+	float * o = out + size_t(i) * RT_DELTA_SAMPLE_OUT;
+	const int index = nee_pick_delta(p, a[0]);
+	const RtDeltaLight light = p.delta_lights[index];
+	DeltaSample sample;
+	bool ok = delta_light_sample(light, mk3(a[1], a[2], a[3]), sample) && light.direction_pdf.w > 0.0f;
+	if (!ok) { sample.to_light = mk3(0.0f); sample.max_distance = 0.0f; sample.radiance = mk3(0.0f); }
+	o[0] = __int_as_float(index);
+	o[1] = sample.to_light.x; o[2] = sample.to_light.y; o[3] = sample.to_light.z;
+	o[4] = sample.max_distance;
+	o[5] = sample.radiance.x; o[6] = sample.radiance.y; o[7] = sample.radiance.z;
+	o[8] = light.direction_pdf.w;
+	o[9] = ok ? 1.0f : 0.0f;
+	o[10] = o[11] = 0.0f;
 }
 
 // ---- shade_material<BSDF> (Pathtracer.cu:557-757) -------------------------------------------------------------
@@ -1071,10 +1149,10 @@ RT_DEV float ray_cone_get_lod(f3 ray_direction, f3 geometric_normal, float cone_
 
 // MERGED: the queue holds the surface hits of every submission in flight (see sort_rays); bounce and sample come
 // from the slot table, the launch arguments are ignored.
-// SKY: sky importance sampling is active (RtParams::sky_nee_share > 0): light samples go to the sky or the emitters, see next_event_estimation.
+// SKY: how the light samples are split (rt_light_split): 1 between the sky and the emitters, 2 with the delta lights as well, see next_event_estimation.
 // NMAP: some material of this slot has a normal map (RtParams::normal_map_slots): a hit whose material has one shades with the mapped
 // normal (normal_map_perturb); a hit whose material has none runs the arithmetic of the plain instance.
-template<typename BSDF, int SLOT, bool MERGED, bool SKY = false, bool NMAP = false>
+template<typename BSDF, int SLOT, bool MERGED, int SKY = 0, bool NMAP = false>
 RT_DEV void shade_material(const RtParams & p, int launch_bounce, int launch_sample_index) {
 	const RtMaterialBuffer & q = p.material[SLOT];
 	const int iq = MERGED ? (p.stream_iteration & 1) : (launch_bounce & 1);
@@ -1281,11 +1359,12 @@ RT_DEV void shade_material(const RtParams & p, int launch_bounce, int launch_sam
 	if (MERGED) stream_stats_flush(p, stats_lds);
 }
 
-// ---- the material kernels: one list, expanded for the four (SKY, NMAP) combinations ----------------------------------
+// ---- the material kernels: one list, expanded for the six (SKY, NMAP) combinations ----------------------------------
 // A row: X(material, _texels or nothing, BSDF type, slot, waves per SIMD of the merged instance, ...). Each row yields, per combination,
 // the per-bounce kernel_material_<material><_texels><suffix> and the merged kernel_material_<material>_stream<_texels><suffix>.
 //   ..._texels: no texture on the device holds compressed blocks (RtParams::textures_compressed == 0)
-//   ..._sky:    sky importance sampling is active (RtParams::sky_nee_share > 0), launched only while it is
+//   ..._sky:    sky importance sampling is active (RtParams::sky_nee_share > 0) and no delta light takes a share, launched only then
+//   ..._split:  delta lights take a share of the light samples (RtParams::delta_nee_share > 0), with or without the sky, launched only then
 //   ..._nmap:   some material of the slot has a normal map (RtParams::normal_map_slots), launched only then
 // The rows' order is material_kernels_for's index: the four slots, then the _texels forms of slots 0 and 1.
 #ifndef RT_SHADE_WAVES_DIFFUSE
@@ -1298,7 +1377,8 @@ RT_DEV void shade_material(const RtParams & p, int launch_bounce, int launch_sam
 	X(conductor,  ,        BSDFConductor,       3, RT_SHADE_WAVES,         __VA_ARGS__) \
 	X(diffuse,    _texels, BSDFDiffuseT<false>, 0, RT_SHADE_WAVES_DIFFUSE, __VA_ARGS__) \
 	X(plastic,    _texels, BSDFPlasticT<false>, 1, RT_SHADE_WAVES,         __VA_ARGS__)
-#define RT_MATERIAL_KERNEL_VARIANTS(X) RT_MATERIAL_KERNEL_LIST(X, , false, false) RT_MATERIAL_KERNEL_LIST(X, _sky, true, false) RT_MATERIAL_KERNEL_LIST(X, _nmap, false, true) RT_MATERIAL_KERNEL_LIST(X, _sky_nmap, true, true)
+#define RT_MATERIAL_KERNEL_VARIANTS(X) RT_MATERIAL_KERNEL_LIST(X, , 0, false) RT_MATERIAL_KERNEL_LIST(X, _sky, 1, false) RT_MATERIAL_KERNEL_LIST(X, _split, 2, false) \
+	RT_MATERIAL_KERNEL_LIST(X, _nmap, 0, true) RT_MATERIAL_KERNEL_LIST(X, _sky_nmap, 1, true) RT_MATERIAL_KERNEL_LIST(X, _split_nmap, 2, true)
 
 #define RT_DEFINE_MATERIAL_KERNELS(MATERIAL, TEXELS, BSDF, SLOT, STREAM_WAVES, SUFFIX, SKY, NMAP) \
 __global__ void __launch_bounds__(RT_SHADE_BLOCK, RT_SHADE_WAVES) kernel_material_##MATERIAL##TEXELS##SUFFIX(RtParams p, int bounce, int sample_index) { shade_material<BSDF, SLOT, false, SKY, NMAP>(p, bounce, sample_index); } \
@@ -1407,21 +1487,22 @@ static int streaming_grid(int work_items) {
 void rt_launch_generate(const RtParams & p, int sample_index, int pixel_offset, int pixel_count, hipStream_t stream) {
 	hipLaunchKernelGGL(kernel_generate, dim3(streaming_grid(pixel_count)), dim3(RT_SHADE_BLOCK), 0, stream, p, sample_index, pixel_offset, pixel_count);
 }
-// (the ..._sky instance while sky importance sampling is active, as for the material kernels)
+// (the ..._sky instance while sky importance sampling is active, the ..._split one while delta lights take a share, as for the material kernels)
 void rt_launch_sort(const RtParams & p, int bounce, int sample_index, hipStream_t stream) {
-	hipLaunchKernelGGL(p.sky_nee_share > 0.0f ? kernel_sort_sky : kernel_sort, dim3(2048 * RT_SHADE_BLOCK / RT_SORT_BLOCK), dim3(RT_SORT_BLOCK), 0, stream, p, bounce, sample_index);
+	const int split = rt_light_split(p);
+	hipLaunchKernelGGL(split == 2 ? kernel_sort_split : split == 1 ? kernel_sort_sky : kernel_sort, dim3(2048 * RT_SHADE_BLOCK / RT_SORT_BLOCK), dim3(RT_SORT_BLOCK), 0, stream, p, bounce, sample_index);
 }
-// The entry points of every row, from the same list: [(NMAP * 2 + SKY) * material_rows + row]
+// The entry points of every row, from the same list: [(NMAP * 3 + SKY) * material_rows + row]
 struct MaterialKernels { void (*bounce)(RtParams, int, int); void (*merged)(RtParams); };
 #define RT_MATERIAL_KERNEL_ENTRY(MATERIAL, TEXELS, BSDF, SLOT, STREAM_WAVES, SUFFIX, SKY, NMAP) { kernel_material_##MATERIAL##TEXELS##SUFFIX, kernel_material_##MATERIAL##_stream##TEXELS##SUFFIX },
 static const MaterialKernels material_kernels[] = { RT_MATERIAL_KERNEL_VARIANTS(RT_MATERIAL_KERNEL_ENTRY) };
-constexpr int material_rows = sizeof(material_kernels) / sizeof(material_kernels[0]) / 4;
+constexpr int material_rows = sizeof(material_kernels) / sizeof(material_kernels[0]) / 6;
 #undef RT_MATERIAL_KERNEL_ENTRY
 #undef RT_MATERIAL_KERNEL_VARIANTS
 #undef RT_MATERIAL_KERNEL_LIST
 // What the material launchers launch for a slot (0 .. 3)
 static const MaterialKernels & material_kernels_for(const RtParams & p, int material_slot) {
-	const int variant = (p.normal_map_slots >> material_slot & 1) * 2 + (p.sky_nee_share > 0.0f ? 1 : 0);
+	const int variant = (p.normal_map_slots >> material_slot & 1) * 3 + rt_light_split(p);
 	const int row = material_slot < 2 && !p.textures_compressed ? 4 + material_slot : material_slot;
 	return material_kernels[variant * material_rows + row];
 }
@@ -1442,7 +1523,8 @@ void rt_launch_stream_advance(RtStreamControl * control, int iteration, int gene
 #define RT_STREAM_SORT_GRID 2048    // ... and of its sort launch (in units of RT_SHADE_BLOCK threads)
 #endif
 void rt_launch_sort_stream(const RtParams & p, hipStream_t stream) {
-	hipLaunchKernelGGL(p.sky_nee_share > 0.0f ? kernel_sort_stream_sky : kernel_sort_stream, dim3(RT_STREAM_SORT_GRID * RT_SHADE_BLOCK / RT_SORT_BLOCK), dim3(RT_SORT_BLOCK), 0, stream, p);
+	const int split = rt_light_split(p);
+	hipLaunchKernelGGL(split == 2 ? kernel_sort_stream_split : split == 1 ? kernel_sort_stream_sky : kernel_sort_stream, dim3(RT_STREAM_SORT_GRID * RT_SHADE_BLOCK / RT_SORT_BLOCK), dim3(RT_SORT_BLOCK), 0, stream, p);
 }
 void rt_launch_material_stream(const RtParams & p, int material_slot, hipStream_t stream) {
 	hipLaunchKernelGGL(material_kernels_for(p, material_slot).merged, dim3(RT_STREAM_SHADE_GRID), dim3(RT_SHADE_BLOCK), 0, stream, p);
@@ -1478,6 +1560,9 @@ static void launch_bsdf_probe(const RtParams & p, int material_type, const float
 }
 void rt_launch_sample_lights(const RtParams & p, const float * probes, int count, bool use_lds, float * out, hipStream_t stream) {
 	hipLaunchKernelGGL(kernel_sample_lights, dim3((count + RT_SHADE_BLOCK - 1) / RT_SHADE_BLOCK), dim3(RT_SHADE_BLOCK), 0, stream, p, probes, count, use_lds ? 1 : 0, out);
+}
+void rt_launch_sample_delta_lights(const RtParams & p, const float * probes, int count, float * out, hipStream_t stream) {
+	hipLaunchKernelGGL(kernel_sample_delta_lights, dim3((count + 255) / 256), dim3(256), 0, stream, p, probes, count, out);
 }
 void rt_launch_bsdf_probe(const RtParams & p, int material_type, bool eval,const float * probes, int count, float * out, hipStream_t stream) {
 	if (eval) launch_bsdf_probe<true>(p, material_type, probes, count, out, stream);

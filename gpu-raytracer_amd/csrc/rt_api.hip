@@ -1074,6 +1074,92 @@ int rt_upload_lights(rt_context * ctx,
 	return RT_OK;
 }
 
+// Delta emitters. Everything is checked before anything is staged: a refused table leaves the one before in force. The staged record
+// carries what the kernels would otherwise compute per sample (the cosines, 1 / (cutoff - beam)) and the light's own selection probability, from the
+// weights in double; the CDF is inclusive and normalised and ends in exactly 1 from the last light of positive weight on, so that binary_search ends
+// for every number below 1 and never selects a light of zero weight that follows a positive one.
+int rt_upload_delta_lights(rt_context * ctx, const rt_delta_light * records, size_t count, float share) {
+	RT_REQUIRE(ctx, ctx, "rt_upload_delta_lights: NULL context");
+	(void)hipSetDevice(ctx->device);
+	if (!records || count == 0) {   // clear
+		if (!ctx->delta_lights) return RT_OK;
+		RT_HIP(ctx, quiesce(ctx));
+		device_free(ctx, ctx->delta_lights); ctx->delta_lights = nullptr;
+		ctx->delta_light_records.clear(); ctx->delta_light_cdf.clear(); ctx->delta_light_share = 0.0f;
+		ctx->params.delta_lights = nullptr; ctx->params.delta_light_cdf = nullptr; ctx->params.delta_light_count = 0;
+		ctx->params.delta_nee_share = 0.0f; ctx->params.nee_taken = ctx->params.sky_nee_share;   // (nothing is in flight; the next render settles the sky's share again)
+		return RT_OK;
+	}
+	if (count > size_t(RT_MAX_DELTA_LIGHTS)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_delta_lights: %zu lights, more than RT_MAX_DELTA_LIGHTS (%d)", count, RT_MAX_DELTA_LIGHTS);
+	if (!(share > 0.0f && share <= 1.0f)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_delta_lights: share is %.9g, outside (0, 1]", double(share));
+	const float pi = 3.14159265358979323846f;
+	double total = 0.0;
+	for (size_t i = 0; i < count; i++) {
+		const rt_delta_light & l = records[i];
+		if (l.type != RT_DELTA_LIGHT_POINT && l.type != RT_DELTA_LIGHT_SPOT && l.type != RT_DELTA_LIGHT_DIRECTIONAL)
+			return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_delta_lights: light %zu: unknown type %d", i, l.type);
+		for (int k = 0; k < 3; k++) {
+			if (l.type != RT_DELTA_LIGHT_DIRECTIONAL && !std::isfinite(l.position[k])) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_delta_lights: light %zu: position is not finite", i);
+			if (!(std::isfinite(l.intensity[k]) && l.intensity[k] >= 0.0f)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_delta_lights: light %zu: intensity %d is %.9g (it must be finite and not negative)", i, k, double(l.intensity[k]));
+		}
+		if (l.type != RT_DELTA_LIGHT_POINT) {
+			double n = double(l.direction[0]) * l.direction[0] + double(l.direction[1]) * l.direction[1] + double(l.direction[2]) * l.direction[2];
+			if (!(std::isfinite(n) && n > 0.0)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_delta_lights: light %zu: direction is zero or not finite", i);
+		}
+		if (l.type == RT_DELTA_LIGHT_SPOT && !(l.beam > 0.0f && l.beam <= l.cutoff && l.cutoff <= pi))
+			return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_delta_lights: light %zu: beam %.9g and cutoff %.9g do not satisfy 0 < beam <= cutoff <= pi", i, double(l.beam), double(l.cutoff));
+		if (!(std::isfinite(l.weight) && l.weight >= 0.0f)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_delta_lights: light %zu: weight is %.9g (it must be finite and not negative)", i, double(l.weight));
+		total += double(l.weight);
+	}
+	if (!(std::isfinite(total) && total > 0.0)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_delta_lights: the total weight is %.9g (it must be finite and positive)", total);
+
+	std::vector<float> staged(count * RT_DELTA_LIGHT_RECORD, 0.0f), cdf(count);
+	size_t last_positive = 0;
+	for (size_t i = 0; i < count; i++) if (records[i].weight > 0.0f) last_positive = i;
+	double running = 0.0;
+	for (size_t i = 0; i < count; i++) {
+		const rt_delta_light & l = records[i];
+		float * r = &staged[i * RT_DELTA_LIGHT_RECORD];
+		const bool has_position = l.type != RT_DELTA_LIGHT_DIRECTIONAL, has_direction = l.type != RT_DELTA_LIGHT_POINT;
+		for (int k = 0; k < 3; k++) r[k] = has_position ? l.position[k] : 0.0f;
+		memcpy(&r[3], &l.type, 4);
+		if (has_direction) {
+			double n = sqrt(double(l.direction[0]) * l.direction[0] + double(l.direction[1]) * l.direction[1] + double(l.direction[2]) * l.direction[2]);
+			for (int k = 0; k < 3; k++) r[4 + k] = float(double(l.direction[k]) / n);
+		} else r[6] = 1.0f;
+		r[7] = float(double(l.weight) / total);
+		for (int k = 0; k < 3; k++) r[8 + k] = l.intensity[k];
+		const bool spot = l.type == RT_DELTA_LIGHT_SPOT;
+		r[11] = spot ? float(cos(double(l.cutoff))) : -1.0f;   // (in double, rounded once: the float64 restatement's own constants)
+		r[12] = spot ? float(cos(double(l.beam))) : -1.0f;
+		r[13] = spot ? l.cutoff : pi;
+		r[14] = spot && l.cutoff > l.beam ? 1.0f / (l.cutoff - l.beam) : 0.0f;
+		running += double(l.weight);
+		cdf[i] = i >= last_positive ? 1.0f : float(running / total);
+	}
+	const size_t record_bytes = staged.size() * sizeof(float);
+	std::vector<char> image(record_bytes + count * sizeof(float));
+	memcpy(image.data(), staged.data(), record_bytes);
+	memcpy(image.data() + record_bytes, cdf.data(), count * sizeof(float));
+	int s = upload(ctx, &ctx->delta_lights, image.data(), image.size()); if (s) return s;   // (drains the context)
+	ctx->params.delta_lights = (const RtDeltaLight *)ctx->delta_lights;
+	ctx->params.delta_light_cdf = (const float *)((const char *)ctx->delta_lights + record_bytes);
+	ctx->params.delta_light_count = int(count);
+	ctx->delta_light_records.swap(staged); ctx->delta_light_cdf.swap(cdf); ctx->delta_light_share = share;
+	return RT_OK;
+}
+
+int rt_read_delta_lights(rt_context * ctx, float * records, float * cdf, size_t capacity, size_t * out_count, float * out_share) {
+	RT_REQUIRE(ctx, ctx, "rt_read_delta_lights: NULL context");
+	const size_t count = ctx->delta_light_cdf.size();
+	if (out_count) *out_count = count;
+	if (out_share) *out_share = ctx->delta_light_share;
+	if ((records || cdf) && capacity < count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_read_delta_lights: room for %zu lights, the table holds %zu", capacity, count);
+	if (records && count) memcpy(records, ctx->delta_light_records.data(), count * RT_DELTA_LIGHT_RECORD * sizeof(float));
+	if (cdf && count) memcpy(cdf, ctx->delta_light_cdf.data(), count * sizeof(float));
+	return RT_OK;
+}
+
 int rt_upload_rng(rt_context * ctx, const float * pmj_samples, const uint8_t * blue_noise) {
 	RT_REQUIRE(ctx, ctx && pmj_samples && blue_noise, "rt_upload_rng: NULL argument");
 	(void)hipSetDevice(ctx->device);
@@ -1121,18 +1207,30 @@ int sky_tables_build(rt_context * ctx, const char * caller) {
 	return RT_OK;
 }
 
-// Before a render: the sky's share of the light samples for this render (RtParams::sky_nee_share), building the tables if sampling is wanted.
-// 0 -- sampling off, NEE off, or a sky without weight -- keeps every kernel on the reference's estimator.
+// Before a render: how this render splits its light samples. The sky's share (RtParams::sky_nee_share), building the tables if sampling is wanted:
+// 0 -- sampling off, NEE off, or a sky without weight; all of them only when there is nothing else to sample, neither triangle emitters nor delta
+// lights. The delta lights' share (RtParams::delta_nee_share): 0 without a table or with NEE off; the upload's share of what the sky
+// leaves while triangle emitters exist; all the sky leaves without them. Both 0 keeps every kernel on the reference's estimator.
 int sky_sampling_prepare(rt_context * ctx, const char * caller) {
 	RtParams & p = ctx->params;
+	const bool emitters = p.lights_total_weight > 0.0f;
+	const bool delta = p.delta_light_count > 0 && p.config.enable_next_event_estimation;
 	float share = 0.0f;
 	if (ctx->sky_sampling > 0.0f && p.config.enable_next_event_estimation) {
 		int s = sky_tables_build(ctx, caller); if (s) return s;
-		if (ctx->sky_total > 0.0 && p.sky_scale != 0.0f) share = p.lights_total_weight > 0.0f ? ctx->sky_sampling : 1.0f;
+		if (ctx->sky_total > 0.0 && p.sky_scale != 0.0f) share = emitters || delta ? ctx->sky_sampling : 1.0f;
 	}
-	if (share != p.sky_nee_share) {
+	float delta_share = 0.0f, taken = share;
+	if (delta) {
+		delta_share = emitters ? (1.0f - share) * ctx->delta_light_share : 1.0f - share;
+		taken = emitters ? fminf(share + delta_share, 1.0f) : 1.0f;
+		// A share of 1 (or next to it) leaves the emitters nothing: s + (1 - s) may round to the float below 1, and a light sample that reached the emitters
+		// with probability 6e-8 would carry a weight of 1.7e7. Then taken IS 1: the emitters are found by BSDF sampling alone (sort_rays: count_light).
+		if (ctx->delta_light_share >= 1.0f || taken >= 0x1.fffffep-1f) { taken = 1.0f; delta_share = 1.0f - share; }
+	}
+	if (share != p.sky_nee_share || delta_share != p.delta_nee_share || taken != p.nee_taken) {
 		RT_HIP(ctx, quiesce(ctx));   // (paths in flight were shaded under the other estimator)
-		p.sky_nee_share = share;
+		p.sky_nee_share = share; p.delta_nee_share = delta_share; p.nee_taken = taken;
 	}
 	return RT_OK;
 }
@@ -2060,7 +2158,7 @@ int rt_render_samples(rt_context * ctx, int sample_index, int sample_count) {
 		for (int i = 0; i < 3; i++) if (from[i] && to[i] && from[i] != to[i]) RT_HIP(ctx, hipMemcpyAsync(to[i], from[i], ctx->frame_pixels * gbuffer_pixel_bytes[i], hipMemcpyDeviceToDevice, st));
 	}
 
-	bool trace_shadows = p.config.enable_next_event_estimation && ((ctx->has_lights && p.lights_total_weight > 0.0f) || p.sky_nee_share > 0.0f);   // (sky importance sampling: shadow rays without emitters)
+	bool trace_shadows = p.config.enable_next_event_estimation && ((ctx->has_lights && p.lights_total_weight > 0.0f) || rt_light_samples_split(p));   // (sky importance sampling, delta lights: shadow rays without emitters)
 	// Shadow rays of bounce b only feed the frame buffers, so they run on the side stream while the
 	// main chain traces bounce b+1; they are joined before the next kernel that touches the frame
 	// buffers (sort: sky / emissive hits), which keeps the order of the float additions per pixel.

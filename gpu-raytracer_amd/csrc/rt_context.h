@@ -185,6 +185,11 @@ struct rt_context {
 	void * sky_table_sums = nullptr;         // doubles: row totals [H], total [1]
 	bool sky_tables_ready = false;
 	double sky_total = 0.0;                  // the sum of the cell weights (0: a black sky, sampling stays inactive; not finite: an error)
+	// delta emitters (rt_upload_delta_lights): one device allocation (the records, then their CDF) and the host's copy of both
+	// (rt_read_delta_lights); the share of the upload. What a render makes of it (RtParams::delta_nee_share) is settled by sky_sampling_prepare.
+	void * delta_lights = nullptr;
+	std::vector<float> delta_light_records, delta_light_cdf;
+	float delta_light_share = 0.0f;
 	void * luts[6] = { }; bool luts_ready = false;
 	int bvh_width = 8;
 

@@ -3,6 +3,7 @@
 #include "rt_context.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <memory>
 
@@ -353,6 +354,27 @@ int rt_sample_lights(rt_context * ctx, const float * probes, size_t count, int u
 	if ((s = probe.allocated())) return s;
 	rt_launch_sample_lights(p, dev_probes, int(count), use_lds != 0, dev_out, ctx->stream);
 	return probe.finish_and_read(out, dev_out, count * RT_LIGHT_SAMPLE_OUT * 4);
+}
+
+int rt_sample_delta_lights(rt_context * ctx, const float * probes, size_t count, float * out) {
+	RT_REQUIRE(ctx, ctx && probes && out, "rt_sample_delta_lights: NULL argument");
+	RT_REQUIRE(ctx, count <= size_t(1) << 24, "rt_sample_delta_lights: more than 2^24 probes");
+	const RtParams & p = ctx->params;
+	if (p.delta_light_count <= 0 || !p.delta_lights || !p.delta_light_cdf)
+		return fail(ctx, RT_ERROR_NOT_READY, "rt_sample_delta_lights: no delta lights uploaded (rt_upload_delta_lights)");
+	for (size_t i = 0; i < count; i++) {   // (the search ends only for numbers up to the table's last entry, 1)
+		const float * a = probes + i * 4;
+		if (!(a[0] >= 0.0f && a[0] < 1.0f)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sample_delta_lights: probe %zu: random number is %.9g, outside [0, 1)", i, double(a[0]));
+		if (!(std::isfinite(a[1]) && std::isfinite(a[2]) && std::isfinite(a[3]))) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sample_delta_lights: probe %zu: origin is not finite", i);
+	}
+	(void)hipSetDevice(ctx->device);
+	if (count == 0) return RT_OK;
+	Probe probe(ctx, "rt_sample_delta_lights");
+	float * dev_probes = probe.array<float>(count * 4, probes);
+	float * dev_out = probe.array<float>(count * RT_DELTA_SAMPLE_OUT);
+	int s = probe.allocated(); if (s) return s;
+	rt_launch_sample_delta_lights(p, dev_probes, int(count), dev_out, ctx->stream);
+	return probe.finish_and_read(out, dev_out, count * RT_DELTA_SAMPLE_OUT * 4);
 }
 
 int rt_perturb_normals(rt_context * ctx, int texture_index, const float * probes, size_t count, float * out) {

@@ -109,6 +109,14 @@ struct RtAOV { float4 * framebuffer, * accumulator; };
 // in word (y * width + x) >> 5, no row padding; 1: opaque. Built once on the device; the traversal kernels read nothing else of the texture.
 struct RtOpacityMask { const unsigned * bits; int width, height; };
 
+// One delta emitter as staged by rt_upload_delta_lights (RT_DELTA_LIGHT_RECORD floats, read back by rt_read_delta_lights).
+struct RtDeltaLight {
+	float4 position_type;        // position, type (int bits: RT_DELTA_LIGHT_*)
+	float4 direction_pdf;        // unit direction (spot: axis; directional: the way the light travels), P_k: the light's selection probability
+	float4 intensity_cos_cutoff; // intensity (W/sr; directional: irradiance), cos(cutoff)
+	float4 spot;                 // cos(beam), cutoff (radians), 1 / (cutoff - beam), pad
+};
+
 // Everything a kernel needs, passed BY VALUE as kernel argument (lives in the kernarg
 // segment and is read with scalar loads; no __constant__ symbols, so several contexts
 // can coexist in one process).
@@ -220,7 +228,18 @@ struct RtParams {
 	const int * material_opacity;
 	const RtOpacityMask * opacity_masks;
 	int opacity_active;
+	// Delta emitters (rt_upload_delta_lights): the records and their inclusive, normalised CDF (last entry 1). delta_nee_share (q) is the
+	// probability that a light sample goes to a delta light, settled per render beside sky_nee_share (s); nee_taken = s + q is what the sky and the delta
+	// lights take together (with q == 0 it is s to the bit). While q is 0 the tables may be null; only the ..._split kernel instances read these.
+	const RtDeltaLight * delta_lights;
+	const float * delta_light_cdf;
+	int   delta_light_count;
+	float delta_nee_share, nee_taken;
 };
+// Which instances of the sort and material kernels a launcher takes: 0 the plain ones, 1 the ..._sky ones (sky importance sampling alone), 2 the ..._split
+// ones (delta lights take a share, with or without the sky). Shadow rays are traced without triangle emitters whenever it is not 0.
+static inline __host__ __device__ int rt_light_split(const RtParams & p) { return p.delta_nee_share > 0.0f ? 2 : p.sky_nee_share > 0.0f ? 1 : 0; }
+static inline __host__ __device__ bool rt_light_samples_split(const RtParams & p) { return rt_light_split(p) != 0; }
 // "Skip behind the hit" (kernels_trace.hip): closest-hit rays drop stacked groups of children that lie behind the hit they hold. Taken when the context wants it
 // (rt_set_skip_behind_hit) AND the scene is ONE tree the flattened scene's engine walks (rt_set_static_geometry(ctx, 1), arrays below 4 GiB): every CWBVH
 // closest-hit kernel -- the merged wavefront's launch, its counting variant, the per-bounce and the explicit kernels -- decides by this one rule.
@@ -298,6 +317,8 @@ void rt_launch_sample_sky(const RtParams & p, const float * directions, int coun
 void rt_launch_bsdf_probe(const RtParams & p, int material_type, bool eval, const float * probes, int count, float * out, hipStream_t stream);
 // Test support: nee_pick_light on explicit random numbers (rt_sample_lights); 4 floats in, RT_LIGHT_SAMPLE_OUT out per probe
 void rt_launch_sample_lights(const RtParams & p, const float * probes, int count, bool use_lds, float * out, hipStream_t stream);
+// Test support: nee_pick_delta and delta_light_sample on explicit probes (rt_sample_delta_lights); 4 floats in, RT_DELTA_SAMPLE_OUT out per probe
+void rt_launch_sample_delta_lights(const RtParams & p, const float * probes, int count, float * out, hipStream_t stream);
 // Test support: normal_map_perturb on explicit hits (rt_perturb_normals); RT_NORMAL_PROBE_IN floats in, 4 out per probe
 void rt_launch_perturb_normals(const RtParams & p, int texture_index, const float * probes, int count, float * out, hipStream_t stream);
 // Sky importance sampling (kernels_sky.hip). build: the three tables of RtParams from the sky; row_total: sky_height doubles, total: one double (the

@@ -109,6 +109,11 @@ struct CPUConfig {
 	// Alpha-tested cut-outs from the albedo textures: 1 = every surface material whose albedo FILE has an alpha channel that is not constant gets an
 	// opacity mask from it (channel a, threshold 0.5; an explicit <bsdf type="mask"> wins). Read when a scene is loaded. 0: off, as the reference renders them.
 	int   alpha_masks = 0;
+	// Delta emitters. delta_lights: 1 = a Mitsuba <emitter type="point"> loads as a true point light (intensity in W/sr); 0 = as the reference's
+	// tiny emissive icosahedron. Read when a scene is loaded; spot and directional emitters are delta lights either way. delta_light_share: the probability
+	// that a light sample the sky did not take goes to a delta light while the scene has triangle emitters too; 0 = by power (Pathtracer::calc_delta_lights).
+	int   delta_lights = 0;
+	float delta_light_share = 0.0f;
 	int   static_slot_learning_viewpoint = 1;   // a quarter of those rays are paths from the camera as it stands when the tree is built (0: none are; half come from points of the free space, the rest from the surface, either way)
 	// ... and early split clipping (StaticBVHBuilder::presplit, as in front of the device build) in front of that builder's own SAH + spatial splits: fraction of
 	// the geometry's longest side above which a triangle is cut blindly first. 0: off.

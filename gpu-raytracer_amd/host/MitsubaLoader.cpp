@@ -12,7 +12,8 @@
 //               dielectric, thindielectric, roughdielectric; twosided / mask / bumpmap / coating are wrappers
 //   shapes      obj, ply, serialized, hair (file meshes); rectangle, cube, disk, cylinder, sphere (generated, the
 //               transform is baked into the vertices); shapegroup + instance
-//   emitters    area (named, or attached to a shape), point, envmap
+//   emitters    area (named, or attached to a shape), envmap; point (the reference's tiny emissive icosahedron, or with cpu_config.delta_lights a
+//               true point light), spot and directional (delta lights, Scene::delta_lights; not in the reference)
 //   sensors     perspective, perspective_rdist, thinlens (+ film size); integrator maxDepth
 // The scene file overrides the command line: film width / height and maxDepth are written into cpu_config /
 // gpu_config (reference: MitsubaLoader.cpp:610-616).
@@ -56,6 +57,13 @@ struct PathName {
 // `value` of the child named `name`, or the fallback
 template<typename T> T property(const XMLNode & node, const char * name, T fallback) { return node.get_child_value_optional(name, fallback); }
 std::string_view plugin(const XMLNode & node) { return node.get_attribute_value("type"); }
+// a <point> or <vector> child: value="x, y, z", or the x / y / z attributes Mitsuba's own files use
+Vector3 vector_property(const XMLNode & node, const char * name, Vector3 fallback) {
+	const XMLNode * given = node.get_child_by_name(name);
+	if (!given) return fallback;
+	if (given->get_attribute("value")) return given->get_attribute_optional("value", fallback);
+	return Vector3(given->get_attribute_optional("x", 0.0f), given->get_attribute_optional("y", 0.0f), given->get_attribute_optional("z", 0.0f));
+}
 std::string filename_property(const XMLNode & node) { return std::string(node.require_child_by_name("filename").get_attribute_value("value")); }
 
 // ---- transforms: each operation of a <transform> multiplies from the left, in document order ---------------
@@ -472,6 +480,37 @@ struct SceneFile {
 			if (dot == std::string::npos)            complain(node, "environment map '" + file + "' has no file extension");
 			else if (file.substr(dot + 1) != "hdr") complain(node, "only HDR environment maps are supported");
 			else cpu_config.sky_filename = PathName::below(folder, file);
+		} else if (kind == "point" && cpu_config.delta_lights) { // a true point light: position from toWorld or `position`, intensity in W/sr
+			DeltaLight light;
+			light.type = DeltaLight::Type::POINT;
+			light.position = node.get_child_by_tag("transform") ? Matrix4::transform_position(to_world(node), Vector3(0.0f)) : vector_property(node, "position", Vector3(0.0f));
+			light.intensity = property(node, "intensity", Vector3(1.0f));
+			scene.delta_lights.push_back(light);
+		} else if (kind == "spot") { // at toWorld's origin, shining along its +z; cutoffAngle and beamWidth in degrees (Mitsuba's defaults: 20, 3/4 of the cutoff)
+			DeltaLight light;
+			light.type = DeltaLight::Type::SPOT;
+			Matrix4 world = to_world(node);
+			light.position  = Matrix4::transform_position(world, Vector3(0.0f));
+			light.direction = Vector3::normalize(Matrix4::transform_direction(world, Vector3(0.0f, 0.0f, 1.0f)));
+			light.intensity = property(node, "intensity", Vector3(1.0f));
+			float cutoff_degrees = property(node, "cutoffAngle", 20.0f);
+			float beam_degrees   = property(node, "beamWidth", cutoff_degrees * 0.75f);
+			if (!(cutoff_degrees > 0.0f && cutoff_degrees <= 180.0f && beam_degrees > 0.0f && beam_degrees <= cutoff_degrees)) {
+				complain(node, "spot emitter needs 0 < beamWidth <= cutoffAngle <= 180: ignored");
+				return;
+			}
+			light.cutoff = Math::deg_to_rad(cutoff_degrees);
+			light.beam   = Math::deg_to_rad(beam_degrees);
+			scene.delta_lights.push_back(light);
+		} else if (kind == "directional") { // the light travels along `direction`, or along toWorld's +z; irradiance in W/m^2
+			DeltaLight light;
+			light.type = DeltaLight::Type::DIRECTIONAL;
+			Vector3 direction = node.get_child_by_name("direction") ? vector_property(node, "direction", Vector3(0.0f, 0.0f, 1.0f))
+			                                                         : Matrix4::transform_direction(to_world(node), Vector3(0.0f, 0.0f, 1.0f));
+			if (!(Vector3::length(direction) > 0.0f)) { complain(node, "directional emitter without a direction: ignored"); return; }
+			light.direction = Vector3::normalize(direction);
+			light.intensity = property(node, "irradiance", Vector3(1.0f));
+			scene.delta_lights.push_back(light);
 		} else if (kind == "point") { // a point light becomes a tiny emissive icosahedron
 			constexpr float RADIUS = 0.0001f;
 			Handle<MeshData> ball = scene.asset_manager.add_mesh_data(Geometry::sphere(to_world(node) * Matrix4::create_scale(RADIUS), 0));

@@ -1,5 +1,7 @@
 #include "Pathtracer.h"
 
+#include <cmath>
+#include <cstring>
 #include <map>
 
 void Pathtracer::gpu_init(int width, int height) {
@@ -123,6 +125,59 @@ void Pathtracer::calc_light_mesh_weights() {
 		lights_total_weight));
 }
 
+// scene.delta_lights -> records with their selection weights, an estimate of the power each sends into the scene: point 4 pi luminance(I); spot
+// 2 pi luminance(I) (1 - (cos beam + cos cutoff) / 2), the cone of the mean of its two angles' cosines; directional pi R^2 luminance(E), what the scene's
+// bounding sphere intercepts. The share against the triangle emitters (whose lights_total_weight is luminance x area: pi times that is their power) is
+// by power, kept inside [0.05, 0.95], unless cpu_config.delta_light_share names one.
+void Pathtracer::calc_delta_lights() {
+	delta_light_records.clear();
+	delta_light_share = 0.0f;
+	if (scene.delta_lights.empty()) {
+		if (ctx && delta_lights_uploaded) { check(rt_upload_delta_lights(ctx, nullptr, 0, 0.0f)); delta_lights_uploaded = false; delta_lights_on_device.clear(); sample_index = 0; }
+		return;
+	}
+	AABB bounds = AABB::create_empty();
+	for (const Mesh & mesh : scene.meshes) bounds.expand(mesh.aabb);
+	const double radius = scene.meshes.empty() ? 0.0 : 0.5 * double(Vector3::length(bounds.max - bounds.min));
+	const double pi = 3.14159265358979323846;
+	double power = 0.0;
+	for (const DeltaLight & light : scene.delta_lights) {
+		rt_delta_light r = { };
+		r.type = int32_t(light.type);
+		r.position[0] = light.position.x; r.position[1] = light.position.y; r.position[2] = light.position.z;
+		r.direction[0] = light.direction.x; r.direction[1] = light.direction.y; r.direction[2] = light.direction.z;
+		r.intensity[0] = light.intensity.x; r.intensity[1] = light.intensity.y; r.intensity[2] = light.intensity.z;
+		r.cutoff = light.cutoff; r.beam = light.beam;
+		const double luminance = double(Math::luminance(light.intensity));
+		double weight = 0.0;
+		switch (light.type) {
+			case DeltaLight::Type::POINT:       weight = 4.0 * pi * luminance; break;
+			case DeltaLight::Type::SPOT:        weight = 2.0 * pi * luminance * (1.0 - 0.5 * (cos(double(light.beam)) + cos(double(light.cutoff)))); break;
+			case DeltaLight::Type::DIRECTIONAL: weight = pi * radius * radius * luminance; break;
+		}
+		r.weight = float(weight);
+		power += double(r.weight);
+		delta_light_records.push_back(r);
+	}
+	if (cpu_config.delta_light_share > 0.0f) delta_light_share = cpu_config.delta_light_share;
+	else {
+		double by_power = power / (power + pi * double(lights_total_weight));
+		delta_light_share = float(by_power < 0.05 ? 0.05 : by_power > 0.95 ? 0.95 : by_power);
+		if (!(power > 0.0)) delta_light_share = 0.05f;   // (black lights: the upload refuses them with its own message)
+	}
+	if (!gpu_config.enable_next_event_estimation && !warned_delta_lights_without_nee) {
+		fprintf(stderr, "WARNING: the scene's point, spot and directional emitters are found by next-event estimation alone: without it they light nothing\n");
+		warned_delta_lights_without_nee = true;
+	}
+	const bool same = delta_lights_uploaded && delta_light_share == delta_light_share_on_device && delta_light_records.size() == delta_lights_on_device.size()
+	                  && memcmp(delta_light_records.data(), delta_lights_on_device.data(), delta_light_records.size() * sizeof(rt_delta_light)) == 0;
+	if (ctx && !same) {
+		check(rt_upload_delta_lights(ctx, delta_light_records.data(), delta_light_records.size(), delta_light_share));
+		delta_lights_uploaded = true; delta_lights_on_device = delta_light_records; delta_light_share_on_device = delta_light_share;
+		sample_index = 0;
+	}
+}
+
 // reference: Pathtracer::update (Pathtracer.cpp:536-736)
 void Pathtracer::update(float delta) {
 	if (invalidated_sky) {
@@ -243,6 +298,10 @@ void Pathtracer::update(float delta) {
 	if (invalidated_light_mesh_weights) {
 		calc_light_mesh_weights();
 		if (!gpu_config.enable_svgf) sample_index = 0;
+	}
+	if (invalidated_light_mesh_weights || invalidated_delta_lights) {   // (after the emitters: the share weighs against their total; after the TLAS: the scene's bounds)
+		if (!scene.delta_lights.empty() || !delta_light_records.empty() || delta_lights_uploaded) calc_delta_lights();
+		invalidated_delta_lights = false;
 	}
 }
 

@@ -13,6 +13,12 @@ struct Pathtracer final : Integrator {
 	std::vector<int>   light_mesh_triangle_span;      // {first, last} per light mesh
 	std::vector<int>   light_mesh_transform_indices;  // TLAS-order mesh id per light mesh
 	float              lights_total_weight = 0.0f;
+	// Delta emitters: scene.delta_lights as rt_upload_delta_lights takes them, and the share that goes with them
+	std::vector<rt_delta_light> delta_light_records;
+	float              delta_light_share = 0.0f;
+	bool               invalidated_delta_lights = true;   // scene.delta_lights or cpu_config.delta_light_share changed
+	bool               delta_lights_uploaded = false, warned_delta_lights_without_nee = false;
+	std::vector<rt_delta_light> delta_lights_on_device; float delta_light_share_on_device = 0.0f;   // what the device holds (an unchanged table is not uploaded again: the upload drains)
 
 	// The SVGFData pair last handed to the device (reference: Pathtracer.cpp:707-717)
 	std::vector<float> svgf_matrices = std::vector<float>(32, 0.0f);
@@ -39,5 +45,6 @@ struct Pathtracer final : Integrator {
 	void calc_light_power();
 	void geometry_was_rebuilt() override { if (scene.has_lights) calc_light_power(); }   // light_triangle_indices name device triangles
 	void calc_light_mesh_weights();
+	void calc_delta_lights();
 
 };

@@ -70,8 +70,17 @@ private:
 	bool assets_loaded = false;
 };
 
+// A light without area: only next-event estimation finds it. intensity: W/sr (point, spot) or irradiance in W/m^2 (directional);
+// direction: a spot's axis, or the way a directional light's light travels; cutoff and beam: a spot's angles in radians.
+struct DeltaLight {
+	enum struct Type { POINT = 0, SPOT = 1, DIRECTIONAL = 2 } type = Type::POINT;
+	Vector3 position, direction = Vector3(0.0f, 0.0f, 1.0f), intensity = Vector3(1.0f);
+	float cutoff = 0.0f, beam = 0.0f;
+};
+
 struct Scene {
 	AssetManager asset_manager;
+	std::vector<DeltaLight> delta_lights;   // (after a change: Pathtracer::invalidated_delta_lights)
 
 	Camera            camera;
 	std::vector<Mesh> meshes;

@@ -75,6 +75,11 @@ int grt_config_set(const char * key, double value) {
 	else if (k == "static_slot_learning_viewpoint")      cpu_config.static_slot_learning_viewpoint = int(value);
 	else if (k == "skip_behind_hit")                     cpu_config.skip_behind_hit = value != 0;
 	else if (k == "alpha_masks")                         cpu_config.alpha_masks = value != 0 ? 1 : 0;
+	else if (k == "delta_lights")                        cpu_config.delta_lights = value != 0 ? 1 : 0;
+	else if (k == "delta_light_share") {   // 0 (by power) or (0, 1]: the delta lights' share of the light samples the sky leaves
+		if (!(value == 0.0 || (value > 0.0 && value <= 1.0))) { g_host_error = "delta_light_share must be 0 (by power) or in (0, 1]"; return -1; }
+		cpu_config.delta_light_share = float(value);
+	}
 	else if (k == "sky_sampling") {   // 0 (off) or (0, 1]: the sky's share of the light samples (rt_set_sky_sampling)
 		if (!(value == 0.0 || (value > 0.0 && value <= 1.0))) { g_host_error = "sky_sampling must be 0 (off) or in (0, 1]"; return -1; }
 		cpu_config.sky_sampling = float(value);
@@ -98,6 +103,8 @@ double grt_config_get(const char * key) {
 	if (k == "skip_behind_hit") return cpu_config.skip_behind_hit;
 	if (k == "sky_sampling")   return cpu_config.sky_sampling;
 	if (k == "alpha_masks")    return cpu_config.alpha_masks;
+	if (k == "delta_lights")   return cpu_config.delta_lights;
+	if (k == "delta_light_share") return cpu_config.delta_light_share;
 	return -1.0;
 }
 
@@ -206,6 +213,33 @@ int grt_scene_set_material_opacity_map(void * scene, int index, int texture, int
 	m.opacity_handle.handle = texture; m.opacity_channel = channel; m.opacity_threshold = threshold; m.opacity_from_albedo = false;
 	return 0;
 }
+// Delta emitters, kept out of grt_scene_describe like the normal maps. A light is 12 floats {type (0 point, 1 spot, 2 directional),
+// position[3], direction[3], intensity[3], cutoff, beam (radians)}; an added light takes effect at the next update after invalidate("delta_lights").
+int grt_scene_delta_light_count(void * scene) { return int(((Scene *)scene)->delta_lights.size()); }
+int grt_scene_get_delta_light(void * scene, int index, float * out12) {
+	Scene * s = (Scene *)scene;
+	if (index < 0 || index >= int(s->delta_lights.size())) { g_host_error = "grt_scene_get_delta_light: light index out of range"; return -1; }
+	const DeltaLight & l = s->delta_lights[index];
+	const float v[12] = { float(int(l.type)), l.position.x, l.position.y, l.position.z, l.direction.x, l.direction.y, l.direction.z, l.intensity.x, l.intensity.y, l.intensity.z, l.cutoff, l.beam };
+	memcpy(out12, v, sizeof(v));
+	return 0;
+}
+int grt_scene_add_delta_light(void * scene, const float * in12) {
+	Scene * s = (Scene *)scene;
+	const int type = int(in12[0]);
+	if (in12[0] != float(type) || type < 0 || type > 2) { g_host_error = "grt_scene_add_delta_light: type must be 0 (point), 1 (spot) or 2 (directional)"; return -1; }
+	for (int i = 1; i < 12; i++) if (!std::isfinite(in12[i])) { g_host_error = "grt_scene_add_delta_light: a value is not finite"; return -1; }
+	DeltaLight l;
+	l.type = DeltaLight::Type(type);
+	l.position = Vector3(in12[1], in12[2], in12[3]); l.direction = Vector3(in12[4], in12[5], in12[6]); l.intensity = Vector3(in12[7], in12[8], in12[9]);
+	l.cutoff = in12[10]; l.beam = in12[11];
+	if (type != 0 && !(Vector3::length(l.direction) > 0.0f)) { g_host_error = "grt_scene_add_delta_light: a spot or directional light needs a direction"; return -1; }
+	if (type == 1 && !(l.beam > 0.0f && l.beam <= l.cutoff && l.cutoff <= 3.14159274f)) { g_host_error = "grt_scene_add_delta_light: a spot needs 0 < beam <= cutoff <= pi (radians)"; return -1; }
+	if (!(l.intensity.x >= 0.0f && l.intensity.y >= 0.0f && l.intensity.z >= 0.0f)) { g_host_error = "grt_scene_add_delta_light: intensity must not be negative"; return -1; }
+	s->delta_lights.push_back(l);
+	return int(s->delta_lights.size()) - 1;
+}
+void grt_scene_clear_delta_lights(void * scene) { ((Scene *)scene)->delta_lights.clear(); }
 // Adds a texture file to the scene; data != 0: a data texture (normal map, see Texture::data). Textures reach the device when a
 // Pathtracer is created, so add them before. Returns the texture index, -1 on failure.
 int grt_scene_add_texture(void * scene, const char * filename, int data) {
@@ -389,6 +423,7 @@ void grt_pathtracer_invalidate(void * pt, const char * what) {
 	if (w == "camera")     p->invalidated_camera = true;
 	if (w == "gpu_config") p->invalidated_gpu_config = true;
 	if (w == "aovs")       p->invalidated_aovs = true;
+	if (w == "delta_lights") if (Pathtracer * pt_only = dynamic_cast<Pathtracer *>(p)) pt_only->invalidated_delta_lights = true;
 }
 void grt_pathtracer_aov_enable(void * pt, int aov, int enable) {
 	if (enable) as_integrator(pt)->aov_enable(AOVType(aov)); else as_integrator(pt)->aov_disable(AOVType(aov));
@@ -428,6 +463,7 @@ int  grt_pathtracer_reflatten_in_progress(void * pt) { Integrator * p = as_integ
 // bytes the flattened tree adds to the device's geometry: its triangle copies (shading + traversal records) and its nodes
 double grt_pathtracer_static_geometry_bytes(void * pt) { Integrator * p = as_integrator(pt); return p->static_geometry.active ? double(p->static_geometry.copy_bytes) : 0.0; }
 double grt_pathtracer_static_geometry_build_seconds(void * pt) { return as_integrator(pt)->static_geometry.build_seconds; }
+float  grt_pathtracer_delta_light_share(void * pt) { { Pathtracer * p = dynamic_cast<Pathtracer *>(as_integrator(pt)); return p ? p->delta_light_share : 0.0f; } }
 float  grt_pathtracer_lights_total_weight(void * pt) { { Pathtracer * p = dynamic_cast<Pathtracer *>(as_integrator(pt)); return p ? p->lights_total_weight : 0.0f; } }
 
 int grt_pathtracer_read_aov(void * pt, int aov, int accumulated, float * dst) {
@@ -555,6 +591,7 @@ const void * grt_pathtracer_array(void * pt, const char * name, size_t * bytes) 
 		if (n == "light_mesh_triangle_span")              RET(pt_only->light_mesh_triangle_span)
 		if (n == "light_mesh_transform_indices")          RET(pt_only->light_mesh_transform_indices)
 		if (n == "svgf_matrices")         RET(pt_only->svgf_matrices)
+		if (n == "delta_light_records")   RET(pt_only->delta_light_records)
 	}
 	if (n == "sky")                   RET(p->scene.sky.data)
 	if (n == "camera") { *bytes = sizeof(rt_camera); return &p->device_camera; }

@@ -97,6 +97,12 @@ std::vector<Option> make_options(CommandLine & cl) {
 		if (!(p == 0.0f || (p > 0.0f && p <= 1.0f))) die("--sky-sampling must be 0 (off) or in (0, 1]");
 		cpu_config.sky_sampling = p;
 	} });
+	o.push_back({ nullptr, "delta-lights", "Point emitters of a scene file load as true point lights (intensity in W/sr) instead of tiny emissive spheres", 0, [](const char *) { cpu_config.delta_lights = 1; } });
+	o.push_back({ nullptr, "delta-light-share", "Share of the light samples that goes to point, spot and directional emitters beside area emitters: 0 = by power (default), (0, 1]", 1, [](const char * v) {
+		float p = parse_float(v, "--delta-light-share");
+		if (!(p == 0.0f || (p > 0.0f && p <= 1.0f))) die("--delta-light-share must be 0 (by power) or in (0, 1]");
+		cpu_config.delta_light_share = p;
+	} });
 	o.push_back({ nullptr, "force-rebuild", "BVH will not be loaded from disk but rebuilt from scratch", 0, [](const char *) { cpu_config.bvh_force_rebuild = true; } });
 	o.push_back({ "O",  "optimize",    "Enables or disables BVH optimization post-processing step", 1, [](const char * v) { cpu_config.enable_bvh_optimization = parse_bool(v); } });
 	o.push_back({ "Ot", "opt-time",    "Sets time limit for BVH optimization (milliseconds, as the reference stores it)", 1, [](const char * v) { cpu_config.bvh_optimizer_max_time = parse_int(v, "--opt-time"); } });

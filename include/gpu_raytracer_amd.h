@@ -156,6 +156,8 @@ const char * rt_version(void);
  *  15  rt_sample_lights (addition); rt_upload_lights refuses tables on which the light search would not end (see there)
  *  16  rt_sort_rays (addition)
  *  17  rt_upload_material_opacity, rt_read_material_opacity (additions only; alpha-tested opacity masks, off until a mask is uploaded)
+ *      (still 17: rt_upload_delta_lights, rt_read_delta_lights, rt_sample_delta_lights -- new entry points and a record of their own, no
+ *      existing struct or call changed; point, spot and directional emitters, off until a table is uploaded)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
 #define RT_ABI_VERSION 17
 int rt_abi_version(void);
@@ -323,6 +325,39 @@ int rt_upload_lights(rt_context * ctx,
                      const float * light_mesh_cumulative_probability, const int32_t * light_mesh_triangle_span /* 2 per mesh */,
                      const int32_t * light_mesh_transform_indices, size_t light_mesh_count,
                      float lights_total_weight);
+/* Delta emitters: point, spot and directional lights, which only next-event estimation can find. One rt_delta_light each:
+ * type; position (point, spot); direction (spot: its axis; directional: the direction the light TRAVELS; any non-zero length, normalised on
+ * upload); intensity (point, spot: W/sr; directional: irradiance, W/m^2); cutoff and beam (spot, radians: full intensity inside `beam`, none
+ * outside `cutoff`, linear in the angle between); weight (>= 0: the light is selected with probability weight / sum of weights).
+ * share in (0, 1]: the probability that a light sample the sky did not take goes to a delta light while triangle emitters exist too
+ * (q = (1 - sky share) * share); without triangle emitters the delta lights take all of them. Checked on the host before anything is
+ * staged: count <= RT_MAX_DELTA_LIGHTS, a known type, finite positions, finite non-zero directions, finite intensities >= 0,
+ * 0 < beam <= cutoff <= pi (spot), finite weights >= 0 with a finite sum > 0, share in (0, 1]. Otherwise RT_ERROR_INVALID_ARG with a message
+ * that names the light, and the table uploaded before stays in force. records == NULL or count == 0 clears the table: the context then
+ * launches exactly the kernels it launched before any upload (the lights are sampled by the ..._split instances of the sort and material kernels, taken only while
+ * a table is in force and next-event estimation is on). Drains the context (not a per-frame upload). With next-event estimation
+ * disabled the lights contribute nothing.                                                                                      */
+#define RT_DELTA_LIGHT_POINT       0
+#define RT_DELTA_LIGHT_SPOT        1
+#define RT_DELTA_LIGHT_DIRECTIONAL 2
+#define RT_MAX_DELTA_LIGHTS        65536
+typedef struct rt_delta_light {
+	int32_t type;
+	float position[3];
+	float direction[3];
+	float intensity[3];
+	float cutoff, beam;
+	float weight;
+	float reserved[3];
+} rt_delta_light; /* 64 bytes */
+int rt_upload_delta_lights(rt_context * ctx, const rt_delta_light * records, size_t count, float share);
+/* The table as staged for the kernels. records: count x RT_DELTA_LIGHT_RECORD floats {position[3], type (int32 bits), unit direction[3],
+ * P_k (the light's selection probability, computed in double from its weight), intensity[3], cos(cutoff), cos(beam), cutoff,
+ * 1 / (cutoff - beam) (0 when they are equal), pad}; cdf: count floats, inclusive and normalised, the last entry exactly 1. Either array
+ * may be NULL; capacity: lights the arrays have room for (RT_ERROR_INVALID_ARG when fewer than the table holds and an array is given).
+ * *out_count: lights in the table; *out_share: the share of the upload (0 without a table).                                       */
+#define RT_DELTA_LIGHT_RECORD 16
+int rt_read_delta_lights(rt_context * ctx, float * records, float * cdf, size_t capacity, size_t * out_count, float * out_share);
 /* Replaces pmj_samples / blue_noise_textures (Integrator.cpp:298-304):
  * pmj = 64*4096 float2, blue_noise = 16*128*128 uchar2.                                   */
 int rt_upload_rng(rt_context * ctx, const float * pmj_samples, const uint8_t * blue_noise);
@@ -616,6 +651,15 @@ int rt_bsdf_sample(rt_context * ctx, int material_type, const float * probes, si
  * normal[3], emission[3], pad[3]}. RT_ERROR_NOT_READY without emitters. Writes no frame buffer.                                      */
 #define RT_LIGHT_SAMPLE_OUT 16
 int rt_sample_lights(rt_context * ctx, const float * probes, size_t count, int use_lds, float * out);
+/* The shade kernels' delta-light sample on explicit probes (synchronous): nee_pick_delta -- the search of the table's CDF -- and
+ * delta_light_sample -- direction, distance, radiance term -- on the table of rt_upload_delta_lights. probes: count x 4 floats
+ * {u in [0, 1), origin[3] (finite; the shadow ray's origin, taken as it is)}. out: count x RT_DELTA_SAMPLE_OUT floats {light index (int32
+ * bits), to_light[3] (unit), max_distance (RT_INFINITY for a directional light), radiance term[3] (intensity x falloff / d^2, or the
+ * irradiance), pdf (P_k of the light's record: the probability of this light among the delta lights), ok (1 / 0: 0 when the distance is 0
+ * or not finite, the falloff is 0, the radiance term is not finite or P_k is 0), pad[2]}. RT_ERROR_NOT_READY without a table. Writes no
+ * frame buffer.                                                                                                                  */
+#define RT_DELTA_SAMPLE_OUT 12
+int rt_sample_delta_lights(rt_context * ctx, const float * probes, size_t count, float * out);
 /* The shade kernels' normal-map perturbation (normal_map_perturb, rt_shading.h) on explicit hits (synchronous), with texture
  * `texture_index` (RT_TEXTURE_RGBA8) of the last rt_upload_textures as the map. probes: count x RT_NORMAL_PROBE_IN floats
  * {p0[3], e1[3], e2[3] (object-space triangle: vertex 0 and the two edges), n0[3], ne1[3], ne2[3] (vertex normal 0 and its
