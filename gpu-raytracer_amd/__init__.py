@@ -55,6 +55,10 @@ class Counters(ctypes.Structure):  # rt_counters
                 ("ms_shadow", c_float), ("ms_post", c_float), ("ms_total", c_float)]
 
 
+class NoiseEstimateRecord(ctypes.Structure):  # rt_noise_estimate
+    _fields_ = [("cells_x", ctypes.c_int32), ("cells_y", ctypes.c_int32), ("pixels", ctypes.c_int64), ("nonfinite_pixels", ctypes.c_int64), ("mean", ctypes.c_double)]
+
+
 class DeviceLibraryMissing(RuntimeError):
     pass
 
@@ -126,6 +130,13 @@ def device_lib():
         lib.rt_read_svgf_state.argtypes = [c_void_p, c_int, c_void_p]
         lib.rt_read_luts.argtypes = [c_void_p] + [c_void_p] * 6
         lib.rt_set_config.argtypes = [c_void_p, POINTER(GPUConfig)]
+        lib.rt_set_noise_estimate.argtypes = [c_void_p, c_int]
+        lib.rt_get_noise_estimate.argtypes = [c_void_p]
+        lib.rt_read_noise_moments.argtypes = [c_void_p, c_void_p]
+        lib.rt_estimate_noise.argtypes = [c_void_p, c_float, POINTER(NoiseEstimateRecord), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+        lib.rt_estimate_noise_images.argtypes = [c_void_p, c_void_p, c_void_p, c_float, POINTER(NoiseEstimateRecord), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+        lib.rt_accumulate_frames.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]
+        lib.rt_set_pixel_tiles.argtypes = [c_void_p, c_int, c_int, c_int]
         _device = lib
     return _device
 
@@ -858,6 +869,78 @@ class Pathtracer:
         _host_check(host_lib().grt_pathtracer_counters(self.handle, byref(c)))
         return c
 
+    # ---- noise estimate
+    def set_noise_estimate(self, enable=True):
+        """The device keeps Welford second moments beside the radiance mean from the next update() on (which restarts the
+        progression when it switches them on). Also on while config noise_target > 0."""
+        lib = host_lib()
+        lib.grt_pathtracer_set_noise_estimate.argtypes = [c_void_p, c_int]
+        lib.grt_pathtracer_set_noise_estimate.restype = None
+        lib.grt_pathtracer_set_noise_estimate(self.handle, 1 if enable else 0)
+
+    def _noise(self, entry, want_map):
+        lib = host_lib()
+        fn = getattr(lib, entry)
+        fn.argtypes = [c_void_p] + [c_void_p] * 4 + [c_size_t] + [c_void_p] * 3
+        cells_x, cells_y = (self.width + 15) // 16, (self.height + 15) // 16
+        n = cells_x * cells_y
+        xy = np.zeros(2, np.int32)
+        sums, counts, nonfinite = np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        mean_figure, pixels = np.zeros(2, np.float64), np.zeros(2, np.int64)
+        pixel_map = np.zeros((self.height, self.pitch), np.float32) if want_map else None
+        _host_check(fn(self.handle, xy.ctypes.data, sums.ctypes.data, counts.ctypes.data, nonfinite.ctypes.data, n, mean_figure.ctypes.data, pixels.ctypes.data,
+                       pixel_map.ctypes.data if want_map else None))
+        shape = (int(xy[1]), int(xy[0]))
+        return {"cells_x": int(xy[0]), "cells_y": int(xy[1]), "cell_sums": sums.reshape(shape), "cell_counts": counts.reshape(shape), "cell_nonfinite": nonfinite.reshape(shape),
+                "mean": float(mean_figure[0]), "figure": float(mean_figure[1]), "pixels": int(pixels[0]), "nonfinite_pixels": int(pixels[1])}, pixel_map
+
+    def noise_estimate(self):
+        """Pathtracer::noise(): the cells (16 x 16 pixels: sums of the per-pixel relative standard error, counts, non-finite counts), the mean over
+        the frame and the figure -- the noise_quantile quantile of the cell means. Completes the work in flight."""
+        return self._noise("grt_pathtracer_noise", False)[0]
+
+    def noise_map(self):
+        """The per-pixel relative standard error, (height, pitch) float32: -1 where the pixel takes no part, -2 where it is not finite."""
+        return self._noise("grt_pathtracer_noise", True)[1]
+
+    def render_until(self, noise_target, max_samples, check_every=16):
+        """Renders until the noise figure is <= noise_target, never fewer than config noise_min_samples samples and never more than max_samples;
+        the figure is asked for every `check_every` samples only (the question drains the wavefront). Returns {"samples", "figure", "mean", "capped"}."""
+        if not (noise_target >= 0.0) or max_samples < 2 or check_every < 1:
+            raise ValueError("render_until: noise_target >= 0, max_samples >= 2 and check_every >= 1 are required")
+        if config_get("enable_svgf"):   # SVGF frames keep no second moments (their accumulators are the filter's images)
+            import warnings
+            warnings.warn("render_until: SVGF frames keep no noise estimate; rendering to max_samples")
+            while True:
+                self.update()
+                self.render()
+                if self.sample_index + 1 >= max_samples:
+                    return {"samples": self.sample_index + 1, "figure": None, "mean": None, "capped": True}
+        self.set_noise_estimate(True)
+        min_samples = int(config_get("noise_min_samples"))
+        estimate = None
+        while True:
+            self.update()
+            first = self.sample_index
+            if first + 1 > max_samples:
+                raise ValueError("render_until: %d samples are accumulated already, max_samples is %d" % (first, max_samples))
+            n = min(check_every - first % check_every, max_samples - first, 16)
+            if first == 0 or n == 1:
+                self.render()
+            else:
+                self.render_samples(n)
+            samples = self.sample_index + 1
+            estimate = None
+            if samples >= min_samples and (samples % check_every == 0 or samples >= max_samples):
+                estimate = self.noise_estimate()
+                if estimate["figure"] <= noise_target:
+                    break
+            if samples >= max_samples:
+                break
+        if estimate is None:
+            estimate = self.noise_estimate()
+        return {"samples": self.sample_index + 1, "figure": estimate["figure"], "mean": estimate["mean"], "capped": not estimate["figure"] <= noise_target}
+
 
 # ---- kernel-level entry points of the C ABI -----------------------------------------------------------
 
@@ -900,6 +983,14 @@ class FrameSplit:
     def render_samples(self, count):
         _host_check(host_lib().grt_frame_split_render_samples(self.handle, int(count)))
 
+    @property
+    def pitch(self):
+        return self.rank(0).pitch
+
+    def noise_estimate(self):
+        """FrameSplit::noise(): the ranks' cell sums and counts added, then the same summary as Pathtracer.noise_estimate()."""
+        return Pathtracer._noise(self, "grt_frame_split_noise", False)[0]
+
 
 class AO(Pathtracer):
     """reference: Src/Renderer/Integrators/AO.h -- the ambient-occlusion integrator. Shares the
@@ -927,6 +1018,86 @@ def _dev_check(ctx, status):
 
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+class DeviceRefusal(RuntimeError):
+    """A device-layer call that returned an error status (.status: the RT_ERROR_* value)."""
+
+    def __init__(self, ctx, status):
+        super().__init__("device layer (%d): %s" % (status, device_lib().rt_last_error(ctx).decode()))
+        self.status = status
+
+
+def set_noise_estimate(ctx, enable):
+    status = device_lib().rt_set_noise_estimate(ctx, 1 if enable else 0)
+    if status:
+        raise DeviceRefusal(ctx, status)
+
+
+def get_noise_estimate(ctx):
+    return bool(device_lib().rt_get_noise_estimate(ctx))
+
+
+def read_noise_moments(ctx, height, pitch):
+    """rt_read_noise_moments: (height, pitch, 4) float32 {M2_r, M2_g, M2_b, w}."""
+    image = np.zeros((height, pitch, 4), np.float32)
+    status = device_lib().rt_read_noise_moments(ctx, image.ctypes.data)
+    if status:
+        raise DeviceRefusal(ctx, status)
+    return image
+
+
+def estimate_noise(ctx, height, width, pitch, floor=1e-2, mean=None, moments=None, want_map=True, cell_capacity=None):
+    """rt_estimate_noise on the context's accumulator and moments, or -- mean and moments given, (height, pitch, 4) float32 -- rt_estimate_noise_images on
+    those. Returns a dict: cells_x, cells_y, pixels, nonfinite_pixels, mean, cell_sums / cell_counts / cell_nonfinite (cells_y, cells_x), pixel_map (height, pitch)."""
+    lib = device_lib()
+    cells_x, cells_y = (width + 15) // 16, (height + 15) // 16
+    n = cells_x * cells_y
+    sums, counts, nonfinite = np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    pixel_map = np.zeros((height, pitch), np.float32) if want_map else None
+    out = NoiseEstimateRecord()
+    tail = (c_float(floor), byref(out), sums.ctypes.data, counts.ctypes.data, nonfinite.ctypes.data, n if cell_capacity is None else cell_capacity, pixel_map.ctypes.data if want_map else None)
+    if mean is None:
+        status = lib.rt_estimate_noise(ctx, *tail)
+    else:
+        mean, moments = _f32(mean), _f32(moments)
+        assert mean.shape == (height, pitch, 4) and moments.shape == (height, pitch, 4)
+        status = lib.rt_estimate_noise_images(ctx, mean.ctypes.data, moments.ctypes.data, *tail)
+    if status:
+        raise DeviceRefusal(ctx, status)
+    return {"cells_x": out.cells_x, "cells_y": out.cells_y, "pixels": out.pixels, "nonfinite_pixels": out.nonfinite_pixels, "mean": out.mean,
+            "cell_sums": sums.reshape(cells_y, cells_x), "cell_counts": counts.reshape(cells_y, cells_x), "cell_nonfinite": nonfinite.reshape(cells_y, cells_x), "pixel_map": pixel_map}
+
+
+def accumulate_frames(ctx, frames, accumulator, moments, first_sample, sample_count=None, merged=False, sentinel=0x7fc0dead):
+    """rt_accumulate_frames: one accumulate launch on explicit images over the context's pixel set. frames: (samples, height, pitch, 4) float32; accumulator and
+    moments (None: the plain kernel): (height, pitch, 4). merged=False: first_sample an int, all frames one batch (<= 16). merged=True: first_sample and
+    sample_count are lists, one entry per submission. Returns (frames, accumulator, moments, final_image) after the launch; final_image holds `sentinel`
+    (uint32 bits) where the launch did not write."""
+    frames, accumulator = _f32(frames).copy(), _f32(accumulator).copy()
+    moments = None if moments is None else _f32(moments).copy()
+    if merged:
+        first, count = np.asarray(first_sample, np.int32).copy(), np.asarray(sample_count, np.int32).copy()
+    else:
+        first, count = np.array([first_sample], np.int32), np.array([frames.shape[0] if sample_count is None else sample_count], np.int32)
+    assert frames.ndim == 4 and frames.shape[0] == int(count.sum()) and frames.shape[1:] == accumulator.shape and (moments is None or moments.shape == accumulator.shape)
+    final = np.zeros(accumulator.shape, np.float32)
+    status = device_lib().rt_accumulate_frames(ctx, 1 if merged else 0, first.ctypes.data, count.ctypes.data, len(first), frames.ctypes.data, accumulator.ctypes.data,
+                                               None if moments is None else moments.ctypes.data, sentinel, final.ctypes.data)
+    if status:
+        raise DeviceRefusal(ctx, status)
+    return frames, accumulator, moments, final
+
+
+def noise_summary(cell_sums, cell_counts, quantile):
+    """grt_noise_summary of the host library: (status, mean, figure, pixels). status 0 fine, 1 no cell has a count, -1 quantile outside (0, 1]."""
+    lib = host_lib()
+    lib.grt_noise_summary.argtypes = [c_void_p, c_void_p, c_size_t, ctypes.c_double, POINTER(ctypes.c_double), POINTER(ctypes.c_double), POINTER(ctypes.c_longlong)]
+    sums = np.ascontiguousarray(cell_sums, np.float64).ravel()
+    counts = np.ascontiguousarray(cell_counts, np.int32).ravel()
+    mean, figure, pixels = ctypes.c_double(), ctypes.c_double(), ctypes.c_longlong()
+    status = lib.grt_noise_summary(sums.ctypes.data, counts.ctypes.data, sums.size, float(quantile), byref(mean), byref(figure), byref(pixels))
+    return status, mean.value, figure.value, pixels.value
 
 
 def trace_rays(ctx, origin, direction, repeat=1):

@@ -1,4 +1,4 @@
-// kernels_post.hip -- image-space kernels: accumulate, SVGF (reproject / variance / a-trous /
+// kernels_post.hip -- image-space kernels: accumulate (with or without second moments), the noise estimate, SVGF (reproject / variance / a-trous /
 // finalize), TAA, plus the Kulla-Conty LUT integration kernels and a bandwidth probe.
 //
 // Replaces kernel_accumulate (CUDA/Pathtracer.cu:775-796), the six kernels of
@@ -36,17 +36,32 @@ RT_DEV void st4(float4 * p, int i, f4 v) { p[i] = to_float4(v); }
 
 // ---- accumulate ---------------------------------------------------------------------------------
 
+// One sample folded into the running mean, AOV.h:35-46: sample 0 sets the mean and sample 1 overwrites it (fb - acc over n = 1), the quirk every
+// comparison with the reference rests on. MOMENTS: Welford's second moment beside it, from the values the mean's own fold has just
+// computed -- d = fb - acc_old and acc_new -- in plain float32 -, /, *, +: m2 = (M2_r, M2_g, M2_b, w), w the number of samples the moment stands for.
+// Samples 0 and 1 leave (0, 0, 0, 1): after either the mean holds one sample alone.
+template<bool MOMENTS> RT_DEV f4 accumulate_fold(f4 acc, f4 & m2, f4 fb, float n) {   // n > 0
+	f4 d = fb - acc;
+	f4 next = acc + d / n;
+	if (MOMENTS) {
+		if (n >= 2.0f) { f4 t = d * (fb - next); m2 = mk4(m2.x + t.x, m2.y + t.y, m2.z + t.z, n); }
+		else m2 = mk4(0.0f, 0.0f, 0.0f, 1.0f);
+	}
+	return next;
+}
+
 // The samples of a batch are folded in one after the other, exactly as separate calls would.
-RT_DEV f4 aov_accumulate(const RtParams & p, int aov, int pixel_index, float n) { // AOV.h:35-46
+template<bool MOMENTS> RT_DEV f4 aov_accumulate(const RtParams & p, int aov, int pixel_index, float n, float4 * moments = nullptr) { // AOV.h:35-46
 	const RtAOV & a = p.aovs[aov];
 	if (!a.framebuffer) return mk4(0.0f);
-	f4 acc = mk4(0.0f);
+	f4 acc = mk4(0.0f), m2 = mk4(0.0f);
 	for (int s = 0; s < p.batch_samples; s++, n += 1.0f) {
 		f4 fb = mk4(a.framebuffer[size_t(s) * p.frame_pixels + pixel_index]);
-		if (n > 0.0f) { if (s == 0) acc = mk4(a.accumulator[pixel_index]); acc = acc + (fb - acc) / n; }
-		else acc = fb;
+		if (n > 0.0f) { if (s == 0) { acc = mk4(a.accumulator[pixel_index]); if (MOMENTS) m2 = mk4(moments[pixel_index]); } acc = accumulate_fold<MOMENTS>(acc, m2, fb, n); }
+		else { acc = fb; if (MOMENTS) m2 = mk4(0.0f, 0.0f, 0.0f, 1.0f); }
 	}
 	a.accumulator[pixel_index] = to_float4(acc);
+	if (MOMENTS) moments[pixel_index] = to_float4(m2);
 	return acc;
 }
 
@@ -56,10 +71,27 @@ __global__ void __launch_bounds__(256) kernel_accumulate(RtParams p, float frame
 		int x = idx % p.screen_width, y = idx / p.screen_width;
 		int pixel_index = x + y * p.screen_pitch;
 
-		f4 colour = aov_accumulate(p, RT_AOV_RADIANCE, pixel_index, frames_accumulated);
-		aov_accumulate(p, RT_AOV_ALBEDO,   pixel_index, frames_accumulated);
-		aov_accumulate(p, RT_AOV_NORMAL,   pixel_index, frames_accumulated);
-		aov_accumulate(p, RT_AOV_POSITION, pixel_index, frames_accumulated);
+		f4 colour = aov_accumulate<false>(p, RT_AOV_RADIANCE, pixel_index, frames_accumulated);
+		aov_accumulate<false>(p, RT_AOV_ALBEDO,   pixel_index, frames_accumulated);
+		aov_accumulate<false>(p, RT_AOV_NORMAL,   pixel_index, frames_accumulated);
+		aov_accumulate<false>(p, RT_AOV_POSITION, pixel_index, frames_accumulated);
+
+		if (!isfinite(colour.x + colour.y + colour.z)) colour = mk4(1000.0f, 0.0f, 1000.0f, 1.0f); // NaN guard, Pathtracer.cu:790-793
+		p.final_image[pixel_index] = to_float4(colour);
+	}
+}
+// ... and the second moment of RADIANCE beside its mean (rt_set_noise_estimate): one more float4 read and written per pixel. (The loop is written out in each
+// kernel: shared through a device function, the plain kernels' code objects came out different from what they were.)
+__global__ void __launch_bounds__(256) kernel_accumulate_moments(RtParams p, float frames_accumulated, int pixel_offset, int pixel_count, float4 * moments) {
+	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < pixel_count; i += gridDim.x * blockDim.x) {
+		int idx = rt_map_pixel(p, i + pixel_offset);
+		int x = idx % p.screen_width, y = idx / p.screen_width;
+		int pixel_index = x + y * p.screen_pitch;
+
+		f4 colour = aov_accumulate<true>(p, RT_AOV_RADIANCE, pixel_index, frames_accumulated, moments);
+		aov_accumulate<false>(p, RT_AOV_ALBEDO,   pixel_index, frames_accumulated);
+		aov_accumulate<false>(p, RT_AOV_NORMAL,   pixel_index, frames_accumulated);
+		aov_accumulate<false>(p, RT_AOV_POSITION, pixel_index, frames_accumulated);
 
 		if (!isfinite(colour.x + colour.y + colour.z)) colour = mk4(1000.0f, 0.0f, 1000.0f, 1.0f); // NaN guard, Pathtracer.cu:790-793
 		p.final_image[pixel_index] = to_float4(colour);
@@ -70,10 +102,10 @@ __global__ void __launch_bounds__(256) kernel_accumulate(RtParams p, float frame
 // order) folded into the accumulators by ONE launch -- the same operations in the same order as one launch per submission,
 // with the accumulator kept in registers in between -- and the per-sample frames cleared on the way (aovs_clear_to_zero:
 // only the pixels this context renders were ever written, a memset of the whole frames moved 8x the bytes on a 1/8 split).
-RT_DEV f4 aov_accumulate_group(const RtParams & p, const RtAccumulateGroup & g, int aov, int pixel_index) {
+template<bool MOMENTS> RT_DEV f4 aov_accumulate_group(const RtParams & p, const RtAccumulateGroup & g, int aov, int pixel_index, float4 * moments = nullptr) {
 	const RtAOV & a = p.aovs[aov];
 	if (!a.framebuffer) return mk4(0.0f);
-	f4 acc = mk4(0.0f);
+	f4 acc = mk4(0.0f), m2 = mk4(0.0f);
 	bool loaded = false;
 	for (int k = 0; k < g.count; k++) {
 		float n = float(g.first_sample[k]);
@@ -82,12 +114,13 @@ RT_DEV f4 aov_accumulate_group(const RtParams & p, const RtAccumulateGroup & g, 
 			float4 * sample = frames + size_t(s) * p.frame_pixels + pixel_index;
 			f4 fb = mk4(*sample);
 			*sample = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-			if (n > 0.0f) { if (!loaded) acc = mk4(a.accumulator[pixel_index]); acc = acc + (fb - acc) / n; }
-			else acc = fb;
+			if (n > 0.0f) { if (!loaded) { acc = mk4(a.accumulator[pixel_index]); if (MOMENTS) m2 = mk4(moments[pixel_index]); } acc = accumulate_fold<MOMENTS>(acc, m2, fb, n); }
+			else { acc = fb; if (MOMENTS) m2 = mk4(0.0f, 0.0f, 0.0f, 1.0f); }
 			loaded = true;
 		}
 	}
 	a.accumulator[pixel_index] = to_float4(acc);
+	if (MOMENTS) moments[pixel_index] = to_float4(m2);
 	return acc;
 }
 
@@ -97,14 +130,76 @@ __global__ void __launch_bounds__(256) kernel_accumulate_group(RtParams p, RtAcc
 		int x = idx % p.screen_width, y = idx / p.screen_width;
 		int pixel_index = x + y * p.screen_pitch;
 
-		f4 colour = aov_accumulate_group(p, g, RT_AOV_RADIANCE, pixel_index);
-		aov_accumulate_group(p, g, RT_AOV_ALBEDO,   pixel_index);
-		aov_accumulate_group(p, g, RT_AOV_NORMAL,   pixel_index);
-		aov_accumulate_group(p, g, RT_AOV_POSITION, pixel_index);
+		f4 colour = aov_accumulate_group<false>(p, g, RT_AOV_RADIANCE, pixel_index);
+		aov_accumulate_group<false>(p, g, RT_AOV_ALBEDO,   pixel_index);
+		aov_accumulate_group<false>(p, g, RT_AOV_NORMAL,   pixel_index);
+		aov_accumulate_group<false>(p, g, RT_AOV_POSITION, pixel_index);
 
 		if (!isfinite(colour.x + colour.y + colour.z)) colour = mk4(1000.0f, 0.0f, 1000.0f, 1.0f); // NaN guard, Pathtracer.cu:790-793
 		p.final_image[pixel_index] = to_float4(colour);
 	}
+}
+__global__ void __launch_bounds__(256) kernel_accumulate_group_moments(RtParams p, RtAccumulateGroup g, int pixel_offset, int pixel_count, float4 * moments) {
+	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < pixel_count; i += gridDim.x * blockDim.x) {
+		int idx = rt_map_pixel(p, i + pixel_offset);
+		int x = idx % p.screen_width, y = idx / p.screen_width;
+		int pixel_index = x + y * p.screen_pitch;
+
+		f4 colour = aov_accumulate_group<true>(p, g, RT_AOV_RADIANCE, pixel_index, moments);
+		aov_accumulate_group<false>(p, g, RT_AOV_ALBEDO,   pixel_index);
+		aov_accumulate_group<false>(p, g, RT_AOV_NORMAL,   pixel_index);
+		aov_accumulate_group<false>(p, g, RT_AOV_POSITION, pixel_index);
+
+		if (!isfinite(colour.x + colour.y + colour.z)) colour = mk4(1000.0f, 0.0f, 1000.0f, 1.0f); // NaN guard, Pathtracer.cu:790-793
+		p.final_image[pixel_index] = to_float4(colour);
+	}
+}
+
+// ---- noise estimate (rt_estimate_noise) ----------------------------------------------------------------
+// One workgroup per cell of RT_NOISE_CELL x RT_NOISE_CELL pixels of the screen (not of the pitch: the padding columns are never read), edge cells
+// clipped; thread t owns pixel (t % 16, t / 16) of the cell. A pixel takes part when w >= 2 and its mean and M2 are finite; with w >= 2 and anything
+// not finite it is counted as non-finite and left out. Its error is the standard error of the mean's three channels over the mean's luminance
+// (`luminance` of rt_shading.h, floored), in float32 in exactly this shape:
+//   v = (M2_r + M2_g) + M2_b;  e_p = sqrtf(v / (w * (w - 1.0f))) / fmaxf(luminance(mean), floor)
+// The cell's sum of e_p (double), its participating and its non-finite pixels are reduced by a fixed tree in LDS -- s[t] += s[t + stride], stride
+// 128 .. 1 -- without atomics: the same bits on every run and every rank, as the sky tables' scans are.
+__global__ void __launch_bounds__(RT_NOISE_CELL * RT_NOISE_CELL) kernel_noise_cells(const float4 * __restrict__ mean, const float4 * __restrict__ moments, int width, int height, int pitch,
+                                                                                    int cells_x, float floor, float * __restrict__ pixel_map,
+                                                                                    double * __restrict__ cell_sums, int * __restrict__ cell_counts, int * __restrict__ cell_nonfinite) {
+	__shared__ double sums[RT_NOISE_CELL * RT_NOISE_CELL];
+	__shared__ int counts[RT_NOISE_CELL * RT_NOISE_CELL], nonfinite[RT_NOISE_CELL * RT_NOISE_CELL];
+	const int t = threadIdx.x;
+	const int x = int(blockIdx.x % unsigned(cells_x)) * RT_NOISE_CELL + t % RT_NOISE_CELL;
+	const int y = int(blockIdx.x / unsigned(cells_x)) * RT_NOISE_CELL + t / RT_NOISE_CELL;
+	double sum = 0.0; int count = 0, bad = 0;
+	if (x < width && y < height) {
+		const size_t pixel_index = size_t(x) + size_t(y) * pitch;
+		const float4 m = moments[pixel_index];
+		float e = -1.0f;
+		if (m.w >= 2.0f) {
+			const float4 c = mean[pixel_index];
+			if (isfinite(c.x) && isfinite(c.y) && isfinite(c.z) && isfinite(m.x) && isfinite(m.y) && isfinite(m.z)) {
+				float v = (m.x + m.y) + m.z;
+				e = sqrtf(v / (m.w * (m.w - 1.0f))) / fmaxf(luminance(c.x, c.y, c.z), floor);
+				sum = double(e); count = 1;
+			} else { e = -2.0f; bad = 1; }
+		}
+		if (pixel_map) pixel_map[pixel_index] = e;
+	}
+	sums[t] = sum; counts[t] = count; nonfinite[t] = bad;
+	__syncthreads();
+	for (int stride = RT_NOISE_CELL * RT_NOISE_CELL / 2; stride >= 1; stride >>= 1) {
+		if (t < stride) { sums[t] += sums[t + stride]; counts[t] += counts[t + stride]; nonfinite[t] += nonfinite[t + stride]; }
+		__syncthreads();
+	}
+	if (t == 0) { cell_sums[blockIdx.x] = sums[0]; cell_counts[blockIdx.x] = counts[0]; cell_nonfinite[blockIdx.x] = nonfinite[0]; }
+}
+
+void rt_launch_noise_cells(const float4 * mean, const float4 * moments, int width, int height, int pitch, float floor, float * pixel_map,
+                           double * cell_sums, int * cell_counts, int * cell_nonfinite, hipStream_t stream) {
+	const int cells_x = (width + RT_NOISE_CELL - 1) / RT_NOISE_CELL, cells_y = (height + RT_NOISE_CELL - 1) / RT_NOISE_CELL;
+	hipLaunchKernelGGL(kernel_noise_cells, dim3(unsigned(cells_x) * unsigned(cells_y)), dim3(RT_NOISE_CELL * RT_NOISE_CELL), 0, stream,
+	                   mean, moments, width, height, pitch, cells_x, floor, pixel_map, cell_sums, cell_counts, cell_nonfinite);
 }
 
 // ---- SVGF ----------------------------------------------------------------------------------------
@@ -729,18 +824,21 @@ void rt_launch_svgf_taa(const RtParams & p, int sample_index, hipStream_t stream
 	#undef RT_TIMED
 }
 
-void rt_launch_accumulate(const RtParams & p, float frames_accumulated, int pixel_offset, int pixel_count, hipStream_t stream) {
+// moments: null for the plain kernel, else the second-moment image the ..._moments kernel keeps beside the RADIANCE mean (rt_set_noise_estimate)
+void rt_launch_accumulate(const RtParams & p, float frames_accumulated, int pixel_offset, int pixel_count, hipStream_t stream, float4 * moments) {
 	int blocks = (pixel_count + 255) / 256;
 	if (blocks > 4096) blocks = 4096;
 	if (blocks < 1) blocks = 1;
-	hipLaunchKernelGGL(kernel_accumulate, dim3(blocks), dim3(256), 0, stream, p, frames_accumulated, pixel_offset, pixel_count);
+	if (moments) hipLaunchKernelGGL(kernel_accumulate_moments, dim3(blocks), dim3(256), 0, stream, p, frames_accumulated, pixel_offset, pixel_count, moments);
+	else hipLaunchKernelGGL(kernel_accumulate, dim3(blocks), dim3(256), 0, stream, p, frames_accumulated, pixel_offset, pixel_count);
 }
 
-void rt_launch_accumulate_group(const RtParams & p, const RtAccumulateGroup & group, int pixel_offset, int pixel_count, hipStream_t stream) {
+void rt_launch_accumulate_group(const RtParams & p, const RtAccumulateGroup & group, int pixel_offset, int pixel_count, hipStream_t stream, float4 * moments) {
 	int blocks = (pixel_count + 255) / 256;
 	if (blocks > 4096) blocks = 4096;
 	if (blocks < 1) blocks = 1;
-	hipLaunchKernelGGL(kernel_accumulate_group, dim3(blocks), dim3(256), 0, stream, p, group, pixel_offset, pixel_count);
+	if (moments) hipLaunchKernelGGL(kernel_accumulate_group_moments, dim3(blocks), dim3(256), 0, stream, p, group, pixel_offset, pixel_count, moments);
+	else hipLaunchKernelGGL(kernel_accumulate_group, dim3(blocks), dim3(256), 0, stream, p, group, pixel_offset, pixel_count);
 }
 
 // ---- Kulla-Conty LUT integration (KullaConty.h:83-240) -------------------------------------------------------

@@ -34,7 +34,6 @@ static void warn_if_streams_share_queues(int streams_needed) {
 	                "the merged scheduler (the default) needs two streams\n", streams_needed, value ? value : "(unset, 4)", queues);
 }
 
-#define RT_MAX_BATCH_SAMPLES 16
 #define RT_RAY_CURSOR_BYTES (RT_MAX_BOUNCES * 2 * sizeof(int))   // RtParams::ray_cursors of a slot: [RT_MAX_BOUNCES][2 (closest hit, shadow)] ints
 
 // SVGF g-buffers, bytes per pixel: normal + depth (float4), mesh + triangle id (int2), previous screen position (float2)
@@ -265,7 +264,7 @@ int check_ready(rt_context * ctx, const char * caller, int needs) {
 
 // The pixels a render call covers: rt_set_pixel_range's (offset, count) -- the rest of the frame for a negative count --
 // or, in tile mode, local pixels 0 .. count-1, which rt_map_pixel maps to this context's tiles.
-static int resolve_pixel_range(rt_context * ctx, const char * caller, int * out_offset, int * out_count) {
+int resolve_pixel_range(rt_context * ctx, const char * caller, int * out_offset, int * out_count) {
 	const RtParams & p = ctx->params;
 	const int frame = p.screen_width * p.screen_height;
 	int offset = ctx->pixel_offset, count = ctx->pixel_count < 0 ? frame - offset : ctx->pixel_count;
@@ -1356,6 +1355,28 @@ static int sync_svgf(rt_context * ctx) {
 	return RT_OK;
 }
 
+// The second-moment image exists exactly while the estimate is on and the frame has a size; it starts from zeros (w == 0: no sample has reached the pixel).
+// The caller has quiesced the context.
+static int sync_noise_moments(rt_context * ctx) {
+	const bool want = ctx->noise_estimate && ctx->frame_pixels > 0;
+	if (want && !ctx->noise_moments) {
+		int s = device_alloc(ctx, &ctx->noise_moments, ctx->frame_pixels * 16); if (s) return s;
+		RT_HIP(ctx, hipMemset(ctx->noise_moments, 0, ctx->frame_pixels * 16));
+	} else if (!want && ctx->noise_moments) { device_free(ctx, ctx->noise_moments); ctx->noise_moments = nullptr; }
+	return RT_OK;
+}
+// A change of the pixel set: the moments of pixels the context no longer renders would go stale beside means that another rank's image replaces.
+static int noise_moments_reset(rt_context * ctx) {
+	if (!ctx->noise_moments) return RT_OK;
+	(void)hipSetDevice(ctx->device);
+	RT_HIP(ctx, quiesce(ctx));
+	RT_HIP(ctx, hipMemset(ctx->noise_moments, 0, ctx->frame_pixels * 16));
+	return RT_OK;
+}
+// What the accumulate launchers get as `moments` for a launch under parameter block p: the image while the estimate is on and the launch is not an SVGF frame's
+// (whose accumulators are the filter's ping-pong images), else null -- the plain kernels, as before.
+float4 * noise_moments_for(const rt_context * ctx, const RtParams & p) { return p.config.enable_svgf ? nullptr : (float4 *)ctx->noise_moments; }
+
 int rt_resize(rt_context * ctx, int width, int height) {
 	RT_REQUIRE(ctx, ctx && width > 0 && height > 0, "rt_resize: invalid size");
 	(void)hipSetDevice(ctx->device);
@@ -1378,9 +1399,10 @@ int rt_resize(rt_context * ctx, int width, int height) {
 	int s = device_alloc(ctx, &ctx->final_image, ctx->frame_pixels * 16); if (s) return s;
 	RT_HIP(ctx, hipMemsetAsync(ctx->final_image, 0, ctx->frame_pixels * 16, ctx->stream));
 	ctx->params.final_image = (float4 *)ctx->final_image;
+	device_free(ctx, ctx->noise_moments); ctx->noise_moments = nullptr;
 	if ((s = sync_aovs(ctx))) return s;
 	if ((s = sync_svgf(ctx))) return s;
-	return RT_OK;
+	return sync_noise_moments(ctx);
 }
 
 int rt_set_camera(rt_context * ctx, const rt_camera * camera) {
@@ -1418,6 +1440,7 @@ int rt_set_config(rt_context * ctx, const rt_gpu_config * config) {
 
 int rt_set_pixel_range(rt_context * ctx, int pixel_offset, int pixel_count) {
 	RT_REQUIRE(ctx, ctx && pixel_offset >= 0, "rt_set_pixel_range: invalid argument");
+	if (ctx->pixel_offset != pixel_offset || ctx->pixel_count != pixel_count || ctx->params.tile_pixels != 0) { int s = noise_moments_reset(ctx); if (s) return s; }
 	ctx->pixel_offset = pixel_offset;
 	ctx->pixel_count  = pixel_count;
 	ctx->params.tile_pixels = 0;
@@ -1426,6 +1449,7 @@ int rt_set_pixel_range(rt_context * ctx, int pixel_offset, int pixel_count) {
 
 int rt_set_pixel_tiles(rt_context * ctx, int tile_pixels, int first_tile, int tile_stride) {
 	RT_REQUIRE(ctx, ctx && tile_pixels > 0 && first_tile >= 0 && tile_stride > 0 && first_tile < tile_stride, "rt_set_pixel_tiles: invalid argument");
+	if (ctx->params.tile_pixels != tile_pixels || ctx->params.tile_first != first_tile || ctx->params.tile_stride != tile_stride) { int s = noise_moments_reset(ctx); if (s) return s; }
 	ctx->params.tile_pixels = tile_pixels;
 	ctx->params.tile_first  = first_tile;
 	ctx->params.tile_stride = tile_stride;
@@ -1865,7 +1889,7 @@ static int stream_complete(rt_context * ctx, const StreamSubmission * subs, int 
 		RtParams pa = p;
 		pa.tile_pixels = head.tile_pixels; pa.tile_first = head.tile_first; pa.tile_stride = head.tile_stride;
 		span_mark(ctx, SPAN_ACCUMULATE, st);
-		rt_launch_accumulate_group(pa, group, head.range_offset, head.range_count, st);
+		rt_launch_accumulate_group(pa, group, head.range_offset, head.range_count, st, noise_moments_for(ctx, pa));
 		span_mark(ctx, SPAN_ACCUMULATE, st);
 		first = k;
 	}
@@ -2216,7 +2240,7 @@ int rt_render_samples(rt_context * ctx, int sample_index, int sample_count) {
 	const bool deferred = p.config.enable_svgf && ctx->defer_filter; // rt_filter_frame does the rest once the ranks have exchanged their tiles
 	if (deferred) { }
 	else if (p.config.enable_svgf) { p.taa_frame_prev = ctx->params.taa_frame_prev; p.taa_frame_next = ctx->params.taa_frame_next; rt_launch_svgf_taa(p, sample_index, st); if (p.config.enable_taa) std::swap(ctx->params.taa_frame_prev, ctx->params.taa_frame_next); }
-	else rt_launch_accumulate(p, float(sample_index), range_offset, range_count, st);
+	else rt_launch_accumulate(p, float(sample_index), range_offset, range_count, st, noise_moments_for(ctx, p));
 	stage_mark(ctx, STAGE_END, st);
 
 	// aovs_clear_to_zero (Integrator.cpp:379-385)
@@ -2403,6 +2427,79 @@ int rt_framebuffer_device_ptr(rt_context * ctx, void ** out_ptr, size_t * out_by
 }
 
 int rt_screen_pitch(rt_context * ctx) { return ctx ? ctx->params.screen_pitch : 0; }
+
+// ---- noise estimate ---------------------------------------------------------------------------------
+
+int rt_set_noise_estimate(rt_context * ctx, int enable) {
+	RT_REQUIRE(ctx, ctx, "rt_set_noise_estimate: NULL context");
+	RT_REQUIRE(ctx, enable == 0 || enable == 1, "rt_set_noise_estimate: enable must be 0 or 1");
+	(void)hipSetDevice(ctx->device);
+	RT_HIP(ctx, quiesce(ctx));   // the accumulate launches in flight were enqueued with or without the image
+	ctx->noise_estimate = enable != 0;
+	int s = sync_noise_moments(ctx); if (s) return s;
+	if (ctx->noise_moments) RT_HIP(ctx, hipMemset(ctx->noise_moments, 0, ctx->frame_pixels * 16));
+	return RT_OK;
+}
+int rt_get_noise_estimate(const rt_context * ctx) { return ctx && ctx->noise_estimate ? 1 : 0; }
+
+int rt_read_noise_moments(rt_context * ctx, float * dst) {
+	RT_REQUIRE(ctx, ctx && dst, "rt_read_noise_moments: NULL argument");
+	(void)hipSetDevice(ctx->device);
+	if (!ctx->noise_moments) return fail(ctx, RT_ERROR_NOT_READY, "rt_read_noise_moments: the noise estimate is off (rt_set_noise_estimate) or rt_resize was not called");
+	RT_HIP(ctx, quiesce(ctx));
+	RT_HIP(ctx, hipMemcpy(dst, ctx->noise_moments, ctx->frame_pixels * 16, hipMemcpyDeviceToHost));
+	return RT_OK;
+}
+
+// kernel_noise_cells on two pitched float4 images of the context's frame size, already on the device (rt_estimate_noise: the RADIANCE accumulator and the moments
+// image; rt_probes.hip: the caller's), on the main stream, which the caller has drained. Shared so that the probe and the entry point cannot differ.
+int noise_estimate_images(rt_context * ctx, const char * caller, const float4 * mean, const float4 * moments, float floor, rt_noise_estimate * out,
+                          double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, size_t cell_capacity, float * pixel_map) {
+	const RtParams & p = ctx->params;
+	const int cells_x = (p.screen_width + RT_NOISE_CELL - 1) / RT_NOISE_CELL, cells_y = (p.screen_height + RT_NOISE_CELL - 1) / RT_NOISE_CELL;
+	const size_t cells = size_t(cells_x) * cells_y;
+	if (cell_capacity < cells) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: cell_capacity %zu is below the %d x %d cells of the frame", caller, cell_capacity, cells_x, cells_y);
+	void * dev_sums = nullptr, * dev_counts = nullptr, * dev_map = nullptr;
+	auto release = [&] { device_free(ctx, dev_sums); device_free(ctx, dev_counts); device_free(ctx, dev_map); };
+	int s = device_alloc(ctx, &dev_sums, cells * 8);
+	if (!s) s = device_alloc(ctx, &dev_counts, cells * 8);   // counts, then non-finite counts
+	if (!s && pixel_map) s = device_alloc(ctx, &dev_map, ctx->frame_pixels * 4);
+	if (s) { release(); return s; }
+	std::vector<float> map_host;
+	hipError_t e = hipSuccess;
+	if (dev_map) {   // the padding columns, which the kernel leaves alone, read as pixels that take no part
+		map_host.assign(ctx->frame_pixels, -1.0f);
+		e = hipMemcpyAsync(dev_map, map_host.data(), ctx->frame_pixels * 4, hipMemcpyHostToDevice, ctx->stream);
+	}
+	if (e == hipSuccess) {
+		rt_launch_noise_cells(mean, moments, p.screen_width, p.screen_height, p.screen_pitch, floor, (float *)dev_map, (double *)dev_sums, (int *)dev_counts, (int *)dev_counts + cells, ctx->stream);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+	if (e == hipSuccess) e = hipMemcpy(cell_sums, dev_sums, cells * 8, hipMemcpyDeviceToHost);
+	if (e == hipSuccess) e = hipMemcpy(cell_counts, dev_counts, cells * 4, hipMemcpyDeviceToHost);
+	if (e == hipSuccess) e = hipMemcpy(cell_nonfinite, (int *)dev_counts + cells, cells * 4, hipMemcpyDeviceToHost);
+	if (e == hipSuccess && dev_map) e = hipMemcpy(pixel_map, dev_map, ctx->frame_pixels * 4, hipMemcpyDeviceToHost);
+	release();
+	if (e != hipSuccess) return fail(ctx, RT_ERROR_HIP, "%s: the noise kernel or its copies failed: %s", caller, hipGetErrorString(e));
+	out->cells_x = cells_x; out->cells_y = cells_y; out->pixels = 0; out->nonfinite_pixels = 0; out->mean = 0.0;
+	double sum = 0.0;   // in cell order, in double: the one order every caller sees
+	for (size_t c = 0; c < cells; c++) { sum += cell_sums[c]; out->pixels += cell_counts[c]; out->nonfinite_pixels += cell_nonfinite[c]; }
+	if (out->pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "%s: no pixel takes part yet (two samples past sample 0 are needed: w >= 2)", caller);
+	out->mean = sum / double(out->pixels);
+	return RT_OK;
+}
+
+int rt_estimate_noise(rt_context * ctx, float floor, rt_noise_estimate * out, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, size_t cell_capacity, float * pixel_map) {
+	RT_REQUIRE(ctx, ctx, "rt_estimate_noise: NULL context");
+	RT_REQUIRE(ctx, out && cell_sums && cell_counts && cell_nonfinite, "rt_estimate_noise: NULL argument");
+	RT_REQUIRE(ctx, floor > 0.0f && floor < __builtin_huge_valf(), "rt_estimate_noise: floor must be finite and positive");
+	(void)hipSetDevice(ctx->device);
+	if (!ctx->noise_moments || !ctx->aov_buffers[RT_AOV_RADIANCE][1]) return fail(ctx, RT_ERROR_NOT_READY, "rt_estimate_noise: the noise estimate is off (rt_set_noise_estimate) or rt_resize was not called");
+	RT_HIP(ctx, quiesce(ctx));
+	return noise_estimate_images(ctx, "rt_estimate_noise", (const float4 *)ctx->aov_buffers[RT_AOV_RADIANCE][1], (const float4 *)ctx->noise_moments, floor, out,
+	                             cell_sums, cell_counts, cell_nonfinite, cell_capacity, pixel_map);
+}
 
 int rt_read_luts(rt_context * ctx, float * dielectric_dir_enter, float * dielectric_dir_leave, float * dielectric_enter, float * dielectric_leave, float * conductor_dir, float * conductor) {
 	RT_REQUIRE(ctx, ctx, "rt_read_luts: NULL context");

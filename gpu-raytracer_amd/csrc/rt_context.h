@@ -13,6 +13,7 @@
 // Why: a wavefront pass is a chain of ~40 launches whose deep bounces are too small to fill 256 CUs
 // and whose persistent trace launches each end in a tail; a second sample's kernels fill those holes.
 #define RT_MAX_SAMPLE_SLOTS 8
+#define RT_MAX_BATCH_SAMPLES 16
 
 // The queues of one wavefront, `capacity` entries each: two trace queues (this bounce's and the next), one per material,
 // one of shadow rays. Each scheduler owns one set (SampleSlot, PathStream); queues_allocate / queues_free handle a set.
@@ -198,6 +199,10 @@ struct rt_context {
 	void * final_image = nullptr;
 	void * svgf_buffers[16] = { }; bool svgf_allocated = false;   // [15]: RtParams::svgf_young_pixels
 	size_t frame_pixels = 0; // pitch * height
+	// noise estimate (rt_set_noise_estimate): (M2_r, M2_g, M2_b, w) per pixel beside the RADIANCE accumulator, kept by the ..._moments
+	// accumulate kernels while the estimate is on and SVGF is off; null while it is off (or before rt_resize)
+	bool noise_estimate = false;
+	void * noise_moments = nullptr;
 
 	// frame exchange of the tile split (rt_comm_*): this context's rank in a group of `world` contexts, each on its own GPU
 	// (RCCL communicator) or, for tests on one GPU, several in one process (peer copies)
@@ -237,6 +242,7 @@ hipError_t quiesce(rt_context * ctx);
 hipError_t main_waits_for_samples(rt_context * ctx);
 RtParams slot_params(const rt_context * ctx, const SampleSlot & slot, int index);
 int check_ready(rt_context * ctx, const char * caller, int needs);
+int resolve_pixel_range(rt_context * ctx, const char * caller, int * out_offset, int * out_count);
 int sky_tables_build(rt_context * ctx, const char * caller);
 int sky_sampling_prepare(rt_context * ctx, const char * caller);
 int ensure_queues(rt_context * ctx, int slot_index = 0, size_t pixels = 0);
@@ -244,6 +250,9 @@ int ensure_luts(rt_context * ctx);
 int stream_create(rt_context * ctx);
 RtParams stream_params(const rt_context * ctx, int iteration);
 int stream_sync_tlas(rt_context * ctx);
+float4 * noise_moments_for(const rt_context * ctx, const RtParams & p);
+int noise_estimate_images(rt_context * ctx, const char * caller, const float4 * mean, const float4 * moments, float floor, rt_noise_estimate * out,
+                          double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, size_t cell_capacity, float * pixel_map);
 }
 #pragma GCC visibility pop
 

@@ -697,6 +697,72 @@ int rt_shade_rays(rt_context * ctx, int merged, int step, int sample_index, int 
 	return probe.read(gbuffer_screen_position_prev, g_sp, pixels * 8);
 }
 
+// rt_accumulate_frames: the accumulate launch (rt_launch_accumulate or rt_launch_accumulate_group, as rt_render_samples and stream_complete call them) on explicit
+// images. The parameter block is the context's with every AOV but RADIANCE taken away, RADIANCE's frames and accumulator and the final image replaced by
+// buffers of this call; the pixel set is the context's. Runs on the main stream after quiesce().
+int rt_accumulate_frames(rt_context * ctx, int merged, const int32_t * first_sample, const int32_t * sample_count, size_t submissions,
+                         float * frames, float * accumulator, float * moments, uint32_t sentinel, float * final_image) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_accumulate_frames: NULL context");
+	RT_REQUIRE(ctx, merged == 0 || merged == 1, "rt_accumulate_frames: merged must be 0 (one batch) or 1 (a group of submissions)");
+	RT_REQUIRE(ctx, first_sample && sample_count && frames && accumulator && final_image, "rt_accumulate_frames: NULL array");
+	RT_REQUIRE(ctx, submissions >= 1 && submissions <= size_t(merged ? RT_ACCUMULATE_GROUP : 1), merged ? "rt_accumulate_frames: 1 to RT_ACCUMULATE_GROUP submissions" : "rt_accumulate_frames: the batch form takes one submission");
+	size_t total = 0;
+	for (size_t k = 0; k < submissions; k++) {
+		RT_REQUIRE(ctx, first_sample[k] >= 0 && sample_count[k] >= 1 && sample_count[k] <= RT_STREAM_SAMPLE_SLOTS, "rt_accumulate_frames: a first sample below 0 or a sample count outside [1, 512]");
+		RT_REQUIRE(ctx, merged || sample_count[k] <= RT_MAX_BATCH_SAMPLES, "rt_accumulate_frames: a batch holds at most 16 samples");
+		RT_REQUIRE(ctx, size_t(first_sample[k]) + size_t(sample_count[k]) <= size_t(1) << 24, "rt_accumulate_frames: sample indices must stay below 2^24");
+		total += size_t(sample_count[k]);
+	}
+	(void)hipSetDevice(ctx->device);
+	const size_t frame_pixels = ctx->frame_pixels;
+	if (frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_accumulate_frames: rt_resize was not called");
+	RT_REQUIRE(ctx, total <= size_t(RT_STREAM_SAMPLE_SLOTS) && total * frame_pixels < size_t(1) << 30, "rt_accumulate_frames: at most 512 samples and fewer than 2^30 pixels in all");
+	int range_offset = 0, range_count = 0;
+	int s = resolve_pixel_range(ctx, "rt_accumulate_frames", &range_offset, &range_count); if (s) return s;
+	RT_HIP(ctx, quiesce(ctx));
+
+	Probe probe(ctx, "rt_accumulate_frames");
+	float4 * dev_frames = probe.array<float4>(total * frame_pixels, frames);
+	float4 * dev_accumulator = probe.array<float4>(frame_pixels, accumulator);
+	float4 * dev_moments = moments ? probe.array<float4>(frame_pixels, moments) : nullptr;
+	probe.staging.assign(frame_pixels * 4, sentinel);
+	float4 * dev_final = (float4 *)probe.array<uint32_t>(frame_pixels * 4, probe.staging.data());
+	if ((s = probe.allocated())) return s;
+
+	RtParams p = ctx->params;
+	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = p.aovs[a].accumulator = nullptr;
+	p.aovs[RT_AOV_RADIANCE].framebuffer = dev_frames; p.aovs[RT_AOV_RADIANCE].accumulator = dev_accumulator;
+	p.final_image = dev_final;
+	if (merged) {
+		RtAccumulateGroup group; group.count = int(submissions);
+		for (int k = 0, base = 0; k < group.count; k++) { group.first_sample[k] = first_sample[k]; group.sample_count[k] = sample_count[k]; group.slot_base[k] = base; base += sample_count[k]; }
+		for (int k = group.count; k < RT_ACCUMULATE_GROUP; k++) group.first_sample[k] = group.sample_count[k] = group.slot_base[k] = 0;
+		rt_launch_accumulate_group(p, group, range_offset, range_count, ctx->stream, dev_moments);
+	} else {
+		p.batch_samples = sample_count[0];
+		rt_launch_accumulate(p, float(first_sample[0]), range_offset, range_count, ctx->stream, dev_moments);
+	}
+	if ((s = probe.finish())) return s;
+	if ((s = probe.read(frames, dev_frames, total * frame_pixels * 16)) || (s = probe.read(accumulator, dev_accumulator, frame_pixels * 16))) return s;
+	if (moments && (s = probe.read(moments, dev_moments, frame_pixels * 16))) return s;
+	return probe.read(final_image, dev_final, frame_pixels * 16);
+}
+
+int rt_estimate_noise_images(rt_context * ctx, const float * mean, const float * moments, float floor, rt_noise_estimate * out, double * cell_sums,
+                             int32_t * cell_counts, int32_t * cell_nonfinite, size_t cell_capacity, float * pixel_map) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_estimate_noise_images: NULL context");
+	RT_REQUIRE(ctx, mean && moments && out && cell_sums && cell_counts && cell_nonfinite, "rt_estimate_noise_images: NULL argument");
+	RT_REQUIRE(ctx, floor > 0.0f && floor < __builtin_huge_valf(), "rt_estimate_noise_images: floor must be finite and positive");
+	(void)hipSetDevice(ctx->device);
+	if (ctx->frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_estimate_noise_images: rt_resize was not called");
+	RT_HIP(ctx, quiesce(ctx));
+	Probe probe(ctx, "rt_estimate_noise_images");
+	float4 * dev_mean = probe.array<float4>(ctx->frame_pixels, mean);
+	float4 * dev_moments = probe.array<float4>(ctx->frame_pixels, moments);
+	int s = probe.allocated(); if (s) return s;
+	return noise_estimate_images(ctx, "rt_estimate_noise_images", dev_mean, dev_moments, floor, out, cell_sums, cell_counts, cell_nonfinite, cell_capacity, pixel_map);
+}
+
 int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps) {
 	RT_REQUIRE(ctx, ctx && out_gbps && bytes >= 1024, "rt_measure_stream_bandwidth: invalid argument");
 	(void)hipSetDevice(ctx->device);

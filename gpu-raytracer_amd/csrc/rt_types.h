@@ -299,11 +299,17 @@ void rt_launch_ambient_occlusion(const RtParams & p, int sample_index, float ao_
 void rt_launch_trace_shadow_ao(const RtParams & p, hipStream_t stream);
 void rt_launch_sort(const RtParams & p, int bounce, int sample_index, hipStream_t stream);
 void rt_launch_material(const RtParams & p, int material_slot, int bounce, int sample_index, hipStream_t stream);
-void rt_launch_accumulate(const RtParams & p, float frames_accumulated, int pixel_offset, int pixel_count, hipStream_t stream);
+// moments (both accumulate launchers): null, or the (M2_r, M2_g, M2_b, w) image of rt_set_noise_estimate -- then the ..._moments kernel runs
+void rt_launch_accumulate(const RtParams & p, float frames_accumulated, int pixel_offset, int pixel_count, hipStream_t stream, float4 * moments = nullptr);
 #define RT_SVGF_YOUNG_HEADER 16
 #define RT_ACCUMULATE_GROUP 8
 struct RtAccumulateGroup { int count; int first_sample[RT_ACCUMULATE_GROUP], sample_count[RT_ACCUMULATE_GROUP], slot_base[RT_ACCUMULATE_GROUP]; };
-void rt_launch_accumulate_group(const RtParams & p, const RtAccumulateGroup & group, int pixel_offset, int pixel_count, hipStream_t stream);
+void rt_launch_accumulate_group(const RtParams & p, const RtAccumulateGroup & group, int pixel_offset, int pixel_count, hipStream_t stream, float4 * moments = nullptr);
+// The noise estimate (kernel_noise_cells): one workgroup per RT_NOISE_CELL^2 pixels of width x height; mean and moments are pitched float4 images, pixel_map
+// (pitched floats) may be null, the three cell arrays hold ceil(width / 16) * ceil(height / 16) entries, row-major.
+#define RT_NOISE_CELL 16
+void rt_launch_noise_cells(const float4 * mean, const float4 * moments, int width, int height, int pitch, float floor, float * pixel_map,
+                           double * cell_sums, int * cell_counts, int * cell_nonfinite, hipStream_t stream);
 // mark(user, k, stream), if given, is called before and after kernel k = 0 reproject, 1 variance, 2 a-trous (each pass), 3 finalize, 4 TAA, 5 TAA finalize
 void rt_launch_svgf_taa(const RtParams & p, int sample_index, hipStream_t stream, void (*mark)(void * user, int svgf_kernel, hipStream_t stream) = nullptr, void * user = nullptr);
 void rt_launch_random(const RtParams & p, int dimension, const unsigned * pixel_indices, int count, unsigned bounce, unsigned sample_index, float2 * out, hipStream_t stream);

@@ -106,6 +106,13 @@ struct CPUConfig {
 	// Sky importance sampling for next-event estimation (rt_set_sky_sampling): 0 = off, the reference's estimator; (0, 1] = the sky's share
 	// of the light samples when the scene has emitters (all of them when it has none). Same expectation, less noise under a sky with a sun.
 	float sky_sampling = 0.0f;
+	// Noise estimate. noise_target: 0 = off; > 0 = the device keeps second moments beside the radiance mean (rt_set_noise_estimate) and the
+	// command-line renderer and Pathtracer.render_until stop once the figure -- the noise_quantile quantile of the cells' mean relative standard error -- is at or
+	// below it, never before noise_min_samples samples. noise_floor: the floor of the luminance the error is taken relative to.
+	float noise_target = 0.0f;
+	int   noise_min_samples = 16;
+	double noise_quantile = 0.95;
+	float noise_floor = 1e-2f;
 	// Alpha-tested cut-outs from the albedo textures: 1 = every surface material whose albedo FILE has an alpha channel that is not constant gets an
 	// opacity mask from it (channel a, threshold 0.5; an explicit <bsdf type="mask"> wins). Read when a scene is loaded. 0: off, as the reference renders them.
 	int   alpha_masks = 0;

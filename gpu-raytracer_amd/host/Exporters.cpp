@@ -1,4 +1,5 @@
 #include "Exporters.h"
+#include <initializer_list>
 
 #include <cmath>
 #include <cstdint>
@@ -81,15 +82,15 @@ bool PPMExporter::save(const std::string & filename, int pitch, int width, int h
 	return fwrite(bytes.data(), 1, bytes.size(), file.f) == bytes.size();
 }
 
-bool EXRExporter::save(const std::string & filename, int pitch, int width, int height, const std::vector<Vector3> & data) {
-	Bytes out;
+// magic, version and the attributes of a scan-line file without compression: `names` (alphabetical, as the format requires) of one pixel type (1 HALF, 2 FLOAT)
+static void exr_header(Bytes & out, std::initializer_list<const char *> names, int pixel_type, int width, int height) {
 	const unsigned char magic_and_version[8] = { 0x76, 0x2f, 0x31, 0x01, 2, 0, 0, 0 };
 	out.raw(magic_and_version, 8);
 
 	Bytes channels;
-	for (const char * name : { "B", "G", "R" }) { // alphabetical, as the format requires
+	for (const char * name : names) {
 		channels.str(name);
-		channels.i32(1);            // pixel type HALF
+		channels.i32(pixel_type);
 		channels.u8(0); channels.u8(0); channels.u8(0); channels.u8(0); // pLinear + reserved
 		channels.i32(1); channels.i32(1); // x / y sampling
 	}
@@ -109,6 +110,28 @@ bool EXRExporter::save(const std::string & filename, int pitch, int width, int h
 	out.attribute("screenWindowCenter", "v2f", centre);
 	out.attribute("screenWindowWidth", "float", one);
 	out.u8(0); // end of header
+}
+
+bool EXRExporter::save_luminance(const std::string & filename, int pitch, int width, int height, const std::vector<float> & data) {
+	Bytes out;
+	exr_header(out, { "Y" }, 2, width, height);
+	size_t row_bytes   = size_t(width) * sizeof(float);
+	size_t chunk_bytes = 8 + row_bytes;
+	uint64_t first_chunk = out.data.size() + size_t(height) * 8;
+	for (int row = 0; row < height; row++) out.u64(first_chunk + uint64_t(row) * chunk_bytes);
+	for (int row = 0; row < height; row++) {
+		out.i32(row);
+		out.i32(int32_t(row_bytes));
+		out.raw(data.data() + size_t(height - 1 - row) * pitch, row_bytes); // file row 0 is the top of the image
+	}
+	File file(filename, "wb");
+	if (!file.f) return false;
+	return fwrite(out.data.data(), 1, out.data.size(), file.f) == out.data.size();
+}
+
+bool EXRExporter::save(const std::string & filename, int pitch, int width, int height, const std::vector<Vector3> & data) {
+	Bytes out;
+	exr_header(out, { "B", "G", "R" }, 1, width, height);
 
 	size_t row_bytes   = size_t(width) * 3 * sizeof(uint16_t);
 	size_t chunk_bytes = 8 + row_bytes;

@@ -16,6 +16,8 @@ namespace EXRExporter {
 	// Scan-line OpenEXR, channels B G R stored as 16-bit half, no compression -- what the
 	// reference's tinyexr call produces for its zero-initialised header
 	bool save(const std::string & filename, int pitch, int width, int height, const std::vector<Vector3> & data);
+	// One channel "Y" of 32-bit floats, same layout otherwise: `data` is one float per pixel at x + y * pitch (the noise map)
+	bool save_luminance(const std::string & filename, int pitch, int width, int height, const std::vector<float> & data);
 }
 
 namespace Exporters {

@@ -95,3 +95,17 @@ void FrameSplit::render_samples(int count) {
 	on_every_rank([this, count](int r) { ranks[r]->render_samples(count); });
 	exchange();
 }
+
+NoiseEstimate FrameSplit::noise(std::vector<float> * pixel_map) {
+	NoiseEstimate total;
+	std::vector<float> rank_map;
+	for (int r = 0; r < world(); r++) {
+		NoiseEstimate e = ranks[r]->noise(pixel_map ? &rank_map : nullptr, true);
+		if (r == 0) { total = e; if (pixel_map) *pixel_map = rank_map; continue; }
+		for (size_t c = 0; c < total.cell_sums.size(); c++) { total.cell_sums[c] += e.cell_sums[c]; total.cell_counts[c] += e.cell_counts[c]; total.cell_nonfinite[c] += e.cell_nonfinite[c]; }
+		total.nonfinite_pixels += e.nonfinite_pixels;
+		if (pixel_map) for (size_t i = 0; i < rank_map.size(); i++) if (rank_map[i] != -1.0f) (*pixel_map)[i] = rank_map[i];
+	}
+	grt_noise_summary(total.cell_sums.data(), total.cell_counts.data(), total.cell_sums.size(), cpu_config.noise_quantile, &total.mean, &total.figure, &total.pixels);
+	return total;
+}

@@ -43,6 +43,10 @@ struct FrameSplit {
 	void render();                   // one sample per pixel on every rank's tiles, then the exchange
 	void render_samples(int count);  // `count` samples as one wavefront per rank (plain path tracing), then the exchange
 
+	// The whole frame's estimate: the ranks own disjoint pixels, so their cell sums and counts are added (rank order) before the one summary function runs.
+	// pixel_map: every pixel from the rank that owns it.
+	NoiseEstimate noise(std::vector<float> * pixel_map = nullptr);
+
 	std::vector<float> read_framebuffer() { return ranks.front()->read_framebuffer(); }
 	void save_image(const std::string & filename) { ranks.front()->save_image(filename); }
 

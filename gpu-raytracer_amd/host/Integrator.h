@@ -55,6 +55,7 @@ struct Integrator {
 	int screen_width = 0, screen_height = 0, screen_pitch = 0;
 	int pixel_count = 0;
 	int sample_index = 0;
+	bool noise_estimate_wanted = false;   // the device keeps second moments (rt_set_noise_estimate) while this is set or cpu_config.noise_target > 0; applied by update()
 
 	// Multi-GPU: scan-order pixel range rendered by this integrator (default: all)
 	int pixel_range_offset = 0, pixel_range_count = -1;

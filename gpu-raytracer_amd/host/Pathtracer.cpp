@@ -1,4 +1,7 @@
 #include "Pathtracer.h"
+#include <algorithm>
+#include <cmath>
+#include <stdexcept>
 
 #include <cmath>
 #include <cstring>
@@ -326,4 +329,42 @@ void Pathtracer::render_samples(int count) {
 		count -= n;
 		if (count > 0) sample_index++;
 	}
+}
+
+int grt_noise_summary(const double * cell_sums, const int32_t * cell_counts, size_t cells, double quantile, double * out_mean, double * out_figure, long long * out_pixels) {
+	if (out_mean) *out_mean = 0.0;
+	if (out_figure) *out_figure = 0.0;
+	if (out_pixels) *out_pixels = 0;
+	if (!(quantile > 0.0 && quantile <= 1.0)) return -1;
+	double sum = 0.0; long long pixels = 0;
+	std::vector<double> means;
+	for (size_t c = 0; c < cells; c++) {
+		if (cell_counts[c] <= 0) continue;
+		sum += cell_sums[c]; pixels += cell_counts[c];
+		means.push_back(cell_sums[c] / double(cell_counts[c]));
+	}
+	if (out_pixels) *out_pixels = pixels;
+	if (means.empty()) return 1;
+	std::sort(means.begin(), means.end());
+	size_t rank = size_t(std::ceil(quantile * double(means.size())));
+	rank = rank < 1 ? 1 : rank > means.size() ? means.size() : rank;
+	if (out_mean) *out_mean = sum / double(pixels);
+	if (out_figure) *out_figure = means[rank - 1];
+	return 0;
+}
+
+NoiseEstimate Pathtracer::noise(std::vector<float> * pixel_map, bool allow_empty) {
+	require_device();
+	if (!rt_get_noise_estimate(ctx)) throw std::runtime_error("Pathtracer::noise: the noise estimate is off (set noise_estimate_wanted or cpu_config.noise_target before update())");
+	NoiseEstimate e;
+	e.cells_x = (screen_width + 15) / 16; e.cells_y = (screen_height + 15) / 16;
+	const size_t cells = size_t(e.cells_x) * e.cells_y;
+	e.cell_sums.assign(cells, 0.0); e.cell_counts.assign(cells, 0); e.cell_nonfinite.assign(cells, 0);
+	if (pixel_map) pixel_map->assign(size_t(screen_pitch) * screen_height, -1.0f);
+	rt_noise_estimate out = { };
+	int status = rt_estimate_noise(ctx, cpu_config.noise_floor, &out, e.cell_sums.data(), e.cell_counts.data(), e.cell_nonfinite.data(), cells, pixel_map ? pixel_map->data() : nullptr);
+	if (!(status == RT_ERROR_NOT_READY && allow_empty && out.cells_x == e.cells_x)) check(status);   // (an empty frame's arrays and counters are filled before the refusal)
+	e.nonfinite_pixels = out.nonfinite_pixels;
+	grt_noise_summary(e.cell_sums.data(), e.cell_counts.data(), cells, cpu_config.noise_quantile, &e.mean, &e.figure, &e.pixels);
+	return e;
 }

@@ -5,6 +5,19 @@
 #pragma once
 #include "Integrator.h"
 
+// The noise estimate of a frame: per cell of 16 x 16 pixels the sum of the pixels' relative standard error e_p, their number and the number of
+// non-finite pixels, as rt_estimate_noise returns them; `mean` is e_p's mean over the frame and `figure` the cpu_config.noise_quantile quantile of the cells'
+// means (cells with a count above 0, nearest rank) -- what a noise target is compared with.
+struct NoiseEstimate {
+	int cells_x = 0, cells_y = 0;
+	std::vector<double> cell_sums; std::vector<int32_t> cell_counts, cell_nonfinite;
+	long long pixels = 0, nonfinite_pixels = 0;
+	double mean = 0.0, figure = 0.0;
+};
+// mean and figure from cell arrays, for C++ and Python alike. The mean: the sums added in cell order over the counts' total. The figure: the means sum / count of
+// the cells with count > 0, sorted; entry ceil(quantile * m) of the m (1-based, at least 1). 0: fine; 1: no cell has a count (both 0); -1: quantile outside (0, 1].
+extern "C" int grt_noise_summary(const double * cell_sums, const int32_t * cell_counts, size_t cells, double quantile, double * out_mean, double * out_figure, long long * out_pixels);
+
 struct Pathtracer final : Integrator {
 	// Light sampling tables (reference: Pathtracer.cpp:384-534)
 	std::vector<int>   light_triangle_indices;
@@ -41,6 +54,10 @@ struct Pathtracer final : Integrator {
 	// update(); render(); `count` times. sample_index ends on the last sample rendered, so the next
 	// update() continues the progression where the reference's loop would be.
 	void render_samples(int count);
+	// The estimate of what has been accumulated so far (completes the work in flight). Needs the device estimate on: noise_estimate_wanted or
+	// cpu_config.noise_target > 0 before the update() of sample 0. pixel_map: e_p per pixel at x + y * pitch, -1 where the pixel takes no part, -2 non-finite.
+	// Throws when the estimate is off; a frame without a participating pixel (allow_empty) returns pixels == 0 instead of throwing.
+	NoiseEstimate noise(std::vector<float> * pixel_map = nullptr, bool allow_empty = false);
 
 	void calc_light_power();
 	void geometry_was_rebuilt() override { if (scene.has_lights) calc_light_power(); }   // light_triangle_indices name device triangles

@@ -84,6 +84,22 @@ int grt_config_set(const char * key, double value) {
 		if (!(value == 0.0 || (value > 0.0 && value <= 1.0))) { g_host_error = "sky_sampling must be 0 (off) or in (0, 1]"; return -1; }
 		cpu_config.sky_sampling = float(value);
 	}
+	else if (k == "noise_target") {   // 0 (off) or a finite positive relative error
+		if (!(value >= 0.0 && value < 1e30)) { g_host_error = "noise_target must be 0 (off) or finite and positive"; return -1; }
+		cpu_config.noise_target = float(value);
+	}
+	else if (k == "noise_min_samples") {
+		if (!(value >= 2.0 && value <= double(1 << 24)) || value != double(int(value))) { g_host_error = "noise_min_samples must be a whole number in [2, 2^24]"; return -1; }
+		cpu_config.noise_min_samples = int(value);
+	}
+	else if (k == "noise_quantile") {
+		if (!(value > 0.0 && value <= 1.0)) { g_host_error = "noise_quantile must be in (0, 1]"; return -1; }
+		cpu_config.noise_quantile = value;
+	}
+	else if (k == "noise_floor") {
+		if (!(value > 0.0 && value < 1e30)) { g_host_error = "noise_floor must be finite and positive"; return -1; }
+		cpu_config.noise_floor = float(value);
+	}
 	else if (k == "static_reseat_distance")              cpu_config.static_reseat_distance = float(value);
 	else if (k == "static_mesh_copy_limit_mb")           cpu_config.static_mesh_copy_limit_mb = int(value);
 	else if (k == "static_copy_budget_mb")               cpu_config.static_copy_budget_mb = int(value);
@@ -105,6 +121,10 @@ double grt_config_get(const char * key) {
 	if (k == "alpha_masks")    return cpu_config.alpha_masks;
 	if (k == "delta_lights")   return cpu_config.delta_lights;
 	if (k == "delta_light_share") return cpu_config.delta_light_share;
+	if (k == "noise_target")      return cpu_config.noise_target;
+	if (k == "noise_min_samples") return cpu_config.noise_min_samples;
+	if (k == "noise_quantile")    return cpu_config.noise_quantile;
+	if (k == "noise_floor")       return cpu_config.noise_floor;
 	return -1.0;
 }
 
@@ -395,6 +415,32 @@ int grt_pathtracer_render_samples(void * pt, int count) {
 	GRT_TRY
 		as_pathtracer(pt)->render_samples(count);
 		return 0;
+	GRT_CATCH(-1)
+}
+// Noise estimate. set: takes effect at the next update(), which restarts the progression when it switches the estimate on.
+void grt_pathtracer_set_noise_estimate(void * pt, int enable) { as_integrator(pt)->noise_estimate_wanted = enable != 0; }
+static int noise_out(const NoiseEstimate & e, int * cells_xy, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, size_t cell_capacity, double * mean_figure, long long * pixels_nonfinite) {
+	if (cell_capacity < e.cell_sums.size()) { g_host_error = "noise: cell_capacity is below cells_x * cells_y"; return -1; }
+	cells_xy[0] = e.cells_x; cells_xy[1] = e.cells_y;
+	memcpy(cell_sums, e.cell_sums.data(), e.cell_sums.size() * 8); memcpy(cell_counts, e.cell_counts.data(), e.cell_counts.size() * 4); memcpy(cell_nonfinite, e.cell_nonfinite.data(), e.cell_nonfinite.size() * 4);
+	mean_figure[0] = e.mean; mean_figure[1] = e.figure; pixels_nonfinite[0] = e.pixels; pixels_nonfinite[1] = e.nonfinite_pixels;
+	return 0;
+}
+// cells_xy: 2 ints; the cell arrays: cell_capacity >= ceil(w / 16) * ceil(h / 16) entries; mean_figure: 2 doubles; pixels_nonfinite: 2 long longs; pixel_map: NULL or pitch * height floats
+int grt_pathtracer_noise(void * pt, int * cells_xy, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, size_t cell_capacity, double * mean_figure, long long * pixels_nonfinite, float * pixel_map) {
+	GRT_TRY
+		std::vector<float> map;
+		NoiseEstimate e = as_pathtracer(pt)->noise(pixel_map ? &map : nullptr);
+		if (pixel_map) memcpy(pixel_map, map.data(), map.size() * 4);
+		return noise_out(e, cells_xy, cell_sums, cell_counts, cell_nonfinite, cell_capacity, mean_figure, pixels_nonfinite);
+	GRT_CATCH(-1)
+}
+int grt_frame_split_noise(void * split, int * cells_xy, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, size_t cell_capacity, double * mean_figure, long long * pixels_nonfinite, float * pixel_map) {
+	GRT_TRY
+		std::vector<float> map;
+		NoiseEstimate e = ((FrameSplit *)split)->noise(pixel_map ? &map : nullptr);
+		if (pixel_map) memcpy(pixel_map, map.data(), map.size() * 4);
+		return noise_out(e, cells_xy, cell_sums, cell_counts, cell_nonfinite, cell_capacity, mean_figure, pixels_nonfinite);
 	GRT_CATCH(-1)
 }
 int grt_pathtracer_resize(void * pt, int width, int height) {

@@ -20,6 +20,7 @@
 #include "../AO.h"
 #include "../FrameSplit.h"
 #include "../Pathtracer.h"
+#include "../Exporters.h"
 
 namespace {
 
@@ -37,6 +38,7 @@ struct CommandLine {
 	int  batch  = 4;
 	bool help   = false;
 	bool print_config = false;
+	std::string noise_map;      // --noise-map
 };
 
 [[noreturn]] void die(const std::string & message) {
@@ -103,6 +105,17 @@ std::vector<Option> make_options(CommandLine & cl) {
 		if (!(p == 0.0f || (p > 0.0f && p <= 1.0f))) die("--delta-light-share must be 0 (by power) or in (0, 1]");
 		cpu_config.delta_light_share = p;
 	} });
+	o.push_back({ nullptr, "noise-target", "Renders until the noise figure (DESIGN.md 7.5) is at or below <e>; -N becomes the cap on the sample count. The figure is asked for at burst boundaries only: the call drains the wavefront", 1, [](const char * v) {
+		float e = parse_float(v, "--noise-target");
+		if (!(e > 0.0f && e < 1e30f)) die("--noise-target must be finite and positive");
+		cpu_config.noise_target = e;
+	} });
+	o.push_back({ nullptr, "noise-min-samples", "With --noise-target: never stop below this many samples (default 16)", 1, [](const char * v) {
+		int n = parse_int(v, "--noise-min-samples");
+		if (n < 2) die("--noise-min-samples must be at least 2");
+		cpu_config.noise_min_samples = n;
+	} });
+	o.push_back({ nullptr, "noise-map", "Writes the per-pixel relative standard error as a one-channel EXR (pixels that take no part are 0)", 1, [&cl](const char * v) { cl.noise_map = v; } });
 	o.push_back({ nullptr, "force-rebuild", "BVH will not be loaded from disk but rebuilt from scratch", 0, [](const char *) { cpu_config.bvh_force_rebuild = true; } });
 	o.push_back({ "O",  "optimize",    "Enables or disables BVH optimization post-processing step", 1, [](const char * v) { cpu_config.enable_bvh_optimization = parse_bool(v); } });
 	o.push_back({ "Ot", "opt-time",    "Sets time limit for BVH optimization (milliseconds, as the reference stores it)", 1, [](const char * v) { cpu_config.bvh_optimizer_max_time = parse_int(v, "--opt-time"); } });
@@ -196,6 +209,34 @@ void parse_command_line(int argc, char ** argv, CommandLine & cl) {
 	}
 }
 
+// --noise-target / --noise-map: asked at burst boundaries (every `interval` samples), since the answer drains the wavefront
+struct NoiseStop {
+	bool active = false, warned = false, reached = false;
+	int interval = 1, next_check = 0;
+	NoiseEstimate last; bool have = false;
+	template<typename Renderer> bool should_stop(Renderer & r, int sample_index) {   // after a render call
+		if (!active || sample_index < cpu_config.noise_min_samples || sample_index < next_check) return false;
+		next_check = sample_index + interval;
+		last = r.noise(); have = true;
+		reached = last.pixels > 0 && last.figure <= double(cpu_config.noise_target);
+		return reached;
+	}
+	template<typename Renderer> void report(Renderer & r, int sample_index, const std::string & map_file, int pitch, int width, int height) {
+		if (active) {
+			if (!reached) { last = r.noise(); have = true; reached = last.pixels > 0 && last.figure <= double(cpu_config.noise_target); }
+			printf("Noise: figure %.6g (mean %.6g, target %.6g) after sample %d; %s\n", last.figure, last.mean, double(cpu_config.noise_target), sample_index,
+			       reached ? "target reached" : "stopped at the sample cap");
+		}
+		if (!map_file.empty()) {
+			std::vector<float> map;
+			r.noise(&map);
+			for (float & v : map) if (v < 0.0f) v = 0.0f;
+			if (!EXRExporter::save_luminance(map_file, pitch, width, height, map)) die("failed to write '" + map_file + "'");
+			printf("Wrote %s\n", map_file.c_str());
+		}
+	}
+};
+
 double seconds_since(std::chrono::steady_clock::time_point t0) {
 	return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -212,21 +253,31 @@ int main(int argc, char ** argv) {
 	try {
 		auto t0 = std::chrono::steady_clock::now();
 		Scene scene;
+		NoiseStop noise;
+		const bool noise_asked = cpu_config.noise_target > 0.0f || !cl.noise_map.empty();
+		if (noise_asked && (gpu_config.enable_svgf || cpu_config.integrator == IntegratorType::AO)) {   // neither keeps second moments
+			fprintf(stderr, "WARNING: --noise-target / --noise-map need plain path tracing (no SVGF, no AO integrator): ignored, rendering to -N\n");
+			cpu_config.noise_target = 0.0f; cl.noise_map.clear();
+		}
+		noise.active = cpu_config.noise_target > 0.0f;
+		if (!cl.noise_map.empty() && !noise.active) cpu_config.noise_target = 1e-30f;   // (keeps the moments; a target nothing reaches, and no stop is asked for)
 		if (cl.devices.size() > 1) { // one frame over several GPUs
 			if (cpu_config.integrator == IntegratorType::AO) die("--devices: the tile split exists for the path tracer");
 			FrameSplit split(cpu_config.initial_width, cpu_config.initial_height, scene, cl.devices);
 			printf("Initialization: %.0f ms (%d ranks)\n", seconds_since(t0) * 1e3, split.world());
 			auto t1 = std::chrono::steady_clock::now();
 			int target = cpu_config.output_sample_index;
+			noise.interval = 8 * cl.batch;
 			while (true) {
 				split.update(0.0f);
 				int remaining = target - split.sample_index() + 1;
 				if (cl.batch > 1 && split.sample_index() > 0 && remaining > 1) split.render_samples(remaining < cl.batch ? remaining : cl.batch);
 				else split.render();
-				if (split.sample_index() >= target) break;
+				if (split.sample_index() >= target || noise.should_stop(split, split.sample_index())) break;
 			}
 			split.read_framebuffer(); // waits for the devices
 			printf("Rendered sample %d at %dx%d in %.1f ms\n", split.sample_index(), split.front().screen_width, split.front().screen_height, seconds_since(t1) * 1e3);
+			noise.report(split, split.sample_index(), cl.noise_map, split.front().screen_pitch, split.front().screen_width, split.front().screen_height);
 			split.save_image(cpu_config.output_filename);
 			printf("Wrote %s\n", cpu_config.output_filename.c_str());
 			return 0;
@@ -246,6 +297,7 @@ int main(int argc, char ** argv) {
 		if (pathtracer && integrator->ctx && cl.batch > 1 && target + 1 > cl.batch && !gpu_config.enable_svgf) {
 			const long long submissions = (long long)(target + cl.batch) / cl.batch;
 			const long long burst = submissions < 8 ? submissions : 8;
+			noise.interval = int(burst) * cl.batch;
 			if (rt_set_frame_pipelining(integrator->ctx, 1) != RT_OK || rt_set_stream_batch(integrator->ctx, burst * cl.batch * (long long)cpu_config.initial_width * cpu_config.initial_height) != RT_OK)
 				die(std::string("ERROR: ") + rt_last_error(integrator->ctx));
 		}
@@ -257,11 +309,12 @@ int main(int argc, char ** argv) {
 			} else {
 				integrator->render();
 			}
-			if (integrator->sample_index >= target) break;
+			if (integrator->sample_index >= target || (pathtracer && noise.should_stop(*pathtracer, integrator->sample_index))) break;
 		}
 		integrator->read_framebuffer(); // waits for the device
 		double render_s = seconds_since(t1);
 		printf("Rendered sample %d at %dx%d in %.1f ms\n", integrator->sample_index, integrator->screen_width, integrator->screen_height, render_s * 1e3);
+		if (pathtracer) noise.report(*pathtracer, integrator->sample_index, cl.noise_map, integrator->screen_pitch, integrator->screen_width, integrator->screen_height);
 
 		integrator->save_image(cpu_config.output_filename);
 		printf("Wrote %s\n", cpu_config.output_filename.c_str());

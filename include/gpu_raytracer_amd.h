@@ -158,6 +158,8 @@ const char * rt_version(void);
  *  17  rt_upload_material_opacity, rt_read_material_opacity (additions only; alpha-tested opacity masks, off until a mask is uploaded)
  *      (still 17: rt_upload_delta_lights, rt_read_delta_lights, rt_sample_delta_lights -- new entry points and a record of their own, no
  *      existing struct or call changed; point, spot and directional emitters, off until a table is uploaded)
+ *      (still 17: rt_set_noise_estimate, rt_get_noise_estimate, rt_read_noise_moments, rt_estimate_noise, rt_accumulate_frames -- new entry points and a
+ *      result struct of their own; the per-pixel noise estimate, off by default)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
 #define RT_ABI_VERSION 17
 int rt_abi_version(void);
@@ -580,6 +582,38 @@ int rt_read_framebuffer(rt_context * ctx, float * dst);
 int rt_framebuffer_device_ptr(rt_context * ctx, void ** out_ptr, size_t * out_bytes);
 int rt_screen_pitch(rt_context * ctx);
 
+/* ---- noise estimate ------------------------------------------------------*/
+/* enable = 1: the accumulate step of every path-traced sample also keeps, per pixel and for RADIANCE only, Welford's second moment beside
+ * the running mean: one float4 (M2_r, M2_g, M2_b, w), w the number of samples it stands for. The mean, every accumulator and the final
+ * image stay what they are with the estimate off, to the bit. The moments follow AOV.h:35-46's quirk, by which sample 1 overwrites sample
+ * 0: samples 0 and 1 leave (0, 0, 0, 1), sample n >= 2 adds d * (fb - mean_new) with d = fb - mean_old and sets w = n. A restart at sample
+ * 0 therefore resets a pixel by itself; rt_resize frees the image with the other frame buffers and a CHANGE of the pixel set
+ * (rt_set_pixel_range, rt_set_pixel_tiles) zeroes it (w == 0: no sample ever reached the pixel -- another rank's tile is such a pixel).
+ * SVGF frames and the AO integrator keep no moments. Off by default; both values drain the context, and the image starts from zeros.    */
+int rt_set_noise_estimate(rt_context * ctx, int enable);
+int rt_get_noise_estimate(const rt_context * ctx);
+/* The moments image: pitch*height float4. RT_ERROR_NOT_READY while the estimate is off. Waits for the work in flight.                   */
+int rt_read_noise_moments(rt_context * ctx, float * dst);
+/* The estimate over cells of 16 x 16 pixels laid over width x height (edge cells clipped), cells_x = ceil(width / 16), row-major.
+ * A pixel takes part when w >= 2 and its mean and M2 are finite; with w >= 2 and anything not finite it is counted as non-finite and
+ * left out of the sums. Per pixel, in float32 and in this shape, with luminance(r, g, b) = 0.299 r + 0.587 g + 0.114 b (`luminance` of
+ * csrc/rt_shading.h, the Y of the shade and filter kernels):
+ *   v = (M2_r + M2_g) + M2_b;   e_p = sqrtf(v / (w * (w - 1.0f))) / fmaxf(luminance(mean), floor)
+ * -- the standard error of the mean over its brightness. cell_sums / cell_counts / cell_nonfinite (cell_capacity entries each, at least
+ * cells_x * cells_y): per cell the sum of e_p in double over its participating pixels (a fixed reduction tree: the same bits on every
+ * run), their number, and the number of non-finite pixels. pixel_map: NULL, or pitch*height floats: e_p, -1 where the pixel takes no
+ * part (the padding columns too), -2 where it is non-finite. out->mean: the cell sums added in cell order, in double, over out->pixels.
+ * Completes the work in flight. RT_ERROR_NOT_READY while the estimate is off or when no pixel takes part (the cell arrays are filled
+ * all the same); RT_ERROR_INVALID_ARG for a floor that is not finite and positive or a capacity that is too small.                      */
+typedef struct rt_noise_estimate {
+	int32_t cells_x, cells_y;
+	int64_t pixels;             /* participating */
+	int64_t nonfinite_pixels;
+	double  mean;               /* of e_p over the participating pixels */
+} rt_noise_estimate;
+int rt_estimate_noise(rt_context * ctx, float floor, rt_noise_estimate * out, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite,
+                      size_t cell_capacity, float * pixel_map);
+
 /* Kulla-Conty LUTs as computed on the device at first use (kernel_integrate_* /
  * kernel_average_*, CUDA/KullaConty.h:83-240): 16^3, 16^3, 16^2, 16^2, 32^2, 32 floats.
  * Any pointer may be NULL. Synchronous.                                                     */
@@ -727,6 +761,21 @@ int rt_shade_rays(rt_context * ctx, int merged, int step, int sample_index, int 
                   uint32_t * trace_out, uint32_t * shadow_out, int32_t * counters3,
                   uint32_t * aov_frames, uint32_t * gbuffer_normal_and_depth, uint32_t * gbuffer_mesh_id_and_triangle_id, uint32_t * gbuffer_screen_position_prev,
                   int32_t * stats);
+/* The accumulate launch on explicit images (synchronous): ONE launch of the production launcher -- rt_launch_accumulate (merged = 0: one
+ * submission, first_sample[0] the sample index the fold starts at, sample_count[0] <= 16 the samples of the batch) or
+ * rt_launch_accumulate_group (merged = 1: 1 .. 8 submissions folded in order, as the merged wavefront completes them) -- over the
+ * context's own pixel set (rt_set_pixel_range / rt_set_pixel_tiles). frames (in / out): the samples of all submissions, one after the
+ * other, pitch*height float4 each (at most 512, below 2^30 pixels together; the merged form clears what it folds). accumulator (in / out):
+ * the RADIANCE mean, pitch*height float4; no other AOV is given to the kernel. moments (in / out): NULL -- the plain kernel runs -- or the
+ * (M2_r, M2_g, M2_b, w) image, and the ..._moments kernel runs. final_image (out): pitch*height float4, filled with `sentinel` first; the
+ * caller fills the in / out images, so a pixel outside the set keeps what it was given everywhere. Sample indices are >= 0 and stay below
+ * 2^24. Leaves no state a frame reads. RT_ERROR_INVALID_ARG with a message for anything else, a NULL context first.                      */
+int rt_accumulate_frames(rt_context * ctx, int merged, const int32_t * first_sample, const int32_t * sample_count, size_t submissions,
+                         float * frames, float * accumulator, float * moments, uint32_t sentinel, float * final_image);
+/* rt_estimate_noise's kernel on explicit images of the context's frame size (synchronous): mean and moments are pitch*height float4 from
+ * the caller; everything else as rt_estimate_noise, which need not be enabled.                                                          */
+int rt_estimate_noise_images(rt_context * ctx, const float * mean, const float * moments, float floor, rt_noise_estimate * out, double * cell_sums,
+                             int32_t * cell_counts, int32_t * cell_nonfinite, size_t cell_capacity, float * pixel_map);
 /* Streaming-read bandwidth probe used as the measured HBM roofline (GB/s).                 */
 int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps);
 
