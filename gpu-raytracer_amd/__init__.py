@@ -59,6 +59,10 @@ class NoiseEstimateRecord(ctypes.Structure):  # rt_noise_estimate
     _fields_ = [("cells_x", ctypes.c_int32), ("cells_y", ctypes.c_int32), ("pixels", ctypes.c_int64), ("nonfinite_pixels", ctypes.c_int64), ("mean", ctypes.c_double)]
 
 
+class CellSelectionRecord(ctypes.Structure):  # rt_cell_selection
+    _fields_ = [("cells_x", ctypes.c_int32), ("cells_y", ctypes.c_int32), ("hot_cells", ctypes.c_int64), ("active_cells", ctypes.c_int64), ("list_pixels", ctypes.c_int64)]
+
+
 class DeviceLibraryMissing(RuntimeError):
     pass
 
@@ -137,6 +141,12 @@ def device_lib():
         lib.rt_estimate_noise_images.argtypes = [c_void_p, c_void_p, c_void_p, c_float, POINTER(NoiseEstimateRecord), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
         lib.rt_accumulate_frames.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]
         lib.rt_set_pixel_tiles.argtypes = [c_void_p, c_int, c_int, c_int]
+        lib.rt_select_active_cells.argtypes = [c_void_p, c_float, c_float, c_int, POINTER(CellSelectionRecord), c_void_p, c_size_t]
+        lib.rt_set_pixel_list.argtypes = [c_void_p, c_int]
+        lib.rt_get_pixel_list.argtypes = [c_void_p]
+        lib.rt_read_pixel_list.argtypes = [c_void_p, c_void_p, c_size_t, POINTER(c_size_t)]
+        lib.rt_select_pixels_images.argtypes = [c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, POINTER(CellSelectionRecord), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]
+        lib.rt_accumulate_list_frames.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_uint32, c_void_p]
         _device = lib
     return _device
 
@@ -903,11 +913,44 @@ class Pathtracer:
         """The per-pixel relative standard error, (height, pitch) float32: -1 where the pixel takes no part, -2 where it is not finite."""
         return self._noise("grt_pathtracer_noise", True)[1]
 
-    def render_until(self, noise_target, max_samples, check_every=16):
+    def select_adaptive(self, threshold):
+        """Pathtracer::select_adaptive (DESIGN.md 7.6): selects the cells whose mean error is above `threshold` (config noise_floor, adaptive_dilate) and lets the
+        next render calls cover their pixels only; an empty selection switches back to the whole frame. Returns {"cells", "hot_cells", "active_cells", "list_pixels"}."""
+        lib = host_lib()
+        lib.grt_pathtracer_select_adaptive.argtypes = [c_void_p, ctypes.c_double, c_void_p]
+        out = np.zeros(4, np.int64)
+        _host_check(lib.grt_pathtracer_select_adaptive(self.handle, float(threshold), out.ctypes.data))
+        return {"cells": int(out[0]), "hot_cells": int(out[1]), "active_cells": int(out[2]), "list_pixels": int(out[3])}
+
+    def adaptive_off(self):
+        """Render calls cover the whole frame again."""
+        lib = host_lib()
+        lib.grt_pathtracer_adaptive_off.argtypes = [c_void_p]
+        _host_check(lib.grt_pathtracer_adaptive_off(self.handle))
+
+    def sample_counts(self):
+        """Pathtracer::sample_counts(): (w per pixel as (height, pitch) float32 -- the number of samples each pixel's mean stands for, one
+        below the samples rendered for it (sample 1 overwrites sample 0) --, the mean of w over the frame)."""
+        lib = host_lib()
+        lib.grt_pathtracer_sample_counts.argtypes = [c_void_p, c_void_p, POINTER(ctypes.c_double)]
+        counts = np.zeros((self.height, self.pitch), np.float32)
+        mean = ctypes.c_double()
+        _host_check(lib.grt_pathtracer_sample_counts(self.handle, counts.ctypes.data, byref(mean)))
+        return counts, mean.value
+
+    def sample_count_map(self):
+        return self.sample_counts()[0]
+
+    def render_until(self, noise_target, max_samples, check_every=16, adaptive=False):
         """Renders until the noise figure is <= noise_target, never fewer than config noise_min_samples samples and never more than max_samples;
-        the figure is asked for every `check_every` samples only (the question drains the wavefront). Returns {"samples", "figure", "mean", "capped"}."""
+        the figure is asked for every `check_every` samples only (the question drains the wavefront). Returns {"samples", "figure", "mean", "capped"}.
+        adaptive=True: at every check that goes on, the cells whose mean error is above noise_target are selected and the next passes render their
+        pixels only; the stop criterion stays the same. The result then also has "mean_samples" (the samples rendered per pixel on average: the mean of w, plus
+        sample 0) and "active_share" (per check, active cells / cells)."""
         if not (noise_target >= 0.0) or max_samples < 2 or check_every < 1:
             raise ValueError("render_until: noise_target >= 0, max_samples >= 2 and check_every >= 1 are required")
+        if adaptive and config_get("enable_svgf"):
+            raise ValueError("render_until: adaptive sampling needs plain path tracing (no SVGF)")
         if config_get("enable_svgf"):   # SVGF frames keep no second moments (their accumulators are the filter's images)
             import warnings
             warnings.warn("render_until: SVGF frames keep no noise estimate; rendering to max_samples")
@@ -916,8 +959,22 @@ class Pathtracer:
                 self.render()
                 if self.sample_index + 1 >= max_samples:
                     return {"samples": self.sample_index + 1, "figure": None, "mean": None, "capped": True}
+        if adaptive and not noise_target > 0.0:
+            raise ValueError("render_until: adaptive sampling needs noise_target > 0")
         self.set_noise_estimate(True)
         min_samples = int(config_get("noise_min_samples"))
+        if not adaptive:
+            return self._render_until(noise_target, max_samples, check_every, min_samples, None)
+        shares = []
+        try:
+            result = self._render_until(noise_target, max_samples, check_every, min_samples, shares)
+            result["mean_samples"] = self.sample_counts()[1] + 1.0
+            result["active_share"] = shares
+            return result
+        finally:
+            self.adaptive_off()
+
+    def _render_until(self, noise_target, max_samples, check_every, min_samples, shares):
         estimate = None
         while True:
             self.update()
@@ -935,6 +992,9 @@ class Pathtracer:
                 estimate = self.noise_estimate()
                 if estimate["figure"] <= noise_target:
                     break
+                if shares is not None and samples < max_samples:
+                    chosen = self.select_adaptive(noise_target)
+                    shares.append(chosen["active_cells"] / chosen["cells"])
             if samples >= max_samples:
                 break
         if estimate is None:
@@ -1084,6 +1144,85 @@ def accumulate_frames(ctx, frames, accumulator, moments, first_sample, sample_co
     final = np.zeros(accumulator.shape, np.float32)
     status = device_lib().rt_accumulate_frames(ctx, 1 if merged else 0, first.ctypes.data, count.ctypes.data, len(first), frames.ctypes.data, accumulator.ctypes.data,
                                                None if moments is None else moments.ctypes.data, sentinel, final.ctypes.data)
+    if status:
+        raise DeviceRefusal(ctx, status)
+    return frames, accumulator, moments, final
+
+
+def _selection(out, flags):
+    shape = (out.cells_y, out.cells_x)
+    return {"cells_x": out.cells_x, "cells_y": out.cells_y, "hot_cells": out.hot_cells, "active_cells": out.active_cells, "list_pixels": out.list_pixels,
+            "hot": (flags & 1).astype(bool).reshape(shape), "active": ((flags >> 1) & 1).astype(bool).reshape(shape)}
+
+
+def select_active_cells(ctx, height, width, threshold, floor=1e-2, dilate=1, cell_capacity=None):
+    """rt_select_active_cells on the context's accumulator and moments; the list stays with the context. Returns a dict: cells_x, cells_y,
+    hot_cells, active_cells, list_pixels, hot / active (cells_y, cells_x) bool."""
+    n = ((width + 15) // 16) * ((height + 15) // 16)
+    flags = np.zeros(n, np.uint8)
+    out = CellSelectionRecord()
+    status = device_lib().rt_select_active_cells(ctx, c_float(floor), c_float(threshold), int(dilate), byref(out), flags.ctypes.data, n if cell_capacity is None else cell_capacity)
+    if status:
+        raise DeviceRefusal(ctx, status)
+    return _selection(out, flags)
+
+
+def set_pixel_list(ctx, enable):
+    status = device_lib().rt_set_pixel_list(ctx, 1 if enable else 0)
+    if status:
+        raise DeviceRefusal(ctx, status)
+
+
+def get_pixel_list(ctx):
+    return bool(device_lib().rt_get_pixel_list(ctx))
+
+
+def read_pixel_list(ctx):
+    """rt_read_pixel_list: the selected list, uint32 x + y * width each."""
+    lib = device_lib()
+    count = c_size_t()
+    status = lib.rt_read_pixel_list(ctx, None, 0, byref(count))
+    if status:
+        raise DeviceRefusal(ctx, status)
+    pixels = np.zeros(count.value, np.uint32)
+    status = lib.rt_read_pixel_list(ctx, pixels.ctypes.data, pixels.size, byref(count))
+    if status:
+        raise DeviceRefusal(ctx, status)
+    return pixels
+
+
+def select_pixels_images(ctx, height, width, pitch, mean, moments, threshold, floor=1e-2, dilate=1, sentinel=0xffffffff):
+    """rt_select_pixels_images: selection and compaction on the caller's (height, pitch, 4) float32 images. Returns the dict of select_active_cells plus cell_sums /
+    cell_counts / cell_nonfinite (cells_y, cells_x), list (the list_pixels entries) and list_tail (the rest of the width * height entries: still `sentinel`)."""
+    mean, moments = _f32(mean), _f32(moments)
+    assert mean.shape == (height, pitch, 4) and moments.shape == (height, pitch, 4)
+    cells_x, cells_y = (width + 15) // 16, (height + 15) // 16
+    n = cells_x * cells_y
+    sums, counts, nonfinite, flags = np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint8)
+    pixels = np.full(width * height, sentinel, np.uint32)
+    out = CellSelectionRecord()
+    status = device_lib().rt_select_pixels_images(ctx, mean.ctypes.data, moments.ctypes.data, c_float(floor), c_float(threshold), int(dilate), byref(out), sums.ctypes.data,
+                                                  counts.ctypes.data, nonfinite.ctypes.data, flags.ctypes.data, n, pixels.ctypes.data, pixels.size)
+    if status:
+        raise DeviceRefusal(ctx, status)
+    result = _selection(out, flags)
+    result.update(cell_sums=sums.reshape(cells_y, cells_x), cell_counts=counts.reshape(cells_y, cells_x), cell_nonfinite=nonfinite.reshape(cells_y, cells_x),
+                  list=pixels[:out.list_pixels].copy(), list_tail=pixels[out.list_pixels:].copy())
+    return result
+
+
+def accumulate_list_frames(ctx, frames, accumulator, moments, pixels, sample_count, first_sample=None, sentinel=0x7fc0dead):
+    """rt_accumulate_list_frames: one launch of the list accumulate launcher. frames (samples, height, pitch, 4), accumulator and moments (height, pitch, 4) float32;
+    pixels: the list (x + y * width); sample_count: one entry per submission (first_sample likewise; it does not enter the fold). Returns (frames, accumulator,
+    moments, final_image) after the launch."""
+    frames, accumulator, moments = _f32(frames).copy(), _f32(accumulator).copy(), _f32(moments).copy()
+    count = np.asarray(sample_count, np.int32).reshape(-1).copy()
+    first = np.full(len(count), 16, np.int32) if first_sample is None else np.asarray(first_sample, np.int32).reshape(-1).copy()
+    pixels = np.ascontiguousarray(pixels, np.uint32)
+    assert frames.ndim == 4 and frames.shape[0] == int(count.sum()) and frames.shape[1:] == accumulator.shape == moments.shape and len(first) == len(count)
+    final = np.zeros(accumulator.shape, np.float32)
+    status = device_lib().rt_accumulate_list_frames(ctx, first.ctypes.data, count.ctypes.data, len(count), frames.ctypes.data, accumulator.ctypes.data, moments.ctypes.data,
+                                                    pixels.ctypes.data, pixels.size, sentinel, final.ctypes.data)
     if status:
         raise DeviceRefusal(ctx, status)
     return frames, accumulator, moments, final

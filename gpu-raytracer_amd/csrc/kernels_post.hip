@@ -202,6 +202,138 @@ void rt_launch_noise_cells(const float4 * mean, const float4 * moments, int widt
 	                   mean, moments, width, height, pitch, cells_x, floor, pixel_map, cell_sums, cell_counts, cell_nonfinite);
 }
 
+// ---- adaptive sampling: the cells still above the noise target, and their pixels as a list (rt_select_active_cells) ----------
+// The in-frame pixels of cell (cx, cy): edge cells are clipped.
+RT_DEV int cell_frame_pixels(int cx, int cy, int width, int height) {
+	return min(RT_NOISE_CELL, width - cx * RT_NOISE_CELL) * min(RT_NOISE_CELL, height - cy * RT_NOISE_CELL);
+}
+// A cell is hot when its mean error is above the threshold -- compared in double, as sum > threshold * count, so that the host reproduces it from the
+// cell arrays -- or when it has in-frame pixels that took no part without being non-finite (w < 2: not sampled enough to judge). A cell of non-finite
+// pixels only is not hot: more samples do not repair a NaN mean.
+RT_DEV bool cell_is_hot(const double * __restrict__ cell_sums, const int * __restrict__ cell_counts, const int * __restrict__ cell_nonfinite, int c, int frame_pixels, float threshold) {
+	const int count = cell_counts[c];
+	if (count > 0 && cell_sums[c] > double(threshold) * double(count)) return true;
+	return count + cell_nonfinite[c] < frame_pixels;
+}
+// One thread per cell. flags: bit 0 hot, bit 1 active (hot, or with dilate = 1 one of the up to 8 neighbours inside the grid hot); active_pixels: the
+// cell's in-frame pixels when it is active, else 0 -- what the scan below turns into list offsets.
+__global__ void __launch_bounds__(256) kernel_select_cells(const double * __restrict__ cell_sums, const int * __restrict__ cell_counts, const int * __restrict__ cell_nonfinite,
+                                                           int width, int height, int cells_x, int cells_y, float threshold, int dilate,
+                                                           unsigned char * __restrict__ flags, int * __restrict__ active_pixels) {
+	const int c = blockIdx.x * blockDim.x + threadIdx.x;
+	if (c >= cells_x * cells_y) return;
+	const int cx = c % cells_x, cy = c / cells_x;
+	const bool hot = cell_is_hot(cell_sums, cell_counts, cell_nonfinite, c, cell_frame_pixels(cx, cy, width, height), threshold);
+	bool active = hot;
+	if (dilate && !hot)
+		for (int ny = max(cy - 1, 0); ny <= min(cy + 1, cells_y - 1); ny++) for (int nx = max(cx - 1, 0); nx <= min(cx + 1, cells_x - 1); nx++)
+			if (cell_is_hot(cell_sums, cell_counts, cell_nonfinite, nx + ny * cells_x, cell_frame_pixels(nx, ny, width, height), threshold)) active = true;
+	flags[c] = (unsigned char)((hot ? 1 : 0) | (active ? 2 : 0));
+	active_pixels[c] = active ? cell_frame_pixels(cx, cy, width, height) : 0;
+}
+// Exclusive prefix sum of active_pixels over the cells in ascending cell index, one workgroup: thread t adds up its run of consecutive cells, the 256 run
+// totals are scanned in LDS (Hillis-Steele, integers), the run is walked again. totals: { list length, hot cells, active cells }. No atomics: the
+// offsets, and with them the list, are the same on every run.
+__global__ void __launch_bounds__(256) kernel_scan_cells(const int * __restrict__ active_pixels, const unsigned char * __restrict__ flags, int cells, int * __restrict__ offsets, int * __restrict__ totals) {
+	__shared__ int pixels[256], hot[256], active[256];
+	const int t = threadIdx.x;
+	const int run = (cells + 255) / 256, begin = min(t * run, cells), end = min(begin + run, cells);
+	int sum = 0, h = 0, a = 0;
+	for (int c = begin; c < end; c++) { sum += active_pixels[c]; h += flags[c] & 1; a += (flags[c] >> 1) & 1; }
+	pixels[t] = sum; hot[t] = h; active[t] = a;
+	__syncthreads();
+	for (int stride = 1; stride < 256; stride <<= 1) {
+		int add = t >= stride ? pixels[t - stride] : 0;
+		__syncthreads();
+		pixels[t] += add;
+		__syncthreads();
+	}
+	int at = pixels[t] - sum;   // exclusive
+	for (int c = begin; c < end; c++) { offsets[c] = at; at += active_pixels[c]; }
+	for (int stride = 128; stride >= 1; stride >>= 1) {
+		if (t < stride) { hot[t] += hot[t + stride]; active[t] += active[t + stride]; }
+		__syncthreads();
+	}
+	if (t == 0) { totals[0] = pixels[255]; totals[1] = hot[0]; totals[2] = active[0]; }
+}
+// One workgroup per cell; an active cell writes its in-frame pixels, x + y * width each, from offsets[cell] on. Thread t stands for the pixel that comes t-th in
+// the cell's order: the four 8 x 8 patches (0,0), (8,0), (0,8), (8,8), a patch row by row -- 64 consecutive entries of an unclipped cell cover one patch, the
+// queue order kernel_generate_stream uses for whole bands. In a clipped cell the pixels outside the frame are skipped and the list stays dense: a pixel's
+// place is its rank among the in-frame threads, an inclusive scan of the 256 flags in LDS.
+__global__ void __launch_bounds__(RT_NOISE_CELL * RT_NOISE_CELL) kernel_compact_cells(const unsigned char * __restrict__ flags, const int * __restrict__ offsets, int width, int height, int cells_x,
+                                                                                      unsigned * __restrict__ list) {
+	__shared__ int rank[RT_NOISE_CELL * RT_NOISE_CELL];
+	const int cell = blockIdx.x;
+	if (!(flags[cell] & 2)) return;   // (the whole workgroup)
+	const int t = threadIdx.x;
+	const int patch = t >> 6, in_patch = t & 63;
+	const int x = (cell % cells_x) * RT_NOISE_CELL + (patch & 1) * 8 + (in_patch & 7);
+	const int y = (cell / cells_x) * RT_NOISE_CELL + (patch >> 1) * 8 + (in_patch >> 3);
+	const int inside = x < width && y < height ? 1 : 0;
+	rank[t] = inside;
+	__syncthreads();
+	for (int stride = 1; stride < RT_NOISE_CELL * RT_NOISE_CELL; stride <<= 1) {
+		int add = t >= stride ? rank[t - stride] : 0;
+		__syncthreads();
+		rank[t] += add;
+		__syncthreads();
+	}
+	if (inside) list[offsets[cell] + rank[t] - 1] = unsigned(x) + unsigned(y) * unsigned(width);
+}
+
+void rt_launch_select_cells(const double * cell_sums, const int * cell_counts, const int * cell_nonfinite, int width, int height, float threshold, int dilate,
+                            unsigned char * flags, int * active_pixels, int * offsets, int * totals, unsigned * list, hipStream_t stream) {
+	const int cells_x = (width + RT_NOISE_CELL - 1) / RT_NOISE_CELL, cells_y = (height + RT_NOISE_CELL - 1) / RT_NOISE_CELL, cells = cells_x * cells_y;
+	hipLaunchKernelGGL(kernel_select_cells, dim3((cells + 255) / 256), dim3(256), 0, stream, cell_sums, cell_counts, cell_nonfinite, width, height, cells_x, cells_y, threshold, dilate, flags, active_pixels);
+	hipLaunchKernelGGL(kernel_scan_cells, dim3(1), dim3(256), 0, stream, active_pixels, flags, cells, offsets, totals);
+	hipLaunchKernelGGL(kernel_compact_cells, dim3(cells), dim3(RT_NOISE_CELL * RT_NOISE_CELL), 0, stream, flags, offsets, width, height, cells_x, list);
+}
+
+// The accumulate step of list submissions (rt_set_pixel_list): entry i of `list` names the pixel, and the fold index is the PIXEL'S OWN -- n = w + 1 at load, w
+// the number of samples its moments stand for, then n + 1 for every further sample of the group; the submissions' first_sample does not enter. All four AOVs fold
+// with that n. w = 0 (never sampled) gives n = 1: the mean takes the sample, the moments become (0, 0, 0, 1); w = 1 gives n = 2, the Welford step proper.
+// Only the list's pixels were written in the sample frames, and only they are cleared.
+template<bool MOMENTS> RT_DEV f4 aov_accumulate_list(const RtParams & p, const RtAccumulateGroup & g, int aov, int pixel_index, float n, float4 * moments = nullptr) {
+	const RtAOV & a = p.aovs[aov];
+	if (!a.framebuffer) return mk4(0.0f);
+	f4 acc = mk4(a.accumulator[pixel_index]), m2 = mk4(0.0f);
+	if (MOMENTS) m2 = mk4(moments[pixel_index]);
+	for (int k = 0; k < g.count; k++) {
+		float4 * frames = a.framebuffer + size_t(g.slot_base[k]) * p.frame_pixels;
+		for (int s = 0; s < g.sample_count[k]; s++, n += 1.0f) {
+			float4 * sample = frames + size_t(s) * p.frame_pixels + pixel_index;
+			f4 fb = mk4(*sample);
+			*sample = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+			acc = accumulate_fold<MOMENTS>(acc, m2, fb, n);
+		}
+	}
+	a.accumulator[pixel_index] = to_float4(acc);
+	if (MOMENTS) moments[pixel_index] = to_float4(m2);
+	return acc;
+}
+__global__ void __launch_bounds__(256) kernel_accumulate_group_list_moments(RtParams p, RtAccumulateGroup g, const unsigned * __restrict__ list, int pixel_count, float4 * moments) {
+	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < pixel_count; i += gridDim.x * blockDim.x) {
+		int idx = int(list[i]);
+		int x = idx % p.screen_width, y = idx / p.screen_width;
+		int pixel_index = x + y * p.screen_pitch;
+		float n = moments[pixel_index].w + 1.0f;
+
+		f4 colour = aov_accumulate_list<true>(p, g, RT_AOV_RADIANCE, pixel_index, n, moments);
+		aov_accumulate_list<false>(p, g, RT_AOV_ALBEDO,   pixel_index, n);
+		aov_accumulate_list<false>(p, g, RT_AOV_NORMAL,   pixel_index, n);
+		aov_accumulate_list<false>(p, g, RT_AOV_POSITION, pixel_index, n);
+
+		if (!isfinite(colour.x + colour.y + colour.z)) colour = mk4(1000.0f, 0.0f, 1000.0f, 1.0f); // NaN guard, Pathtracer.cu:790-793
+		p.final_image[pixel_index] = to_float4(colour);
+	}
+}
+void rt_launch_accumulate_group_list(const RtParams & p, const RtAccumulateGroup & group, const unsigned * list, int pixel_count, hipStream_t stream, float4 * moments) {
+	int blocks = (pixel_count + 255) / 256;
+	if (blocks > 4096) blocks = 4096;
+	if (blocks < 1) blocks = 1;
+	hipLaunchKernelGGL(kernel_accumulate_group_list_moments, dim3(blocks), dim3(256), 0, stream, p, group, list, pixel_count, moments);
+}
+
 // ---- SVGF ----------------------------------------------------------------------------------------
 
 #define RT_SVGF_EPSILON 1e-8f

@@ -268,7 +268,8 @@ int resolve_pixel_range(rt_context * ctx, const char * caller, int * out_offset,
 	const RtParams & p = ctx->params;
 	const int frame = p.screen_width * p.screen_height;
 	int offset = ctx->pixel_offset, count = ctx->pixel_count < 0 ? frame - offset : ctx->pixel_count;
-	if (p.tile_pixels > 0) {
+	if (ctx->pixel_list_on) { offset = 0; count = ctx->pixel_list_count; }   // entries 0 .. count-1 of the selected list (rt_set_pixel_list)
+	else if (p.tile_pixels > 0) {
 		int tiles_total = (frame + p.tile_pixels - 1) / p.tile_pixels;
 		int owned = p.tile_first < tiles_total ? (tiles_total - p.tile_first + p.tile_stride - 1) / p.tile_stride : 0;
 		offset = 0; count = owned * p.tile_pixels;
@@ -1355,6 +1356,11 @@ static int sync_svgf(rt_context * ctx) {
 	return RT_OK;
 }
 
+// The pixel list of adaptive sampling is a selection from one state of the moments image: dropped whenever that image is zeroed, freed with it.
+// The caller has quiesced the context -- no submission in flight reads the list.
+static void pixel_list_drop(rt_context * ctx) { ctx->pixel_list_on = false; ctx->pixel_list_selected = false; ctx->pixel_list_count = 0; }
+static void pixel_list_free(rt_context * ctx) { pixel_list_drop(ctx); if (ctx->pixel_list) { device_free(ctx, ctx->pixel_list); ctx->pixel_list = nullptr; } }
+
 // The second-moment image exists exactly while the estimate is on and the frame has a size; it starts from zeros (w == 0: no sample has reached the pixel).
 // The caller has quiesced the context.
 static int sync_noise_moments(rt_context * ctx) {
@@ -1363,6 +1369,7 @@ static int sync_noise_moments(rt_context * ctx) {
 		int s = device_alloc(ctx, &ctx->noise_moments, ctx->frame_pixels * 16); if (s) return s;
 		RT_HIP(ctx, hipMemset(ctx->noise_moments, 0, ctx->frame_pixels * 16));
 	} else if (!want && ctx->noise_moments) { device_free(ctx, ctx->noise_moments); ctx->noise_moments = nullptr; }
+	if (!want) pixel_list_free(ctx);
 	return RT_OK;
 }
 // A change of the pixel set: the moments of pixels the context no longer renders would go stale beside means that another rank's image replaces.
@@ -1371,6 +1378,7 @@ static int noise_moments_reset(rt_context * ctx) {
 	(void)hipSetDevice(ctx->device);
 	RT_HIP(ctx, quiesce(ctx));
 	RT_HIP(ctx, hipMemset(ctx->noise_moments, 0, ctx->frame_pixels * 16));
+	pixel_list_drop(ctx);
 	return RT_OK;
 }
 // What the accumulate launchers get as `moments` for a launch under parameter block p: the image while the estimate is on and the launch is not an SVGF frame's
@@ -1400,6 +1408,7 @@ int rt_resize(rt_context * ctx, int width, int height) {
 	RT_HIP(ctx, hipMemsetAsync(ctx->final_image, 0, ctx->frame_pixels * 16, ctx->stream));
 	ctx->params.final_image = (float4 *)ctx->final_image;
 	device_free(ctx, ctx->noise_moments); ctx->noise_moments = nullptr;
+	pixel_list_free(ctx);
 	if ((s = sync_aovs(ctx))) return s;
 	if ((s = sync_svgf(ctx))) return s;
 	return sync_noise_moments(ctx);
@@ -1882,14 +1891,15 @@ static int stream_complete(rt_context * ctx, const StreamSubmission * subs, int 
 		int k = first;
 		for (; k < count && group.count < RT_ACCUMULATE_GROUP; k++) {
 			const StreamSubmission & sub = subs[k];
-			if (sub.range_offset != head.range_offset || sub.range_count != head.range_count || sub.tile_pixels != head.tile_pixels || sub.tile_first != head.tile_first || sub.tile_stride != head.tile_stride) break;
+			if (sub.range_offset != head.range_offset || sub.range_count != head.range_count || sub.tile_pixels != head.tile_pixels || sub.tile_first != head.tile_first || sub.tile_stride != head.tile_stride || sub.list != head.list) break;
 			group.first_sample[group.count] = sub.first_sample; group.sample_count[group.count] = sub.sample_count; group.slot_base[group.count] = sub.slot_base;
 			group.count++;
 		}
 		RtParams pa = p;
 		pa.tile_pixels = head.tile_pixels; pa.tile_first = head.tile_first; pa.tile_stride = head.tile_stride;
 		span_mark(ctx, SPAN_ACCUMULATE, st);
-		rt_launch_accumulate_group(pa, group, head.range_offset, head.range_count, st, noise_moments_for(ctx, pa));
+		if (head.list) rt_launch_accumulate_group_list(pa, group, (const unsigned *)ctx->pixel_list, head.range_count, st, (float4 *)ctx->noise_moments);   // (the list does not change while a submission is in flight)
+		else rt_launch_accumulate_group(pa, group, head.range_offset, head.range_count, st, noise_moments_for(ctx, pa));
 		span_mark(ctx, SPAN_ACCUMULATE, st);
 		first = k;
 	}
@@ -1956,7 +1966,8 @@ static int stream_generate(rt_context * ctx, const StreamSubmission & sub) {
 	const int order = 8;
 	const int frame = pg.screen_width * pg.screen_height;
 	const bool whole_bands = sub.tile_pixels > 0 ? sub.tile_pixels % (order * pg.screen_width) == 0 : (sub.range_offset == 0 && sub.range_count == frame);
-	rt_launch_generate_stream(pg, sub.first_sample, sub.range_offset, sub.range_count, sub.slot_base, int(s.pending_paths), whole_bands ? order : 0, whole_bands ? order : 0, st);
+	if (sub.list) rt_launch_generate_stream_list(pg, sub.first_sample, (const unsigned *)ctx->pixel_list, sub.range_count, sub.slot_base, int(s.pending_paths), st);   // (in patch order already)
+	else rt_launch_generate_stream(pg, sub.first_sample, sub.range_offset, sub.range_count, sub.slot_base, int(s.pending_paths), whole_bands ? order : 0, whole_bands ? order : 0, st);
 	span_mark(ctx, SPAN_GENERATE, st);
 	s.pending++; s.pending_paths += sub.paths;
 	return RT_OK;
@@ -2073,6 +2084,7 @@ static int stream_submit(rt_context * ctx, int sample_index, int sample_count, i
 	sub.birth = s.iteration; sub.last = s.iteration + num_bounces - 1; sub.paths = int(paths);
 	sub.range_offset = range_offset; sub.range_count = range_count;
 	sub.tile_pixels = ctx->params.tile_pixels; sub.tile_first = ctx->params.tile_first; sub.tile_stride = ctx->params.tile_stride;
+	sub.list = ctx->pixel_list_on;
 	for (int k = 0; k < sample_count; k++) {
 		s.slot_used[slot_base + k] = true;
 		s.table_host.slots[slot_base + k] = { sample_index + k, sub.birth, sub.ring, k };
@@ -2135,6 +2147,13 @@ int rt_render_samples(rt_context * ctx, int sample_index, int sample_count) {
 	                    && !(ctx->params.config.enable_svgf && ctx->defer_filter) // the tile split of SVGF frames exchanges the filter's inputs per frame
 	                    && !(ctx->batch_size_request > 0); // explicit pixel batches (a VRAM bound of the reference) are a slot-scheduler feature
 	if (ctx->params.config.enable_svgf && sample_count != 1) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_render_samples: SVGF frames are rendered one sample at a time");
+	if (ctx->pixel_list_on) {   // a refusal, never a silent uniform render: the list kernels exist for the merged wavefront's plain frames, and a pixel's own count starts at w >= 1
+		if (ctx->scheduler != RT_SCHEDULER_MERGED) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_render_samples: a pixel list (rt_set_pixel_list) needs RT_SCHEDULER_MERGED");
+		if (!merged) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_render_samples: a pixel list (rt_set_pixel_list) needs the merged wavefront, which this context does not take (num_bounces 0, a BVH other than CWBVH, or an explicit pixel batch size)");
+		if (ctx->params.config.enable_svgf) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_render_samples: SVGF frames cannot cover a pixel list (rt_set_pixel_list)");
+		if (sample_index < 2) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_render_samples: a pixel list (rt_set_pixel_list) continues a progression, sample_index %d is below 2", sample_index);
+	}
+	else if (sample_index < 2 && ctx->pixel_list_selected) pixel_list_drop(ctx);   // a uniform sample 0 or 1 starts the pixels' moments over: a selection made from the ones before says nothing about them
 	if (merged != ctx->last_render_merged) { RT_HIP(ctx, quiesce(ctx)); ctx->last_render_merged = merged; }
 	if (ctx->has_material[2] || ctx->has_material[3]) { s = ensure_luts(ctx); if (s) return s; }
 	s = sky_sampling_prepare(ctx, "rt_render_sample"); if (s) return s;
@@ -2257,6 +2276,7 @@ int rt_render_ao_sample(rt_context * ctx, int sample_index, float ao_radius) {
 	(void)hipSetDevice(ctx->device);
 	int s = check_ready(ctx, "rt_render_ao_sample", NEED_SCENE | NEED_RNG | NEED_FRAME); if (s) return s;
 	if (ctx->params.tile_pixels > 0) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_render_ao_sample: tile mode is not supported, use rt_set_pixel_range");
+	if (ctx->pixel_list_on) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_render_ao_sample: the AO integrator cannot cover a pixel list (rt_set_pixel_list)");
 	int range_offset = 0, range_count = 0;
 	s = resolve_pixel_range(ctx, "rt_render_ao_sample", &range_offset, &range_count); if (s) return s;
 
@@ -2438,6 +2458,7 @@ int rt_set_noise_estimate(rt_context * ctx, int enable) {
 	ctx->noise_estimate = enable != 0;
 	int s = sync_noise_moments(ctx); if (s) return s;
 	if (ctx->noise_moments) RT_HIP(ctx, hipMemset(ctx->noise_moments, 0, ctx->frame_pixels * 16));
+	pixel_list_drop(ctx);
 	return RT_OK;
 }
 int rt_get_noise_estimate(const rt_context * ctx) { return ctx && ctx->noise_estimate ? 1 : 0; }
@@ -2499,6 +2520,104 @@ int rt_estimate_noise(rt_context * ctx, float floor, rt_noise_estimate * out, do
 	RT_HIP(ctx, quiesce(ctx));
 	return noise_estimate_images(ctx, "rt_estimate_noise", (const float4 *)ctx->aov_buffers[RT_AOV_RADIANCE][1], (const float4 *)ctx->noise_moments, floor, out,
 	                             cell_sums, cell_counts, cell_nonfinite, cell_capacity, pixel_map);
+}
+
+// ---- adaptive sampling ------------------------------------------------------------------------------
+
+// The noise kernel, the selection and the compaction on two pitched float4 images of the context's frame size, already on the device, into `list` (room for
+// width * height entries), on the main stream, which the caller has drained. cell_sums / cell_counts / cell_nonfinite / cell_flags may each be null.
+// Shared by rt_select_active_cells and the probe so that they cannot differ.
+int select_cells_images(rt_context * ctx, const char * caller, const float4 * mean, const float4 * moments, float floor, float threshold, int dilate, unsigned * list,
+                        rt_cell_selection * out, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, uint8_t * cell_flags, size_t cell_capacity) {
+	const RtParams & p = ctx->params;
+	const int cells_x = (p.screen_width + RT_NOISE_CELL - 1) / RT_NOISE_CELL, cells_y = (p.screen_height + RT_NOISE_CELL - 1) / RT_NOISE_CELL;
+	const size_t cells = size_t(cells_x) * cells_y;
+	if ((cell_sums || cell_counts || cell_nonfinite || cell_flags) && cell_capacity < cells)
+		return fail(ctx, RT_ERROR_INVALID_ARG, "%s: cell_capacity %zu is below the %d x %d cells of the frame", caller, cell_capacity, cells_x, cells_y);
+	// one allocation: sums (double), then counts, non-finite counts, active pixels, offsets (int each), totals (3 ints, padded to 4), flags (bytes)
+	void * dev = nullptr;
+	int s = device_alloc(ctx, &dev, cells * 8 + cells * 16 + 16 + cells); if (s) return s;
+	double * dev_sums = (double *)dev;
+	int * dev_counts = (int *)(dev_sums + cells), * dev_nonfinite = dev_counts + cells, * dev_active = dev_nonfinite + cells, * dev_offsets = dev_active + cells, * dev_totals = dev_offsets + cells;
+	unsigned char * dev_flags = (unsigned char *)(dev_totals + 4);
+	rt_launch_noise_cells(mean, moments, p.screen_width, p.screen_height, p.screen_pitch, floor, nullptr, dev_sums, dev_counts, dev_nonfinite, ctx->stream);
+	rt_launch_select_cells(dev_sums, dev_counts, dev_nonfinite, p.screen_width, p.screen_height, threshold, dilate, dev_flags, dev_active, dev_offsets, dev_totals, list, ctx->stream);
+	int totals[3] = { 0, 0, 0 };
+	hipError_t e = hipGetLastError();
+	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+	if (e == hipSuccess) e = hipMemcpy(totals, dev_totals, sizeof(totals), hipMemcpyDeviceToHost);
+	if (e == hipSuccess && cell_sums) e = hipMemcpy(cell_sums, dev_sums, cells * 8, hipMemcpyDeviceToHost);
+	if (e == hipSuccess && cell_counts) e = hipMemcpy(cell_counts, dev_counts, cells * 4, hipMemcpyDeviceToHost);
+	if (e == hipSuccess && cell_nonfinite) e = hipMemcpy(cell_nonfinite, dev_nonfinite, cells * 4, hipMemcpyDeviceToHost);
+	if (e == hipSuccess && cell_flags) e = hipMemcpy(cell_flags, dev_flags, cells, hipMemcpyDeviceToHost);
+	device_free(ctx, dev);
+	if (e != hipSuccess) return fail(ctx, RT_ERROR_HIP, "%s: the selection kernels or their copies failed: %s", caller, hipGetErrorString(e));
+	out->cells_x = cells_x; out->cells_y = cells_y; out->list_pixels = totals[0]; out->hot_cells = totals[1]; out->active_cells = totals[2];
+	return RT_OK;
+}
+
+int selection_arguments(rt_context * ctx, const char * caller, float floor, float threshold, int dilate) {
+	if (!(floor > 0.0f && floor < __builtin_huge_valf())) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: floor must be finite and positive", caller);
+	if (!(threshold >= 0.0f && threshold < __builtin_huge_valf())) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: threshold must be finite and at least 0", caller);
+	if (dilate != 0 && dilate != 1) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: dilate must be 0 or 1", caller);
+	return RT_OK;
+}
+
+// Why a list cannot stand for this context's pixel set (null: it can): the list names pixels of the whole frame, and SVGF frames keep no moments.
+static const char * pixel_list_obstacle(const rt_context * ctx) {
+	const RtParams & p = ctx->params;
+	if (p.tile_pixels > 0) return "a tile split is set (rt_set_pixel_tiles)";
+	if (ctx->pixel_offset != 0 || (ctx->pixel_count >= 0 && ctx->pixel_count != p.screen_width * p.screen_height)) return "a pixel range other than the whole frame is set (rt_set_pixel_range)";
+	if (p.config.enable_svgf) return "SVGF is on";
+	return nullptr;
+}
+
+int rt_select_active_cells(rt_context * ctx, float floor, float threshold, int dilate, rt_cell_selection * out, uint8_t * cell_flags, size_t cell_capacity) {
+	RT_REQUIRE(ctx, ctx, "rt_select_active_cells: NULL context");
+	RT_REQUIRE(ctx, out, "rt_select_active_cells: NULL argument");
+	int s = selection_arguments(ctx, "rt_select_active_cells", floor, threshold, dilate); if (s) return s;
+	(void)hipSetDevice(ctx->device);
+	if (!ctx->noise_moments || !ctx->aov_buffers[RT_AOV_RADIANCE][1]) return fail(ctx, RT_ERROR_NOT_READY, "rt_select_active_cells: the noise estimate is off (rt_set_noise_estimate) or rt_resize was not called");
+	if (const char * why = pixel_list_obstacle(ctx)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_select_active_cells: %s", why);
+	RT_HIP(ctx, quiesce(ctx));   // from here on no submission reads the list: the new one may replace it
+	if (!ctx->pixel_list) { s = device_alloc(ctx, &ctx->pixel_list, ctx->frame_pixels * 4); if (s) return s; }
+	const bool was_on = ctx->pixel_list_on;
+	pixel_list_drop(ctx);
+	s = select_cells_images(ctx, "rt_select_active_cells", (const float4 *)ctx->aov_buffers[RT_AOV_RADIANCE][1], (const float4 *)ctx->noise_moments, floor, threshold, dilate,
+	                        (unsigned *)ctx->pixel_list, out, nullptr, nullptr, nullptr, cell_flags, cell_capacity);
+	if (s) return s;
+	ctx->pixel_list_selected = true; ctx->pixel_list_count = int(out->list_pixels);
+	ctx->pixel_list_on = was_on && ctx->pixel_list_count > 0;   // (render calls that were covering the list go on with the new one; an empty list covers nothing and switches it off)
+	return RT_OK;
+}
+
+int rt_set_pixel_list(rt_context * ctx, int enable) {
+	RT_REQUIRE(ctx, ctx, "rt_set_pixel_list: NULL context");
+	RT_REQUIRE(ctx, enable == 0 || enable == 1, "rt_set_pixel_list: enable must be 0 or 1");
+	(void)hipSetDevice(ctx->device);
+	if (enable) {
+		if (!ctx->pixel_list_selected || !ctx->pixel_list) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_set_pixel_list: no selection exists (rt_select_active_cells)");
+		if (ctx->pixel_list_count <= 0) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_set_pixel_list: the selected list is empty");
+		// (a pixel range or a tile split needs no check of its own: setting either zeroes the moments, which drops the selection, and none can be made under them)
+		if (ctx->params.config.enable_svgf) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_set_pixel_list: SVGF is on");
+	}
+	if ((enable != 0) != ctx->pixel_list_on) RT_HIP(ctx, quiesce(ctx));
+	ctx->pixel_list_on = enable != 0;
+	return RT_OK;
+}
+int rt_get_pixel_list(const rt_context * ctx) { return ctx && ctx->pixel_list_on ? 1 : 0; }
+
+int rt_read_pixel_list(rt_context * ctx, uint32_t * dst, size_t capacity, size_t * out_count) {
+	RT_REQUIRE(ctx, ctx, "rt_read_pixel_list: NULL context");
+	RT_REQUIRE(ctx, out_count, "rt_read_pixel_list: NULL argument");
+	(void)hipSetDevice(ctx->device);
+	if (!ctx->pixel_list_selected || !ctx->pixel_list) return fail(ctx, RT_ERROR_NOT_READY, "rt_read_pixel_list: no selection exists (rt_select_active_cells)");
+	*out_count = size_t(ctx->pixel_list_count);
+	if (!dst) return RT_OK;
+	if (capacity < size_t(ctx->pixel_list_count)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_read_pixel_list: capacity %zu is below the %d entries of the list", capacity, ctx->pixel_list_count);
+	RT_HIP(ctx, quiesce(ctx));
+	if (ctx->pixel_list_count > 0) RT_HIP(ctx, hipMemcpy(dst, ctx->pixel_list, size_t(ctx->pixel_list_count) * 4, hipMemcpyDeviceToHost));
+	return RT_OK;
 }
 
 int rt_read_luts(rt_context * ctx, float * dielectric_dir_enter, float * dielectric_dir_leave, float * dielectric_enter, float * dielectric_leave, float * conductor_dir, float * conductor) {

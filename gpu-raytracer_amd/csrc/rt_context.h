@@ -93,6 +93,7 @@ struct SceneRing {
 struct StreamSubmission {
 	int first_sample, sample_count, slot_base, ring, birth, last, paths;
 	int range_offset, range_count, tile_pixels, tile_first, tile_stride;
+	bool list = false;   // over the context's pixel list (rt_set_pixel_list): range_offset 0, range_count the list's length
 };
 
 struct PathStream {
@@ -203,6 +204,12 @@ struct rt_context {
 	// accumulate kernels while the estimate is on and SVGF is off; null while it is off (or before rt_resize)
 	bool noise_estimate = false;
 	void * noise_moments = nullptr;
+	// adaptive sampling (rt_select_active_cells): the pixels of the active cells, x + y * screen_width each, pixel_list_count of them in a buffer of
+	// frame_pixels entries -- allocated at the first selection, freed by rt_resize and with the estimate, dropped whenever the moments image is zeroed.
+	// pixel_list_on (rt_set_pixel_list): render calls cover the list.
+	void * pixel_list = nullptr;
+	int pixel_list_count = 0;
+	bool pixel_list_selected = false, pixel_list_on = false;
 
 	// frame exchange of the tile split (rt_comm_*): this context's rank in a group of `world` contexts, each on its own GPU
 	// (RCCL communicator) or, for tests on one GPU, several in one process (peer copies)
@@ -253,6 +260,9 @@ int stream_sync_tlas(rt_context * ctx);
 float4 * noise_moments_for(const rt_context * ctx, const RtParams & p);
 int noise_estimate_images(rt_context * ctx, const char * caller, const float4 * mean, const float4 * moments, float floor, rt_noise_estimate * out,
                           double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, size_t cell_capacity, float * pixel_map);
+int selection_arguments(rt_context * ctx, const char * caller, float floor, float threshold, int dilate);
+int select_cells_images(rt_context * ctx, const char * caller, const float4 * mean, const float4 * moments, float floor, float threshold, int dilate, unsigned * list,
+                        rt_cell_selection * out, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, uint8_t * cell_flags, size_t cell_capacity);
 }
 #pragma GCC visibility pop
 

@@ -717,6 +717,7 @@ int rt_accumulate_frames(rt_context * ctx, int merged, const int32_t * first_sam
 	const size_t frame_pixels = ctx->frame_pixels;
 	if (frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_accumulate_frames: rt_resize was not called");
 	RT_REQUIRE(ctx, total <= size_t(RT_STREAM_SAMPLE_SLOTS) && total * frame_pixels < size_t(1) << 30, "rt_accumulate_frames: at most 512 samples and fewer than 2^30 pixels in all");
+	if (ctx->pixel_list_on) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_accumulate_frames: the context covers a pixel list (rt_set_pixel_list); rt_accumulate_list_frames is the probe of that launch");
 	int range_offset = 0, range_count = 0;
 	int s = resolve_pixel_range(ctx, "rt_accumulate_frames", &range_offset, &range_count); if (s) return s;
 	RT_HIP(ctx, quiesce(ctx));
@@ -761,6 +762,73 @@ int rt_estimate_noise_images(rt_context * ctx, const float * mean, const float *
 	float4 * dev_moments = probe.array<float4>(ctx->frame_pixels, moments);
 	int s = probe.allocated(); if (s) return s;
 	return noise_estimate_images(ctx, "rt_estimate_noise_images", dev_mean, dev_moments, floor, out, cell_sums, cell_counts, cell_nonfinite, cell_capacity, pixel_map);
+}
+
+int rt_select_pixels_images(rt_context * ctx, const float * mean, const float * moments, float floor, float threshold, int dilate, rt_cell_selection * out,
+                            double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, uint8_t * cell_flags, size_t cell_capacity, uint32_t * list, size_t list_capacity) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_select_pixels_images: NULL context");
+	RT_REQUIRE(ctx, mean && moments && out && cell_sums && cell_counts && cell_nonfinite && cell_flags && list, "rt_select_pixels_images: NULL argument");
+	int s = selection_arguments(ctx, "rt_select_pixels_images", floor, threshold, dilate); if (s) return s;
+	(void)hipSetDevice(ctx->device);
+	if (ctx->frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_select_pixels_images: rt_resize was not called");
+	const size_t frame = size_t(ctx->params.screen_width) * size_t(ctx->params.screen_height);
+	RT_REQUIRE(ctx, list_capacity >= frame, "rt_select_pixels_images: list_capacity is below width * height");
+	RT_HIP(ctx, quiesce(ctx));
+	Probe probe(ctx, "rt_select_pixels_images");
+	float4 * dev_mean = probe.array<float4>(ctx->frame_pixels, mean);
+	float4 * dev_moments = probe.array<float4>(ctx->frame_pixels, moments);
+	unsigned * dev_list = probe.array<unsigned>(frame, list);   // (what the kernels do not write comes back as the caller gave it)
+	if ((s = probe.allocated())) return s;
+	if ((s = select_cells_images(ctx, "rt_select_pixels_images", dev_mean, dev_moments, floor, threshold, dilate, dev_list, out, cell_sums, cell_counts, cell_nonfinite, cell_flags, cell_capacity))) return s;
+	return probe.read(list, dev_list, frame * 4);
+}
+
+int rt_accumulate_list_frames(rt_context * ctx, const int32_t * first_sample, const int32_t * sample_count, size_t submissions,
+                              float * frames, float * accumulator, float * moments, const uint32_t * list, size_t list_count, uint32_t sentinel, float * final_image) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_accumulate_list_frames: NULL context");
+	RT_REQUIRE(ctx, first_sample && sample_count && frames && accumulator && moments && list && final_image, "rt_accumulate_list_frames: NULL array");
+	RT_REQUIRE(ctx, submissions >= 1 && submissions <= size_t(RT_ACCUMULATE_GROUP), "rt_accumulate_list_frames: 1 to RT_ACCUMULATE_GROUP submissions");
+	size_t total = 0;
+	for (size_t k = 0; k < submissions; k++) {
+		RT_REQUIRE(ctx, first_sample[k] >= 0 && sample_count[k] >= 1 && sample_count[k] <= RT_STREAM_SAMPLE_SLOTS, "rt_accumulate_list_frames: a first sample below 0 or a sample count outside [1, 512]");
+		total += size_t(sample_count[k]);
+	}
+	(void)hipSetDevice(ctx->device);
+	const size_t frame_pixels = ctx->frame_pixels;
+	if (frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_accumulate_list_frames: rt_resize was not called");
+	RT_REQUIRE(ctx, total <= size_t(RT_STREAM_SAMPLE_SLOTS) && total * frame_pixels < size_t(1) << 30, "rt_accumulate_list_frames: at most 512 samples and fewer than 2^30 pixels in all");
+	// before any launch: every entry inside the frame, no pixel twice (two threads folding one pixel would race)
+	const size_t frame = size_t(ctx->params.screen_width) * size_t(ctx->params.screen_height);
+	RT_REQUIRE(ctx, list_count >= 1 && list_count <= frame, "rt_accumulate_list_frames: the list holds 1 to width * height entries");
+	std::vector<bool> seen(frame, false);
+	for (size_t i = 0; i < list_count; i++) {
+		if (list[i] >= frame) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_accumulate_list_frames: list entry %zu (%u) lies outside the %zu pixel frame", i, list[i], frame);
+		if (seen[list[i]]) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_accumulate_list_frames: list entry %zu names pixel %u a second time", i, list[i]);
+		seen[list[i]] = true;
+	}
+	RT_HIP(ctx, quiesce(ctx));
+
+	Probe probe(ctx, "rt_accumulate_list_frames");
+	float4 * dev_frames = probe.array<float4>(total * frame_pixels, frames);
+	float4 * dev_accumulator = probe.array<float4>(frame_pixels, accumulator);
+	float4 * dev_moments = probe.array<float4>(frame_pixels, moments);
+	unsigned * dev_list = probe.array<unsigned>(list_count, list);
+	probe.staging.assign(frame_pixels * 4, sentinel);
+	float4 * dev_final = (float4 *)probe.array<uint32_t>(frame_pixels * 4, probe.staging.data());
+	int s = probe.allocated(); if (s) return s;
+
+	RtParams p = ctx->params;
+	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = p.aovs[a].accumulator = nullptr;
+	p.aovs[RT_AOV_RADIANCE].framebuffer = dev_frames; p.aovs[RT_AOV_RADIANCE].accumulator = dev_accumulator;
+	p.final_image = dev_final;
+	RtAccumulateGroup group; group.count = int(submissions);
+	for (int k = 0, base = 0; k < group.count; k++) { group.first_sample[k] = first_sample[k]; group.sample_count[k] = sample_count[k]; group.slot_base[k] = base; base += sample_count[k]; }
+	for (int k = group.count; k < RT_ACCUMULATE_GROUP; k++) group.first_sample[k] = group.sample_count[k] = group.slot_base[k] = 0;
+	rt_launch_accumulate_group_list(p, group, dev_list, int(list_count), ctx->stream, dev_moments);
+	if ((s = probe.finish())) return s;
+	if ((s = probe.read(frames, dev_frames, total * frame_pixels * 16)) || (s = probe.read(accumulator, dev_accumulator, frame_pixels * 16))) return s;
+	if ((s = probe.read(moments, dev_moments, frame_pixels * 16))) return s;
+	return probe.read(final_image, dev_final, frame_pixels * 16);
 }
 
 int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps) {

@@ -310,6 +310,14 @@ void rt_launch_accumulate_group(const RtParams & p, const RtAccumulateGroup & gr
 #define RT_NOISE_CELL 16
 void rt_launch_noise_cells(const float4 * mean, const float4 * moments, int width, int height, int pitch, float floor, float * pixel_map,
                            double * cell_sums, int * cell_counts, int * cell_nonfinite, hipStream_t stream);
+// Adaptive sampling. select: kernel_select_cells, kernel_scan_cells and kernel_compact_cells on the cell arrays of rt_launch_noise_cells: flags
+// (one byte per cell: bit 0 hot, bit 1 active), active_pixels and offsets (one int per cell), totals (3 ints: list length, hot cells, active cells), list (room for
+// width * height entries, x + y * width each). The ..._list launchers are the generate and accumulate steps of a submission over such a list; the accumulate one
+// folds every pixel with its own sample count (moments is required: w is read from it).
+void rt_launch_select_cells(const double * cell_sums, const int * cell_counts, const int * cell_nonfinite, int width, int height, float threshold, int dilate,
+                            unsigned char * flags, int * active_pixels, int * offsets, int * totals, unsigned * list, hipStream_t stream);
+void rt_launch_generate_stream_list(const RtParams & p, int sample_index, const unsigned * list, int pixel_count, int slot_base, int queue_offset, hipStream_t stream);
+void rt_launch_accumulate_group_list(const RtParams & p, const RtAccumulateGroup & group, const unsigned * list, int pixel_count, hipStream_t stream, float4 * moments);
 // mark(user, k, stream), if given, is called before and after kernel k = 0 reproject, 1 variance, 2 a-trous (each pass), 3 finalize, 4 TAA, 5 TAA finalize
 void rt_launch_svgf_taa(const RtParams & p, int sample_index, hipStream_t stream, void (*mark)(void * user, int svgf_kernel, hipStream_t stream) = nullptr, void * user = nullptr);
 void rt_launch_random(const RtParams & p, int dimension, const unsigned * pixel_indices, int count, unsigned bounce, unsigned sample_index, float2 * out, hipStream_t stream);

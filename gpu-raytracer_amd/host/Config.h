@@ -113,6 +113,13 @@ struct CPUConfig {
 	int   noise_min_samples = 16;
 	double noise_quantile = 0.95;
 	float noise_floor = 1e-2f;
+	// Adaptive sampling (needs noise_target > 0). adaptive_sampling 1: after noise_min_samples uniform samples, every noise check that goes on selects
+	// the cells whose mean error is above the target and the next passes render their pixels only. adaptive_dilate 1: the neighbours of such a cell stay active too.
+	// adaptive_sampling is read by the command-line renderer's loop alone (--adaptive sets it): Pathtracer::render never selects by itself, Python's render_until
+	// takes its own `adaptive` argument, and FrameSplit has no pixel lists (the command line warns and renders uniformly). adaptive_dilate is read by
+	// Pathtracer::select_adaptive, whoever calls it.
+	int   adaptive_sampling = 0;
+	int   adaptive_dilate = 1;
 	// Alpha-tested cut-outs from the albedo textures: 1 = every surface material whose albedo FILE has an alpha channel that is not constant gets an
 	// opacity mask from it (channel a, threshold 0.5; an explicit <bsdf type="mask"> wins). Read when a scene is loaded. 0: off, as the reference renders them.
 	int   alpha_masks = 0;

@@ -308,8 +308,14 @@ void Pathtracer::update(float delta) {
 	}
 }
 
+// A progression that starts over renders the whole frame: the list was selected from the moments of the progression before.
+static void restart_drops_pixel_list(rt_context * ctx, int sample_index) {
+	if (sample_index < 2 && rt_get_pixel_list(ctx)) rt_set_pixel_list(ctx, 0);
+}
+
 void Pathtracer::render() {
 	require_device();
+	restart_drops_pixel_list(ctx, sample_index);
 	check(rt_render_sample(ctx, sample_index));
 	if (pixel_query_status == PixelQueryStatus::PENDING) pixel_query_status = PixelQueryStatus::OUTPUT_READY; // Pathtracer.cpp:852-854
 }
@@ -317,6 +323,7 @@ void Pathtracer::render() {
 void Pathtracer::render_samples(int count) {
 	require_device();
 	if (count < 1) return;
+	restart_drops_pixel_list(ctx, sample_index);
 	if (pixel_query_status == PixelQueryStatus::PENDING) pixel_query_status = PixelQueryStatus::OUTPUT_READY;
 	if (gpu_config.enable_svgf) { // SVGF frames feed each other's history: one at a time
 		for (int i = 0; i < count; i++) { if (i) sample_index++; check(rt_render_sample(ctx, sample_index)); }
@@ -367,4 +374,34 @@ NoiseEstimate Pathtracer::noise(std::vector<float> * pixel_map, bool allow_empty
 	e.nonfinite_pixels = out.nonfinite_pixels;
 	grt_noise_summary(e.cell_sums.data(), e.cell_counts.data(), cells, cpu_config.noise_quantile, &e.mean, &e.figure, &e.pixels);
 	return e;
+}
+
+AdaptiveSelection Pathtracer::select_adaptive(float threshold) {
+	require_device();
+	if (!rt_get_noise_estimate(ctx)) throw std::runtime_error("Pathtracer::select_adaptive: the noise estimate is off (set noise_estimate_wanted or cpu_config.noise_target before update())");
+	rt_cell_selection out = { };
+	check(rt_select_active_cells(ctx, cpu_config.noise_floor, threshold, cpu_config.adaptive_dilate ? 1 : 0, &out, nullptr, 0));
+	check(rt_set_pixel_list(ctx, out.list_pixels > 0 ? 1 : 0));
+	AdaptiveSelection a;
+	a.cells = (long long)out.cells_x * out.cells_y; a.hot_cells = out.hot_cells; a.active_cells = out.active_cells; a.list_pixels = out.list_pixels;
+	return a;
+}
+
+void Pathtracer::adaptive_off() {
+	require_device();
+	check(rt_set_pixel_list(ctx, 0));
+}
+
+double Pathtracer::sample_counts(std::vector<float> * counts) {
+	require_device();
+	std::vector<float> moments(size_t(screen_pitch) * screen_height * 4);
+	check(rt_read_noise_moments(ctx, moments.data()));
+	if (counts) counts->assign(size_t(screen_pitch) * screen_height, 0.0f);
+	double sum = 0.0;
+	for (int y = 0; y < screen_height; y++) for (int x = 0; x < screen_width; x++) {
+		const float w = moments[(size_t(x) + size_t(y) * screen_pitch) * 4 + 3];
+		if (counts) (*counts)[size_t(x) + size_t(y) * screen_pitch] = w;
+		sum += double(w);
+	}
+	return sum / (double(screen_width) * double(screen_height));
 }

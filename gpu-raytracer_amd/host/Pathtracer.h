@@ -18,6 +18,10 @@ struct NoiseEstimate {
 // the cells with count > 0, sorted; entry ceil(quantile * m) of the m (1-based, at least 1). 0: fine; 1: no cell has a count (both 0); -1: quantile outside (0, 1].
 extern "C" int grt_noise_summary(const double * cell_sums, const int32_t * cell_counts, size_t cells, double quantile, double * out_mean, double * out_figure, long long * out_pixels);
 
+// What Pathtracer::select_adaptive chose: of `cells` cells, the hot ones (mean error above the threshold, or pixels not judged yet), the active
+// ones (hot, or beside a hot one under cpu_config.adaptive_dilate) and the pixels of the active cells -- what the next render calls cover.
+struct AdaptiveSelection { long long cells = 0, hot_cells = 0, active_cells = 0, list_pixels = 0; };
+
 struct Pathtracer final : Integrator {
 	// Light sampling tables (reference: Pathtracer.cpp:384-534)
 	std::vector<int>   light_triangle_indices;
@@ -58,6 +62,15 @@ struct Pathtracer final : Integrator {
 	// cpu_config.noise_target > 0 before the update() of sample 0. pixel_map: e_p per pixel at x + y * pitch, -1 where the pixel takes no part, -2 non-finite.
 	// Throws when the estimate is off; a frame without a participating pixel (allow_empty) returns pixels == 0 instead of throwing.
 	NoiseEstimate noise(std::vector<float> * pixel_map = nullptr, bool allow_empty = false);
+	// Adaptive sampling: selects the cells whose mean error is above `threshold` (rt_select_active_cells with cpu_config.noise_floor and
+	// adaptive_dilate) and switches the render calls over to their pixels (rt_set_pixel_list); an empty selection switches back to the whole frame. The pass
+	// index goes on as before -- it is the random-number index; every pixel folds with its own count. Needs the estimate on and at least two samples past
+	// sample 0. A restart of the progression (sample_index 0 at render time: camera, scene, config, resize) switches the list off by itself.
+	AdaptiveSelection select_adaptive(float threshold);
+	void adaptive_off();
+	// w per pixel (x + y * pitch; 0 in the padding) -- the number of samples the pixel's mean stands for -- and, returned, the mean of w over the frame's pixels.
+	// w is one below the samples rendered for the pixel: sample 1 overwrites sample 0 (AOV.h:35-46). Reports of "samples per pixel" add the 1.
+	double sample_counts(std::vector<float> * counts = nullptr);
 
 	void calc_light_power();
 	void geometry_was_rebuilt() override { if (scene.has_lights) calc_light_power(); }   // light_triangle_indices name device triangles

@@ -86,6 +86,7 @@ int grt_config_set(const char * key, double value) {
 	}
 	else if (k == "noise_target") {   // 0 (off) or a finite positive relative error
 		if (!(value >= 0.0 && value < 1e30)) { g_host_error = "noise_target must be 0 (off) or finite and positive"; return -1; }
+		if (value == 0.0 && cpu_config.adaptive_sampling) { g_host_error = "noise_target 0 (off) while adaptive_sampling is 1: switch adaptive_sampling off first"; return -1; }
 		cpu_config.noise_target = float(value);
 	}
 	else if (k == "noise_min_samples") {
@@ -99,6 +100,15 @@ int grt_config_set(const char * key, double value) {
 	else if (k == "noise_floor") {
 		if (!(value > 0.0 && value < 1e30)) { g_host_error = "noise_floor must be finite and positive"; return -1; }
 		cpu_config.noise_floor = float(value);
+	}
+	else if (k == "adaptive_sampling") {   // (needs a noise target: there is nothing to select by without one)
+		if (!(value == 0.0 || value == 1.0)) { g_host_error = "adaptive_sampling must be 0 or 1"; return -1; }
+		if (value == 1.0 && !(cpu_config.noise_target > 0.0f)) { g_host_error = "adaptive_sampling needs noise_target > 0 (set it first)"; return -1; }
+		cpu_config.adaptive_sampling = int(value);
+	}
+	else if (k == "adaptive_dilate") {
+		if (!(value == 0.0 || value == 1.0)) { g_host_error = "adaptive_dilate must be 0 or 1"; return -1; }
+		cpu_config.adaptive_dilate = int(value);
 	}
 	else if (k == "static_reseat_distance")              cpu_config.static_reseat_distance = float(value);
 	else if (k == "static_mesh_copy_limit_mb")           cpu_config.static_mesh_copy_limit_mb = int(value);
@@ -125,6 +135,8 @@ double grt_config_get(const char * key) {
 	if (k == "noise_min_samples") return cpu_config.noise_min_samples;
 	if (k == "noise_quantile")    return cpu_config.noise_quantile;
 	if (k == "noise_floor")       return cpu_config.noise_floor;
+	if (k == "adaptive_sampling") return cpu_config.adaptive_sampling;
+	if (k == "adaptive_dilate")   return cpu_config.adaptive_dilate;
 	return -1.0;
 }
 
@@ -441,6 +453,30 @@ int grt_frame_split_noise(void * split, int * cells_xy, double * cell_sums, int3
 		NoiseEstimate e = ((FrameSplit *)split)->noise(pixel_map ? &map : nullptr);
 		if (pixel_map) memcpy(pixel_map, map.data(), map.size() * 4);
 		return noise_out(e, cells_xy, cell_sums, cell_counts, cell_nonfinite, cell_capacity, mean_figure, pixels_nonfinite);
+	GRT_CATCH(-1)
+}
+// Adaptive sampling. out4: cells, hot cells, active cells, list pixels.
+int grt_pathtracer_select_adaptive(void * pt, double threshold, long long * out4) {
+	GRT_TRY
+		AdaptiveSelection a = as_pathtracer(pt)->select_adaptive(float(threshold));
+		out4[0] = a.cells; out4[1] = a.hot_cells; out4[2] = a.active_cells; out4[3] = a.list_pixels;
+		return 0;
+	GRT_CATCH(-1)
+}
+int grt_pathtracer_adaptive_off(void * pt) {
+	GRT_TRY
+		as_pathtracer(pt)->adaptive_off();
+		return 0;
+	GRT_CATCH(-1)
+}
+// counts: pitch * height floats (w per pixel); mean: over the width * height pixels
+int grt_pathtracer_sample_counts(void * pt, float * counts, double * mean) {
+	GRT_TRY
+		std::vector<float> w;
+		double m = as_pathtracer(pt)->sample_counts(&w);
+		if (counts) memcpy(counts, w.data(), w.size() * 4);
+		if (mean) *mean = m;
+		return 0;
 	GRT_CATCH(-1)
 }
 int grt_pathtracer_resize(void * pt, int width, int height) {

@@ -15,6 +15,7 @@
 #include <functional>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../AO.h"
@@ -39,6 +40,7 @@ struct CommandLine {
 	bool help   = false;
 	bool print_config = false;
 	std::string noise_map;      // --noise-map
+	std::string sample_map;     // --sample-map
 };
 
 [[noreturn]] void die(const std::string & message) {
@@ -116,6 +118,13 @@ std::vector<Option> make_options(CommandLine & cl) {
 		cpu_config.noise_min_samples = n;
 	} });
 	o.push_back({ nullptr, "noise-map", "Writes the per-pixel relative standard error as a one-channel EXR (pixels that take no part are 0)", 1, [&cl](const char * v) { cl.noise_map = v; } });
+	o.push_back({ nullptr, "adaptive", "With --noise-target: after --noise-min-samples uniform samples, renders only the 16 x 16 cells whose noise is still above the target (DESIGN.md 7.6)", 0, [](const char *) { cpu_config.adaptive_sampling = 1; } });
+	o.push_back({ nullptr, "adaptive-dilate", "With --adaptive: 1 (default) keeps the neighbours of a noisy cell active too, 0 does not", 1, [](const char * v) {
+		int d = parse_int(v, "--adaptive-dilate");
+		if (d != 0 && d != 1) die("--adaptive-dilate must be 0 or 1");
+		cpu_config.adaptive_dilate = d;
+	} });
+	o.push_back({ nullptr, "sample-map", "Writes the number of samples every pixel's mean stands for as a one-channel EXR", 1, [&cl](const char * v) { cl.sample_map = v; } });
 	o.push_back({ nullptr, "force-rebuild", "BVH will not be loaded from disk but rebuilt from scratch", 0, [](const char *) { cpu_config.bvh_force_rebuild = true; } });
 	o.push_back({ "O",  "optimize",    "Enables or disables BVH optimization post-processing step", 1, [](const char * v) { cpu_config.enable_bvh_optimization = parse_bool(v); } });
 	o.push_back({ "Ot", "opt-time",    "Sets time limit for BVH optimization (milliseconds, as the reference stores it)", 1, [](const char * v) { cpu_config.bvh_optimizer_max_time = parse_int(v, "--opt-time"); } });
@@ -193,6 +202,7 @@ void parse_command_line(int argc, char ** argv, CommandLine & cl) {
 		print_help(options);
 		exit(0);
 	}
+	if (cpu_config.adaptive_sampling && !(cpu_config.noise_target > 0.0f)) die("--adaptive needs --noise-target: the cells are selected by it");
 	if (cl.print_config) { // one line, floats as bit patterns; the form oracle/ref/ref_scene_harness.cpp writes for the reference's Args::parse
 		auto bits = [](float f) { unsigned u; memcpy(&u, &f, 4); return u; };
 		std::string scenes;
@@ -214,12 +224,34 @@ struct NoiseStop {
 	bool active = false, warned = false, reached = false;
 	int interval = 1, next_check = 0;
 	NoiseEstimate last; bool have = false;
+	bool adaptive = false;               // --adaptive: every check that goes on selects the cells the next passes render
+	std::vector<double> active_share;    // ... and notes the share of the cells that stayed active
 	template<typename Renderer> bool should_stop(Renderer & r, int sample_index) {   // after a render call
 		if (!active || sample_index < cpu_config.noise_min_samples || sample_index < next_check) return false;
 		next_check = sample_index + interval;
 		last = r.noise(); have = true;
 		reached = last.pixels > 0 && last.figure <= double(cpu_config.noise_target);
+		if constexpr (std::is_same<Renderer, Pathtracer>::value) if (adaptive && !reached) {
+			AdaptiveSelection chosen = r.select_adaptive(cpu_config.noise_target);
+			active_share.push_back(double(chosen.active_cells) / double(chosen.cells));
+		}
 		return reached;
+	}
+	// --adaptive's lines of the final report, --sample-map
+	void report_samples(Pathtracer & r, const std::string & map_file, int pitch, int width, int height) {
+		if (!adaptive && map_file.empty()) return;
+		std::vector<float> counts;
+		double mean = r.sample_counts(&counts);
+		if (adaptive) {
+			// (w counts the samples past sample 0, which sample 1 overwrites: a pixel with w samples in its mean was rendered w + 1 times)
+			printf("Adaptive: %.3f samples per pixel on average; %.1f %% of the cells active at the end; per check:", mean + 1.0, active_share.empty() ? 100.0 : 100.0 * active_share.back());
+			for (double share : active_share) printf(" %.3f", share);
+			printf("\n");
+		}
+		if (!map_file.empty()) {
+			if (!EXRExporter::save_luminance(map_file, pitch, width, height, counts)) die("failed to write '" + map_file + "'");
+			printf("Wrote %s\n", map_file.c_str());
+		}
 	}
 	template<typename Renderer> void report(Renderer & r, int sample_index, const std::string & map_file, int pitch, int width, int height) {
 		if (active) {
@@ -259,8 +291,18 @@ int main(int argc, char ** argv) {
 			fprintf(stderr, "WARNING: --noise-target / --noise-map need plain path tracing (no SVGF, no AO integrator): ignored, rendering to -N\n");
 			cpu_config.noise_target = 0.0f; cl.noise_map.clear();
 		}
+		if ((cpu_config.adaptive_sampling || !cl.sample_map.empty()) && (gpu_config.enable_svgf || cpu_config.integrator == IntegratorType::AO)) {
+			fprintf(stderr, "WARNING: --adaptive / --sample-map need plain path tracing (no SVGF, no AO integrator): ignored\n");
+			cpu_config.adaptive_sampling = 0; cl.sample_map.clear();
+		}
+		if (cpu_config.adaptive_sampling && cl.devices.size() > 1) {   // (once: the tile split has no pixel lists)
+			fprintf(stderr, "WARNING: --adaptive does not work across --devices: rendering uniformly\n");
+			cpu_config.adaptive_sampling = 0;
+		}
+		if (!cl.sample_map.empty() && cl.devices.size() > 1) { fprintf(stderr, "WARNING: --sample-map does not work across --devices: ignored\n"); cl.sample_map.clear(); }
 		noise.active = cpu_config.noise_target > 0.0f;
-		if (!cl.noise_map.empty() && !noise.active) cpu_config.noise_target = 1e-30f;   // (keeps the moments; a target nothing reaches, and no stop is asked for)
+		noise.adaptive = noise.active && cpu_config.adaptive_sampling != 0;
+		if ((!cl.noise_map.empty() || !cl.sample_map.empty()) && !noise.active) cpu_config.noise_target = 1e-30f;   // (keeps the moments; a target nothing reaches, and no stop is asked for)
 		if (cl.devices.size() > 1) { // one frame over several GPUs
 			if (cpu_config.integrator == IntegratorType::AO) die("--devices: the tile split exists for the path tracer");
 			FrameSplit split(cpu_config.initial_width, cpu_config.initial_height, scene, cl.devices);
@@ -315,6 +357,7 @@ int main(int argc, char ** argv) {
 		double render_s = seconds_since(t1);
 		printf("Rendered sample %d at %dx%d in %.1f ms\n", integrator->sample_index, integrator->screen_width, integrator->screen_height, render_s * 1e3);
 		if (pathtracer) noise.report(*pathtracer, integrator->sample_index, cl.noise_map, integrator->screen_pitch, integrator->screen_width, integrator->screen_height);
+		if (pathtracer) noise.report_samples(*pathtracer, cl.sample_map, integrator->screen_pitch, integrator->screen_width, integrator->screen_height);
 
 		integrator->save_image(cpu_config.output_filename);
 		printf("Wrote %s\n", cpu_config.output_filename.c_str());

@@ -160,6 +160,8 @@ const char * rt_version(void);
  *      existing struct or call changed; point, spot and directional emitters, off until a table is uploaded)
  *      (still 17: rt_set_noise_estimate, rt_get_noise_estimate, rt_read_noise_moments, rt_estimate_noise, rt_accumulate_frames -- new entry points and a
  *      result struct of their own; the per-pixel noise estimate, off by default)
+ *      (still 17: rt_select_active_cells, rt_set_pixel_list, rt_get_pixel_list, rt_read_pixel_list, rt_select_pixels_images, rt_accumulate_list_frames
+ *      -- new entry points and a result struct of their own; adaptive sampling, off by default)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
 #define RT_ABI_VERSION 17
 int rt_abi_version(void);
@@ -614,6 +616,38 @@ typedef struct rt_noise_estimate {
 int rt_estimate_noise(rt_context * ctx, float floor, rt_noise_estimate * out, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite,
                       size_t cell_capacity, float * pixel_map);
 
+/* ---- adaptive sampling ---------------------------------------------------*/
+/* Which cells of the noise estimate still need samples, and their pixels as a list render calls can cover instead of the frame.
+ * rt_select_active_cells completes the work in flight, runs the noise kernel on the context's accumulator and moments, then selects:
+ * a cell c is HOT when  cell_counts[c] > 0 && cell_sums[c] > (double)threshold * (double)cell_counts[c]  (in double, in this shape), or
+ * when  cell_counts[c] + cell_nonfinite[c] <  its in-frame pixel count (it has pixels with w < 2, not sampled enough to judge). A cell
+ * whose pixels are all non-finite is not hot. A cell is ACTIVE when it is hot or, with dilate = 1, when one of its up to 8 neighbours
+ * inside the cell grid is hot. The list: one uint32 x + y * width per in-frame pixel of the active cells; the cells by ascending index,
+ * inside a cell the 8 x 8 patches (0,0), (8,0), (0,8), (8,8), a patch row by row, pixels outside the frame skipped (the list is dense).
+ * No atomics decide anything: the same bits on every run. The list stays with the context (pitch*height uint32, allocated at the first
+ * selection) until the next selection, rt_resize, rt_set_noise_estimate or a change of the pixel set, each of which also switches
+ * rt_set_pixel_list off; a uniform rt_render_samples of sample 0 or 1 -- a progression that starts over -- drops the selection too. cell_flags: NULL, or cell_capacity >= cells_x * cells_y bytes: bit 0 hot, bit 1 active.
+ * RT_ERROR_NOT_READY while the estimate is off; RT_ERROR_INVALID_ARG for a floor that is not finite and positive, a threshold that is
+ * not finite and >= 0, a dilate outside {0, 1}, a capacity that is too small, under a tile split or a pixel range, and while SVGF is on. */
+typedef struct rt_cell_selection {
+	int32_t cells_x, cells_y;
+	int64_t hot_cells, active_cells;
+	int64_t list_pixels;        /* the length of the list */
+} rt_cell_selection;
+int rt_select_active_cells(rt_context * ctx, float floor, float threshold, int dilate, rt_cell_selection * out, uint8_t * cell_flags, size_t cell_capacity);
+/* enable = 1: rt_render_samples covers the selected list instead of the frame. Every pixel folds with its OWN sample count: n = w + 1,
+ * w from the moments image, then n + 1 for each further sample of the call; sample_index is the random-number index only, and a pixel's
+ * primary ray and random numbers are the ones a uniform call with that sample_index gives it. Refused (RT_ERROR_INVALID_ARG) when no
+ * selection exists (under a pixel range other than the whole frame or a tile split none can: setting either drops it, and
+ * rt_select_active_cells is refused there), the list is empty, or SVGF is on. While on,
+ * rt_render_samples is refused -- never rendered uniformly -- under RT_SCHEDULER_SLOTS or wherever the merged wavefront would not be
+ * taken, for sample_index < 2, and so is rt_render_ao_sample. Both values complete the work in flight.                              */
+int rt_set_pixel_list(rt_context * ctx, int enable);
+int rt_get_pixel_list(const rt_context * ctx);
+/* The selected list: *out_count entries (also with dst == NULL); RT_ERROR_INVALID_ARG when capacity is below it, RT_ERROR_NOT_READY
+ * without a selection.                                                                                                                */
+int rt_read_pixel_list(rt_context * ctx, uint32_t * dst, size_t capacity, size_t * out_count);
+
 /* Kulla-Conty LUTs as computed on the device at first use (kernel_integrate_* /
  * kernel_average_*, CUDA/KullaConty.h:83-240): 16^3, 16^3, 16^2, 16^2, 32^2, 32 floats.
  * Any pointer may be NULL. Synchronous.                                                     */
@@ -769,13 +803,26 @@ int rt_shade_rays(rt_context * ctx, int merged, int step, int sample_index, int 
  * the RADIANCE mean, pitch*height float4; no other AOV is given to the kernel. moments (in / out): NULL -- the plain kernel runs -- or the
  * (M2_r, M2_g, M2_b, w) image, and the ..._moments kernel runs. final_image (out): pitch*height float4, filled with `sentinel` first; the
  * caller fills the in / out images, so a pixel outside the set keeps what it was given everywhere. Sample indices are >= 0 and stay below
- * 2^24. Leaves no state a frame reads. RT_ERROR_INVALID_ARG with a message for anything else, a NULL context first.                      */
+ * 2^24. Leaves no state a frame reads. RT_ERROR_INVALID_ARG with a message for anything else, a NULL context first -- and while the
+ * context covers a pixel list (rt_set_pixel_list): rt_accumulate_list_frames is the probe of that launch.                               */
 int rt_accumulate_frames(rt_context * ctx, int merged, const int32_t * first_sample, const int32_t * sample_count, size_t submissions,
                          float * frames, float * accumulator, float * moments, uint32_t sentinel, float * final_image);
 /* rt_estimate_noise's kernel on explicit images of the context's frame size (synchronous): mean and moments are pitch*height float4 from
  * the caller; everything else as rt_estimate_noise, which need not be enabled.                                                          */
 int rt_estimate_noise_images(rt_context * ctx, const float * mean, const float * moments, float floor, rt_noise_estimate * out, double * cell_sums,
                              int32_t * cell_counts, int32_t * cell_nonfinite, size_t cell_capacity, float * pixel_map);
+/* Selection and compaction (rt_select_active_cells' kernels) on explicit images of the context's frame size (synchronous): mean and
+ * moments are pitch*height float4. The cell arrays (cell_capacity >= cells_x * cells_y entries each; cell_flags bytes) and the list
+ * (list_capacity >= width * height entries; out->list_pixels are written) come back. Leaves the context's own list alone.            */
+int rt_select_pixels_images(rt_context * ctx, const float * mean, const float * moments, float floor, float threshold, int dilate, rt_cell_selection * out,
+                            double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, uint8_t * cell_flags, size_t cell_capacity,
+                            uint32_t * list, size_t list_capacity);
+/* ONE launch of the list accumulate launcher (what the merged wavefront runs for list submissions) on explicit images (synchronous):
+ * 1 .. 8 submissions of sample_count[k] samples; first_sample is passed on and does not enter the fold. frames, accumulator, moments
+ * (required), final_image and sentinel as in rt_accumulate_frames. list: list_count entries x + y * width. Refused before any launch
+ * (RT_ERROR_INVALID_ARG): an entry outside the frame and a pixel listed twice -- the fold is a plain read-modify-write.                */
+int rt_accumulate_list_frames(rt_context * ctx, const int32_t * first_sample, const int32_t * sample_count, size_t submissions,
+                              float * frames, float * accumulator, float * moments, const uint32_t * list, size_t list_count, uint32_t sentinel, float * final_image);
 /* Streaming-read bandwidth probe used as the measured HBM roofline (GB/s).                 */
 int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps);
 
