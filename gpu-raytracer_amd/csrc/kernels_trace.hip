@@ -19,6 +19,8 @@
 //     v_cvt_f32_ubyte0..3;
 //   * the dynamic-fetch heuristic of Ylitie et al. (section 4.4) is re-expressed for 64
 //     lanes: a wave goes back to fetch rays once it has lost RT_N_W lane-iterations.
+//   * in the merged wavefront's launch a shadow ray that reached its light only notes its queue index in a per-wave list in LDS; the wave adds the listed contributions
+//     to the frame together, an entry per lane, instead of three dependent memory trips in every refill (profiles/refill_pipeline.txt).
 // Triangle postponing (BVH8.h:200,234-240) is intentionally absent: every ray visits nodes
 // and triangles in exactly the order of the sequential algorithm, which keeps hits
 // bit-identical to the CPU oracle even when two triangles tie in t.
@@ -545,6 +547,19 @@ __shared__ int   shared_fetch[RT_TRACE_BLOCK / RT_WAVE_SIZE][4]; // per wave: ne
 // wait behind it in the middle of a round; from LDS it costs a fraction of that latency.
 #define RT_ROOTS_IN_LDS 1024
 __shared__ int   shared_roots[RT_ROOTS_IN_LDS];
+// The merged wavefront's launch: queue indices of the shadow rays of a wave that reached their light and whose contribution to the frame is still to be
+// added (bvh8_trace_engine: contribution_flush): 512 B per wave and the word that counts them, BEHIND the wave's four ray-claim words in one array -- one base address for
+// both, the one the engine holds anyway (an array of its own cost the flattened scene's kernel a register it did not have: 8 B of scratch). Only the kernels whose source
+// defers (source_defers_contributions) allocate it.
+#ifndef RT_SHADOW_BATCH
+#define RT_SHADOW_BATCH 1   // 0: every such ray adds its contribution in the refill in which it retires
+#endif
+#define RT_CONTRIBUTION_LIST (2 * RT_WAVE_SIZE)
+__shared__ int   shared_fetch_and_contributions[RT_TRACE_BLOCK / RT_WAVE_SIZE][8 + RT_CONTRIBUTION_LIST];   // per wave: the four words of shared_fetch, the count, three unused, the list
+// A source whose unoccluded shadow rays may add their contribution at any time before the launch ends says so with contribute(i): finish(i) of such a ray, callable for
+// any queue index by any lane.
+template<typename Source, typename = void> struct source_defers_contributions { static constexpr bool value = false; };
+template<typename Source> struct source_defers_contributions<Source, decltype(void(&Source::contribute))> { static constexpr bool value = RT_SHADOW_BATCH != 0; };
 // The common traversal engine. RaySource supplies rays and consumes results so that the same
 // code serves the wavefront queues and the stand-alone entry points.
 // COUNT adds per-ray work counters (nodes fetched, triangles tested, instance entries) that are
@@ -563,6 +578,28 @@ template<int MODE, typename Source> RT_DEV void source_finish(const Source & src
 	if constexpr (MODE == RT_TRACE_MIXED) src.finish(shadow, i, hit, occluded); else src.finish(i, hit, occluded);
 }
 
+// Probe build only (RT_WAVE_CLOCK, see trace_stream below): the time a wave spends in the refill block at the top of the engine's outer loop -- the hand-over of finished
+// rays, fetch_ray and the load of the new rays, up to the arrival of their values (the wait the shipped kernel takes in front of reciprocal()) -- as ticks of the constant-rate
+// clock, summed per wave next to the number of refills and the wave's time in the engine. The part of it up to the end of the hand-over (list appends and flushes included; its stores issued, not waited for) is summed on its own. A lane leaves its sums in refill_probe[0..3] when it leaves the engine; the caller
+// takes the largest of the wave's lanes (the lane that left last). With the macro off the six hooks are empty and the kernels' code is what it is without them.
+#ifdef RT_WAVE_CLOCK
+#define RT_REFILL_PROBE_PARAMETER , unsigned * refill_probe = nullptr
+#define RT_REFILL_PROBE_ENTER const unsigned long long probe_entered = __builtin_amdgcn_s_memrealtime(); unsigned long long probe_begin = probe_entered; unsigned probe_ticks = 0, probe_refills = 0, probe_handover = 0;
+#define RT_REFILL_PROBE_BEGIN __builtin_amdgcn_sched_barrier(0); probe_begin = __builtin_amdgcn_s_memrealtime(); __builtin_amdgcn_sched_barrier(0);
+#define RT_REFILL_PROBE_MID   __builtin_amdgcn_sched_barrier(0); probe_handover += unsigned(__builtin_amdgcn_s_memrealtime() - probe_begin); __builtin_amdgcn_sched_barrier(0);   /* (issue only: no wait for the hand-over's stores) */
+#define RT_REFILL_PROBE_END   __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0x0070); /* vmcnt(0) lgkmcnt(0) */ \
+	probe_ticks += unsigned(__builtin_amdgcn_s_memrealtime() - probe_begin); probe_refills++; __builtin_amdgcn_sched_barrier(0);
+#define RT_REFILL_PROBE_LEAVE if (refill_probe) { const unsigned long long probe_now = __builtin_amdgcn_s_memrealtime(); \
+	refill_probe[0] = probe_ticks + unsigned(probe_now - probe_begin); refill_probe[1] = probe_refills + 1; refill_probe[2] = unsigned(probe_now - probe_entered); refill_probe[3] = probe_handover; }
+#else
+#define RT_REFILL_PROBE_PARAMETER
+#define RT_REFILL_PROBE_ENTER
+#define RT_REFILL_PROBE_BEGIN
+#define RT_REFILL_PROBE_MID
+#define RT_REFILL_PROBE_END
+#define RT_REFILL_PROBE_LEAVE
+#endif
+
 // UNIFIED: the TLAS nodes have been copied into the slots [0, tlas_node_count) that the BLAS node array reserves for them
 // (the merged wavefront does that whenever the TLAS changes, rt_api.hip: stream_sync_tlas), so a node is fetched from ONE
 // base address: no compare / select of two 64-bit bases and no scalar load of the TLAS size in every round.
@@ -573,8 +610,10 @@ template<int MODE, typename Source> RT_DEV void source_finish(const Source & src
 // MASK: opacity masks (opacity_accepts above; launched only while p.opacity_active). A rejected candidate moves nothing, so the skipping walk needs
 // nothing else: hit.t only ever moves on accepted hits.
 template<int MODE, bool COUNT, bool NARROW, bool UNIFIED = false, bool FLAT = false, bool SKIP = false, bool MASK = false, typename Source>
-RT_DEV void bvh8_trace_engine(const RtParams & p, Source & src, int ray_count, int * cursor, unsigned long long * stats = nullptr, int ray_count_2 = 0, int * cursor_2 = nullptr, int * regions = nullptr) {
+RT_DEV void bvh8_trace_engine(const RtParams & p, Source & src, int ray_count, int * cursor, unsigned long long * stats = nullptr, int ray_count_2 = 0, int * cursor_2 = nullptr, int * regions = nullptr RT_REFILL_PROBE_PARAMETER) {
+	RT_REFILL_PROBE_ENTER
 	constexpr bool SHADOW = MODE == RT_TRACE_SHADOW;   // the kind of every ray, unless MODE == RT_TRACE_MIXED: then lane_shadow
+	constexpr bool DEFER = MODE != RT_TRACE_CLOSEST && source_defers_contributions<Source>::value;   // unoccluded shadow rays go on the wave's list (contribution_flush below)
 	bool lane_shadow = SHADOW;
 	#define RT_IS_SHADOW (MODE == RT_TRACE_MIXED ? lane_shadow : SHADOW)
 	const float4 * __restrict__ nodes     = p.bvh8_nodes;
@@ -614,8 +653,27 @@ RT_DEV void bvh8_trace_engine(const RtParams & p, Source & src, int ray_count, i
 	// volatile: the words are written by one lane and read by OTHER lanes of the same wave with no
 	// barrier in between; without it the compiler forwards a lane's own last view of them.
 	typedef volatile __attribute__((address_space(3))) int LdsFetchWord; // typed: ds_read/ds_write, not FLAT
-	LdsFetchWord * fetch_state = (LdsFetchWord *)&shared_fetch[wave][0];
+	LdsFetchWord * fetch_state = DEFER ? (LdsFetchWord *)&shared_fetch_and_contributions[wave][0] : (LdsFetchWord *)&shared_fetch[wave][0];
 	if (lane == 0) { fetch_state[0] = 0; fetch_state[1] = 0; fetch_state[2] = 0; fetch_state[3] = 0; }
+	// A shadow ray that reached its light adds its illumination to the frame: a load of (illumination, pixel), a load of the pixel and a store, each waiting for the one
+	// before it -- three HBM-class trips that stalled the whole wave in the refill for the ~5 of 64 lanes that had such a ray. Such a lane now only notes its queue index
+	// in the wave's list in LDS; the list is flushed by all lanes of the wave together, an entry per lane, when it holds a wave's worth (so that the appends of one more
+	// refill always fit) and by the lanes that leave the engine.
+	LdsFetchWord * contribution_count = fetch_state + 4;
+	if (DEFER && lane == 0) contribution_count[0] = 0;
+	// Called converged by any subset of the wave's lanes: they share the `held` entries among them.
+	// The order in which contributions reach the frame is free: a path has at most one shadow ray in a launch and a (virtual) pixel belongs to one path, so a pixel has ONE
+	// contributor per launch -- no two entries of any wave's list name the same pixel -- and the traversal launch writes nothing else to these frames.
+	auto contribution_flush = [&](int held) {
+		if constexpr (DEFER) {
+			const unsigned long long live = __ballot(1);
+			const int step = __popcll(live);
+			// (the list's address is made here, from a copy of the claim words' that the compiler cannot see through: hoisted out of the engine's loops it was a register held
+			// through every round, which the flattened scene's kernel does not have -- 8 B of scratch)
+			LdsFetchWord * contribution_list = fetch_state; asm volatile("" : "+v"(contribution_list)); contribution_list += 8;
+			for (int entry = int(__builtin_amdgcn_mbcnt_hi(unsigned(live >> 32), __builtin_amdgcn_mbcnt_lo(unsigned(live), 0u))); entry < held; entry += step) src.contribute(contribution_list[entry]);
+		}
+	};
 	// Called (converged) by the lanes that need a ray; returns its index or -1 once the launch is drained.
 	// Narrow mode: whole groups call it, every lane of a group gets the group's ray.
 	// Mixed launches: fetch_state[3] says which queue the wave is claiming from (0: closest hit, 1: shadow); a wave moves on
@@ -740,8 +798,23 @@ RT_DEV void bvh8_trace_engine(const RtParams & p, Source & src, int ray_count, i
 	// next round's loads (one counter for both on this chip: a wait for a load is a wait for every store before it).
 	int result_pending = 0;   // 1: finished (closest hit or a shadow ray that reached its light), 2: shadow ray occluded
 	while (true) {
+		RT_REFILL_PROBE_BEGIN
 		bool inactive = stack.size == 0 && current_group.y == 0 && triangle_group.y == 0;
 
+		if constexpr (DEFER) {
+			const bool append = RT_IS_SHADOW && result_pending == 1 && (!NARROW || group_child == 0);
+			const unsigned long long appenders = __ballot(append);
+			if (appenders) {   // (the same for every lane)
+				int held = contribution_count[0];
+				if (held >= RT_WAVE_SIZE) { contribution_flush(held); held = 0; }
+				const unsigned rank = __builtin_amdgcn_mbcnt_hi(unsigned(appenders >> 32), __builtin_amdgcn_mbcnt_lo(unsigned(appenders), 0u));
+				if (append) {
+					fetch_state[8 + held + int(rank)] = ray_index;
+					if (rank == 0) contribution_count[0] = held + __popcll(appenders);
+				}
+			}
+			if (RT_IS_SHADOW) result_pending = 0;
+		}
 		if (result_pending) {
 			if (!RT_IS_SHADOW && p.has_triangle_aliases && hit.triangle_id != RT_INVALID) { // a copy in the flattened static BLAS reports its original (rt_upload_triangle_aliases)
 				float4 names = triangles[size_t(hit.triangle_id) * 3 + 2];
@@ -750,9 +823,15 @@ RT_DEV void bvh8_trace_engine(const RtParams & p, Source & src, int ray_count, i
 			if (!NARROW || group_child == 0) source_finish<MODE>(src, RT_IS_SHADOW, ray_index, hit, result_pending == 2);
 			result_pending = 0;
 		}
+		RT_REFILL_PROBE_MID
 		if (inactive) {
 			ray_index = fetch_ray();
-			if (ray_index < 0) { if constexpr (COUNT) flush_counts(); return; }
+			if (ray_index < 0) {   // drained: this lane leaves (the lanes still in a ray follow at later refills, the last of them after the wave's last append)
+				if constexpr (DEFER) { const int held = contribution_count[0]; if (held) { contribution_flush(held); contribution_count[0] = 0; } }
+				if constexpr (COUNT) flush_counts();
+				RT_REFILL_PROBE_LEAVE
+				return;
+			}
 
 			float max_distance;
 			source_load<MODE>(src, RT_IS_SHADOW, ray_index, ray, max_distance);   // (closest-hit sources: infinity)
@@ -768,6 +847,7 @@ RT_DEV void bvh8_trace_engine(const RtParams & p, Source & src, int ray_count, i
 			current_group   = make_uint2(0, 0x80000000u);
 			tlas_stack_size = FLAT ? 0 : p.entry_tlas_stack_size;
 		}
+		RT_REFILL_PROBE_END
 
 		int iterations_lost = 0;
 		bool running = true;   // a lane that has finished its ray idles (masked) until the wave refills
@@ -1034,8 +1114,9 @@ struct ShadowStreamSource {
 	RtShadowBuffer buffer;
 	RtAOV radiance, direct, indirect;
 	RT_DEV void load(int i, Ray3 & ray, float & max_distance) const { ray.origin = load3(buffer.origin, i); ray.direction = load3(buffer.direction, i); max_distance = buffer.max_distance[i]; }
-	RT_DEV void finish(int i, const HitRecord &, bool occluded) const {
-		if (occluded) return;
+	RT_DEV void finish(int i, const HitRecord &, bool occluded) const { if (!occluded) contribute(i); }
+	// (what the miss lambda does; the engine calls it for the entries of a wave's list, see source_defers_contributions)
+	RT_DEV void contribute(int i) const {
 		float4 ip = buffer.illumination_and_pixel_index[i];
 		unsigned pixel_word = __float_as_uint(ip.w);
 		int pixel_index = int(pixel_word & ~RT_SHADOW_FLAG_BOUNCE_0);
@@ -1322,6 +1403,7 @@ struct MixedStreamSource {
 	ClosestHitSource closest; ShadowStreamSource shadow;
 	RT_DEV void load(bool is_shadow, int i, Ray3 & ray, float & max_distance) const { if (is_shadow) shadow.load(i, ray, max_distance); else closest.load(i, ray, max_distance); }
 	RT_DEV void finish(bool is_shadow, int i, const HitRecord & hit, bool occluded) const { if (is_shadow) shadow.finish(i, hit, occluded); else closest.finish(i, hit, occluded); }
+	RT_DEV void contribute(int i) const { shadow.contribute(i); }
 };
 #ifdef RT_WAVE_CLOCK
 // Probe build (tools/build_trace_variant.sh waveclock "-DRT_WAVE_CLOCK=1"; tools/wave_clock_probe.py): every wave of the merged wavefront's traversal launch leaves the
@@ -1334,27 +1416,43 @@ extern "C" int rt_debug_read_wave_clock(void * clocks, void * meta) {
 	if (hipMemcpyFromSymbol(clocks, HIP_SYMBOL(grt_wave_clock), sizeof(grt_wave_clock)) != hipSuccess) return 1;
 	return hipMemcpyFromSymbol(meta, HIP_SYMBOL(grt_wave_clock_meta), sizeof(grt_wave_clock_meta)) != hipSuccess;
 }
-template<bool COUNT, bool FLAT = false, bool SKIP = false, bool MASK = false> RT_DEV void trace_stream_probed(const RtParams & p, unsigned long long * stats, unsigned long long * mid);
+// ... and what the engines' refill probe summed (RT_REFILL_PROBE_*): per wave and engine -- 0: closest hit, 1: shadow (the two engines of a launch above RT_MIXED_MAX_RAYS),
+// 2: mixed -- {ticks inside the refill block, refills, ticks inside the engine, ticks of the block's hand-over part}; zeros for an engine the wave did not run.
+__device__ unsigned grt_refill_clock[RT_WAVE_CLOCK_SLOTS][RT_WAVE_CLOCK_WAVES][3][4];
+extern "C" int rt_debug_read_refill_clock(void * ticks) {
+	return hipMemcpyFromSymbol(ticks, HIP_SYMBOL(grt_refill_clock), sizeof(grt_refill_clock)) != hipSuccess;
+}
+template<bool COUNT, bool FLAT = false, bool SKIP = false, bool MASK = false> RT_DEV void trace_stream_probed(const RtParams & p, unsigned long long * stats, unsigned long long * mid, unsigned (* refill)[4]);
 template<bool COUNT, bool FLAT = false, bool SKIP = false, bool MASK = false>
 RT_DEV void trace_stream(const RtParams & p, unsigned long long * stats) {
 	const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
 	unsigned long long t1 = 0;
-	trace_stream_probed<COUNT, FLAT, SKIP, MASK>(p, stats, &t1);
+	unsigned refill[3][4] = { { 0, 0, 0, 0 }, { 0, 0, 0, 0 }, { 0, 0, 0, 0 } };
+	trace_stream_probed<COUNT, FLAT, SKIP, MASK>(p, stats, &t1, refill);
 	const unsigned long long t2 = __builtin_amdgcn_s_memrealtime();
+	#pragma unroll
+	for (int k = 0; k < 12; k++) {   // the lane that left an engine last holds the wave's sums
+		unsigned v = refill[k / 4][k % 4];
+		for (int offset = RT_WAVE_SIZE / 2; offset > 0; offset >>= 1) v = max(v, unsigned(__shfl_xor(int(v), offset)));
+		refill[k / 4][k % 4] = v;
+	}
 	if ((threadIdx.x & 63) == 0) {
 		const int slot = p.stream_iteration % RT_WAVE_CLOCK_SLOTS, wave = blockIdx.x * (RT_TRACE_BLOCK / RT_WAVE_SIZE) + threadIdx.x / RT_WAVE_SIZE;
+		if (wave < RT_WAVE_CLOCK_WAVES) for (int k = 0; k < 12; k++) grt_refill_clock[slot][wave][k / 4][k % 4] = refill[k / 4][k % 4];
 		if (wave < RT_WAVE_CLOCK_WAVES) { grt_wave_clock[slot][wave][0] = t0; grt_wave_clock[slot][wave][1] = t1 ? t1 : t2; grt_wave_clock[slot][wave][2] = t2; }
 		if (wave == 0) { const int q = p.stream_iteration & 1; grt_wave_clock_meta[slot][0] = p.stream_iteration; grt_wave_clock_meta[slot][1] = p.stream->trace_count[q]; grt_wave_clock_meta[slot][2] = p.stream->shadow_count[q ^ 1]; grt_wave_clock_meta[slot][3] = gridDim.x * (RT_TRACE_BLOCK / RT_WAVE_SIZE); }
 	}
 }
 #define trace_stream_body trace_stream_probed
-#define RT_WAVE_CLOCK_MID , unsigned long long * mid
+#define RT_WAVE_CLOCK_MID , unsigned long long * mid, unsigned (* refill)[4]
+#define RT_REFILL_PROBE_OF(engine) , refill[engine]
 #define RT_WAVE_CLOCK_MARK *mid = __builtin_amdgcn_s_memrealtime();
 #else
 template<bool COUNT, bool FLAT = false, bool SKIP = false, bool MASK = false> RT_DEV void trace_stream(const RtParams & p, unsigned long long * stats);
 #define trace_stream_body trace_stream
 #define RT_WAVE_CLOCK_MID
 #define RT_WAVE_CLOCK_MARK
+#define RT_REFILL_PROBE_OF(engine)
 #endif
 template<bool COUNT, bool FLAT, bool SKIP, bool MASK>
 RT_DEV void trace_stream_body(const RtParams & p, unsigned long long * stats RT_WAVE_CLOCK_MID) {
@@ -1377,11 +1475,11 @@ RT_DEV void trace_stream_body(const RtParams & p, unsigned long long * stats RT_
 	if (!COUNT && closest_count + shadow_count <= RT_NARROW_MAX_RAYS)
 		bvh8_trace_engine<RT_TRACE_MIXED, false, true, true, FLAT, SKIP, MASK>(p, src, closest_count, &p.stream->cursor[q][0], nullptr, shadow_count, &p.stream->cursor[q][1]);
 	else if (COUNT || closest_count + shadow_count <= RT_MIXED_MAX_RAYS)
-		bvh8_trace_engine<RT_TRACE_MIXED, COUNT, false, true, FLAT, SKIP, MASK>(p, src, closest_count, &p.stream->cursor[q][0], stats, shadow_count, &p.stream->cursor[q][1], RT_ENDGAME ? &p.stream->endgame[q][0][0] : nullptr);
+		bvh8_trace_engine<RT_TRACE_MIXED, COUNT, false, true, FLAT, SKIP, MASK>(p, src, closest_count, &p.stream->cursor[q][0], stats, shadow_count, &p.stream->cursor[q][1], RT_ENDGAME ? &p.stream->endgame[q][0][0] : nullptr RT_REFILL_PROBE_OF(2));
 	else {
-		bvh8_trace_engine<RT_TRACE_CLOSEST, false, false, true, FLAT, SKIP, MASK>(p, src.closest, closest_count, &p.stream->cursor[q][0], nullptr, 0, nullptr, RT_ENDGAME ? &p.stream->endgame[q][0][0] : nullptr);
+		bvh8_trace_engine<RT_TRACE_CLOSEST, false, false, true, FLAT, SKIP, MASK>(p, src.closest, closest_count, &p.stream->cursor[q][0], nullptr, 0, nullptr, RT_ENDGAME ? &p.stream->endgame[q][0][0] : nullptr RT_REFILL_PROBE_OF(0));
 		RT_WAVE_CLOCK_MARK
-		bvh8_trace_engine<RT_TRACE_SHADOW,  false, false, true, FLAT, false, MASK>(p, src.shadow,  shadow_count,  &p.stream->cursor[q][1], nullptr, 0, nullptr, RT_ENDGAME ? &p.stream->endgame[q][1][0] : nullptr);   // (a shadow ray's limit never moves: nothing to skip)
+		bvh8_trace_engine<RT_TRACE_SHADOW,  false, false, true, FLAT, false, MASK>(p, src.shadow,  shadow_count,  &p.stream->cursor[q][1], nullptr, 0, nullptr, RT_ENDGAME ? &p.stream->endgame[q][1][0] : nullptr RT_REFILL_PROBE_OF(1));   // (a shadow ray's limit never moves: nothing to skip)
 	}
 }
 __global__ void __launch_bounds__(RT_TRACE_BLOCK, RT_TRACE_LAUNCH_WAVES) kernel_trace_stream_bvh8(RtParams p) { trace_stream<false>(p, nullptr); }
