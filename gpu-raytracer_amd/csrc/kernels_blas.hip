@@ -24,34 +24,13 @@
 // invariants with the independent decoder of tests/test_tlas.py. A Morton tree is cheaper to build and dearer to traverse
 // than the SAH tree (measured: profiles/r03_device_blas.txt): the host classes use it on request (device_blas = 1).
 #include "rt_math.h"
-#include "rt_tlas_build.h"
+#include "rt_build_args.h"
 #include <algorithm>
 
 #include <cstring>   // (rocPRIM's texture iterator calls memset from host code without including it)
 #include <rocprim/rocprim.hpp>
 
 #define RT_BLAS_LEAF 3     // triangles per leaf (the meta byte holds their count in unary: BVH8Converter.cpp:293-303)
-
-struct BlasBuildArgs {
-	int triangle_count, mesh_count, first_node;     // first_node: index of mesh 0's root (node slots below it are reserved for the TLAS)
-	const float4 * triangles;                        // input, 6 float4 each, meshes back to back
-	const int * mesh_first;                          // [mesh_count + 1]
-	float4 * triangles_out, * positions_out;         // leaf order: 6 resp. 3 float4 per triangle
-	uint32_t * nodes;                                // 20 words per node
-	int * order, * position;                         // leaf position -> input triangle, and back
-	// scratch
-	TlasBox * triangle_boxes, * sorted_boxes, * mesh_boxes, * child_boxes;
-	TlasBox * box_table;                             // [table_levels][triangle_count]: entry (j, i) = box of sorted triangles [i, i + 2^(j+1)), clamped at the end (level 0 of the idea is sorted_boxes)
-	int table_levels, split_widest;                  // split_widest: the round-3 rule (the piece with the most triangles first), for comparison
-	int * triangle_mesh;
-	uint64_t * keys; int * ids;                      // unsorted
-	uint64_t * sorted_keys; int * sorted_ids;
-	int2 * range;                                    // per node: its run [lo, hi) of the sorted order
-	int * runs;                                      // per node of the level: begin[9], children, inner children, leaf triangles
-	int * inner_count, * leaf_count, * inner_base, * leaf_base;   // per node of the level
-	int * level_state;                               // { nodes used, triangles placed, nodes of the next level }
-	const float * given_boxes; int given_first, given_count;   // rt_set_build_boxes: triangles [given_first, given_first + given_count) come with boxes of their own (6 floats: min, max), null / 0: none
-};
 
 // Step 1 in three launches, all of them as wide as the input: a mesh's box used to be reduced by ONE workgroup per mesh, which is the whole chip
 // idle behind one CU when the "mesh" is a flattened scene of half a million triangles (2 of that build's 2.8 ms). Floats are accumulated as integers

@@ -25,32 +25,10 @@
 // (diagnostic build RT_TLAS_PHASE_TIMES, profiles/r02_device_tlas_phases.txt). Everything a lane touches now has a
 // compile-time index.
 #include "rt_math.h"
-#include "rt_tlas_build.h"
+#include "rt_build_args.h"
 
 #define RT_BUILD_THREADS 1024
 #define RT_BUILD_SMALL   1024   // instances up to which 256 threads build and the sorted boxes live in LDS
-
-struct TlasBuildArgs {
-	int count;                       // instances
-	// scene order inputs
-	const int    * root_indices;     // BLAS root | identity flag << 31
-	const int    * material_ids;
-	const float4 * transforms, * transforms_inv, * transforms_prev; // 3 float4 per instance
-	const float  * local_boxes;      // 6 floats per instance: object-space min, max of its BLAS
-	// TLAS order outputs
-	uint32_t * nodes;                // 20 words per node, capacity 2 * count nodes
-	int      * out_root_indices, * out_material_ids;
-	float4   * out_transforms, * out_transforms_inv, * out_transforms_prev;
-	int      * order;                // position -> scene index
-	int      * position;             // scene index -> position
-	int      * node_count;
-	// scratch (global): boxes[count], queues 2 x count x {node, lo, hi}, per level-node records
-	TlasBox  * boxes, * sorted_boxes;
-	int      * queue;                // [2][count][3]
-	int      * runs;                 // [count][12]: begin[9], children, inner children, leaf children
-	int      * bases;                // [count][2]: first child node index, first leaf position
-	TlasBox  * child_boxes;          // (unused since the lane-per-child build; kept for the layout of the scratch area)
-};
 
 // min / max / or over the 8 lanes of a group (xor shuffles stay inside the group)
 RT_DEV float group8_fmin(float v) { v = tlas_minf(v, __shfl_xor(v, 1)); v = tlas_minf(v, __shfl_xor(v, 2)); return tlas_minf(v, __shfl_xor(v, 4)); }

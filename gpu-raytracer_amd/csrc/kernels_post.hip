@@ -849,7 +849,7 @@ RT_DEV f3 clamp3(f3 v, f3 lo, f3 hi) { return mk3(clampf(v.x, lo.x, hi.x), clamp
 // Reads taa_frame_curr (3 x 3 around the pixel) and taa_frame_prev (4 x 4 around where the pixel was), and writes what the reference's
 // kernel_taa and kernel_taa_finalize write between them (TAA.h:10-172): the resolved colour as the NEXT frame's history, the displayed image
 // (the tone mapping undone), the cleared motion vector. The history goes to a third image, taa_frame_next -- other threads are still reading
-// taa_frame_prev --, and the host swaps the two pointers after the launch (rt_api.hip: after every rt_launch_svgf_taa). The reference needs
+// taa_frame_prev --, and the host swaps the two pointers after the launch (rt_api.hip, rt_render.hip, rt_stream.hip: after every rt_launch_svgf_taa). The reference needs
 // the second kernel because it resolves in place; here that pass (read 16, write 40 bytes per pixel) is gone.
 __global__ void __launch_bounds__(256) kernel_taa(RtParams p, int sample_index) {
 	int x, y;

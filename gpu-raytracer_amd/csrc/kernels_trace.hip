@@ -601,7 +601,7 @@ template<int MODE, typename Source> RT_DEV void source_finish(const Source & src
 #endif
 
 // UNIFIED: the TLAS nodes have been copied into the slots [0, tlas_node_count) that the BLAS node array reserves for them
-// (the merged wavefront does that whenever the TLAS changes, rt_api.hip: stream_sync_tlas), so a node is fetched from ONE
+// (the merged wavefront does that whenever the TLAS changes, rt_stream.hip: stream_sync_tlas), so a node is fetched from ONE
 // base address: no compare / select of two 64-bit bases and no scalar load of the TLAS size in every round.
 // FLAT: the whole scene is one world-space tree rooted in node 0 (rt_set_static_geometry): there is no TLAS to walk, no instance
 // to enter or leave, no object-space ray -- the code for those and the three registers that track them are compiled out.

@@ -1,5 +1,7 @@
-// rt_context.h -- what the units of the C ABI (rt_api.hip, rt_exchange.hip, rt_probes.hip) share: the context and the structs it is made of,
-// error handling, and the internal functions that cross a unit boundary. Private to csrc/.
+// rt_context.h -- what the units of the C ABI share: the context and the structs it is made of, error handling, and the internal functions that
+// cross a unit boundary. The units: rt_api.hip (context, frame state, results), rt_scene.hip (scene uploads and device builds), rt_render.hip (the slot
+// scheduler and the render entry points), rt_stream.hip (the merged wavefront's host side), rt_noise.hip (noise estimate, adaptive sampling),
+// rt_exchange.hip (frame exchange of the tile split), rt_probes.hip (kernel-level entry points). Private to csrc/.
 #pragma once
 #include "rt_types.h"
 
@@ -238,32 +240,59 @@ struct rt_context {
 	std::vector<hipEvent_t> stage_events; std::vector<int> stage_kinds; size_t stage_used = 0;
 };
 
-// Internal functions that cross a unit boundary, all defined in rt_api.hip (where each is described). Hidden: the library exports the C ABI only.
-// C linkage because some are defined between the entry points, inside their extern "C" blocks.
+// SVGF g-buffers: a set is three images, bytes per pixel: normal + depth (float4), mesh + triangle id (int2), previous screen position (float2).
+// gbuffer_bytes: member i of one set at the current frame size. stream_gbuffer: member i of the set of the merged wavefront's sample slot `slot`
+// (PathStream::gbuffers[i] holds frame_slots sets, one behind the other).
+static const size_t gbuffer_pixel_bytes[3] = { 16, 8, 8 };
+inline size_t gbuffer_bytes(const rt_context * ctx, int i) { return ctx->frame_pixels * gbuffer_pixel_bytes[i]; }
+inline void * stream_gbuffer(const rt_context * ctx, int i, int slot) { return (char *)ctx->path_stream.gbuffers[i] + gbuffer_bytes(ctx, i) * size_t(slot); }
+
+// Internal functions that cross a unit boundary, by the unit that defines them (where each is described). Hidden: the library exports the C ABI only.
 #pragma GCC visibility push(hidden)
-extern "C" {
+// rt_api.hip
 int fail(rt_context * ctx, int status, const char * fmt, ...);
 int device_alloc(rt_context * ctx, void ** out, size_t bytes);
 void device_free(rt_context * ctx, void * p);
 hipError_t quiesce(rt_context * ctx);
 hipError_t main_waits_for_samples(rt_context * ctx);
-RtParams slot_params(const rt_context * ctx, const SampleSlot & slot, int index);
 int check_ready(rt_context * ctx, const char * caller, int needs);
 int resolve_pixel_range(rt_context * ctx, const char * caller, int * out_offset, int * out_count);
+// rt_scene.hip
+int mark_scene_versions_in_use(rt_context * ctx, int slot_index, hipStream_t st);
 int sky_tables_build(rt_context * ctx, const char * caller);
 int sky_sampling_prepare(rt_context * ctx, const char * caller);
-int ensure_queues(rt_context * ctx, int slot_index = 0, size_t pixels = 0);
 int ensure_luts(rt_context * ctx);
+// rt_render.hip
+void use_queues(RtParams & p, const WavefrontQueues & q);
+int queues_allocate(rt_context * ctx, WavefrontQueues & q, size_t entries);
+void queues_free(rt_context * ctx, WavefrontQueues & q);
+int ensure_slot(rt_context * ctx, int index);
+RtParams slot_params(const rt_context * ctx, const SampleSlot & slot, int index);
+int ensure_queues(rt_context * ctx, int slot_index = 0, size_t pixels = 0);
+void stage_mark(rt_context * ctx, int kind, hipStream_t stream);
+void span_mark(rt_context * ctx, int kind, hipStream_t stream);
+// rt_stream.hip
 int stream_create(rt_context * ctx);
+void stream_destroy(rt_context * ctx);
+void stream_save_gbuffers(rt_context * ctx);
+void stream_release_frames(rt_context * ctx);
 RtParams stream_params(const rt_context * ctx, int iteration);
 int stream_sync_tlas(rt_context * ctx);
+int stream_enqueue_iteration(rt_context * ctx);
+int stream_launch_pending(rt_context * ctx);
+hipError_t stream_flush(rt_context * ctx);
+int stream_submit(rt_context * ctx, int sample_index, int sample_count, int range_offset, int range_count);
+// rt_noise.hip
+void pixel_list_drop(rt_context * ctx);
+void pixel_list_free(rt_context * ctx);
+int sync_noise_moments(rt_context * ctx);
+int noise_moments_reset(rt_context * ctx);
 float4 * noise_moments_for(const rt_context * ctx, const RtParams & p);
 int noise_estimate_images(rt_context * ctx, const char * caller, const float4 * mean, const float4 * moments, float floor, rt_noise_estimate * out,
                           double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, size_t cell_capacity, float * pixel_map);
 int selection_arguments(rt_context * ctx, const char * caller, float floor, float threshold, int dilate);
 int select_cells_images(rt_context * ctx, const char * caller, const float4 * mean, const float4 * moments, float floor, float threshold, int dilate, unsigned * list,
                         rt_cell_selection * out, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, uint8_t * cell_flags, size_t cell_capacity);
-}
 #pragma GCC visibility pop
 
 #define RT_HIP(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(ctx, RT_ERROR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
@@ -272,3 +301,9 @@ int select_cells_images(rt_context * ctx, const char * caller, const float4 * me
 // What a render or trace entry point needs uploaded before it launches anything. NEED_SCENE reports missing geometry
 // and missing instances apart; NEED_SCENE_JOINT (the explicit-ray entry points) reports them as one.
 enum { NEED_SCENE = 1, NEED_SCENE_JOINT = 2, NEED_MATERIALS = 4, NEED_RNG = 8, NEED_SKY = 16, NEED_FRAME = 32 };
+
+// the `kind` of stage_mark (rt_set_profiling(ctx, 1))
+enum { STAGE_GENERATE = 0, STAGE_TRACE, STAGE_SORT, STAGE_SHADE, STAGE_SHADOW, STAGE_POST, STAGE_END };
+// what a [begin, end] event pair of rt_set_profiling(ctx, 2 / 3) brackets (the `kind` of rt_get_launch_timings)
+enum { SPAN_TRACE = RT_TIMING_TRACE, SPAN_SHADOW = RT_TIMING_SHADOW, SPAN_SORT = RT_TIMING_SORT, SPAN_GENERATE = RT_TIMING_GENERATE, SPAN_ACCUMULATE = RT_TIMING_ACCUMULATE,
+       SPAN_MATERIAL = RT_TIMING_MATERIAL_0, SPAN_SVGF = RT_TIMING_SVGF_REPROJECT };

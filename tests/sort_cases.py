@@ -143,7 +143,7 @@ class World:
         self.pt.close(); self.scene.close(); self.grt.config_reset()
 
     def effective_share(self, setup, config):
-        """RtParams::sky_nee_share as a render settles it (rt_api.hip: sky_sampling_prepare)."""
+        """RtParams::sky_nee_share as a render settles it (rt_scene.hip: sky_sampling_prepare)."""
         if setup.sky_sampling <= 0 or not config.enable_next_event_estimation:
             return 0.0
         return setup.sky_sampling if setup.lights else 1.0
