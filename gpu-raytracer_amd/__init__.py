@@ -90,6 +90,7 @@ def device_lib():
         lib.rt_trace_shadow_rays.argtypes = [c_void_p] + [c_void_p] * 7 + [c_size_t, c_void_p, c_int, POINTER(c_float)]
         lib.rt_trace_stream_rays.argtypes = [c_void_p, c_int] + [c_void_p] * 6 + [c_size_t, c_void_p] + [c_void_p] * 7 + [c_size_t, c_void_p, c_void_p, c_void_p]
         lib.rt_generate_rays.argtypes = [c_void_p, c_int, c_int, c_int] + [c_void_p] * 7
+        lib.rt_generate_primary_rays.argtypes = [c_void_p] + [c_int] * 14 + [c_void_p, c_size_t] + [c_void_p] * 8
         lib.rt_random_samples.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_uint32, c_uint32, c_void_p]
         lib.rt_sample_texture.argtypes = [c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]
         lib.rt_sample_table.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]
@@ -1286,6 +1287,30 @@ def generate_rays(ctx, sample_index, pixel_offset, pixel_count):
     px = np.zeros(pixel_count, np.uint32)
     _dev_check(ctx, device_lib().rt_generate_rays(ctx, sample_index, pixel_offset, pixel_count, o[0].ctypes.data, o[1].ctypes.data, o[2].ctypes.data, d[0].ctypes.data, d[1].ctypes.data, d[2].ctypes.data, px.ctypes.data))
     return o, d, px
+
+
+def generate_primary_rays(ctx, kernel, queue, first_sample=0, sample_count=1, pixel_offset=0, pixel_count=0, tiles=(0, 0, 0), slot_base=0, iteration=0,
+                          queue_before=0, queue_offset=0, order=None, pixel_list=None):
+    """rt_generate_primary_rays: kernel 0 kernel_generate, 1 kernel_generate_stream, 2 kernel_generate_stream_list on the submission given here.
+    `queue` (7, capacity) uint32 is what the seven queue arrays {ox, oy, oz, dx, dy, dz, pixel word} hold before the launch; tiles = (tile_pixels,
+    tile_first, tile_stride); order = (block_width, band_rows), None for the scheduler's choice; pixel_list (kernel 2) replaces pixel_offset / pixel_count.
+    Returns (queue after the launch (7, capacity) uint32, info int32[4] {block_width, band_rows, workgroups, count word after})."""
+    out = np.array(queue, np.uint32, order="C", copy=True)
+    if out.ndim != 2 or out.shape[0] != 7:
+        raise ValueError("generate_primary_rays: queue must be (7, capacity)")
+    px = None
+    if pixel_list is not None:
+        px = np.ascontiguousarray(pixel_list, np.uint32).ravel()
+        pixel_count = px.size
+    block_width, band_rows = (-1, -1) if order is None else order
+    info = np.zeros(4, np.int32)
+    status = device_lib().rt_generate_primary_rays(ctx, int(kernel), int(iteration), int(first_sample), int(sample_count), int(pixel_offset), int(pixel_count),
+                                                   int(tiles[0]), int(tiles[1]), int(tiles[2]), int(slot_base), int(queue_before), int(queue_offset),
+                                                   int(block_width), int(band_rows), px.ctypes.data if px is not None else None, out.shape[1],
+                                                   *[out[i].ctypes.data for i in range(7)], info.ctypes.data)
+    if status:
+        raise DeviceRefusal(ctx, status)
+    return out, info
 
 
 def random_samples(ctx, dimension, pixel_indices, bounce, sample_index):

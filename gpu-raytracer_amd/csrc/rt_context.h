@@ -278,6 +278,7 @@ void stream_save_gbuffers(rt_context * ctx);
 void stream_release_frames(rt_context * ctx);
 RtParams stream_params(const rt_context * ctx, int iteration);
 int stream_sync_tlas(rt_context * ctx);
+void stream_launch_generate(const RtParams & pg, int first_sample, const unsigned * list, int range_offset, int range_count, int slot_base, int queue_offset, hipStream_t st, int * order2);
 int stream_enqueue_iteration(rt_context * ctx);
 int stream_launch_pending(rt_context * ctx);
 hipError_t stream_flush(rt_context * ctx);

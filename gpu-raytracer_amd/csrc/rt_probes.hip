@@ -204,6 +204,91 @@ int rt_generate_rays(rt_context * ctx, int sample_index, int pixel_offset, int p
 	return s;
 }
 
+// rt_generate_primary_rays: one of the three generate launches (rt_launch_generate, rt_launch_generate_stream, rt_launch_generate_stream_list, as the
+// per-bounce loop and stream_generate call them) on a caller-given submission. The parameter block is the context's (ctx->params, or
+// stream_params(ctx, iteration)) with the submission's batch_samples and tiles, and with the trace queue (of parity iteration & 1 for the stream
+// kernels) and the counters (RtBufferSizes) or the control block replaced by buffers of this call. Camera, filter, SVGF flag and RNG tables are
+// the context's. Runs on the main stream after quiesce(); nothing of the context changes but what the scheduler would set up itself (stream_create).
+int rt_generate_primary_rays(rt_context * ctx, int kernel, int iteration, int first_sample, int sample_count, int pixel_offset, int pixel_count,
+                             int tile_pixels, int tile_first, int tile_stride, int slot_base, int queue_before, int queue_offset,
+                             int block_width, int band_rows, const uint32_t * pixel_list, size_t capacity,
+                             float * ox, float * oy, float * oz, float * dx, float * dy, float * dz, uint32_t * pixel_index_and_flags, int32_t * info) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_generate_primary_rays: NULL context");
+	RT_REQUIRE(ctx, ox && oy && oz && dx && dy && dz && pixel_index_and_flags && info, "rt_generate_primary_rays: NULL array");
+	RT_REQUIRE(ctx, kernel >= 0 && kernel <= 2, "rt_generate_primary_rays: kernel must be 0 (kernel_generate), 1 (kernel_generate_stream) or 2 (kernel_generate_stream_list)");
+	RT_REQUIRE(ctx, iteration >= 0 && first_sample >= 0 && pixel_offset >= 0 && pixel_count >= 0 && tile_pixels >= 0 && tile_first >= 0 && tile_stride >= 0 &&
+	                slot_base >= 0 && queue_before >= 0 && queue_offset >= 0, "rt_generate_primary_rays: a count below zero");
+	RT_REQUIRE(ctx, sample_count >= 1 && sample_count <= RT_MAX_BATCH_SAMPLES, "rt_generate_primary_rays: sample_count must be 1..16");
+	RT_REQUIRE(ctx, slot_base + sample_count <= RT_STREAM_SAMPLE_SLOTS, "rt_generate_primary_rays: slot_base + sample_count beyond the 512 sample slots");
+	RT_REQUIRE(ctx, kernel != 0 || (slot_base == 0 && queue_before == 0 && queue_offset == 0), "rt_generate_primary_rays: kernel_generate has no slot_base, queue count or queue_offset");
+	RT_REQUIRE(ctx, kernel != 2 || (pixel_offset == 0 && tile_pixels == 0), "rt_generate_primary_rays: kernel_generate_stream_list has no pixel_offset and no tiles");
+	RT_REQUIRE(ctx, kernel != 2 || pixel_list || pixel_count == 0, "rt_generate_primary_rays: NULL pixel list");
+	RT_REQUIRE(ctx, tile_pixels == 0 || tile_stride >= 1, "rt_generate_primary_rays: tile_stride must be at least 1 with tiles");
+	RT_REQUIRE(ctx, (block_width == -1 && band_rows == -1) || (block_width == 0 && band_rows == 0) || (kernel == 1 && block_width > 0 && band_rows > 0),
+	           "rt_generate_primary_rays: block_width and band_rows must both be -1 (the scheduler's choice), both 0 (scan lines) or, for kernel_generate_stream, both positive");
+	RT_REQUIRE(ctx, capacity >= 1 && capacity <= size_t(1) << 28, "rt_generate_primary_rays: capacity must be in [1, 2^28]");
+	(void)hipSetDevice(ctx->device);
+	if (!ctx->params.pmj_samples || !ctx->params.blue_noise || ctx->frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_generate_primary_rays: RNG tables not uploaded or rt_resize not called");
+	const size_t frame_pixels = ctx->frame_pixels;
+	const size_t frame = size_t(ctx->params.screen_width) * size_t(ctx->params.screen_height);
+	RT_REQUIRE(ctx, size_t(slot_base + sample_count) * frame_pixels < size_t(1) << 30, "rt_generate_primary_rays: (slot_base + sample_count) * frame_pixels must be below 2^30");
+	const size_t rays = size_t(pixel_count) * size_t(sample_count);
+	RT_REQUIRE(ctx, size_t(queue_before) + size_t(queue_offset) + rays <= capacity, "rt_generate_primary_rays: capacity below queue count + queue_offset + rays");
+	if (kernel == 2) {
+		for (int i = 0; i < pixel_count; i++)
+			if (pixel_list[i] >= frame) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_generate_primary_rays: list entry %d: pixel %u beyond the %zu pixels of the frame", i, pixel_list[i], frame);
+	} else if (pixel_count > 0) {   // rt_map_pixel grows with the local index: the last pixel decides
+		const size_t i = size_t(pixel_offset) + size_t(pixel_count) - 1;
+		const size_t last = tile_pixels == 0 ? i : ((i / size_t(tile_pixels)) * size_t(tile_stride) + size_t(tile_first)) * size_t(tile_pixels) + i % size_t(tile_pixels);
+		if (last >= frame) return fail(ctx, RT_ERROR_OUT_OF_RANGE, "rt_generate_primary_rays: the last pixel of the range, %zu, lies beyond the %zu pixel frame", last, frame);
+	}
+	RT_HIP(ctx, quiesce(ctx));
+	int s = stream_create(ctx); if (s) return s;
+	const int q = kernel == 0 ? 0 : iteration & 1;
+
+	Probe probe(ctx, "rt_generate_primary_rays");
+	RtTraceBuffer trace = { };
+	trace.origin = probe.vec3(capacity, ox, oy, oz); trace.direction = probe.vec3(capacity, dx, dy, dz);   // the caller's values: a sentinel shows an entry the launch never wrote
+	trace.pixel_index_and_flags = probe.array<unsigned>(capacity, pixel_index_and_flags);
+	const unsigned * list = kernel == 2 ? probe.array<unsigned>(size_t(pixel_count), pixel_list) : nullptr;
+	RtBufferSizes * sizes = nullptr; RtStreamControl * control = nullptr;
+	if (kernel == 0) {
+		RtBufferSizes sizes_host = { };
+		sizes = probe.array<RtBufferSizes>(1, &sizes_host);
+	} else {
+		std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());   // (value-initialised: zero cursors and region words)
+		control_host->trace_count[q] = queue_before;
+		control = probe.array<RtStreamControl>(1, control_host.get());
+	}
+	if ((s = probe.allocated())) return s;
+
+	RtParams p = kernel == 0 ? ctx->params : stream_params(ctx, iteration);
+	p.batch_samples = sample_count;
+	p.tile_pixels = tile_pixels; p.tile_first = tile_first; p.tile_stride = tile_stride;
+	p.trace[q] = trace;
+	p.sizes = sizes; p.stream = control;
+	int order[2] = { block_width, band_rows };
+	if (kernel == 0) { order[0] = order[1] = 0; rt_launch_generate(p, first_sample, pixel_offset, pixel_count, ctx->stream); }
+	else if (kernel == 2 || block_width < 0) stream_launch_generate(p, first_sample, list, pixel_offset, pixel_count, slot_base, queue_offset, ctx->stream, order);   // (a list has one order)
+	else rt_launch_generate_stream(p, first_sample, pixel_offset, pixel_count, slot_base, queue_offset, block_width, band_rows, ctx->stream);
+	if ((s = probe.finish())) return s;
+
+	void * const dst[7] = { ox, oy, oz, dx, dy, dz, pixel_index_and_flags };
+	const void * const src[7] = { trace.origin.x, trace.origin.y, trace.origin.z, trace.direction.x, trace.direction.y, trace.direction.z, trace.pixel_index_and_flags };
+	for (int i = 0; i < 7; i++) if ((s = probe.read(dst[i], src[i], capacity * 4))) return s;
+	// the grid of the three launchers: one thread per pixel (kernel_generate) or per ray, at most 2 048 workgroups of 256, the rest grid-strided
+	const size_t blocks = ((kernel == 0 ? size_t(pixel_count) : rays) + 255) / 256;
+	info[0] = order[0]; info[1] = order[1]; info[2] = int(std::min(std::max(blocks, size_t(1)), size_t(2048)));
+	if (kernel == 0) {
+		RtBufferSizes sizes_host;
+		if ((s = probe.read(&sizes_host, sizes, sizeof(RtBufferSizes)))) return s;
+		info[3] = sizes_host.trace[0];
+	} else {
+		if ((s = probe.read(&info[3], &control->trace_count[q], sizeof(int)))) return s;
+	}
+	return RT_OK;
+}
+
 int rt_random_samples(rt_context * ctx, int dimension, const uint32_t * pixel_indices, size_t count, uint32_t bounce, uint32_t sample_index, float * out_xy) {
 	RT_REQUIRE(ctx, ctx && pixel_indices && out_xy && dimension >= 0 && dimension < 7, "rt_random_samples: invalid argument");
 	(void)hipSetDevice(ctx->device);

@@ -229,6 +229,19 @@ int stream_sync_tlas(rt_context * ctx) {
 	return RT_OK;
 }
 
+// The generate launch of a submission, as the scheduler chooses it (stream_generate below, and rt_generate_primary_rays, which reports the choice
+// to the tests). `pg`: the parameters of the iteration with the submission's batch_samples and tiles; `list`: its pixel list, or null.
+// Queue order of the primary rays: 8 x 8 pixel patches along bands of 8 scan lines when the submission's pixel list is made of whole bands
+// (the whole frame, or tiles of whole bands: rt_map_pixel keeps a band together); scan lines otherwise. order2, if given: { block_width, band_rows }.
+void stream_launch_generate(const RtParams & pg, int first_sample, const unsigned * list, int range_offset, int range_count, int slot_base, int queue_offset, hipStream_t st, int * order2) {
+	const int order = 8;
+	const int frame = pg.screen_width * pg.screen_height;
+	const bool whole_bands = pg.tile_pixels > 0 ? pg.tile_pixels % (order * pg.screen_width) == 0 : (range_offset == 0 && range_count == frame);
+	if (order2) order2[0] = order2[1] = list ? 0 : whole_bands ? order : 0;   // (a list is in patch order already: the kernel walks it as it is)
+	if (list) rt_launch_generate_stream_list(pg, first_sample, list, range_count, slot_base, queue_offset, st);
+	else rt_launch_generate_stream(pg, first_sample, range_offset, range_count, slot_base, queue_offset, whole_bands ? order : 0, whole_bands ? order : 0, st);
+}
+
 // The primary rays of a new submission: appended to the trace queue of the iteration that is enqueued next, behind the
 // rays of the submissions already waiting for it.
 static int stream_generate(rt_context * ctx, const StreamSubmission & sub) {
@@ -241,13 +254,7 @@ static int stream_generate(rt_context * ctx, const StreamSubmission & sub) {
 	RT_HIP(ctx, hipEventRecord(s.ev_begin[sub.ring], st));
 	stage_mark(ctx, STAGE_GENERATE, st);
 	span_mark(ctx, SPAN_GENERATE, st);
-	// Queue order of the primary rays: 8 x 8 pixel patches along bands of 8 scan lines when the submission's pixel list is made of whole bands
-	// (the whole frame, or tiles of whole bands: rt_map_pixel keeps a band together); scan lines otherwise.
-	const int order = 8;
-	const int frame = pg.screen_width * pg.screen_height;
-	const bool whole_bands = sub.tile_pixels > 0 ? sub.tile_pixels % (order * pg.screen_width) == 0 : (sub.range_offset == 0 && sub.range_count == frame);
-	if (sub.list) rt_launch_generate_stream_list(pg, sub.first_sample, (const unsigned *)ctx->pixel_list, sub.range_count, sub.slot_base, int(s.pending_paths), st);   // (in patch order already)
-	else rt_launch_generate_stream(pg, sub.first_sample, sub.range_offset, sub.range_count, sub.slot_base, int(s.pending_paths), whole_bands ? order : 0, whole_bands ? order : 0, st);
+	stream_launch_generate(pg, sub.first_sample, sub.list ? (const unsigned *)ctx->pixel_list : nullptr, sub.range_offset, sub.range_count, sub.slot_base, int(s.pending_paths), st, nullptr);
 	span_mark(ctx, SPAN_GENERATE, st);
 	s.pending++; s.pending_paths += sub.paths;
 	return RT_OK;

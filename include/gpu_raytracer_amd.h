@@ -681,6 +681,23 @@ int rt_trace_stream_rays(rt_context * ctx, int iteration,
 int rt_generate_rays(rt_context * ctx, int sample_index, int pixel_offset, int pixel_count,
                      float * ox, float * oy, float * oz, float * dx, float * dy, float * dz,
                      uint32_t * pixel_index_and_flags);
+/* One of the three generate launches on a caller-given submission (synchronous). kernel: 0 kernel_generate (per-bounce schedulers), 1
+ * kernel_generate_stream, 2 kernel_generate_stream_list (merged wavefront), each through the launcher the schedulers call. Camera, filter, SVGF flag
+ * and RNG tables are the context's; the submission is the call's: samples first_sample .. first_sample + sample_count - 1 (1..16: batch_samples) of
+ * local pixels [pixel_offset, pixel_offset + pixel_count), which tile_pixels / tile_first / tile_stride map to the frame as rt_set_tile_split does
+ * (tile_pixels 0: no tiles), or -- kernel 2 -- of the pixel_count entries (x + y * width) of pixel_list. Kernels 1 and 2: sample s goes to sample
+ * slot slot_base + s, `iteration`'s parity picks the queue half, the queue holds queue_before entries already (the control block's count word) and the
+ * rays land behind queue_before + queue_offset. Kernel 0 takes 0 for these three. block_width / band_rows (kernel 1): the queue order, both 0 for scan
+ * lines, both -1 for what the scheduler chooses for such a submission. The seven queue arrays hold `capacity` entries each: they are uploaded first
+ * and read back whole, so a value the launch never overwrites stays. info: 4 ints {block_width, band_rows as launched, workgroups of the grid, the
+ * count word after the launch: RtBufferSizes::trace[0] for kernel 0, else trace_count[iteration & 1], which the stream kernels leave alone}.
+ * Refused: NULL arrays, counts below zero, sample_count outside [1, 16], slot_base + sample_count > 512, (slot_base + sample_count) * frame_pixels
+ * >= 2^30, capacity < queue_before + queue_offset + pixel_count * sample_count, a pixel beyond width * height; RT_ERROR_NOT_READY without RNG tables
+ * or rt_resize. Leaves no state a frame reads. (An addition that changes no struct: RT_ABI_VERSION stays.)                                          */
+int rt_generate_primary_rays(rt_context * ctx, int kernel, int iteration, int first_sample, int sample_count, int pixel_offset, int pixel_count,
+                             int tile_pixels, int tile_first, int tile_stride, int slot_base, int queue_before, int queue_offset,
+                             int block_width, int band_rows, const uint32_t * pixel_list, size_t capacity,
+                             float * ox, float * oy, float * oz, float * dx, float * dy, float * dz, uint32_t * pixel_index_and_flags, int32_t * info);
 /* random<Dim>() (CUDA/Sampling.h:44-84) for `count` (pixel_index) values: out = float2 each. */
 int rt_random_samples(rt_context * ctx, int dimension, const uint32_t * pixel_indices, size_t count,
                       uint32_t bounce, uint32_t sample_index, float * out_xy);

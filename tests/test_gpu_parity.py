@@ -245,6 +245,20 @@ def test_random_samples_are_bit_exact(grt, oracle):
         got = grt.random_samples(pt.ctx, dim, px, bounce, sample)
         want = view.random(dim, px, bounce, sample)
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (dim, bounce, sample)
+    # the two dimensions of the primary rays (DIM_FILTER, DIM_APERTURE) at the pixels and samples of tests/generate_cases.py: either side of the PMJ
+    # table's end, and pixels whose blue-noise cell wraps (x or y >= 128)
+    assert (px % pt.pitch >= 128).any() and (px // pt.pitch >= 128).any()
+    for frame in (33, 17), (136, 24):
+        scene_f, pt_f = make_pathtracer(grt, "cornellbox", *frame, 0)
+        view_f = oracle.SceneView(pt_f)
+        scan = np.arange(frame[0] * frame[1])
+        px_f = (scan % frame[0] + scan // frame[0] * pt_f.pitch).astype(np.uint32)
+        for dim in (0, 1):
+            for sample in (0, 1, 2, 3, 5, 20, 4094, 4095, 4096, 4097, 4099):
+                got = grt.random_samples(pt_f.ctx, dim, px_f, 0, sample)
+                want = view_f.random(dim, px_f, 0, sample)
+                assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (frame, dim, sample)
+        pt_f.close(); scene_f.close()
     pt.close(); scene.close()
 
 

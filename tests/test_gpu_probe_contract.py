@@ -59,6 +59,7 @@ def test_refusals_empty_batches_and_a_render_afterwards(grt):
         (lambda: lib.rt_trace_stream_rays(ctx, 0, *[None] * 6, 0, o, *[None] * 7, 0, o, o, None), "rt_trace_stream_rays: NULL info"),
         (lambda: lib.rt_trace_stream_rays(ctx, 0, *[None] * 6, 3, o, *[None] * 7, 0, o, o, o), "rt_trace_stream_rays: NULL closest-hit ray or hit array"),
         (lambda: lib.rt_generate_rays(ctx, 0, 0, -1, *[o] * 7), "rt_generate_rays: negative pixel_count"),
+        (lambda: lib.rt_generate_primary_rays(ctx, 1, 0, 0, 17, 0, 1, 0, 0, 0, 0, 0, 0, -1, -1, None, 64, *[o] * 8), "rt_generate_primary_rays: sample_count must be 1..16"),
         (lambda: lib.rt_random_samples(ctx, 7, z, 1, 0, 0, o), "rt_random_samples: invalid argument"),
         (lambda: lib.rt_measure_stream_bandwidth(ctx, 512, 1, byref(gbps)), "rt_measure_stream_bandwidth: invalid argument"),
         (lambda: lib.rt_shade_rays(ctx, 2, 0, 0, 0, None, 0, None, 0, None, 1, 1, SENTINEL, *[o] * 7, None), "rt_shade_rays: merged must be 0 (per-bounce launch) or 1 (merged wavefront)"),

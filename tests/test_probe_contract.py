@@ -15,6 +15,7 @@ PROBES = {
     "rt_trace_shadow_rays":        ([P] * 7 + [Z, P, I, P],                          [None] * 7 + [0, None, 0, None],                        "NULL argument"),
     "rt_trace_stream_rays":        ([I] + [P] * 6 + [Z, P] + [P] * 7 + [Z, P, P, P], [0] + [None] * 6 + [0, None] + [None] * 7 + [0, None, None, None], "NULL context"),
     "rt_generate_rays":            ([I, I, I] + [P] * 7,                             [0, 0, 0] + [None] * 7,                                 "NULL argument"),
+    "rt_generate_primary_rays":    ([I] * 14 + [P, Z] + [P] * 8,                     [0] * 14 + [None, 0] + [None] * 8,                      "NULL context"),
     "rt_random_samples":           ([I, P, Z, U, U, P],                              [0, None, 0, 0, 0, None],                               "invalid argument"),
     "rt_sample_texture":           ([I, I, P, Z, P],                                 [0, 0, None, 0, None],                                  "NULL argument"),
     "rt_sample_table":             ([P, I, I, I, I, P, Z, P],                        [None, 0, 0, 0, 0, None, 0, None],                      "NULL argument"),
@@ -39,8 +40,8 @@ def lib(grt):
     return lib
 
 
-def test_there_are_seventeen_probes():
-    assert len(PROBES) == 17
+def test_there_are_eighteen_probes():
+    assert len(PROBES) == 18
 
 
 @pytest.mark.parametrize("name", sorted(PROBES))
