@@ -107,6 +107,11 @@ def device_lib():
         lib.rt_upload_delta_lights.argtypes = [c_void_p, c_void_p, c_size_t, c_float]
         lib.rt_read_delta_lights.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, POINTER(c_size_t), POINTER(c_float)]
         lib.rt_sample_delta_lights.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
+        lib.rt_set_fog_volume.argtypes = [c_void_p, c_void_p]
+        lib.rt_get_fog_volume.argtypes = [c_void_p, c_void_p, POINTER(c_int)]
+        lib.rt_fog_segments.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
+        lib.rt_attenuate_shadow_rays.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
+        lib.rt_sort_rays_fog.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_uint32] + [c_void_p] * 10 + [POINTER(c_int)]
         lib.rt_set_bvh_type.argtypes = [c_void_p, c_int]
         lib.rt_upload_material_opacity.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]
         lib.rt_read_material_opacity.argtypes = [c_void_p, c_int, c_void_p, c_size_t, POINTER(c_int), POINTER(c_int)]
@@ -163,6 +168,10 @@ def host_lib():
         lib.grt_last_error.restype = c_char_p
         lib.grt_config_set.argtypes = [c_char_p, c_double]
         lib.grt_config_get.argtypes = [c_char_p]
+        lib.grt_config_set_string.argtypes = [c_char_p, c_char_p]
+        lib.grt_scene_set_fog.argtypes = [c_void_p, POINTER(c_float)]
+        lib.grt_scene_get_fog.argtypes = [c_void_p, POINTER(c_float)]
+        lib.grt_scene_clear_fog.argtypes = [c_void_p]
         lib.grt_config_get.restype = c_double
         lib.grt_scene_load.restype = c_void_p
         lib.grt_scene_load.argtypes = [c_char_p, c_char_p]
@@ -431,6 +440,11 @@ def config_set(**kwargs):
     for key, value in kwargs.items():
         if key == "bvh_type" and isinstance(value, str):
             value = BVH_TYPES[value.lower()]
+        if key in ("fog", "fog_sigma_a", "fog_sigma_s") and not isinstance(value, (int, float)):   # "off" or a box; one number or three
+            text = value if isinstance(value, str) else ",".join(repr(float(v)) for v in value)
+            if lib.grt_config_set_string(key.encode(), text.encode()) != 0:
+                raise KeyError(lib.grt_last_error().decode(errors="replace"))
+            continue
         if lib.grt_config_set(key.encode(), float(value)) != 0:
             raise KeyError(lib.grt_last_error().decode(errors="replace"))
 
@@ -612,6 +626,25 @@ class Scene:
     def add_directional_light(self, direction, irradiance):
         """A directional light whose light travels along `direction`, with RGB `irradiance` in W/m^2 on a surface facing it. Returns its index."""
         return self._add_delta_light(DELTA_LIGHT_DIRECTIONAL, (0, 0, 0), direction, irradiance, 0.0, 0.0)
+
+    def set_fog(self, box_min, box_max, sigma_a, sigma_s, g=0.0):
+        """The scene-wide fog volume: a homogeneous medium inside the box, absorption and scattering per unit length (one number
+        or RGB), Henyey-Greenstein asymmetry g in (-1, 1). Takes effect at the next update() after Pathtracer.invalidate("fog")."""
+        r = fog_volume_record(box_min, box_max, sigma_a, sigma_s, g)
+        values = (c_float * 13)(*[float(v) for v in r[:13]])
+        _host_check(host_lib().grt_scene_set_fog(self.handle, values))
+
+    def clear_fog(self):
+        host_lib().grt_scene_clear_fog(self.handle)
+
+    @property
+    def fog(self):
+        """None, or the volume as a dict {box_min, box_max, sigma_a, sigma_s (3 floats each), g}."""
+        values = (c_float * 13)()
+        if not host_lib().grt_scene_get_fog(self.handle, values):
+            return None
+        v = [float(x) for x in values]
+        return dict(box_min=tuple(v[0:3]), box_max=tuple(v[3:6]), sigma_a=tuple(v[6:9]), sigma_s=tuple(v[9:12]), g=v[12])
 
     def clear_delta_lights(self):
         host_lib().grt_scene_clear_delta_lights(self.handle)
@@ -1393,7 +1426,7 @@ class SortResult:
 
 
 def sort_rays(ctx, trace_in, frame_pixels, frame_slots, bounce=None, sample_index=0, iteration=None, slot_table=None, submission_birth=None,
-              capacity=None, sentinel=0xFFC0DE42, aov=None, gbuffer_normal_and_depth=None, gbuffer_ids=None, gbuffer_screen_prev=None, pixel_query=None):
+              capacity=None, sentinel=0xFFC0DE42, aov=None, gbuffer_normal_and_depth=None, gbuffer_ids=None, gbuffer_screen_prev=None, pixel_query=None, _fog=False):
     """rt_sort_rays: the production sort launch on explicit entries. trace_in: (N, 20) uint32 records. Per-bounce form: bounce and
     sample_index; merged form: iteration, slot_table (S, 4) int32 and submission_birth int32[128]. The frames hold frame_slots *
     frame_pixels pixels; aov / g-buffers / pixel_query are their contents before the launch (zeros / the sentinel when None)."""
@@ -1415,12 +1448,24 @@ def sort_rays(ctx, trace_in, frame_pixels, frame_slots, bounce=None, sample_inde
     if merged:
         slots = np.ascontiguousarray(slot_table, np.int32).reshape(-1, 4)
         births = np.ascontiguousarray(submission_birth, np.int32).reshape(STREAM_SUBMISSIONS)
-    _dev_check(ctx, device_lib().rt_sort_rays(ctx, 1 if merged else 0, int(iteration if merged else bounce), int(sample_index), t.ctypes.data if n else None, n,
-                                              slots.ctypes.data if merged else None, slots.shape[0] if merged else 0, births.ctypes.data if merged else None,
-                                              capacity, int(frame_slots), int(sentinel), r.trace_out.ctypes.data, r.material_out.ctypes.data, r.counters.ctypes.data,
-                                              r.aov.ctypes.data, r.gbuffer_normal_and_depth.ctypes.data, r.gbuffer_ids.ctypes.data, r.gbuffer_screen_prev.ctypes.data,
-                                              r.pixel_query.ctypes.data, r.stats.ctypes.data if merged else None))
+    args = (ctx, 1 if merged else 0, int(iteration if merged else bounce), int(sample_index), t.ctypes.data if n else None, n,
+            slots.ctypes.data if merged else None, slots.shape[0] if merged else 0, births.ctypes.data if merged else None,
+            capacity, int(frame_slots), int(sentinel), r.trace_out.ctypes.data, r.material_out.ctypes.data, r.counters.ctypes.data,
+            r.aov.ctypes.data, r.gbuffer_normal_and_depth.ctypes.data, r.gbuffer_ids.ctypes.data, r.gbuffer_screen_prev.ctypes.data,
+            r.pixel_query.ctypes.data, r.stats.ctypes.data if merged else None)
+    if _fog:
+        r.shadow_out = np.zeros((capacity, 11), np.uint32); shadow_count = c_int()
+        _dev_check(ctx, device_lib().rt_sort_rays_fog(*args, r.shadow_out.ctypes.data, byref(shadow_count)))
+        r.shadow_count = shadow_count.value
+    else:
+        _dev_check(ctx, device_lib().rt_sort_rays(*args))
     return r
+
+
+def sort_rays_fog(ctx, trace_in, frame_pixels, frame_slots, **kwargs):
+    """rt_sort_rays_fog: sort_rays with the fog volume in force (the ..._fog instance). The SortResult also carries shadow_out (capacity, 11)
+    uint32 {origin, direction, max_distance, illumination, pixel word}, the light samples of the scatter vertices, and shadow_count."""
+    return sort_rays(ctx, trace_in, frame_pixels, frame_slots, _fog=True, **kwargs)
 
 
 SHADE_SHADOW_WORDS = 11   # RT_SHADE_SHADOW_WORDS
@@ -1529,6 +1574,67 @@ def sample_delta_lights(ctx, probes):
     p = _f32(probes).reshape(-1, 4)
     out = np.zeros((p.shape[0], DELTA_SAMPLE_OUT), np.float32)
     _dev_check(ctx, device_lib().rt_sample_delta_lights(ctx, p.ctypes.data, p.shape[0], out.ctypes.data))
+    return out
+
+
+FOG_VOLUME_WORDS = 16    # 32-bit words of an rt_fog_volume
+FOG_SEGMENT_IN = 16      # words per probe record of rt_fog_segments
+FOG_SEGMENT_OUT = 16     # words per output record of rt_fog_segments
+
+
+def fog_volume_record(box_min, box_max, sigma_a, sigma_s, g=0.0):
+    """An rt_fog_volume as (16,) float32: box_min[3], box_max[3], sigma_a[3], sigma_s[3], g, 3 reserved words. sigma_a / sigma_s: one number or three."""
+    r = np.zeros(FOG_VOLUME_WORDS, np.float32)
+    r[0:3] = _f32(box_min).reshape(3); r[3:6] = _f32(box_max).reshape(3)
+    r[6:9] = np.broadcast_to(_f32(sigma_a).reshape(-1), (3,)); r[9:12] = np.broadcast_to(_f32(sigma_s).reshape(-1), (3,))
+    r[12] = g
+    return r
+
+
+def set_fog_volume(ctx, record):
+    """rt_set_fog_volume on a (16,) float32 record (fog_volume_record); None clears the volume. Returns the status (0: RT_OK); the message of a
+    refusal is rt_last_error's."""
+    if record is None:
+        return device_lib().rt_set_fog_volume(ctx, None)
+    r = _f32(record).reshape(FOG_VOLUME_WORDS)
+    return device_lib().rt_set_fog_volume(ctx, r.ctypes.data)
+
+
+def get_fog_volume(ctx):
+    """rt_get_fog_volume: the (16,) float32 record in force, or None when no volume is set."""
+    r = np.zeros(FOG_VOLUME_WORDS, np.float32); is_set = c_int()
+    _dev_check(ctx, device_lib().rt_get_fog_volume(ctx, r.ctypes.data, byref(is_set)))
+    return r if is_set.value else None
+
+
+def fog_segment_probes(origin, direction, t_end, pixel, bounce, sample, throughput, inside_medium=0):
+    """(N, 16) uint32 probe records of rt_fog_segments from per-probe arrays (scalars broadcast)."""
+    o = _f32(origin).reshape(-1, 3)
+    n = o.shape[0]
+    r = np.zeros((n, FOG_SEGMENT_IN), np.uint32)
+    f = r.view(np.float32)
+    f[:, 0:3] = o; f[:, 3:6] = _f32(direction).reshape(-1, 3); f[:, 6] = _f32(t_end)
+    r[:, 7] = np.asarray(pixel, np.uint32); r[:, 8] = np.asarray(bounce, np.uint32); r[:, 9] = np.asarray(sample, np.uint32)
+    f[:, 10:13] = _f32(throughput).reshape(-1, 3)
+    r[:, 13] = np.asarray(inside_medium, np.uint32)
+    return r
+
+
+def fog_segments(ctx, probes):
+    """rt_fog_segments: the fog's segment step on (N, 16) uint32 records (fog_segment_probes). Returns (N, 16) uint32 {t0, t1, the two random
+    numbers, scattered, distance, throughput'[3], vertex[3], pad[4]}; view the floats with .view(np.float32)."""
+    p = np.ascontiguousarray(probes, np.uint32).reshape(-1, FOG_SEGMENT_IN)
+    out = np.zeros((p.shape[0], FOG_SEGMENT_OUT), np.uint32)
+    _dev_check(ctx, device_lib().rt_fog_segments(ctx, p.ctypes.data if p.size else None, p.shape[0], out.ctypes.data if p.size else None))
+    return out
+
+
+def attenuate_shadow_rays(ctx, shadow_in):
+    """rt_attenuate_shadow_rays: the fog's attenuation pass, as the context's scheduler launches it, on (N, 11) uint32 shadow records
+    {origin[3], direction[3], max_distance, illumination[3], pixel word}. Returns the queue after the pass."""
+    q = np.ascontiguousarray(shadow_in, np.uint32).reshape(-1, SHADE_SHADOW_WORDS)
+    out = np.zeros_like(q)
+    _dev_check(ctx, device_lib().rt_attenuate_shadow_rays(ctx, q.ctypes.data if q.size else None, q.shape[0], out.ctypes.data if q.size else None))
     return out
 
 

@@ -325,6 +325,45 @@ int rt_set_config(rt_context * ctx, const rt_gpu_config * config) {
 	return sync_svgf(ctx);
 }
 
+// The fog volume. Everything is checked before anything changes; a change completes what is in flight first (paths in flight were
+// sorted under the other estimator), as a change of the sky's share does.
+int rt_set_fog_volume(rt_context * ctx, const rt_fog_volume * volume) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_set_fog_volume: NULL context");
+	rt_fog_volume v = { };
+	if (volume) {
+		v = *volume;
+		memset(v.reserved, 0, sizeof(v.reserved));
+		for (int k = 0; k < 3; k++) {
+			if (!(std::isfinite(v.box_min[k]) && std::isfinite(v.box_max[k]))) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_set_fog_volume: the box is not finite on axis %d (%.9g .. %.9g)", k, double(v.box_min[k]), double(v.box_max[k]));
+			if (!(v.box_min[k] < v.box_max[k])) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_set_fog_volume: the box needs min < max on axis %d (%.9g .. %.9g)", k, double(v.box_min[k]), double(v.box_max[k]));
+			if (!(std::isfinite(v.sigma_a[k]) && v.sigma_a[k] >= 0.0f)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_set_fog_volume: sigma_a[%d] = %.9g must be finite and >= 0", k, double(v.sigma_a[k]));
+			if (!(std::isfinite(v.sigma_s[k]) && v.sigma_s[k] >= 0.0f)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_set_fog_volume: sigma_s[%d] = %.9g must be finite and >= 0", k, double(v.sigma_s[k]));
+		}
+		if (!(std::fabs(v.g) < 1.0f)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_set_fog_volume: g = %.9g must lie in (-1, 1)", double(v.g));
+	}
+	const bool set = volume != nullptr;
+	if (set == ctx->fog_set && memcmp(&v, &ctx->fog, sizeof(v)) == 0) return RT_OK;
+	(void)hipSetDevice(ctx->device);
+	RT_HIP(ctx, quiesce(ctx));
+	ctx->fog_set = set; ctx->fog = v;
+	RtParams & p = ctx->params;
+	float density = 0.0f;
+	for (int k = 0; k < 3; k++) {
+		p.fog_box_min[k] = v.box_min[k]; p.fog_box_max[k] = v.box_max[k]; p.fog_sigma_a[k] = v.sigma_a[k]; p.fog_sigma_s[k] = v.sigma_s[k];
+		density = fmaxf(density, v.sigma_a[k] + v.sigma_s[k]);
+	}
+	p.fog_g = v.g;
+	p.fog_active = set && density > 0.0f;   // a volume of zero density is stored and renders as no volume
+	return RT_OK;
+}
+
+int rt_get_fog_volume(rt_context * ctx, rt_fog_volume * out, int * out_set) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_get_fog_volume: NULL context");
+	RT_REQUIRE(ctx, out && out_set, "rt_get_fog_volume: NULL argument");
+	*out = ctx->fog; *out_set = ctx->fog_set ? 1 : 0;
+	return RT_OK;
+}
+
 int rt_set_pixel_range(rt_context * ctx, int pixel_offset, int pixel_count) {
 	RT_REQUIRE(ctx, ctx && pixel_offset >= 0, "rt_set_pixel_range: invalid argument");
 	if (ctx->pixel_offset != pixel_offset || ctx->pixel_count != pixel_count || ctx->params.tile_pixels != 0) { int s = noise_moments_reset(ctx); if (s) return s; }

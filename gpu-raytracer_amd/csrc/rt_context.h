@@ -194,6 +194,9 @@ struct rt_context {
 	void * delta_lights = nullptr;
 	std::vector<float> delta_light_records, delta_light_cdf;
 	float delta_light_share = 0.0f;
+	// fog volume (rt_set_fog_volume): what the caller set, as rt_get_fog_volume returns it; RtParams::fog_* hold what the kernels read
+	bool fog_set = false;
+	rt_fog_volume fog = { };
 	void * luts[6] = { }; bool luts_ready = false;
 	int bvh_width = 8;
 

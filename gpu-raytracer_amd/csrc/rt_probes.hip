@@ -485,13 +485,15 @@ int rt_perturb_normals(rt_context * ctx, int texture_index, const float * probes
 // explicit trace queue. The parameter block is the context's (ctx->params, or stream_params(ctx, iteration)) with both trace queues, the four
 // material queues, the counters (RtBufferSizes) or the control block and slot table, the AOV frames, the g-buffers and the pixel-query word
 // replaced by buffers of this call, every output array filled with the caller's sentinel. Runs on the main stream after quiesce().
-int rt_sort_rays(rt_context * ctx, int merged, int step, int sample_index, const uint32_t * trace_in, size_t count,
-                 const int32_t * slot_table, size_t slot_count, const int32_t * submission_birth,
-                 size_t capacity, size_t frame_slots, uint32_t sentinel,
-                 uint32_t * trace_out, uint32_t * material_out, int32_t * counters6,
-                 float * aov_frames, float * gbuffer_normal_and_depth, int32_t * gbuffer_mesh_id_and_triangle_id, float * gbuffer_screen_position_prev,
-                 int32_t * pixel_query2, int32_t * stats) {
-	RT_REQUIRE(ctx, ctx != nullptr, "rt_sort_rays: NULL context");
+// rt_sort_rays_fog is the same call with a shadow queue (shadow_out / shadow_count, both null for rt_sort_rays): the ..._fog instance appends the light
+// samples of its scatter vertices to it. The messages name rt_sort_rays either way.
+} // extern "C"
+static int sort_rays_probe(rt_context * ctx, int merged, int step, int sample_index, const uint32_t * trace_in, size_t count,
+                           const int32_t * slot_table, size_t slot_count, const int32_t * submission_birth,
+                           size_t capacity, size_t frame_slots, uint32_t sentinel,
+                           uint32_t * trace_out, uint32_t * material_out, int32_t * counters6,
+                           float * aov_frames, float * gbuffer_normal_and_depth, int32_t * gbuffer_mesh_id_and_triangle_id, float * gbuffer_screen_position_prev,
+                           int32_t * pixel_query2, int32_t * stats, uint32_t * shadow_out, int32_t * shadow_count) {
 	RT_REQUIRE(ctx, merged == 0 || merged == 1, "rt_sort_rays: merged must be 0 (per-bounce launch) or 1 (merged wavefront)");
 	RT_REQUIRE(ctx, (trace_in || count == 0) && trace_out && material_out && counters6 && aov_frames && gbuffer_normal_and_depth &&
 	                gbuffer_mesh_id_and_triangle_id && gbuffer_screen_position_prev && pixel_query2, "rt_sort_rays: NULL array");
@@ -588,10 +590,16 @@ int rt_sort_rays(rt_context * ctx, int merged, int step, int sample_index, const
 		sizes_host.trace[step] = int(count);
 		sizes = probe.array<RtBufferSizes>(1, &sizes_host);
 	}
+	RtShadowBuffer shadow = { };
+	if (shadow_out) {
+		shadow.origin = vec3(nullptr, 0, 0, 0); shadow.direction = vec3(nullptr, 0, 0, 0);
+		shadow.max_distance = (float *)upload_column(nullptr, 0, 0, 0, 1); shadow.illumination_and_pixel_index = (float4 *)upload_column(nullptr, 0, 0, 0, 4);
+	}
 	if ((s = probe.allocated())) return s;
 
 	RtParams p = merged ? stream_params(ctx, step) : ctx->params;
 	p.trace[q] = in; p.trace[q ^ 1] = out;
+	if (shadow_out) p.shadow = shadow; else p.fog_active = 0;   // (rt_sort_rays: the instances it always launched; the ..._fog ones need this call's shadow queue)
 	for (int m = 0; m < 4; m++) p.material[m] = material[m];
 	p.sizes = sizes; p.stream = control; p.stream_table = table;
 	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = nullptr;
@@ -618,16 +626,26 @@ int rt_sort_rays(rt_context * ctx, int merged, int step, int sample_index, const
 		            && download_column(b.throughput.x, records, MW, 8, 1) && download_column(b.throughput.y, records, MW, 9, 1) && download_column(b.throughput.z, records, MW, 10, 1)
 		            && download_column(b.medium, records, MW, 11, 1) && download_column(b.cone_angle, records, MW, 12, 1) && download_column(b.cone_width, records, MW, 13, 1);
 	}
+	if (shadow_out) {
+		const size_t SW = RT_SHADE_SHADOW_WORDS;
+		for (size_t i = 0; i < capacity * SW; i++) shadow_out[i] = sentinel;
+		const RtVec3SoA * const shadow_vec[2] = { &shadow.origin, &shadow.direction };
+		for (int v = 0; v < 2; v++) read = read && download_column(shadow_vec[v]->x, shadow_out, SW, 3 * v, 1) && download_column(shadow_vec[v]->y, shadow_out, SW, 3 * v + 1, 1)
+		                                        && download_column(shadow_vec[v]->z, shadow_out, SW, 3 * v + 2, 1);
+		read = read && download_column(shadow.max_distance, shadow_out, SW, 6, 1) && download_column(shadow.illumination_and_pixel_index, shadow_out, SW, 7, 4);
+	}
 	if (!read) return fail(ctx, RT_ERROR_HIP, "rt_sort_rays: reading the queues back failed");
 	if (merged) {
 		std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());
 		if ((s = probe.read(control_host.get(), control, sizeof(RtStreamControl)))) return s;
+		if (shadow_count) *shadow_count = control_host->shadow_count[q];
 		for (int m = 0; m < 4; m++) counters6[m] = control_host->material_count[m];
 		counters6[4] = control_host->trace_count[q ^ 1]; counters6[5] = control_host->trace_count[q];
 		memcpy(stats, control_host->stats, sizeof(control_host->stats));
 	} else {
 		RtBufferSizes sizes_host;
 		if ((s = probe.read(&sizes_host, sizes, sizeof(RtBufferSizes)))) return s;
+		if (shadow_count) *shadow_count = sizes_host.shadow[step];
 		counters6[0] = sizes_host.diffuse[step]; counters6[1] = sizes_host.plastic[step]; counters6[2] = sizes_host.dielectric[step]; counters6[3] = sizes_host.conductor[step];
 		counters6[4] = step + 1 < RT_MAX_BOUNCES ? sizes_host.trace[step + 1] : 0; counters6[5] = sizes_host.trace[step];
 	}
@@ -635,6 +653,95 @@ int rt_sort_rays(rt_context * ctx, int merged, int step, int sample_index, const
 	if (s || (s = probe.read(gbuffer_normal_and_depth, g_nd, pixels * 16)) || (s = probe.read(gbuffer_mesh_id_and_triangle_id, g_id, pixels * 8))
 	      || (s = probe.read(gbuffer_screen_position_prev, g_sp, pixels * 8))) return s;
 	return probe.read(pixel_query2, query, 8);
+}
+extern "C" {
+
+int rt_sort_rays(rt_context * ctx, int merged, int step, int sample_index, const uint32_t * trace_in, size_t count,
+                 const int32_t * slot_table, size_t slot_count, const int32_t * submission_birth,
+                 size_t capacity, size_t frame_slots, uint32_t sentinel,
+                 uint32_t * trace_out, uint32_t * material_out, int32_t * counters6,
+                 float * aov_frames, float * gbuffer_normal_and_depth, int32_t * gbuffer_mesh_id_and_triangle_id, float * gbuffer_screen_position_prev,
+                 int32_t * pixel_query2, int32_t * stats) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_sort_rays: NULL context");
+	return sort_rays_probe(ctx, merged, step, sample_index, trace_in, count, slot_table, slot_count, submission_birth, capacity, frame_slots, sentinel, trace_out, material_out, counters6,
+	                       aov_frames, gbuffer_normal_and_depth, gbuffer_mesh_id_and_triangle_id, gbuffer_screen_position_prev, pixel_query2, stats, nullptr, nullptr);
+}
+
+int rt_sort_rays_fog(rt_context * ctx, int merged, int step, int sample_index, const uint32_t * trace_in, size_t count,
+                     const int32_t * slot_table, size_t slot_count, const int32_t * submission_birth,
+                     size_t capacity, size_t frame_slots, uint32_t sentinel,
+                     uint32_t * trace_out, uint32_t * material_out, int32_t * counters6,
+                     float * aov_frames, float * gbuffer_normal_and_depth, int32_t * gbuffer_mesh_id_and_triangle_id, float * gbuffer_screen_position_prev,
+                     int32_t * pixel_query2, int32_t * stats, uint32_t * shadow_out, int32_t * shadow_count) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_sort_rays_fog: NULL context");
+	RT_REQUIRE(ctx, shadow_out && shadow_count, "rt_sort_rays_fog: NULL shadow queue or counter");
+	if (!ctx->params.fog_active) return fail(ctx, RT_ERROR_NOT_READY, "rt_sort_rays_fog: no fog volume of positive density is in force (rt_set_fog_volume)");
+	RT_REQUIRE(ctx, !ctx->params.config.enable_svgf, "rt_sort_rays_fog: a fog volume cannot be rendered with enable_svgf");
+	return sort_rays_probe(ctx, merged, step, sample_index, trace_in, count, slot_table, slot_count, submission_birth, capacity, frame_slots, sentinel, trace_out, material_out, counters6,
+	                       aov_frames, gbuffer_normal_and_depth, gbuffer_mesh_id_and_triangle_id, gbuffer_screen_position_prev, pixel_query2, stats, shadow_out, shadow_count);
+}
+
+// rt_fog_segments: the fog's segment step (rt_fog.h: clip, hashed pair, distance sample) on explicit segments, on the volume in force.
+int rt_fog_segments(rt_context * ctx, const uint32_t * probes, size_t count, uint32_t * out) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_fog_segments: NULL context");
+	RT_REQUIRE(ctx, (probes && out) || count == 0, "rt_fog_segments: NULL argument");
+	RT_REQUIRE(ctx, count <= size_t(1) << 24, "rt_fog_segments: more than 2^24 probes");
+	if (!ctx->fog_set) return fail(ctx, RT_ERROR_NOT_READY, "rt_fog_segments: no fog volume set (rt_set_fog_volume)");
+	(void)hipSetDevice(ctx->device);
+	int s = check_ready(ctx, "rt_fog_segments", NEED_RNG | NEED_FRAME); if (s) return s;
+	for (size_t i = 0; i < count; i++) {
+		const uint32_t * a = probes + i * RT_FOG_SEGMENT_IN;
+		if (a[7] >= 1u << 30) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_fog_segments: probe %zu: pixel %u beyond the 30-bit path index", i, a[7]);
+		if (a[8] >= unsigned(RT_MAX_BOUNCES)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_fog_segments: probe %zu: bounce %u outside [0, RT_MAX_BOUNCES)", i, a[8]);
+	}
+	if (count == 0) return RT_OK;
+	Probe probe(ctx, "rt_fog_segments");
+	uint32_t * dev_probes = probe.array<uint32_t>(count * RT_FOG_SEGMENT_IN, probes);
+	uint32_t * dev_out = probe.array<uint32_t>(count * RT_FOG_SEGMENT_OUT);
+	if ((s = probe.allocated())) return s;
+	rt_launch_fog_segments(ctx->params, dev_probes, int(count), dev_out, ctx->stream);
+	return probe.finish_and_read(out, dev_out, count * RT_FOG_SEGMENT_OUT * 4);
+}
+
+// rt_attenuate_shadow_rays: the fog's attenuation pass, as the context's scheduler launches it, on an explicit shadow queue. The parameter block is the
+// context's with the shadow queue and the word the launch reads its count from replaced by buffers of this call.
+int rt_attenuate_shadow_rays(rt_context * ctx, const uint32_t * shadow_in, size_t count, uint32_t * shadow_out) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_attenuate_shadow_rays: NULL context");
+	RT_REQUIRE(ctx, (shadow_in && shadow_out) || count == 0, "rt_attenuate_shadow_rays: NULL argument");
+	RT_REQUIRE(ctx, count <= size_t(1) << 28, "rt_attenuate_shadow_rays: more than 2^28 rays");
+	if (!ctx->fog_set) return fail(ctx, RT_ERROR_NOT_READY, "rt_attenuate_shadow_rays: no fog volume set (rt_set_fog_volume)");
+	(void)hipSetDevice(ctx->device);
+	RT_HIP(ctx, quiesce(ctx));
+	const bool merged = ctx->scheduler == RT_SCHEDULER_MERGED;
+	const size_t SW = RT_SHADE_SHADOW_WORDS;
+	Probe probe(ctx, "rt_attenuate_shadow_rays");
+	RtShadowBuffer shadow = { };
+	shadow.origin = probe.column3(shadow_in, count, SW, 0, count, 0u); shadow.direction = probe.column3(shadow_in, count, SW, 3, count, 0u);
+	shadow.max_distance = (float *)probe.column(shadow_in, count, SW, 6, 1, count, 0u);
+	shadow.illumination_and_pixel_index = (float4 *)probe.column(shadow_in, count, SW, 7, 4, count, 0u);
+	RtBufferSizes * sizes = nullptr; RtStreamControl * control = nullptr;
+	if (merged) {
+		std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());
+		control_host->shadow_count[0] = int(count);
+		control = probe.array<RtStreamControl>(1, control_host.get());
+	} else {
+		RtBufferSizes sizes_host = { };
+		sizes_host.shadow[0] = int(count);
+		sizes = probe.array<RtBufferSizes>(1, &sizes_host);
+	}
+	int s = probe.allocated(); if (s) return s;
+	RtParams p = ctx->params;
+	p.shadow = shadow; p.sizes = sizes; p.stream = control; p.stream_iteration = 0;
+	if (merged) rt_launch_fog_attenuate_shadows_stream(p, ctx->stream); else rt_launch_fog_attenuate_shadows(p, 0, ctx->stream);
+	if ((s = probe.finish(ctx->stream))) return s;
+	if (count == 0) return RT_OK;
+	bool read = true;
+	const RtVec3SoA * const shadow_vec[2] = { &shadow.origin, &shadow.direction };
+	for (int v = 0; v < 2; v++) read = read && probe.column_back(shadow_vec[v]->x, shadow_out, SW, 3 * v, 1, count) && probe.column_back(shadow_vec[v]->y, shadow_out, SW, 3 * v + 1, 1, count)
+	                                        && probe.column_back(shadow_vec[v]->z, shadow_out, SW, 3 * v + 2, 1, count);
+	read = read && probe.column_back(shadow.max_distance, shadow_out, SW, 6, 1, count) && probe.column_back(shadow.illumination_and_pixel_index, shadow_out, SW, 7, 4, count);
+	if (!read) return fail(ctx, RT_ERROR_HIP, "rt_attenuate_shadow_rays: reading the queue back failed");
+	return RT_OK;
 }
 
 // rt_shade_rays: the material launch (rt_launch_material or rt_launch_material_stream, as the per-bounce loop and stream_enqueue_iteration call them) on an

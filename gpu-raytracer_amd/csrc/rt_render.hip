@@ -205,6 +205,7 @@ int rt_render_samples(rt_context * ctx, int sample_index, int sample_count) {
 	const bool merged = ctx->scheduler == RT_SCHEDULER_MERGED && ctx->params.config.num_bounces > 0 && ctx->bvh_width == 8
 	                    && !(ctx->params.config.enable_svgf && ctx->defer_filter) // the tile split of SVGF frames exchanges the filter's inputs per frame
 	                    && !(ctx->batch_size_request > 0); // explicit pixel batches (a VRAM bound of the reference) are a slot-scheduler feature
+	if (ctx->params.config.enable_svgf && ctx->params.fog_active) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_render_samples: a fog volume (rt_set_fog_volume) cannot be rendered with enable_svgf: a scatter vertex has no g-buffer");
 	if (ctx->params.config.enable_svgf && sample_count != 1) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_render_samples: SVGF frames are rendered one sample at a time");
 	if (ctx->pixel_list_on) {   // a refusal, never a silent uniform render: the list kernels exist for the merged wavefront's plain frames, and a pixel's own count starts at w >= 1
 		if (ctx->scheduler != RT_SCHEDULER_MERGED) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_render_samples: a pixel list (rt_set_pixel_list) needs RT_SCHEDULER_MERGED");
@@ -260,7 +261,8 @@ int rt_render_samples(rt_context * ctx, int sample_index, int sample_count) {
 		for (int i = 0; i < 3; i++) if (from[i] && to[i] && from[i] != to[i]) RT_HIP(ctx, hipMemcpyAsync(to[i], from[i], gbuffer_bytes(ctx, i), hipMemcpyDeviceToDevice, st));
 	}
 
-	bool trace_shadows = p.config.enable_next_event_estimation && ((ctx->has_lights && p.lights_total_weight > 0.0f) || rt_light_samples_split(p));   // (sky importance sampling, delta lights: shadow rays without emitters)
+	bool trace_shadows = p.config.enable_next_event_estimation && ((ctx->has_lights && p.lights_total_weight > 0.0f) || rt_light_samples_split(p) || p.fog_active);   // (sky importance sampling, delta lights: shadow rays without emitters; a fog volume: whenever NEE is on)
+	const bool fog_shadows = trace_shadows && p.fog_active;   // the queue passes through the fog's attenuation pass on the stream that traces it
 	// Shadow rays of bounce b only feed the frame buffers, so they run on the side stream while the
 	// main chain traces bounce b+1; they are joined before the next kernel that touches the frame
 	// buffers (sort: sky / emissive hits), which keeps the order of the float additions per pixel.
@@ -293,11 +295,13 @@ int rt_render_samples(rt_context * ctx, int sample_index, int sample_count) {
 			if (svgf && bounce == 0 && pixels_left <= batch_size) RT_HIP(ctx, hipEventRecord(slot.ev_gbuffers, st)); // last pixel batch: the g-buffers of this frame are complete
 			if (trace_shadows) {
 				stage_mark(ctx, STAGE_SHADOW, st);
+				if (fog_shadows && !overlap) rt_launch_fog_attenuate_shadows(p, bounce, st);
 				if (ctx->trace_statistics) rt_launch_trace_shadow_counting(p, bounce, ctx->trace_stats, st);
 				else if (!overlap) rt_launch_trace_shadow(p, bounce, st);
 				else {
 					RT_HIP(ctx, hipEventRecord(slot.ev_shaded, st));
 					RT_HIP(ctx, hipStreamWaitEvent(slot.side, slot.ev_shaded, 0));
+					if (fog_shadows) rt_launch_fog_attenuate_shadows(p_shadow, bounce, slot.side);
 					span_mark(ctx, SPAN_SHADOW, slot.side);
 					rt_launch_trace_shadow(p_shadow, bounce, slot.side);
 					span_mark(ctx, SPAN_SHADOW, slot.side);

@@ -295,6 +295,7 @@ int stream_enqueue_iteration(rt_context * ctx) {
 	span_mark(ctx, SPAN_SORT, st);
 	stage_mark(ctx, STAGE_SHADE, st);
 	for (int m = 0; m < 4; m++) if (ctx->has_material[m]) { span_mark(ctx, SPAN_MATERIAL + m, st); rt_launch_material_stream(p, m, st); span_mark(ctx, SPAN_MATERIAL + m, st); }
+	if (p.fog_active && p.config.enable_next_event_estimation) { stage_mark(ctx, STAGE_SHADOW, st); rt_launch_fog_attenuate_shadows_stream(p, st); }   // the shadow rays of this iteration (sort's scatter vertices, the material kernels' hits), before the next iteration traces them
 	stage_mark(ctx, STAGE_END, st);
 	s.iteration = i + 1;
 	StreamSubmission done[RT_STREAM_MAX_BATCH]; int done_count = 0;

@@ -235,6 +235,13 @@ struct RtParams {
 	const float * delta_light_cdf;
 	int   delta_light_count;
 	float delta_nee_share, nee_taken;
+	// Fog volume (rt_set_fog_volume): one homogeneous medium inside an axis-aligned box. fog_active: a volume of positive density is in
+	// force -- only then do the launchers take the ..._fog instances of the sort kernels and the attenuation pass of the shadow queue, the only kernels
+	// that read the other fog fields; a material kernel reads fog_active alone (a path's first segment may then have lost throughput, see shade_material).
+	int   fog_active;
+	float fog_box_min[3], fog_box_max[3];
+	float fog_sigma_a[3], fog_sigma_s[3];
+	float fog_g;
 };
 // Which instances of the sort and material kernels a launcher takes: 0 the plain ones, 1 the ..._sky ones (sky importance sampling alone), 2 the ..._split
 // ones (delta lights take a share, with or without the sky). Shadow rays are traced without triangle emitters whenever it is not 0.
@@ -333,6 +340,11 @@ void rt_launch_bsdf_probe(const RtParams & p, int material_type, bool eval, cons
 void rt_launch_sample_lights(const RtParams & p, const float * probes, int count, bool use_lds, float * out, hipStream_t stream);
 // Test support: nee_pick_delta and delta_light_sample on explicit probes (rt_sample_delta_lights); 4 floats in, RT_DELTA_SAMPLE_OUT out per probe
 void rt_launch_sample_delta_lights(const RtParams & p, const float * probes, int count, float * out, hipStream_t stream);
+// Fog volume: the shadow queue's attenuation pass -- the per-bounce loop's (the queue of `bounce`) and the merged wavefront's (the queue the
+// material kernels of p.stream_iteration appended to) -- and the probe of the segment step (rt_fog_segments).
+void rt_launch_fog_attenuate_shadows(const RtParams & p, int bounce, hipStream_t stream);
+void rt_launch_fog_attenuate_shadows_stream(const RtParams & p, hipStream_t stream);
+void rt_launch_fog_segments(const RtParams & p, const uint32_t * probes, int count, uint32_t * out, hipStream_t stream);
 // Test support: normal_map_perturb on explicit hits (rt_perturb_normals); RT_NORMAL_PROBE_IN floats in, 4 out per probe
 void rt_launch_perturb_normals(const RtParams & p, int texture_index, const float * probes, int count, float * out, hipStream_t stream);
 // Sky importance sampling (kernels_sky.hip). build: the three tables of RtParams from the sky; row_total: sky_height doubles, total: one double (the

@@ -128,6 +128,15 @@ struct CPUConfig {
 	// that a light sample the sky did not take goes to a delta light while the scene has triangle emitters too; 0 = by power (Pathtracer::calc_delta_lights).
 	int   delta_lights = 0;
 	float delta_light_share = 0.0f;
+	// Fog volume: one homogeneous medium inside an axis-aligned box, handed to a scene when it is loaded. fog: off, or the box {min[3], max[3]};
+	// fog_sigma_a / fog_sigma_s: absorption and scattering per unit length, RGB; fog_g: Henyey-Greenstein asymmetry. fog_volumes: 1 = a Mitsuba shape
+	// with <bsdf type="null"/> and an interior homogeneous medium becomes the fog over its world bounding box and is not added to the scene; 0: loaded as before.
+	// With both, the key `fog` wins: its volume replaces the file's, with a warning.
+	bool  fog = false;
+	float fog_box[6] = { 0.0f, 0.0f, 0.0f, 1.0f, 1.0f, 1.0f };
+	float fog_sigma_a[3] = { 0.0f, 0.0f, 0.0f }, fog_sigma_s[3] = { 0.1f, 0.1f, 0.1f };
+	float fog_g = 0.0f;
+	int   fog_volumes = 0;
 	int   static_slot_learning_viewpoint = 1;   // a quarter of those rays are paths from the camera as it stands when the tree is built (0: none are; half come from points of the free space, the rest from the surface, either way)
 	// ... and early split clipping (StaticBVHBuilder::presplit, as in front of the device build) in front of that builder's own SAH + spatial splits: fraction of
 	// the geometry's longest side above which a triangle is cut blindly first. 0: off.

@@ -359,7 +359,18 @@ struct SceneFile {
 		}
 		Medium medium;
 		if (const XMLAttribute * name = given->get_attribute("name")) medium.name = name->value;
+		Vector3 absorb, scatter;
+		homogeneous_coefficients(*given, absorb, scatter, medium.g);
+		const float g = medium.g;
+		medium.g = 0.0f;
+		medium.from_sigmas(absorb, scatter);   // (with g = 0: the phase function is read afterwards, as in the reference)
+		medium.g = g;
+		return scene.asset_manager.add_medium(std::move(medium));
+	}
 
+	// The coefficients of a <medium type="homogeneous">, scaled by its density, and the g of its phase function.
+	void homogeneous_coefficients(const XMLNode & medium, Vector3 & absorb_out, Vector3 & scatter_out, float & g) {
+		const XMLNode * given = &medium;
 		// coefficients: (sigmaA, sigmaS) or (sigmaT, albedo), exactly one of the pairs
 		auto coefficient = [&](const char * name) { return given->get_child_by_name(name); };
 		const XMLNode * a = coefficient("sigmaA"), * s = coefficient("sigmaS"), * t = coefficient("sigmaT"), * albedo = coefficient("albedo");
@@ -376,15 +387,41 @@ struct SceneFile {
 			absorb  = extinction - scatter;
 		}
 		const float density = property(*given, "scale", 1.0f);
-		medium.from_sigmas(density * absorb, density * scatter);   // (with g = 0: the phase function is read afterwards, as in the reference)
+		absorb_out = density * absorb; scatter_out = density * scatter;
 
 		if (const XMLNode * phase = given->get_child_by_tag("phase")) {
 			std::string_view kind = plugin(*phase);
-			if      (kind == "isotropic") medium.g = 0.0f;
-			else if (kind == "hg")        medium.g = property(*phase, "g", 0.0f);
+			if      (kind == "isotropic") g = 0.0f;
+			else if (kind == "hg")        g = property(*phase, "g", 0.0f);
 			else complain(*given, "phase function type '" + std::string(kind) + "' not supported");
 		}
-		return scene.asset_manager.add_medium(std::move(medium));
+	}
+
+	// -- the fog volume (config fog_volumes = 1): a shape with <bsdf type="null"/> and an interior homogeneous medium is the scene's fog over
+	// the shape's world bounding box, and is not added to the scene. One warning per file when the shape is not that box; a second such shape is refused.
+	static bool fog_shape_triangles(SceneFile & file, const XMLNode & shape, std::vector<Triangle> & triangles);
+	bool warned_fog_shape_is_no_box = false;
+	bool fog_volume(const XMLNode & node) {
+		if (cpu_config.fog_volumes != 1) return false;
+		const XMLNode * bsdf = node.get_child_by_tag("bsdf"), * medium = node.get_child_by_tag("medium");
+		if (!bsdf || plugin(*bsdf) != "null" || !medium || plugin(*medium) != "homogeneous") return false;
+		if (const XMLAttribute * name = medium->get_attribute("name")) if (name->value != "interior") return false;
+		std::vector<Triangle> triangles;
+		if (!fog_shape_triangles(*this, node, triangles) || triangles.empty()) return false;   // (a shape this loader cannot read as a volume: loaded as before)
+		if (scene.has_fog) throw ParseError(node.location + ": a second fog volume (a shape with a null BSDF and an interior homogeneous medium); the scene has one already");
+		Vector3 lo(INFINITY), hi(-INFINITY);
+		for (const Triangle & t : triangles) for (const Vector3 * p : { &t.position_0, &t.position_1, &t.position_2 }) { lo = Vector3::min(lo, *p); hi = Vector3::max(hi, *p); }
+		bool is_box = triangles.size() == 12;
+		for (const Triangle & t : triangles) for (const Vector3 * p : { &t.position_0, &t.position_1, &t.position_2 })
+			is_box = is_box && (p->x == lo.x || p->x == hi.x) && (p->y == lo.y || p->y == hi.y) && (p->z == lo.z || p->z == hi.z);
+		if (!is_box && !warned_fog_shape_is_no_box) { complain(node, "the fog volume is the shape's axis-aligned bounding box, which this shape does not fill"); warned_fog_shape_is_no_box = true; }
+		FogVolume fog;
+		fog.box_min = lo; fog.box_max = hi;
+		homogeneous_coefficients(*medium, fog.sigma_a, fog.sigma_s, fog.g);
+		std::string why = fog.complaint();
+		if (!why.empty()) throw ParseError(node.location + ": fog volume: " + why);
+		scene.fog = fog; scene.has_fog = true;
+		return true;
 	}
 
 	// -- shapes
@@ -420,6 +457,7 @@ struct SceneFile {
 			return;
 		}
 
+		if (fog_volume(node)) return;
 		std::string mesh_name;
 		Handle<MeshData> mesh_data = geometry(node, mesh_name);
 		Handle<Material> surface   = material(node);
@@ -582,6 +620,24 @@ Handle<MeshData> hair_mesh(SceneFile & file, const XMLNode & shape, std::string 
 	mesh_name = filename_property(shape);
 	const float radius = property(shape, "radius", 0.0025f);
 	return file.scene.asset_manager.add_mesh_data(PathName::below(file.folder, mesh_name), [radius](const std::string & path) { return MitshairLoader::load(path, radius); });
+}
+
+// The triangles of a shape in world space, without a word to the asset manager: the generated kinds, and obj / ply files.
+bool SceneFile::fog_shape_triangles(SceneFile & file, const XMLNode & shape, std::vector<Triangle> & triangles) {
+	const std::string_view kind = plugin(shape);
+	const Matrix4 world = to_world(shape);
+	if      (kind == "rectangle") triangles = rectangle_of(shape, world);
+	else if (kind == "cube")      triangles = cube_of(shape, world);
+	else if (kind == "disk")      triangles = disk_of(shape, world);
+	else if (kind == "cylinder")  triangles = cylinder_of(shape, world);
+	else if (kind == "sphere")    triangles = sphere_of(shape, world);
+	else if (kind == "obj" || kind == "ply") {
+		std::string path = PathName::below(file.folder, filename_property(shape));
+		triangles = kind == "obj" ? OBJLoader::load(path) : PLYLoader::load(path);
+		for (Triangle & t : triangles) for (Vector3 * p : { &t.position_0, &t.position_1, &t.position_2 }) *p = Matrix4::transform_position(world, *p);
+	}
+	else return false;
+	return true;
 }
 
 const ShapeKind SHAPE_KINDS[] = {

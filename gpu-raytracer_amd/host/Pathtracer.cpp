@@ -302,6 +302,20 @@ void Pathtracer::update(float delta) {
 		calc_light_mesh_weights();
 		if (!gpu_config.enable_svgf) sample_index = 0;
 	}
+	if (invalidated_fog) {
+		rt_fog_volume v = { };
+		if (scene.has_fog) {
+			const FogVolume & f = scene.fog;
+			const float values[13] = { f.box_min.x, f.box_min.y, f.box_min.z, f.box_max.x, f.box_max.y, f.box_max.z, f.sigma_a.x, f.sigma_a.y, f.sigma_a.z, f.sigma_s.x, f.sigma_s.y, f.sigma_s.z, f.g };
+			memcpy(&v, values, sizeof(values));
+		}
+		if (ctx && (scene.has_fog != fog_on_device || memcmp(&v, &fog_record_on_device, sizeof(v)) != 0)) {
+			check(rt_set_fog_volume(ctx, scene.has_fog ? &v : nullptr));
+			fog_on_device = scene.has_fog; fog_record_on_device = v;
+			sample_index = 0;
+		}
+		invalidated_fog = false;
+	}
 	if (invalidated_light_mesh_weights || invalidated_delta_lights) {   // (after the emitters: the share weighs against their total; after the TLAS: the scene's bounds)
 		if (!scene.delta_lights.empty() || !delta_light_records.empty() || delta_lights_uploaded) calc_delta_lights();
 		invalidated_delta_lights = false;

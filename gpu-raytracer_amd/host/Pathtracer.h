@@ -33,6 +33,9 @@ struct Pathtracer final : Integrator {
 	// Delta emitters: scene.delta_lights as rt_upload_delta_lights takes them, and the share that goes with them
 	std::vector<rt_delta_light> delta_light_records;
 	float              delta_light_share = 0.0f;
+	// Fog volume: scene.fog reaches the device at update() when it has changed (the call drains what is in flight)
+	bool               invalidated_fog = true;
+	bool               fog_on_device = false; rt_fog_volume fog_record_on_device = { };
 	bool               invalidated_delta_lights = true;   // scene.delta_lights or cpu_config.delta_light_share changed
 	bool               delta_lights_uploaded = false, warned_delta_lights_without_nee = false;
 	std::vector<rt_delta_light> delta_lights_on_device; float delta_light_share_on_device = 0.0f;   // what the device holds (an unchanged table is not uploaded again: the upload drains)

@@ -369,6 +369,27 @@ Scene::Scene() : camera(Math::deg_to_rad(85.0f)) {
 	}
 	sky.load(cpu_config.sky_filename);
 	if (cpu_config.alpha_masks) asset_manager.add_alpha_masks();
+	if (cpu_config.fog) {
+		const float * b = cpu_config.fog_box, * a = cpu_config.fog_sigma_a, * s = cpu_config.fog_sigma_s;
+		fog.box_min = Vector3(b[0], b[1], b[2]); fog.box_max = Vector3(b[3], b[4], b[5]);
+		fog.sigma_a = Vector3(a[0], a[1], a[2]); fog.sigma_s = Vector3(s[0], s[1], s[2]); fog.g = cpu_config.fog_g;
+		std::string why = fog.complaint();
+		if (!why.empty()) throw ParseError("fog: " + why);
+		// (the files are loaded by now: the loader's "second fog volume" speaks of shapes of the files alone, never of this key)
+		if (has_fog) fprintf(stderr, "WARNING: the config key fog (--fog) replaces the fog volume of the scene file\n");
+		has_fog = true;
+	}
+}
+
+std::string FogVolume::complaint() const {
+	const float lo[3] = { box_min.x, box_min.y, box_min.z }, hi[3] = { box_max.x, box_max.y, box_max.z };
+	const float a[3] = { sigma_a.x, sigma_a.y, sigma_a.z }, s[3] = { sigma_s.x, sigma_s.y, sigma_s.z };
+	for (int k = 0; k < 3; k++) {
+		if (!(std::isfinite(lo[k]) && std::isfinite(hi[k]) && lo[k] < hi[k])) return "the box must be finite with min < max on every axis";
+		if (!(std::isfinite(a[k]) && a[k] >= 0.0f && std::isfinite(s[k]) && s[k] >= 0.0f)) return "sigma_a and sigma_s must be finite and not negative";
+	}
+	if (!(std::fabs(g) < 1.0f)) return "g must lie in (-1, 1)";
+	return "";
 }
 
 Mesh & Scene::add_mesh(std::string name, Handle<MeshData> mesh_data_handle, Handle<Material> material_handle) {

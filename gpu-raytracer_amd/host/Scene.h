@@ -78,8 +78,18 @@ struct DeltaLight {
 	float cutoff = 0.0f, beam = 0.0f;
 };
 
+// The scene-wide fog volume: a homogeneous medium inside an axis-aligned box. Not part of a scene's description (grt_scene_describe).
+struct FogVolume {
+	Vector3 box_min, box_max = Vector3(1.0f), sigma_a, sigma_s;
+	float g = 0.0f;
+	// what rt_set_fog_volume will ask too, with its reason (empty: fine)
+	std::string complaint() const;
+};
+
 struct Scene {
 	AssetManager asset_manager;
+	bool      has_fog = false;   // (after a change of either: Pathtracer::invalidated_fog)
+	FogVolume fog;
 	std::vector<DeltaLight> delta_lights;   // (after a change: Pathtracer::invalidated_delta_lights)
 
 	Camera            camera;

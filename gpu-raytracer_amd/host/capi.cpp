@@ -7,7 +7,10 @@
 #include "Exporters.h"
 #include "BlockCompression.h"
 #include "AO.h"
+#include "capi.h"
 
+#include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 
@@ -80,6 +83,23 @@ int grt_config_set(const char * key, double value) {
 		if (!(value == 0.0 || (value > 0.0 && value <= 1.0))) { g_host_error = "delta_light_share must be 0 (by power) or in (0, 1]"; return -1; }
 		cpu_config.delta_light_share = float(value);
 	}
+	else if (k == "fog") {   // 0: off (a box is given as a string: grt_config_set_string)
+		if (value != 0.0) { g_host_error = "fog must be 0 / \"off\" or a box \"minx,miny,minz,maxx,maxy,maxz\""; return -1; }
+		cpu_config.fog = false;
+	}
+	else if (k == "fog_sigma_a" || k == "fog_sigma_s") {   // one number for all three channels (three: grt_config_set_string)
+		if (!(value >= 0.0 && value < 1e30)) { g_host_error = k + " must be finite and not negative"; return -1; }
+		float * sigma = k == "fog_sigma_a" ? cpu_config.fog_sigma_a : cpu_config.fog_sigma_s;
+		sigma[0] = sigma[1] = sigma[2] = float(value);
+	}
+	else if (k == "fog_g") {
+		if (!(value > -1.0 && value < 1.0)) { g_host_error = "fog_g must lie in (-1, 1)"; return -1; }
+		cpu_config.fog_g = float(value);
+	}
+	else if (k == "fog_volumes") {
+		if (!(value == 0.0 || value == 1.0)) { g_host_error = "fog_volumes must be 0 or 1"; return -1; }
+		cpu_config.fog_volumes = int(value);
+	}
 	else if (k == "sky_sampling") {   // 0 (off) or (0, 1]: the sky's share of the light samples (rt_set_sky_sampling)
 		if (!(value == 0.0 || (value > 0.0 && value <= 1.0))) { g_host_error = "sky_sampling must be 0 (off) or in (0, 1]"; return -1; }
 		cpu_config.sky_sampling = float(value);
@@ -119,6 +139,37 @@ int grt_config_set(const char * key, double value) {
 	return 0;
 }
 
+// The keys whose values are lists of numbers: fog ("off", or the box "minx,miny,minz,maxx,maxy,maxz"), fog_sigma_a and fog_sigma_s (one number or three).
+int grt_config_set_string(const char * key, const char * value) {
+	std::string k(key), text(value ? value : "");
+	if (k != "fog" && k != "fog_sigma_a" && k != "fog_sigma_s") { g_host_error = "config key '" + k + "' does not take a string"; return -1; }
+	if (k == "fog" && (text == "off" || text == "0")) { cpu_config.fog = false; return 0; }
+	float numbers[6]; int count = 0;
+	const char * cursor = text.c_str();
+	while (*cursor) {
+		char * end = nullptr;
+		float v = strtof(cursor, &end);
+		if (end == cursor || count == 6 || !std::isfinite(v)) { count = -1; break; }
+		numbers[count++] = v;
+		cursor = end;
+		while (*cursor == ' ') cursor++;
+		if (*cursor == ',') { cursor++; if (!*cursor) { count = -1; break; } }
+		else if (*cursor) { count = -1; break; }
+	}
+	if (k == "fog") {
+		if (count != 6) { g_host_error = "fog must be \"off\" or a box \"minx,miny,minz,maxx,maxy,maxz\""; return -1; }
+		for (int a = 0; a < 3; a++) if (!(numbers[a] < numbers[a + 3])) { g_host_error = "fog: the box needs min < max on every axis"; return -1; }
+		memcpy(cpu_config.fog_box, numbers, sizeof(cpu_config.fog_box));
+		cpu_config.fog = true;
+		return 0;
+	}
+	if (count != 1 && count != 3) { g_host_error = k + " takes one number or three (\"r,g,b\")"; return -1; }
+	for (int a = 0; a < count; a++) if (!(numbers[a] >= 0.0f)) { g_host_error = k + " must not be negative"; return -1; }
+	float * sigma = k == "fog_sigma_a" ? cpu_config.fog_sigma_a : cpu_config.fog_sigma_s;
+	for (int a = 0; a < 3; a++) sigma[a] = numbers[count == 1 ? 0 : a];
+	return 0;
+}
+
 double grt_config_get(const char * key) {
 	std::string k(key);
 	if (k == "num_bounces")    return gpu_config.num_bounces;
@@ -130,6 +181,9 @@ double grt_config_get(const char * key) {
 	if (k == "sky_sampling")   return cpu_config.sky_sampling;
 	if (k == "alpha_masks")    return cpu_config.alpha_masks;
 	if (k == "delta_lights")   return cpu_config.delta_lights;
+	if (k == "fog")            return cpu_config.fog ? 1.0 : 0.0;
+	if (k == "fog_g")          return cpu_config.fog_g;
+	if (k == "fog_volumes")    return cpu_config.fog_volumes;
 	if (k == "delta_light_share") return cpu_config.delta_light_share;
 	if (k == "noise_target")      return cpu_config.noise_target;
 	if (k == "noise_min_samples") return cpu_config.noise_min_samples;
@@ -272,6 +326,26 @@ int grt_scene_add_delta_light(void * scene, const float * in12) {
 	return int(s->delta_lights.size()) - 1;
 }
 void grt_scene_clear_delta_lights(void * scene) { ((Scene *)scene)->delta_lights.clear(); }
+// The fog volume as 13 floats {box_min[3], box_max[3], sigma_a[3], sigma_s[3], g}; a change takes effect at the next update after invalidate("fog").
+int grt_scene_set_fog(void * scene, const float * in13) {
+	Scene * s = (Scene *)scene;
+	FogVolume f;
+	f.box_min = Vector3(in13[0], in13[1], in13[2]); f.box_max = Vector3(in13[3], in13[4], in13[5]);
+	f.sigma_a = Vector3(in13[6], in13[7], in13[8]); f.sigma_s = Vector3(in13[9], in13[10], in13[11]); f.g = in13[12];
+	std::string why = f.complaint();
+	if (!why.empty()) { g_host_error = "grt_scene_set_fog: " + why; return -1; }
+	s->fog = f; s->has_fog = true;
+	return 0;
+}
+void grt_scene_clear_fog(void * scene) { ((Scene *)scene)->has_fog = false; }
+int grt_scene_get_fog(void * scene, float * out13) {
+	const Scene * s = (const Scene *)scene;
+	if (!s->has_fog) return 0;
+	const FogVolume & f = s->fog;
+	const float values[13] = { f.box_min.x, f.box_min.y, f.box_min.z, f.box_max.x, f.box_max.y, f.box_max.z, f.sigma_a.x, f.sigma_a.y, f.sigma_a.z, f.sigma_s.x, f.sigma_s.y, f.sigma_s.z, f.g };
+	memcpy(out13, values, sizeof(values));
+	return 1;
+}
 // Adds a texture file to the scene; data != 0: a data texture (normal map, see Texture::data). Textures reach the device when a
 // Pathtracer is created, so add them before. Returns the texture index, -1 on failure.
 int grt_scene_add_texture(void * scene, const char * filename, int data) {
@@ -506,6 +580,7 @@ void grt_pathtracer_invalidate(void * pt, const char * what) {
 	if (w == "gpu_config") p->invalidated_gpu_config = true;
 	if (w == "aovs")       p->invalidated_aovs = true;
 	if (w == "delta_lights") if (Pathtracer * pt_only = dynamic_cast<Pathtracer *>(p)) pt_only->invalidated_delta_lights = true;
+	if (w == "fog") if (Pathtracer * pt_only = dynamic_cast<Pathtracer *>(p)) pt_only->invalidated_fog = true;
 }
 void grt_pathtracer_aov_enable(void * pt, int aov, int enable) {
 	if (enable) as_integrator(pt)->aov_enable(AOVType(aov)); else as_integrator(pt)->aov_disable(AOVType(aov));

@@ -21,6 +21,7 @@
 #include "../AO.h"
 #include "../FrameSplit.h"
 #include "../Pathtracer.h"
+#include "../capi.h"
 #include "../Exporters.h"
 
 namespace {
@@ -100,6 +101,23 @@ std::vector<Option> make_options(CommandLine & cl) {
 		float p = parse_float(v, "--sky-sampling");
 		if (!(p == 0.0f || (p > 0.0f && p <= 1.0f))) die("--sky-sampling must be 0 (off) or in (0, 1]");
 		cpu_config.sky_sampling = p;
+	} });
+	o.push_back({ nullptr, "fog", "A homogeneous fog volume inside the box <minx,miny,minz,maxx,maxy,maxz> (or off): scattering with light sampling at every scatter event", 1, [](const char * v) {
+		if (grt_config_set_string("fog", v) != 0) die(std::string("--fog: ") + grt_last_error());
+	} });
+	o.push_back({ nullptr, "fog-sigma-a", "Absorption coefficient of the fog per unit length: one number or r,g,b (default 0)", 1, [](const char * v) {
+		if (grt_config_set_string("fog_sigma_a", v) != 0) die(std::string("--fog-sigma-a: ") + grt_last_error());
+	} });
+	o.push_back({ nullptr, "fog-sigma-s", "Scattering coefficient of the fog per unit length: one number or r,g,b (default 0.1)", 1, [](const char * v) {
+		if (grt_config_set_string("fog_sigma_s", v) != 0) die(std::string("--fog-sigma-s: ") + grt_last_error());
+	} });
+	o.push_back({ nullptr, "fog-g", "Henyey-Greenstein asymmetry of the fog in (-1, 1): 0 isotropic (default), towards 1 forward scattering", 1, [](const char * v) {
+		float g = parse_float(v, "--fog-g");
+		if (!(g > -1.0f && g < 1.0f)) die("--fog-g must lie in (-1, 1)");
+		cpu_config.fog_g = g;
+	} });
+	o.push_back({ nullptr, "fog-volumes", "1: a scene file's shape with a null BSDF and an interior homogeneous medium becomes the fog volume over its bounding box; 0 (default): loaded as before", 1, [](const char * v) {
+		cpu_config.fog_volumes = parse_bool(v) ? 1 : 0;
 	} });
 	o.push_back({ nullptr, "delta-lights", "Point emitters of a scene file load as true point lights (intensity in W/sr) instead of tiny emissive spheres", 0, [](const char *) { cpu_config.delta_lights = 1; } });
 	o.push_back({ nullptr, "delta-light-share", "Share of the light samples that goes to point, spot and directional emitters beside area emitters: 0 = by power (default), (0, 1]", 1, [](const char * v) {

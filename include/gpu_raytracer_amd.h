@@ -162,6 +162,8 @@ const char * rt_version(void);
  *      result struct of their own; the per-pixel noise estimate, off by default)
  *      (still 17: rt_select_active_cells, rt_set_pixel_list, rt_get_pixel_list, rt_read_pixel_list, rt_select_pixels_images, rt_accumulate_list_frames
  *      -- new entry points and a result struct of their own; adaptive sampling, off by default)
+ *      (still 17: rt_set_fog_volume, rt_get_fog_volume, rt_fog_segments, rt_attenuate_shadow_rays, rt_sort_rays_fog -- new entry points and a
+ *      struct of their own; the fog volume, off until one is set)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
 #define RT_ABI_VERSION 17
 int rt_abi_version(void);
@@ -804,7 +806,9 @@ int rt_sort_rays(rt_context * ctx, int merged, int step, int sample_index, const
  * virtual pixel beyond the frames, two entries with one virtual pixel, a mesh id beyond the instance table, a triangle id beyond the
  * triangle array, an instance whose material is not of the queue's type, a medium id beyond rt_upload_media's table on an entry flagged
  * inside a medium, a slot beyond the table, a submission beyond 128, an entry's bounce outside [0, min(RT_MAX_BOUNCES, num_bounces)) or
- * a slot whose birth is not its submission's. (An addition that changes no struct: RT_ABI_VERSION stays.)                          */
+ * a slot whose birth is not its submission's. (An addition that changes no struct: RT_ABI_VERSION stays.)
+ * While a fog volume of positive density is in force (rt_set_fog_volume) an entry of bounce 0 is shaded with the throughput its record carries, as the
+ * ..._fog sort instances store it (the camera's segment may have crossed the fog); without one, bounce 0 takes a throughput of 1 whatever the record holds. */
 #define RT_SHADE_SHADOW_WORDS 11
 int rt_shade_rays(rt_context * ctx, int merged, int step, int sample_index, int material_slot, const uint32_t * material_in, size_t count,
                   const int32_t * slot_table, size_t slot_count, const int32_t * submission_birth,
@@ -840,6 +844,47 @@ int rt_select_pixels_images(rt_context * ctx, const float * mean, const float * 
  * (RT_ERROR_INVALID_ARG): an entry outside the frame and a pixel listed twice -- the fold is a plain read-modify-write.                */
 int rt_accumulate_list_frames(rt_context * ctx, const int32_t * first_sample, const int32_t * sample_count, size_t submissions,
                               float * frames, float * accumulator, float * moments, const uint32_t * list, size_t list_count, uint32_t sentinel, float * final_image);
+/* ---- fog volume ---------------------------------------------------------------------------------------------------
+ * One scene-wide homogeneous medium inside an axis-aligned box, with multiple scattering and light sampling at every scatter vertex. Off
+ * until a volume is set; while it is off a context launches exactly the kernels it launched before these calls existed. (Additions that
+ * change no struct and no call: RT_ABI_VERSION stays.)
+ * rt_set_fog_volume: NULL clears the volume. Checked on the host before anything is staged -- a finite box with min < max on every axis,
+ * finite sigmas >= 0, |g| < 1 -- and a refused call (RT_ERROR_INVALID_ARG with a message) leaves the volume before it in force. A change
+ * completes what the context has in flight first. A volume whose sigma_a + sigma_s is 0 in all three channels is stored (rt_get_fog_volume
+ * returns it) but renders as no volume. Rendering with a volume in force and enable_svgf is refused (a scatter vertex has no g-buffer);
+ * the AO integrator ignores the volume.                                                                                            */
+typedef struct rt_fog_volume {
+	float box_min[3], box_max[3];
+	float sigma_a[3], sigma_s[3];   /* absorption and scattering coefficients per unit length, RGB */
+	float g;                        /* Henyey-Greenstein asymmetry, |g| < 1 */
+	uint32_t reserved[3];           /* ignored on input, 0 on output */
+} rt_fog_volume;                    /* 64 bytes */
+int rt_set_fog_volume(rt_context * ctx, const rt_fog_volume * volume);
+int rt_get_fog_volume(rt_context * ctx, rt_fog_volume * out, int * out_set);
+/* The fog's segment step on explicit segments (synchronous), through the device functions the sort kernels call, on the volume in force
+ * (RT_ERROR_NOT_READY without one; a volume of zero density is taken as it is). probes: count x RT_FOG_SEGMENT_IN 32-bit words {o[3],
+ * d[3], t_end (RT_INFINITY: a miss), pixel, bounce, sample (uint32), throughput[3], inside_medium (uint32: 0 / 1), pad[2]}. out: count x
+ * RT_FOG_SEGMENT_OUT words {t0, t1 (the clipped interval; both 0 when it is empty), the two random numbers, scattered (uint32), distance
+ * (along the clipped interval; RT_INFINITY beyond its end), throughput'[3], vertex[3], pad[4]}. An entry flagged inside a medium comes back
+ * with t0 = t1 = 0, its throughput untouched. Needs the RNG tables and rt_resize (the pixel's random numbers).                       */
+#define RT_FOG_SEGMENT_IN  16
+#define RT_FOG_SEGMENT_OUT 16
+int rt_fog_segments(rt_context * ctx, const uint32_t * probes, size_t count, uint32_t * out);
+/* kernel_fog_attenuate_shadows on an explicit shadow queue (synchronous): shadow_in / shadow_out: count x RT_SHADE_SHADOW_WORDS in
+ * rt_shade_rays' layout. The launch is the one of the context's scheduler (rt_set_scheduler): the per-bounce loop's reads the count from
+ * RtBufferSizes::shadow[0], the merged wavefront's from the control block's shadow_count[0]. The volume in force applies (RT_ERROR_NOT_READY
+ * without one; a volume of zero density is taken as it is).                                                                          */
+int rt_attenuate_shadow_rays(rt_context * ctx, const uint32_t * shadow_in, size_t count, uint32_t * shadow_out);
+/* rt_sort_rays with the fog volume in force: the ..._fog instance of the sort launch, which appends the light samples of its scatter
+ * vertices to the shadow queue. Arguments as rt_sort_rays, plus shadow_out: capacity x RT_SHADE_SHADOW_WORDS (rt_shade_rays' layout; filled
+ * with the sentinel first) and shadow_count: the shadow queue's counter after the launch. RT_ERROR_NOT_READY without a volume of positive
+ * density.                                                                                                                          */
+int rt_sort_rays_fog(rt_context * ctx, int merged, int step, int sample_index, const uint32_t * trace_in, size_t count,
+                     const int32_t * slot_table, size_t slot_count, const int32_t * submission_birth,
+                     size_t capacity, size_t frame_slots, uint32_t sentinel,
+                     uint32_t * trace_out, uint32_t * material_out, int32_t * counters6,
+                     float * aov_frames, float * gbuffer_normal_and_depth, int32_t * gbuffer_mesh_id_and_triangle_id, float * gbuffer_screen_position_prev,
+                     int32_t * pixel_query2, int32_t * stats, uint32_t * shadow_out, int32_t * shadow_count);
 /* Streaming-read bandwidth probe used as the measured HBM roofline (GB/s).                 */
 int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps);
 
