@@ -20,8 +20,9 @@
 //                 leaf order of its triangles, the ranges of its inner children = the next level
 //   4  the 96-byte shading triangles and the 48-byte traversal copy are gathered into leaf order
 // Closest hits do not depend on the shape of the tree (up to exact ties in t between different triangles, which a scene
-// with duplicated geometry can have); tests/test_gpu_blas.py checks hits against the host-built trees and the node
-// invariants with the independent decoder of tests/test_tlas.py. A Morton tree is cheaper to build and dearer to traverse
+// with duplicated geometry can have); tests/test_gpu_blas.py checks hits against the host-built trees on whole scenes, and
+// tests/test_gpu_blas_cases.py holds every step below to its float32 restatement (tests/blas_reference.py) byte for byte and to
+// float64 rules on the nodes, case by case (tests/blas_cases.py). A Morton tree is cheaper to build and dearer to traverse
 // than the SAH tree (measured: profiles/r03_device_blas.txt): the host classes use it on request (device_blas = 1).
 #include "rt_math.h"
 #include "rt_build_args.h"
@@ -294,6 +295,9 @@ __global__ void __launch_bounds__(256) kernel_blas_nodes(BlasBuildArgs a, int le
 			float lo = floorf((box.min[d] - node.min[d]) * inv_e[d]);
 			float hi = ceilf ((box.max[d] - node.min[d]) * inv_e[d]);
 			lo = tlas_minf(tlas_maxf(lo, 0.0f), 255.0f); hi = tlas_minf(tlas_maxf(hi, 0.0f), 255.0f);
+			// the padding of flat triangle boxes does not survive `box - node.min` once |node.min| >= 2^16 (0.001 is below half a float32
+			// spacing there): both bounds land on one grid line and the child would never be entered. The TLAS build's rule: one step wider
+			tlas_keep_thickness(lo, hi);
 			bytes[32 + 16 * d + my_slot]     = uint8_t(lo);
 			bytes[32 + 16 * d + 8 + my_slot] = uint8_t(hi);
 		}

@@ -306,7 +306,8 @@ int rt_build_geometry(rt_context * ctx, const void * triangles, size_t triangle_
 	// for the next build, of possibly unrelated geometry: advisor finding, round 5); whatever does not fit the input is ignored
 	std::vector<float> given_boxes; size_t given_first = 0;
 	if (ctx) { given_boxes.swap(ctx->build_boxes); given_first = ctx->build_boxes_first; ctx->build_boxes_first = 0; }
-	RT_REQUIRE(ctx, ctx && triangles && mesh_first_triangle && mesh_count >= 1, "rt_build_geometry: NULL argument");
+	RT_REQUIRE(ctx, ctx && triangles && mesh_first_triangle, "rt_build_geometry: NULL argument");
+	RT_REQUIRE(ctx, triangle_count >= 1 && mesh_count >= 1, "rt_build_geometry: at least one triangle and one mesh (a mesh may be empty, the input may not)");
 	RT_REQUIRE(ctx, triangle_count < (size_t(1) << 30) && mesh_count < (size_t(1) << 24), "rt_build_geometry: too many triangles / meshes");
 	RT_REQUIRE(ctx, mesh_first_triangle[0] == 0 && size_t(mesh_first_triangle[mesh_count]) == triangle_count, "rt_build_geometry: mesh_first_triangle must run from 0 to triangle_count");
 	for (size_t m = 0; m < mesh_count; m++) RT_REQUIRE(ctx, mesh_first_triangle[m] <= mesh_first_triangle[m + 1], "rt_build_geometry: mesh_first_triangle must not decrease");

@@ -130,7 +130,8 @@ RT_HD void tlas_assign_slots(const TlasBox & node, const TlasBox * children, int
 // No flat child boxes: the traversal's node test is `tmin < tmax`, a child box whose lower and upper bound were quantised to the
 // same grid line is never entered and the instance below it is lost (a flat mesh, or one much smaller than a grid step, whose
 // bounds happen to lie on a grid line). Such a box is widened by one grid step: upwards, or downwards at the end of the grid.
-// (kernels_blas.hip has the same lesson for the BLAS build, where it pads the triangle boxes themselves.)
+// (kernels_blas.hip pads the triangle boxes themselves for the BLAS build and applies this rule as well: the padding is lost
+// in `box - node.min` far from a node's origin.)
 RT_HD void tlas_keep_thickness(float & lo, float & hi) {
 	if (hi == lo) { if (hi < 255.0f) hi += 1.0f; else lo -= 1.0f; }
 }

@@ -232,7 +232,10 @@ int rt_get_sky_sampling(const rt_context * ctx, float * out_probability);
  * triangles per leaf) and stores the triangles in leaf order: out_triangle_positions[i] is where input triangle i went (the
  * caller remaps whatever names triangles by index: light tables), out_root_indices[m] the root node of mesh m (node slots
  * [0, reserved_tlas_nodes) stay free for the TLAS). A linear BVH: built in a fraction of the host build's time, dearer to
- * traverse than the SAH tree; closest hits are the same. rt_read_geometry returns what was built (host views, checker).   */
+ * traverse than the SAH tree; closest hits are the same. rt_read_geometry returns what was built (host views, checker).
+ * A mesh may have no triangles (its root is a node without children); an input of no triangles or no meshes is refused with
+ * RT_ERROR_INVALID_ARG, like a mesh_first_triangle that decreases or does not run from 0 to triangle_count, and leaves the
+ * context's geometry as it was.                                                                                            */
 int rt_build_geometry(rt_context * ctx, const void * triangles, size_t triangle_count, const int32_t * mesh_first_triangle, size_t mesh_count,
                       size_t reserved_tlas_nodes, int32_t * out_root_indices, int32_t * out_triangle_positions, size_t * out_node_count, float * out_build_ms);
 /* Spatial splits for the build above, decided by the caller (early split clipping): triangles [first_triangle, first_triangle + count) of the NEXT
