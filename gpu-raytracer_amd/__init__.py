@@ -112,6 +112,9 @@ def device_lib():
         lib.rt_fog_segments.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
         lib.rt_attenuate_shadow_rays.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
         lib.rt_sort_rays_fog.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_uint32] + [c_void_p] * 10 + [POINTER(c_int)]
+        lib.rt_set_fog_density.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int]
+        lib.rt_get_fog_density_info.argtypes = [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_float), POINTER(c_int)]
+        lib.rt_fog_density_segments.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
         lib.rt_set_bvh_type.argtypes = [c_void_p, c_int]
         lib.rt_upload_material_opacity.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]
         lib.rt_read_material_opacity.argtypes = [c_void_p, c_int, c_void_p, c_size_t, POINTER(c_int), POINTER(c_int)]
@@ -172,6 +175,11 @@ def host_lib():
         lib.grt_scene_set_fog.argtypes = [c_void_p, POINTER(c_float)]
         lib.grt_scene_get_fog.argtypes = [c_void_p, POINTER(c_float)]
         lib.grt_scene_clear_fog.argtypes = [c_void_p]
+        lib.grt_scene_set_fog_density.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int]
+        lib.grt_scene_get_fog_density.argtypes = [c_void_p, POINTER(c_int), c_void_p, c_size_t]
+        lib.grt_scene_clear_fog_density.argtypes = [c_void_p]
+        lib.grt_vol_read.argtypes = [c_char_p, POINTER(c_int), POINTER(c_float), c_void_p, c_size_t]
+        lib.grt_vol_write.argtypes = [c_char_p, c_void_p, c_int, c_int, c_int, POINTER(c_float)]
         lib.grt_config_get.restype = c_double
         lib.grt_scene_load.restype = c_void_p
         lib.grt_scene_load.argtypes = [c_char_p, c_char_p]
@@ -440,8 +448,8 @@ def config_set(**kwargs):
     for key, value in kwargs.items():
         if key == "bvh_type" and isinstance(value, str):
             value = BVH_TYPES[value.lower()]
-        if key in ("fog", "fog_sigma_a", "fog_sigma_s") and not isinstance(value, (int, float)):   # "off" or a box; one number or three
-            text = value if isinstance(value, str) else ",".join(repr(float(v)) for v in value)
+        if key in ("fog", "fog_sigma_a", "fog_sigma_s", "fog_density") and not isinstance(value, (int, float)):   # "off" or a box; one number or three; "off" or a path
+            text = str(value) if isinstance(value, (str, os.PathLike)) else ",".join(repr(float(v)) for v in value)
             if lib.grt_config_set_string(key.encode(), text.encode()) != 0:
                 raise KeyError(lib.grt_last_error().decode(errors="replace"))
             continue
@@ -645,6 +653,27 @@ class Scene:
             return None
         v = [float(x) for x in values]
         return dict(box_min=tuple(v[0:3]), box_max=tuple(v[3:6]), sigma_a=tuple(v[6:9]), sigma_s=tuple(v[9:12]), g=v[12])
+
+    def set_fog_density(self, density):
+        """The density grid of the fog volume: an array of shape (nz, ny, nx) of finite values >= 0, laid over the box of the fog
+        volume; inside a voxel the volume's sigmas are multiplied by its value. Takes effect at the next update() after Pathtracer.invalidate("fog")."""
+        d = _f32(density)
+        if d.ndim != 3:
+            raise ValueError("a density grid has shape (nz, ny, nx), not %r" % (d.shape,))
+        _host_check(host_lib().grt_scene_set_fog_density(self.handle, d.ctypes.data, d.shape[2], d.shape[1], d.shape[0]))
+
+    def clear_fog_density(self):
+        host_lib().grt_scene_clear_fog_density(self.handle)
+
+    @property
+    def fog_density(self):
+        """None, or the density grid as a float32 array of shape (nz, ny, nx)."""
+        dims = (c_int * 3)()
+        if not host_lib().grt_scene_get_fog_density(self.handle, dims, None, 0):
+            return None
+        out = np.zeros((dims[2], dims[1], dims[0]), np.float32)
+        host_lib().grt_scene_get_fog_density(self.handle, dims, out.ctypes.data, out.size)
+        return out
 
     def clear_delta_lights(self):
         host_lib().grt_scene_clear_delta_lights(self.handle)
@@ -1636,6 +1665,55 @@ def attenuate_shadow_rays(ctx, shadow_in):
     out = np.zeros_like(q)
     _dev_check(ctx, device_lib().rt_attenuate_shadow_rays(ctx, q.ctypes.data if q.size else None, q.shape[0], out.ctypes.data if q.size else None))
     return out
+
+
+def set_fog_density(ctx, density):
+    """rt_set_fog_density: the density grid of the fog volume as an array of shape (nz, ny, nx), x fastest; None clears the grid.
+    Returns the status (0: RT_OK); the message of a refusal is rt_last_error's."""
+    if density is None:
+        return device_lib().rt_set_fog_density(ctx, None, 0, 0, 0)
+    d = _f32(density)
+    if d.ndim != 3:
+        raise ValueError("a density grid has shape (nz, ny, nx), not %r" % (d.shape,))
+    nz, ny, nx = d.shape
+    return device_lib().rt_set_fog_density(ctx, d.ctypes.data, nx, ny, nz)
+
+
+def get_fog_density_info(ctx):
+    """rt_get_fog_density_info: None without a grid, else dict(dims=(nx, ny, nz), bricks=, empty_bricks=, max_density=)."""
+    dims = (c_int * 3)(); bricks = c_int(); empty = c_int(); largest = c_float(); is_set = c_int()
+    _dev_check(ctx, device_lib().rt_get_fog_density_info(ctx, dims, byref(bricks), byref(empty), byref(largest), byref(is_set)))
+    if not is_set.value:
+        return None
+    return dict(dims=tuple(dims), bricks=bricks.value, empty_bricks=empty.value, max_density=largest.value)
+
+
+def fog_density_segments(ctx, probes):
+    """rt_fog_density_segments: the segment step over the density grid in force on (N, 16) uint32 records (fog_segment_probes). Returns
+    rt_fog_segments' records with word 12 the density length (float), word 13 the voxels read, word 14 the empty bricks crossed."""
+    p = np.ascontiguousarray(probes, np.uint32).reshape(-1, FOG_SEGMENT_IN)
+    out = np.zeros((p.shape[0], FOG_SEGMENT_OUT), np.uint32)
+    _dev_check(ctx, device_lib().rt_fog_density_segments(ctx, p.ctypes.data if p.size else None, p.shape[0], out.ctypes.data if p.size else None))
+    return out
+
+
+def read_vol(path):
+    """A Mitsuba 0.6 gridvolume file (VOL, version 3, float32, one channel) as (density of shape (nz, ny, nx), box (6,) float32: min[3], max[3])."""
+    lib = host_lib()
+    dims = (c_int * 3)(); box = (c_float * 6)()
+    _host_check(lib.grt_vol_read(str(path).encode(), dims, box, None, 0))
+    density = np.zeros((dims[2], dims[1], dims[0]), np.float32)
+    _host_check(lib.grt_vol_read(str(path).encode(), dims, box, density.ctypes.data, density.size))
+    return density, np.array(list(box), np.float32)
+
+
+def write_vol(path, density, box=(0.0, 0.0, 0.0, 1.0, 1.0, 1.0)):
+    """Write `density` (nz, ny, nx) with the bounding box (min[3], max[3]) as a Mitsuba 0.6 gridvolume file."""
+    d = _f32(density)
+    if d.ndim != 3:
+        raise ValueError("a density grid has shape (nz, ny, nx), not %r" % (d.shape,))
+    b = (c_float * 6)(*[float(v) for v in box])
+    _host_check(host_lib().grt_vol_write(str(path).encode(), d.ctypes.data, d.shape[2], d.shape[1], d.shape[0], b))
 
 
 NORMAL_PROBE_IN = 48   # floats per probe record of rt_perturb_normals

@@ -327,6 +327,18 @@ int rt_set_config(rt_context * ctx, const rt_gpu_config * config) {
 
 // The fog volume. Everything is checked before anything changes; a change completes what is in flight first (paths in flight were
 // sorted under the other estimator), as a change of the sky's share does.
+// fog_active: a volume is set, some sigma is positive, and there is no density grid or one with a positive maximum -- a volume of zero density, and a grid of
+// zeros over any volume, are stored and render as no volume. fog_grid: the ..._grid kernels are the ones to launch. A grid without a volume is inert.
+static void fog_refresh_active(rt_context * ctx) {
+	RtParams & p = ctx->params;
+	float density = 0.0f;
+	for (int k = 0; k < 3; k++) density = fmaxf(density, ctx->fog.sigma_a[k] + ctx->fog.sigma_s[k]);
+	const bool grid = ctx->fog_grid_set;
+	p.fog_active = ctx->fog_set && density > 0.0f && (!grid || ctx->fog_grid_max > 0.0f);
+	p.fog_grid = p.fog_active && grid;
+	for (int k = 0; k < 3; k++) p.fog_grid_dims[k] = ctx->fog_grid_dims[k];
+	p.fog_density = (const float *)ctx->fog_density; p.fog_bricks = (const unsigned char *)ctx->fog_bricks;
+}
 int rt_set_fog_volume(rt_context * ctx, const rt_fog_volume * volume) {
 	RT_REQUIRE(ctx, ctx != nullptr, "rt_set_fog_volume: NULL context");
 	rt_fog_volume v = { };
@@ -347,13 +359,71 @@ int rt_set_fog_volume(rt_context * ctx, const rt_fog_volume * volume) {
 	RT_HIP(ctx, quiesce(ctx));
 	ctx->fog_set = set; ctx->fog = v;
 	RtParams & p = ctx->params;
-	float density = 0.0f;
-	for (int k = 0; k < 3; k++) {
-		p.fog_box_min[k] = v.box_min[k]; p.fog_box_max[k] = v.box_max[k]; p.fog_sigma_a[k] = v.sigma_a[k]; p.fog_sigma_s[k] = v.sigma_s[k];
-		density = fmaxf(density, v.sigma_a[k] + v.sigma_s[k]);
-	}
+	for (int k = 0; k < 3; k++) { p.fog_box_min[k] = v.box_min[k]; p.fog_box_max[k] = v.box_max[k]; p.fog_sigma_a[k] = v.sigma_a[k]; p.fog_sigma_s[k] = v.sigma_s[k]; }
 	p.fog_g = v.g;
-	p.fog_active = set && density > 0.0f;   // a volume of zero density is stored and renders as no volume
+	fog_refresh_active(ctx);
+	return RT_OK;
+}
+
+// The density grid: state of its own beside the volume, mapped onto whatever box is in force. Checked on the host before anything is
+// staged; the new grid is allocated, copied and its brick table marked before the one before it is let go, so a refused or failed call leaves that in force.
+int rt_set_fog_density(rt_context * ctx, const float * density, int nx, int ny, int nz) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_set_fog_density: NULL context");
+	if (!density) {
+		if (!ctx->fog_grid_set) return RT_OK;
+		(void)hipSetDevice(ctx->device);
+		RT_HIP(ctx, quiesce(ctx));
+		device_free(ctx, ctx->fog_density); device_free(ctx, ctx->fog_bricks);
+		ctx->fog_density = ctx->fog_bricks = nullptr;
+		ctx->fog_grid_set = false; ctx->fog_grid_dims[0] = ctx->fog_grid_dims[1] = ctx->fog_grid_dims[2] = 0;
+		ctx->fog_grid_bricks = ctx->fog_grid_empty_bricks = 0; ctx->fog_grid_max = 0.0f;
+		fog_refresh_active(ctx);
+		return RT_OK;
+	}
+	const int dims[3] = { nx, ny, nz };
+	for (int k = 0; k < 3; k++) if (dims[k] < 1 || dims[k] > 1024) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_set_fog_density: n%c = %d outside 1 .. 1024", "xyz"[k], dims[k]);
+	const size_t cells = size_t(nx) * size_t(ny) * size_t(nz);
+	if (cells > size_t(1) << 27) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_set_fog_density: %d x %d x %d = %zu cells, more than 2^27", nx, ny, nz, cells);
+	float max_density = 0.0f;
+	for (size_t i = 0; i < cells; i++) {
+		const float v = density[i];
+		if (!(std::isfinite(v) && v >= 0.0f)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_set_fog_density: cell (%zu, %zu, %zu) = %.9g must be finite and >= 0", i % size_t(nx), i / size_t(nx) % size_t(ny), i / (size_t(nx) * size_t(ny)), double(v));
+		max_density = fmaxf(max_density, v);
+	}
+	(void)hipSetDevice(ctx->device);
+	RT_HIP(ctx, quiesce(ctx));
+	const int bricks = ((nx + 7) / 8) * ((ny + 7) / 8) * ((nz + 7) / 8);
+	void * dev_density = nullptr, * dev_bricks = nullptr, * dev_empty = nullptr;
+	int s = device_alloc(ctx, &dev_density, cells * sizeof(float));
+	if (!s) s = device_alloc(ctx, &dev_bricks, size_t(bricks));
+	if (!s) s = device_alloc(ctx, &dev_empty, sizeof(int));
+	int empty = 0;
+	hipError_t e = hipSuccess;
+	if (!s) {
+		e = hipMemcpyAsync(dev_density, density, cells * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+		if (e == hipSuccess) e = hipMemsetAsync(dev_empty, 0, sizeof(int), ctx->stream);
+		if (e == hipSuccess) { rt_launch_fog_mark_bricks((const float *)dev_density, nx, ny, nz, (unsigned char *)dev_bricks, (int *)dev_empty, ctx->stream); e = hipGetLastError(); }
+		if (e == hipSuccess) e = hipMemcpyAsync(&empty, dev_empty, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+		if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+	}
+	device_free(ctx, dev_empty);
+	if (s || e != hipSuccess) {
+		device_free(ctx, dev_density); device_free(ctx, dev_bricks);
+		return s ? s : fail(ctx, RT_ERROR_HIP, "rt_set_fog_density: %s", hipGetErrorString(e));
+	}
+	device_free(ctx, ctx->fog_density); device_free(ctx, ctx->fog_bricks);
+	ctx->fog_density = dev_density; ctx->fog_bricks = dev_bricks;
+	ctx->fog_grid_set = true; ctx->fog_grid_dims[0] = nx; ctx->fog_grid_dims[1] = ny; ctx->fog_grid_dims[2] = nz;
+	ctx->fog_grid_bricks = bricks; ctx->fog_grid_empty_bricks = empty; ctx->fog_grid_max = max_density;
+	fog_refresh_active(ctx);
+	return RT_OK;
+}
+
+int rt_get_fog_density_info(rt_context * ctx, int dims[3], int * bricks, int * empty_bricks, float * max_density, int * out_set) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_get_fog_density_info: NULL context");
+	RT_REQUIRE(ctx, dims && bricks && empty_bricks && max_density && out_set, "rt_get_fog_density_info: NULL argument");
+	for (int k = 0; k < 3; k++) dims[k] = ctx->fog_grid_dims[k];
+	*bricks = ctx->fog_grid_bricks; *empty_bricks = ctx->fog_grid_empty_bricks; *max_density = ctx->fog_grid_max; *out_set = ctx->fog_grid_set ? 1 : 0;
 	return RT_OK;
 }
 

@@ -197,6 +197,12 @@ struct rt_context {
 	// fog volume (rt_set_fog_volume): what the caller set, as rt_get_fog_volume returns it; RtParams::fog_* hold what the kernels read
 	bool fog_set = false;
 	rt_fog_volume fog = { };
+	// its density grid (rt_set_fog_density), state of its own beside the volume: the device copy, the brick table, what
+	// rt_get_fog_density_info reports. fog_refresh_active (rt_api.hip) settles RtParams::fog_active and fog_grid from both.
+	bool fog_grid_set = false;
+	int fog_grid_dims[3] = { 0, 0, 0 }, fog_grid_bricks = 0, fog_grid_empty_bricks = 0;
+	float fog_grid_max = 0.0f;
+	void * fog_density = nullptr, * fog_bricks = nullptr;
 	void * luts[6] = { }; bool luts_ready = false;
 	int bvh_width = 8;
 

@@ -703,6 +703,31 @@ int rt_fog_segments(rt_context * ctx, const uint32_t * probes, size_t count, uin
 	return probe.finish_and_read(out, dev_out, count * RT_FOG_SEGMENT_OUT * 4);
 }
 
+// rt_fog_density_segments: the segment step over the density grid in force (rt_fog_grid.h: the voxel march under the same clip, pair and weights), on
+// rt_fog_segments' records.
+int rt_fog_density_segments(rt_context * ctx, const uint32_t * probes, size_t count, uint32_t * out) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_fog_density_segments: NULL context");
+	RT_REQUIRE(ctx, (probes && out) || count == 0, "rt_fog_density_segments: NULL argument");
+	RT_REQUIRE(ctx, count <= size_t(1) << 24, "rt_fog_density_segments: more than 2^24 probes");
+	if (!ctx->fog_set) return fail(ctx, RT_ERROR_NOT_READY, "rt_fog_density_segments: no fog volume set (rt_set_fog_volume)");
+	if (!ctx->fog_grid_set) return fail(ctx, RT_ERROR_NOT_READY, "rt_fog_density_segments: no density grid set (rt_set_fog_density)");
+	(void)hipSetDevice(ctx->device);
+	int s = check_ready(ctx, "rt_fog_density_segments", NEED_RNG | NEED_FRAME); if (s) return s;
+	for (size_t i = 0; i < count; i++) {
+		const uint32_t * a = probes + i * RT_FOG_SEGMENT_IN;
+		if (a[7] >= 1u << 30) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_fog_density_segments: probe %zu: pixel %u beyond the 30-bit path index", i, a[7]);
+		if (a[8] >= unsigned(RT_MAX_BOUNCES)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_fog_density_segments: probe %zu: bounce %u outside [0, RT_MAX_BOUNCES)", i, a[8]);
+	}
+	if (count == 0) return RT_OK;
+	Probe probe(ctx, "rt_fog_density_segments");
+	uint32_t * dev_probes = probe.array<uint32_t>(count * RT_FOG_SEGMENT_IN, probes);
+	uint32_t * dev_out = probe.array<uint32_t>(count * RT_FOG_SEGMENT_OUT);
+	if ((s = probe.allocated())) return s;
+	RtParams p = ctx->params;   // (a grid of zeros, or a volume without density, is marched as it is: the device fields are set whenever a grid is)
+	rt_launch_fog_density_segments(p, dev_probes, int(count), dev_out, ctx->stream);
+	return probe.finish_and_read(out, dev_out, count * RT_FOG_SEGMENT_OUT * 4);
+}
+
 // rt_attenuate_shadow_rays: the fog's attenuation pass, as the context's scheduler launches it, on an explicit shadow queue. The parameter block is the
 // context's with the shadow queue and the word the launch reads its count from replaced by buffers of this call.
 int rt_attenuate_shadow_rays(rt_context * ctx, const uint32_t * shadow_in, size_t count, uint32_t * shadow_out) {

@@ -242,6 +242,13 @@ struct RtParams {
 	float fog_box_min[3], fog_box_max[3];
 	float fog_sigma_a[3], fog_sigma_s[3];
 	float fog_g;
+	// Density grid of the fog volume (rt_set_fog_density): rho[z][y][x] over the box above, x fastest, and one byte per brick of 8 x 8 x 8
+	// voxels (0: the brick holds no density). fog_grid: a grid with a positive maximum is in force -- only then do the launchers take the ..._fog_grid sort
+	// instances and the ..._grid attenuation kernels, the only kernels that read these fields. (A grid of zeros clears fog_active instead.)
+	int   fog_grid;
+	int   fog_grid_dims[3];
+	const float * fog_density;
+	const unsigned char * fog_bricks;
 };
 // Which instances of the sort and material kernels a launcher takes: 0 the plain ones, 1 the ..._sky ones (sky importance sampling alone), 2 the ..._split
 // ones (delta lights take a share, with or without the sky). Shadow rays are traced without triangle emitters whenever it is not 0.
@@ -345,6 +352,11 @@ void rt_launch_sample_delta_lights(const RtParams & p, const float * probes, int
 void rt_launch_fog_attenuate_shadows(const RtParams & p, int bounce, hipStream_t stream);
 void rt_launch_fog_attenuate_shadows_stream(const RtParams & p, hipStream_t stream);
 void rt_launch_fog_segments(const RtParams & p, const uint32_t * probes, int count, uint32_t * out, hipStream_t stream);
+// Density grid. The two attenuation launchers above take their ..._grid kernels while p.fog_grid; rt_launch_fog_density_segments is the
+// grid's segment step on rt_fog_segments' records; rt_launch_fog_mark_bricks fills the brick table of an uploaded grid (one workgroup per brick) and
+// adds the number of empty bricks to *empty_count.
+void rt_launch_fog_density_segments(const RtParams & p, const uint32_t * probes, int count, uint32_t * out, hipStream_t stream);
+void rt_launch_fog_mark_bricks(const float * density, int nx, int ny, int nz, unsigned char * bricks, int * empty_count, hipStream_t stream);
 // Test support: normal_map_perturb on explicit hits (rt_perturb_normals); RT_NORMAL_PROBE_IN floats in, 4 out per probe
 void rt_launch_perturb_normals(const RtParams & p, int texture_index, const float * probes, int count, float * out, hipStream_t stream);
 // Sky importance sampling (kernels_sky.hip). build: the three tables of RtParams from the sky; row_total: sky_height doubles, total: one double (the

@@ -137,6 +137,8 @@ struct CPUConfig {
 	float fog_sigma_a[3] = { 0.0f, 0.0f, 0.0f }, fog_sigma_s[3] = { 0.1f, 0.1f, 0.1f };
 	float fog_g = 0.0f;
 	int   fog_volumes = 0;
+	// Density grid of the fog volume: empty (off), or the path of a Mitsuba gridvolume file (.vol) laid over the volume's box
+	std::string fog_density;
 	int   static_slot_learning_viewpoint = 1;   // a quarter of those rays are paths from the camera as it stands when the tree is built (0: none are; half come from points of the free space, the rest from the surface, either way)
 	// ... and early split clipping (StaticBVHBuilder::presplit, as in front of the device build) in front of that builder's own SAH + spatial splits: fraction of
 	// the geometry's longest side above which a triangle is cut blindly first. 0: off.

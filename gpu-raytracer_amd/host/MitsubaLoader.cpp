@@ -399,12 +399,16 @@ struct SceneFile {
 
 	// -- the fog volume (config fog_volumes = 1): a shape with <bsdf type="null"/> and an interior homogeneous medium is the scene's fog over
 	// the shape's world bounding box, and is not added to the scene. One warning per file when the shape is not that box; a second such shape is refused.
+	// An interior medium of type "heterogeneous"  is the fog with a density grid: it must have a gridvolume density, a constant albedo and a
+	// scale; sigma_s = albedo * scale, sigma_a = (1 - albedo) * scale, and the grid's values lie over the shape's box (the file's own box is ignored, with one
+	// warning if it differs).
 	static bool fog_shape_triangles(SceneFile & file, const XMLNode & shape, std::vector<Triangle> & triangles);
 	bool warned_fog_shape_is_no_box = false;
 	bool fog_volume(const XMLNode & node) {
 		if (cpu_config.fog_volumes != 1) return false;
 		const XMLNode * bsdf = node.get_child_by_tag("bsdf"), * medium = node.get_child_by_tag("medium");
-		if (!bsdf || plugin(*bsdf) != "null" || !medium || plugin(*medium) != "homogeneous") return false;
+		if (!bsdf || plugin(*bsdf) != "null" || !medium || (plugin(*medium) != "homogeneous" && plugin(*medium) != "heterogeneous")) return false;
+		const bool heterogeneous = plugin(*medium) == "heterogeneous";
 		if (const XMLAttribute * name = medium->get_attribute("name")) if (name->value != "interior") return false;
 		std::vector<Triangle> triangles;
 		if (!fog_shape_triangles(*this, node, triangles) || triangles.empty()) return false;   // (a shape this loader cannot read as a volume: loaded as before)
@@ -417,10 +421,32 @@ struct SceneFile {
 		if (!is_box && !warned_fog_shape_is_no_box) { complain(node, "the fog volume is the shape's axis-aligned bounding box, which this shape does not fill"); warned_fog_shape_is_no_box = true; }
 		FogVolume fog;
 		fog.box_min = lo; fog.box_max = hi;
-		homogeneous_coefficients(*medium, fog.sigma_a, fog.sigma_s, fog.g);
+		FogDensity grid;
+		if (heterogeneous) {
+			const XMLNode * density = medium->get_child_by_name("density"), * albedo = medium->get_child_by_name("albedo"), * scale = medium->get_child_by_name("scale");
+			if (!density || plugin(*density) != "gridvolume") throw ParseError(medium->location + ": the heterogeneous medium of a fog volume needs a <volume name=\"density\" type=\"gridvolume\">");
+			if (!albedo || plugin(*albedo) != "constvolume" || !albedo->get_child_by_name("value")) throw ParseError(medium->location + ": the heterogeneous medium of a fog volume needs a constant albedo (<volume name=\"albedo\" type=\"constvolume\"> with a value)");
+			if (!scale) throw ParseError(medium->location + ": the heterogeneous medium of a fog volume needs a <float name=\"scale\">");
+			const Vector3 a = albedo->get_child_by_name("value")->require_attribute("value").as_vector3();
+			const float factor = property(*medium, "scale", 1.0f);
+			fog.sigma_s = factor * a; fog.sigma_a = factor * (Vector3(1.0f) - a);
+			if (const XMLNode * phase = medium->get_child_by_tag("phase")) {
+				std::string_view kind = plugin(*phase);
+				if      (kind == "isotropic") fog.g = 0.0f;
+				else if (kind == "hg")        fog.g = property(*phase, "g", 0.0f);
+				else complain(*medium, "phase function type '" + std::string(kind) + "' not supported");
+			}
+			float box[6];
+			grid = FogDensity::read_vol(PathName::below(folder, filename_property(*density)), box);
+			const float shape_box[6] = { lo.x, lo.y, lo.z, hi.x, hi.y, hi.z };
+			bool same = true;
+			for (int k = 0; k < 6; k++) same = same && fabsf(box[k] - shape_box[k]) <= 1e-5f * fmaxf(1.0f, fabsf(shape_box[k]));
+			if (!same) complain(*density, "the bounding box of the gridvolume file is ignored: the grid lies over the shape's bounding box");
+		} else homogeneous_coefficients(*medium, fog.sigma_a, fog.sigma_s, fog.g);
 		std::string why = fog.complaint();
 		if (!why.empty()) throw ParseError(node.location + ": fog volume: " + why);
 		scene.fog = fog; scene.has_fog = true;
+		if (heterogeneous) { scene.fog_density = std::move(grid); scene.has_fog_density = true; }
 		return true;
 	}
 

@@ -314,6 +314,15 @@ void Pathtracer::update(float delta) {
 			fog_on_device = scene.has_fog; fog_record_on_device = v;
 			sample_index = 0;
 		}
+		// the density grid: state of its own on the device; uploaded when its values or dims have changed
+		const FogDensity & grid = scene.fog_density;
+		if (ctx && (scene.has_fog_density != fog_density_on_device || (scene.has_fog_density && (grid.values != fog_density_values_on_device || grid.nx != fog_density_dims_on_device[0] || grid.ny != fog_density_dims_on_device[1] || grid.nz != fog_density_dims_on_device[2])))) {
+			check(rt_set_fog_density(ctx, scene.has_fog_density ? grid.values.data() : nullptr, grid.nx, grid.ny, grid.nz));
+			fog_density_on_device = scene.has_fog_density;
+			fog_density_values_on_device = scene.has_fog_density ? grid.values : std::vector<float>();
+			fog_density_dims_on_device[0] = grid.nx; fog_density_dims_on_device[1] = grid.ny; fog_density_dims_on_device[2] = grid.nz;
+			sample_index = 0;
+		}
 		invalidated_fog = false;
 	}
 	if (invalidated_light_mesh_weights || invalidated_delta_lights) {   // (after the emitters: the share weighs against their total; after the TLAS: the scene's bounds)

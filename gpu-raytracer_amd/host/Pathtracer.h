@@ -36,6 +36,7 @@ struct Pathtracer final : Integrator {
 	// Fog volume: scene.fog reaches the device at update() when it has changed (the call drains what is in flight)
 	bool               invalidated_fog = true;
 	bool               fog_on_device = false; rt_fog_volume fog_record_on_device = { };
+	bool               fog_density_on_device = false; std::vector<float> fog_density_values_on_device; int fog_density_dims_on_device[3] = { 0, 0, 0 };   // 
 	bool               invalidated_delta_lights = true;   // scene.delta_lights or cpu_config.delta_light_share changed
 	bool               delta_lights_uploaded = false, warned_delta_lights_without_nee = false;
 	std::vector<rt_delta_light> delta_lights_on_device; float delta_light_share_on_device = 0.0f;   // what the device holds (an unchanged table is not uploaded again: the upload drains)

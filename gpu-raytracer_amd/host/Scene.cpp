@@ -379,6 +379,57 @@ Scene::Scene() : camera(Math::deg_to_rad(85.0f)) {
 		if (has_fog) fprintf(stderr, "WARNING: the config key fog (--fog) replaces the fog volume of the scene file\n");
 		has_fog = true;
 	}
+	if (!cpu_config.fog_density.empty()) {
+		float box[6];
+		FogDensity grid = FogDensity::read_vol(cpu_config.fog_density, box);   // (the file's own box is not used: the grid lies over the volume's)
+		if (has_fog_density) fprintf(stderr, "WARNING: the config key fog_density (--fog-density) replaces the density grid of the scene file\n");
+		fog_density = std::move(grid); has_fog_density = true;
+	}
+}
+
+std::string FogDensity::complaint() const {
+	const int dims[3] = { nx, ny, nz };
+	for (int k = 0; k < 3; k++) if (dims[k] < 1 || dims[k] > 1024) return std::string("n") + "xyz"[k] + " = " + std::to_string(dims[k]) + " outside 1 .. 1024";
+	const size_t cells = size_t(nx) * size_t(ny) * size_t(nz);
+	if (cells > size_t(1) << 27) return "more than 2^27 cells";
+	if (values.size() != cells) return "the values do not match the dims";
+	for (size_t i = 0; i < cells; i++) if (!(std::isfinite(values[i]) && values[i] >= 0.0f))
+		return "cell (" + std::to_string(i % size_t(nx)) + ", " + std::to_string(i / size_t(nx) % size_t(ny)) + ", " + std::to_string(i / (size_t(nx) * size_t(ny))) + ") must be finite and not negative";
+	return "";
+}
+
+FogDensity FogDensity::read_vol(const std::string & filename, float box[6]) {
+	FILE * file = fopen(filename.c_str(), "rb");
+	if (!file) throw ParseError("'" + filename + "': cannot open the density grid");
+	struct Closer { FILE * f; ~Closer() { fclose(f); } } closer = { file };
+	unsigned char magic[4]; int32_t header[5];
+	if (fread(magic, 1, 4, file) != 4 || fread(header, 4, 5, file) != 5 || fread(box, 4, 6, file) != 6) throw ParseError("'" + filename + "': shorter than a gridvolume header (48 bytes)");
+	if (magic[0] != 'V' || magic[1] != 'O' || magic[2] != 'L') throw ParseError("'" + filename + "': not a gridvolume file (no \"VOL\" at its start)");
+	if (magic[3] != 3) throw ParseError("'" + filename + "': gridvolume version " + std::to_string(int(magic[3])) + ", only 3 is read");
+	if (header[0] != 1) throw ParseError("'" + filename + "': gridvolume encoding " + std::to_string(header[0]) + ", only 1 (float32) is read");
+	if (header[4] != 1) throw ParseError("'" + filename + "': " + std::to_string(header[4]) + " channels, a density grid has 1");
+	FogDensity grid;
+	grid.nx = header[1]; grid.ny = header[2]; grid.nz = header[3];
+	for (int k = 1; k <= 3; k++) if (header[k] < 1 || header[k] > 1024) throw ParseError("'" + filename + "': dims " + std::to_string(header[1]) + " x " + std::to_string(header[2]) + " x " + std::to_string(header[3]) + " outside 1 .. 1024");
+	const size_t cells = size_t(grid.nx) * size_t(grid.ny) * size_t(grid.nz);
+	if (cells > size_t(1) << 27) throw ParseError("'" + filename + "': more than 2^27 cells");
+	grid.values.resize(cells);
+	if (fread(grid.values.data(), 4, cells, file) != cells) throw ParseError("'" + filename + "': shorter than its " + std::to_string(cells) + " cells");
+	std::string why = grid.complaint();
+	if (!why.empty()) throw ParseError("'" + filename + "': " + why);
+	return grid;
+}
+
+void FogDensity::write_vol(const std::string & filename, const float box[6]) const {
+	std::string why = complaint();
+	if (!why.empty()) throw ParseError("'" + filename + "': " + why);
+	FILE * file = fopen(filename.c_str(), "wb");
+	if (!file) throw ParseError("'" + filename + "': cannot write the density grid");
+	const unsigned char magic[4] = { 'V', 'O', 'L', 3 };
+	const int32_t header[5] = { 1, nx, ny, nz, 1 };
+	bool ok = fwrite(magic, 1, 4, file) == 4 && fwrite(header, 4, 5, file) == 5 && fwrite(box, 4, 6, file) == 6 && fwrite(values.data(), 4, values.size(), file) == values.size();
+	ok = fclose(file) == 0 && ok;
+	if (!ok) throw ParseError("'" + filename + "': writing the density grid failed");
 }
 
 std::string FogVolume::complaint() const {

@@ -86,10 +86,24 @@ struct FogVolume {
 	std::string complaint() const;
 };
 
+// The density grid of the fog volume: nx * ny * nz values >= 0, x fastest, laid over the volume's box. Not part of a scene's description either.
+// read_vol / write_vol: Mitsuba 0.6's gridvolume file -- "VOL", version 3, encoding 1 (float32), the dims, 1 channel, the bounding box {min[3], max[3]},
+// the data x fastest. A refusal (ParseError) carries the file name.
+struct FogDensity {
+	std::vector<float> values;
+	int nx = 0, ny = 0, nz = 0;
+	// what rt_set_fog_density will ask too, with its reason (empty: fine)
+	std::string complaint() const;
+	static FogDensity read_vol(const std::string & filename, float box[6]);
+	void write_vol(const std::string & filename, const float box[6]) const;
+};
+
 struct Scene {
 	AssetManager asset_manager;
 	bool      has_fog = false;   // (after a change of either: Pathtracer::invalidated_fog)
 	FogVolume fog;
+	bool       has_fog_density = false;   // (state of its own beside the volume; after a change: Pathtracer::invalidated_fog too)
+	FogDensity fog_density;
 	std::vector<DeltaLight> delta_lights;   // (after a change: Pathtracer::invalidated_delta_lights)
 
 	Camera            camera;

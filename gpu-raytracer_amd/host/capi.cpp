@@ -139,9 +139,15 @@ int grt_config_set(const char * key, double value) {
 	return 0;
 }
 
-// The keys whose values are lists of numbers: fog ("off", or the box "minx,miny,minz,maxx,maxy,maxz"), fog_sigma_a and fog_sigma_s (one number or three).
+// The keys whose values are lists of numbers: fog ("off", or the box "minx,miny,minz,maxx,maxy,maxz"), fog_sigma_a and fog_sigma_s (one number or three);
+// and fog_density: "off" or the path of a gridvolume file (read when a scene is loaded).
 int grt_config_set_string(const char * key, const char * value) {
 	std::string k(key), text(value ? value : "");
+	if (k == "fog_density") {
+		if (text.empty()) { g_host_error = "fog_density must be \"off\" or the path of a gridvolume file"; return -1; }
+		cpu_config.fog_density = text == "off" ? std::string() : text;
+		return 0;
+	}
 	if (k != "fog" && k != "fog_sigma_a" && k != "fog_sigma_s") { g_host_error = "config key '" + k + "' does not take a string"; return -1; }
 	if (k == "fog" && (text == "off" || text == "0")) { cpu_config.fog = false; return 0; }
 	float numbers[6]; int count = 0;
@@ -184,6 +190,7 @@ double grt_config_get(const char * key) {
 	if (k == "fog")            return cpu_config.fog ? 1.0 : 0.0;
 	if (k == "fog_g")          return cpu_config.fog_g;
 	if (k == "fog_volumes")    return cpu_config.fog_volumes;
+	if (k == "fog_density")    return cpu_config.fog_density.empty() ? 0.0 : 1.0;
 	if (k == "delta_light_share") return cpu_config.delta_light_share;
 	if (k == "noise_target")      return cpu_config.noise_target;
 	if (k == "noise_min_samples") return cpu_config.noise_min_samples;
@@ -345,6 +352,47 @@ int grt_scene_get_fog(void * scene, float * out13) {
 	const float values[13] = { f.box_min.x, f.box_min.y, f.box_min.z, f.box_max.x, f.box_max.y, f.box_max.z, f.sigma_a.x, f.sigma_a.y, f.sigma_a.z, f.sigma_s.x, f.sigma_s.y, f.sigma_s.z, f.g };
 	memcpy(out13, values, sizeof(values));
 	return 1;
+}
+// The density grid of the fog volume, nx * ny * nz floats, x fastest; a change takes effect at the next update after invalidate("fog").
+int grt_scene_set_fog_density(void * scene, const float * values, int nx, int ny, int nz) {
+	GRT_TRY
+		Scene * s = (Scene *)scene;
+		FogDensity grid;
+		grid.nx = nx; grid.ny = ny; grid.nz = nz;
+		if (nx >= 1 && ny >= 1 && nz >= 1 && nx <= 1024 && ny <= 1024 && nz <= 1024) grid.values.assign(values, values + size_t(nx) * size_t(ny) * size_t(nz));
+		std::string why = grid.complaint();
+		if (!why.empty()) { g_host_error = "grt_scene_set_fog_density: " + why; return -1; }
+		s->fog_density = std::move(grid); s->has_fog_density = true;
+		return 0;
+	GRT_CATCH(-1)
+}
+void grt_scene_clear_fog_density(void * scene) { Scene * s = (Scene *)scene; s->has_fog_density = false; s->fog_density = FogDensity(); }
+// 0 without a grid; else 1, the dims, and (capacity >= nx * ny * nz) the values
+int grt_scene_get_fog_density(void * scene, int * dims3, float * out, size_t capacity) {
+	const Scene * s = (const Scene *)scene;
+	if (!s->has_fog_density) return 0;
+	const FogDensity & g = s->fog_density;
+	dims3[0] = g.nx; dims3[1] = g.ny; dims3[2] = g.nz;
+	if (out && capacity >= g.values.size()) memcpy(out, g.values.data(), g.values.size() * sizeof(float));
+	return 1;
+}
+// A gridvolume file (FogDensity::read_vol / write_vol). read: the dims and the box, and (capacity >= the cells) the values; -1 with the file's name in the message.
+int grt_vol_read(const char * filename, int * dims3, float * box6, float * out, size_t capacity) {
+	GRT_TRY
+		FogDensity g = FogDensity::read_vol(filename, box6);
+		dims3[0] = g.nx; dims3[1] = g.ny; dims3[2] = g.nz;
+		if (out && capacity >= g.values.size()) memcpy(out, g.values.data(), g.values.size() * sizeof(float));
+		return 0;
+	GRT_CATCH(-1)
+}
+int grt_vol_write(const char * filename, const float * values, int nx, int ny, int nz, const float * box6) {
+	GRT_TRY
+		FogDensity g;
+		g.nx = nx; g.ny = ny; g.nz = nz;
+		if (nx >= 1 && ny >= 1 && nz >= 1 && nx <= 1024 && ny <= 1024 && nz <= 1024) g.values.assign(values, values + size_t(nx) * size_t(ny) * size_t(nz));
+		g.write_vol(filename, box6);
+		return 0;
+	GRT_CATCH(-1)
 }
 // Adds a texture file to the scene; data != 0: a data texture (normal map, see Texture::data). Textures reach the device when a
 // Pathtracer is created, so add them before. Returns the texture index, -1 on failure.

@@ -2,7 +2,8 @@
 #pragma once
 
 extern "C" {
-// fog ("off", or the box "minx,miny,minz,maxx,maxy,maxz"), fog_sigma_a and fog_sigma_s (one number or three); -1 with a message for anything else
+// fog ("off", or the box "minx,miny,minz,maxx,maxy,maxz"), fog_sigma_a and fog_sigma_s (one number or three), fog_density ("off" or a gridvolume
+// file's path); -1 with a message for anything else
 int grt_config_set_string(const char * key, const char * value);
 const char * grt_last_error();
 }

@@ -116,6 +116,9 @@ std::vector<Option> make_options(CommandLine & cl) {
 		if (!(g > -1.0f && g < 1.0f)) die("--fog-g must lie in (-1, 1)");
 		cpu_config.fog_g = g;
 	} });
+	o.push_back({ nullptr, "fog-density", "A density grid laid over the fog volume's box: a Mitsuba gridvolume file <file.vol> (float32, one channel) whose values scale the fog's sigmas voxel by voxel (or off)", 1, [](const char * v) {
+		if (grt_config_set_string("fog_density", v) != 0) die(std::string("--fog-density: ") + grt_last_error());
+	} });
 	o.push_back({ nullptr, "fog-volumes", "1: a scene file's shape with a null BSDF and an interior homogeneous medium becomes the fog volume over its bounding box; 0 (default): loaded as before", 1, [](const char * v) {
 		cpu_config.fog_volumes = parse_bool(v) ? 1 : 0;
 	} });

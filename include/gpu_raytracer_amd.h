@@ -164,6 +164,7 @@ const char * rt_version(void);
  *      -- new entry points and a result struct of their own; adaptive sampling, off by default)
  *      (still 17: rt_set_fog_volume, rt_get_fog_volume, rt_fog_segments, rt_attenuate_shadow_rays, rt_sort_rays_fog -- new entry points and a
  *      struct of their own; the fog volume, off until one is set)
+ *      (still 17: rt_set_fog_density, rt_get_fog_density_info, rt_fog_density_segments -- new entry points; the volume's density grid)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
 #define RT_ABI_VERSION 17
 int rt_abi_version(void);
@@ -888,6 +889,25 @@ int rt_sort_rays_fog(rt_context * ctx, int merged, int step, int sample_index, c
                      uint32_t * trace_out, uint32_t * material_out, int32_t * counters6,
                      float * aov_frames, float * gbuffer_normal_and_depth, int32_t * gbuffer_mesh_id_and_triangle_id, float * gbuffer_screen_position_prev,
                      int32_t * pixel_query2, int32_t * stats, uint32_t * shadow_out, int32_t * shadow_count);
+/* ---- density grid of the fog volume -----------------------------------------------------------------------------------
+ * rho[z][y][x], nx x ny x nz float32 values laid over the box of the fog volume in force (x fastest; voxel (i, j, k) spans [min + i * cell,
+ * min + (i + 1) * cell) per axis, cell = (max - min) / n; no interpolation): inside a voxel the coefficients are rho * sigma_a and rho *
+ * sigma_s, g is unchanged. Paths scatter by the homogeneous scheme over DENSITY LENGTH (the integral of rho along the ray, by a voxel march
+ * that crosses bricks of 8 x 8 x 8 voxels without density in one step); shadow rays are multiplied by exp(-sigma_t * density length).
+ * (Additions that change no struct and no call: RT_ABI_VERSION stays.)
+ * rt_set_fog_density: `density` is a host pointer; NULL clears the grid. Checked on the host before anything is staged -- dims in 1 .. 1024,
+ * nx * ny * nz <= 2^27, every value finite and >= 0 -- and a refused call (RT_ERROR_INVALID_ARG, the message names the first bad cell)
+ * leaves the grid before it in force. A change completes what the context has in flight first. The grid is state of its own: it survives
+ * rt_set_fog_volume calls and maps onto whatever box is in force; without a volume it is stored and inert. A grid of zeros renders as no
+ * volume (exactly the kernels of a context without one). rt_fog_segments stays the homogeneous step and ignores the grid;
+ * rt_attenuate_shadow_rays and rt_sort_rays_fog launch what the context would launch: the ..._grid instances while a grid is in force.
+ * rt_get_fog_density_info: the dims of the grid in force, its bricks (ceil(n / 8) per axis), how many hold no density, the largest value.
+ * rt_fog_density_segments: rt_fog_segments' records through the grid's segment step, with pad words filled: word 12 the density length (over
+ * the whole clipped interval when the path did not scatter, over [t0, vertex] when it did), word 13 the voxels read, word 14 the empty
+ * bricks crossed. RT_ERROR_NOT_READY without a volume or without a grid.                                                             */
+int rt_set_fog_density(rt_context * ctx, const float * density, int nx, int ny, int nz);
+int rt_get_fog_density_info(rt_context * ctx, int dims[3], int * bricks, int * empty_bricks, float * max_density, int * out_set);
+int rt_fog_density_segments(rt_context * ctx, const uint32_t * probes, size_t count, uint32_t * out);
 /* Streaming-read bandwidth probe used as the measured HBM roofline (GB/s).                 */
 int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps);
 
