@@ -1804,6 +1804,21 @@ def read_luts(ctx):
     return arrays
 
 
+def read_sky_tables(ctx):
+    """rt_read_sky_tables: the sky importance sampling's tables as the device built them (built now if need be). Returns a dict:
+    width, height, marginal (H,) float32, conditional (H, W) float32, cell_pdf (H, W) float32, row_totals (H,) float64, total (float)."""
+    lib = device_lib()
+    lib.rt_read_sky_tables.argtypes = [c_void_p, POINTER(c_int), POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_double), c_size_t]
+    w, h, total = c_int(), c_int(), c_double()
+    _dev_check(ctx, lib.rt_read_sky_tables(ctx, byref(w), byref(h), None, None, None, None, None, 0))
+    W, H = w.value, h.value
+    marginal = np.zeros(H, np.float32); conditional = np.zeros((H, W), np.float32); cell_pdf = np.zeros((H, W), np.float32)
+    row_totals = np.zeros(H, np.float64)
+    _dev_check(ctx, lib.rt_read_sky_tables(ctx, byref(w), byref(h), marginal.ctypes.data, conditional.ctypes.data, cell_pdf.ctypes.data,
+                                           row_totals.ctypes.data, byref(total), W * H))
+    return dict(width=W, height=H, marginal=marginal, conditional=conditional, cell_pdf=cell_pdf, row_totals=row_totals, total=total.value)
+
+
 def set_trace_statistics(ctx, enable):
     lib = device_lib()
     lib.rt_set_trace_statistics.argtypes = [c_void_p, c_int]

@@ -26,6 +26,10 @@ RT_DEV double block_inclusive_scan(double v, double * lds) {
 	}
 	return v;
 }
+// What lies in front of this thread's span, after block_inclusive_scan: the scan's entry of the thread before. Not `inclusive - sum`: where the span's
+// own sum is 2^53 times what lies in front of it (a sun beside a dim texel, both in one span), that difference has no correct digit left and the row's
+// CDF steps back at the span's first entry.
+RT_DEV double sky_exclusive_prefix(const double * lds) { return threadIdx.x > 0 ? lds[threadIdx.x - 1] : 0.0; }
 
 // Largest luminance over the clamped 3 x 3 neighbourhood of texel (x, y); a NaN anywhere in it makes the result NaN.
 RT_DEV float sky_footprint_luminance(const float4 * __restrict__ sky, int width, int height, int x, int y) {
@@ -61,9 +65,9 @@ __global__ void __launch_bounds__(RT_SKY_BLOCK) kernel_sky_rows(const float4 * _
 		lum[x] = m;
 		sum += double(m) * omega;
 	}
-	double inclusive = block_inclusive_scan(sum, lds);
+	block_inclusive_scan(sum, lds);
 	const double total = lds[RT_SKY_BLOCK - 1];
-	double prefix = inclusive - sum;
+	double prefix = sky_exclusive_prefix(lds);
 	for (int x = first; x < last; x++) {
 		prefix += double(lum[x]) * omega;
 		cdf[x] = !(total > 0.0) ? float(x + 1) / float(width) : x == width - 1 ? 1.0f : float(prefix / total);   // (a row without weight is never picked)
@@ -77,9 +81,9 @@ __global__ void __launch_bounds__(RT_SKY_BLOCK) kernel_sky_marginal(const double
 	const int first = min(int(threadIdx.x) * per_thread, height), last = min(first + per_thread, height);
 	double sum = 0.0;
 	for (int y = first; y < last; y++) sum += row_total[y];
-	double inclusive = block_inclusive_scan(sum, lds);
+	block_inclusive_scan(sum, lds);
 	const double total = lds[RT_SKY_BLOCK - 1];
-	double prefix = inclusive - sum;
+	double prefix = sky_exclusive_prefix(lds);
 	for (int y = first; y < last; y++) {
 		prefix += row_total[y];
 		marginal_cdf[y] = !(total > 0.0) ? float(y + 1) / float(height) : y == height - 1 ? 1.0f : float(prefix / total);

@@ -875,6 +875,29 @@ int rt_get_sky_sampling(const rt_context * ctx, float * out_probability) {
 	return RT_OK;
 }
 
+// The sky's sampling tables as the device built them (built here if no render or probe has wanted them yet: the state a render with sampling on leaves).
+int rt_read_sky_tables(rt_context * ctx, int * out_width, int * out_height, float * marginal_cdf, float * conditional_cdf, float * cell_pdf,
+                       double * row_totals, double * out_total, size_t capacity) {
+	RT_REQUIRE(ctx, ctx, "rt_read_sky_tables: NULL context");
+	RT_REQUIRE(ctx, ctx->params.sky, "rt_read_sky_tables: no sky uploaded (rt_set_sky)");
+	const size_t w = size_t(ctx->params.sky_width), h = size_t(ctx->params.sky_height);
+	if (out_width) *out_width = int(w);
+	if (out_height) *out_height = int(h);
+	if ((marginal_cdf || conditional_cdf || cell_pdf || row_totals) && capacity < w * h)
+		return fail(ctx, RT_ERROR_INVALID_ARG, "rt_read_sky_tables: room for %zu cells, the %zux%zu sky has %zu", capacity, w, h, w * h);
+	(void)hipSetDevice(ctx->device);
+	int s = sky_tables_build(ctx, "rt_read_sky_tables"); if (s) return s;
+	const float * tables = (const float *)ctx->sky_tables;
+	const double * sums = (const double *)ctx->sky_table_sums;
+	if (marginal_cdf)    RT_HIP(ctx, hipMemcpyAsync(marginal_cdf, tables, h * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+	if (conditional_cdf) RT_HIP(ctx, hipMemcpyAsync(conditional_cdf, tables + h, w * h * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+	if (cell_pdf)        RT_HIP(ctx, hipMemcpyAsync(cell_pdf, tables + h + w * h, w * h * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+	if (row_totals)      RT_HIP(ctx, hipMemcpyAsync(row_totals, sums, h * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (out_total)       RT_HIP(ctx, hipMemcpyAsync(out_total, sums + h, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return RT_OK;
+}
+
 } // extern "C"
 
 // The sky's sampling tables (kernels_sky.hip), built once per rt_set_sky; synchronous (it reads the total back).

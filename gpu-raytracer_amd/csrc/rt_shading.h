@@ -454,23 +454,48 @@ RT_DEV f3 sky_sample_direction(const RtParams & p, float u1, float u2, float & p
 	float fy, fx;
 	int row    = sky_cdf_invert(p.sky_marginal_cdf, height, u2, fy);
 	int column = sky_cdf_invert(p.sky_conditional_cdf + size_t(row) * width, width, u1, fx);
-	float phi = ((float(column) + fx) / float(width) - 0.5f) * RT_TWO_PI;
-	// cos(theta) uniform between the row's edges, interpolated as 1 - cos (upper half) or 1 + cos (lower half): no cancellation near a pole
-	float half_0 = 0.5f * RT_PI * float(row) / float(height), half_1 = 0.5f * RT_PI * float(row + 1) / float(height);
-	float cos_theta, sin_theta;
-	if (2 * row + 1 <= height) {
-		float s0 = sinf(half_0), s1 = sinf(half_1);
-		float a0 = 2.0f * s0 * s0, a1 = 2.0f * s1 * s1;
-		float a = a0 + fy * (a1 - a0);
-		cos_theta = 1.0f - a; sin_theta = sqrtf(fmaxf(a * (2.0f - a), 0.0f));
-	} else {
-		float c0 = cosf(half_0), c1 = cosf(half_1);
-		float b0 = 2.0f * c0 * c0, b1 = 2.0f * c1 * c1;
-		float b = b0 + fy * (b1 - b0);
-		cos_theta = b - 1.0f; sin_theta = sqrtf(fmaxf(b * (2.0f - b), 0.0f));
+	const int picked = column + row * width;
+	// The direction has to lie in the picked cell AS sky_cell FINDS IT, so that the pdf returned here is the one a BSDF ray in that direction looks up.
+	// A point on the cell's border (u equal to a CDF entry, u = 0 behind weightless cells) goes through atan2f / acosf into the neighbour about every
+	// other time -- whose pdf is another and may be 0. Such a point, and no other, is pulled inside: first by more than the round trip moves it in phi
+	// and, where the row was off, in theta (W 2^-21 and H 2^-21 of the cell, 3e-6 and 1.5e-6 rad; at a pole itself, where no column has a direction, sin theta
+	// becomes 1.3e-6), then, in the rows next to a pole, where acosf resolves y = 1 - 5e-6 to a hundredth of a row, by single float steps of y. A sky
+	// too tall for that (a polar row below one float of y, H > 5000) keeps the neighbour's lookup.
+	f3 direction;
+	float off_pole = 0.0f;
+	#pragma unroll 1
+	for (int attempt = 0; attempt < 6; attempt++) {
+		if (attempt < 2) {
+			float phi = ((float(column) + fx) / float(width) - 0.5f) * RT_TWO_PI;
+			// cos(theta) uniform between the row's edges, interpolated as 1 - cos (upper half) or 1 + cos (lower half): no cancellation near a pole
+			float half_0 = 0.5f * RT_PI * float(row) / float(height), half_1 = 0.5f * RT_PI * float(row + 1) / float(height);
+			float cos_theta, sin_theta;
+			if (2 * row + 1 <= height) {
+				float s0 = sinf(half_0), s1 = sinf(half_1);
+				float a0 = 2.0f * s0 * s0, a1 = 2.0f * s1 * s1;
+				float a = fmaxf(a0 + fy * (a1 - a0), off_pole);
+				cos_theta = 1.0f - a; sin_theta = sqrtf(fmaxf(a * (2.0f - a), 0.0f));
+			} else {
+				float c0 = cosf(half_0), c1 = cosf(half_1);
+				float b0 = 2.0f * c0 * c0, b1 = 2.0f * c1 * c1;
+				float b = fmaxf(b0 + fy * (b1 - b0), off_pole);
+				cos_theta = b - 1.0f; sin_theta = sqrtf(fmaxf(b * (2.0f - b), 0.0f));
+			}
+			direction = mk3(sin_theta * cosf(phi), cos_theta, -sin_theta * sinf(phi));
+		}
+		int cell = sky_cell(p, direction);
+		if (cell == picked) break;
+		if (attempt == 0) {
+			float ex = fminf(float(width) * 0x1p-21f, 0.5f), ey = fminf(float(height) * 0x1p-21f, 0.5f);
+			fx = fminf(fmaxf(fx, ex), 1.0f - ex); off_pole = 0x1p-40f;   // (always: the steps of y below cannot mend a column)
+			if (cell / width != row) fy = fminf(fmaxf(fy, ey), 1.0f - ey);
+		} else {
+			int found = cell / width;
+			if (found == row || direction.y == 0.0f) break;
+			direction.y = __int_as_float(__float_as_int(direction.y) + ((found < row) == (direction.y > 0.0f) ? -1 : 1));   // towards the row
+		}
 	}
-	f3 direction = mk3(sin_theta * cosf(phi), cos_theta, -sin_theta * sinf(phi));
-	pdf = sky_pdf(p, direction);   // the table's value for the cell the direction lies in, as a BSDF ray in that direction would look it up
+	pdf = p.sky_cell_pdf[picked];
 	return direction;
 }
 

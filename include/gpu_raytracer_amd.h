@@ -165,6 +165,7 @@ const char * rt_version(void);
  *      (still 17: rt_set_fog_volume, rt_get_fog_volume, rt_fog_segments, rt_attenuate_shadow_rays, rt_sort_rays_fog -- new entry points and a
  *      struct of their own; the fog volume, off until one is set)
  *      (still 17: rt_set_fog_density, rt_get_fog_density_info, rt_fog_density_segments -- new entry points; the volume's density grid)
+ *      (still 17: rt_read_sky_tables -- a new entry point; the read-back of the sky's sampling tables)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
 #define RT_ABI_VERSION 17
 int rt_abi_version(void);
@@ -659,6 +660,14 @@ int rt_read_pixel_list(rt_context * ctx, uint32_t * dst, size_t capacity, size_t
  * Any pointer may be NULL. Synchronous.                                                     */
 int rt_read_luts(rt_context * ctx, float * dielectric_directional_enter, float * dielectric_directional_leave,
                  float * dielectric_enter, float * dielectric_leave, float * conductor_directional, float * conductor);
+/* The tables of sky importance sampling as the device built them for the last rt_set_sky (kernels_sky.hip; built here if nothing has
+ * wanted them yet, which leaves the context as a render with sampling on leaves it). *out_width, *out_height: the sky's size (W, H);
+ * marginal_cdf: H floats; conditional_cdf and cell_pdf: H x W floats, x fastest; row_totals: H doubles (the rows' weights before
+ * normalisation); *out_total: their sum. Any pointer may be NULL. capacity: the room of every array given, in cells; below W x H with an
+ * array given: RT_ERROR_INVALID_ARG (the sizes are still written, so a first call with no array asks for them). RT_ERROR_INVALID_ARG
+ * also without a sky and for a sky with NaN or infinite texels. Synchronous. (An addition that changes no struct: RT_ABI_VERSION stays.) */
+int rt_read_sky_tables(rt_context * ctx, int * out_width, int * out_height, float * marginal_cdf, float * conditional_cdf, float * cell_pdf,
+                       double * row_totals, double * out_total, size_t capacity);
 
 /* ---- kernel-level entry points (parity tests and micro-benchmarks) ----------------------*/
 /* kernel_trace_bvh8 / kernel_trace_shadow_bvh8 on caller-supplied rays (SoA host arrays).

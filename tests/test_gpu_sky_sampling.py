@@ -187,8 +187,12 @@ def test_sun_lit_plane_converges_with_less_noise(grt, tmp_path):
     """The plane's every pixel is ALBEDO / pi * E (E: the float64 quadrature of the bilinear sky). With the option on -- MIS on and
     off -- and off, the image mean is that value within five standard errors; at equal samples the option's MSE is at least 10x lower.
     Measured on the MI355X (64 x 64, 16 samples): MSE off / on = 820.7; required: 100."""
+    _check_sun_lit_plane(grt, tmp_path, ref.sun_sky())
+
+
+def _check_sun_lit_plane(grt, tmp_path, sky):
+    """The body of test_sun_lit_plane_converges_with_less_noise under a given sky (test_gpu_sky_tables.py runs it under a 1027 x 515 one)."""
     xml = _plane_scene(tmp_path)
-    sky = ref.sun_sky()
     want = ALBEDO / math.pi * ref.upper_hemisphere_irradiance(sky)
     def check(img, label):
         err = img - want
