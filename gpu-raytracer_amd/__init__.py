@@ -63,6 +63,24 @@ class CellSelectionRecord(ctypes.Structure):  # rt_cell_selection
     _fields_ = [("cells_x", ctypes.c_int32), ("cells_y", ctypes.c_int32), ("hot_cells", ctypes.c_int64), ("active_cells", ctypes.c_int64), ("list_pixels", ctypes.c_int64)]
 
 
+class DenoiseParams(ctypes.Structure):  # rt_denoise_params
+    _fields_ = [("iterations", c_int), ("sigma_l", c_float), ("sigma_n", c_float), ("sigma_z", c_float), ("depth_floor", c_float), ("albedo_floor", c_float)]
+
+
+# the values DESIGN.md 7.9 settled on (CPUConfig's denoise_* fields hold the same)
+DENOISE_DEFAULTS = {"iterations": 5, "sigma_l": 4.0, "sigma_n": 128.0, "sigma_z": 1.0, "depth_floor": 1e-2, "albedo_floor": 1e-2}
+
+
+def denoise_params(**params):
+    unknown = set(params) - set(DENOISE_DEFAULTS)
+    if unknown:
+        raise TypeError("unknown denoise parameter(s): %s" % ", ".join(sorted(unknown)))
+    merged = dict(DENOISE_DEFAULTS, **params)
+    if int(merged["iterations"]) != merged["iterations"]:
+        raise ValueError("iterations must be a whole number")
+    return DenoiseParams(int(merged["iterations"]), *[float(merged[k]) for k in ("sigma_l", "sigma_n", "sigma_z", "depth_floor", "albedo_floor")])
+
+
 class DeviceLibraryMissing(RuntimeError):
     pass
 
@@ -156,6 +174,10 @@ def device_lib():
         lib.rt_read_pixel_list.argtypes = [c_void_p, c_void_p, c_size_t, POINTER(c_size_t)]
         lib.rt_select_pixels_images.argtypes = [c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, POINTER(CellSelectionRecord), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]
         lib.rt_accumulate_list_frames.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_uint32, c_void_p]
+        lib.rt_denoise.argtypes = [c_void_p, POINTER(DenoiseParams)]
+        lib.rt_read_denoised.argtypes = [c_void_p, c_void_p]
+        lib.rt_denoise_timed.argtypes = [c_void_p, POINTER(DenoiseParams), c_int, c_void_p, c_size_t, POINTER(c_size_t)]
+        lib.rt_denoise_images.argtypes = [c_void_p, c_int, c_int, c_int] + [c_void_p] * 7 + [POINTER(DenoiseParams), c_int, c_void_p]
         _device = lib
     return _device
 
@@ -264,6 +286,8 @@ def host_lib():
         lib.grt_pathtracer_read_framebuffer.argtypes = [c_void_p, c_void_p]
         lib.grt_pathtracer_save_image.argtypes = [c_void_p, c_char_p]
         lib.grt_export_image.argtypes = [c_char_p, c_int, c_int, c_int, c_void_p]
+        lib.grt_pathtracer_denoise.argtypes = [c_void_p, c_void_p, c_void_p]
+        lib.grt_pathtracer_save_denoised_image.argtypes = [c_void_p, c_char_p, c_void_p]
         lib.grt_pathtracer_array.restype = c_void_p
         lib.grt_pathtracer_array.argtypes = [c_void_p, c_char_p, POINTER(c_size_t)]
         lib.grt_pathtracer_sky_size.argtypes = [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_float)]
@@ -942,6 +966,38 @@ class Pathtracer:
         _host_check(host_lib().grt_pathtracer_counters(self.handle, byref(c)))
         return c
 
+    # ---- denoised stills
+    def set_denoise(self, enable=True):
+        """config denoise: from the next update() on (which restarts the progression when it switches them on) the device keeps the noise estimate and the
+        ALBEDO, NORMAL and POSITION AOVs that denoise() filters by."""
+        config_set(denoise=1 if enable else 0)
+
+    @staticmethod
+    def _denoise_params(params):
+        if not params:
+            return None   # the configuration's (config denoise_iterations, denoise_sigma_l / _n / _z)
+        unknown = set(params) - set(DENOISE_DEFAULTS)
+        if unknown:
+            raise TypeError("unknown denoise parameter(s): %s" % ", ".join(sorted(unknown)))
+        merged = {k: config_get("denoise_" + k) for k in ("iterations", "sigma_l", "sigma_n", "sigma_z")}
+        merged.update(depth_floor=DENOISE_DEFAULTS["depth_floor"], albedo_floor=DENOISE_DEFAULTS["albedo_floor"])
+        merged.update(params)
+        return np.array([merged[k] for k in ("iterations", "sigma_l", "sigma_n", "sigma_z", "depth_floor", "albedo_floor")], np.float64)
+
+    def denoise(self, **params):
+        """Pathtracer::denoise(): the accumulated frame through the variance-guided a-trous filter. Returns (image, variance): (height, width, 3) float32 and
+        the (height, width) plane of the filtered variance (0: sky, -1: a pixel that was not valid and carries the final image's colour). params: iterations,
+        sigma_l, sigma_n, sigma_z, depth_floor, albedo_floor; what is not given is the configuration's. Completes the work in flight."""
+        values = self._denoise_params(params)
+        image = np.zeros((self.height, self.pitch, 4), np.float32)
+        _host_check(host_lib().grt_pathtracer_denoise(self.handle, values.ctypes.data if values is not None else None, image.ctypes.data))
+        return image[:, :self.width, :3].copy(), image[:, :self.width, 3].copy()
+
+    def save_denoised_image(self, filename, **params):
+        """save_image's exporters (.ppm, .exr) on the denoised image."""
+        values = self._denoise_params(params)
+        _host_check(host_lib().grt_pathtracer_save_denoised_image(self.handle, str(filename).encode(), values.ctypes.data if values is not None else None))
+
     # ---- noise estimate (DESIGN.md 7.5)
     def set_noise_estimate(self, enable=True):
         """The device keeps Welford second moments beside the radiance mean from the next update() on (which restarts the
@@ -1190,6 +1246,50 @@ def estimate_noise(ctx, height, width, pitch, floor=1e-2, mean=None, moments=Non
         raise DeviceRefusal(ctx, status)
     return {"cells_x": out.cells_x, "cells_y": out.cells_y, "pixels": out.pixels, "nonfinite_pixels": out.nonfinite_pixels, "mean": out.mean,
             "cell_sums": sums.reshape(cells_y, cells_x), "cell_counts": counts.reshape(cells_y, cells_x), "cell_nonfinite": nonfinite.reshape(cells_y, cells_x), "pixel_map": pixel_map}
+
+
+def denoise(ctx, **params):
+    """rt_denoise on the context's frame; the image comes back through read_denoised."""
+    record = denoise_params(**params)
+    status = device_lib().rt_denoise(ctx, byref(record))
+    if status:
+        raise DeviceRefusal(ctx, status)
+
+
+def read_denoised(ctx, height, pitch):
+    """rt_read_denoised: (height, pitch, 4) float32 {r, g, b, variance}."""
+    image = np.zeros((height, pitch, 4), np.float32)
+    status = device_lib().rt_read_denoised(ctx, image.ctypes.data)
+    if status:
+        raise DeviceRefusal(ctx, status)
+    return image
+
+
+def denoise_timed(ctx, tiled=True, **params):
+    """rt_denoise_timed: rt_denoise with an event pair around every kernel; returns the kernels' times in ms (prepare first)."""
+    record = denoise_params(**params)
+    ms, count = np.zeros(8, np.float32), c_size_t(0)
+    status = device_lib().rt_denoise_timed(ctx, byref(record), 1 if tiled else 0, ms.ctypes.data, ms.size, byref(count))
+    if status:
+        raise DeviceRefusal(ctx, status)
+    return ms[:count.value].copy()
+
+
+def denoise_images(ctx, colour, moments, albedo, normal, position, fallback, eye, width=None, tiled=True, sentinel=None, **params):
+    """rt_denoise_images: the denoiser's launchers on explicit (height, pitch, 4) float32 images; width defaults to pitch. Returns (height, pitch, 4) float32
+    {r, g, b, variance}; what the kernels do not write (the padding columns) holds `sentinel` (a float32 bit pattern; default 0x7fc0dead)."""
+    images = [_f32(a) for a in (colour, moments, albedo, normal, position, fallback)]
+    height, pitch = images[0].shape[:2]
+    assert all(a.shape == (height, pitch, 4) for a in images)
+    width = pitch if width is None else width
+    record = denoise_params(**params)
+    out = np.full((height, pitch, 4), 0x7fc0dead if sentinel is None else sentinel, np.uint32).view(np.float32)
+    eye = _f32(eye)
+    assert eye.shape == (3,)
+    status = device_lib().rt_denoise_images(ctx, width, height, pitch, *[a.ctypes.data for a in images], eye.ctypes.data, byref(record), 1 if tiled else 0, out.ctypes.data)
+    if status:
+        raise DeviceRefusal(ctx, status)
+    return out
 
 
 def accumulate_frames(ctx, frames, accumulator, moments, first_sample, sample_count=None, merged=False, sentinel=0x7fc0dead):

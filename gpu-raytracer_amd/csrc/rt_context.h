@@ -1,6 +1,6 @@
 // rt_context.h -- what the units of the C ABI share: the context and the structs it is made of, error handling, and the internal functions that
 // cross a unit boundary. The units: rt_api.hip (context, frame state, results), rt_scene.hip (scene uploads and device builds), rt_render.hip (the slot
-// scheduler and the render entry points), rt_stream.hip (the merged wavefront's host side), rt_noise.hip (noise estimate, adaptive sampling),
+// scheduler and the render entry points), rt_stream.hip (the merged wavefront's host side), rt_noise.hip (noise estimate, adaptive sampling), rt_denoise.hip (denoised stills),
 // rt_exchange.hip (frame exchange of the tile split), rt_probes.hip (kernel-level entry points). Private to csrc/.
 #pragma once
 #include "rt_types.h"
@@ -222,6 +222,12 @@ struct rt_context {
 	int pixel_list_count = 0;
 	bool pixel_list_selected = false, pixel_list_on = false;
 
+	// still-image denoiser (rt_denoise): three (I, v) images -- two of them a run's ping-pong pair, the third the result of the last successful
+	// run (denoise_result, -1: none), a run's last kernel writing into the pair's free image -- and the guide image; a flag the prepare kernel raises when a pixel is valid. Allocated at
+	// the first rt_denoise, freed by rt_resize.
+	void * denoise_images[3] = { }, * denoise_guide = nullptr; int * denoise_any_valid = nullptr;
+	int denoise_result = -1;
+
 	// frame exchange of the tile split (rt_comm_*): this context's rank in a group of `world` contexts, each on its own GPU
 	// (RCCL communicator) or, for tests on one GPU, several in one process (peer copies)
 	struct FrameExchange {
@@ -303,6 +309,9 @@ int noise_estimate_images(rt_context * ctx, const char * caller, const float4 * 
 int selection_arguments(rt_context * ctx, const char * caller, float floor, float threshold, int dilate);
 int select_cells_images(rt_context * ctx, const char * caller, const float4 * mean, const float4 * moments, float floor, float threshold, int dilate, unsigned * list,
                         rt_cell_selection * out, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, uint8_t * cell_flags, size_t cell_capacity);
+// rt_denoise.hip
+void denoise_free(rt_context * ctx);
+int denoise_arguments(rt_context * ctx, const char * caller, const rt_denoise_params * params);
 #pragma GCC visibility pop
 
 #define RT_HIP(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(ctx, RT_ERROR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)

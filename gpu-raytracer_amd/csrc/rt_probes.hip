@@ -1000,6 +1000,28 @@ int rt_select_pixels_images(rt_context * ctx, const float * mean, const float * 
 	return probe.read(list, dev_list, frame * 4);
 }
 
+int rt_denoise_images(rt_context * ctx, int width, int height, int pitch, const float * colour, const float * moments, const float * albedo, const float * normal,
+                      const float * position, const float * fallback, const float * eye, const rt_denoise_params * params, int tiled, float * out) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_denoise_images: NULL context");
+	RT_REQUIRE(ctx, colour && moments && albedo && normal && position && fallback && eye && out, "rt_denoise_images: NULL argument");
+	int s = denoise_arguments(ctx, "rt_denoise_images", params); if (s) return s;
+	RT_REQUIRE(ctx, tiled == 0 || tiled == 1, "rt_denoise_images: tiled must be 0 or 1");
+	RT_REQUIRE(ctx, width > 0 && height > 0 && pitch >= width, "rt_denoise_images: width and height must be positive and pitch at least width");
+	RT_REQUIRE(ctx, (long long)pitch * height < (1ll << 26), "rt_denoise_images: pitch * height must stay below 2^26");
+	RT_REQUIRE(ctx, std::isfinite(eye[0]) && std::isfinite(eye[1]) && std::isfinite(eye[2]), "rt_denoise_images: eye is not finite");
+	(void)hipSetDevice(ctx->device);
+	RT_HIP(ctx, quiesce(ctx));
+	Probe probe(ctx, "rt_denoise_images");
+	const size_t pixels = size_t(pitch) * size_t(height);
+	RtDenoiseImages images = { probe.array<float4>(pixels, colour), probe.array<float4>(pixels, moments), probe.array<float4>(pixels, albedo), probe.array<float4>(pixels, normal),
+	                           probe.array<float4>(pixels, position), probe.array<float4>(pixels, fallback), { probe.array<float4>(pixels), probe.array<float4>(pixels) },
+	                           probe.array<float4>(pixels), probe.array<float4>(pixels, out), nullptr };
+	if ((s = probe.allocated())) return s;
+	const RtDenoiseArgs args = { width, height, pitch, params->iterations, params->sigma_l, params->sigma_n, params->sigma_z, params->depth_floor, params->albedo_floor, { eye[0], eye[1], eye[2] } };
+	rt_launch_denoise(args, images, tiled != 0, ctx->stream);
+	return probe.finish_and_read(out, images.out, pixels * 16);
+}
+
 int rt_accumulate_list_frames(rt_context * ctx, const int32_t * first_sample, const int32_t * sample_count, size_t submissions,
                               float * frames, float * accumulator, float * moments, const uint32_t * list, size_t list_count, uint32_t sentinel, float * final_image) {
 	RT_REQUIRE(ctx, ctx != nullptr, "rt_accumulate_list_frames: NULL context");

@@ -332,6 +332,14 @@ void rt_launch_select_cells(const double * cell_sums, const int * cell_counts, c
                             unsigned char * flags, int * active_pixels, int * offsets, int * totals, unsigned * list, hipStream_t stream);
 void rt_launch_generate_stream_list(const RtParams & p, int sample_index, const unsigned * list, int pixel_count, int slot_base, int queue_offset, hipStream_t stream);
 void rt_launch_accumulate_group_list(const RtParams & p, const RtAccumulateGroup & group, const unsigned * list, int pixel_count, hipStream_t stream, float4 * moments);
+// The still-image denoiser (kernels_denoise.hip): prepare, `iterations` a-trous passes (0..6) of step 1, 2, 4, ..., the last of which finalizes;
+// with 0 iterations prepare and a finalize kernel. any_valid: null, or one int the prepare kernel sets to 1 when a pixel is valid. All images are pitched float4; iv[0], iv[1] and guide are the filter's own (iv[1] is not touched below 2
+// iterations), `out` receives the result, the rest is read only. Arguments of the kernels' own: RtParams keeps its size. tiled: the passes stage their taps in LDS.
+// mark(user, k, stream), if given, is called before kernel k = 0 and after every kernel (k = 1 ...).
+struct RtDenoiseArgs { int width, height, pitch, iterations; float sigma_l, sigma_n, sigma_z, depth_floor, albedo_floor; float eye[3]; };
+struct RtDenoiseImages { const float4 * colour, * moments, * albedo, * normal, * position, * fallback; float4 * iv[2], * guide, * out; int * any_valid; };
+void rt_launch_denoise(const RtDenoiseArgs & args, const RtDenoiseImages & images, bool tiled, hipStream_t stream,
+                       void (*mark)(void * user, int kernel, hipStream_t stream) = nullptr, void * user = nullptr);
 // mark(user, k, stream), if given, is called before and after kernel k = 0 reproject, 1 variance, 2 a-trous (each pass), 3 finalize, 4 TAA, 5 TAA finalize
 void rt_launch_svgf_taa(const RtParams & p, int sample_index, hipStream_t stream, void (*mark)(void * user, int svgf_kernel, hipStream_t stream) = nullptr, void * user = nullptr);
 void rt_launch_random(const RtParams & p, int dimension, const unsigned * pixel_indices, int count, unsigned bounce, unsigned sample_index, float2 * out, hipStream_t stream);

@@ -120,6 +120,13 @@ struct CPUConfig {
 	// Pathtracer::select_adaptive, whoever calls it.
 	int   adaptive_sampling = 0;
 	int   adaptive_dilate = 1;
+	// Denoised stills. denoise 1: the first Pathtracer::update() switches on the noise estimate and the ALBEDO, NORMAL and POSITION AOVs, which
+	// Pathtracer::denoise() filters the accumulated frame by; the command-line renderer (--denoise) then writes the filtered image. The frame itself is rendered
+	// as with 0. denoise_iterations: a-trous passes of step 1, 2, 4, ... (0..6); denoise_sigma_l / _n / _z: the edge-stopping weights' luminance, normal and depth terms.
+	int   denoise = 0;
+	int   denoise_iterations = 5;
+	float denoise_sigma_l = 4.0f, denoise_sigma_n = 128.0f, denoise_sigma_z = 1.0f;
+	float denoise_depth_floor = 1e-2f, denoise_albedo_floor = 1e-2f;
 	// Alpha-tested cut-outs from the albedo textures: 1 = every surface material whose albedo FILE has an alpha channel that is not constant gets an
 	// opacity mask from it (channel a, threshold 0.5; an explicit <bsdf type="mask"> wins). Read when a scene is loaded. 0: off, as the reference renders them.
 	int   alpha_masks = 0;

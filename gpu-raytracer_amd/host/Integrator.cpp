@@ -813,7 +813,7 @@ void Integrator::update(float delta) {
 	}
 	if (ctx) check(rt_set_sky_sampling(ctx, cpu_config.sky_sampling));   // (a value; the device applies it at the next render)
 	if (ctx) {   // (drains the context, so only on a change; the moments then start over, as the mean does at sample 0)
-		const bool want = noise_estimate_wanted || cpu_config.noise_target > 0.0f;
+		const bool want = noise_estimate_wanted || cpu_config.noise_target > 0.0f || cpu_config.denoise != 0;   // (the denoiser filters by the measured variance)
 		if (want != (rt_get_noise_estimate(ctx) != 0)) { check(rt_set_noise_estimate(ctx, want ? 1 : 0)); if (want) invalidated_gpu_config = true; }   // (the progression restarts at sample 0: moments that join a running mean would miss its past)
 	}
 	if (cpu_config.enable_scene_update) {

@@ -1,4 +1,5 @@
 #include "Pathtracer.h"
+#include "Exporters.h"
 #include <algorithm>
 #include <cmath>
 #include <stdexcept>
@@ -290,6 +291,10 @@ void Pathtracer::update(float delta) {
 		if (invalidated_aovs && !aov_is_enabled(AOVType::ALBEDO)) aov_enable(AOVType::ALBEDO);
 	}
 
+	if (cpu_config.denoise && !gpu_config.enable_svgf) {   // the denoiser's guides (the estimate itself: Integrator::update)
+		for (AOVType guide : { AOVType::ALBEDO, AOVType::NORMAL, AOVType::POSITION }) if (!aov_is_enabled(guide)) aov_enable(guide);
+	}
+
 	Integrator::update(delta);
 
 	if (gpu_config.enable_svgf && ctx) {
@@ -413,6 +418,28 @@ AdaptiveSelection Pathtracer::select_adaptive(float threshold) {
 void Pathtracer::adaptive_off() {
 	require_device();
 	check(rt_set_pixel_list(ctx, 0));
+}
+
+rt_denoise_params Pathtracer::denoise_defaults() {
+	rt_denoise_params p = { cpu_config.denoise_iterations, cpu_config.denoise_sigma_l, cpu_config.denoise_sigma_n, cpu_config.denoise_sigma_z, cpu_config.denoise_depth_floor, cpu_config.denoise_albedo_floor };
+	return p;
+}
+
+std::vector<float> Pathtracer::denoise(const rt_denoise_params * params) {
+	require_device();
+	const rt_denoise_params p = params ? *params : denoise_defaults();
+	check(rt_denoise(ctx, &p));
+	std::vector<float> image(size_t(screen_pitch) * screen_height * 4);
+	check(rt_read_denoised(ctx, image.data()));
+	return image;
+}
+
+void Pathtracer::save_denoised_image(const std::string & filename, const rt_denoise_params * params) {
+	const std::vector<float> rgba = denoise(params);
+	std::vector<Vector3> rgb(rgba.size() / 4);
+	for (size_t i = 0; i < rgb.size(); i++) rgb[i] = Vector3(rgba[4 * i], rgba[4 * i + 1], rgba[4 * i + 2]);
+	std::string error;
+	if (!Exporters::save(filename, screen_pitch, screen_width, screen_height, rgb, &error)) throw std::runtime_error(error);
 }
 
 double Pathtracer::sample_counts(std::vector<float> * counts) {

@@ -72,6 +72,13 @@ struct Pathtracer final : Integrator {
 	// sample 0. A restart of the progression (sample_index 0 at render time: camera, scene, config, resize) switches the list off by itself.
 	AdaptiveSelection select_adaptive(float threshold);
 	void adaptive_off();
+	// Denoised stills: the accumulated frame through rt_denoise, pitch * height float4 (r, g, b, variance of the filtered luminance over albedo).
+	// Needs the noise estimate and the ALBEDO, NORMAL and POSITION AOVs on -- cpu_config.denoise = 1 before the update() of sample 0 does all four -- and no SVGF.
+	// params: null for the configuration's (denoise_defaults). Completes the work in flight and changes nothing a later render reads.
+	static rt_denoise_params denoise_defaults();
+	std::vector<float> denoise(const rt_denoise_params * params = nullptr);
+	// The denoised image through the exporters save_image uses (ppm, exr by the file's extension); the AOV files save_image writes beside its image are not written
+	void save_denoised_image(const std::string & filename, const rt_denoise_params * params = nullptr);
 	// w per pixel (x + y * pitch; 0 in the padding) -- the number of samples the pixel's mean stands for -- and, returned, the mean of w over the frame's pixels.
 	// w is one below the samples rendered for the pixel: sample 1 overwrites sample 0 (AOV.h:35-46). Reports of "samples per pixel" add the 1.
 	double sample_counts(std::vector<float> * counts = nullptr);

@@ -130,6 +130,18 @@ int grt_config_set(const char * key, double value) {
 		if (!(value == 0.0 || value == 1.0)) { g_host_error = "adaptive_dilate must be 0 or 1"; return -1; }
 		cpu_config.adaptive_dilate = int(value);
 	}
+	else if (k == "denoise") {
+		if (!(value == 0.0 || value == 1.0)) { g_host_error = "denoise must be 0 or 1"; return -1; }
+		cpu_config.denoise = int(value);
+	}
+	else if (k == "denoise_iterations") {
+		if (!(value >= 0.0 && value <= 6.0) || value != double(int(value))) { g_host_error = "denoise_iterations must be a whole number in [0, 6]"; return -1; }
+		cpu_config.denoise_iterations = int(value);
+	}
+	else if (k == "denoise_sigma_l" || k == "denoise_sigma_n" || k == "denoise_sigma_z") {
+		if (!(value >= 0.0 && value < 1e30)) { g_host_error = k + " must be finite and not negative"; return -1; }
+		(k == "denoise_sigma_l" ? cpu_config.denoise_sigma_l : k == "denoise_sigma_n" ? cpu_config.denoise_sigma_n : cpu_config.denoise_sigma_z) = float(value);
+	}
 	else if (k == "static_reseat_distance")              cpu_config.static_reseat_distance = float(value);
 	else if (k == "static_mesh_copy_limit_mb")           cpu_config.static_mesh_copy_limit_mb = int(value);
 	else if (k == "static_copy_budget_mb")               cpu_config.static_copy_budget_mb = int(value);
@@ -198,6 +210,11 @@ double grt_config_get(const char * key) {
 	if (k == "noise_floor")       return cpu_config.noise_floor;
 	if (k == "adaptive_sampling") return cpu_config.adaptive_sampling;
 	if (k == "adaptive_dilate")   return cpu_config.adaptive_dilate;
+	if (k == "denoise")            return cpu_config.denoise;
+	if (k == "denoise_iterations") return cpu_config.denoise_iterations;
+	if (k == "denoise_sigma_l")    return cpu_config.denoise_sigma_l;
+	if (k == "denoise_sigma_n")    return cpu_config.denoise_sigma_n;
+	if (k == "denoise_sigma_z")    return cpu_config.denoise_sigma_z;
 	return -1.0;
 }
 
@@ -598,6 +615,31 @@ int grt_pathtracer_sample_counts(void * pt, float * counts, double * mean) {
 		double m = as_pathtracer(pt)->sample_counts(&w);
 		if (counts) memcpy(counts, w.data(), w.size() * 4);
 		if (mean) *mean = m;
+		return 0;
+	GRT_CATCH(-1)
+}
+// Denoised stills. params: NULL (the configuration's), or 6 doubles: iterations, sigma_l, sigma_n, sigma_z, depth_floor, albedo_floor.
+// dst: pitch * height float4, (r, g, b, variance).
+static rt_denoise_params denoise_params_of(const double * params) {
+	rt_denoise_params p = Pathtracer::denoise_defaults();
+	if (params) { p.iterations = int(params[0]); p.sigma_l = float(params[1]); p.sigma_n = float(params[2]); p.sigma_z = float(params[3]); p.depth_floor = float(params[4]); p.albedo_floor = float(params[5]); }
+	return p;
+}
+int grt_pathtracer_denoise(void * pt, const double * params, float * dst) {
+	GRT_TRY
+		if (!pt || !dst) throw std::runtime_error("grt_pathtracer_denoise: NULL argument");
+		if (params && params[0] != double(int(params[0]))) throw std::runtime_error("grt_pathtracer_denoise: iterations must be a whole number");
+		const rt_denoise_params p = denoise_params_of(params);
+		std::vector<float> image = as_pathtracer(pt)->denoise(&p);
+		memcpy(dst, image.data(), image.size() * sizeof(float));
+		return 0;
+	GRT_CATCH(-1)
+}
+int grt_pathtracer_save_denoised_image(void * pt, const char * filename, const double * params) {
+	GRT_TRY
+		if (!pt || !filename) throw std::runtime_error("grt_pathtracer_save_denoised_image: NULL argument");
+		const rt_denoise_params p = denoise_params_of(params);
+		as_pathtracer(pt)->save_denoised_image(filename, &p);
 		return 0;
 	GRT_CATCH(-1)
 }

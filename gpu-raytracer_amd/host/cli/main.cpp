@@ -42,6 +42,8 @@ struct CommandLine {
 	bool print_config = false;
 	std::string noise_map;      // --noise-map
 	std::string sample_map;     // --sample-map
+	std::string denoise_noisy;  // --denoise-noisy
+	bool denoise_option = false;   // an option that needs --denoise was given
 };
 
 [[noreturn]] void die(const std::string & message) {
@@ -145,6 +147,13 @@ std::vector<Option> make_options(CommandLine & cl) {
 		if (d != 0 && d != 1) die("--adaptive-dilate must be 0 or 1");
 		cpu_config.adaptive_dilate = d;
 	} });
+	o.push_back({ nullptr, "denoise", "Filters the finished still by its measured variance (DESIGN.md 7.9): -o receives the denoised image. Keeps the noise estimate and the albedo, normal and position AOVs", 0, [](const char *) { cpu_config.denoise = 1; } });
+	o.push_back({ nullptr, "denoise-iterations", "With --denoise: a-trous passes of step 1, 2, 4, ... (0..6, default 5)", 1, [&cl](const char * v) {
+		int n = parse_int(v, "--denoise-iterations");
+		if (n < 0 || n > 6) die("--denoise-iterations must be between 0 and 6");
+		cpu_config.denoise_iterations = n; cl.denoise_option = true;
+	} });
+	o.push_back({ nullptr, "denoise-noisy", "With --denoise: also writes the unfiltered image to <file> (ppm, exr)", 1, [&cl](const char * v) { cl.denoise_noisy = v; cl.denoise_option = true; } });
 	o.push_back({ nullptr, "sample-map", "Writes the number of samples every pixel's mean stands for as a one-channel EXR", 1, [&cl](const char * v) { cl.sample_map = v; } });
 	o.push_back({ nullptr, "force-rebuild", "BVH will not be loaded from disk but rebuilt from scratch", 0, [](const char *) { cpu_config.bvh_force_rebuild = true; } });
 	o.push_back({ "O",  "optimize",    "Enables or disables BVH optimization post-processing step", 1, [](const char * v) { cpu_config.enable_bvh_optimization = parse_bool(v); } });
@@ -224,6 +233,8 @@ void parse_command_line(int argc, char ** argv, CommandLine & cl) {
 		exit(0);
 	}
 	if (cpu_config.adaptive_sampling && !(cpu_config.noise_target > 0.0f)) die("--adaptive needs --noise-target: the cells are selected by it");
+	if (cl.denoise_option && !cpu_config.denoise) die("--denoise-iterations / --denoise-noisy need --denoise");
+	if (!cl.denoise_noisy.empty() && cl.denoise_noisy == cpu_config.output_filename) die("--denoise-noisy names the output file: the denoised image goes there");
 	if (cl.print_config) { // one line, floats as bit patterns; the form oracle/ref/ref_scene_harness.cpp writes for the reference's Args::parse
 		auto bits = [](float f) { unsigned u; memcpy(&u, &f, 4); return u; };
 		std::string scenes;
@@ -320,6 +331,14 @@ int main(int argc, char ** argv) {
 			fprintf(stderr, "WARNING: --adaptive does not work across --devices: rendering uniformly\n");
 			cpu_config.adaptive_sampling = 0;
 		}
+		if (cpu_config.denoise && (gpu_config.enable_svgf || cpu_config.integrator == IntegratorType::AO)) {   // neither keeps second moments
+			fprintf(stderr, "WARNING: --denoise needs plain path tracing (no SVGF, no AO integrator): ignored, writing the plain image\n");
+			cpu_config.denoise = 0;
+		}
+		if (cpu_config.denoise && cl.devices.size() > 1) {   // (moments and guides are not gathered)
+			fprintf(stderr, "WARNING: --denoise does not work across --devices: writing the plain image\n");
+			cpu_config.denoise = 0;
+		}
 		if (!cl.sample_map.empty() && cl.devices.size() > 1) { fprintf(stderr, "WARNING: --sample-map does not work across --devices: ignored\n"); cl.sample_map.clear(); }
 		noise.active = cpu_config.noise_target > 0.0f;
 		noise.adaptive = noise.active && cpu_config.adaptive_sampling != 0;
@@ -380,7 +399,19 @@ int main(int argc, char ** argv) {
 		if (pathtracer) noise.report(*pathtracer, integrator->sample_index, cl.noise_map, integrator->screen_pitch, integrator->screen_width, integrator->screen_height);
 		if (pathtracer) noise.report_samples(*pathtracer, cl.sample_map, integrator->screen_pitch, integrator->screen_width, integrator->screen_height);
 
-		integrator->save_image(cpu_config.output_filename);
+		if (pathtracer && cpu_config.denoise) {
+			if (!cl.denoise_noisy.empty()) {
+				std::vector<float> rgba = integrator->read_framebuffer();
+				std::vector<Vector3> rgb(rgba.size() / 4);
+				for (size_t i = 0; i < rgb.size(); i++) rgb[i] = Vector3(rgba[4 * i], rgba[4 * i + 1], rgba[4 * i + 2]);
+				std::string error;
+				if (!Exporters::save(cl.denoise_noisy, integrator->screen_pitch, integrator->screen_width, integrator->screen_height, rgb, &error)) die(error);
+				printf("Wrote %s\n", cl.denoise_noisy.c_str());
+			}
+			auto t2 = std::chrono::steady_clock::now();
+			pathtracer->save_denoised_image(cpu_config.output_filename);
+			printf("Denoised: %d iterations, filter and export %.1f ms\n", cpu_config.denoise_iterations, seconds_since(t2) * 1e3);
+		} else integrator->save_image(cpu_config.output_filename);
 		printf("Wrote %s\n", cpu_config.output_filename.c_str());
 	} catch (const std::exception & e) {
 		die(std::string("ERROR: ") + e.what());

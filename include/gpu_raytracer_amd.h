@@ -166,6 +166,8 @@ const char * rt_version(void);
  *      struct of their own; the fog volume, off until one is set)
  *      (still 17: rt_set_fog_density, rt_get_fog_density_info, rt_fog_density_segments -- new entry points; the volume's density grid)
  *      (still 17: rt_read_sky_tables -- a new entry point; the read-back of the sky's sampling tables)
+ *      (still 17: rt_denoise, rt_read_denoised, rt_denoise_timed, rt_denoise_images -- new entry points and a parameter struct of their own; the
+ *      still-image denoiser, which runs only when called)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
 #define RT_ABI_VERSION 17
 int rt_abi_version(void);
@@ -655,6 +657,37 @@ int rt_get_pixel_list(const rt_context * ctx);
  * without a selection.                                                                                                                */
 int rt_read_pixel_list(rt_context * ctx, uint32_t * dst, size_t capacity, size_t * out_count);
 
+/* ---- denoised stills -----------------------------------------------------*/
+/* A variance-guided a-trous filter on the accumulated frame, for stills: the RADIANCE mean, its measured variance (the moments of the noise
+ * estimate) and the accumulated ALBEDO, NORMAL and POSITION means as guides. Per pixel, all in float32 and in the shapes DESIGN.md 7.9 gives:
+ *   valid    w >= 2 and r, g, b / x, y, z of the mean, the moments, albedo, normal and position (and w) finite
+ *   surface  valid and |N|^2 >= 0.25                         a = max(A, albedo_floor)          I = C / a
+ *   v = luminance(sqrt(var_r), sqrt(var_g), sqrt(var_b))^2,  var_c = M2_c / (w (w - 1)) / a_c^2   (the variance of the mean's luminance for fully correlated channels)
+ *   guide (n, z) = (N / |N|, |P - camera position|); the depth gradient g per axis: forward difference of z to a surface neighbour inside the image, else backward, else 0
+ * Pass k = 0 .. iterations - 1, step s = 2^k, for every surface pixel p over its surface taps q = p + s (i, j) inside the image, centre weight 1:
+ *   w_q = 2^-(|i|+|j|) * exp2(sigma_n * log2(max(0, n_p . n_q)) - (|l_p - l_q| * denom + |z_p - z_q| / (sigma_z * max(|g . (s i, s j)|, depth_floor * z_p) + 1e-8)) * log2(e))
+ *   denom = 1 / sqrt(sigma_l^2 * max(0, blur3x3(v)) + 1e-8),   I' = sum(w I) / sum(w),   v' = sum(w^2 v) / sum(w)^2
+ * The result, pitch*height float4: (I * a, v) for surface pixels, (C, 0) for valid pixels that are no surface (sky), and for invalid pixels the final
+ * image's pixel with .w = -1; invalid pixels are never tapped. The padding columns are not written.
+ * rt_denoise completes the work in flight and filters the context's frame (camera position: the last rt_set_camera's) into an image of the context's; its
+ * working images (48 B per pixel, and the 16 B of the result) are allocated at the first call and freed by rt_resize. It writes no accumulator, no moments and
+ * not the final image: rendering goes on afterwards as if it had not been called. RT_ERROR_NOT_READY, each with its own message, while the noise estimate is
+ * off, while ALBEDO, NORMAL or POSITION is not enabled, while SVGF is on, and when no pixel is valid; RT_ERROR_INVALID_ARG for a NULL pointer, iterations
+ * outside 0..6, sigmas that are negative or not finite, floors that are not finite and positive. A refused call leaves the previous result in place.
+ * rt_read_denoised: the result of the last successful rt_denoise; RT_ERROR_NOT_READY without one (rt_resize drops it).
+ * (Additions that change no struct and no call: RT_ABI_VERSION stays.)                                                                              */
+typedef struct rt_denoise_params {
+	int32_t iterations;          /* 0..6; the host's default: 5 */
+	float   sigma_l, sigma_n, sigma_z;   /* the host's defaults: 4, 128, 1 */
+	float   depth_floor;         /* the host's default: 1e-2 */
+	float   albedo_floor;        /* the host's default: 1e-2 */
+} rt_denoise_params;
+int rt_denoise(rt_context * ctx, const rt_denoise_params * params);
+int rt_read_denoised(rt_context * ctx, float * dst);
+/* rt_denoise with a HIP event pair around each of its kernels: kernel_ms[0] prepare, then one entry per pass (or the finalize kernel with 0 iterations);
+ * *out_count entries are written, capacity must be at least iterations + 1 (or 2). tiled: as rt_denoise_images. For measurements (tools/denoise_cost.py). */
+int rt_denoise_timed(rt_context * ctx, const rt_denoise_params * params, int tiled, float * kernel_ms, size_t capacity, size_t * out_count);
+
 /* Kulla-Conty LUTs as computed on the device at first use (kernel_integrate_* /
  * kernel_average_*, CUDA/KullaConty.h:83-240): 16^3, 16^3, 16^2, 16^2, 32^2, 32 floats.
  * Any pointer may be NULL. Synchronous.                                                     */
@@ -857,6 +890,13 @@ int rt_select_pixels_images(rt_context * ctx, const float * mean, const float * 
  * (RT_ERROR_INVALID_ARG): an entry outside the frame and a pixel listed twice -- the fold is a plain read-modify-write.                */
 int rt_accumulate_list_frames(rt_context * ctx, const int32_t * first_sample, const int32_t * sample_count, size_t submissions,
                               float * frames, float * accumulator, float * moments, const uint32_t * list, size_t list_count, uint32_t sentinel, float * final_image);
+/* rt_denoise's launchers on explicit images of a size of the caller's (synchronous; the context needs no frame, no scene and no estimate): colour, moments,
+ * albedo, normal, position and fallback (what rt_denoise takes from the final image) are pitch*height float4, pitch >= width, width * height and pitch * height
+ * below 2^26; eye: the camera position. out: pitch*height float4, read first: what the kernels do not write -- the padding columns -- comes back as the caller
+ * gave it. tiled = 1: the passes stage their taps in LDS (what rt_denoise runs), 0: the plain pass kernel; the two agree bit for bit. Parameters are refused as
+ * by rt_denoise. Leaves the context's own images untouched.                                                                                              */
+int rt_denoise_images(rt_context * ctx, int width, int height, int pitch, const float * colour, const float * moments, const float * albedo, const float * normal,
+                      const float * position, const float * fallback, const float * eye, const rt_denoise_params * params, int tiled, float * out);
 /* ---- fog volume ---------------------------------------------------------------------------------------------------
  * One scene-wide homogeneous medium inside an axis-aligned box, with multiple scattering and light sampling at every scatter vertex. Off
  * until a volume is set; while it is off a context launches exactly the kernels it launched before these calls existed. (Additions that
