@@ -81,6 +81,24 @@ def denoise_params(**params):
     return DenoiseParams(int(merged["iterations"]), *[float(merged[k]) for k in ("sigma_l", "sigma_n", "sigma_z", "depth_floor", "albedo_floor")])
 
 
+class FireflyParams(ctypes.Structure):  # rt_firefly_params
+    _fields_ = [("tiers", c_int), ("start", c_float), ("support", c_float)]
+
+
+# the values DESIGN.md 7.10 proposes (CPUConfig's firefly_* fields hold the same)
+FIREFLY_DEFAULTS = {"tiers": 6, "start": 1.0, "support": 4.0}
+
+
+def firefly_params(**params):
+    unknown = set(params) - set(FIREFLY_DEFAULTS)
+    if unknown:
+        raise TypeError("unknown firefly parameter(s): %s" % ", ".join(sorted(unknown)))
+    merged = dict(FIREFLY_DEFAULTS, **params)
+    if int(merged["tiers"]) != merged["tiers"]:
+        raise ValueError("tiers must be a whole number")
+    return FireflyParams(int(merged["tiers"]), float(merged["start"]), float(merged["support"]))
+
+
 class DeviceLibraryMissing(RuntimeError):
     pass
 
@@ -178,6 +196,16 @@ def device_lib():
         lib.rt_read_denoised.argtypes = [c_void_p, c_void_p]
         lib.rt_denoise_timed.argtypes = [c_void_p, POINTER(DenoiseParams), c_int, c_void_p, c_size_t, POINTER(c_size_t)]
         lib.rt_denoise_images.argtypes = [c_void_p, c_int, c_int, c_int] + [c_void_p] * 7 + [POINTER(DenoiseParams), c_int, c_void_p]
+        lib.rt_set_firefly_cascade.argtypes = [c_void_p, POINTER(FireflyParams)]
+        lib.rt_get_firefly_cascade.argtypes = [c_void_p, POINTER(FireflyParams)]
+        lib.rt_read_firefly_cascade.argtypes = [c_void_p, c_void_p, c_size_t]
+        lib.rt_resolve_fireflies.argtypes = [c_void_p, c_float]
+        lib.rt_read_resolved.argtypes = [c_void_p, c_void_p]
+        lib.rt_resolve_fireflies_timed.argtypes = [c_void_p, c_float, c_int, POINTER(c_float)]
+        lib.rt_set_denoise_source.argtypes = [c_void_p, c_int]
+        lib.rt_get_denoise_source.argtypes = [c_void_p]
+        lib.rt_accumulate_cascade_frames.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, POINTER(FireflyParams), c_void_p, c_uint32, c_void_p]
+        lib.rt_resolve_fireflies_images.argtypes = [c_void_p, c_int, c_int, c_int] + [c_void_p] * 4 + [POINTER(FireflyParams), c_int, c_void_p]
         _device = lib
     return _device
 
@@ -288,6 +316,8 @@ def host_lib():
         lib.grt_export_image.argtypes = [c_char_p, c_int, c_int, c_int, c_void_p]
         lib.grt_pathtracer_denoise.argtypes = [c_void_p, c_void_p, c_void_p]
         lib.grt_pathtracer_save_denoised_image.argtypes = [c_void_p, c_char_p, c_void_p]
+        lib.grt_pathtracer_resolve_fireflies.argtypes = [c_void_p, ctypes.c_double, c_void_p]
+        lib.grt_pathtracer_save_resolved_image.argtypes = [c_void_p, c_char_p, ctypes.c_double]
         lib.grt_pathtracer_array.restype = c_void_p
         lib.grt_pathtracer_array.argtypes = [c_void_p, c_char_p, POINTER(c_size_t)]
         lib.grt_pathtracer_sky_size.argtypes = [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_float)]
@@ -998,6 +1028,27 @@ class Pathtracer:
         values = self._denoise_params(params)
         _host_check(host_lib().grt_pathtracer_save_denoised_image(self.handle, str(filename).encode(), values.ctypes.data if values is not None else None))
 
+    # ---- firefly filter
+    def set_firefly_filter(self, enable=True, **params):
+        """config firefly_filter (and firefly_tiers / firefly_start / firefly_support from tiers, start, support): from the next update() on (which restarts the
+        progression when it switches them on) the device keeps the noise estimate and the tier cascade that resolve_fireflies() reweights."""
+        unknown = set(params) - set(FIREFLY_DEFAULTS)
+        if unknown:
+            raise TypeError("unknown firefly parameter(s): %s" % ", ".join(sorted(unknown)))
+        config_set(firefly_filter=1 if enable else 0, **{"firefly_" + k: v for k, v in params.items()})
+
+    def resolve_fireflies(self, support=None):
+        """Pathtracer::resolve_fireflies(): the tier cascade, every tier scaled by how well its neighbourhood supports it. Returns (image, held_back): (height, width, 3)
+        float32 and the (height, width) plane of the luminance that was held back (-1: a pixel that was not valid and carries the final image's colour).
+        support: kappa; None for the configuration's. Completes the work in flight."""
+        image = np.zeros((self.height, self.pitch, 4), np.float32)
+        _host_check(host_lib().grt_pathtracer_resolve_fireflies(self.handle, 0.0 if support is None else float(support), image.ctypes.data))
+        return image[:, :self.width, :3].copy(), image[:, :self.width, 3].copy()
+
+    def save_resolved_image(self, filename, support=None):
+        """save_image's exporters (.ppm, .exr) on the resolved image."""
+        _host_check(host_lib().grt_pathtracer_save_resolved_image(self.handle, str(filename).encode(), 0.0 if support is None else float(support)))
+
     # ---- noise estimate (DESIGN.md 7.5)
     def set_noise_estimate(self, enable=True):
         """The device keeps Welford second moments beside the radiance mean from the next update() on (which restarts the
@@ -1290,6 +1341,104 @@ def denoise_images(ctx, colour, moments, albedo, normal, position, fallback, eye
     if status:
         raise DeviceRefusal(ctx, status)
     return out
+
+
+# ---- firefly filter
+def set_firefly_cascade(ctx, enable=True, **params):
+    """rt_set_firefly_cascade: tiers, start, support (FIREFLY_DEFAULTS); enable=False switches it off and frees the tiers."""
+    status = device_lib().rt_set_firefly_cascade(ctx, byref(firefly_params(**params)) if enable else None)
+    if status:
+        raise DeviceRefusal(ctx, status)
+
+
+def get_firefly_cascade(ctx):
+    """None while the cascade is off, else {"tiers", "start", "support"}."""
+    record = FireflyParams()
+    if not device_lib().rt_get_firefly_cascade(ctx, byref(record)):
+        return None
+    return {"tiers": record.tiers, "start": record.start, "support": record.support}
+
+
+def read_firefly_cascade(ctx, height, pitch):
+    """rt_read_firefly_cascade: (tiers, height, pitch, 4) float32 (sum w r, sum w g, sum w b, sum w)."""
+    state = get_firefly_cascade(ctx)
+    tiers = np.zeros((state["tiers"] if state else 1, height, pitch, 4), np.float32)
+    status = device_lib().rt_read_firefly_cascade(ctx, tiers.ctypes.data, tiers.size)
+    if status:
+        raise DeviceRefusal(ctx, status)
+    return tiers
+
+
+def resolve_fireflies(ctx, support=None):
+    """rt_resolve_fireflies on the context's frame; the image comes back through read_resolved. support: None for the cascade's own."""
+    if support is None:
+        state = get_firefly_cascade(ctx)
+        support = state["support"] if state else FIREFLY_DEFAULTS["support"]
+    status = device_lib().rt_resolve_fireflies(ctx, c_float(support))
+    if status:
+        raise DeviceRefusal(ctx, status)
+
+
+def resolve_fireflies_timed(ctx, support=FIREFLY_DEFAULTS["support"], tiled=True):
+    """rt_resolve_fireflies_timed: the resolve kernel's time in ms."""
+    ms = c_float(0.0)
+    status = device_lib().rt_resolve_fireflies_timed(ctx, c_float(support), 1 if tiled else 0, byref(ms))
+    if status:
+        raise DeviceRefusal(ctx, status)
+    return ms.value
+
+
+def read_resolved(ctx, height, pitch):
+    """rt_read_resolved: (height, pitch, 4) float32 {r, g, b, held-back luminance}."""
+    image = np.zeros((height, pitch, 4), np.float32)
+    status = device_lib().rt_read_resolved(ctx, image.ctypes.data)
+    if status:
+        raise DeviceRefusal(ctx, status)
+    return image
+
+
+def set_denoise_source(ctx, source):
+    """rt_set_denoise_source: "mean" or "resolved"."""
+    status = device_lib().rt_set_denoise_source(ctx, {"mean": 0, "resolved": 1}.get(source, source))
+    if status:
+        raise DeviceRefusal(ctx, status)
+
+
+def resolve_fireflies_images(ctx, mean, moments, tiers, fallback, width=None, tiled=True, sentinel=None, tier_count=None, **params):
+    """rt_resolve_fireflies_images: the resolve kernel on explicit images: mean, moments, fallback (height, pitch, 4) float32, tiers (K, height, pitch, 4); width
+    defaults to pitch; params: start, support (the number of tiers is the array's, unless tier_count says otherwise). Returns (height, pitch, 4) float32 {r, g, b, held-back luminance}; what the kernel
+    does not write (the padding columns) holds `sentinel` (a float32 bit pattern; default 0x7fc0dead)."""
+    mean, moments, tiers, fallback = (_f32(a) for a in (mean, moments, tiers, fallback))
+    height, pitch = mean.shape[:2]
+    assert moments.shape == fallback.shape == mean.shape == (height, pitch, 4) and tiers.ndim == 4 and tiers.shape[1:] == mean.shape
+    record = firefly_params(tiers=tiers.shape[0] if tier_count is None else tier_count, **params)
+    assert record.tiers <= tiers.shape[0] or not 2 <= record.tiers <= 8
+    out = np.full((height, pitch, 4), 0x7fc0dead if sentinel is None else sentinel, np.uint32).view(np.float32)
+    status = device_lib().rt_resolve_fireflies_images(ctx, pitch if width is None else width, height, pitch, mean.ctypes.data, moments.ctypes.data, tiers.ctypes.data, fallback.ctypes.data,
+                                                      byref(record), 1 if tiled else 0, out.ctypes.data)
+    if status:
+        raise DeviceRefusal(ctx, status)
+    return out
+
+
+def accumulate_cascade_frames(ctx, frames, accumulator, moments, tiers, first_sample, sample_count=None, merged=False, pixels=None, sentinel=0x7fc0dead, **params):
+    """rt_accumulate_cascade_frames: accumulate_frames / accumulate_list_frames (pixels: the list, merged only) with the cascade; tiers: (K, height, pitch, 4) in
+    and out; params: start, support. Returns (frames, accumulator, moments, tiers, final_image) after the ONE launch."""
+    frames, accumulator, moments, tiers = (_f32(a).copy() for a in (frames, accumulator, moments, tiers))
+    if merged:
+        first, count = np.asarray(first_sample, np.int32).copy(), np.asarray(sample_count, np.int32).copy()
+    else:
+        first, count = np.array([first_sample], np.int32), np.array([frames.shape[0] if sample_count is None else sample_count], np.int32)
+    assert frames.ndim == 4 and frames.shape[0] == int(count.sum()) and frames.shape[1:] == accumulator.shape == moments.shape == tiers.shape[1:]
+    record = firefly_params(tiers=tiers.shape[0], **params)
+    pixels = None if pixels is None else np.ascontiguousarray(pixels, np.uint32)
+    final = np.zeros(accumulator.shape, np.float32)
+    status = device_lib().rt_accumulate_cascade_frames(ctx, 1 if merged else 0, first.ctypes.data, count.ctypes.data, len(first), frames.ctypes.data, accumulator.ctypes.data,
+                                                       moments.ctypes.data, None if pixels is None else pixels.ctypes.data, 0 if pixels is None else pixels.size, byref(record),
+                                                       tiers.ctypes.data, sentinel, final.ctypes.data)
+    if status:
+        raise DeviceRefusal(ctx, status)
+    return frames, accumulator, moments, tiers, final
 
 
 def accumulate_frames(ctx, frames, accumulator, moments, first_sample, sample_count=None, merged=False, sentinel=0x7fc0dead):

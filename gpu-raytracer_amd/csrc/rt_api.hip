@@ -288,6 +288,7 @@ int rt_resize(rt_context * ctx, int width, int height) {
 	device_free(ctx, ctx->noise_moments); ctx->noise_moments = nullptr;
 	pixel_list_free(ctx);
 	denoise_free(ctx);
+	firefly_free(ctx);
 	if ((s = sync_aovs(ctx))) return s;
 	if ((s = sync_svgf(ctx))) return s;
 	return sync_noise_moments(ctx);

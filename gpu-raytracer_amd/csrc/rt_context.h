@@ -1,6 +1,6 @@
 // rt_context.h -- what the units of the C ABI share: the context and the structs it is made of, error handling, and the internal functions that
 // cross a unit boundary. The units: rt_api.hip (context, frame state, results), rt_scene.hip (scene uploads and device builds), rt_render.hip (the slot
-// scheduler and the render entry points), rt_stream.hip (the merged wavefront's host side), rt_noise.hip (noise estimate, adaptive sampling), rt_denoise.hip (denoised stills),
+// scheduler and the render entry points), rt_stream.hip (the merged wavefront's host side), rt_noise.hip (noise estimate, adaptive sampling), rt_denoise.hip (denoised stills), rt_fireflies.hip (firefly filter),
 // rt_exchange.hip (frame exchange of the tile split), rt_probes.hip (kernel-level entry points). Private to csrc/.
 #pragma once
 #include "rt_types.h"
@@ -227,6 +227,16 @@ struct rt_context {
 	// the first rt_denoise, freed by rt_resize.
 	void * denoise_images[3] = { }, * denoise_guide = nullptr; int * denoise_any_valid = nullptr;
 	int denoise_result = -1;
+	int denoise_source = RT_DENOISE_SOURCE_MEAN;   // rt_set_denoise_source
+
+	// firefly filter (rt_set_firefly_cascade): firefly.tiers images of (sum w rgb, sum w), frame_pixels apart in one allocation, kept by the ..._cascade
+	// accumulate kernels beside the moments image and zeroed whenever that image is; they exist exactly while the cascade is on, the moments image exists and the
+	// frame has a size. firefly_resolved: the result image of rt_resolve_fireflies (allocated at the first call, freed by rt_resize); it is current while
+	// firefly_resolved_at == folds, the number of accumulate launches and zeroings the frame has seen.
+	bool firefly_on = false;
+	rt_firefly_params firefly = { };
+	void * firefly_tiers = nullptr, * firefly_resolved = nullptr; int * firefly_any_valid = nullptr;
+	unsigned long long folds = 1, firefly_resolved_at = 0;
 
 	// frame exchange of the tile split (rt_comm_*): this context's rank in a group of `world` contexts, each on its own GPU
 	// (RCCL communicator) or, for tests on one GPU, several in one process (peer copies)
@@ -312,6 +322,12 @@ int select_cells_images(rt_context * ctx, const char * caller, const float4 * me
 // rt_denoise.hip
 void denoise_free(rt_context * ctx);
 int denoise_arguments(rt_context * ctx, const char * caller, const rt_denoise_params * params);
+// rt_fireflies.hip
+int sync_firefly_tiers(rt_context * ctx);
+int firefly_tiers_zero(rt_context * ctx);
+void firefly_free(rt_context * ctx);
+bool firefly_tiers_for(rt_context * ctx, const RtParams & p, RtFireflyTiers * out);
+int firefly_arguments(rt_context * ctx, const char * caller, int tiers, float start, float support);
 #pragma GCC visibility pop
 
 #define RT_HIP(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(ctx, RT_ERROR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)

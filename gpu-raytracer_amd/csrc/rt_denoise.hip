@@ -48,6 +48,12 @@ static int denoise_frame(rt_context * ctx, const char * caller, const rt_denoise
 	const size_t kernels = params->iterations == 0 ? 2 : size_t(params->iterations) + 1;
 	if (kernel_ms && capacity < kernels) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: capacity %zu is below the %zu kernels of the run", caller, capacity, kernels);
 	RT_HIP(ctx, quiesce(ctx));
+	const float4 * colour = (const float4 *)ctx->aov_buffers[RT_AOV_RADIANCE][1];
+	if (ctx->denoise_source == RT_DENOISE_SOURCE_RESOLVED) {   // (after quiesce: the folds in flight are counted)
+		if (!ctx->firefly_resolved || ctx->firefly_resolved_at == 0) return fail(ctx, RT_ERROR_NOT_READY, "%s: the source is the resolved image (rt_set_denoise_source) and none exists (rt_resolve_fireflies)", caller);
+		if (ctx->firefly_resolved_at != ctx->folds) return fail(ctx, RT_ERROR_NOT_READY, "%s: the resolved image is older than the frame: samples were folded in since (rt_resolve_fireflies)", caller);
+		colour = (const float4 *)ctx->firefly_resolved;
+	}
 	for (void *& image : ctx->denoise_images) if (!image) { s = device_alloc(ctx, &image, ctx->frame_pixels * 16); if (s) return s; RT_HIP(ctx, hipMemset(image, 0, ctx->frame_pixels * 16)); }
 	if (!ctx->denoise_guide) { s = device_alloc(ctx, &ctx->denoise_guide, ctx->frame_pixels * 16); if (s) return s; }
 	if (!ctx->denoise_any_valid) { s = device_alloc(ctx, (void **)&ctx->denoise_any_valid, 16); if (s) return s; }
@@ -58,7 +64,7 @@ static int denoise_frame(rt_context * ctx, const char * caller, const rt_denoise
 	const int last_input = params->iterations == 0 ? 0 : (params->iterations - 1) & 1;
 	RtDenoiseArgs args = { p.screen_width, p.screen_height, p.screen_pitch, params->iterations, params->sigma_l, params->sigma_n, params->sigma_z, params->depth_floor, params->albedo_floor,
 	                       { p.camera.position[0], p.camera.position[1], p.camera.position[2] } };
-	RtDenoiseImages images = { (const float4 *)ctx->aov_buffers[RT_AOV_RADIANCE][1], (const float4 *)ctx->noise_moments, (const float4 *)ctx->aov_buffers[RT_AOV_ALBEDO][1],
+	RtDenoiseImages images = { colour, (const float4 *)ctx->noise_moments, (const float4 *)ctx->aov_buffers[RT_AOV_ALBEDO][1],
 	                           (const float4 *)ctx->aov_buffers[RT_AOV_NORMAL][1], (const float4 *)ctx->aov_buffers[RT_AOV_POSITION][1], (const float4 *)ctx->final_image,
 	                           { (float4 *)ctx->denoise_images[pair[0]], (float4 *)ctx->denoise_images[pair[1]] }, (float4 *)ctx->denoise_guide,
 	                           (float4 *)ctx->denoise_images[pair[last_input ^ 1]], ctx->denoise_any_valid };

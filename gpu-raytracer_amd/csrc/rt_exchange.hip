@@ -190,6 +190,7 @@ static int exchange_group(rt_context ** contexts, int count, int what) {
 		rt_context * ctx = contexts[i]; rt_context::FrameExchange & x = ctx->exchange;
 		(void)hipSetDevice(ctx->device);
 		const int tiles = int(exchange_tiles_per_rank(ctx, ctx->params.tile_pixels, x.world));
+		ctx->folds++;   // (other ranks' pixels replace this context's: a resolved image is older than the frame)
 		if (what == 0) rt_launch_unpack_pixels(ctx->params, x.gathered, ctx->params.tile_pixels, x.world, tiles, ctx->stream);
 		else rt_launch_unpack_svgf(slot_params(ctx, ctx->slots[0], 0), x.gathered, ctx->params.tile_pixels, x.world, tiles, ctx->stream);
 		RT_HIP(ctx, hipGetLastError());

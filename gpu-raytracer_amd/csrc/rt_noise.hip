@@ -16,7 +16,7 @@ int sync_noise_moments(rt_context * ctx) {
 		RT_HIP(ctx, hipMemset(ctx->noise_moments, 0, ctx->frame_pixels * 16));
 	} else if (!want && ctx->noise_moments) { device_free(ctx, ctx->noise_moments); ctx->noise_moments = nullptr; }
 	if (!want) pixel_list_free(ctx);
-	return RT_OK;
+	return sync_firefly_tiers(ctx);   // (beside the moments image, or not at all)
 }
 // A change of the pixel set: the moments of pixels the context no longer renders would go stale beside means that another rank's image replaces.
 int noise_moments_reset(rt_context * ctx) {
@@ -25,7 +25,7 @@ int noise_moments_reset(rt_context * ctx) {
 	RT_HIP(ctx, quiesce(ctx));
 	RT_HIP(ctx, hipMemset(ctx->noise_moments, 0, ctx->frame_pixels * 16));
 	pixel_list_drop(ctx);
-	return RT_OK;
+	return firefly_tiers_zero(ctx);
 }
 // What the accumulate launchers get as `moments` for a launch under parameter block p: the image while the estimate is on and the launch is not an SVGF frame's
 // (whose accumulators are the filter's ping-pong images), else null -- the plain kernels, as before.
@@ -131,7 +131,7 @@ int rt_set_noise_estimate(rt_context * ctx, int enable) {
 	int s = sync_noise_moments(ctx); if (s) return s;
 	if (ctx->noise_moments) RT_HIP(ctx, hipMemset(ctx->noise_moments, 0, ctx->frame_pixels * 16));
 	pixel_list_drop(ctx);
-	return RT_OK;
+	return firefly_tiers_zero(ctx);
 }
 int rt_get_noise_estimate(const rt_context * ctx) { return ctx && ctx->noise_estimate ? 1 : 0; }
 

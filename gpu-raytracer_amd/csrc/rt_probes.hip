@@ -1070,6 +1070,94 @@ int rt_accumulate_list_frames(rt_context * ctx, const int32_t * first_sample, co
 	return probe.read(final_image, dev_final, frame_pixels * 16);
 }
 
+// rt_accumulate_frames and rt_accumulate_list_frames with the cascade: the same parameter block and checks, ONE launch of the production launcher.
+int rt_accumulate_cascade_frames(rt_context * ctx, int merged, const int32_t * first_sample, const int32_t * sample_count, size_t submissions, float * frames,
+                                 float * accumulator, float * moments, const uint32_t * list, size_t list_count, const rt_firefly_params * params, float * tiers,
+                                 uint32_t sentinel, float * final_image) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_accumulate_cascade_frames: NULL context");
+	RT_REQUIRE(ctx, merged == 0 || merged == 1, "rt_accumulate_cascade_frames: merged must be 0 (one batch) or 1 (a group of submissions)");
+	RT_REQUIRE(ctx, first_sample && sample_count && frames && accumulator && moments && params && tiers && final_image, "rt_accumulate_cascade_frames: NULL array");
+	RT_REQUIRE(ctx, !list || merged, "rt_accumulate_cascade_frames: a pixel list takes the merged form");
+	int s = firefly_arguments(ctx, "rt_accumulate_cascade_frames", params->tiers, params->start, params->support); if (s) return s;
+	RT_REQUIRE(ctx, submissions >= 1 && submissions <= size_t(merged ? RT_ACCUMULATE_GROUP : 1), merged ? "rt_accumulate_cascade_frames: 1 to RT_ACCUMULATE_GROUP submissions" : "rt_accumulate_cascade_frames: the batch form takes one submission");
+	size_t total = 0;
+	for (size_t k = 0; k < submissions; k++) {
+		RT_REQUIRE(ctx, first_sample[k] >= 0 && sample_count[k] >= 1 && sample_count[k] <= RT_STREAM_SAMPLE_SLOTS, "rt_accumulate_cascade_frames: a first sample below 0 or a sample count outside [1, 512]");
+		RT_REQUIRE(ctx, merged || sample_count[k] <= RT_MAX_BATCH_SAMPLES, "rt_accumulate_cascade_frames: a batch holds at most 16 samples");
+		RT_REQUIRE(ctx, size_t(first_sample[k]) + size_t(sample_count[k]) <= size_t(1) << 24, "rt_accumulate_cascade_frames: sample indices must stay below 2^24");
+		total += size_t(sample_count[k]);
+	}
+	(void)hipSetDevice(ctx->device);
+	const size_t frame_pixels = ctx->frame_pixels;
+	if (frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_accumulate_cascade_frames: rt_resize was not called");
+	RT_REQUIRE(ctx, total <= size_t(RT_STREAM_SAMPLE_SLOTS) && total * frame_pixels < size_t(1) << 30, "rt_accumulate_cascade_frames: at most 512 samples and fewer than 2^30 pixels in all");
+	int range_offset = 0, range_count = 0;
+	if (list) {   // before any launch: every entry inside the frame, no pixel twice (two threads folding one pixel would race)
+		const size_t frame = size_t(ctx->params.screen_width) * size_t(ctx->params.screen_height);
+		RT_REQUIRE(ctx, list_count >= 1 && list_count <= frame, "rt_accumulate_cascade_frames: the list holds 1 to width * height entries");
+		std::vector<bool> seen(frame, false);
+		for (size_t i = 0; i < list_count; i++) {
+			if (list[i] >= frame) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_accumulate_cascade_frames: list entry %zu (%u) lies outside the %zu pixel frame", i, list[i], frame);
+			if (seen[list[i]]) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_accumulate_cascade_frames: list entry %zu names pixel %u a second time", i, list[i]);
+			seen[list[i]] = true;
+		}
+	} else {
+		if (ctx->pixel_list_on) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_accumulate_cascade_frames: the context covers a pixel list (rt_set_pixel_list); pass a list");
+		if ((s = resolve_pixel_range(ctx, "rt_accumulate_cascade_frames", &range_offset, &range_count))) return s;
+	}
+	RT_HIP(ctx, quiesce(ctx));
+
+	Probe probe(ctx, "rt_accumulate_cascade_frames");
+	float4 * dev_frames = probe.array<float4>(total * frame_pixels, frames);
+	float4 * dev_accumulator = probe.array<float4>(frame_pixels, accumulator);
+	float4 * dev_moments = probe.array<float4>(frame_pixels, moments);
+	float4 * dev_tiers = probe.array<float4>(frame_pixels * size_t(params->tiers), tiers);
+	unsigned * dev_list = list ? probe.array<unsigned>(list_count, list) : nullptr;
+	probe.staging.assign(frame_pixels * 4, sentinel);
+	float4 * dev_final = (float4 *)probe.array<uint32_t>(frame_pixels * 4, probe.staging.data());
+	if ((s = probe.allocated())) return s;
+
+	RtParams p = ctx->params;
+	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = p.aovs[a].accumulator = nullptr;
+	p.aovs[RT_AOV_RADIANCE].framebuffer = dev_frames; p.aovs[RT_AOV_RADIANCE].accumulator = dev_accumulator;
+	p.final_image = dev_final;
+	const RtFireflyTiers cascade = { dev_tiers, frame_pixels, params->tiers, params->start };
+	if (merged) {
+		RtAccumulateGroup group; group.count = int(submissions);
+		for (int k = 0, base = 0; k < group.count; k++) { group.first_sample[k] = first_sample[k]; group.sample_count[k] = sample_count[k]; group.slot_base[k] = base; base += sample_count[k]; }
+		for (int k = group.count; k < RT_ACCUMULATE_GROUP; k++) group.first_sample[k] = group.sample_count[k] = group.slot_base[k] = 0;
+		if (list) rt_launch_accumulate_group_list_cascade(p, group, dev_list, int(list_count), ctx->stream, dev_moments, cascade);
+		else rt_launch_accumulate_group_cascade(p, group, range_offset, range_count, ctx->stream, dev_moments, cascade);
+	} else {
+		p.batch_samples = sample_count[0];
+		rt_launch_accumulate_cascade(p, float(first_sample[0]), range_offset, range_count, ctx->stream, dev_moments, cascade);
+	}
+	if ((s = probe.finish())) return s;
+	if ((s = probe.read(frames, dev_frames, total * frame_pixels * 16)) || (s = probe.read(accumulator, dev_accumulator, frame_pixels * 16))) return s;
+	if ((s = probe.read(moments, dev_moments, frame_pixels * 16)) || (s = probe.read(tiers, dev_tiers, frame_pixels * size_t(params->tiers) * 16))) return s;
+	return probe.read(final_image, dev_final, frame_pixels * 16);
+}
+
+int rt_resolve_fireflies_images(rt_context * ctx, int width, int height, int pitch, const float * mean, const float * moments, const float * tiers, const float * fallback,
+                                const rt_firefly_params * params, int tiled, float * out) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_resolve_fireflies_images: NULL context");
+	RT_REQUIRE(ctx, mean && moments && tiers && fallback && params && out, "rt_resolve_fireflies_images: NULL argument");
+	int s = firefly_arguments(ctx, "rt_resolve_fireflies_images", params->tiers, params->start, params->support); if (s) return s;
+	RT_REQUIRE(ctx, tiled == 0 || tiled == 1, "rt_resolve_fireflies_images: tiled must be 0 or 1");
+	RT_REQUIRE(ctx, width > 0 && height > 0 && pitch >= width, "rt_resolve_fireflies_images: width and height must be positive and pitch at least width");
+	RT_REQUIRE(ctx, (long long)pitch * height < (1ll << 26), "rt_resolve_fireflies_images: pitch * height must stay below 2^26");
+	(void)hipSetDevice(ctx->device);
+	RT_HIP(ctx, quiesce(ctx));
+	Probe probe(ctx, "rt_resolve_fireflies_images");
+	const size_t pixels = size_t(pitch) * size_t(height);
+	const RtFireflyResolveImages images = { probe.array<float4>(pixels, mean), probe.array<float4>(pixels, moments), probe.array<float4>(pixels, fallback),
+	                                        probe.array<float4>(pixels * size_t(params->tiers), tiers), pixels, probe.array<float4>(pixels, out), nullptr };
+	if ((s = probe.allocated())) return s;
+	const RtFireflyResolveArgs args = { width, height, pitch, params->tiers, params->start, params->support };
+	rt_launch_fireflies_resolve(args, images, tiled != 0, ctx->stream);
+	return probe.finish_and_read(out, images.out, pixels * 16);
+}
+
 int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps) {
 	RT_REQUIRE(ctx, ctx && out_gbps && bytes >= 1024, "rt_measure_stream_bandwidth: invalid argument");
 	(void)hipSetDevice(ctx->device);

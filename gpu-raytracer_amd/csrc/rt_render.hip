@@ -322,7 +322,11 @@ int rt_render_samples(rt_context * ctx, int sample_index, int sample_count) {
 	const bool deferred = p.config.enable_svgf && ctx->defer_filter; // rt_filter_frame does the rest once the ranks have exchanged their tiles
 	if (deferred) { }
 	else if (p.config.enable_svgf) { p.taa_frame_prev = ctx->params.taa_frame_prev; p.taa_frame_next = ctx->params.taa_frame_next; rt_launch_svgf_taa(p, sample_index, st); if (p.config.enable_taa) std::swap(ctx->params.taa_frame_prev, ctx->params.taa_frame_next); }
-	else rt_launch_accumulate(p, float(sample_index), range_offset, range_count, st, noise_moments_for(ctx, p));
+	else {
+		RtFireflyTiers tiers;   // (the cascade forms of the same kernels while rt_set_firefly_cascade is on)
+		if (firefly_tiers_for(ctx, p, &tiers)) rt_launch_accumulate_cascade(p, float(sample_index), range_offset, range_count, st, noise_moments_for(ctx, p), tiers);
+		else rt_launch_accumulate(p, float(sample_index), range_offset, range_count, st, noise_moments_for(ctx, p));
+	}
 	stage_mark(ctx, STAGE_END, st);
 
 	// aovs_clear_to_zero (Integrator.cpp:379-385)
@@ -376,6 +380,7 @@ int rt_render_ao_sample(rt_context * ctx, int sample_index, float ao_radius) {
 	}
 	RtParams p_acc = p; // kernel_accumulate of AO.cu:161-183 folds RADIANCE, NORMAL and POSITION only
 	p_acc.aovs[RT_AOV_ALBEDO].framebuffer = nullptr;
+	ctx->folds++;   // (the mean moves: a resolved image is older than the frame from here on)
 	rt_launch_accumulate(p_acc, float(sample_index), range_offset, range_count, st);
 	for (int i = 0; i < RT_AOV_COUNT; i++) if (p.aovs[i].framebuffer) RT_HIP(ctx, hipMemsetAsync(p.aovs[i].framebuffer, 0, ctx->frame_pixels * 16, st));
 	return finish_slot_submission(ctx, 0);

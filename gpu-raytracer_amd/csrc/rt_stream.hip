@@ -178,7 +178,11 @@ static int stream_complete(rt_context * ctx, const StreamSubmission * subs, int 
 		RtParams pa = p;
 		pa.tile_pixels = head.tile_pixels; pa.tile_first = head.tile_first; pa.tile_stride = head.tile_stride;
 		span_mark(ctx, SPAN_ACCUMULATE, st);
-		if (head.list) rt_launch_accumulate_group_list(pa, group, (const unsigned *)ctx->pixel_list, head.range_count, st, (float4 *)ctx->noise_moments);   // (the list does not change while a submission is in flight)
+		RtFireflyTiers tiers;   // (the cascade forms of the same kernels while rt_set_firefly_cascade is on)
+		const bool cascade = firefly_tiers_for(ctx, pa, &tiers);
+		if (head.list && cascade) rt_launch_accumulate_group_list_cascade(pa, group, (const unsigned *)ctx->pixel_list, head.range_count, st, (float4 *)ctx->noise_moments, tiers);
+		else if (head.list) rt_launch_accumulate_group_list(pa, group, (const unsigned *)ctx->pixel_list, head.range_count, st, (float4 *)ctx->noise_moments);   // (the list does not change while a submission is in flight)
+		else if (cascade) rt_launch_accumulate_group_cascade(pa, group, head.range_offset, head.range_count, st, noise_moments_for(ctx, pa), tiers);
 		else rt_launch_accumulate_group(pa, group, head.range_offset, head.range_count, st, noise_moments_for(ctx, pa));
 		span_mark(ctx, SPAN_ACCUMULATE, st);
 		first = k;

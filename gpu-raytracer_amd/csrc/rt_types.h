@@ -340,6 +340,20 @@ struct RtDenoiseArgs { int width, height, pitch, iterations; float sigma_l, sigm
 struct RtDenoiseImages { const float4 * colour, * moments, * albedo, * normal, * position, * fallback; float4 * iv[2], * guide, * out; int * any_valid; };
 void rt_launch_denoise(const RtDenoiseArgs & args, const RtDenoiseImages & images, bool tiled, hipStream_t stream,
                        void (*mark)(void * user, int kernel, hipStream_t stream) = nullptr, void * user = nullptr);
+// The firefly filter (kernels_fireflies.hip). Tiers: `count` (2..8) pitched float4 images (sum w r, sum w g, sum w b, sum w), `plane` pixels apart in one
+// allocation; tier j takes the samples whose luminance lies around start * 8^j. The ..._cascade launchers are the three moments accumulate launchers above with the
+// splat beside the fold (moments is required): mean, moments and final image come out as the plain kernels leave them. The tier pointers are a kernel argument of
+// their own: RtParams keeps its size.
+#define RT_FIREFLY_MAX_TIERS 8
+struct RtFireflyTiers { float4 * tiers; size_t plane; int count; float start; };
+void rt_launch_accumulate_cascade(const RtParams & p, float frames_accumulated, int pixel_offset, int pixel_count, hipStream_t stream, float4 * moments, const RtFireflyTiers & tiers);
+void rt_launch_accumulate_group_cascade(const RtParams & p, const RtAccumulateGroup & group, int pixel_offset, int pixel_count, hipStream_t stream, float4 * moments, const RtFireflyTiers & tiers);
+void rt_launch_accumulate_group_list_cascade(const RtParams & p, const RtAccumulateGroup & group, const unsigned * list, int pixel_count, hipStream_t stream, float4 * moments, const RtFireflyTiers & tiers);
+// The resolve: (mean, moments, tiers) -> out = (R / N, luminance(T - R) / N), and (fallback.rgb, -1) for a pixel that is not valid. All images are pitched float4;
+// any_valid: null, or one int the kernel sets to 1 when a pixel is valid. tiled: the W of the tile's halo are staged in LDS; the plain kernel gives the same bits.
+struct RtFireflyResolveArgs { int width, height, pitch, tiers; float start, support; };
+struct RtFireflyResolveImages { const float4 * mean, * moments, * fallback, * tiers; size_t plane; float4 * out; int * any_valid; };
+void rt_launch_fireflies_resolve(const RtFireflyResolveArgs & args, const RtFireflyResolveImages & images, bool tiled, hipStream_t stream);
 // mark(user, k, stream), if given, is called before and after kernel k = 0 reproject, 1 variance, 2 a-trous (each pass), 3 finalize, 4 TAA, 5 TAA finalize
 void rt_launch_svgf_taa(const RtParams & p, int sample_index, hipStream_t stream, void (*mark)(void * user, int svgf_kernel, hipStream_t stream) = nullptr, void * user = nullptr);
 void rt_launch_random(const RtParams & p, int dimension, const unsigned * pixel_indices, int count, unsigned bounce, unsigned sample_index, float2 * out, hipStream_t stream);

@@ -9,6 +9,7 @@ struct AO final : Integrator {
 	float ao_radius = 1.0f; // AO.h:102
 
 	AO(int width, int height, Scene & scene, int device_ordinal = 0) : Integrator(scene, device_ordinal) {
+		splats_fireflies = false;   // (rt_render_ao_sample accumulates without moments)
 		gpu_init(width, height);
 	}
 	// Source compatibility with `AO(frame_buffer_handle, width, height, scene)` (Main.cpp:69)

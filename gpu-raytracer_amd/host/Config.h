@@ -127,6 +127,13 @@ struct CPUConfig {
 	int   denoise_iterations = 5;
 	float denoise_sigma_l = 4.0f, denoise_sigma_n = 128.0f, denoise_sigma_z = 1.0f;
 	float denoise_depth_floor = 1e-2f, denoise_albedo_floor = 1e-2f;
+	// Firefly filter. firefly_filter 1: the first Pathtracer::update() switches on the noise estimate and the tier cascade beside it, which
+	// Pathtracer::resolve_fireflies() reweights into an image; the command-line renderer (--firefly-filter) then writes that image. The frame itself is rendered as
+	// with 0. firefly_tiers: K, 2..8; firefly_start: b_0 > 0, the luminance tier 0 stands for (tier j: b_0 * 8^j); firefly_support: kappa > 1, the number of
+	// neighbouring samples that keep a tier whole.
+	int   firefly_filter = 0;
+	int   firefly_tiers = 6;
+	float firefly_start = 1.0f, firefly_support = 4.0f;
 	// Alpha-tested cut-outs from the albedo textures: 1 = every surface material whose albedo FILE has an alpha channel that is not constant gets an
 	// opacity mask from it (channel a, threshold 0.5; an explicit <bsdf type="mask"> wins). Read when a scene is loaded. 0: off, as the reference renders them.
 	int   alpha_masks = 0;

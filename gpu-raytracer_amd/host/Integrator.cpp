@@ -813,8 +813,16 @@ void Integrator::update(float delta) {
 	}
 	if (ctx) check(rt_set_sky_sampling(ctx, cpu_config.sky_sampling));   // (a value; the device applies it at the next render)
 	if (ctx) {   // (drains the context, so only on a change; the moments then start over, as the mean does at sample 0)
-		const bool want = noise_estimate_wanted || cpu_config.noise_target > 0.0f || cpu_config.denoise != 0;   // (the denoiser filters by the measured variance)
+		const bool want = noise_estimate_wanted || cpu_config.noise_target > 0.0f || cpu_config.denoise != 0 || (cpu_config.firefly_filter != 0 && splats_fireflies);   // (the denoiser filters by the measured variance; the firefly cascade lives beside the moments)
 		if (want != (rt_get_noise_estimate(ctx) != 0)) { check(rt_set_noise_estimate(ctx, want ? 1 : 0)); if (want) invalidated_gpu_config = true; }   // (the progression restarts at sample 0: moments that join a running mean would miss its past)
+		// The firefly cascade, the same way: tiers that join a running mean would miss its past.
+		rt_firefly_params have = { };
+		const bool on = rt_get_firefly_cascade(ctx, &have) != 0;
+		if (cpu_config.firefly_filter && splats_fireflies) {
+			const rt_firefly_params wanted = { cpu_config.firefly_tiers, cpu_config.firefly_start, cpu_config.firefly_support };
+			if (!on || have.tiers != wanted.tiers || have.start != wanted.start) { check(rt_set_firefly_cascade(ctx, &wanted)); invalidated_gpu_config = true; }
+			else if (have.support != wanted.support) check(rt_set_firefly_cascade(ctx, &wanted));   // (a value of the resolve)
+		} else if (on) check(rt_set_firefly_cascade(ctx, nullptr));
 	}
 	if (cpu_config.enable_scene_update) {
 		if (!scene_advanced_by_another_integrator) scene.update(delta);

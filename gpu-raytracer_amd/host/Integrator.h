@@ -55,6 +55,7 @@ struct Integrator {
 	int screen_width = 0, screen_height = 0, screen_pitch = 0;
 	int pixel_count = 0;
 	int sample_index = 0;
+	bool splats_fireflies = true;         // false for an integrator whose accumulate keeps no moments (AO): update() then leaves the firefly cascade of cpu_config.firefly_filter off
 	bool noise_estimate_wanted = false;   // the device keeps second moments (rt_set_noise_estimate) while this is set or cpu_config.noise_target > 0; applied by update()
 
 	// Multi-GPU: scan-order pixel range rendered by this integrator (default: all)

@@ -442,6 +442,22 @@ void Pathtracer::save_denoised_image(const std::string & filename, const rt_deno
 	if (!Exporters::save(filename, screen_pitch, screen_width, screen_height, rgb, &error)) throw std::runtime_error(error);
 }
 
+std::vector<float> Pathtracer::resolve_fireflies(float support) {
+	require_device();
+	check(rt_resolve_fireflies(ctx, support > 0.0f ? support : cpu_config.firefly_support));
+	std::vector<float> image(size_t(screen_pitch) * screen_height * 4);
+	check(rt_read_resolved(ctx, image.data()));
+	return image;
+}
+
+void Pathtracer::save_resolved_image(const std::string & filename, float support) {
+	const std::vector<float> rgba = resolve_fireflies(support);
+	std::vector<Vector3> rgb(rgba.size() / 4);
+	for (size_t i = 0; i < rgb.size(); i++) rgb[i] = Vector3(rgba[4 * i], rgba[4 * i + 1], rgba[4 * i + 2]);
+	std::string error;
+	if (!Exporters::save(filename, screen_pitch, screen_width, screen_height, rgb, &error)) throw std::runtime_error(error);
+}
+
 double Pathtracer::sample_counts(std::vector<float> * counts) {
 	require_device();
 	std::vector<float> moments(size_t(screen_pitch) * screen_height * 4);

@@ -79,6 +79,12 @@ struct Pathtracer final : Integrator {
 	std::vector<float> denoise(const rt_denoise_params * params = nullptr);
 	// The denoised image through the exporters save_image uses (ppm, exr by the file's extension); the AOV files save_image writes beside its image are not written
 	void save_denoised_image(const std::string & filename, const rt_denoise_params * params = nullptr);
+	// Firefly filter: the tier cascade through rt_resolve_fireflies, pitch * height float4 (r, g, b, luminance held back). Needs
+	// cpu_config.firefly_filter = 1 before the update() of sample 0 (which switches on the noise estimate and the cascade) and no SVGF. support: kappa, 0 for the
+	// configuration's. Completes the work in flight and changes nothing a later render reads.
+	std::vector<float> resolve_fireflies(float support = 0.0f);
+	// The resolved image through the exporters save_image uses (ppm, exr by the file's extension)
+	void save_resolved_image(const std::string & filename, float support = 0.0f);
 	// w per pixel (x + y * pitch; 0 in the padding) -- the number of samples the pixel's mean stands for -- and, returned, the mean of w over the frame's pixels.
 	// w is one below the samples rendered for the pixel: sample 1 overwrites sample 0 (AOV.h:35-46). Reports of "samples per pixel" add the 1.
 	double sample_counts(std::vector<float> * counts = nullptr);

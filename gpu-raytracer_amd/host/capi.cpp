@@ -142,6 +142,22 @@ int grt_config_set(const char * key, double value) {
 		if (!(value >= 0.0 && value < 1e30)) { g_host_error = k + " must be finite and not negative"; return -1; }
 		(k == "denoise_sigma_l" ? cpu_config.denoise_sigma_l : k == "denoise_sigma_n" ? cpu_config.denoise_sigma_n : cpu_config.denoise_sigma_z) = float(value);
 	}
+	else if (k == "firefly_filter") {
+		if (!(value == 0.0 || value == 1.0)) { g_host_error = "firefly_filter must be 0 or 1"; return -1; }
+		cpu_config.firefly_filter = int(value);
+	}
+	else if (k == "firefly_tiers") {
+		if (!(value >= 2.0 && value <= 8.0) || value != double(int(value))) { g_host_error = "firefly_tiers must be a whole number in [2, 8]"; return -1; }
+		cpu_config.firefly_tiers = int(value);
+	}
+	else if (k == "firefly_start") {
+		if (!(value > 0.0 && value < 1e30)) { g_host_error = "firefly_start must be finite and above 0"; return -1; }
+		cpu_config.firefly_start = float(value);
+	}
+	else if (k == "firefly_support") {
+		if (!(value > 1.0 && value < 1e30)) { g_host_error = "firefly_support must be finite and above 1"; return -1; }
+		cpu_config.firefly_support = float(value);
+	}
 	else if (k == "static_reseat_distance")              cpu_config.static_reseat_distance = float(value);
 	else if (k == "static_mesh_copy_limit_mb")           cpu_config.static_mesh_copy_limit_mb = int(value);
 	else if (k == "static_copy_budget_mb")               cpu_config.static_copy_budget_mb = int(value);
@@ -215,6 +231,10 @@ double grt_config_get(const char * key) {
 	if (k == "denoise_sigma_l")    return cpu_config.denoise_sigma_l;
 	if (k == "denoise_sigma_n")    return cpu_config.denoise_sigma_n;
 	if (k == "denoise_sigma_z")    return cpu_config.denoise_sigma_z;
+	if (k == "firefly_filter")     return cpu_config.firefly_filter;
+	if (k == "firefly_tiers")      return cpu_config.firefly_tiers;
+	if (k == "firefly_start")      return cpu_config.firefly_start;
+	if (k == "firefly_support")    return cpu_config.firefly_support;
 	return -1.0;
 }
 
@@ -640,6 +660,22 @@ int grt_pathtracer_save_denoised_image(void * pt, const char * filename, const d
 		if (!pt || !filename) throw std::runtime_error("grt_pathtracer_save_denoised_image: NULL argument");
 		const rt_denoise_params p = denoise_params_of(params);
 		as_pathtracer(pt)->save_denoised_image(filename, &p);
+		return 0;
+	GRT_CATCH(-1)
+}
+// Firefly filter. support: 0 for the configuration's. dst: pitch * height float4, (r, g, b, luminance held back).
+int grt_pathtracer_resolve_fireflies(void * pt, double support, float * dst) {
+	GRT_TRY
+		if (!pt || !dst) throw std::runtime_error("grt_pathtracer_resolve_fireflies: NULL argument");
+		std::vector<float> image = as_pathtracer(pt)->resolve_fireflies(float(support));
+		memcpy(dst, image.data(), image.size() * sizeof(float));
+		return 0;
+	GRT_CATCH(-1)
+}
+int grt_pathtracer_save_resolved_image(void * pt, const char * filename, double support) {
+	GRT_TRY
+		if (!pt || !filename) throw std::runtime_error("grt_pathtracer_save_resolved_image: NULL argument");
+		as_pathtracer(pt)->save_resolved_image(filename, float(support));
 		return 0;
 	GRT_CATCH(-1)
 }

@@ -44,6 +44,9 @@ struct CommandLine {
 	std::string sample_map;     // --sample-map
 	std::string denoise_noisy;  // --denoise-noisy
 	bool denoise_option = false;   // an option that needs --denoise was given
+	std::string firefly_map;         // --firefly-map
+	std::string firefly_unfiltered;  // --firefly-unfiltered
+	bool firefly_option = false;     // an option that needs --firefly-filter was given
 };
 
 [[noreturn]] void die(const std::string & message) {
@@ -154,6 +157,24 @@ std::vector<Option> make_options(CommandLine & cl) {
 		cpu_config.denoise_iterations = n; cl.denoise_option = true;
 	} });
 	o.push_back({ nullptr, "denoise-noisy", "With --denoise: also writes the unfiltered image to <file> (ppm, exr)", 1, [&cl](const char * v) { cl.denoise_noisy = v; cl.denoise_option = true; } });
+	o.push_back({ nullptr, "firefly-filter", "Keeps every pixel's samples in tiers by brightness and scales each tier by its support among the neighbours (DESIGN.md 7.10): -o receives the resolved image (with --denoise: the denoiser's source)", 0, [](const char *) { cpu_config.firefly_filter = 1; } });
+	o.push_back({ nullptr, "firefly-tiers", "With --firefly-filter: number of tiers (2..8, default 6)", 1, [&cl](const char * v) {
+		int n = parse_int(v, "--firefly-tiers");
+		if (n < 2 || n > 8) die("--firefly-tiers must be between 2 and 8");
+		cpu_config.firefly_tiers = n; cl.firefly_option = true;
+	} });
+	o.push_back({ nullptr, "firefly-start", "With --firefly-filter: the luminance the lowest tier stands for; tier j stands for 8^j times it (default 1)", 1, [&cl](const char * v) {
+		float b = parse_float(v, "--firefly-start");
+		if (!(b > 0.0f && b < 1e30f)) die("--firefly-start must be finite and above 0");
+		cpu_config.firefly_start = b; cl.firefly_option = true;
+	} });
+	o.push_back({ nullptr, "firefly-support", "With --firefly-filter: the number of neighbouring samples that keeps a tier whole (above 1, default 4)", 1, [&cl](const char * v) {
+		float k = parse_float(v, "--firefly-support");
+		if (!(k > 1.0f && k < 1e30f)) die("--firefly-support must be finite and above 1");
+		cpu_config.firefly_support = k; cl.firefly_option = true;
+	} });
+	o.push_back({ nullptr, "firefly-map", "With --firefly-filter: writes the luminance held back per pixel as a one-channel EXR", 1, [&cl](const char * v) { cl.firefly_map = v; cl.firefly_option = true; } });
+	o.push_back({ nullptr, "firefly-unfiltered", "With --firefly-filter: also writes the plain image to <file> (ppm, exr)", 1, [&cl](const char * v) { cl.firefly_unfiltered = v; cl.firefly_option = true; } });
 	o.push_back({ nullptr, "sample-map", "Writes the number of samples every pixel's mean stands for as a one-channel EXR", 1, [&cl](const char * v) { cl.sample_map = v; } });
 	o.push_back({ nullptr, "force-rebuild", "BVH will not be loaded from disk but rebuilt from scratch", 0, [](const char *) { cpu_config.bvh_force_rebuild = true; } });
 	o.push_back({ "O",  "optimize",    "Enables or disables BVH optimization post-processing step", 1, [](const char * v) { cpu_config.enable_bvh_optimization = parse_bool(v); } });
@@ -235,6 +256,9 @@ void parse_command_line(int argc, char ** argv, CommandLine & cl) {
 	if (cpu_config.adaptive_sampling && !(cpu_config.noise_target > 0.0f)) die("--adaptive needs --noise-target: the cells are selected by it");
 	if (cl.denoise_option && !cpu_config.denoise) die("--denoise-iterations / --denoise-noisy need --denoise");
 	if (!cl.denoise_noisy.empty() && cl.denoise_noisy == cpu_config.output_filename) die("--denoise-noisy names the output file: the denoised image goes there");
+	if (cl.firefly_option && !cpu_config.firefly_filter) die("--firefly-tiers / --firefly-start / --firefly-support / --firefly-map / --firefly-unfiltered need --firefly-filter");
+	if (!cl.firefly_unfiltered.empty() && cl.firefly_unfiltered == cpu_config.output_filename) die("--firefly-unfiltered names the output file: the resolved image goes there");
+	if (!cl.firefly_map.empty() && (cl.firefly_map == cpu_config.output_filename || cl.firefly_map == cl.firefly_unfiltered)) die("--firefly-map names a file another image goes to");
 	if (cl.print_config) { // one line, floats as bit patterns; the form oracle/ref/ref_scene_harness.cpp writes for the reference's Args::parse
 		auto bits = [](float f) { unsigned u; memcpy(&u, &f, 4); return u; };
 		std::string scenes;
@@ -339,6 +363,14 @@ int main(int argc, char ** argv) {
 			fprintf(stderr, "WARNING: --denoise does not work across --devices: writing the plain image\n");
 			cpu_config.denoise = 0;
 		}
+		if (cpu_config.firefly_filter && (gpu_config.enable_svgf || cpu_config.integrator == IntegratorType::AO)) {   // neither splats: their accumulate keeps no moments
+			fprintf(stderr, "WARNING: --firefly-filter needs plain path tracing (no SVGF, no AO integrator): ignored, writing the plain image\n");
+			cpu_config.firefly_filter = 0;
+		}
+		if (cpu_config.firefly_filter && cl.devices.size() > 1) {   // (the tiers are not gathered)
+			fprintf(stderr, "WARNING: --firefly-filter does not work across --devices: writing the plain image\n");
+			cpu_config.firefly_filter = 0;
+		}
 		if (!cl.sample_map.empty() && cl.devices.size() > 1) { fprintf(stderr, "WARNING: --sample-map does not work across --devices: ignored\n"); cl.sample_map.clear(); }
 		noise.active = cpu_config.noise_target > 0.0f;
 		noise.adaptive = noise.active && cpu_config.adaptive_sampling != 0;
@@ -399,6 +431,33 @@ int main(int argc, char ** argv) {
 		if (pathtracer) noise.report(*pathtracer, integrator->sample_index, cl.noise_map, integrator->screen_pitch, integrator->screen_width, integrator->screen_height);
 		if (pathtracer) noise.report_samples(*pathtracer, cl.sample_map, integrator->screen_pitch, integrator->screen_width, integrator->screen_height);
 
+		const bool resolve = pathtracer && cpu_config.firefly_filter;
+		if (resolve) {
+			auto save_rgb = [&](const std::string & file, const std::vector<float> & rgba) {
+				std::vector<Vector3> rgb(rgba.size() / 4);
+				for (size_t i = 0; i < rgb.size(); i++) rgb[i] = Vector3(rgba[4 * i], rgba[4 * i + 1], rgba[4 * i + 2]);
+				std::string error;
+				if (!Exporters::save(file, integrator->screen_pitch, integrator->screen_width, integrator->screen_height, rgb, &error)) die(error);
+			};
+			if (!cl.firefly_unfiltered.empty()) { save_rgb(cl.firefly_unfiltered, integrator->read_framebuffer()); printf("Wrote %s\n", cl.firefly_unfiltered.c_str()); }
+			auto t2 = std::chrono::steady_clock::now();
+			const std::vector<float> resolved = pathtracer->resolve_fireflies();
+			double held = 0.0, kept = 0.0;   // over the valid pixels, in luminance
+			std::vector<float> plane(resolved.size() / 4, 0.0f);
+			for (int y = 0; y < integrator->screen_height; y++) for (int x = 0; x < integrator->screen_width; x++) {
+				const size_t i = size_t(y) * integrator->screen_pitch + x;
+				plane[i] = resolved[4 * i + 3];
+				if (resolved[4 * i + 3] >= 0.0f) { held += resolved[4 * i + 3]; kept += 0.299 * resolved[4 * i] + 0.587 * resolved[4 * i + 1] + 0.114 * resolved[4 * i + 2]; }
+			}
+			printf("Firefly filter: %d tiers from %g, support %g; %.3f %% of the luminance held back; resolve %.1f ms\n", cpu_config.firefly_tiers, cpu_config.firefly_start, cpu_config.firefly_support,
+			       held + kept > 0.0 ? 100.0 * held / (held + kept) : 0.0, seconds_since(t2) * 1e3);
+			if (!cl.firefly_map.empty()) {
+				if (!EXRExporter::save_luminance(cl.firefly_map, integrator->screen_pitch, integrator->screen_width, integrator->screen_height, plane)) die("failed to write '" + cl.firefly_map + "'");
+				printf("Wrote %s\n", cl.firefly_map.c_str());
+			}
+			if (cpu_config.denoise) { if (rt_set_denoise_source(integrator->ctx, RT_DENOISE_SOURCE_RESOLVED) != RT_OK) die(std::string("ERROR: ") + rt_last_error(integrator->ctx)); }
+			else save_rgb(cpu_config.output_filename, resolved);
+		}
 		if (pathtracer && cpu_config.denoise) {
 			if (!cl.denoise_noisy.empty()) {
 				std::vector<float> rgba = integrator->read_framebuffer();
@@ -411,7 +470,7 @@ int main(int argc, char ** argv) {
 			auto t2 = std::chrono::steady_clock::now();
 			pathtracer->save_denoised_image(cpu_config.output_filename);
 			printf("Denoised: %d iterations, filter and export %.1f ms\n", cpu_config.denoise_iterations, seconds_since(t2) * 1e3);
-		} else integrator->save_image(cpu_config.output_filename);
+		} else if (!resolve) integrator->save_image(cpu_config.output_filename);
 		printf("Wrote %s\n", cpu_config.output_filename.c_str());
 	} catch (const std::exception & e) {
 		die(std::string("ERROR: ") + e.what());

@@ -168,6 +168,9 @@ const char * rt_version(void);
  *      (still 17: rt_read_sky_tables -- a new entry point; the read-back of the sky's sampling tables)
  *      (still 17: rt_denoise, rt_read_denoised, rt_denoise_timed, rt_denoise_images -- new entry points and a parameter struct of their own; the
  *      still-image denoiser, which runs only when called)
+ *      (still 17: rt_set_firefly_cascade, rt_get_firefly_cascade, rt_read_firefly_cascade, rt_resolve_fireflies, rt_read_resolved, rt_resolve_fireflies_timed,
+ *      rt_set_denoise_source, rt_get_denoise_source, rt_accumulate_cascade_frames, rt_resolve_fireflies_images -- new entry points and a parameter struct of their
+ *      own; the firefly filter, off until it is set)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
 #define RT_ABI_VERSION 17
 int rt_abi_version(void);
@@ -688,6 +691,58 @@ int rt_read_denoised(rt_context * ctx, float * dst);
  * *out_count entries are written, capacity must be at least iterations + 1 (or 2). tiled: as rt_denoise_images. For measurements (tools/denoise_cost.py). */
 int rt_denoise_timed(rt_context * ctx, const rt_denoise_params * params, int tiled, float * kernel_ms, size_t capacity, size_t * out_count);
 
+/* ---- firefly filter ------------------------------------------------------*/
+/* Tiered accumulation with a reweighted resolve, after Zirr, Hanika and Dachsbacher 2018, "Re-weighting firefly samples". Off until rt_set_firefly_cascade; while
+ * it is off a context launches exactly the kernels it launched before these calls existed and allocates nothing for them.
+ * While it is on, every RADIANCE sample an accumulate kernel folds into the mean is also splatted into `tiers` (K) images beside the moments image, per pixel
+ * S_j = (sum w r, sum w g, sum w b, sum w), tier j standing for the luminance b_j = start * 8^j. All float32, IEEE division, no contraction:
+ *   L = luminance(sample.rgb); a sample whose L is not finite is not splatted
+ *   lo = start; j = 0; while (L >= lo * 8 && j < K - 1) { lo *= 8; j++; }
+ *   j == K - 1 or L <= lo:  S_j += (rgb, 1)
+ *   otherwise, hi = lo * 8: wl = clamp((lo / L - lo / hi) / (1 - lo / hi), 0, 1);  S_j += wl * (rgb, 1);  S_j+1 += (1 - wl) * (rgb, 1)
+ * so the tiers of a pixel sum to the sum of its samples (nothing is clamped away), sum_j W_j is its sample count, and one splat puts at most b_j of luminance into
+ * a tier below the top one. The tiers follow the mean and the moments: a fold with index <= 1 (sample 0 sets the mean, sample 1 overwrites it) zeroes the pixel's
+ * tiers before its splat, and whatever zeroes the moments image (rt_set_noise_estimate, a change of the pixel set) zeroes the tiers; rt_resize gives them the new
+ * size, zeroed. Mean, moments and final image are the same bits with the cascade on and off. SVGF frames and the AO integrator never splat.
+ * rt_set_firefly_cascade: params NULL switches it off and frees the tiers. Completes the work in flight; the tiers are allocated and zeroed on switching on and
+ * on every change of `tiers` or `start` (the samples folded before are not in them: restart the progression). tiers * 16 B per pixel of the pitched frame: about
+ * 200 MB at 1920 x 1080 with 6 tiers. RT_ERROR_NOT_READY while the noise estimate is off (switching the estimate off switches the cascade off as NULL does: tiers and resolved image are freed);
+ * RT_ERROR_INVALID_ARG for tiers outside 2..8, start not finite and positive, support not finite and above 1. A refused call leaves the previous state in force.
+ * rt_get_firefly_cascade: 1 and *out (may be NULL) while it is on, else 0. rt_read_firefly_cascade: the tiers, `tiers` images of pitch*height float4 one behind
+ * the other (capacity: floats), after the work in flight.
+ *
+ * rt_resolve_fireflies, on the whole frame, float32, sums in the stated order:
+ *   valid(q)  w(q) >= 1 (the moments image), the mean's r, g, b finite, all tiers finite
+ *   for a valid p, N = w(p):  A_j = sum of W_j(q) over the valid q of the 3 x 3 neighbourhood inside the image, in row order
+ *     n_j = (A_j-1 + A_j) + A_j+1, A_-1 = A_K = 0;   R = S_0.rgb (r_0 = 1);   for j = 1 .. K - 1 in order, b_j = start * 8^j:
+ *     rc = clamp((n_j - 1) / (support - 1), 0, 1);  rcol = min(1, luminance(R) / b_j);  r_j = max(rc, rcol);  R += r_j * S_j.rgb
+ *   out(p) = (R / N, luminance(T - R) / N), T = sum_j S_j.rgb in tier order: .w is the luminance that was held back
+ *   an invalid p gets the final image's pixel with .w = -1, and is never counted in a neighbourhood
+ * The estimator is consistent, not unbiased: for a tier of positive probability n_j grows with N, so r_j -> 1.
+ * It completes the work in flight and writes one result image of the context's (allocated at the first call, freed by rt_resize): no accumulator, no moments, no
+ * tiers and not the final image; rendering goes on afterwards as if it had not been called. support: the kappa above (> 1, finite; the host's default 4).
+ * RT_ERROR_NOT_READY, each with its own message, while the cascade is off, while SVGF is on, and when no pixel is valid.
+ * rt_read_resolved: the last successful resolve, pitch*height float4; RT_ERROR_NOT_READY without one.
+ * rt_resolve_fireflies_timed: the resolve with a HIP event pair around its kernel, *kernel_ms its time; tiled as rt_resolve_fireflies_images.
+ * rt_set_denoise_source: RT_DENOISE_SOURCE_RESOLVED makes rt_denoise take its colour image from the last resolve instead of the RADIANCE mean (the moments stay the
+ * measured ones: a firefly's pixel carries a large variance and accepts its neighbours); rt_denoise then answers RT_ERROR_NOT_READY when there is no resolve or
+ * the frame has been folded into or zeroed since. No denoise kernel differs.
+ * (Additions that change no struct and no call: RT_ABI_VERSION stays.)                                                                              */
+typedef struct rt_firefly_params {
+	int32_t tiers;     /* 2..8; the host's default: 6 */
+	float   start;     /* b_0 > 0; the host's default: 1 */
+	float   support;   /* kappa > 1, what rt_resolve_fireflies_images and the host take as default; the host's default: 4 */
+} rt_firefly_params;
+enum { RT_DENOISE_SOURCE_MEAN = 0, RT_DENOISE_SOURCE_RESOLVED = 1 };
+int rt_set_firefly_cascade(rt_context * ctx, const rt_firefly_params * params);
+int rt_get_firefly_cascade(const rt_context * ctx, rt_firefly_params * out);
+int rt_read_firefly_cascade(rt_context * ctx, float * dst, size_t capacity);
+int rt_resolve_fireflies(rt_context * ctx, float support);
+int rt_read_resolved(rt_context * ctx, float * dst);
+int rt_resolve_fireflies_timed(rt_context * ctx, float support, int tiled, float * kernel_ms);
+int rt_set_denoise_source(rt_context * ctx, int source);
+int rt_get_denoise_source(const rt_context * ctx);
+
 /* Kulla-Conty LUTs as computed on the device at first use (kernel_integrate_* /
  * kernel_average_*, CUDA/KullaConty.h:83-240): 16^3, 16^3, 16^2, 16^2, 32^2, 32 floats.
  * Any pointer may be NULL. Synchronous.                                                     */
@@ -897,6 +952,19 @@ int rt_accumulate_list_frames(rt_context * ctx, const int32_t * first_sample, co
  * by rt_denoise. Leaves the context's own images untouched.                                                                                              */
 int rt_denoise_images(rt_context * ctx, int width, int height, int pitch, const float * colour, const float * moments, const float * albedo, const float * normal,
                       const float * position, const float * fallback, const float * eye, const rt_denoise_params * params, int tiled, float * out);
+/* rt_accumulate_frames and rt_accumulate_list_frames in one, with the cascade: ONE launch of the production launcher (rt_set_firefly_cascade's kernels) on
+ * explicit images. merged = 0: the batch form (one submission, <= 16 samples, frames not cleared); merged = 1: the merged group; list != NULL (merged must be 1):
+ * the group over a pixel list, checked as by rt_accumulate_list_frames. tiers: params->tiers images of pitch*height float4 one behind the other, in and out.
+ * moments is required. Everything else as in those two probes; params->support is checked and not used.                                            */
+int rt_accumulate_cascade_frames(rt_context * ctx, int merged, const int32_t * first_sample, const int32_t * sample_count, size_t submissions, float * frames,
+                                 float * accumulator, float * moments, const uint32_t * list, size_t list_count, const rt_firefly_params * params, float * tiers,
+                                 uint32_t sentinel, float * final_image);
+/* rt_resolve_fireflies' kernel on explicit images of a size of the caller's (synchronous; the context needs no frame and no scene): mean, moments and fallback are
+ * pitch*height float4, tiers params->tiers such images one behind the other, pitch >= width, pitch * height below 2^26. out: pitch*height float4, read first: what
+ * the kernel does not write -- the padding columns -- comes back as the caller gave it. tiled = 1: the W of a tile's halo staged in LDS (what rt_resolve_fireflies
+ * runs), 0: the plain kernel; the two agree bit for bit.                                                                                            */
+int rt_resolve_fireflies_images(rt_context * ctx, int width, int height, int pitch, const float * mean, const float * moments, const float * tiers, const float * fallback,
+                                const rt_firefly_params * params, int tiled, float * out);
 /* ---- fog volume ---------------------------------------------------------------------------------------------------
  * One scene-wide homogeneous medium inside an axis-aligned box, with multiple scattering and light sampling at every scatter vertex. Off
  * until a volume is set; while it is off a context launches exactly the kernels it launched before these calls existed. (Additions that
