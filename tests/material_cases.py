@@ -9,7 +9,11 @@ shading normal is not the geometric one, and the curvature is not zero.
 
 Hits are synthetic, as in sort_cases: (instance, triangle, t, u, v) from the scene's tables, directions uniform over the sphere (so
 about half the entries arrive at the back face). Entries are built in the state the sort leaves them: at bounce 0 the throughput and
-cone words hold the sentinel, outside a medium the medium word holds it, the padding holds it."""
+cone words hold the sentinel, outside a medium the medium word holds it, the padding holds it.
+
+The variants of the launch (test_gpu_material_variants.py on the device, their reference-only checks in test_material.py) have setups of their
+own (SKY_SETUPS: the sky takes a share of the light samples), a world of their own (VariantWorld, at the end of this file) and their launches
+(sky_launches, sky_length_launches, sky_lights_launch, map_launches, sky_map_launches). PLAIN_SETUPS are the setups the oracle can be asked about."""
 import ctypes
 
 import numpy as np
@@ -53,8 +57,19 @@ SETUPS = [
     Setup("smooth", smooth=True),
     Setup("frames_off", aov_mask=1),
     Setup("bc1_present", bc1=True),
+    # the _sky instances (test_gpu_material_variants.py): the sky takes a share of the light samples
+    Setup("sky_share_0.25", sky_sampling=0.25),
+    Setup("sky_share_0.5", sky_sampling=0.5),
+    Setup("sky_share_1", sky_sampling=1.0),
+    Setup("sky_share_0.5_mis_off", {"enable_multiple_importance_sampling": 0}, sky_sampling=0.5),
+    Setup("sky_share_0.5_no_emitters", sky_sampling=0.5, lights=False),
+    Setup("sky_share_0.5_1x1", sky="one", sky_sampling=0.5),
+    Setup("sky_share_0.5_svgf", {"enable_svgf": 1}, sky_sampling=0.5),
+    Setup("sky_share_0.5_bc1", bc1=True, sky_sampling=0.5),
 ]
 SETUP = {s.name: s for s in SETUPS}
+SKY_SETUPS = tuple(s for s in SETUPS if s.sky_sampling > 0)
+PLAIN_SETUPS = tuple(s for s in SETUPS if not s.sky_sampling > 0)   # what the oracle, which samples no sky, can be asked about
 
 
 class World(sort_cases.World):
@@ -370,4 +385,196 @@ def light_table_launches(world):
     assert 2 <= good.size <= 4, good
     for k, launch in enumerate(out):
         launch.entries.triangle[:] = np.random.default_rng(2110 + k).choice(good, launch.entries.n)
+    return out
+
+
+# ---- the variants of the launch: _sky, _nmap, _sky_nmap (test_gpu_material_variants.py; their left-out caps in test_material.py) -------
+
+TILT, FLAT, INWARD = (200, 90, 180), (128, 128, 255), (128, 128, 0)   # the constant normal maps: a strong tilt; the unperturbed normal within 8 bits; t.z = -1 (the view guard fires)
+MAP_TEXELS = (FLAT, TILT, INWARD)   # in upload order, behind the scene's own textures (and the BC1 one of a bc1 setup)
+
+
+class VariantWorld(World):
+    """World plus what the variants' launches need and World lacks (its dielectric and conductor are untransformed spheres, every triangle of
+    it has texture coordinates with a determinant): a rough dielectric and a rough conductor quad under a rotation and a non-unit scale, whose
+    triangles (quad.obj) carry non-degenerate texture coordinates, and a conductor mesh without texture coordinates (uv_det == 0: the mapped
+    normal falls back). Mirrored coordinates (uv_det < 0) World has already: the loader stores v as 1 - v, so every quad.obj triangle has
+    them, next to the spheres' uv_det > 0. Hits are synthetic, so any instance goes with any triangle: a launch picks its triangles by
+    determinant (triangles_where). Three constant RGBA8 textures lie behind the scene's own: MAP_TEXELS."""
+    EXTRA_SHAPES = World.EXTRA_SHAPES + (
+        '<shape type="obj"><string name="filename" value="quad.obj"/><transform name="toWorld"><scale value="0.6"/><rotate y="1" angle="40"/><rotate x="1" angle="-50"/>'
+        '<translate x="-2.4" y="1.4" z="-1.5"/></transform><bsdf type="roughdielectric"><float name="intIOR" value="1.5"/><float name="alpha" value="0.3"/></bsdf></shape>'
+        '<shape type="obj"><string name="filename" value="quad.obj"/><transform name="toWorld"><scale value="1.7"/><rotate z="1" angle="25"/><rotate x="1" angle="70"/>'
+        '<translate x="0.5" y="1.8" z="-3.0"/></transform><bsdf type="roughconductor"><string name="material" value="Cu"/><float name="alpha" value="0.2"/></bsdf></shape>'
+        '<shape type="obj"><string name="filename" value="bare.obj"/><transform name="toWorld"><scale value="0.8"/><rotate y="1" angle="-35"/>'
+        '<translate x="3.0" y="0.6" z="1.0"/></transform><bsdf type="roughconductor"><string name="material" value="Au"/><float name="alpha" value="0.25"/></bsdf></shape>')
+
+    def prepare(self, directory):
+        super().prepare(directory)
+        (directory / "bare.obj").write_text("v -1 0 -1\nv 1 0 -1\nv 1 0 1\nv -1 0.3 1\nf 1 3 2\nf 1 4 3\n")   # no vt: the loader leaves the coordinates 0; the first triangle is level and faces +y
+
+    def __init__(self, grt, oracle, directory, device):
+        super().__init__(grt, oracle, directory, device)
+        tri = np.asarray(self.view.keep["triangles"], np.float32).reshape(-1, 24).astype(np.float64)
+        self.uv_det = tri[:, 20] * tri[:, 23] - tri[:, 22] * tri[:, 21]
+        e1, e2 = tri[:, 3:6], tri[:, 6:9]
+        with np.errstate(all="ignore"):
+            self.squareness = np.linalg.norm(np.cross(e1, e2), axis=1) / (np.linalg.norm(e1, axis=1) * np.linalg.norm(e2, axis=1))
+        assert (self.uv_det > 0).sum() > 100 and (self.uv_det < 0).sum() >= 4 and (self.uv_det == 0).sum() >= 2, "the scene lacks a sign of uv_det"
+        ids = np.asarray(self.view.keep["mesh_material_ids"], np.int32)
+        rows = np.asarray(self.view.keep["mesh_transforms"], np.float32).reshape(-1, 3, 4).astype(np.float64)
+        scale = np.linalg.norm(rows[:, 0, :3], axis=1)
+        rotated = np.array([not np.allclose(m[:, :3], np.diag(np.diag(m[:, :3])), atol=1e-6) for m in rows])
+        self.transformed_instance = rotated & (np.abs(scale - 1.0) > 0.1)
+        for kind in (DIELECTRIC, CONDUCTOR):
+            mine = self.instances[kind]
+            assert self.transformed_instance[mine].any() and (~self.transformed_instance[mine]).any(), "type %d: no instance under a rotation and a scale, or none without" % kind
+        self.instance_material = ids
+        self.map_base = None
+        if self.ctx is not None:
+            self.upload_textures(False)
+
+    def upload_textures(self, with_bc1):
+        """World's, with the three constant maps behind: 4 x 4 RGBA8 images with their whole mip chain, every texel the same."""
+        from texture_cases import bc1_texture
+        from test_gpu_texture_unit import TextureDesc
+        scene_textures = self.pt.textures()
+        extra = [bc1_texture(8, 8, 7)] if with_bc1 else []
+        self._maps = [np.ascontiguousarray(np.tile(np.array(list(c) + [255], np.uint8), 16 + 4 + 1)) for c in MAP_TEXELS]
+        count = len(scene_textures) + len(extra) + len(self._maps)
+        descs = (TextureDesc * count)()
+        for i, (texels, w, h, levels) in enumerate(scene_textures):
+            descs[i].texels, descs[i].width, descs[i].height, descs[i].mip_levels, descs[i].format = texels.ctypes.data, w, h, levels, 0
+            descs[i].lod_width, descs[i].lod_height = self.pt.texture_lod_size(i)
+        k = len(scene_textures)
+        for t in extra:
+            d = descs[k]; k += 1
+            d.texels, d.width, d.height, d.mip_levels, d.format = t.data.ctypes.data, t.width, t.height, t.mip_levels, t.format
+        self.map_base = k
+        for texels in self._maps:
+            d = descs[k]; k += 1
+            d.texels, d.width, d.height, d.mip_levels, d.format = texels.ctypes.data, 4, 4, 3, 0
+        lib = self.lib
+        lib.rt_set_texture_expansion.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        lib.rt_upload_textures.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+        assert lib.rt_set_texture_expansion(self.ctx, 0 if with_bc1 else 1) == 0, lib.rt_last_error(self.ctx)
+        assert lib.rt_upload_textures(self.ctx, descs, count) == 0, lib.rt_last_error(self.ctx)
+        self.textures_compressed = with_bc1
+
+    def triangles_where(self, what):
+        """Triangle ids by their texture coordinates: "regular" (uv_det > 0), "mirrored" (uv_det < 0), "degenerate" (uv_det == 0); none a sliver."""
+        sign = {"regular": self.uv_det > 0, "mirrored": self.uv_det < 0, "degenerate": self.uv_det == 0}[what]
+        return np.nonzero(sign & (self.squareness > 0.2))[0].astype(np.int32)
+
+    def set_maps(self, tables, which):
+        """Puts normal maps in force: `which` maps a material type to one of MAP_TEXELS, for that type's materials that can take it -- the
+        untextured ones of the diffuse and plastic slots (texel known, albedo constant), the transformed instances' of the dielectric and conductor
+        slots (the spheres stay unmapped: every launch holds both kinds of hit). On the device and in `tables` (map_ids, map_texels) for
+        material_reference.evaluate. An empty `which` clears them."""
+        base = self.map_base if self.map_base is not None else len(self.pt.textures())
+        ids = np.full(self.materials.shape[0], -1, np.int32)
+        textured = self.materials[:, 3].view(np.int32) >= 0
+        for kind, texel in which.items():
+            for material in np.unique(self.instance_material[self.instances[kind]]):
+                if kind in (DIFFUSE, PLASTIC):
+                    takes = not textured[material]
+                else:
+                    takes = self.transformed_instance[(self.instance_material == material)].all()
+                if takes:
+                    ids[material] = base + MAP_TEXELS.index(texel)
+        if self.ctx is not None:
+            assert self.grt.upload_material_normal_maps(self.ctx, ids) == 0, self.lib.rt_last_error(self.ctx)
+        tables.map_ids = ids if which else None
+        tables.map_texels = {base + k: c for k, c in enumerate(MAP_TEXELS)}
+        for k in range(base):
+            tables.map_texels[k] = "varied"
+        return ids
+
+
+def _restrict(world, launch, what, seed, meshes=None):
+    """The launch with its triangles drawn from triangles_where(what) (and its instances from `meshes`)."""
+    rng = np.random.default_rng(seed)
+    launch.entries.triangle[:] = rng.choice(world.triangles_where(what), launch.entries.n)
+    if meshes is not None:
+        launch.entries.mesh[:] = rng.choice(np.asarray(meshes, np.int32), launch.entries.n)
+    return launch
+
+
+def sky_launches(world, setup):
+    """The _sky instances under a setup with a sky share: under sky_share_0.5 all four slots at bounce 0 and 2 (1500 entries) and merged (2500);
+    under the others bounce 1 of the diffuse and the conductor slot and the merged plastic one."""
+    tag = "sky"
+    if setup.name == "sky_share_0.5":
+        out = []
+        for slot in range(4):
+            out += [per_bounce(world, tag, slot, 1500, b, seed=4000 + 10 * slot + b) for b in (0, 2)]
+            out.append(merged(world, tag, slot, 2500, seed=4050 + slot))
+        return out
+    k = [s.name for s in SKY_SETUPS].index(setup.name)
+    return [per_bounce(world, tag, 0, 1500, 1, seed=4100 + 10 * k), per_bounce(world, tag, 3, 1500, 1, seed=4101 + 10 * k), merged(world, tag, 1, 2500, seed=4102 + 10 * k)]
+
+
+SKY_LENGTHS = (1, 64, 257)
+
+
+def sky_length_launches(world):
+    """Order and structure of the _sky instances (sky_share_0.5): one entry, one wave, a workgroup and one entry; per bounce and merged."""
+    out = []
+    for k, n in enumerate(SKY_LENGTHS):
+        out.append(per_bounce(world, "sky_length", (2 * k) % 4, n, 1, seed=4200 + k, slots=1))
+        out.append(merged(world, "sky_length", (2 * k + 1) % 4, n, seed=4210 + k))
+    return out
+
+
+def sky_lights_launch(world):
+    """A LightsWorld launch (meshes65: the light tables in global memory) for a _sky instance."""
+    return light_table_launches(world)[1]
+
+
+def lights_world_sky(world, share, sky):
+    """Gives a LightsWorld the sky `sky` ((H, W, 4) float32) and a sky share: in the oracle's view, on the device, and in world.tables."""
+    import sky_sampling_reference as sky_ref
+    s, k = world.view.scene, world.view.keep
+    k["sky"] = sky; s.sky = sky.ctypes.data; s.sky_height, s.sky_width = sky.shape[:2]; s.sky_scale = 1.0
+    if world.ctx is not None:
+        lib = world.lib
+        lib.rt_set_sky_sampling.argtypes = [ctypes.c_void_p, ctypes.c_float]
+        assert lib.rt_set_sky(world.ctx, sky.ctypes.data, sky.shape[1], sky.shape[0], ctypes.c_float(1.0)) == 0, lib.rt_last_error(world.ctx)
+        assert lib.rt_set_sky_sampling(world.ctx, share) == 0, lib.rt_last_error(world.ctx)
+    t = world.tables
+    t.sky = np.asarray(sky, np.float32); t.sky_scale = 1.0
+    t.sky_share = float(np.float32(share)); t.sky_tables = sky_ref.Tables(t.sky)
+    return t
+
+
+def map_launches(world):
+    """The _nmap instances (SKY == 0, under svgf_on): (maps, launch) pairs, `maps` what set_maps takes. The tilt map on the dielectric and the
+    conductor slot (bounce 0, 2, merged) and on the untextured diffuse and plastic materials; the two other constant maps on the conductor
+    slot; the conductor slot on mirrored triangles only and on triangles without texture coordinates only. The general launches draw from
+    the regular and the mirrored triangles alike."""
+    out = []
+    both = np.concatenate([world.triangles_where("regular"), world.triangles_where("mirrored")])
+    for slot in (2, 3, 0, 1):
+        maps = {SLOT_TYPES[slot]: TILT}
+        for launch in [per_bounce(world, "nmap", slot, 1500, b, seed=4300 + 10 * slot + b) for b in (0, 2)] + [merged(world, "nmap", slot, 1500, seed=4350 + slot)]:
+            launch.entries.triangle[:] = np.random.default_rng(4360 + slot).choice(both, launch.entries.n)
+            out.append((maps, launch))
+    for k, (texel, label) in enumerate(((FLAT, "flat"), (INWARD, "inward"))):
+        launch = per_bounce(world, "nmap_" + label, 3, 1500, 0, seed=4400 + k)
+        launch.entries.triangle[:] = np.random.default_rng(4410 + k).choice(both, launch.entries.n)
+        out.append(({CONDUCTOR: texel}, launch))
+    mapped_conductors = [i for i in world.instances[CONDUCTOR] if world.transformed_instance[i]]
+    out.append(({CONDUCTOR: TILT}, _restrict(world, per_bounce(world, "nmap_mirrored", 3, 1500, 0, seed=4420), "mirrored", 4421, mapped_conductors)))
+    out.append(({CONDUCTOR: TILT}, _restrict(world, per_bounce(world, "nmap_degenerate", 3, 1500, 0, seed=4430), "degenerate", 4431, mapped_conductors)))
+    return out
+
+
+def sky_map_launches(world):
+    """The _sky_nmap instances (sky_share_0.5, the tilt map): the diffuse and the conductor slot, bounce 1 per bounce and merged."""
+    out = []
+    both = np.concatenate([world.triangles_where("regular"), world.triangles_where("mirrored")])
+    for slot in (0, 3):
+        for launch in (per_bounce(world, "sky_nmap", slot, 1500, 1, seed=4500 + slot), merged(world, "sky_nmap", slot, 1500, seed=4510 + slot)):
+            launch.entries.triangle[:] = np.random.default_rng(4520 + slot).choice(both, launch.entries.n)
+            out.append(({SLOT_TYPES[slot]: TILT}, launch))
     return out

@@ -11,7 +11,7 @@ Structure (exact, every launch; check_structure):
   set exactly where last_pdf was written; INSIDE_MEDIUM set exactly where the medium word was written, which then names a medium of the
   table; the cone words written exactly with mip-mapping;
 * a shadow record is written whole; its pixel word carries RT_SHADOW_FLAG_BOUNCE_0 exactly in the merged form at bounce 0;
-* without next-event estimation (off, or no lights) there is no shadow ray;
+* without next-event estimation (off, or neither lights nor a sky share) there is no shadow ray;
 * frames and g-buffers: a pixel holds the sentinel unless a bounce-0 entry names it; a frame the context has disabled, and the g-buffers
   without SVGF, hold it everywhere; a pixel is written whole (four, two, two words) and in NORMAL, POSITION and the g-buffers together;
 * merged form: the statistics rows equal the shadow rays counted per (submission, bounce) from the matched records, every other cell is 0.
@@ -185,7 +185,7 @@ def check_structure(name, tables, launch, out):
         i = s_index[_first(flagged != expected)]
         raise AssertionError("%s: entry %d (pixel %d, bounce %d, %s form): RT_SHADOW_FLAG_BOUNCE_0 is %s" % (
             name, i, e.pixel[i], bounce[i], "merged" if launch.merged else "per-bounce", "set" if flagged[_first(flagged != expected)] else "clear"))
-    nee = cfg["enable_next_event_estimation"] != 0 and tables.lights_total_weight > 0.0
+    nee = cfg["enable_next_event_estimation"] != 0 and (tables.lights_total_weight > 0.0 or tables.sky_share > 0.0)   # (a sky share: light samples without emitters)
     if not nee:
         assert out.counters[1] == 0, "%s: %d shadow rays without next-event estimation" % (name, out.counters[1])
 
@@ -371,6 +371,11 @@ MEASURED = {
     "shadow_direction": (6.92e-07, "default/mixed_diffuse_bounce0_3000"),
     "shadow_distance":  (4.22e-07, "mis_off/small_diffuse_bounce0_700"),
     "illumination":     (0.00453, "default/mixed_conductor_merged_4000"),
+    # the throughput on the launches of material_cases.VariantWorld (test_material.py: test_variant_world_bound_is_four_times_the_worst_case)
+    "variant_throughput": (0.00242, "svgf_on/nmap_flat_conductor_bounce0_1500"),
+    # the NORMAL frame of a mapped hit: material_reference.mapped_normal32, the float32 restatement of normal_map_perturb, against float64
+    # (test_material.py: test_mapped_normal_bound_is_four_times_the_float32_restatement); absolute, per component
+    "mapped_normal":    (2.02e-06, "svgf_on/nmap_inward_conductor_bounce0_1500"),
 }
 BOUNDS = {q: 4.0 * v[0] for q, v in MEASURED.items()}
 
@@ -465,7 +470,10 @@ def compare_with_reference(name, tables, launch, out, at, r, bounds):
     f = out.shadow_out[shadow_at[index]].view(np.float32).astype(np.float64)
     measure("shadow_origin", _point(f[:, 0:3], r.shadow_origin[index]), index)
     measure("shadow_direction", np.abs(f[:, 3:6] - r.shadow_direction[index]).max(axis=1), index)
-    measure("shadow_distance", _relative(f[:, 6], r.shadow_distance[index], 1e-30), index)
+    # (a sky entry's ray runs to infinity: RT_INFINITY exactly, and a finite length for every emitter entry)
+    to_sky = np.isposinf(r.shadow_distance[index])
+    outcome(np.isin(np.arange(e.n), index[np.isposinf(f[:, 6]) != to_sky]), "max_distance is +inf for a shadow ray to an emitter, or finite for one to the sky")
+    measure("shadow_distance", _relative(f[~to_sky, 6], r.shadow_distance[index][~to_sky], 1e-30), index[~to_sky])
     plain = ~r.textured[index]
     measure("illumination", _per_channel(f[plain, 7:10], r.illumination[index][plain]), index[plain])
 

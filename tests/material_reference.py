@@ -16,11 +16,26 @@ to this reference in everything but their albedo, throughput and illumination, a
 
 `evaluate` also says how close every deciding comparison of an entry comes to its threshold: entering_material (dot(direction, geometric
 normal) < 0), omega_i.z <= 0, cos_theta_hit <= 0 and pdf_is_valid(light_pdf) of the light sample, and the BSDF's own branches and
-pdf_is_valid (bsdf_reference.py's replay: `near`). An entry is non-robust when one of them is within its margin."""
+pdf_is_valid (bsdf_reference.py's replay: `near`). An entry is non-robust when one of them is within its margin.
+
+The variants of the launch (kernels_shade.hip: the _sky and _nmap instances), composed from the modules that restate their parts:
+* a sky share s = tables.sky_share > 0 (next_event_estimation<1>): each allowed entry is routed in float32 as the kernel routes it -- to the
+  sky where DIM_NEE_LIGHT.x < s, else to the emitters on the rescaled number min((u - s) / (1 - s), 0x1.fffffep-1), whose light pdf carries
+  the factor 1 - s into pdf_is_valid and into the MIS weight. A sky entry takes its direction and cell pdf from the DIM_NEE_TRIANGLE pair
+  through the sky's tables (sky_sampling_reference.py), its radiance from sample_sky, light_pdf = s x pdf, valid when positive and finite,
+  and an infinite max_distance. With s >= 1 (a share of 1, or no emitters) every entry goes to the sky and no light table is read;
+* normal maps (the NMAP branch of shade_material): `map_ids`, one map per material (-1: none), and `map_texels`, per map its constant texel
+  (three bytes) or "varied". A mapped hit of a constant map shades with normal_map_reference.perturb on that texel -- every filter and level
+  of a constant 8-bit image returns it, so no fetch is restated -- in the BSDF frame, omega_i.z <= 0, next-event estimation, the NORMAL
+  frame and the g-buffer; the ray cone's curvature term and its dot(normal, direction) keep the interpolated normal. A hit of a varied map
+  has no reference value here (`varied`; rt_perturb_normals holds those) and counts as left out.
+Their deciding comparisons carry near flags of their own (near_sky, near_map), counted like the others."""
 import numpy as np
 
 import bsdf_reference
 import nee_reference
+import normal_map_reference
+import sky_sampling_reference
 from sort_reference import DIFFUSE, DIELECTRIC, _normalize, _oct_encode
 
 DIM_BSDF_0, DIM_BSDF_1, DIM_NEE_LIGHT, DIM_NEE_TRIANGLE = 5, 6, 3, 4   # Sampling.h:30-42
@@ -30,6 +45,16 @@ INVALID = -1
 # on top of the unit vectors' own (each component within 2^-24 relative of its float64 value after a normalisation of three roundings).
 DOT_MARGIN = 16 * 2.0 ** -24
 PDF_MARGIN = 1e-5   # relative, around pdf_is_valid's 1e-4: the light pdf is distance^2 / cosine, some twenty float32 operations
+ONE_BELOW_ONE = np.float32(np.nextafter(np.float32(1), np.float32(0)))   # 0x1.fffffep-1
+# How close to a border of its sky cell (in cells) a direction may lie before the float32 atan2f / acosf of sky_cell may find the neighbour:
+# their error is a few 2^-24 of a turn, times the 64 to 1024 cells of a row.
+SKY_CELL_MARGIN = 1e-4
+T_LENGTH_MARGIN = 1e-3   # relative, around normal_map_perturb's |t|^2 > 1e-8 |dpdu|^2
+# A sampled direction that grazes the shading plane: G2's `o_back` decides on the sign of omega_o.z, the diffuse lobe and the pdf are proportional
+# to it, so its float32 error of about 2^-23 is DOT_MARGIN / |omega_o.z| of the throughput. bsdf_checks.py calls |omega_o.z| < 1e-3 grazing and holds
+# the value there to 1 only. A mapped normal leans against the surface, and the view guard pins omega_i.z at 1e-2 for every hit it moves: such
+# samples, rare in an unmapped launch, are a few per thousand mapped hits. They are flagged (mapped hits only) and left out.
+GRAZING = 1e-3
 
 
 class Result:
@@ -66,8 +91,32 @@ def _probes(materials, normal, direction, entering, pixel, sample, bounce, to_li
     return p
 
 
-def evaluate(world, tables, launch, bsdf_tables):
-    """The launch in float64. Per entry (N): alive (the set-up keeps it), continues, has_shadow, robust and the near_* masks; normal,
+def route(u, share):
+    """Where next_event_estimation<1> sends a light sample, in float32 as the kernel computes it: (to the sky, the rescaled number of the
+    emitters' half)."""
+    u = np.asarray(u, np.float32); s = np.float32(share)
+    with np.errstate(all="ignore"):
+        rescaled = np.minimum(((u - s) / (np.float32(1) - s)).astype(np.float32), ONE_BELOW_ONE)
+    return u < s, rescaled
+
+
+def map_records(tri, u, v, world_m, direction):
+    """The (N, 48) float64 records of normal_map_reference.frame / perturb for hits on (N, 24) triangles."""
+    rec = np.zeros((tri.shape[0], normal_map_reference.PROBE_IN))
+    rec[:, 0:24] = tri
+    rec[:, 24], rec[:, 25] = u, v
+    rec[:, 26:38] = world_m.reshape(-1, 12)
+    rec[:, 38:41] = direction
+    return rec
+
+
+def evaluate(world, tables, launch, bsdf_tables, sky_directions=None, sky_pdfs=None, map_ids=None, map_texels=None):
+    """The launch in float64. sky_directions (N, 3), sky_pdfs (N,): what to use in place of the reference's own inversion of the sky's
+    tables for the tail of a sky entry, where finite (the device test hands over the direction a launch wrote, which it holds to the
+    inversion separately, and rt_sky_pdf's value for it; an entry whose float64 cell has another pdf is flagged). map_ids, map_texels:
+    the normal maps (default: tables.map_ids, tables.map_texels where a test has set them). Further fields with a sky share: to_sky (the
+    route), u_emitter, sky_direction, sky_pdf, near_sky; with maps: mapped, varied, map_fallback, map_guarded, interpolated_normal, near_map.
+     Per entry (N): alive (the set-up keeps it), continues, has_shadow, robust and the near_* masks; normal,
     position (what the NORMAL and POSITION frames get at bounce 0), gnd (N, 4), gid (N, 2), gsp (N, 2) (the g-buffer rows under SVGF);
     cone_width, cone_angle and cone_angle_scale (what the angle's error is relative to); direction, origin, pdf, throughput (NaN rows
     for a textured hit), medium, allow_nee of the continuation ray; shadow_origin, shadow_direction, shadow_distance, illumination
@@ -104,15 +153,45 @@ def evaluate(world, tables, launch, bsdf_tables):
         sliver = np.sqrt((we1 * we1).sum(axis=1) * (we2 * we2).sum(axis=1)) / area
         facing = _dot(d, gn)
         entering = facing < 0
-        normal = np.where(entering[:, None], normal, -normal); curvature = np.where(entering, curvature, -curvature)
+        interpolated = np.where(entering[:, None], normal, -normal); curvature = np.where(entering, curvature, -curvature)
+        material_id = tables.material_ids[e.mesh]
+
+        # the NMAP branch: the shading normal of a mapped hit; `interpolated` stays what the ray cone reads
+        normal = interpolated
+        map_ids = getattr(tables, "map_ids", None) if map_ids is None else map_ids
+        map_texels = getattr(tables, "map_texels", None) if map_texels is None else map_texels
+        r.mapped = np.zeros(n, bool); r.varied = np.zeros(n, bool); r.near_map = np.zeros(n, bool); r.map_fallback = np.zeros(n, bool); r.map_guarded = np.zeros(n, bool)
+        if map_ids is not None and n:
+            entry_map = np.asarray(map_ids, np.int32)[material_id]
+            r.mapped = entry_map >= 0
+            normal = interpolated.copy()
+            for m in np.unique(entry_map[r.mapped]):
+                at = np.nonzero(entry_map == m)[0]
+                texel = map_texels[int(m)]
+                if isinstance(texel, str):   # "varied": the fetch is not restated
+                    r.varied[at] = True
+                    continue
+                rec = map_records(tri[at], u[at, 0], v[at, 0], world_m[at], d[at])
+                c = np.asarray(texel, np.float64)[None, :3] / 255.0   # (the byte over 255, as texel_to_float has it within float32 rounding)
+                shading, fallback, info = normal_map_reference.perturb(rec, np.repeat(c, at.size, axis=0))
+                normal[at] = shading
+                r.map_fallback[at] = fallback
+                r.map_guarded[at] = info["fired"]   # the view guard moved the mapped normal
+                fr = info["frame"]
+                close_guard = np.abs(info["cos_view"] - normal_map_reference.EPS) <= DOT_MARGIN
+                close_tangent = np.abs(fr["sin_tn"] ** 2 - 1e-8) <= T_LENGTH_MARGIN * 1e-8
+                close_side = ~(np.abs(_dot(fr["ng"], fr["n"])) > DOT_MARGIN * sliver[at])
+                degenerate = ~(np.isfinite(fr["det"]) & (fr["det"] != 0.0))
+                r.near_map[at] = ~degenerate & (close_tangent | (~fallback & (close_guard | close_side)))
+        r.interpolated_normal = interpolated
         omega_i_z = _dot(-d, normal)
         alive = omega_i_z > 0
         r.near_entering = ~(np.abs(facing) > DOT_MARGIN * sliver)
         r.near_alive = np.abs(omega_i_z) <= DOT_MARGIN
         r.alive, r.entering, r.normal, r.position, r.geometric_normal = alive, entering, normal, position, gn
-        term = 2.0 * curvature * np.abs(width) / _dot(normal, d)
+        term = 2.0 * curvature * np.abs(width) / _dot(interpolated, d)
         r.cone_width, r.cone_angle = width, angle_in - term
-        r.cone_angle_scale = np.abs(angle_in) + np.abs(term) * (1.0 + 1.0 / np.abs(_dot(normal, d)))
+        r.cone_angle_scale = np.abs(angle_in) + np.abs(term) * (1.0 + 1.0 / np.abs(_dot(interpolated, d)))
 
         # g-buffers (SVGF.cu as kernels_shade.hip: svgf_set_gbuffers)
         prev_m = tables.transforms_prev[e.mesh].astype(f64)
@@ -141,7 +220,9 @@ def evaluate(world, tables, launch, bsdf_tables):
         uniforms = [tables.random(DIM_BSDF_0, real, bounce, sample), tables.random(DIM_BSDF_1, real, bounce, sample)]
         probes = _probes(materials, normal, d, entering, real, sample, bounce)
         s64, _ = bsdf_reference.evaluate(kind, probes, bsdf_tables, eval=False, uniforms=uniforms)
+        r.sample_probes, r.sample_factor = probes, s64.value   # (what a float32 restatement of the BSDF's sample is handed, and float64's answer)
         r.near_sample = alive & s64.near
+        r.near_map |= r.mapped & ~r.map_fallback & alive & (s64.ok == 1) & (np.abs(_dot(s64.direction, normal)) < GRAZING)
         r.continues = alive & (s64.ok == 1)
         r.allow_nee = s64.allow_nee
         r.direction = s64.direction
@@ -159,39 +240,101 @@ def evaluate(world, tables, launch, bsdf_tables):
             r.medium = inside_in
 
         # next-event estimation (Pathtracer.cu:465-555): the light the random numbers select, then the tail
-        nee = (cfg["enable_next_event_estimation"] != 0) and tables.lights_total_weight > 0.0
-        r.has_shadow = np.zeros(n, bool); r.near_light = np.zeros(n, bool)
+        share = f64(np.float32(tables.sky_share)) if cfg["enable_next_event_estimation"] != 0 else 0.0   # the _sky instances: RtParams::sky_nee_share
+        emitters = tables.lights_total_weight > 0.0 and share < 1.0
+        nee = (cfg["enable_next_event_estimation"] != 0) and (tables.lights_total_weight > 0.0 or share > 0.0)
+        r.has_shadow = np.zeros(n, bool); r.near_light = np.zeros(n, bool); r.near_sky = np.zeros(n, bool); r.to_sky = np.zeros(n, bool)
         r.shadow_origin = np.full((n, 3), np.nan); r.shadow_direction = np.full((n, 3), np.nan); r.shadow_distance = np.full(n, np.nan); r.illumination = np.full((n, 3), np.nan)
+        r.u_emitter = np.full(n, np.nan, np.float32); r.sky_direction = np.full((n, 3), np.nan); r.sky_pdf = np.full(n, np.nan); r.light_pdf = np.full(n, np.nan)
         if nee and n:
             rl, rt = tables.random(DIM_NEE_LIGHT, real, bounce, sample), tables.random(DIM_NEE_TRIANGLE, real, bounce, sample)
-            light = nee_reference.sample_lights(nee_reference.Tables(tables.view), np.concatenate([rl, rt], axis=1))
-            hit = _offset(position, light.point - position, gn)
-            light_point = _offset(light.point, hit - light.point, light.normal)
-            to_light = light_point - hit
-            distance = np.sqrt((to_light * to_light).sum(axis=1))
-            to_light = to_light / distance[:, None]
-            cos_light = np.abs(_dot(to_light, light.normal))
+            allowed = alive & s64.allow_nee
+            to_sky = np.zeros(n, bool)
+            u_light = rl[:, 0].astype(f64)
+            if share > 0.0:
+                to_sky, r.u_emitter = route(rl[:, 0], share)
+                if not emitters:
+                    to_sky = np.ones(n, bool)
+                rl = rl.copy(); rl[:, 0] = np.where(to_sky, 0.0, r.u_emitter)
+            selection = f64(np.float32(1) - np.float32(share))   # `selection` of nee_connect<true>: 1.0f - share
+            r.to_sky = to_sky
+
+            # the emitters' half: the light the (rescaled) random numbers select, then both epsilon offsets
+            origin = np.full((n, 3), np.nan); to_light = np.full((n, 3), np.nan); distance = np.full(n, np.nan); light_pdf = np.full(n, np.nan)
+            radiance = np.full((n, 3), np.nan); near_half = np.zeros(n, bool)
+            if emitters:
+                light = nee_reference.sample_lights(nee_reference.Tables(tables.view), np.concatenate([rl, rt], axis=1))
+                hit = _offset(position, light.point - position, gn)
+                light_point = _offset(light.point, hit - light.point, light.normal)
+                to_light = light_point - hit
+                distance = np.sqrt((to_light * to_light).sum(axis=1))
+                to_light = to_light / distance[:, None]
+                cos_light = np.abs(_dot(to_light, light.normal))
+                power = f64(np.float32(0.299)) * light.emission[:, 0] + f64(np.float32(0.587)) * light.emission[:, 1] + f64(np.float32(0.114)) * light.emission[:, 2]
+                light_pdf = power * distance * distance / (cos_light * tables.lights_total_weight)
+                if share > 0.0:
+                    light_pdf = light_pdf * selection
+                valid = np.isfinite(light_pdf) & (light_pdf > 1e-4)
+                origin, radiance = hit, light.emission
+                # (the sides of the two epsilon offsets follow two more dot products)
+                near_half = ((np.abs(light_pdf - 1e-4) <= PDF_MARGIN * 1e-4 * (1.0 + 1.0 / cos_light))
+                             | ~(np.abs(_dot(light.point - position, gn)) > DOT_MARGIN * sliver * distance)
+                             | ~(np.abs(_dot(hit - light.point, light.normal)) > DOT_MARGIN * distance))
+            else:
+                valid = np.zeros(n, bool)
+
+            # the sky's half: the direction and its cell's pdf from the DIM_NEE_TRIANGLE pair, one offset, a ray to infinity
+            if share > 0.0:
+                sky = tables.sky_tables
+                own_direction, _, _, own_pdf = sky.invert(rt)
+                r.sky_direction, r.sky_pdf = own_direction, own_pdf
+                to_sky_direction, pdf_sky = own_direction, sky.pdf_of(own_direction)
+                if sky_directions is not None:
+                    given = np.isfinite(np.asarray(sky_directions, f64)).all(axis=1)
+                    to_sky_direction = np.where(given[:, None], np.asarray(sky_directions, f64), own_direction)
+                    pdf_sky = sky.pdf_of(to_sky_direction)
+                sky_origin = _offset(position, to_sky_direction, gn)
+                sky_light_pdf = share * pdf_sky
+                sky_valid = np.isfinite(sky_light_pdf) & (sky_light_pdf > 0.0)
+                uu = np.arctan2(-to_sky_direction[:, 2], to_sky_direction[:, 0]) / (2.0 * np.pi) + 0.5
+                vv = np.arccos(np.clip(to_sky_direction[:, 1], -1.0, 1.0)) / np.pi
+                on_border = np.zeros(n, bool)
+                for c, cells in ((uu, sky.w), (vv, sky.h)):
+                    x = c * cells
+                    on_border |= np.abs(x - np.round(x)) <= SKY_CELL_MARGIN
+                if sky_pdfs is not None:   # the cell rt_sky_pdf found for the written direction is not float64's
+                    seen = np.asarray(sky_pdfs, f64)
+                    on_border |= np.isfinite(seen) & ~(np.abs(seen - pdf_sky) <= 1e-5 * pdf_sky)
+                one_ulp = f64(np.spacing(np.float32(share)))
+                near_route = emitters & (np.abs(u_light - share) <= one_ulp)
+                near_sky_half = (on_border | ~(np.abs(_dot(to_sky_direction, gn)) > DOT_MARGIN * sliver))
+                k = to_sky[:, None]
+                origin = np.where(k, sky_origin, origin); to_light = np.where(k, to_sky_direction, to_light); distance = np.where(to_sky, np.inf, distance)
+                light_pdf = np.where(to_sky, sky_light_pdf, light_pdf); valid = np.where(to_sky, sky_valid, valid)
+                radiance = np.where(k, sky_sampling_reference.sample_sky(tables.sky, tables.sky_scale, to_sky_direction), radiance)
+                near_half = np.where(to_sky, near_sky_half, near_half) | near_route
+                cos_margin = np.where(to_sky, 4 * DOT_MARGIN, DOT_MARGIN)
+            else:
+                cos_margin = DOT_MARGIN
+
+            # the tail (nee_finish): the BSDF towards the sample, the MIS weight, the illumination
             cos_hit = _dot(to_light, normal)
-            power = f64(np.float32(0.299)) * light.emission[:, 0] + f64(np.float32(0.587)) * light.emission[:, 1] + f64(np.float32(0.114)) * light.emission[:, 2]
-            light_pdf = power * distance * distance / (cos_light * tables.lights_total_weight)
             e_probes = _probes(materials, normal, d, entering, real, sample, bounce, to_light=to_light, cos_o=cos_hit)
             e64, _ = bsdf_reference.evaluate(kind, e_probes, bsdf_tables, eval=True)
-            valid = np.isfinite(light_pdf) & (light_pdf > 1e-4)
-            allowed = alive & s64.allow_nee
             r.has_shadow = allowed & (e64.ok == 1) & valid
-            # (the sides of the two epsilon offsets follow two more dot products)
-            r.near_light = allowed & (e64.near | (np.abs(cos_hit) <= DOT_MARGIN) | (np.abs(light_pdf - 1e-4) <= PDF_MARGIN * 1e-4 * (1.0 + 1.0 / cos_light))
-                                      | ~(np.abs(_dot(light.point - position, gn)) > DOT_MARGIN * sliver * distance)
-                                      | ~(np.abs(_dot(hit - light.point, light.normal)) > DOT_MARGIN * distance))
+            r.near_light = allowed & (e64.near | (np.abs(cos_hit) <= cos_margin) | near_half)
+            r.near_sky = r.near_light & to_sky
             weight = light_pdf ** 2 / (light_pdf ** 2 + e64.pdf ** 2) if cfg["enable_multiple_importance_sampling"] else 1.0
-            illumination = throughput * e64.value * light.emission * np.asarray(weight)[..., None] / light_pdf[:, None]
-            r.shadow_origin, r.shadow_direction, r.shadow_distance = hit, to_light, distance
+            illumination = throughput * e64.value * radiance * np.asarray(weight)[..., None] / light_pdf[:, None]
+            r.shadow_origin, r.shadow_direction, r.shadow_distance = origin, to_light, distance
             r.illumination = np.where(textured[:, None], np.nan, illumination)
             r.light_pdf = light_pdf
+            r.bsdf_pdf_to_light = e64.pdf
     r.textured = textured
-    r.near = r.near_entering | r.near_alive | r.near_sample | r.near_light
+    r.near = r.near_entering | r.near_alive | r.near_sample | r.near_light | r.near_map | r.varied
     r.robust = ~r.near
     return r
+
 
 
 def reference_of(world, tables, launch):
@@ -201,3 +344,63 @@ def reference_of(world, tables, launch):
         launch._reference = (tables, evaluate(world, tables, launch, world.bsdf_tables))
     return launch._reference[1]
 
+
+
+# ---- float32 restatement of the mapped normal (normal_map_perturb and the set-up that feeds it), operation by operation ---------------
+# numpy float32 arithmetic is IEEE and unfused, as the kernels are built (-ffp-contract=off); sums run left to right as rt_math.h writes them.
+# test_material.py measures this against float64 (material_checks.MEASURED["mapped_normal"]); the device is held to 4 x that.
+
+_F = np.float32
+
+
+def _dot32(a, b):
+    return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
+
+
+def _cross32(a, b):
+    return np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2], a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], axis=1)
+
+
+def _normalize32(a):
+    inv = _F(1.0) / np.sqrt(_dot32(a, a))
+    return a * inv[:, None]
+
+
+def _m_direction32(m, v):
+    return np.stack([(m[:, i, 0] * v[:, 0] + m[:, i, 1] * v[:, 1]) + m[:, i, 2] * v[:, 2] for i in range(3)], axis=1)
+
+
+def mapped_normal32(triangles, u16, v16, transforms, direction, texel):
+    """The shading normal shade_material<.., NMAP> hands its BSDF for hits of a constant map `texel` (three bytes), in float32: (N, 3)
+    float32 and whether normal_map_perturb fell back. triangles (N, 24), transforms (N, 3, 4), direction (N, 3) float32."""
+    tri = np.ascontiguousarray(triangles, _F); world = np.ascontiguousarray(transforms, _F); d = np.ascontiguousarray(direction, _F)
+    with np.errstate(all="ignore"):
+        u = (u16.astype(_F) / _F(65535.0))[:, None]; v = (v16.astype(_F) / _F(65535.0))[:, None]
+        e1, e2, n0, ne1, ne2 = tri[:, 3:6], tri[:, 6:9], tri[:, 9:12], tri[:, 12:15], tri[:, 15:18]
+        duv1, duv2 = tri[:, 20:22], tri[:, 22:24]
+        n = _normalize32(_m_direction32(world, (n0 + u * ne1) + v * ne2))
+        det = duv1[:, 0] * duv2[:, 1] - duv2[:, 0] * duv1[:, 1]
+        dpdu = _m_direction32(world, (duv2[:, 1:2] * e1 - duv1[:, 1:2] * e2) / det[:, None])
+        gn = _cross32(_m_direction32(world, e1), _m_direction32(world, e2))
+        gn = gn * (_F(1.0) / np.sqrt(_dot32(gn, gn)))[:, None]
+        entering = _dot32(d, gn) < 0
+        t = dpdu - n * _dot32(n, dpdu)[:, None]
+        t2 = _dot32(t, t)
+        fallback = ~((det != 0) & np.isfinite(det)) | ~((t2 > _F(1e-8) * _dot32(dpdu, dpdu)) & np.isfinite(t2))
+        t = t / np.sqrt(t2)[:, None]
+        b = _cross32(n, t)
+        b = np.where(((det < 0) != (_dot32(gn, n) < 0))[:, None], -b, b)
+        c = np.asarray(texel, np.uint8).astype(_F)[:3] * (_F(1.0) / _F(255.0))   # texel_to_float
+        x = _F(2.0) * c - _F(1.0)
+        m = (x[0] * t + x[1] * b) + x[2] * n
+        m2 = _dot32(m, m)
+        fallback |= ~(m2 > 0)
+        m = m / np.sqrt(m2)[:, None]
+        m = np.where(entering[:, None], m, -m)
+        w = -d
+        cos_view = _dot32(m, w)
+        eps = _F(normal_map_reference.EPS)
+        guarded = _normalize32(m + (eps - cos_view)[:, None] * w)
+        m = np.where((cos_view < eps)[:, None], guarded, m)
+        plain = np.where(entering[:, None], n, -n)
+    return np.where(fallback[:, None], plain, m).astype(_F), fallback

@@ -73,7 +73,7 @@ def run(world, setup_name, tables, launch, capacity=None):
     return got, got_at
 
 
-@pytest.mark.parametrize("setup", cases.SETUPS, ids=[s.name for s in cases.SETUPS])
+@pytest.mark.parametrize("setup", cases.PLAIN_SETUPS, ids=[s.name for s in cases.PLAIN_SETUPS])
 def test_device_obeys_the_rules_and_matches_the_oracle(world, setup):
     tables = world.apply(setup)
     for launch in cases.plan(world, setup, tables):

@@ -70,6 +70,9 @@ def _angle(a, b):
     return 2.0 * np.arcsin(np.clip(np.linalg.norm(a - b, axis=1) / 2.0, 0.0, 1.0))
 
 
+INVERSION_BOUND = 1e-5   # rad: rt_sample_sky_distribution's direction against the numpy inversion of the same tables (test_gpu_material_variants.py imports it)
+
+
 def test_inversion_and_pdf_match_float64(grt, bare, tmp_path):
     """rt_sample_sky_distribution on a stratified grid: the numpy inversion's directions within 1e-5 rad, a counted handful apart at
     cell borders (float32 CDF entries of another summation order); the returned pdf is rt_sky_pdf's for the same direction and the
@@ -84,7 +87,7 @@ def test_inversion_and_pdf_match_float64(grt, bare, tmp_path):
         t = ref.Tables(sky)
         want, row, col, want_pdf = t.invert(uv)
         assert np.allclose(np.linalg.norm(got[:, :3], axis=1), 1.0, atol=1e-6), name
-        far = _angle(got[:, :3].astype(np.float64), want) > 1e-5
+        far = _angle(got[:, :3].astype(np.float64), want) > INVERSION_BOUND
         assert far.sum() <= 16, (name, int(far.sum()))
         assert np.array_equal(got[:, 3], grt.sky_pdf(ctx, got[:, :3])), name
         rel = np.abs(got[:, 3] - want_pdf) / want_pdf
