@@ -125,6 +125,7 @@ def device_lib():
         lib.rt_trace_rays.argtypes = [c_void_p] + [c_void_p] * 6 + [c_size_t, c_void_p, c_int, POINTER(c_float)]
         lib.rt_trace_shadow_rays.argtypes = [c_void_p] + [c_void_p] * 7 + [c_size_t, c_void_p, c_int, POINTER(c_float)]
         lib.rt_trace_stream_rays.argtypes = [c_void_p, c_int] + [c_void_p] * 6 + [c_size_t, c_void_p] + [c_void_p] * 7 + [c_size_t, c_void_p, c_void_p, c_void_p]
+        lib.rt_trace_queue_rays.argtypes = [c_void_p, c_int, c_int, c_int] + [c_void_p] * 6 + [c_size_t, c_void_p] + [c_void_p] * 9 + [c_size_t] + [c_void_p] * 3 + [c_size_t, c_void_p, c_void_p]
         lib.rt_generate_rays.argtypes = [c_void_p, c_int, c_int, c_int] + [c_void_p] * 7
         lib.rt_generate_primary_rays.argtypes = [c_void_p] + [c_int] * 14 + [c_void_p, c_size_t] + [c_void_p] * 8
         lib.rt_random_samples.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_uint32, c_uint32, c_void_p]
@@ -1590,6 +1591,42 @@ def trace_stream_rays(ctx, iteration, origin, direction, hits, shadow_origin, sh
         names = ("nodes", "triangles", "instances_transformed", "instances_identity", "rays")
         stats = {kind: {name: int(stats[5 * j + i]) for i, name in enumerate(names)} for j, kind in enumerate(("closest", "shadow"))}
     return out, light, stats, info
+
+
+TRACE_QUEUE_PLAIN, TRACE_QUEUE_COUNTING, TRACE_QUEUE_AO = 0, 1, 2   # RT_TRACE_QUEUE_*: the forms of rt_trace_queue_rays
+TRACE_QUEUE_FLAG_BOUNCE_0 = 1 << 30                                  # merged form: the pixel word of a shadow ray of bounce 0
+
+
+def trace_queue_rays(ctx, step, origin, direction, hits, shadow_origin, shadow_direction, max_distance, illumination, pixel_words, frames, frame_pixels,
+                     merged=False, form=TRACE_QUEUE_PLAIN):
+    """rt_trace_queue_rays: one bounce's traversal launches of the slots scheduler (step = bounce), or with `merged` the merged wavefront's launch
+    (step = iteration), on explicit queues. origin/direction (3, N), shadow_origin/shadow_direction (3, M) float32 SoA, max_distance (M,),
+    illumination (M, 3) float32, pixel_words (M,) uint32; `hits` (N, 4) uint32 is what the hit records hold before the launch; frames: three
+    (frame_pixels, 4) float32 arrays {RADIANCE, RADIANCE_DIRECT, RADIANCE_INDIRECT} as they are before the launch, None for a frame the launch does
+    not have. Returns (hits, [the three frames after the launch, None where None], stats dict as get_trace_statistics or None, info int32[6])."""
+    o, d = _f32(origin).reshape(3, -1), _f32(direction).reshape(3, -1)
+    so, sd, m = _f32(shadow_origin).reshape(3, -1), _f32(shadow_direction).reshape(3, -1), _f32(max_distance).reshape(-1)
+    light = _f32(illumination).reshape(-1, 3)
+    words = np.ascontiguousarray(pixel_words, np.uint32).reshape(-1)
+    n, k = o.shape[1], so.shape[1]
+    if d.shape[1] != n or sd.shape[1] != k or m.size != k or light.shape[0] != k or words.size != k:
+        raise ValueError("trace_queue_rays: ray arrays of different lengths")
+    out = np.array(hits, np.uint32, order="C", copy=True).reshape(n, 4)
+    after = [None if f is None else np.array(f, np.float32, order="C", copy=True).reshape(frame_pixels, 4) for f in frames]
+    if len(after) != 3:
+        raise ValueError("trace_queue_rays: three frames (or None) are expected")
+    counting = form == TRACE_QUEUE_COUNTING
+    stats = np.zeros(10, np.uint64) if counting else None
+    info = np.zeros(6, np.int32)
+    _dev_check(ctx, device_lib().rt_trace_queue_rays(ctx, 1 if merged else 0, step, form,
+                                                     o[0].ctypes.data, o[1].ctypes.data, o[2].ctypes.data, d[0].ctypes.data, d[1].ctypes.data, d[2].ctypes.data, n, out.ctypes.data,
+                                                     so[0].ctypes.data, so[1].ctypes.data, so[2].ctypes.data, sd[0].ctypes.data, sd[1].ctypes.data, sd[2].ctypes.data, m.ctypes.data,
+                                                     light.ctypes.data, words.ctypes.data, k, *[None if f is None else f.ctypes.data for f in after], frame_pixels,
+                                                     stats.ctypes.data if counting else None, info.ctypes.data))
+    if counting:
+        names = ("nodes", "triangles", "instances_transformed", "instances_identity", "rays")
+        stats = {kind: {name: int(stats[5 * j + i]) for i, name in enumerate(names)} for j, kind in enumerate(("closest", "shadow"))}
+    return out, after, stats, info
 
 
 def generate_rays(ctx, sample_index, pixel_offset, pixel_count):

@@ -1541,14 +1541,28 @@ template<auto K2, auto K4, auto K8, auto K8M, typename... A> static void launch_
 	else launch_for_mask<K8, K8M>(p, stream, args...);
 }
 
+// ... and the waves of the persistent grid those two launch
+template<auto K8, auto K8M> static int waves_for_mask(const RtParams & p) {
+	return (p.opacity_active ? persistent_grid<K8M>() : persistent_grid<K8>()) * (RT_TRACE_BLOCK / RT_WAVE_SIZE);
+}
+template<auto K2, auto K4, auto K8, auto K8M> static int waves_for_width(const RtParams & p) {
+	if (p.bvh_width == 2) return persistent_grid<K2>() * (RT_TRACE_BLOCK / RT_WAVE_SIZE);
+	if (p.bvh_width == 4) return persistent_grid<K4>() * (RT_TRACE_BLOCK / RT_WAVE_SIZE);
+	return waves_for_mask<K8, K8M>(p);
+}
+
+// The per-bounce launches' kernels by width and mask, listed once: what the launchers launch and what rt_trace_queue_launch_info reports
+#define RT_TRACE_FAMILY           kernel_trace_bvh2, kernel_trace_bvh4, kernel_trace_bvh8, kernel_trace_bvh8_mask
+#define RT_TRACE_SHADOW_FAMILY    kernel_trace_shadow_bvh2, kernel_trace_shadow_bvh4, kernel_trace_shadow_bvh8, kernel_trace_shadow_bvh8_mask
+#define RT_TRACE_SHADOW_AO_FAMILY kernel_trace_shadow_bvh2_ao, kernel_trace_shadow_bvh4_ao, kernel_trace_shadow_bvh8_ao, kernel_trace_shadow_bvh8_ao_mask
 void rt_launch_trace(const RtParams & p, int bounce, hipStream_t stream) {
-	launch_for_width<kernel_trace_bvh2, kernel_trace_bvh4, kernel_trace_bvh8, kernel_trace_bvh8_mask>(p, stream, bounce);
+	launch_for_width<RT_TRACE_FAMILY>(p, stream, bounce);
 }
 void rt_launch_trace_shadow(const RtParams & p, int bounce, hipStream_t stream) {
-	launch_for_width<kernel_trace_shadow_bvh2, kernel_trace_shadow_bvh4, kernel_trace_shadow_bvh8, kernel_trace_shadow_bvh8_mask>(p, stream, bounce);
+	launch_for_width<RT_TRACE_SHADOW_FAMILY>(p, stream, bounce);
 }
 void rt_launch_trace_shadow_ao(const RtParams & p, hipStream_t stream) {
-	launch_for_width<kernel_trace_shadow_bvh2_ao, kernel_trace_shadow_bvh4_ao, kernel_trace_shadow_bvh8_ao, kernel_trace_shadow_bvh8_ao_mask>(p, stream);
+	launch_for_width<RT_TRACE_SHADOW_AO_FAMILY>(p, stream);
 }
 // The merged launch: which of its eight kernels p takes (RT_STREAM_KERNEL_*; the four _MASK values follow the four plain ones in their order) ...
 static int stream_kernel_id(const RtParams & p, bool stats) {
@@ -1585,11 +1599,23 @@ void rt_trace_stream_launch_info(const RtParams & p, bool stats, int32_t * info)
 	const int kernel = stream_kernel_id(p, stats);
 	info[0] = kernel; info[1] = stream_kernels[kernel].grid() * (RT_TRACE_BLOCK / RT_WAVE_SIZE); info[2] = RT_NARROW_MAX_RAYS; info[3] = RT_MIXED_MAX_RAYS;
 }
+#define RT_TRACE_COUNTING_FAMILY        kernel_trace_bvh8_counting, kernel_trace_bvh8_counting_mask
+#define RT_TRACE_SHADOW_COUNTING_FAMILY kernel_trace_shadow_bvh8_counting, kernel_trace_shadow_bvh8_counting_mask
 void rt_launch_trace_counting(const RtParams & p, int bounce, unsigned long long * stats, hipStream_t stream) {
-	launch_for_mask<kernel_trace_bvh8_counting, kernel_trace_bvh8_counting_mask>(p, stream, bounce, stats);
+	launch_for_mask<RT_TRACE_COUNTING_FAMILY>(p, stream, bounce, stats);
 }
 void rt_launch_trace_shadow_counting(const RtParams & p, int bounce, unsigned long long * stats, hipStream_t stream) {
-	launch_for_mask<kernel_trace_shadow_bvh8_counting, kernel_trace_shadow_bvh8_counting_mask>(p, stream, bounce, stats);
+	launch_for_mask<RT_TRACE_SHADOW_COUNTING_FAMILY>(p, stream, bounce, stats);
+}
+// What the per-bounce launchers launch for p: info[0] the BVH width, info[1] the waves of the closest-hit launch's persistent grid (rt_launch_trace, or
+// rt_launch_trace_counting with `counting`), info[2] those of the shadow launch (rt_launch_trace_shadow, ..._counting, or ..._ao with `ao`),
+// info[3] RT_NARROW_MAX_RAYS, info[4] RT_FETCH_BLOCK_MAX. For rt_trace_queue_rays, which reports it to tests. (The counting kernels walk the CWBVH only.)
+void rt_trace_queue_launch_info(const RtParams & p, bool counting, bool ao, int32_t * info) {
+	info[0] = p.bvh_width == 2 || p.bvh_width == 4 ? p.bvh_width : 8;
+	info[1] = counting ? waves_for_mask<RT_TRACE_COUNTING_FAMILY>(p) : waves_for_width<RT_TRACE_FAMILY>(p);
+	info[2] = counting ? waves_for_mask<RT_TRACE_SHADOW_COUNTING_FAMILY>(p)
+	        : ao ? waves_for_width<RT_TRACE_SHADOW_AO_FAMILY>(p) : waves_for_width<RT_TRACE_SHADOW_FAMILY>(p);
+	info[3] = RT_NARROW_MAX_RAYS; info[4] = RT_FETCH_BLOCK_MAX;
 }
 void rt_launch_trace_explicit(const RtParams & p, RtVec3SoA origin, RtVec3SoA direction, uint4 * hits, int ray_count, int * retired_counter, hipStream_t stream) {
 	launch_for_width<kernel_trace_bvh2_explicit, kernel_trace_bvh4_explicit, kernel_trace_bvh8_explicit, kernel_trace_bvh8_explicit_mask>(p, stream, origin, direction, hits, ray_count, retired_counter);

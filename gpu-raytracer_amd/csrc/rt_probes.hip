@@ -85,6 +85,113 @@ template<typename Launch> static int time_explicit_launches(Probe & probe, int r
 	return RT_OK;
 }
 
+// The queues and frames of the two trace-launch probes (rt_trace_stream_rays, rt_trace_queue_rays) as the caller gave them ...
+namespace {
+struct TraceQueueArgs {
+	const float * origin[3], * direction[3]; size_t closest_count; uint32_t * hits;
+	const float * shadow_origin[3], * shadow_direction[3], * max_distance; size_t shadow_count;
+	const float4 * light;        // per shadow ray: illumination and pixel word, as the shade kernels queue them
+	float * frames[3];           // RADIANCE, RADIANCE_DIRECT, RADIANCE_INDIRECT: frame_pixels float4 each; NULL: the launch has no such frame
+	size_t frame_pixels;
+	uint64_t * stats10;          // NULL, or the counting kernels' ten words
+};
+const int trace_queue_frame_aov[3] = { RT_AOV_RADIANCE, RT_AOV_RADIANCE_DIRECT, RT_AOV_RADIANCE_INDIRECT };
+static_assert(RT_TRACE_QUEUE_FLAG_BOUNCE_0 == RT_SHADOW_FLAG_BOUNCE_0, "the public header names the kernels' flag");
+// ... and on the device: every array is the caller's before the launch (a hit record or a pixel the launch never writes keeps its value) and read back whole after it
+struct TraceQueueBuffers {
+	RtTraceBuffer trace = { }; RtShadowBuffer shadow = { }; float4 * frames[3] = { nullptr, nullptr, nullptr }; unsigned long long * stats = nullptr;
+	void upload(Probe & probe, const TraceQueueArgs & a) {
+		trace.origin = probe.vec3(a.closest_count, a.origin[0], a.origin[1], a.origin[2]); trace.direction = probe.vec3(a.closest_count, a.direction[0], a.direction[1], a.direction[2]);
+		trace.hits = probe.array<uint4>(a.closest_count, a.hits);
+		shadow.origin = probe.vec3(a.shadow_count, a.shadow_origin[0], a.shadow_origin[1], a.shadow_origin[2]);
+		shadow.direction = probe.vec3(a.shadow_count, a.shadow_direction[0], a.shadow_direction[1], a.shadow_direction[2]);
+		shadow.max_distance = probe.array<float>(a.shadow_count, a.max_distance);
+		shadow.illumination_and_pixel_index = probe.array<float4>(a.shadow_count, a.light);
+		for (int k = 0; k < 3; k++) if (a.frames[k]) frames[k] = probe.array<float4>(a.frame_pixels, a.frames[k]);
+		const unsigned long long zeros[10] = { };
+		if (a.stats10) stats = probe.array<unsigned long long>(10, zeros);
+	}
+	// the launch's frames: these three where given, no other AOV
+	void patch_frames(RtParams & p) const {
+		for (int i = 0; i < RT_AOV_COUNT; i++) p.aovs[i].framebuffer = nullptr;
+		for (int k = 0; k < 3; k++) p.aovs[trace_queue_frame_aov[k]].framebuffer = frames[k];
+	}
+	int read(Probe & probe, const TraceQueueArgs & a) const {
+		int s = RT_OK;
+		if (a.closest_count && (s = probe.read(a.hits, trace.hits, a.closest_count * 16))) return s;
+		for (int k = 0; k < 3; k++) if (frames[k] && a.frame_pixels && (s = probe.read(a.frames[k], frames[k], a.frame_pixels * 16))) return s;
+		return stats ? probe.read(a.stats10, stats, 10 * sizeof(unsigned long long)) : RT_OK;
+	}
+};
+} // namespace
+
+// The merged wavefront's traversal launch (rt_launch_trace_stream, as stream_enqueue_iteration calls it) on the queues of `a`, for both probes. The
+// parameter block is stream_params(ctx, iteration) with the closest-hit queue of parity iteration & 1, the shadow queue, the control block and the
+// three radiance frames replaced by buffers of this call. Runs on the wavefront's own stream with its own spill area, after quiesce(); nothing of the
+// context changes but what the scheduler would set up itself (stream_create, stream_sync_tlas). info4: rt_trace_stream_launch_info's.
+static int trace_stream_probe(rt_context * ctx, const char * name, int iteration, const TraceQueueArgs & a, int32_t * info4) {
+	(void)hipSetDevice(ctx->device);
+	RT_HIP(ctx, quiesce(ctx)); // the wavefront's stream and spill area are borrowed
+	int s = check_ready(ctx, name, NEED_SCENE_JOINT); if (s) return s;
+	if (ctx->params.bvh_width != 8) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: the merged wavefront's launch walks the CWBVH (bvh_width %d)", name, ctx->params.bvh_width);
+	s = stream_create(ctx); if (s) return s;
+	s = stream_sync_tlas(ctx); if (s) return s;
+	PathStream & ps = ctx->path_stream;
+	const int q = iteration & 1;
+
+	Probe probe(ctx, name);
+	TraceQueueBuffers b; b.upload(probe, a);
+	std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());   // (value-initialised: zero cursors and region words)
+	control_host->trace_count[q] = int(a.closest_count);
+	control_host->shadow_count[q ^ 1] = int(a.shadow_count);
+	RtStreamControl * control = probe.array<RtStreamControl>(1, control_host.get());
+	if ((s = probe.allocated())) return s;
+
+	RtParams p = stream_params(ctx, iteration);
+	p.trace[q] = b.trace;
+	p.shadow = b.shadow;
+	p.stream = control;
+	b.patch_frames(p);
+	rt_trace_stream_launch_info(p, b.stats != nullptr, info4);
+	rt_launch_trace_stream(p, b.stats, ps.stream);
+	if ((s = probe.finish(ps.stream))) return s;
+	return b.read(probe, a);
+}
+
+// One bounce of the slots scheduler's traversal (rt_render_samples: rt_launch_trace, then rt_launch_trace_shadow with the slot's second spill area;
+// their _counting forms; or rt_launch_trace_shadow_ao alone, as rt_render_ao_sample launches it) on the queues of `a`. The parameter block is slot 0's
+// with the closest-hit queue of parity bounce & 1, the shadow queue, the counters, the cursors and the three radiance frames replaced by buffers of
+// this call. Runs on the main stream after quiesce(). info5: rt_trace_queue_launch_info's.
+static int trace_bounce_probe(rt_context * ctx, const char * name, int bounce, int form, const TraceQueueArgs & a, int32_t * info5) {
+	(void)hipSetDevice(ctx->device);
+	RT_HIP(ctx, quiesce(ctx)); // slot 0's spill areas are borrowed
+	int s = check_ready(ctx, name, NEED_SCENE_JOINT); if (s) return s;
+	const bool counting = form == RT_TRACE_QUEUE_COUNTING, ao = form == RT_TRACE_QUEUE_AO;
+	if (counting && ctx->params.bvh_width != 8) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: the counting kernels walk the CWBVH (bvh_width %d)", name, ctx->params.bvh_width);
+
+	Probe probe(ctx, name);
+	TraceQueueBuffers b; b.upload(probe, a);
+	RtBufferSizes sizes_host = { };
+	sizes_host.trace[bounce] = int(a.closest_count); sizes_host.shadow[bounce] = int(a.shadow_count);
+	RtBufferSizes * sizes = probe.array<RtBufferSizes>(1, &sizes_host);
+	const std::vector<int> zero_cursors(RT_MAX_BOUNCES * 2, 0);
+	int * cursors = probe.array<int>(zero_cursors.size(), zero_cursors.data());
+	if ((s = probe.allocated())) return s;
+
+	RtParams p = ctx->params;
+	p.trace[bounce & 1] = b.trace;
+	p.shadow = b.shadow;
+	p.sizes = sizes; p.ray_cursors = cursors;
+	b.patch_frames(p);
+	RtParams p_shadow = p; p_shadow.stack_spill = (uint2 *)ctx->slots[0].spill[1];   // (as the render loop: the shadow launch may be resident with the next closest-hit launch)
+	rt_trace_queue_launch_info(p, counting, ao, info5);
+	if (ao) rt_launch_trace_shadow_ao(p, ctx->stream);
+	else if (counting) { rt_launch_trace_counting(p, bounce, b.stats, ctx->stream); rt_launch_trace_shadow_counting(p, bounce, b.stats, ctx->stream); }
+	else { rt_launch_trace(p, bounce, ctx->stream); rt_launch_trace_shadow(p_shadow, bounce, ctx->stream); }
+	if ((s = probe.finish())) return s;
+	return b.read(probe, a);
+}
+
 extern "C" {
 
 int rt_trace_rays(rt_context * ctx, const float * ox, const float * oy, const float * oz,
@@ -118,11 +225,8 @@ int rt_trace_shadow_rays(rt_context * ctx, const float * ox, const float * oy, c
 	return probe.read(occluded, dev_occ, ray_count);
 }
 
-// rt_trace_stream_rays: the merged wavefront's traversal launch (rt_launch_trace_stream, as stream_enqueue_iteration calls it) on explicit
-// rays. The parameter block is stream_params(ctx, iteration) with the closest-hit queue of parity iteration & 1, the shadow queue, the
-// control block and the radiance frame replaced by buffers of this call; every shadow ray i carries illumination (1, 0, 0) for pixel i,
-// so what the launch adds to pixel i tells how often ray i reached its light unoccluded. Runs on the wavefront's own stream with its own
-// spill area, after quiesce(); nothing of the context changes but what the scheduler would set up itself (stream_create, stream_sync_tlas).
+// rt_trace_stream_rays: trace_stream_probe on explicit rays, with a radiance frame of one pixel per shadow ray and no other: every shadow ray i
+// carries illumination (1, 0, 0) for pixel i, so what the launch adds to pixel i tells how often ray i reached its light unoccluded.
 int rt_trace_stream_rays(rt_context * ctx, int iteration,
                          const float * ox, const float * oy, const float * oz, const float * dx, const float * dy, const float * dz,
                          size_t closest_count, uint32_t * hits,
@@ -135,55 +239,65 @@ int rt_trace_stream_rays(rt_context * ctx, int iteration,
 	RT_REQUIRE(ctx, closest_count == 0 || (ox && oy && oz && dx && dy && dz && hits), "rt_trace_stream_rays: NULL closest-hit ray or hit array");
 	RT_REQUIRE(ctx, shadow_count == 0 || (sox && soy && soz && sdx && sdy && sdz && max_distance && shadow_light), "rt_trace_stream_rays: NULL shadow ray, max_distance or shadow_light array");
 	RT_REQUIRE(ctx, closest_count + shadow_count <= size_t(1) << 28, "rt_trace_stream_rays: more than 2^28 rays in one launch");
-	(void)hipSetDevice(ctx->device);
-	RT_HIP(ctx, quiesce(ctx)); // the wavefront's stream and spill area are borrowed
-	int s = check_ready(ctx, "rt_trace_stream_rays", NEED_SCENE_JOINT); if (s) return s;
-	if (ctx->params.bvh_width != 8) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_trace_stream_rays: the merged wavefront's launch walks the CWBVH (bvh_width %d)", ctx->params.bvh_width);
-	s = stream_create(ctx); if (s) return s;
-	s = stream_sync_tlas(ctx); if (s) return s;
-	PathStream & ps = ctx->path_stream;
-	const int q = iteration & 1;
-
-	Probe probe(ctx, "rt_trace_stream_rays");
-	RtTraceBuffer trace = { };
-	trace.origin = probe.vec3(closest_count, ox, oy, oz); trace.direction = probe.vec3(closest_count, dx, dy, dz);
-	trace.hits = probe.array<uint4>(closest_count, hits);   // the caller's values: a sentinel shows a ray the launch never dealt
-	std::vector<float4> light(shadow_count);
+	std::vector<float4> light(shadow_count), radiance(shadow_count, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
 	for (size_t i = 0; i < shadow_count; i++) {   // (i < 2^28: RT_SHADOW_FLAG_BOUNCE_0 clear)
 		uint32_t pixel_word = uint32_t(i); float w; memcpy(&w, &pixel_word, 4);
 		light[i] = make_float4(1.0f, 0.0f, 0.0f, w);
 	}
-	RtShadowBuffer shadow = { };
-	shadow.origin = probe.vec3(shadow_count, sox, soy, soz); shadow.direction = probe.vec3(shadow_count, sdx, sdy, sdz);
-	shadow.max_distance = probe.array<float>(shadow_count, max_distance);
-	shadow.illumination_and_pixel_index = probe.array<float4>(shadow_count, light.data());
-	float4 * radiance = probe.array<float4>(shadow_count);
-	std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());   // (value-initialised: zero cursors and region words)
-	control_host->trace_count[q] = int(closest_count);
-	control_host->shadow_count[q ^ 1] = int(shadow_count);
-	RtStreamControl * control = probe.array<RtStreamControl>(1, control_host.get());
-	unsigned long long * stats = stats10 ? probe.array<unsigned long long>(10) : nullptr;
-	if ((s = probe.allocated())) return s;
-	if (shadow_count) RT_HIP(ctx, hipMemset(radiance, 0, shadow_count * 16));
-	if (stats) RT_HIP(ctx, hipMemset(stats, 0, 10 * sizeof(unsigned long long)));
-
-	RtParams p = stream_params(ctx, iteration);
-	p.trace[q] = trace;
-	p.shadow = shadow;
-	p.stream = control;
-	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = nullptr;
-	p.aovs[RT_AOV_RADIANCE].framebuffer = radiance;
-	rt_trace_stream_launch_info(p, stats != nullptr, info);
-	rt_launch_trace_stream(p, stats, ps.stream);
-	if ((s = probe.finish(ps.stream))) return s;
-	if (closest_count && (s = probe.read(hits, trace.hits, closest_count * 16))) return s;
-	if (shadow_count) {
-		std::vector<float4> added(shadow_count);
-		if ((s = probe.read(added.data(), radiance, shadow_count * 16))) return s;
-		for (size_t i = 0; i < shadow_count; i++) shadow_light[i] = added[i].x;
-	}
-	return stats10 ? probe.read(stats10, stats, 10 * sizeof(unsigned long long)) : RT_OK;
+	const TraceQueueArgs a = { { ox, oy, oz }, { dx, dy, dz }, closest_count, hits, { sox, soy, soz }, { sdx, sdy, sdz }, max_distance, shadow_count, light.data(),
+	                           { shadow_count ? &radiance[0].x : nullptr, nullptr, nullptr }, shadow_count, stats10 };
+	int s = trace_stream_probe(ctx, "rt_trace_stream_rays", iteration, a, info); if (s) return s;
+	for (size_t i = 0; i < shadow_count; i++) shadow_light[i] = radiance[i].x;
+	return RT_OK;
 }
+
+// rt_trace_queue_rays: one bounce's traversal launches of the slots scheduler (trace_bounce_probe), or the merged wavefront's launch
+// (trace_stream_probe), on explicit queues whose shadow rays carry the caller's illumination and pixel words into the caller's three frames.
+int rt_trace_queue_rays(rt_context * ctx, int merged, int step, int form,
+                        const float * ox, const float * oy, const float * oz, const float * dx, const float * dy, const float * dz,
+                        size_t closest_count, uint32_t * hits,
+                        const float * sox, const float * soy, const float * soz, const float * sdx, const float * sdy, const float * sdz,
+                        const float * max_distance, const float * illumination, const uint32_t * pixel_words, size_t shadow_count,
+                        float * radiance, float * radiance_direct, float * radiance_indirect, size_t frame_pixels,
+                        uint64_t * stats10, int32_t * info) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_trace_queue_rays: NULL context");
+	RT_REQUIRE(ctx, info != nullptr, "rt_trace_queue_rays: NULL info");
+	RT_REQUIRE(ctx, merged == 0 || merged == 1, "rt_trace_queue_rays: merged must be 0 (per-bounce launches) or 1 (merged wavefront)");
+	RT_REQUIRE(ctx, form == RT_TRACE_QUEUE_PLAIN || form == RT_TRACE_QUEUE_COUNTING || (form == RT_TRACE_QUEUE_AO && !merged),
+	           "rt_trace_queue_rays: form must be 0 (the frame's kernels), 1 (the counting kernels) or, per-bounce only, 2 (the AO integrator's shadow launch)");
+	RT_REQUIRE(ctx, step >= 0 && (merged || step < RT_MAX_BOUNCES), merged ? "rt_trace_queue_rays: negative iteration" : "rt_trace_queue_rays: bounce outside [0, RT_MAX_BOUNCES)");
+	RT_REQUIRE(ctx, form != RT_TRACE_QUEUE_AO || (step == 0 && closest_count == 0), "rt_trace_queue_rays: the AO form launches the shadow queue of bounce 0 alone (step and closest_count must be 0)");
+	RT_REQUIRE(ctx, (form == RT_TRACE_QUEUE_COUNTING) == (stats10 != nullptr), "rt_trace_queue_rays: stats10 must be given for the counting kernels and NULL otherwise");
+	RT_REQUIRE(ctx, closest_count == 0 || (ox && oy && oz && dx && dy && dz && hits), "rt_trace_queue_rays: NULL closest-hit ray or hit array");
+	RT_REQUIRE(ctx, shadow_count == 0 || (sox && soy && soz && sdx && sdy && sdz && max_distance && illumination && pixel_words),
+	           "rt_trace_queue_rays: NULL shadow ray, max_distance, illumination or pixel word array");
+	RT_REQUIRE(ctx, closest_count <= size_t(1) << 28 && shadow_count <= size_t(1) << 28 && closest_count + shadow_count <= size_t(1) << 28, "rt_trace_queue_rays: more than 2^28 rays in one launch");
+	RT_REQUIRE(ctx, frame_pixels <= size_t(1) << 28, "rt_trace_queue_rays: more than 2^28 pixels in a frame");
+	std::vector<float4> light(shadow_count);
+	{	// every pixel a shadow ray names lies inside the frames, and no two rays name the same one: the contribution is a plain read-modify-write,
+		// and a frame never queues two shadow rays per pixel and bounce
+		std::vector<uint8_t> seen((frame_pixels + 7) / 8, 0);
+		for (size_t i = 0; i < shadow_count; i++) {
+			const uint32_t word = pixel_words[i];
+			if (!merged && (word & RT_SHADOW_FLAG_BOUNCE_0)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_trace_queue_rays: shadow ray %zu: the bounce-0 flag is set in the pixel word of a per-bounce launch", i);
+			const uint32_t pixel = word & ~RT_SHADOW_FLAG_BOUNCE_0;
+			if (pixel >= frame_pixels) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_trace_queue_rays: shadow ray %zu: pixel %u beyond the %zu pixels of the frames", i, pixel, frame_pixels);
+			if (seen[pixel >> 3] & (1u << (pixel & 7))) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_trace_queue_rays: shadow ray %zu: pixel %u appears twice", i, pixel);
+			seen[pixel >> 3] |= uint8_t(1u << (pixel & 7));
+			float w; memcpy(&w, &word, 4);
+			light[i] = make_float4(illumination[3 * i], illumination[3 * i + 1], illumination[3 * i + 2], w);
+		}
+	}
+	const TraceQueueArgs a = { { ox, oy, oz }, { dx, dy, dz }, closest_count, hits, { sox, soy, soz }, { sdx, sdy, sdz }, max_distance, shadow_count, light.data(),
+	                           { radiance, radiance_direct, radiance_indirect }, frame_pixels, stats10 };
+	for (int i = 0; i < RT_TRACE_QUEUE_INFO; i++) info[i] = -1;
+	if (!merged) return trace_bounce_probe(ctx, "rt_trace_queue_rays", step, form, a, info);
+	int32_t stream_info[4];
+	int s = trace_stream_probe(ctx, "rt_trace_queue_rays", step, a, stream_info); if (s) return s;
+	info[0] = 8; info[1] = info[2] = stream_info[1]; info[3] = stream_info[2]; info[5] = stream_info[0];   // (one launch: one grid; no ray_block of this kind)
+	return RT_OK;
+}
+
 
 int rt_generate_rays(rt_context * ctx, int sample_index, int pixel_offset, int pixel_count,
                      float * ox, float * oy, float * oz, float * dx, float * dy, float * dz, uint32_t * pixel_index_and_flags) {

@@ -306,6 +306,7 @@ void rt_launch_trace_stream(const RtParams & p, unsigned long long * stats, hipS
 enum { RT_STREAM_KERNEL_GENERAL = 0, RT_STREAM_KERNEL_FLAT = 1, RT_STREAM_KERNEL_FLAT_SKIP = 2, RT_STREAM_KERNEL_COUNTING = 3,
        RT_STREAM_KERNEL_GENERAL_MASK = 4, RT_STREAM_KERNEL_FLAT_MASK = 5, RT_STREAM_KERNEL_FLAT_SKIP_MASK = 6, RT_STREAM_KERNEL_COUNTING_MASK = 7 };   // (_MASK: p.opacity_active)
 void rt_trace_stream_launch_info(const RtParams & p, bool stats, int32_t * info);   // the kernel rt_launch_trace_stream picks, its grid in waves, the two engine limits
+void rt_trace_queue_launch_info(const RtParams & p, bool counting, bool ao, int32_t * info);   // the per-bounce launchers' choice: BVH width, waves of the closest-hit and of the shadow grid, RT_NARROW_MAX_RAYS, RT_FETCH_BLOCK_MAX
 void rt_launch_sort_stream(const RtParams & p, hipStream_t stream);
 void rt_launch_material_stream(const RtParams & p, int material_slot, hipStream_t stream);
 void rt_launch_trace_shadow(const RtParams & p, int bounce, hipStream_t stream);

@@ -171,6 +171,7 @@ const char * rt_version(void);
  *      (still 17: rt_set_firefly_cascade, rt_get_firefly_cascade, rt_read_firefly_cascade, rt_resolve_fireflies, rt_read_resolved, rt_resolve_fireflies_timed,
  *      rt_set_denoise_source, rt_get_denoise_source, rt_accumulate_cascade_frames, rt_resolve_fireflies_images -- new entry points and a parameter struct of their
  *      own; the firefly filter, off until it is set)
+ *      (still 17: rt_trace_queue_rays -- a new entry point; the frame's per-bounce traversal launches on explicit queues, for tests)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
 #define RT_ABI_VERSION 17
 int rt_abi_version(void);
@@ -780,6 +781,33 @@ int rt_trace_stream_rays(rt_context * ctx, int iteration,
                          const float * sox, const float * soy, const float * soz, const float * sdx, const float * sdy, const float * sdz,
                          const float * max_distance, size_t shadow_count, float * shadow_light,
                          uint64_t * stats10, int32_t * info);
+/* The frame's traversal launches on explicit queues whose shadow rays carry the caller's illumination and pixel words into the caller's frames
+ * (synchronous). merged 0, step = bounce in [0, RT_MAX_BOUNCES): what the slots scheduler launches for one bounce -- the closest-hit launch, then the
+ * shadow launch on the slot's second spill area -- by the launchers a frame calls, so the BVH width (2, 4, 8) and the opacity-mask instances are the
+ * context's. form RT_TRACE_QUEUE_PLAIN: the frame's kernels; RT_TRACE_QUEUE_COUNTING: the counting kernels (CWBVH only), their ten counters in stats10
+ * as rt_trace_stream_rays returns them (stats10 is NULL for every other form); RT_TRACE_QUEUE_AO: the AO integrator's shadow launch alone (step 0, no
+ * closest-hit rays). merged 1, step = iteration: the merged wavefront's one launch, as rt_trace_stream_rays runs it (CWBVH only; form PLAIN or COUNTING).
+ * closest_count rays (ox..dz) write hits as there (uploaded first: a value the launch never overwrites stays). shadow_count rays (sox..sdz,
+ * max_distance) carry illumination[3 * i .. 3 * i + 2] for the pixel pixel_words[i]; in the merged form bit RT_TRACE_QUEUE_FLAG_BOUNCE_0 of the word
+ * marks a ray of bounce 0 (refused in the per-bounce form, where the bounce is `step`). radiance, radiance_direct, radiance_indirect: frame_pixels x 4
+ * floats each, uploaded first and read back whole; NULL: the launch has no such frame. An unoccluded shadow ray adds (illumination, 0) to RADIANCE,
+ * and sets RADIANCE_DIRECT to it (bounce 0) or adds it to RADIANCE_INDIRECT (later bounces); the AO form sets RADIANCE to (1, 1, 1, 1). Refused
+ * before any launch: a pixel at or beyond frame_pixels, two shadow rays that name the same pixel (the contribution is a plain read-modify-write), more
+ * than 2^28 rays or pixels. info: RT_TRACE_QUEUE_INFO ints {BVH width, waves of the closest-hit launch's persistent grid, waves of the shadow launch's
+ * (merged: the one launch's, twice), RT_NARROW_MAX_RAYS, RT_FETCH_BLOCK_MAX (-1 merged), the merged launch's kernel as rt_trace_stream_rays numbers
+ * them (-1 per-bounce)}. Leaves no state a frame reads. (An addition that changes no struct: RT_ABI_VERSION stays.) */
+#define RT_TRACE_QUEUE_PLAIN    0
+#define RT_TRACE_QUEUE_COUNTING 1
+#define RT_TRACE_QUEUE_AO       2
+#define RT_TRACE_QUEUE_INFO     6
+#define RT_TRACE_QUEUE_FLAG_BOUNCE_0 (1u << 30)
+int rt_trace_queue_rays(rt_context * ctx, int merged, int step, int form,
+                        const float * ox, const float * oy, const float * oz, const float * dx, const float * dy, const float * dz,
+                        size_t closest_count, uint32_t * hits,
+                        const float * sox, const float * soy, const float * soz, const float * sdx, const float * sdy, const float * sdz,
+                        const float * max_distance, const float * illumination, const uint32_t * pixel_words, size_t shadow_count,
+                        float * radiance, float * radiance_direct, float * radiance_indirect, size_t frame_pixels,
+                        uint64_t * stats10, int32_t * info);
 /* kernel_generate only: writes the primary rays of pixels [offset, offset+count).          */
 int rt_generate_rays(rt_context * ctx, int sample_index, int pixel_offset, int pixel_count,
                      float * ox, float * oy, float * oz, float * dx, float * dy, float * dz,

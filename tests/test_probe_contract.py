@@ -14,6 +14,7 @@ PROBES = {
     "rt_trace_rays":               ([P] * 6 + [Z, P, I, P],                          [None] * 6 + [0, None, 0, None],                        "NULL argument"),
     "rt_trace_shadow_rays":        ([P] * 7 + [Z, P, I, P],                          [None] * 7 + [0, None, 0, None],                        "NULL argument"),
     "rt_trace_stream_rays":        ([I] + [P] * 6 + [Z, P] + [P] * 7 + [Z, P, P, P], [0] + [None] * 6 + [0, None] + [None] * 7 + [0, None, None, None], "NULL context"),
+    "rt_trace_queue_rays":         ([I, I, I] + [P] * 6 + [Z, P] + [P] * 9 + [Z] + [P] * 3 + [Z, P, P], [0, 0, 0] + [None] * 6 + [0, None] + [None] * 9 + [0] + [None] * 3 + [0, None, None], "NULL context"),
     "rt_generate_rays":            ([I, I, I] + [P] * 7,                             [0, 0, 0] + [None] * 7,                                 "NULL argument"),
     "rt_generate_primary_rays":    ([I] * 14 + [P, Z] + [P] * 8,                     [0] * 14 + [None, 0] + [None] * 8,                      "NULL context"),
     "rt_random_samples":           ([I, P, Z, U, U, P],                              [0, None, 0, 0, 0, None],                               "invalid argument"),
@@ -40,8 +41,8 @@ def lib(grt):
     return lib
 
 
-def test_there_are_eighteen_probes():
-    assert len(PROBES) == 18
+def test_there_are_nineteen_probes():
+    assert len(PROBES) == 19
 
 
 @pytest.mark.parametrize("name", sorted(PROBES))

@@ -16,6 +16,7 @@ import trace_reference as ref
 
 TOL_GAP = ref.TOL.GAP / ref.TOL.T
 STACK_LIMIT = 32   # RT_STACK_SIZE (kernels_trace.hip): entries per lane; the device does not check its spill index
+LDS_STACK = 10     # RT_LDS_STACK: the entries of them kept in LDS; a deeper stack spills to HBM
 
 
 def load(grt, case, device, **config):
@@ -91,6 +92,70 @@ def check_closest(label, case, pt, origin, direction, hits, bf, report=None):
     if report is not None:
         leaks = int((~hit).sum()) if case.closed else None
         report.add(label, float(robust.mean()), report_t, report_ulp, report_uv, leaks)
+
+
+FLAG_BOUNCE_0 = np.uint32(1 << 30)   # RT_SHADOW_FLAG_BOUNCE_0: merged wavefront, the pixel word of a shadow ray emitted at bounce 0
+RADIANCE, DIRECT, INDIRECT = range(3)   # the three frames of rt_trace_queue_rays, in its order
+
+
+def expected_frames(frames, illumination, pixel_words, occluded, bounce=None, ao=False):
+    """What a shadow launch leaves in the frames [RADIANCE, DIRECT, INDIRECT] ((P, 4) float32 each, None: the launch has no such frame), in float32
+    as the kernels add (ShadowQueueSource::finish, ShadowStreamSource::contribute, ShadowAOSource::finish in kernels_trace.hip): an unoccluded ray
+    of illumination (M, 3) adds value = (illumination, 0) to its RADIANCE pixel in all four channels, SETS its DIRECT pixel to value when it is of
+    bounce 0 and adds value to its INDIRECT pixel otherwise; an occluded ray writes nothing. `bounce`: the per-bounce launch's (the pixel word is
+    the pixel); None: the merged launch, where FLAG_BOUNCE_0 of the word says bounce 0 and the rest is the pixel. ao: the AO integrator's launch,
+    which sets RADIANCE to (1, 1, 1, 1) and touches nothing else. No two rays may name one pixel. Returns new arrays (None where None)."""
+    words = np.asarray(pixel_words, np.uint32)
+    light = np.asarray(illumination, np.float32).reshape(-1, 3)
+    live = ~np.asarray(occluded).astype(bool)
+    if bounce is None:
+        pixel, first = (words & ~FLAG_BOUNCE_0).astype(np.int64), (words & FLAG_BOUNCE_0) != 0
+    else:
+        assert not (words & FLAG_BOUNCE_0).any(), "a per-bounce launch has no flag in its pixel words"
+        pixel, first = words.astype(np.int64), np.full(words.size, bounce == 0)
+    assert np.unique(pixel).size == pixel.size, "two shadow rays name one pixel"
+    value = np.concatenate([light, np.zeros((light.shape[0], 1), np.float32)], 1)
+    out = [None if f is None else np.array(f, np.float32, copy=True) for f in frames]
+    if ao:
+        if out[RADIANCE] is not None:
+            out[RADIANCE][pixel[live]] = np.float32(1.0)
+        return out
+    if out[RADIANCE] is not None:
+        out[RADIANCE][pixel[live]] = out[RADIANCE][pixel[live]] + value[live]
+    if out[DIRECT] is not None:
+        out[DIRECT][pixel[live & first]] = value[live & first]
+    if out[INDIRECT] is not None:
+        out[INDIRECT][pixel[live & ~first]] = out[INDIRECT][pixel[live & ~first]] + value[live & ~first]
+    return out
+
+
+def check_frames(label, got, want, prefill, illumination, pixel_words):
+    """The frames a launch left, against expected_frames, AS BITS; a pixel that differs is named with what happened to it where that can be told: a
+    contribution lost (the prefill is still there) or made twice (prefill + 2 x value). Returns the pixels compared per frame."""
+    words = np.asarray(pixel_words, np.uint32)
+    pixel = (words & ~FLAG_BOUNCE_0).astype(np.int64)
+    value = np.concatenate([np.asarray(illumination, np.float32).reshape(-1, 3), np.zeros((words.size, 1), np.float32)], 1)
+    counts = []
+    for name, g, w, before in zip(("RADIANCE", "RADIANCE_DIRECT", "RADIANCE_INDIRECT"), got, want, prefill):
+        assert (g is None) == (w is None), "%s: %s is %s" % (label, name, "missing" if g is None else "unexpected")
+        if g is None:
+            counts.append(0)
+            continue
+        bad = np.nonzero((g.view(np.uint32) != w.view(np.uint32)).any(1))[0]
+        if bad.size:
+            p = int(bad[0])
+            ray = np.nonzero(pixel == p)[0]
+            what = "no ray names it"
+            if ray.size:
+                r = int(ray[0])
+                twice = np.asarray(before, np.float32)[p] + value[r] + value[r]
+                what = "ray %d names it (word 0x%08x, value %s): %s" % (r, int(words[r]), value[r].tolist(),
+                       "its contribution was LOST (the prefill is unchanged)" if np.array_equal(g[p].view(np.uint32), np.asarray(before, np.float32)[p].view(np.uint32))
+                       else "its contribution was made TWICE" if np.array_equal(g[p].view(np.uint32), twice.view(np.uint32)) else "neither lost nor doubled")
+            raise AssertionError("%s: %d pixels of %s differ from the expected frame, first pixel %d: got %s, want %s, prefill %s; %s" % (
+                label, bad.size, name, p, g[p].tolist(), w[p].tolist(), np.asarray(before, np.float32)[p].tolist(), what))
+        counts.append(int(g.shape[0]))
+    return counts
 
 
 def check_shadow(label, occluded, bf, max_distance):
