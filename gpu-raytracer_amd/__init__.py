@@ -1422,21 +1422,28 @@ def resolve_fireflies_images(ctx, mean, moments, tiers, fallback, width=None, ti
     return out
 
 
+def _accumulate_staging(frames, images, first_sample, sample_count, merged):
+    """What the three accumulate probes are handed: float32 copies of the frames and of the (height, pitch, 4) images (None stays None), one first sample and one
+    sample count per submission (merged=False: the one batch holds all frames unless sample_count says otherwise) and a zeroed final image."""
+    frames, images = _f32(frames).copy(), [None if image is None else _f32(image).copy() for image in images]
+    if merged:
+        first, count = np.asarray(first_sample, np.int32).reshape(-1).copy(), np.asarray(sample_count, np.int32).reshape(-1).copy()
+    else:
+        first, count = np.array([first_sample], np.int32), np.array([frames.shape[0] if sample_count is None else sample_count], np.int32)
+    assert frames.ndim == 4 and frames.shape[0] == int(count.sum()) and len(first) == len(count) and all(image is None or image.shape == frames.shape[1:] for image in images)
+    return frames, images, first, count, np.zeros(frames.shape[1:], np.float32)
+
+
 def accumulate_cascade_frames(ctx, frames, accumulator, moments, tiers, first_sample, sample_count=None, merged=False, pixels=None, sentinel=0x7fc0dead, **params):
     """rt_accumulate_cascade_frames: accumulate_frames / accumulate_list_frames (pixels: the list, merged only) with the cascade; tiers: (K, height, pitch, 4) in
     and out; params: start, support. Returns (frames, accumulator, moments, tiers, final_image) after the ONE launch."""
-    frames, accumulator, moments, tiers = (_f32(a).copy() for a in (frames, accumulator, moments, tiers))
-    if merged:
-        first, count = np.asarray(first_sample, np.int32).copy(), np.asarray(sample_count, np.int32).copy()
-    else:
-        first, count = np.array([first_sample], np.int32), np.array([frames.shape[0] if sample_count is None else sample_count], np.int32)
-    assert frames.ndim == 4 and frames.shape[0] == int(count.sum()) and frames.shape[1:] == accumulator.shape == moments.shape == tiers.shape[1:]
+    frames, (accumulator, moments), first, count, final = _accumulate_staging(frames, (accumulator, moments), first_sample, sample_count, merged)
+    tiers = _f32(tiers).copy()
+    assert tiers.shape[1:] == accumulator.shape
     record = firefly_params(tiers=tiers.shape[0], **params)
     pixels = None if pixels is None else np.ascontiguousarray(pixels, np.uint32)
-    final = np.zeros(accumulator.shape, np.float32)
     status = device_lib().rt_accumulate_cascade_frames(ctx, 1 if merged else 0, first.ctypes.data, count.ctypes.data, len(first), frames.ctypes.data, accumulator.ctypes.data,
-                                                       moments.ctypes.data, None if pixels is None else pixels.ctypes.data, 0 if pixels is None else pixels.size, byref(record),
-                                                       tiers.ctypes.data, sentinel, final.ctypes.data)
+                                                       moments.ctypes.data, None if pixels is None else pixels.ctypes.data, 0 if pixels is None else pixels.size, byref(record), tiers.ctypes.data, sentinel, final.ctypes.data)
     if status:
         raise DeviceRefusal(ctx, status)
     return frames, accumulator, moments, tiers, final
@@ -1447,14 +1454,7 @@ def accumulate_frames(ctx, frames, accumulator, moments, first_sample, sample_co
     moments (None: the plain kernel): (height, pitch, 4). merged=False: first_sample an int, all frames one batch (<= 16). merged=True: first_sample and
     sample_count are lists, one entry per submission. Returns (frames, accumulator, moments, final_image) after the launch; final_image holds `sentinel`
     (uint32 bits) where the launch did not write."""
-    frames, accumulator = _f32(frames).copy(), _f32(accumulator).copy()
-    moments = None if moments is None else _f32(moments).copy()
-    if merged:
-        first, count = np.asarray(first_sample, np.int32).copy(), np.asarray(sample_count, np.int32).copy()
-    else:
-        first, count = np.array([first_sample], np.int32), np.array([frames.shape[0] if sample_count is None else sample_count], np.int32)
-    assert frames.ndim == 4 and frames.shape[0] == int(count.sum()) and frames.shape[1:] == accumulator.shape and (moments is None or moments.shape == accumulator.shape)
-    final = np.zeros(accumulator.shape, np.float32)
+    frames, (accumulator, moments), first, count, final = _accumulate_staging(frames, (accumulator, moments), first_sample, sample_count, merged)
     status = device_lib().rt_accumulate_frames(ctx, 1 if merged else 0, first.ctypes.data, count.ctypes.data, len(first), frames.ctypes.data, accumulator.ctypes.data,
                                                None if moments is None else moments.ctypes.data, sentinel, final.ctypes.data)
     if status:
@@ -1525,15 +1525,12 @@ def select_pixels_images(ctx, height, width, pitch, mean, moments, threshold, fl
 
 
 def accumulate_list_frames(ctx, frames, accumulator, moments, pixels, sample_count, first_sample=None, sentinel=0x7fc0dead):
-    """rt_accumulate_list_frames: one launch of the list accumulate launcher. frames (samples, height, pitch, 4), accumulator and moments (height, pitch, 4) float32;
+    """rt_accumulate_list_frames: one launch of the accumulate step over a pixel list. frames (samples, height, pitch, 4), accumulator and moments (height, pitch, 4) float32;
     pixels: the list (x + y * width); sample_count: one entry per submission (first_sample likewise; it does not enter the fold). Returns (frames, accumulator,
     moments, final_image) after the launch."""
-    frames, accumulator, moments = _f32(frames).copy(), _f32(accumulator).copy(), _f32(moments).copy()
-    count = np.asarray(sample_count, np.int32).reshape(-1).copy()
-    first = np.full(len(count), 16, np.int32) if first_sample is None else np.asarray(first_sample, np.int32).reshape(-1).copy()
+    first_sample = np.full(np.size(sample_count), 16, np.int32) if first_sample is None else first_sample
+    frames, (accumulator, moments), first, count, final = _accumulate_staging(frames, (accumulator, moments), first_sample, sample_count, True)
     pixels = np.ascontiguousarray(pixels, np.uint32)
-    assert frames.ndim == 4 and frames.shape[0] == int(count.sum()) and frames.shape[1:] == accumulator.shape == moments.shape and len(first) == len(count)
-    final = np.zeros(accumulator.shape, np.float32)
     status = device_lib().rt_accumulate_list_frames(ctx, first.ctypes.data, count.ctypes.data, len(count), frames.ctypes.data, accumulator.ctypes.data, moments.ctypes.data,
                                                     pixels.ctypes.data, pixels.size, sentinel, final.ctypes.data)
     if status:

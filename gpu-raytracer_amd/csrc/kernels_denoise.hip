@@ -2,7 +2,7 @@
 //   prepare   (C, moments, A, N, P) -> (I, v) = (demodulated colour, variance of the mean's luminance) and the guide (n, z)
 //   pass k    one a-trous pass of step 2^k on (I, v) under the guide, tiled in LDS (kernel_denoise_pass_tiled) or plain (kernel_denoise_pass)
 //   finalize  (I, v) -> (I * a, v); the LAST pass does this in registers, the kernel of its own runs with 0 iterations only
-// A unit of its own: no existing unit's code object moves. Same contract as the other image kernels: -ffp-contract=off, every operation a plain IEEE
+// Same contract as the other image kernels: -ffp-contract=off, every operation a plain IEEE
 // float32 one in the order written, except the weight's log2 / exp2 / rcp, which are the hardware's (1 ulp each), as in edge_stopping_weights
 // of kernels_post.hip, whose form the weight below has.
 #include "rt_shading.h"
@@ -14,13 +14,12 @@
 #define RT_DENOISE_ROWS 8   // rows of pixels per workgroup (one wave each) of the tiled passes up to step 16; 4 at step 32
 #endif
 
-// Pixel of this thread in the untiled kernels: tiles of 64 x 4 pixels, XCD k takes the k-th eighth of the row-major tile sequence (post_tile_pixel of
-// kernels_post.hip, on explicit sizes). The launch is one-dimensional and padded to a multiple of 8 workgroups; false for a padding workgroup.
+// Pixel of this thread in the untiled kernels: tiles of 64 x 4 pixels, row-major, in XCD bands (xcd_tile of rt_shading.h has the reasons); false for a
+// padding workgroup and outside the image.
 RT_DEV bool denoise_tile_pixel(const RtDenoiseArgs & a, int & x, int & y) {
 	const unsigned tiles_x = (unsigned(a.pitch) + RT_DENOISE_BLOCK_X - 1) / RT_DENOISE_BLOCK_X;
 	const unsigned tiles_y = (unsigned(a.height) + RT_DENOISE_BLOCK_Y - 1) / RT_DENOISE_BLOCK_Y;
-	const unsigned tiles = tiles_x * tiles_y, per_xcd = gridDim.x / 8u;
-	const unsigned tile = (blockIdx.x % 8u) * per_xcd + blockIdx.x / 8u;
+	const unsigned tiles = tiles_x * tiles_y, tile = xcd_tile();
 	if (tile >= tiles) return false;
 	x = int(tile % tiles_x) * RT_DENOISE_BLOCK_X + int(threadIdx.x);
 	y = int(tile / tiles_x) * RT_DENOISE_BLOCK_Y + int(threadIdx.y);
@@ -28,10 +27,9 @@ RT_DEV bool denoise_tile_pixel(const RtDenoiseArgs & a, int & x, int & y) {
 }
 static unsigned denoise_grid(const RtDenoiseArgs & a) {
 	const unsigned tiles = ((unsigned(a.pitch) + RT_DENOISE_BLOCK_X - 1) / RT_DENOISE_BLOCK_X) * ((unsigned(a.height) + RT_DENOISE_BLOCK_Y - 1) / RT_DENOISE_BLOCK_Y);
-	return (tiles + 7) / 8 * 8;
+	return xcd_tile_grid(tiles);
 }
 
-RT_DEV bool finite3(float4 v) { return fabsf(v.x) < __builtin_huge_valf() && fabsf(v.y) < __builtin_huge_valf() && fabsf(v.z) < __builtin_huge_valf(); }
 // A guide is a surface's exactly when its normal is not the zero vector (a surface's is a unit vector).
 RT_DEV bool guide_is_surface(float4 g) { return g.x != 0.0f || g.y != 0.0f || g.z != 0.0f; }
 
@@ -45,13 +43,7 @@ __global__ void __launch_bounds__(256) kernel_denoise_prepare(RtDenoiseArgs a, R
 	const int pixel_index = x + y * a.pitch;
 	const float4 c = im.colour[pixel_index], m = im.moments[pixel_index], al = im.albedo[pixel_index], nr = im.normal[pixel_index], ps = im.position[pixel_index];
 	const bool valid = m.w >= 2.0f && fabsf(m.w) < __builtin_huge_valf() && finite3(c) && finite3(m) && finite3(al) && finite3(nr) && finite3(ps);
-	if (im.any_valid) {
-		// One lane of a wave with a valid pixel raises the flag, and only while it reads as 0: all but the first waves stop at the load. (A count, one atomic add per wave
-		// on one word, made this kernel 0.38 ms at 1080p for 0.04 ms of traffic: the L2 retires such atomics one after the other.)
-		const unsigned long long mask = __ballot(valid);
-		if (valid && int(lane_id()) == __ffsll((long long)mask) - 1 && __hip_atomic_load(im.any_valid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
-			__hip_atomic_store(im.any_valid, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	}
+	raise_any_valid(im.any_valid, valid);
 	const float nn = nr.x * nr.x + nr.y * nr.y + nr.z * nr.z;
 	if (!(valid && nn >= 0.25f)) {
 		if (valid) { im.iv[0][pixel_index] = make_float4(c.x, c.y, c.z, 0.0f); im.guide[pixel_index] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
@@ -181,8 +173,7 @@ __global__ void __launch_bounds__(64 * TY) kernel_denoise_pass_tiled(RtDenoiseAr
 	__shared__ float4 tile_iv[N], tile_g[N];
 	const unsigned tiles_x = (unsigned(a.width) + 63u) / 64u;
 	const unsigned blocks_y = (unsigned(a.height) + unsigned(TY * STEP) - 1u) / unsigned(TY * STEP);
-	const unsigned tiles = tiles_x * unsigned(STEP) * blocks_y, per_xcd = gridDim.x / 8u;
-	const unsigned tile = (blockIdx.x % 8u) * per_xcd + blockIdx.x / 8u;
+	const unsigned tiles = tiles_x * unsigned(STEP) * blocks_y, tile = xcd_tile();
 	if (tile >= tiles) return;   // (the whole workgroup: no barrier is left waiting)
 	const int x0 = int(tile % tiles_x) * 64;
 	const unsigned above = tile / tiles_x;
@@ -229,8 +220,8 @@ __global__ void __launch_bounds__(256) kernel_denoise_finalize(RtDenoiseArgs a, 
 template<int STEP, int TY>
 static void launch_denoise_tiled(const RtDenoiseArgs & a, bool final_pass, const float4 * iv_in, const float4 * guide, float4 * target, const float4 * albedo, hipStream_t stream) {
 	const unsigned tiles = ((unsigned(a.width) + 63u) / 64u) * unsigned(STEP) * ((unsigned(a.height) + unsigned(TY * STEP) - 1u) / unsigned(TY * STEP));
-	if (final_pass) hipLaunchKernelGGL((kernel_denoise_pass_tiled<STEP, TY, true>), dim3((tiles + 7) / 8 * 8), dim3(64 * TY), 0, stream, a, iv_in, guide, target, albedo);
-	else hipLaunchKernelGGL((kernel_denoise_pass_tiled<STEP, TY, false>), dim3((tiles + 7) / 8 * 8), dim3(64 * TY), 0, stream, a, iv_in, guide, target, albedo);
+	if (final_pass) hipLaunchKernelGGL((kernel_denoise_pass_tiled<STEP, TY, true>), dim3(xcd_tile_grid(tiles)), dim3(64 * TY), 0, stream, a, iv_in, guide, target, albedo);
+	else hipLaunchKernelGGL((kernel_denoise_pass_tiled<STEP, TY, false>), dim3(xcd_tile_grid(tiles)), dim3(64 * TY), 0, stream, a, iv_in, guide, target, albedo);
 }
 static void launch_denoise_tiled_step(const RtDenoiseArgs & a, int step, bool final_pass, const float4 * iv_in, const float4 * guide, float4 * target, const float4 * albedo, hipStream_t stream) {
 	switch (step) {   // LDS per workgroup: (64 + 2 STEP) x (TY + 2) x 32 B = 21.1 / 21.8 / 23.0 / 25.6 / 30.7 / 24.6 KB with 8 rows (4 at step 32)

@@ -1,8 +1,7 @@
-// kernels_post.hip -- image-space kernels: accumulate (with or without second moments), the noise estimate, SVGF (reproject / variance / a-trous /
-// finalize), TAA, plus the Kulla-Conty LUT integration kernels and a bandwidth probe.
+// kernels_post.hip -- image-space kernels: the noise estimate, the adaptive-sampling cell selection, SVGF (reproject / variance / a-trous /
+// finalize), TAA, plus the Kulla-Conty LUT integration kernels and a bandwidth probe. (The accumulate step is kernels_accumulate.hip.)
 //
-// Replaces kernel_accumulate (CUDA/Pathtracer.cu:775-796), the six kernels of
-// CUDA/SVGF/{SVGF,TAA}.h and the four LUT kernels of CUDA/KullaConty.h:83-240.
+// Replaces the six kernels of CUDA/SVGF/{SVGF,TAA}.h and the four LUT kernels of CUDA/KullaConty.h:83-240.
 // All of these stream pitch x height float4 images: HBM-bandwidth bound, so each thread
 // handles one pixel with 16-byte loads/stores and consecutive lanes touch consecutive
 // pixels (256 B per wave per access). CUDA surfaces become plain pitched arrays; reads the
@@ -12,19 +11,12 @@
 #define RT_POST_BLOCK_X 64
 #define RT_POST_BLOCK_Y 4
 
-// Pixel of this thread in the image-space kernels below (SVGF, TAA): tiles of 64 x 4 pixels, dealt to the workgroups so
-// that the tiles one XCD works on are NEIGHBOURS. Workgroup b runs on XCD b % 8 (MI355X_MICROARCH.md: observed, for speed
-// only) and every XCD has its own 4 MiB L2: with tile = workgroup index, horizontally adjacent tiles land on eight
-// different L2s, every XCD pulls the whole frame through the fabric, and a stencil's taps -- nine rows of three images in
-// an a-trous pass -- are fetched up to nine times from the Infinity Cache instead of once (measured: 0.078 ms per pass for
-// 0.17 GB of compulsory traffic). Here XCD k takes the k-th eighth of the row-major tile sequence, in order: a band of
-// ~135 rows at 1080p, swept top to bottom, whose taps stay in the band's own L2 lines.
-// The launch is one-dimensional and padded to a multiple of 8 workgroups; returns false for a padding workgroup.
+// Pixel of this thread in the image-space kernels below (SVGF, TAA): tiles of 64 x 4 pixels, row-major, in XCD bands (xcd_tile of rt_shading.h has the
+// reasons). Returns false for a padding workgroup.
 RT_DEV bool post_tile_pixel(const RtParams & p, int & x, int & y) {
 	const unsigned tiles_x = (unsigned(p.screen_pitch) + RT_POST_BLOCK_X - 1) / RT_POST_BLOCK_X;
 	const unsigned tiles_y = (unsigned(p.screen_height) + RT_POST_BLOCK_Y - 1) / RT_POST_BLOCK_Y;
-	const unsigned tiles = tiles_x * tiles_y, per_xcd = gridDim.x / 8u;
-	const unsigned tile = (blockIdx.x % 8u) * per_xcd + blockIdx.x / 8u;
+	const unsigned tiles = tiles_x * tiles_y, tile = xcd_tile();
 	if (tile >= tiles) return false;
 	x = int(tile % tiles_x) * RT_POST_BLOCK_X + int(threadIdx.x);
 	y = int(tile / tiles_x) * RT_POST_BLOCK_Y + int(threadIdx.y);
@@ -33,127 +25,6 @@ RT_DEV bool post_tile_pixel(const RtParams & p, int & x, int & y) {
 
 RT_DEV f4 ld4(const float4 * p, int i) { return mk4(p[i]); }
 RT_DEV void st4(float4 * p, int i, f4 v) { p[i] = to_float4(v); }
-
-// ---- accumulate ---------------------------------------------------------------------------------
-
-// One sample folded into the running mean, AOV.h:35-46: sample 0 sets the mean and sample 1 overwrites it (fb - acc over n = 1), the quirk every
-// comparison with the reference rests on. MOMENTS: Welford's second moment beside it, from the values the mean's own fold has just
-// computed -- d = fb - acc_old and acc_new -- in plain float32 -, /, *, +: m2 = (M2_r, M2_g, M2_b, w), w the number of samples the moment stands for.
-// Samples 0 and 1 leave (0, 0, 0, 1): after either the mean holds one sample alone.
-template<bool MOMENTS> RT_DEV f4 accumulate_fold(f4 acc, f4 & m2, f4 fb, float n) {   // n > 0
-	f4 d = fb - acc;
-	f4 next = acc + d / n;
-	if (MOMENTS) {
-		if (n >= 2.0f) { f4 t = d * (fb - next); m2 = mk4(m2.x + t.x, m2.y + t.y, m2.z + t.z, n); }
-		else m2 = mk4(0.0f, 0.0f, 0.0f, 1.0f);
-	}
-	return next;
-}
-
-// The samples of a batch are folded in one after the other, exactly as separate calls would.
-template<bool MOMENTS> RT_DEV f4 aov_accumulate(const RtParams & p, int aov, int pixel_index, float n, float4 * moments = nullptr) { // AOV.h:35-46
-	const RtAOV & a = p.aovs[aov];
-	if (!a.framebuffer) return mk4(0.0f);
-	f4 acc = mk4(0.0f), m2 = mk4(0.0f);
-	for (int s = 0; s < p.batch_samples; s++, n += 1.0f) {
-		f4 fb = mk4(a.framebuffer[size_t(s) * p.frame_pixels + pixel_index]);
-		if (n > 0.0f) { if (s == 0) { acc = mk4(a.accumulator[pixel_index]); if (MOMENTS) m2 = mk4(moments[pixel_index]); } acc = accumulate_fold<MOMENTS>(acc, m2, fb, n); }
-		else { acc = fb; if (MOMENTS) m2 = mk4(0.0f, 0.0f, 0.0f, 1.0f); }
-	}
-	a.accumulator[pixel_index] = to_float4(acc);
-	if (MOMENTS) moments[pixel_index] = to_float4(m2);
-	return acc;
-}
-
-__global__ void __launch_bounds__(256) kernel_accumulate(RtParams p, float frames_accumulated, int pixel_offset, int pixel_count) {
-	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < pixel_count; i += gridDim.x * blockDim.x) {
-		int idx = rt_map_pixel(p, i + pixel_offset);
-		int x = idx % p.screen_width, y = idx / p.screen_width;
-		int pixel_index = x + y * p.screen_pitch;
-
-		f4 colour = aov_accumulate<false>(p, RT_AOV_RADIANCE, pixel_index, frames_accumulated);
-		aov_accumulate<false>(p, RT_AOV_ALBEDO,   pixel_index, frames_accumulated);
-		aov_accumulate<false>(p, RT_AOV_NORMAL,   pixel_index, frames_accumulated);
-		aov_accumulate<false>(p, RT_AOV_POSITION, pixel_index, frames_accumulated);
-
-		if (!isfinite(colour.x + colour.y + colour.z)) colour = mk4(1000.0f, 0.0f, 1000.0f, 1.0f); // NaN guard, Pathtracer.cu:790-793
-		p.final_image[pixel_index] = to_float4(colour);
-	}
-}
-// ... and the second moment of RADIANCE beside its mean (rt_set_noise_estimate): one more float4 read and written per pixel. (The loop is written out in each
-// kernel: shared through a device function, the plain kernels' code objects came out different from what they were.)
-__global__ void __launch_bounds__(256) kernel_accumulate_moments(RtParams p, float frames_accumulated, int pixel_offset, int pixel_count, float4 * moments) {
-	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < pixel_count; i += gridDim.x * blockDim.x) {
-		int idx = rt_map_pixel(p, i + pixel_offset);
-		int x = idx % p.screen_width, y = idx / p.screen_width;
-		int pixel_index = x + y * p.screen_pitch;
-
-		f4 colour = aov_accumulate<true>(p, RT_AOV_RADIANCE, pixel_index, frames_accumulated, moments);
-		aov_accumulate<false>(p, RT_AOV_ALBEDO,   pixel_index, frames_accumulated);
-		aov_accumulate<false>(p, RT_AOV_NORMAL,   pixel_index, frames_accumulated);
-		aov_accumulate<false>(p, RT_AOV_POSITION, pixel_index, frames_accumulated);
-
-		if (!isfinite(colour.x + colour.y + colour.z)) colour = mk4(1000.0f, 0.0f, 1000.0f, 1.0f); // NaN guard, Pathtracer.cu:790-793
-		p.final_image[pixel_index] = to_float4(colour);
-	}
-}
-
-// Merged wavefront: the submissions that complete in one iteration (up to RT_ACCUMULATE_GROUP of them, in submission
-// order) folded into the accumulators by ONE launch -- the same operations in the same order as one launch per submission,
-// with the accumulator kept in registers in between -- and the per-sample frames cleared on the way (aovs_clear_to_zero:
-// only the pixels this context renders were ever written, a memset of the whole frames moved 8x the bytes on a 1/8 split).
-template<bool MOMENTS> RT_DEV f4 aov_accumulate_group(const RtParams & p, const RtAccumulateGroup & g, int aov, int pixel_index, float4 * moments = nullptr) {
-	const RtAOV & a = p.aovs[aov];
-	if (!a.framebuffer) return mk4(0.0f);
-	f4 acc = mk4(0.0f), m2 = mk4(0.0f);
-	bool loaded = false;
-	for (int k = 0; k < g.count; k++) {
-		float n = float(g.first_sample[k]);
-		float4 * frames = a.framebuffer + size_t(g.slot_base[k]) * p.frame_pixels;
-		for (int s = 0; s < g.sample_count[k]; s++, n += 1.0f) {
-			float4 * sample = frames + size_t(s) * p.frame_pixels + pixel_index;
-			f4 fb = mk4(*sample);
-			*sample = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-			if (n > 0.0f) { if (!loaded) { acc = mk4(a.accumulator[pixel_index]); if (MOMENTS) m2 = mk4(moments[pixel_index]); } acc = accumulate_fold<MOMENTS>(acc, m2, fb, n); }
-			else { acc = fb; if (MOMENTS) m2 = mk4(0.0f, 0.0f, 0.0f, 1.0f); }
-			loaded = true;
-		}
-	}
-	a.accumulator[pixel_index] = to_float4(acc);
-	if (MOMENTS) moments[pixel_index] = to_float4(m2);
-	return acc;
-}
-
-__global__ void __launch_bounds__(256) kernel_accumulate_group(RtParams p, RtAccumulateGroup g, int pixel_offset, int pixel_count) {
-	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < pixel_count; i += gridDim.x * blockDim.x) {
-		int idx = rt_map_pixel(p, i + pixel_offset);
-		int x = idx % p.screen_width, y = idx / p.screen_width;
-		int pixel_index = x + y * p.screen_pitch;
-
-		f4 colour = aov_accumulate_group<false>(p, g, RT_AOV_RADIANCE, pixel_index);
-		aov_accumulate_group<false>(p, g, RT_AOV_ALBEDO,   pixel_index);
-		aov_accumulate_group<false>(p, g, RT_AOV_NORMAL,   pixel_index);
-		aov_accumulate_group<false>(p, g, RT_AOV_POSITION, pixel_index);
-
-		if (!isfinite(colour.x + colour.y + colour.z)) colour = mk4(1000.0f, 0.0f, 1000.0f, 1.0f); // NaN guard, Pathtracer.cu:790-793
-		p.final_image[pixel_index] = to_float4(colour);
-	}
-}
-__global__ void __launch_bounds__(256) kernel_accumulate_group_moments(RtParams p, RtAccumulateGroup g, int pixel_offset, int pixel_count, float4 * moments) {
-	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < pixel_count; i += gridDim.x * blockDim.x) {
-		int idx = rt_map_pixel(p, i + pixel_offset);
-		int x = idx % p.screen_width, y = idx / p.screen_width;
-		int pixel_index = x + y * p.screen_pitch;
-
-		f4 colour = aov_accumulate_group<true>(p, g, RT_AOV_RADIANCE, pixel_index, moments);
-		aov_accumulate_group<false>(p, g, RT_AOV_ALBEDO,   pixel_index);
-		aov_accumulate_group<false>(p, g, RT_AOV_NORMAL,   pixel_index);
-		aov_accumulate_group<false>(p, g, RT_AOV_POSITION, pixel_index);
-
-		if (!isfinite(colour.x + colour.y + colour.z)) colour = mk4(1000.0f, 0.0f, 1000.0f, 1.0f); // NaN guard, Pathtracer.cu:790-793
-		p.final_image[pixel_index] = to_float4(colour);
-	}
-}
 
 // ---- noise estimate (rt_estimate_noise) ----------------------------------------------------------------
 // One workgroup per cell of RT_NOISE_CELL x RT_NOISE_CELL pixels of the screen (not of the pitch: the padding columns are never read), edge cells
@@ -287,51 +158,6 @@ void rt_launch_select_cells(const double * cell_sums, const int * cell_counts, c
 	hipLaunchKernelGGL(kernel_select_cells, dim3((cells + 255) / 256), dim3(256), 0, stream, cell_sums, cell_counts, cell_nonfinite, width, height, cells_x, cells_y, threshold, dilate, flags, active_pixels);
 	hipLaunchKernelGGL(kernel_scan_cells, dim3(1), dim3(256), 0, stream, active_pixels, flags, cells, offsets, totals);
 	hipLaunchKernelGGL(kernel_compact_cells, dim3(cells), dim3(RT_NOISE_CELL * RT_NOISE_CELL), 0, stream, flags, offsets, width, height, cells_x, list);
-}
-
-// The accumulate step of list submissions (rt_set_pixel_list): entry i of `list` names the pixel, and the fold index is the PIXEL'S OWN -- n = w + 1 at load, w
-// the number of samples its moments stand for, then n + 1 for every further sample of the group; the submissions' first_sample does not enter. All four AOVs fold
-// with that n. w = 0 (never sampled) gives n = 1: the mean takes the sample, the moments become (0, 0, 0, 1); w = 1 gives n = 2, the Welford step proper.
-// Only the list's pixels were written in the sample frames, and only they are cleared.
-template<bool MOMENTS> RT_DEV f4 aov_accumulate_list(const RtParams & p, const RtAccumulateGroup & g, int aov, int pixel_index, float n, float4 * moments = nullptr) {
-	const RtAOV & a = p.aovs[aov];
-	if (!a.framebuffer) return mk4(0.0f);
-	f4 acc = mk4(a.accumulator[pixel_index]), m2 = mk4(0.0f);
-	if (MOMENTS) m2 = mk4(moments[pixel_index]);
-	for (int k = 0; k < g.count; k++) {
-		float4 * frames = a.framebuffer + size_t(g.slot_base[k]) * p.frame_pixels;
-		for (int s = 0; s < g.sample_count[k]; s++, n += 1.0f) {
-			float4 * sample = frames + size_t(s) * p.frame_pixels + pixel_index;
-			f4 fb = mk4(*sample);
-			*sample = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-			acc = accumulate_fold<MOMENTS>(acc, m2, fb, n);
-		}
-	}
-	a.accumulator[pixel_index] = to_float4(acc);
-	if (MOMENTS) moments[pixel_index] = to_float4(m2);
-	return acc;
-}
-__global__ void __launch_bounds__(256) kernel_accumulate_group_list_moments(RtParams p, RtAccumulateGroup g, const unsigned * __restrict__ list, int pixel_count, float4 * moments) {
-	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < pixel_count; i += gridDim.x * blockDim.x) {
-		int idx = int(list[i]);
-		int x = idx % p.screen_width, y = idx / p.screen_width;
-		int pixel_index = x + y * p.screen_pitch;
-		float n = moments[pixel_index].w + 1.0f;
-
-		f4 colour = aov_accumulate_list<true>(p, g, RT_AOV_RADIANCE, pixel_index, n, moments);
-		aov_accumulate_list<false>(p, g, RT_AOV_ALBEDO,   pixel_index, n);
-		aov_accumulate_list<false>(p, g, RT_AOV_NORMAL,   pixel_index, n);
-		aov_accumulate_list<false>(p, g, RT_AOV_POSITION, pixel_index, n);
-
-		if (!isfinite(colour.x + colour.y + colour.z)) colour = mk4(1000.0f, 0.0f, 1000.0f, 1.0f); // NaN guard, Pathtracer.cu:790-793
-		p.final_image[pixel_index] = to_float4(colour);
-	}
-}
-void rt_launch_accumulate_group_list(const RtParams & p, const RtAccumulateGroup & group, const unsigned * list, int pixel_count, hipStream_t stream, float4 * moments) {
-	int blocks = (pixel_count + 255) / 256;
-	if (blocks > 4096) blocks = 4096;
-	if (blocks < 1) blocks = 1;
-	hipLaunchKernelGGL(kernel_accumulate_group_list_moments, dim3(blocks), dim3(256), 0, stream, p, group, list, pixel_count, moments);
 }
 
 // ---- SVGF ----------------------------------------------------------------------------------------
@@ -784,8 +610,7 @@ __global__ void __launch_bounds__(64 * TY) kernel_svgf_atrous_tiled(RtParams p, 
 	__shared__ float4 tile_d[N], tile_i[N], tile_nd[N];
 	const unsigned tiles_x = (unsigned(p.screen_width) + 63u) / 64u;
 	const unsigned blocks_y = (unsigned(p.screen_height) + unsigned(TY * STEP) - 1u) / unsigned(TY * STEP);
-	const unsigned tiles = tiles_x * unsigned(STEP) * blocks_y, per_xcd = gridDim.x / 8u;
-	const unsigned tile = (blockIdx.x % 8u) * per_xcd + blockIdx.x / 8u;
+	const unsigned tiles = tiles_x * unsigned(STEP) * blocks_y, tile = xcd_tile();
 	if (tile >= tiles) return;   // (the whole workgroup: no barrier is left waiting)
 	const int x0 = int(tile % tiles_x) * 64;
 	const unsigned above = tile / tiles_x;
@@ -820,8 +645,8 @@ __global__ void __launch_bounds__(64 * TY) kernel_svgf_atrous_tiled(RtParams p, 
 template<int STEP, int TY>
 static void launch_atrous_tiled(const RtParams & p, bool final_pass, const float4 * d_in, const float4 * i_in, float4 * d_out, float4 * i_out, const float2 * variance_in, float2 * variance_out, hipStream_t stream) {
 	const unsigned tiles = ((unsigned(p.screen_width) + 63u) / 64u) * unsigned(STEP) * ((unsigned(p.screen_height) + unsigned(TY * STEP) - 1u) / unsigned(TY * STEP));
-	if (final_pass) hipLaunchKernelGGL((kernel_svgf_atrous_tiled<STEP, TY, true>), dim3((tiles + 7) / 8 * 8), dim3(64 * TY), 0, stream, p, d_in, i_in, d_out, i_out, variance_in, variance_out);
-	else hipLaunchKernelGGL((kernel_svgf_atrous_tiled<STEP, TY, false>), dim3((tiles + 7) / 8 * 8), dim3(64 * TY), 0, stream, p, d_in, i_in, d_out, i_out, variance_in, variance_out);
+	if (final_pass) hipLaunchKernelGGL((kernel_svgf_atrous_tiled<STEP, TY, true>), dim3(xcd_tile_grid(tiles)), dim3(64 * TY), 0, stream, p, d_in, i_in, d_out, i_out, variance_in, variance_out);
+	else hipLaunchKernelGGL((kernel_svgf_atrous_tiled<STEP, TY, false>), dim3(xcd_tile_grid(tiles)), dim3(64 * TY), 0, stream, p, d_in, i_in, d_out, i_out, variance_in, variance_out);
 }
 // false: no tiled form for this step size (more than six iterations): the caller launches kernel_svgf_atrous
 static bool launch_atrous_tiled_step(const RtParams & p, int step_size, bool final_pass, const float4 * d_in, const float4 * i_in, float4 * d_out, float4 * i_out, const float2 * variance_in, float2 * variance_out, hipStream_t stream) {
@@ -916,7 +741,7 @@ __global__ void __launch_bounds__(256) kernel_taa(RtParams p, int sample_index) 
 void rt_launch_svgf_taa(const RtParams & p, int sample_index, hipStream_t stream, void (*mark)(void * user, int svgf_kernel, hipStream_t stream), void * user) {
 	dim3 block(RT_POST_BLOCK_X, RT_POST_BLOCK_Y);
 	const unsigned tiles = ((p.screen_pitch + block.x - 1) / block.x) * ((p.screen_height + block.y - 1) / block.y);
-	dim3 grid((tiles + 7) / 8 * 8);   // post_tile_pixel: XCD k sweeps the k-th eighth of the tiles
+	dim3 grid(xcd_tile_grid(tiles));
 	#define RT_TIMED(k, launch) { if (mark) mark(user, k, stream); launch; if (mark) mark(user, k, stream); }
 
 	float4 * direct_in    = p.aovs[RT_AOV_RADIANCE_DIRECT].framebuffer;
@@ -954,23 +779,6 @@ void rt_launch_svgf_taa(const RtParams & p, int sample_index, hipStream_t stream
 		RT_TIMED(4, hipLaunchKernelGGL(kernel_taa, grid, block, 0, stream, p, sample_index));   // (the caller swaps taa_frame_prev / taa_frame_next)
 	}
 	#undef RT_TIMED
-}
-
-// moments: null for the plain kernel, else the second-moment image the ..._moments kernel keeps beside the RADIANCE mean (rt_set_noise_estimate)
-void rt_launch_accumulate(const RtParams & p, float frames_accumulated, int pixel_offset, int pixel_count, hipStream_t stream, float4 * moments) {
-	int blocks = (pixel_count + 255) / 256;
-	if (blocks > 4096) blocks = 4096;
-	if (blocks < 1) blocks = 1;
-	if (moments) hipLaunchKernelGGL(kernel_accumulate_moments, dim3(blocks), dim3(256), 0, stream, p, frames_accumulated, pixel_offset, pixel_count, moments);
-	else hipLaunchKernelGGL(kernel_accumulate, dim3(blocks), dim3(256), 0, stream, p, frames_accumulated, pixel_offset, pixel_count);
-}
-
-void rt_launch_accumulate_group(const RtParams & p, const RtAccumulateGroup & group, int pixel_offset, int pixel_count, hipStream_t stream, float4 * moments) {
-	int blocks = (pixel_count + 255) / 256;
-	if (blocks > 4096) blocks = 4096;
-	if (blocks < 1) blocks = 1;
-	if (moments) hipLaunchKernelGGL(kernel_accumulate_group_moments, dim3(blocks), dim3(256), 0, stream, p, group, pixel_offset, pixel_count, moments);
-	else hipLaunchKernelGGL(kernel_accumulate_group, dim3(blocks), dim3(256), 0, stream, p, group, pixel_offset, pixel_count);
 }
 
 // ---- Kulla-Conty LUT integration (KullaConty.h:83-240) -------------------------------------------------------

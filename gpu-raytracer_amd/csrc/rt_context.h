@@ -326,7 +326,7 @@ int denoise_arguments(rt_context * ctx, const char * caller, const rt_denoise_pa
 int sync_firefly_tiers(rt_context * ctx);
 int firefly_tiers_zero(rt_context * ctx);
 void firefly_free(rt_context * ctx);
-bool firefly_tiers_for(rt_context * ctx, const RtParams & p, RtFireflyTiers * out);
+RtFireflyTiers firefly_tiers_for(rt_context * ctx, const RtParams & p);
 int firefly_arguments(rt_context * ctx, const char * caller, int tiers, float start, float support);
 #pragma GCC visibility pop
 

@@ -38,13 +38,12 @@ int firefly_tiers_zero(rt_context * ctx) {
 	RT_HIP(ctx, hipMemset(ctx->firefly_tiers, 0, ctx->frame_pixels * 16 * size_t(ctx->firefly.tiers)));
 	return RT_OK;
 }
-// What an accumulate launch under parameter block p with a moments image splats into: false (the plain ..._moments kernels, as before) while the cascade is off
-// or the launch is an SVGF frame's. Counts the launch as a fold either way it goes.
-bool firefly_tiers_for(rt_context * ctx, const RtParams & p, RtFireflyTiers * out) {
+// What an accumulate launch under parameter block p with a moments image splats into: none (tiers null: the plain kernels) while the cascade is off or the
+// launch is an SVGF frame's. Counts the launch as a fold either way it goes.
+RtFireflyTiers firefly_tiers_for(rt_context * ctx, const RtParams & p) {
 	ctx->folds++;
-	if (!ctx->firefly_tiers || !ctx->noise_moments || p.config.enable_svgf) return false;
-	*out = { (float4 *)ctx->firefly_tiers, ctx->frame_pixels, ctx->firefly.tiers, ctx->firefly.start };
-	return true;
+	if (!ctx->firefly_tiers || !ctx->noise_moments || p.config.enable_svgf) return { };
+	return { (float4 *)ctx->firefly_tiers, ctx->frame_pixels, ctx->firefly.tiers, ctx->firefly.start };
 }
 
 // rt_resolve_fireflies and rt_resolve_fireflies_timed (kernel_ms != nullptr)

@@ -1028,56 +1028,77 @@ int rt_shade_rays(rt_context * ctx, int merged, int step, int sample_index, int 
 	return probe.read(gbuffer_screen_position_prev, g_sp, pixels * 8);
 }
 
-// rt_accumulate_frames: the accumulate launch (rt_launch_accumulate or rt_launch_accumulate_group, as rt_render_samples and stream_complete call them) on explicit
-// images. The parameter block is the context's with every AOV but RADIANCE taken away, RADIANCE's frames and accumulator and the final image replaced by
-// buffers of this call; the pixel set is the context's. Runs on the main stream after quiesce().
-int rt_accumulate_frames(rt_context * ctx, int merged, const int32_t * first_sample, const int32_t * sample_count, size_t submissions,
-                         float * frames, float * accumulator, float * moments, uint32_t sentinel, float * final_image) {
-	RT_REQUIRE(ctx, ctx != nullptr, "rt_accumulate_frames: NULL context");
-	RT_REQUIRE(ctx, merged == 0 || merged == 1, "rt_accumulate_frames: merged must be 0 (one batch) or 1 (a group of submissions)");
-	RT_REQUIRE(ctx, first_sample && sample_count && frames && accumulator && final_image, "rt_accumulate_frames: NULL array");
-	RT_REQUIRE(ctx, submissions >= 1 && submissions <= size_t(merged ? RT_ACCUMULATE_GROUP : 1), merged ? "rt_accumulate_frames: 1 to RT_ACCUMULATE_GROUP submissions" : "rt_accumulate_frames: the batch form takes one submission");
+// The three accumulate probes -- rt_accumulate_frames, rt_accumulate_list_frames, rt_accumulate_cascade_frames -- after their own NULL and mode checks: ONE
+// launch of rt_launch_accumulate, as rt_render_samples (merged false: a batch) and stream_complete (merged: a group) make it, on explicit images. The parameter
+// block is the context's with every AOV but RADIANCE taken away, RADIANCE's frames and accumulator and the final image replaced by buffers of this call. list
+// null: the pixel set is the context's, which must not cover a list (without_list: where to go then). indices_enter: first_sample reaches the fold, so it is
+// held below 2^24. moments, and cascade with tiers, may be null. Runs on the main stream after quiesce().
+static int accumulate_probe(rt_context * ctx, const char * name, bool merged, bool indices_enter, const char * without_list, const int32_t * first_sample, const int32_t * sample_count,
+                            size_t submissions, float * frames, float * accumulator, float * moments, const uint32_t * list, size_t list_count, const rt_firefly_params * cascade,
+                            float * tiers, uint32_t sentinel, float * final_image) {
+	if (submissions < 1 || submissions > size_t(merged ? RT_ACCUMULATE_GROUP : 1))
+		return fail(ctx, RT_ERROR_INVALID_ARG, merged ? "%s: 1 to RT_ACCUMULATE_GROUP submissions" : "%s: the batch form takes one submission", name);
+	RtAccumulate a = { };
 	size_t total = 0;
 	for (size_t k = 0; k < submissions; k++) {
-		RT_REQUIRE(ctx, first_sample[k] >= 0 && sample_count[k] >= 1 && sample_count[k] <= RT_STREAM_SAMPLE_SLOTS, "rt_accumulate_frames: a first sample below 0 or a sample count outside [1, 512]");
-		RT_REQUIRE(ctx, merged || sample_count[k] <= RT_MAX_BATCH_SAMPLES, "rt_accumulate_frames: a batch holds at most 16 samples");
-		RT_REQUIRE(ctx, size_t(first_sample[k]) + size_t(sample_count[k]) <= size_t(1) << 24, "rt_accumulate_frames: sample indices must stay below 2^24");
+		if (first_sample[k] < 0 || sample_count[k] < 1 || sample_count[k] > RT_STREAM_SAMPLE_SLOTS) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: a first sample below 0 or a sample count outside [1, 512]", name);
+		if (!merged && sample_count[k] > RT_MAX_BATCH_SAMPLES) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: a batch holds at most 16 samples", name);
+		if (indices_enter && size_t(first_sample[k]) + size_t(sample_count[k]) > size_t(1) << 24) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: sample indices must stay below 2^24", name);
+		a.group.first_sample[k] = first_sample[k]; a.group.sample_count[k] = sample_count[k]; a.group.slot_base[k] = int(total);
 		total += size_t(sample_count[k]);
 	}
+	a.group.count = int(submissions); a.clear = merged;
 	(void)hipSetDevice(ctx->device);
 	const size_t frame_pixels = ctx->frame_pixels;
-	if (frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_accumulate_frames: rt_resize was not called");
-	RT_REQUIRE(ctx, total <= size_t(RT_STREAM_SAMPLE_SLOTS) && total * frame_pixels < size_t(1) << 30, "rt_accumulate_frames: at most 512 samples and fewer than 2^30 pixels in all");
-	if (ctx->pixel_list_on) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_accumulate_frames: the context covers a pixel list (rt_set_pixel_list); rt_accumulate_list_frames is the probe of that launch");
-	int range_offset = 0, range_count = 0;
-	int s = resolve_pixel_range(ctx, "rt_accumulate_frames", &range_offset, &range_count); if (s) return s;
+	if (frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "%s: rt_resize was not called", name);
+	if (total > size_t(RT_STREAM_SAMPLE_SLOTS) || total * frame_pixels >= size_t(1) << 30) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: at most 512 samples and fewer than 2^30 pixels in all", name);
+	int s;
+	if (list) {   // before any launch: every entry inside the frame, no pixel twice (two threads folding one pixel would race)
+		const size_t frame = size_t(ctx->params.screen_width) * size_t(ctx->params.screen_height);
+		if (list_count < 1 || list_count > frame) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: the list holds 1 to width * height entries", name);
+		std::vector<bool> seen(frame, false);
+		for (size_t i = 0; i < list_count; i++) {
+			if (list[i] >= frame) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: list entry %zu (%u) lies outside the %zu pixel frame", name, i, list[i], frame);
+			if (seen[list[i]]) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: list entry %zu names pixel %u a second time", name, i, list[i]);
+			seen[list[i]] = true;
+		}
+		a.pixel_count = int(list_count);
+	} else {
+		if (ctx->pixel_list_on) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: the context covers a pixel list (rt_set_pixel_list); %s", name, without_list);
+		if ((s = resolve_pixel_range(ctx, name, &a.pixel_offset, &a.pixel_count))) return s;
+	}
 	RT_HIP(ctx, quiesce(ctx));
 
-	Probe probe(ctx, "rt_accumulate_frames");
+	Probe probe(ctx, name);
+	const size_t tier_pixels = cascade ? frame_pixels * size_t(cascade->tiers) : 0;
 	float4 * dev_frames = probe.array<float4>(total * frame_pixels, frames);
 	float4 * dev_accumulator = probe.array<float4>(frame_pixels, accumulator);
-	float4 * dev_moments = moments ? probe.array<float4>(frame_pixels, moments) : nullptr;
+	if (moments) a.moments = probe.array<float4>(frame_pixels, moments);
+	if (cascade) a.tiers = { probe.array<float4>(tier_pixels, tiers), frame_pixels, cascade->tiers, cascade->start };
+	if (list) a.list = probe.array<unsigned>(list_count, list);
 	probe.staging.assign(frame_pixels * 4, sentinel);
 	float4 * dev_final = (float4 *)probe.array<uint32_t>(frame_pixels * 4, probe.staging.data());
 	if ((s = probe.allocated())) return s;
 
 	RtParams p = ctx->params;
-	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = p.aovs[a].accumulator = nullptr;
+	for (int v = 0; v < RT_AOV_COUNT; v++) p.aovs[v].framebuffer = p.aovs[v].accumulator = nullptr;
 	p.aovs[RT_AOV_RADIANCE].framebuffer = dev_frames; p.aovs[RT_AOV_RADIANCE].accumulator = dev_accumulator;
 	p.final_image = dev_final;
-	if (merged) {
-		RtAccumulateGroup group; group.count = int(submissions);
-		for (int k = 0, base = 0; k < group.count; k++) { group.first_sample[k] = first_sample[k]; group.sample_count[k] = sample_count[k]; group.slot_base[k] = base; base += sample_count[k]; }
-		for (int k = group.count; k < RT_ACCUMULATE_GROUP; k++) group.first_sample[k] = group.sample_count[k] = group.slot_base[k] = 0;
-		rt_launch_accumulate_group(p, group, range_offset, range_count, ctx->stream, dev_moments);
-	} else {
-		p.batch_samples = sample_count[0];
-		rt_launch_accumulate(p, float(first_sample[0]), range_offset, range_count, ctx->stream, dev_moments);
-	}
+	rt_launch_accumulate(p, a, ctx->stream);
 	if ((s = probe.finish())) return s;
 	if ((s = probe.read(frames, dev_frames, total * frame_pixels * 16)) || (s = probe.read(accumulator, dev_accumulator, frame_pixels * 16))) return s;
-	if (moments && (s = probe.read(moments, dev_moments, frame_pixels * 16))) return s;
+	if (moments && (s = probe.read(moments, a.moments, frame_pixels * 16))) return s;
+	if (cascade && (s = probe.read(tiers, a.tiers.tiers, tier_pixels * 16))) return s;
 	return probe.read(final_image, dev_final, frame_pixels * 16);
+}
+
+int rt_accumulate_frames(rt_context * ctx, int merged, const int32_t * first_sample, const int32_t * sample_count, size_t submissions,
+                         float * frames, float * accumulator, float * moments, uint32_t sentinel, float * final_image) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_accumulate_frames: NULL context");
+	RT_REQUIRE(ctx, merged == 0 || merged == 1, "rt_accumulate_frames: merged must be 0 (one batch) or 1 (a group of submissions)");
+	RT_REQUIRE(ctx, first_sample && sample_count && frames && accumulator && final_image, "rt_accumulate_frames: NULL array");
+	return accumulate_probe(ctx, "rt_accumulate_frames", merged != 0, true, "rt_accumulate_list_frames is the probe of that launch", first_sample, sample_count, submissions, frames, accumulator,
+	                        moments, nullptr, 0, nullptr, nullptr, sentinel, final_image);
 }
 
 int rt_estimate_noise_images(rt_context * ctx, const float * mean, const float * moments, float floor, rt_noise_estimate * out, double * cell_sums,
@@ -1140,51 +1161,10 @@ int rt_accumulate_list_frames(rt_context * ctx, const int32_t * first_sample, co
                               float * frames, float * accumulator, float * moments, const uint32_t * list, size_t list_count, uint32_t sentinel, float * final_image) {
 	RT_REQUIRE(ctx, ctx != nullptr, "rt_accumulate_list_frames: NULL context");
 	RT_REQUIRE(ctx, first_sample && sample_count && frames && accumulator && moments && list && final_image, "rt_accumulate_list_frames: NULL array");
-	RT_REQUIRE(ctx, submissions >= 1 && submissions <= size_t(RT_ACCUMULATE_GROUP), "rt_accumulate_list_frames: 1 to RT_ACCUMULATE_GROUP submissions");
-	size_t total = 0;
-	for (size_t k = 0; k < submissions; k++) {
-		RT_REQUIRE(ctx, first_sample[k] >= 0 && sample_count[k] >= 1 && sample_count[k] <= RT_STREAM_SAMPLE_SLOTS, "rt_accumulate_list_frames: a first sample below 0 or a sample count outside [1, 512]");
-		total += size_t(sample_count[k]);
-	}
-	(void)hipSetDevice(ctx->device);
-	const size_t frame_pixels = ctx->frame_pixels;
-	if (frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_accumulate_list_frames: rt_resize was not called");
-	RT_REQUIRE(ctx, total <= size_t(RT_STREAM_SAMPLE_SLOTS) && total * frame_pixels < size_t(1) << 30, "rt_accumulate_list_frames: at most 512 samples and fewer than 2^30 pixels in all");
-	// before any launch: every entry inside the frame, no pixel twice (two threads folding one pixel would race)
-	const size_t frame = size_t(ctx->params.screen_width) * size_t(ctx->params.screen_height);
-	RT_REQUIRE(ctx, list_count >= 1 && list_count <= frame, "rt_accumulate_list_frames: the list holds 1 to width * height entries");
-	std::vector<bool> seen(frame, false);
-	for (size_t i = 0; i < list_count; i++) {
-		if (list[i] >= frame) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_accumulate_list_frames: list entry %zu (%u) lies outside the %zu pixel frame", i, list[i], frame);
-		if (seen[list[i]]) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_accumulate_list_frames: list entry %zu names pixel %u a second time", i, list[i]);
-		seen[list[i]] = true;
-	}
-	RT_HIP(ctx, quiesce(ctx));
-
-	Probe probe(ctx, "rt_accumulate_list_frames");
-	float4 * dev_frames = probe.array<float4>(total * frame_pixels, frames);
-	float4 * dev_accumulator = probe.array<float4>(frame_pixels, accumulator);
-	float4 * dev_moments = probe.array<float4>(frame_pixels, moments);
-	unsigned * dev_list = probe.array<unsigned>(list_count, list);
-	probe.staging.assign(frame_pixels * 4, sentinel);
-	float4 * dev_final = (float4 *)probe.array<uint32_t>(frame_pixels * 4, probe.staging.data());
-	int s = probe.allocated(); if (s) return s;
-
-	RtParams p = ctx->params;
-	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = p.aovs[a].accumulator = nullptr;
-	p.aovs[RT_AOV_RADIANCE].framebuffer = dev_frames; p.aovs[RT_AOV_RADIANCE].accumulator = dev_accumulator;
-	p.final_image = dev_final;
-	RtAccumulateGroup group; group.count = int(submissions);
-	for (int k = 0, base = 0; k < group.count; k++) { group.first_sample[k] = first_sample[k]; group.sample_count[k] = sample_count[k]; group.slot_base[k] = base; base += sample_count[k]; }
-	for (int k = group.count; k < RT_ACCUMULATE_GROUP; k++) group.first_sample[k] = group.sample_count[k] = group.slot_base[k] = 0;
-	rt_launch_accumulate_group_list(p, group, dev_list, int(list_count), ctx->stream, dev_moments);
-	if ((s = probe.finish())) return s;
-	if ((s = probe.read(frames, dev_frames, total * frame_pixels * 16)) || (s = probe.read(accumulator, dev_accumulator, frame_pixels * 16))) return s;
-	if ((s = probe.read(moments, dev_moments, frame_pixels * 16))) return s;
-	return probe.read(final_image, dev_final, frame_pixels * 16);
+	return accumulate_probe(ctx, "rt_accumulate_list_frames", true, false, nullptr, first_sample, sample_count, submissions, frames, accumulator, moments, list, list_count, nullptr, nullptr,
+	                        sentinel, final_image);
 }
 
-// rt_accumulate_frames and rt_accumulate_list_frames with the cascade: the same parameter block and checks, ONE launch of the production launcher.
 int rt_accumulate_cascade_frames(rt_context * ctx, int merged, const int32_t * first_sample, const int32_t * sample_count, size_t submissions, float * frames,
                                  float * accumulator, float * moments, const uint32_t * list, size_t list_count, const rt_firefly_params * params, float * tiers,
                                  uint32_t sentinel, float * final_image) {
@@ -1193,63 +1173,8 @@ int rt_accumulate_cascade_frames(rt_context * ctx, int merged, const int32_t * f
 	RT_REQUIRE(ctx, first_sample && sample_count && frames && accumulator && moments && params && tiers && final_image, "rt_accumulate_cascade_frames: NULL array");
 	RT_REQUIRE(ctx, !list || merged, "rt_accumulate_cascade_frames: a pixel list takes the merged form");
 	int s = firefly_arguments(ctx, "rt_accumulate_cascade_frames", params->tiers, params->start, params->support); if (s) return s;
-	RT_REQUIRE(ctx, submissions >= 1 && submissions <= size_t(merged ? RT_ACCUMULATE_GROUP : 1), merged ? "rt_accumulate_cascade_frames: 1 to RT_ACCUMULATE_GROUP submissions" : "rt_accumulate_cascade_frames: the batch form takes one submission");
-	size_t total = 0;
-	for (size_t k = 0; k < submissions; k++) {
-		RT_REQUIRE(ctx, first_sample[k] >= 0 && sample_count[k] >= 1 && sample_count[k] <= RT_STREAM_SAMPLE_SLOTS, "rt_accumulate_cascade_frames: a first sample below 0 or a sample count outside [1, 512]");
-		RT_REQUIRE(ctx, merged || sample_count[k] <= RT_MAX_BATCH_SAMPLES, "rt_accumulate_cascade_frames: a batch holds at most 16 samples");
-		RT_REQUIRE(ctx, size_t(first_sample[k]) + size_t(sample_count[k]) <= size_t(1) << 24, "rt_accumulate_cascade_frames: sample indices must stay below 2^24");
-		total += size_t(sample_count[k]);
-	}
-	(void)hipSetDevice(ctx->device);
-	const size_t frame_pixels = ctx->frame_pixels;
-	if (frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_accumulate_cascade_frames: rt_resize was not called");
-	RT_REQUIRE(ctx, total <= size_t(RT_STREAM_SAMPLE_SLOTS) && total * frame_pixels < size_t(1) << 30, "rt_accumulate_cascade_frames: at most 512 samples and fewer than 2^30 pixels in all");
-	int range_offset = 0, range_count = 0;
-	if (list) {   // before any launch: every entry inside the frame, no pixel twice (two threads folding one pixel would race)
-		const size_t frame = size_t(ctx->params.screen_width) * size_t(ctx->params.screen_height);
-		RT_REQUIRE(ctx, list_count >= 1 && list_count <= frame, "rt_accumulate_cascade_frames: the list holds 1 to width * height entries");
-		std::vector<bool> seen(frame, false);
-		for (size_t i = 0; i < list_count; i++) {
-			if (list[i] >= frame) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_accumulate_cascade_frames: list entry %zu (%u) lies outside the %zu pixel frame", i, list[i], frame);
-			if (seen[list[i]]) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_accumulate_cascade_frames: list entry %zu names pixel %u a second time", i, list[i]);
-			seen[list[i]] = true;
-		}
-	} else {
-		if (ctx->pixel_list_on) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_accumulate_cascade_frames: the context covers a pixel list (rt_set_pixel_list); pass a list");
-		if ((s = resolve_pixel_range(ctx, "rt_accumulate_cascade_frames", &range_offset, &range_count))) return s;
-	}
-	RT_HIP(ctx, quiesce(ctx));
-
-	Probe probe(ctx, "rt_accumulate_cascade_frames");
-	float4 * dev_frames = probe.array<float4>(total * frame_pixels, frames);
-	float4 * dev_accumulator = probe.array<float4>(frame_pixels, accumulator);
-	float4 * dev_moments = probe.array<float4>(frame_pixels, moments);
-	float4 * dev_tiers = probe.array<float4>(frame_pixels * size_t(params->tiers), tiers);
-	unsigned * dev_list = list ? probe.array<unsigned>(list_count, list) : nullptr;
-	probe.staging.assign(frame_pixels * 4, sentinel);
-	float4 * dev_final = (float4 *)probe.array<uint32_t>(frame_pixels * 4, probe.staging.data());
-	if ((s = probe.allocated())) return s;
-
-	RtParams p = ctx->params;
-	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = p.aovs[a].accumulator = nullptr;
-	p.aovs[RT_AOV_RADIANCE].framebuffer = dev_frames; p.aovs[RT_AOV_RADIANCE].accumulator = dev_accumulator;
-	p.final_image = dev_final;
-	const RtFireflyTiers cascade = { dev_tiers, frame_pixels, params->tiers, params->start };
-	if (merged) {
-		RtAccumulateGroup group; group.count = int(submissions);
-		for (int k = 0, base = 0; k < group.count; k++) { group.first_sample[k] = first_sample[k]; group.sample_count[k] = sample_count[k]; group.slot_base[k] = base; base += sample_count[k]; }
-		for (int k = group.count; k < RT_ACCUMULATE_GROUP; k++) group.first_sample[k] = group.sample_count[k] = group.slot_base[k] = 0;
-		if (list) rt_launch_accumulate_group_list_cascade(p, group, dev_list, int(list_count), ctx->stream, dev_moments, cascade);
-		else rt_launch_accumulate_group_cascade(p, group, range_offset, range_count, ctx->stream, dev_moments, cascade);
-	} else {
-		p.batch_samples = sample_count[0];
-		rt_launch_accumulate_cascade(p, float(first_sample[0]), range_offset, range_count, ctx->stream, dev_moments, cascade);
-	}
-	if ((s = probe.finish())) return s;
-	if ((s = probe.read(frames, dev_frames, total * frame_pixels * 16)) || (s = probe.read(accumulator, dev_accumulator, frame_pixels * 16))) return s;
-	if ((s = probe.read(moments, dev_moments, frame_pixels * 16)) || (s = probe.read(tiers, dev_tiers, frame_pixels * size_t(params->tiers) * 16))) return s;
-	return probe.read(final_image, dev_final, frame_pixels * 16);
+	return accumulate_probe(ctx, "rt_accumulate_cascade_frames", merged != 0, true, "pass a list", first_sample, sample_count, submissions, frames, accumulator, moments, list, list_count, params, tiers,
+	                        sentinel, final_image);
 }
 
 int rt_resolve_fireflies_images(rt_context * ctx, int width, int height, int pitch, const float * mean, const float * moments, const float * tiers, const float * fallback,

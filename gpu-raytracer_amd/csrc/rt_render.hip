@@ -193,6 +193,14 @@ extern "C" {
 
 int rt_render_sample(rt_context * ctx, int sample_index) { return rt_render_samples(ctx, sample_index, 1); }
 
+// The accumulate step of a batch: one submission, its frames at slot 0, cleared by the caller after the launch.
+static RtAccumulate batch_accumulate(int sample_index, int sample_count, int range_offset, int range_count, float4 * moments, const RtFireflyTiers & tiers) {
+	RtAccumulate a = { };
+	a.group.count = 1; a.group.first_sample[0] = sample_index; a.group.sample_count[0] = sample_count;
+	a.pixel_offset = range_offset; a.pixel_count = range_count; a.moments = moments; a.tiers = tiers;
+	return a;
+}
+
 int rt_render_samples(rt_context * ctx, int sample_index, int sample_count) {
 	RT_REQUIRE(ctx, ctx, "rt_render_sample: NULL context");
 	RT_REQUIRE(ctx, sample_count >= 1 && sample_count <= RT_MAX_BATCH_SAMPLES, "rt_render_samples: sample_count must be 1..16");
@@ -322,11 +330,7 @@ int rt_render_samples(rt_context * ctx, int sample_index, int sample_count) {
 	const bool deferred = p.config.enable_svgf && ctx->defer_filter; // rt_filter_frame does the rest once the ranks have exchanged their tiles
 	if (deferred) { }
 	else if (p.config.enable_svgf) { p.taa_frame_prev = ctx->params.taa_frame_prev; p.taa_frame_next = ctx->params.taa_frame_next; rt_launch_svgf_taa(p, sample_index, st); if (p.config.enable_taa) std::swap(ctx->params.taa_frame_prev, ctx->params.taa_frame_next); }
-	else {
-		RtFireflyTiers tiers;   // (the cascade forms of the same kernels while rt_set_firefly_cascade is on)
-		if (firefly_tiers_for(ctx, p, &tiers)) rt_launch_accumulate_cascade(p, float(sample_index), range_offset, range_count, st, noise_moments_for(ctx, p), tiers);
-		else rt_launch_accumulate(p, float(sample_index), range_offset, range_count, st, noise_moments_for(ctx, p));
-	}
+	else rt_launch_accumulate(p, batch_accumulate(sample_index, sample_count, range_offset, range_count, noise_moments_for(ctx, p), firefly_tiers_for(ctx, p)), st);
 	stage_mark(ctx, STAGE_END, st);
 
 	// aovs_clear_to_zero (Integrator.cpp:379-385)
@@ -381,7 +385,7 @@ int rt_render_ao_sample(rt_context * ctx, int sample_index, float ao_radius) {
 	RtParams p_acc = p; // kernel_accumulate of AO.cu:161-183 folds RADIANCE, NORMAL and POSITION only
 	p_acc.aovs[RT_AOV_ALBEDO].framebuffer = nullptr;
 	ctx->folds++;   // (the mean moves: a resolved image is older than the frame from here on)
-	rt_launch_accumulate(p_acc, float(sample_index), range_offset, range_count, st);
+	rt_launch_accumulate(p_acc, batch_accumulate(sample_index, 1, range_offset, range_count, nullptr, { }), st);
 	for (int i = 0; i < RT_AOV_COUNT; i++) if (p.aovs[i].framebuffer) RT_HIP(ctx, hipMemsetAsync(p.aovs[i].framebuffer, 0, ctx->frame_pixels * 16, st));
 	return finish_slot_submission(ctx, 0);
 }

@@ -186,6 +186,27 @@ RT_DEV float sign_of(float x) { return copysignf(1.0f, x); }
 RT_DEV float abs_dot(f3 a, f3 b) { return fabsf(dot(a, b)); }
 RT_DEV float remap(float v, float a0, float a1, float b0, float b1) { return b0 + (v - a0) / (a1 - a0) * (b1 - b0); }
 
+// ---- shared by the image-space units (kernels_post.hip, kernels_denoise.hip, kernels_fireflies.hip) -----------------------------------
+RT_DEV bool finite3(float4 v) { return fabsf(v.x) < __builtin_huge_valf() && fabsf(v.y) < __builtin_huge_valf() && fabsf(v.z) < __builtin_huge_valf(); }
+RT_DEV bool finite4(float4 v) { return finite3(v) && fabsf(v.w) < __builtin_huge_valf(); }
+// any_valid (null, or one int) becomes 1 when some pixel is valid: one lane of a wave with a valid pixel raises the flag, and only while it reads as 0, so all but
+// the first waves stop at the load. (A count, one atomic add per wave on one word, made kernel_denoise_prepare 0.38 ms at 1080p for 0.04 ms of traffic: the L2
+// retires such atomics one after the other.) Every lane of the wave calls this.
+RT_DEV void raise_any_valid(int * any_valid, bool valid) {
+	if (!any_valid) return;
+	const unsigned long long mask = __ballot(valid);
+	if (valid && int(lane_id()) == __ffsll((long long)mask) - 1 && __hip_atomic_load(any_valid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
+		__hip_atomic_store(any_valid, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// The image-space kernels work on tiles (64 x 4 pixels, or a workgroup's LDS tile), dealt to the workgroups so that the tiles one XCD works on are NEIGHBOURS.
+// Workgroup b runs on XCD b % 8 (MI355X_MICROARCH.md: observed, for speed only) and every XCD has its own 4 MiB L2: with tile = workgroup index, horizontally
+// adjacent tiles land on eight different L2s, every XCD pulls the whole frame through the fabric, and a stencil's taps -- nine rows of three images in an a-trous
+// pass -- are fetched up to nine times from the Infinity Cache instead of once (measured: 0.078 ms per pass for 0.17 GB of compulsory traffic). Here XCD k takes
+// the k-th eighth of the tile sequence, in order: with row-major tiles a band of ~135 rows at 1080p, swept top to bottom, whose taps stay in the band's own L2 lines.
+// The launch is one-dimensional and padded to a multiple of 8 workgroups (xcd_tile_grid); a padding workgroup gets a tile number past the last tile.
+RT_DEV unsigned xcd_tile() { const unsigned per_xcd = gridDim.x / 8u; return (blockIdx.x % 8u) * per_xcd + blockIdx.x / 8u; }
+static inline unsigned xcd_tile_grid(unsigned tiles) { return (tiles + 7) / 8 * 8; }
+
 RT_DEV f3 ray_origin_epsilon_offset(f3 origin, f3 direction, f3 geometric_normal) {
 	return origin + sign_of(dot(direction, geometric_normal)) * RT_EPSILON * geometric_normal;
 }

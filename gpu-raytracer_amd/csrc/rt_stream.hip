@@ -167,7 +167,8 @@ static int stream_complete(rt_context * ctx, const StreamSubmission * subs, int 
 	for (int first = 0; first < count; ) {
 		// one launch for a run of submissions over the same pixels
 		const StreamSubmission & head = subs[first];
-		RtAccumulateGroup group; group.count = 0;
+		RtAccumulate a = { };
+		RtAccumulateGroup & group = a.group;
 		int k = first;
 		for (; k < count && group.count < RT_ACCUMULATE_GROUP; k++) {
 			const StreamSubmission & sub = subs[k];
@@ -178,12 +179,11 @@ static int stream_complete(rt_context * ctx, const StreamSubmission * subs, int 
 		RtParams pa = p;
 		pa.tile_pixels = head.tile_pixels; pa.tile_first = head.tile_first; pa.tile_stride = head.tile_stride;
 		span_mark(ctx, SPAN_ACCUMULATE, st);
-		RtFireflyTiers tiers;   // (the cascade forms of the same kernels while rt_set_firefly_cascade is on)
-		const bool cascade = firefly_tiers_for(ctx, pa, &tiers);
-		if (head.list && cascade) rt_launch_accumulate_group_list_cascade(pa, group, (const unsigned *)ctx->pixel_list, head.range_count, st, (float4 *)ctx->noise_moments, tiers);
-		else if (head.list) rt_launch_accumulate_group_list(pa, group, (const unsigned *)ctx->pixel_list, head.range_count, st, (float4 *)ctx->noise_moments);   // (the list does not change while a submission is in flight)
-		else if (cascade) rt_launch_accumulate_group_cascade(pa, group, head.range_offset, head.range_count, st, noise_moments_for(ctx, pa), tiers);
-		else rt_launch_accumulate_group(pa, group, head.range_offset, head.range_count, st, noise_moments_for(ctx, pa));
+		a.clear = true; a.pixel_offset = head.range_offset; a.pixel_count = head.range_count;
+		a.list = head.list ? (const unsigned *)ctx->pixel_list : nullptr;   // (the list does not change while a submission is in flight)
+		a.moments = noise_moments_for(ctx, pa);
+		a.tiers = firefly_tiers_for(ctx, pa);   // (the cascade forms of the same kernels while rt_set_firefly_cascade is on)
+		rt_launch_accumulate(pa, a, st);
 		span_mark(ctx, SPAN_ACCUMULATE, st);
 		first = k;
 	}

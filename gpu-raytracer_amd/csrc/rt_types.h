@@ -314,12 +314,24 @@ void rt_launch_ambient_occlusion(const RtParams & p, int sample_index, float ao_
 void rt_launch_trace_shadow_ao(const RtParams & p, hipStream_t stream);
 void rt_launch_sort(const RtParams & p, int bounce, int sample_index, hipStream_t stream);
 void rt_launch_material(const RtParams & p, int material_slot, int bounce, int sample_index, hipStream_t stream);
-// moments (both accumulate launchers): null, or the (M2_r, M2_g, M2_b, w) image of rt_set_noise_estimate -- then the ..._moments kernel runs
-void rt_launch_accumulate(const RtParams & p, float frames_accumulated, int pixel_offset, int pixel_count, hipStream_t stream, float4 * moments = nullptr);
 #define RT_SVGF_YOUNG_HEADER 16
+// The accumulate step (kernels_accumulate.hip): ONE launch folds the submissions of `group`, in order, into the accumulators.
+//   group    count submissions; submission k holds sample_count[k] samples from first_sample[k] on, its sample frames slot_base[k] frames into the AOVs' framebuffers
+//   clear    true: the frames are cleared on the way (the merged wavefront). false: a batch -- count 1, slot_base 0 -- whose frames the caller clears
+//   list     null: pixels [pixel_offset, pixel_offset + pixel_count) of the context's pixel set. Else pixel_count entries x + y * width, every pixel folded
+//            with its own sample count: needs clear, and moments (w is read from it)
+//   moments  null, or the (M2_r, M2_g, M2_b, w) image of rt_set_noise_estimate, kept beside the RADIANCE mean
+//   tiers    tiers.tiers null, or the firefly filter's tier images: `count` (2..8) pitched float4 images (sum w r, sum w g, sum w b, sum w), `plane`
+//            pixels apart in one allocation; tier j takes the samples whose luminance lies around start * 8^j. Needs moments; mean, moments and final image come
+//            out as without the tiers
+// A kernel argument of its own: RtParams keeps its size.
 #define RT_ACCUMULATE_GROUP 8
+#define RT_FIREFLY_MAX_TIERS 8
+#define RT_FIREFLY_BASE 8.0f
 struct RtAccumulateGroup { int count; int first_sample[RT_ACCUMULATE_GROUP], sample_count[RT_ACCUMULATE_GROUP], slot_base[RT_ACCUMULATE_GROUP]; };
-void rt_launch_accumulate_group(const RtParams & p, const RtAccumulateGroup & group, int pixel_offset, int pixel_count, hipStream_t stream, float4 * moments = nullptr);
+struct RtFireflyTiers { float4 * tiers; size_t plane; int count; float start; };
+struct RtAccumulate { RtAccumulateGroup group; bool clear; const unsigned * list; int pixel_offset, pixel_count; float4 * moments; RtFireflyTiers tiers; };
+void rt_launch_accumulate(const RtParams & p, const RtAccumulate & accumulate, hipStream_t stream);
 // The noise estimate (kernel_noise_cells): one workgroup per RT_NOISE_CELL^2 pixels of width x height; mean and moments are pitched float4 images, pixel_map
 // (pitched floats) may be null, the three cell arrays hold ceil(width / 16) * ceil(height / 16) entries, row-major.
 #define RT_NOISE_CELL 16
@@ -327,12 +339,10 @@ void rt_launch_noise_cells(const float4 * mean, const float4 * moments, int widt
                            double * cell_sums, int * cell_counts, int * cell_nonfinite, hipStream_t stream);
 // Adaptive sampling. select: kernel_select_cells, kernel_scan_cells and kernel_compact_cells on the cell arrays of rt_launch_noise_cells: flags
 // (one byte per cell: bit 0 hot, bit 1 active), active_pixels and offsets (one int per cell), totals (3 ints: list length, hot cells, active cells), list (room for
-// width * height entries, x + y * width each). The ..._list launchers are the generate and accumulate steps of a submission over such a list; the accumulate one
-// folds every pixel with its own sample count (moments is required: w is read from it).
+// width * height entries, x + y * width each). rt_launch_generate_stream_list is the generate step of a submission over such a list.
 void rt_launch_select_cells(const double * cell_sums, const int * cell_counts, const int * cell_nonfinite, int width, int height, float threshold, int dilate,
                             unsigned char * flags, int * active_pixels, int * offsets, int * totals, unsigned * list, hipStream_t stream);
 void rt_launch_generate_stream_list(const RtParams & p, int sample_index, const unsigned * list, int pixel_count, int slot_base, int queue_offset, hipStream_t stream);
-void rt_launch_accumulate_group_list(const RtParams & p, const RtAccumulateGroup & group, const unsigned * list, int pixel_count, hipStream_t stream, float4 * moments);
 // The still-image denoiser (kernels_denoise.hip): prepare, `iterations` a-trous passes (0..6) of step 1, 2, 4, ..., the last of which finalizes;
 // with 0 iterations prepare and a finalize kernel. any_valid: null, or one int the prepare kernel sets to 1 when a pixel is valid. All images are pitched float4; iv[0], iv[1] and guide are the filter's own (iv[1] is not touched below 2
 // iterations), `out` receives the result, the rest is read only. Arguments of the kernels' own: RtParams keeps its size. tiled: the passes stage their taps in LDS.
@@ -341,15 +351,7 @@ struct RtDenoiseArgs { int width, height, pitch, iterations; float sigma_l, sigm
 struct RtDenoiseImages { const float4 * colour, * moments, * albedo, * normal, * position, * fallback; float4 * iv[2], * guide, * out; int * any_valid; };
 void rt_launch_denoise(const RtDenoiseArgs & args, const RtDenoiseImages & images, bool tiled, hipStream_t stream,
                        void (*mark)(void * user, int kernel, hipStream_t stream) = nullptr, void * user = nullptr);
-// The firefly filter (kernels_fireflies.hip). Tiers: `count` (2..8) pitched float4 images (sum w r, sum w g, sum w b, sum w), `plane` pixels apart in one
-// allocation; tier j takes the samples whose luminance lies around start * 8^j. The ..._cascade launchers are the three moments accumulate launchers above with the
-// splat beside the fold (moments is required): mean, moments and final image come out as the plain kernels leave them. The tier pointers are a kernel argument of
-// their own: RtParams keeps its size.
-#define RT_FIREFLY_MAX_TIERS 8
-struct RtFireflyTiers { float4 * tiers; size_t plane; int count; float start; };
-void rt_launch_accumulate_cascade(const RtParams & p, float frames_accumulated, int pixel_offset, int pixel_count, hipStream_t stream, float4 * moments, const RtFireflyTiers & tiers);
-void rt_launch_accumulate_group_cascade(const RtParams & p, const RtAccumulateGroup & group, int pixel_offset, int pixel_count, hipStream_t stream, float4 * moments, const RtFireflyTiers & tiers);
-void rt_launch_accumulate_group_list_cascade(const RtParams & p, const RtAccumulateGroup & group, const unsigned * list, int pixel_count, hipStream_t stream, float4 * moments, const RtFireflyTiers & tiers);
+// The firefly filter (kernels_fireflies.hip): the tiers are filled by the accumulate step (RtAccumulate).
 // The resolve: (mean, moments, tiers) -> out = (R / N, luminance(T - R) / N), and (fallback.rgb, -1) for a pixel that is not valid. All images are pitched float4;
 // any_valid: null, or one int the kernel sets to 1 when a pixel is valid. tiled: the W of the tile's halo are staged in LDS; the plain kernel gives the same bits.
 struct RtFireflyResolveArgs { int width, height, pitch, tiers; float start, support; };

@@ -260,6 +260,50 @@ def test_after_an_adaptive_render(grt, cornell):
     assert got[:, :W].tobytes() == _resolve_own_images(grt, pt, support=3.0)[:, :W].tobytes() and np.isfinite(got[:, :W]).all()
 
 
+@pytest.mark.parametrize("mode", ["merged", "slots", "list"])
+def test_all_four_means_are_the_same_with_the_cascade_on_and_off(grt, cornell, mode):
+    """The probes take every AOV but RADIANCE away, so this is what holds the cascade kernels' folds of ALBEDO, NORMAL and POSITION: 6 samples with the three
+    enabled (list: then two adaptive passes of 4 over the cells above the 0.9 quantile, as test_after_an_adaptive_render), rendered with the cascade on and off.
+    The four accumulators, the moments and the final image are the same bytes."""
+    scene, pt = cornell
+    guides = (grt.AOV_ALBEDO, grt.AOV_NORMAL, grt.AOV_POSITION)
+
+    def frame():
+        _render(grt, pt, 6, mode)
+        if mode == "list":
+            estimate = pt.noise_estimate()
+            means = estimate["cell_sums"] / np.maximum(estimate["cell_counts"], 1)
+            chosen = pt.select_adaptive(float(np.quantile(means, 0.9)))
+            try:
+                assert 0 < chosen["active_cells"] < chosen["cells"]
+                for _ in range(2):
+                    pt.update(); pt.render_samples(4)
+            finally:
+                pt.adaptive_off()
+        return [pt.read_framebuffer().copy(), grt.read_noise_moments(pt.ctx, H, pt.pitch)] + [pt.read_aov(aov).copy() for aov in (grt.AOV_RADIANCE,) + guides]
+
+    try:
+        for aov in guides:
+            pt.aov_enable(aov)
+        on = frame()
+        assert grt.get_firefly_cascade(pt.ctx) is not None and grt.read_firefly_cascade(pt.ctx, H, pt.pitch).any()
+        grt.config_set(firefly_filter=0, noise_target=1e-30)   # (the estimate stays on)
+        off = frame()
+        assert grt.get_firefly_cascade(pt.ctx) is None
+        assert all(image[:, :W, :3].any() for image in on[2:]), "an AOV was not folded"
+        if mode == "list":
+            assert on[1][:, :W, 3].min() < on[1][:, :W, 3].max()   # some pixels took the adaptive passes, some did not
+        for a, b, what in zip(on, off, ("final image", "moments", "radiance mean", "albedo mean", "normal mean", "position mean")):
+            assert a.tobytes() == b.tobytes(), what
+    finally:
+        grt.config_set(firefly_filter=1, noise_target=0.0)
+        for aov in guides:
+            pt.aov_enable(aov, False)
+        grt.set_scheduler(pt.ctx, "merged")
+        _render(grt, pt, 2)
+    assert grt.get_firefly_cascade(pt.ctx) is not None
+
+
 def test_refusals_zeroing_and_resize(grt, cornell):
     scene, pt = cornell
     lib = grt.device_lib()
