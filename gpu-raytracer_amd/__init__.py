@@ -63,6 +63,10 @@ class CellSelectionRecord(ctypes.Structure):  # rt_cell_selection
     _fields_ = [("cells_x", ctypes.c_int32), ("cells_y", ctypes.c_int32), ("hot_cells", ctypes.c_int64), ("active_cells", ctypes.c_int64), ("list_pixels", ctypes.c_int64)]
 
 
+class ExposureRecord(ctypes.Structure):  # rt_exposure
+    _fields_ = [("pixels", ctypes.c_int64), ("dark_pixels", ctypes.c_int64), ("nonfinite_pixels", ctypes.c_int64)]
+
+
 class DenoiseParams(ctypes.Structure):  # rt_denoise_params
     _fields_ = [("iterations", c_int), ("sigma_l", c_float), ("sigma_n", c_float), ("sigma_z", c_float), ("depth_floor", c_float), ("albedo_floor", c_float)]
 
@@ -207,6 +211,16 @@ def device_lib():
         lib.rt_get_denoise_source.argtypes = [c_void_p]
         lib.rt_accumulate_cascade_frames.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, POINTER(FireflyParams), c_void_p, c_uint32, c_void_p]
         lib.rt_resolve_fireflies_images.argtypes = [c_void_p, c_int, c_int, c_int] + [c_void_p] * 4 + [POINTER(FireflyParams), c_int, c_void_p]
+        lib.rt_measure_exposure.argtypes = [c_void_p, POINTER(ExposureRecord), c_void_p]
+        lib.rt_measure_exposure_images.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, POINTER(ExposureRecord), c_void_p]
+        lib.rt_estimate_noise_robust.argtypes = [c_void_p, c_float, c_float, POINTER(NoiseEstimateRecord), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, POINTER(ctypes.c_int64)]
+        lib.rt_estimate_noise_robust_images.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, POINTER(NoiseEstimateRecord), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
+                                                        POINTER(ctypes.c_int64)]
+        lib.rt_select_pixels_robust_images.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_int, POINTER(CellSelectionRecord), c_void_p, c_void_p, c_void_p, c_void_p,
+                                                       c_void_p, c_size_t, c_void_p, c_size_t]
+        lib.rt_set_noise_robust.argtypes = [c_void_p, c_float]
+        lib.rt_get_noise_robust.argtypes = [c_void_p]
+        lib.rt_get_noise_robust.restype = c_float
         _device = lib
     return _device
 
@@ -1030,13 +1044,38 @@ class Pathtracer:
         _host_check(host_lib().grt_pathtracer_save_denoised_image(self.handle, str(filename).encode(), values.ctypes.data if values is not None else None))
 
     # ---- firefly filter
-    def set_firefly_filter(self, enable=True, **params):
+    def set_firefly_filter(self, enable=True, auto_start=None, start_shift=None, pilot_samples=None, **params):
         """config firefly_filter (and firefly_tiers / firefly_start / firefly_support from tiers, start, support): from the next update() on (which restarts the
-        progression when it switches them on) the device keeps the noise estimate and the tier cascade that resolve_fireflies() reweights."""
+        progression when it switches them on) the device keeps the noise estimate and the tier cascade that resolve_fireflies() reweights.
+        auto_start (config firefly_auto_start, with firefly_start_shift and firefly_pilot_samples from start_shift and pilot_samples): after the
+        pilot samples the start is taken from the frame's own exposure and the progression starts over; firefly_start then says what is in force. None leaves a key alone."""
         unknown = set(params) - set(FIREFLY_DEFAULTS)
         if unknown:
             raise TypeError("unknown firefly parameter(s): %s" % ", ".join(sorted(unknown)))
-        config_set(firefly_filter=1 if enable else 0, **{"firefly_" + k: v for k, v in params.items()})
+        automatic = {"firefly_auto_start": None if auto_start is None else (1 if auto_start else 0), "firefly_start_shift": start_shift, "firefly_pilot_samples": pilot_samples}
+        config_set(firefly_filter=1 if enable else 0, **{"firefly_" + k: v for k, v in params.items()}, **{k: v for k, v in automatic.items() if v is not None})
+
+    def _firefly_start_state(self):
+        lib = host_lib()
+        lib.grt_pathtracer_firefly_start.argtypes = [c_void_p, c_void_p]
+        out = np.zeros(3, np.float64)
+        _host_check(lib.grt_pathtracer_firefly_start(self.handle, out.ctypes.data))
+        return out
+
+    @property
+    def firefly_start(self):
+        """Pathtracer::firefly_start(): the start of the cascade in force -- config firefly_start, or what auto_start measured after the pilot."""
+        return float(self._firefly_start_state()[0])
+
+    @property
+    def firefly_start_measured(self):
+        """True once the pilot of the current configuration has been rendered and measured (auto_start)."""
+        return bool(self._firefly_start_state()[1])
+
+    @property
+    def firefly_pilot_samples_discarded(self):
+        """The samples rendered and dropped by the restarts auto_start has made so far."""
+        return int(self._firefly_start_state()[2])
 
     def resolve_fireflies(self, support=None):
         """Pathtracer::resolve_fireflies(): the tier cascade, every tier scaled by how well its neighbourhood supports it. Returns (image, held_back): (height, width, 3)
@@ -1051,9 +1090,12 @@ class Pathtracer:
         _host_check(host_lib().grt_pathtracer_save_resolved_image(self.handle, str(filename).encode(), 0.0 if support is None else float(support)))
 
     # ---- noise estimate
-    def set_noise_estimate(self, enable=True):
+    def set_noise_estimate(self, enable=True, robust=False, held_fraction=0.25):
         """The device keeps Welford second moments beside the radiance mean from the next update() on (which restarts the
-        progression when it switches them on). Also on while config noise_target > 0."""
+        progression when it switches them on). Also on while config noise_target > 0.
+        robust (config noise_robust and noise_held_fraction; needs the firefly filter, else one warning and the plain estimate): noise_estimate(),
+        noise_map(), select_adaptive() and render_until() leave out the pixels of which the resolve holds back more than held_fraction of their brightness."""
+        config_set(noise_robust=1 if robust else 0, noise_held_fraction=held_fraction)
         lib = host_lib()
         lib.grt_pathtracer_set_noise_estimate.argtypes = [c_void_p, c_int]
         lib.grt_pathtracer_set_noise_estimate.restype = None
@@ -1072,8 +1114,14 @@ class Pathtracer:
         _host_check(fn(self.handle, xy.ctypes.data, sums.ctypes.data, counts.ctypes.data, nonfinite.ctypes.data, n, mean_figure.ctypes.data, pixels.ctypes.data,
                        pixel_map.ctypes.data if want_map else None))
         shape = (int(xy[1]), int(xy[0]))
-        return {"cells_x": int(xy[0]), "cells_y": int(xy[1]), "cell_sums": sums.reshape(shape), "cell_counts": counts.reshape(shape), "cell_nonfinite": nonfinite.reshape(shape),
-                "mean": float(mean_figure[0]), "figure": float(mean_figure[1]), "pixels": int(pixels[0]), "nonfinite_pixels": int(pixels[1])}, pixel_map
+        result = {"cells_x": int(xy[0]), "cells_y": int(xy[1]), "cell_sums": sums.reshape(shape), "cell_counts": counts.reshape(shape), "cell_nonfinite": nonfinite.reshape(shape),
+                  "mean": float(mean_figure[0]), "figure": float(mean_figure[1]), "pixels": int(pixels[0]), "nonfinite_pixels": int(pixels[1]), "robust": False, "held_pixels": 0}
+        if entry == "grt_pathtracer_noise":   # what the call above found beyond its fixed outputs (the firefly-robust estimate)
+            lib.grt_pathtracer_noise_held.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t]
+            held, cell_held = np.zeros(2, np.int64), np.zeros(n, np.int32)
+            _host_check(lib.grt_pathtracer_noise_held(self.handle, held.ctypes.data, cell_held.ctypes.data, n))
+            result.update(robust=bool(held[0]), held_pixels=int(held[1]), cell_held=cell_held.reshape(shape))
+        return result, pixel_map
 
     def noise_estimate(self):
         """Pathtracer::noise(): the cells (16 x 16 pixels: sums of the per-pixel relative standard error, counts, non-finite counts), the mean over
@@ -1081,7 +1129,8 @@ class Pathtracer:
         return self._noise("grt_pathtracer_noise", False)[0]
 
     def noise_map(self):
-        """The per-pixel relative standard error, (height, pitch) float32: -1 where the pixel takes no part, -2 where it is not finite."""
+        """The per-pixel relative standard error, (height, pitch) float32: -1 where the pixel takes no part, -2 where it is not finite, -3 where the robust estimate
+        holds it."""
         return self._noise("grt_pathtracer_noise", True)[1]
 
     def select_adaptive(self, threshold):
@@ -1132,7 +1181,7 @@ class Pathtracer:
                     return {"samples": self.sample_index + 1, "figure": None, "mean": None, "capped": True}
         if adaptive and not noise_target > 0.0:
             raise ValueError("render_until: adaptive sampling needs noise_target > 0")
-        self.set_noise_estimate(True)
+        self.set_noise_estimate(True, robust=bool(config_get("noise_robust")), held_fraction=config_get("noise_held_fraction"))   # (whatever is set stays)
         min_samples = int(config_get("noise_min_samples"))
         if not adaptive:
             return self._render_until(noise_target, max_samples, check_every, min_samples, None)
@@ -1420,6 +1469,99 @@ def resolve_fireflies_images(ctx, mean, moments, tiers, fallback, width=None, ti
     if status:
         raise DeviceRefusal(ctx, status)
     return out
+
+
+# ---- the frame's exposure and the firefly-robust noise estimate
+def measure_exposure(ctx):
+    """rt_measure_exposure on the context's RADIANCE mean and moments. Returns a dict: pixels, dark_pixels, nonfinite_pixels, histogram ((256,) uint64: the pixels
+    whose luminance has that biased float32 exponent)."""
+    return measure_exposure_images(ctx, None, None)
+
+
+def measure_exposure_images(ctx, mean, moments, width=None):
+    """rt_measure_exposure_images: the exposure histogram of explicit (height, pitch, 4) float32 images; width defaults to pitch. As measure_exposure."""
+    histogram, out = np.zeros(256, np.uint64), ExposureRecord()
+    if mean is None:
+        status = device_lib().rt_measure_exposure(ctx, byref(out), histogram.ctypes.data)
+    else:
+        mean, moments = _f32(mean), _f32(moments)
+        height, pitch = mean.shape[:2]
+        assert mean.shape == moments.shape == (height, pitch, 4)
+        status = device_lib().rt_measure_exposure_images(ctx, pitch if width is None else width, height, pitch, mean.ctypes.data, moments.ctypes.data, byref(out), histogram.ctypes.data)
+    if status:
+        raise DeviceRefusal(ctx, status)
+    return {"pixels": out.pixels, "dark_pixels": out.dark_pixels, "nonfinite_pixels": out.nonfinite_pixels, "histogram": histogram}
+
+
+def exposure_start(histogram, shift=0):
+    """grt_exposure_start of the host library: (start, median exponent + shift, clamped to -96 .. 96) -- start = 2 ** that --, or None for an empty histogram."""
+    lib = host_lib()
+    lib.grt_exposure_start.argtypes = [c_void_p, c_int, POINTER(c_float), POINTER(c_int)]
+    histogram = np.ascontiguousarray(histogram, np.uint64).ravel()
+    assert histogram.size == 256
+    start, exponent = c_float(), c_int()
+    if lib.grt_exposure_start(histogram.ctypes.data, int(shift), byref(start), byref(exponent)):
+        return None
+    return start.value, exponent.value
+
+
+def estimate_noise_robust(ctx, height, width, pitch, floor=1e-2, held_fraction=0.25, mean=None, moments=None, resolved=None, want_map=True, cell_capacity=None):
+    """rt_estimate_noise_robust on the context's frame (after a resolve of its own), or -- mean, moments and resolved given, (height, pitch, 4) float32 --
+    rt_estimate_noise_robust_images on those. The dict of estimate_noise plus cell_held (cells_y, cells_x) and held_pixels; a held pixel is -3 in pixel_map."""
+    lib = device_lib()
+    cells_x, cells_y = (width + 15) // 16, (height + 15) // 16
+    n = cells_x * cells_y
+    sums, counts, nonfinite, held = np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    pixel_map = np.zeros((height, pitch), np.float32) if want_map else None
+    out, held_pixels = NoiseEstimateRecord(), ctypes.c_int64()
+    tail = (c_float(floor), c_float(held_fraction), byref(out), sums.ctypes.data, counts.ctypes.data, nonfinite.ctypes.data, held.ctypes.data, n if cell_capacity is None else cell_capacity,
+            pixel_map.ctypes.data if want_map else None, byref(held_pixels))
+    if mean is None:
+        status = lib.rt_estimate_noise_robust(ctx, *tail)
+    else:
+        mean, moments, resolved = _f32(mean), _f32(moments), _f32(resolved)
+        assert mean.shape == moments.shape == resolved.shape == (height, pitch, 4)
+        status = lib.rt_estimate_noise_robust_images(ctx, mean.ctypes.data, moments.ctypes.data, resolved.ctypes.data, *tail)
+    if status:
+        raise DeviceRefusal(ctx, status)
+    return {"cells_x": out.cells_x, "cells_y": out.cells_y, "pixels": out.pixels, "nonfinite_pixels": out.nonfinite_pixels, "mean": out.mean, "held_pixels": held_pixels.value,
+            "cell_sums": sums.reshape(cells_y, cells_x), "cell_counts": counts.reshape(cells_y, cells_x), "cell_nonfinite": nonfinite.reshape(cells_y, cells_x),
+            "cell_held": held.reshape(cells_y, cells_x), "pixel_map": pixel_map}
+
+
+def estimate_noise_robust_images(ctx, height, width, pitch, mean, moments, resolved, **given):
+    """rt_estimate_noise_robust_images: estimate_noise_robust on the caller's images."""
+    return estimate_noise_robust(ctx, height, width, pitch, mean=mean, moments=moments, resolved=resolved, **given)
+
+
+def set_noise_robust(ctx, held_fraction):
+    """rt_set_noise_robust: held_fraction in (0, 1) makes rt_select_active_cells select from the robust cells; 0 (or None, False) switches that off."""
+    status = device_lib().rt_set_noise_robust(ctx, c_float(held_fraction or 0.0))
+    if status:
+        raise DeviceRefusal(ctx, status)
+
+
+def get_noise_robust(ctx):
+    return float(device_lib().rt_get_noise_robust(ctx))
+
+
+def select_pixels_robust_images(ctx, height, width, pitch, mean, moments, resolved, threshold, floor=1e-2, held_fraction=0.25, dilate=1, sentinel=0xffffffff):
+    """rt_select_pixels_robust_images: select_pixels_images from the robust cells of the caller's images; the dict gains cell_held (cells_y, cells_x)."""
+    mean, moments, resolved = _f32(mean), _f32(moments), _f32(resolved)
+    assert mean.shape == moments.shape == resolved.shape == (height, pitch, 4)
+    cells_x, cells_y = (width + 15) // 16, (height + 15) // 16
+    n = cells_x * cells_y
+    sums, counts, nonfinite, held, flags = np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint8)
+    pixels = np.full(width * height, sentinel, np.uint32)
+    out = CellSelectionRecord()
+    status = device_lib().rt_select_pixels_robust_images(ctx, mean.ctypes.data, moments.ctypes.data, resolved.ctypes.data, c_float(floor), c_float(held_fraction), c_float(threshold), int(dilate),
+                                                         byref(out), sums.ctypes.data, counts.ctypes.data, nonfinite.ctypes.data, held.ctypes.data, flags.ctypes.data, n, pixels.ctypes.data, pixels.size)
+    if status:
+        raise DeviceRefusal(ctx, status)
+    result = _selection(out, flags)
+    result.update(cell_sums=sums.reshape(cells_y, cells_x), cell_counts=counts.reshape(cells_y, cells_x), cell_nonfinite=nonfinite.reshape(cells_y, cells_x),
+                  cell_held=held.reshape(cells_y, cells_x), list=pixels[:out.list_pixels].copy(), list_tail=pixels[out.list_pixels:].copy())
+    return result
 
 
 def _accumulate_staging(frames, images, first_sample, sample_count, merged):

@@ -1,7 +1,9 @@
-// kernels_fireflies.hip -- the resolve of the firefly filter (tiered accumulation with a reweighted resolve, after Zirr, Hanika and Dachsbacher
+// kernels_fireflies.hip -- the resolve of the firefly filter and its exposure measurement (tiered accumulation with a reweighted resolve, after Zirr, Hanika and Dachsbacher
 // 2018; the accumulate step of kernels_accumulate.hip splats every RADIANCE sample into the pixel's K tier images).
 //   kernel_fireflies_resolve(_tiled)   (mean, moments, tiers) -> (R / N, luminance held back / N): every tier scaled by how well its 3 x 3 neighbourhood
 //                                      supports it; tiled in LDS, or plain (the probe's cross-check)
+//   kernel_exposure_histogram          (mean, moments) -> the histogram of the float32 exponents of the mean's luminance (the cascade's start
+//                                      taken from the frame's own exposure); integer counts
 // Same contract as the other image kernels: -ffp-contract=off, every operation a plain IEEE float32 one in the order written (the divisions are IEEE
 // divisions), so the float32 restatement of tests/firefly_reference.py gives the same bits.
 #include "rt_shading.h"
@@ -120,6 +122,37 @@ __global__ void __launch_bounds__(64 * TY) kernel_fireflies_resolve_tiled(RtFire
 
 	if (!has_pixel) return;
 	fireflies_resolve_pixel(a, im, pixel_index, valid, s, n, [&](int j, int i, int k) { return tile_w[j][centre + i + k * W]; });
+}
+
+// The exposure histogram (rt_measure_exposure): which power of two the frame's pixels are bright as, so that the cascade's start can follow the
+// median class. A pixel with w >= 1 is non-finite when r, g, b or the luminance of its mean is not finite, dark when Y = luminance(mean) <= 0, and else counts in
+// bin (bits(Y) >> 23) & 255, its biased exponent (denormals: bin 0). The padding columns are never read. Counts are integers, so the atomics decide nothing: a
+// workgroup counts its pixels -- index i of the width x height frame, a stride of the whole grid apart -- in LDS and adds the bins it filled to the global words.
+__global__ void __launch_bounds__(256) kernel_exposure_histogram(const float4 * __restrict__ mean, const float4 * __restrict__ moments, int width, int height, int pitch,
+                                                                 unsigned long long * __restrict__ histogram) {
+	__shared__ unsigned bins[RT_EXPOSURE_WORDS];
+	for (int t = threadIdx.x; t < RT_EXPOSURE_WORDS; t += 256) bins[t] = 0u;
+	__syncthreads();
+	const unsigned pixels = unsigned(width) * unsigned(height);
+	for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < pixels; i += gridDim.x * 256u) {
+		const size_t pixel_index = size_t(i % unsigned(width)) + size_t(i / unsigned(width)) * size_t(pitch);
+		if (!(moments[pixel_index].w >= 1.0f)) continue;
+		const float4 c = mean[pixel_index];
+		const float lum = luminance(c.x, c.y, c.z);
+		int bin = RT_EXPOSURE_NONFINITE;
+		if (finite3(c) && fabsf(lum) < __builtin_huge_valf()) bin = lum <= 0.0f ? RT_EXPOSURE_DARK : int((__float_as_uint(lum) >> 23) & 255u);
+		atomicAdd(&bins[bin], 1u);
+	}
+	__syncthreads();
+	for (int t = threadIdx.x; t < RT_EXPOSURE_WORDS; t += 256) if (bins[t]) atomicAdd(&histogram[t], (unsigned long long)bins[t]);
+}
+
+// At most 1024 workgroups (four to a compute unit): every one ends with an atomic per bin it filled, and atomics on one word retire one after the other.
+void rt_launch_exposure_histogram(const float4 * mean, const float4 * moments, int width, int height, int pitch, unsigned long long * histogram, hipStream_t stream) {
+	const unsigned pixels = unsigned(width) * unsigned(height);
+	unsigned blocks = (pixels + 255u) / 256u;
+	blocks = blocks > 1024u ? 1024u : blocks < 1u ? 1u : blocks;
+	hipLaunchKernelGGL(kernel_exposure_histogram, dim3(blocks), dim3(256), 0, stream, mean, moments, width, height, pitch, histogram);
 }
 
 void rt_launch_fireflies_resolve(const RtFireflyResolveArgs & a, const RtFireflyResolveImages & im, bool tiled, hipStream_t stream) {

@@ -34,15 +34,21 @@ RT_DEV void st4(float4 * p, int i, f4 v) { p[i] = to_float4(v); }
 //   v = (M2_r + M2_g) + M2_b;  e_p = sqrtf(v / (w * (w - 1.0f))) / fmaxf(luminance(mean), floor)
 // The cell's sum of e_p (double), its participating and its non-finite pixels are reduced by a fixed tree in LDS -- s[t] += s[t + stride], stride
 // 128 .. 1 -- without atomics: the same bits on every run and every rank, as the sky tables' scans are.
-__global__ void __launch_bounds__(RT_NOISE_CELL * RT_NOISE_CELL) kernel_noise_cells(const float4 * __restrict__ mean, const float4 * __restrict__ moments, int width, int height, int pitch,
-                                                                                    int cells_x, float floor, float * __restrict__ pixel_map,
-                                                                                    double * __restrict__ cell_sums, int * __restrict__ cell_counts, int * __restrict__ cell_nonfinite) {
+//
+// ROBUST (rt_estimate_noise_robust) is the same text beside the resolved image of the firefly filter: a pixel that takes part by the rule above is
+// HELD when the resolve found it valid (resolved.w >= 0) and held back more than held_fraction of its brightness, in float32
+//   resolved.w > held_fraction * fmaxf(luminance(mean), floor)
+// A held pixel is left out of sum and count, counted in cell_held, and -3 in the map. With no held pixel in a cell its three results are the plain kernel's bits.
+template<bool ROBUST>
+RT_DEV void noise_cells(const float4 * __restrict__ mean, const float4 * __restrict__ moments, const float4 * __restrict__ resolved, int width, int height, int pitch,
+                        int cells_x, float floor, float held_fraction, float * __restrict__ pixel_map,
+                        double * __restrict__ cell_sums, int * __restrict__ cell_counts, int * __restrict__ cell_nonfinite, int * __restrict__ cell_held) {
 	__shared__ double sums[RT_NOISE_CELL * RT_NOISE_CELL];
-	__shared__ int counts[RT_NOISE_CELL * RT_NOISE_CELL], nonfinite[RT_NOISE_CELL * RT_NOISE_CELL];
+	__shared__ int counts[RT_NOISE_CELL * RT_NOISE_CELL], nonfinite[RT_NOISE_CELL * RT_NOISE_CELL], held[ROBUST ? RT_NOISE_CELL * RT_NOISE_CELL : 1];
 	const int t = threadIdx.x;
 	const int x = int(blockIdx.x % unsigned(cells_x)) * RT_NOISE_CELL + t % RT_NOISE_CELL;
 	const int y = int(blockIdx.x / unsigned(cells_x)) * RT_NOISE_CELL + t / RT_NOISE_CELL;
-	double sum = 0.0; int count = 0, bad = 0;
+	double sum = 0.0; int count = 0, bad = 0, back = 0;
 	if (x < width && y < height) {
 		const size_t pixel_index = size_t(x) + size_t(y) * pitch;
 		const float4 m = moments[pixel_index];
@@ -53,17 +59,32 @@ __global__ void __launch_bounds__(RT_NOISE_CELL * RT_NOISE_CELL) kernel_noise_ce
 				float v = (m.x + m.y) + m.z;
 				e = sqrtf(v / (m.w * (m.w - 1.0f))) / fmaxf(luminance(c.x, c.y, c.z), floor);
 				sum = double(e); count = 1;
+				if (ROBUST) {
+					const float r = resolved[pixel_index].w;
+					if (r >= 0.0f && r > held_fraction * fmaxf(luminance(c.x, c.y, c.z), floor)) { e = -3.0f; sum = 0.0; count = 0; back = 1; }
+				}
 			} else { e = -2.0f; bad = 1; }
 		}
 		if (pixel_map) pixel_map[pixel_index] = e;
 	}
 	sums[t] = sum; counts[t] = count; nonfinite[t] = bad;
+	if (ROBUST) held[t] = back;
 	__syncthreads();
 	for (int stride = RT_NOISE_CELL * RT_NOISE_CELL / 2; stride >= 1; stride >>= 1) {
-		if (t < stride) { sums[t] += sums[t + stride]; counts[t] += counts[t + stride]; nonfinite[t] += nonfinite[t + stride]; }
+		if (t < stride) { sums[t] += sums[t + stride]; counts[t] += counts[t + stride]; nonfinite[t] += nonfinite[t + stride]; if (ROBUST) held[t] += held[t + stride]; }
 		__syncthreads();
 	}
-	if (t == 0) { cell_sums[blockIdx.x] = sums[0]; cell_counts[blockIdx.x] = counts[0]; cell_nonfinite[blockIdx.x] = nonfinite[0]; }
+	if (t == 0) { cell_sums[blockIdx.x] = sums[0]; cell_counts[blockIdx.x] = counts[0]; cell_nonfinite[blockIdx.x] = nonfinite[0]; if (ROBUST) cell_held[blockIdx.x] = held[0]; }
+}
+__global__ void __launch_bounds__(RT_NOISE_CELL * RT_NOISE_CELL) kernel_noise_cells(const float4 * __restrict__ mean, const float4 * __restrict__ moments, int width, int height, int pitch,
+                                                                                    int cells_x, float floor, float * __restrict__ pixel_map,
+                                                                                    double * __restrict__ cell_sums, int * __restrict__ cell_counts, int * __restrict__ cell_nonfinite) {
+	noise_cells<false>(mean, moments, nullptr, width, height, pitch, cells_x, floor, 0.0f, pixel_map, cell_sums, cell_counts, cell_nonfinite, nullptr);
+}
+__global__ void __launch_bounds__(RT_NOISE_CELL * RT_NOISE_CELL) kernel_noise_cells_robust(const float4 * __restrict__ mean, const float4 * __restrict__ moments, const float4 * __restrict__ resolved,
+                                                                                           int width, int height, int pitch, int cells_x, float floor, float held_fraction, float * __restrict__ pixel_map,
+                                                                                           double * __restrict__ cell_sums, int * __restrict__ cell_counts, int * __restrict__ cell_nonfinite, int * __restrict__ cell_held) {
+	noise_cells<true>(mean, moments, resolved, width, height, pitch, cells_x, floor, held_fraction, pixel_map, cell_sums, cell_counts, cell_nonfinite, cell_held);
 }
 
 void rt_launch_noise_cells(const float4 * mean, const float4 * moments, int width, int height, int pitch, float floor, float * pixel_map,
@@ -71,6 +92,12 @@ void rt_launch_noise_cells(const float4 * mean, const float4 * moments, int widt
 	const int cells_x = (width + RT_NOISE_CELL - 1) / RT_NOISE_CELL, cells_y = (height + RT_NOISE_CELL - 1) / RT_NOISE_CELL;
 	hipLaunchKernelGGL(kernel_noise_cells, dim3(unsigned(cells_x) * unsigned(cells_y)), dim3(RT_NOISE_CELL * RT_NOISE_CELL), 0, stream,
 	                   mean, moments, width, height, pitch, cells_x, floor, pixel_map, cell_sums, cell_counts, cell_nonfinite);
+}
+void rt_launch_noise_cells_robust(const float4 * mean, const float4 * moments, const float4 * resolved, int width, int height, int pitch, float floor, float held_fraction,
+                                  float * pixel_map, double * cell_sums, int * cell_counts, int * cell_nonfinite, int * cell_held, hipStream_t stream) {
+	const int cells_x = (width + RT_NOISE_CELL - 1) / RT_NOISE_CELL, cells_y = (height + RT_NOISE_CELL - 1) / RT_NOISE_CELL;
+	hipLaunchKernelGGL(kernel_noise_cells_robust, dim3(unsigned(cells_x) * unsigned(cells_y)), dim3(RT_NOISE_CELL * RT_NOISE_CELL), 0, stream,
+	                   mean, moments, resolved, width, height, pitch, cells_x, floor, held_fraction, pixel_map, cell_sums, cell_counts, cell_nonfinite, cell_held);
 }
 
 // ---- adaptive sampling: the cells still above the noise target, and their pixels as a list (rt_select_active_cells) ----------
@@ -81,26 +108,39 @@ RT_DEV int cell_frame_pixels(int cx, int cy, int width, int height) {
 // A cell is hot when its mean error is above the threshold -- compared in double, as sum > threshold * count, so that the host reproduces it from the
 // cell arrays -- or when it has in-frame pixels that took no part without being non-finite (w < 2: not sampled enough to judge). A cell of non-finite
 // pixels only is not hot: more samples do not repair a NaN mean.
-RT_DEV bool cell_is_hot(const double * __restrict__ cell_sums, const int * __restrict__ cell_counts, const int * __restrict__ cell_nonfinite, int c, int frame_pixels, float threshold) {
+// HELD (the robust cells): the pixels the firefly filter holds back count as judged too -- a cell of held and non-finite pixels only is not hot.
+template<bool HELD>
+RT_DEV bool cell_is_hot(const double * __restrict__ cell_sums, const int * __restrict__ cell_counts, const int * __restrict__ cell_nonfinite, const int * __restrict__ cell_held, int c, int frame_pixels, float threshold) {
 	const int count = cell_counts[c];
 	if (count > 0 && cell_sums[c] > double(threshold) * double(count)) return true;
-	return count + cell_nonfinite[c] < frame_pixels;
+	return count + cell_nonfinite[c] + (HELD ? cell_held[c] : 0) < frame_pixels;
 }
 // One thread per cell. flags: bit 0 hot, bit 1 active (hot, or with dilate = 1 one of the up to 8 neighbours inside the grid hot); active_pixels: the
 // cell's in-frame pixels when it is active, else 0 -- what the scan below turns into list offsets.
-__global__ void __launch_bounds__(256) kernel_select_cells(const double * __restrict__ cell_sums, const int * __restrict__ cell_counts, const int * __restrict__ cell_nonfinite,
-                                                           int width, int height, int cells_x, int cells_y, float threshold, int dilate,
-                                                           unsigned char * __restrict__ flags, int * __restrict__ active_pixels) {
+template<bool HELD>
+RT_DEV void select_cells(const double * __restrict__ cell_sums, const int * __restrict__ cell_counts, const int * __restrict__ cell_nonfinite, const int * __restrict__ cell_held,
+                         int width, int height, int cells_x, int cells_y, float threshold, int dilate,
+                         unsigned char * __restrict__ flags, int * __restrict__ active_pixels) {
 	const int c = blockIdx.x * blockDim.x + threadIdx.x;
 	if (c >= cells_x * cells_y) return;
 	const int cx = c % cells_x, cy = c / cells_x;
-	const bool hot = cell_is_hot(cell_sums, cell_counts, cell_nonfinite, c, cell_frame_pixels(cx, cy, width, height), threshold);
+	const bool hot = cell_is_hot<HELD>(cell_sums, cell_counts, cell_nonfinite, cell_held, c, cell_frame_pixels(cx, cy, width, height), threshold);
 	bool active = hot;
 	if (dilate && !hot)
 		for (int ny = max(cy - 1, 0); ny <= min(cy + 1, cells_y - 1); ny++) for (int nx = max(cx - 1, 0); nx <= min(cx + 1, cells_x - 1); nx++)
-			if (cell_is_hot(cell_sums, cell_counts, cell_nonfinite, nx + ny * cells_x, cell_frame_pixels(nx, ny, width, height), threshold)) active = true;
+			if (cell_is_hot<HELD>(cell_sums, cell_counts, cell_nonfinite, cell_held, nx + ny * cells_x, cell_frame_pixels(nx, ny, width, height), threshold)) active = true;
 	flags[c] = (unsigned char)((hot ? 1 : 0) | (active ? 2 : 0));
 	active_pixels[c] = active ? cell_frame_pixels(cx, cy, width, height) : 0;
+}
+__global__ void __launch_bounds__(256) kernel_select_cells(const double * __restrict__ cell_sums, const int * __restrict__ cell_counts, const int * __restrict__ cell_nonfinite,
+                                                           int width, int height, int cells_x, int cells_y, float threshold, int dilate,
+                                                           unsigned char * __restrict__ flags, int * __restrict__ active_pixels) {
+	select_cells<false>(cell_sums, cell_counts, cell_nonfinite, nullptr, width, height, cells_x, cells_y, threshold, dilate, flags, active_pixels);
+}
+__global__ void __launch_bounds__(256) kernel_select_cells_robust(const double * __restrict__ cell_sums, const int * __restrict__ cell_counts, const int * __restrict__ cell_nonfinite,
+                                                                  const int * __restrict__ cell_held, int width, int height, int cells_x, int cells_y, float threshold, int dilate,
+                                                                  unsigned char * __restrict__ flags, int * __restrict__ active_pixels) {
+	select_cells<true>(cell_sums, cell_counts, cell_nonfinite, cell_held, width, height, cells_x, cells_y, threshold, dilate, flags, active_pixels);
 }
 // Exclusive prefix sum of active_pixels over the cells in ascending cell index, one workgroup: thread t adds up its run of consecutive cells, the 256 run
 // totals are scanned in LDS (Hillis-Steele, integers), the run is walked again. totals: { list length, hot cells, active cells }. No atomics: the
@@ -153,9 +193,10 @@ __global__ void __launch_bounds__(RT_NOISE_CELL * RT_NOISE_CELL) kernel_compact_
 }
 
 void rt_launch_select_cells(const double * cell_sums, const int * cell_counts, const int * cell_nonfinite, int width, int height, float threshold, int dilate,
-                            unsigned char * flags, int * active_pixels, int * offsets, int * totals, unsigned * list, hipStream_t stream) {
+                            unsigned char * flags, int * active_pixels, int * offsets, int * totals, unsigned * list, hipStream_t stream, const int * cell_held) {
 	const int cells_x = (width + RT_NOISE_CELL - 1) / RT_NOISE_CELL, cells_y = (height + RT_NOISE_CELL - 1) / RT_NOISE_CELL, cells = cells_x * cells_y;
-	hipLaunchKernelGGL(kernel_select_cells, dim3((cells + 255) / 256), dim3(256), 0, stream, cell_sums, cell_counts, cell_nonfinite, width, height, cells_x, cells_y, threshold, dilate, flags, active_pixels);
+	if (cell_held) hipLaunchKernelGGL(kernel_select_cells_robust, dim3((cells + 255) / 256), dim3(256), 0, stream, cell_sums, cell_counts, cell_nonfinite, cell_held, width, height, cells_x, cells_y, threshold, dilate, flags, active_pixels);
+	else hipLaunchKernelGGL(kernel_select_cells, dim3((cells + 255) / 256), dim3(256), 0, stream, cell_sums, cell_counts, cell_nonfinite, width, height, cells_x, cells_y, threshold, dilate, flags, active_pixels);
 	hipLaunchKernelGGL(kernel_scan_cells, dim3(1), dim3(256), 0, stream, active_pixels, flags, cells, offsets, totals);
 	hipLaunchKernelGGL(kernel_compact_cells, dim3(cells), dim3(RT_NOISE_CELL * RT_NOISE_CELL), 0, stream, flags, offsets, width, height, cells_x, list);
 }

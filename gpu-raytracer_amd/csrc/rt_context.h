@@ -237,6 +237,9 @@ struct rt_context {
 	rt_firefly_params firefly = { };
 	void * firefly_tiers = nullptr, * firefly_resolved = nullptr; int * firefly_any_valid = nullptr;
 	unsigned long long folds = 1, firefly_resolved_at = 0;
+	// firefly-robust noise estimate (rt_set_noise_robust): the held fraction while rt_select_active_cells selects from the robust cells, else 0.
+	// On only while the cascade is.
+	float noise_robust = 0.0f;
 
 	// frame exchange of the tile split (rt_comm_*): this context's rank in a group of `world` contexts, each on its own GPU
 	// (RCCL communicator) or, for tests on one GPU, several in one process (peer copies)
@@ -314,11 +317,14 @@ void pixel_list_free(rt_context * ctx);
 int sync_noise_moments(rt_context * ctx);
 int noise_moments_reset(rt_context * ctx);
 float4 * noise_moments_for(const rt_context * ctx, const RtParams & p);
+struct NoiseRobust { const float4 * resolved; float held_fraction; int32_t * cell_held; int64_t * held_pixels; };   // the robust forms of the two sequences below
 int noise_estimate_images(rt_context * ctx, const char * caller, const float4 * mean, const float4 * moments, float floor, rt_noise_estimate * out,
-                          double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, size_t cell_capacity, float * pixel_map);
+                          double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, size_t cell_capacity, float * pixel_map, const NoiseRobust * robust = nullptr);
 int selection_arguments(rt_context * ctx, const char * caller, float floor, float threshold, int dilate);
+int held_fraction_argument(rt_context * ctx, const char * caller, float held_fraction);
 int select_cells_images(rt_context * ctx, const char * caller, const float4 * mean, const float4 * moments, float floor, float threshold, int dilate, unsigned * list,
-                        rt_cell_selection * out, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, uint8_t * cell_flags, size_t cell_capacity);
+                        rt_cell_selection * out, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, uint8_t * cell_flags, size_t cell_capacity,
+                        const NoiseRobust * robust = nullptr);
 // rt_denoise.hip
 void denoise_free(rt_context * ctx);
 int denoise_arguments(rt_context * ctx, const char * caller, const rt_denoise_params * params);
@@ -328,6 +334,8 @@ int firefly_tiers_zero(rt_context * ctx);
 void firefly_free(rt_context * ctx);
 RtFireflyTiers firefly_tiers_for(rt_context * ctx, const RtParams & p);
 int firefly_arguments(rt_context * ctx, const char * caller, int tiers, float start, float support);
+int firefly_resolve_frame(rt_context * ctx, const char * caller, float support, bool tiled, float * kernel_ms);
+int exposure_measure_images(rt_context * ctx, const char * caller, const float4 * mean, const float4 * moments, int width, int height, int pitch, rt_exposure * out, uint64_t * histogram256);
 #pragma GCC visibility pop
 
 #define RT_HIP(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(ctx, RT_ERROR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)

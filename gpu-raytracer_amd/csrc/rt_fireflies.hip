@@ -1,6 +1,6 @@
 // rt_fireflies.hip -- the part of the C ABI (include/gpu_raytracer_amd.h) that is the firefly filter: the tier images as the context keeps them beside
-// the moments image, and the entry points on the context's frame. The probes on explicit images, rt_accumulate_cascade_frames and rt_resolve_fireflies_images, are
-// in rt_probes.hip; they run the same launchers.
+// the moments image, and the entry points on the context's frame, the exposure measurement (7.10.1) among them. The probes on explicit images,
+// rt_accumulate_cascade_frames, rt_resolve_fireflies_images and rt_measure_exposure_images, are in rt_probes.hip; they run the same launchers.
 #include "rt_context.h"
 
 #include <cmath>
@@ -21,7 +21,7 @@ void firefly_free(rt_context * ctx) {
 // The tiers exist exactly while the cascade is on, the moments image exists and the frame has a size; they start from zeros, as the moments do. Without the
 // estimate the cascade goes off. The caller has quiesced the context and calls this after sync_noise_moments.
 int sync_firefly_tiers(rt_context * ctx) {
-	if (!ctx->noise_estimate && ctx->firefly_on) { ctx->firefly_on = false; firefly_free(ctx); }   // (as rt_set_firefly_cascade(ctx, NULL): the resolved image goes too)
+	if (!ctx->noise_estimate && ctx->firefly_on) { ctx->firefly_on = false; ctx->noise_robust = 0.0f; firefly_free(ctx); }   // (as rt_set_firefly_cascade(ctx, NULL): the resolved image goes too)
 	const bool want = ctx->firefly_on && ctx->noise_moments && ctx->frame_pixels > 0;
 	if (want && !ctx->firefly_tiers) {
 		const size_t bytes = ctx->frame_pixels * 16 * size_t(ctx->firefly.tiers);
@@ -46,8 +46,8 @@ RtFireflyTiers firefly_tiers_for(rt_context * ctx, const RtParams & p) {
 	return { (float4 *)ctx->firefly_tiers, ctx->frame_pixels, ctx->firefly.tiers, ctx->firefly.start };
 }
 
-// rt_resolve_fireflies and rt_resolve_fireflies_timed (kernel_ms != nullptr)
-static int resolve_frame(rt_context * ctx, const char * caller, float support, bool tiled, float * kernel_ms) {
+// rt_resolve_fireflies, rt_resolve_fireflies_timed (kernel_ms != nullptr) and the resolve of rt_estimate_noise_robust / the robust rt_select_active_cells (rt_noise.hip)
+int firefly_resolve_frame(rt_context * ctx, const char * caller, float support, bool tiled, float * kernel_ms) {
 	(void)hipSetDevice(ctx->device);
 	if (!ctx->firefly_on) return fail(ctx, RT_ERROR_NOT_READY, "%s: the firefly cascade is off (rt_set_firefly_cascade)", caller);
 	int s = firefly_arguments(ctx, caller, ctx->firefly.tiers, ctx->firefly.start, support); if (s) return s;
@@ -77,7 +77,37 @@ static int resolve_frame(rt_context * ctx, const char * caller, float support, b
 	return RT_OK;
 }
 
+// kernel_exposure_histogram on two pitched float4 images already on the device (rt_measure_exposure: the RADIANCE accumulator and the moments image;
+// rt_probes.hip: the caller's), on the main stream, which the caller has drained. Shared so that the probe and the entry point cannot differ.
+int exposure_measure_images(rt_context * ctx, const char * caller, const float4 * mean, const float4 * moments, int width, int height, int pitch, rt_exposure * out, uint64_t * histogram256) {
+	void * dev = nullptr;
+	int s = device_alloc(ctx, &dev, RT_EXPOSURE_WORDS * 8); if (s) return s;
+	unsigned long long words[RT_EXPOSURE_WORDS] = { };
+	hipError_t e = hipMemsetAsync(dev, 0, RT_EXPOSURE_WORDS * 8, ctx->stream);
+	if (e == hipSuccess) { rt_launch_exposure_histogram(mean, moments, width, height, pitch, (unsigned long long *)dev, ctx->stream); e = hipGetLastError(); }
+	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+	if (e == hipSuccess) e = hipMemcpy(words, dev, sizeof(words), hipMemcpyDeviceToHost);
+	device_free(ctx, dev);
+	if (e != hipSuccess) return fail(ctx, RT_ERROR_HIP, "%s: the histogram kernel or its copies failed: %s", caller, hipGetErrorString(e));
+	out->pixels = 0; out->dark_pixels = int64_t(words[RT_EXPOSURE_DARK]); out->nonfinite_pixels = int64_t(words[RT_EXPOSURE_NONFINITE]);
+	for (int b = 0; b < RT_EXPOSURE_BINS; b++) { histogram256[b] = uint64_t(words[b]); out->pixels += int64_t(words[b]); }
+	return RT_OK;
+}
+
 extern "C" {
+
+int rt_measure_exposure(rt_context * ctx, rt_exposure * out, uint64_t * histogram256) {
+	RT_REQUIRE(ctx, ctx, "rt_measure_exposure: NULL context");
+	RT_REQUIRE(ctx, out && histogram256, "rt_measure_exposure: NULL argument");
+	(void)hipSetDevice(ctx->device);
+	const RtParams & p = ctx->params;
+	if (!ctx->noise_estimate) return fail(ctx, RT_ERROR_NOT_READY, "rt_measure_exposure: the noise estimate is off (rt_set_noise_estimate): its moments image says which pixels hold a sample");
+	if (p.config.enable_svgf) return fail(ctx, RT_ERROR_NOT_READY, "rt_measure_exposure: SVGF is on: its frames keep no moments");
+	if (!ctx->noise_moments || !ctx->aov_buffers[RT_AOV_RADIANCE][1]) return fail(ctx, RT_ERROR_NOT_READY, "rt_measure_exposure: rt_resize was not called");
+	RT_HIP(ctx, quiesce(ctx));
+	return exposure_measure_images(ctx, "rt_measure_exposure", (const float4 *)ctx->aov_buffers[RT_AOV_RADIANCE][1], (const float4 *)ctx->noise_moments, p.screen_width, p.screen_height,
+	                               p.screen_pitch, out, histogram256);
+}
 
 int rt_set_firefly_cascade(rt_context * ctx, const rt_firefly_params * params) {
 	RT_REQUIRE(ctx, ctx, "rt_set_firefly_cascade: NULL context");
@@ -87,7 +117,7 @@ int rt_set_firefly_cascade(rt_context * ctx, const rt_firefly_params * params) {
 		if (!ctx->noise_estimate) return fail(ctx, RT_ERROR_NOT_READY, "rt_set_firefly_cascade: the noise estimate is off (rt_set_noise_estimate): the tiers live beside its moments image");
 	}
 	RT_HIP(ctx, quiesce(ctx));   // the accumulate launches in flight were enqueued with or without the tiers
-	if (!params) { ctx->firefly_on = false; firefly_free(ctx); ctx->folds++; return RT_OK; }
+	if (!params) { ctx->firefly_on = false; ctx->noise_robust = 0.0f; firefly_free(ctx); ctx->folds++; return RT_OK; }   // (the robust estimate follows the resolve: off with it)
 	const bool same = ctx->firefly_on && ctx->firefly.tiers == params->tiers && ctx->firefly.start == params->start;
 	if (same) { ctx->firefly = *params; return RT_OK; }   // (support alone: a value the host reads back)
 	// The new tiers first, the old ones freed once they exist: a call that fails to allocate leaves the previous state in force.
@@ -125,14 +155,14 @@ int rt_read_firefly_cascade(rt_context * ctx, float * dst, size_t capacity) {
 
 int rt_resolve_fireflies(rt_context * ctx, float support) {
 	RT_REQUIRE(ctx, ctx, "rt_resolve_fireflies: NULL context");
-	return resolve_frame(ctx, "rt_resolve_fireflies", support, true, nullptr);
+	return firefly_resolve_frame(ctx, "rt_resolve_fireflies", support, true, nullptr);
 }
 
 int rt_resolve_fireflies_timed(rt_context * ctx, float support, int tiled, float * kernel_ms) {
 	RT_REQUIRE(ctx, ctx, "rt_resolve_fireflies_timed: NULL context");
 	RT_REQUIRE(ctx, kernel_ms, "rt_resolve_fireflies_timed: NULL argument");
 	RT_REQUIRE(ctx, tiled == 0 || tiled == 1, "rt_resolve_fireflies_timed: tiled must be 0 or 1");
-	return resolve_frame(ctx, "rt_resolve_fireflies_timed", support, tiled != 0, kernel_ms);
+	return firefly_resolve_frame(ctx, "rt_resolve_fireflies_timed", support, tiled != 0, kernel_ms);
 }
 
 int rt_read_resolved(rt_context * ctx, float * dst) {

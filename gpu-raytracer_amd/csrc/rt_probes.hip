@@ -1197,6 +1197,59 @@ int rt_resolve_fireflies_images(rt_context * ctx, int width, int height, int pit
 	return probe.finish_and_read(out, images.out, pixels * 16);
 }
 
+int rt_measure_exposure_images(rt_context * ctx, int width, int height, int pitch, const float * mean, const float * moments, rt_exposure * out, uint64_t * histogram256) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_measure_exposure_images: NULL context");
+	RT_REQUIRE(ctx, mean && moments && out && histogram256, "rt_measure_exposure_images: NULL argument");
+	RT_REQUIRE(ctx, width > 0 && height > 0 && pitch >= width, "rt_measure_exposure_images: width and height must be positive and pitch at least width");
+	RT_REQUIRE(ctx, (long long)pitch * height < (1ll << 26), "rt_measure_exposure_images: pitch * height must stay below 2^26");
+	(void)hipSetDevice(ctx->device);
+	RT_HIP(ctx, quiesce(ctx));
+	Probe probe(ctx, "rt_measure_exposure_images");
+	const size_t pixels = size_t(pitch) * size_t(height);
+	const float4 * dev_mean = probe.array<float4>(pixels, mean), * dev_moments = probe.array<float4>(pixels, moments);
+	int s = probe.allocated(); if (s) return s;
+	return exposure_measure_images(ctx, "rt_measure_exposure_images", dev_mean, dev_moments, width, height, pitch, out, histogram256);
+}
+
+int rt_estimate_noise_robust_images(rt_context * ctx, const float * mean, const float * moments, const float * resolved, float floor, float held_fraction,
+                                    rt_noise_estimate * out, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, int32_t * cell_held, size_t cell_capacity,
+                                    float * pixel_map, int64_t * out_held_pixels) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_estimate_noise_robust_images: NULL context");
+	RT_REQUIRE(ctx, mean && moments && resolved && out && cell_sums && cell_counts && cell_nonfinite && cell_held, "rt_estimate_noise_robust_images: NULL argument");
+	RT_REQUIRE(ctx, floor > 0.0f && floor < __builtin_huge_valf(), "rt_estimate_noise_robust_images: floor must be finite and positive");
+	int s = held_fraction_argument(ctx, "rt_estimate_noise_robust_images", held_fraction); if (s) return s;
+	(void)hipSetDevice(ctx->device);
+	if (ctx->frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_estimate_noise_robust_images: rt_resize was not called");
+	RT_HIP(ctx, quiesce(ctx));
+	Probe probe(ctx, "rt_estimate_noise_robust_images");
+	const float4 * dev_mean = probe.array<float4>(ctx->frame_pixels, mean), * dev_moments = probe.array<float4>(ctx->frame_pixels, moments);
+	const NoiseRobust robust = { probe.array<float4>(ctx->frame_pixels, resolved), held_fraction, cell_held, out_held_pixels };
+	if ((s = probe.allocated())) return s;
+	return noise_estimate_images(ctx, "rt_estimate_noise_robust_images", dev_mean, dev_moments, floor, out, cell_sums, cell_counts, cell_nonfinite, cell_capacity, pixel_map, &robust);
+}
+
+int rt_select_pixels_robust_images(rt_context * ctx, const float * mean, const float * moments, const float * resolved, float floor, float held_fraction, float threshold,
+                                   int dilate, rt_cell_selection * out, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, int32_t * cell_held,
+                                   uint8_t * cell_flags, size_t cell_capacity, uint32_t * list, size_t list_capacity) {
+	RT_REQUIRE(ctx, ctx != nullptr, "rt_select_pixels_robust_images: NULL context");
+	RT_REQUIRE(ctx, mean && moments && resolved && out && cell_sums && cell_counts && cell_nonfinite && cell_held && cell_flags && list, "rt_select_pixels_robust_images: NULL argument");
+	int s = selection_arguments(ctx, "rt_select_pixels_robust_images", floor, threshold, dilate); if (s) return s;
+	if ((s = held_fraction_argument(ctx, "rt_select_pixels_robust_images", held_fraction))) return s;
+	(void)hipSetDevice(ctx->device);
+	if (ctx->frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_select_pixels_robust_images: rt_resize was not called");
+	const size_t frame = size_t(ctx->params.screen_width) * size_t(ctx->params.screen_height);
+	RT_REQUIRE(ctx, list_capacity >= frame, "rt_select_pixels_robust_images: list_capacity is below width * height");
+	RT_HIP(ctx, quiesce(ctx));
+	Probe probe(ctx, "rt_select_pixels_robust_images");
+	const float4 * dev_mean = probe.array<float4>(ctx->frame_pixels, mean), * dev_moments = probe.array<float4>(ctx->frame_pixels, moments);
+	const NoiseRobust robust = { probe.array<float4>(ctx->frame_pixels, resolved), held_fraction, cell_held, nullptr };
+	unsigned * dev_list = probe.array<unsigned>(frame, list);   // (what the kernels do not write comes back as the caller gave it)
+	if ((s = probe.allocated())) return s;
+	if ((s = select_cells_images(ctx, "rt_select_pixels_robust_images", dev_mean, dev_moments, floor, threshold, dilate, dev_list, out, cell_sums, cell_counts, cell_nonfinite, cell_flags,
+	                             cell_capacity, &robust))) return s;
+	return probe.read(list, dev_list, frame * 4);
+}
+
 int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps) {
 	RT_REQUIRE(ctx, ctx && out_gbps && bytes >= 1024, "rt_measure_stream_bandwidth: invalid argument");
 	(void)hipSetDevice(ctx->device);

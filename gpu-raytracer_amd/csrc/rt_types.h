@@ -337,11 +337,16 @@ void rt_launch_accumulate(const RtParams & p, const RtAccumulate & accumulate, h
 #define RT_NOISE_CELL 16
 void rt_launch_noise_cells(const float4 * mean, const float4 * moments, int width, int height, int pitch, float floor, float * pixel_map,
                            double * cell_sums, int * cell_counts, int * cell_nonfinite, hipStream_t stream);
+// The firefly-robust estimate: the same kernel text beside the resolved image of the firefly filter. A participating pixel whose resolved .w >= 0
+// and .w > held_fraction * fmaxf(luminance(mean), floor) is held: left out of sum and count, counted in cell_held, -3 in the map.
+void rt_launch_noise_cells_robust(const float4 * mean, const float4 * moments, const float4 * resolved, int width, int height, int pitch, float floor, float held_fraction,
+                                  float * pixel_map, double * cell_sums, int * cell_counts, int * cell_nonfinite, int * cell_held, hipStream_t stream);
 // Adaptive sampling. select: kernel_select_cells, kernel_scan_cells and kernel_compact_cells on the cell arrays of rt_launch_noise_cells: flags
 // (one byte per cell: bit 0 hot, bit 1 active), active_pixels and offsets (one int per cell), totals (3 ints: list length, hot cells, active cells), list (room for
 // width * height entries, x + y * width each). rt_launch_generate_stream_list is the generate step of a submission over such a list.
+// cell_held (the robust cells; null: the plain selection): held pixels count as judged, as non-finite ones do.
 void rt_launch_select_cells(const double * cell_sums, const int * cell_counts, const int * cell_nonfinite, int width, int height, float threshold, int dilate,
-                            unsigned char * flags, int * active_pixels, int * offsets, int * totals, unsigned * list, hipStream_t stream);
+                            unsigned char * flags, int * active_pixels, int * offsets, int * totals, unsigned * list, hipStream_t stream, const int * cell_held = nullptr);
 void rt_launch_generate_stream_list(const RtParams & p, int sample_index, const unsigned * list, int pixel_count, int slot_base, int queue_offset, hipStream_t stream);
 // The still-image denoiser (kernels_denoise.hip): prepare, `iterations` a-trous passes (0..6) of step 1, 2, 4, ..., the last of which finalizes;
 // with 0 iterations prepare and a finalize kernel. any_valid: null, or one int the prepare kernel sets to 1 when a pixel is valid. All images are pitched float4; iv[0], iv[1] and guide are the filter's own (iv[1] is not touched below 2
@@ -357,6 +362,14 @@ void rt_launch_denoise(const RtDenoiseArgs & args, const RtDenoiseImages & image
 struct RtFireflyResolveArgs { int width, height, pitch, tiers; float start, support; };
 struct RtFireflyResolveImages { const float4 * mean, * moments, * fallback, * tiers; size_t plane; float4 * out; int * any_valid; };
 void rt_launch_fireflies_resolve(const RtFireflyResolveArgs & args, const RtFireflyResolveImages & images, bool tiled, hipStream_t stream);
+// The exposure histogram (kernel_exposure_histogram): over the width x height pixels with w >= 1, the float32 exponent of luminance(mean) counted
+// into histogram[0 .. 255], the pixels with luminance <= 0 into [RT_EXPOSURE_DARK], those with a mean that is not finite into [RT_EXPOSURE_NONFINITE]. The
+// caller zeroes the RT_EXPOSURE_WORDS words; the kernel adds to them.
+#define RT_EXPOSURE_BINS 256
+#define RT_EXPOSURE_DARK 256
+#define RT_EXPOSURE_NONFINITE 257
+#define RT_EXPOSURE_WORDS 258
+void rt_launch_exposure_histogram(const float4 * mean, const float4 * moments, int width, int height, int pitch, unsigned long long * histogram, hipStream_t stream);
 // mark(user, k, stream), if given, is called before and after kernel k = 0 reproject, 1 variance, 2 a-trous (each pass), 3 finalize, 4 TAA, 5 TAA finalize
 void rt_launch_svgf_taa(const RtParams & p, int sample_index, hipStream_t stream, void (*mark)(void * user, int svgf_kernel, hipStream_t stream) = nullptr, void * user = nullptr);
 void rt_launch_random(const RtParams & p, int dimension, const unsigned * pixel_indices, int count, unsigned bounce, unsigned sample_index, float2 * out, hipStream_t stream);

@@ -134,6 +134,18 @@ struct CPUConfig {
 	int   firefly_filter = 0;
 	int   firefly_tiers = 6;
 	float firefly_start = 1.0f, firefly_support = 4.0f;
+	// A start taken from the frame's own exposure. firefly_auto_start 1: the progression begins with firefly_start, as above; after
+	// firefly_pilot_samples uniform samples (>= 2: sample 1 overwrites sample 0) Pathtracer measures the exponent histogram of the mean's luminance
+	// (rt_measure_exposure), takes start = 2^(median exponent + firefly_start_shift) (grt_exposure_start) and, where that differs from the start in force, sets
+	// it and starts over at sample 0. firefly_start_shift, -16 .. 16: 0, the measured default (tools/fireflies_sweep.py --auto-start), makes the median brightness
+	// class the lowest tier's boundary; tiers are a factor 8 apart, so shifts three apart resolve alike while the tiers cover the frame's range.
+	int   firefly_auto_start = 0;
+	int   firefly_start_shift = 0;
+	int   firefly_pilot_samples = 4;
+	// The firefly-robust noise estimate (needs firefly_filter = 1, else one warning and the plain estimate). noise_robust 1: Pathtracer::noise and
+	// select_adaptive leave out the pixels of which the resolve holds back more than noise_held_fraction (in (0, 1)) of their brightness.
+	int   noise_robust = 0;
+	float noise_held_fraction = 0.25f;
 	// Alpha-tested cut-outs from the albedo textures: 1 = every surface material whose albedo FILE has an alpha channel that is not constant gets an
 	// opacity mask from it (channel a, threshold 0.5; an explicit <bsdf type="mask"> wins). Read when a scene is loaded. 0: off, as the reference renders them.
 	int   alpha_masks = 0;

@@ -1,5 +1,6 @@
 #include "FrameSplit.h"
 
+#include <cstdio>
 #include <stdexcept>
 #include <string>
 
@@ -9,6 +10,7 @@ FrameSplit::FrameSplit(int width, int height, Scene & scene, const std::vector<i
 		ranks.push_back(std::make_unique<Pathtracer>(width, height, scene, device));
 		if (!ranks.back()->ctx) throw std::runtime_error("FrameSplit: no device context for device " + std::to_string(device));
 		contexts.push_back(ranks.back()->ctx);
+		ranks.back()->noise_robust_allowed = false;   // the tiers are not gathered: the ranks keep the plain estimate (update() warns once)
 	}
 	tile_pixels = width * TILE_ROWS;
 	if (world() > 1) {
@@ -62,6 +64,10 @@ void FrameSplit::check(rt_context * ctx, int status) const {
 }
 
 void FrameSplit::update(float delta) {
+	if (cpu_config.noise_robust && !warned_noise_robust) {
+		fprintf(stderr, "WARNING: noise_robust does not work across a frame split (the firefly tiers are not gathered): keeping the plain noise estimate\n");
+		warned_noise_robust = true;
+	}
 	// the ranks share the host scene: rank 0's update() advances it (camera matrices, animated meshes: "current" becomes
 	// "previous"), the others upload the state it left
 	for (int r = 0; r < world(); r++) {

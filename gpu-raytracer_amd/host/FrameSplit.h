@@ -31,6 +31,7 @@ struct FrameSplit {
 	Scene & scene;
 	std::vector<std::unique_ptr<Pathtracer>> ranks;   // ranks[r] renders tiles r, r + world, r + 2 world, ...
 	int tile_pixels = 0;
+	bool warned_noise_robust = false;
 
 	FrameSplit(int width, int height, Scene & scene, const std::vector<int> & device_ordinals);
 	~FrameSplit();

@@ -819,7 +819,8 @@ void Integrator::update(float delta) {
 		rt_firefly_params have = { };
 		const bool on = rt_get_firefly_cascade(ctx, &have) != 0;
 		if (cpu_config.firefly_filter && splats_fireflies) {
-			const rt_firefly_params wanted = { cpu_config.firefly_tiers, cpu_config.firefly_start, cpu_config.firefly_support };
+			const float start = cpu_config.firefly_auto_start && firefly_start_in_force > 0.0f ? firefly_start_in_force : cpu_config.firefly_start;   // (the measured start stays in force across restarts)
+			const rt_firefly_params wanted = { cpu_config.firefly_tiers, start, cpu_config.firefly_support };
 			if (!on || have.tiers != wanted.tiers || have.start != wanted.start) { check(rt_set_firefly_cascade(ctx, &wanted)); invalidated_gpu_config = true; }
 			else if (have.support != wanted.support) check(rt_set_firefly_cascade(ctx, &wanted));   // (a value of the resolve)
 		} else if (on) check(rt_set_firefly_cascade(ctx, nullptr));

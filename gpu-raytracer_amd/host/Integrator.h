@@ -56,6 +56,7 @@ struct Integrator {
 	int pixel_count = 0;
 	int sample_index = 0;
 	bool splats_fireflies = true;         // false for an integrator whose accumulate keeps no moments (AO): update() then leaves the firefly cascade of cpu_config.firefly_filter off
+	float firefly_start_in_force = 0.0f;  // cpu_config.firefly_auto_start: the start Pathtracer measured, which update() then keeps on the device; 0: none yet, cpu_config.firefly_start
 	bool noise_estimate_wanted = false;   // the device keeps second moments (rt_set_noise_estimate) while this is set or cpu_config.noise_target > 0; applied by update()
 
 	// Multi-GPU: scan-order pixel range rendered by this integrator (default: all)

@@ -184,6 +184,12 @@ void Pathtracer::calc_delta_lights() {
 
 // reference: Pathtracer::update (Pathtracer.cpp:536-736)
 void Pathtracer::update(float delta) {
+	{   // automatic start: a resize, a change of the scene or of a firefly key drops the measured start -- Integrator::update then puts firefly_start back
+		const FireflyStartKey key = { screen_width, screen_height, cpu_config.firefly_filter, cpu_config.firefly_auto_start, cpu_config.firefly_tiers, cpu_config.firefly_start_shift,
+		                              cpu_config.firefly_pilot_samples, cpu_config.firefly_start };
+		const bool scene_changed = invalidated_sky || invalidated_materials || invalidated_mediums || (invalidated_scene && !cpu_config.enable_scene_update);
+		if (scene_changed || memcmp(&key, &firefly_start_key, sizeof(key)) != 0) { firefly_start_key = key; firefly_start_measured = false; firefly_start_in_force = 0.0f; }
+	}
 	if (invalidated_sky) {
 		invalidated_sky = false;
 		if (ctx) check(rt_set_sky(ctx, &scene.sky.data[0].x, scene.sky.width, scene.sky.height, scene.sky.scale));
@@ -330,6 +336,15 @@ void Pathtracer::update(float delta) {
 		}
 		invalidated_fog = false;
 	}
+	if (ctx) {   // the firefly-robust estimate follows the cascade
+		const bool cascade = rt_get_firefly_cascade(ctx, nullptr) != 0;
+		if (cpu_config.noise_robust && !cascade && noise_robust_allowed && !warned_noise_robust) {
+			fprintf(stderr, "WARNING: noise_robust needs the firefly filter (firefly_filter = 1, plain path tracing): keeping the plain noise estimate\n");
+			warned_noise_robust = true;
+		}
+		const float wanted = cpu_config.noise_robust && cascade && noise_robust_allowed ? cpu_config.noise_held_fraction : 0.0f;
+		if (rt_get_noise_robust(ctx) != wanted) check(rt_set_noise_robust(ctx, wanted));
+	}
 	if (invalidated_light_mesh_weights || invalidated_delta_lights) {   // (after the emitters: the share weighs against their total; after the TLAS: the scene's bounds)
 		if (!scene.delta_lights.empty() || !delta_light_records.empty() || delta_lights_uploaded) calc_delta_lights();
 		invalidated_delta_lights = false;
@@ -341,8 +356,41 @@ static void restart_drops_pixel_list(rt_context * ctx, int sample_index) {
 	if (sample_index < 2 && rt_get_pixel_list(ctx)) rt_set_pixel_list(ctx, 0);
 }
 
+float Pathtracer::firefly_start() const {
+	rt_firefly_params have = { };
+	return ctx && rt_get_firefly_cascade(ctx, &have) ? have.start : cpu_config.firefly_start;
+}
+
+bool Pathtracer::firefly_pilot_pending() const {
+	return cpu_config.firefly_filter && cpu_config.firefly_auto_start && !firefly_start_measured && !gpu_config.enable_svgf && rt_get_firefly_cascade(ctx, nullptr) != 0;
+}
+
+// Automatic start, called before sample `sample_index` is rendered: once the pilot samples 0 .. firefly_pilot_samples - 1 are in the frame, the
+// exposure is measured and the start computed; a start other than the one in force is set -- which zeroes the tiers -- and the progression starts over at sample 0.
+void Pathtracer::measure_firefly_start() {
+	if (!firefly_pilot_pending() || sample_index < cpu_config.firefly_pilot_samples) return;
+	rt_exposure exposure = { }; uint64_t histogram[256];
+	check(rt_measure_exposure(ctx, &exposure, histogram));
+	firefly_start_measured = true;
+	float start = 0.0f;
+	if (grt_exposure_start(histogram, cpu_config.firefly_start_shift, &start, &firefly_median_exponent) != 0) {
+		if (!warned_firefly_start_empty) fprintf(stderr, "WARNING: firefly_auto_start: no pixel of the pilot has a positive finite luminance; keeping firefly_start %g\n", cpu_config.firefly_start);
+		warned_firefly_start_empty = true;
+		return;
+	}
+	rt_firefly_params cascade = { };
+	rt_get_firefly_cascade(ctx, &cascade);
+	firefly_start_in_force = start;
+	if (cascade.start == start) return;
+	cascade.start = start;
+	check(rt_set_firefly_cascade(ctx, &cascade));
+	firefly_pilot_samples_discarded += sample_index;
+	sample_index = 0;
+}
+
 void Pathtracer::render() {
 	require_device();
+	measure_firefly_start();
 	restart_drops_pixel_list(ctx, sample_index);
 	check(rt_render_sample(ctx, sample_index));
 	if (pixel_query_status == PixelQueryStatus::PENDING) pixel_query_status = PixelQueryStatus::OUTPUT_READY; // Pathtracer.cpp:852-854
@@ -351,6 +399,7 @@ void Pathtracer::render() {
 void Pathtracer::render_samples(int count) {
 	require_device();
 	if (count < 1) return;
+	measure_firefly_start();
 	restart_drops_pixel_list(ctx, sample_index);
 	if (pixel_query_status == PixelQueryStatus::PENDING) pixel_query_status = PixelQueryStatus::OUTPUT_READY;
 	if (gpu_config.enable_svgf) { // SVGF frames feed each other's history: one at a time
@@ -359,10 +408,11 @@ void Pathtracer::render_samples(int count) {
 	}
 	while (count > 0) {
 		int n = count < 16 ? count : 16;
+		if (firefly_pilot_pending() && sample_index < cpu_config.firefly_pilot_samples && n > cpu_config.firefly_pilot_samples - sample_index) n = cpu_config.firefly_pilot_samples - sample_index;   // the pilot ends a burst
 		check(rt_render_samples(ctx, sample_index, n));
 		sample_index += n - 1;
 		count -= n;
-		if (count > 0) sample_index++;
+		if (count > 0) { sample_index++; measure_firefly_start(); restart_drops_pixel_list(ctx, sample_index); }
 	}
 }
 
@@ -388,6 +438,23 @@ int grt_noise_summary(const double * cell_sums, const int32_t * cell_counts, siz
 	return 0;
 }
 
+// The cascade's start from the exposure histogram of rt_measure_exposure: two to the median exponent plus `shift`. The median bin is the
+// smallest bin whose cumulative count reaches rank (pixels + 1) / 2; the exponent is clamped to -96 .. 96, which keeps start * 8^7 finite. 1, with nothing
+// written, for an empty histogram.
+int grt_exposure_start(const uint64_t * histogram256, int shift, float * out_start, int * out_median_exponent) {
+	uint64_t pixels = 0;
+	for (int b = 0; b < 256; b++) pixels += histogram256[b];
+	if (pixels == 0) return 1;
+	const uint64_t rank = pixels / 2 + pixels % 2;   // (pixels + 1) / 2 without the overflow
+	uint64_t reached = 0; int bin = 0;
+	for (; bin < 256; bin++) { reached += histogram256[bin]; if (reached >= rank) break; }
+	int exponent = bin - 127 + shift;
+	exponent = exponent < -96 ? -96 : exponent > 96 ? 96 : exponent;
+	if (out_start) *out_start = std::ldexp(1.0f, exponent);
+	if (out_median_exponent) *out_median_exponent = exponent;
+	return 0;
+}
+
 NoiseEstimate Pathtracer::noise(std::vector<float> * pixel_map, bool allow_empty) {
 	require_device();
 	if (!rt_get_noise_estimate(ctx)) throw std::runtime_error("Pathtracer::noise: the noise estimate is off (set noise_estimate_wanted or cpu_config.noise_target before update())");
@@ -397,10 +464,20 @@ NoiseEstimate Pathtracer::noise(std::vector<float> * pixel_map, bool allow_empty
 	e.cell_sums.assign(cells, 0.0); e.cell_counts.assign(cells, 0); e.cell_nonfinite.assign(cells, 0);
 	if (pixel_map) pixel_map->assign(size_t(screen_pitch) * screen_height, -1.0f);
 	rt_noise_estimate out = { };
-	int status = rt_estimate_noise(ctx, cpu_config.noise_floor, &out, e.cell_sums.data(), e.cell_counts.data(), e.cell_nonfinite.data(), cells, pixel_map ? pixel_map->data() : nullptr);
+	const float held_fraction = rt_get_noise_robust(ctx);   // (update() keeps it at cpu_config.noise_held_fraction while noise_robust is in force)
+	e.robust = held_fraction > 0.0f;
+	int status;
+	if (e.robust) {
+		e.cell_held.assign(cells, 0);
+		int64_t held = 0;
+		status = rt_estimate_noise_robust(ctx, cpu_config.noise_floor, held_fraction, &out, e.cell_sums.data(), e.cell_counts.data(), e.cell_nonfinite.data(), e.cell_held.data(), cells,
+		                                  pixel_map ? pixel_map->data() : nullptr, &held);
+		e.held_pixels = held;
+	} else status = rt_estimate_noise(ctx, cpu_config.noise_floor, &out, e.cell_sums.data(), e.cell_counts.data(), e.cell_nonfinite.data(), cells, pixel_map ? pixel_map->data() : nullptr);
 	if (!(status == RT_ERROR_NOT_READY && allow_empty && out.cells_x == e.cells_x)) check(status);   // (an empty frame's arrays and counters are filled before the refusal)
 	e.nonfinite_pixels = out.nonfinite_pixels;
 	grt_noise_summary(e.cell_sums.data(), e.cell_counts.data(), cells, cpu_config.noise_quantile, &e.mean, &e.figure, &e.pixels);
+	last_noise_robust = e.robust; last_noise_held_pixels = e.held_pixels; last_noise_cell_held = e.cell_held;
 	return e;
 }
 

@@ -13,10 +13,16 @@ struct NoiseEstimate {
 	std::vector<double> cell_sums; std::vector<int32_t> cell_counts, cell_nonfinite;
 	long long pixels = 0, nonfinite_pixels = 0;
 	double mean = 0.0, figure = 0.0;
+	// The firefly-robust estimate (cpu_config.noise_robust): the pixels the resolve holds back are left out of sums and counts and counted here
+	bool robust = false;
+	std::vector<int32_t> cell_held; long long held_pixels = 0;
 };
 // mean and figure from cell arrays, for C++ and Python alike. The mean: the sums added in cell order over the counts' total. The figure: the means sum / count of
 // the cells with count > 0, sorted; entry ceil(quantile * m) of the m (1-based, at least 1). 0: fine; 1: no cell has a count (both 0); -1: quantile outside (0, 1].
 extern "C" int grt_noise_summary(const double * cell_sums, const int32_t * cell_counts, size_t cells, double quantile, double * out_mean, double * out_figure, long long * out_pixels);
+// The firefly cascade's start from the exposure histogram of rt_measure_exposure: 2^(median exponent + shift), the exponent clamped to
+// -96 .. 96. 0: fine; 1: the histogram is empty, nothing is written. Either result may be NULL.
+extern "C" int grt_exposure_start(const uint64_t * histogram256, int shift, float * out_start, int * out_median_exponent);
 
 // What Pathtracer::select_adaptive chose: of `cells` cells, the hot ones (mean error above the threshold, or pixels not judged yet), the active
 // ones (hot, or beside a hot one under cpu_config.adaptive_dilate) and the pixels of the active cells -- what the next render calls cover.
@@ -64,6 +70,8 @@ struct Pathtracer final : Integrator {
 	void render_samples(int count);
 	// The estimate of what has been accumulated so far (completes the work in flight). Needs the device estimate on: noise_estimate_wanted or
 	// cpu_config.noise_target > 0 before the update() of sample 0. pixel_map: e_p per pixel at x + y * pitch, -1 where the pixel takes no part, -2 non-finite.
+	// While cpu_config.noise_robust is in force (update() sets rt_set_noise_robust) this is rt_estimate_noise_robust -- a resolve, then the cells without the held
+	// pixels, -3 in the map --, and select_adaptive selects from the same cells.
 	// Throws when the estimate is off; a frame without a participating pixel (allow_empty) returns pixels == 0 instead of throwing.
 	NoiseEstimate noise(std::vector<float> * pixel_map = nullptr, bool allow_empty = false);
 	// Adaptive sampling: selects the cells whose mean error is above `threshold` (rt_select_active_cells with cpu_config.noise_floor and
@@ -83,6 +91,14 @@ struct Pathtracer final : Integrator {
 	// cpu_config.firefly_filter = 1 before the update() of sample 0 (which switches on the noise estimate and the cascade) and no SVGF. support: kappa, 0 for the
 	// configuration's. Completes the work in flight and changes nothing a later render reads.
 	std::vector<float> resolve_fireflies(float support = 0.0f);
+	// The start of the cascade in force: cpu_config.firefly_start, or under cpu_config.firefly_auto_start what was measured after the pilot samples
+	// (DESIGN.md 7.10.1). The measured start survives restarts of the progression; a resize, a change of the scene or of a firefly key measures again.
+	float firefly_start() const;
+	bool noise_robust_allowed = true;               // false: a rank of a FrameSplit, whose tiers are not gathered -- update() keeps the plain estimate
+	bool last_noise_robust = false; long long last_noise_held_pixels = 0; std::vector<int32_t> last_noise_cell_held;   // of the last noise()
+	bool firefly_start_measured = false;            // the pilot of the current configuration has been rendered and measured
+	int  firefly_median_exponent = 0;               // what it found (with the shift, clamped), when a start could be computed
+	long long firefly_pilot_samples_discarded = 0;  // samples rendered and dropped by restarts after a measurement ("extra")
 	// The resolved image through the exporters save_image uses (ppm, exr by the file's extension)
 	void save_resolved_image(const std::string & filename, float support = 0.0f);
 	// w per pixel (x + y * pitch; 0 in the padding) -- the number of samples the pixel's mean stands for -- and, returned, the mean of w over the frame's pixels.
@@ -93,5 +109,11 @@ struct Pathtracer final : Integrator {
 	void geometry_was_rebuilt() override { if (scene.has_lights) calc_light_power(); }   // light_triangle_indices name device triangles
 	void calc_light_mesh_weights();
 	void calc_delta_lights();
+
+private:
+	void measure_firefly_start();   // before a sample is rendered
+	bool firefly_pilot_pending() const;
+	struct FireflyStartKey { int width, height, filter, automatic, tiers, shift, pilot; float start; } firefly_start_key = { };
+	bool warned_firefly_start_empty = false, warned_noise_robust = false;
 
 };

@@ -154,6 +154,26 @@ int grt_config_set(const char * key, double value) {
 		if (!(value > 0.0 && value < 1e30)) { g_host_error = "firefly_start must be finite and above 0"; return -1; }
 		cpu_config.firefly_start = float(value);
 	}
+	else if (k == "firefly_auto_start") {
+		if (!(value == 0.0 || value == 1.0)) { g_host_error = "firefly_auto_start must be 0 or 1"; return -1; }
+		cpu_config.firefly_auto_start = int(value);
+	}
+	else if (k == "firefly_start_shift") {
+		if (!(value >= -16.0 && value <= 16.0) || value != double(int(value))) { g_host_error = "firefly_start_shift must be a whole number in [-16, 16]"; return -1; }
+		cpu_config.firefly_start_shift = int(value);
+	}
+	else if (k == "firefly_pilot_samples") {
+		if (!(value >= 2.0 && value <= 1e6) || value != double(int(value))) { g_host_error = "firefly_pilot_samples must be a whole number of at least 2 (sample 1 overwrites sample 0)"; return -1; }
+		cpu_config.firefly_pilot_samples = int(value);
+	}
+	else if (k == "noise_robust") {
+		if (!(value == 0.0 || value == 1.0)) { g_host_error = "noise_robust must be 0 or 1"; return -1; }
+		cpu_config.noise_robust = int(value);
+	}
+	else if (k == "noise_held_fraction") {
+		if (!(value > 0.0 && value < 1.0)) { g_host_error = "noise_held_fraction must lie inside (0, 1)"; return -1; }
+		cpu_config.noise_held_fraction = float(value);
+	}
 	else if (k == "firefly_support") {
 		if (!(value > 1.0 && value < 1e30)) { g_host_error = "firefly_support must be finite and above 1"; return -1; }
 		cpu_config.firefly_support = float(value);
@@ -235,6 +255,11 @@ double grt_config_get(const char * key) {
 	if (k == "firefly_tiers")      return cpu_config.firefly_tiers;
 	if (k == "firefly_start")      return cpu_config.firefly_start;
 	if (k == "firefly_support")    return cpu_config.firefly_support;
+	if (k == "firefly_auto_start") return cpu_config.firefly_auto_start;
+	if (k == "firefly_start_shift") return cpu_config.firefly_start_shift;
+	if (k == "firefly_pilot_samples") return cpu_config.firefly_pilot_samples;
+	if (k == "noise_robust")       return cpu_config.noise_robust;
+	if (k == "noise_held_fraction") return cpu_config.noise_held_fraction;
 	return -1.0;
 }
 
@@ -604,6 +629,30 @@ int grt_pathtracer_noise(void * pt, int * cells_xy, double * cell_sums, int32_t 
 		NoiseEstimate e = as_pathtracer(pt)->noise(pixel_map ? &map : nullptr);
 		if (pixel_map) memcpy(pixel_map, map.data(), map.size() * 4);
 		return noise_out(e, cells_xy, cell_sums, cell_counts, cell_nonfinite, cell_capacity, mean_figure, pixels_nonfinite);
+	GRT_CATCH(-1)
+}
+// The firefly-robust estimate: what the last Pathtracer::noise (grt_pathtracer_noise) found and grt_pathtracer_noise's fixed outputs have no room
+// for. out2: robust (0 / 1), held pixels; cell_held: NULL, or cell_capacity entries (zeros under the plain estimate).
+int grt_pathtracer_noise_held(void * pt, long long * out2, int32_t * cell_held, size_t cell_capacity) {
+	GRT_TRY
+		if (!pt || !out2) throw std::runtime_error("grt_pathtracer_noise_held: NULL argument");
+		const Pathtracer * p = as_pathtracer(pt);
+		out2[0] = p->last_noise_robust ? 1 : 0; out2[1] = p->last_noise_held_pixels;
+		if (cell_held) {
+			if (cell_capacity < p->last_noise_cell_held.size()) { g_host_error = "noise: cell_capacity is below cells_x * cells_y"; return -1; }
+			memset(cell_held, 0, cell_capacity * 4);
+			memcpy(cell_held, p->last_noise_cell_held.data(), p->last_noise_cell_held.size() * 4);
+		}
+		return 0;
+	GRT_CATCH(-1)
+}
+// Automatic start of the firefly cascade. out3: the start in force, 1 when the pilot has been measured (else 0), the pilot samples discarded so far.
+int grt_pathtracer_firefly_start(void * pt, double * out3) {
+	GRT_TRY
+		if (!pt || !out3) throw std::runtime_error("grt_pathtracer_firefly_start: NULL argument");
+		Pathtracer * p = as_pathtracer(pt);
+		out3[0] = p->firefly_start(); out3[1] = p->firefly_start_measured ? 1.0 : 0.0; out3[2] = double(p->firefly_pilot_samples_discarded);
+		return 0;
 	GRT_CATCH(-1)
 }
 int grt_frame_split_noise(void * split, int * cells_xy, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, size_t cell_capacity, double * mean_figure, long long * pixels_nonfinite, float * pixel_map) {

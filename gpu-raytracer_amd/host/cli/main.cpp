@@ -47,6 +47,8 @@ struct CommandLine {
 	std::string firefly_map;         // --firefly-map
 	std::string firefly_unfiltered;  // --firefly-unfiltered
 	bool firefly_option = false;     // an option that needs --firefly-filter was given
+	bool firefly_auto_option = false;   // an option that needs --firefly-auto-start was given
+	bool noise_robust_option = false;   // an option that needs --noise-robust was given
 };
 
 [[noreturn]] void die(const std::string & message) {
@@ -173,6 +175,23 @@ std::vector<Option> make_options(CommandLine & cl) {
 		if (!(k > 1.0f && k < 1e30f)) die("--firefly-support must be finite and above 1");
 		cpu_config.firefly_support = k; cl.firefly_option = true;
 	} });
+	o.push_back({ nullptr, "firefly-auto-start", "With --firefly-filter: takes the lowest tier's luminance from the frame's own exposure after a few pilot samples, then starts over (DESIGN.md 7.10.1); replaces --firefly-start unless no pixel is lit", 0, [](const char *) { cpu_config.firefly_auto_start = 1; } });
+	o.push_back({ nullptr, "firefly-start-shift", "With --firefly-auto-start: the start is 2^(median exponent of the luminance + n), n in -16 .. 16 (default 0)", 1, [&cl](const char * v) {
+		int n = parse_int(v, "--firefly-start-shift");
+		if (n < -16 || n > 16) die("--firefly-start-shift must be between -16 and 16");
+		cpu_config.firefly_start_shift = n; cl.firefly_auto_option = true;
+	} });
+	o.push_back({ nullptr, "firefly-pilot", "With --firefly-auto-start: the number of pilot samples the exposure is measured on (at least 2, default 4); they are discarded", 1, [&cl](const char * v) {
+		int n = parse_int(v, "--firefly-pilot");
+		if (n < 2 || n > 1000000) die("--firefly-pilot must be at least 2 (sample 1 overwrites sample 0)");
+		cpu_config.firefly_pilot_samples = n; cl.firefly_auto_option = true;
+	} });
+	o.push_back({ nullptr, "noise-robust", "With --firefly-filter and --noise-target or --noise-map: the noise estimate and --adaptive leave out the pixels the firefly filter holds back (DESIGN.md 7.10.2)", 0, [](const char *) { cpu_config.noise_robust = 1; } });
+	o.push_back({ nullptr, "noise-held-fraction", "With --noise-robust: a pixel is held when more than this fraction of its brightness is held back (inside (0, 1), default 0.25)", 1, [&cl](const char * v) {
+		float t = parse_float(v, "--noise-held-fraction");
+		if (!(t > 0.0f && t < 1.0f)) die("--noise-held-fraction must lie inside (0, 1)");
+		cpu_config.noise_held_fraction = t; cl.noise_robust_option = true;
+	} });
 	o.push_back({ nullptr, "firefly-map", "With --firefly-filter: writes the luminance held back per pixel as a one-channel EXR", 1, [&cl](const char * v) { cl.firefly_map = v; cl.firefly_option = true; } });
 	o.push_back({ nullptr, "firefly-unfiltered", "With --firefly-filter: also writes the plain image to <file> (ppm, exr)", 1, [&cl](const char * v) { cl.firefly_unfiltered = v; cl.firefly_option = true; } });
 	o.push_back({ nullptr, "sample-map", "Writes the number of samples every pixel's mean stands for as a one-channel EXR", 1, [&cl](const char * v) { cl.sample_map = v; } });
@@ -257,6 +276,11 @@ void parse_command_line(int argc, char ** argv, CommandLine & cl) {
 	if (cl.denoise_option && !cpu_config.denoise) die("--denoise-iterations / --denoise-noisy need --denoise");
 	if (!cl.denoise_noisy.empty() && cl.denoise_noisy == cpu_config.output_filename) die("--denoise-noisy names the output file: the denoised image goes there");
 	if (cl.firefly_option && !cpu_config.firefly_filter) die("--firefly-tiers / --firefly-start / --firefly-support / --firefly-map / --firefly-unfiltered need --firefly-filter");
+	if (cpu_config.firefly_auto_start && !cpu_config.firefly_filter) die("--firefly-auto-start needs --firefly-filter");
+	if (cl.firefly_auto_option && !cpu_config.firefly_auto_start) die("--firefly-start-shift / --firefly-pilot need --firefly-auto-start");
+	if (cpu_config.noise_robust && !cpu_config.firefly_filter) die("--noise-robust needs --firefly-filter: it follows the filter's judgement");
+	if (cpu_config.noise_robust && !(cpu_config.noise_target > 0.0f) && cl.noise_map.empty()) die("--noise-robust needs --noise-target or --noise-map: it is an estimate nobody asks for");
+	if (cl.noise_robust_option && !cpu_config.noise_robust) die("--noise-held-fraction needs --noise-robust");
 	if (!cl.firefly_unfiltered.empty() && cl.firefly_unfiltered == cpu_config.output_filename) die("--firefly-unfiltered names the output file: the resolved image goes there");
 	if (!cl.firefly_map.empty() && (cl.firefly_map == cpu_config.output_filename || cl.firefly_map == cl.firefly_unfiltered)) die("--firefly-map names a file another image goes to");
 	if (cl.print_config) { // one line, floats as bit patterns; the form oracle/ref/ref_scene_harness.cpp writes for the reference's Args::parse
@@ -312,13 +336,16 @@ struct NoiseStop {
 	template<typename Renderer> void report(Renderer & r, int sample_index, const std::string & map_file, int pitch, int width, int height) {
 		if (active) {
 			if (!reached) { last = r.noise(); have = true; reached = last.pixels > 0 && last.figure <= double(cpu_config.noise_target); }
-			printf("Noise: figure %.6g (mean %.6g, target %.6g) after sample %d; %s\n", last.figure, last.mean, double(cpu_config.noise_target), sample_index,
-			       reached ? "target reached" : "stopped at the sample cap");
+			if (last.robust) printf("Noise (firefly-robust, %lld pixels held): figure %.6g (mean %.6g, target %.6g) after sample %d; %s\n", last.held_pixels, last.figure, last.mean,
+			                        double(cpu_config.noise_target), sample_index, reached ? "target reached" : "stopped at the sample cap");
+			else printf("Noise: figure %.6g (mean %.6g, target %.6g) after sample %d; %s\n", last.figure, last.mean, double(cpu_config.noise_target), sample_index,
+			            reached ? "target reached" : "stopped at the sample cap");
 		}
 		if (!map_file.empty()) {
 			std::vector<float> map;
-			r.noise(&map);
-			for (float & v : map) if (v < 0.0f) v = 0.0f;
+			const NoiseEstimate mapped = r.noise(&map);
+			if (mapped.robust && !active) printf("Noise map: firefly-robust, %lld pixels held\n", mapped.held_pixels);
+			for (float & v : map) if (v < 0.0f) v = 0.0f;   // (no part, non-finite, held)
 			if (!EXRExporter::save_luminance(map_file, pitch, width, height, map)) die("failed to write '" + map_file + "'");
 			printf("Wrote %s\n", map_file.c_str());
 		}
@@ -370,6 +397,10 @@ int main(int argc, char ** argv) {
 		if (cpu_config.firefly_filter && cl.devices.size() > 1) {   // (the tiers are not gathered)
 			fprintf(stderr, "WARNING: --firefly-filter does not work across --devices: writing the plain image\n");
 			cpu_config.firefly_filter = 0;
+		}
+		if (cpu_config.noise_robust && !cpu_config.firefly_filter) {   // (switched off above: the robust estimate follows the filter's resolve)
+			fprintf(stderr, "WARNING: --noise-robust needs the firefly filter: keeping the plain noise estimate\n");
+			cpu_config.noise_robust = 0;
 		}
 		if (!cl.sample_map.empty() && cl.devices.size() > 1) { fprintf(stderr, "WARNING: --sample-map does not work across --devices: ignored\n"); cl.sample_map.clear(); }
 		noise.active = cpu_config.noise_target > 0.0f;
@@ -449,7 +480,11 @@ int main(int argc, char ** argv) {
 				plane[i] = resolved[4 * i + 3];
 				if (resolved[4 * i + 3] >= 0.0f) { held += resolved[4 * i + 3]; kept += 0.299 * resolved[4 * i] + 0.587 * resolved[4 * i + 1] + 0.114 * resolved[4 * i + 2]; }
 			}
-			printf("Firefly filter: %d tiers from %g, support %g; %.3f %% of the luminance held back; resolve %.1f ms\n", cpu_config.firefly_tiers, cpu_config.firefly_start, cpu_config.firefly_support,
+			if (cpu_config.firefly_auto_start && pathtracer->firefly_start_measured && pathtracer->firefly_start_in_force > 0.0f)
+				printf("Firefly start: %g from the exposure of %d pilot samples (median exponent %d with shift %d; %lld samples discarded)\n", double(pathtracer->firefly_start()),
+				       cpu_config.firefly_pilot_samples, pathtracer->firefly_median_exponent, cpu_config.firefly_start_shift, pathtracer->firefly_pilot_samples_discarded);
+			else if (cpu_config.firefly_auto_start) printf("Firefly start: %g (no exposure could be measured)\n", double(pathtracer->firefly_start()));
+			printf("Firefly filter: %d tiers from %g, support %g; %.3f %% of the luminance held back; resolve %.1f ms\n", cpu_config.firefly_tiers, double(pathtracer->firefly_start()), cpu_config.firefly_support,
 			       held + kept > 0.0 ? 100.0 * held / (held + kept) : 0.0, seconds_since(t2) * 1e3);
 			if (!cl.firefly_map.empty()) {
 				if (!EXRExporter::save_luminance(cl.firefly_map, integrator->screen_pitch, integrator->screen_width, integrator->screen_height, plane)) die("failed to write '" + cl.firefly_map + "'");

@@ -172,6 +172,9 @@ const char * rt_version(void);
  *      rt_set_denoise_source, rt_get_denoise_source, rt_accumulate_cascade_frames, rt_resolve_fireflies_images -- new entry points and a parameter struct of their
  *      own; the firefly filter, off until it is set)
  *      (still 17: rt_trace_queue_rays -- a new entry point; the frame's per-bounce traversal launches on explicit queues, for tests)
+ *      (still 17: rt_measure_exposure, rt_measure_exposure_images, rt_estimate_noise_robust, rt_set_noise_robust, rt_get_noise_robust,
+ *      rt_estimate_noise_robust_images, rt_select_pixels_robust_images -- new entry points and a result struct of their own; the frame's exposure and the
+ *      firefly-robust noise estimate, both off until they are called or set)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
 #define RT_ABI_VERSION 17
 int rt_abi_version(void);
@@ -744,6 +747,33 @@ int rt_resolve_fireflies_timed(rt_context * ctx, float support, int tiled, float
 int rt_set_denoise_source(rt_context * ctx, int source);
 int rt_get_denoise_source(const rt_context * ctx);
 
+/* The frame's exposure: which power of two its pixels are bright as, for a cascade start relative to the frame (grt_exposure_start of the
+ * host library turns the histogram into one). Over the width x height pixels of the RADIANCE mean and the moments image, the padding columns never read:
+ * a pixel with w < 1 (or a w that is NaN) takes no part; with w >= 1 and r, g, b or luminance(mean) not finite it counts in nonfinite_pixels; Y =
+ * luminance(mean), float32 in the shape of rt_estimate_noise; Y <= 0 counts in dark_pixels; else histogram256[(bits(Y) >> 23) & 255] gets one count -- the
+ * biased exponent, denormals in bin 0. pixels: the total of the 256 bins. Integer counts: the same on every run.
+ * rt_measure_exposure completes the work in flight and writes nothing a render reads; RT_ERROR_NOT_READY while the noise estimate is off (no w), while SVGF is on
+ * (its frames keep no moments) and before rt_resize. (Additions that change no struct and no call: RT_ABI_VERSION stays.)                              */
+typedef struct rt_exposure { int64_t pixels, dark_pixels, nonfinite_pixels; } rt_exposure;
+int rt_measure_exposure(rt_context * ctx, rt_exposure * out, uint64_t * histogram256);
+
+/* The firefly-robust noise estimate: rt_estimate_noise that follows the resolve's judgement. held_fraction tau in (0, 1) (the host's default
+ * 0.25: a quarter of the pixel's light is unsupported) is part of the definition, as floor is. A pixel that takes part by rt_estimate_noise's rule is HELD when
+ * the resolve found it valid (resolved.w >= 0) and, in float32,  resolved.w > tau * fmaxf(luminance(mean), floor).  A held pixel is left out of its cell's sum
+ * and count, counted in cell_held, and -3 in the map; everything else is rt_estimate_noise to the letter, and a cell without a held pixel has its bits.
+ * *out_held_pixels (may be NULL): the total of cell_held.
+ * rt_estimate_noise_robust completes the work in flight, runs rt_resolve_fireflies with the cascade's support -- a resolve like any other: rt_read_resolved returns
+ * it, rt_set_denoise_source takes it as fresh -- and then the robust cells kernel. Errors as rt_estimate_noise, and RT_ERROR_NOT_READY while the cascade is off or
+ * when the resolve finds no valid pixel, RT_ERROR_INVALID_ARG for a tau outside (0, 1).
+ * rt_set_noise_robust: while held_fraction is in (0, 1), rt_select_active_cells selects from the robust cells (resolve included), with a second clause that
+ * counts held pixels as judged:  cell_counts[c] + cell_nonfinite[c] + cell_held[c] < its in-frame pixel count;  out and cell_flags keep their meaning. 0 switches
+ * it off. Refused (RT_ERROR_NOT_READY) while the cascade is off; switching the cascade off switches it off; rt_resize keeps it as it keeps the cascade.
+ * rt_estimate_noise itself never changes. (Additions that change no struct and no call: RT_ABI_VERSION stays.)                                          */
+int rt_estimate_noise_robust(rt_context * ctx, float floor, float held_fraction, rt_noise_estimate * out, double * cell_sums, int32_t * cell_counts,
+                             int32_t * cell_nonfinite, int32_t * cell_held, size_t cell_capacity, float * pixel_map, int64_t * out_held_pixels);
+int rt_set_noise_robust(rt_context * ctx, float held_fraction);   /* 0: off */
+float rt_get_noise_robust(const rt_context * ctx);
+
 /* Kulla-Conty LUTs as computed on the device at first use (kernel_integrate_* /
  * kernel_average_*, CUDA/KullaConty.h:83-240): 16^3, 16^3, 16^2, 16^2, 32^2, 32 floats.
  * Any pointer may be NULL. Synchronous.                                                     */
@@ -993,6 +1023,18 @@ int rt_accumulate_cascade_frames(rt_context * ctx, int merged, const int32_t * f
  * runs), 0: the plain kernel; the two agree bit for bit.                                                                                            */
 int rt_resolve_fireflies_images(rt_context * ctx, int width, int height, int pitch, const float * mean, const float * moments, const float * tiers, const float * fallback,
                                 const rt_firefly_params * params, int tiled, float * out);
+/* rt_measure_exposure's kernel on explicit images of a size of the caller's (synchronous; the context needs no frame, no scene and no estimate): mean and
+ * moments are pitch*height float4, pitch >= width, pitch * height below 2^26.                                                                          */
+int rt_measure_exposure_images(rt_context * ctx, int width, int height, int pitch, const float * mean, const float * moments, rt_exposure * out, uint64_t * histogram256);
+/* rt_estimate_noise_robust's cells kernel and the robust selection on explicit images of the context's frame size (synchronous): as rt_estimate_noise_images and
+ * rt_select_pixels_images, with `resolved` -- pitch*height float4 as rt_read_resolved gives them -- from the caller instead of a resolve, and cell_held beside
+ * the other cell arrays. Neither needs the estimate or the cascade.                                                                                     */
+int rt_estimate_noise_robust_images(rt_context * ctx, const float * mean, const float * moments, const float * resolved, float floor, float held_fraction,
+                                    rt_noise_estimate * out, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, int32_t * cell_held, size_t cell_capacity,
+                                    float * pixel_map, int64_t * out_held_pixels);
+int rt_select_pixels_robust_images(rt_context * ctx, const float * mean, const float * moments, const float * resolved, float floor, float held_fraction, float threshold,
+                                   int dilate, rt_cell_selection * out, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, int32_t * cell_held,
+                                   uint8_t * cell_flags, size_t cell_capacity, uint32_t * list, size_t list_capacity);
 /* ---- fog volume ---------------------------------------------------------------------------------------------------
  * One scene-wide homogeneous medium inside an axis-aligned box, with multiple scattering and light sampling at every scatter vertex. Off
  * until a volume is set; while it is off a context launches exactly the kernels it launched before these calls existed. (Additions that
