@@ -1105,7 +1105,7 @@ class Pathtracer:
         lib = host_lib()
         fn = getattr(lib, entry)
         fn.argtypes = [c_void_p] + [c_void_p] * 4 + [c_size_t] + [c_void_p] * 3
-        cells_x, cells_y = (self.width + 15) // 16, (self.height + 15) // 16
+        cells_x, cells_y = _noise_cells(self.width, self.height)
         n = cells_x * cells_y
         xy = np.zeros(2, np.int32)
         sums, counts, nonfinite = np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.int32)
@@ -1300,6 +1300,22 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _soa_pointers(origin, direction):
+    """The six component pointers {ox, oy, oz, dx, dy, dz} of two (3, N) SoA arrays."""
+    return [a[k].ctypes.data for a in (origin, direction) for k in range(3)]
+
+
+def _noise_cells(width, height):
+    """(cells_x, cells_y): the 16 x 16 pixel cells of the noise estimate that cover a frame."""
+    return (width + 15) // 16, (height + 15) // 16
+
+
+def _trace_statistics(raw10):
+    """The kernels' ten statistics words as {'closest': {...}, 'shadow': {...}} with nodes / triangles / instances_transformed / instances_identity / rays."""
+    names = ("nodes", "triangles", "instances_transformed", "instances_identity", "rays")
+    return {kind: {name: int(raw10[5 * j + i]) for i, name in enumerate(names)} for j, kind in enumerate(("closest", "shadow"))}
+
+
 class DeviceRefusal(RuntimeError):
     """A device-layer call that returned an error status (.status: the RT_ERROR_* value)."""
 
@@ -1327,26 +1343,37 @@ def read_noise_moments(ctx, height, pitch):
     return image
 
 
+def _estimate_noise(ctx, height, width, pitch, floor, held_fraction, images, want_map, cell_capacity):
+    """The one body of estimate_noise (held_fraction None) and estimate_noise_robust. images: the caller's (height, pitch, 4) float32 images -- mean, moments and,
+    robust, resolved -- or () for the context's frame."""
+    robust = held_fraction is not None
+    cells_x, cells_y = _noise_cells(width, height)
+    n = cells_x * cells_y
+    cells = {"cell_sums": np.zeros(n, np.float64), "cell_counts": np.zeros(n, np.int32), "cell_nonfinite": np.zeros(n, np.int32)}
+    if robust:
+        cells["cell_held"] = np.zeros(n, np.int32)
+    pixel_map = np.zeros((height, pitch), np.float32) if want_map else None
+    out, held_pixels = NoiseEstimateRecord(), ctypes.c_int64()
+    images = [_f32(image) for image in images]
+    assert all(image.shape == (height, pitch, 4) for image in images)
+    # (the robust entry points take held_fraction after floor, cell_held after cell_nonfinite and the held count last)
+    args = [image.ctypes.data for image in images] + [c_float(floor)] + ([c_float(held_fraction)] if robust else []) + [byref(out)] + [a.ctypes.data for a in cells.values()]
+    args += [n if cell_capacity is None else cell_capacity, pixel_map.ctypes.data if want_map else None] + ([byref(held_pixels)] if robust else [])
+    entry = "rt_estimate_noise" + ("_robust" if robust else "") + ("_images" if images else "")
+    status = getattr(device_lib(), entry)(ctx, *args)
+    if status:
+        raise DeviceRefusal(ctx, status)
+    result = {"cells_x": out.cells_x, "cells_y": out.cells_y, "pixels": out.pixels, "nonfinite_pixels": out.nonfinite_pixels, "mean": out.mean, "pixel_map": pixel_map}
+    result.update((name, a.reshape(cells_y, cells_x)) for name, a in cells.items())
+    if robust:
+        result["held_pixels"] = held_pixels.value
+    return result
+
+
 def estimate_noise(ctx, height, width, pitch, floor=1e-2, mean=None, moments=None, want_map=True, cell_capacity=None):
     """rt_estimate_noise on the context's accumulator and moments, or -- mean and moments given, (height, pitch, 4) float32 -- rt_estimate_noise_images on
     those. Returns a dict: cells_x, cells_y, pixels, nonfinite_pixels, mean, cell_sums / cell_counts / cell_nonfinite (cells_y, cells_x), pixel_map (height, pitch)."""
-    lib = device_lib()
-    cells_x, cells_y = (width + 15) // 16, (height + 15) // 16
-    n = cells_x * cells_y
-    sums, counts, nonfinite = np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.int32)
-    pixel_map = np.zeros((height, pitch), np.float32) if want_map else None
-    out = NoiseEstimateRecord()
-    tail = (c_float(floor), byref(out), sums.ctypes.data, counts.ctypes.data, nonfinite.ctypes.data, n if cell_capacity is None else cell_capacity, pixel_map.ctypes.data if want_map else None)
-    if mean is None:
-        status = lib.rt_estimate_noise(ctx, *tail)
-    else:
-        mean, moments = _f32(mean), _f32(moments)
-        assert mean.shape == (height, pitch, 4) and moments.shape == (height, pitch, 4)
-        status = lib.rt_estimate_noise_images(ctx, mean.ctypes.data, moments.ctypes.data, *tail)
-    if status:
-        raise DeviceRefusal(ctx, status)
-    return {"cells_x": out.cells_x, "cells_y": out.cells_y, "pixels": out.pixels, "nonfinite_pixels": out.nonfinite_pixels, "mean": out.mean,
-            "cell_sums": sums.reshape(cells_y, cells_x), "cell_counts": counts.reshape(cells_y, cells_x), "cell_nonfinite": nonfinite.reshape(cells_y, cells_x), "pixel_map": pixel_map}
+    return _estimate_noise(ctx, height, width, pitch, floor, None, () if mean is None else (mean, moments), want_map, cell_capacity)
 
 
 def denoise(ctx, **params):
@@ -1508,25 +1535,7 @@ def exposure_start(histogram, shift=0):
 def estimate_noise_robust(ctx, height, width, pitch, floor=1e-2, held_fraction=0.25, mean=None, moments=None, resolved=None, want_map=True, cell_capacity=None):
     """rt_estimate_noise_robust on the context's frame (after a resolve of its own), or -- mean, moments and resolved given, (height, pitch, 4) float32 --
     rt_estimate_noise_robust_images on those. The dict of estimate_noise plus cell_held (cells_y, cells_x) and held_pixels; a held pixel is -3 in pixel_map."""
-    lib = device_lib()
-    cells_x, cells_y = (width + 15) // 16, (height + 15) // 16
-    n = cells_x * cells_y
-    sums, counts, nonfinite, held = np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
-    pixel_map = np.zeros((height, pitch), np.float32) if want_map else None
-    out, held_pixels = NoiseEstimateRecord(), ctypes.c_int64()
-    tail = (c_float(floor), c_float(held_fraction), byref(out), sums.ctypes.data, counts.ctypes.data, nonfinite.ctypes.data, held.ctypes.data, n if cell_capacity is None else cell_capacity,
-            pixel_map.ctypes.data if want_map else None, byref(held_pixels))
-    if mean is None:
-        status = lib.rt_estimate_noise_robust(ctx, *tail)
-    else:
-        mean, moments, resolved = _f32(mean), _f32(moments), _f32(resolved)
-        assert mean.shape == moments.shape == resolved.shape == (height, pitch, 4)
-        status = lib.rt_estimate_noise_robust_images(ctx, mean.ctypes.data, moments.ctypes.data, resolved.ctypes.data, *tail)
-    if status:
-        raise DeviceRefusal(ctx, status)
-    return {"cells_x": out.cells_x, "cells_y": out.cells_y, "pixels": out.pixels, "nonfinite_pixels": out.nonfinite_pixels, "mean": out.mean, "held_pixels": held_pixels.value,
-            "cell_sums": sums.reshape(cells_y, cells_x), "cell_counts": counts.reshape(cells_y, cells_x), "cell_nonfinite": nonfinite.reshape(cells_y, cells_x),
-            "cell_held": held.reshape(cells_y, cells_x), "pixel_map": pixel_map}
+    return _estimate_noise(ctx, height, width, pitch, floor, held_fraction, () if mean is None else (mean, moments, resolved), want_map, cell_capacity)
 
 
 def estimate_noise_robust_images(ctx, height, width, pitch, mean, moments, resolved, **given):
@@ -1547,21 +1556,7 @@ def get_noise_robust(ctx):
 
 def select_pixels_robust_images(ctx, height, width, pitch, mean, moments, resolved, threshold, floor=1e-2, held_fraction=0.25, dilate=1, sentinel=0xffffffff):
     """rt_select_pixels_robust_images: select_pixels_images from the robust cells of the caller's images; the dict gains cell_held (cells_y, cells_x)."""
-    mean, moments, resolved = _f32(mean), _f32(moments), _f32(resolved)
-    assert mean.shape == moments.shape == resolved.shape == (height, pitch, 4)
-    cells_x, cells_y = (width + 15) // 16, (height + 15) // 16
-    n = cells_x * cells_y
-    sums, counts, nonfinite, held, flags = np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint8)
-    pixels = np.full(width * height, sentinel, np.uint32)
-    out = CellSelectionRecord()
-    status = device_lib().rt_select_pixels_robust_images(ctx, mean.ctypes.data, moments.ctypes.data, resolved.ctypes.data, c_float(floor), c_float(held_fraction), c_float(threshold), int(dilate),
-                                                         byref(out), sums.ctypes.data, counts.ctypes.data, nonfinite.ctypes.data, held.ctypes.data, flags.ctypes.data, n, pixels.ctypes.data, pixels.size)
-    if status:
-        raise DeviceRefusal(ctx, status)
-    result = _selection(out, flags)
-    result.update(cell_sums=sums.reshape(cells_y, cells_x), cell_counts=counts.reshape(cells_y, cells_x), cell_nonfinite=nonfinite.reshape(cells_y, cells_x),
-                  cell_held=held.reshape(cells_y, cells_x), list=pixels[:out.list_pixels].copy(), list_tail=pixels[out.list_pixels:].copy())
-    return result
+    return _select_pixels_images(ctx, height, width, pitch, (mean, moments, resolved), threshold, floor, held_fraction, dilate, sentinel)
 
 
 def _accumulate_staging(frames, images, first_sample, sample_count, merged):
@@ -1613,7 +1608,8 @@ def _selection(out, flags):
 def select_active_cells(ctx, height, width, threshold, floor=1e-2, dilate=1, cell_capacity=None):
     """rt_select_active_cells on the context's accumulator and moments; the list stays with the context. Returns a dict: cells_x, cells_y,
     hot_cells, active_cells, list_pixels, hot / active (cells_y, cells_x) bool."""
-    n = ((width + 15) // 16) * ((height + 15) // 16)
+    cells_x, cells_y = _noise_cells(width, height)
+    n = cells_x * cells_y
     flags = np.zeros(n, np.uint8)
     out = CellSelectionRecord()
     status = device_lib().rt_select_active_cells(ctx, c_float(floor), c_float(threshold), int(dilate), byref(out), flags.ctypes.data, n if cell_capacity is None else cell_capacity)
@@ -1646,24 +1642,34 @@ def read_pixel_list(ctx):
     return pixels
 
 
-def select_pixels_images(ctx, height, width, pitch, mean, moments, threshold, floor=1e-2, dilate=1, sentinel=0xffffffff):
-    """rt_select_pixels_images: selection and compaction on the caller's (height, pitch, 4) float32 images. Returns the dict of select_active_cells plus cell_sums /
-    cell_counts / cell_nonfinite (cells_y, cells_x), list (the list_pixels entries) and list_tail (the rest of the width * height entries: still `sentinel`)."""
-    mean, moments = _f32(mean), _f32(moments)
-    assert mean.shape == (height, pitch, 4) and moments.shape == (height, pitch, 4)
-    cells_x, cells_y = (width + 15) // 16, (height + 15) // 16
+def _select_pixels_images(ctx, height, width, pitch, images, threshold, floor, held_fraction, dilate, sentinel):
+    """The one body of select_pixels_images (images: mean and moments; held_fraction None) and select_pixels_robust_images (mean, moments and resolved)."""
+    robust = held_fraction is not None
+    images = [_f32(image) for image in images]
+    assert all(image.shape == (height, pitch, 4) for image in images)
+    cells_x, cells_y = _noise_cells(width, height)
     n = cells_x * cells_y
-    sums, counts, nonfinite, flags = np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint8)
+    cells = {"cell_sums": np.zeros(n, np.float64), "cell_counts": np.zeros(n, np.int32), "cell_nonfinite": np.zeros(n, np.int32)}
+    if robust:
+        cells["cell_held"] = np.zeros(n, np.int32)
+    flags = np.zeros(n, np.uint8)
     pixels = np.full(width * height, sentinel, np.uint32)
     out = CellSelectionRecord()
-    status = device_lib().rt_select_pixels_images(ctx, mean.ctypes.data, moments.ctypes.data, c_float(floor), c_float(threshold), int(dilate), byref(out), sums.ctypes.data,
-                                                  counts.ctypes.data, nonfinite.ctypes.data, flags.ctypes.data, n, pixels.ctypes.data, pixels.size)
+    args = [image.ctypes.data for image in images] + [c_float(floor)] + ([c_float(held_fraction)] if robust else []) + [c_float(threshold), int(dilate), byref(out)]
+    args += [a.ctypes.data for a in cells.values()] + [flags.ctypes.data, n, pixels.ctypes.data, pixels.size]
+    status = getattr(device_lib(), "rt_select_pixels_robust_images" if robust else "rt_select_pixels_images")(ctx, *args)
     if status:
         raise DeviceRefusal(ctx, status)
     result = _selection(out, flags)
-    result.update(cell_sums=sums.reshape(cells_y, cells_x), cell_counts=counts.reshape(cells_y, cells_x), cell_nonfinite=nonfinite.reshape(cells_y, cells_x),
-                  list=pixels[:out.list_pixels].copy(), list_tail=pixels[out.list_pixels:].copy())
+    result.update((name, a.reshape(cells_y, cells_x)) for name, a in cells.items())
+    result.update(list=pixels[:out.list_pixels].copy(), list_tail=pixels[out.list_pixels:].copy())
     return result
+
+
+def select_pixels_images(ctx, height, width, pitch, mean, moments, threshold, floor=1e-2, dilate=1, sentinel=0xffffffff):
+    """rt_select_pixels_images: selection and compaction on the caller's (height, pitch, 4) float32 images. Returns the dict of select_active_cells plus cell_sums /
+    cell_counts / cell_nonfinite (cells_y, cells_x), list (the list_pixels entries) and list_tail (the rest of the width * height entries: still `sentinel`)."""
+    return _select_pixels_images(ctx, height, width, pitch, (mean, moments), threshold, floor, None, dilate, sentinel)
 
 
 def accumulate_list_frames(ctx, frames, accumulator, moments, pixels, sample_count, first_sample=None, sentinel=0x7fc0dead):
@@ -1697,7 +1703,7 @@ def trace_rays(ctx, origin, direction, repeat=1):
     n = o.shape[1]
     hits = np.zeros((n, 4), np.uint32)
     ms = c_float()
-    _dev_check(ctx, device_lib().rt_trace_rays(ctx, o[0].ctypes.data, o[1].ctypes.data, o[2].ctypes.data, d[0].ctypes.data, d[1].ctypes.data, d[2].ctypes.data, n, hits.ctypes.data, repeat, byref(ms)))
+    _dev_check(ctx, device_lib().rt_trace_rays(ctx, *_soa_pointers(o, d), n, hits.ctypes.data, repeat, byref(ms)))
     return hits, ms.value
 
 
@@ -1706,7 +1712,7 @@ def trace_shadow_rays(ctx, origin, direction, max_distance, repeat=1):
     n = o.shape[1]
     occluded = np.zeros(n, np.uint8)
     ms = c_float()
-    _dev_check(ctx, device_lib().rt_trace_shadow_rays(ctx, o[0].ctypes.data, o[1].ctypes.data, o[2].ctypes.data, d[0].ctypes.data, d[1].ctypes.data, d[2].ctypes.data, m.ctypes.data, n, occluded.ctypes.data, repeat, byref(ms)))
+    _dev_check(ctx, device_lib().rt_trace_shadow_rays(ctx, *_soa_pointers(o, d), m.ctypes.data, n, occluded.ctypes.data, repeat, byref(ms)))
     return occluded, ms.value
 
 
@@ -1723,13 +1729,9 @@ def trace_stream_rays(ctx, iteration, origin, direction, hits, shadow_origin, sh
     light = np.zeros(k, np.float32)
     stats = np.zeros(10, np.uint64) if counting else None
     info = np.zeros(4, np.int32)
-    _dev_check(ctx, device_lib().rt_trace_stream_rays(ctx, iteration, o[0].ctypes.data, o[1].ctypes.data, o[2].ctypes.data, d[0].ctypes.data, d[1].ctypes.data, d[2].ctypes.data, n, out.ctypes.data,
-                                                      so[0].ctypes.data, so[1].ctypes.data, so[2].ctypes.data, sd[0].ctypes.data, sd[1].ctypes.data, sd[2].ctypes.data, m.ctypes.data, k, light.ctypes.data,
+    _dev_check(ctx, device_lib().rt_trace_stream_rays(ctx, iteration, *_soa_pointers(o, d), n, out.ctypes.data, *_soa_pointers(so, sd), m.ctypes.data, k, light.ctypes.data,
                                                       stats.ctypes.data if counting else None, info.ctypes.data))
-    if counting:
-        names = ("nodes", "triangles", "instances_transformed", "instances_identity", "rays")
-        stats = {kind: {name: int(stats[5 * j + i]) for i, name in enumerate(names)} for j, kind in enumerate(("closest", "shadow"))}
-    return out, light, stats, info
+    return out, light, _trace_statistics(stats) if counting else None, info
 
 
 TRACE_QUEUE_PLAIN, TRACE_QUEUE_COUNTING, TRACE_QUEUE_AO = 0, 1, 2   # RT_TRACE_QUEUE_*: the forms of rt_trace_queue_rays
@@ -1757,22 +1759,17 @@ def trace_queue_rays(ctx, step, origin, direction, hits, shadow_origin, shadow_d
     counting = form == TRACE_QUEUE_COUNTING
     stats = np.zeros(10, np.uint64) if counting else None
     info = np.zeros(6, np.int32)
-    _dev_check(ctx, device_lib().rt_trace_queue_rays(ctx, 1 if merged else 0, step, form,
-                                                     o[0].ctypes.data, o[1].ctypes.data, o[2].ctypes.data, d[0].ctypes.data, d[1].ctypes.data, d[2].ctypes.data, n, out.ctypes.data,
-                                                     so[0].ctypes.data, so[1].ctypes.data, so[2].ctypes.data, sd[0].ctypes.data, sd[1].ctypes.data, sd[2].ctypes.data, m.ctypes.data,
+    _dev_check(ctx, device_lib().rt_trace_queue_rays(ctx, 1 if merged else 0, step, form, *_soa_pointers(o, d), n, out.ctypes.data, *_soa_pointers(so, sd), m.ctypes.data,
                                                      light.ctypes.data, words.ctypes.data, k, *[None if f is None else f.ctypes.data for f in after], frame_pixels,
                                                      stats.ctypes.data if counting else None, info.ctypes.data))
-    if counting:
-        names = ("nodes", "triangles", "instances_transformed", "instances_identity", "rays")
-        stats = {kind: {name: int(stats[5 * j + i]) for i, name in enumerate(names)} for j, kind in enumerate(("closest", "shadow"))}
-    return out, after, stats, info
+    return out, after, _trace_statistics(stats) if counting else None, info
 
 
 def generate_rays(ctx, sample_index, pixel_offset, pixel_count):
     o = np.zeros((3, pixel_count), np.float32)
     d = np.zeros((3, pixel_count), np.float32)
     px = np.zeros(pixel_count, np.uint32)
-    _dev_check(ctx, device_lib().rt_generate_rays(ctx, sample_index, pixel_offset, pixel_count, o[0].ctypes.data, o[1].ctypes.data, o[2].ctypes.data, d[0].ctypes.data, d[1].ctypes.data, d[2].ctypes.data, px.ctypes.data))
+    _dev_check(ctx, device_lib().rt_generate_rays(ctx, sample_index, pixel_offset, pixel_count, *_soa_pointers(o, d), px.ctypes.data))
     return o, d, px
 
 
@@ -1872,6 +1869,25 @@ SORT_TRACE_WORDS, SORT_MATERIAL_WORDS = 20, 16   # RT_SORT_TRACE_WORDS, RT_SORT_
 STREAM_SUBMISSIONS, STAT_KINDS, MAX_BOUNCES = 128, 6, 128
 
 
+def _queue_launch_staging(r, records_in, words, frame_pixels, frame_slots, bounce, sample_index, iteration, slot_table, submission_birth, capacity, sentinel, material_slot=None):
+    """What sort_rays and shade_rays stage alike: the entries as (N, words) uint32, the merged form's slot table and births, the capacity, and on the result `r`
+    trace_out (capacity, 20) and stats. Returns (r, the arguments of the entry point from `merged` to `sentinel`, pixels in the frames); r._staged keeps the staged
+    arrays alive for the call."""
+    records = np.ascontiguousarray(records_in, np.uint32).reshape(-1, words)
+    n = records.shape[0]
+    merged = iteration is not None
+    capacity = max(n, 1) if capacity is None else int(capacity)
+    r.trace_out = np.zeros((capacity, SORT_TRACE_WORDS), np.uint32)
+    r.stats = np.zeros((STREAM_SUBMISSIONS, STAT_KINDS, MAX_BOUNCES), np.int32) if merged else None
+    slots = np.ascontiguousarray(slot_table, np.int32).reshape(-1, 4) if merged else None
+    births = np.ascontiguousarray(submission_birth, np.int32).reshape(STREAM_SUBMISSIONS) if merged else None
+    r._staged = (records, slots, births)
+    head = [1 if merged else 0, int(iteration if merged else bounce), int(sample_index)] + ([] if material_slot is None else [int(material_slot)])
+    head += [records.ctypes.data if n else None, n, slots.ctypes.data if merged else None, slots.shape[0] if merged else 0, births.ctypes.data if merged else None,
+             capacity, int(frame_slots), int(sentinel)]
+    return r, head, int(frame_pixels) * int(frame_slots)
+
+
 class SortResult:
     """What one sort launch left behind (rt_sort_rays): trace_out (capacity, 20) and material_out (4, capacity, 16) uint32 records read
     back to their capacity, counters int32[6] {diffuse, plastic, dielectric, conductor, next trace, this trace}, aov (4, P, 4) float32
@@ -1884,13 +1900,8 @@ def sort_rays(ctx, trace_in, frame_pixels, frame_slots, bounce=None, sample_inde
     """rt_sort_rays: the production sort launch on explicit entries. trace_in: (N, 20) uint32 records. Per-bounce form: bounce and
     sample_index; merged form: iteration, slot_table (S, 4) int32 and submission_birth int32[128]. The frames hold frame_slots *
     frame_pixels pixels; aov / g-buffers / pixel_query are their contents before the launch (zeros / the sentinel when None)."""
-    t = np.ascontiguousarray(trace_in, np.uint32).reshape(-1, SORT_TRACE_WORDS)
-    n = t.shape[0]
-    merged = iteration is not None
-    capacity = max(n, 1) if capacity is None else int(capacity)
-    pixels = int(frame_pixels) * int(frame_slots)
-    r = SortResult()
-    r.trace_out = np.zeros((capacity, SORT_TRACE_WORDS), np.uint32)
+    r, head, pixels = _queue_launch_staging(SortResult(), trace_in, SORT_TRACE_WORDS, frame_pixels, frame_slots, bounce, sample_index, iteration, slot_table, submission_birth, capacity, sentinel)
+    capacity, merged = r.trace_out.shape[0], iteration is not None
     r.material_out = np.zeros((4, capacity, SORT_MATERIAL_WORDS), np.uint32)
     r.counters = np.zeros(6, np.int32)
     r.aov = np.zeros((4, pixels, 4), np.float32) if aov is None else np.array(aov, np.float32, order="C", copy=True).reshape(4, pixels, 4)
@@ -1898,13 +1909,7 @@ def sort_rays(ctx, trace_in, frame_pixels, frame_slots, bounce=None, sample_inde
     r.gbuffer_ids = np.zeros((pixels, 2), np.int32) if gbuffer_ids is None else np.array(gbuffer_ids, np.int32, order="C", copy=True).reshape(pixels, 2)
     r.gbuffer_screen_prev = np.zeros((pixels, 2), np.float32) if gbuffer_screen_prev is None else np.array(gbuffer_screen_prev, np.float32, order="C", copy=True).reshape(pixels, 2)
     r.pixel_query = np.full(2, sentinel, np.uint32).view(np.int32) if pixel_query is None else np.array(pixel_query, np.int32, copy=True).reshape(2)
-    r.stats = np.zeros((STREAM_SUBMISSIONS, STAT_KINDS, MAX_BOUNCES), np.int32) if merged else None
-    if merged:
-        slots = np.ascontiguousarray(slot_table, np.int32).reshape(-1, 4)
-        births = np.ascontiguousarray(submission_birth, np.int32).reshape(STREAM_SUBMISSIONS)
-    args = (ctx, 1 if merged else 0, int(iteration if merged else bounce), int(sample_index), t.ctypes.data if n else None, n,
-            slots.ctypes.data if merged else None, slots.shape[0] if merged else 0, births.ctypes.data if merged else None,
-            capacity, int(frame_slots), int(sentinel), r.trace_out.ctypes.data, r.material_out.ctypes.data, r.counters.ctypes.data,
+    args = (ctx, *head, r.trace_out.ctypes.data, r.material_out.ctypes.data, r.counters.ctypes.data,
             r.aov.ctypes.data, r.gbuffer_normal_and_depth.ctypes.data, r.gbuffer_ids.ctypes.data, r.gbuffer_screen_prev.ctypes.data,
             r.pixel_query.ctypes.data, r.stats.ctypes.data if merged else None)
     if _fog:
@@ -1937,26 +1942,16 @@ def shade_rays(ctx, material_slot, material_in, frame_pixels, frame_slots, bounc
     """rt_shade_rays: the production material launch of queue `material_slot` on explicit entries. material_in: (N, 16) uint32 records, one
     of the queues of SortResult.material_out. Per-bounce form: bounce and sample_index; merged form: iteration, slot_table (S, 4) int32 and
     submission_birth int32[128]. The frames hold frame_slots * frame_pixels pixels."""
-    m = np.ascontiguousarray(material_in, np.uint32).reshape(-1, SORT_MATERIAL_WORDS)
-    n = m.shape[0]
-    merged = iteration is not None
-    capacity = max(n, 1) if capacity is None else int(capacity)
-    pixels = int(frame_pixels) * int(frame_slots)
-    r = ShadeResult()
-    r.trace_out = np.zeros((capacity, SORT_TRACE_WORDS), np.uint32)
+    r, head, pixels = _queue_launch_staging(ShadeResult(), material_in, SORT_MATERIAL_WORDS, frame_pixels, frame_slots, bounce, sample_index, iteration, slot_table, submission_birth, capacity, sentinel,
+                                            material_slot)
+    capacity, merged = r.trace_out.shape[0], iteration is not None
     r.shadow_out = np.zeros((capacity, SHADE_SHADOW_WORDS), np.uint32)
     r.counters = np.zeros(3, np.int32)
     r.aov = np.zeros((3, pixels, 4), np.uint32)
     r.gbuffer_normal_and_depth = np.zeros((pixels, 4), np.uint32)
     r.gbuffer_ids = np.zeros((pixels, 2), np.uint32)
     r.gbuffer_screen_prev = np.zeros((pixels, 2), np.uint32)
-    r.stats = np.zeros((STREAM_SUBMISSIONS, STAT_KINDS, MAX_BOUNCES), np.int32) if merged else None
-    if merged:
-        slots = np.ascontiguousarray(slot_table, np.int32).reshape(-1, 4)
-        births = np.ascontiguousarray(submission_birth, np.int32).reshape(STREAM_SUBMISSIONS)
-    _dev_check(ctx, device_lib().rt_shade_rays(ctx, 1 if merged else 0, int(iteration if merged else bounce), int(sample_index), int(material_slot), m.ctypes.data if n else None, n,
-                                               slots.ctypes.data if merged else None, slots.shape[0] if merged else 0, births.ctypes.data if merged else None,
-                                               capacity, int(frame_slots), int(sentinel), r.trace_out.ctypes.data, r.shadow_out.ctypes.data, r.counters.ctypes.data,
+    _dev_check(ctx, device_lib().rt_shade_rays(ctx, *head, r.trace_out.ctypes.data, r.shadow_out.ctypes.data, r.counters.ctypes.data,
                                                r.aov.ctypes.data, r.gbuffer_normal_and_depth.ctypes.data, r.gbuffer_ids.ctypes.data, r.gbuffer_screen_prev.ctypes.data,
                                                r.stats.ctypes.data if merged else None))
     return r
@@ -2258,12 +2253,10 @@ def get_trace_statistics(ctx):
     lib.rt_get_trace_statistics.argtypes = [c_void_p, c_void_p]
     raw = np.zeros(10, np.uint64)
     _dev_check(ctx, lib.rt_get_trace_statistics(ctx, raw.ctypes.data))
-    out = {}
-    for k, name in enumerate(("closest", "shadow")):
-        nodes, tris, ix, ii, rays = [int(v) for v in raw[5 * k:5 * k + 5]]
-        per_ray = 24 + (16 if k == 0 else 4)
-        out[name] = dict(nodes=nodes, triangles=tris, instances_transformed=ix, instances_identity=ii, rays=rays,
-                         algorithmic_bytes=per_ray * rays + 80 * nodes + 48 * tris + 52 * ix + 4 * ii)
+    out = _trace_statistics(raw)
+    for kind, hit_bytes in (("closest", 16), ("shadow", 4)):
+        c = out[kind]
+        c["algorithmic_bytes"] = (24 + hit_bytes) * c["rays"] + 80 * c["nodes"] + 48 * c["triangles"] + 52 * c["instances_transformed"] + 4 * c["instances_identity"]
     return out
 
 

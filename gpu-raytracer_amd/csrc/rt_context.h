@@ -5,6 +5,7 @@
 #pragma once
 #include "rt_types.h"
 
+#include <cstddef>
 #include <deque>
 #include <string>
 #include <vector>
@@ -350,3 +351,48 @@ enum { STAGE_GENERATE = 0, STAGE_TRACE, STAGE_SORT, STAGE_SHADE, STAGE_SHADOW, S
 // what a [begin, end] event pair of rt_set_profiling(ctx, 2 / 3) brackets (the `kind` of rt_get_launch_timings)
 enum { SPAN_TRACE = RT_TIMING_TRACE, SPAN_SHADOW = RT_TIMING_SHADOW, SPAN_SORT = RT_TIMING_SORT, SPAN_GENERATE = RT_TIMING_GENERATE, SPAN_ACCUMULATE = RT_TIMING_ACCUMULATE,
        SPAN_MATERIAL = RT_TIMING_MATERIAL_0, SPAN_SVGF = RT_TIMING_SVGF_REPROJECT };
+
+// The queue records of the launch probes (include/gpu_raytracer_amd.h: RT_SORT_TRACE_WORDS, RT_SORT_MATERIAL_WORDS, RT_SHADE_SHADOW_WORDS), described ONCE: which
+// array of the queue -- the pointer `member` bytes into the buffer struct -- holds words [word, word + words) of an entry's record. Host side only; the probes'
+// staging and read-back (rt_probes.hip: Probe::queue, Probe::queue_back) and their entry checks go by these tables, so a new queue member is one line here.
+struct RecordField { size_t member; int word, words; };
+#define RT_RECORD_FIELD(B, m, word, words) { offsetof(B, m), word, words }
+#define RT_RECORD_VEC3(B, m, word) RT_RECORD_FIELD(B, m.x, word, 1), RT_RECORD_FIELD(B, m.y, (word) + 1, 1), RT_RECORD_FIELD(B, m.z, (word) + 2, 1)
+template<typename B> struct RecordLayout;
+template<> struct RecordLayout<RtTraceBuffer> {   // words 18 and 19 are padding
+	static constexpr int words = RT_SORT_TRACE_WORDS;
+	static constexpr RecordField fields[] = { RT_RECORD_VEC3(RtTraceBuffer, origin, 0), RT_RECORD_VEC3(RtTraceBuffer, direction, 3), RT_RECORD_FIELD(RtTraceBuffer, hits, 6, 4),
+		RT_RECORD_FIELD(RtTraceBuffer, pixel_index_and_flags, 10, 1), RT_RECORD_VEC3(RtTraceBuffer, throughput, 11), RT_RECORD_FIELD(RtTraceBuffer, last_pdf, 14, 1),
+		RT_RECORD_FIELD(RtTraceBuffer, medium, 15, 1), RT_RECORD_FIELD(RtTraceBuffer, cone_angle, 16, 1), RT_RECORD_FIELD(RtTraceBuffer, cone_width, 17, 1) };
+};
+template<> struct RecordLayout<RtMaterialBuffer> {   // words 14 and 15 are padding
+	static constexpr int words = RT_SORT_MATERIAL_WORDS;
+	static constexpr RecordField fields[] = { RT_RECORD_VEC3(RtMaterialBuffer, direction, 0), RT_RECORD_FIELD(RtMaterialBuffer, hits, 3, 4), RT_RECORD_FIELD(RtMaterialBuffer, pixel_index_and_flags, 7, 1),
+		RT_RECORD_VEC3(RtMaterialBuffer, throughput, 8), RT_RECORD_FIELD(RtMaterialBuffer, medium, 11, 1), RT_RECORD_FIELD(RtMaterialBuffer, cone_angle, 12, 1),
+		RT_RECORD_FIELD(RtMaterialBuffer, cone_width, 13, 1) };
+};
+template<> struct RecordLayout<RtShadowBuffer> {
+	static constexpr int words = RT_SHADE_SHADOW_WORDS;
+	static constexpr RecordField fields[] = { RT_RECORD_VEC3(RtShadowBuffer, origin, 0), RT_RECORD_VEC3(RtShadowBuffer, direction, 3), RT_RECORD_FIELD(RtShadowBuffer, max_distance, 6, 1),
+		RT_RECORD_FIELD(RtShadowBuffer, illumination_and_pixel_index, 7, 4) };
+};
+// the first word of the array `member` (an offsetof into B) in B's record
+template<typename B> constexpr int record_word(size_t member) {
+	for (const RecordField & f : RecordLayout<B>::fields) if (f.member == member) return f.word;
+	return -1;
+}
+// every array of the buffer is described exactly once, inside the record, and no word belongs to two arrays
+template<typename B> constexpr bool record_layout_sound() {
+	unsigned long long words = 0, members = 0; size_t count = 0;
+	for (const RecordField & f : RecordLayout<B>::fields) {
+		const unsigned long long member = 1ull << (f.member / sizeof(void *));
+		if (f.member % sizeof(void *) || f.member >= sizeof(B) || (members & member) || f.words < 1) return false;
+		members |= member; count++;
+		for (int w = f.word; w < f.word + f.words; w++) {
+			if (w < 0 || w >= RecordLayout<B>::words || (words >> w & 1)) return false;
+			words |= 1ull << w;
+		}
+	}
+	return count * sizeof(void *) == sizeof(B);
+}
+static_assert(record_layout_sound<RtTraceBuffer>() && record_layout_sound<RtMaterialBuffer>() && record_layout_sound<RtShadowBuffer>(), "a queue record's table does not match its buffer");

@@ -157,15 +157,25 @@ int rt_read_noise_moments(rt_context * ctx, float * dst) {
 	return RT_OK;
 }
 
+// rt_estimate_noise and rt_estimate_noise_robust after their NULL checks. robust: null, or the robust form's held_fraction, cell_held and held count; its image
+// is the context's, after a resolve of its own (which drains the context, and refuses while the cascade is off).
+static int estimate_noise_frame(rt_context * ctx, const char * name, float floor, rt_noise_estimate * out, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite,
+                                size_t cell_capacity, float * pixel_map, NoiseRobust * robust) {
+	if (!(floor > 0.0f && floor < __builtin_huge_valf())) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: floor must be finite and positive", name);
+	int s = robust ? held_fraction_argument(ctx, name, robust->held_fraction) : RT_OK; if (s) return s;
+	(void)hipSetDevice(ctx->device);
+	if (!ctx->noise_moments || !ctx->aov_buffers[RT_AOV_RADIANCE][1]) return fail(ctx, RT_ERROR_NOT_READY, "%s: the noise estimate is off (rt_set_noise_estimate) or rt_resize was not called", name);
+	if (!robust) RT_HIP(ctx, quiesce(ctx));
+	else if ((s = firefly_resolve_frame(ctx, name, ctx->firefly.support, true, nullptr))) return s;
+	else robust->resolved = (const float4 *)ctx->firefly_resolved;
+	return noise_estimate_images(ctx, name, (const float4 *)ctx->aov_buffers[RT_AOV_RADIANCE][1], (const float4 *)ctx->noise_moments, floor, out, cell_sums, cell_counts, cell_nonfinite,
+	                             cell_capacity, pixel_map, robust);
+}
+
 int rt_estimate_noise(rt_context * ctx, float floor, rt_noise_estimate * out, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, size_t cell_capacity, float * pixel_map) {
 	RT_REQUIRE(ctx, ctx, "rt_estimate_noise: NULL context");
 	RT_REQUIRE(ctx, out && cell_sums && cell_counts && cell_nonfinite, "rt_estimate_noise: NULL argument");
-	RT_REQUIRE(ctx, floor > 0.0f && floor < __builtin_huge_valf(), "rt_estimate_noise: floor must be finite and positive");
-	(void)hipSetDevice(ctx->device);
-	if (!ctx->noise_moments || !ctx->aov_buffers[RT_AOV_RADIANCE][1]) return fail(ctx, RT_ERROR_NOT_READY, "rt_estimate_noise: the noise estimate is off (rt_set_noise_estimate) or rt_resize was not called");
-	RT_HIP(ctx, quiesce(ctx));
-	return noise_estimate_images(ctx, "rt_estimate_noise", (const float4 *)ctx->aov_buffers[RT_AOV_RADIANCE][1], (const float4 *)ctx->noise_moments, floor, out,
-	                             cell_sums, cell_counts, cell_nonfinite, cell_capacity, pixel_map);
+	return estimate_noise_frame(ctx, "rt_estimate_noise", floor, out, cell_sums, cell_counts, cell_nonfinite, cell_capacity, pixel_map, nullptr);
 }
 
 // ---- firefly-robust estimate -----------------------------------------------------------------------
@@ -174,14 +184,8 @@ int rt_estimate_noise_robust(rt_context * ctx, float floor, float held_fraction,
                              int32_t * cell_held, size_t cell_capacity, float * pixel_map, int64_t * out_held_pixels) {
 	RT_REQUIRE(ctx, ctx, "rt_estimate_noise_robust: NULL context");
 	RT_REQUIRE(ctx, out && cell_sums && cell_counts && cell_nonfinite && cell_held, "rt_estimate_noise_robust: NULL argument");
-	RT_REQUIRE(ctx, floor > 0.0f && floor < __builtin_huge_valf(), "rt_estimate_noise_robust: floor must be finite and positive");
-	int s = held_fraction_argument(ctx, "rt_estimate_noise_robust", held_fraction); if (s) return s;
-	(void)hipSetDevice(ctx->device);
-	if (!ctx->noise_moments || !ctx->aov_buffers[RT_AOV_RADIANCE][1]) return fail(ctx, RT_ERROR_NOT_READY, "rt_estimate_noise_robust: the noise estimate is off (rt_set_noise_estimate) or rt_resize was not called");
-	if ((s = firefly_resolve_frame(ctx, "rt_estimate_noise_robust", ctx->firefly.support, true, nullptr))) return s;   // (drains the context; refuses while the cascade is off)
-	const NoiseRobust robust = { (const float4 *)ctx->firefly_resolved, held_fraction, cell_held, out_held_pixels };
-	return noise_estimate_images(ctx, "rt_estimate_noise_robust", (const float4 *)ctx->aov_buffers[RT_AOV_RADIANCE][1], (const float4 *)ctx->noise_moments, floor, out,
-	                             cell_sums, cell_counts, cell_nonfinite, cell_capacity, pixel_map, &robust);
+	NoiseRobust robust = { nullptr, held_fraction, cell_held, out_held_pixels };
+	return estimate_noise_frame(ctx, "rt_estimate_noise_robust", floor, out, cell_sums, cell_counts, cell_nonfinite, cell_capacity, pixel_map, &robust);
 }
 
 int rt_set_noise_robust(rt_context * ctx, float held_fraction) {

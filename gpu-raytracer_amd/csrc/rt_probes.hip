@@ -1,5 +1,7 @@
 // rt_probes.hip -- the kernel-level entry points of include/gpu_raytracer_amd.h ("probes"): one kernel, or one launch of a frame, on explicit
-// arguments, for the tests and for bench.py. All are synchronous.
+// arguments, for the tests and for bench.py. All are synchronous. In order: the scaffold every probe stands on (Probe, with the codec of the queue
+// records rt_context.h describes; PixelsOnce), the trace and generate probes, the one-array-in, one-array-out probes, the sort, fog and material launch
+// probes on their shared front and back (QueueLaunch, LaunchCounters, LaunchFrames), and the image probes (accumulate, noise, selection, denoise, fireflies).
 #include "rt_context.h"
 
 #include <algorithm>
@@ -35,23 +37,35 @@ struct Probe {
 	}
 	int read(void * dst, const void * src, size_t bytes) { RT_HIP(ctx, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); return RT_OK; }
 	int finish_and_read(void * dst, const void * src, size_t bytes) { int s = finish(); return s ? s : read(dst, src, bytes); }   // (main stream, one result)
-	// One component array of a queue of `capacity` entries (the launch probes): word `word` (`words` of them, consecutive) of `n` records of `stride`
-	// 32-bit words; the rest of the array holds `sentinel`. records == nullptr: an output array, all sentinel.
-	void * column(const uint32_t * records, size_t n, size_t stride, size_t word, size_t words, size_t capacity, uint32_t sentinel) {
-		staging.assign(std::max(capacity, size_t(1)) * words, sentinel);
-		for (size_t i = 0; i < n; i++) for (size_t w = 0; w < words; w++) staging[i * words + w] = records[i * stride + word + w];
-		return array<uint32_t>(capacity * words, staging.data());
+	// `count` 32-bit words: a copy of the caller's `src`, or (src == nullptr) all `sentinel`
+	void * words(size_t count, const void * src, uint32_t sentinel) {
+		if (!src) staging.assign(count, sentinel);
+		return array<uint32_t>(count, src ? src : staging.data());
 	}
-	RtVec3SoA column3(const uint32_t * records, size_t n, size_t stride, size_t word, size_t capacity, uint32_t sentinel) {
-		RtVec3SoA v; v.x = (float *)column(records, n, stride, word, 1, capacity, sentinel); v.y = (float *)column(records, n, stride, word + 1, 1, capacity, sentinel);
-		v.z = (float *)column(records, n, stride, word + 2, 1, capacity, sentinel);
-		return v;
+	// A queue of `capacity` entries (the launch probes; B: RtTraceBuffer, RtMaterialBuffer or RtShadowBuffer, its record in rt_context.h's RecordLayout<B>) from `n`
+	// records; every word of the arrays beyond them holds `sentinel` ...
+	template<typename B> B queue(const uint32_t * records, size_t n, size_t capacity, uint32_t sentinel) {
+		B b = { };
+		for (const RecordField & f : RecordLayout<B>::fields) {
+			staging.assign(std::max(capacity, size_t(1)) * f.words, sentinel);
+			for (size_t i = 0; i < n; i++) for (int w = 0; w < f.words; w++) staging[i * f.words + w] = records[i * RecordLayout<B>::words + f.word + w];
+			void * p = array<uint32_t>(capacity * f.words, staging.data());
+			memcpy((char *)&b + f.member, &p, sizeof p);
+		}
+		return b;
 	}
-	// ... and back: the whole array into word `word` of `capacity` records
-	bool column_back(const void * device, uint32_t * records, size_t stride, size_t word, size_t words, size_t capacity) {
-		staging.resize(std::max(capacity, size_t(1)) * words);
-		if (read(staging.data(), device, capacity * words * 4)) return false;
-		for (size_t i = 0; i < capacity; i++) for (size_t w = 0; w < words; w++) records[i * stride + word + w] = staging[i * words + w];
+	// ... an output queue, all sentinel ...
+	template<typename B> B queue(size_t capacity, uint32_t sentinel) { return queue<B>(nullptr, 0, capacity, sentinel); }
+	// ... and back: the whole arrays into `capacity` records, whose padding words get `sentinel`
+	template<typename B> bool queue_back(const B & b, uint32_t * records, size_t capacity, uint32_t sentinel) {
+		const size_t stride = RecordLayout<B>::words;
+		std::fill(records, records + capacity * stride, sentinel);
+		for (const RecordField & f : RecordLayout<B>::fields) {
+			void * p; memcpy(&p, (const char *)&b + f.member, sizeof p);
+			staging.resize(std::max(capacity, size_t(1)) * f.words);
+			if (read(staging.data(), p, capacity * f.words * 4)) return false;
+			for (size_t i = 0; i < capacity; i++) for (int w = 0; w < f.words; w++) records[i * stride + f.word + w] = staging[i * f.words + w];
+		}
 		return true;
 	}
 	std::vector<uint32_t> staging;
@@ -65,6 +79,21 @@ struct Probe {
 		RT_HIP(ctx, quiesce(ctx));
 		RT_HIP(ctx, hipEventElapsedTime(ms, begin, end));
 		return RT_OK;
+	}
+};
+
+// "Every pixel in range and named once", for the probes whose launch writes a pixel per entry without an atomic: name() says what an entry's pixel is, and
+// the caller words its own refusal.
+struct PixelsOnce {
+	enum Named { FRESH, BEYOND, TWICE };
+	std::vector<uint8_t> seen; size_t pixels;
+	explicit PixelsOnce(size_t n) : seen((n + 7) / 8, 0), pixels(n) { }
+	Named name(size_t pixel) {
+		if (pixel >= pixels) return BEYOND;
+		const uint8_t bit = uint8_t(1u << (pixel & 7));
+		if (seen[pixel >> 3] & bit) return TWICE;
+		seen[pixel >> 3] |= bit;
+		return FRESH;
 	}
 };
 } // namespace
@@ -276,14 +305,14 @@ int rt_trace_queue_rays(rt_context * ctx, int merged, int step, int form,
 	std::vector<float4> light(shadow_count);
 	{	// every pixel a shadow ray names lies inside the frames, and no two rays name the same one: the contribution is a plain read-modify-write,
 		// and a frame never queues two shadow rays per pixel and bounce
-		std::vector<uint8_t> seen((frame_pixels + 7) / 8, 0);
+		PixelsOnce once(frame_pixels);
 		for (size_t i = 0; i < shadow_count; i++) {
 			const uint32_t word = pixel_words[i];
 			if (!merged && (word & RT_SHADOW_FLAG_BOUNCE_0)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_trace_queue_rays: shadow ray %zu: the bounce-0 flag is set in the pixel word of a per-bounce launch", i);
 			const uint32_t pixel = word & ~RT_SHADOW_FLAG_BOUNCE_0;
-			if (pixel >= frame_pixels) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_trace_queue_rays: shadow ray %zu: pixel %u beyond the %zu pixels of the frames", i, pixel, frame_pixels);
-			if (seen[pixel >> 3] & (1u << (pixel & 7))) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_trace_queue_rays: shadow ray %zu: pixel %u appears twice", i, pixel);
-			seen[pixel >> 3] |= uint8_t(1u << (pixel & 7));
+			const PixelsOnce::Named named = once.name(pixel);
+			if (named == PixelsOnce::BEYOND) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_trace_queue_rays: shadow ray %zu: pixel %u beyond the %zu pixels of the frames", i, pixel, frame_pixels);
+			if (named == PixelsOnce::TWICE) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_trace_queue_rays: shadow ray %zu: pixel %u appears twice", i, pixel);
 			float w; memcpy(&w, &word, 4);
 			light[i] = make_float4(illumination[3 * i], illumination[3 * i + 1], illumination[3 * i + 2], w);
 		}
@@ -595,179 +624,220 @@ int rt_perturb_normals(rt_context * ctx, int texture_index, const float * probes
 	return probe.finish_and_read(out, dev_out, count * 16);
 }
 
+} // extern "C"
+
+// ---- the sort and material launch probes: what rt_sort_rays (with its fog form) and rt_shade_rays do around their launch, written once ----
+namespace {
+// The arguments the two share. `name` is the entry point's, for every message.
+struct QueueLaunch {
+	rt_context * ctx; const char * name;
+	int merged, step; size_t count;   // merged: `step` is the iteration, else the bounce; `count` entries in the queue the launch reads
+	const int32_t * slot_table; size_t slot_count; const int32_t * submission_birth;   // (merged form)
+	size_t capacity, frame_slots;
+	size_t pixels() const { return frame_slots * ctx->frame_pixels; }
+};
+
+// The argument checks in the order the refusals are decided: `merged`, the entry point's own refusal (`own`: its text, or null), then what the two share, down to the
+// slot table. tables_given: slot table, births and statistics (merged form). bounce_limit: RT_MAX_BOUNCES, or one less for a launch that appends to the NEXT
+// bounce's trace queue, whose per-bounce counter RtBufferSizes::trace[bounce + 1] would else be the next array's first word.
+int queue_launch_arguments(const QueueLaunch & a, const char * own, bool tables_given, int bounce_limit) {
+	rt_context * ctx = a.ctx; const char * name = a.name;
+	if (a.merged != 0 && a.merged != 1) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: merged must be 0 (per-bounce launch) or 1 (merged wavefront)", name);
+	if (own) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: %s", name, own);
+	if (a.merged && !tables_given) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: NULL slot table, submission births or statistics (merged form)", name);
+	if (a.step < 0 || (!a.merged && a.step >= bounce_limit))
+		return fail(ctx, RT_ERROR_INVALID_ARG, a.merged ? "%s: negative iteration" : bounce_limit == RT_MAX_BOUNCES ? "%s: bounce outside [0, RT_MAX_BOUNCES)" : "%s: bounce outside [0, RT_MAX_BOUNCES - 1)", name);
+	if (a.capacity < 1 || a.capacity > size_t(1) << 28) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: capacity must be in [1, 2^28]", name);
+	if (a.count > a.capacity) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: more entries than the queue capacity", name);
+	// a bounce the path length does not reach is refused too: beyond it the per-bounce counter of the next trace queue runs into the next array of RtBufferSizes
+	if (!a.merged && a.step >= ctx->params.config.num_bounces) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: bounce outside [0, num_bounces)", name);
+	(void)hipSetDevice(ctx->device);
+	int s = check_ready(ctx, name, NEED_SCENE_JOINT | NEED_MATERIALS | NEED_RNG | NEED_SKY | NEED_FRAME); if (s) return s;
+	if (a.frame_slots < 1 || a.frame_slots > size_t(RT_STREAM_SAMPLE_SLOTS) || a.frame_slots * ctx->frame_pixels >= size_t(1) << 30)
+		return fail(ctx, RT_ERROR_INVALID_ARG, "%s: frame_slots must be in [1, 512] and frame_slots * frame_pixels below 2^30", name);
+	if (!a.merged) return RT_OK;
+	if (a.slot_count < 1 || a.slot_count > size_t(RT_STREAM_SAMPLE_SLOTS)) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: slot_count must be in [1, 512]", name);
+	for (size_t k = 0; k < a.slot_count; k++) {
+		const int32_t * e = a.slot_table + 4 * k;
+		if (e[2] < 0 || e[2] >= RT_STREAM_SUBMISSIONS) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: slot %zu: submission %d outside [0, %d)", name, k, e[2], RT_STREAM_SUBMISSIONS);
+		if (e[1] != a.submission_birth[e[2]]) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: slot %zu: birth iteration %d is not its submission's (%d)", name, k, e[1], a.submission_birth[e[2]]);
+	}
+	return RT_OK;
+}
+
+// Every index the kernel forms from an entry of the queue it reads (B: RtTraceBuffer or RtMaterialBuffer) stays inside the call's buffers and the context's tables.
+// miss_allowed: a triangle id of RT_INVALID names no triangle and no instance. also(i, mesh_id): the entry point's own test of a hit entry, after these.
+template<typename B, typename Also> int queue_launch_entries(const QueueLaunch & a, const uint32_t * records, bool miss_allowed, Also && also) {
+	constexpr int PIXEL = record_word<B>(offsetof(B, pixel_index_and_flags)), HIT = record_word<B>(offsetof(B, hits)), MEDIUM = record_word<B>(offsetof(B, medium));
+	static_assert(PIXEL >= 0 && HIT >= 0 && MEDIUM >= 0, "the record has a pixel word, a hit and a medium");
+	rt_context * ctx = a.ctx; const char * name = a.name;
+	const size_t pixels = a.pixels(), frame_pixels = ctx->frame_pixels;
+	PixelsOnce once(pixels);
+	for (size_t i = 0; i < a.count; i++) {
+		const uint32_t * r = records + i * RecordLayout<B>::words;
+		const uint32_t v = r[PIXEL] & ~RT_FLAGS_ALL;
+		const PixelsOnce::Named named = once.name(v);
+		if (named == PixelsOnce::BEYOND) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: entry %zu: virtual pixel %u beyond the %zu pixels of the frames", name, i, v, pixels);
+		if (named == PixelsOnce::TWICE) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: entry %zu: virtual pixel %u appears twice", name, i, v);
+		const int32_t mesh_id = int32_t(r[HIT]), triangle_id = int32_t(r[HIT + 1]);
+		if (!miss_allowed || triangle_id != RT_INVALID) {
+			if (triangle_id < 0 || size_t(triangle_id) >= ctx->triangle_count) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: entry %zu: triangle id %d beyond the %zu triangles", name, i, triangle_id, ctx->triangle_count);
+			if (mesh_id < 0 || size_t(mesh_id) >= ctx->mesh_count) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: entry %zu: mesh id %d beyond the %zu instances", name, i, mesh_id, ctx->mesh_count);
+			if (int s = also(i, mesh_id)) return s;
+		}
+		if (r[PIXEL] & RT_FLAG_INSIDE_MEDIUM) {
+			const int32_t medium = int32_t(r[MEDIUM]);
+			if (medium < 0 || size_t(medium) >= ctx->medium_count) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: entry %zu: medium id %d beyond the %zu media", name, i, medium, ctx->medium_count);
+		}
+		if (a.merged) {
+			const size_t slot = v / frame_pixels;
+			if (slot >= a.slot_count) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: entry %zu: slot %zu beyond the %zu slots of the table", name, i, slot, a.slot_count);
+			const int bounce = a.step - a.slot_table[4 * slot + 1];
+			if (bounce < 0 || bounce >= RT_MAX_BOUNCES || bounce >= ctx->params.config.num_bounces)
+				return fail(ctx, RT_ERROR_INVALID_ARG, "%s: entry %zu: bounce %d outside [0, min(RT_MAX_BOUNCES, num_bounces))", name, i, bounce);
+		}
+	}
+	return RT_OK;
+}
+
+// The counters a launch reads and writes, as its scheduler keeps them: the control block (merged; with the slot table where one is given) or RtBufferSizes, all
+// zero but for what `set_control` / `set_sizes` write -- the count of the queue the launch reads. After read() the host copies are what the launch left.
+struct LaunchCounters {
+	RtBufferSizes * sizes = nullptr; RtStreamControl * control = nullptr; RtStreamTable * table = nullptr;
+	std::unique_ptr<RtStreamControl> control_host; RtBufferSizes sizes_host = { };
+	template<typename SetControl, typename SetSizes>
+	void stage(Probe & probe, bool merged, SetControl && set_control, SetSizes && set_sizes, const int32_t * slot_table = nullptr, size_t slot_count = 0, const int32_t * submission_birth = nullptr) {
+		if (!merged) { set_sizes(sizes_host); sizes = probe.array<RtBufferSizes>(1, &sizes_host); return; }
+		control_host.reset(new RtStreamControl());   // (value-initialised: zero cursors and region words)
+		set_control(*control_host);
+		control = probe.array<RtStreamControl>(1, control_host.get());
+		if (!slot_table) return;
+		std::unique_ptr<RtStreamTable> table_host(new RtStreamTable());
+		memcpy(table_host->slots, slot_table, slot_count * sizeof(RtStreamSlot));
+		memcpy(table_host->submission_birth, submission_birth, sizeof(table_host->submission_birth));
+		table = probe.array<RtStreamTable>(1, table_host.get());
+	}
+	void patch(RtParams & p) const { p.sizes = sizes; p.stream = control; p.stream_table = table; }
+	// (stats: the merged form's statistics, the control block's)
+	int read(Probe & probe, int32_t * stats) {
+		if (!control) return probe.read(&sizes_host, sizes, sizeof(RtBufferSizes));
+		int s = probe.read(control_host.get(), control, sizeof(RtStreamControl)); if (s) return s;
+		memcpy(stats, control_host->stats, sizeof(control_host->stats));
+		return RT_OK;
+	}
+};
+int * material_sizes(RtBufferSizes & z, int material_slot) { return material_slot == 0 ? z.diffuse : material_slot == 1 ? z.plastic : material_slot == 2 ? z.dielectric : z.conductor; }
+
+// The AOV frames of a launch (`count` of them, at most four, of the kinds `aov`; one after the other in the caller's `frames`) and the three g-buffers, `pixels`
+// pixels each: before the launch the caller's values, or (stage(..., false, ...)) the sentinel in every word; read back whole after it.
+struct LaunchFrames {
+	const int * aov; int count; void * frames, * normal_and_depth, * mesh_id_and_triangle_id, * screen_position_prev;   // the caller's: 4, 4, 2 and 2 words a pixel
+	float4 * dev_frames[4] = { }; float4 * g_nd = nullptr; int2 * g_id = nullptr; float2 * g_sp = nullptr;
+	void stage(Probe & probe, size_t pixels, bool callers_values, uint32_t sentinel) {
+		auto image = [&](const void * host, size_t words) { return probe.words(pixels * words, callers_values ? host : nullptr, sentinel); };
+		for (int k = 0; k < count; k++) dev_frames[k] = (float4 *)image((const uint32_t *)frames + size_t(k) * pixels * 4, 4);
+		g_nd = (float4 *)image(normal_and_depth, 4); g_id = (int2 *)image(mesh_id_and_triangle_id, 2); g_sp = (float2 *)image(screen_position_prev, 2);
+	}
+	// the launch has these frames where the context has the AOV, and no other
+	void patch(const rt_context * ctx, RtParams & p) const {
+		for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = nullptr;
+		for (int k = 0; k < count; k++) if (ctx->aov_buffers[aov[k]][0]) p.aovs[aov[k]].framebuffer = dev_frames[k];
+		p.gbuffer_normal_and_depth = g_nd; p.gbuffer_mesh_id_and_triangle_id = g_id; p.gbuffer_screen_position_prev = g_sp;
+	}
+	int read(Probe & probe, size_t pixels) const {
+		int s = RT_OK;
+		for (int k = 0; k < count && s == RT_OK; k++) s = probe.read((uint32_t *)frames + size_t(k) * pixels * 4, dev_frames[k], pixels * 16);
+		if (s || (s = probe.read(normal_and_depth, g_nd, pixels * 16)) || (s = probe.read(mesh_id_and_triangle_id, g_id, pixels * 8))) return s;
+		return probe.read(screen_position_prev, g_sp, pixels * 8);
+	}
+};
+} // namespace
+
 // rt_sort_rays: the sort launch (rt_launch_sort or rt_launch_sort_stream, as the per-bounce loop and stream_enqueue_iteration call them) on an
 // explicit trace queue. The parameter block is the context's (ctx->params, or stream_params(ctx, iteration)) with both trace queues, the four
 // material queues, the counters (RtBufferSizes) or the control block and slot table, the AOV frames, the g-buffers and the pixel-query word
 // replaced by buffers of this call, every output array filled with the caller's sentinel. Runs on the main stream after quiesce().
 // rt_sort_rays_fog is the same call with a shadow queue (shadow_out / shadow_count, both null for rt_sort_rays): the ..._fog instance appends the light
 // samples of its scatter vertices to it. The messages name rt_sort_rays either way.
-} // extern "C"
 static int sort_rays_probe(rt_context * ctx, int merged, int step, int sample_index, const uint32_t * trace_in, size_t count,
                            const int32_t * slot_table, size_t slot_count, const int32_t * submission_birth,
                            size_t capacity, size_t frame_slots, uint32_t sentinel,
                            uint32_t * trace_out, uint32_t * material_out, int32_t * counters6,
                            float * aov_frames, float * gbuffer_normal_and_depth, int32_t * gbuffer_mesh_id_and_triangle_id, float * gbuffer_screen_position_prev,
                            int32_t * pixel_query2, int32_t * stats, uint32_t * shadow_out, int32_t * shadow_count) {
-	RT_REQUIRE(ctx, merged == 0 || merged == 1, "rt_sort_rays: merged must be 0 (per-bounce launch) or 1 (merged wavefront)");
-	RT_REQUIRE(ctx, (trace_in || count == 0) && trace_out && material_out && counters6 && aov_frames && gbuffer_normal_and_depth &&
-	                gbuffer_mesh_id_and_triangle_id && gbuffer_screen_position_prev && pixel_query2, "rt_sort_rays: NULL array");
-	RT_REQUIRE(ctx, !merged || (slot_table && submission_birth && stats), "rt_sort_rays: NULL slot table, submission births or statistics (merged form)");
-	RT_REQUIRE(ctx, step >= 0 && (merged || step < RT_MAX_BOUNCES), merged ? "rt_sort_rays: negative iteration" : "rt_sort_rays: bounce outside [0, RT_MAX_BOUNCES)");
-	RT_REQUIRE(ctx, capacity >= 1 && capacity <= size_t(1) << 28, "rt_sort_rays: capacity must be in [1, 2^28]");
-	RT_REQUIRE(ctx, count <= capacity, "rt_sort_rays: more entries than the queue capacity");
-	// a bounce the path length does not reach is refused too: beyond it the per-bounce counter of the next trace queue runs into the next array of RtBufferSizes
-	RT_REQUIRE(ctx, merged || step < ctx->params.config.num_bounces, "rt_sort_rays: bounce outside [0, num_bounces)");
-	(void)hipSetDevice(ctx->device);
-	int s = check_ready(ctx, "rt_sort_rays", NEED_SCENE_JOINT | NEED_MATERIALS | NEED_RNG | NEED_SKY | NEED_FRAME); if (s) return s;
-	const size_t frame_pixels = ctx->frame_pixels;
-	RT_REQUIRE(ctx, frame_slots >= 1 && frame_slots <= size_t(RT_STREAM_SAMPLE_SLOTS) && frame_slots * frame_pixels < size_t(1) << 30,
-	           "rt_sort_rays: frame_slots must be in [1, 512] and frame_slots * frame_pixels below 2^30");
-	RT_REQUIRE(ctx, !merged || (slot_count >= 1 && slot_count <= size_t(RT_STREAM_SAMPLE_SLOTS)), "rt_sort_rays: slot_count must be in [1, 512]");
-	const size_t pixels = frame_slots * frame_pixels;
-	if (merged) for (size_t k = 0; k < slot_count; k++) {
-		const int32_t * e = slot_table + 4 * k;
-		if (e[2] < 0 || e[2] >= RT_STREAM_SUBMISSIONS) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: slot %zu: submission %d outside [0, %d)", k, e[2], RT_STREAM_SUBMISSIONS);
-		if (e[1] != submission_birth[e[2]]) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: slot %zu: birth iteration %d is not its submission's (%d)", k, e[1], submission_birth[e[2]]);
-	}
-	{	// every index the kernel forms from an entry stays inside the call's buffers and the context's tables
-		std::vector<uint8_t> seen((pixels + 7) / 8, 0);
-		for (size_t i = 0; i < count; i++) {
-			const uint32_t * r = trace_in + i * RT_SORT_TRACE_WORDS;
-			const uint32_t v = r[10] & ~RT_FLAGS_ALL;
-			if (v >= pixels) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: virtual pixel %u beyond the %zu pixels of the frames", i, v, pixels);
-			if (seen[v >> 3] & (1u << (v & 7))) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: virtual pixel %u appears twice", i, v);
-			seen[v >> 3] |= uint8_t(1u << (v & 7));
-			const int32_t mesh_id = int32_t(r[6]), triangle_id = int32_t(r[7]);
-			if (triangle_id != RT_INVALID) {
-				if (triangle_id < 0 || size_t(triangle_id) >= ctx->triangle_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: triangle id %d beyond the %zu triangles", i, triangle_id, ctx->triangle_count);
-				if (mesh_id < 0 || size_t(mesh_id) >= ctx->mesh_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: mesh id %d beyond the %zu instances", i, mesh_id, ctx->mesh_count);
-			}
-			if (r[10] & RT_FLAG_INSIDE_MEDIUM) {
-				const int32_t medium = int32_t(r[15]);
-				if (medium < 0 || size_t(medium) >= ctx->medium_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: medium id %d beyond the %zu media", i, medium, ctx->medium_count);
-			}
-			if (merged) {
-				const size_t slot = v / frame_pixels;
-				if (slot >= slot_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: slot %zu beyond the %zu slots of the table", i, slot, slot_count);
-				const int bounce = step - slot_table[4 * slot + 1];
-				if (bounce < 0 || bounce >= RT_MAX_BOUNCES || bounce >= ctx->params.config.num_bounces)
-					return fail(ctx, RT_ERROR_INVALID_ARG, "rt_sort_rays: entry %zu: bounce %d outside [0, min(RT_MAX_BOUNCES, num_bounces))", i, bounce);
-			}
-		}
-	}
+	const QueueLaunch a = { ctx, "rt_sort_rays", merged, step, count, slot_table, slot_count, submission_birth, capacity, frame_slots };
+	const bool arrays = (trace_in || count == 0) && trace_out && material_out && counters6 && aov_frames && gbuffer_normal_and_depth &&
+	                    gbuffer_mesh_id_and_triangle_id && gbuffer_screen_position_prev && pixel_query2;
+	int s = queue_launch_arguments(a, arrays ? nullptr : "NULL array", slot_table && submission_birth && stats, RT_MAX_BOUNCES); if (s) return s;
+	if ((s = queue_launch_entries<RtTraceBuffer>(a, trace_in, true, [](size_t, int32_t) { return int(RT_OK); }))) return s;
 	RT_HIP(ctx, quiesce(ctx));
-	s = sky_sampling_prepare(ctx, "rt_sort_rays"); if (s) return s;   // (as a render settles it: it decides the instance)
+	s = sky_sampling_prepare(ctx, a.name); if (s) return s;   // (as a render settles it: it decides the instance)
 
-	Probe probe(ctx, "rt_sort_rays");
-	auto upload_column = [&](const uint32_t * records, size_t n, size_t stride, size_t word, size_t words) { return probe.column(records, n, stride, word, words, capacity, sentinel); };
-	auto download_column = [&](const void * device, uint32_t * records, size_t stride, size_t word, size_t words) { return probe.column_back(device, records, stride, word, words, capacity); };
-	auto vec3 = [&](const uint32_t * records, size_t n, size_t stride, size_t word) { return probe.column3(records, n, stride, word, capacity, sentinel); };
-	auto trace_buffer = [&](const uint32_t * records, size_t n) -> RtTraceBuffer {
-		const size_t W = RT_SORT_TRACE_WORDS;
-		RtTraceBuffer t = { };
-		t.origin = vec3(records, n, W, 0); t.direction = vec3(records, n, W, 3);
-		t.hits = (uint4 *)upload_column(records, n, W, 6, 4);
-		t.pixel_index_and_flags = (unsigned *)upload_column(records, n, W, 10, 1);
-		t.throughput = vec3(records, n, W, 11);
-		t.last_pdf = (float *)upload_column(records, n, W, 14, 1);
-		t.medium = (int *)upload_column(records, n, W, 15, 1);
-		t.cone_angle = (float *)upload_column(records, n, W, 16, 1); t.cone_width = (float *)upload_column(records, n, W, 17, 1);
-		return t;
-	};
-	const int q = step & 1;
-	RtTraceBuffer in = trace_buffer(trace_in, count), out = trace_buffer(nullptr, 0);
+	Probe probe(ctx, a.name);
+	const int q = step & 1; const size_t pixels = a.pixels();
+	const RtTraceBuffer in = probe.queue<RtTraceBuffer>(trace_in, count, capacity, sentinel), out = probe.queue<RtTraceBuffer>(capacity, sentinel);
 	RtMaterialBuffer material[4];
-	for (RtMaterialBuffer & m : material) {
-		m = { };
-		m.direction = vec3(nullptr, 0, 0, 0); m.hits = (uint4 *)upload_column(nullptr, 0, 0, 0, 4);
-		m.pixel_index_and_flags = (unsigned *)upload_column(nullptr, 0, 0, 0, 1); m.throughput = vec3(nullptr, 0, 0, 0);
-		m.medium = (int *)upload_column(nullptr, 0, 0, 0, 1);
-		m.cone_angle = (float *)upload_column(nullptr, 0, 0, 0, 1); m.cone_width = (float *)upload_column(nullptr, 0, 0, 0, 1);
-	}
-	float4 * frames[4]; const int frame_aov[4] = { RT_AOV_RADIANCE, RT_AOV_RADIANCE_DIRECT, RT_AOV_RADIANCE_INDIRECT, RT_AOV_ALBEDO };
-	for (int k = 0; k < 4; k++) frames[k] = probe.array<float4>(pixels, aov_frames + size_t(k) * pixels * 4);
-	float4 * g_nd = probe.array<float4>(pixels, gbuffer_normal_and_depth);
-	int2 * g_id = probe.array<int2>(pixels, gbuffer_mesh_id_and_triangle_id);
-	float2 * g_sp = probe.array<float2>(pixels, gbuffer_screen_position_prev);
+	for (RtMaterialBuffer & m : material) m = probe.queue<RtMaterialBuffer>(capacity, sentinel);
+	const RtShadowBuffer shadow = shadow_out ? probe.queue<RtShadowBuffer>(capacity, sentinel) : RtShadowBuffer { };
+	static const int frame_aov[4] = { RT_AOV_RADIANCE, RT_AOV_RADIANCE_DIRECT, RT_AOV_RADIANCE_INDIRECT, RT_AOV_ALBEDO };
+	LaunchFrames frames = { frame_aov, 4, aov_frames, gbuffer_normal_and_depth, gbuffer_mesh_id_and_triangle_id, gbuffer_screen_position_prev };
+	frames.stage(probe, pixels, true, sentinel);
 	int * query = probe.array<int>(2, pixel_query2);
-	RtBufferSizes * sizes = nullptr; RtStreamControl * control = nullptr; RtStreamTable * table = nullptr;
-	if (merged) {
-		std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());
-		control_host->trace_count[q] = int(count);
-		control = probe.array<RtStreamControl>(1, control_host.get());
-		std::unique_ptr<RtStreamTable> table_host(new RtStreamTable());
-		memcpy(table_host->slots, slot_table, slot_count * sizeof(RtStreamSlot));
-		memcpy(table_host->submission_birth, submission_birth, sizeof(table_host->submission_birth));
-		table = probe.array<RtStreamTable>(1, table_host.get());
-	} else {
-		RtBufferSizes sizes_host = { };
-		sizes_host.trace[step] = int(count);
-		sizes = probe.array<RtBufferSizes>(1, &sizes_host);
-	}
-	RtShadowBuffer shadow = { };
-	if (shadow_out) {
-		shadow.origin = vec3(nullptr, 0, 0, 0); shadow.direction = vec3(nullptr, 0, 0, 0);
-		shadow.max_distance = (float *)upload_column(nullptr, 0, 0, 0, 1); shadow.illumination_and_pixel_index = (float4 *)upload_column(nullptr, 0, 0, 0, 4);
-	}
+	LaunchCounters counters;
+	counters.stage(probe, merged != 0, [&](RtStreamControl & c) { c.trace_count[q] = int(count); }, [&](RtBufferSizes & z) { z.trace[step] = int(count); }, slot_table, slot_count, submission_birth);
 	if ((s = probe.allocated())) return s;
 
 	RtParams p = merged ? stream_params(ctx, step) : ctx->params;
 	p.trace[q] = in; p.trace[q ^ 1] = out;
 	if (shadow_out) p.shadow = shadow; else p.fog_active = 0;   // (rt_sort_rays: the instances it always launched; the ..._fog ones need this call's shadow queue)
 	for (int m = 0; m < 4; m++) p.material[m] = material[m];
-	p.sizes = sizes; p.stream = control; p.stream_table = table;
-	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = nullptr;
-	for (int k = 0; k < 4; k++) if (ctx->aov_buffers[frame_aov[k]][0]) p.aovs[frame_aov[k]].framebuffer = frames[k];
-	p.gbuffer_normal_and_depth = g_nd; p.gbuffer_mesh_id_and_triangle_id = g_id; p.gbuffer_screen_position_prev = g_sp;
+	counters.patch(p); frames.patch(ctx, p);
 	p.pixel_query_out = query;
 	if (merged) rt_launch_sort_stream(p, ctx->stream); else rt_launch_sort(p, step, sample_index, ctx->stream);
 	if ((s = probe.finish(ctx->stream))) return s;
 
-	const size_t TW = RT_SORT_TRACE_WORDS, MW = RT_SORT_MATERIAL_WORDS;
-	for (size_t i = 0; i < capacity * TW; i++) trace_out[i] = sentinel;
-	for (size_t i = 0; i < 4 * capacity * MW; i++) material_out[i] = sentinel;
-	bool read = true;
-	const float * const out_vec[3][3] = { { out.origin.x, out.origin.y, out.origin.z }, { out.direction.x, out.direction.y, out.direction.z }, { out.throughput.x, out.throughput.y, out.throughput.z } };
-	const size_t out_word[3] = { 0, 3, 11 };
-	for (int v = 0; v < 3; v++) for (int c = 0; c < 3; c++) read = read && download_column(out_vec[v][c], trace_out, TW, out_word[v] + c, 1);
-	read = read && download_column(out.hits, trace_out, TW, 6, 4) && download_column(out.pixel_index_and_flags, trace_out, TW, 10, 1) && download_column(out.last_pdf, trace_out, TW, 14, 1)
-	            && download_column(out.medium, trace_out, TW, 15, 1) && download_column(out.cone_angle, trace_out, TW, 16, 1) && download_column(out.cone_width, trace_out, TW, 17, 1);
-	for (int m = 0; m < 4; m++) {
-		uint32_t * records = material_out + size_t(m) * capacity * MW;
-		const RtMaterialBuffer & b = material[m];
-		read = read && download_column(b.direction.x, records, MW, 0, 1) && download_column(b.direction.y, records, MW, 1, 1) && download_column(b.direction.z, records, MW, 2, 1)
-		            && download_column(b.hits, records, MW, 3, 4) && download_column(b.pixel_index_and_flags, records, MW, 7, 1)
-		            && download_column(b.throughput.x, records, MW, 8, 1) && download_column(b.throughput.y, records, MW, 9, 1) && download_column(b.throughput.z, records, MW, 10, 1)
-		            && download_column(b.medium, records, MW, 11, 1) && download_column(b.cone_angle, records, MW, 12, 1) && download_column(b.cone_width, records, MW, 13, 1);
-	}
-	if (shadow_out) {
-		const size_t SW = RT_SHADE_SHADOW_WORDS;
-		for (size_t i = 0; i < capacity * SW; i++) shadow_out[i] = sentinel;
-		const RtVec3SoA * const shadow_vec[2] = { &shadow.origin, &shadow.direction };
-		for (int v = 0; v < 2; v++) read = read && download_column(shadow_vec[v]->x, shadow_out, SW, 3 * v, 1) && download_column(shadow_vec[v]->y, shadow_out, SW, 3 * v + 1, 1)
-		                                        && download_column(shadow_vec[v]->z, shadow_out, SW, 3 * v + 2, 1);
-		read = read && download_column(shadow.max_distance, shadow_out, SW, 6, 1) && download_column(shadow.illumination_and_pixel_index, shadow_out, SW, 7, 4);
-	}
-	if (!read) return fail(ctx, RT_ERROR_HIP, "rt_sort_rays: reading the queues back failed");
+	bool read = probe.queue_back(out, trace_out, capacity, sentinel);
+	for (int m = 0; m < 4; m++) read = read && probe.queue_back(material[m], material_out + size_t(m) * capacity * RT_SORT_MATERIAL_WORDS, capacity, sentinel);
+	if (shadow_out) read = read && probe.queue_back(shadow, shadow_out, capacity, sentinel);
+	if (!read) return fail(ctx, RT_ERROR_HIP, "%s: reading the queues back failed", a.name);
+	if ((s = counters.read(probe, stats))) return s;
 	if (merged) {
-		std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());
-		if ((s = probe.read(control_host.get(), control, sizeof(RtStreamControl)))) return s;
-		if (shadow_count) *shadow_count = control_host->shadow_count[q];
-		for (int m = 0; m < 4; m++) counters6[m] = control_host->material_count[m];
-		counters6[4] = control_host->trace_count[q ^ 1]; counters6[5] = control_host->trace_count[q];
-		memcpy(stats, control_host->stats, sizeof(control_host->stats));
+		const RtStreamControl & c = *counters.control_host;
+		if (shadow_count) *shadow_count = c.shadow_count[q];
+		for (int m = 0; m < 4; m++) counters6[m] = c.material_count[m];
+		counters6[4] = c.trace_count[q ^ 1]; counters6[5] = c.trace_count[q];
 	} else {
-		RtBufferSizes sizes_host;
-		if ((s = probe.read(&sizes_host, sizes, sizeof(RtBufferSizes)))) return s;
-		if (shadow_count) *shadow_count = sizes_host.shadow[step];
-		counters6[0] = sizes_host.diffuse[step]; counters6[1] = sizes_host.plastic[step]; counters6[2] = sizes_host.dielectric[step]; counters6[3] = sizes_host.conductor[step];
-		counters6[4] = step + 1 < RT_MAX_BOUNCES ? sizes_host.trace[step + 1] : 0; counters6[5] = sizes_host.trace[step];
+		RtBufferSizes & z = counters.sizes_host;
+		if (shadow_count) *shadow_count = z.shadow[step];
+		for (int m = 0; m < 4; m++) counters6[m] = material_sizes(z, m)[step];
+		counters6[4] = step + 1 < RT_MAX_BOUNCES ? z.trace[step + 1] : 0; counters6[5] = z.trace[step];
 	}
-	for (int k = 0; k < 4 && s == RT_OK; k++) s = probe.read(aov_frames + size_t(k) * pixels * 4, frames[k], pixels * 16);
-	if (s || (s = probe.read(gbuffer_normal_and_depth, g_nd, pixels * 16)) || (s = probe.read(gbuffer_mesh_id_and_triangle_id, g_id, pixels * 8))
-	      || (s = probe.read(gbuffer_screen_position_prev, g_sp, pixels * 8))) return s;
+	if ((s = frames.read(probe, pixels))) return s;
 	return probe.read(pixel_query2, query, 8);
 }
+
+// rt_fog_segments and rt_fog_density_segments after their NULL checks: the fog's segment step on explicit segments, on the volume (density: and the grid) in force.
+static int fog_segments_probe(rt_context * ctx, const char * name, bool density, const uint32_t * probes, size_t count, uint32_t * out) {
+	if (count > size_t(1) << 24) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: more than 2^24 probes", name);
+	if (!ctx->fog_set) return fail(ctx, RT_ERROR_NOT_READY, "%s: no fog volume set (rt_set_fog_volume)", name);
+	if (density && !ctx->fog_grid_set) return fail(ctx, RT_ERROR_NOT_READY, "%s: no density grid set (rt_set_fog_density)", name);
+	(void)hipSetDevice(ctx->device);
+	int s = check_ready(ctx, name, NEED_RNG | NEED_FRAME); if (s) return s;
+	for (size_t i = 0; i < count; i++) {
+		const uint32_t * a = probes + i * RT_FOG_SEGMENT_IN;
+		if (a[7] >= 1u << 30) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: probe %zu: pixel %u beyond the 30-bit path index", name, i, a[7]);
+		if (a[8] >= unsigned(RT_MAX_BOUNCES)) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: probe %zu: bounce %u outside [0, RT_MAX_BOUNCES)", name, i, a[8]);
+	}
+	if (count == 0) return RT_OK;
+	Probe probe(ctx, name);
+	uint32_t * dev_probes = probe.array<uint32_t>(count * RT_FOG_SEGMENT_IN, probes);
+	uint32_t * dev_out = probe.array<uint32_t>(count * RT_FOG_SEGMENT_OUT);
+	if ((s = probe.allocated())) return s;
+	// (a grid of zeros, or a volume without density, is marched as it is: the device fields are set whenever a grid is)
+	(density ? rt_launch_fog_density_segments : rt_launch_fog_segments)(ctx->params, dev_probes, int(count), dev_out, ctx->stream);
+	return probe.finish_and_read(out, dev_out, count * RT_FOG_SEGMENT_OUT * 4);
+}
+
 extern "C" {
 
 int rt_sort_rays(rt_context * ctx, int merged, int step, int sample_index, const uint32_t * trace_in, size_t count,
@@ -799,22 +869,7 @@ int rt_sort_rays_fog(rt_context * ctx, int merged, int step, int sample_index, c
 int rt_fog_segments(rt_context * ctx, const uint32_t * probes, size_t count, uint32_t * out) {
 	RT_REQUIRE(ctx, ctx != nullptr, "rt_fog_segments: NULL context");
 	RT_REQUIRE(ctx, (probes && out) || count == 0, "rt_fog_segments: NULL argument");
-	RT_REQUIRE(ctx, count <= size_t(1) << 24, "rt_fog_segments: more than 2^24 probes");
-	if (!ctx->fog_set) return fail(ctx, RT_ERROR_NOT_READY, "rt_fog_segments: no fog volume set (rt_set_fog_volume)");
-	(void)hipSetDevice(ctx->device);
-	int s = check_ready(ctx, "rt_fog_segments", NEED_RNG | NEED_FRAME); if (s) return s;
-	for (size_t i = 0; i < count; i++) {
-		const uint32_t * a = probes + i * RT_FOG_SEGMENT_IN;
-		if (a[7] >= 1u << 30) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_fog_segments: probe %zu: pixel %u beyond the 30-bit path index", i, a[7]);
-		if (a[8] >= unsigned(RT_MAX_BOUNCES)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_fog_segments: probe %zu: bounce %u outside [0, RT_MAX_BOUNCES)", i, a[8]);
-	}
-	if (count == 0) return RT_OK;
-	Probe probe(ctx, "rt_fog_segments");
-	uint32_t * dev_probes = probe.array<uint32_t>(count * RT_FOG_SEGMENT_IN, probes);
-	uint32_t * dev_out = probe.array<uint32_t>(count * RT_FOG_SEGMENT_OUT);
-	if ((s = probe.allocated())) return s;
-	rt_launch_fog_segments(ctx->params, dev_probes, int(count), dev_out, ctx->stream);
-	return probe.finish_and_read(out, dev_out, count * RT_FOG_SEGMENT_OUT * 4);
+	return fog_segments_probe(ctx, "rt_fog_segments", false, probes, count, out);
 }
 
 // rt_fog_density_segments: the segment step over the density grid in force (rt_fog_grid.h: the voxel march under the same clip, pair and weights), on
@@ -822,24 +877,7 @@ int rt_fog_segments(rt_context * ctx, const uint32_t * probes, size_t count, uin
 int rt_fog_density_segments(rt_context * ctx, const uint32_t * probes, size_t count, uint32_t * out) {
 	RT_REQUIRE(ctx, ctx != nullptr, "rt_fog_density_segments: NULL context");
 	RT_REQUIRE(ctx, (probes && out) || count == 0, "rt_fog_density_segments: NULL argument");
-	RT_REQUIRE(ctx, count <= size_t(1) << 24, "rt_fog_density_segments: more than 2^24 probes");
-	if (!ctx->fog_set) return fail(ctx, RT_ERROR_NOT_READY, "rt_fog_density_segments: no fog volume set (rt_set_fog_volume)");
-	if (!ctx->fog_grid_set) return fail(ctx, RT_ERROR_NOT_READY, "rt_fog_density_segments: no density grid set (rt_set_fog_density)");
-	(void)hipSetDevice(ctx->device);
-	int s = check_ready(ctx, "rt_fog_density_segments", NEED_RNG | NEED_FRAME); if (s) return s;
-	for (size_t i = 0; i < count; i++) {
-		const uint32_t * a = probes + i * RT_FOG_SEGMENT_IN;
-		if (a[7] >= 1u << 30) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_fog_density_segments: probe %zu: pixel %u beyond the 30-bit path index", i, a[7]);
-		if (a[8] >= unsigned(RT_MAX_BOUNCES)) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_fog_density_segments: probe %zu: bounce %u outside [0, RT_MAX_BOUNCES)", i, a[8]);
-	}
-	if (count == 0) return RT_OK;
-	Probe probe(ctx, "rt_fog_density_segments");
-	uint32_t * dev_probes = probe.array<uint32_t>(count * RT_FOG_SEGMENT_IN, probes);
-	uint32_t * dev_out = probe.array<uint32_t>(count * RT_FOG_SEGMENT_OUT);
-	if ((s = probe.allocated())) return s;
-	RtParams p = ctx->params;   // (a grid of zeros, or a volume without density, is marched as it is: the device fields are set whenever a grid is)
-	rt_launch_fog_density_segments(p, dev_probes, int(count), dev_out, ctx->stream);
-	return probe.finish_and_read(out, dev_out, count * RT_FOG_SEGMENT_OUT * 4);
+	return fog_segments_probe(ctx, "rt_fog_density_segments", true, probes, count, out);
 }
 
 // rt_attenuate_shadow_rays: the fog's attenuation pass, as the context's scheduler launches it, on an explicit shadow queue. The parameter block is the
@@ -852,34 +890,17 @@ int rt_attenuate_shadow_rays(rt_context * ctx, const uint32_t * shadow_in, size_
 	(void)hipSetDevice(ctx->device);
 	RT_HIP(ctx, quiesce(ctx));
 	const bool merged = ctx->scheduler == RT_SCHEDULER_MERGED;
-	const size_t SW = RT_SHADE_SHADOW_WORDS;
 	Probe probe(ctx, "rt_attenuate_shadow_rays");
-	RtShadowBuffer shadow = { };
-	shadow.origin = probe.column3(shadow_in, count, SW, 0, count, 0u); shadow.direction = probe.column3(shadow_in, count, SW, 3, count, 0u);
-	shadow.max_distance = (float *)probe.column(shadow_in, count, SW, 6, 1, count, 0u);
-	shadow.illumination_and_pixel_index = (float4 *)probe.column(shadow_in, count, SW, 7, 4, count, 0u);
-	RtBufferSizes * sizes = nullptr; RtStreamControl * control = nullptr;
-	if (merged) {
-		std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());
-		control_host->shadow_count[0] = int(count);
-		control = probe.array<RtStreamControl>(1, control_host.get());
-	} else {
-		RtBufferSizes sizes_host = { };
-		sizes_host.shadow[0] = int(count);
-		sizes = probe.array<RtBufferSizes>(1, &sizes_host);
-	}
+	const RtShadowBuffer shadow = probe.queue<RtShadowBuffer>(shadow_in, count, count, 0u);   // (a queue of exactly `count` entries: nothing to fill)
+	LaunchCounters counters;
+	counters.stage(probe, merged, [&](RtStreamControl & c) { c.shadow_count[0] = int(count); }, [&](RtBufferSizes & z) { z.shadow[0] = int(count); });
 	int s = probe.allocated(); if (s) return s;
 	RtParams p = ctx->params;
-	p.shadow = shadow; p.sizes = sizes; p.stream = control; p.stream_iteration = 0;
+	p.shadow = shadow; p.sizes = counters.sizes; p.stream = counters.control; p.stream_iteration = 0;
 	if (merged) rt_launch_fog_attenuate_shadows_stream(p, ctx->stream); else rt_launch_fog_attenuate_shadows(p, 0, ctx->stream);
 	if ((s = probe.finish(ctx->stream))) return s;
 	if (count == 0) return RT_OK;
-	bool read = true;
-	const RtVec3SoA * const shadow_vec[2] = { &shadow.origin, &shadow.direction };
-	for (int v = 0; v < 2; v++) read = read && probe.column_back(shadow_vec[v]->x, shadow_out, SW, 3 * v, 1, count) && probe.column_back(shadow_vec[v]->y, shadow_out, SW, 3 * v + 1, 1, count)
-	                                        && probe.column_back(shadow_vec[v]->z, shadow_out, SW, 3 * v + 2, 1, count);
-	read = read && probe.column_back(shadow.max_distance, shadow_out, SW, 6, 1, count) && probe.column_back(shadow.illumination_and_pixel_index, shadow_out, SW, 7, 4, count);
-	if (!read) return fail(ctx, RT_ERROR_HIP, "rt_attenuate_shadow_rays: reading the queue back failed");
+	if (!probe.queue_back(shadow, shadow_out, count, 0u)) return fail(ctx, RT_ERROR_HIP, "rt_attenuate_shadow_rays: reading the queue back failed");
 	return RT_OK;
 }
 
@@ -894,96 +915,35 @@ int rt_shade_rays(rt_context * ctx, int merged, int step, int sample_index, int 
                   uint32_t * aov_frames, uint32_t * gbuffer_normal_and_depth, uint32_t * gbuffer_mesh_id_and_triangle_id, uint32_t * gbuffer_screen_position_prev,
                   int32_t * stats) {
 	RT_REQUIRE(ctx, ctx != nullptr, "rt_shade_rays: NULL context");
-	RT_REQUIRE(ctx, merged == 0 || merged == 1, "rt_shade_rays: merged must be 0 (per-bounce launch) or 1 (merged wavefront)");
-	RT_REQUIRE(ctx, material_slot >= 0 && material_slot < 4, "rt_shade_rays: material_slot must be 0 (diffuse), 1 (plastic), 2 (dielectric) or 3 (conductor)");
-	RT_REQUIRE(ctx, (material_in || count == 0) && trace_out && shadow_out && counters3 && aov_frames && gbuffer_normal_and_depth &&
-	                gbuffer_mesh_id_and_triangle_id && gbuffer_screen_position_prev, "rt_shade_rays: NULL array");
-	RT_REQUIRE(ctx, !merged || (slot_table && submission_birth && stats), "rt_shade_rays: NULL slot table, submission births or statistics (merged form)");
-	// (the per-bounce counter of the next trace queue is RtBufferSizes::trace[bounce + 1]: at RT_MAX_BOUNCES - 1 it would be the next array's first word)
-	RT_REQUIRE(ctx, step >= 0 && (merged || step < RT_MAX_BOUNCES - 1), merged ? "rt_shade_rays: negative iteration" : "rt_shade_rays: bounce outside [0, RT_MAX_BOUNCES - 1)");
-	RT_REQUIRE(ctx, capacity >= 1 && capacity <= size_t(1) << 28, "rt_shade_rays: capacity must be in [1, 2^28]");
-	RT_REQUIRE(ctx, count <= capacity, "rt_shade_rays: more entries than the queue capacity");
-	RT_REQUIRE(ctx, merged || step < ctx->params.config.num_bounces, "rt_shade_rays: bounce outside [0, num_bounces)");
-	(void)hipSetDevice(ctx->device);
-	int s = check_ready(ctx, "rt_shade_rays", NEED_SCENE_JOINT | NEED_MATERIALS | NEED_RNG | NEED_SKY | NEED_FRAME); if (s) return s;
-	const size_t frame_pixels = ctx->frame_pixels;
-	RT_REQUIRE(ctx, frame_slots >= 1 && frame_slots <= size_t(RT_STREAM_SAMPLE_SLOTS) && frame_slots * frame_pixels < size_t(1) << 30,
-	           "rt_shade_rays: frame_slots must be in [1, 512] and frame_slots * frame_pixels below 2^30");
-	RT_REQUIRE(ctx, !merged || (slot_count >= 1 && slot_count <= size_t(RT_STREAM_SAMPLE_SLOTS)), "rt_shade_rays: slot_count must be in [1, 512]");
-	const size_t pixels = frame_slots * frame_pixels;
-	if (merged) for (size_t k = 0; k < slot_count; k++) {
-		const int32_t * e = slot_table + 4 * k;
-		if (e[2] < 0 || e[2] >= RT_STREAM_SUBMISSIONS) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: slot %zu: submission %d outside [0, %d)", k, e[2], RT_STREAM_SUBMISSIONS);
-		if (e[1] != submission_birth[e[2]]) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: slot %zu: birth iteration %d is not its submission's (%d)", k, e[1], submission_birth[e[2]]);
-	}
+	const QueueLaunch a = { ctx, "rt_shade_rays", merged, step, count, slot_table, slot_count, submission_birth, capacity, frame_slots };
+	const bool arrays = (material_in || count == 0) && trace_out && shadow_out && counters3 && aov_frames && gbuffer_normal_and_depth &&
+	                    gbuffer_mesh_id_and_triangle_id && gbuffer_screen_position_prev;
+	const char * own = material_slot < 0 || material_slot >= 4 ? "material_slot must be 0 (diffuse), 1 (plastic), 2 (dielectric) or 3 (conductor)" : arrays ? nullptr : "NULL array";
+	int s = queue_launch_arguments(a, own, slot_table && submission_birth && stats, RT_MAX_BOUNCES - 1); if (s) return s;
 	RT_HIP(ctx, quiesce(ctx));
-	{	// every index the kernel forms from an entry stays inside the call's buffers and the context's tables, and the entry sits in its material's queue
-		std::vector<int32_t> mesh_material(ctx->mesh_count);
-		if (count) RT_HIP(ctx, hipMemcpy(mesh_material.data(), ctx->params.mesh_material_ids, ctx->mesh_count * 4, hipMemcpyDeviceToHost));
-		std::vector<uint8_t> seen((pixels + 7) / 8, 0);
-		for (size_t i = 0; i < count; i++) {
-			const uint32_t * r = material_in + i * RT_SORT_MATERIAL_WORDS;
-			const uint32_t v = r[7] & ~RT_FLAGS_ALL;
-			if (v >= pixels) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: entry %zu: virtual pixel %u beyond the %zu pixels of the frames", i, v, pixels);
-			if (seen[v >> 3] & (1u << (v & 7))) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: entry %zu: virtual pixel %u appears twice", i, v);
-			seen[v >> 3] |= uint8_t(1u << (v & 7));
-			const int32_t mesh_id = int32_t(r[3]), triangle_id = int32_t(r[4]);
-			if (triangle_id < 0 || size_t(triangle_id) >= ctx->triangle_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: entry %zu: triangle id %d beyond the %zu triangles", i, triangle_id, ctx->triangle_count);
-			if (mesh_id < 0 || size_t(mesh_id) >= ctx->mesh_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: entry %zu: mesh id %d beyond the %zu instances", i, mesh_id, ctx->mesh_count);
-			const int32_t material_id = mesh_material[mesh_id];
-			if (material_id < 0 || size_t(material_id) >= ctx->material_type_list.size() || int(ctx->material_type_list[material_id]) != RT_MATERIAL_DIFFUSE + material_slot)
-				return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: entry %zu: the material of instance %d (material %d) does not belong to queue %d", i, mesh_id, material_id, material_slot);
-			if (r[7] & RT_FLAG_INSIDE_MEDIUM) {
-				const int32_t medium = int32_t(r[11]);
-				if (medium < 0 || size_t(medium) >= ctx->medium_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: entry %zu: medium id %d beyond the %zu media", i, medium, ctx->medium_count);
-			}
-			if (merged) {
-				const size_t slot = v / frame_pixels;
-				if (slot >= slot_count) return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: entry %zu: slot %zu beyond the %zu slots of the table", i, slot, slot_count);
-				const int bounce = step - slot_table[4 * slot + 1];
-				if (bounce < 0 || bounce >= RT_MAX_BOUNCES || bounce >= ctx->params.config.num_bounces)
-					return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: entry %zu: bounce %d outside [0, min(RT_MAX_BOUNCES, num_bounces))", i, bounce);
-			}
-		}
-	}
+	std::vector<int32_t> mesh_material(ctx->mesh_count);
+	if (count) RT_HIP(ctx, hipMemcpy(mesh_material.data(), ctx->params.mesh_material_ids, ctx->mesh_count * 4, hipMemcpyDeviceToHost));
+	s = queue_launch_entries<RtMaterialBuffer>(a, material_in, false, [&](size_t i, int32_t mesh_id) -> int {   // ... and the entry sits in its material's queue
+		const int32_t material_id = mesh_material[mesh_id];
+		if (material_id < 0 || size_t(material_id) >= ctx->material_type_list.size() || int(ctx->material_type_list[material_id]) != RT_MATERIAL_DIFFUSE + material_slot)
+			return fail(ctx, RT_ERROR_INVALID_ARG, "rt_shade_rays: entry %zu: the material of instance %d (material %d) does not belong to queue %d", i, mesh_id, material_id, material_slot);
+		return RT_OK;
+	});
+	if (s) return s;
 	if (material_slot >= 2) { s = ensure_luts(ctx); if (s) return s; }   // (as a render settles them)
-	s = sky_sampling_prepare(ctx, "rt_shade_rays"); if (s) return s;   // (... and this: it decides the instance)
+	s = sky_sampling_prepare(ctx, a.name); if (s) return s;   // (... and this: it decides the instance)
 
-	Probe probe(ctx, "rt_shade_rays");
-	const size_t MW = RT_SORT_MATERIAL_WORDS, TW = RT_SORT_TRACE_WORDS, SW = RT_SHADE_SHADOW_WORDS;
-	auto in_column = [&](size_t word, size_t words) { return probe.column(material_in, count, MW, word, words, capacity, sentinel); };
-	auto out_column = [&](size_t words) { return probe.column(nullptr, 0, 0, 0, words, capacity, sentinel); };
-	auto out_vec3 = [&]() { return probe.column3(nullptr, 0, 0, 0, capacity, sentinel); };
-	RtMaterialBuffer in = { };
-	in.direction = probe.column3(material_in, count, MW, 0, capacity, sentinel); in.hits = (uint4 *)in_column(3, 4);
-	in.pixel_index_and_flags = (unsigned *)in_column(7, 1); in.throughput = probe.column3(material_in, count, MW, 8, capacity, sentinel);
-	in.medium = (int *)in_column(11, 1); in.cone_angle = (float *)in_column(12, 1); in.cone_width = (float *)in_column(13, 1);
-	RtTraceBuffer out = { };
-	out.origin = out_vec3(); out.direction = out_vec3(); out.hits = (uint4 *)out_column(4); out.pixel_index_and_flags = (unsigned *)out_column(1);
-	out.throughput = out_vec3(); out.last_pdf = (float *)out_column(1); out.medium = (int *)out_column(1);
-	out.cone_angle = (float *)out_column(1); out.cone_width = (float *)out_column(1);
-	RtShadowBuffer shadow = { };
-	shadow.origin = out_vec3(); shadow.direction = out_vec3(); shadow.max_distance = (float *)out_column(1); shadow.illumination_and_pixel_index = (float4 *)out_column(4);
-	// the frames and g-buffers, all sentinel: 4 + 4 + 4 words per pixel (ALBEDO, NORMAL, POSITION), then 4, 2, 2
-	float4 * frames[3]; const int frame_aov[3] = { RT_AOV_ALBEDO, RT_AOV_NORMAL, RT_AOV_POSITION };
-	auto filled = [&](size_t words) { probe.staging.assign(pixels * words, sentinel); return probe.array<uint32_t>(pixels * words, probe.staging.data()); };
-	for (int k = 0; k < 3; k++) frames[k] = (float4 *)filled(4);
-	float4 * g_nd = (float4 *)filled(4); int2 * g_id = (int2 *)filled(2); float2 * g_sp = (float2 *)filled(2);
-	const int q = step & 1;
-	RtBufferSizes * sizes = nullptr; RtStreamControl * control = nullptr; RtStreamTable * table = nullptr;
-	if (merged) {
-		std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());
-		control_host->material_count[material_slot] = int(count);
-		control = probe.array<RtStreamControl>(1, control_host.get());
-		std::unique_ptr<RtStreamTable> table_host(new RtStreamTable());
-		memcpy(table_host->slots, slot_table, slot_count * sizeof(RtStreamSlot));
-		memcpy(table_host->submission_birth, submission_birth, sizeof(table_host->submission_birth));
-		table = probe.array<RtStreamTable>(1, table_host.get());
-	} else {
-		RtBufferSizes sizes_host = { };
-		(material_slot == 0 ? sizes_host.diffuse : material_slot == 1 ? sizes_host.plastic : material_slot == 2 ? sizes_host.dielectric : sizes_host.conductor)[step] = int(count);
-		sizes = probe.array<RtBufferSizes>(1, &sizes_host);
-	}
+	Probe probe(ctx, a.name);
+	const int q = step & 1; const size_t pixels = a.pixels();
+	const RtMaterialBuffer in = probe.queue<RtMaterialBuffer>(material_in, count, capacity, sentinel);
+	const RtTraceBuffer out = probe.queue<RtTraceBuffer>(capacity, sentinel);
+	const RtShadowBuffer shadow = probe.queue<RtShadowBuffer>(capacity, sentinel);
+	static const int frame_aov[3] = { RT_AOV_ALBEDO, RT_AOV_NORMAL, RT_AOV_POSITION };
+	LaunchFrames frames = { frame_aov, 3, aov_frames, gbuffer_normal_and_depth, gbuffer_mesh_id_and_triangle_id, gbuffer_screen_position_prev };
+	frames.stage(probe, pixels, false, sentinel);
+	LaunchCounters counters;
+	counters.stage(probe, merged != 0, [&](RtStreamControl & c) { c.material_count[material_slot] = int(count); }, [&](RtBufferSizes & z) { material_sizes(z, material_slot)[step] = int(count); },
+	               slot_table, slot_count, submission_birth);
 	if ((s = probe.allocated())) return s;
 
 	RtParams p = merged ? stream_params(ctx, step) : ctx->params;
@@ -991,41 +951,21 @@ int rt_shade_rays(rt_context * ctx, int merged, int step, int sample_index, int 
 	for (int m = 0; m < 4; m++) p.material[m] = RtMaterialBuffer { };
 	p.material[material_slot] = in;
 	p.shadow = shadow;
-	p.sizes = sizes; p.stream = control; p.stream_table = table;
-	for (int a = 0; a < RT_AOV_COUNT; a++) p.aovs[a].framebuffer = nullptr;
-	for (int k = 0; k < 3; k++) if (ctx->aov_buffers[frame_aov[k]][0]) p.aovs[frame_aov[k]].framebuffer = frames[k];
-	p.gbuffer_normal_and_depth = g_nd; p.gbuffer_mesh_id_and_triangle_id = g_id; p.gbuffer_screen_position_prev = g_sp;
+	counters.patch(p); frames.patch(ctx, p);
 	p.pixel_query_out = nullptr;
 	if (merged) rt_launch_material_stream(p, material_slot, ctx->stream); else rt_launch_material(p, material_slot, step, sample_index, ctx->stream);
 	if ((s = probe.finish(ctx->stream))) return s;
 
-	bool read = true;
-	const RtVec3SoA * const out_vec[3] = { &out.origin, &out.direction, &out.throughput }; const size_t out_word[3] = { 0, 3, 11 };
-	for (int v = 0; v < 3; v++) read = read && probe.column_back(out_vec[v]->x, trace_out, TW, out_word[v], 1, capacity) && probe.column_back(out_vec[v]->y, trace_out, TW, out_word[v] + 1, 1, capacity)
-	                                        && probe.column_back(out_vec[v]->z, trace_out, TW, out_word[v] + 2, 1, capacity);
-	read = read && probe.column_back(out.hits, trace_out, TW, 6, 4, capacity) && probe.column_back(out.pixel_index_and_flags, trace_out, TW, 10, 1, capacity)
-	            && probe.column_back(out.last_pdf, trace_out, TW, 14, 1, capacity) && probe.column_back(out.medium, trace_out, TW, 15, 1, capacity)
-	            && probe.column_back(out.cone_angle, trace_out, TW, 16, 1, capacity) && probe.column_back(out.cone_width, trace_out, TW, 17, 1, capacity);
-	for (size_t i = 0; i < capacity; i++) trace_out[i * TW + 18] = trace_out[i * TW + 19] = sentinel;   // (padding)
-	const RtVec3SoA * const shadow_vec[2] = { &shadow.origin, &shadow.direction };
-	for (int v = 0; v < 2; v++) read = read && probe.column_back(shadow_vec[v]->x, shadow_out, SW, 3 * v, 1, capacity) && probe.column_back(shadow_vec[v]->y, shadow_out, SW, 3 * v + 1, 1, capacity)
-	                                        && probe.column_back(shadow_vec[v]->z, shadow_out, SW, 3 * v + 2, 1, capacity);
-	read = read && probe.column_back(shadow.max_distance, shadow_out, SW, 6, 1, capacity) && probe.column_back(shadow.illumination_and_pixel_index, shadow_out, SW, 7, 4, capacity);
-	if (!read) return fail(ctx, RT_ERROR_HIP, "rt_shade_rays: reading the queues back failed");
+	if (!probe.queue_back(out, trace_out, capacity, sentinel) || !probe.queue_back(shadow, shadow_out, capacity, sentinel)) return fail(ctx, RT_ERROR_HIP, "%s: reading the queues back failed", a.name);
+	if ((s = counters.read(probe, stats))) return s;
 	if (merged) {
-		std::unique_ptr<RtStreamControl> control_host(new RtStreamControl());
-		if ((s = probe.read(control_host.get(), control, sizeof(RtStreamControl)))) return s;
-		counters3[0] = control_host->trace_count[q ^ 1]; counters3[1] = control_host->shadow_count[q]; counters3[2] = control_host->material_count[material_slot];
-		memcpy(stats, control_host->stats, sizeof(control_host->stats));
+		const RtStreamControl & c = *counters.control_host;
+		counters3[0] = c.trace_count[q ^ 1]; counters3[1] = c.shadow_count[q]; counters3[2] = c.material_count[material_slot];
 	} else {
-		RtBufferSizes sizes_host;
-		if ((s = probe.read(&sizes_host, sizes, sizeof(RtBufferSizes)))) return s;
-		counters3[0] = sizes_host.trace[step + 1]; counters3[1] = sizes_host.shadow[step];
-		counters3[2] = (material_slot == 0 ? sizes_host.diffuse : material_slot == 1 ? sizes_host.plastic : material_slot == 2 ? sizes_host.dielectric : sizes_host.conductor)[step];
+		RtBufferSizes & z = counters.sizes_host;
+		counters3[0] = z.trace[step + 1]; counters3[1] = z.shadow[step]; counters3[2] = material_sizes(z, material_slot)[step];
 	}
-	for (int k = 0; k < 3 && s == RT_OK; k++) s = probe.read(aov_frames + size_t(k) * pixels * 4, frames[k], pixels * 16);
-	if (s || (s = probe.read(gbuffer_normal_and_depth, g_nd, pixels * 16)) || (s = probe.read(gbuffer_mesh_id_and_triangle_id, g_id, pixels * 8))) return s;
-	return probe.read(gbuffer_screen_position_prev, g_sp, pixels * 8);
+	return frames.read(probe, pixels);
 }
 
 // The three accumulate probes -- rt_accumulate_frames, rt_accumulate_list_frames, rt_accumulate_cascade_frames -- after their own NULL and mode checks: ONE
@@ -1056,11 +996,11 @@ static int accumulate_probe(rt_context * ctx, const char * name, bool merged, bo
 	if (list) {   // before any launch: every entry inside the frame, no pixel twice (two threads folding one pixel would race)
 		const size_t frame = size_t(ctx->params.screen_width) * size_t(ctx->params.screen_height);
 		if (list_count < 1 || list_count > frame) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: the list holds 1 to width * height entries", name);
-		std::vector<bool> seen(frame, false);
+		PixelsOnce once(frame);
 		for (size_t i = 0; i < list_count; i++) {
-			if (list[i] >= frame) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: list entry %zu (%u) lies outside the %zu pixel frame", name, i, list[i], frame);
-			if (seen[list[i]]) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: list entry %zu names pixel %u a second time", name, i, list[i]);
-			seen[list[i]] = true;
+			const PixelsOnce::Named named = once.name(list[i]);
+			if (named == PixelsOnce::BEYOND) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: list entry %zu (%u) lies outside the %zu pixel frame", name, i, list[i], frame);
+			if (named == PixelsOnce::TWICE) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: list entry %zu names pixel %u a second time", name, i, list[i]);
 		}
 		a.pixel_count = int(list_count);
 	} else {
@@ -1076,8 +1016,7 @@ static int accumulate_probe(rt_context * ctx, const char * name, bool merged, bo
 	if (moments) a.moments = probe.array<float4>(frame_pixels, moments);
 	if (cascade) a.tiers = { probe.array<float4>(tier_pixels, tiers), frame_pixels, cascade->tiers, cascade->start };
 	if (list) a.list = probe.array<unsigned>(list_count, list);
-	probe.staging.assign(frame_pixels * 4, sentinel);
-	float4 * dev_final = (float4 *)probe.array<uint32_t>(frame_pixels * 4, probe.staging.data());
+	float4 * dev_final = (float4 *)probe.words(frame_pixels * 4, nullptr, sentinel);
 	if ((s = probe.allocated())) return s;
 
 	RtParams p = ctx->params;
@@ -1101,38 +1040,60 @@ int rt_accumulate_frames(rt_context * ctx, int merged, const int32_t * first_sam
 	                        moments, nullptr, 0, nullptr, nullptr, sentinel, final_image);
 }
 
+} // extern "C"
+
+// The estimate and the selection on the caller's images, after the entry points' NULL checks; each plain (resolved null: no held_fraction, cell_held or held
+// count) or firefly-robust.
+static int estimate_noise_images_probe(rt_context * ctx, const char * name, const float * mean, const float * moments, const float * resolved, float floor, float held_fraction,
+                                       rt_noise_estimate * out, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, int32_t * cell_held, size_t cell_capacity,
+                                       float * pixel_map, int64_t * out_held_pixels) {
+	if (!(floor > 0.0f && floor < __builtin_huge_valf())) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: floor must be finite and positive", name);
+	int s = resolved ? held_fraction_argument(ctx, name, held_fraction) : RT_OK; if (s) return s;
+	(void)hipSetDevice(ctx->device);
+	if (ctx->frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "%s: rt_resize was not called", name);
+	RT_HIP(ctx, quiesce(ctx));
+	Probe probe(ctx, name);
+	const float4 * dev_mean = probe.array<float4>(ctx->frame_pixels, mean), * dev_moments = probe.array<float4>(ctx->frame_pixels, moments);
+	const NoiseRobust robust = { resolved ? probe.array<float4>(ctx->frame_pixels, resolved) : nullptr, held_fraction, cell_held, out_held_pixels };
+	if ((s = probe.allocated())) return s;
+	return noise_estimate_images(ctx, name, dev_mean, dev_moments, floor, out, cell_sums, cell_counts, cell_nonfinite, cell_capacity, pixel_map, resolved ? &robust : nullptr);
+}
+
+static int select_pixels_images_probe(rt_context * ctx, const char * name, const float * mean, const float * moments, const float * resolved, float floor, float held_fraction,
+                                      float threshold, int dilate, rt_cell_selection * out, double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, int32_t * cell_held,
+                                      uint8_t * cell_flags, size_t cell_capacity, uint32_t * list, size_t list_capacity) {
+	int s = selection_arguments(ctx, name, floor, threshold, dilate); if (s) return s;
+	if (resolved && (s = held_fraction_argument(ctx, name, held_fraction))) return s;
+	(void)hipSetDevice(ctx->device);
+	if (ctx->frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "%s: rt_resize was not called", name);
+	const size_t frame = size_t(ctx->params.screen_width) * size_t(ctx->params.screen_height);
+	if (list_capacity < frame) return fail(ctx, RT_ERROR_INVALID_ARG, "%s: list_capacity is below width * height", name);
+	RT_HIP(ctx, quiesce(ctx));
+	Probe probe(ctx, name);
+	const float4 * dev_mean = probe.array<float4>(ctx->frame_pixels, mean), * dev_moments = probe.array<float4>(ctx->frame_pixels, moments);
+	const NoiseRobust robust = { resolved ? probe.array<float4>(ctx->frame_pixels, resolved) : nullptr, held_fraction, cell_held, nullptr };
+	unsigned * dev_list = probe.array<unsigned>(frame, list);   // (what the kernels do not write comes back as the caller gave it)
+	if ((s = probe.allocated())) return s;
+	if ((s = select_cells_images(ctx, name, dev_mean, dev_moments, floor, threshold, dilate, dev_list, out, cell_sums, cell_counts, cell_nonfinite, cell_flags, cell_capacity,
+	                             resolved ? &robust : nullptr))) return s;
+	return probe.read(list, dev_list, frame * 4);
+}
+
+extern "C" {
+
 int rt_estimate_noise_images(rt_context * ctx, const float * mean, const float * moments, float floor, rt_noise_estimate * out, double * cell_sums,
                              int32_t * cell_counts, int32_t * cell_nonfinite, size_t cell_capacity, float * pixel_map) {
 	RT_REQUIRE(ctx, ctx != nullptr, "rt_estimate_noise_images: NULL context");
 	RT_REQUIRE(ctx, mean && moments && out && cell_sums && cell_counts && cell_nonfinite, "rt_estimate_noise_images: NULL argument");
-	RT_REQUIRE(ctx, floor > 0.0f && floor < __builtin_huge_valf(), "rt_estimate_noise_images: floor must be finite and positive");
-	(void)hipSetDevice(ctx->device);
-	if (ctx->frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_estimate_noise_images: rt_resize was not called");
-	RT_HIP(ctx, quiesce(ctx));
-	Probe probe(ctx, "rt_estimate_noise_images");
-	float4 * dev_mean = probe.array<float4>(ctx->frame_pixels, mean);
-	float4 * dev_moments = probe.array<float4>(ctx->frame_pixels, moments);
-	int s = probe.allocated(); if (s) return s;
-	return noise_estimate_images(ctx, "rt_estimate_noise_images", dev_mean, dev_moments, floor, out, cell_sums, cell_counts, cell_nonfinite, cell_capacity, pixel_map);
+	return estimate_noise_images_probe(ctx, "rt_estimate_noise_images", mean, moments, nullptr, floor, 0.0f, out, cell_sums, cell_counts, cell_nonfinite, nullptr, cell_capacity, pixel_map, nullptr);
 }
 
 int rt_select_pixels_images(rt_context * ctx, const float * mean, const float * moments, float floor, float threshold, int dilate, rt_cell_selection * out,
                             double * cell_sums, int32_t * cell_counts, int32_t * cell_nonfinite, uint8_t * cell_flags, size_t cell_capacity, uint32_t * list, size_t list_capacity) {
 	RT_REQUIRE(ctx, ctx != nullptr, "rt_select_pixels_images: NULL context");
 	RT_REQUIRE(ctx, mean && moments && out && cell_sums && cell_counts && cell_nonfinite && cell_flags && list, "rt_select_pixels_images: NULL argument");
-	int s = selection_arguments(ctx, "rt_select_pixels_images", floor, threshold, dilate); if (s) return s;
-	(void)hipSetDevice(ctx->device);
-	if (ctx->frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_select_pixels_images: rt_resize was not called");
-	const size_t frame = size_t(ctx->params.screen_width) * size_t(ctx->params.screen_height);
-	RT_REQUIRE(ctx, list_capacity >= frame, "rt_select_pixels_images: list_capacity is below width * height");
-	RT_HIP(ctx, quiesce(ctx));
-	Probe probe(ctx, "rt_select_pixels_images");
-	float4 * dev_mean = probe.array<float4>(ctx->frame_pixels, mean);
-	float4 * dev_moments = probe.array<float4>(ctx->frame_pixels, moments);
-	unsigned * dev_list = probe.array<unsigned>(frame, list);   // (what the kernels do not write comes back as the caller gave it)
-	if ((s = probe.allocated())) return s;
-	if ((s = select_cells_images(ctx, "rt_select_pixels_images", dev_mean, dev_moments, floor, threshold, dilate, dev_list, out, cell_sums, cell_counts, cell_nonfinite, cell_flags, cell_capacity))) return s;
-	return probe.read(list, dev_list, frame * 4);
+	return select_pixels_images_probe(ctx, "rt_select_pixels_images", mean, moments, nullptr, floor, 0.0f, threshold, dilate, out, cell_sums, cell_counts, cell_nonfinite, nullptr, cell_flags,
+	                                  cell_capacity, list, list_capacity);
 }
 
 int rt_denoise_images(rt_context * ctx, int width, int height, int pitch, const float * colour, const float * moments, const float * albedo, const float * normal,
@@ -1216,16 +1177,8 @@ int rt_estimate_noise_robust_images(rt_context * ctx, const float * mean, const 
                                     float * pixel_map, int64_t * out_held_pixels) {
 	RT_REQUIRE(ctx, ctx != nullptr, "rt_estimate_noise_robust_images: NULL context");
 	RT_REQUIRE(ctx, mean && moments && resolved && out && cell_sums && cell_counts && cell_nonfinite && cell_held, "rt_estimate_noise_robust_images: NULL argument");
-	RT_REQUIRE(ctx, floor > 0.0f && floor < __builtin_huge_valf(), "rt_estimate_noise_robust_images: floor must be finite and positive");
-	int s = held_fraction_argument(ctx, "rt_estimate_noise_robust_images", held_fraction); if (s) return s;
-	(void)hipSetDevice(ctx->device);
-	if (ctx->frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_estimate_noise_robust_images: rt_resize was not called");
-	RT_HIP(ctx, quiesce(ctx));
-	Probe probe(ctx, "rt_estimate_noise_robust_images");
-	const float4 * dev_mean = probe.array<float4>(ctx->frame_pixels, mean), * dev_moments = probe.array<float4>(ctx->frame_pixels, moments);
-	const NoiseRobust robust = { probe.array<float4>(ctx->frame_pixels, resolved), held_fraction, cell_held, out_held_pixels };
-	if ((s = probe.allocated())) return s;
-	return noise_estimate_images(ctx, "rt_estimate_noise_robust_images", dev_mean, dev_moments, floor, out, cell_sums, cell_counts, cell_nonfinite, cell_capacity, pixel_map, &robust);
+	return estimate_noise_images_probe(ctx, "rt_estimate_noise_robust_images", mean, moments, resolved, floor, held_fraction, out, cell_sums, cell_counts, cell_nonfinite, cell_held, cell_capacity,
+	                                   pixel_map, out_held_pixels);
 }
 
 int rt_select_pixels_robust_images(rt_context * ctx, const float * mean, const float * moments, const float * resolved, float floor, float held_fraction, float threshold,
@@ -1233,21 +1186,8 @@ int rt_select_pixels_robust_images(rt_context * ctx, const float * mean, const f
                                    uint8_t * cell_flags, size_t cell_capacity, uint32_t * list, size_t list_capacity) {
 	RT_REQUIRE(ctx, ctx != nullptr, "rt_select_pixels_robust_images: NULL context");
 	RT_REQUIRE(ctx, mean && moments && resolved && out && cell_sums && cell_counts && cell_nonfinite && cell_held && cell_flags && list, "rt_select_pixels_robust_images: NULL argument");
-	int s = selection_arguments(ctx, "rt_select_pixels_robust_images", floor, threshold, dilate); if (s) return s;
-	if ((s = held_fraction_argument(ctx, "rt_select_pixels_robust_images", held_fraction))) return s;
-	(void)hipSetDevice(ctx->device);
-	if (ctx->frame_pixels == 0) return fail(ctx, RT_ERROR_NOT_READY, "rt_select_pixels_robust_images: rt_resize was not called");
-	const size_t frame = size_t(ctx->params.screen_width) * size_t(ctx->params.screen_height);
-	RT_REQUIRE(ctx, list_capacity >= frame, "rt_select_pixels_robust_images: list_capacity is below width * height");
-	RT_HIP(ctx, quiesce(ctx));
-	Probe probe(ctx, "rt_select_pixels_robust_images");
-	const float4 * dev_mean = probe.array<float4>(ctx->frame_pixels, mean), * dev_moments = probe.array<float4>(ctx->frame_pixels, moments);
-	const NoiseRobust robust = { probe.array<float4>(ctx->frame_pixels, resolved), held_fraction, cell_held, nullptr };
-	unsigned * dev_list = probe.array<unsigned>(frame, list);   // (what the kernels do not write comes back as the caller gave it)
-	if ((s = probe.allocated())) return s;
-	if ((s = select_cells_images(ctx, "rt_select_pixels_robust_images", dev_mean, dev_moments, floor, threshold, dilate, dev_list, out, cell_sums, cell_counts, cell_nonfinite, cell_flags,
-	                             cell_capacity, &robust))) return s;
-	return probe.read(list, dev_list, frame * 4);
+	return select_pixels_images_probe(ctx, "rt_select_pixels_robust_images", mean, moments, resolved, floor, held_fraction, threshold, dilate, out, cell_sums, cell_counts, cell_nonfinite, cell_held,
+	                                  cell_flags, cell_capacity, list, list_capacity);
 }
 
 int rt_measure_stream_bandwidth(rt_context * ctx, size_t bytes, int repeat, float * out_gbps) {
