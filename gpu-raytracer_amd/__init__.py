@@ -148,6 +148,14 @@ def device_lib():
         lib.rt_upload_delta_lights.argtypes = [c_void_p, c_void_p, c_size_t, c_float]
         lib.rt_read_delta_lights.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, POINTER(c_size_t), POINTER(c_float)]
         lib.rt_sample_delta_lights.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
+        lib.rt_upload_geometry.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]
+        lib.rt_build_tlas.argtypes = [c_void_p] * 7 + [c_size_t]
+        lib.rt_read_instances.argtypes = [c_void_p] * 7
+        lib.rt_set_light_tree.argtypes = [c_void_p, c_int]
+        lib.rt_get_light_tree.argtypes = [c_void_p]
+        lib.rt_read_light_tree.argtypes = [c_void_p, POINTER(c_int), POINTER(c_int), c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
+        lib.rt_sample_light_tree.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
+        lib.rt_light_tree_pmf.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
         lib.rt_set_fog_volume.argtypes = [c_void_p, c_void_p]
         lib.rt_get_fog_volume.argtypes = [c_void_p, c_void_p, POINTER(c_int)]
         lib.rt_fog_segments.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
@@ -823,6 +831,11 @@ class Pathtracer:
         if self.handle:
             host_lib().grt_pathtracer_free(self.handle)
             self.handle = None
+
+    def set_light_tree(self, enable):
+        """The light tree of next-event estimation: config key light_tree, applied by the next update(), after the light tables are uploaded.
+        The progression then restarts at sample 0. Like every config key it holds for all integrators of the process."""
+        config_set(light_tree=1 if enable else 0)
 
     @property
     def ctx(self):
@@ -2023,6 +2036,62 @@ def sample_delta_lights(ctx, probes):
     p = _f32(probes).reshape(-1, 4)
     out = np.zeros((p.shape[0], DELTA_SAMPLE_OUT), np.float32)
     _dev_check(ctx, device_lib().rt_sample_delta_lights(ctx, p.ctypes.data, p.shape[0], out.ctypes.data))
+    return out
+
+
+MAX_LIGHT_TREE_LEAVES = 1 << 22   # RT_MAX_LIGHT_TREE_LEAVES
+
+
+class LightTree:
+    """What rt_read_light_tree returns: leaf_count N, padded M; nodes (2M - 1, 8) float32 {box_min[3], Phi, box_max[3], pad} in heap numbering; leaf_entry,
+    leaf_triangle (N,) int32 and leaf_area, leaf_power (N,) float32 by leaf id; slot_of_leaf (N,) int32; entry_of_mesh, place_of_triangle int32."""
+
+
+def set_light_tree(ctx, enable):
+    """rt_set_light_tree. Returns the status (0: RT_OK); the message of a refusal is rt_last_error's."""
+    return device_lib().rt_set_light_tree(ctx, 1 if enable else 0)
+
+
+def read_light_tree(ctx, mesh_count=0, triangle_count=0):
+    """rt_read_light_tree: the light tree as built (a LightTree; leaf_count 0 while none exists). mesh_count / triangle_count: the scene's instances and
+    triangles, to read the inverse tables entry_of_mesh and place_of_triangle as well (0: not read)."""
+    lib = device_lib()
+    n, m = c_int(), c_int()
+    _dev_check(ctx, lib.rt_read_light_tree(ctx, byref(n), byref(m), None, 0, None, None, 0, None, 0, None, 0))
+    t = LightTree()
+    t.leaf_count, t.padded = n.value, m.value
+    nodes = np.zeros((max(2 * t.padded - 1, 0), 8), np.float32)
+    leaves = np.zeros((t.leaf_count, 4), np.uint32)
+    t.slot_of_leaf = np.zeros(t.leaf_count, np.int32)
+    t.entry_of_mesh = np.full(mesh_count, -1, np.int32); t.place_of_triangle = np.full(triangle_count, -1, np.int32)
+    if t.padded:
+        _dev_check(ctx, lib.rt_read_light_tree(ctx, byref(n), byref(m), nodes.ctypes.data, nodes.shape[0], leaves.ctypes.data, t.slot_of_leaf.ctypes.data, t.leaf_count,
+                                               t.entry_of_mesh.ctypes.data if mesh_count else None, mesh_count,
+                                               t.place_of_triangle.ctypes.data if triangle_count else None, triangle_count))
+    t.nodes = nodes
+    t.leaf_entry = leaves[:, 0].view(np.int32).copy(); t.leaf_triangle = leaves[:, 1].view(np.int32).copy()
+    t.leaf_area = leaves[:, 2].view(np.float32).copy(); t.leaf_power = leaves[:, 3].view(np.float32).copy()
+    return t
+
+
+def sample_light_tree(ctx, u, u2, points):
+    """rt_sample_light_tree: the kernels' descent of the light tree on N probes -- u, u2 in [0, 1) (scalars or (N,)), points (N, 3). Returns (leaf id (N,) int32,
+    -1 where the tree holds no power; node (N,) int32; pmf (N,) float32)."""
+    pts = _f32(points).reshape(-1, 3)
+    probes = np.empty((pts.shape[0], 5), np.float32)
+    probes[:, 0] = u; probes[:, 1] = u2; probes[:, 2:] = pts
+    out = np.zeros((pts.shape[0], 4), np.float32)
+    _dev_check(ctx, device_lib().rt_sample_light_tree(ctx, probes.ctypes.data, probes.shape[0], out.ctypes.data))
+    return out[:, 0].view(np.int32).copy(), out[:, 1].view(np.int32).copy(), out[:, 2].copy()
+
+
+def light_tree_pmf(ctx, leaves, points):
+    """rt_light_tree_pmf: the probability with which the descent from points[i] arrives at leaf leaves[i] (ids; a scalar or (N,)), (N,) float32."""
+    pts = _f32(points).reshape(-1, 3)
+    probes = np.empty((pts.shape[0], 4), np.float32)
+    probes.view(np.int32)[:, 0] = leaves; probes[:, 1:] = pts
+    out = np.zeros(pts.shape[0], np.float32)
+    _dev_check(ctx, device_lib().rt_light_tree_pmf(ctx, probes.ctypes.data, probes.shape[0], out.ctypes.data))
     return out
 
 

@@ -1,7 +1,7 @@
 // rt_context.h -- what the units of the C ABI share: the context and the structs it is made of, error handling, and the internal functions that
 // cross a unit boundary. The units: rt_api.hip (context, frame state, results), rt_scene.hip (scene uploads and device builds), rt_render.hip (the slot
 // scheduler and the render entry points), rt_stream.hip (the merged wavefront's host side), rt_noise.hip (noise estimate, adaptive sampling), rt_denoise.hip (denoised stills), rt_fireflies.hip (firefly filter),
-// rt_exchange.hip (frame exchange of the tile split), rt_probes.hip (kernel-level entry points). Private to csrc/.
+// rt_exchange.hip (frame exchange of the tile split), rt_light_tree.hip (the light tree of next-event estimation), rt_probes.hip (kernel-level entry points). Private to csrc/.
 #pragma once
 #include "rt_types.h"
 
@@ -204,6 +204,12 @@ struct rt_context {
 	int fog_grid_dims[3] = { 0, 0, 0 }, fog_grid_bricks = 0, fog_grid_empty_bricks = 0;
 	float fog_grid_max = 0.0f;
 	void * fog_density = nullptr, * fog_bricks = nullptr;
+	// light tree (rt_set_light_tree): the wish; the spans of the light tables uploaded last (the leaves are counted from them); the one allocation
+	// behind RtParams::light_tree, which says whether a tree is built
+	bool light_tree_on = false, light_tree_fog_warned = false;
+	bool light_tree_dirty = false;   // an upload the tree depends on has come since it was built (geometry, instances, TLAS build, materials, light tables): light_tree_refresh rebuilds
+	std::vector<int32_t> light_spans;
+	void * light_tree_memory = nullptr;
 	void * luts[6] = { }; bool luts_ready = false;
 	int bvh_width = 8;
 
@@ -291,6 +297,10 @@ int mark_scene_versions_in_use(rt_context * ctx, int slot_index, hipStream_t st)
 int sky_tables_build(rt_context * ctx, const char * caller);
 int sky_sampling_prepare(rt_context * ctx, const char * caller);
 int ensure_luts(rt_context * ctx);
+// rt_light_tree.hip
+int light_tree_leaves_allowed(rt_context * ctx, const char * caller, const int32_t * spans, size_t entries);
+int light_tree_refresh(rt_context * ctx, const char * caller);
+void light_tree_fog_warning(rt_context * ctx);
 // rt_render.hip
 void use_queues(RtParams & p, const WavefrontQueues & q);
 int queues_allocate(rt_context * ctx, WavefrontQueues & q, size_t entries);

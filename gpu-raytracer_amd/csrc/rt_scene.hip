@@ -108,6 +108,7 @@ static int upload_geometry(rt_context * ctx, const char * caller, int width, con
 	s = upload(ctx, &a.device, nodes, node_count * a.node_bytes); if (s) return s;
 	s = upload_triangle_positions(ctx, triangles, triangle_count); if (s) return s;
 	ctx->triangle_count = triangle_count; a.count = node_count;
+	ctx->light_tree_dirty = true;   // (place_of_triangle is sized by the triangle count)
 	ctx->params.triangles = (const float4 *)ctx->triangles;
 	a.param = (const float4 *)a.device;
 	if (width == 8) {   // what only the CWBVH has: the merged wavefront's TLAS copy in its node array, the flattened scene's engine
@@ -385,6 +386,7 @@ int rt_build_geometry(rt_context * ctx, const void * triangles, size_t triangle_
 	device_free(ctx, ctx->triangles); device_free(ctx, ctx->triangle_positions); device_free(ctx, ctx->bvh8_nodes);
 	ctx->triangles = out_triangles; ctx->triangle_positions = out_positions; ctx->bvh8_nodes = out_nodes;
 	ctx->triangle_count = T; ctx->bvh8_node_count = size_t(node_count);
+	ctx->light_tree_dirty = true;
 	ctx->tlas_version_in_nodes = ~0ull;
 	ctx->params.triangles = (const float4 *)out_triangles; ctx->params.triangle_positions = (const float4 *)out_positions; ctx->params.bvh8_nodes = (const float4 *)out_nodes;
 	ctx->params.geometry_below_4gib = rt_geometry_fits_flat_engine(size_t(node_count), size_t(T));
@@ -438,6 +440,7 @@ int rt_upload_instances(rt_context * ctx, const int32_t * root_indices, const in
 	ctx->params.mesh_transforms_prev  = (const float4 *)(base + offset[4]);
 	ctx->params.mesh_position = nullptr;   // the host supplies everything in TLAS order
 	ctx->device_tlas_order = nullptr; ctx->device_tlas_node_count = nullptr;
+	ctx->light_tree_dirty = true;   // (rebuilt once, before the next launch that reads it: light_tree_refresh)
 	return RT_OK;
 }
 
@@ -499,6 +502,7 @@ int rt_build_tlas(rt_context * ctx, const int32_t * root_indices, const int32_t 
 	ctx->params.mesh_transforms_prev  = a.out_transforms_prev;
 	ctx->params.mesh_position         = a.position;
 	ctx->device_tlas_order = a.order; ctx->device_tlas_node_count = a.node_count;
+	ctx->light_tree_dirty = true;
 	return RT_OK;
 }
 
@@ -558,6 +562,7 @@ int rt_upload_materials(rt_context * ctx, const uint8_t * types, const void * ma
 			default: return fail(ctx, RT_ERROR_INVALID_ARG, "rt_upload_materials: unknown material type %d at index %zu", int(types[i]), i);
 		}
 	}
+	ctx->light_tree_dirty = true;   // (emission may have changed)
 	return RT_OK;
 }
 
@@ -729,6 +734,7 @@ int rt_upload_lights(rt_context * ctx,
 	int s = check_light_tables(ctx, light_triangle_indices, light_triangle_cumulative_probability, light_triangle_count,
 	                           light_mesh_cumulative_probability, light_mesh_triangle_span, light_mesh_transform_indices, light_mesh_count, lights_total_weight);
 	if (s) return s;   // (nothing staged: the tables uploaded before stay in force)
+	if (ctx->light_tree_on && (s = light_tree_leaves_allowed(ctx, "rt_upload_lights", light_mesh_triangle_span, light_mesh_count))) return s;
 	(void)hipSetDevice(ctx->device);
 	// the per-mesh tables change with every TLAS rebuild (they are in TLAS order): versioned like the TLAS itself
 	const void * src[5] = { light_triangle_indices, light_triangle_cumulative_probability, light_mesh_cumulative_probability, light_mesh_triangle_span, light_mesh_transform_indices };
@@ -748,6 +754,8 @@ int rt_upload_lights(rt_context * ctx,
 	ctx->params.light_mesh_count    = int(light_mesh_count);
 	ctx->params.light_triangle_count = int(light_triangle_count);
 	ctx->params.lights_total_weight = lights_total_weight;
+	ctx->light_spans.assign(light_mesh_triangle_span, light_mesh_triangle_span + 2 * light_mesh_count);
+	ctx->light_tree_dirty = true;
 	return RT_OK;
 }
 
@@ -927,6 +935,8 @@ int sky_tables_build(rt_context * ctx, const char * caller) {
 // leaves while triangle emitters exist; all the sky leaves without them. Both 0 keeps every kernel on the reference's estimator.
 int sky_sampling_prepare(rt_context * ctx, const char * caller) {
 	RtParams & p = ctx->params;
+	{ int s = light_tree_refresh(ctx, caller); if (s) return s; }   // (the light tree follows the uploads since the last launch: one drain and one build, however many they were)
+	light_tree_fog_warning(ctx);   // (a fog volume displaces the light tree: said once)
 	const bool emitters = p.lights_total_weight > 0.0f;
 	const bool delta = p.delta_light_count > 0 && p.config.enable_next_event_estimation;
 	float share = 0.0f;

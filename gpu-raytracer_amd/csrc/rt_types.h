@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "../../include/gpu_raytracer_amd.h"
+#include "rt_light_tree.h"
 
 #define RT_WAVE_SIZE 64
 #define RT_INFINITY __builtin_huge_valf()
@@ -249,10 +250,18 @@ struct RtParams {
 	int   fog_grid_dims[3];
 	const float * fog_density;
 	const unsigned char * fog_bricks;
+	// Light tree (rt_set_light_tree, DESIGN.md 7.11, rt_light_tree.h): position-aware selection of the triangle emitters. light_tree.padded > 0: a tree is
+	// built -- only then, with next-event estimation on and no fog volume in force, do the launchers take the ..._tree instances of the sort and material
+	// kernels, the only kernels that read these fields.
+	RtLightTree light_tree;
 };
 // Which instances of the sort and material kernels a launcher takes: 0 the plain ones, 1 the ..._sky ones (sky importance sampling alone), 2 the ..._split
-// ones (delta lights take a share, with or without the sky). Shadow rays are traced without triangle emitters whenever it is not 0.
-static inline __host__ __device__ int rt_light_split(const RtParams & p) { return p.delta_nee_share > 0.0f ? 2 : p.sky_nee_share > 0.0f ? 1 : 0; }
+// ones (delta lights take a share, with or without the sky), 3 the ..._tree ones (a light tree is in force: everything 2 does, nee_taken may be 0, the emitters
+// picked by the tree). Shadow rays are traced without triangle emitters whenever it is not 0.
+static inline __host__ __device__ bool rt_light_tree_in_force(const RtParams & p) {
+	return p.light_tree.padded > 0 && p.config.enable_next_event_estimation && !p.fog_active && p.lights_total_weight > 0.0f;
+}
+static inline __host__ __device__ int rt_light_split(const RtParams & p) { return rt_light_tree_in_force(p) ? 3 : p.delta_nee_share > 0.0f ? 2 : p.sky_nee_share > 0.0f ? 1 : 0; }
 static inline __host__ __device__ bool rt_light_samples_split(const RtParams & p) { return rt_light_split(p) != 0; }
 // "Skip behind the hit" (kernels_trace.hip): closest-hit rays drop stacked groups of children that lie behind the hit they hold. Taken when the context wants it
 // (rt_set_skip_behind_hit) AND the scene is ONE tree the flattened scene's engine walks (rt_set_static_geometry(ctx, 1), arrays below 4 GiB): every CWBVH

@@ -106,6 +106,10 @@ struct CPUConfig {
 	// Sky importance sampling for next-event estimation (rt_set_sky_sampling): 0 = off, the reference's estimator; (0, 1] = the sky's share
 	// of the light samples when the scene has emitters (all of them when it has none). Same expectation, less noise under a sky with a sun.
 	float sky_sampling = 0.0f;
+	// Light tree (rt_set_light_tree): 1 = next-event estimation picks a triangle emitter by a descent of a tree over all of them from the shading
+	// point, instead of by power alone. Same expectation, less noise with many lights; off by default. The path tracer switches it after the light tables
+	// are uploaded; the AO integrator ignores it.
+	int   light_tree = 0;
 	// Noise estimate. noise_target: 0 = off; > 0 = the device keeps second moments beside the radiance mean (rt_set_noise_estimate) and the
 	// command-line renderer and Pathtracer.render_until stop once the figure -- the noise_quantile quantile of the cells' mean relative standard error -- is at or
 	// below it, never before noise_min_samples samples. noise_floor: the floor of the luminance the error is taken relative to.

@@ -848,6 +848,10 @@ void Integrator::update(float delta) {
 		invalidated_scene = false;
 		build_tlas();
 	}
+	if (ctx) {   // the light tree, behind the light tables; on a change only: the switch drains the context, and the progression restarts at sample 0
+		const bool want = cpu_config.light_tree != 0 && cpu_config.integrator == IntegratorType::PATHTRACER;
+		if (want != (rt_get_light_tree(ctx) != 0)) { check(rt_set_light_tree(ctx, want ? 1 : 0)); invalidated_gpu_config = true; }
+	}
 
 	scene.camera.update(delta);
 

@@ -104,6 +104,10 @@ int grt_config_set(const char * key, double value) {
 		if (!(value == 0.0 || (value > 0.0 && value <= 1.0))) { g_host_error = "sky_sampling must be 0 (off) or in (0, 1]"; return -1; }
 		cpu_config.sky_sampling = float(value);
 	}
+	else if (k == "light_tree") {   // the light tree of next-event estimation (rt_set_light_tree)
+		if (!(value == 0.0 || value == 1.0)) { g_host_error = "light_tree must be 0 or 1"; return -1; }
+		cpu_config.light_tree = int(value);
+	}
 	else if (k == "noise_target") {   // 0 (off) or a finite positive relative error
 		if (!(value >= 0.0 && value < 1e30)) { g_host_error = "noise_target must be 0 (off) or finite and positive"; return -1; }
 		if (value == 0.0 && cpu_config.adaptive_sampling) { g_host_error = "noise_target 0 (off) while adaptive_sampling is 1: switch adaptive_sampling off first"; return -1; }
@@ -233,6 +237,7 @@ double grt_config_get(const char * key) {
 	if (k == "enable_svgf")    return gpu_config.enable_svgf;
 	if (k == "skip_behind_hit") return cpu_config.skip_behind_hit;
 	if (k == "sky_sampling")   return cpu_config.sky_sampling;
+	if (k == "light_tree")     return cpu_config.light_tree;
 	if (k == "alpha_masks")    return cpu_config.alpha_masks;
 	if (k == "delta_lights")   return cpu_config.delta_lights;
 	if (k == "fog")            return cpu_config.fog ? 1.0 : 0.0;

@@ -109,6 +109,7 @@ std::vector<Option> make_options(CommandLine & cl) {
 		if (!(p == 0.0f || (p > 0.0f && p <= 1.0f))) die("--sky-sampling must be 0 (off) or in (0, 1]");
 		cpu_config.sky_sampling = p;
 	} });
+	o.push_back({ nullptr, "light-tree", "NEE picks a triangle emitter by a light tree from the shading point instead of by power alone (DESIGN.md 7.11): less noise with many lights", 0, [](const char *) { cpu_config.light_tree = 1; } });
 	o.push_back({ nullptr, "fog", "A homogeneous fog volume inside the box <minx,miny,minz,maxx,maxy,maxz> (or off): scattering with light sampling at every scatter event", 1, [](const char * v) {
 		if (grt_config_set_string("fog", v) != 0) die(std::string("--fog: ") + grt_last_error());
 	} });

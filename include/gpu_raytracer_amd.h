@@ -175,6 +175,8 @@ const char * rt_version(void);
  *      (still 17: rt_measure_exposure, rt_measure_exposure_images, rt_estimate_noise_robust, rt_set_noise_robust, rt_get_noise_robust,
  *      rt_estimate_noise_robust_images, rt_select_pixels_robust_images -- new entry points and a result struct of their own; the frame's exposure and the
  *      firefly-robust noise estimate, both off until they are called or set)
+ *      (still 17: rt_set_light_tree, rt_get_light_tree, rt_read_light_tree, rt_sample_light_tree, rt_light_tree_pmf -- new entry points; the light tree of
+ *      next-event estimation, off until it is set)
  * Check `rt_abi_version() == RT_ABI_VERSION` once after loading the library.                                          */
 #define RT_ABI_VERSION 17
 int rt_abi_version(void);
@@ -371,6 +373,31 @@ typedef struct rt_delta_light {
 	float reserved[3];
 } rt_delta_light; /* 64 bytes */
 int rt_upload_delta_lights(rt_context * ctx, const rt_delta_light * records, size_t count, float share);
+/* The light tree: position-aware selection of the triangle emitters in next-event estimation. Off by default; while it is off nothing
+ * changes: the same kernels are launched and the frames are the same to the bit. enable = 1: a tree over all triangle emitters in world space is built on the
+ * device -- one leaf per (light-mesh entry m of rt_upload_lights, triangle j of its span), id leaf_base[m] + j in table order, at most
+ * RT_MAX_LIGHT_TREE_LEAVES of them, else RT_ERROR_INVALID_ARG and the state before stays in force -- as soon as geometry, instances, materials and light tables
+ * are all there, and again after any rt_upload_lights, rt_upload_instances, rt_build_tlas, rt_upload_materials or geometry upload: those calls mark the tree, and it is
+ * rebuilt once before the next render, launch probe or read-back that uses it; a build drains the context. While a
+ * tree exists, next-event estimation is on and no fog volume is active, a light sample that goes to the emitters picks its triangle by a descent of the tree
+ * from the shading point, and the matching probability enters the MIS weight of an emitter that a BSDF-sampled ray hits (the ..._tree kernel instances).
+ * Without triangle emitters nothing is built and the plain kernels run. The AO integrator ignores it.                                                        */
+#define RT_MAX_LIGHT_TREE_LEAVES (1 << 22)
+int rt_set_light_tree(rt_context * ctx, int enable);
+int rt_get_light_tree(rt_context * ctx);
+/* The tree as built (waits for the work in flight). *out_leaf_count = N, *out_padded = M = 2^ceil(log2 N) (both 0 while no tree exists; both pointers are
+ * required). nodes: 2 M - 1 nodes of 8 floats {box_min[3], Phi, box_max[3], pad} in heap numbering (children of i: 2i + 1, 2i + 2; the leaf at sorted place s:
+ * M - 1 + s; padding leaves: Phi 0, an inverted box). leaves: N records of 4 words, by id {light-mesh entry (int32), triangle id (int32), world area A
+ * (float), power Phi (float)}. slot_of_leaf: N node indices. entry_of_mesh: per row of the instance tables its light-mesh entry or -1; place_of_triangle: per
+ * triangle its place in light_triangle_indices or -1. Any array may be NULL; an array given with less room than it needs is RT_ERROR_INVALID_ARG.           */
+int rt_read_light_tree(rt_context * ctx, int32_t * out_leaf_count, int32_t * out_padded, float * nodes, size_t node_capacity,
+                       uint32_t * leaves, int32_t * slot_of_leaf, size_t leaf_capacity,
+                       int32_t * entry_of_mesh, size_t mesh_capacity, int32_t * place_of_triangle, size_t triangle_capacity);
+/* The kernels' selection and its pmf on explicit probes (synchronous; RT_ERROR_INVALID_ARG while no tree exists). rt_sample_light_tree: probes count x 5 floats
+ * {u, u2 in [0, 1), p[3] finite}; out count x 4 words {leaf id (int32; -1: the tree holds no power), node (int32), pmf (float), pad}.
+ * rt_light_tree_pmf: probes count x 4 words {leaf id (int32), p[3]}; out count floats, the bits rt_sample_light_tree reports when it picks that leaf from p.  */
+int rt_sample_light_tree(rt_context * ctx, const float * probes, size_t count, float * out);
+int rt_light_tree_pmf(rt_context * ctx, const float * probes, size_t count, float * out);
 /* The table as staged for the kernels. records: count x RT_DELTA_LIGHT_RECORD floats {position[3], type (int32 bits), unit direction[3],
  * P_k (the light's selection probability, computed in double from its weight), intensity[3], cos(cutoff), cos(beam), cutoff,
  * 1 / (cutoff - beam) (0 when they are equal), pad}; cdf: count floats, inclusive and normalised, the last entry exactly 1. Either array
