@@ -165,8 +165,9 @@ class Launch:
     """One material launch: the queue of slot `slot`, how its entries' bounce and sample are found (per-bounce form: bounce,
     sample_index; merged form: iteration, slot_table (S, 4) int32, submission_birth int32[128]), the frames' size."""
 
-    def __init__(self, name, slot, entries, frame_pixels, frame_slots, bounce=None, sample_index=0, iteration=None, slot_table=None, submission_birth=None):
+    def __init__(self, name, slot, entries, frame_pixels, frame_slots, bounce=None, sample_index=0, iteration=None, slot_table=None, submission_birth=None, first_throughput=False):
         self.name, self.slot, self.entries, self.frame_pixels, self.frame_slots = name, int(slot), entries, int(frame_pixels), int(frame_slots)
+        self.first_throughput = bool(first_throughput)   # the queue holds bounce 0's throughput too, as the ..._fog sort instance stores it
         self.bounce, self.sample_index, self.iteration = bounce, sample_index, iteration
         self.slot_table = None if slot_table is None else np.ascontiguousarray(slot_table, np.int32).reshape(-1, 4)
         self.submission_birth = None if submission_birth is None else np.ascontiguousarray(submission_birth, np.int32)
@@ -183,6 +184,11 @@ class Launch:
         zero = np.zeros(e.n, np.int64)
         return slot, real, zero + self.bounce, self.sample_index + slot, zero
 
+    def sub(self, index, name=None):
+        """The launch on the entries `index` alone."""
+        return Launch(name or self.name + "_sample", self.slot, self.entries.take(index), self.frame_pixels, self.frame_slots, bounce=self.bounce, sample_index=self.sample_index,
+                      iteration=self.iteration, slot_table=self.slot_table, submission_birth=self.submission_birth, first_throughput=self.first_throughput)
+
     def pack(self, garbage=None):
         """(N, 16) uint32 records as the sort writes them; `garbage` (a float32) replaces the sentinel in the words the sort leaves
         unwritten at bounce 0 (throughput, cone) -- the launch must not read them."""
@@ -193,7 +199,8 @@ class Launch:
         r[:, 3] = e.mesh.view(np.uint32); r[:, 4] = e.triangle.view(np.uint32); r[:, 5] = e.t.view(np.uint32); r[:, 6] = (e.u16 & 0xffff) | (e.v16 << 16)
         r[:, 7] = e.pixel | (e.inside.astype(np.uint32) << 30)
         later = bounce > 0
-        r[later, 8:11] = e.throughput.view(np.uint32)[later]
+        carried = later | self.first_throughput
+        r[carried, 8:11] = e.throughput.view(np.uint32)[carried]
         r[e.inside, 11] = e.medium.view(np.uint32)[e.inside]
         r[later, 12] = e.cone_angle.view(np.uint32)[later]; r[later, 13] = e.cone_width.view(np.uint32)[later]
         if garbage is not None:
@@ -431,15 +438,19 @@ class VariantWorld(World):
             assert self.transformed_instance[mine].any() and (~self.transformed_instance[mine]).any(), "type %d: no instance under a rotation and a scale, or none without" % kind
         self.instance_material = ids
         self.map_base = None
+        from texture_cases import bc1_texture_above
+        self.bc1 = bc1_texture_above(16, 16, 7, 64)   # blocks decoded per fetch; 64 / 255 >= ALBEDO_FLOOR in every channel of every texel and level
+        self.bc1_index = len(self.pt.textures())
+        self._oracle_textures = (self.view.keep["tex_table"], self.view.scene.textures, self.view.scene.texture_count)
         if self.ctx is not None:
             self.upload_textures(False)
 
     def upload_textures(self, with_bc1):
-        """World's, with the three constant maps behind: 4 x 4 RGBA8 images with their whole mip chain, every texel the same."""
-        from texture_cases import bc1_texture
+        """World's, with the three constant maps behind: 4 x 4 RGBA8 images with their whole mip chain, every texel the same. The BC1 texture of a bc1
+        setup is self.bc1 (every texel at or above ALBEDO_FLOOR), at index self.bc1_index."""
         from test_gpu_texture_unit import TextureDesc
         scene_textures = self.pt.textures()
-        extra = [bc1_texture(8, 8, 7)] if with_bc1 else []
+        extra = [self.bc1] if with_bc1 else []
         self._maps = [np.ascontiguousarray(np.tile(np.array(list(c) + [255], np.uint8), 16 + 4 + 1)) for c in MAP_TEXELS]
         count = len(scene_textures) + len(extra) + len(self._maps)
         descs = (TextureDesc * count)()
@@ -460,6 +471,34 @@ class VariantWorld(World):
         assert lib.rt_set_texture_expansion(self.ctx, 0 if with_bc1 else 1) == 0, lib.rt_last_error(self.ctx)
         assert lib.rt_upload_textures(self.ctx, descs, count) == 0, lib.rt_last_error(self.ctx)
         self.textures_compressed = with_bc1
+
+    def with_bc1_albedo(self, materials):
+        """The materials table with the textured diffuse and plastic materials' albedo texture replaced by the BC1 texture."""
+        out = materials.copy()
+        textured = (materials[:, 3].view(np.int32) >= 0) & np.isin(self.material_types, (DIFFUSE, PLASTIC))
+        assert {int(t) for t in self.material_types[textured]} == {DIFFUSE, PLASTIC}
+        out[:, 3].view(np.int32)[textured] = self.bc1_index
+        return out
+
+    def oracle_textures(self, with_bc1):
+        """The oracle's texture table: the scene's, and (with_bc1) the BC1 texture behind them as the RGBA8 chain its blocks decode to -- the oracle's
+        unit reads texels, the device's decodes the blocks at every fetch (test_gpu_texture_unit.py holds the two to each other)."""
+        from oracle.binding import OracleTexture
+        from texture_reference import chain_bytes
+        k, s = self.view.keep, self.view.scene
+        table, pointer, count = self._oracle_textures
+        if with_bc1:
+            assert count == self.bc1_index
+            chain = np.ascontiguousarray(chain_bytes(self.bc1.levels()))
+            bigger = (OracleTexture * (count + 1))()
+            for i in range(count):
+                ctypes.memmove(ctypes.byref(bigger[i]), ctypes.byref(table[i]), ctypes.sizeof(OracleTexture))
+            t = bigger[count]
+            t.texels, t.width, t.height, t.mip_levels, t.lod_width, t.lod_height = chain.ctypes.data, self.bc1.width, self.bc1.height, self.bc1.mip_levels, 0, 0
+            k["tex_table_bc1"], k["tex_chain_bc1"] = bigger, chain
+            s.textures, s.texture_count = ctypes.cast(bigger, ctypes.c_void_p), count + 1
+        else:
+            s.textures, s.texture_count = pointer, count
 
     def triangles_where(self, what):
         """Triangle ids by their texture coordinates: "regular" (uv_det > 0), "mirrored" (uv_det < 0), "degenerate" (uv_det == 0); none a sliver."""
@@ -489,6 +528,226 @@ class VariantWorld(World):
         for k in range(base):
             tables.map_texels[k] = "varied"
         return ids
+
+
+    def apply(self, setup):
+        """World's, plus what an InstanceSetup asks for beyond a sky share -- delta lights (tables.delta), the light tree (tables.tree), a fog
+        volume (tables.fog_active) -- on the device and in the tables of material_reference.evaluate; any other setup clears all three."""
+        import delta_light_reference
+        import light_tree_cases
+        import light_tree_reference
+        import material_reference
+        grt, ctx = self.grt, self.ctx
+        delta, tree, fog = getattr(setup, "delta", None), getattr(setup, "tree", False), getattr(setup, "fog", False)
+        albedo = bool(getattr(setup, "bc1_albedo", False))
+        assert not albedo or setup.bc1
+        if ctx is not None:   # (the tree off before the light tables change: it is built again, from the tables in force, when it is enabled below)
+            assert grt.set_light_tree(ctx, False) == 0 and grt.upload_delta_lights(ctx, None) == 0 and grt.set_fog_volume(ctx, None) == 0, self.lib.rt_last_error(ctx)
+            if albedo and not self.textures_compressed:
+                self.upload_textures(True)   # (before the materials that name the texture)
+        scene_materials = self.rough_materials, self.smooth_materials
+        if albedo:
+            self.rough_materials, self.smooth_materials = (self.with_bc1_albedo(m) for m in scene_materials)
+        try:
+            tables = super().apply(setup)
+        finally:
+            self.rough_materials, self.smooth_materials = scene_materials
+            self.materials = self.rough_materials
+        self.oracle_textures(albedo)
+        tables.delta = tables.tree = None
+        tables.fog_active = bool(fog)
+        if delta is not None:
+            table = delta_light_reference.Table(DELTA_LIGHTS, DELTA_WEIGHTS)
+            records = cdf = None
+            if ctx is not None:
+                assert grt.upload_delta_lights(ctx, grt.delta_light_records(DELTA_LIGHTS, DELTA_WEIGHTS), delta) == 0, self.lib.rt_last_error(ctx)
+                records, cdf, share = grt.read_delta_lights(ctx)
+                assert share == np.float32(delta)
+            tables.delta = material_reference.Delta(table, delta, records, cdf)
+        if tree:
+            scene = light_tree_cases.scene_from_pathtracer(self.pt)
+            want = light_tree_reference.build32(scene)
+            nodes, slot_of_leaf, area = want.nodes, want.slot_of_leaf, want.leaves.area
+            if ctx is not None:
+                assert grt.set_light_tree(ctx, True) == 0, self.lib.rt_last_error(ctx)
+                got = grt.read_light_tree(ctx)
+                assert got.leaf_count == want.leaf_count > 0 and np.array_equal(got.nodes.view(np.uint32), want.nodes.view(np.uint32)), "the device's tree is not its restatement"
+                nodes, slot_of_leaf, area = got.nodes, got.slot_of_leaf, got.leaf_area
+            tables.tree = material_reference.TreeTables(scene, light_tree_reference.tree_from_nodes(nodes, want.leaf_count, slot_of_leaf), area)
+        if fog and ctx is not None:
+            assert grt.set_fog_volume(ctx, grt.fog_volume_record(*FOG)) == 0, self.lib.rt_last_error(ctx)
+        return tables
+
+
+# ---- every instance of the material launch (test_gpu_material_instances.py; the conditions on its launches in test_material.py) ----------
+
+# The delta lights of the launch tests: a point light, a spot whose cones cross the scene, a directional light, a second point light
+DELTA_LIGHTS = np.array([[0, 0.5, 3.0, 0.5, 0, 0, 1, 30, 25, 20, 0, 0],
+                         [1, -1.5, 4.0, 1.0, 0.3, -1.0, -0.2, 80, 90, 100, 0.9, 0.5],
+                         [2, 0, 0, 0, -0.3, -1.0, 0.2, 2.0, 2.5, 3.0, 0, 0],
+                         [0, 2.0, 1.5, -1.0, 0, 0, 1, 4, 8, 12, 0, 0]], np.float32)   # delta_light_reference.lights_array rows
+DELTA_WEIGHTS = np.array([3.0, 2.0, 4.0, 1.0], np.float32)
+FOG = ((-6.0, 0.0, -6.0), (6.0, 3.0, 6.0), 0.02, 0.05, 0.3)   # fog_volume_record's arguments: a box around the scene, absorbing and scattering
+LIGHT_SUFFIXES = ("", "_sky", "_split", "_tree")   # by rt_light_split
+
+
+class InstanceSetup(Setup):
+    """Setup plus `delta`: the share rt_upload_delta_lights gives DELTA_LIGHTS (None: no delta lights); `tree`: the light tree on; `fog`: the
+    volume FOG in force; `bc1_albedo` (with bc1): the textured diffuse and plastic materials take the BC1 texture as their albedo, so that the blocks
+    are decoded inside the material kernel."""
+
+    def __init__(self, name, config=None, delta=None, tree=False, fog=False, bc1_albedo=False, **rest):
+        super().__init__(name, config, **rest)
+        self.delta, self.tree, self.fog, self.bc1_albedo = delta, tree, fog, bc1_albedo
+
+
+def light_split(tables):
+    """rt_light_split for the tables of a setup in force: tree > delta share > sky share."""
+    import material_reference
+    nee_on, share, lit, delta, tree, fog = material_reference.settings_in_force(tables)
+    return 3 if tree is not None else 2 if delta is not None else 1 if share > 0 else 0
+
+
+def instance(world, tables, launch):
+    """The __global__ entry point material_kernels_for picks for the launch (kernels_shade.hip): the slot's row (the _texels one of the diffuse and
+    plastic slots while no texture holds compressed blocks), the form, the split in force, the slot's bit of normal_map_slots."""
+    map_ids = getattr(tables, "map_ids", None)
+    mapped = map_ids is not None and bool((map_ids[tables.material_types == SLOT_TYPES[launch.slot]] >= 0).any())
+    return instance_name(launch.slot, launch.merged, launch.slot < 2 and not world.textures_compressed, light_split(tables), mapped)
+
+
+def instance_name(slot, merged, texels, split, mapped):
+    return "kernel_material_" + SLOT_NAMES[slot] + ("_stream" if merged else "") + ("_texels" if texels else "") + LIGHT_SUFFIXES[split] + ("_nmap" if mapped else "")
+
+
+def all_instances():
+    """The 96 names by the rule: 6 rows (four slots, the _texels forms of the first two) x 4 splits x _nmap x 2 forms."""
+    return {instance_name(slot, merged, texels, split, mapped) for slot in range(4) for texels in ((False, True) if slot < 2 else (False,))
+            for split in range(4) for mapped in (False, True) for merged in (False, True)}
+
+
+def listed_instances(path):
+    """The same set read from kernels_shade.hip as text: the rows of RT_MATERIAL_KERNEL_LIST, the suffixes of RT_MATERIAL_KERNEL_VARIANTS, and
+    RT_DEFINE_MATERIAL_KERNELS' two names per pair."""
+    import re
+    text = open(path).read()
+    rows = re.findall(r"^\tX\((\w+),\s*(\w*),\s*\w+(?:<\w+>)?,\s*(\d),", text, re.M)
+    variants = text[text.index("#define RT_MATERIAL_KERNEL_VARIANTS(X)"):text.index("#define RT_DEFINE_MATERIAL_KERNELS")]
+    suffixes = re.findall(r"RT_MATERIAL_KERNEL_LIST\(X, (\w*), (\d), (true|false)\)", variants)
+    assert len(rows) == 6 and len(suffixes) == 8, (rows, suffixes)
+    for suffix, split, mapped in suffixes:   # (a suffix says what its template arguments say)
+        assert suffix == LIGHT_SUFFIXES[int(split)] + ("_nmap" if mapped == "true" else ""), (suffix, split, mapped)
+    for material, texels, slot in rows:
+        assert SLOT_NAMES[int(slot)] == material, (material, slot)
+    return {"kernel_material_%s%s%s%s" % (material, stream, texels, suffix) for material, texels, _ in rows for suffix, _, _ in suffixes for stream in ("", "_stream")}
+
+
+LIGHT_VARIANTS = {   # light variant -> what puts it in force: all three routes under _split and _tree
+    "": dict(),
+    "_sky": dict(sky_sampling=0.25),
+    "_split": dict(sky_sampling=0.25, delta=0.5),
+    "_tree": dict(sky_sampling=0.25, delta=0.5, tree=True),
+}
+# per-bounce, merged: the shortest rung of a ladder of LENGTH_STEP entries a step at which every route in force holds more than 100 robust shadow entries in every
+# launch of INSTANCE_CASES -- found on the CPU from the reference alone (test_material.py: test_instance_launches_are_the_shortest_that_hold_every_route)
+INSTANCE_LENGTHS, LENGTH_STEP = (1250, 1500), 250
+
+
+def instance_setup(variant, compressed=False, **changes):
+    name = "instances%s%s" % (variant or "_plain", "_bc1" if compressed else "") + "".join("_%s" % k for k in sorted(changes) if changes[k])
+    settings = dict(LIGHT_VARIANTS[variant], bc1=compressed, bc1_albedo=compressed)
+    config = {}
+    if changes.pop("mis_off", False):
+        config["enable_multiple_importance_sampling"] = 0
+    if changes.pop("taken0", False):
+        settings.update(sky_sampling=0.0, delta=None)
+    settings.update(changes)
+    return InstanceSetup(name, config, **settings)
+
+
+INSTANCE_ROWS = tuple((slot, compressed) for compressed in (False, True) for slot in ((0, 1, 2, 3) if not compressed else (0, 1)))   # the six rows of RT_MATERIAL_KERNEL_LIST
+
+
+# every (light variant, mapped, slot, compressed) whose two launches make up the 96: the rows that can decode compressed blocks last (the textures are
+# uploaded again when a setup changes that)
+INSTANCE_CASES = [(light, mapped, slot, compressed) for compressed in (False, True) for mapped in (False, True) for light in LIGHT_VARIANTS
+                  for slot, c in INSTANCE_ROWS if c == compressed]
+
+
+def instance_case_id(case):
+    light, mapped, slot, compressed = case
+    return "%s%s-%s%s" % (light.lstrip("_") or "plain", "_nmap" if mapped else "", SLOT_NAMES[slot], "" if compressed or slot >= 2 else "_texels")
+
+
+def instance_launches(world, variant, mapped, slot, compressed, lengths=INSTANCE_LENGTHS, tag="instances"):
+    """One per-bounce launch (bounce 0 and 2 alternate across the rows) and one merged launch of a row: (maps, launch) pairs. A mapped launch draws
+    from the regular and the mirrored triangles, as map_launches does."""
+    row = INSTANCE_ROWS.index((slot, compressed))
+    k = 100 * tuple(LIGHT_VARIANTS).index(variant) + 50 * mapped + 4 * row
+    maps = {SLOT_TYPES[slot]: TILT} if mapped else {}
+    out = [per_bounce(world, tag, slot, lengths[0], (0, 2)[row % 2], seed=6000 + k), merged(world, tag, slot, lengths[1], seed=6001 + k)]
+    if mapped:
+        both = np.concatenate([world.triangles_where("regular"), world.triangles_where("mirrored")])
+        for launch in out:
+            launch.entries.triangle[:] = np.random.default_rng(6002 + k).choice(both, launch.entries.n)
+    return [(maps, launch) for launch in out]
+
+
+def instance_length_launches(world, variant_index):
+    """Order and structure of one light variant: one entry, one wave, a workgroup and one entry; per bounce and merged, over the slots in turn."""
+    out = []
+    for k, n in enumerate(SKY_LENGTHS):
+        out.append(per_bounce(world, "instances_length", (2 * k + variant_index) % 4, n, 1, seed=6500 + 10 * variant_index + k, slots=1))
+        out.append(merged(world, "instances_length", (2 * k + 1 + variant_index) % 4, n, seed=6550 + 10 * variant_index + k))
+    return out
+
+
+def fog_launches(world):
+    """The material launch while a fog volume is in force: bounce 0 per bounce and the merged form, the diffuse and the conductor slot. Every entry
+    carries a throughput of its own, bounce 0 included (the ..._fog sort instance stores it: the first segment may have crossed the fog)."""
+    out = []
+    for slot in (0, 3):
+        for launch in (per_bounce(world, "fog", slot, 1500, 0, seed=6600 + slot), merged(world, "fog", slot, 2500, seed=6610 + slot)):
+            e = launch.entries
+            rng = np.random.default_rng(6620 + slot)
+            first = launch.paths()[2] == 0
+            e.throughput[first] = (rng.uniform(0.2, 0.9, (int(first.sum()), 3)) * rng.uniform(0.3, 1.0, (int(first.sum()), 1))).astype(np.float32)
+            launch.first_throughput = True   # (per_bounce and merged build the plain queue; this one is the fog's)
+            out.append(launch)
+    return out
+
+
+class WideWorld(VariantWorld):
+    """VariantWorld in a frame of 128 x 64 pixels: 8192 x 256 + 1 distinct (slot, pixel) entries fit the slot table's 512 sample slots (257 of them)."""
+    FRAME = (2 * WIDTH, HEIGHT)
+
+
+STREAM_SECOND_ROUND = STREAM_GRID * BLOCK + 1   # merged form: one entry in a second grid-stride round
+
+
+def second_round_merged(world, slot, seed):
+    """8192 x 256 + 1 entries of the merged form: the last one is alone in the second grid-stride round. Every sample slot the entries need has a row in the
+    table, over three submissions at bounces 0, 1 and the last."""
+    rng = np.random.default_rng(seed)
+    n, iteration = STREAM_SECOND_ROUND, NUM_BOUNCES + 3
+    slots = slots_needed(n, world.frame_pixels)
+    assert slots <= 512
+    k = np.arange(slots)
+    submission = np.array([3, 9, 64])[k % 3]
+    birth = np.array([iteration, iteration - 1, iteration - (NUM_BOUNCES - 1)])[k % 3]
+    table = np.stack([1000 + k, birth, submission, k // 3], axis=1).astype(np.int32)
+    births = np.full(SUBMISSIONS, iteration + 1000, np.int32)
+    births[[3, 9, 64]] = [iteration, iteration - 1, iteration - (NUM_BOUNCES - 1)]
+    px = pixels_for(rng, n, world.frame_pixels, slots)
+    bounce = iteration - table[px // world.frame_pixels, 1]
+    e = make_entries(world, rng, px, slot, bounce)
+    return Launch("second_round_%s_merged_%d" % (SLOT_NAMES[slot], n), slot, e, world.frame_pixels, slots, iteration=iteration, slot_table=table, submission_birth=births)
+
+
+def value_sample(n, seed):
+    """At most MAX_VALUE_ENTRIES of n entries: the last 257 and a seeded random sample of the rest."""
+    rest = np.random.default_rng(seed).choice(n - 257, MAX_VALUE_ENTRIES - 257, replace=False)
+    return np.unique(np.concatenate([rest, np.arange(n - 257, n)]))
 
 
 def _restrict(world, launch, what, seed, meshes=None):

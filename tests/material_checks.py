@@ -376,6 +376,8 @@ MEASURED = {
     # the NORMAL frame of a mapped hit: material_reference.mapped_normal32, the float32 restatement of normal_map_perturb, against float64
     # (test_material.py: test_mapped_normal_bound_is_four_times_the_float32_restatement); absolute, per component
     "mapped_normal":    (2.02e-06, "svgf_on/nmap_inward_conductor_bounce0_1500"),
+    # the throughput on the unmapped conductor launches of test_gpu_material_instances.py (test_material.py: test_instance_throughput_bound_is_four_times_the_worst_case)
+    "instance_throughput": (0.0007, "instances_plain/instances_conductor_bounce2_1250"),
 }
 BOUNDS = {q: 4.0 * v[0] for q, v in MEASURED.items()}
 

@@ -29,10 +29,25 @@ The variants of the launch (kernels_shade.hip: the _sky and _nmap instances), co
   of a constant 8-bit image returns it, so no fetch is restated -- in the BSDF frame, omega_i.z <= 0, next-event estimation, the NORMAL
   frame and the g-buffer; the ray cone's curvature term and its dot(normal, direction) keep the interpolated normal. A hit of a varied map
   has no reference value here (`varied`; rt_perturb_normals holds those) and counts as left out.
-Their deciding comparisons carry near flags of their own (near_sky, near_map), counted like the others."""
+* delta lights (the _split instances, next_event_estimation<2>): `tables.delta`, a Delta -- the table of delta_light_reference.py, the P_k and the CDF
+  as the device holds them, and the upload's share. The shares settle as delta_light_reference.split settles them and every allowed entry is
+  routed by delta_light_reference.route, in float32: to the sky below s, to a delta light below taken = s + q, else to the emitters on
+  (u - taken) / (1 - taken), whose pdf carries 1 - taken. A delta entry: the light from the CDF on (u - s) / q, one epsilon offset towards it
+  (against its direction for a directional light), the sample of delta_light_reference.sample from that origin, pdf q P_k, no MIS weight, and
+  a max_distance of +inf exactly for a directional light;
+* the light tree (the _tree instances, next_event_estimation<3>): `tables.tree`, a TreeTables -- the scene, the tree and the leaves' areas as
+  the device holds them (light_tree_reference.py). The routing is the _split instances' (taken may be 0); an emitter entry takes the leaf the
+  descent picks from the hit point on (u', DIM_NEE_LIGHT.y), the point on it from the DIM_NEE_TRIANGLE pair, and
+  pdf = pmf d^2 / (A cos) (1 - taken). The tree is not in force without emitters, with NEE off or under a fog volume.
+`route` says per entry where its light sample goes (ROUTE_SKY, ROUTE_DELTA, ROUTE_POWER, ROUTE_TREE).
+* a fog volume (`tables.fog_active`): shade_material takes bounce 0's throughput from the queue, as every other bounce's.
+Their deciding comparisons carry near flags of their own (near_sky, near_map; near_light takes in the routes' edges, a spot's two cosines, the
+sliver margin of the offset towards a delta light, and a descent of the tree that a few ulps of u would turn), counted like the others."""
 import numpy as np
 
 import bsdf_reference
+import delta_light_reference
+import light_tree_reference
 import nee_reference
 import normal_map_reference
 import sky_sampling_reference
@@ -55,6 +70,30 @@ T_LENGTH_MARGIN = 1e-3   # relative, around normal_map_perturb's |t|^2 > 1e-8 |d
 # the value there to 1 only. A mapped normal leans against the surface, and the view guard pins omega_i.z at 1e-2 for every hit it moves: such
 # samples, rare in an unmapped launch, are a few per thousand mapped hits. They are flagged (mapped hits only) and left out.
 GRAZING = 1e-3
+ROUTE_SKY, ROUTE_DELTA, ROUTE_POWER, ROUTE_TREE = range(4)
+ROUTE_NAMES = ("sky", "delta light", "emitter by power", "emitter by tree")
+# A spot's c = dot(-to_light, axis) against its two cosines: the direction's float32 error grows with 1 / distance (test_gpu_delta_lights.py)
+SPOT_MARGIN = 64 * 2.0 ** -24
+# The epsilon offset towards a delta light follows the sign of dot(toward, geometric normal), `toward` not normalised
+DELTA_SIDE_MARGIN = 64 * DOT_MARGIN
+
+
+class Delta:
+    """`tables.delta`: the delta lights in force. table: delta_light_reference.Table; share: rt_upload_delta_lights' (of what the sky leaves);
+    records, cdf: rt_read_delta_lights' (without a device: the table's own numbers rounded to float32)."""
+
+    def __init__(self, table, share, records=None, cdf=None):
+        self.table, self.share = table, float(share)
+        self.pdf32 = np.asarray(table.pdf if records is None else records[:, 7], np.float32)
+        self.cdf32 = np.asarray(table.cdf if cdf is None else cdf, np.float32)
+
+
+class TreeTables:
+    """`tables.tree`: the light tree in force. scene: light_tree_reference.Scene; tree: the nodes as the device holds them (tree_from_nodes of
+    rt_read_light_tree, or build32's without a device: bit-identical); leaf_area: float32 per leaf id."""
+
+    def __init__(self, scene, tree, leaf_area):
+        self.scene, self.tree, self.leaf_area = scene, tree, np.asarray(leaf_area, np.float32)
 
 
 class Result:
@@ -108,6 +147,28 @@ def map_records(tri, u, v, world_m, direction):
     rec[:, 26:38] = world_m.reshape(-1, 12)
     rec[:, 38:41] = direction
     return rec
+
+
+def settings_in_force(tables):
+    """What decides the light variant of a launch, as sky_sampling_prepare and rt_light_tree_in_force settle it: (NEE on, the sky's share, emitters
+    exist, tables.delta or None, tables.tree or None, a fog volume is in force). No delta lights with NEE off; no tree without NEE, without emitters, or under fog."""
+    nee_on = tables.config["enable_next_event_estimation"] != 0
+    share = np.float64(np.float32(tables.sky_share)) if nee_on else 0.0   # the _sky instances: RtParams::sky_nee_share
+    lit = tables.lights_total_weight > 0.0
+    fog = bool(getattr(tables, "fog_active", False))
+    delta = getattr(tables, "delta", None) if nee_on else None
+    tree = getattr(tables, "tree", None) if nee_on and lit and not fog else None
+    return nee_on, share, lit, delta, tree, fog
+
+
+def route_in_force(tables, route):
+    """Whether light samples of a launch under `tables` can take `route`."""
+    nee_on, share, lit, delta, tree, fog = settings_in_force(tables)
+    taken = share
+    if delta is not None or tree is not None:
+        taken = np.float64(delta_light_reference.split(np.float32(share), delta.share if delta is not None else 0.0, lit)[2])
+    return bool(nee_on and {ROUTE_SKY: share > 0.0, ROUTE_DELTA: delta is not None and taken > share, ROUTE_POWER: lit and taken < 1.0 and tree is None,
+                            ROUTE_TREE: lit and taken < 1.0 and tree is not None}[route])
 
 
 def evaluate(world, tables, launch, bsdf_tables, sky_directions=None, sky_pdfs=None, map_ids=None, map_texels=None):
@@ -210,7 +271,8 @@ def evaluate(world, tables, launch, bsdf_tables, sky_directions=None, sky_pdfs=N
         textured = world.textured_instance[e.mesh]
         if kind in (bsdf_reference.DIFFUSE, bsdf_reference.PLASTIC):
             materials[:, 3] = np.array([INVALID], np.int32).view(np.float32)[0]
-        throughput_in = np.where(first[:, None], 1.0, e.throughput.astype(f64))
+        fog = settings_in_force(tables)[5]   # (the ..._fog sort instance has stored bounce 0's throughput too)
+        throughput_in = e.throughput.astype(f64) if fog else np.where(first[:, None], 1.0, e.throughput.astype(f64))
         svgf_first = (cfg["enable_svgf"] != 0) & first
         albedo = materials[:, :3].astype(f64)
         if kind == bsdf_reference.DIFFUSE:   # calc_albedo: the diffuse BSDF's albedo goes into the throughput at once, unless SVGF demodulates the first hit
@@ -240,30 +302,49 @@ def evaluate(world, tables, launch, bsdf_tables, sky_directions=None, sky_pdfs=N
             r.medium = inside_in
 
         # next-event estimation (Pathtracer.cu:465-555): the light the random numbers select, then the tail
-        share = f64(np.float32(tables.sky_share)) if cfg["enable_next_event_estimation"] != 0 else 0.0   # the _sky instances: RtParams::sky_nee_share
-        emitters = tables.lights_total_weight > 0.0 and share < 1.0
-        nee = (cfg["enable_next_event_estimation"] != 0) and (tables.lights_total_weight > 0.0 or share > 0.0)
+        nee_on, share, lit, delta, tree, fog = settings_in_force(tables)
+        split = delta is not None or tree is not None   # the _split and _tree instances: three routes
+        taken = share
+        if split:
+            s32, q32, taken32 = delta_light_reference.split(np.float32(share), delta.share if delta is not None else 0.0, lit)
+            taken = f64(taken32)
+        emitters = lit and taken < 1.0
+        nee = nee_on and (lit or share > 0.0 or delta is not None)
         r.has_shadow = np.zeros(n, bool); r.near_light = np.zeros(n, bool); r.near_sky = np.zeros(n, bool); r.to_sky = np.zeros(n, bool)
         r.shadow_origin = np.full((n, 3), np.nan); r.shadow_direction = np.full((n, 3), np.nan); r.shadow_distance = np.full(n, np.nan); r.illumination = np.full((n, 3), np.nan)
         r.u_emitter = np.full(n, np.nan, np.float32); r.sky_direction = np.full((n, 3), np.nan); r.sky_pdf = np.full(n, np.nan); r.light_pdf = np.full(n, np.nan)
+        r.route = np.full(n, ROUTE_TREE if tree is not None else ROUTE_POWER, np.int8); r.to_delta = np.zeros(n, bool)
         if nee and n:
             rl, rt = tables.random(DIM_NEE_LIGHT, real, bounce, sample), tables.random(DIM_NEE_TRIANGLE, real, bounce, sample)
             allowed = alive & s64.allow_nee
-            to_sky = np.zeros(n, bool)
+            to_sky = np.zeros(n, bool); to_delta = np.zeros(n, bool); near_route = np.zeros(n, bool)
             u_light = rl[:, 0].astype(f64)
-            if share > 0.0:
+            if split:
+                where, u_delta, r.u_emitter = delta_light_reference.route(rl[:, 0], s32, q32, taken32)
+                to_sky, to_delta = where == 0, where == 1
+                rl = rl.copy(); rl[:, 0] = np.where(where == 2, r.u_emitter, 0.0)
+                selection = f64(np.float32(1) - taken32)
+                if q32 > 0:
+                    near_route |= np.abs(u_light - taken) <= f64(np.spacing(taken32))
+            elif share > 0.0:
                 to_sky, r.u_emitter = route(rl[:, 0], share)
                 if not emitters:
                     to_sky = np.ones(n, bool)
                 rl = rl.copy(); rl[:, 0] = np.where(to_sky, 0.0, r.u_emitter)
-            selection = f64(np.float32(1) - np.float32(share))   # `selection` of nee_connect<true>: 1.0f - share
-            r.to_sky = to_sky
+            if not split:
+                selection = f64(np.float32(1) - np.float32(share))   # `selection` of nee_connect<true>: 1.0f - share
+            r.to_sky, r.to_delta = to_sky, to_delta
+            r.route = np.where(to_sky, ROUTE_SKY, np.where(to_delta, ROUTE_DELTA, r.route)).astype(np.int8)
 
             # the emitters' half: the light the (rescaled) random numbers select, then both epsilon offsets
             origin = np.full((n, 3), np.nan); to_light = np.full((n, 3), np.nan); distance = np.full(n, np.nan); light_pdf = np.full(n, np.nan)
             radiance = np.full((n, 3), np.nan); near_half = np.zeros(n, bool)
             if emitters:
-                light = nee_reference.sample_lights(nee_reference.Tables(tables.view), np.concatenate([rl, rt], axis=1))
+                if tree is not None:   # the leaf the descent picks from the un-offset hit point, the point on it as nee_pick_light takes it
+                    leaf, pmf, robust_pick = light_tree_reference.pick_leaves(tree.tree, position, rl[:, 0], rl[:, 1])
+                    light = light_tree_reference.lights_on_leaves(tree.scene, leaf, rt)
+                else:
+                    light = nee_reference.sample_lights(nee_reference.Tables(tables.view), np.concatenate([rl, rt], axis=1))
                 hit = _offset(position, light.point - position, gn)
                 light_point = _offset(light.point, hit - light.point, light.normal)
                 to_light = light_point - hit
@@ -271,8 +352,11 @@ def evaluate(world, tables, launch, bsdf_tables, sky_directions=None, sky_pdfs=N
                 to_light = to_light / distance[:, None]
                 cos_light = np.abs(_dot(to_light, light.normal))
                 power = f64(np.float32(0.299)) * light.emission[:, 0] + f64(np.float32(0.587)) * light.emission[:, 1] + f64(np.float32(0.114)) * light.emission[:, 2]
-                light_pdf = power * distance * distance / (cos_light * tables.lights_total_weight)
-                if share > 0.0:
+                if tree is not None:
+                    light_pdf = pmf * distance * distance / (tree.leaf_area[leaf].astype(f64) * cos_light)
+                else:
+                    light_pdf = power * distance * distance / (cos_light * tables.lights_total_weight)
+                if share > 0.0 or split:
                     light_pdf = light_pdf * selection
                 valid = np.isfinite(light_pdf) & (light_pdf > 1e-4)
                 origin, radiance = hit, light.emission
@@ -280,8 +364,27 @@ def evaluate(world, tables, launch, bsdf_tables, sky_directions=None, sky_pdfs=N
                 near_half = ((np.abs(light_pdf - 1e-4) <= PDF_MARGIN * 1e-4 * (1.0 + 1.0 / cos_light))
                              | ~(np.abs(_dot(light.point - position, gn)) > DOT_MARGIN * sliver * distance)
                              | ~(np.abs(_dot(hit - light.point, light.normal)) > DOT_MARGIN * distance))
+                if tree is not None:
+                    near_half |= ~robust_pick
+                    r.tree_leaf = leaf
             else:
                 valid = np.zeros(n, bool)
+
+            # the delta lights' share: the light from the CDF, one offset on the hit's side, the sample the light offers that origin; no MIS weight
+            if delta is not None:
+                table = delta.table
+                picked = delta_light_reference.select(delta.cdf32, np.where(to_delta, u_delta, 0.0))
+                toward = np.where((table.type[picked] == delta_light_reference.DIRECTIONAL)[:, None], -table.direction[picked], table.position[picked] - position)
+                delta_origin = _offset(position, toward, gn)
+                smp = delta_light_reference.sample(table, picked, delta_origin)
+                delta_pdf = f64(q32) * delta.pdf32[picked].astype(f64)
+                near_delta = (((table.type[picked] == delta_light_reference.SPOT) & (smp.margin <= SPOT_MARGIN * (1.0 + 1.0 / np.maximum(smp.distance, 1e-3))))
+                              | ~(np.abs(_dot(toward, gn)) > DELTA_SIDE_MARGIN * np.sqrt(_dot(toward, toward))))
+                k = to_delta[:, None]
+                origin = np.where(k, delta_origin, origin); to_light = np.where(k, smp.to_light, to_light); distance = np.where(to_delta, smp.distance, distance)
+                light_pdf = np.where(to_delta, delta_pdf, light_pdf); valid = np.where(to_delta, smp.ok & np.isfinite(delta_pdf) & (delta_pdf > 0.0), valid)
+                radiance = np.where(k, smp.radiance, radiance); near_half = np.where(to_delta, near_delta, near_half)
+                r.delta_light = np.where(to_delta, picked, -1)
 
             # the sky's half: the direction and its cell's pdf from the DIM_NEE_TRIANGLE pair, one offset, a ray to infinity
             if share > 0.0:
@@ -306,16 +409,15 @@ def evaluate(world, tables, launch, bsdf_tables, sky_directions=None, sky_pdfs=N
                     seen = np.asarray(sky_pdfs, f64)
                     on_border |= np.isfinite(seen) & ~(np.abs(seen - pdf_sky) <= 1e-5 * pdf_sky)
                 one_ulp = f64(np.spacing(np.float32(share)))
-                near_route = emitters & (np.abs(u_light - share) <= one_ulp)
+                near_route |= (emitters | (delta is not None)) & (np.abs(u_light - share) <= one_ulp)
                 near_sky_half = (on_border | ~(np.abs(_dot(to_sky_direction, gn)) > DOT_MARGIN * sliver))
                 k = to_sky[:, None]
                 origin = np.where(k, sky_origin, origin); to_light = np.where(k, to_sky_direction, to_light); distance = np.where(to_sky, np.inf, distance)
                 light_pdf = np.where(to_sky, sky_light_pdf, light_pdf); valid = np.where(to_sky, sky_valid, valid)
                 radiance = np.where(k, sky_sampling_reference.sample_sky(tables.sky, tables.sky_scale, to_sky_direction), radiance)
-                near_half = np.where(to_sky, near_sky_half, near_half) | near_route
-                cos_margin = np.where(to_sky, 4 * DOT_MARGIN, DOT_MARGIN)
-            else:
-                cos_margin = DOT_MARGIN
+                near_half = np.where(to_sky, near_sky_half, near_half)
+            near_half = near_half | near_route
+            cos_margin = np.where(to_sky | to_delta, 4 * DOT_MARGIN, DOT_MARGIN)
 
             # the tail (nee_finish): the BSDF towards the sample, the MIS weight, the illumination
             cos_hit = _dot(to_light, normal)
@@ -325,6 +427,8 @@ def evaluate(world, tables, launch, bsdf_tables, sky_directions=None, sky_pdfs=N
             r.near_light = allowed & (e64.near | (np.abs(cos_hit) <= cos_margin) | near_half)
             r.near_sky = r.near_light & to_sky
             weight = light_pdf ** 2 / (light_pdf ** 2 + e64.pdf ** 2) if cfg["enable_multiple_importance_sampling"] else 1.0
+            if delta is not None:   # (no BSDF-sampled ray finds a delta light)
+                weight = np.where(to_delta, 1.0, weight)
             illumination = throughput * e64.value * radiance * np.asarray(weight)[..., None] / light_pdf[:, None]
             r.shadow_origin, r.shadow_direction, r.shadow_distance = origin, to_light, distance
             r.illumination = np.where(textured[:, None], np.nan, illumination)

@@ -20,6 +20,7 @@ import pytest
 
 import delta_light_cases as cases
 import delta_light_reference as ref
+from material_cases import DELTA_LIGHTS, DELTA_WEIGHTS   # the launch tests' delta lights, shared with test_gpu_material_instances.py
 from delta_light_reference import POINT, SPOT, DIRECTIONAL, ONE_BELOW_ONE
 
 pytestmark = pytest.mark.gpu
@@ -483,53 +484,21 @@ def world(grt, oracle, tmp_path_factory):
     w.close()
 
 
-WORLD_LIGHTS = ref.lights_array([
-    (POINT, (0.5, 3.0, 0.5), (0, 0, 1), (30, 25, 20), 0, 0),
-    (SPOT, (-1.5, 4.0, 1.0), (0.3, -1.0, -0.2), (80, 90, 100), 0.9, 0.5),
-    (DIRECTIONAL, (0, 0, 0), (-0.3, -1.0, 0.2), (2.0, 2.5, 3.0), 0, 0),
-    (POINT, (2.0, 1.5, -1.0), (0, 0, 1), (4, 8, 12), 0, 0),
-])
-WORLD_WEIGHTS = np.array([3.0, 2.0, 4.0, 1.0], np.float32)
-
-
-def _delta_expectation(world, tables, launch, table, records, cdf, s, q, taken):
-    """Per entry of a material launch: where its light sample goes, and for those that go to a delta light the shadow entry in float64."""
-    import bsdf_reference
+def _delta_expectation(world, tables, launch, sky_share, share):
+    """Per entry of a material launch: where its light sample goes, and its shadow entry in float64 -- material_reference.evaluate with the delta lights
+    (the table in float64, the P_k and the CDF read back from the device) and the sky's share in its tables: the one restatement of every instance."""
+    import copy
     import material_reference as mref
-    e, n = launch.entries, launch.entries.n
-    slot, real, bounce, sample, submission = launch.paths()
-    r = mref.evaluate(world, tables, launch, world.bsdf_tables)
-    rl = tables.random(mref.DIM_NEE_LIGHT, real, bounce, sample)
-    where, u_delta, u_emitter = ref.route(rl[:, 0], s, q, taken)
-    index = ref.select(cdf, np.where(where == 1, u_delta, 0.0))
-    toward = np.where((table.type[index] == DIRECTIONAL)[:, None], -table.direction[index], table.position[index] - r.position)
-    origin = mref._offset(r.position, toward, r.geometric_normal)
-    smp = ref.sample(table, index, origin)
-    cos_hit = (smp.to_light * r.normal).sum(axis=1)
-    kind = mref.DIFFUSE + launch.slot
-    materials = tables.materials[tables.material_ids[e.mesh]].copy()
-    if kind in (bsdf_reference.DIFFUSE, bsdf_reference.PLASTIC):
-        materials[:, 3] = np.array([-1], np.int32).view(np.float32)[0]
-    probes = mref._probes(materials, r.normal, e.direction.astype(np.float64), r.entering, real, sample, bounce, to_light=smp.to_light, cos_o=cos_hit)
-    e64, _ = bsdf_reference.evaluate(kind, probes, world.bsdf_tables, eval=True)
-    first = bounce == 0
-    throughput_in = np.where(first[:, None], 1.0, e.throughput.astype(np.float64))
-    if kind == bsdf_reference.DIFFUSE:
-        svgf_first = (tables.config["enable_svgf"] != 0) & first
-        throughput = np.where(svgf_first[:, None], throughput_in, throughput_in * materials[:, :3].astype(np.float64))
-    else:
-        throughput = throughput_in
-    pdf = float(q) * records[index, 7].astype(np.float64)
-    with np.errstate(all="ignore"):
-        illumination = throughput * e64.value * smp.radiance / pdf[:, None]
-    allowed = r.alive & r.allow_nee
-    has_shadow = allowed & (where == 1) & (e64.ok == 1) & smp.ok
-    sliver_margin = mref.DOT_MARGIN * 64
-    near = (r.near_entering | r.near_alive | e64.near | (np.abs(cos_hit) <= mref.DOT_MARGIN * 4)
-            | ((table.type[index] == SPOT) & (smp.margin <= 64 * EPS * (1.0 + 1.0 / np.maximum(smp.distance, 1e-3))))
-            | ~(np.abs((toward * r.geometric_normal).sum(axis=1)) > sliver_margin * np.linalg.norm(toward, axis=1)))
-    return dict(r=r, where=where, u_emitter=u_emitter, index=index, origin=origin, sample=smp, illumination=illumination, has_shadow=has_shadow,
-                allowed=allowed, robust=~near, textured=r.textured)
+    import sky_sampling_reference
+    with_delta = copy.copy(tables)
+    with_delta.sky_share = float(np.float32(sky_share))
+    with_delta.sky_tables = sky_sampling_reference.Tables(tables.sky) if sky_share > 0 else None
+    records, cdf, _ = world.grt.read_delta_lights(world.ctx)
+    with_delta.delta = mref.Delta(ref.Table(DELTA_LIGHTS, DELTA_WEIGHTS), share, records, cdf)
+    r = mref.evaluate(world, with_delta, launch, world.bsdf_tables)
+    where = np.where(r.route == mref.ROUTE_SKY, 0, np.where(r.route == mref.ROUTE_DELTA, 1, 2))
+    return dict(r=r, where=where, u_emitter=r.u_emitter, origin=r.shadow_origin, to_light=r.shadow_direction, distance=r.shadow_distance, illumination=r.illumination,
+                has_shadow=r.has_shadow, allowed=r.alive & r.allow_nee, robust=r.robust, textured=r.textured)
 
 
 def _check_delta_entries(name, launch, got, shadow_at, x, bounds):
@@ -541,14 +510,13 @@ def _check_delta_entries(name, launch, got, shadow_at, x, bounds):
     assert not wrong.any(), "%s: entry %d: a shadow ray %s, float64 says otherwise" % (name, np.nonzero(wrong)[0][0], "is emitted" if emitted[np.nonzero(wrong)[0][0]] else "is missing")
     index = np.nonzero(mine & emitted)[0]
     f = got.shadow_out[shadow_at[index]].view(np.float32).astype(np.float64)
-    smp = x["sample"]
     errors = {
         "shadow_origin": mc._point(f[:, 0:3], x["origin"][index]),
-        "shadow_direction": np.abs(f[:, 3:6] - smp.to_light[index]).max(axis=1),
+        "shadow_direction": np.abs(f[:, 3:6] - x["to_light"][index]).max(axis=1),
     }
-    finite = np.isfinite(smp.distance[index])
+    finite = np.isfinite(x["distance"][index])
     assert np.array_equal(np.isposinf(f[:, 6]), ~finite), "%s: RT_INFINITY exactly for the directional lights' shadow rays" % name
-    errors["shadow_distance"] = mc._relative(f[finite, 6], smp.distance[index][finite], 1e-30)
+    errors["shadow_distance"] = mc._relative(f[finite, 6], x["distance"][index][finite], 1e-30)
     plain = ~x["textured"][index]
     errors["illumination"] = mc._per_channel(f[plain, 7:10], x["illumination"][index][plain])
     worst = {k: float(v.max(initial=0)) for k, v in errors.items()}
@@ -563,17 +531,15 @@ def test_material_launch_under_a_delta_only_table(grt, world, slot):
     import material_cases as mcases
     import material_checks as mc
     tables = world.apply(mcases.SETUP["no_lights"])
-    table = ref.Table(WORLD_LIGHTS, WORLD_WEIGHTS)
     try:
-        assert grt.upload_delta_lights(world.ctx, grt.delta_light_records(WORLD_LIGHTS, WORLD_WEIGHTS), 0.5) == 0, world.lib.rt_last_error(world.ctx)
-        records, cdf, _ = grt.read_delta_lights(world.ctx)
+        assert grt.upload_delta_lights(world.ctx, grt.delta_light_records(DELTA_LIGHTS, DELTA_WEIGHTS), 0.5) == 0, world.lib.rt_last_error(world.ctx)
         s, q, taken = ref.split(0.0, 0.5, emitters=False)
         launches = [mcases.per_bounce(world, "delta", slot, 1500, b, seed=3100 + 10 * slot + b) for b in (0, 2)] + [mcases.merged(world, "delta", slot, 2500, seed=3150 + slot)]
         for launch in launches:
             name = "delta_only/" + launch.name
             got = mc.device_launch(grt, world.ctx, launch, capacity=launch.entries.n + 37)
             trace_at, shadow_at = mc.match(launch, got, name)
-            x = _delta_expectation(world, tables, launch, table, records, cdf, s, q, taken)
+            x = _delta_expectation(world, tables, launch, 0.0, 0.5)
             assert (x["where"] == 1).all()
             count, left_out, worst = _check_delta_entries(name, launch, got, shadow_at, x, mc.BOUNDS)
             assert count > 200 and left_out <= mc.NON_ROBUST_CAP * launch.entries.n, (name, count, left_out)
@@ -602,20 +568,19 @@ def test_material_launch_splits_its_light_samples(grt, world, sky_share):
     assert ref.split(0.25, float(ONE_BELOW_ONE), True) == (np.float32(0.25), np.float32(0.75), np.float32(1))   # (next to 1 is 1: taken is not the float below it)
     setup = mcases.SETUP["mis_off"]
     tables = world.apply(setup)
-    table = ref.Table(WORLD_LIGHTS, WORLD_WEIGHTS)
     lib = world.lib
     lib.rt_set_sky_sampling.argtypes = [c_void_p, c_float]
     try:
-        assert grt.upload_delta_lights(world.ctx, grt.delta_light_records(WORLD_LIGHTS, WORLD_WEIGHTS), 0.5) == 0, lib.rt_last_error(world.ctx)
+        assert grt.upload_delta_lights(world.ctx, grt.delta_light_records(DELTA_LIGHTS, DELTA_WEIGHTS), 0.5) == 0, lib.rt_last_error(world.ctx)
         assert lib.rt_set_sky_sampling(world.ctx, sky_share) == 0
-        records, cdf, _ = grt.read_delta_lights(world.ctx)
         s, q, taken = ref.split(sky_share, 0.5, emitters=True)
         launch = mcases.per_bounce(world, "split", 0, 3000, 1, seed=3300)
         name = "split_%g/%s" % (sky_share, launch.name)
         got = mc.device_launch(grt, world.ctx, launch, capacity=launch.entries.n + 37)
         trace_at, shadow_at = mc.match(launch, got, name)
-        x = _delta_expectation(world, tables, launch, table, records, cdf, s, q, taken)
+        x = _delta_expectation(world, tables, launch, sky_share, 0.5)
         where = x["where"]
+        assert np.array_equal(where, ref.route(tables.random(mref.DIM_NEE_LIGHT, *launch.paths()[1:4])[:, 0], s, q, taken)[0])
         assert all((where == k).sum() > 100 for k in ((0, 1, 2) if sky_share > 0 else (1, 2))), np.bincount(where)
         count, left_out, worst = _check_delta_entries(name, launch, got, shadow_at, x, mc.BOUNDS)
         # the emitters' share: the plain launch's reference on the rescaled number, illumination / (1 - taken)
@@ -730,7 +695,7 @@ def test_sort_launch_weighs_emitter_hits_with_one_minus_taken(grt, sort_world, s
     setup = scases.SETUP[setup_name]
     tables = world.apply(setup)
     try:
-        assert grt.upload_delta_lights(world.ctx, grt.delta_light_records(WORLD_LIGHTS, WORLD_WEIGHTS), share) == 0, world.lib.rt_last_error(world.ctx)
+        assert grt.upload_delta_lights(world.ctx, grt.delta_light_records(DELTA_LIGHTS, DELTA_WEIGHTS), share) == 0, world.lib.rt_last_error(world.ctx)
         if share == float(ONE_BELOW_ONE):   # s + (1 - s) share is the float below 1: taken is 1 all the same, or a light sample would reach the emitters with a weight of 1.7e7
             assert np.float32(0.25) + np.float32(np.float32(0.75) * ONE_BELOW_ONE) == ONE_BELOW_ONE
         s, q, taken = ref.split(setup.sky_sampling, share, emitters=True)
@@ -762,7 +727,7 @@ def test_sort_launch_adds_a_sky_miss_whole_without_sky_sampling(grt, sort_world,
     setup = scases.SETUP[setup_name]
     tables = world.apply(setup)
     try:
-        assert grt.upload_delta_lights(world.ctx, grt.delta_light_records(WORLD_LIGHTS, WORLD_WEIGHTS), 0.5) == 0, world.lib.rt_last_error(world.ctx)
+        assert grt.upload_delta_lights(world.ctx, grt.delta_light_records(DELTA_LIGHTS, DELTA_WEIGHTS), 0.5) == 0, world.lib.rt_last_error(world.ctx)
         assert tables.sky_share == setup.sky_sampling
         for launch in _sort_launches(world, (scases.MISS,), 4200):
             e = launch.entries

@@ -384,11 +384,12 @@ def test_tree_on_against_off_same_mean_less_noise(grt, tmp_path):
 
 
 # ---- the launches, entry by entry ----------------------------------------------------------------------------------------------------------
-# rt_shade_rays and rt_sort_rays with the tree in force take the _tree instances. Their float64 restatements are the plain launches' (material_reference.py,
-# sort_reference.py) with two substitutions from light_tree_reference.py: the light a hit's numbers select is the leaf the descent picks from the hit point, and
-# lights_total_weight is, per entry, Y A / pmf -- so that Y d^2 / (cos W) is pmf d^2 / (A cos). The tolerances are material_checks.BOUNDS and sort_checks.BOUNDS.
+# rt_shade_rays and rt_sort_rays with the tree in force take the _tree instances. The material launch's float64 restatement is material_reference.evaluate with the
+# tree in its tables (tables.tree: the leaf the descent picks from the hit point, pdf = pmf d^2 / (A cos) (1 - taken)). The sort launch's is the plain one
+# (sort_reference.py) with lights_total_weight, per entry, Y A / pmf -- so that Y d^2 / (cos W) is pmf d^2 / (A cos). The tolerances are material_checks.BOUNDS and sort_checks.BOUNDS.
 
 WORLD_DELTA = [(0, (0.5, 3.0, 0.5), (0, 0, 1), (30, 25, 20), 0, 0), (0, (2.0, 1.5, -1.0), (0, 0, 1), (4, 8, 12), 0, 0)]   # two point lights (delta_light_reference.lights_array rows)
+WORLD_DELTA_WEIGHTS = np.array([1.0, 2.0], F)
 
 
 def _tree_of(grt, world):
@@ -408,7 +409,7 @@ def _shares(grt, world, sky_share, delta):
     if delta:
         lights = dref.lights_array(WORLD_DELTA)
         share = 0.5 if delta is True else float(delta)
-        assert grt.upload_delta_lights(world.ctx, grt.delta_light_records(lights, np.array([1.0, 2.0], F)), share) == 0, world.lib.rt_last_error(world.ctx)
+        assert grt.upload_delta_lights(world.ctx, grt.delta_light_records(lights, WORLD_DELTA_WEIGHTS), share) == 0, world.lib.rt_last_error(world.ctx)
         return dref.split(sky_share, share, emitters=True)
     return F(sky_share), F(0), F(sky_share)
 
@@ -432,15 +433,14 @@ def material_world(grt, oracle, tmp_path_factory):
 
 @pytest.mark.parametrize("sky_share,delta,mis", [(0.0, False, True), (0.0, False, False), (0.25, False, True), (0.0, True, True), (0.25, True, False)],
                          ids=["taken0", "taken0_mis_off", "sky", "delta", "sky_delta_mis_off"])
-def test_material_launch_with_the_tree_carries_the_restated_shadow_rays(grt, material_world, monkeypatch, sky_share, delta, mis):
+def test_material_launch_with_the_tree_carries_the_restated_shadow_rays(grt, material_world, sky_share, delta, mis):
     """A _tree material launch (diffuse hits, per-bounce at bounces 0 and 2 and merged): the shadow ray of every hit whose light sample goes to the emitters carries
     throughput f L w / pdf of the float64 restatement with pdf = pmf d^2 / (A cos)(1 - taken), from the restated origin in the restated direction. Entries whose pick is
     not robust (u within 64 ulps of a node's boundary) or that the plain restatement flags are left out, at most material_checks.NON_ROBUST_CAP of a launch."""
-    import copy
+    import delta_light_reference as dref
     import material_cases as mcases
     import material_checks as mc
     import material_reference as mref
-    import nee_reference
     world = material_world
     tables = world.apply(mcases.SETUP["default" if mis else "mis_off"])
     try:
@@ -452,26 +452,16 @@ def test_material_launch_with_the_tree_carries_the_restated_shadow_rays(grt, mat
             name = "tree_%s/%s" % ("mis" if mis else "nomis", launch.name)
             got = mc.device_launch(grt, world.ctx, launch, capacity=launch.entries.n + 37)
             trace_at, shadow_at = mc.match(launch, got, name)
-            with_taken = _with_share(tables, taken)
-            plain = mref.evaluate(world, with_taken, launch, world.bsdf_tables)       # pass 1: the hit points, the route, the rescaled numbers
+            under_tree = _with_share(tables, s_)   # the one restatement of every instance: the sky's share, the delta lights and the tree in its tables
+            under_tree.delta = mref.Delta(dref.Table(dref.lights_array(WORLD_DELTA), WORLD_DELTA_WEIGHTS), 0.5 if delta is True else float(delta), *grt.read_delta_lights(world.ctx)[:2]) if delta else None
+            under_tree.tree = mref.TreeTables(s, tree, got_tree.leaf_area)
+            r = mref.evaluate(world, under_tree, launch, world.bsdf_tables)
+            to_emitters = r.route == mref.ROUTE_TREE
             slot_, real, bounce, sample, submission = launch.paths()
-            rl = tables.random(mref.DIM_NEE_LIGHT, real, bounce, sample)
-            u = plain.u_emitter if float(taken) > 0 else rl[:, 0]
-            to_emitters = ~plain.to_sky if float(taken) > 0 else np.ones(launch.entries.n, bool)
-            if delta:   # u in [s, taken) goes to a delta light on the device; the restatement under share = taken calls it sky: neither is compared here
-                to_emitters &= ~(rl[:, 0] < taken)
-            u = np.where(to_emitters, np.nan_to_num(u), 0.0).astype(F)
-            leaf, pmf, robust_pick = ref.pick_leaves(tree, plain.position, u, rl[:, 1])
-            emission = s.materials[s.material_ids[s.leaf_table()[3][leaf]], :3].astype(np.float64)
-            y = np.float64(F(0.299)) * emission[:, 0] + np.float64(F(0.587)) * emission[:, 1] + np.float64(F(0.114)) * emission[:, 2]
-            with np.errstate(all="ignore"):
-                weights = ref.PerEntry(np.where(pmf > 0, y * got_tree.leaf_area[leaf].astype(np.float64) / pmf, np.inf))
-            under_tree = copy.copy(with_taken); under_tree.lights_total_weight = weights
-            monkeypatch.setattr(nee_reference, "sample_lights", lambda _tables, probes: ref.lights_on_leaves(s, leaf, np.asarray(probes, F).reshape(-1, 4)[:, 2:4]))
-            r = mref.evaluate(world, under_tree, launch, world.bsdf_tables)           # pass 2: the tail under the tree's light and pdf
-            monkeypatch.undo()
-            mine = to_emitters & r.alive & r.allow_nee & r.robust & robust_pick
-            left_out = int((to_emitters & r.alive & r.allow_nee & ~(r.robust & robust_pick)).sum())
+            assert np.array_equal(to_emitters, ~(tables.random(mref.DIM_NEE_LIGHT, real, bounce, sample)[:, 0] < taken))   # (u below taken goes to the sky or a delta light)
+            leaf = r.tree_leaf
+            mine = to_emitters & r.alive & r.allow_nee & r.robust
+            left_out = int((to_emitters & r.alive & r.allow_nee & ~r.robust).sum())
             emitted = shadow_at >= 0
             wrong = mine & (emitted != r.has_shadow)
             assert not wrong.any(), "%s: entry %d: a shadow ray %s, float64 says otherwise" % (name, np.nonzero(wrong)[0][0], "is emitted" if emitted[np.nonzero(wrong)[0][0]] else "is missing")

@@ -1,5 +1,5 @@
 """The variants of the material launch on the device, entry by entry: the _sky, _nmap and _sky_nmap instances that rt_launch_material and
-rt_launch_material_stream pick through material_kernels_for ([(NMAP * 3 + SKY) * rows + row]) when the sky takes a share of the light samples
+rt_launch_material_stream pick through material_kernels_for ([(NMAP * 4 + SKY) * rows + row]) when the sky takes a share of the light samples
 (rt_set_sky_sampling) or a material of the slot has a normal map (rt_upload_material_normal_maps), run by rt_shade_rays on the launches of
 material_cases.py (VariantWorld) and held to the float64 composition of material_reference.py. The oracle samples no sky and knows no normal
 map: float64 is the only reference here, as for the delta lights.
@@ -58,16 +58,7 @@ def timed(request):
     print("%s: %.2f s" % (request.node.name, time.perf_counter() - start))
 
 
-def instance(world, tables, launch):
-    """The __global__ entry point material_kernels_for picks for the launch (kernels_shade.hip)."""
-    name = "kernel_material_" + cases.SLOT_NAMES[launch.slot] + ("_stream" if launch.merged else "")
-    if launch.slot < 2 and not world.textures_compressed:
-        name += "_texels"
-    name += "_sky" if tables.sky_share > 0 else ""
-    map_ids = getattr(tables, "map_ids", None)
-    if map_ids is not None and (map_ids[tables.material_types == cases.SLOT_TYPES[launch.slot]] >= 0).any():
-        name += "_nmap"
-    return name
+instance = cases.instance   # the __global__ entry point material_kernels_for picks for a launch: any of the 96 (material_cases.py)
 
 
 def device_random(world, dimension, launch):
@@ -106,24 +97,33 @@ def sky_directions(world, name, tables, launch, got, shadow_at, r):
     return directions, pdfs, far, float(apart[apart <= INVERSION_BOUND].max(initial=0.0))
 
 
-def run(world, setup_name, tables, launch, sides=True, bounds=checks.BOUNDS):
+def run(world, setup_name, tables, launch, sides=True, bounds=checks.BOUNDS, sample=None):
+    """One launch of any instance: check_structure, check_order up to one workgroup, compare_with_reference on every quantity with robust entries taking
+    float64's outcomes exactly, the values under `bounds`. sides: every route in force holds more than 100 robust shadow entries. sample: the entries
+    whose values are compared (a large queue: structure on all of it)."""
     name = "%s/%s" % (setup_name, launch.name)
+    kernel = instance(world, tables, launch)
     n = launch.entries.n
     got = checks.device_launch(world.grt, world.ctx, launch, capacity=n + 37)
     got_at = checks.check_structure(name, tables, launch, got)
     if n <= cases.BLOCK:
         checks.check_order(name, launch, got, *got_at)
+    if sample is not None:
+        launch = launch.sub(sample)
+        got_at = (got_at[0][sample], got_at[1][sample])
+        n = launch.entries.n
     r = ref.evaluate(world, tables, launch, world.bsdf_tables)   # the reference's own inversion: the routes
     far, inversion = np.zeros(n, bool), 0.0
-    if tables.sky_share > 0:
+    if r.to_sky.any():
         directions, pdfs, far, inversion = sky_directions(world, name, tables, launch, got, got_at[1], r)
         r = ref.evaluate(world, tables, launch, world.bsdf_tables, sky_directions=directions, sky_pdfs=pdfs)
     errors = checks.compare_with_reference(name, tables, launch, got, got_at, r, None)   # (outcomes asserted; the values measured, printed, then held)
     left_out = int((r.near | far).sum())
     held = r.robust & ~far & (got_at[1] >= 0)
-    sky, emitter, mapped = int((held & r.to_sky).sum()), int((held & ~r.to_sky).sum()), int((r.mapped & r.robust).sum())
-    print("%-50s %-46s %5d entries, held: %4d sky, %4d emitter shadow entries, %4d mapped hits; %3d left out; inversion %.2g " % (
-        name, instance(world, tables, launch), n, sky, emitter, mapped, left_out, inversion) + " ".join("%s %.2g" % (q, v[0]) for q, v in errors.items()))
+    routes = [int((held & (r.route == k)).sum()) for k in range(4)]
+    sky, emitter, mapped = routes[ref.ROUTE_SKY], routes[ref.ROUTE_POWER] + routes[ref.ROUTE_TREE], int((r.mapped & r.robust).sum())
+    print("%-50s %-46s %5d entries, held: %4d sky, %4d delta, %4d emitter (%s) shadow entries, %4d mapped hits; %3d left out; inversion %.2g " % (
+        name, kernel, n, sky, routes[ref.ROUTE_DELTA], emitter, "tree" if routes[ref.ROUTE_TREE] else "power", mapped, left_out, inversion) + " ".join("%s %.2g" % (q, v[0]) for q, v in errors.items()))
     e, bounce = launch.entries, launch.paths()[2]
     if r.mapped.any() and "normal" in errors:
         # the NORMAL frame by kind of hit: under the existing bound, but for a mapped normal the view guard has moved -- normalising the guard's
@@ -138,12 +138,12 @@ def run(world, setup_name, tables, launch, sides=True, bounds=checks.BOUNDS):
             print("%-50s   NORMAL frame of %s hit: %.3g from float64's (bound %.3g, %d hits)" % (name, label, worst, bound, pick.sum()))
             assert worst <= bound, "%s: the NORMAL frame of %s hit is %.3g from float64's, the bound is %.3g" % (name, label, worst, bound)
     for quantity, (error, i) in errors.items():
-        assert error <= bounds[quantity], "%s: entry %d (pixel %d, bounce %d, %s%s): %s is %.3g from float64's, the bound is %.3g" % (
-            name, i, e.pixel[i], bounce[i], "to the sky" if r.to_sky[i] else "to an emitter", ", mapped" if r.mapped[i] else "", quantity, error, bounds[quantity])
+        assert error <= bounds[quantity], "%s: entry %d (pixel %d, bounce %d, to %s%s): %s is %.3g from float64's, the bound is %.3g" % (
+            name, i, e.pixel[i], bounce[i], ref.ROUTE_NAMES[r.route[i]], ", mapped" if r.mapped[i] else "", quantity, error, bounds[quantity])
     assert left_out <= checks.NON_ROBUST_CAP * n, "%s: %d of %d entries left out" % (name, left_out, n)
     if sides:
-        assert sky > 100 or not tables.sky_share > 0, "%s: %d sky entries held" % (name, sky)
-        assert emitter > 100 or not (tables.lights_total_weight > 0 and tables.sky_share < 1), "%s: %d emitter entries held" % (name, emitter)
+        for route, count in enumerate(routes):
+            assert count > 100 or not ref.route_in_force(tables, route), "%s: %d %s entries held" % (name, count, ref.ROUTE_NAMES[route])
     return got, got_at, r
 
 

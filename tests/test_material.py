@@ -495,3 +495,251 @@ def test_mapped_normal_bound_is_four_times_the_float32_restatement(variant_world
     print("mapped_normal      worst %.3g  (%s)  recorded %.3g  bound %.3g" % (worst[0], worst[1], recorded, checks.BOUNDS["mapped_normal"]))
     assert worst[0] <= recorded * 1.0000001 and recorded <= worst[0] * 1.06 and name == worst[1], "mapped_normal: recorded %.3g (%s), the worst case is %.3g (%s)" % (recorded, name, worst[0], worst[1])
     assert checks.BOUNDS["mapped_normal"] == 4.0 * recorded
+
+
+# ---- every instance of the launch (test_gpu_material_instances.py): the conditions on its launches, from the reference alone ----------
+
+def test_instance_names_are_the_list_of_kernels_shade():
+    """The 96 names material_cases.instance() can form, by the rule, are the entry points kernels_shade.hip defines: the rows of RT_MATERIAL_KERNEL_LIST
+    times the suffixes of RT_MATERIAL_KERNEL_VARIANTS times the two forms, read as text."""
+    import os
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpu-raytracer_amd", "csrc", "kernels_shade.hip")
+    by_rule, listed = cases.all_instances(), cases.listed_instances(path)
+    assert len(by_rule) == 96 and by_rule == listed, sorted(by_rule ^ listed)
+    text = open(path).read()
+    assert "const int variant = (p.normal_map_slots >> material_slot & 1) * 4 + rt_light_split(p);" in text   # (the index the docstrings quote)
+
+
+def routes_held(world, setup_name, tables, launch, sides=True):
+    """The conditions test_gpu_material_variants.run asserts, as far as the reference alone decides them: the left-out share within NON_ROBUST_CAP, the
+    routes a partition of the entries, every route in force holding more than 100 robust shadow entries. Returns the Result and the counts."""
+    name = "%s/%s" % (setup_name, launch.name)
+    r = ref.evaluate(world, tables, launch, world.bsdf_tables)
+    n = launch.entries.n
+    held = r.robust & r.has_shadow
+    routes = [int((held & (r.route == k)).sum()) for k in range(4)]
+    print("%-58s %-46s %5d entries, held: %4d sky, %4d delta, %4d by power, %4d by tree; %4d mapped; %3d next to a threshold" % (
+        name, cases.instance(world, tables, launch), n, *routes, (r.mapped & r.robust).sum(), r.near.sum()))
+    assert r.near.sum() <= checks.NON_ROBUST_CAP * n, "%s: %d of %d entries are next to a threshold" % (name, r.near.sum(), n)
+    in_force = [ref.route_in_force(tables, k) for k in range(4)]
+    assert sum(int((r.route == k).sum()) for k in range(4)) == n and all(in_force[k] or not (r.route == k).any() for k in range(4)), "%s: the routes do not partition the entries" % name
+    assert np.array_equal(r.route == ref.ROUTE_SKY, r.to_sky) and np.array_equal(r.route == ref.ROUTE_DELTA, r.to_delta), name
+    assert not (r.has_shadow & ~np.array(in_force)[r.route]).any(), name
+    # the route says what the shadow ray looks like: to infinity for the sky and for a directional light, finite otherwise
+    endless = np.isposinf(r.shadow_distance[r.has_shadow])
+    directional = np.zeros(n, bool)
+    if r.to_delta.any():
+        directional = r.to_delta & (tables.delta.table.type[np.maximum(r.delta_light, 0)] == 2)
+    assert np.array_equal(endless, (r.to_sky | directional)[r.has_shadow]), name
+    if sides:
+        for k in range(4):
+            assert routes[k] > 100 or not in_force[k], "%s: %d robust %s entries" % (name, routes[k], ref.ROUTE_NAMES[k])
+    return r, routes
+
+
+@pytest.mark.parametrize("case", cases.INSTANCE_CASES, ids=cases.instance_case_id)
+def test_instance_launches_keep_the_conditions(variant_world, case):
+    world = variant_world
+    light, mapped, slot, compressed = case
+    setup = cases.instance_setup(light, compressed)
+    tables = world.apply(setup)
+    assert ref.route_in_force(tables, ref.ROUTE_SKY) == (light != "") and ref.route_in_force(tables, ref.ROUTE_DELTA) == (light in ("_split", "_tree"))
+    assert ref.route_in_force(tables, ref.ROUTE_TREE) == (light == "_tree") and ref.route_in_force(tables, ref.ROUTE_POWER) == (light != "_tree")
+    for maps, launch in cases.instance_launches(world, light, mapped, slot, compressed):
+        world.set_maps(tables, maps)
+        world.textures_compressed = compressed   # (without a device no texture is uploaded: what instance() reads)
+        try:
+            assert cases.instance(world, tables, launch) == cases.instance_name(slot, launch.merged, slot < 2 and not compressed, tuple(cases.LIGHT_VARIANTS).index(light), mapped)
+        finally:
+            world.textures_compressed = False
+        r, routes = routes_held(world, setup.name, tables, launch)
+        assert not mapped or ((r.mapped & r.robust).sum() > 100 and (~r.mapped & r.robust).sum() > 100), launch.name
+        if compressed:
+            # the textured materials' albedo is the BC1 texture; the oracle fetches it from the decoded chain, and no fetch falls below the floor
+            bc1 = tables.materials[:, 3].view(np.int32) == world.bc1_index
+            on_bc1 = bc1[tables.material_ids[launch.entries.mesh]]
+            assert bc1.sum() == 2 and np.array_equal(on_bc1, r.textured) and on_bc1.sum() > 100, launch.name
+            assert min(int(level.min()) for level in world.bc1.levels()) >= 64 and 64 / 255 >= cases.ALBEDO_FLOOR
+            if light == "" and not mapped:
+                out = checks.oracle_launch(tables, launch)
+                checks.check_structure(setup.name + "/" + launch.name, tables, launch, out)
+                px = launch.entries.pixel[on_bc1 & (launch.paths()[2] == 0) & r.alive]
+                albedo = out.aov[checks.ALBEDO][px, :3].view(np.float32)
+                first = (launch.paths()[2] == 0).any()   # (the ALBEDO frame is written at bounce 0)
+                assert (px.size > 50 and np.unique(albedo).size > 50 if first else px.size == 0) and (albedo >= cases.ALBEDO_FLOOR).all() and (albedo <= 1.0).all(), launch.name
+
+
+def test_instance_launches_are_the_shortest_that_hold_every_route(variant_world):
+    """INSTANCE_LENGTHS is the shortest rung, not the shortest queue: the first rung of the ladder (steps of LENGTH_STEP) at which every launch of INSTANCE_CASES holds more than 100 robust entries on every
+    route in force: one rung lower, some launch of each form holds 100 or fewer on some route. (The case above asserts the rung itself.)"""
+    world = variant_world
+    short = [False, False]
+    lower = tuple(n - cases.LENGTH_STEP for n in cases.INSTANCE_LENGTHS)
+    for light, mapped, slot, compressed in cases.INSTANCE_CASES:
+        if all(short):
+            break
+        setup = cases.instance_setup(light, compressed)
+        tables = world.apply(setup)
+        for form, (maps, launch) in enumerate(cases.instance_launches(world, light, mapped, slot, compressed, lengths=lower)):
+            world.set_maps(tables, maps)
+            r = ref.evaluate(world, tables, launch, world.bsdf_tables)
+            held = r.robust & r.has_shadow
+            if any(ref.route_in_force(tables, k) and (held & (r.route == k)).sum() <= 100 for k in range(4)):
+                print("%s/%s: a route holds 100 entries or fewer at %d" % (setup.name, launch.name, launch.entries.n))
+                short[form] = True
+    assert all(short) and cases.INSTANCE_LENGTHS[0] <= 1500 and cases.INSTANCE_LENGTHS[1] <= 2500, short
+
+
+def test_further_instance_launches_keep_the_conditions(variant_world, grt, oracle, tmp_path):
+    """MIS off, the tree with nothing taken, the smooth rows, the queue lengths, the fog launches, and the sampled entries of the merged form's second round."""
+    world = variant_world
+    for light in cases.LIGHT_VARIANTS:
+        index = tuple(cases.LIGHT_VARIANTS).index(light)
+        setup = cases.instance_setup(light, mis_off=True)
+        tables = world.apply(setup); world.set_maps(tables, {})
+        for maps, launch in cases.instance_launches(world, light, False, index, False, tag="instances_mis_off"):
+            routes_held(world, setup.name, tables, launch)
+        setup = cases.instance_setup(light)
+        tables = world.apply(setup); world.set_maps(tables, {})
+        for launch in cases.instance_length_launches(world, index):
+            routes_held(world, setup.name, tables, launch, sides=False)
+    setup = cases.instance_setup("_tree", taken0=True)
+    tables = world.apply(setup); world.set_maps(tables, {})
+    for maps, launch in cases.instance_launches(world, "_tree", False, 0, False, tag="instances_taken0"):
+        r, routes = routes_held(world, setup.name, tables, launch)
+        assert (r.route == ref.ROUTE_TREE).all() and cases.light_split(tables) == 3
+    for light in ("_split", "_tree"):
+        setup = cases.instance_setup(light, smooth=True)
+        tables = world.apply(setup); world.set_maps(tables, {})
+        for slot in (2, 3):
+            for maps, launch in cases.instance_launches(world, light, False, slot, False, tag="instances_smooth"):
+                r, routes = routes_held(world, setup.name, tables, launch, sides=False)
+                assert not r.has_shadow.any() and not r.allow_nee.any() and r.continues.sum() > 100
+    for changes, split in ((dict(), 2), (dict(taken0=True), 0)):
+        setup = cases.instance_setup("_tree", fog=True, **changes)
+        tables = world.apply(setup); world.set_maps(tables, {})
+        assert tables.tree is not None and cases.light_split(tables) == split
+        for launch in cases.fog_launches(world):
+            r, routes = routes_held(world, setup.name, tables, launch)
+            first = launch.paths()[2] == 0
+            assert not (r.route == ref.ROUTE_TREE).any() and first.sum() > 100 and np.isfinite(r.throughput[first & r.continues & ~r.textured]).all()
+    wide = cases.WideWorld(grt, oracle, tmp_path, -1)
+    try:
+        for light, slot in (("", 0), ("_tree", 3)):
+            setup = cases.instance_setup(light)
+            tables = wide.apply(setup); wide.set_maps(tables, {})
+            launch = cases.second_round_merged(wide, slot, seed=6700 + slot)
+            sample = cases.value_sample(launch.entries.n, 6710 + slot)
+            assert launch.entries.n == 8192 * 256 + 1 and np.unique(launch.entries.pixel).size == launch.entries.n and launch.frame_slots <= 512
+            routes_held(wide, setup.name, tables, launch.sub(sample))
+    finally:
+        wide.close()
+
+
+@pytest.mark.parametrize("sky_share", [0.0, 0.5])
+def test_a_delta_share_no_number_reaches_is_the_launch_without_delta_lights(variant_world, sky_share):
+    """The three-way routing of the _split instances against the restatement as it stood before them: with a delta-light share of 1e-30, q = (1 - s) 1e-30
+    is positive and taken = s + q rounds to s, so no random number lies in [s, taken) -- every field of the Result equals, bit for bit, that of the
+    same launch without delta lights (the plain restatement with s = 0, the _sky one with s = 0.5). With `delta` and `tree` None the Result is that of
+    tables which never had the attributes."""
+    import copy
+    import delta_light_reference
+    world = variant_world
+    setup = cases.SETUP["sky_share_0.5" if sky_share else "default"]
+    tables = world.apply(setup); world.set_maps(tables, {})
+    never = copy.copy(tables)
+    for name in ("delta", "tree", "fog_active"):
+        delattr(never, name)
+    unreached = copy.copy(tables)
+    unreached.delta = ref.Delta(delta_light_reference.Table(cases.DELTA_LIGHTS, cases.DELTA_WEIGHTS), 1e-30)
+    for launch in (cases.sky_launches(world, setup) if sky_share else cases.small_launches(world)):
+        a = ref.evaluate(world, never, launch, world.bsdf_tables)
+        for label, other in (("delta and tree None", tables), ("a share no number reaches", unreached)):
+            b = ref.evaluate(world, other, launch, world.bsdf_tables)
+            assert cases.light_split(other) == (2 if other is unreached else 1 if sky_share else 0)
+            for field, value in vars(a).items():
+                if other is unreached and (field == "route" or (field == "u_emitter" and not sky_share)):   # (the plain restatement rescales no number: NaN there, u itself here)
+                    assert field == "route" or np.array_equal(b.u_emitter, tables.random(ref.DIM_NEE_LIGHT, *launch.paths()[1:4])[:, 0])
+                    continue
+                x, y = np.asarray(value), np.asarray(getattr(b, field))
+                assert x.shape == y.shape and x.tobytes() == y.tobytes(), "%s (%s): %s differs" % (launch.name, label, field)
+            assert not b.to_delta.any()
+
+
+# kernel_material_conductor_stream on the MI355X, instances_plain/instances_conductor_merged_1500: the entry furthest from float64's throughput, how far, and
+# the launch's worst direction error (printed by test_gpu_material_instances.py)
+DEVICE_WORST_ENTRY, DEVICE_WORST_THROUGHPUT, DEVICE_DIRECTION_ERROR = 199, 2.32e-3, 9.3e-6
+
+
+def _oracle_on_instance_launches(world, mapped_too=False):
+    """The oracle's plain shade_material on the entries of the unmapped conductor launches of INSTANCE_CASES, under the plain setup (the continuation ray of a hit does not depend on
+    the light variant) against float64: {quantity: (worst error, launch)}."""
+    worst = {}
+    for compressed in (False, True):
+        setup = cases.instance_setup("", compressed)
+        tables = world.apply(setup)
+        tables.map_ids = None
+        for light, mapped, slot, c in cases.INSTANCE_CASES:
+            if c != compressed or slot != 3 or (mapped and not mapped_too):
+                continue
+            for maps, launch in cases.instance_launches(world, light, mapped, slot, compressed):
+                name = "%s/%s" % (cases.instance_setup(light, compressed).name, launch.name)
+                out = checks.oracle_launch(tables, launch)
+                at = checks.check_structure(name, tables, launch, out)
+                errors = checks.compare_with_reference(name, tables, launch, out, at, ref.evaluate(world, tables, launch, world.bsdf_tables), None)
+                for quantity, (error, _) in errors.items():
+                    if error > worst.get(quantity, (0.0, ""))[0]:
+                        worst[quantity] = (error, name)
+    return worst
+
+
+def test_instance_throughput_bound_is_four_times_the_worst_case(variant_world):
+    """The unmapped conductor rows of the instance launches are further queues of VariantWorld's hits, and on one of them the device's throughput leaves
+    BOUNDS["throughput"], which World's launches set: 2.32e-3 against 1.97e-3, kernel_material_conductor_stream, entry 199 of
+    instances_plain/instances_conductor_merged_1500 -- a rough conductor's sample 2.3e-3 above the shading plane (omega_o.z), where G2 / G1 and the
+    Kulla-Conty term change by about 1 / omega_o.z of every change of the direction. That is asserted here, in float64: the BSDF's value / pdf at the
+    sampled direction is the sample's factor (within 1e-4), and moving that direction by DEVICE_DIRECTION_ERROR along the normal -- the device's worst
+    direction error in that launch, 9.3e-6, a fortieth of BOUNDS["direction"] -- moves the factor of that entry by more than the 2.32e-3 seen, while the
+    launch's median entry moves by less than a hundredth of that. So the reference's throughput is ill-conditioned in the direction there, whoever
+    computes it, and the kernel's direction is within its bound. The bound is measured as "variant_throughput" was: the oracle against float64 on the
+    entries of every unmapped conductor launch of INSTANCE_CASES under the plain setup (a hit's continuation ray does not depend on the light variant);
+    material_checks.MEASURED["instance_throughput"] is this run's maximum, and the device's unmapped conductor rows are held to 4 x it (2.8e-3); every
+    other unmapped row keeps BOUNDS, the mapped ones VARIANT_BOUNDS. Every other quantity stays within its bound here too."""
+    import bsdf_reference
+    world = variant_world
+    tables = world.apply(cases.instance_setup(""))
+    world.set_maps(tables, {})
+    launch = cases.instance_launches(world, "", False, 3, False)[1][1]
+    assert launch.name == "instances_conductor_merged_1500"
+    r = ref.evaluate(world, tables, launch, world.bsdf_tables)
+    e = launch.entries
+    slot, real, bounce, sample, submission = launch.paths()
+    materials = tables.materials[tables.material_ids[e.mesh]]
+
+    def factor(direction):   # value / pdf of the BSDF's eval towards `direction`: what its sample multiplies the throughput by
+        probes = ref._probes(materials, r.normal, e.direction.astype(np.float64), r.entering, real, sample, bounce, to_light=direction, cos_o=(direction * r.normal).sum(axis=1))
+        with np.errstate(all="ignore"):
+            x, _ = bsdf_reference.evaluate(bsdf_reference.CONDUCTOR, probes, world.bsdf_tables, eval=True)
+            return x.value / x.pdf[:, None]
+    held = r.continues & r.robust
+    at = factor(r.direction)
+    assert held[DEVICE_WORST_ENTRY] and np.abs(at[held] / r.sample_factor[held] - 1.0).max() <= 1e-4
+    moved = r.direction + DEVICE_DIRECTION_ERROR * r.normal
+    moved /= np.linalg.norm(moved, axis=1)[:, None]
+    change = np.abs(factor(moved)[held] / at[held] - 1.0).max(axis=1)
+    mine = change[np.nonzero(held)[0] == DEVICE_WORST_ENTRY][0]
+    height = (r.direction[DEVICE_WORST_ENTRY] * r.normal[DEVICE_WORST_ENTRY]).sum()
+    print("entry %d: omega_o.z %.3g; a direction error of %.2g moves its throughput by %.3g (the device is %.3g from float64), the launch's median entry by %.3g" % (
+        DEVICE_WORST_ENTRY, height, DEVICE_DIRECTION_ERROR, mine, DEVICE_WORST_THROUGHPUT, np.median(change)))
+    assert 1e-3 < height < 3e-3 and mine > DEVICE_WORST_THROUGHPUT and np.median(change) < 0.01 * DEVICE_WORST_THROUGHPUT
+    assert DEVICE_DIRECTION_ERROR < checks.BOUNDS["direction"] / 30 and checks.BOUNDS["throughput"] < DEVICE_WORST_THROUGHPUT <= checks.BOUNDS["instance_throughput"]
+    worst = _oracle_on_instance_launches(variant_world)
+    for quantity, (error, name) in sorted(worst.items()):
+        print("%-18s worst %.3g  (%s)  bound %.3g" % (quantity, error, name, checks.BOUNDS[quantity]))
+    error, name = worst["throughput"]
+    recorded, launch = checks.MEASURED["instance_throughput"]
+    assert error <= recorded * 1.0000001 and recorded <= error * 1.06 and launch == name, "instance_throughput: recorded %.3g (%s), the worst case is %.3g (%s)" % (recorded, launch, error, name)
+    assert checks.BOUNDS["instance_throughput"] == 4.0 * recorded
+    for quantity, (error, name) in worst.items():
+        if quantity != "throughput":
+            assert error <= checks.BOUNDS[quantity], "%s: the oracle is %.3g from float64 on %s" % (quantity, error, name)

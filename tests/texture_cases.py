@@ -51,6 +51,21 @@ def bc1_texture(w, h, seed):
     return Texture("bc1_%dx%d" % (w, h), w, h, levels, bc1_blocks(bc1_block_count(w, h, levels), rng).reshape(-1), 1)
 
 
+def bc1_texture_above(w, h, seed, floor):
+    """bc1_texture whose every decoded texel is opaque and at least `floor` (a byte) in every channel: both endpoints of a block lie at or above it and
+    c0 > c1 (the four-colour mode, whose two other colours lie between the endpoints; no transparent black)."""
+    rng = np.random.default_rng(seed)
+    levels = full_chain_levels(w, h)
+    count = bc1_block_count(w, h, levels)
+    lo5, lo6 = (floor + 7) // 8, (floor + 3) // 4   # (a 5-bit r expands to at least 8 r, a 6-bit g to at least 4 g)
+    r1 = rng.integers(lo5, 31, count); r0 = rng.integers(r1 + 1, 32)   # c0's red above c1's: c0 > c1 as 16-bit numbers
+    g, b = rng.integers(lo6, 64, (2, count)), rng.integers(lo5, 32, (2, count))
+    c0, c1 = (r0 << 11) | (g[0] << 5) | b[0], (r1 << 11) | (g[1] << 5) | b[1]
+    blocks = rng.integers(0, 256, (count, 8), dtype=np.uint8)   # (the indices: any)
+    blocks[:, 0], blocks[:, 1], blocks[:, 2], blocks[:, 3] = c0 & 255, c0 >> 8, c1 & 255, c1 >> 8
+    return Texture("bc1_above_%dx%d" % (w, h), w, h, levels, blocks.reshape(-1), 1)
+
+
 def rgba8_textures():
     return [rgba8_texture(w, h, 100 + i) for i, (w, h) in enumerate(RGBA8_SIZES)]
 
