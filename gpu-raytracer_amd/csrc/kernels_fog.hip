@@ -1,5 +1,5 @@
 // kernels_fog.hip -- the fog volume's own launches: the attenuation pass of the shadow queue, the probes of the segment step, and the
-// brick table of a density grid. (The scatter events themselves live in the ..._fog and ..._fog_grid instances of the sort kernels, kernels_shade.hip.)
+// brick table of a density grid. (The scatter events themselves live in the ..._fog and ..._fog_grid instances of the sort kernels, kernels_sort.hip.)
 #include "rt_fog_grid.h"
 
 #define RT_FOG_BLOCK 256

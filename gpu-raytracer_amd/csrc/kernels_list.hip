@@ -1,10 +1,9 @@
 // kernels_list.hip -- the generate step of submissions over a pixel list (rt_set_pixel_list). A unit of its own so that the units of the
 // kernels that existed before it keep their code objects to the byte of every instruction (profiles/adaptive_sampling_resources.txt).
+#include "rt_surface.h"   // RT_SHADE_BLOCK
 #include "rt_camera.h"
 
-#define RT_SHADE_BLOCK 256   // as kernels_shade.hip
-
-// kernel_generate_stream of kernels_shade.hip over a pixel list (rt_set_pixel_list): queue entry i of sample s takes pixel list[i] = x + y * screen_width, the third mapping of the domain
+// kernel_generate_stream of kernels_generate.hip over a pixel list (rt_set_pixel_list): queue entry i of sample s takes pixel list[i] = x + y * screen_width, the third mapping of the domain
 // rt_map_pixel maps. The list is in patch order already (64 consecutive entries of an unclipped cell cover an 8 x 8 patch). camera_generate_ray gets what a
 // uniform submission of the same first sample passes for the pixel: its primary ray and all its random numbers are those of uniform rendering.
 __global__ void __launch_bounds__(RT_SHADE_BLOCK) kernel_generate_stream_list(RtParams p, int sample_index, const unsigned * __restrict__ list, int pixel_count, int slot_base, int queue_offset) {

@@ -1,0 +1,5 @@
+// kernels_material_dielectric.hip -- the material kernels of the row `dielectric` of RT_MATERIAL_KERNEL_LIST (rt_material.h): eight variants, two forms.
+// Replaces kernel_material_dielectric of the reference (CUDA/Pathtracer.cu:557-757).
+#define RT_MATERIAL_ROW_dielectric(...) __VA_ARGS__
+#include "rt_material.h"
+RT_MATERIAL_UNIT(dielectric)

@@ -436,7 +436,7 @@ RT_DEV bool triangle_test_loaded(float4 part_0, float4 part_1, float4 part_2, in
 // hit's texture coordinate; a rejected candidate leaves the ray as if the triangle had not been tested (hit untouched, a shadow ray
 // not occluded). The material is the one the hit would be reported with: a copy in the flattened static BLAS stands for the
 // (instance, triangle) named in its position record. (s, t) = uv_0 + u * uv_edge_1 + v * uv_edge_2 of the 96-byte shading triangle
-// (floats 18..23) in float32, the expression of barycentric() in kernels_shade.hip; the texel is the one whose centre
+// (floats 18..23) in float32, the expression of barycentric() in rt_surface.h; the texel is the one whose centre
 // texture_bilinear puts at (x + 1/2) / W. Reached by the few candidates that got this far, so its loads (dependent: alias,
 // material, mask index, mask, texture coordinates, word) stay out of the walk of every other candidate, and it addresses with
 // 64-bit offsets: the 96-byte array is twice as long as the one RtParams::geometry_below_4gib vouches for.

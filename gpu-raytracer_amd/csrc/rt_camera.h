@@ -1,4 +1,4 @@
-// rt_camera.h -- the primary ray of a pixel and sample (CUDA/Camera.h:20-62), for the generate kernels of kernels_shade.hip and kernels_list.hip.
+// rt_camera.h -- the primary ray of a pixel and sample (CUDA/Camera.h:20-62), for the generate kernels of kernels_generate.hip and kernels_list.hip.
 #pragma once
 #include "rt_shading.h"
 

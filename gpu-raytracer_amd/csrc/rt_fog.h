@@ -1,6 +1,6 @@
 // rt_fog.h -- the fog volume: one homogeneous medium inside an axis-aligned box. The device functions of a path segment -- the clip
 // against the box, the hashed pair of random numbers, the distance sample with its weights -- and of the phase function, shared by the ..._fog
-// instances of the sort kernels (kernels_shade.hip), the attenuation pass of the shadow queue and the probe of the segment step (kernels_fog.hip).
+// instances of the sort kernels (kernels_sort.hip), the attenuation pass of the shadow queue and the probe of the segment step (kernels_fog.hip).
 // tests/fog_reference.py restates every function of this file in float64 / integers.
 #pragma once
 #include "rt_shading.h"

@@ -2,7 +2,7 @@
 // force, constant within a voxel; inside voxel v the coefficients are rho_v * sigma_a and rho_v * sigma_s. The homogeneous estimator of rt_fog.h holds
 // unchanged with length replaced by DENSITY LENGTH D(t) = integral of rho ds: the same hashed pair, the same channel choice, the same weights (rho
 // scales sigma_a and sigma_s alike and cancels from the scatter weight). This file is the voxel march that gives D and inverts it, shared by the
-// ..._fog_grid instances of the sort kernels (kernels_shade.hip), the ..._grid attenuation kernels and the probe (kernels_fog.hip).
+// ..._fog_grid instances of the sort kernels (kernels_sort.hip), the ..._grid attenuation kernels and the probe (kernels_fog.hip).
 // tests/fog_density_reference.py restates D and its inversion in float64 by another method (sorted plane crossings, voxels from interval midpoints).
 #pragma once
 #include "rt_fog.h"

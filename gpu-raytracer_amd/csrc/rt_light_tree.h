@@ -1,5 +1,5 @@
 // rt_light_tree.h -- the light tree: what the kernels read of it, and the selection and its pmf as device functions shared by the
-// material and sort kernels (kernels_shade.hip, the ..._tree instances) and the probes (kernels_light_tree.hip: rt_sample_light_tree, rt_light_tree_pmf).
+// material and sort kernels (rt_lights.h and kernels_sort.hip, the ..._tree instances) and the probes (kernels_light_tree.hip: rt_sample_light_tree, rt_light_tree_pmf).
 //
 // The tree: one leaf per (light-mesh entry m, triangle j of its span), id k = leaf_base[m] + j; the leaves sorted along a Morton curve of their box
 // centres (ties by id); an implicit complete binary tree over the sorted order, padded to M = 2^ceil(log2 N) leaves, in heap numbering -- the children of

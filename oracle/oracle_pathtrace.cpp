@@ -604,7 +604,7 @@ inline void add_radiance(Context & c, int bounce, int pixel_index, float3 illumi
 }
 
 // What oracle_sort adds to kernel_sort, and oracle_render_sample never uses: the pixel query (Pathtracer.cu:345-348), and the two places where the
-// device's sort_rays<*, true> (sky importance sampling, no counterpart in the reference) differs -- restated from kernels_shade.hip / rt_shading.h.
+// device's sort_rays<*, true> (sky importance sampling, no counterpart in the reference) differs -- restated from kernels_sort.hip / rt_shading.h.
 struct SortExtras {
 	int pixel_query_pixel; int32_t * pixel_query_out;   // RT_INVALID / null: no query
 	float sky_share; const float * sky_cell_pdf;        // 0: the reference's estimator

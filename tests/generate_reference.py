@@ -1,5 +1,5 @@
 """The first stage of the wavefront restated: which (pixel, sample) every queue entry of a generate launch holds, and that entry's ray in float64.
-numpy only; reads nothing of the product. The layout follows the comments above kernel_generate_stream (kernels_shade.hip) and rt_map_pixel
+numpy only; reads nothing of the product. The layout follows the comments above kernel_generate_stream (kernels_generate.hip) and rt_map_pixel
 (rt_types.h), the ray follows camera_generate_ray (rt_camera.h; CUDA/Camera.h:20-62 of the reference)."""
 import numpy as np
 

@@ -609,7 +609,7 @@ def light_split(tables):
 
 
 def instance(world, tables, launch):
-    """The __global__ entry point material_kernels_for picks for the launch (kernels_shade.hip): the slot's row (the _texels one of the diffuse and
+    """The __global__ entry point material_kernels_for picks for the launch (kernels_material.hip): the slot's row (the _texels one of the diffuse and
     plastic slots while no texture holds compressed blocks), the form, the split in force, the slot's bit of normal_map_slots."""
     map_ids = getattr(tables, "map_ids", None)
     mapped = map_ids is not None and bool((map_ids[tables.material_types == SLOT_TYPES[launch.slot]] >= 0).any())
@@ -627,7 +627,7 @@ def all_instances():
 
 
 def listed_instances(path):
-    """The same set read from kernels_shade.hip as text: the rows of RT_MATERIAL_KERNEL_LIST, the suffixes of RT_MATERIAL_KERNEL_VARIANTS, and
+    """The same set read from rt_material.h as text: the rows of RT_MATERIAL_KERNEL_LIST, the suffixes of RT_MATERIAL_KERNEL_VARIANTS, and
     RT_DEFINE_MATERIAL_KERNELS' two names per pair."""
     import re
     text = open(path).read()

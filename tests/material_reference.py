@@ -1,4 +1,4 @@
-"""numpy float64 restatement of the material launch (kernels_shade.hip: shade_material and the tail of next-event estimation; the reference's
+"""numpy float64 restatement of the material launch (rt_material.h: shade_material, and rt_lights.h: the tail of next-event estimation; the reference's
 shade_material and next_event_estimation, Pathtracer.cu:465-757 as oracle_pathtrace.cpp cites them) on the records of rt_shade_rays, for
 test_material.py (oracle against this) and test_gpu_material.py (device against this). Vectorised over the entries of one launch; float32
 inputs are taken exactly, every operation is float64.
@@ -18,7 +18,7 @@ to this reference in everything but their albedo, throughput and illumination, a
 normal) < 0), omega_i.z <= 0, cos_theta_hit <= 0 and pdf_is_valid(light_pdf) of the light sample, and the BSDF's own branches and
 pdf_is_valid (bsdf_reference.py's replay: `near`). An entry is non-robust when one of them is within its margin.
 
-The variants of the launch (kernels_shade.hip: the _sky and _nmap instances), composed from the modules that restate their parts:
+The variants of the launch (rt_material.h: the _sky and _nmap instances), composed from the modules that restate their parts:
 * a sky share s = tables.sky_share > 0 (next_event_estimation<1>): each allowed entry is routed in float32 as the kernel routes it -- to the
   sky where DIM_NEE_LIGHT.x < s, else to the emitters on the rescaled number min((u - s) / (1 - s), 0x1.fffffep-1), whose light pdf carries
   the factor 1 - s into pdf_is_valid and into the MIS weight. A sky entry takes its direction and cell pdf from the DIM_NEE_TRIANGLE pair
@@ -254,7 +254,7 @@ def evaluate(world, tables, launch, bsdf_tables, sky_directions=None, sky_pdfs=N
         r.cone_width, r.cone_angle = width, angle_in - term
         r.cone_angle_scale = np.abs(angle_in) + np.abs(term) * (1.0 + 1.0 / np.abs(_dot(interpolated, d)))
 
-        # g-buffers (SVGF.cu as kernels_shade.hip: svgf_set_gbuffers)
+        # g-buffers (SVGF.cu as rt_surface.h: svgf_set_gbuffers)
         prev_m = tables.transforms_prev[e.mesh].astype(f64)
         position_prev = _rows(prev_m, local) + prev_m[:, :, 3]
         one = np.ones((n, 1))

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-LIGHT_MESHES_IN_LDS, LIGHT_TRIANGLES_IN_LDS = 64, 2048   # RT_LIGHT_MESHES_IN_LDS, RT_LIGHT_TRIANGLES_IN_LDS (kernels_shade.hip)
+LIGHT_MESHES_IN_LDS, LIGHT_TRIANGLES_IN_LDS = 64, 2048   # RT_LIGHT_MESHES_IN_LDS, RT_LIGHT_TRIANGLES_IN_LDS (rt_lights.h)
 ONE_BELOW_ONE = np.float32(np.nextafter(np.float32(1), np.float32(0)))   # 0x1.fffffep-1
 
 HEAD = ('<scene version="0.5.0"><integrator type="path"><integer name="maxDepth" value="4"/></integrator>'

@@ -1,5 +1,5 @@
 """Float64 numpy restatement of the shade kernels' light selection (sample_light, sample_triangle, nee_pick_light of
-kernels_shade.hip; Sampling.h:180-190 and Pathtracer.cu:472-493 of the reference), and the exact selection probabilities.
+rt_lights.h; Sampling.h:180-190 and Pathtracer.cu:472-493 of the reference), and the exact selection probabilities.
 
 The table search is `searchsorted(..., side="left")` within the span: the first entry >= u, which is what `binary_search`
 returns whenever it returns (it returns `middle` only if u <= cdf[middle] and, unless middle is the span's first entry,

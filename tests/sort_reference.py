@@ -1,4 +1,4 @@
-"""numpy float64 restatement of the sort launch (kernels_shade.hip: sort_rays; the reference's kernel_sort, Pathtracer.cu:199-463 as
+"""numpy float64 restatement of the sort launch (kernels_sort.hip: sort_rays; the reference's kernel_sort, Pathtracer.cu:199-463 as
 oracle_pathtrace.cpp cites it) on the records of rt_sort_rays, for test_sort.py (oracle against this) and test_gpu_sort.py (device
 against this). Vectorised over the entries of one launch; float32 inputs are taken exactly, every operation is float64.
 

@@ -47,7 +47,7 @@ def timed(request):
 
 
 def instance(world, tables, launch):
-    """The __global__ entry point rt_launch_material / rt_launch_material_stream picks for the launch (kernels_shade.hip)."""
+    """The __global__ entry point rt_launch_material / rt_launch_material_stream picks for the launch (kernels_material.hip)."""
     name = "kernel_material_" + cases.SLOT_NAMES[launch.slot] + ("_stream" if launch.merged else "")
     if launch.slot < 2 and not world.textures_compressed:
         name += "_texels"

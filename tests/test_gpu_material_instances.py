@@ -1,4 +1,4 @@
-"""Every instance of the material launch on the device, entry by entry: the 96 entry points kernels_shade.hip compiles from shade_material -- 6 rows
+"""Every instance of the material launch on the device, entry by entry: the 96 entry points the kernels_material_*.hip units compile from shade_material (rt_material.h) -- 6 rows
 (diffuse, plastic, dielectric, conductor, and the _texels forms of the first two) x 8 variants (the light split: plain, _sky, _split, _tree; with and
 without _nmap) x 2 forms (per-bounce, _stream) -- each picked by material_kernels_for ([(NMAP * 4 + SKY) * rows + row]) from the context's settings,
 run by rt_shade_rays on the launches of material_cases.py (VariantWorld) and held to the float64 composition of material_reference.py with the runner
@@ -220,7 +220,7 @@ def test_launch_under_a_fog_volume(world, shares):
 
 
 def test_every_instance_was_launched():
-    """The union of instance() over the launches this module ran is the list of kernels_shade.hip, all 96 (test_material.py holds that list to the text)."""
+    """The union of instance() over the launches this module ran is the list of rt_material.h, all 96 (test_material.py holds that list to the text)."""
     if len(CASES_DONE) < len(EVERY_CASE):
         pytest.skip("counts the launches of test_every_instance: run the whole module (%d of %d cases ran)" % (len(CASES_DONE), len(EVERY_CASE)))
     every = cases.all_instances()

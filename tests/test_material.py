@@ -499,14 +499,14 @@ def test_mapped_normal_bound_is_four_times_the_float32_restatement(variant_world
 
 # ---- every instance of the launch (test_gpu_material_instances.py): the conditions on its launches, from the reference alone ----------
 
-def test_instance_names_are_the_list_of_kernels_shade():
-    """The 96 names material_cases.instance() can form, by the rule, are the entry points kernels_shade.hip defines: the rows of RT_MATERIAL_KERNEL_LIST
-    times the suffixes of RT_MATERIAL_KERNEL_VARIANTS times the two forms, read as text."""
+def test_instance_names_are_the_list_of_rt_material():
+    """The 96 names material_cases.instance() can form, by the rule, are the entry points the slots' units define from rt_material.h: the rows of
+    RT_MATERIAL_KERNEL_LIST times the suffixes of RT_MATERIAL_KERNEL_VARIANTS times the two forms, read as text. The selector is kernels_material.hip's."""
     import os
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpu-raytracer_amd", "csrc", "kernels_shade.hip")
-    by_rule, listed = cases.all_instances(), cases.listed_instances(path)
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpu-raytracer_amd", "csrc")
+    by_rule, listed = cases.all_instances(), cases.listed_instances(os.path.join(csrc, "rt_material.h"))
     assert len(by_rule) == 96 and by_rule == listed, sorted(by_rule ^ listed)
-    text = open(path).read()
+    text = open(os.path.join(csrc, "kernels_material.hip")).read()
     assert "const int variant = (p.normal_map_slots >> material_slot & 1) * 4 + rt_light_split(p);" in text   # (the index the docstrings quote)
 
 

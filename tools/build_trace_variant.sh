@@ -12,8 +12,7 @@ OBJS=""
 for src in csrc/*.hip; do
   base=$(basename $src .hip)
   if echo " $FILES " | grep -q " $base.hip "; then
-    PERFILE=""; case $base in kernels_shade|kernels_post) PERFILE="-fno-slp-vectorize";; esac   # (the Makefile's HIPFLAGS_<unit>)
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function -I../include $PERFILE $FLAGS -c -o csrc/_variants/$NAME/$base.o $src
+    $(make -s print-compile-$base) $FLAGS -c -o csrc/_variants/$NAME/$base.o $src   # (the Makefile's compile line of the unit)
     OBJS="$OBJS csrc/_variants/$NAME/$base.o"
   else
     OBJS="$OBJS csrc/$base.o"

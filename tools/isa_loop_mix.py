@@ -49,10 +49,11 @@ def classify(op):
 
 def compile_unit(unit, flags):
     out = "/tmp/isa_loop_mix_%s.s" % unit
-    per_file = ["-fno-slp-vectorize"] if unit in ("kernels_shade", "kernels_post") else []   # the Makefile's HIPFLAGS_<unit>
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-I" + os.path.join(ROOT, "include"),
-           "--cuda-device-only", "-S", "-o", out, os.path.join(ROOT, "gpu-raytracer_amd", "csrc", unit + ".hip")] + per_file + flags.split()
-    subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
+    make_dir = os.path.join(ROOT, "gpu-raytracer_amd")
+    # the unit's compile line is the Makefile's (compiler, common flags, the unit's own), run from the Makefile's directory
+    line = subprocess.run(["make", "-s", "print-compile-" + unit], cwd=make_dir, check=True, capture_output=True, text=True).stdout.split()
+    cmd = line + ["--cuda-device-only", "-S", "-o", out, os.path.join("csrc", unit + ".hip")] + flags.split()
+    subprocess.run(cmd, cwd=make_dir, check=True, stderr=subprocess.DEVNULL)
     return out
 
 
